@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- trees-fit/sec (+ predict rows/sec) of the MI355X-native GBRL hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Timed workload (BASELINE.json configs[1], the configuration the metric is quoted on): oblivious tree, L2 split score, quantile
@@ -11,7 +11,9 @@ HBM).  One "step" = one GBRL.step() = one tree fitted on the whole batch.  With 
 (weak scaling: 2^20 rows per GPU, the SAME tree is grown on every rank from all-reduced integer histograms), and `value`
 counts 2^20-row batches: value = steps * n_gpus / seconds.  `python bench.py --gpus N` without a launcher starts its own N ranks.
 
-Printed JSON (rank 0, one line): the driver contract + "roofline" for the dominant kernel (split-score histogram build,
+Printed JSON (rank 0, one line).  A plain run sets up, warms up, times the K steps and prints the driver contract (metric, value,
+unit, ms_per_step, dtype, ...) and the configuration; --dump-outputs DIR also writes the tree the last timed step grew as DIR/<name>.npy.
+Everything else is measured with --full only: the driver contract + "roofline" for the dominant kernel (split-score histogram build,
 HBM-bound, algorithmic bytes from SURVEY.md 8(d)) + "cpu_baseline" (the reference's own CPU path if oracle/_ref is
 loadable, else this repo's restatement) on a bounded sample + predict throughput with its own roofline ("predict",
 "predict_large_ensemble") + two further single-GPU legs measured after the timed region: "cfg3" (BASELINE configs[2]: greedy /
@@ -676,6 +678,22 @@ def leg_cfg5(torch, np, gbrl_amd, dev, D, depth, B, trees, N=1 << 20, F=192, Fc=
     return out
 
 
+def dump_outputs(np, m, out_dir):
+    """--dump-outputs: the tree the last timed step added to the ensemble, as a caller reads it back (get_ensemble_data), one
+    DIR/<name>.npy per array in float32 (values, thresholds, edge weights) or float64 (exact integer / flag arrays).  Per-tree arrays keep
+    the last tree's row, per-leaf arrays the rows of its leaves."""
+    e = m.get_ensemble_data()
+    offsets = np.asarray(e["tree_indices"])
+    n_trees, n_leaves = len(offsets), int(np.asarray(e["values"]).shape[0])
+    first_leaf = int(offsets[-1])
+    os.makedirs(out_dir, exist_ok=True)
+    for k in ("depths", "feature_indices", "feature_values", "is_numerics", "inequality_directions", "edge_weights", "values"):
+        a = np.asarray(e[k])
+        a = a[first_leaf:] if a.shape[0] == n_leaves and n_leaves != n_trees else a[-1:]
+        a = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -689,7 +707,7 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-rows", type=int, default=0, help="0: grow the CPU sample while the leg stays within ~20 s on this host")
     ap.add_argument("--cpu-full-tree", action="store_true",
-                    help="opt-in (minutes of CPU time): ALSO time ONE tree of the reference's CPU path at the full batch (2^20 x 128 on this host's cores, "
+                    help="opt-in with --full (minutes of CPU time): ALSO time ONE tree of the reference's CPU path at the full batch (2^20 x 128 on this host's cores, "
                          "SURVEY 8d) and report it as cpu_baseline.full_tree -- no extrapolation")
     ap.add_argument("--force-collective", action="store_true",
                     help="diagnostic: run the row-sharded code path (collective hooks through RCCL) on ONE GPU")
@@ -705,6 +723,12 @@ def main():
                     help="test hook (one process): the rows of K ranks (their seeds, concatenated in rank order) as ONE unsharded batch -- the "
                          "single-process twin of `--gpus K` for tree-equality checks")
     ap.add_argument("--dump-ensemble", default=None, help="test hook: rank 0 writes the grown ensemble's structure arrays to this .npz")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the tree grown by the last timed step to DIR/<name>.npy (float32 / float64) after the timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: diagnostic phase pass, roofline, predict throughput, the large "
+                         "ensemble, the extra legs (collective, cfg3, predict_depth8, predict_cfg5, cfg1, full_size_parity) and the CPU "
+                         "baselines.  Without it a run only sets up, warms up, times the steps and prints the result line")
     ap.add_argument("--large-ensemble", type=int, default=1000,
                     help="also time predict() over an ensemble of this many trees (the row-trees/s rate is flat from ~100 trees on; "
                          "BASELINE configs[4] has 10000).  The extra trees are grown after the timed region with the same "
@@ -828,6 +852,35 @@ def main():
         e = m.get_ensemble_data()
         np.savez(args.dump_ensemble, **{k: np.asarray(e[k]) for k in ("tree_indices", "depths", "feature_indices", "feature_values",
                                                                     "inequality_directions", "edge_weights", "values")})
+    if args.dump_outputs and rank == 0:
+        dump_outputs(np, m, args.dump_outputs)
+
+    steps = args.steps
+    ms_per_step = dt / steps * 1e3
+    try:
+        build_info = json.load(open(os.path.join(ROOT, "gbrl_amd", "build_info.json")))
+    except Exception:
+        build_info = None
+    head = {
+        "build": build_info,
+        "metric": "trees-fit/sec + predict rows/sec at batch=2^20, feat=128, depth=6, out=8",
+        "value": steps * world * (N / float(1 << 20)) / dt,
+        "unit": "trees/s (2^20-row batches fitted per second; one tree per batch per step)",
+        "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32 fixed-point sums / f32 scores",
+        "data": "synthetic",
+        "config": {"workload": ("BASELINE configs[1]: oblivious tree, L2 score, quantile candidates" if args.workload == "cfg2" else
+                                "BASELINE configs[2]: greedy tree, Cosine score, quantile candidates, policy + value optimisers"), "rows_per_gpu": N,
+                   "n_features": F, "output_dim": D, "max_depth": depth, "n_bins": B, "sharding": "rows x%d" % world + (" (collective path forced)" if args.force_collective else ""), "exchange": exchange},
+    }
+    if not args.full:   # a plain run: the headline figure only
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.barrier()
+        if world > 1 or args.force_collective:
+            dist.destroy_process_group()
+        return
 
     # diagnostic pass (untimed): every phase bracketed with events
     m.set_profiling(2)
@@ -929,8 +982,6 @@ def main():
             extra["full_size_parity"] = {"error": repr(e)}
 
     if rank == 0:
-        steps = args.steps
-        ms_per_step = dt / steps * 1e3
         # live, inside the timed region: at profiling level 1 the engine attaches the event pair to one k_hist_build launch in seven (every
         # tree level in turn; a pair on every launch cost 1.8 % of the step), so the per-tree time is depth x the mean sampled launch
         n_samp = phase_acc.get("hist_build_sampled_launches", 0.0)
@@ -954,21 +1005,8 @@ def main():
                 traffic_src = "profiles/hist_traffic.json = the builder's rocprofv3 PMC passes (%s; %s, taken %s)" % (tj.get("method", "2*FETCH_SIZE + WRITE_SIZE"), tj.get("commit", "?"), tj.get("taken", "?"))
             except Exception:
                 traffic = None
-        try:
-            build_info = json.load(open(os.path.join(ROOT, "gbrl_amd", "build_info.json")))
-        except Exception:
-            build_info = None
-        out = {
-            "build": build_info,
-            "metric": "trees-fit/sec + predict rows/sec at batch=2^20, feat=128, depth=6, out=8",
-            "value": steps * world * (N / float(1 << 20)) / dt,
-            "unit": "trees/s (2^20-row batches fitted per second; one tree per batch per step)",
-            "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32 fixed-point sums / f32 scores",
-            "data": "synthetic",
-            "config": {"workload": ("BASELINE configs[1]: oblivious tree, L2 score, quantile candidates" if args.workload == "cfg2" else
-                                    "BASELINE configs[2]: greedy tree, Cosine score, quantile candidates, policy + value optimisers"), "rows_per_gpu": N,
-                       "n_features": F, "output_dim": D, "max_depth": depth, "n_bins": B, "sharding": "rows x%d" % world + (" (collective path forced)" if args.force_collective else ""), "exchange": exchange},
+        out = dict(head)
+        out.update({
             "predict": {"rows_per_s": world * N / dtp, "trees": n_trees, "ms_per_call": dtp * 1e3, "kernel_ms": pk,
                         "row_trees_per_s": world * N * n_trees / dtp, "roofline": predict_roofline(N, F, D, n_trees, depth, dtp)},
             "predict_large_ensemble": large,
@@ -991,7 +1029,7 @@ def main():
                          "hist_build_plus_reduce_ms_per_tree": hist_ms,
                          "frac_including_reduce": (alg / (hist_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if hist_ms > 0 else 0.0,
                          "note": "LDS-atomic-issue bound in practice: 9 ds_add_u32 per (row, feature), 8 at the root; see DESIGN.md section 5"},
-        }
+        })
         if not args.no_cpu_baseline and world == 1:   # reported at N=1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(F, D, depth, B, 1 << 20, args.cpu_sample_rows)

@@ -1,6 +1,7 @@
 """CPU-only sweep (authoring container or GPU box): the oracle RESTATEMENT (oracle/oracle.cpp) against the REAL reference build
 (oracle/_ref) on random cases, including regimes no committed fixture covers (many outputs, many bins, weights with zeros, many
-categorical columns).  Structure must be bit-identical or an explained near-tie; values / predictions within 1e-5.
+categorical columns).  Structure must be bit-identical or an explained near-tie; values / predictions within 1e-5.  Without oracle/_ref
+the reference's trees are read from tests/golden/ref_recordings.npz (recorded for the arguments tests/test_oracle.py uses).
     OMP_NUM_THREADS=8 python scripts/oracle_vs_ref_sweep.py [n_cases] [first_seed]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,11 +10,9 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden
 import numpy as np
 import cases as K
 import neartie
-from helpers import assert_structure_equal, assert_values_close, rel_err
+from helpers import assert_structure_equal, assert_values_close, ref_arrays, rel_err
 import oracle
 
-ref = oracle.load_ref()
-assert ref is not None
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 100
 rng = np.random.default_rng(seed0)
@@ -33,8 +32,12 @@ for i in range(n_cases):
         if max(case["feature_weights"]) == 0.0: case["feature_weights"][0] = 1.0
     X, Xc, G, y = K.make_inputs(case)
     o = oracle.OracleGBRL(**K.ctor_kwargs(case)); po = np.asarray(K.drive(o, case, X, Xc, G, y))
-    r = ref.GBRL(**K.ctor_kwargs(case)); pr = np.asarray(K.drive(r, case, X, Xc, G, y))
-    eo, er = o.get_ensemble_data(), r.get_ensemble_data()
+    def reference(ref):
+        r = ref.GBRL(**K.ctor_kwargs(case)); pr = np.asarray(K.drive(r, case, X, Xc, G, y))
+        return dict(r.get_ensemble_data(), pred=pr)
+    er = ref_arrays("ovr_%d_%d" % (seed0, i), reference)
+    pr = er.pop("pred")
+    eo = o.get_ensemble_data()
     scale = float(np.abs(G).mean())
     try:
         assert_structure_equal(eo, er); assert_values_close(eo, er, scale, 1e-5); assert rel_err(po, pr, scale) <= 1e-5

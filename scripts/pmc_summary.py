@@ -29,7 +29,7 @@ for d, ctr in ((fetch_dir, "FETCH_SIZE"), (write_dir, "WRITE_SIZE")):
     cur = sqlite3.connect(db).cursor()
     for k, v, c in cur.execute("select kernel_name, sum(value), count(*) from counters_collection where counter_name=? group by kernel_name", (ctr,)):
         res.setdefault(short(k), {})[ctr] = (v, c)
-lines = ["# " + STAMP, "# per-kernel HBM-side traffic, rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate runs of: python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline)",
+lines = ["# " + STAMP, "# per-kernel HBM-side traffic, rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate runs of: python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline)",
          "# corrected = 2*FETCH_SIZE + WRITE_SIZE (gfx950: FETCH_SIZE counts 128-B requests at 64 B; calibrated on k_transpose_keys / k_bin_cols, see scripts/pmc_summary.py)",
          "%-48s %6s %16s %16s %18s" % ("kernel", "calls", "FETCH_KiB/call", "WRITE_KiB/call", "corrected_MB/call")]
 summary = {}

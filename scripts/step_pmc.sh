@@ -5,7 +5,7 @@
 set -u
 R="$GRAFT_REPO_ROOT"; W=/tmp/gbrl_step_pmc; rm -rf "$W"; mkdir -p "$W" "$(dirname "$R/$1")"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-extra-legs --steps 6 --warmup 2 --large-ensemble 32"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-extra-legs --steps 6 --warmup 2 --large-ensemble 32"
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_BUSY_CYCLES -d "$W/a" -o a -- $B > /dev/null 2>&1
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_LDS_BANK_CONFLICT -d "$W/b" -o b -- $B > /dev/null 2>&1
 rocprofv3 --kernel-trace --stats -d "$W/t" -o t -- $B > /dev/null 2>&1

@@ -2,7 +2,7 @@
 idle gap in front of it, averaged over the last steps of the run; plus busy time (union of the dispatch intervals) against the step's
 span.  Steps are cut at the first dispatch of `marker` (default k_transpose_count: one per step at the bench shape).
     python3 scripts/step_timeline.py <rocprof-output-dir> out.txt [marker] [n_last_steps]
-Run on the GPU box after  rocprofv3 --kernel-trace -d DIR -o t -- python3 bench.py --no-cpu-baseline --no-extra-legs --steps 20 --warmup 5"""
+Run on an MI355X after  rocprofv3 --kernel-trace -d DIR -o t -- python3 bench.py --full --no-cpu-baseline --no-extra-legs --steps 20 --warmup 5"""
 import glob, os, re, sqlite3, sys
 
 src, dst = sys.argv[1], sys.argv[2]

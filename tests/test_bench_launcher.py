@@ -63,7 +63,7 @@ def test_the_launch_has_a_wall_clock_limit():
 def test_two_ranks_on_one_gpu_report_n_gpus_2():
     """The real N=2 bench path on a single-GPU box: both ranks on cuda:0, reductions staged through gloo (numbers meaningless)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--rows", "16384",
-                          "--features", "16", "--no-cpu-baseline", "--large-ensemble", "0"],
+                          "--features", "16", "--no-cpu-baseline", "--large-ensemble", "0", "--full"],
                          env=_clean_env(BENCH_SHARE_DEVICE="1"), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     lines = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
@@ -100,9 +100,9 @@ def test_two_ranks_grow_the_trees_of_one_process_on_the_same_rows(tmp_path):
 @pytest.mark.gpu
 def test_the_bench_line_keeps_its_contract():
     """One JSON line with the driver's keys, the `roofline` object of the dominant kernel and the `cpu_baseline` object (kind "reference" or
-    "port", cores, sample), at a reduced shape so that the test takes seconds (the numbers are not the headline's)."""
+    "port", cores, sample) under --full, at a reduced shape so that the test takes seconds (the numbers are not the headline's)."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--rows", "131072", "--features", "32",
-                          "--no-extra-legs", "--large-ensemble", "0", "--cpu-sample-rows", "4096"],
+                          "--no-extra-legs", "--large-ensemble", "0", "--cpu-sample-rows", "4096", "--full"],
                          env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -121,3 +121,29 @@ def test_the_bench_line_keeps_its_contract():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in c, k
     assert c["kind"] in ("reference", "port") and c["cores"] >= 1 and c["value"] > 0
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_and_dumps_the_last_tree(tmp_path):
+    """Without --full the run only times its steps: one JSON line with the driver's keys and none of the --full figures.  --dump-outputs
+    writes the tree of the last timed step as float32 / float64 .npy files, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--rows", "131072", "--features", "32",
+                              "--dump-outputs", str(d)], env=_clean_env(), capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, "exactly ONE json line on stdout"
+        r = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+            assert k in r, k
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["higher_is_better"] is True
+        assert abs(r["value"] - 3 * (131072 / float(1 << 20)) / (r["ms_per_step"] * 3e-3)) <= 1e-6 * r["value"]
+        assert not {"roofline", "cpu_baseline", "predict", "cfg3"} & set(r), sorted(r)
+    files = sorted(os.listdir(dirs[0]))
+    assert "values.npy" in files and "feature_values.npy" in files and files == sorted(os.listdir(dirs[1]))
+    for f in files:
+        a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and np.array_equal(a, b), f
+    assert np.load(dirs[0] / "values.npy").shape == (64, 8) and np.load(dirs[0] / "feature_values.npy").shape == (1, 6)

@@ -10,7 +10,7 @@ import pytest
 
 import cases as K
 import gbrl_amd
-from helpers import load_golden
+from helpers import load_golden, ref_arrays
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -102,29 +102,35 @@ def test_model_file_of_a_fresh_model_is_the_file_the_reference_writes(tmp_path):
     assert m.save(str(p)) == 0
     ours = p.read_bytes()
     assert ours[24 + 80] == 1 and ours[24 + 81] == 0          # parallel_predict, use_cv
-    ref = oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
-    r = ref.GBRL(**kw)
-    r.set_optimizer(algo="SGD", scheduler="Const", init_lr=0.1, start_idx=0, stop_idx=1)
-    r.set_optimizer(algo="SGD", scheduler="Const", init_lr=0.01, start_idx=1, stop_idx=2)
-    q = tmp_path / "fresh_ref.gbrl_model"
-    assert r.save(str(q)) == 0
-    assert _mask_header_padding(ours) == _mask_header_padding(q.read_bytes())
+
+    def reference(ref):
+        r = ref.GBRL(**kw)
+        r.set_optimizer(algo="SGD", scheduler="Const", init_lr=0.1, start_idx=0, stop_idx=1)
+        r.set_optimizer(algo="SGD", scheduler="Const", init_lr=0.01, start_idx=1, stop_idx=2)
+        q = tmp_path / "fresh_ref.gbrl_model"
+        assert r.save(str(q)) == 0
+        return {"model_file": np.frombuffer(q.read_bytes(), np.uint8)}
+    theirs = ref_arrays("fresh_model_file", reference)["model_file"].tobytes()
+    assert _mask_header_padding(ours) == _mask_header_padding(theirs)
 
 
 def test_model_file_written_here_loads_in_the_reference(tmp_path):
+    """The reference loads the file written here (live), or -- recorded from the reference build -- the file written here is the file
+    the reference loaded then, byte for byte, and it read the golden ensemble from it."""
     import oracle
-    ref = oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built")
     case, g, _ = load_golden("grd_cos_q_ac")
     p = tmp_path / "a.gbrl_model"
     p.write_bytes(g["model_file"].tobytes())
     q = tmp_path / "b.gbrl_model"
     gbrl_amd.GBRL.load(str(p)).save(str(q))
-    r = ref.GBRL.load(str(q))
-    er = r.get_ensemble_data()
+    ours = q.read_bytes()
+
+    def reference(ref):
+        er = ref.GBRL.load(str(q)).get_ensemble_data()
+        return dict({k: er[k] for k in K.ENSEMBLE_KEYS}, model_file=np.frombuffer(ours, np.uint8))
+    er = ref_arrays("model_file_loaded_by_the_reference", reference)
+    if oracle.load_ref() is None:
+        assert _mask_header_padding(ours) == _mask_header_padding(er["model_file"].tobytes())
     for k in K.ENSEMBLE_KEYS:
         assert np.array_equal(np.asarray(er[k]), g[k]), k
 
@@ -210,10 +216,6 @@ def test_product_does_not_touch_the_oracle():
 def test_python_signatures_match_the_reference_class():
     """Every public method of the reference's gbrl_cpp.GBRL exists here with the same argument names, order, defaults and annotated
     types (pybind11 writes them into the docstrings); only additions are allowed."""
-    import oracle
-    ref_mod = oracle.load_ref()
-    if ref_mod is None:
-        pytest.skip("oracle/_ref not built")
 
     def signatures(cls):
         out = {}
@@ -225,7 +227,9 @@ def test_python_signatures_match_the_reference_class():
             out[n] = [re.sub(r"gbrl_cpp(_ref)?\.GBRL", "GBRL", re.sub(r"^\s*\d+\.\s*", "", ln)).strip() for ln in lines]
         return out
 
-    ref, mine = signatures(ref_mod.GBRL), signatures(gbrl_amd.GBRL)
+    import json
+    recorded = ref_arrays("gbrl_signatures", lambda ref_mod: {"json": np.array(json.dumps(signatures(ref_mod.GBRL), sort_keys=True))})
+    ref, mine = json.loads(str(recorded["json"])), signatures(gbrl_amd.GBRL)
     assert not set(ref) - set(mine), sorted(set(ref) - set(mine))
     for name, sig in ref.items():
         if name == "get_feature_mapping":       # same call, the return annotation here is more specific

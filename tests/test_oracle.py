@@ -1,6 +1,6 @@
 """Pins the oracle: the restatement (oracle/oracle.cpp) must reproduce, bit for bit, the golden vectors that the
-reference's own CPU path produced (tests/golden/make_golden.py), and -- when the reference build oracle/_ref is
-present -- the reference itself on fresh seeds."""
+reference's own CPU path produced (tests/golden/make_golden.py), and the reference itself on fresh seeds -- live when the
+reference build oracle/_ref is present, else as recorded from it (tests/golden/ref_recordings.npz)."""
 import os
 
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 
 import cases as K
 import oracle
-from helpers import STRUCTURE_KEYS, VALUE_KEYS, load_golden
+from helpers import STRUCTURE_KEYS, VALUE_KEYS, RefScalars, load_golden, ref_arrays
 
 
 @pytest.mark.parametrize("name", [c["name"] for c in K.CASES])
@@ -27,20 +27,22 @@ def test_restatement_matches_golden_bit_exact(name):
 @pytest.mark.parametrize("policy,score,gen", [("oblivious", "L2", "Quantile"), ("greedy", "Cosine", "Uniform"),
                                               ("greedy", "L2", "Quantile"), ("oblivious", "Cosine", "Quantile")])
 def test_restatement_matches_reference_build_live(seed, policy, score, gen):
-    ref = oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
     case = dict(name="live", seed=seed, N=900, F=5, Fc=1, D=2, depth=3, n_bins=64, score=score, gen=gen,
                 policy=policy, trees=2)
     X, Xc, G, y = K.make_inputs(case)
-    a = ref.GBRL(**K.ctor_kwargs(case))
-    pa = K.drive(a, case, X, Xc, G, y)
+
+    def reference(ref):
+        a = ref.GBRL(**K.ctor_kwargs(case))
+        pa = K.drive(a, case, X, Xc, G, y)
+        ea = a.get_ensemble_data()
+        return dict({k: ea[k] for k in STRUCTURE_KEYS + VALUE_KEYS}, pred=pa)
+    ea = ref_arrays("live_%d_%s_%s_%s" % (seed, policy, score, gen), reference)
     b = oracle.OracleGBRL(**K.ctor_kwargs(case))
     pb = K.drive(b, case, X, Xc, G, y)
-    ea, eb = a.get_ensemble_data(), b.get_ensemble_data()
+    eb = b.get_ensemble_data()
     for k in STRUCTURE_KEYS + VALUE_KEYS:
         assert np.array_equal(np.asarray(ea[k]), eb[k]), k
-    assert np.array_equal(np.asarray(pa), pb)
+    assert np.array_equal(np.asarray(ea["pred"]), pb)
 
 
 def test_quantile_thresholds_are_order_statistics():
@@ -77,12 +79,10 @@ def test_uniform_thresholds_are_fused_multiply_add():
 def test_restatement_agrees_with_the_reference_build_beyond_the_fixtures():
     """scripts/oracle_vs_ref_sweep.py in miniature: the restatement against the REAL reference build on random cases from regimes no
     committed fixture covers (13-33 outputs, 500 bins, feature weights with zeros, many categorical columns).  150 cases were run when
-    the script was written: 149 bit-identical, 1 explained near-tie."""
+    the script was written: 149 bit-identical, 1 explained near-tie.  Without oracle/_ref the script reads the reference's trees from the
+    recording."""
     import subprocess
     import sys
-    import oracle
-    if oracle.load_ref() is None:
-        pytest.skip("oracle/_ref not built")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "scripts", "oracle_vs_ref_sweep.py"), "16", "977"], capture_output=True, text=True,
                          timeout=900, env=dict(os.environ, OMP_NUM_THREADS="8"))
@@ -134,24 +134,23 @@ def test_replay_sequence_is_the_reference_functions_bit_for_bit(cosine):
     """oracle/replay_sequence.cpp (explicit fmaf / rounded products, built without contraction) against TreeNode::splitScoreCosine /
     splitScoreL2 and scoreCosine / scoreL2 of the reference build on random nodes: every output width 1..130, nodes of 0..600 rows,
     gradient scales over six decades.  This pins the operation sequence the product's near-tie replay implements."""
-    if oracle.ref_score_probe() is None:
-        pytest.skip("oracle/_ref/ref_score_probe.so not built (needs /root/reference)")
     rng = np.random.default_rng(5 if cosine else 6)
+    ref = RefScalars("replay_cosine" if cosine else "replay_l2")
     for rep in range(3000):
         obs, g, rows, f, v = _random_node(rng, rep)
         md = 0 if rep % 5 else int(rng.integers(0, 4))
-        a = oracle.ref_scores(obs, g, rows, f, v, md, cosine)
+        a = ref.next(lambda: oracle.ref_scores(obs, g, rows, f, v, md, cosine))
         b = oracle.replay_scores(obs, g, rows, f, v, md, cosine)
         assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes(), (rep, a, b, g.shape, len(rows))
+    ref.finish()
 
 
 @pytest.mark.parametrize("cosine", [True, False])
 def test_categorical_scores_follow_the_same_sequence(cosine):
     """TreeNode::splitScoreCosineCategorical / splitScoreL2Categorical (node.cpp:253-319, 378-434) are separate functions of the reference: the
     compiler could have contracted their expressions differently.  It did not: same bits as the restated sequence on the equivalent 0/1 column."""
-    if oracle.ref_score_probe() is None:
-        pytest.skip("oracle/_ref/ref_score_probe.so not built (needs /root/reference)")
     rng = np.random.default_rng(3)
+    ref = RefScalars("categorical_cosine" if cosine else "categorical_l2")
     for rep in range(1500):
         D, N = int(rng.integers(1, 41)), int(rng.integers(1, 500))
         sc = np.exp(rng.standard_normal() * 3)
@@ -160,9 +159,10 @@ def test_categorical_scores_follow_the_same_sequence(cosine):
         cat = np.zeros((N, 1), "S128")
         cat[:, 0] = np.array([b"a", b"b", b"c"])[tok]
         rows = np.flatnonzero(rng.integers(0, 4, N) > 0).astype(np.int32)
-        a = oracle.ref_split_score_cat(cat, g, rows, 0, b"a", 0, cosine)
+        a = ref.next(lambda: (oracle.ref_split_score_cat(cat, g, rows, 0, b"a", 0, cosine),))[0]
         b = oracle.replay_scores((tok == 0).astype(np.float32).reshape(N, 1), g, rows, 0, 0.5, 0, cosine)[0]
         assert a.tobytes() == b.tobytes(), (rep, a, b)
+    ref.finish()
 
 
 @pytest.mark.parametrize("seed", [9894, 23064, 23089])
@@ -170,17 +170,19 @@ def test_restatement_takes_the_references_side_of_a_mirror_tie(seed):
     """Two-token categorical columns make mirror-image candidates ("== a" against "== b"): their scores tie exactly in exact arithmetic and the
     reference's asymmetric float32 expression decides (fma(norm_r, n_r, norm_l * n_l)).  The restatement evaluates that expression as the
     reference's build does (replay_sequence.cpp) -- before round 5 its own compiler's contraction decided, and these seeds came out the other way."""
-    ref = oracle.load_ref()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
     rng = np.random.default_rng(seed)
     case = dict(name="mirror", seed=seed, N=2500, F=0, Fc=2, D=int(rng.choice([1, 2])), depth=4, n_bins=4, score="Cosine", gen="Quantile", policy="greedy",
                 trees=1, min_data_in_leaf=5, n_tokens=3)
     X, Xc, G, y = K.make_inputs(case)
-    a = ref.GBRL(**K.ctor_kwargs(case))
-    K.drive(a, case, X, Xc, G, y)
+
+    def reference(ref):
+        a = ref.GBRL(**K.ctor_kwargs(case))
+        K.drive(a, case, X, Xc, G, y)
+        ea = a.get_ensemble_data()
+        return {k: ea[k] for k in STRUCTURE_KEYS + VALUE_KEYS}
+    ea = ref_arrays("mirror_%d" % seed, reference)
     b = oracle.OracleGBRL(**K.ctor_kwargs(case))
     K.drive(b, case, X, Xc, G, y)
-    ea, eb = a.get_ensemble_data(), b.get_ensemble_data()
+    eb = b.get_ensemble_data()
     for k in STRUCTURE_KEYS + VALUE_KEYS:
         assert np.array_equal(np.asarray(ea[k]), eb[k]), k
