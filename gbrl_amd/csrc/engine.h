@@ -62,6 +62,12 @@ class PinnedBuf {
 namespace detail {
 struct GrowCtx;
 struct HNode;
+struct GrowDims;
+struct StepTables;
+struct LevelWork;
+struct Level;
+class TreeBuilder;
+class Stager;
 // a categorical split candidate: class `cls` of feature `feat` is the category `name` (the raw 128-byte cell, types.h:55-58)
 struct CatCandidate {
     int feat;
@@ -125,6 +131,26 @@ class Engine {
     uint64_t cat_dict_token();
     void grow_tree(const detail::GrowCtx &c, std::vector<detail::HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc,
                    double &leaf_scale);
+    // the growth paths grow_tree chooses from (engine_grow.hip, engine_grow_levels.hip; engine_grow_detail.h has the structs)
+    enum class SmallGrowth { Grown, NearTie, Unavailable };
+    detail::StepTables upload_step_tables(const detail::GrowCtx &c, const detail::GrowDims &dims);
+    SmallGrowth grow_small(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::StepTables &t, int blocks, detail::TreeBuilder &tb,
+                           std::vector<int64_t> &acc, double &leaf_scale, const char *&why);
+    void grow_levels(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::StepTables &t, detail::TreeBuilder &tb,
+                     std::vector<int64_t> &acc, double &leaf_scale);
+    detail::LevelWork level_workspace(const detail::GrowCtx &c, const detail::GrowDims &dims);
+    void grow_levels_planned(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::StepTables &t, detail::LevelWork &w, detail::TreeBuilder &tb);
+    void grow_levels_host(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::StepTables &t, detail::LevelWork &w, detail::TreeBuilder &tb,
+                          detail::Stager &sta, detail::Stager &stb);
+    detail::Level stage_level(const detail::GrowCtx &c, const detail::GrowDims &dims, detail::LevelWork &w, detail::TreeBuilder &tb, detail::Stager &sta, int depth,
+                              std::vector<int> active);
+    void level_histograms(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::LevelWork &w, const detail::Level &L);
+    uint32_t score_select_level(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::StepTables &t, const detail::LevelWork &w, const detail::Level &L);
+    void replay_near_ties(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::StepTables &t, const detail::LevelWork &w,
+                          const std::vector<detail::HNode> &nodes, const detail::Level &L);
+    void finish_leaves(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::LevelWork &w, detail::TreeBuilder &tb, detail::Stager &sta,
+                       std::vector<int64_t> &acc, double &leaf_scale);
+    uint32_t next_seq() { const uint32_t seq = ++level_seq_; return seq ? seq : ++level_seq_; }   // 0 is never published
     bool device_categorical_candidates(const char *dcells, const char *hcells, int N, int Fc, int B,
                                        std::vector<detail::CatCandidate> &cat_cands, std::vector<int> &cat_classes, bool launch_only = false);
     void sharded_categorical_ranking(const char *hcat, const float *hgrads, int N, int Fc, int D, int B, std::vector<detail::CatCandidate> &cat_cands,
@@ -191,7 +217,6 @@ class Engine {
     size_t leafacc_clean_bytes_ = 0;
     DevBuf d_codes_fm_;               // feature-major copy of the numeric class codes (kern::small_prep -> kern::small_grow)
     DevBuf d_am_s_, d_near_list_, d_near_ent_, d_near_rep_, d_near_nr_, d_near_maps_, d_near_pos_, d_near_nrb_, d_near_vals_, d_near_means_, d_near_sums_, d_near_chains_, d_near_rowsort_, d_near_tiles_;   // near-tie replay (kern::near_tie_replay): runner-up per arg-max block, candidate lists, ordered row lists, replayed scores
-    bool force_level_loop_ = false;   // grow_tree: the one-launch kernel met a near-tie and handed the tree to the level loop
     bool small_grow_off_ = false;     // latched after a failed launch / an abandoned grid barrier of the one-launch kernel: this engine keeps to the level loop
     long long small_grow_fallbacks_ = 0;   // trees the level loop grew after such a failure (diagnostics)
     long long near_replays_ = 0, near_bailouts_ = 0, near_in_kernel_ = 0;   // levels replayed / one-launch trees handed over (diagnostics: phases at profiling level 2)
@@ -215,12 +240,11 @@ class Engine {
     DevBuf d_thr_, d_thrkeys_, d_prefix_, d_trial_, d_counts_, d_cum_, d_minmax_;
     DevBuf d_selcnt_, d_kcls_, d_kt_, d_qflags_, d_splitters_, d_ccounts_, d_c2l_, d_tgt_list_, d_tgt_rank_, d_list_off_, d_qlists_;
     DevBuf d_radix_state_, d_radix_partial_, d_radix_global_, d_scales_;
-    DevBuf d_codes_, d_catcodes_, d_rows_[2], d_chunks_, d_chunk_begin_;
-    DevBuf d_hist_prev_, d_slotmap_, d_am_v_, d_am_i_, d_stage_const_, d_stage_a_, d_stage_b_, d_results_;
+    DevBuf d_codes_, d_catcodes_, d_rows_[2];
+    DevBuf d_hist_prev_, d_am_v_, d_am_i_, d_stage_const_, d_stage_a_, d_stage_b_, d_results_;
     PinnedBuf pin_const_, pin_a_, pin_b_, pin_res_, pin_thr_, pin_acc_, pin_cat_, pin_cat_dict_;
-    DevBuf d_hist_partials_, d_hist_, d_hist_local_, d_hist_recv_, d_gather_, d_slots_, d_scores_, d_parent_, d_cand_w_, d_cand_ref_;
-    DevBuf d_path_len_, d_path_slot_, d_path_val_, d_path_bin_, d_isroot_;
-    DevBuf d_best_idx_, d_best_score_, d_splits_, d_ntotal_, d_nright_, d_cursors_, d_leafacc_, d_plan_, d_res_all_;
+    DevBuf d_hist_partials_, d_hist_, d_hist_local_, d_hist_recv_, d_gather_, d_scores_, d_parent_;
+    DevBuf d_splits_, d_cursors_, d_leafacc_, d_plan_, d_res_all_;
     PinnedBuf pin_res_all_, pin_cum_;
     long long cum_cache_n_ = -1;   // (global rows, n_bins) the device copy of the quantile target ranks was built for
     int cum_cache_b_ = -1;

@@ -1,6 +1,7 @@
-// engine_step_detail.h -- what the three translation units of step() share (round 6: engine_step.hip was one 2 500-line file):
+// engine_step_detail.h -- what the translation units of step() share (round 6: engine_step.hip was one 2 500-line file):
 //   engine_candidates.hip  split candidates: categorical cells on the device, sharded ranking, numeric thresholds (A3-A5)
-//   engine_grow.hip        Engine::grow_tree: the one-launch growth of RL-sized steps and the level loop (A6-A10)
+//   engine_grow.hip        Engine::grow_tree: the choice of the growth path, the one-launch growth of RL-sized steps, the host tree's bookkeeping
+//   engine_grow_levels.hip Engine::grow_levels: the level loops and the final leaves (A6-A10); engine_grow_detail.h has what these two share
 //   engine_step.hip        Engine::step / Engine::fit, the host scan of categorical cells, the tree joining the ensemble (A1, A2, A10-A11)
 #pragma once
 #include "engine.h"

@@ -1,7 +1,7 @@
 // small_grow.hip -- RL-sized steps (N <= 8192 rows on one GPU): the WHOLE growth of a tree -- every level's histograms, scores,
 // arg-max, row routing, and the leaf sums -- in ONE launch (round 5).
 //
-// The level-synchronous host loop (engine_step.hip, grow_tree) needs 4-6 dispatches and a host round trip per level; at a few thousand
+// The level-synchronous host loop (engine_grow_levels.hip, Engine::grow_levels_host) needs 4-6 dispatches and a host round trip per level; at a few thousand
 // rows each of them is launch latency on an idle device, and its dense int64 level buffers [node][F][257][D+1] cost as much for 4096
 // rows as for a million.  Here a block owns feature slots (block b: slots b, b + G, ...), keeps the int32 histogram of ONE slot for a
 // batch of nodes in its LDS and never writes it out:
