@@ -576,7 +576,7 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         const int n = gbrl_hip_num_optimizers(self.h);
         if (n == 0) fail("No optimizers found");
         py::array_t<float> a(n);
-        for (int i = 0; i < n; ++i) { gbrl_hip_optimizer o{}; gbrl_hip_get_optimizer(self.h, i, &o); a.mutable_data()[i] = o.init_lr; }
+        gbrl_hip_get_scheduler_lrs(self.h, a.mutable_data());
         return a;
     });
     g.def("get_num_trees", [](PyGBRL &self) { return self.meta().n_trees; });

@@ -275,6 +275,12 @@ int gbrl_hip_get_optimizer(const gbrl_hip_model *m, int idx, gbrl_hip_optimizer 
     *out = m->engine.model.opts[idx];
     return GBRL_HIP_OK;
 }
+int gbrl_hip_get_scheduler_lrs(const gbrl_hip_model *m, float *out) {
+    if (!m || !out) return GBRL_HIP_E_INVALID;
+    const gbrl::Model &md = m->engine.model;
+    for (size_t i = 0; i < md.opts.size(); ++i) out[i] = gbrl::scheduler_lr(md.opts[i], md.meta.n_trees);   // gbrl.cpp:527-539
+    return GBRL_HIP_OK;
+}
 const char *gbrl_hip_learner_name(const gbrl_hip_model *m) { return m ? m->engine.model.learner_name.c_str() : ""; }
 
 int gbrl_hip_get_ensemble(const gbrl_hip_model *m, int32_t *tree_indices, int32_t *depths, float *values,

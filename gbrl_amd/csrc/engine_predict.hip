@@ -224,6 +224,19 @@ void Engine::sync_model_to_device() {
     append(m_opt_start_, os.data(), 4, 0, os.size());
     append(m_opt_stop_, oe.data(), 4, 0, oe.size());
     append(m_opt_lr_, olr.data(), 4, 0, olr.size());
+    if (model.scheduled()) {
+        const size_t NO = model.opts.size();
+        const bool same = rate_opts_.size() == NO && std::memcmp(rate_opts_.data(), model.opts.data(), NO * sizeof(gbrl_hip_optimizer)) == 0;
+        if (!same || rate_trees_ > T) { rate_trees_ = 0; rate_opts_ = model.opts; }
+        rate_host_.resize(std::max<size_t>(T, 1) * NO, 0.0f);
+        for (size_t t = rate_trees_; t < T; ++t)
+            for (size_t o = 0; o < NO; ++o) rate_host_[t * NO + o] = scheduler_lr(model.opts[o], static_cast<int>(t));
+        append(m_rate_, rate_host_.data(), 4, rate_trees_ * NO, T * NO);
+        rate_trees_ = T;
+    } else {
+        rate_trees_ = 0;
+        rate_opts_.clear();
+    }
     flush_segments();
     mirror_version_ = model.version;
 }
@@ -533,13 +546,19 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     pm.coef_ok = D <= 64 ? 1 : 0;
     pm.coef_cover = 0;
     for (int j = 0; j < 64; ++j) pm.coef[j] = 0.0f;
-    for (const auto &o : model.opts) {   // one learning rate per output unless two optimisers share an output
+    for (int j = 0; j < 64; ++j) pm.owner[j] = 0;
+    for (size_t oi = 0; oi < model.opts.size(); ++oi) {   // one learning rate per output unless two optimisers share an output
+        const auto &o = model.opts[oi];
         for (int j = o.start_idx; j < o.stop_idx && pm.coef_ok; ++j) {
             if (j < 0 || j >= D || ((pm.coef_cover >> j) & 1ull)) { pm.coef_ok = 0; break; }
             pm.coef_cover |= 1ull << j;
             pm.coef[j] = o.init_lr;
+            pm.owner[j] = static_cast<uint8_t>(oi);
         }
     }
+    if (model.opts.size() > 255) pm.coef_ok = pm.coef_ok && !model.scheduled();   // (owner is a byte; D <= 64 bounds the optimizers of a covered model anyway)
+    // Linear schedules: the kernels of predict_sched.hip read the rate of (tree, optimizer) from the mirror's table
+    pm.rate = (model.scheduled() && md.n_trees > 0) ? m_rate_.as<float>() : nullptr;
     // small batches: scratch for up to 64 partial sums per output (tree ranges spread over blocks, kern::predict)
     pm.partial = nullptr; pm.partial_floats = 0; pm.tree_chunk = 0;
     // (not inside fit(): its gradients follow the reference's per-row tree-order chain at every batch size)

@@ -412,13 +412,23 @@ bool export_header(const Model &m, const std::string &model_name, const std::str
     h << "};\n\tconst " << ctype << " feature_values[" << prefix << "BINARY_FEATURES] = {";
     list(n_conditions, [&](int i) { put_number(h, fmt, m.feature_values[i]); });
     h << "};\n\tconst " << ctype << " leaf_values[" << prefix << "N_LEAVES*" << prefix << "N_OUTPUTS]  = {";
-    // every optimizer contributes its own output range, scaled by -lr (constant schedules only: model.cpp add_optimizer)
-    for (int leaf = 0; leaf < L; ++leaf)
+    // every optimizer contributes its own output range, scaled by -lr(tree).  The tree a leaf is charged to is found the way the
+    // reference finds it (types.cpp:597-604): the counter advances when the leaf index EXCEEDS the first leaf of the current tree, so
+    // leaf 0 gets tree 0, the other leaves of tree k and the first leaf of tree k + 1 get tree k + 1, and behind the last tree's
+    // first leaf the counter advances with every leaf (the reference reads zeros behind tree_indices there).  It matters for Linear
+    // schedules only, and the exported text is the reference's.
+    int tree_idx = 0, limit_leaf = T > 0 ? m.tree_indices[0] : 0;
+    for (int leaf = 0; leaf < L; ++leaf) {
+        if (leaf > limit_leaf) {
+            ++tree_idx;
+            limit_leaf = tree_idx < T ? m.tree_indices[tree_idx] : 0;
+        }
         for (const gbrl_hip_optimizer &o : m.opts)
             for (int j = o.start_idx; j < o.stop_idx; ++j) {
-                put_number(h, fmt, -m.values[static_cast<size_t>(leaf) * D + j] * o.init_lr);
+                put_number(h, fmt, -m.values[static_cast<size_t>(leaf) * D + j] * scheduler_lr(o, tree_idx));
                 if (leaf < L - 1 || j < D - 1) h << ", ";
             }
+    }
     h << "};\n\tleaf_ptr = 0;\n\tcond_ptr = 0;\n\tunsigned char pass;\n\tfor (tree_idx = 0; tree_idx < " << prefix << "N_TREES; ++tree_idx)\n\t{\n";
     if (compact) {
         h << "\t\tidx = 0;\n";

@@ -49,6 +49,7 @@ namespace hooks {
     X(PREDICT_REG_ONLY) \
     X(PREDICT_REG_WAVES) \
     X(PREDICT_RG) \
+    X(PREDICT_SCHED_MIN_ROWS) \
     X(PREDICT_TT) \
     X(QUANTILE_RADIX) \
     X(QUANTILE_SAMPLE) \

@@ -447,6 +447,10 @@ struct PredictModel {
     int obl_ok, coef_ok;
     uint64_t coef_cover;
     float coef[64];
+    // Linear schedules (predict_sched.hip): rate[t * n_opts + o] = learning rate of optimizer o for the tree with absolute index t, for
+    // every tree of the ensemble; nullptr when every optimizer is Const.  owner[j] = the optimizer of output j (valid when coef_ok).
+    const float *rate;
+    uint8_t owner[64];
     float *partial;          // scratch for tree-split prediction of small batches (nullable), partial_floats elements
     size_t partial_floats;
     int tree_chunk;          // set by kern::predict: trees per block column (0 = every block walks the whole range)
@@ -477,8 +481,20 @@ int obl2_levels(int max_depth);     // 4, 6, 8 (0: max_depth > 8)
 bool obl2_feasible(int max_depth, int D, bool greedy);   // false: no launch plan can take the shape (the mirror is then not built)
 // Small / medium batches against large ensembles: leaf search spread over the chip, then one fused multiply-add chain per (row,
 // output) in tree order -- the bits of the one-chain-per-row kernels (predict_chain.hip).  false: not covered, nothing was launched.
+constexpr int kChainU = 64;              // slot rows are padded in multiples of this many trees
+constexpr int kSlotPad = 10 * kChainU;   // the relays request up to 3 W - 2 batches behind the range (k_chain_relay / k_sched_relay assert it)
 size_t predict_chain_slot_ints(int n, int trees);
 bool predict_chain(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
+                   float *out, hipStream_t s);
+// The first launch of predict_chain alone: slots[row][tree of the range] = byte offset of the leaf's values row, *Ts_out = the row stride of
+// `slots`.  false: not covered, nothing was launched.  (predict_sched.hip runs its own chain stage behind it.)
+bool predict_chain_slots(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
+                         int *Ts_out, hipStream_t s);
+// Ensembles with a Linear learning-rate schedule (PredictModel::rate != nullptr; predict_sched.hip): general, streaming and chain kernels
+// that scale tree t by rate[t][optimizer].  Always launches.
+// out[r][j] = bias[j] + the pm.tree_splits partial sums of pm.partial, in tree order (small batches whose trees were spread over block columns)
+void predict_combine(const PredictModel &pm, int n, float *out, hipStream_t s);
+void predict_sched(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
                    float *out, hipStream_t s);
 bool predict_obl2(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
                   float *out, hipStream_t s);   // false: shape not covered, nothing was launched

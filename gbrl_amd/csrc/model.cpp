@@ -100,6 +100,23 @@ void Model::set_feature_mapping(const int32_t *mapping, const uint8_t *is_numeri
     ++version;
 }
 
+float scheduler_lr(const gbrl_hip_optimizer &o, int t) {
+#pragma STDC FP_CONTRACT OFF   // every operation below rounds to float32 on its own, as in the reference's build for x86-64
+    if (o.scheduler != GBRL_HIP_SCHED_LINEAR) return o.init_lr;
+    // the fraction of the schedule that is left after tree t, then the interpolation from init_lr towards stop_lr, then the clamp
+    const float total = static_cast<float>(o.T);
+    const float trees_done = static_cast<float>(t) + 1;
+    const float left = (total - trees_done) / total;
+    const float rate = o.init_lr + (1.0f - left) * (o.stop_lr - o.init_lr);
+    return rate < o.stop_lr ? o.stop_lr : rate;
+}
+
+bool Model::scheduled() const {
+    for (const auto &o : opts)
+        if (o.scheduler == GBRL_HIP_SCHED_LINEAR) return true;
+    return false;
+}
+
 void Model::add_optimizer(const gbrl_hip_optimizer &o) {
     // GBRL::set_optimizer, gbrl.cpp:452-525 (same checks, same order)
     if (opts.size() >= static_cast<size_t>(meta.output_dim)) throw std::runtime_error("Optimizer Limit Reached");
@@ -108,8 +125,10 @@ void Model::add_optimizer(const gbrl_hip_optimizer &o) {
         throw std::runtime_error("invalid index ranges");
     if (o.algo != GBRL_HIP_ALGO_SGD)  // the reference's GPU path rejects Adam as well (gbrl.cpp:477-482)
         throw std::runtime_error("Incompatible GPU optimizer");
-    if (o.scheduler != GBRL_HIP_SCHED_CONST)  // ... and the Linear scheduler (gbrl.cpp:499-505)
-        throw std::runtime_error("Incompatible GPU scheduler");
+    // The reference's GPU path rejects the Linear scheduler too (gbrl.cpp:499-505); its CPU path runs it, and so does this build.
+    if (o.scheduler != GBRL_HIP_SCHED_CONST && o.scheduler != GBRL_HIP_SCHED_LINEAR) throw std::runtime_error("Incompatible GPU scheduler");
+    // LinearScheduler::get_lr divides by T (scheduler.h:127): the reference would produce inf / NaN rates, here the call fails
+    if (o.scheduler == GBRL_HIP_SCHED_LINEAR && o.T <= 0) throw std::runtime_error("Linear scheduler: T must be positive");
     opts.push_back(o);
     ++version;
 }
@@ -147,12 +166,14 @@ void Model::save(const std::string &filename) const {
     const int32_t n_opts = static_cast<int32_t>(opts.size());
     put(f, n_opts);
     for (const auto &o : opts) {
-        // SGDOptimizer::saveToFile optimizer.cpp:120-131 + ConstScheduler::saveToFile scheduler.cpp:99-108
+        // SGDOptimizer::saveToFile optimizer.cpp:120-131 + ConstScheduler::saveToFile scheduler.cpp:99-108 /
+        // LinearScheduler::saveToFile scheduler.cpp:64-75 (type, init_lr, stop_lr, T)
         put(f, static_cast<uint8_t>(o.algo));
         put(f, static_cast<int32_t>(o.start_idx));
         put(f, static_cast<int32_t>(o.stop_idx));
         put(f, static_cast<uint8_t>(o.scheduler));
         put(f, o.init_lr);
+        if (o.scheduler == GBRL_HIP_SCHED_LINEAR) { put(f, o.stop_lr); put(f, static_cast<int32_t>(o.T)); }
     }
     if (!f.good()) throw std::runtime_error("Writing to file error");
 }
@@ -231,9 +252,10 @@ Model Model::load(const std::string &filename) {
         if (sched == GBRL_HIP_SCHED_LINEAR) { get(f, o.stop_lr); get(f, o.T); }  // scheduler.cpp:64-75
         o.algo = algo; o.scheduler = sched; o.start_idx = start; o.stop_idx = stop;
         if (!f.good()) throw std::runtime_error("Optimizer load error");
-        // Files with Adam / Linear records parse, but this build cannot run them (no CPU path): refuse loudly.
-        if (algo != GBRL_HIP_ALGO_SGD || sched != GBRL_HIP_SCHED_CONST)
-            throw std::runtime_error("model file uses Adam or a Linear scheduler: CPU-only in the reference, unsupported here");
+        // Files with Adam records parse, but this build cannot run them (no CPU path): refuse loudly.
+        if (algo != GBRL_HIP_ALGO_SGD || (sched != GBRL_HIP_SCHED_CONST && sched != GBRL_HIP_SCHED_LINEAR))
+            throw std::runtime_error("model file uses Adam or an unknown scheduler: CPU-only in the reference, unsupported here");
+        if (sched == GBRL_HIP_SCHED_LINEAR && o.T <= 0) throw std::runtime_error("Optimizer load error");   // get_lr would divide by zero
         m.opts.push_back(o);
     }
     return m;

@@ -22,6 +22,11 @@ constexpr int kTreesBatch = 25000;       // TREES_BATCH, types.h:52
 
 static_assert(sizeof(gbrl_hip_metadata) == 80, "ensembleMetaData must be 80 bytes (SURVEY.md A12)");
 
+// Learning rate of optimizer `o` for the tree with ABSOLUTE index t: ConstScheduler::get_lr / LinearScheduler::get_lr
+// (scheduler.h:124-134) in float32 with the reference's operation order.  THE one definition: predict's device rate table, the
+// exported header and get_scheduler_lrs all call it.
+float scheduler_lr(const gbrl_hip_optimizer &o, int t);
+
 struct Model {
     gbrl_hip_metadata meta{};
     std::string learner_name = "GBRL";
@@ -54,7 +59,8 @@ struct Model {
     // reserve room for one more tree with `n_leaves_new` leaves; maintains the reference's capacity book-keeping
     void begin_tree();
     void set_feature_mapping(const int32_t *mapping, const uint8_t *is_numeric);
-    void add_optimizer(const gbrl_hip_optimizer &o);  // throws std::runtime_error like GBRL::set_optimizer
+    void add_optimizer(const gbrl_hip_optimizer &o);  // throws std::runtime_error like GBRL::set_optimizer (SGD with a Const or Linear schedule)
+    bool scheduled() const;                           // some optimizer has a Linear schedule: its rate depends on the tree index
 
     void save(const std::string &filename) const;    // throws on I/O error
     static Model load(const std::string &filename);  // throws on I/O error

@@ -673,6 +673,11 @@ __global__ void k_predict_combine(const float *__restrict__ partial, int splits,
     out[i] = p;
 }
 
+void predict_combine(const PredictModel &pm, int n, float *out, hipStream_t s) {
+    const size_t n_el = static_cast<size_t>(n) * pm.D;
+    hipLaunchKernelGGL(k_predict_combine, dim3(static_cast<unsigned>((n_el + 255) / 256)), dim3(256), 0, s, pm.partial, pm.tree_splits, n_el, pm.D, pm.bias, out);
+}
+
 void predict(const PredictModel &pm_in, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree,
              int stop_tree, float *out, hipStream_t s) {
     // Small batches with large ensembles (an RL agent acting: tens to thousands of rows, hundreds to thousands of trees) would walk
@@ -688,6 +693,8 @@ void predict(const PredictModel &pm_in, const float *obs, int F, const int32_t *
     // 50 000 trees, measured), so beyond a few thousand trees a differently associated -- more accurate -- sum would leave the 1e-5
     // band around the reference's chain; larger ensembles keep the chain wherever the reference runs it.
     pm.tree_splits = 1;
+    // (tests/test_gpu_sched.py::_slices restates the slice arithmetic below -- the thresholds 1024 / 16 384 rows, 128 / 2048 trees, par_th,
+    // the scratch cap -- to check the slice sums of scheduled ensembles bit for bit: retune the two together)
     // (up to 1024 rows the exact chain of kern::predict_chain costs the same -- 17 vs 14 us at 600 trees, 36 vs 32 us at 2000 -- and is taken
     // instead: those batches get the same bits whatever their size)
     const bool chain_first = pm.slots != nullptr && n <= 1024;
@@ -713,6 +720,10 @@ void predict(const PredictModel &pm_in, const float *obs, int F, const int32_t *
             pm.tree_splits = n_tree_thr;
             pm.tree_chunk = trees / n_tree_thr;
         }
+    }
+    if (pm.rate != nullptr) {   // some optimizer has a Linear schedule: the kernels that read the per-tree rate table (same tree slices)
+        predict_sched(pm, obs, F, cat_codes, Fc, n, start_tree, stop_tree, out, s);
+        return;
     }
     if (pm.tree_chunk == 0 && pm.slots && predict_chain(pm, obs, F, cat_codes, Fc, n, start_tree, stop_tree, out, s)) return;
     struct Combine {   // runs after whichever fast kernel took the launch

@@ -26,8 +26,6 @@ namespace kern {
 
 namespace {
 
-constexpr int kChainU = 64;          // slot rows are padded in multiples of this many trees
-constexpr int kSlotPad = 10 * kChainU;   // the relay requests up to 3 W - 2 batches behind the range (k_chain_relay asserts it)
 
 struct ChainCoef {
     float c[64];        // -lr of the optimiser that owns the output
@@ -244,8 +242,8 @@ size_t predict_chain_slot_ints(int n, int trees) {
     return static_cast<size_t>(n) * Ts;
 }
 
-bool predict_chain(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
-                   float *out, hipStream_t s) {
+bool predict_chain_slots(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
+                         int *Ts_out, hipStream_t s) {
     const int Tn = stop_tree - start_tree;
     if (!pm.slots || Tn <= 0 || n <= 0 || F <= 0 || !pm.coef_ok || pm.D > 64) return false;
     if (pm.oblivious ? !(pm.obl_ok && pm.cond_pack) : !(pm.grd_ok && pm.grd_nodes)) return false;
@@ -267,6 +265,15 @@ bool predict_chain(const PredictModel &pm, const float *obs, int F, const int32_
     else if (pm.max_depth <= 6) GBRL_SLOTS(false, 6);
     else GBRL_SLOTS(false, 8);
 #undef GBRL_SLOTS
+    *Ts_out = Ts;
+    return true;
+}
+
+bool predict_chain(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
+                   float *out, hipStream_t s) {
+    const int Tn = stop_tree - start_tree;
+    int Ts = 0;
+    if (!predict_chain_slots(pm, obs, F, cat_codes, Fc, n, start_tree, stop_tree, &Ts, s)) return false;
     ChainCoef coef;
     for (int j = 0; j < 64; ++j) coef.c[j] = j < pm.D ? -pm.coef[j] : 0.0f;
     coef.cover = pm.coef_cover;

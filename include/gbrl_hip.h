@@ -73,7 +73,9 @@ typedef struct {
     int32_t n_num_features, n_cat_features, iteration;
 } gbrl_hip_metadata;
 
-/* optimizerConfig, gbrl/src/cpp/types.h:186-197 */
+/* optimizerConfig, gbrl/src/cpp/types.h:186-197.  algo must be SGD.  scheduler Const: every tree's values enter predictions scaled by
+ * init_lr.  Linear (scheduler.h:124-134): tree t (absolute index) is scaled by max(stop_lr, init_lr + ((t + 1) / T) * (stop_lr - init_lr)),
+ * evaluated in float32; T must be positive. */
 typedef struct {
     int32_t algo, scheduler;
     float init_lr, stop_lr;
@@ -112,6 +114,8 @@ int gbrl_hip_get_feature_weights(const gbrl_hip_model *m, float *out);          
 int gbrl_hip_get_feature_mapping(const gbrl_hip_model *m, int32_t *feature_mapping, uint8_t *mapping_numerics);
 int gbrl_hip_num_optimizers(const gbrl_hip_model *m);
 int gbrl_hip_get_optimizer(const gbrl_hip_model *m, int idx, gbrl_hip_optimizer *out);           /* binding.cpp:393-419 */
+/* GBRL::get_scheduler_lrs (gbrl.cpp:527-539): out[i] = the rate optimizer i's schedule gives the NEXT tree, get_lr(n_trees) */
+int gbrl_hip_get_scheduler_lrs(const gbrl_hip_model *m, float *out /*[num_optimizers]*/);
 const char *gbrl_hip_learner_name(const gbrl_hip_model *m);
 /* GBRL::get_ensemble_data (gbrl.cpp:1344-1356): copies of the ensembleData arrays (types.h:279-304).  Sizes:
  * T=n_trees, L=n_leaves, S = T (oblivious) or L (greedy), md=max_depth, D=output_dim, in=input_dim.  Any
