@@ -453,6 +453,28 @@ py::array_t<float> shap_impl(PyGBRL &self, bool whole_ensemble, int tree_idx, py
 
 PYBIND11_MODULE(gbrl_cpp, m) {
     m.doc() = "MI355X-native drop-in for NVlabs/gbrl's gbrl_cpp (step / predict hot path), backed by libgbrl_hip.so";
+    // test helper (gbrl_hip_cat_rank_stats): the device's ranking statistics of a batch's categorical cells -- (feature, first row, count,
+    // total) of every distinct (feature, cell) pair
+    m.def("_cat_rank_stats", [](py::object cat, py::object grads) {
+        Input c = read_input(cat, "cat_obs", false, "_cat_rank_stats", 1);
+        Input g = read_input(grads, "grads", false, "_cat_rank_stats", 0);
+        if (c.on_device || g.on_device) fail("_cat_rank_stats takes NumPy arrays");
+        if (c.shape.empty() || g.shape.empty() || c.shape[0] != g.shape[0] || c.shape[0] == 0) fail("_cat_rank_stats: cat_obs [n, n_cat] and grads [n, output_dim] must have the same n > 0");
+        const size_t n = c.shape[0], fc = c.shape.size() > 1 ? c.shape[1] : 1, d = g.shape.size() > 1 ? g.shape[1] : 1;
+        if (n * fc >= (size_t(1) << 31) || fc == 0 || d == 0) fail("_cat_rank_stats: shape not supported");
+        const int cap = static_cast<int>(std::min<size_t>(n * fc, size_t(1) << 21));
+        py::array_t<int32_t> feat(cap), first(cap), count(cap);
+        py::array_t<float> total(cap);
+        int nd = -1, rc;
+        {
+            py::gil_scoped_release release;
+            rc = gbrl_hip_cat_rank_stats(static_cast<const char *>(c.ptr), static_cast<int>(n), static_cast<int>(fc), static_cast<const float *>(g.ptr),
+                                         static_cast<int>(d), cap, feat.mutable_data(), first.mutable_data(), count.mutable_data(), total.mutable_data(), &nd);
+        }
+        check(rc);
+        feat.resize({nd}, false); first.resize({nd}, false); count.resize({nd}, false); total.resize({nd}, false);
+        return py::make_tuple(feat, first, count, total);
+    }, py::arg("categorical_obs"), py::arg("grads"));
     py::class_<PyGBRL> g(m, "GBRL");
     g.def(py::init<int, int, int, int, int, int, int, float, std::string, std::string, bool, int, std::string, int, std::string, std::string>(),
           py::arg("input_dim") = 1, py::arg("output_dim") = 1, py::arg("policy_dim") = 1, py::arg("max_depth") = 4,

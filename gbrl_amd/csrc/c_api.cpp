@@ -476,6 +476,18 @@ int gbrl_hip_seq_sums(const float *x, const uint32_t *lens, const float *starts,
     });
 }
 
+int gbrl_hip_cat_rank_stats(const char *cells, int n, int n_cat, const float *grads, int output_dim, int cap, int32_t *feature,
+                            int32_t *first_row, int32_t *count, float *total, int *n_distinct) {
+    if (!cells || !grads || !feature || !first_row || !count || !total || !n_distinct || n < 1 || n_cat < 1 || output_dim < 1 || cap < 1) return GBRL_HIP_E_INVALID;
+    *n_distinct = -1;
+    return guarded([&] {
+        const int rc = gbrl::kern::cat_rank_selftest(cells, n, n_cat, grads, output_dim, cap, feature, first_row, count, total);
+        if (rc == -2) throw gbrl::InvalidArgument("cat_rank_stats: more distinct cells than cap");
+        if (rc < 0) throw gbrl::HipError("categorical ranking kernels failed (no HIP device, or more than 2^21 distinct cells?)");
+        *n_distinct = rc;
+    });
+}
+
 int gbrl_hip_set_profiling(gbrl_hip_model *m, int enabled) {
     if (!m) return GBRL_HIP_E_INVALID;
     m->engine.set_profiling(enabled < 0 ? 0 : (enabled > 2 ? 2 : enabled));

@@ -59,7 +59,8 @@ __global__ __launch_bounds__(256) void k_cat_publish(int32_t *__restrict__ meta,
                                                      int log2_cap, const char *__restrict__ cells, int Fc, int cap,
                                                      int32_t *__restrict__ h_hdr, int32_t *__restrict__ h_feat, int32_t *__restrict__ h_first,
                                                      unsigned long long *__restrict__ h_hash, char *__restrict__ h_names,
-                                                     int32_t *__restrict__ slot_q, uint32_t seq) {
+                                                     int32_t *__restrict__ slot_q, uint32_t seq, const int32_t *__restrict__ rank_count,
+                                                     const float *__restrict__ rank_total, int32_t *__restrict__ h_count, float *__restrict__ h_total) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;   // one 16-byte piece per thread
     const int n = min(meta[2], cap);
     if (i == 0) { h_hdr[0] = meta[0]; h_hdr[1] = meta[1]; h_hdr[2] = meta[2]; h_hdr[3] = n; }
@@ -68,11 +69,14 @@ __global__ __launch_bounds__(256) void k_cat_publish(int32_t *__restrict__ meta,
         const int32_t slot = list_slot[item];
         const int feat = slot >> log2_cap, row = first[slot];
         if (piece == 0) {
-            h_feat[item] = feat; h_first[item] = row; h_hash[item] = keys[slot];
+            if (h_names) { h_feat[item] = feat; h_first[item] = row; h_hash[item] = keys[slot]; }
             if (slot_q) slot_q[slot] = item;
+            if (h_count) { h_count[item] = rank_count[item]; h_total[item] = rank_total[item]; }   // cat_rank's statistics (overflow case)
         }
-        const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(cells + (static_cast<size_t>(row) * Fc + feat) * 128);
-        reinterpret_cast<ulonglong2 *>(h_names + static_cast<size_t>(item) * 128)[piece] = src[piece];
+        if (h_names) {   // (null: the records have been published before, only the statistics are new)
+            const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(cells + (static_cast<size_t>(row) * Fc + feat) * 128);
+            reinterpret_cast<ulonglong2 *>(h_names + static_cast<size_t>(item) * 128)[piece] = src[piece];
+        }
     }
     __threadfence_system();
     __syncthreads();
@@ -137,10 +141,11 @@ void cat_distinct_insert(const char *cells, int n, int Fc, uint64_t *keys, int32
 }
 void cat_publish(int32_t *meta, const int32_t *list_slot, const uint64_t *keys, const int32_t *first, int log2_cap, const char *cells,
                  int Fc, int cap, int32_t *h_hdr, int32_t *h_feat, int32_t *h_first, uint64_t *h_hash, char *h_names, int32_t *slot_q,
-                 uint32_t seq, hipStream_t s) {
-    hipLaunchKernelGGL(k_cat_publish, dim3((std::max(1, cap) * 8 + 255) / 256), dim3(256), 0, s, meta, list_slot,
+                 uint32_t seq, hipStream_t s, const int32_t *rank_count, const float *rank_total, int32_t *h_count, float *h_total) {
+    if (!rank_count || !rank_total || !h_count || !h_total) { rank_count = nullptr; rank_total = nullptr; h_count = nullptr; h_total = nullptr; }
+    hipLaunchKernelGGL(k_cat_publish, dim3(static_cast<unsigned>((static_cast<size_t>(std::max(1, cap)) * 8 + 255) / 256)), dim3(256), 0, s, meta, list_slot,
                        reinterpret_cast<const unsigned long long *>(keys), first, log2_cap, cells, Fc, cap, h_hdr, h_feat, h_first,
-                       reinterpret_cast<unsigned long long *>(h_hash), h_names, slot_q, seq);
+                       reinterpret_cast<unsigned long long *>(h_hash), h_names, slot_q, seq, rank_count, rank_total, h_count, h_total);
 }
 // Class codes of a step batch straight from the scan's own hash tables (one GPU, ordinary steps): the batch's cells are all in
 // the table and k_cat_distinct_verify has shown that equal hashes mean equal cells IN THIS BATCH, so the probe that inserted a cell finds

@@ -152,7 +152,8 @@ class Engine {
                        std::vector<int64_t> &acc, double &leaf_scale);
     uint32_t next_seq() { const uint32_t seq = ++level_seq_; return seq ? seq : ++level_seq_; }   // 0 is never published
     bool device_categorical_candidates(const char *dcells, const char *hcells, int N, int Fc, int B,
-                                       std::vector<detail::CatCandidate> &cat_cands, std::vector<int> &cat_classes, bool launch_only = false);
+                                       std::vector<detail::CatCandidate> &cat_cands, std::vector<int> &cat_classes, bool launch_only = false,
+                                       const float *dgrads = nullptr, int D = 0);   // dgrads: the batch's raw gradients (device), for the mean-gradient ranking
     void sharded_categorical_ranking(const char *hcat, const float *hgrads, int N, int Fc, int D, int B, std::vector<detail::CatCandidate> &cat_cands,
                                      std::vector<uint16_t> &h_catcodes, std::vector<int> &cat_classes);
     void numeric_thresholds(const float *dobs, int N, int F, int B, long long n_global, const uint32_t *d_kt, float *d_thr,
@@ -285,6 +286,7 @@ class Engine {
     const uint32_t *root_le_ = nullptr;   // this step's #{keys <= threshold} table (radix selection, one GPU), null otherwise
     DevBuf d_cat_keys_, d_cat_first_, d_cat_meta_, d_cat_lslot_, d_sdict_, d_cat_xchg_, d_cat_slotq_, d_cat_clsq_;
     PinnedBuf pin_cat_cls_;
+    DevBuf d_cat_rank_, d_cat_rank_cnt_, d_cat_rank_tot_;   // kern::cat_rank: scratch, count and total per distinct cell (more distinct cells than candidates)
     uint32_t cat_pub_seq_ = 0;                          // sequence word of k_cat_publish's completion flag
     // ordinary steps on one GPU: the class codes come from the scan's own tables (k_cat_step_codes_table) instead of a dictionary
     struct { bool valid = false; const uint64_t *keys = nullptr; const int32_t *slot_q = nullptr, *cls_of_q = nullptr; int log2_cap = 0; } cat_table_;

@@ -184,13 +184,14 @@ void Engine::sharded_categorical_ranking(const char *hcat, const float *hgrads, 
 // kernel's own completion word, so the host's replay of the reference's container (~0.1 ms at configs[4]) runs while the device works through
 // the numeric preparation instead of in front of an idle device (0.17 ms per 4096-row step, profiles/r04_cfg5_timeline_*.txt).
 bool Engine::device_categorical_candidates(const char *dcells, const char *hcells, int N, int Fc, int B,
-                                           std::vector<detail::CatCandidate> &cat_cands, std::vector<int> &cat_classes, bool launch_only) {
+                                           std::vector<detail::CatCandidate> &cat_cands, std::vector<int> &cat_classes, bool launch_only,
+                                           const float *dgrads, int D) {
     (void)hcells;   // the distinct cells are gathered from the device copy either way
     hipStream_t s = stream_;
     const long long keep = static_cast<long long>(Fc) * B;
     if (keep > (1 << 20)) return false;
     int full_log2 = 8;
-    while ((1ll << full_log2) < 4 * std::min<long long>(N, keep + 1) && full_log2 < 20) ++full_log2;
+    while ((1ll << full_log2) < 4ll * N && full_log2 < 20) ++full_log2;   // (every row of a column may be a category of its own: they are ranked below)
     if ((static_cast<size_t>(Fc) << full_log2) >= (1ull << 31)) return false;   // list records are 32-bit table slots
     const bool resume = cat_launched_;   // the first round of the loop below is already on the stream
     cat_launched_ = false;
@@ -198,7 +199,8 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
     // categories, so the step starts with four times the largest distinct count the previous step saw and repeats with the full size
     // only if a table overflowed (12 MB of memsets and atomics on a 12 MB table -> 0.2 MB at configs[4]).
     int log2_cap = std::min(full_log2, std::max(8, cat_log2_hint_));
-    const int list_cap = static_cast<int>(keep) + 1;
+    // the list holds EVERY distinct cell (up to 2^21): a batch with more of them than candidates are kept is ranked on the device (kern::cat_rank)
+    const int list_cap = static_cast<int>(std::min<long long>(static_cast<long long>(N) * Fc, 1ll << 21));
     int32_t *d_meta = static_cast<int32_t *>(d_cat_meta_.ensure(sizeof(int32_t) * 4));               // flags[2], counter
     int32_t *d_lslot = static_cast<int32_t *>(d_cat_lslot_.ensure(sizeof(int32_t) * list_cap));
     uint64_t *d_keys = nullptr;
@@ -210,21 +212,29 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
     const int32_t *h_hdr = nullptr, *lfeat = nullptr, *lfirst = nullptr;
     const uint64_t *lhash = nullptr;
     const char *names = nullptr;
+    const int32_t *lcount = nullptr;   // ranking statistics (stats != 0 only)
+    const float *ltotal = nullptr;
     bool names_in_pinned = false;
-    auto publish = [&](int cap, bool launch, bool collect) {
-        const size_t bytes = 64 + static_cast<size_t>(cap) * (8 + 4 + 4 + kCat);
+    int32_t *d_rcnt = nullptr;
+    float *d_rtot = nullptr;
+    // stats: 0 = the records; 1 = the records and kern::cat_rank's (count, total); 2 = only (count, total) of records that a publish with the
+    // same cap has already delivered (their feature, first row, hash and cell stay where they are)
+    auto publish = [&](int cap, bool launch, bool collect, int stats = 0) {
+        const size_t bytes = 64 + static_cast<size_t>(cap) * (8 + 4 + 4 + kCat + 4 + 4);
         char *h = static_cast<char *>(pin_cat_.ensure(bytes));
         void *dv = nullptr;
         hip_check(hipHostGetDevicePointer(&dv, h, 0), "hipHostGetDevicePointer");
         char *d = static_cast<char *>(dv);
         const size_t o_hash = 64, o_feat = o_hash + 8 * static_cast<size_t>(cap), o_first = o_feat + 4 * static_cast<size_t>(cap),
-                     o_names = o_first + 4 * static_cast<size_t>(cap);   // 64 + 16 cap: 16-byte aligned
+                     o_names = o_first + 4 * static_cast<size_t>(cap),   // 64 + 16 cap: 16-byte aligned
+                     o_cnt = o_names + static_cast<size_t>(kCat) * cap, o_tot = o_cnt + 4 * static_cast<size_t>(cap);
         volatile uint32_t *flag = reinterpret_cast<volatile uint32_t *>(h) + 4;   // header word 4: written last, by the last block
         if (launch) {
             *flag = 0;
             d_slotq = static_cast<int32_t *>(d_cat_slotq_.ensure(sizeof(int32_t) * (static_cast<size_t>(Fc) << log2_cap)));
             kern::cat_publish(d_meta, d_lslot, d_keys, d_first, log2_cap, dcells, Fc, cap, reinterpret_cast<int32_t *>(d), reinterpret_cast<int32_t *>(d + o_feat),
-                              reinterpret_cast<int32_t *>(d + o_first), reinterpret_cast<uint64_t *>(d + o_hash), d + o_names, d_slotq, ++cat_pub_seq_, s);
+                              reinterpret_cast<int32_t *>(d + o_first), reinterpret_cast<uint64_t *>(d + o_hash), stats == 2 ? nullptr : d + o_names, d_slotq, ++cat_pub_seq_, s,
+                              stats ? d_rcnt : nullptr, stats ? d_rtot : nullptr, reinterpret_cast<int32_t *>(d + o_cnt), reinterpret_cast<float *>(d + o_tot));
         }
         if (!collect) return;
         spin_until_published(flag, cat_pub_seq_, s, "the batch's distinct categorical cells");   // the publish only: kernels enqueued behind it keep running
@@ -235,7 +245,7 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
         // tree (verify_pending_categories); only new cells are read here.)
         const bool copy_names = has_coll_;
         const int n_pub = std::max(0, std::min(reinterpret_cast<const int32_t *>(h)[3], cap));
-        cat_host_.resize(64 + static_cast<size_t>(n_pub) * (8 + 4 + 4 + (copy_names ? kCat : 0)));
+        cat_host_.resize(64 + static_cast<size_t>(n_pub) * (8 + 4 + 4 + (copy_names ? kCat : 0) + (stats ? 8 : 0)));
         char *c = cat_host_.data();
         std::memcpy(c, h, 64);
         const size_t c_hash = 64, c_feat = c_hash + 8 * static_cast<size_t>(n_pub), c_first = c_feat + 4 * static_cast<size_t>(n_pub),
@@ -244,6 +254,13 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
         std::memcpy(c + c_feat, h + o_feat, 4 * static_cast<size_t>(n_pub));
         std::memcpy(c + c_first, h + o_first, 4 * static_cast<size_t>(n_pub));
         if (copy_names) std::memcpy(c + c_names, h + o_names, static_cast<size_t>(kCat) * n_pub);
+        if (stats) {
+            const size_t c_cnt = c_names + (copy_names ? static_cast<size_t>(kCat) * n_pub : 0), c_tot = c_cnt + 4 * static_cast<size_t>(n_pub);
+            std::memcpy(c + c_cnt, h + o_cnt, 4 * static_cast<size_t>(n_pub));
+            std::memcpy(c + c_tot, h + o_tot, 4 * static_cast<size_t>(n_pub));
+            lcount = reinterpret_cast<const int32_t *>(c + c_cnt);
+            ltotal = reinterpret_cast<const float *>(c + c_tot);
+        }
         h_hdr = reinterpret_cast<const int32_t *>(c);
         lhash = reinterpret_cast<const uint64_t *>(c + c_hash);
         lfeat = reinterpret_cast<const int32_t *>(c + c_feat);
@@ -251,6 +268,7 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
         names = copy_names ? c + c_names : h + o_names;
         names_in_pinned = !copy_names;
     };
+    int pub_cap = 0;
     for (bool first = true;; first = false) {
         const size_t slots = static_cast<size_t>(Fc) << log2_cap;
         d_keys = static_cast<uint64_t *>(d_cat_keys_.ensure(sizeof(uint64_t) * slots));
@@ -273,7 +291,8 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
             kern::cat_distinct_insert(dcells, N, Fc, d_keys, d_first, log2_cap, d_meta, d_lslot, d_meta + 2, list_cap, s);
             kern::cat_distinct_verify(dcells, N, Fc, d_keys, d_first, log2_cap, d_meta, s);
         }
-        publish(std::min(list_cap, std::max(256, cat_publish_guess_)), !enqueued, !launch_only);
+        pub_cap = std::min(list_cap, std::max(256, cat_publish_guess_));
+        publish(pub_cap, !enqueued, !launch_only);
         if (launch_only) { cat_launched_ = true; return true; }
         if (h_hdr[0] != 0 && log2_cap < full_log2) { log2_cap = full_log2; continue; }   // a table (or the list) overflowed: once more at full size
         break;
@@ -282,7 +301,12 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
     std::chrono::steady_clock::time_point cp[6];
     if (cat_prof) cp[0] = std::chrono::steady_clock::now();
     int n_distinct = h_hdr[2];
-    bool declined = h_hdr[0] != 0 || h_hdr[1] != 0 || n_distinct > keep;
+    // More distinct cells than candidates are kept: the reference ranks them by mean gradient norm (split_candidate_generator.cpp:131-150).
+    // One GPU: count and total of every distinct cell are computed on the device and published beside the list.  Row-sharded: declined,
+    // as before (sharded_categorical_ranking).
+    const bool overflow = n_distinct > keep;
+    const bool can_rank = !has_coll_ && dgrads != nullptr && D > 0 && n_distinct <= list_cap && kern::cat_rank_fits(N, Fc);
+    bool declined = h_hdr[0] != 0 || h_hdr[1] != 0 || (overflow && !can_rank);
     if (has_coll_) {   // every rank must take the same path
         int64_t *d_flag = static_cast<int64_t *>(d_cat_xchg_.ensure(sizeof(int64_t)));
         int64_t hv = declined ? 1 : 0;
@@ -293,7 +317,20 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
         declined = hv != 0;
     }
     if (declined) return false;
-    if (n_distinct > h_hdr[3]) publish(n_distinct, true, true);
+    if (overflow) {
+        phase_begin(/*key=*/true);
+        void *d_scr = d_cat_rank_.ensure(kern::cat_rank_scratch_bytes(N, Fc, n_distinct));
+        d_rcnt = static_cast<int32_t *>(d_cat_rank_cnt_.ensure(sizeof(int32_t) * static_cast<size_t>(n_distinct)));
+        d_rtot = static_cast<float *>(d_cat_rank_tot_.ensure(sizeof(float) * static_cast<size_t>(n_distinct)));
+        d_slotq = static_cast<int32_t *>(d_cat_slotq_.ensure(sizeof(int32_t) * (static_cast<size_t>(Fc) << log2_cap)));
+        kern::cat_rank(dcells, N, Fc, dgrads, D, d_keys, log2_cap, d_meta, d_lslot, n_distinct, d_slotq, d_scr, d_rcnt, d_rtot, s);
+        const bool all_here = n_distinct <= h_hdr[3];   // every record has arrived already: only 8 bytes per distinct cell travel now
+        const int cap2 = all_here ? pub_cap : n_distinct;
+        publish(cap2, true, false, all_here ? 2 : 1);
+        phase_end("cat_rank", /*key=*/true);
+        publish(cap2, false, true, all_here ? 2 : 1);
+        if (h_hdr[0] != 0 || h_hdr[2] != n_distinct) return false;   // a cell was not found in its table (cannot happen): the host scan decides
+    } else if (n_distinct > h_hdr[3]) publish(n_distinct, true, true);
     cat_publish_guess_ = n_distinct + n_distinct / 4 + 64;
     // the reference's insertion order: feature-major, then row of first occurrence -- one LSD radix sort (11-bit digits) of
     // feature * N + first row with the list index in the low 21 bits (std::sort of the per-feature buckets: 30 us at configs[4])
@@ -471,6 +508,17 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
         for (const auto &kv : ref_map) { if (!same) break; same = cand_item[k++] == kv.second; }
         if (!same) throw HipError("categorical candidates: the hash-replay order differs from the string-keyed container's");
     }
+    if (overflow && !has_coll_ && static_cast<long long>(cand_item.size()) > keep) {
+        // split_candidate_generator.cpp:131-150: (key, mean) in the container's iteration order, std::sort by descending mean, the first
+        // Fc * n_bins survive.  The comparator reads the means only, so sorting list indices instead of the reference's strings moves the
+        // elements identically; mean = float32 total / float(count), total bit-identical to the reference's row-order sum (kern::cat_rank).
+        std::vector<std::pair<int, float>> vec;
+        vec.reserve(cand_item.size());
+        for (int q : cand_item) vec.emplace_back(q, ltotal[q] / static_cast<float>(lcount[q]));
+        std::sort(vec.begin(), vec.end(), [](const std::pair<int, float> &a, const std::pair<int, float> &b2) { return a.second > b2.second; });
+        cand_item.resize(static_cast<size_t>(keep));
+        for (size_t k = 0; k < cand_item.size(); ++k) cand_item[k] = vec[k].first;
+    }
     if (static_cast<long long>(cand_item.size()) > keep)
         throw Unsupported("more distinct categories than Fc * n_bins in a row-sharded step (the reference's mean-gradient ranking is not available sharded)");
     // candidates + the step's dictionary (per feature: entries sorted by raw hash, then class), packed into ONE pinned block and
@@ -481,6 +529,7 @@ bool Engine::device_categorical_candidates(const char *dcells, const char *hcell
         // ordinary step on one GPU: the scan's tables ARE the dictionary; the host hands back the class of every list record only
         int32_t *hc = static_cast<int32_t *>(pin_cat_cls_.ensure(sizeof(int32_t) * static_cast<size_t>(std::max(1, n_distinct))));
         cat_cands.reserve(cat_cands.size() + n_ent);
+        if (overflow) std::fill(hc, hc + n_distinct, 0);   // a category that is not kept: class 0
         for (int q : cand_item) {
             const int f = lfeat[q];
             const int cls = ++cat_classes[f];

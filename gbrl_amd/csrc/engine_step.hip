@@ -358,7 +358,7 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
             cat_codes_on_device = true;
         } else {
             cat_codes_on_device = (has_coll_ || !force_host_categorical_) &&
-                                  device_categorical_candidates(dcells, cat_dev ? nullptr : cat, N, Fc, B, cat_cands, cat_classes);
+                                  device_categorical_candidates(dcells, cat_dev ? nullptr : cat, N, Fc, B, cat_cands, cat_classes, /*launch_only=*/false, dgrads, D);
         }
         if (!cat_codes_on_device) {
             std::vector<char> cat_host_buf;
@@ -390,8 +390,8 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
         if (Fc > 0) {
             verify_pending_categories();
             if (cat_clash_) { cat_clash_ = false; cat_items_.clear(); cat_tab_key_.clear(); cat_tab_id_.clear(); throw HipError("two different categories of one feature share a 64-bit hash: fit() refused"); }
-            if (!cat_codes_on_device)
-                throw Unsupported("fit(): the data set holds more distinct categories than Fc * n_bins (mean-gradient ranking of the whole data set is not implemented)");
+            if (!cat_codes_on_device)   // (the host scan: GBRL_HIP_HOST_CATEGORICAL=1, or the device scan declined -- more than 2^21 distinct cells)
+                throw Unsupported("fit(): the categorical candidates of the whole data set need the device scan (GBRL_HIP_HOST_CATEGORICAL=1, or more than 2^21 distinct categories)");
             fixed_cat_cands_ = cat_cands;
             fixed_cat_classes_ = cat_classes;
             fixed_cat_valid_ = true;
@@ -622,10 +622,23 @@ float Engine::fit(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
     for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(hs[d] / static_cast<double>(n));
     ++model.version;
 
-    // split candidates from the whole data set, once (fitter.cpp:134-150)
+    // split candidates from the whole data set, once (fitter.cpp:134-164)
     {
+        // Categorical columns: when the data set holds more distinct categories than Fc * n_bins the reference ranks them by the norms of
+        // `full_grads` (fitter.cpp:152-160) = predict_cpu(whole data set, trees [0, iterations)) - targets.  predict() restates that call's
+        // quirks (predictor.cpp:127-135): a fresh model, or iterations > n_trees, gives the bias alone; iterations == 0 means every tree.
+        const float *cand_grads = dtar;   // numeric-only: the gradients feed the (unused) statistics only
+        if (Fc > 0) {
+            float *fp = static_cast<float *>(d_fit_preds_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+            in_fit_ = true;
+            try { predict(dobs, true, dcat, true, n, F, Fc, 0, iterations, fp, true); } catch (...) { in_fit_ = false; throw; }
+            in_fit_ = false;
+            float *fg = static_cast<float *>(d_fit_grads_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+            kern::sub_arrays(fp, dtar, fg, static_cast<size_t>(n) * D, s);
+            cand_grads = fg;
+        }
         candidates_only_ = true;
-        step(dobs, true, dcat, true, dtar, true, n, F, Fc);   // returns right after the candidates; `dtar` only feeds the (unused) statistics
+        step(dobs, true, dcat, true, cand_grads, true, n, F, Fc);   // returns right after the candidates
         candidates_only_ = false;
     }
     const int bs = md.batch_size;

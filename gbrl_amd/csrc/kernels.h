@@ -523,9 +523,23 @@ void cat_distinct_insert(const char *cells, int n, int Fc, uint64_t *keys, int32
                          int32_t *counter, int list_cap, hipStream_t s);
 void cat_distinct_verify(const char *cells, int n, int Fc, const uint64_t *keys, const int32_t *first, int log2_cap, int32_t *flags,
                          hipStream_t s);
+// rank_count / rank_total (nullable, device): the ranking statistics of cat_rank, published as two more words per record (h_count, h_total);
+// h_names null: a second publish of records whose feature, first row, hash and cell have already arrived -- only the statistics travel.
 void cat_publish(int32_t *meta, const int32_t *list_slot, const uint64_t *keys, const int32_t *first, int log2_cap, const char *cells,
                  int Fc, int cap, int32_t *h_hdr, int32_t *h_feat, int32_t *h_first, uint64_t *h_hash, char *h_names, int32_t *slot_q,
-                 uint32_t seq, hipStream_t s);
+                 uint32_t seq, hipStream_t s, const int32_t *rank_count = nullptr, const float *rank_total = nullptr, int32_t *h_count = nullptr,
+                 float *h_total = nullptr);
+// cat_rank.hip: more distinct (feature, cell) pairs than candidates are kept -- per list record q of the scan above the number of rows that
+// carry it (count) and the float32 sum of their squared gradient norms in ascending row order from 0.0f (total), bit for bit the reference's
+// loop (split_candidate_generator.cpp:119-129).  n_q = records in the list (the host has read it from the published header); slot_q is
+// filled for all of them; meta[0] is set when a cell is not found in the tables.  Everything is enqueued on s, nothing is read back.
+bool cat_rank_fits(int N, int Fc);
+size_t cat_rank_scratch_bytes(int N, int Fc, int n_q);
+void cat_rank(const char *cells, int N, int Fc, const float *grads, int D, const uint64_t *keys, int log2_cap, int32_t *meta,
+              const int32_t *list_slot, int n_q, int32_t *slot_q, void *scratch, int32_t *count, float *total, hipStream_t s);
+// diagnostics: host arrays in, (feature, first row, count, total) of every distinct pair out; returns their number, -2: more than cap, -1: failed
+int cat_rank_selftest(const char *cells, int n, int Fc, const float *grads, int D, int cap, int32_t *feat, int32_t *first_row, int32_t *count,
+                      float *total);
 // class codes of a step batch from the scan's own tables: cls_of_q[slot_q[slot of the cell]] (see k_cat_step_codes_table)
 void cat_step_codes_table(const char *cells, int n, int Fc, int F, const uint64_t *keys, const int32_t *slot_q, const int32_t *cls_of_q,
                           int log2_cap, uint16_t *codes, hipStream_t s);

@@ -246,6 +246,15 @@ int gbrl_hip_replay_scores(const float *grads, const uint8_t *in_node, const uin
  * No reference counterpart (the reference IS the plain loop: node.cpp:336-352). */
 int gbrl_hip_seq_sums(const float *x, const uint32_t *lens, const float *starts, int n_chains, float *out, uint32_t *n_slow_blocks);
 
+/* Diagnostics for the tests: the ranking statistics of a batch's categorical cells as the device computes them when the batch holds more
+ * distinct (feature, cell) pairs than n_cat * n_bins (cat_rank.hip).  Host pointers: cells [n][n_cat][128] bytes, grads [n][output_dim].
+ * Per distinct pair, in no particular order: its feature, the first row that carries it, the number of rows that carry it and the float32
+ * sum of those rows' squared gradient norms in ascending row order from 0.0f -- the operands of the reference's mean
+ * (split_candidate_generator.cpp:119-137), bit for bit.  The four outputs hold `cap` entries; *n_distinct receives the number written.
+ * GBRL_HIP_E_INVALID when cap is too small (then *n_distinct is left at -1). */
+int gbrl_hip_cat_rank_stats(const char *cells, int n, int n_cat, const float *grads, int output_dim, int cap, int32_t *feature,
+                            int32_t *first_row, int32_t *count, float *total, int *n_distinct);
+
 /* ---- device / stream contract (new; the reference pins everything to device 0 and the null stream, cuda_types.cu:32-106) -- */
 /* The device the model computes on: the ordinal given at creation, or -- for -1 -- the calling thread's current device at the
  * first call that needs it (it is latched by this call too).  -1 when no HIP device is usable.  A caller that hands out
