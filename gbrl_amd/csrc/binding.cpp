@@ -172,27 +172,10 @@ class PyGBRL {
     }
 };
 
-py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object start_obj, py::object stop_obj,
-                        bool return_torch, const uint64_t *ids_token = nullptr /* non-null: `cat` holds int32 dictionary ids (predict_encoded) */) {
-    const gbrl_hip_metadata md = self.meta();
-    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
-    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
-    // bounds as binding.cpp:800-811
-    if (start < 0 || (start >= md.n_trees && md.n_trees > 0)) {
-        std::stringstream ss;
-        ss << "start_tree_idx is out of bounds! Got " << start << ", but valid range is [0, " << md.n_trees - 1 << "]";
-        fail(ss.str());
-    }
-    if (stop < 0 || stop > md.n_trees) {
-        std::stringstream ss;
-        ss << "stop_tree_idx is out of bounds! Got " << stop << ", but valid range is [0, " << md.n_trees << "]";
-        fail(ss.str());
-    }
-    Input o = read_input(obs, "obs", true, "predict", false);
-    Input c = read_input(cat, "cat_obs", true, "predict", ids_token ? 2 : 1);
-    if (!o.ptr && !c.ptr) fail("Cannot call predict without observations!");
+// rows, numeric and categorical feature counts of a predict batch: shape inference for 1-D inputs as binding.cpp:820-923
+struct BatchShape { int n, n_num, n_cat; };
+BatchShape infer_batch(const Input &o, const Input &c, int in_dim) {
     int n = 0, n_num = 0, n_cat = 0;
-    const int in_dim = md.input_dim;
     auto neq = [&](size_t a, size_t b) {
         if (a != b) {
             std::stringstream ss;
@@ -200,7 +183,6 @@ py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::obje
             fail(ss.str());
         }
     };
-    // shape inference for 1-D inputs as binding.cpp:820-923
     if (o.ptr && c.ptr) {
         if (o.shape.size() == 1 && c.shape.size() == 1) {
             if (static_cast<int>(o.shape[0] + c.shape[0]) == in_dim) { n = 1; n_num = static_cast<int>(o.shape[0]); n_cat = static_cast<int>(c.shape[0]); }
@@ -222,6 +204,30 @@ py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::obje
         ss << "Total number of features " << n_num + n_cat << " != input dim " << in_dim;
         fail(ss.str());
     }
+    return {n, n_num, n_cat};
+}
+
+py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object start_obj, py::object stop_obj,
+                        bool return_torch, const uint64_t *ids_token = nullptr /* non-null: `cat` holds int32 dictionary ids (predict_encoded) */) {
+    const gbrl_hip_metadata md = self.meta();
+    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
+    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    // bounds as binding.cpp:800-811
+    if (start < 0 || (start >= md.n_trees && md.n_trees > 0)) {
+        std::stringstream ss;
+        ss << "start_tree_idx is out of bounds! Got " << start << ", but valid range is [0, " << md.n_trees - 1 << "]";
+        fail(ss.str());
+    }
+    if (stop < 0 || stop > md.n_trees) {
+        std::stringstream ss;
+        ss << "stop_tree_idx is out of bounds! Got " << stop << ", but valid range is [0, " << md.n_trees << "]";
+        fail(ss.str());
+    }
+    Input o = read_input(obs, "obs", true, "predict", false);
+    Input c = read_input(cat, "cat_obs", true, "predict", ids_token ? 2 : 1);
+    if (!o.ptr && !c.ptr) fail("Cannot call predict without observations!");
+    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const int n = bs.n, n_num = bs.n_num, n_cat = bs.n_cat;
     const int D = md.output_dim;
     std::vector<int64_t> shape;
     if (D == 1) shape = {n}; else shape = {n, D};  // binding.cpp:281-286
@@ -254,6 +260,54 @@ py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::obje
     if (dev_out || return_torch) return make_dlpack(out, shape, dev_out, dev_id);
     py::capsule owner(out, [](void *p) { delete[] static_cast<float *>(p); });
     std::vector<py::ssize_t> shp(shape.begin(), shape.end());
+    return py::array_t<float>(shp, out, owner);
+}
+
+// Extension: predict_continue(obs, categorical_obs, base, start, stop) / predict_continue_encoded(obs, ids, token, base, start, stop): `base`, the
+// caller's prediction over the trees [0, start), carried through the trees [start, stop) (include/gbrl_hip.h).  A float32 NumPy `base` of shape
+// [n, D] ([n] when D == 1) is left untouched and a new array is returned; a (data_ptr, shape, "torch.float32", device) tuple is updated in place
+// and None is returned.
+py::object predict_continue_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &base, py::object start_obj, py::object stop_obj,
+                                 const uint64_t *ids_token = nullptr) {
+    const gbrl_hip_metadata md = self.meta();
+    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
+    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    Input o = read_input(obs, "obs", true, "predict_continue", false);
+    Input c = read_input(cat, "cat_obs", true, "predict_continue", ids_token ? 2 : 1);
+    if (!o.ptr && !c.ptr) fail("Cannot call predict_continue without observations!");
+    Input b = read_input(base, "base", false, "predict_continue", false);
+    if (!b.ptr) fail("Cannot call predict_continue without base!");
+    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const int n = bs.n, n_num = bs.n_num, n_cat = bs.n_cat, D = md.output_dim;
+    const bool shape_ok = (b.shape.size() == 2 && b.shape[0] == static_cast<size_t>(n) && b.shape[1] == static_cast<size_t>(D)) ||
+                          (b.shape.size() == 1 && D == 1 && b.shape[0] == static_cast<size_t>(n));
+    if (!shape_ok) {
+        std::stringstream ss;
+        ss << "Expected base of shape (" << n << ", " << D << ")" << (D == 1 ? " or (" + std::to_string(n) + ",)" : std::string()) << ", but got (";
+        for (size_t i = 0; i < b.shape.size(); ++i) ss << (i ? ", " : "") << b.shape[i];
+        ss << ")";
+        fail(ss.str());
+    }
+    const bool in_place = py::isinstance<py::tuple>(base);
+    float *out = in_place ? static_cast<float *>(const_cast<void *>(b.ptr)) : new float[static_cast<size_t>(n) * D];
+    const int out_dev = in_place && b.on_device;
+    int rc;
+    {
+        py::gil_scoped_release release;
+        if (ids_token)
+            rc = gbrl_hip_predict_continue_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device,
+                                                   *ids_token, n, n_num, n_cat, start, stop, static_cast<const float *>(b.ptr), b.on_device, out, out_dev);
+        else
+            rc = gbrl_hip_predict_continue(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, n_num,
+                                           n_cat, start, stop, static_cast<const float *>(b.ptr), b.on_device, out, out_dev);
+    }
+    if (rc != GBRL_HIP_OK) {
+        if (!in_place) delete[] out;
+        fail(gbrl_hip_last_error());
+    }
+    if (in_place) return py::none();
+    py::capsule owner(out, [](void *p) { delete[] static_cast<float *>(p); });
+    std::vector<py::ssize_t> shp(b.shape.begin(), b.shape.end());
     return py::array_t<float>(shp, out, owner);
 }
 
@@ -499,6 +553,14 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         return predict_impl(self, obs, ids, start, stop, return_torch, &token);
     }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0,
           py::arg("return_torch") = false);
+    // extension: a held prediction carried through the trees grown since (include/gbrl_hip.h)
+    g.def("predict_continue", [](PyGBRL &self, py::object &obs, py::object &cat, py::object &base, py::object start, py::object stop) {
+        return predict_continue_impl(self, obs, cat, base, start, stop);
+    }, py::arg("obs"), py::arg("categorical_obs"), py::arg("base"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0);
+    g.def("predict_continue_encoded", [](PyGBRL &self, py::object &obs, py::object &ids, uint64_t token, py::object &base, py::object start, py::object stop) {
+        return predict_continue_impl(self, obs, ids, base, start, stop, &token);
+    }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("base"), py::arg("start_tree_idx") = 0,
+          py::arg("stop_tree_idx") = 0);
     g.def("fit", &fit_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("iterations"),
           py::arg("shuffle") = true, py::arg("loss_type") = "MultiRMSE");
     g.def("set_bias", [](PyGBRL &self, py::object &bias) {

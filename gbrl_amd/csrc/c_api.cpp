@@ -352,6 +352,26 @@ int gbrl_hip_predict_encoded(gbrl_hip_model *m, const float *obs, int obs_on_dev
     });
 }
 
+int gbrl_hip_predict_continue(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device, int n_samples,
+                              int n_num_features, int n_cat_features, int start_tree, int stop_tree, const float *base, int base_on_device,
+                              float *out, int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.predict_continue(obs, obs_on_device != 0, cat_obs, cat_on_device != 0, n_samples, n_num_features, n_cat_features, start_tree,
+                                   stop_tree, base, base_on_device != 0, out, out_on_device != 0);
+    });
+}
+
+int gbrl_hip_predict_continue_encoded(gbrl_hip_model *m, const float *obs, int obs_on_device, const int32_t *cat_ids, int ids_on_device,
+                                      uint64_t dictionary_token, int n_samples, int n_num_features, int n_cat_features, int start_tree,
+                                      int stop_tree, const float *base, int base_on_device, float *out, int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.predict_continue_encoded(obs, obs_on_device != 0, cat_ids, ids_on_device != 0, dictionary_token, n_samples, n_num_features,
+                                           n_cat_features, start_tree, stop_tree, base, base_on_device != 0, out, out_on_device != 0);
+    });
+}
+
 int gbrl_hip_set_collective(gbrl_hip_model *m, const gbrl_hip_collective *hooks) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");

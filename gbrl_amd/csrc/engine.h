@@ -99,6 +99,15 @@ class Engine {
     void encode_categorical(const char *cat, bool cat_dev, int n, int n_cat, int32_t *ids_out, bool out_dev, uint64_t *token);
     void predict_encoded(const float *obs, bool obs_dev, const int32_t *cat_ids, bool ids_dev, uint64_t token, int n, int n_num, int n_cat,
                          int start_tree, int stop_tree, float *out, bool out_dev);
+    // Extension: continue a held prediction.  `base` [n][D] is the caller's prediction over the trees [0, start_tree); out[r][j] is base[r][j]
+    // carried through the trees [start_tree, stop_tree) in tree order -- p = fma(-lr_o(t), value, p) for every optimizer o that owns output j,
+    // lr_o(t) = scheduler_lr at the absolute tree index; an output no optimizer owns keeps its base value and the bias is never added -- so the
+    // result has the bits of one walk over [0, stop_tree).  Never sliced over tree ranges, at any batch size.  stop_tree == 0: n_trees;
+    // start_tree == stop_tree: out = base; start_tree > stop_tree or stop_tree > n_trees: InvalidArgument.  out == base is allowed.
+    void predict_continue(const float *obs, bool obs_dev, const char *cat, bool cat_dev, int n, int n_num, int n_cat, int start_tree,
+                          int stop_tree, const float *base, bool base_dev, float *out, bool out_dev);
+    void predict_continue_encoded(const float *obs, bool obs_dev, const int32_t *cat_ids, bool ids_dev, uint64_t token, int n, int n_num,
+                                  int n_cat, int start_tree, int stop_tree, const float *base, bool base_dev, float *out, bool out_dev);
     // GBRL::fit (gbrl.cpp:983-1104) + Fitter::fit_cpu (fitter.cpp:117-261): bias = mean(targets), split candidates from the
     // WHOLE data set once, then `iterations` boosting rounds over consecutive batches of metadata.batch_size rows
     // (predict -> MultiRMSE gradients -> one tree per batch); returns the final MultiRMSE loss on the whole data set.
@@ -126,8 +135,9 @@ class Engine {
     void ensure_device();
     void sync_model_to_device();
     int32_t *encode_categorical_batch(const char *cat, bool cat_dev, int n, int n_cat);
+    struct ContinueBase { const float *base; bool on_device; };   // predict_continue: the held prediction (nullptr in predict_core: an ordinary predict)
     void predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
-                      int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev);
+                      int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont = nullptr);
     uint64_t cat_dict_token();
     void grow_tree(const detail::GrowCtx &c, std::vector<detail::HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc,
                    double &leaf_scale);

@@ -438,8 +438,23 @@ void Engine::predict_encoded(const float *obs, bool obs_dev, const int32_t *cat_
     predict_core(obs, obs_dev, nullptr, false, cat_ids, ids_dev, &token, n, n_num, n_cat, start_tree, stop_tree, out, out_dev);
 }
 
+// Extension: `base` is the prediction over the trees [0, start_tree); `out` (which may be `base`) gets it carried through [start_tree, stop_tree).
+// See kern::predict_continue for the arithmetic.  Everything but the range rule and the kernel is predict_core's.
+void Engine::predict_continue(const float *obs, bool obs_dev, const char *cat, bool cat_dev, int n, int n_num, int n_cat, int start_tree,
+                              int stop_tree, const float *base, bool base_dev, float *out, bool out_dev) {
+    const ContinueBase cont{base, base_dev};
+    predict_core(obs, obs_dev, cat, cat_dev, nullptr, false, nullptr, n, n_num, n_cat, start_tree, stop_tree, out, out_dev, &cont);
+}
+
+void Engine::predict_continue_encoded(const float *obs, bool obs_dev, const int32_t *cat_ids, bool ids_dev, uint64_t token, int n, int n_num,
+                                      int n_cat, int start_tree, int stop_tree, const float *base, bool base_dev, float *out, bool out_dev) {
+    if (n_cat > 0 && cat_ids == nullptr) throw InvalidArgument("Cannot call predict without observations!");
+    const ContinueBase cont{base, base_dev};
+    predict_core(obs, obs_dev, nullptr, false, cat_ids, ids_dev, &token, n, n_num, n_cat, start_tree, stop_tree, out, out_dev, &cont);
+}
+
 void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
-                          int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev) {
+                          int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont) {
     gbrl_hip_metadata &md = model.meta;
     // GBRL::predict, gbrl.cpp:378-390
     if (md.iteration == 0) { md.n_num_features = n_num; md.n_cat_features = n_cat; }
@@ -450,6 +465,13 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     if (n_cat > 0 && cat == nullptr && cat_ids == nullptr) throw InvalidArgument("Cannot call predict without observations!");
     if (md.output_dim > 128) throw Unsupported("predict: output_dim > 128");
     if (start_tree < 0 || stop_tree < 0) throw InvalidArgument("invalid tree range");   // the reference would index out of bounds
+    if (cont != nullptr) {
+        // predict_continue has no reference behaviour to mirror: a range the ensemble does not hold is an error, never a silent no-op (a cache
+        // that is handed back unchanged is a stale prediction)
+        if (cont->base == nullptr) throw InvalidArgument("predict_continue: no base prediction");
+        const int resolved = stop_tree == 0 ? md.n_trees : stop_tree;
+        if (resolved > md.n_trees || start_tree > resolved) throw InvalidArgument("predict_continue: invalid tree range");
+    }
     ensure_device();
     ev_used_ = 0;
     ev_names_.clear();
@@ -457,10 +479,11 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     const int D = md.output_dim;
     // predict_cpu, predictor.cpp:127-141
     int stop = stop_tree;
-    if (md.n_trees == 0 || stop > md.n_trees || model.opts.empty()) { start_tree = 0; stop = 0; }
+    if (cont != nullptr) { if (stop == 0) stop = md.n_trees; }   // (validated above)
+    else if (md.n_trees == 0 || stop > md.n_trees || model.opts.empty()) { start_tree = 0; stop = 0; }
     else if (stop == 0) stop = md.n_trees;
     // an empty or inverted range walks no tree: predict_cpu's loops run from start to stop (predictor.cpp:139-163), the result is the bias
-    if (start_tree >= stop) { start_tree = 0; stop = 0; }
+    if (start_tree >= stop && cont == nullptr) { start_tree = 0; stop = 0; }
     sync_model_to_device();
     phase_begin();
     const float *dobs = obs;
@@ -484,6 +507,14 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     }
     float *dout = out;
     if (!out_dev) dout = static_cast<float *>(d_pout_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+    const float *dbase = nullptr;
+    if (cont != nullptr) {   // a base in host memory is copied into the output buffer and continued in place
+        dbase = cont->base;
+        if (!cont->on_device) {
+            hip_check(hipMemcpyAsync(dout, cont->base, sizeof(float) * static_cast<size_t>(n) * D, hipMemcpyHostToDevice, s), "H2D base");
+            dbase = dout;
+        }
+    }
     phase_end("inputs");
     phase_begin(/*key=*/true);
     kern::PredictModel pm{};
@@ -526,7 +557,7 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
         const char *no_pc = hooks::raw(hooks::PREDICT_NO_PC), *no_reg = hooks::raw(hooks::PREDICT_NO_REG), *mr = hooks::raw(hooks::PREDICT_REG_MIN_ROWS);
         const int min_rows = mr ? std::atoi(mr) : 32768;
         const bool fp32_takes_it = n_cat == 0 && n_num <= 128 && (n_num & 3) == 0 && (reinterpret_cast<uintptr_t>(dobs) & 15) == 0 && !(no_reg && no_reg[0] == '1');
-        if (!(no_pc && no_pc[0] == '1') && !in_fit_ && pm.values_sw != nullptr && model.oblivious() && n >= min_rows && !fp32_takes_it &&
+        if (cont == nullptr && !(no_pc && no_pc[0] == '1') && !in_fit_ && pm.values_sw != nullptr && model.oblivious() && n >= min_rows && !fp32_takes_it &&
             kern::predict_pc_shape_ok(pm.obl2_maxd, D) && ensure_pc_book(n_num, n_cat)) {
             pm.pc_cond = m_pc_cond_.as<int32_t>();
             pm.pc_thr = m_pc_thr_.as<float>();
@@ -559,6 +590,15 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     if (model.opts.size() > 255) pm.coef_ok = pm.coef_ok && !model.scheduled();   // (owner is a byte; D <= 64 bounds the optimizers of a covered model anyway)
     // Linear schedules: the kernels of predict_sched.hip read the rate of (tree, optimizer) from the mirror's table
     pm.rate = (model.scheduled() && md.n_trees > 0) ? m_rate_.as<float>() : nullptr;
+    if (cont != nullptr) {
+        kern::predict_continue(pm, dobs, n_num, dcat, n_cat, n, start_tree, stop, dbase, dout, hooks::on(hooks::CONTINUE_GENERIC), s);
+        hip_check(hipGetLastError(), "predict_continue launch");
+        phase_end("predict", /*key=*/true);
+        if (!out_dev) hip_check(hipMemcpyAsync(out, dout, sizeof(float) * static_cast<size_t>(n) * D, hipMemcpyDeviceToHost, s), "D2H preds");
+        hip_check(hipStreamSynchronize(s), "sync");
+        phases_resolve();
+        return;
+    }
     // small batches: scratch for up to 64 partial sums per output (tree ranges spread over blocks, kern::predict)
     pm.partial = nullptr; pm.partial_floats = 0; pm.tree_chunk = 0;
     // (not inside fit(): its gradients follow the reference's per-row tree-order chain at every batch size)

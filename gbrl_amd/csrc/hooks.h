@@ -13,6 +13,7 @@ namespace hooks {
     X(BIN_PLAIN) \
     X(CAT_CHECK) \
     X(CAT_PROF) \
+    X(CONTINUE_GENERIC) \
     X(DEVICE_LEVELS) \
     X(EVENT_RESULTS) \
     X(FORCE_BISECTION) \

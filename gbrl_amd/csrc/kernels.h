@@ -549,6 +549,12 @@ void encode_categories(const char *cells, int n, int Fc, const int32_t *feat_off
                        const uint64_t *dict_words, int32_t *codes, hipStream_t s);
 void predict(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree,
              int stop_tree, float *out, hipStream_t s);
+// Continue a held prediction (predict_continue.hip): out[r][j] = base[r][j] carried through the trees [start_tree, stop_tree) in tree order,
+// p = fma(-rate(t, o), value, p) for every optimizer o that owns output j; an output no optimizer owns keeps its base value, the bias is never
+// added.  ONE chain per (row, output) at every batch size and range length (no tree-range split, unlike kern::predict).  base and out are
+// device pointers and may be the same buffer.  generic: the one-thread-per-row kernel only (GBRL_HIP_CONTINUE_GENERIC=1).  Always launches.
+void predict_continue(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
+                      const float *base, float *out, bool generic, hipStream_t s);
 
 // ---- Linear TreeSHAP (shap.hip): a uniform program over explicit trees, one thread per (sample, output) ----
 enum { SHAP_ENTER = 0, SHAP_AFTER_LEFT = 1, SHAP_AFTER_RIGHT = 2, SHAP_EXIT = 3 };

@@ -166,6 +166,25 @@ int gbrl_hip_predict_encoded(gbrl_hip_model *m, const float *obs, int obs_on_dev
                              uint64_t dictionary_token, int n_samples, int n_num_features, int n_cat_features,
                              int start_tree, int stop_tree, float *out, int out_on_device);
 
+/* Extension (no counterpart in the reference, whose predict can only start from the bias): a training loop that keeps a batch resident and
+ * adds one tree per step holds the ensemble's output on that batch and applies only the trees grown since, instead of walking the whole
+ * ensemble again.  `base` is float32 [n_samples, output_dim], the caller's prediction over the trees [0, start_tree) -- for start_tree == 0
+ * the tiled bias.  out[r][j] is base[r][j] carried through the trees t = start_tree .. stop_tree - 1 in order: for every optimizer o with
+ * start_idx <= j < stop_idx, p = fma(-lr_o(t), leaf_value(r, t)[j], p), lr_o(t) the optimizer's scheduled rate at the ABSOLUTE tree index
+ * (Const and Linear).  An output that no optimizer owns keeps its base value, and the bias is never added: it is already in `base`.  The
+ * call never splits the range over partial sums, at any batch size or range length, so continuing gbrl_hip_predict's tree-order chain over
+ * [0, start_tree) gives the chain over [0, stop_tree) bit for bit.  stop_tree == 0 means n_trees; start_tree == stop_tree returns `base`
+ * unchanged; start_tree < 0, start_tree > stop_tree (after resolving 0) or stop_tree > n_trees fail with GBRL_HIP_E_INVALID (a silent no-op
+ * in a cache would be a stale prediction); output_dim > 128 is refused as in gbrl_hip_predict.  `out` may be `base` (in place: the expected
+ * use).  gbrl_hip_predict_continue_encoded takes the ids and token of gbrl_hip_encode_categorical in place of the cells; a stale token fails
+ * as in gbrl_hip_predict_encoded. */
+int gbrl_hip_predict_continue(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device,
+                              int n_samples, int n_num_features, int n_cat_features, int start_tree, int stop_tree,
+                              const float *base, int base_on_device, float *out, int out_on_device);
+int gbrl_hip_predict_continue_encoded(gbrl_hip_model *m, const float *obs, int obs_on_device, const int32_t *cat_ids, int ids_on_device,
+                                      uint64_t dictionary_token, int n_samples, int n_num_features, int n_cat_features,
+                                      int start_tree, int stop_tree, const float *base, int base_on_device, float *out, int out_on_device);
+
 /* ---- row-sharded multi-GPU (new; the reference is single-GPU) ------------------------------------------ */
 /* One process per GPU, each holding a contiguous block of rows.  When hooks are installed, step() calls them at
  * its exchange points so that every rank grows the identical tree; predict() needs no exchange.  Buffers are
