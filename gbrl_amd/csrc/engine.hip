@@ -71,7 +71,7 @@ void *DevBuf::ensure_keep(size_t bytes, size_t keep_bytes, hipStream_t s) {
 
 Engine::Engine(const gbrl_hip_config &cfg) : model(cfg), device_ordinal_(cfg.device_ordinal) {}
 Engine::Engine(Model &&loaded, int device_ordinal) : model(std::move(loaded)), device_ordinal_(device_ordinal) {}
-Engine::Engine(const Engine &o) : model(o.model), device_ordinal_(o.device_ordinal_) {}
+Engine::Engine(const Engine &o) : model(o.model), device_ordinal_(o.device_ordinal_), parity_(o.parity_) {}   // (a clone is never sharded: no hooks, no communicator)
 
 Engine::~Engine() {
     if (device_ready_) {
@@ -117,12 +117,32 @@ void Engine::set_stream(hipStream_t s) {
     stream_ = s ? s : own_stream_;
 }
 
+// The near-tie replay needs every row of a node on one GPU (neartie.hip walks them in ascending row order), so a row-sharded model
+// cannot promise the reference's choice at a near-tie: the two settings exclude each other, whichever comes second is refused.
+static const char *const kShardedParityMsg =
+    "parity mode \"reference\" is not available on a row-sharded model (collective hooks or an RCCL communicator): row-sharded runs hold the "
+    "exact arg-max; use \"default\" or \"exact_argmax\" there";
+
+void Engine::set_parity(ParityMode mode, int max_node_rows) {
+    if (mode != ParityMode::Default && mode != ParityMode::Reference && mode != ParityMode::ExactArgmax) throw InvalidArgument("invalid parity mode");
+    if (max_node_rows < 0) throw InvalidArgument("parity mode: max_node_rows must not be negative (0 = every node)");
+    if (mode == ParityMode::Reference && (has_coll_ || rccl_comm_)) throw Unsupported(kShardedParityMsg);
+    parity_.mode = mode;
+    parity_.max_node_rows = max_node_rows;
+}
+
+void Engine::refuse_sharding_in_reference_mode() const {
+    if (parity_.mode == ParityMode::Reference) throw Unsupported(kShardedParityMsg);
+}
+
 void Engine::set_collective(const gbrl_hip_collective *hooks) {
     // world_size 1 normally means "no exchange"; GBRL_HIP_FORCE_COLLECTIVE=1 keeps the hooks installed anyway so that the
     // sharded code path (hook calls, stream hand-over, no sibling subtraction, counting quantiles) can be tested on ONE GPU
     const char *force = gbrl::hooks::raw(gbrl::hooks::FORCE_COLLECTIVE);
+    const bool installs = hooks != nullptr && (hooks->world_size > 1 || (force && force[0] == '1'));
+    if (installs) refuse_sharding_in_reference_mode();   // (before anything changes: the model stays as it was)
     if (rccl_comm_ && rccl_api().ok) { (void)rccl_api().CommDestroy(rccl_comm_); rccl_comm_ = nullptr; }
-    if (hooks == nullptr || (hooks->world_size <= 1 && !(force && force[0] == '1'))) {
+    if (!installs) {
         has_coll_ = false;
         return;
     }
@@ -133,6 +153,7 @@ void Engine::set_collective(const gbrl_hip_collective *hooks) {
 }
 
 void Engine::set_rccl(const void *id128, int world_size, int rank, bool keep_world1) {
+    refuse_sharding_in_reference_mode();   // (before the collective CommInitRank: every rank of a uniformly configured job refuses)
     const RcclApi &api = rccl_api();
     if (!api.ok) throw Unsupported("RCCL is not available in this process");
     if (world_size < 1 || rank < 0 || rank >= world_size || id128 == nullptr) throw InvalidArgument("invalid RCCL communicator arguments");

@@ -6,7 +6,7 @@
 namespace gbrl {
 namespace detail {
 
-GrowDims::GrowDims(const GrowCtx &c, bool has_coll, int world_size, int rank) {
+GrowDims::GrowDims(const GrowCtx &c, bool has_coll, int world_size, int rank, Engine::Parity parity) {
     const int N = c.N, D = c.D, MD = c.MD, NB = c.NB, Fp = c.Fp;
     max_front = 1 << std::max(0, MD - 1);
     max_nodes = 2 * (1 << MD);
@@ -32,8 +32,14 @@ GrowDims::GrowDims(const GrowCtx &c, bool has_coll, int world_size, int rank) {
     res_bytes = ResultBlock::bytes(max_front);
     const char *rel_env = hooks::raw(hooks::NEARTIE_REL), *max_env = hooks::raw(hooks::NEARTIE_MAX_ROWS);
     near_rel = rel_env ? static_cast<float>(std::atof(rel_env)) : 9.5367431640625e-07f;
-    near_max_rows = N <= kern::kNearMaxRows ? 0 : (max_env ? std::max(0, std::atoi(max_env)) : -1);
-    near_on = !hooks::on(hooks::NO_NEARTIE_REPLAY) && !has_coll && c.n_global == N && c.n_cand > 0 && kern::near_tie_supported(N, D) && near_max_rows >= 0;
+    // The model's parity setting, then the two hooks over it: each hook that is set does exactly what it did before the setting existed.
+    Engine::ParityMode mode = parity.mode;
+    int limit = parity.max_node_rows;
+    if (max_env && N > kern::kNearMaxRows) { mode = Engine::ParityMode::Reference; limit = std::max(0, std::atoi(max_env)); }
+    if (hooks::on(hooks::NO_NEARTIE_REPLAY)) mode = Engine::ParityMode::ExactArgmax;
+    near_max_rows = N <= kern::kNearMaxRows ? 0 : (mode == Engine::ParityMode::Reference ? limit : -1);
+    near_on = mode != Engine::ParityMode::ExactArgmax && !has_coll && c.n_global == N && c.n_cand > 0 && kern::near_tie_supported(N, D) && near_max_rows >= 0;
+    reference_asked = parity.mode == Engine::ParityMode::Reference && mode == Engine::ParityMode::Reference;
     event_results = hooks::on(hooks::EVENT_RESULTS);
 }
 
@@ -228,7 +234,14 @@ using namespace detail;
 // ---- the tree of one step: on return `nodes` is the tree, `frontier` the unsplit nodes of the last level, acc the per-node int64
 // fixed-point sums of the raw gradients (| count) and leaf_scale their scale.
 void Engine::grow_tree(const GrowCtx &c, std::vector<HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc, double &leaf_scale) {
-    const GrowDims dims(c, has_coll_, coll_.world_size, coll_.rank);
+    const GrowDims dims(c, has_coll_, coll_.world_size, coll_.rank, parity_);
+    if (dims.reference_asked && c.n_cand > 0) {
+        // "reference" is a promise about the result, so a step that cannot replay says so instead of growing the exact arg-max's tree quietly.
+        // Nothing has been booked yet: the model is as it was before the call.
+        if (!dims.near_on) throw Unsupported("parity mode \"reference\": the near-tie replay does not support this shape (at most 2^30 rows, output_dim <= 1024)");
+        if (dims.event_results) throw Unsupported("parity mode \"reference\": GBRL_HIP_EVENT_RESULTS=1 reads the level results without the near-tie replay; unset it or use another parity mode");
+        if (c.oblivious && device_levels_requested()) throw Unsupported("parity mode \"reference\": GBRL_HIP_DEVICE_LEVELS=1 grows oblivious trees without the near-tie replay; unset it or use another parity mode");
+    }
     const StepTables tables = upload_step_tables(c, dims);
     TreeBuilder tb(c, has_coll_, nodes, frontier);
     // RL-sized steps on one GPU grow the whole tree in ONE launch (kern::small_grow, small_grow.hip): no level buffers, no partials,

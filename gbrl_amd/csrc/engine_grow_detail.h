@@ -9,7 +9,7 @@ namespace detail {
 
 // Per-tree constants derived from the step's context, computed once by grow_tree and read-only afterwards.
 struct GrowDims {
-    GrowDims(const GrowCtx &c, bool has_coll, int world_size, int rank);
+    GrowDims(const GrowCtx &c, bool has_coll, int world_size, int rank, Engine::Parity parity);
     int max_front, max_nodes, max_chunks;
     bool l2_degenerate;      // L2 with ONE row: the reference's unbiased variance is 0/0 (math_ops.cpp:461-513), every standardised gradient and
                              // every split score is NaN, no comparison succeeds and the tree stays a depth-0 leaf (fitter.cpp:357, :458)
@@ -39,9 +39,15 @@ struct GrowDims {
     // replay's chains are serial (a 2^20-row level costs 10-100 ms against a 1.85 ms step: profiles/r06_neartie_fullsize_cost.txt), so those
     // batches replay only on request -- GBRL_HIP_NEARTIE_MAX_ROWS=<n>: nodes of up to n rows (0: every node).  Unset: the exact arg-max, as in
     // rounds 1-5.  Batches of up to 65 536 rows replay every flagged node as before.
+    // The model's parity setting (Engine::Parity, gbrl_hip_set_parity_mode) says the same per model: "reference" = GBRL_HIP_NEARTIE_MAX_ROWS=
+    // <max_node_rows>, "exact_argmax" = GBRL_HIP_NO_NEARTIE_REPLAY=1, "default" = neither.  A hook that is set overrides the setting and does
+    // what it always did: NO_NEARTIE_REPLAY turns the replay off whatever the mode, NEARTIE_MAX_ROWS turns it on with its limit for batches
+    // above 65 536 rows whatever the mode (NO_NEARTIE_REPLAY wins over it).  near_on and near_max_rows are the ONLY outcome of all three:
+    // every growth path (one-launch kernel, level loop; step() and fit()) reads them and nothing else.
     bool near_on;
     float near_rel;          // 2^-20 unless GBRL_HIP_NEARTIE_REL (measurement hook) says otherwise
     int near_max_rows;       // 0: no limit, -1: no replay
+    bool reference_asked;    // the model's own setting is "reference" and GBRL_HIP_NO_NEARTIE_REPLAY does not override it: grow_tree refuses the paths that cannot replay
     bool event_results;      // GBRL_HIP_EVENT_RESULTS=1 (measurement hook): results through the copy engine and an event
 };
 

@@ -127,6 +127,36 @@ int gbrl_hip_get_ensemble(const gbrl_hip_model *m,
                           uint8_t *inequality_directions /*[L*md]*/, char *categorical_values /*[S*md*128]*/,
                           int32_t *reverse_num_feature_mapping /*[in]*/, int32_t *reverse_cat_feature_mapping /*[in]*/);
 
+/* ---- parity mode (new; the reference IS the reference) --------------------------------------------------------------- */
+/* The contract is "tree structure bit-identical to the CPU reference".  Where the exact (float64) arg-max of a node has a runner-up inside
+ * the reference's float32 summation noise, the reference's own rounding decides which candidate wins; the near-tie replay (csrc/neartie.hip)
+ * re-scores such candidates in the reference's float32 operation sequence and takes its choice.  The replay costs time on large batches
+ * (DESIGN.md section 3a), so WHERE it runs is a setting of the model:
+ *   GBRL_HIP_PARITY_DEFAULT       replay for batches of up to 65 536 rows on one GPU, the exact arg-max above.
+ *   GBRL_HIP_PARITY_REFERENCE     replay at every batch size.  max_node_rows > 0: in batches above 65 536 rows only nodes of up to that many
+ *                                 rows are replayed (an oblivious level: when all of its nodes are that small), larger nodes keep the exact
+ *                                 arg-max; 0: every node.  Batches of up to 65 536 rows replay every flagged node whatever the limit.
+ *   GBRL_HIP_PARITY_EXACT_ARGMAX  never replay: the exact arg-max decides everywhere.
+ * max_node_rows is stored with every mode and read in REFERENCE only; negative values and unknown modes fail with GBRL_HIP_E_INVALID.
+ * The setting holds for step() and fit(), on every growth path.  A new model is DEFAULT.  gbrl_hip_clone carries the setting.
+ * gbrl_hip_save / gbrl_hip_load do NOT: the .gbrl_model format is the reference's and stays byte-compatible, so a loaded model is DEFAULT
+ * (max_node_rows 0) and the caller sets the mode again.
+ * Row-sharded models cannot replay (a node's rows are spread over the ranks), they hold the exact arg-max: REFERENCE on a model with
+ * collective hooks or an RCCL communicator fails with GBRL_HIP_E_UNSUPPORTED, and so do gbrl_hip_set_collective / gbrl_hip_set_rccl* on a
+ * model in REFERENCE mode; DEFAULT and EXACT_ARGMAX are accepted there and both mean the exact arg-max.  In REFERENCE mode a step that
+ * cannot replay fails with GBRL_HIP_E_UNSUPPORTED instead of growing another tree quietly (GBRL_HIP_DEVICE_LEVELS=1 on oblivious trees,
+ * GBRL_HIP_EVENT_RESULTS=1, output_dim > 1024); the model is left unchanged.
+ * Environment hooks override the setting, exactly as they behaved before it existed: GBRL_HIP_NO_NEARTIE_REPLAY=1
+ * turns the replay off in every mode; GBRL_HIP_NEARTIE_MAX_ROWS=<n> turns it on for batches above 65 536 rows with limit n in every mode
+ * (GBRL_HIP_NO_NEARTIE_REPLAY wins over it).  The getter reports the model's setting, not what a hook makes of it. */
+typedef enum {
+    GBRL_HIP_PARITY_DEFAULT = 0,
+    GBRL_HIP_PARITY_REFERENCE = 1,
+    GBRL_HIP_PARITY_EXACT_ARGMAX = 2
+} gbrl_hip_parity_mode;
+int gbrl_hip_set_parity_mode(gbrl_hip_model *m, int mode /* gbrl_hip_parity_mode */, int max_node_rows);
+int gbrl_hip_get_parity_mode(const gbrl_hip_model *m, int *mode, int *max_node_rows);   /* either pointer may be NULL */
+
 /* ---- THE HOT PATH ------------------------------------------------------------------------------------- */
 /* GBRL::step (gbrl.cpp:939-981) == Fitter::step_cpu semantics (fitter.cpp:50-115), computed on the GPU:
  * fits ONE tree to `grads` and appends it to the ensemble.
@@ -189,8 +219,11 @@ int gbrl_hip_predict_continue_encoded(gbrl_hip_model *m, const float *obs, int o
 /* One process per GPU, each holding a contiguous block of rows.  When hooks are installed, step() calls them at
  * its exchange points so that every rank grows the identical tree; predict() needs no exchange.  Buffers are
  * DEVICE pointers; the hook must return only after the reduced result is visible on the HIP null stream
- * ordering used by the model.  sum hooks are exact (integers), so 1/2/4/8-GPU trees are
- * bit-identical.  Install NULL hooks to go back to single-GPU. */
+ * ordering used by the model.  sum hooks are exact (integers), so the trees of 2/4/8-GPU runs are
+ * bit-identical to each other.  Against a ONE-GPU model they are bit-identical when that model holds the exact arg-max too:
+ * always for batches above 65 536 rows in GBRL_HIP_PARITY_DEFAULT, and for batches of up to 65 536 rows only against a one-GPU
+ * model in GBRL_HIP_PARITY_EXACT_ARGMAX (the one-GPU default replays near-ties there, a row-sharded run cannot).  Install NULL
+ * hooks to go back to single-GPU.  Refused (GBRL_HIP_E_UNSUPPORTED) on a model in GBRL_HIP_PARITY_REFERENCE, see above. */
 typedef struct {
     void *ctx;
     int world_size, rank;
