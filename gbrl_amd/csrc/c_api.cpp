@@ -514,6 +514,11 @@ int gbrl_hip_seq_sums(const float *x, const uint32_t *lens, const float *starts,
     });
 }
 
+int gbrl_hip_seq_sums_model(const float *x, const uint32_t *lens, const float *starts, int n_chains, float *out, uint32_t *n_slow_blocks, uint32_t *n_fast_blocks) {
+    if (!lens || !out || n_chains < 0) return GBRL_HIP_E_INVALID;
+    return guarded([&] { (void)gbrl::kern::seq_sums_model(x, lens, starts, n_chains, out, n_slow_blocks, n_fast_blocks); });
+}
+
 int gbrl_hip_cat_rank_stats(const char *cells, int n, int n_cat, const float *grads, int output_dim, int cap, int32_t *feature,
                             int32_t *first_row, int32_t *count, float *total, int *n_distinct) {
     if (!cells || !grads || !feature || !first_row || !count || !total || !n_distinct || n < 1 || n_cat < 1 || output_dim < 1 || cap < 1) return GBRL_HIP_E_INVALID;

@@ -340,6 +340,8 @@ struct SeqChain { const float *x; uint32_t len; uint32_t blk0; float start; };  
 size_t seq_sums_scratch_bytes(uint32_t n_blocks);
 void seq_sums(const SeqChain *d_chains, int n_chains, uint32_t n_blocks, void *d_scratch, float *d_out, uint32_t *d_n_slow /*nullable*/, hipStream_t s);
 bool seq_sums_selftest(const float *x, const uint32_t *lens, const float *starts /*nullable*/, int n_chains, float *out, uint32_t *n_slow_out /*nullable*/);
+// diagnostics (gbrl_hip_seq_sums_model): the same chains walked on the CPU with the arithmetic of seqsum_core.h, the kernels' decisions in the kernels' order; no HIP call
+bool seq_sums_model(const float *x, const uint32_t *lens, const float *starts /*nullable*/, int n_chains, float *out, uint32_t *n_slow_out /*nullable*/, uint32_t *n_fast_out /*nullable*/);
 
 // rows going right per node for the chosen splits (row-sharded runs: local child sizes without a local histogram)
 void localize_splits(NodeSplit *splits, const int32_t *n_local, const int64_t *right_local, int n_nodes, hipStream_t s);

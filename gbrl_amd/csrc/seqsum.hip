@@ -10,13 +10,20 @@
 //   1. k_seq_blocksum  : fp64 sum of every block of 256 elements                      (all CUs)
 //   2. k_seq_prefix    : per chain, exclusive fp64 prefix over its blocks -> the running sum every block starts from, to ~1e-16
 //   3. k_seq_summary   : per block, the summary under the exponent that prefix predicts (all CUs)
-//   4. k_seq_stitch    : one wave per chain walks the summaries in order: when the TRUE running sum has the predicted exponent and
-//                        A0 + min_p .. A0 + max_p stay inside the binade (same sign), the block is applied in O(1); otherwise the block's 256
-//                        elements are added one by one (the start of a chain, a crossing of a power of two, a cancellation).
+//   4. k_seq_stitch    : one wave per chain walks the summaries in order: when the TRUE running sum has the predicted exponent and both it
+//                        and every partial sum A0 + min_p .. A0 + max_p lie strictly between 2^23 and 2^24 (same sign) -- the OPEN binade:
+//                        just below a power of two the spacing is u / 2, so a sum that starts on one or touches it rounds the next small
+//                        opposite-sign element differently from the model (seq_apply, seqsum_core.h) -- the block is applied in O(1);
+//                        otherwise the block's 256 elements are added one by one (the start of a chain, a power of two touched or
+//                        crossed, a cancellation).
 // The result never depends on a prediction being right -- a wrong one only costs the serial fallback for that block.
-// Prototype with the same arithmetic: scripts/experiments/seqsum_prototype.py (300 random chains against the plain loop, ties included).
+// The arithmetic (seq_element, seq_one, seq_compose, seq_apply) lives in seqsum_core.h and compiles for the host as well: seq_sums_model below
+// walks whole chains with it on the CPU, decision by decision as the kernels do (gbrl_hip_seq_sums_model; tests/test_seqsum_host.py puts
+// running sums exactly on powers of two, on (2^24 - 1) u and on zero, where random chains never land).
+// Prototype with the same arithmetic: scripts/experiments/seqsum_prototype.py (300 random chains and constructed binade edges against the plain loop).
 #include "kernels.h"
 #include "kernels_common.h"
+#include "seqsum_core.h"
 
 #include <algorithm>
 #include <vector>
@@ -28,58 +35,6 @@ namespace kern {
 
 namespace {
 
-constexpr int kSeqBlock = 256;            // elements per summary (one wave, four per lane)
-constexpr int kSeqBig = 1 << 28;          // clamp of a summary's fields (anything beyond 2^25 already fails the binade check; two clamped values add without overflow)
-
-struct SeqSumm { int d[2], lo[2], hi[2]; };   // per starting parity: total change, least and greatest partial sum (relative to the start, after >= 1 element)
-
-__device__ __forceinline__ int seq_clamp(int v) { return max(-kSeqBig, min(kSeqBig, v)); }
-
-// one element under ulp exponent e (u = 2^(e - 23)): f = floor(x / u), h = 0 (fraction below a half) | 1 (above) | 2 (tie); false: not summarisable.
-// An element whose exponent reaches the running sum's (k <= 0) always takes the sum out of its binade (same sign: beyond 2^(e+1); opposite: below
-// 2^e or through zero), so it is not summarisable by definition -- which keeps every quantity inside 32 bits (|f| < 2^23).
-__device__ __forceinline__ bool seq_element(float x, int e, int &f, int &h) {
-    const uint32_t b = __float_as_uint(x);
-    const int ex = static_cast<int>((b >> 23) & 0xffu);
-    if (ex == 0xff) return false;                               // inf / nan: the serial loop decides
-    const int m = ex ? static_cast<int>((b & 0x7fffffu) | 0x800000u) : static_cast<int>(b & 0x7fffffu);
-    const int sm = (b >> 31) ? -m : m;                          // x = sm * 2^(ee - 23)
-    const int ee = ex ? ex - 127 : -126;
-    const int k = e - ee;
-    if (k <= 0) return false;
-    if (k >= 25) {                                              // |x| < u / 2: positive rounds away, negative floors to -1 and rounds back up
-        f = sm < 0 ? -1 : 0; h = sm < 0 ? 1 : 0;
-        return true;
-    }
-    f = sm >> k;                                                // arithmetic shift = floor
-    const int rem = sm - (f << k), half = 1 << (k - 1);
-    h = rem < half ? 0 : (rem > half ? 1 : 2);
-    return true;
-}
-__device__ __forceinline__ SeqSumm seq_one(int f, int h) {
-    SeqSumm s;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        int t = f;
-        if (h == 1) t += 1;
-        else if (h == 2) t += (p + f) & 1;
-        s.d[p] = t; s.lo[p] = t; s.hi[p] = t;
-    }
-    return s;
-}
-// a, then b
-__device__ __forceinline__ SeqSumm seq_compose(const SeqSumm &a, const SeqSumm &b) {
-    SeqSumm r;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const int d = a.d[p];
-        const int q = (p + d) & 1;
-        r.d[p] = seq_clamp(d + b.d[q]);
-        r.lo[p] = seq_clamp(min(a.lo[p], d + b.lo[q]));
-        r.hi[p] = seq_clamp(max(a.hi[p], d + b.hi[q]));
-    }
-    return r;
-}
 __device__ __forceinline__ long long seq_shfl_xor(long long v, int o) {
     const int lo = __shfl_xor(static_cast<int>(v & 0xffffffffll), o, kWave), hi = __shfl_xor(static_cast<int>(v >> 32), o, kWave);
     return (static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo);
@@ -92,7 +47,7 @@ __device__ __forceinline__ int seq_chain_of(const SeqChain *__restrict__ chains,
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (chains[mid].blk0 <= b) lo = mid; else hi = mid - 1; }
     return lo;
 }
-// the block's elements, four consecutive ones per lane (zeros beyond the chain's end: x + 0 = x)
+// the block's elements, four consecutive ones per lane (-0.0f beyond the chain's end: x + -0.0f = x for EVERY x; +0.0f would turn a sum of -0.0f into +0.0f)
 __device__ __forceinline__ void seq_load(const SeqChain &c, uint32_t lb, int lane, float (&v)[4]) {
     const uint32_t i0 = lb * kSeqBlock + 4u * lane;
     if (i0 + 4 <= c.len && (reinterpret_cast<uintptr_t>(c.x + i0) & 15) == 0) {
@@ -100,7 +55,7 @@ __device__ __forceinline__ void seq_load(const SeqChain &c, uint32_t lb, int lan
         v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
     } else {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) v[u] = i0 + u < c.len ? c.x[i0 + u] : 0.0f;
+        for (int u = 0; u < 4; ++u) v[u] = i0 + u < c.len ? c.x[i0 + u] : -0.0f;
     }
 }
 
@@ -151,7 +106,7 @@ __global__ __launch_bounds__(256) void k_seq_summary(const SeqChain *__restrict_
     const SeqChain c = chains[ci];
     if (b - c.blk0 >= (c.len + kSeqBlock - 1) / kSeqBlock) return;
     const float start = static_cast<float>(static_cast<double>(c.start) + blk[b]);   // the running sum this block will (very nearly) start from
-    const uint32_t sb = __float_as_uint(start);
+    const uint32_t sb = seq_bits(start);
     const int sex = static_cast<int>((sb >> 23) & 0xffu);
     int e = -1000;
     if (sex > 20 && sex < 235) e = sex - 127;                     // normal, away from the ends of the range
@@ -188,24 +143,10 @@ __global__ __launch_bounds__(256) void k_seq_summary(const SeqChain *__restrict_
     }
 }
 
-// Does the running sum s (normal, exponent e) stay inside its binade through a run summarised by (d, lo, hi)[parity]?  If so apply it.
-__device__ __forceinline__ bool seq_apply(float &s, int e, int d0, int d1, int lo0, int lo1, int hi0, int hi1) {
-    const uint32_t sb = __float_as_uint(s);
-    if (static_cast<int>((sb >> 23) & 0xffu) - 127 != e) return false;
-    const int m = static_cast<int>((sb & 0x7fffffu) | 0x800000u);
-    const int A0 = (sb >> 31) ? -m : m;
-    const bool odd = (A0 & 1) != 0;
-    const int d = odd ? d1 : d0, lo = odd ? lo1 : lo0, hi = odd ? hi1 : hi0;
-    const bool ok = A0 > 0 ? (A0 + lo >= (1 << 23) && A0 + hi < (1 << 24)) : (A0 + hi <= -(1 << 23) && A0 + lo > -(1 << 24));
-    if (ok) s = ldexpf(static_cast<float>(A0 + d), e - 23);     // exact: |A0 + d| < 2^24
-    return ok;
-}
-
 // one wave per chain; every lane carries the same running sum (the control flow is wave-uniform).  Two levels: the summaries of 16 consecutive
 // blocks formed under ONE exponent are composed (they are the same kind of function) and tried first -- a chain that drifts away from zero (a
 // dot chain, a column with a mean) crosses a power of two a few dozen times in 2^20 elements and takes 4096 elements per step in between; a
 // group that fails is walked block by block, a block that fails element by element.
-constexpr int kSeqGroup = 16;
 __global__ __launch_bounds__(64) void k_seq_stitch(const SeqChain *__restrict__ chains, int n_chains, uint32_t n_blocks, const int32_t *__restrict__ planes,
                                                    const int32_t *__restrict__ expo, float *__restrict__ out, uint32_t *__restrict__ n_slow /*nullable: blocks added one by one*/) {
     const int ci = blockIdx.x, lane = threadIdx.x;
@@ -312,6 +253,90 @@ bool seq_sums_selftest(const float *x, const uint32_t *lens, const float *starts
     if (hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return false; }
     if (hipMemcpy(out, dout.p, sizeof(float) * n_chains, hipMemcpyDeviceToHost) != hipSuccess) return false;
     if (n_slow_out && hipMemcpy(n_slow_out, dslow.p, 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    return true;
+}
+
+// diagnostics (gbrl_hip_seq_sums_model): what the four kernels compute, on the CPU and without any HIP call -- the same functions of
+// seqsum_core.h, the same decisions in the same order: fp64 block sums (four elements per lane left to right, the lanes as a balanced tree),
+// their exclusive prefix in scans of 64 blocks, the block summaries under the exponent float(start + prefix) has (elements composed four per
+// lane, the lanes as a balanced tree), and k_seq_stitch's walk: the composed summary of 16 blocks under one exponent first, then block by
+// block, then element by element.  n_slow = blocks added element by element, n_fast = blocks a summary applied.
+bool seq_sums_model(const float *x, const uint32_t *lens, const float *starts, int n_chains, float *out, uint32_t *n_slow_out, uint32_t *n_fast_out) {
+    uint32_t slow = 0, fast = 0;
+    size_t off = 0;
+    std::vector<double> pre;
+    std::vector<SeqSumm> summ;
+    std::vector<int> expo;
+    const SeqSumm ident{{0, 0}, {kSeqBig, kSeqBig}, {-kSeqBig, -kSeqBig}};
+    for (int ci = 0; ci < n_chains; ++ci) {
+        const float *cx = x + off;
+        const uint32_t len = lens[ci], nb = (len + kSeqBlock - 1) / kSeqBlock;
+        const float start = starts ? starts[ci] : 0.0f;
+        off += len;
+        auto at = [&](uint32_t i) { return i < len ? cx[i] : -0.0f; };          // seq_load: -0.0f behind the chain's end
+        pre.assign(nb, 0.0); summ.assign(nb, ident); expo.assign(nb, -1000);
+        for (uint32_t b = 0; b < nb; ++b) {                                    // k_seq_blocksum
+            double l[kWave];
+            for (int lane = 0; lane < kWave; ++lane) {
+                const uint32_t i0 = b * kSeqBlock + 4u * lane;
+                l[lane] = i0 < len ? ((static_cast<double>(at(i0)) + static_cast<double>(at(i0 + 1))) + static_cast<double>(at(i0 + 2))) + static_cast<double>(at(i0 + 3)) : -0.0;
+            }
+            for (int o = 1; o < kWave; o <<= 1) for (int i = 0; i < kWave; i += 2 * o) l[i] += l[i + o];
+            pre[b] = l[0];
+        }
+        double run = 0.0;
+        for (uint32_t b0 = 0; b0 < nb; b0 += kWave) {                          // k_seq_prefix
+            double mine[kWave], incl[kWave];
+            for (int lane = 0; lane < kWave; ++lane) incl[lane] = mine[lane] = b0 + lane < nb ? pre[b0 + lane] : 0.0;
+            for (int o = 1; o < kWave; o <<= 1) for (int lane = kWave - 1; lane >= o; --lane) incl[lane] += incl[lane - o];
+            for (int lane = 0; lane < kWave && b0 + lane < nb; ++lane) pre[b0 + lane] = run + (incl[lane] - mine[lane]);
+            run += incl[kWave - 1];
+        }
+        for (uint32_t b = 0; b < nb; ++b) {                                    // k_seq_summary
+            const int sex = static_cast<int>((seq_bits(static_cast<float>(static_cast<double>(start) + pre[b])) >> 23) & 0xffu);
+            if (!(sex > 20 && sex < 235)) continue;
+            const int e = sex - 127;
+            SeqSumm l[kWave];
+            bool ok = true;
+            for (int lane = 0; lane < kWave && ok; ++lane) {
+                const uint32_t i0 = b * kSeqBlock + 4u * lane;
+                if (lane > 0 && i0 - 4u >= len) { l[lane] = l[lane - 1]; continue; }   // (this lane and the one before it wholly behind the chain's end: the same four -0.0f)
+                for (int u = 0; u < 4 && ok; ++u) {
+                    int f, h;
+                    ok = seq_element(at(i0 + u), e, f, h);
+                    if (ok) l[lane] = u ? seq_compose(l[lane], seq_one(seq_clamp(f), h)) : seq_one(seq_clamp(f), h);
+                }
+            }
+            if (!ok) continue;
+            for (int o = 1; o < kWave; o <<= 1) for (int i = 0; i < kWave; i += 2 * o) l[i] = seq_compose(l[i], l[i + o]);
+            summ[b] = l[0]; expo[b] = e;
+        }
+        float s = start;                                                       // k_seq_stitch
+        for (uint32_t b0 = 0; b0 < nb; b0 += kWave) {
+            const int cnt = static_cast<int>(std::min(static_cast<uint32_t>(kWave), nb - b0));
+            for (int g0 = 0; g0 < cnt; g0 += kSeqGroup) {
+                const int g1 = std::min(cnt, g0 + kSeqGroup);
+                SeqSumm grp[kSeqGroup];
+                bool g_ok = true;
+                for (int j = 0; j < kSeqGroup; ++j) {                          // (beyond the chain's end: the identity under the last block's exponent)
+                    grp[j] = g0 + j < cnt ? summ[b0 + g0 + j] : ident;
+                    const int ej = expo[b0 + std::min(g0 + j, cnt - 1)];
+                    g_ok = g_ok && ej != -1000 && ej == expo[b0 + g0];
+                }
+                for (int o = 1; o < kSeqGroup; o <<= 1) for (int i = 0; i < kSeqGroup; i += 2 * o) grp[i] = seq_compose(grp[i], grp[i + o]);
+                if (g_ok && seq_apply(s, expo[b0 + g0], grp[0])) { fast += static_cast<uint32_t>(g1 - g0); continue; }
+                for (int j = g0; j < g1; ++j) {
+                    const uint32_t b = b0 + j;
+                    if (expo[b] != -1000 && seq_apply(s, expo[b], summ[b])) { ++fast; continue; }
+                    ++slow;
+                    for (uint32_t i = b * kSeqBlock; i < (b + 1) * kSeqBlock; ++i) s = s + at(i);    // (all 256, as the wave does: what stands behind the chain's end is added too)
+                }
+            }
+        }
+        out[ci] = s;
+    }
+    if (n_slow_out) *n_slow_out = slow;
+    if (n_fast_out) *n_fast_out = fast;
     return true;
 }
 

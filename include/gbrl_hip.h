@@ -297,6 +297,13 @@ int gbrl_hip_replay_scores(const float *grads, const uint8_t *in_node, const uin
  * loop bit for bit.  Host pointers; starts nullable (zeros); n_slow_blocks nullable: how many 256-element blocks took the serial fallback.
  * No reference counterpart (the reference IS the plain loop: node.cpp:336-352). */
 int gbrl_hip_seq_sums(const float *x, const uint32_t *lens, const float *starts, int n_chains, float *out, uint32_t *n_slow_blocks);
+/* Diagnostics for the tests: the same sums evaluated on the CPU by the arithmetic the kernels are compiled from (csrc/seqsum_core.h), walking
+ * every chain as the kernels do -- exponent predicted from the fp64 prefix of the 256-element block sums plus the start, summaries composed
+ * from single elements, 16 blocks under one exponent tried first, then block by block, then element by element.  No HIP call: it runs without
+ * a device.  Arguments as above; n_fast_blocks nullable: how many blocks a summary applied (n_slow_blocks + n_fast_blocks = all blocks).
+ * Nothing in the product calls it. */
+int gbrl_hip_seq_sums_model(const float *x, const uint32_t *lens, const float *starts, int n_chains, float *out, uint32_t *n_slow_blocks,
+                            uint32_t *n_fast_blocks);
 
 /* Diagnostics for the tests: the ranking statistics of a batch's categorical cells as the device computes them when the batch holds more
  * distinct (feature, cell) pairs than n_cat * n_bins (cat_rank.hip).  Host pointers: cells [n][n_cat][128] bytes, grads [n][output_dim].

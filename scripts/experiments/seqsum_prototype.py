@@ -1,4 +1,5 @@
-"""Prototype: exact evaluation of a sequential float32 sum through block summaries (functions of the running sum's parity)."""
+"""Prototype: exact evaluation of a sequential float32 sum through block summaries (functions of the running sum's parity).
+300 random chains and constructed binade edges against the plain loop; prints `bad 0`."""
 import numpy as np
 
 def seq_sum(x, s0=np.float32(0)):
@@ -52,9 +53,10 @@ def block_summary(x, e):
         out.append((A - p, lo, hi_))
     return out
 
-def fast_sum(x, block=64):
-    """sequential float32 sum of x through block summaries; falls back to the serial loop where the binade hypothesis fails."""
-    s = np.float32(0)
+def fast_sum(x, block=64, s0=np.float32(0)):
+    """sequential float32 sum of x through block summaries; falls back to the serial loop where the binade hypothesis fails: the running sum
+    and every partial sum must lie strictly between 2^23 and 2^24 units (below a power of two the spacing is u / 2, which the model ignores)."""
+    s = np.float32(s0)
     n_fast = n_slow = 0
     for b0 in range(0, len(x), block):
         xb = x[b0:b0 + block]
@@ -67,8 +69,8 @@ def fast_sum(x, block=64):
                 if summ is not None:
                     A0 = sg * m
                     d, lo, hi = summ[A0 & 1]
-                    if sg > 0: ok = (A0 + lo >= (1 << 23)) and (A0 + hi < (1 << 24))
-                    else: ok = (A0 + hi <= -(1 << 23)) and (A0 + lo > -(1 << 24))
+                    if sg > 0: ok = (A0 > (1 << 23)) and (A0 + lo > (1 << 23)) and (A0 + hi < (1 << 24))
+                    else: ok = (A0 < -(1 << 23)) and (A0 + hi < -(1 << 23)) and (A0 + lo > -(1 << 24))
                     if ok:
                         A = A0 + d
                         s = np.float32(np.ldexp(np.float64(A), e - 23))
@@ -96,4 +98,27 @@ if __name__ == "__main__":
             bad += 1
             print("MISMATCH", t, kind, n, want, got)
         if t < 12: print(t, kind, n, want, got, "fast blocks", nf, "slow", ns)
+    # constructed: the sum exactly on +-2^k -- as the start, as the sum a block ends on, inside a block -- then opposite-sign dust of c * u.
+    # (0.25, 0.5] u steps the loop down to 2^k - u/2; a summary that accepted a sum ON the power of two would stay.  [1.0, 0 ...] [-0.4 u, 0 ...]
+    # is the smallest case: 0.99999994, not 1.0.
+    n_con = 0
+    for k in (-20, -1, 0, 1, 19):
+        for sg in (1.0, -1.0):
+            P, u = sg * 2.0 ** k, 2.0 ** (k - 23)
+            for c in (2.0 ** -30, 0.25, 0.26, 0.3, 0.4, 0.5, 0.6, 0.75, 1.0, 1.25, 1.5):
+                dust = [-sg * c * u] * 3
+                z = [0.0] * 63
+                walk = list(rng.integers(-500, 501, 40) * u)
+                for s0, x in ((P, dust + z),                                               # the chain's start
+                              (0.0, [P] + z + dust + z),                                   # the sum a block ends on
+                              (1.5 * P, walk + [P - (1.5 * P + sum(walk))] + dust + z),    # inside a block (the walk is exact: multiples of u around 1.5 P)
+                              (P, dust + [3 * sg * u, -3 * sg * u] + dust + [0.5 * P] + z + walk)):   # back onto it, then away to mid-binade
+                    x = np.array(x, np.float32)
+                    want = seq_sum(x, np.float32(s0))
+                    got, nf, ns = fast_sum(x, s0=np.float32(s0))
+                    n_con += 1
+                    if want.tobytes() != got.tobytes():
+                        bad += 1
+                        print("MISMATCH constructed k", k, "sign", sg, "c", c, "start", s0, want, got)
+    print(n_con, "constructed chains")
     print("bad", bad)

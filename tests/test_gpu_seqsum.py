@@ -8,6 +8,9 @@ import os
 import numpy as np
 import pytest
 
+import seqsum_cases as S
+from seqsum_cases import chain as _chain      # the ten kinds of chains and the lengths: shared with tests/test_seqsum_host.py
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,34 +42,10 @@ def _device(lib, chains, starts):
     return out, int(slow[0])
 
 
-def _chain(rng, kind, n):
-    if kind == 0: return rng.standard_normal(n).astype(np.float32)
-    if kind == 1: return (rng.standard_normal(n) + 0.3).astype(np.float32)
-    if kind == 2: return (rng.standard_normal(n) * np.exp(rng.standard_normal(n) * 3)).astype(np.float32)
-    if kind == 3: return (np.round(rng.standard_normal(n) * 8) / 8 + 0.5).astype(np.float32)           # many exact ties
-    if kind == 4: return (-np.abs(rng.standard_normal(n))).astype(np.float32)
-    if kind == 5: return (rng.integers(-3, 4, n) * 0.25).astype(np.float32)                           # returns to zero again and again
-    if kind == 6:
-        x = (rng.standard_normal(n) + 1.0).astype(np.float32)
-        x[rng.integers(0, n, max(1, n // 200))] = np.float32(1e30)                                   # elements far above the running sum
-        x[rng.integers(0, n, max(1, n // 200))] = np.float32(-1e30)
-        return x
-    if kind == 7:
-        x = (rng.standard_normal(n) * 1e-3 + 1.0).astype(np.float32)
-        x[rng.integers(0, n, max(1, n // 100))] = np.float32(1e-38)                                  # subnormal-range dust
-        x[rng.integers(0, n, max(1, n // 100))] = np.float32(0.0)
-        return x
-    if kind == 8:
-        x = (rng.standard_normal(n) + 0.5).astype(np.float32)
-        if n > 3: x[n // 2] = np.float32(np.inf) if rng.integers(0, 2) else np.float32(np.nan)
-        return x
-    return (np.float32(2.0) ** rng.integers(-30, 30, n) * rng.choice([-1.0, 1.0], n)).astype(np.float32)   # pure powers of two
-
-
 def test_parallel_sequential_sums_equal_the_plain_loop_bit_for_bit():
     lib = _lib()
     rng = np.random.default_rng(5)
-    lengths = [0, 1, 2, 3, 63, 64, 255, 256, 257, 511, 512, 513, 1000, 4096, 4097, 20000]
+    lengths = S.LENGTHS
     chains, starts = [], []
     for t in range(400):
         n = lengths[t % len(lengths)] if t < 160 else int(rng.integers(1, 6000))
@@ -100,3 +79,52 @@ def test_long_chains_mostly_take_the_summaries():
     n_blocks = 3 * (n // 256)
     print("3 chains of 2^20 elements: %d of %d blocks took the serial fallback" % (slow, n_blocks))
     assert slow <= n_blocks // 4
+
+
+# ---- constructed chains (tests/seqsum_cases.py): running sums exactly on a power of two, on (2^24 - 1) u, on zero -----------------------------
+# Each family goes through the kernels and through the host walk of the same arithmetic (gbrl_hip_seq_sums_model): both must give the plain
+# loop's bytes, hence each other's (NaN equals NaN: which NaN an add returns is the hardware's choice); the blocks each added element by
+# element are printed side by side (the walk makes the kernels' decisions in the kernels' order).
+
+def _device_loop_and_model_agree(names, chains, starts):
+    lib = S.lib()
+    got, slow = S.device(lib, chains, starts)
+    ref, m_slow, m_fast = S.model(lib, chains, starts)
+    bad = S.mismatches(got, chains, starts, names)
+    print("%d chains, %d blocks: the kernels added %d element by element, the host walk %d; %d sums differ from the plain loop" % (
+        len(chains), S.n_blocks(chains), slow, m_slow, len(bad)))
+    assert not bad, (len(bad), bad[:10])
+    differ = [(n, float(r), float(g)) for n, r, g in zip(names, ref, got) if not S.same(r, g)]
+    assert not differ, (len(differ), differ[:10])
+    assert m_slow + m_fast == S.n_blocks(chains)
+    return slow
+
+
+def test_edges_of_the_binade_equal_the_plain_loop_and_the_host_walk():
+    """The sum exactly on +-2^k (chain start, first / last element of a block, mid-block, elements 4096 and 16384: where a group of 16 blocks
+    and a scan of 64 begin) followed by opposite-sign elements of 2^-30 .. 1.5 u, once and again and again; the sum on (2^24 - 1) u followed by
+    0.4 .. 1 u of its own sign; k at both ends of the accepted range, one beyond each, and in between.  Below 2^k the spacing is u / 2, which
+    the parity model does not know: a run that starts on or touches the power of two has to take the loop.  And not ALL runs may: the blocks
+    added element by element are bounded by those that hold or directly follow an edge (the chains' other blocks keep every partial sum in
+    [1.25, 1.75] 2^k; tests/test_seqsum_host.py checks that premise on the inputs)."""
+    fam = S.edge_families()
+    slow = _device_loop_and_model_agree([c.name for c in fam], [c.x for c in fam], [c.start for c in fam])
+    cap = sum(c.cap for c in fam)
+    assert slow <= cap, (slow, cap)
+
+
+def test_zero_signed_zero_subnormals_and_non_finite_equal_the_plain_loop_and_the_host_walk():
+    """Exact cancellation to +0.0 and on; -0.0 kept by a -0.0 start and -0.0 elements (also behind a chain's last element inside a block: the
+    padding must be the identity of EVERY sum) and lost to one +0.0; subnormal elements under the smallest sums; inf / nan / overflow inside a
+    group of 16 blocks that is summarisable otherwise."""
+    _device_loop_and_model_agree(*S.zero_family())
+
+
+def test_the_advisors_example():
+    """s = 1.0f takes -0.4 * 2^-23: the loop steps down to 0.99999994 (the spacing below 1.0 is 2^-24); a summary that accepts a sum sitting ON
+    the power of two keeps 1.0.  As the chain's start, as the sum a block ends on, and mirrored."""
+    names, chains, starts, want = S.advice_example()
+    got, _ = S.device(S.lib(), chains, starts)
+    for n, w, g in zip(names, want, got):
+        assert np.float32(g).tobytes() == w.tobytes(), (n, float(w), float(g))
+    assert want[0] == np.float32(0.99999994) and want[0] < 1
