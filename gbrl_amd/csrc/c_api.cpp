@@ -519,6 +519,14 @@ int gbrl_hip_seq_sums_model(const float *x, const uint32_t *lens, const float *s
     return guarded([&] { (void)gbrl::kern::seq_sums_model(x, lens, starts, n_chains, out, n_slow_blocks, n_fast_blocks); });
 }
 
+int gbrl_hip_shap_plan(int max_depth, int output_dim, int *threads, int *samples_per_block) {
+    if (!threads || !samples_per_block || output_dim < 1) return GBRL_HIP_E_INVALID;
+    const int nt = gbrl::kern::shap_block_threads(max_depth, output_dim);
+    *threads = nt;
+    *samples_per_block = nt > 0 ? nt / output_dim : 0;
+    return GBRL_HIP_OK;
+}
+
 int gbrl_hip_cat_rank_stats(const char *cells, int n, int n_cat, const float *grads, int output_dim, int cap, int32_t *feature,
                             int32_t *first_row, int32_t *count, float *total, int *n_distinct) {
     if (!cells || !grads || !feature || !first_row || !count || !total || !n_distinct || n < 1 || n_cat < 1 || output_dim < 1 || cap < 1) return GBRL_HIP_E_INVALID;

@@ -117,6 +117,7 @@ class Engine {
     // Linear TreeSHAP of tree `tree_idx` (-1: every tree, summed in tree order) on the device; host pointers in and out, `out`
     // [n][n_num + n_cat][D] is overwritten.  Returns false when it was NOT computed (no HIP device, max_depth / output_dim beyond
     // the kernel's LDS budget, GBRL_HIP_SHAP_HOST=1): the caller then evaluates on the host (explain.cpp), which gives the same bits.
+    // With GBRL_HIP_SHAP_DEVICE_ONLY=1 (test hook) the first two raise instead, so a result that came back was computed by k_shap.
     bool shap_on_device(int tree_idx, const float *obs, const char *cat, int n, const float *norm, const float *base_poly,
                         const float *offset, float *out);
 

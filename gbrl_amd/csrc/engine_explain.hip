@@ -5,6 +5,8 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
+#include <string>
 
 namespace gbrl {
 
@@ -30,8 +32,16 @@ bool Engine::shap_on_device(int tree_idx, const float *obs, const char *cat, int
     const gbrl_hip_metadata &md = model.meta;
     const int D = md.output_dim, depth = md.max_depth, n_num = md.n_num_features, n_cat = md.n_cat_features;
     if (const char *e = hooks::raw(hooks::SHAP_HOST)) { if (e[0] == '1') return false; }   // test hook: host evaluation
-    if (kern::shap_block_threads(depth, D) == 0) return false;
-    try { ensure_device(); } catch (const NoDeviceError &) { return false; }   // inspection also works on a machine without a GPU
+    const bool only = hooks::on(hooks::SHAP_DEVICE_ONLY);   // test hook: raise where the host would silently take over
+    if (kern::shap_block_threads(depth, D) == 0) {
+        if (only) throw std::runtime_error("GBRL_HIP_SHAP_DEVICE_ONLY=1: k_shap has no launch plan for max_depth " + std::to_string(depth) +
+                                           ", output_dim " + std::to_string(D) + " (the host evaluation would take this shape)");
+        return false;
+    }
+    try { ensure_device(); } catch (const NoDeviceError &e) {   // inspection also works on a machine without a GPU
+        if (only) throw std::runtime_error(std::string("GBRL_HIP_SHAP_DEVICE_ONLY=1: no device for k_shap (the host evaluation would run): ") + e.what());
+        return false;
+    }
     if (md.n_trees == 0 || n <= 0) return true;
     hipStream_t s = stream_;
     sync_model_to_device();   // categorical conditions -> dictionary ids

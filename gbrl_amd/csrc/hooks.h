@@ -56,6 +56,7 @@ namespace hooks {
     X(QUANTILE_SAMPLE) \
     X(RADIX_PLAIN_LOADS) \
     X(ROOT_COUNTS) \
+    X(SHAP_DEVICE_ONLY) \
     X(SHAP_HOST) \
     X(SMALL_GROW_BLOCKS) \
     X(SMALL_GROW_PROF) \

@@ -314,6 +314,12 @@ int gbrl_hip_seq_sums_model(const float *x, const uint32_t *lens, const float *s
 int gbrl_hip_cat_rank_stats(const char *cells, int n, int n_cat, const float *grads, int output_dim, int cap, int32_t *feature,
                             int32_t *first_row, int32_t *count, float *total, int *n_distinct);
 
+/* Diagnostics for the tests: the launch plan of the device TreeSHAP kernel (csrc/shap.hip, kern::shap_block_threads) for a model with this
+ * max_depth and output_dim.  *threads = threads per block (256 while the two coefficient stacks of every thread fit the LDS, then 128, then
+ * 64), *samples_per_block = threads / output_dim; both 0 when the kernel declines the shape (the stacks fit no block size, or one sample's
+ * outputs do not fit the block): tree_shap / ensemble_shap then evaluate on the host.  No HIP call: it runs without a device. */
+int gbrl_hip_shap_plan(int max_depth, int output_dim, int *threads, int *samples_per_block);
+
 /* ---- device / stream contract (new; the reference pins everything to device 0 and the null stream, cuda_types.cu:32-106) -- */
 /* The device the model computes on: the ordinal given at creation, or -- for -1 -- the calling thread's current device at the
  * first call that needs it (it is latched by this call too).  -1 when no HIP device is usable.  A caller that hands out

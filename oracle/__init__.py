@@ -192,6 +192,18 @@ def load_ref_capacity():
     return mod
 
 
+def load_ref_small():
+    """The inspection-capacity reference build (oracle/Makefile target ref-small: INITAL_MAX_TREES 50000 -> 4 in a /tmp copy, so that
+    models with max_depth up to 17 can be constructed; tests/golden/make_shap_edge_golden.py).  Returns the module or None."""
+    hits = sorted(glob.glob(os.path.join(_HERE, "_ref", "small", "gbrl_cpp_refsmall*.so")))
+    if not hits:
+        return None
+    spec = importlib.util.spec_from_file_location("gbrl_cpp_refsmall", hits[0])
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
 def load_ref(native: bool = False):
     """Import the reference's own CPU build (oracle/_ref).  Returns the module or None."""
     path = ref_path(native)

@@ -33,6 +33,26 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.gbrl_hip_device_count() >= 0
 
 
+def test_shap_launch_plan_is_exported_and_follows_the_lds_budget():
+    """gbrl_hip_shap_plan (diagnostic, no device needed): k_shap's block is the largest of 256 / 128 / 64 threads whose two coefficient stacks
+    -- 2 * (max_depth + 1)^2 floats per thread -- fit 156 KiB of LDS, i.e. max_depth <= 7 / <= 11 / <= 16; threads / output_dim samples share
+    a block; the kernel declines (0, 0) a deeper model and one whose output_dim exceeds that block."""
+    lib = ctypes.CDLL(gbrl_amd.LIB_PATH)
+    lib.gbrl_hip_shap_plan.restype = ctypes.c_int
+    lib.gbrl_hip_shap_plan.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    nt, per = ctypes.c_int(), ctypes.c_int()
+    for md in range(1, 21):
+        fits = [t for t in (256, 128, 64) if 4 * t * 2 * (md + 1) ** 2 <= 156 * 1024]
+        assert (fits[0] if fits else 0) == (256 if md <= 7 else 128 if md <= 11 else 64 if md <= 16 else 0)
+        for D in (1, 2, 3, 5, 7, 63, 64, 65, 127, 128, 129, 200, 255, 256, 257, 512):
+            assert lib.gbrl_hip_shap_plan(md, D, ctypes.byref(nt), ctypes.byref(per)) == 0
+            want = fits[0] if fits and D <= fits[0] else 0
+            assert (nt.value, per.value) == (want, want // D), (md, D)
+    assert lib.gbrl_hip_shap_plan(0, 3, ctypes.byref(nt), ctypes.byref(per)) == 0 and (nt.value, per.value) == (0, 0)
+    assert lib.gbrl_hip_shap_plan(4, 0, ctypes.byref(nt), ctypes.byref(per)) != 0        # GBRL_HIP_E_INVALID
+    assert lib.gbrl_hip_shap_plan(4, 3, None, ctypes.byref(per)) != 0
+
+
 def test_header_is_plain_c_and_links_against_the_library(tmp_path):
     """include/gbrl_hip.h is the drop-in boundary: it must be valid C99 (no C++, no torch types) and a C program must link
     against libgbrl_hip.so and call an entry point without a GPU."""
