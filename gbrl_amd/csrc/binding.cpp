@@ -323,6 +323,99 @@ py::object predict_continue_impl(PyGBRL &self, py::object &obs, py::object &cat,
     return py::array_t<float>(shp, out, owner);
 }
 
+// Extension: predict_staged(obs, categorical_obs, stops=None) / staged_loss(obs, categorical_obs, targets, stops=None): every ensemble prefix in
+// one walk (include/gbrl_hip.h).  `stops`: a strictly ascending sequence of tree counts k, 0 <= k <= n_trees; k == 0 is the bias alone (0 never
+// means "all trees" here); None means 1, 2, ..., n_trees.  predict_staged returns float32 [len(stops), n, D] ([len(stops), n] when D == 1) --
+// NumPy for a "cpu" model, a DLPack capsule on the model's device for a "cuda" one, as predict does; staged_loss returns float64 [len(stops)].
+std::vector<int32_t> read_stops(py::object &stops_obj, int n_trees) {
+    std::vector<int32_t> stops;
+    if (stops_obj.is_none()) {
+        for (int k = 1; k <= n_trees; ++k) stops.push_back(k);
+    } else {
+        for (py::handle k : py::iter(stops_obj)) stops.push_back(k.cast<int32_t>());
+    }
+    // the engine checks the same (c_api callers); here too because a "cuda" model allocates its result on the device before the C call
+    if (stops.empty()) fail("stops is empty: nothing to evaluate");
+    for (size_t i = 0; i < stops.size(); ++i) {
+        if (stops[i] < 0 || stops[i] > n_trees) {
+            std::stringstream ss;
+            ss << "a stop is out of bounds! Got " << stops[i] << ", but valid range is [0, " << n_trees << "]";
+            fail(ss.str());
+        }
+        if (i > 0 && stops[i] <= stops[i - 1]) fail("stops must be strictly ascending");
+    }
+    return stops;
+}
+
+py::object predict_staged_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &stops_obj) {
+    const gbrl_hip_metadata md = self.meta();
+    Input o = read_input(obs, "obs", true, "predict_staged", false);
+    Input c = read_input(cat, "cat_obs", true, "predict_staged", 1);
+    if (!o.ptr && !c.ptr) fail("Cannot call predict_staged without observations!");
+    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const std::vector<int32_t> stops = read_stops(stops_obj, md.n_trees);
+    const int n = bs.n, D = md.output_dim, S = static_cast<int>(stops.size());
+    std::vector<int64_t> shape;
+    if (D == 1) shape = {S, n}; else shape = {S, n, D};
+    const size_t total = static_cast<size_t>(S) * n * D;
+    const bool dev_out = self.device == 1;
+    float *out = nullptr;
+    int dev_id = 0;
+    if (dev_out) {
+        dev_id = gbrl_hip_device_ordinal(self.h);
+        if (dev_id < 0) fail(gbrl_hip_last_error());
+        out = static_cast<float *>(gbrl_hip_device_alloc_on(dev_id, sizeof(float) * total));
+        if (!out) fail(gbrl_hip_last_error());
+    } else {
+        out = new float[total];
+    }
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_predict_staged(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, bs.n_num,
+                                     bs.n_cat, stops.data(), S, out, dev_out);
+    }
+    if (rc != GBRL_HIP_OK) {
+        if (dev_out) gbrl_hip_device_free(out); else delete[] out;
+        fail(gbrl_hip_last_error());
+    }
+    if (dev_out) return make_dlpack(out, shape, true, dev_id);
+    py::capsule owner(out, [](void *p) { delete[] static_cast<float *>(p); });
+    std::vector<py::ssize_t> shp(shape.begin(), shape.end());
+    return py::array_t<float>(shp, out, owner);
+}
+
+py::object staged_loss_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, py::object &stops_obj) {
+    const gbrl_hip_metadata md = self.meta();
+    Input o = read_input(obs, "obs", true, "staged_loss", false);
+    Input c = read_input(cat, "cat_obs", true, "staged_loss", 1);
+    if (!o.ptr && !c.ptr) fail("Cannot call staged_loss without observations!");
+    Input y = read_input(targets, "targets", false, "staged_loss", false);
+    if (!y.ptr) fail("Cannot call staged_loss without targets!");
+    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const int n = bs.n, D = md.output_dim;
+    const bool shape_ok = (y.shape.size() == 2 && y.shape[0] == static_cast<size_t>(n) && y.shape[1] == static_cast<size_t>(D)) ||
+                          (y.shape.size() == 1 && D == 1 && y.shape[0] == static_cast<size_t>(n));
+    if (!shape_ok) {
+        std::stringstream ss;
+        ss << "Expected targets of shape (" << n << ", " << D << ")" << (D == 1 ? " or (" + std::to_string(n) + ",)" : std::string()) << ", but got (";
+        for (size_t i = 0; i < y.shape.size(); ++i) ss << (i ? ", " : "") << y.shape[i];
+        ss << ")";
+        fail(ss.str());
+    }
+    const std::vector<int32_t> stops = read_stops(stops_obj, md.n_trees);
+    py::array_t<double> loss(static_cast<py::ssize_t>(stops.size()));
+    double *lp = loss.mutable_data();
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_staged_loss(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device,
+                                  static_cast<const float *>(y.ptr), y.on_device, n, bs.n_num, bs.n_cat, stops.data(), static_cast<int>(stops.size()), lp);
+    }
+    check(rc);
+    return loss;
+}
+
 // Extension: (ids, token) = encode_categorical(categorical_obs): int32 dictionary ids [n, n_cat] of a batch of cells -- a DLPack capsule on the
 // model's device for a "cuda" model, a NumPy array otherwise -- for predict_encoded(obs, ids, token, ...).
 py::tuple encode_categorical_impl(PyGBRL &self, py::object &cat) {
@@ -590,6 +683,9 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         return predict_continue_impl(self, obs, ids, base, start, stop, &token);
     }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("base"), py::arg("start_tree_idx") = 0,
           py::arg("stop_tree_idx") = 0);
+    // extension: every ensemble prefix in one walk -- the prediction, or the MultiRMSE loss against targets, after every stops[s] trees
+    g.def("predict_staged", &predict_staged_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("stops") = py::none());
+    g.def("staged_loss", &staged_loss_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("stops") = py::none());
     g.def("fit", &fit_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("iterations"),
           py::arg("shuffle") = true, py::arg("loss_type") = "MultiRMSE");
     g.def("set_bias", [](PyGBRL &self, py::object &bias) {

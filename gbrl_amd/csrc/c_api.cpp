@@ -372,6 +372,25 @@ int gbrl_hip_predict_continue_encoded(gbrl_hip_model *m, const float *obs, int o
     });
 }
 
+int gbrl_hip_predict_staged(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device, int n_samples,
+                            int n_num_features, int n_cat_features, const int32_t *stops, int n_stops, float *out, int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.predict_staged(obs, obs_on_device != 0, cat_obs, cat_on_device != 0, n_samples, n_num_features, n_cat_features, stops, n_stops, out,
+                                 out_on_device != 0);
+    });
+}
+
+int gbrl_hip_staged_loss(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device, const float *targets,
+                         int targets_on_device, int n_samples, int n_num_features, int n_cat_features, const int32_t *stops, int n_stops,
+                         double *loss_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.staged_loss(obs, obs_on_device != 0, cat_obs, cat_on_device != 0, targets, targets_on_device != 0, n_samples, n_num_features,
+                              n_cat_features, stops, n_stops, loss_out);
+    });
+}
+
 static_assert(static_cast<int>(gbrl::Engine::ParityMode::Default) == GBRL_HIP_PARITY_DEFAULT && static_cast<int>(gbrl::Engine::ParityMode::Reference) == GBRL_HIP_PARITY_REFERENCE &&
               static_cast<int>(gbrl::Engine::ParityMode::ExactArgmax) == GBRL_HIP_PARITY_EXACT_ARGMAX, "the engine's parity modes are the header's");
 int gbrl_hip_set_parity_mode(gbrl_hip_model *m, int mode, int max_node_rows) {

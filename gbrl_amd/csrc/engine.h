@@ -108,6 +108,15 @@ class Engine {
                           int stop_tree, const float *base, bool base_dev, float *out, bool out_dev);
     void predict_continue_encoded(const float *obs, bool obs_dev, const int32_t *cat_ids, bool ids_dev, uint64_t token, int n, int n_num,
                                   int n_cat, int start_tree, int stop_tree, const float *base, bool base_dev, float *out, bool out_dev);
+    // Extension: every ensemble prefix in one walk.  `stops` (host, n_stops > 0) is a strictly ascending list of tree counts k, 0 <= k <= n_trees;
+    // k == 0 is the bias alone -- unlike predict's stop_tree, 0 never means "all trees" here.  Stage s is, bit for bit, what
+    // predict_continue(base = tiled bias, 0, stops[s]) returns.  predict_staged: out [n_stops][n][D].  staged_loss: loss_out[s] (host) =
+    // sqrt(0.5 * S / n) in float64, S the float64 sum of (double)g * (double)g, g = fl32(p - y), over all rows and outputs in a fixed order
+    // (MultiRMSE as fit() defines it).  Errors (InvalidArgument / Unsupported) are raised before the device is touched.
+    void predict_staged(const float *obs, bool obs_dev, const char *cat, bool cat_dev, int n, int n_num, int n_cat, const int32_t *stops, int n_stops,
+                        float *out, bool out_dev);
+    void staged_loss(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num, int n_cat,
+                     const int32_t *stops, int n_stops, double *loss_out);
     // GBRL::fit (gbrl.cpp:983-1104) + Fitter::fit_cpu (fitter.cpp:117-261): bias = mean(targets), split candidates from the
     // WHOLE data set once, then `iterations` boosting rounds over consecutive batches of metadata.batch_size rows
     // (predict -> MultiRMSE gradients -> one tree per batch); returns the final MultiRMSE loss on the whole data set.
@@ -145,8 +154,11 @@ class Engine {
     void sync_model_to_device();
     int32_t *encode_categorical_batch(const char *cat, bool cat_dev, int n, int n_cat);
     struct ContinueBase { const float *base; bool on_device; };   // predict_continue: the held prediction (nullptr in predict_core: an ordinary predict)
+    // predict_staged / staged_loss: the checkpoints (host) and, in loss mode, the targets and where the losses go (nullptr in predict_core: no stages)
+    struct StagedPlan { const int32_t *stops; int n_stops; bool loss; const float *targets; bool targets_dev; double *loss_out; };
     void predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
-                      int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont = nullptr);
+                      int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont = nullptr,
+                      const StagedPlan *staged = nullptr);
     uint64_t cat_dict_token();
     void grow_tree(const detail::GrowCtx &c, std::vector<detail::HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc,
                    double &leaf_scale);
@@ -272,6 +284,7 @@ class Engine {
     int cum_cache_b_ = -1;
     // ---- predict workspace + device mirror of the ensemble ----
     DevBuf d_pobs_, d_pcat_, d_pout_;
+    DevBuf d_staged_stops_, d_staged_targets_, d_staged_part_, d_staged_sums_;   // predict_staged / staged_loss: stops table, staged targets, loss partials and sums
     DevBuf m_tree_indices_, m_depths_, m_feature_indices_, m_feature_values_, m_values_, m_is_numerics_, m_ineq_,
         m_cat_ids_, m_bias_, m_opt_start_, m_opt_stop_, m_opt_lr_, m_cond_pack_, m_grd_nodes_, m_grd_off_, m_values_sw_, m_cond_ra_;
     size_t up_trees_ = 0, up_leaves_ = 0, up_splits_ = 0;  // how much of the append-only arrays is already on the device

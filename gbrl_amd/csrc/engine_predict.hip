@@ -453,14 +453,30 @@ void Engine::predict_continue_encoded(const float *obs, bool obs_dev, const int3
     predict_core(obs, obs_dev, nullptr, false, cat_ids, ids_dev, &token, n, n_num, n_cat, start_tree, stop_tree, out, out_dev, &cont);
 }
 
+// Extension: every prefix [0, stops[s]) of the ensemble in one walk (kern::predict_staged).  Everything but the checkpoints and the kernel is
+// predict_core's; the call is one chain per (row, output) and is never sliced over tree ranges.
+void Engine::predict_staged(const float *obs, bool obs_dev, const char *cat, bool cat_dev, int n, int n_num, int n_cat, const int32_t *stops, int n_stops,
+                            float *out, bool out_dev) {
+    const StagedPlan plan{stops, n_stops, false, nullptr, false, nullptr};
+    predict_core(obs, obs_dev, cat, cat_dev, nullptr, false, nullptr, n, n_num, n_cat, 0, 0, out, out_dev, nullptr, &plan);
+}
+
+void Engine::staged_loss(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num, int n_cat,
+                         const int32_t *stops, int n_stops, double *loss_out) {
+    const StagedPlan plan{stops, n_stops, true, targets, targets_dev, loss_out};
+    predict_core(obs, obs_dev, cat, cat_dev, nullptr, false, nullptr, n, n_num, n_cat, 0, 0, nullptr, false, nullptr, &plan);
+}
+
 void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
-                          int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont) {
+                          int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont,
+                          const StagedPlan *staged) {
     gbrl_hip_metadata &md = model.meta;
     // GBRL::predict, gbrl.cpp:378-390
     if (md.iteration == 0) { md.n_num_features = n_num; md.n_cat_features = n_cat; }
     if (n_num + n_cat != md.input_dim) throw InvalidArgument("Incompatible dataset");
     if (n_num != md.n_num_features || n_cat != md.n_cat_features) throw InvalidArgument("Incompatible dataset");
-    if (n <= 0 || out == nullptr) throw InvalidArgument("Cannot call predict without observations!");
+    const bool staged_loss_mode = staged != nullptr && staged->loss;   // (its results are n_stops doubles: there is no `out`)
+    if (n <= 0 || (out == nullptr && !staged_loss_mode)) throw InvalidArgument("Cannot call predict without observations!");
     if (n_num > 0 && obs == nullptr) throw InvalidArgument("Cannot call predict without observations!");
     if (n_cat > 0 && cat == nullptr && cat_ids == nullptr) throw InvalidArgument("Cannot call predict without observations!");
     if (md.output_dim > 128) throw Unsupported("predict: output_dim > 128");
@@ -472,6 +488,17 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
         const int resolved = stop_tree == 0 ? md.n_trees : stop_tree;
         if (resolved > md.n_trees || start_tree > resolved) throw InvalidArgument("predict_continue: invalid tree range");
     }
+    if (staged != nullptr) {
+        // like predict_continue, no reference behaviour to mirror: a stage the ensemble does not hold is an error, reported before the device is touched
+        if (staged->stops == nullptr || staged->n_stops <= 0) throw InvalidArgument("staged evaluation: stops is empty");
+        for (int i = 0; i < staged->n_stops; ++i) {
+            const int k = staged->stops[i];
+            if (k < 0 || k > md.n_trees) throw InvalidArgument("staged evaluation: a stop is out of bounds! Got " + std::to_string(k) + ", but valid range is [0, " + std::to_string(md.n_trees) + "]");
+            if (i > 0 && k <= staged->stops[i - 1]) throw InvalidArgument("staged evaluation: stops must be strictly ascending");
+        }
+        if (staged->loss && staged->targets == nullptr) throw InvalidArgument("Cannot call staged_loss without targets!");
+        if (staged->loss && staged->loss_out == nullptr) throw InvalidArgument("staged_loss: no output array");
+    }
     ensure_device();
     ev_used_ = 0;
     ev_names_.clear();
@@ -479,7 +506,8 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     const int D = md.output_dim;
     // predict_cpu, predictor.cpp:127-141
     int stop = stop_tree;
-    if (cont != nullptr) { if (stop == 0) stop = md.n_trees; }   // (validated above)
+    if (staged != nullptr) { start_tree = 0; stop = 0; }         // (the stops table is the range)
+    else if (cont != nullptr) { if (stop == 0) stop = md.n_trees; }   // (validated above)
     else if (md.n_trees == 0 || stop > md.n_trees || model.opts.empty()) { start_tree = 0; stop = 0; }
     else if (stop == 0) stop = md.n_trees;
     // an empty or inverted range walks no tree: predict_cpu's loops run from start to stop (predictor.cpp:139-163), the result is the bias
@@ -505,8 +533,24 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     } else if (n_cat > 0) {
         dcat = encode_categorical_batch(cat, cat_dev, n, n_cat);
     }
+    const size_t out_floats = static_cast<size_t>(n) * D * (staged != nullptr ? static_cast<size_t>(staged->n_stops) : 1);
     float *dout = out;
-    if (!out_dev) dout = static_cast<float *>(d_pout_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+    if (!out_dev && !staged_loss_mode) dout = static_cast<float *>(d_pout_.ensure(sizeof(float) * out_floats));
+    kern::StagedStops dstops{nullptr, 0, 0};
+    const float *dtargets = nullptr;
+    if (staged != nullptr) {   // the stops table lives on the device (the pageable copy has left the host array when the call returns)
+        int32_t *ds = static_cast<int32_t *>(d_staged_stops_.ensure(sizeof(int32_t) * staged->n_stops));
+        hip_check(hipMemcpyAsync(ds, staged->stops, sizeof(int32_t) * staged->n_stops, hipMemcpyHostToDevice, s), "H2D stops");
+        dstops = kern::StagedStops{ds, staged->n_stops, staged->stops[staged->n_stops - 1]};
+        if (staged->loss) {
+            dtargets = staged->targets;
+            if (!staged->targets_dev) {
+                float *dt = static_cast<float *>(d_staged_targets_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+                hip_check(hipMemcpyAsync(dt, staged->targets, sizeof(float) * static_cast<size_t>(n) * D, hipMemcpyHostToDevice, s), "H2D targets");
+                dtargets = dt;
+            }
+        }
+    }
     const float *dbase = nullptr;
     if (cont != nullptr) {   // a base in host memory is copied into the output buffer and continued in place
         dbase = cont->base;
@@ -557,7 +601,7 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
         const char *no_pc = hooks::raw(hooks::PREDICT_NO_PC), *no_reg = hooks::raw(hooks::PREDICT_NO_REG), *mr = hooks::raw(hooks::PREDICT_REG_MIN_ROWS);
         const int min_rows = mr ? std::atoi(mr) : 32768;
         const bool fp32_takes_it = n_cat == 0 && n_num <= 128 && (n_num & 3) == 0 && (reinterpret_cast<uintptr_t>(dobs) & 15) == 0 && !(no_reg && no_reg[0] == '1');
-        if (cont == nullptr && !(no_pc && no_pc[0] == '1') && !in_fit_ && pm.values_sw != nullptr && model.oblivious() && n >= min_rows && !fp32_takes_it &&
+        if (cont == nullptr && staged == nullptr && !(no_pc && no_pc[0] == '1') && !in_fit_ && pm.values_sw != nullptr && model.oblivious() && n >= min_rows && !fp32_takes_it &&
             kern::predict_pc_shape_ok(pm.obl2_maxd, D) && ensure_pc_book(n_num, n_cat)) {
             pm.pc_cond = m_pc_cond_.as<int32_t>();
             pm.pc_thr = m_pc_thr_.as<float>();
@@ -590,6 +634,27 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     if (model.opts.size() > 255) pm.coef_ok = pm.coef_ok && !model.scheduled();   // (owner is a byte; D <= 64 bounds the optimizers of a covered model anyway)
     // Linear schedules: the kernels of predict_sched.hip read the rate of (tree, optimizer) from the mirror's table
     pm.rate = (model.scheduled() && md.n_trees > 0) ? m_rate_.as<float>() : nullptr;
+    if (staged != nullptr) {
+        double *dpart = nullptr, *dsums = nullptr;
+        if (staged->loss) {
+            dpart = static_cast<double *>(d_staged_part_.ensure(sizeof(double) * static_cast<size_t>(staged->n_stops) * kern::staged_loss_partials(n)));
+            dsums = static_cast<double *>(d_staged_sums_.ensure(sizeof(double) * staged->n_stops));
+        }
+        kern::predict_staged(pm, dobs, n_num, dcat, n_cat, n, dstops, staged->loss ? nullptr : dout, dtargets, dpart, dsums, hooks::on(hooks::STAGED_GENERIC), s);
+        hip_check(hipGetLastError(), "predict_staged launch");
+        phase_end("predict", /*key=*/true);
+        if (staged->loss) {
+            std::vector<double> sums(staged->n_stops);
+            hip_check(hipMemcpyAsync(sums.data(), dsums, sizeof(double) * staged->n_stops, hipMemcpyDeviceToHost, s), "D2H loss sums");
+            hip_check(hipStreamSynchronize(s), "sync");
+            for (int i = 0; i < staged->n_stops; ++i) staged->loss_out[i] = std::sqrt(0.5 * sums[i] / static_cast<double>(n));   // loss.cpp:42-56, in float64
+        } else {
+            if (!out_dev) hip_check(hipMemcpyAsync(out, dout, sizeof(float) * out_floats, hipMemcpyDeviceToHost, s), "D2H preds");
+            hip_check(hipStreamSynchronize(s), "sync");
+        }
+        phases_resolve();
+        return;
+    }
     if (cont != nullptr) {
         kern::predict_continue(pm, dobs, n_num, dcat, n_cat, n, start_tree, stop, dbase, dout, hooks::on(hooks::CONTINUE_GENERIC), s);
         hip_check(hipGetLastError(), "predict_continue launch");

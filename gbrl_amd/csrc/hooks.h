@@ -63,6 +63,7 @@ namespace hooks {
     X(SMALL_PREP_PROF) \
     X(SORT_NO_CODES) \
     X(SPIN_SECONDS) \
+    X(STAGED_GENERIC) \
     X(TEST_CAT_CLASH) \
     X(TEST_SMALL_GROW_FAIL) \
     X(TRANSPOSE_COUNT) \

@@ -557,6 +557,16 @@ void predict(const PredictModel &pm, const float *obs, int F, const int32_t *cat
 // device pointers and may be the same buffer.  generic: the one-thread-per-row kernel only (GBRL_HIP_CONTINUE_GENERIC=1).  Always launches.
 void predict_continue(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
                       const float *base, float *out, bool generic, hipStream_t s);
+// Every prefix [0, stops[s]) of the ensemble in one walk (predict_staged.hip): stage s has the bits of predict_continue(tiled bias, 0, stops[s]);
+// stops[s] == 0 is the bias alone.  `stops` is a device array, strictly ascending, 0 <= stops[s] <= n_trees (the caller has checked);
+// last_stop = stops[n_stops - 1].  Predict mode (targets == nullptr): out[s][r][j], device [n_stops][n][D].  Loss mode (targets != nullptr,
+// device [n][D]): sums[s] = the float64 sum of (double)g * (double)g, g = fl32(p - y), over all rows and outputs, reduced in a fixed order --
+// part is scratch for n_stops x staged_loss_partials(n) doubles, sums holds n_stops.  generic: the one-thread-per-row kernel only
+// (GBRL_HIP_STAGED_GENERIC=1; same bytes in both modes).  Always launches.
+struct StagedStops { const int32_t *stops; int n_stops; int last_stop; };
+int staged_loss_partials(int n);
+void predict_staged(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, const StagedStops &st, float *out,
+                    const float *targets, double *part, double *sums, bool generic, hipStream_t s);
 
 // ---- Linear TreeSHAP (shap.hip): a uniform program over explicit trees, one thread per (sample, output) ----
 enum { SHAP_ENTER = 0, SHAP_AFTER_LEFT = 1, SHAP_AFTER_RIGHT = 2, SHAP_EXIT = 3 };

@@ -21,6 +21,7 @@
 // `base` and `out` may be the same buffer: a thread reads and writes its own row only.
 #include "kernels.h"
 #include "kernels_common.h"
+#include "predict_stream_common.h"
 
 #include <algorithm>
 
@@ -93,26 +94,10 @@ __global__ __launch_bounds__(256) void k_continue_general(ContModel cm, const fl
 }
 
 // ------------------------------------------------------------------------------------------------------------ streaming kernel
-constexpr int kContRows = 64;   // rows per block = one wave
+constexpr int kContRows = kStreamRows;   // rows per block = one wave
 
 template <int DMAX>
 struct ContOwner { uint8_t opt[DMAX]; };   // optimizer that owns output j (meaningful where bit j of `cover` is set)
-
-// D floats of one row into registers: 16-byte accesses when the row is a whole number of them and its address allows it
-template <int DMAX>
-__device__ __forceinline__ void cont_load_row(const float *src, int D, bool vec4, float (&v)[DMAX]) {
-    if (vec4) {
-        const float4 *s4 = reinterpret_cast<const float4 *>(src);
-#pragma unroll
-        for (int q = 0; q < DMAX / 4; ++q) {
-            const float4 w = 4 * q < D ? s4[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-            v[4 * q] = w.x; v[4 * q + 1] = w.y; v[4 * q + 2] = w.z; v[4 * q + 3] = w.w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < DMAX; ++j) v[j] = j < D ? src[j] : 0.0f;
-    }
-}
 
 template <int DMAX, bool GREEDY>
 __global__ __launch_bounds__(kContRows) void k_continue(ContModel cm, ContOwner<DMAX> own, uint64_t cover, const float *__restrict__ obs, int F,
@@ -129,43 +114,12 @@ __global__ __launch_bounds__(kContRows) void k_continue(ContModel cm, ContOwner<
     const size_t row = static_cast<size_t>(r0) + lane;
     float p[DMAX];
     if (live) {
-        cont_load_row<DMAX>(base + row * D, D, vec_io != 0, p);
+        stream_load_row<DMAX>(base + row * D, D, vec_io != 0, p);
     } else {
 #pragma unroll
         for (int j = 0; j < DMAX; ++j) p[j] = 0.0f;
     }
-    // coalesced staging of the block's rows (contiguous in the row-major matrix), 16 x 16 bytes in flight per lane
-    {
-        const float *src = obs + static_cast<size_t>(r0) * F;
-        if (F > 0 && (F & 3) == 0 && (reinterpret_cast<uintptr_t>(obs) & 15) == 0) {
-            const float4 *src4 = reinterpret_cast<const float4 *>(src);
-            const int F4 = F >> 2, tot4 = rows * F4;
-            constexpr int UL = 16;
-            for (int i0 = lane; i0 < tot4; i0 += kContRows * UL) {
-                float4 v[UL];
-#pragma unroll
-                for (int u = 0; u < UL; ++u) {
-                    const int i = i0 + u * kContRows;
-                    v[u] = i < tot4 ? src4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-#pragma unroll
-                for (int u = 0; u < UL; ++u) {
-                    const int i = i0 + u * kContRows;
-                    if (i < tot4) {
-                        const int r = i / F4, f = (i - r * F4) << 2;
-                        float *dst = ctile + r * xs + f;
-                        dst[0] = v[u].x; dst[1] = v[u].y; dst[2] = v[u].z; dst[3] = v[u].w;
-                    }
-                }
-            }
-        } else {
-            const int tot = rows * F;
-            for (int i = lane; i < tot; i += kContRows) {
-                const int r = i / F, f = i - r * F;
-                ctile[r * xs + f] = src[i];
-            }
-        }
-    }
+    stream_stage_tile(ctile, obs, F, r0, rows, lane);
     __syncthreads();
     if (live) {
         const float *x = ctile + lane * xs;
@@ -201,7 +155,7 @@ __global__ __launch_bounds__(kContRows) void k_continue(ContModel cm, ContOwner<
             float v[kG][DMAX];
 #pragma unroll
             for (int g = 0; g < kG; ++g)
-                if (t0 + g < stop_tree) cont_load_row<DMAX>(cm.values + static_cast<size_t>(leaf[g]) * D, D, vec_values != 0, v[g]);
+                if (t0 + g < stop_tree) stream_load_row<DMAX>(cm.values + static_cast<size_t>(leaf[g]) * D, D, vec_values != 0, v[g]);
 #pragma unroll
             for (int g = 0; g < kG; ++g) {
                 const int t = t0 + g;

@@ -215,6 +215,27 @@ int gbrl_hip_predict_continue_encoded(gbrl_hip_model *m, const float *obs, int o
                                       uint64_t dictionary_token, int n_samples, int n_num_features, int n_cat_features,
                                       int start_tree, int stop_tree, const float *base, int base_on_device, float *out, int out_on_device);
 
+/* Extension (no counterpart in the reference): every prefix of the ensemble in ONE walk -- the prediction, or the MultiRMSE loss on a held-out
+ * set, after every k trees; the curve that answers "how many trees to keep".  `stops` is a HOST array of n_stops > 0 tree counts k, strictly
+ * ascending, 0 <= k <= n_trees.  k == 0 is a legal stage and means the bias alone: unlike stop_tree of gbrl_hip_predict, 0 NEVER means "all
+ * trees" here.  Stage s is, bit for bit, what gbrl_hip_predict_continue(base = tiled bias, start_tree = 0, stop_tree = stops[s]) returns: one
+ * chain per (row, output) in tree order, rates at the absolute tree index (Const and Linear), an output that no optimizer owns keeps the bias
+ * bits, and the walk is never split over tree ranges, at any batch size.  The rows are read once, whatever n_stops is.
+ *   gbrl_hip_predict_staged: `out` is float32 [n_stops, n_samples, output_dim], host or device per out_on_device.
+ *   gbrl_hip_staged_loss:    `targets` is float32 [n_samples, output_dim], host or device; loss_out is a HOST array of n_stops doubles,
+ *                            loss_out[s] = sqrt(0.5 * S / n_samples) in float64, S = the float64 sum of (double)g * (double)g over all rows and
+ *                            outputs, g = fl32(prediction - target) -- MultiRMSE as gbrl_hip_fit defines it.  The sum has a fixed reduction
+ *                            order and uses no floating-point atomics: two identical calls return identical bytes.
+ * Reported with GBRL_HIP_E_INVALID before the device is touched: n_stops <= 0 or stops NULL; a stop that is negative, above n_trees or not above
+ * its predecessor; targets / loss_out NULL; the data set errors of gbrl_hip_predict.  output_dim > 128 is refused as in gbrl_hip_predict.
+ * Row-sharded models need no exchange: each rank evaluates its own rows. */
+int gbrl_hip_predict_staged(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device,
+                            int n_samples, int n_num_features, int n_cat_features, const int32_t *stops, int n_stops,
+                            float *out, int out_on_device);
+int gbrl_hip_staged_loss(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device,
+                         const float *targets, int targets_on_device, int n_samples, int n_num_features, int n_cat_features,
+                         const int32_t *stops, int n_stops, double *loss_out);
+
 /* ---- row-sharded multi-GPU (new; the reference is single-GPU) ------------------------------------------ */
 /* One process per GPU, each holding a contiguous block of rows.  When hooks are installed, step() calls them at
  * its exchange points so that every rank grows the identical tree; predict() needs no exchange.  Buffers are
