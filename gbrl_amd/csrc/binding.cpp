@@ -416,6 +416,78 @@ py::object staged_loss_impl(PyGBRL &self, py::object &obs, py::object &cat, py::
     return loss;
 }
 
+// Extension: predict_leaves(obs, categorical_obs, start, stop) / leaf_counts(...) and their _encoded variants (obs, ids, token, start, stop): where
+// a row lands (include/gbrl_hip.h).  predict_leaves returns int32 [n, stop - start] global leaf indices -- NumPy for a "cpu" model, a DLPack
+// capsule on the model's device for a "cuda" one; leaf_counts returns int64 NumPy [n_leaves], the rows of the batch per global leaf.
+py::object leaves_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object start_obj, py::object stop_obj, bool counts,
+                       const uint64_t *ids_token = nullptr) {
+    const gbrl_hip_metadata md = self.meta();
+    const char *fn = counts ? "leaf_counts" : "predict_leaves";
+    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
+    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    Input o = read_input(obs, "obs", true, fn, false);
+    Input c = read_input(cat, "cat_obs", true, fn, ids_token ? 2 : 1);
+    if (!o.ptr && !c.ptr) fail(std::string("Cannot call ") + fn + " without observations!");
+    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const int n = bs.n, n_num = bs.n_num, n_cat = bs.n_cat;
+    // the engine checks the same (c_api callers); here too because the result is allocated before the C call
+    if (md.n_trees == 0) fail(std::string(fn) + ": the model has no trees");
+    const int resolved = stop == 0 ? md.n_trees : stop;
+    if (start < 0 || stop < 0 || resolved > md.n_trees || start >= resolved) {
+        std::stringstream ss;
+        ss << fn << ": invalid tree range [" << start << ", " << stop << ") for " << md.n_trees << " trees";
+        fail(ss.str());
+    }
+    if (counts) {
+        py::array_t<int64_t> res(static_cast<py::ssize_t>(md.n_leaves));
+        int64_t *rp = res.mutable_data();
+        int rc;
+        {
+            py::gil_scoped_release release;
+            if (ids_token)
+                rc = gbrl_hip_leaf_counts_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device,
+                                                  *ids_token, n, n_num, n_cat, start, stop, rp);
+            else
+                rc = gbrl_hip_leaf_counts(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, n_num,
+                                          n_cat, start, stop, rp);
+        }
+        check(rc);
+        return res;
+    }
+    const int T = resolved - start;
+    if (static_cast<int64_t>(n) * T >= (int64_t(1) << 31)) fail("predict_leaves: n_samples x trees >= 2^31 indices: slice the tree range");
+    const size_t total = static_cast<size_t>(n) * T;
+    const bool dev_out = self.device == 1;
+    int32_t *out = nullptr;
+    int dev_id = 0;
+    if (dev_out) {
+        dev_id = gbrl_hip_device_ordinal(self.h);
+        if (dev_id < 0) fail(gbrl_hip_last_error());
+        out = static_cast<int32_t *>(gbrl_hip_device_alloc_on(dev_id, sizeof(int32_t) * total));
+        if (!out) fail(gbrl_hip_last_error());
+    } else {
+        out = new int32_t[total];
+    }
+    int rc;
+    {
+        py::gil_scoped_release release;
+        if (ids_token)
+            rc = gbrl_hip_predict_leaves_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device,
+                                                 *ids_token, n, n_num, n_cat, start, stop, out, dev_out);
+        else
+            rc = gbrl_hip_predict_leaves(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, n_num,
+                                         n_cat, start, stop, out, dev_out);
+    }
+    if (rc != GBRL_HIP_OK) {
+        if (dev_out) gbrl_hip_device_free(out); else delete[] out;
+        fail(gbrl_hip_last_error());
+    }
+    const std::vector<int64_t> shape = {n, T};
+    if (dev_out) return make_dlpack(out, shape, true, dev_id, /*int32=*/true);
+    py::capsule owner(out, [](void *p) { delete[] static_cast<int32_t *>(p); });
+    return py::array_t<int32_t>(std::vector<py::ssize_t>{n, T}, out, owner);
+}
+
 // Extension: (ids, token) = encode_categorical(categorical_obs): int32 dictionary ids [n, n_cat] of a batch of cells -- a DLPack capsule on the
 // model's device for a "cuda" model, a NumPy array otherwise -- for predict_encoded(obs, ids, token, ...).
 py::tuple encode_categorical_impl(PyGBRL &self, py::object &cat) {
@@ -683,6 +755,20 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         return predict_continue_impl(self, obs, ids, base, start, stop, &token);
     }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("base"), py::arg("start_tree_idx") = 0,
           py::arg("stop_tree_idx") = 0);
+    // extension: where a row lands -- the global leaf index per (row, tree), or the rows per leaf reduced on the device
+    g.def("predict_leaves", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop) {
+        return leaves_impl(self, obs, cat, start, stop, false);
+    }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0);
+    g.def("predict_leaves_encoded", [](PyGBRL &self, py::object &obs, py::object &ids, uint64_t token, py::object start, py::object stop) {
+        return leaves_impl(self, obs, ids, start, stop, false, &token);
+    }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0);
+    g.def("leaf_counts", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop) {
+        return leaves_impl(self, obs, cat, start, stop, true);
+    }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0);
+    g.def("leaf_counts_encoded", [](PyGBRL &self, py::object &obs, py::object &ids, uint64_t token, py::object start, py::object stop) {
+        return leaves_impl(self, obs, ids, start, stop, true, &token);
+    }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0);
+    g.def_static("leaf_counts_chunk", []() { return gbrl_hip_leaf_counts_chunk(); });   // leaf counters one launch of leaf_counts holds on chip
     // extension: every ensemble prefix in one walk -- the prediction, or the MultiRMSE loss against targets, after every stops[s] trees
     g.def("predict_staged", &predict_staged_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("stops") = py::none());
     g.def("staged_loss", &staged_loss_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("stops") = py::none());

@@ -391,6 +391,48 @@ int gbrl_hip_staged_loss(gbrl_hip_model *m, const float *obs, int obs_on_device,
     });
 }
 
+int gbrl_hip_predict_leaves(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device, int n_samples,
+                            int n_num_features, int n_cat_features, int start_tree, int stop_tree, int32_t *out, int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.predict_leaves(obs, obs_on_device != 0, cat_obs, cat_on_device != 0, nullptr, false, nullptr, n_samples, n_num_features, n_cat_features,
+                                 start_tree, stop_tree, out, out_on_device != 0);
+    });
+}
+
+int gbrl_hip_predict_leaves_encoded(gbrl_hip_model *m, const float *obs, int obs_on_device, const int32_t *cat_ids, int ids_on_device,
+                                    uint64_t dictionary_token, int n_samples, int n_num_features, int n_cat_features, int start_tree, int stop_tree,
+                                    int32_t *out, int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        if (n_cat_features > 0 && cat_ids == nullptr) throw gbrl::InvalidArgument("Cannot call predict without observations!");
+        m->engine.predict_leaves(obs, obs_on_device != 0, nullptr, false, cat_ids, ids_on_device != 0, &dictionary_token, n_samples, n_num_features,
+                                 n_cat_features, start_tree, stop_tree, out, out_on_device != 0);
+    });
+}
+
+int gbrl_hip_leaf_counts(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device, int n_samples,
+                         int n_num_features, int n_cat_features, int start_tree, int stop_tree, int64_t *out_host) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.leaf_counts(obs, obs_on_device != 0, cat_obs, cat_on_device != 0, nullptr, false, nullptr, n_samples, n_num_features, n_cat_features,
+                              start_tree, stop_tree, out_host);
+    });
+}
+
+int gbrl_hip_leaf_counts_encoded(gbrl_hip_model *m, const float *obs, int obs_on_device, const int32_t *cat_ids, int ids_on_device,
+                                 uint64_t dictionary_token, int n_samples, int n_num_features, int n_cat_features, int start_tree, int stop_tree,
+                                 int64_t *out_host) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        if (n_cat_features > 0 && cat_ids == nullptr) throw gbrl::InvalidArgument("Cannot call predict without observations!");
+        m->engine.leaf_counts(obs, obs_on_device != 0, nullptr, false, cat_ids, ids_on_device != 0, &dictionary_token, n_samples, n_num_features,
+                              n_cat_features, start_tree, stop_tree, out_host);
+    });
+}
+
+int gbrl_hip_leaf_counts_chunk(void) { return gbrl::kern::leaf_counts_chunk(); }
+
 static_assert(static_cast<int>(gbrl::Engine::ParityMode::Default) == GBRL_HIP_PARITY_DEFAULT && static_cast<int>(gbrl::Engine::ParityMode::Reference) == GBRL_HIP_PARITY_REFERENCE &&
               static_cast<int>(gbrl::Engine::ParityMode::ExactArgmax) == GBRL_HIP_PARITY_EXACT_ARGMAX, "the engine's parity modes are the header's");
 int gbrl_hip_set_parity_mode(gbrl_hip_model *m, int mode, int max_node_rows) {

@@ -117,6 +117,19 @@ class Engine {
                         float *out, bool out_dev);
     void staged_loss(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num, int n_cat,
                      const int32_t *stops, int n_stops, double *loss_out);
+    // Extension: where a row lands.  For every tree t of [start_tree, stop_tree) the GLOBAL leaf index -- the row of `values`; minus tree_indices[t]
+    // it is the index within the tree.  Oblivious: tree_indices[t] + sum_d pass(cond[t * max_depth + d]) << (depths[t] - 1 - d).  Greedy: the first
+    // leaf in storage order from tree_indices[t] on whose conditions all hold (a depth-0 leaf never passes, Q7; -1 when the search runs off the
+    // ensemble -- neither happens in a well-formed tree with a split).  stop_tree == 0: n_trees; then 0 <= start_tree < stop_tree <= n_trees or
+    // InvalidArgument, as for a model without trees, the data set errors of predict and a stale dictionary token.  No leaf value is read: no
+    // output_dim limit.  predict_leaves: out int32 [n][stop_tree - start_tree], row-major; n * trees >= 2^31 is Unsupported (slice the range).
+    // leaf_counts: counts_out (host) int64 [n_leaves] over the WHOLE ensemble, entry l = rows of the batch that reach leaf l, 0 outside the range;
+    // reduced on the device with integer atomics (two calls, the same bytes).  Every error is raised before the device is touched.
+    // cat_ids != nullptr: pre-encoded cells and their dictionary token (the _encoded variants); cat is ignored then.
+    void predict_leaves(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token, int n,
+                        int n_num, int n_cat, int start_tree, int stop_tree, int32_t *out, bool out_dev);
+    void leaf_counts(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token, int n,
+                     int n_num, int n_cat, int start_tree, int stop_tree, int64_t *counts_out);
     // GBRL::fit (gbrl.cpp:983-1104) + Fitter::fit_cpu (fitter.cpp:117-261): bias = mean(targets), split candidates from the
     // WHOLE data set once, then `iterations` boosting rounds over consecutive batches of metadata.batch_size rows
     // (predict -> MultiRMSE gradients -> one tree per batch); returns the final MultiRMSE loss on the whole data set.
@@ -152,13 +165,16 @@ class Engine {
    private:
     void ensure_device();
     void sync_model_to_device();
+    void sync_cat_dict();   // the host half of it: cat_dict_ / cat_ids_host_ follow the model (no device needed)
     int32_t *encode_categorical_batch(const char *cat, bool cat_dev, int n, int n_cat);
     struct ContinueBase { const float *base; bool on_device; };   // predict_continue: the held prediction (nullptr in predict_core: an ordinary predict)
     // predict_staged / staged_loss: the checkpoints (host) and, in loss mode, the targets and where the losses go (nullptr in predict_core: no stages)
     struct StagedPlan { const int32_t *stops; int n_stops; bool loss; const float *targets; bool targets_dev; double *loss_out; };
+    // predict_leaves / leaf_counts: where the int32 indices or the int64 counts go (nullptr in predict_core: a call that sums values)
+    struct LeavesPlan { bool counts; int32_t *out; bool out_dev; int64_t *counts_out; };
     void predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
                       int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont = nullptr,
-                      const StagedPlan *staged = nullptr);
+                      const StagedPlan *staged = nullptr, const LeavesPlan *leaves = nullptr);
     uint64_t cat_dict_token();
     void grow_tree(const detail::GrowCtx &c, std::vector<detail::HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc,
                    double &leaf_scale);
@@ -284,6 +300,7 @@ class Engine {
     int cum_cache_b_ = -1;
     // ---- predict workspace + device mirror of the ensemble ----
     DevBuf d_pobs_, d_pcat_, d_pout_;
+    DevBuf d_leaves_out_, d_leaf_counts_;   // predict_leaves: indices bound for the host; leaf_counts: the uint32 counters
     DevBuf d_staged_stops_, d_staged_targets_, d_staged_part_, d_staged_sums_;   // predict_staged / staged_loss: stops table, staged targets, loss partials and sums
     DevBuf m_tree_indices_, m_depths_, m_feature_indices_, m_feature_values_, m_values_, m_is_numerics_, m_ineq_,
         m_cat_ids_, m_bias_, m_opt_start_, m_opt_stop_, m_opt_lr_, m_cond_pack_, m_grd_nodes_, m_grd_off_, m_values_sw_, m_cond_ra_;
@@ -295,6 +312,7 @@ class Engine {
     std::vector<gbrl_hip_optimizer> rate_opts_;   // the optimizers the table was built from
     size_t rate_trees_ = 0;
     uint64_t mirror_version_ = ~0ull;
+    uint64_t dict_model_version_ = ~0ull; size_t dict_splits_ = 0;   // sync_cat_dict(): the model version / split rows cat_dict_ covers
     // dictionary of the categorical strings that occur in the model's conditions: (cat feature, string) -> id >= 1
     std::vector<int32_t> cat_ids_host_, cond_pack_host_, grd_nodes_host_, grd_off_host_, cond_ra_host_;
     std::vector<float> values_sw_host_;   // second-generation oblivious predict: see kern::PredictModel::values_sw

@@ -19,15 +19,16 @@ constexpr int kChainMinTrees = 512;   // below: the tiled kernels are as fast (m
 constexpr int kChainMaxRows = 8192;   // 5000 rows x 20 000 trees: 1.58 -> 0.88 ms, 8192 x 5000: 0.39 -> 0.32 ms; beyond, the leaf search alone costs as much
 
 // ===================================================================================================== predict
-void Engine::sync_model_to_device() {
-    hipStream_t s = stream_;
+// The category dictionary of the model's conditions: host work only, so that a call can check a dictionary token before it needs a device
+// (predict_leaves_encoded).  sync_model_to_device() starts with it; a second call for the same model version does nothing.
+void Engine::sync_cat_dict() {
     const gbrl_hip_metadata &md = model.meta;
-    const size_t T = md.n_trees, L = md.n_leaves, S = model.split_rows(), MD = md.max_depth, D = md.output_dim;
-    if (mirror_version_ == model.version) return;
+    const size_t T = md.n_trees, L = md.n_leaves, S = model.split_rows(), MD = md.max_depth;
+    if (dict_model_version_ == model.version) return;
     // dictionary ids for the categorical conditions (strings are compared on the host once; the device compares ids)
-    if (up_splits_ > S || up_trees_ > T || up_leaves_ > L) { up_splits_ = up_trees_ = up_leaves_ = 0; grd_up_nodes_ = 0; cat_dict_.clear(); cat_ids_host_.clear(); cond_pack_host_.clear(); dict_version_ = static_cast<size_t>(-1); }
+    if (up_splits_ > S || up_trees_ > T || up_leaves_ > L || dict_splits_ > S) { up_splits_ = up_trees_ = up_leaves_ = 0; dict_splits_ = 0; grd_up_nodes_ = 0; cat_dict_.clear(); cat_ids_host_.clear(); cond_pack_host_.clear(); dict_version_ = static_cast<size_t>(-1); }
     cat_ids_host_.resize(S * MD, 0);
-    for (size_t c = up_splits_ * MD; c < S * MD; ++c) {
+    for (size_t c = dict_splits_ * MD; c < S * MD; ++c) {
         if (model.is_numerics[c]) continue;
         const int f = model.feature_indices[c];
         std::string name(&model.categorical_values[c * kCat], kCat);
@@ -37,6 +38,16 @@ void Engine::sync_model_to_device() {
         if (id == 0) { cat_dict_.emplace_back(f, name); id = static_cast<int>(cat_dict_.size()); }
         cat_ids_host_[c] = id;
     }
+    dict_splits_ = S;
+    dict_model_version_ = model.version;
+}
+
+void Engine::sync_model_to_device() {
+    hipStream_t s = stream_;
+    const gbrl_hip_metadata &md = model.meta;
+    const size_t T = md.n_trees, L = md.n_leaves, S = model.split_rows(), MD = md.max_depth, D = md.output_dim;
+    if (mirror_version_ == model.version) return;
+    sync_cat_dict();
     // The appended slices (one new tree after a step: a dozen pieces of a few hundred bytes) are collected here and leave together at the end
     // (flush_segments): staged in ONE pinned block and copied by one kernel launch, instead of a hipMemcpyAsync from pageable memory per
     // piece plus a stream synchronisation -- 0.1 ms per predict-after-step in an RL loop (round 4).
@@ -467,20 +478,49 @@ void Engine::staged_loss(const float *obs, bool obs_dev, const char *cat, bool c
     predict_core(obs, obs_dev, cat, cat_dev, nullptr, false, nullptr, n, n_num, n_cat, 0, 0, nullptr, false, nullptr, &plan);
 }
 
+// Extension: the leaf every tree of [start_tree, stop_tree) routes a row to, or the rows per leaf (kern::predict_leaves / kern::leaf_counts).
+// Input handling, encoding, the device mirror and the validation order are predict_core's.
+void Engine::predict_leaves(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
+                            int n, int n_num, int n_cat, int start_tree, int stop_tree, int32_t *out, bool out_dev) {
+    const LeavesPlan plan{false, out, out_dev, nullptr};
+    predict_core(obs, obs_dev, cat, cat_dev, cat_ids, ids_dev, token, n, n_num, n_cat, start_tree, stop_tree, nullptr, false, nullptr, nullptr, &plan);
+}
+
+void Engine::leaf_counts(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token, int n,
+                         int n_num, int n_cat, int start_tree, int stop_tree, int64_t *counts_out) {
+    const LeavesPlan plan{true, nullptr, false, counts_out};
+    predict_core(obs, obs_dev, cat, cat_dev, cat_ids, ids_dev, token, n, n_num, n_cat, start_tree, stop_tree, nullptr, false, nullptr, nullptr, &plan);
+}
+
 void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
                           int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont,
-                          const StagedPlan *staged) {
+                          const StagedPlan *staged, const LeavesPlan *leaves) {
     gbrl_hip_metadata &md = model.meta;
     // GBRL::predict, gbrl.cpp:378-390
     if (md.iteration == 0) { md.n_num_features = n_num; md.n_cat_features = n_cat; }
     if (n_num + n_cat != md.input_dim) throw InvalidArgument("Incompatible dataset");
     if (n_num != md.n_num_features || n_cat != md.n_cat_features) throw InvalidArgument("Incompatible dataset");
     const bool staged_loss_mode = staged != nullptr && staged->loss;   // (its results are n_stops doubles: there is no `out`)
-    if (n <= 0 || (out == nullptr && !staged_loss_mode)) throw InvalidArgument("Cannot call predict without observations!");
+    const bool no_out = leaves != nullptr && (leaves->counts ? leaves->counts_out == nullptr : leaves->out == nullptr);
+    if (n <= 0 || (out == nullptr && !staged_loss_mode && leaves == nullptr) || no_out) throw InvalidArgument("Cannot call predict without observations!");
     if (n_num > 0 && obs == nullptr) throw InvalidArgument("Cannot call predict without observations!");
     if (n_cat > 0 && cat == nullptr && cat_ids == nullptr) throw InvalidArgument("Cannot call predict without observations!");
-    if (md.output_dim > 128) throw Unsupported("predict: output_dim > 128");
+    if (md.output_dim > 128 && leaves == nullptr) throw Unsupported("predict: output_dim > 128");   // (leaf routing reads no value: any width)
     if (start_tree < 0 || stop_tree < 0) throw InvalidArgument("invalid tree range");   // the reference would index out of bounds
+    if (leaves != nullptr) {
+        // like predict_continue, no reference behaviour to mirror: a range the ensemble does not hold is an error, and so is an empty one
+        // (there is no index to return)
+        if (md.n_trees == 0) throw InvalidArgument("predict_leaves: the model has no trees");
+        const int resolved = stop_tree == 0 ? md.n_trees : stop_tree;
+        if (resolved > md.n_trees || start_tree >= resolved) throw InvalidArgument("predict_leaves: invalid tree range");
+        if (!leaves->counts && static_cast<int64_t>(n) * (resolved - start_tree) >= (int64_t(1) << 31))
+            throw Unsupported("predict_leaves: n_samples x trees >= 2^31 indices: slice the tree range");
+        if (n_cat > 0 && cat_ids != nullptr) {   // the dictionary is host state: a stale token is refused before a device is needed
+            sync_cat_dict();
+            if (token == nullptr || *token != cat_dict_token())
+                throw InvalidArgument("predict: the categorical ids were encoded for another category dictionary (the model has grown or is a different one): encode the batch again");
+        }
+    }
     if (cont != nullptr) {
         // predict_continue has no reference behaviour to mirror: a range the ensemble does not hold is an error, never a silent no-op (a cache
         // that is handed back unchanged is a stale prediction)
@@ -507,11 +547,11 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     // predict_cpu, predictor.cpp:127-141
     int stop = stop_tree;
     if (staged != nullptr) { start_tree = 0; stop = 0; }         // (the stops table is the range)
-    else if (cont != nullptr) { if (stop == 0) stop = md.n_trees; }   // (validated above)
+    else if (cont != nullptr || leaves != nullptr) { if (stop == 0) stop = md.n_trees; }   // (validated above)
     else if (md.n_trees == 0 || stop > md.n_trees || model.opts.empty()) { start_tree = 0; stop = 0; }
     else if (stop == 0) stop = md.n_trees;
     // an empty or inverted range walks no tree: predict_cpu's loops run from start to stop (predictor.cpp:139-163), the result is the bias
-    if (start_tree >= stop && cont == nullptr) { start_tree = 0; stop = 0; }
+    if (start_tree >= stop && cont == nullptr && leaves == nullptr) { start_tree = 0; stop = 0; }
     sync_model_to_device();
     phase_begin();
     const float *dobs = obs;
@@ -535,7 +575,7 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     }
     const size_t out_floats = static_cast<size_t>(n) * D * (staged != nullptr ? static_cast<size_t>(staged->n_stops) : 1);
     float *dout = out;
-    if (!out_dev && !staged_loss_mode) dout = static_cast<float *>(d_pout_.ensure(sizeof(float) * out_floats));
+    if (!out_dev && !staged_loss_mode && leaves == nullptr) dout = static_cast<float *>(d_pout_.ensure(sizeof(float) * out_floats));
     kern::StagedStops dstops{nullptr, 0, 0};
     const float *dtargets = nullptr;
     if (staged != nullptr) {   // the stops table lives on the device (the pageable copy has left the host array when the call returns)
@@ -601,7 +641,7 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
         const char *no_pc = hooks::raw(hooks::PREDICT_NO_PC), *no_reg = hooks::raw(hooks::PREDICT_NO_REG), *mr = hooks::raw(hooks::PREDICT_REG_MIN_ROWS);
         const int min_rows = mr ? std::atoi(mr) : 32768;
         const bool fp32_takes_it = n_cat == 0 && n_num <= 128 && (n_num & 3) == 0 && (reinterpret_cast<uintptr_t>(dobs) & 15) == 0 && !(no_reg && no_reg[0] == '1');
-        if (cont == nullptr && staged == nullptr && !(no_pc && no_pc[0] == '1') && !in_fit_ && pm.values_sw != nullptr && model.oblivious() && n >= min_rows && !fp32_takes_it &&
+        if (cont == nullptr && staged == nullptr && leaves == nullptr && !(no_pc && no_pc[0] == '1') && !in_fit_ && pm.values_sw != nullptr && model.oblivious() && n >= min_rows && !fp32_takes_it &&
             kern::predict_pc_shape_ok(pm.obl2_maxd, D) && ensure_pc_book(n_num, n_cat)) {
             pm.pc_cond = m_pc_cond_.as<int32_t>();
             pm.pc_thr = m_pc_thr_.as<float>();
@@ -634,6 +674,31 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     if (model.opts.size() > 255) pm.coef_ok = pm.coef_ok && !model.scheduled();   // (owner is a byte; D <= 64 bounds the optimizers of a covered model anyway)
     // Linear schedules: the kernels of predict_sched.hip read the rate of (tree, optimizer) from the mirror's table
     pm.rate = (model.scheduled() && md.n_trees > 0) ? m_rate_.as<float>() : nullptr;
+    if (leaves != nullptr) {
+        const bool generic = hooks::on(hooks::LEAVES_GENERIC);
+        if (leaves->counts) {
+            const size_t L = static_cast<size_t>(md.n_leaves);
+            uint32_t *dcounts = static_cast<uint32_t *>(d_leaf_counts_.ensure(sizeof(uint32_t) * std::max<size_t>(L, 1)));
+            hip_check(hipMemsetAsync(dcounts, 0, sizeof(uint32_t) * L, s), "zero leaf counters");
+            kern::leaf_counts(pm, model.tree_indices.data(), dobs, n_num, dcat, n_cat, n, start_tree, stop, dcounts, generic, s);
+            hip_check(hipGetLastError(), "leaf_counts launch");
+            phase_end("predict", /*key=*/true);
+            std::vector<uint32_t> h(L);
+            hip_check(hipMemcpyAsync(h.data(), dcounts, sizeof(uint32_t) * L, hipMemcpyDeviceToHost, s), "D2H leaf counts");
+            hip_check(hipStreamSynchronize(s), "sync");
+            for (size_t l = 0; l < L; ++l) leaves->counts_out[l] = static_cast<int64_t>(h[l]);   // (n < 2^31 rows: a counter cannot wrap)
+        } else {
+            const size_t ints = static_cast<size_t>(n) * (stop - start_tree);
+            int32_t *dl = leaves->out_dev ? leaves->out : static_cast<int32_t *>(d_leaves_out_.ensure(sizeof(int32_t) * ints));
+            kern::predict_leaves(pm, dobs, n_num, dcat, n_cat, n, start_tree, stop, dl, generic, s);
+            hip_check(hipGetLastError(), "predict_leaves launch");
+            phase_end("predict", /*key=*/true);
+            if (!leaves->out_dev) hip_check(hipMemcpyAsync(leaves->out, dl, sizeof(int32_t) * ints, hipMemcpyDeviceToHost, s), "D2H leaves");
+            hip_check(hipStreamSynchronize(s), "sync");
+        }
+        phases_resolve();
+        return;
+    }
     if (staged != nullptr) {
         double *dpart = nullptr, *dsums = nullptr;
         if (staged->loss) {

@@ -23,6 +23,7 @@ namespace hooks {
     X(HIST_PIPE) \
     X(HOST_CATEGORICAL) \
     X(KEEP_LAST_DERIVED) \
+    X(LEAVES_GENERIC) \
     X(NEARTIE_DEBUG) \
     X(NEARTIE_MAX_ROWS) \
     X(NEARTIE_REL) \

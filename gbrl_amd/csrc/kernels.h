@@ -567,6 +567,20 @@ struct StagedStops { const int32_t *stops; int n_stops; int last_stop; };
 int staged_loss_partials(int n);
 void predict_staged(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, const StagedStops &st, float *out,
                     const float *targets, double *part, double *sums, bool generic, hipStream_t s);
+// Where a row lands (predict_leaves.hip): the GLOBAL leaf index -- the row of `values` -- that each tree of [start_tree, stop_tree) routes a row to.
+// Oblivious: tree_indices[t] + the bits of the tree's conditions.  Greedy: the first leaf in storage order from tree_indices[t] on whose conditions
+// all hold; a depth-0 leaf never passes (Q7), and -1 when the search runs off the ensemble.  No leaf value is read: no limit on output_dim.
+// predict_leaves: out is device int32 [n][stop_tree - start_tree], row-major (the caller keeps n * trees < 2^31).
+// leaf_counts: counts is device uint32 [n_leaves], ZEROED by the caller on `s`; counts[l] += rows that reach leaf l.  The counters of a run of
+// trees are kept in LDS (at most kLeafCountChunk per launch; longer ranges are cut into runs of whole trees, one launch each, the rows re-read
+// per run) and added to `counts` once per block.  tree_first_leaf: the HOST copy of tree_indices (the runs are planned on the host).
+// generic: the one-thread-per-row kernels only (GBRL_HIP_LEAVES_GENERIC=1; same bytes).  Both always launch.
+constexpr int kLeafCountChunk = 4096;   // 16 KiB of counters behind the 64-row tile
+int leaf_counts_chunk();
+void predict_leaves(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree, int32_t *out,
+                    bool generic, hipStream_t s);
+void leaf_counts(const PredictModel &pm, const int32_t *tree_first_leaf, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree,
+                 int stop_tree, uint32_t *counts, bool generic, hipStream_t s);
 
 // ---- Linear TreeSHAP (shap.hip): a uniform program over explicit trees, one thread per (sample, output) ----
 enum { SHAP_ENTER = 0, SHAP_AFTER_LEFT = 1, SHAP_AFTER_RIGHT = 2, SHAP_EXIT = 3 };

@@ -236,6 +236,38 @@ int gbrl_hip_staged_loss(gbrl_hip_model *m, const float *obs, int obs_on_device,
                          const float *targets, int targets_on_device, int n_samples, int n_num_features, int n_cat_features,
                          const int32_t *stops, int n_stops, double *loss_out);
 
+/* Extension (sklearn's apply, XGBoost's and LightGBM's pred_leaf, CatBoost's calc_leaf_indexes): WHERE a row lands.  For a row and a tree t of
+ * [start_tree, stop_tree) the answer is the GLOBAL leaf index: the row of `values` in the ensemble data; minus tree_indices[t] it is the index
+ * within the tree.
+ *   oblivious trees: tree_indices[t] + sum over d of pass(condition d of tree t) << (depth of t - 1 - d); a numeric condition passes when
+ *                    x[feature] > threshold, a categorical one when the cell equals its category; a tree of depth 0 gives tree_indices[t].
+ *   greedy trees:    the first leaf in storage order from tree_indices[t] on whose conditions all hold, each tested against its inequality
+ *                    direction.  As in the reference's walk, a leaf of depth 0 never passes (the search then runs on into the following trees)
+ *                    and a search that runs off the ensemble gives -1; a well-formed tree with at least one split does neither.
+ * Range: stop_tree == 0 means n_trees; after that 0 <= start_tree < stop_tree <= n_trees is required.  Reported with GBRL_HIP_E_INVALID before
+ * the device is touched: any other range, a model without trees, the data set errors of gbrl_hip_predict, a stale dictionary token.  No leaf
+ * value is read, so there is NO output_dim limit.  Row-sharded models need no exchange: each rank answers for its own rows.
+ *   gbrl_hip_predict_leaves[_encoded]: `out` is int32 [n_samples, stop_tree - start_tree], row-major, host or device per out_on_device.
+ *                    n_samples * (stop_tree - start_tree) >= 2^31 is refused with GBRL_HIP_E_UNSUPPORTED, also before the device is touched:
+ *                    slice the tree range.
+ *   gbrl_hip_leaf_counts[_encoded]: out_host is a HOST array of n_leaves int64, indexed by global leaf over the WHOLE ensemble: entry l is the
+ *                    number of rows of this batch that reach leaf l; leaves of trees outside the range are 0.  Reduced on the device with
+ *                    integer atomics only (the index matrix is never materialised): two identical calls return identical bytes.  The counters
+ *                    of at most gbrl_hip_leaf_counts_chunk() leaves are held on chip per launch; a longer range is processed in runs of whole
+ *                    trees, and the rows are read once per run. */
+int gbrl_hip_predict_leaves(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device,
+                            int n_samples, int n_num_features, int n_cat_features, int start_tree, int stop_tree,
+                            int32_t *out, int out_on_device);
+int gbrl_hip_predict_leaves_encoded(gbrl_hip_model *m, const float *obs, int obs_on_device, const int32_t *cat_ids, int ids_on_device,
+                                    uint64_t dictionary_token, int n_samples, int n_num_features, int n_cat_features,
+                                    int start_tree, int stop_tree, int32_t *out, int out_on_device);
+int gbrl_hip_leaf_counts(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device,
+                         int n_samples, int n_num_features, int n_cat_features, int start_tree, int stop_tree, int64_t *out_host);
+int gbrl_hip_leaf_counts_encoded(gbrl_hip_model *m, const float *obs, int obs_on_device, const int32_t *cat_ids, int ids_on_device,
+                                 uint64_t dictionary_token, int n_samples, int n_num_features, int n_cat_features,
+                                 int start_tree, int stop_tree, int64_t *out_host);
+int gbrl_hip_leaf_counts_chunk(void);   /* leaf counters one launch of leaf_counts holds on chip (diagnostic; no device needed) */
+
 /* ---- row-sharded multi-GPU (new; the reference is single-GPU) ------------------------------------------ */
 /* One process per GPU, each holding a contiguous block of rows.  When hooks are installed, step() calls them at
  * its exchange points so that every rank grows the identical tree; predict() needs no exchange.  Buffers are
