@@ -416,6 +416,40 @@ py::object staged_loss_impl(PyGBRL &self, py::object &obs, py::object &cat, py::
     return loss;
 }
 
+// Extension: refit_leaves(obs, categorical_obs, targets, start_tree_idx=0, stop_tree_idx=0, decay_rate=0.0): the leaf values of the trees
+// [start, stop) fitted again on this batch, the structure kept (include/gbrl_hip.h).  Returns the MultiRMSE loss of the refitted prefix, a float:
+// staged_loss(obs, categorical_obs, targets, stops=[stop])[0] called right after, bit for bit.
+double refit_leaves_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, py::object start_obj, py::object stop_obj, double decay) {
+    const gbrl_hip_metadata md = self.meta();
+    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
+    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    Input o = read_input(obs, "obs", true, "refit_leaves", false);
+    Input c = read_input(cat, "cat_obs", true, "refit_leaves", 1);
+    if (!o.ptr && !c.ptr) fail("Cannot call refit_leaves without observations!");
+    Input y = read_input(targets, "targets", true, "refit_leaves", false);
+    if (!y.ptr) fail("Cannot call refit_leaves without targets!");
+    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const int n = bs.n, D = md.output_dim;
+    const bool shape_ok = (y.shape.size() == 2 && y.shape[0] == static_cast<size_t>(n) && y.shape[1] == static_cast<size_t>(D)) ||
+                          (y.shape.size() == 1 && D == 1 && y.shape[0] == static_cast<size_t>(n));
+    if (!shape_ok) {
+        std::stringstream ss;
+        ss << "Expected targets of shape (" << n << ", " << D << ")" << (D == 1 ? " or (" + std::to_string(n) + ",)" : std::string()) << ", but got (";
+        for (size_t i = 0; i < y.shape.size(); ++i) ss << (i ? ", " : "") << y.shape[i];
+        ss << ")";
+        fail(ss.str());
+    }
+    double loss = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_refit_leaves(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device,
+                                   static_cast<const float *>(y.ptr), y.on_device, n, bs.n_num, bs.n_cat, start, stop, decay, &loss);
+    }
+    check(rc);
+    return loss;
+}
+
 // Extension: predict_leaves(obs, categorical_obs, start, stop) / leaf_counts(...) and their _encoded variants (obs, ids, token, start, stop): where
 // a row lands (include/gbrl_hip.h).  predict_leaves returns int32 [n, stop - start] global leaf indices -- NumPy for a "cpu" model, a DLPack
 // capsule on the model's device for a "cuda" one; leaf_counts returns int64 NumPy [n_leaves], the rows of the batch per global leaf.
@@ -772,6 +806,14 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     // extension: every ensemble prefix in one walk -- the prediction, or the MultiRMSE loss against targets, after every stops[s] trees
     g.def("predict_staged", &predict_staged_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("stops") = py::none());
     g.def("staged_loss", &staged_loss_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("stops") = py::none());
+    // extension: the leaf values of a tree range fitted again on new data, the structure kept; returns the loss of the refitted prefix
+    g.def("refit_leaves", &refit_leaves_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("start_tree_idx") = 0,
+          py::arg("stop_tree_idx") = 0, py::arg("decay_rate") = 0.0,
+          "refit_leaves(obs, categorical_obs, targets, start_tree_idx=0, stop_tree_idx=0, decay_rate=0.0) -> float\n\n"
+          "Fit the leaf values of the trees [start_tree_idx, stop_tree_idx) again on this batch; the structure stays.  stop_tree_idx == 0 means n_trees.\n"
+          "New value = decay_rate * old + (1 - decay_rate) * the leaf mean of fit()'s MultiRMSE gradient; a leaf without rows keeps its value.\n"
+          "Returns staged_loss(obs, categorical_obs, targets, stops=[stop_tree_idx])[0] of the refitted model.  Trees behind stop_tree_idx are not\n"
+          "touched and are stale with respect to the new prefix.");
     g.def("fit", &fit_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("iterations"),
           py::arg("shuffle") = true, py::arg("loss_type") = "MultiRMSE");
     g.def("set_bias", [](PyGBRL &self, py::object &bias) {

@@ -431,6 +431,16 @@ int gbrl_hip_leaf_counts_encoded(gbrl_hip_model *m, const float *obs, int obs_on
     });
 }
 
+int gbrl_hip_refit_leaves(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device, const float *targets,
+                          int targets_on_device, int n_samples, int n_num_features, int n_cat_features, int start_tree, int stop_tree, double decay_rate,
+                          double *loss_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.refit_leaves(obs, obs_on_device != 0, cat_obs, cat_on_device != 0, targets, targets_on_device != 0, n_samples, n_num_features,
+                               n_cat_features, start_tree, stop_tree, decay_rate, loss_out);
+    });
+}
+
 int gbrl_hip_leaf_counts_chunk(void) { return gbrl::kern::leaf_counts_chunk(); }
 
 static_assert(static_cast<int>(gbrl::Engine::ParityMode::Default) == GBRL_HIP_PARITY_DEFAULT && static_cast<int>(gbrl::Engine::ParityMode::Reference) == GBRL_HIP_PARITY_REFERENCE &&

@@ -130,6 +130,15 @@ class Engine {
                         int n_num, int n_cat, int start_tree, int stop_tree, int32_t *out, bool out_dev);
     void leaf_counts(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token, int n,
                      int n_num, int n_cat, int start_tree, int stop_tree, int64_t *counts_out);
+    // Extension: refit the leaf values of the trees [start_tree, stop_tree) on a batch, the structure kept (kern::refit_leaves; include/gbrl_hip.h
+    // has the contract).  stop_tree == 0: n_trees; then 0 <= start_tree < stop_tree <= n_trees.  decay_rate in [0, 1]: new value = decay * old +
+    // (1 - decay) * leaf mean of fit()'s MultiRMSE gradient.  Only model.values of the range changes; *loss_out = staged_loss(..., {stop_tree})
+    // of the refitted model.  One enqueue for the whole range and one wait; every argument error is raised before the device is touched, a
+    // run that meets a non-finite gradient is InvalidArgument, and after any failure the model (host and device mirror) is unchanged.
+    // A model with a communicator or collective hooks is Unsupported (the sums would need an exchange per tree), and so is a greedy tree of
+    // depth 0 among the trees [start_tree - 1, stop_tree) (the prediction walks past it into values that are not refitted yet).
+    void refit_leaves(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num, int n_cat,
+                      int start_tree, int stop_tree, double decay_rate, double *loss_out);
     // GBRL::fit (gbrl.cpp:983-1104) + Fitter::fit_cpu (fitter.cpp:117-261): bias = mean(targets), split candidates from the
     // WHOLE data set once, then `iterations` boosting rounds over consecutive batches of metadata.batch_size rows
     // (predict -> MultiRMSE gradients -> one tree per batch); returns the final MultiRMSE loss on the whole data set.
@@ -165,6 +174,7 @@ class Engine {
    private:
     void ensure_device();
     void sync_model_to_device();
+    void invalidate_mirror();   // values of existing trees have changed (refit_leaves): the append-only mirror is uploaded again, the dictionary stays
     void sync_cat_dict();   // the host half of it: cat_dict_ / cat_ids_host_ follow the model (no device needed)
     int32_t *encode_categorical_batch(const char *cat, bool cat_dev, int n, int n_cat);
     struct ContinueBase { const float *base; bool on_device; };   // predict_continue: the held prediction (nullptr in predict_core: an ordinary predict)
@@ -172,9 +182,13 @@ class Engine {
     struct StagedPlan { const int32_t *stops; int n_stops; bool loss; const float *targets; bool targets_dev; double *loss_out; };
     // predict_leaves / leaf_counts: where the int32 indices or the int64 counts go (nullptr in predict_core: a call that sums values)
     struct LeavesPlan { bool counts; int32_t *out; bool out_dev; int64_t *counts_out; };
+    // refit_leaves: the range is checked by the caller; predict_core stages the inputs and the mirror, runs the refit and books it
+    struct RefitPlan { const float *targets; bool targets_dev; double decay; double *loss_out; };
+    void refit_run(const kern::PredictModel &pm, const float *dobs, const int32_t *dcat, const float *dtargets, int n, int n_num, int n_cat, int start_tree,
+                   int stop, const RefitPlan &plan);   // engine_refit.hip: called by predict_core with the inputs staged and the mirror in step
     void predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
                       int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont = nullptr,
-                      const StagedPlan *staged = nullptr, const LeavesPlan *leaves = nullptr);
+                      const StagedPlan *staged = nullptr, const LeavesPlan *leaves = nullptr, const RefitPlan *refit = nullptr);
     uint64_t cat_dict_token();
     void grow_tree(const detail::GrowCtx &c, std::vector<detail::HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc,
                    double &leaf_scale);
@@ -301,6 +315,7 @@ class Engine {
     // ---- predict workspace + device mirror of the ensemble ----
     DevBuf d_pobs_, d_pcat_, d_pout_;
     DevBuf d_leaves_out_, d_leaf_counts_;   // predict_leaves: indices bound for the host; leaf_counts: the uint32 counters
+    DevBuf d_refit_p_, d_refit_leaf_, d_refit_acc_, d_refit_values_, d_refit_gmax_;   // refit_leaves: running prediction, leaf per row, int64 sums, new values, max |g| per tree
     DevBuf d_staged_stops_, d_staged_targets_, d_staged_part_, d_staged_sums_;   // predict_staged / staged_loss: stops table, staged targets, loss partials and sums
     DevBuf m_tree_indices_, m_depths_, m_feature_indices_, m_feature_values_, m_values_, m_is_numerics_, m_ineq_,
         m_cat_ids_, m_bias_, m_opt_start_, m_opt_stop_, m_opt_lr_, m_cond_pack_, m_grd_nodes_, m_grd_off_, m_values_sw_, m_cond_ra_;

@@ -42,6 +42,18 @@ void Engine::sync_cat_dict() {
     dict_model_version_ = model.version;
 }
 
+// The mirror below only ever appends: up_trees_ / up_leaves_ / up_splits_ say how much of the ensemble is on the device, and the pre-swizzled
+// values, the greedy node records and the packed conditions are extended from there.  When values of EXISTING trees change (refit_leaves) all of
+// it is stale; counting the uploaded part as empty makes the next sync_model_to_device() build and upload every derived array again (the
+// code book of the packed-code path and the SHAP program follow model.version by themselves).  The category dictionary is NOT reset -- unlike
+// the reset branch of sync_cat_dict(): the conditions have not changed, so ids encoded before the refit and the dictionary token stay valid.
+void Engine::invalidate_mirror() {
+    up_trees_ = up_leaves_ = up_splits_ = 0;
+    grd_up_nodes_ = 0;
+    rate_trees_ = 0;
+    mirror_version_ = ~0ull;
+}
+
 void Engine::sync_model_to_device() {
     hipStream_t s = stream_;
     const gbrl_hip_metadata &md = model.meta;
@@ -494,7 +506,7 @@ void Engine::leaf_counts(const float *obs, bool obs_dev, const char *cat, bool c
 
 void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
                           int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont,
-                          const StagedPlan *staged, const LeavesPlan *leaves) {
+                          const StagedPlan *staged, const LeavesPlan *leaves, const RefitPlan *refit) {
     gbrl_hip_metadata &md = model.meta;
     // GBRL::predict, gbrl.cpp:378-390
     if (md.iteration == 0) { md.n_num_features = n_num; md.n_cat_features = n_cat; }
@@ -502,7 +514,7 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     if (n_num != md.n_num_features || n_cat != md.n_cat_features) throw InvalidArgument("Incompatible dataset");
     const bool staged_loss_mode = staged != nullptr && staged->loss;   // (its results are n_stops doubles: there is no `out`)
     const bool no_out = leaves != nullptr && (leaves->counts ? leaves->counts_out == nullptr : leaves->out == nullptr);
-    if (n <= 0 || (out == nullptr && !staged_loss_mode && leaves == nullptr) || no_out) throw InvalidArgument("Cannot call predict without observations!");
+    if (n <= 0 || (out == nullptr && !staged_loss_mode && leaves == nullptr && refit == nullptr) || no_out) throw InvalidArgument("Cannot call predict without observations!");
     if (n_num > 0 && obs == nullptr) throw InvalidArgument("Cannot call predict without observations!");
     if (n_cat > 0 && cat == nullptr && cat_ids == nullptr) throw InvalidArgument("Cannot call predict without observations!");
     if (md.output_dim > 128 && leaves == nullptr) throw Unsupported("predict: output_dim > 128");   // (leaf routing reads no value: any width)
@@ -547,11 +559,11 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     // predict_cpu, predictor.cpp:127-141
     int stop = stop_tree;
     if (staged != nullptr) { start_tree = 0; stop = 0; }         // (the stops table is the range)
-    else if (cont != nullptr || leaves != nullptr) { if (stop == 0) stop = md.n_trees; }   // (validated above)
+    else if (cont != nullptr || leaves != nullptr || refit != nullptr) { if (stop == 0) stop = md.n_trees; }   // (validated above)
     else if (md.n_trees == 0 || stop > md.n_trees || model.opts.empty()) { start_tree = 0; stop = 0; }
     else if (stop == 0) stop = md.n_trees;
     // an empty or inverted range walks no tree: predict_cpu's loops run from start to stop (predictor.cpp:139-163), the result is the bias
-    if (start_tree >= stop && cont == nullptr && leaves == nullptr) { start_tree = 0; stop = 0; }
+    if (start_tree >= stop && cont == nullptr && leaves == nullptr && refit == nullptr) { start_tree = 0; stop = 0; }
     sync_model_to_device();
     phase_begin();
     const float *dobs = obs;
@@ -575,7 +587,7 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     }
     const size_t out_floats = static_cast<size_t>(n) * D * (staged != nullptr ? static_cast<size_t>(staged->n_stops) : 1);
     float *dout = out;
-    if (!out_dev && !staged_loss_mode && leaves == nullptr) dout = static_cast<float *>(d_pout_.ensure(sizeof(float) * out_floats));
+    if (!out_dev && !staged_loss_mode && leaves == nullptr && refit == nullptr) dout = static_cast<float *>(d_pout_.ensure(sizeof(float) * out_floats));
     kern::StagedStops dstops{nullptr, 0, 0};
     const float *dtargets = nullptr;
     if (staged != nullptr) {   // the stops table lives on the device (the pageable copy has left the host array when the call returns)
@@ -589,6 +601,14 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
                 hip_check(hipMemcpyAsync(dt, staged->targets, sizeof(float) * static_cast<size_t>(n) * D, hipMemcpyHostToDevice, s), "H2D targets");
                 dtargets = dt;
             }
+        }
+    }
+    if (refit != nullptr) {
+        dtargets = refit->targets;
+        if (!refit->targets_dev) {
+            float *dt = static_cast<float *>(d_staged_targets_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+            hip_check(hipMemcpyAsync(dt, refit->targets, sizeof(float) * static_cast<size_t>(n) * D, hipMemcpyHostToDevice, s), "H2D targets");
+            dtargets = dt;
         }
     }
     const float *dbase = nullptr;
@@ -674,6 +694,10 @@ void Engine::predict_core(const float *obs, bool obs_dev, const char *cat, bool 
     if (model.opts.size() > 255) pm.coef_ok = pm.coef_ok && !model.scheduled();   // (owner is a byte; D <= 64 bounds the optimizers of a covered model anyway)
     // Linear schedules: the kernels of predict_sched.hip read the rate of (tree, optimizer) from the mirror's table
     pm.rate = (model.scheduled() && md.n_trees > 0) ? m_rate_.as<float>() : nullptr;
+    if (refit != nullptr) {   // engine_refit.hip: the run, the read-back and the booking
+        refit_run(pm, dobs, dcat, dtargets, n, n_num, n_cat, start_tree, stop, *refit);
+        return;
+    }
     if (leaves != nullptr) {
         const bool generic = hooks::on(hooks::LEAVES_GENERIC);
         if (leaves->counts) {

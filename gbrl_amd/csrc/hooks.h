@@ -56,6 +56,7 @@ namespace hooks {
     X(QUANTILE_RADIX) \
     X(QUANTILE_SAMPLE) \
     X(RADIX_PLAIN_LOADS) \
+    X(REFIT_GENERIC) \
     X(ROOT_COUNTS) \
     X(SHAP_DEVICE_ONLY) \
     X(SHAP_HOST) \

@@ -567,6 +567,9 @@ struct StagedStops { const int32_t *stops; int n_stops; int last_stop; };
 int staged_loss_partials(int n);
 void predict_staged(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, const StagedStops &st, float *out,
                     const float *targets, double *part, double *sums, bool generic, hipStream_t s);
+// The loss stage of predict_staged for predictions the caller already holds (device [n][D]): *sum = what sums[s] is for a stage with these
+// bits -- the same row sums, butterflies and finishing tree.  part: scratch for staged_loss_partials(n) doubles.
+void staged_loss_of_predictions(const float *preds, const float *targets, int n, int D, double *part, double *sum, hipStream_t s);
 // Where a row lands (predict_leaves.hip): the GLOBAL leaf index -- the row of `values` -- that each tree of [start_tree, stop_tree) routes a row to.
 // Oblivious: tree_indices[t] + the bits of the tree's conditions.  Greedy: the first leaf in storage order from tree_indices[t] on whose conditions
 // all hold; a depth-0 leaf never passes (Q7), and -1 when the search runs off the ensemble.  No leaf value is read: no limit on output_dim.
@@ -581,6 +584,25 @@ void predict_leaves(const PredictModel &pm, const float *obs, int F, const int32
                     bool generic, hipStream_t s);
 void leaf_counts(const PredictModel &pm, const int32_t *tree_first_leaf, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree,
                  int stop_tree, uint32_t *counts, bool generic, hipStream_t s);
+
+// Refit the leaf values of the trees [start_tree, stop_tree) on a batch, the structure kept (refit.hip).  Everything is enqueued on `s`; nothing
+// is read back and the host never waits.  Per tree t, in order: g = fl32(P - targets); the fixed point 2^lbits from gmax[t - start_tree] by the
+// step's rule (leaf_sum_bits_dev, n = the rows of this call); per leaf of the tree, routed as predict_leaves routes, the exact int64 sums of
+// llrint((double)g * 2^lbits) and the row count (integer atomics: the same bytes on every run and on both kernel families); the new value
+// (float)(sum / 2^lbits / count), mixed as decay * old + keep * mean (two rounded float64 products, one rounded sum) when decay != 0 -- a leaf
+// without rows and a leaf of depth 0 keep the old value; P = fma(-rate(t, o), new value, P) for every optimizer o that owns the output (a row
+// whose greedy search left the tree keeps its P and joins no sum); gmax[t + 1 - start_tree] from the new P.  pm.values is only read.
+//   P           [n][D]      scratch; on return the prediction of the refitted ensemble over [0, stop_tree): predict_continue's bits
+//   leaf_idx    [n]         scratch: the global leaf of the current tree per row
+//   acc         [leaves of the range][D + 1] int64 sums | count, ZEROED by the caller on `s`; acc + (tree_first_leaf[t] - tree_first_leaf[start]) * (D + 1)
+//   new_values  [leaves of the range][D]: the result (rows of `values` from tree_first_leaf[start_tree] on)
+//   gmax        [trees of the range + 1] uint32, ZEROED by the caller: the bits of max |g| before each tree and, last, of the final P; a NaN
+//               as +inf; the caller rejects the run when one is not finite
+// tree_first_leaf: the HOST copy of tree_indices.  generic: the one-thread-per-row kernels only (GBRL_HIP_REFIT_GENERIC=1; same bytes).
+// Returns the number of trees whose accumulate pass took the streaming kernel (a diagnostic: the tests pin the path with it).
+int refit_leaves(const PredictModel &pm, const int32_t *tree_first_leaf, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree,
+                 int stop_tree, double decay, const float *targets, float *P, int32_t *leaf_idx, unsigned long long *acc, float *new_values,
+                 uint32_t *gmax, bool generic, hipStream_t s);
 
 // ---- Linear TreeSHAP (shap.hip): a uniform program over explicit trees, one thread per (sample, output) ----
 enum { SHAP_ENTER = 0, SHAP_AFTER_LEFT = 1, SHAP_AFTER_RIGHT = 2, SHAP_EXIT = 3 };

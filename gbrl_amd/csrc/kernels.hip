@@ -122,9 +122,9 @@ __global__ __launch_bounds__(256) void k_stats_finish(const double *__restrict__
     }
     if (threadIdx.x == 0) {
         const float hraw = m1[0], hbuild = stat_centred ? m0[0] : m1[0];
-        int sbits = 20, lbits = 40;
+        int sbits = 20;
         if (hbuild > 0.f && hbuild < INFINITY) sbits = min(100, ilog2_floor_dev(2147483647.0 / (static_cast<double>(chunk_rows) * hbuild)) - 1);
-        if (hraw > 0.f && hraw < INFINITY) lbits = min(60, ilog2_floor_dev(4.0e18 / (static_cast<double>(n) * hraw)) - 1);
+        const int lbits = leaf_sum_bits_dev(n, hraw);
         StepScales o{};
         o.sbits = sbits; o.lbits = lbits;
         o.scale = static_cast<float>(ldexp(1.0, sbits));

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 
@@ -22,6 +23,17 @@ __device__ __forceinline__ uint32_t float_to_key(float x) {
 __device__ __forceinline__ float key_to_float(uint32_t k) {
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __uint_as_float(u);
+}
+
+__device__ __forceinline__ int ilog2_floor_dev(double x) { int e; (void)frexp(x, &e); return e - 1; }
+
+// Bits of the int64 fixed point of the leaf sums: 2^lbits scales the raw gradients of a batch of n rows whose largest magnitude is hraw, so
+// that n * hraw * 2^lbits < 2^61 and no exact sum can wrap.  40 when hraw is 0 or not finite (the caller rejects the latter).  ONE rule for
+// the step (k_stats_finish, small_stats_body) and for kern::refit_leaves, which must store what the step would have stored.
+__device__ __forceinline__ int leaf_sum_bits_dev(long long n, float hraw) {
+    int lbits = 40;
+    if (hraw > 0.f && hraw < INFINITY) lbits = min(60, ilog2_floor_dev(4.0e18 / (static_cast<double>(n) * hraw)) - 1);
+    return lbits;
 }
 
 inline int grid_for(size_t n, int bs, int cap) {

@@ -268,6 +268,24 @@ __global__ __launch_bounds__(kFinishThreads) void k_staged_finish(const double *
     if (threadIdx.x == 0) sums[blockIdx.x] = sh[0];
 }
 
+// the loss checkpoint of k_staged_general on predictions that already exist (kern::staged_loss_of_predictions): the same row sum, the same
+// butterfly over the same 64 rows, the same part[] entry
+__global__ __launch_bounds__(256) void k_loss_of_predictions(const float *__restrict__ preds, const float *__restrict__ targets, int n, int D,
+                                                             double *__restrict__ part, int nb) {
+    const size_t row = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    double acc = 0.0;
+    if (row < static_cast<size_t>(n)) {
+        const float *p = preds + row * D, *y = targets + row * D;
+        for (int j = 0; j < D; ++j) {
+            const double g = static_cast<double>(__fsub_rn(p[j], y[j]));
+            acc = fma(g, g, acc);
+        }
+    }
+    acc = staged_wave_sum(acc);
+    const size_t wave = row / kStagedRows;
+    if ((threadIdx.x & (kStagedRows - 1)) == 0 && wave < static_cast<size_t>(nb)) part[wave] = acc;
+}
+
 template <int DMAX, bool GREEDY, bool LOSS>
 bool launch_staged(const StagedModel &cm, const StagedIo &io, const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n,
                    hipStream_t s) {
@@ -325,6 +343,12 @@ void staged_dispatch(const StagedModel &cm, const StagedIo &io, const PredictMod
 }  // namespace
 
 int staged_loss_partials(int n) { return (n + kStagedRows - 1) / kStagedRows; }
+
+void staged_loss_of_predictions(const float *preds, const float *targets, int n, int D, double *part, double *sum, hipStream_t s) {
+    const int nb = staged_loss_partials(n);
+    hipLaunchKernelGGL(k_loss_of_predictions, dim3((n + 255) / 256), dim3(256), 0, s, preds, targets, n, D, part, nb);
+    hipLaunchKernelGGL(k_staged_finish, dim3(1), dim3(kFinishThreads), 0, s, part, nb, sum);
+}
 
 void predict_staged(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, const StagedStops &st, float *out,
                     const float *targets, double *part, double *sums, bool generic, hipStream_t s) {

@@ -16,8 +16,6 @@ namespace gbrl {
 namespace kern {
 namespace {
 
-__device__ __forceinline__ int ilog2_floor_dev(double x) { int e; (void)frexp(x, &e); return e - 1; }
-
 // ------------------------------------------------------------------------------------------------------------
 // RL-sized batches (round 4): the whole statistics chain -- column sums, mean, centred squares, std / maxima / scales, quantisation --
 // in ONE block.  The chain above takes seven launches for an L2 step; at a few thousand rows each of them is pure launch latency.
@@ -142,9 +140,9 @@ __device__ __forceinline__ void small_stats_body(const float *__restrict__ g, in
         if (h0 != h0) h0 = INFINITY;
         if (h1 != h1) h1 = INFINITY;
         const float hraw = h1, hbuild = stat_centred ? h0 : h1;
-        int sbits = 20, lbits = 40;
+        int sbits = 20;
         if (hbuild > 0.f && hbuild < INFINITY) sbits = min(100, ilog2_floor_dev(2147483647.0 / (static_cast<double>(chunk_rows) * hbuild)) - 1);
-        if (hraw > 0.f && hraw < INFINITY) lbits = min(60, ilog2_floor_dev(4.0e18 / (static_cast<double>(static_cast<long long>(n)) * hraw)) - 1);
+        const int lbits = leaf_sum_bits_dev(static_cast<long long>(n), hraw);
         StepScales o{};
         o.sbits = sbits; o.lbits = lbits;
         o.scale = static_cast<float>(ldexp(1.0, sbits));

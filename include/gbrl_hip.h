@@ -268,6 +268,36 @@ int gbrl_hip_leaf_counts_encoded(gbrl_hip_model *m, const float *obs, int obs_on
                                  int start_tree, int stop_tree, int64_t *out_host);
 int gbrl_hip_leaf_counts_chunk(void);   /* leaf counters one launch of leaf_counts holds on chip (diagnostic; no device needed) */
 
+/* Extension (LightGBM's Booster.refit, XGBoost's process_type=update with updater=refresh): the leaf VALUES of the trees [start_tree, stop_tree)
+ * are fitted again on this batch; the structure stays.  `values` and `tree_indices` below are the arrays of the ensemble data.
+ *   P = the float32 prediction gbrl_hip_predict_continue(tiled bias, 0, start_tree) gives on these rows (start_tree == 0: the tiled bias).
+ *   For t = start_tree .. stop_tree - 1, in order:
+ *     g[r][j] = fl32(P[r][j] - targets[r][j]) for ALL outputs: the MultiRMSE gradient of gbrl_hip_fit.  gmax = max |g|, a NaN carried as +inf.
+ *     lbits = the step's rule for its exact leaf sums with n = n_samples of this call: min(60, floor(log2(4.0e18 / (n * gmax))) - 1), 40 when
+ *     gmax == 0.  Per global leaf l of tree t, routed exactly as gbrl_hip_predict_leaves defines: S[l][j] = the exact int64 sum of
+ *     llrint((double)g * 2^lbits) (nearest even) and cnt[l] = the rows that reach l -- integer atomics only: two calls on equal models return
+ *     identical bytes.  mean = ((double)S / 2^lbits) / (double)cnt, the expression a step stores.  New value: (float)mean when decay_rate == 0,
+ *     else (float)(decay_rate * (double)old + (1 - decay_rate) * mean) with two rounded float64 products and one rounded float64 sum (no fused
+ *     multiply-add).  A leaf with cnt == 0 and any leaf of depth 0 keep their value (an oblivious tree of depth 0 is one such leaf: every row
+ *     reaches it, and P is advanced with the kept value).  A row whose greedy search leaves tree t (index -1 or outside [tree_indices[t],
+ *     tree_indices[t + 1]): a hand-edited file) joins no sum of that tree and keeps its P.
+ *     P[r][j] = fmaf(-lr_o(t), new value[leaf][j], P[r][j]) for every optimizer o that owns j, lr_o(t) the rate at the absolute tree index
+ *     (Const and Linear); an output nobody owns keeps P -- the bits of gbrl_hip_predict_continue's chain.
+ * Only `values` of the trees in the range change.  The structure, n_trees, iteration, bias, optimizers, the category dictionary and its token
+ * stay, and so do the trees outside the range: the trees from stop_tree on were fitted against the OLD prefix and are stale with respect to the
+ * new one (refit up to n_trees, or grow them again).  *loss_out (host) = bit for bit what gbrl_hip_staged_loss(obs, cat_obs, targets,
+ * stops = {stop_tree}) returns right after.  `targets` is float32 [n_samples, output_dim], host or device.
+ * Range: stop_tree == 0 means n_trees; after that 0 <= start_tree < stop_tree <= n_trees is required.  Reported before the device is touched,
+ * with GBRL_HIP_E_INVALID: a model without trees, any other range, targets or loss_out NULL, decay_rate outside [0, 1] or NaN, the data set
+ * errors of gbrl_hip_predict; with GBRL_HIP_E_UNSUPPORTED: output_dim > 128, and a model with collective hooks or an RCCL communicator (the
+ * sums would need an exchange per tree: row-sharded refit is out of scope), and a GREEDY tree of depth 0 among the trees [start_tree - 1,
+ * stop_tree): its leaf never passes, so the prediction walks on and applies a leaf of the next tree at this tree's rate -- a value the refit has
+ * not computed yet, so the chain above cannot be followed (a stump further in front only touches unchanged trees and is fine).  A run in which
+ * some gmax, or max |g| of the final P, is not finite (non-finite targets, an overflowing prediction) fails with GBRL_HIP_E_INVALID.  After ANY failure the model is unchanged.  The whole range is one enqueue and one wait. */
+int gbrl_hip_refit_leaves(gbrl_hip_model *m, const float *obs, int obs_on_device, const char *cat_obs, int cat_on_device,
+                          const float *targets, int targets_on_device, int n_samples, int n_num_features, int n_cat_features,
+                          int start_tree, int stop_tree, double decay_rate, double *loss_out);
+
 /* ---- row-sharded multi-GPU (new; the reference is single-GPU) ------------------------------------------ */
 /* One process per GPU, each holding a contiguous block of rows.  When hooks are installed, step() calls them at
  * its exchange points so that every rank grows the identical tree; predict() needs no exchange.  Buffers are
