@@ -1,5 +1,6 @@
 // predict_leaves.hip -- gfx950 kernels behind GBRL::predict_leaves / GBRL::leaf_counts: WHERE a row lands, not what it sums to.  For a row and a
-// tree t the answer is the GLOBAL leaf index, the row of `values` the walk of predict_continue.hip gathers:
+// tree t the answer is the GLOBAL leaf index, the row of `values` the walk of predict_continue.hip gathers (both walks are predict_rowwalk.h's,
+// the ones k_continue, k_staged and k_refit_accum call, as are the model view, the family choice and the LDS opt-in):
 //   oblivious (predictor.cpp:99-118)   tree_indices[t] + sum_d pass(cond[t * max_depth + d]) << (depths[t] - 1 - d); depth 0: tree_indices[t]
 //   greedy    (predictor.cpp:208-228)  the first leaf in storage order from tree_indices[t] on whose conditions all hold (tested from depth - 1
 //                                      down to 0 against inequality_directions).  A depth-0 leaf never passes there (Q7): the search then runs on
@@ -8,7 +9,7 @@
 // The walk reads no leaf value, so nothing here depends on output_dim.
 //
 //   k_leaves<GREEDY>         k_continue's layout without the base load, the value gather and the chain: lane = row, one wave per block, the
-//                            block's 64 rows in LDS at stride F | 1 (predict_stream_common.h), conditions / node records through wave-uniform
+//                            block's 64 rows in LDS at stride F | 1 (predict_rowwalk.h), conditions / node records through wave-uniform
 //                            addresses, trees in groups of kLeavesG = 16.  The output is row-major [n][T]: a lane-per-row store would have stride
 //                            T, so a group's 64 x 16 indices are staged in LDS (stride 17: lane-per-row writes touch 64 banks) and written so
 //                            that consecutive lanes cover a row's contiguous segment -- one 16-byte store per lane and quad when T % 4 == 0 and
@@ -26,8 +27,7 @@
 //                            issues one global add per distinct leaf and wave.
 #include "kernels.h"
 #include "kernels_common.h"
-#include "predict_leaves_walk.h"
-#include "predict_stream_common.h"
+#include "predict_rowwalk.h"
 
 #include <algorithm>
 
@@ -150,11 +150,10 @@ __global__ __launch_bounds__(kLeavesRows) void k_leaf_counts(LeavesModel cm, con
 template <bool GREEDY>
 bool launch_leaves(const LeavesModel &cm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree, int32_t *out,
                    hipStream_t s) {
-    const size_t lds = static_cast<size_t>(kLeavesRows) * (F | 1) * sizeof(float) + kLeavesStageBytes;
-    if (lds > kLeavesLdsBudget) return false;   // rows too wide for an LDS tile beside the staging buffer
-    static PerDeviceOnce attr;
-    static uint64_t unsupported = 0;
-    if (!leaves_lds_ok(k_leaves<GREEDY>, attr, unsupported, lds)) return false;
+    const size_t lds = stream_tile_bytes(F) + kLeavesStageBytes;
+    if (lds > kStreamLdsBudget) return false;   // rows too wide for an LDS tile beside the staging buffer
+    static StreamLdsOptIn optin;
+    if (!optin.ok(k_leaves<GREEDY>, lds)) return false;
     const int vec_out = ((stop_tree - start_tree) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
     hipLaunchKernelGGL((k_leaves<GREEDY>), dim3((n + kLeavesRows - 1) / kLeavesRows), dim3(kLeavesRows), lds, s, cm, obs, F, cat_codes, Fc, n, start_tree,
                        stop_tree, out, vec_out);
@@ -164,15 +163,14 @@ bool launch_leaves(const LeavesModel &cm, const float *obs, int F, const int32_t
 template <bool GREEDY>
 bool launch_leaf_counts(const LeavesModel &cm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
                         int leaf_base, int n_counters, uint32_t *counts, hipStream_t s) {
-    const size_t lds = static_cast<size_t>(kLeavesRows) * (F | 1) * sizeof(float) + static_cast<size_t>(n_counters) * sizeof(uint32_t);
-    if (lds > kLeavesLdsBudget) return false;   // rows too wide for an LDS tile beside the counters
-    static PerDeviceOnce attr;
-    static uint64_t unsupported = 0;
-    if (!leaves_lds_ok(k_leaf_counts<GREEDY>, attr, unsupported, lds)) return false;
+    const size_t lds = stream_tile_bytes(F) + static_cast<size_t>(n_counters) * sizeof(uint32_t);
+    if (lds > kStreamLdsBudget) return false;   // rows too wide for an LDS tile beside the counters
+    static StreamLdsOptIn optin;
+    if (!optin.ok(k_leaf_counts<GREEDY>, lds)) return false;
     const int n_tiles = (n + kLeavesRows - 1) / kLeavesRows;
     // as many blocks as the chip holds at once (160 KiB of LDS per CU, at most 8 one-wave blocks counted per CU): each then flushes once
     const int per_cu = static_cast<int>(std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1))));
-    const int blocks = std::min(n_tiles, leaves_cu_count() * per_cu);
+    const int blocks = std::min(n_tiles, stream_cu_count() * per_cu);
     hipLaunchKernelGGL((k_leaf_counts<GREEDY>), dim3(blocks), dim3(kLeavesRows), lds, s, cm, obs, F, cat_codes, Fc, n, n_tiles, start_tree, stop_tree,
                        leaf_base, n_counters, counts);
     return true;

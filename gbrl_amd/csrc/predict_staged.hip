@@ -12,32 +12,25 @@
 //                     the chain (D <= 64: at most 64 more VGPRs of the 512 a one-wave block may use); re-reading them per checkpoint would
 //                     cost 4 D bytes per row and stage, more than the observation tile from a few dozen stages on.  The rows are read once:
 //                     predict mode moves n (4 F + 4 D stages) bytes, loss mode n (4 F + 4 D) + 16 stages n / 64 (the partials written, then read).
-//                     The tile staging and the row load are k_continue's own (predict_stream_common.h).
+//                     The group body, the tile staging and the row load and store are k_continue's own (predict_rowwalk.h).
 //                     Every output owned by at most one optimizer, D <= 64, a row tile that fits in LDS.
-//   k_staged_general  anything the file format can hold: one thread per row, the reference's walk (greedy: leaf by leaf, Q7, its state carried
-//                     across the checkpoints so that stage s is the walk over [0, stops[s]) and not a restart), optimizers that share outputs,
-//                     D <= 128, rows too wide for an LDS tile.  The targets are re-read per checkpoint.  A wave still covers 64 consecutive rows
-//                     and reduces them with the same butterfly, so both kernels write the same part[][] and staged_loss has the same bytes
-//                     through either.  Also the cross-check behind GBRL_HIP_STAGED_GENERIC=1.
+//   k_staged_general  anything the file format can hold: one thread per row, k_continue_general's walk (predict_rowwalk.h; greedy: leaf by leaf,
+//                     Q7) suspended at each checkpoint, so that stage s is the walk over [0, stops[s]) and not a restart, optimizers that share
+//                     outputs, D <= 128, rows too wide for an LDS tile.  The targets are re-read per checkpoint.  A wave still covers 64
+//                     consecutive rows and reduces them with the same butterfly, so both kernels write the same part[][] and staged_loss has
+//                     the same bytes through either.  Also the cross-check behind GBRL_HIP_STAGED_GENERIC=1.
 //   k_staged_finish   one block per stage: part[s][0 .. nb) summed in a fixed order (a strided serial sum per thread, then a fixed LDS tree).
 //                     No floating-point atomics anywhere: two identical calls return identical bytes.
+// This file keeps the checkpoints, the loss butterfly, k_staged_finish and k_loss_of_predictions; the model view, both walks, the family
+// choice and the LDS opt-in are predict_rowwalk.h's, shared with predict_continue.hip, predict_leaves.hip and refit.hip.
 #include "kernels.h"
 #include "kernels_common.h"
-#include "predict_stream_common.h"
-
-#include <algorithm>
+#include "predict_rowwalk.h"
 
 namespace gbrl {
 namespace kern {
 
 namespace {
-
-struct StagedModel {
-    const int32_t *tree_indices, *depths, *feature_indices, *cat_ids, *cond_pack, *grd_nodes, *grd_node_off, *opt_start, *opt_stop;
-    const float *feature_values, *values, *rate, *bias;
-    const uint8_t *is_numerics, *inequality_directions;
-    int n_leaves, max_depth, D, oblivious, n_opts, rate_stride;   // rate_stride: n_opts (rate table) or 0 (one rate per optimizer)
-};
 
 // what a checkpoint emits: predict mode (out != nullptr) or loss mode (targets, part)
 struct StagedIo {
@@ -74,63 +67,22 @@ __device__ __forceinline__ double staged_row_loss(const float (&p)[DMAX], const 
 
 // ------------------------------------------------------------------------------------------------------------ general kernel
 template <int DMAX, bool LOSS>
-__global__ __launch_bounds__(256) void k_staged_general(StagedModel cm, StagedIo io, const float *__restrict__ obs, int F,
+__global__ __launch_bounds__(256) void k_staged_general(ChainModel cm, StagedIo io, const float *__restrict__ obs, int F,
                                                         const int32_t *__restrict__ cat_codes, int Fc, int n) {
     const size_t row = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const bool live = row < static_cast<size_t>(n);
-    const int D = cm.D, md = cm.max_depth;
+    const int D = cm.D;
     float p[DMAX];
 #pragma unroll
     for (int j = 0; j < DMAX; ++j) p[j] = j < D ? cm.bias[j] : 0.0f;
-    const float *x = obs + (live ? row : 0) * F;
-    const int32_t *xc = cat_codes ? cat_codes + (live ? row : 0) * Fc : nullptr;
-    auto test = [&](int c) -> bool {
-        const int f = cm.feature_indices[c];
-        return cm.is_numerics[c] ? (x[f] > cm.feature_values[c]) : (xc != nullptr && xc[f] == cm.cat_ids[c]);
-    };
-    auto apply = [&](int t, const float *v) {
-        for (int o = 0; o < cm.n_opts; ++o) {
-            const float lr = cm.rate[static_cast<size_t>(t) * cm.rate_stride + o];
-            const int a = cm.opt_start[o], b = cm.opt_stop[o];
-#pragma unroll
-            for (int j = 0; j < DMAX; ++j)
-                if (j >= a && j < b && j < D) p[j] = __fmaf_rn(-lr, v[j], p[j]);
-        }
-    };
-    int t = 0, leaf = 0;
-    bool at_root = true;   // greedy: the walk is about to enter tree t
+    const GeneralRow r{obs + (live ? row : 0) * F, cat_codes ? cat_codes + (live ? row : 0) * Fc : nullptr};
+    int t = 0;
+    bool ended = false;   // a greedy search ran off the ensemble: every later stage is the walk as it stands
     for (int s = 0; s < io.n_stops; ++s) {   // (uniform over the block)
         const int stop = io.walk ? io.stops[s] : 0;
-        if (live) {
-            if (cm.oblivious) {
-                for (; t < stop; ++t) {
-                    const int depth = cm.depths[t], cond = t * md;
-                    int l = 0;
-                    for (int d = 0; d < depth; ++d) l |= (test(cond + d) ? 1 : 0) << (depth - 1 - d);
-                    apply(t, cm.values + static_cast<size_t>(cm.tree_indices[t] + l) * D);
-                }
-            } else {
-                // k_continue_general's walk over [0, stop), suspended at the checkpoint: a leaf that never passes lets the walk run on into the
-                // leaves of the following trees (Q7), so the state (t, leaf) is carried, not rebuilt per stage
-                while (t < stop) {
-                    if (at_root) { leaf = cm.tree_indices[t]; at_root = false; }
-                    if (leaf >= cm.n_leaves) break;
-                    const int depth = cm.depths[leaf], cond = leaf * md;
-                    bool passed = false;
-                    for (int d = depth - 1; d >= 0; --d) {
-                        passed = (test(cond + d) == (cm.inequality_directions[cond + d] != 0));
-                        if (!passed) break;
-                    }
-                    if (passed) {
-                        apply(t, cm.values + static_cast<size_t>(leaf) * D);
-                        ++t;
-                        at_root = true;
-                    } else {
-                        ++leaf;
-                    }
-                }
-            }
-        }
+        if (live)
+            for (; t < stop && !ended; ++t)
+                if (!general_chain_tree<DMAX>(cm, r, t, p)) ended = true;
         if constexpr (!LOSS) {
             if (live) {
                 float *o = io.out + (static_cast<size_t>(s) * n + row) * D;
@@ -149,17 +101,13 @@ __global__ __launch_bounds__(256) void k_staged_general(StagedModel cm, StagedIo
 }
 
 // ------------------------------------------------------------------------------------------------------------ streaming kernel
-template <int DMAX>
-struct StagedOwner { uint8_t opt[DMAX]; };   // optimizer that owns output j (meaningful where bit j of `cover` is set)
-
 template <int DMAX, bool GREEDY, bool LOSS>
-__global__ __launch_bounds__(kStagedRows) void k_staged(StagedModel cm, StagedIo io, StagedOwner<DMAX> own, uint64_t cover, const float *__restrict__ obs,
+__global__ __launch_bounds__(kStagedRows) void k_staged(ChainModel cm, StagedIo io, StreamOwner<DMAX> own, uint64_t cover, const float *__restrict__ obs,
                                                         int F, const int32_t *__restrict__ cat_codes, int Fc, int n, int vec_values, int vec_io) {
     extern __shared__ float stile[];   // [kStagedRows][F | 1]
-    constexpr int kG = DMAX <= 4 ? 8 : DMAX <= 8 ? 4 : DMAX <= 16 ? 2 : 1;   // trees whose leaf values are in flight together
     const int lane = threadIdx.x;
     const int xs = F | 1;
-    const int D = cm.D, md = cm.max_depth;
+    const int D = cm.D;
     const int r0 = blockIdx.x * kStagedRows;
     const int rows = min(kStagedRows, n - r0);
     const bool live = lane < rows;
@@ -180,69 +128,15 @@ __global__ __launch_bounds__(kStagedRows) void k_staged(StagedModel cm, StagedIo
     __syncthreads();
     const float *x = stile + (live ? lane : 0) * xs;
     const int32_t *xc = cat_codes ? cat_codes + (live ? row : 0) * Fc : nullptr;
-    // feature word >= 0: numeric feature against a threshold; < 0: ~categorical feature against a dictionary id
-    auto pass = [&](int fi, int tv) -> bool { return fi >= 0 ? (x[fi] > __int_as_float(tv)) : (xc != nullptr && xc[~fi] == tv); };
     int start_tree = 0;
     for (int s = 0; s < io.n_stops; ++s) {   // (wave-uniform)
         const int stop_tree = io.walk ? io.stops[s] : 0;
-        if (live) {
-            for (int t0 = start_tree; t0 < stop_tree; t0 += kG) {   // a group ends at the checkpoint
-                int leaf[kG];
-#pragma unroll
-                for (int g = 0; g < kG; ++g) {
-                    const int t = t0 + g;
-                    leaf[g] = 0;
-                    if (t < stop_tree) {   // (wave-uniform)
-                        if (!GREEDY) {
-                            const int depth = cm.depths[t];
-                            const int32_t *cp = cm.cond_pack + static_cast<size_t>(t) * 2 * md;
-                            int l = 0;
-                            for (int d = 0; d < depth; ++d) l |= pass(cp[2 * d], cp[2 * d + 1]) ? (1 << (depth - 1 - d)) : 0;
-                            leaf[g] = cm.tree_indices[t] + l;
-                        } else {
-                            // descent of the rebuilt binary tree: a child >= 0 is a node of the tree, < 0 is ~(leaf within the tree); a leaf lies
-                            // at most max_depth steps below the root
-                            const int4 *nodes = reinterpret_cast<const int4 *>(cm.grd_nodes) + cm.grd_node_off[t];
-                            int node = 0;
-                            for (int d = 0; d < md && node >= 0; ++d) {
-                                const int4 nd = nodes[node];
-                                node = pass(nd.x, nd.y) ? nd.w : nd.z;
-                            }
-                            leaf[g] = cm.tree_indices[t] + (node < 0 ? ~node : 0);
-                        }
-                    }
-                }
-                float v[kG][DMAX];
-#pragma unroll
-                for (int g = 0; g < kG; ++g)
-                    if (t0 + g < stop_tree) stream_load_row<DMAX>(cm.values + static_cast<size_t>(leaf[g]) * D, D, vec_values != 0, v[g]);
-#pragma unroll
-                for (int g = 0; g < kG; ++g) {
-                    const int t = t0 + g;
-                    if (t < stop_tree) {
-                        const float *rt = cm.rate + static_cast<size_t>(t) * cm.rate_stride;
-#pragma unroll
-                        for (int j = 0; j < DMAX; ++j)
-                            if (j < D && ((cover >> j) & 1ull)) p[j] = __fmaf_rn(-rt[own.opt[j]], v[g][j], p[j]);
-                    }
-                }
-            }
-        }
+        if (live)
+            for (int t0 = start_tree; t0 < stop_tree; t0 += kStreamGroup<DMAX>)   // a group ends at the checkpoint
+                stream_chain_group<DMAX, GREEDY>(cm, own, cover, x, xc, t0, stop_tree, vec_values, p);
         start_tree = max(start_tree, stop_tree);
         if constexpr (!LOSS) {
-            if (live) {
-                float *o = io.out + (static_cast<size_t>(s) * n + row) * D;
-                if (vec_io) {
-                    float4 *o4 = reinterpret_cast<float4 *>(o);
-#pragma unroll
-                    for (int q = 0; q < DMAX / 4; ++q)
-                        if (4 * q < D) o4[q] = make_float4(p[4 * q], p[4 * q + 1], p[4 * q + 2], p[4 * q + 3]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < DMAX; ++j)
-                        if (j < D) o[j] = p[j];
-                }
-            }
+            if (live) stream_store_row<DMAX>(io.out + (static_cast<size_t>(s) * n + row) * D, D, vec_io != 0, p);
         } else {
             double acc = 0.0;
             if (live) acc = staged_row_loss<DMAX>(p, y, D);
@@ -287,57 +181,32 @@ __global__ __launch_bounds__(256) void k_loss_of_predictions(const float *__rest
 }
 
 template <int DMAX, bool GREEDY, bool LOSS>
-bool launch_staged(const StagedModel &cm, const StagedIo &io, const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n,
+bool launch_staged(const ChainModel &cm, const StagedIo &io, const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n,
                    hipStream_t s) {
-    const size_t lds = static_cast<size_t>(kStagedRows) * (F | 1) * sizeof(float);
-    if (lds > 156 * 1024) return false;   // rows too wide for an LDS tile
-    static PerDeviceOnce attr;
-    static uint64_t unsupported = 0;   // devices that refused the LDS opt-in: tiles above the default 64 KiB take the general kernel there
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = (dev >= 0 && dev < 64) ? (1ull << dev) : 0;
-    if (attr.first() && hipFuncSetAttribute(reinterpret_cast<const void *>(k_staged<DMAX, GREEDY, LOSS>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) {
-        (void)hipGetLastError();
-        unsupported |= bit;
-    }
-    if ((unsupported & bit) && lds > 64 * 1024) return false;
-    StagedOwner<DMAX> own;
-    for (int j = 0; j < DMAX; ++j) own.opt[j] = j < pm.D ? pm.owner[j] : 0;
+    const size_t lds = stream_tile_bytes(F);
+    if (lds > kStreamLdsBudget) return false;   // rows too wide for an LDS tile
+    static StreamLdsOptIn optin;
+    if (!optin.ok(k_staged<DMAX, GREEDY, LOSS>, lds)) return false;
     const bool d4 = (pm.D & 3) == 0;
     const int vec_values = d4 && (reinterpret_cast<uintptr_t>(pm.values) & 15) == 0;
     const int vec_io = d4 && (reinterpret_cast<uintptr_t>(LOSS ? static_cast<const void *>(io.targets) : static_cast<const void *>(io.out)) & 15) == 0;
-    hipLaunchKernelGGL((k_staged<DMAX, GREEDY, LOSS>), dim3((n + kStagedRows - 1) / kStagedRows), dim3(kStagedRows), lds, s, cm, io, own, pm.coef_cover,
-                       obs, F, cat_codes, Fc, n, vec_values, vec_io);
+    hipLaunchKernelGGL((k_staged<DMAX, GREEDY, LOSS>), dim3((n + kStagedRows - 1) / kStagedRows), dim3(kStagedRows), lds, s, cm, io,
+                       stream_owner<DMAX>(pm), pm.coef_cover, obs, F, cat_codes, Fc, n, vec_values, vec_io);
     return true;
 }
 
-template <bool GREEDY, bool LOSS>
-bool launch_staged_d(const StagedModel &cm, const StagedIo &io, const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n,
-                     hipStream_t s) {
-    if (pm.D <= 4) return launch_staged<4, GREEDY, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s);
-    if (pm.D <= 8) return launch_staged<8, GREEDY, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s);
-    if (pm.D <= 16) return launch_staged<16, GREEDY, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s);
-    if (pm.D <= 32) return launch_staged<32, GREEDY, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s);
-    return launch_staged<64, GREEDY, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s);
-}
-
 template <bool LOSS>
-void staged_dispatch(const StagedModel &cm, const StagedIo &io, const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n,
+void staged_dispatch(const ChainModel &cm, const StagedIo &io, const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n,
                      bool generic, hipStream_t s) {
-    // the streaming family: every output owned by at most one optimizer (owner[] is valid), the packed conditions / rebuilt node records
-    const bool fast = !generic && pm.coef_ok && pm.D <= 64 && pm.max_depth >= 1 &&
-                      (pm.oblivious ? pm.cond_pack != nullptr : (pm.grd_ok && pm.grd_nodes != nullptr && pm.grd_node_off != nullptr));
-    if (fast) {
-        if (pm.oblivious ? launch_staged_d<false, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s) : launch_staged_d<true, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s))
-            return;
-    }
-    dim3 grid((n + 255) / 256), block(256);
-    if (pm.D <= 8)
-        hipLaunchKernelGGL((k_staged_general<8, LOSS>), grid, block, 0, s, cm, io, obs, F, cat_codes, Fc, n);
-    else if (pm.D <= 32)
-        hipLaunchKernelGGL((k_staged_general<32, LOSS>), grid, block, 0, s, cm, io, obs, F, cat_codes, Fc, n);
-    else
-        hipLaunchKernelGGL((k_staged_general<128, LOSS>), grid, block, 0, s, cm, io, obs, F, cat_codes, Fc, n);
+    if (chain_streamable(pm, generic) && with_stream_dmax(pm.D, [&](auto dmax) {
+            constexpr int DMAX = decltype(dmax)::value;
+            return pm.oblivious ? launch_staged<DMAX, false, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s)
+                                : launch_staged<DMAX, true, LOSS>(cm, io, pm, obs, F, cat_codes, Fc, n, s);
+        }))
+        return;
+    with_general_dmax(pm.D, [&](auto dmax) {
+        hipLaunchKernelGGL((k_staged_general<decltype(dmax)::value, LOSS>), dim3((n + 255) / 256), dim3(256), 0, s, cm, io, obs, F, cat_codes, Fc, n);
+    });
 }
 
 }  // namespace
@@ -352,15 +221,7 @@ void staged_loss_of_predictions(const float *preds, const float *targets, int n,
 
 void predict_staged(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, const StagedStops &st, float *out,
                     const float *targets, double *part, double *sums, bool generic, hipStream_t s) {
-    StagedModel cm{};
-    cm.tree_indices = pm.tree_indices; cm.depths = pm.depths; cm.feature_indices = pm.feature_indices; cm.cat_ids = pm.cat_ids;
-    cm.cond_pack = pm.cond_pack; cm.grd_nodes = pm.grd_nodes; cm.grd_node_off = pm.grd_node_off;
-    cm.opt_start = pm.opt_start; cm.opt_stop = pm.opt_stop;
-    cm.feature_values = pm.feature_values; cm.values = pm.values; cm.bias = pm.bias;
-    cm.rate = pm.rate != nullptr ? pm.rate : pm.opt_lr;
-    cm.rate_stride = pm.rate != nullptr ? pm.n_opts : 0;
-    cm.is_numerics = pm.is_numerics; cm.inequality_directions = pm.inequality_directions;
-    cm.n_leaves = pm.n_leaves; cm.max_depth = pm.max_depth; cm.D = pm.D; cm.oblivious = pm.oblivious; cm.n_opts = pm.n_opts;
+    const ChainModel cm = chain_model(pm);
     StagedIo io{};
     io.stops = st.stops; io.n_stops = st.n_stops;
     io.walk = (pm.n_opts > 0 && pm.n_trees > 0 && st.last_stop > 0) ? 1 : 0;   // as kern::predict_continue: no optimizer, no tree to apply

@@ -1,7 +1,7 @@
 // refit.hip -- gfx950 kernels behind GBRL::refit_leaves: the leaf values of the trees [start, stop) fitted again on a batch, the structure kept.
 // The running prediction P [n][D] lives on the device for the whole range; per tree the host enqueues three launches and never waits:
 //
-//   accumulate   routes every row through tree t (the walks of predict_leaves_walk.h, so a leaf gets exactly the rows predict_leaves reports),
+//   accumulate   routes every row through tree t (the walks of predict_rowwalk.h, so a leaf gets exactly the rows predict_leaves reports),
 //                stores the row's global leaf to leaf_idx[n] and adds q = llrint((double)fl32(P - y) * 2^lbits) per output, and 1, to the leaf's
 //                int64 accumulators.  2^lbits comes from gmax[t], the bits of max |g| the previous apply pass left on the device, through
 //                leaf_sum_bits_dev -- the step's own rule.  Integer adds only: exact and order-free, so every run and both kernel families
@@ -20,11 +20,12 @@
 //                order-free; NaN is carried as +inf).
 //
 // The accumulators of the whole range are zeroed once by the caller, so no pass clears them.  pm.values is only read: the result goes to
-// new_values, and the caller writes the model after it has seen every gmax finite.
+// new_values, and the caller writes the model after it has seen every gmax finite.  The model view, both walks, the rate rule of the apply
+// pass (ChainRates), the tile staging, the row load, the LDS opt-in and the template-width ladder are predict_rowwalk.h's, shared with
+// predict_continue.hip, predict_staged.hip and predict_leaves.hip.
 #include "kernels.h"
 #include "kernels_common.h"
-#include "predict_leaves_walk.h"
-#include "predict_stream_common.h"
+#include "predict_rowwalk.h"
 
 #include <algorithm>
 
@@ -43,12 +44,6 @@ struct RefitTree {
     uint32_t *gmax_next;             // where the apply pass leaves the next tree's (behind the last tree: max |g| of the final prediction)
     unsigned long long *acc;         // [n_leaves][D + 1]
     float *new_values;               // [n_leaves][D]
-};
-
-struct RefitRates {
-    const int32_t *opt_start, *opt_stop;
-    const float *rate;
-    int n_opts, rate_stride;
 };
 
 // bits of |g| as an unsigned integer: ordered like the magnitudes; NaN is carried as +inf
@@ -208,7 +203,7 @@ __global__ __launch_bounds__(256) void k_refit_finalize(RefitTree rt, const int3
 }
 
 // ------------------------------------------------------------------------------------------------------------ apply
-__global__ __launch_bounds__(256) void k_refit_apply(RefitTree rt, RefitRates rr, const int32_t *__restrict__ leaf_idx, const float *__restrict__ Y, int D,
+__global__ __launch_bounds__(256) void k_refit_apply(RefitTree rt, ChainRates rr, const int32_t *__restrict__ leaf_idx, const float *__restrict__ Y, int D,
                                                      size_t total, float *__restrict__ P) {
     uint32_t m = 0;
     const float *rate = rr.rate + static_cast<size_t>(rt.t) * rr.rate_stride;
@@ -232,28 +227,17 @@ __global__ __launch_bounds__(256) void k_refit_apply(RefitTree rt, RefitRates rr
 template <int DMAX, bool GREEDY>
 bool launch_refit_accum(const LeavesModel &cm, const RefitTree &rt, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int D, const float *P,
                         const float *Y, int32_t *leaf_idx, hipStream_t s) {
-    const size_t lds = static_cast<size_t>(kRefitRows) * (F | 1) * sizeof(float) + static_cast<size_t>(rt.n_leaves) * (D + 1) * sizeof(unsigned long long);
-    if (lds > kLeavesLdsBudget) return false;   // rows too wide, or a tree with too many accumulators, for the LDS of a CU
-    static PerDeviceOnce attr;
-    static uint64_t unsupported = 0;
-    if (!leaves_lds_ok(k_refit_accum<DMAX, GREEDY>, attr, unsupported, lds)) return false;
+    const size_t lds = stream_tile_bytes(F) + static_cast<size_t>(rt.n_leaves) * (D + 1) * sizeof(unsigned long long);
+    if (lds > kStreamLdsBudget) return false;   // rows too wide, or a tree with too many accumulators, for the LDS of a CU
+    static StreamLdsOptIn optin;
+    if (!optin.ok(k_refit_accum<DMAX, GREEDY>, lds)) return false;
     const int n_tiles = (n + kRefitRows - 1) / kRefitRows;
     const int per_cu = static_cast<int>(std::min<size_t>(kRefitBlocksPerCu, std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1))));
-    const int blocks = std::min(n_tiles, leaves_cu_count() * per_cu);
+    const int blocks = std::min(n_tiles, stream_cu_count() * per_cu);
     const int vec_io = (D & 3) == 0 && ((reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0;
     hipLaunchKernelGGL((k_refit_accum<DMAX, GREEDY>), dim3(blocks), dim3(kRefitRows), lds, s, cm, rt, obs, F, cat_codes, Fc, n, n_tiles, D, P, Y, leaf_idx,
                        vec_io);
     return true;
-}
-
-template <bool GREEDY>
-bool launch_refit_accum_d(const LeavesModel &cm, const RefitTree &rt, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int D, const float *P,
-                          const float *Y, int32_t *leaf_idx, hipStream_t s) {
-    if (D <= 4) return launch_refit_accum<4, GREEDY>(cm, rt, obs, F, cat_codes, Fc, n, D, P, Y, leaf_idx, s);
-    if (D <= 8) return launch_refit_accum<8, GREEDY>(cm, rt, obs, F, cat_codes, Fc, n, D, P, Y, leaf_idx, s);
-    if (D <= 16) return launch_refit_accum<16, GREEDY>(cm, rt, obs, F, cat_codes, Fc, n, D, P, Y, leaf_idx, s);
-    if (D <= 32) return launch_refit_accum<32, GREEDY>(cm, rt, obs, F, cat_codes, Fc, n, D, P, Y, leaf_idx, s);
-    return launch_refit_accum<64, GREEDY>(cm, rt, obs, F, cat_codes, Fc, n, D, P, Y, leaf_idx, s);
 }
 
 }  // namespace
@@ -272,7 +256,7 @@ int refit_leaves(const PredictModel &pm, const int32_t *tree_first_leaf, const f
     hipLaunchKernelGGL(k_refit_tile_bias, dim3(eblocks), dim3(256), 0, s, pm.bias, D, total, P);
     if (start_tree > 0) predict_continue(pm, obs, F, cat_codes, Fc, n, 0, start_tree, P, P, generic, s);
     hipLaunchKernelGGL(k_refit_gmax, dim3(eblocks), dim3(256), 0, s, P, targets, total, gmax);
-    RefitRates rr{pm.opt_start, pm.opt_stop, pm.rate != nullptr ? pm.rate : pm.opt_lr, pm.n_opts, pm.rate != nullptr ? pm.n_opts : 0};
+    const ChainRates rr = chain_rates(pm);
     const int base = first_leaf(start_tree);
     for (int t = start_tree; t < stop_tree; ++t) {
         RefitTree rt{};
@@ -283,8 +267,11 @@ int refit_leaves(const PredictModel &pm, const int32_t *tree_first_leaf, const f
         rt.new_values = new_values + static_cast<size_t>(rt.leaf0 - base) * D;
         bool done = rt.n_leaves <= 0;   // (a tree without leaves, which no grower writes: nothing to sum, the apply pass only hands gmax on)
         if (!done && stream)
-            done = pm.oblivious ? launch_refit_accum_d<false>(cm, rt, obs, F, cat_codes, Fc, n, D, P, targets, leaf_idx, s)
-                                : launch_refit_accum_d<true>(cm, rt, obs, F, cat_codes, Fc, n, D, P, targets, leaf_idx, s);
+            done = with_stream_dmax(D, [&](auto dmax) {
+                constexpr int DMAX = decltype(dmax)::value;
+                return pm.oblivious ? launch_refit_accum<DMAX, false>(cm, rt, obs, F, cat_codes, Fc, n, D, P, targets, leaf_idx, s)
+                                    : launch_refit_accum<DMAX, true>(cm, rt, obs, F, cat_codes, Fc, n, D, P, targets, leaf_idx, s);
+            });
         if (done && rt.n_leaves > 0) ++streamed;
         if (!done)
             hipLaunchKernelGGL(k_refit_accum_general, dim3((n + 255) / 256), dim3(256), 0, s, cm, rt, obs, F, cat_codes, Fc, n, D, P, targets, leaf_idx);

@@ -22,9 +22,9 @@ KG = 16          # trees per group of k_leaves (predict_leaves.hip: kLeavesG)
 BATCHES = (1, 63, 64, 65, 200)
 
 
-def _model(F, Fc, D, depth, policy="oblivious", lr=0.1, name="leaves"):
+def _model(F, Fc, D, depth, policy="oblivious", lr=0.1, name="leaves", min_data_in_leaf=0):
     import gbrl_amd
-    m = gbrl_amd.GBRL(input_dim=F + Fc, output_dim=D, policy_dim=D, max_depth=depth, min_data_in_leaf=0, n_bins=32, par_th=10, cv_beta=0.9,
+    m = gbrl_amd.GBRL(input_dim=F + Fc, output_dim=D, policy_dim=D, max_depth=depth, min_data_in_leaf=min_data_in_leaf, n_bins=32, par_th=10, cv_beta=0.9,
                       split_score_func="L2", generator_type="Quantile", use_control_variates=False, batch_size=5000, grow_policy=policy,
                       verbose=0, device="cpu", learner_name=name)
     m.set_feature_weights(np.ones(F + Fc, np.float32))
@@ -284,8 +284,8 @@ def test_fallback_rows_too_wide_for_the_lds_tile(policy):
 def test_trees_grown_on_gradients_constant_in_x():
     """The contract's fallback list names a model with a depth-0 stump, which gradients that are constant in X were expected to produce.  At
     these settings (256 rows, F = 8, max_depth = 3, n_bins = 32, all-ones and all-zero gradients) the grower never emits one -- it still grows
-    full-depth trees under both policies -- so there is NO depth-0 case in this file.  The trees it does grow from such gradients are checked
-    like any others; the NumPy walk holds whatever their depth."""
+    full-depth trees under both policies.  The trees it does grow from such gradients are checked like any others; the NumPy walk holds
+    whatever their depth.  The depth-0 case is test_a_depth0_tree_in_the_middle_and_last below, which grows one with min_data_in_leaf."""
     F, D = 8, 2
     rng = np.random.default_rng(95)
     for policy in ("oblivious", "greedy"):
@@ -297,6 +297,41 @@ def test_trees_grown_on_gradients_constant_in_x():
         e = m.get_ensemble_data()
         for a, b in ((0, 0), (1, 3)):
             _check(m, e, policy, X[:65], None, a, b)
+
+
+@pytest.mark.parametrize("policy", ["oblivious", "greedy"])
+@pytest.mark.parametrize("where", ["middle", "last"])
+def test_a_depth0_tree_in_the_middle_and_last(where, policy):
+    """Grown as tests/test_gpu_edges.py grows it: min_data_in_leaf = 60, a step on 300 rows splits, a step on 100 rows appends a single depth-0
+    leaf.  "middle": 3 trees, the depth-0 tree, 2 trees; "last": 3 trees, then two depth-0 trees.  Oblivious: the depth-0 tree routes every row
+    to its one leaf.  Greedy: that leaf never passes, so the tree reports a leaf of the following tree, and -1 where no tree follows -- those
+    rows join no count."""
+    F, D = 4, 2
+    plan = {"middle": (300, 300, 300, 100, 300, 300), "last": (300, 300, 300, 100, 100)}[where]
+    T = len(plan)
+    rng = np.random.default_rng(81 + (where == "last") + 2 * (policy == "greedy"))
+    m = _model(F, 0, D, 3, policy, min_data_in_leaf=60)
+    for rows in plan:
+        _grow(m, rng, 1, F, 0, D, rows=rows)
+    assert m.get_num_trees() == T
+    e = m.get_ensemble_data()
+    ti = np.asarray(e["tree_indices"]); dep = np.asarray(e["depths"]); n_leaves = np.asarray(e["values"]).shape[0]
+    ends = np.append(ti[1:], n_leaves)
+    depths = [int(dep[t]) if policy == "oblivious" else int(dep[ti[t]:ends[t]].max()) for t in range(T)]
+    assert [d == 0 for d in depths] == [rows == 100 for rows in plan], depths
+    for n in (65, 200):
+        X, _ = _batch(rng, n, F, 0)
+        for a, b in [(0, 0), (1, T)] + [(t, t + 1) for t in range(T)]:
+            leaves, counts = _check(m, e, policy, X, None, a, b)
+            if (a, b) != (0, 0):
+                continue
+            for t in range(T):
+                if depths[t] > 0 or policy == "oblivious":
+                    assert ((leaves[:, t] >= ti[t]) & (leaves[:, t] < ends[t])).all()
+                elif where == "middle":
+                    assert ((leaves[:, t] >= ti[t + 1]) & (leaves[:, t] < ends[t + 1])).all()      # a leaf of the following tree
+                else:
+                    assert (leaves[:, t] == -1).all()                                              # the search ran off the ensemble
 
 
 @pytest.mark.parametrize("policy", ["oblivious", "greedy"])

@@ -16,9 +16,9 @@ pytestmark = pytest.mark.gpu
 TOKENS = np.array(["tok%d" % i for i in range(6)], dtype="S128")
 
 
-def _model(F, Fc, D, depth, policy="oblivious", opts=None, bias=None, name="cont"):
+def _model(F, Fc, D, depth, policy="oblivious", opts=None, bias=None, name="cont", min_data_in_leaf=0):
     import gbrl_amd
-    m = gbrl_amd.GBRL(input_dim=F + Fc, output_dim=D, policy_dim=D, max_depth=depth, min_data_in_leaf=0, n_bins=32, par_th=10, cv_beta=0.9,
+    m = gbrl_amd.GBRL(input_dim=F + Fc, output_dim=D, policy_dim=D, max_depth=depth, min_data_in_leaf=min_data_in_leaf, n_bins=32, par_th=10, cv_beta=0.9,
                       split_score_func="L2", generator_type="Quantile", use_control_variates=False, batch_size=5000, grow_policy=policy,
                       verbose=0, device="cpu", learner_name=name)
     m.set_feature_weights(np.ones(F + Fc, np.float32))
@@ -231,6 +231,37 @@ def test_optimizers_rates_follow_the_absolute_tree_index():
         got = _continue_both(m, X, None, base, 2, 12)
         assert got[:, 3].tobytes() == base[:, 3].tobytes()
         assert not np.array_equal(got[:, :3], base[:, :3])
+
+
+def _depth0_model(policy, where, rng, F=4, D=2):
+    """A depth-0 tree among normal ones, grown as tests/test_gpu_edges.py grows it: min_data_in_leaf = 60, so a step on 300 rows splits and a
+    step on 100 rows cannot (no candidate leaves 60 rows on either side) and appends a single depth-0 leaf.  where = "middle": 3 trees, the
+    depth-0 tree, 2 trees; "last": 3 trees, then two depth-0 trees.  A greedy depth-0 leaf never passes (Q7): the search of that tree runs on
+    into the leaves of the following trees, and off the ensemble when there are none.  Returns (model, T)."""
+    plan = {"middle": (300, 300, 300, 100, 300, 300), "last": (300, 300, 300, 100, 100)}[where]
+    m = _model(F, 0, D, 3, policy=policy, min_data_in_leaf=60)
+    for rows in plan:
+        _grow(m, rng, 1, F, 0, D, rows=rows)
+    T = len(plan)
+    assert m.get_num_trees() == T
+    e = m.get_ensemble_data()
+    ti = np.asarray(e["tree_indices"]); dep = np.asarray(e["depths"])
+    ends = np.append(ti[1:], np.asarray(e["values"]).shape[0])
+    depths = [int(dep[t]) if policy == "oblivious" else int(dep[ti[t]:ends[t]].max()) for t in range(T)]
+    assert [d == 0 for d in depths] == [rows == 100 for rows in plan], depths
+    return m, T
+
+
+@pytest.mark.parametrize("policy", ["oblivious", "greedy"])
+@pytest.mark.parametrize("where", ["middle", "last"])
+def test_split_anywhere_around_a_depth0_tree(where, policy):
+    """Every split point k in 0 .. T: continue(chain over [0, k), k, T) has the bits of the chain over [0, T), through both kernels."""
+    rng = np.random.default_rng(61 + (where == "last") + 2 * (policy == "greedy"))
+    m, T = _depth0_model(policy, where, rng)
+    for n in (65, 200):
+        X, _ = _batch(rng, n, 4, 0)
+        for k in range(T + 1):
+            _split_check(m, X, None, k, T)
 
 
 def test_never_sliced():

@@ -21,9 +21,9 @@ TOKENS = np.array(["tok%d" % i for i in range(6)], dtype="S128")
 ROWS = (1, 63, 64, 65, 200)
 
 
-def _model(F, Fc, D, depth, policy="oblivious", opts=None, bias=None, device="cpu", batch_size=5000):
+def _model(F, Fc, D, depth, policy="oblivious", opts=None, bias=None, device="cpu", batch_size=5000, min_data_in_leaf=0):
     import gbrl_amd
-    m = gbrl_amd.GBRL(input_dim=F + Fc, output_dim=D, policy_dim=D, max_depth=depth, min_data_in_leaf=0, n_bins=32, par_th=10, cv_beta=0.9,
+    m = gbrl_amd.GBRL(input_dim=F + Fc, output_dim=D, policy_dim=D, max_depth=depth, min_data_in_leaf=min_data_in_leaf, n_bins=32, par_th=10, cv_beta=0.9,
                       split_score_func="L2", generator_type="Quantile", use_control_variates=False, batch_size=batch_size, grow_policy=policy,
                       verbose=0, device=device, learner_name="staged")
     m.set_feature_weights(np.ones(F + Fc, np.float32))
@@ -148,6 +148,43 @@ def test_depth_one_and_twenty_trees():
     m = _model(F, 0, D, 1)
     _grow(m, rng, T, F, 0, D, rows=384)
     _sweep(m, rng, F, 0, D, T, rows=(65, 200))
+
+
+def _depth0_model(policy, where, rng, F=4, D=2):
+    """tests/test_gpu_predict_continue.py::_depth0_model: min_data_in_leaf = 60, a step on 300 rows splits, a step on 100 rows appends a single
+    depth-0 leaf.  where = "middle": 3 trees, the depth-0 tree, 2 trees; "last": 3 trees, then two depth-0 trees.  Returns (model, T)."""
+    plan = {"middle": (300, 300, 300, 100, 300, 300), "last": (300, 300, 300, 100, 100)}[where]
+    m = _model(F, 0, D, 3, policy=policy, min_data_in_leaf=60)
+    for rows in plan:
+        _grow(m, rng, 1, F, 0, D, rows=rows)
+    T = len(plan)
+    assert m.get_num_trees() == T
+    e = m.get_ensemble_data()
+    ti = np.asarray(e["tree_indices"]); dep = np.asarray(e["depths"])
+    ends = np.append(ti[1:], np.asarray(e["values"]).shape[0])
+    depths = [int(dep[t]) if policy == "oblivious" else int(dep[ti[t]:ends[t]].max()) for t in range(T)]
+    assert [d == 0 for d in depths] == [rows == 100 for rows in plan], depths
+    return m, T
+
+
+@pytest.mark.parametrize("policy", ["oblivious", "greedy"])
+@pytest.mark.parametrize("where", ["middle", "last"])
+def test_checkpoints_around_a_depth0_tree(where, policy):
+    """A greedy depth-0 leaf never passes (Q7): the search of that tree runs on into the leaves of the following trees.  With the depth-0 trees
+    last, the walk runs off the ensemble at tree 3 and the checkpoints 4 and 5 follow: the suspended walk must stay ended.  Every stage is the
+    chain over its prefix (`predict` under GBRL_HIP_PREDICT_GENERIC=1, which is what the yardstick of this file is pinned to), for every tree
+    count 0 .. T and for sparse subsets."""
+    rng = np.random.default_rng(71 + (where == "last") + 2 * (policy == "greedy"))
+    m, T = _depth0_model(policy, where, rng)
+    for n in (65, 200):
+        X, _ = _batch(rng, n, 4, 0)
+        Y = rng.standard_normal((n, 2)).astype(np.float32)
+        want = _stage_table(m, X, None, n, T)
+        for k in range(1, T + 1):
+            with _env("GBRL_HIP_PREDICT_GENERIC", "1"):
+                assert want[k].tobytes() == np.asarray(m.predict(X, None, 0, k)).tobytes(), "the yardstick is not the chain over [0, %d)" % k
+        for stops in (None, list(range(T + 1)), [0, 2, T], [1, T - 1, T], [T - 1]):
+            _check(m, X, None, Y, want, stops, T)
 
 
 def test_actor_and_critic_rates():
