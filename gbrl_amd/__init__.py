@@ -32,6 +32,7 @@ _spec.loader.exec_module(gbrl_cpp)
 
 GBRL = gbrl_cpp.GBRL          # the reference exposes this as gbrl.GBRL_CPP (gbrl/__init__.py:115-118)
 GBRL_CPP = gbrl_cpp.GBRL
+PreparedDataset = gbrl_cpp.PreparedDataset   # GBRL.prepare_dataset(obs) -> PreparedDataset; GBRL.step_prepared(ds, grads, rows=None)
 cuda_available = gbrl_cpp.GBRL.cuda_available
 
-__all__ = ["GBRL", "GBRL_CPP", "gbrl_cpp", "cuda_available", "LIB_PATH"]
+__all__ = ["GBRL", "GBRL_CPP", "PreparedDataset", "gbrl_cpp", "cuda_available", "LIB_PATH"]

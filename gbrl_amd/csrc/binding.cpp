@@ -14,6 +14,7 @@
 #include <pybind11/pybind11.h>
 
 #include <cstring>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -605,6 +606,100 @@ void step_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &grads
     check(rc);
 }
 
+// Extension: a batch binned once and stepped on many times (gbrl_hip_dataset, include/gbrl_hip.h).
+class PyDataset {
+   public:
+    gbrl_hip_dataset *h = nullptr;
+    explicit PyDataset(gbrl_hip_dataset *d) : h(d) {}
+    PyDataset(const PyDataset &) = delete;
+    PyDataset &operator=(const PyDataset &) = delete;
+    ~PyDataset() { gbrl_hip_dataset_destroy(h); }
+    gbrl_hip_dataset_desc info() const {
+        gbrl_hip_dataset_desc d{};
+        check(gbrl_hip_dataset_info(h, &d));
+        return d;
+    }
+};
+
+// rows=None | int32 NumPy vector | (data_ptr, (m,), "torch.int32", device)
+Input read_rows(py::object &rows, const std::string &fn) {
+    Input r = read_input(rows, "rows", true, fn, 2);
+    if (!rows.is_none() && !r.ptr && !(r.shape.size() == 1 && r.shape[0] == 0)) fail("Cannot call " + fn + " with a null rows pointer!");
+    if (!rows.is_none() && r.shape.size() != 1) fail("rows must be a one-dimensional int32 vector");
+    return r;
+}
+
+std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs) {
+    // categorical cells cannot be prepared: their split candidates depend on the step's gradients
+    bool cells = false;
+    if (py::isinstance<py::array>(obs)) cells = py::array(obs).dtype().kind() == 'S';
+    else if (py::isinstance<py::tuple>(obs) && py::len(obs) == 4) { const std::string dt = py::str(obs.cast<py::tuple>()[2]); cells = dt == "S128" || dt == "|S128"; }
+    if (cells) fail("prepare_dataset: categorical columns are not supported (their split candidates depend on the step's gradients)");
+    const gbrl_hip_metadata md = self.meta();
+    Input o = read_input(obs, "obs", false, "prepare_dataset", false);
+    if (!o.ptr) fail("Cannot call prepare_dataset without obs!");
+    int n, n_num;
+    if (o.shape.size() == 1) {   // as predict reads a 1-D input: one row of input_dim features, or a column
+        if (static_cast<int>(o.shape[0]) == md.input_dim) { n = 1; n_num = md.input_dim; } else { n = static_cast<int>(o.shape[0]); n_num = 1; }
+    } else if (o.shape.size() == 2) { n = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]);
+    } else fail("obs must have one or two dimensions");
+    gbrl_hip_dataset *d = nullptr;
+    {
+        py::gil_scoped_release release;
+        d = gbrl_hip_dataset_create(self.h, static_cast<const float *>(o.ptr), o.on_device, n, n_num);
+    }
+    if (!d) fail(gbrl_hip_last_error());
+    return std::unique_ptr<PyDataset>(new PyDataset(d));
+}
+
+void step_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &grads, py::object &rows) {
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    Input g = read_input(grads, "grads", false, "step_prepared", false);
+    int n, gdim;   // as step reads its gradients
+    if (g.shape.size() == 1) {
+        if (md.output_dim > 1) { n = 1; gdim = static_cast<int>(g.shape[0]); } else { n = static_cast<int>(g.shape[0]); gdim = 1; }
+    } else { n = static_cast<int>(g.shape[0]); gdim = static_cast<int>(g.shape[1]); }
+    if (gdim != md.output_dim) {
+        std::stringstream ss;
+        ss << "Gradient output dim " << gdim << " != correct output dim " << md.output_dim;
+        fail(ss.str());
+    }
+    Input r = read_rows(rows, "step_prepared");
+    if (!rows.is_none()) {
+        const int m = static_cast<int>(r.shape[0]);
+        if (m != n) {
+            std::stringstream ss;
+            ss << "Number of rows " << m << " != number of gradient samples " << n;
+            fail(ss.str());
+        }
+    }
+    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
+    const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_step_prepared(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, rp, r.ptr ? r.on_device : 0, n);
+    }
+    check(rc);
+}
+
+py::array dataset_codes_impl(PyDataset &self, py::object &rows) {
+    const gbrl_hip_dataset_desc d = self.info();
+    Input r = read_rows(rows, "codes");
+    const int m = rows.is_none() ? d.n_rows : static_cast<int>(r.shape[0]);
+    if (m <= 0) fail("dataset_codes: no rows (m must be positive)");
+    py::array_t<uint16_t> out({static_cast<py::ssize_t>(d.code_groups), static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(16)});
+    uint16_t *op = out.mutable_data();
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_dataset_codes(self.h, static_cast<const int32_t *>(r.ptr), r.on_device, m, op);
+    }
+    check(rc);
+    return std::move(out);
+}
+
 float fit_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, int iterations, bool shuffle,
                const std::string &loss_type) {
     if (loss_type != "MultiRMSE") fail("Invalid loss function! Options are: MultiRMSE");   // stringTolossType, types.cpp:52-56
@@ -740,6 +835,25 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         feat.resize({nd}, false); first.resize({nd}, false); count.resize({nd}, false); total.resize({nd}, false);
         return py::make_tuple(feat, first, count, total);
     }, py::arg("categorical_obs"), py::arg("grads"));
+    py::class_<PyDataset> pds(m, "PreparedDataset",
+                              "A batch of numeric observations binned once (GBRL.prepare_dataset) and stepped on many times (GBRL.step_prepared): thresholds, "
+                              "threshold keys and class codes on the device.  Read-only after its creation; several models may share one.");
+    pds.def_property_readonly("n_rows", [](const PyDataset &d) { return d.info().n_rows; });
+    pds.def_property_readonly("n_features", [](const PyDataset &d) { return d.info().n_features; });
+    pds.def_property_readonly("n_bins", [](const PyDataset &d) { return d.info().n_bins; });
+    pds.def_property_readonly("generator_type", [](const PyDataset &d) { return std::string(d.info().generator_type == GBRL_HIP_GEN_UNIFORM ? "Uniform" : "Quantile"); });
+    pds.def_property_readonly("nbytes", [](const PyDataset &d) { return static_cast<size_t>(d.info().nbytes); });
+    pds.def("_handle", [](const PyDataset &d) { return reinterpret_cast<uintptr_t>(d.h); }, "the gbrl_hip_dataset* of this data set (tests that call the C ABI)");
+    pds.def("thresholds", [](const PyDataset &d) {
+        const gbrl_hip_dataset_desc i = d.info();
+        py::array_t<float> out({static_cast<py::ssize_t>(i.n_features), static_cast<py::ssize_t>(i.n_bins)});
+        check(gbrl_hip_dataset_thresholds(d.h, out.mutable_data()));
+        return out;
+    }, "thresholds() -> float32 [n_features, n_bins]: the split candidates of the batch");
+    pds.def("codes", &dataset_codes_impl, py::arg("rows") = py::none(),
+            "codes(rows=None) -> uint16 [ceil(n_features / 16), m, 16]: the class codes, group-major; code of feature f and row r at [f // 16, r, f % 16] = number of\n"
+            "thresholds of f below obs[r, f].  rows (int32 vector, NumPy or (ptr, (m,), 'torch.int32', 'cuda'), duplicates allowed): the records of those rows,\n"
+            "gathered on the device.");
     py::class_<PyGBRL> g(m, "GBRL");
     g.def(py::init<int, int, int, int, int, int, int, float, std::string, std::string, bool, int, std::string, int, std::string, std::string>(),
           py::arg("input_dim") = 1, py::arg("output_dim") = 1, py::arg("policy_dim") = 1, py::arg("max_depth") = 4,
@@ -772,6 +886,16 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     }, py::return_value_policy::take_ownership);
     g.def("to_device", [](PyGBRL &self, const std::string &d) { self.device = parse_device(d); }, py::arg("device"));
     g.def("step", &step_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("grads"));
+    g.def("prepare_dataset", &prepare_dataset_impl, py::arg("obs"),
+          "prepare_dataset(obs) -> PreparedDataset\n\n"
+          "The numeric preparation of step(obs, None, grads) -- key transpose, split thresholds, class codes, on step's own code paths -- done once and kept on\n"
+          "the device.  obs is not needed after the call.  Numeric columns only: categorical split candidates depend on the step's gradients.");
+    g.def("step_prepared", &step_prepared_impl, py::arg("ds"), py::arg("grads"), py::arg("rows") = py::none(),
+          "step_prepared(ds, grads, rows=None)\n\n"
+          "One boosting step on a prepared data set: with rows=None the model ends up byte for byte as step(obs, None, grads) would leave it, without the\n"
+          "transpose, candidates and binning phases.  rows (int32 vector of length m, duplicates allowed, entries in [0, ds.n_rows)): the tree is grown on\n"
+          "those rows, grads [m, output_dim] in their order, with the DATA SET'S thresholds (as fit() uses whole-data-set candidates), not the subset's\n"
+          "quantiles.  Any model on the same device with the data set's n_bins and generator_type and input_dim == ds.n_features may step on it.");
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);
     }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("return_torch") = false);

@@ -1,7 +1,9 @@
 // c_api.cpp -- the extern "C" surface declared in include/gbrl_hip.h.  Exceptions never cross the boundary: they are
 // turned into status codes + a thread-local message (the reference throws std::runtime_error at the same places).
+#include <memory>
 #include <mutex>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 #include <utility>
 #include <hip/hip_runtime.h>
@@ -26,6 +28,10 @@ struct gbrl_hip_model {
     explicit gbrl_hip_model(const gbrl_hip_model &o) : engine(o.engine) {}
 };
 
+struct gbrl_hip_dataset {
+    std::unique_ptr<gbrl::PreparedDataset> d;
+};
+
 namespace {
 thread_local std::string g_err;
 
@@ -41,6 +47,21 @@ int guarded(Fn &&fn) {
     } catch (const gbrl::InvalidArgument &e) { g_err = e.what(); return GBRL_HIP_E_INVALID;
     } catch (const std::bad_alloc &) { g_err = "out of host memory"; return GBRL_HIP_E_INVALID;
     } catch (const std::exception &e) { g_err = e.what(); return GBRL_HIP_E_INVALID; }
+}
+
+thread_local int g_ds_status = GBRL_HIP_OK;   // gbrl_hip_dataset_create returns a handle: its status is kept per thread
+
+struct DatasetRegistry {
+    std::mutex mu;
+    std::unordered_set<const gbrl_hip_dataset *> live;
+};
+DatasetRegistry &ds_registry() { static DatasetRegistry *r = new DatasetRegistry(); return *r; }
+const gbrl::PreparedDataset &live_dataset(const gbrl_hip_dataset *ds) {
+    if (ds) {
+        std::lock_guard<std::mutex> lk(ds_registry().mu);
+        if (ds_registry().live.count(ds)) return *ds->d;
+    }
+    throw gbrl::InvalidArgument(ds ? "the data set has been destroyed (or is not a data set of this library)" : "null data set");
 }
 
 int copy_in(void *dst, const void *src, size_t bytes, int on_device) {
@@ -438,6 +459,58 @@ int gbrl_hip_refit_leaves(gbrl_hip_model *m, const float *obs, int obs_on_device
         if (!m) throw gbrl::InvalidArgument("null model");
         m->engine.refit_leaves(obs, obs_on_device != 0, cat_obs, cat_on_device != 0, targets, targets_on_device != 0, n_samples, n_num_features,
                                n_cat_features, start_tree, stop_tree, decay_rate, loss_out);
+    });
+}
+
+// ---- prepared data sets: handles are looked up in a registry, so a destroyed (or never created) handle is an argument error, not a dangling read
+gbrl_hip_dataset *gbrl_hip_dataset_create(gbrl_hip_model *m, const float *obs, int obs_on_device, int n_samples, int n_num_features) {
+    gbrl_hip_dataset *ds = nullptr;
+    g_ds_status = guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        std::unique_ptr<gbrl::PreparedDataset> p(m->engine.prepare_dataset(obs, obs_on_device != 0, n_samples, n_num_features));
+        ds = new gbrl_hip_dataset{std::move(p)};
+        std::lock_guard<std::mutex> lk(ds_registry().mu);
+        ds_registry().live.insert(ds);
+    });
+    return ds;
+}
+int gbrl_hip_dataset_last_status(void) { return g_ds_status; }
+
+void gbrl_hip_dataset_destroy(gbrl_hip_dataset *ds) {
+    if (!ds) return;
+    {
+        std::lock_guard<std::mutex> lk(ds_registry().mu);
+        if (ds_registry().live.erase(ds) == 0) return;   // not (or no longer) a data set of this library
+    }
+    delete ds;
+}
+
+int gbrl_hip_dataset_info(const gbrl_hip_dataset *ds, gbrl_hip_dataset_desc *out) {
+    return guarded([&] {
+        const gbrl::PreparedDataset &d = live_dataset(ds);
+        if (!out) throw gbrl::InvalidArgument("null argument");
+        out->n_rows = d.n; out->n_features = d.F; out->n_bins = d.n_bins; out->generator_type = d.generator_type; out->device = d.device;
+        out->code_groups = d.code_groups(); out->nbytes = d.nbytes();
+    });
+}
+
+int gbrl_hip_dataset_thresholds(const gbrl_hip_dataset *ds, float *out) {
+    return guarded([&] {
+        const gbrl::PreparedDataset &d = live_dataset(ds);
+        if (!out) throw gbrl::InvalidArgument("null argument");
+        std::memcpy(out, d.h_thr.data(), sizeof(float) * d.h_thr.size());
+    });
+}
+
+int gbrl_hip_dataset_codes(const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, uint16_t *out) {
+    return guarded([&] { live_dataset(ds).codes_to_host(rows, rows_on_device != 0, n_rows, out); });
+}
+
+int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *grads, int grads_on_device, const int32_t *rows,
+                           int rows_on_device, int n_rows) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.step_prepared(&live_dataset(ds), grads, grads_on_device != 0, rows, rows_on_device != 0, n_rows);
     });
 }
 

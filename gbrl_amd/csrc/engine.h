@@ -59,9 +59,50 @@ class PinnedBuf {
     size_t cap_ = 0;
 };
 
+// The numeric preparation of a batch -- everything the growth paths read about the observations (detail::GrowCtx: d_thr, d_thrkeys, root_le, d_kt,
+// d_codes, d_codes_fm) lands in one buffer set: the engine's per-step workspace for step(), a PreparedDataset's own for prepare_dataset().
+struct PrepBuffers {
+    DevBuf kt;         // [F][N] feature-major ordered keys of the observations (the partition's 4-byte reads)
+    DevBuf codes;      // [ceil(slots / 16)][N][16] u16 class codes, group-major
+    DevBuf thr;        // [F][B] thresholds
+    DevBuf thrkeys;    // [F][B] ordered keys of the thresholds
+    DevBuf codes_fm;   // [F][N] feature-major copy of the numeric codes (kern::small_prep -> kern::small_grow)
+    DevBuf root_le;    // [F][B] + [F]: #{keys <= threshold} from the radix selection
+};
+// What a preparation left in its buffer set (null: this path does not produce it; both are legal inputs of the growth paths).
+struct NumericPrep {
+    float *d_thr = nullptr;
+    uint32_t *d_thrkeys = nullptr;
+    uint16_t *d_codes = nullptr;
+    const uint32_t *d_kt = nullptr;
+    const uint16_t *d_codes_fm = nullptr;
+    const uint32_t *root_le = nullptr;
+};
+
+// Extension: a batch of numeric observations binned ONCE (Engine::prepare_dataset) and stepped on many times (Engine::step_prepared) -- LightGBM's
+// Dataset, XGBoost's QuantileDMatrix.  It owns its device buffers and is only ever read after its creation: any model on the same device with the
+// same n_bins, generator_type and input_dim == F may step on it, several models may share one.  include/gbrl_hip.h has the contract.
+class PreparedDataset {
+   public:
+    int n = 0, F = 0, n_bins = 0, generator_type = 0, device = -1;
+    PrepBuffers buf;
+    NumericPrep prep;              // pointers into buf
+    std::vector<float> h_thr;      // host copy of the thresholds [F][B]
+    int code_groups() const { return (F + 15) / 16; }
+    size_t nbytes() const {        // device bytes held + the host copy
+        return buf.kt.capacity() + buf.codes.capacity() + buf.thr.capacity() + buf.thrkeys.capacity() + buf.codes_fm.capacity() + buf.root_le.capacity() +
+               h_thr.size() * sizeof(float);
+    }
+    // the codes on the host (diagnostics; the data set's device, the null stream): out [G][m][16]; rows == nullptr: every row (m = n), else what
+    // kern::gather_code_records gives for rows (int32 [m], host or device, every entry in [0, n) or InvalidArgument)
+    void codes_to_host(const int32_t *rows, bool rows_dev, int m, uint16_t *out) const;
+};
+
 namespace detail {
 struct GrowCtx;
 struct HNode;
+struct StepData;
+struct FusedStats;
 struct GrowDims;
 struct StepTables;
 struct LevelWork;
@@ -91,6 +132,15 @@ class Engine {
 
     void step(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *grads, bool grads_dev, int n,
               int n_num, int n_cat);
+    // Extension (engine_prepared.hip): the numeric preparation of step() -- key transpose, thresholds, class codes, on the same code paths -- into
+    // a data set of its own, and a step on it.  prepare_dataset waits for the stream: `obs` is not needed afterwards.  step_prepared runs the
+    // gradient statistics, grows the tree from the data set's buffers and appends it; with rows == nullptr the model ends up byte for byte as
+    // step(obs, nullptr, grads) would leave it.  rows (int32 [m], host or device, duplicates allowed, every entry in [0, n)): the tree is grown on
+    // those m rows with THE DATA SET'S thresholds (not the quantiles of the subset; what fit() does with whole-data-set candidates), grads is
+    // [m][D] in the order of rows.  Numeric-only, one GPU.  Every argument error is raised before the device is touched, an out-of-range index
+    // before anything reads through it; after any failure the model is unchanged.
+    PreparedDataset *prepare_dataset(const float *obs, bool obs_dev, int n, int n_num);
+    void step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m);
     void predict(const float *obs, bool obs_dev, const char *cat, bool cat_dev, int n, int n_num, int n_cat, int start_tree,
                  int stop_tree, float *out, bool out_dev);
     // Extension (not in the reference, which compares the 128-byte cells inside every predict call): the dictionary ids of a batch of
@@ -218,7 +268,17 @@ class Engine {
     void sharded_categorical_ranking(const char *hcat, const float *hgrads, int N, int Fc, int D, int B, std::vector<detail::CatCandidate> &cat_cands,
                                      std::vector<uint16_t> &h_catcodes, std::vector<int> &cat_classes);
     void numeric_thresholds(const float *dobs, int N, int F, int B, long long n_global, const uint32_t *d_kt, float *d_thr,
-                            uint32_t *d_thrkeys, int pass1_chunks = 0, uint16_t *d_codes_out = nullptr, bool *codes_written = nullptr);
+                            uint32_t *d_thrkeys, DevBuf &root_le_buf, const uint32_t **root_le_out, int pass1_chunks = 0, uint16_t *d_codes_out = nullptr,
+                            bool *codes_written = nullptr);
+    // ---- the stages step() and step_prepared() share (engine_step.hip) ----
+    void read_step_hooks();                                              // the per-call test hooks that choose the selection path
+    bool fused_prep_applies(int N, int F, long long n_global) const;     // kern::small_prep is tried for this shape
+    void check_prepared_model(const char *what) const;                   // numeric-only, one GPU, step()'s limits: raised before the device is touched
+    // numeric preparation of a batch into `pb` (phases transpose / candidates / binning); fs: the gradient statistics that step() lets the
+    // fused preparation kernel compute in its launch (nullptr: want_stats = false)
+    NumericPrep prepare_numeric(PrepBuffers &pb, const float *dobs, int N, int F, int Fc, long long n_global, bool prep_candidate, detail::FusedStats *fs);
+    void run_grad_stats(detail::FusedStats &g, int N, long long &n_global);   // A2: statistics + quantisation (kern::small_stats when it applies)
+    void grow_step_tree(const detail::StepData &d, std::vector<detail::HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc, double &leaf_scale);
     int64_t *quantile_cum_device(const std::vector<int64_t> &cum, long long n_global, int B);   // device copy of the quantile target ranks (cached)
     void phase_begin(bool key = false);
     void phase_end(const char *name, bool key = false);
@@ -279,7 +339,8 @@ class Engine {
     const void *pub_done_ptr_ = nullptr;
     const void *leafacc_clean_ptr_ = nullptr;   // leaf accumulators known to be zero (handed back clean by the last publication)
     size_t leafacc_clean_bytes_ = 0;
-    DevBuf d_codes_fm_;               // feature-major copy of the numeric class codes (kern::small_prep -> kern::small_grow)
+    PrepBuffers prep_ws_;             // step()'s numeric preparation; step_prepared(rows) gathers the subset's codes into prep_ws_.codes
+    DevBuf d_sub_rows_, d_rows_mm_;   // step_prepared(rows): device copy of a host index vector, min / max of a device one
     DevBuf d_am_s_, d_near_list_, d_near_ent_, d_near_rep_, d_near_nr_, d_near_maps_, d_near_pos_, d_near_nrb_, d_near_vals_, d_near_means_, d_near_sums_, d_near_chains_, d_near_rowsort_, d_near_tiles_;   // near-tie replay (kern::near_tie_replay): runner-up per arg-max block, candidate lists, ordered row lists, replayed scores
     bool small_grow_off_ = false;     // latched after a failed launch / an abandoned grid barrier of the one-launch kernel: this engine keeps to the level loop
     long long small_grow_fallbacks_ = 0;   // trees the level loop grew after such a failure (diagnostics)
@@ -301,10 +362,10 @@ class Engine {
 
     // ---- per-step workspace (grow-only, reused across steps) ----
     DevBuf d_obs_, d_grads_, d_qg_, d_stat_, d_partials_f64_, d_meanden_, d_maxbits_;
-    DevBuf d_thr_, d_thrkeys_, d_prefix_, d_trial_, d_counts_, d_cum_, d_minmax_;
-    DevBuf d_selcnt_, d_kcls_, d_kt_, d_qflags_, d_splitters_, d_ccounts_, d_c2l_, d_tgt_list_, d_tgt_rank_, d_list_off_, d_qlists_;
+    DevBuf d_prefix_, d_trial_, d_counts_, d_cum_, d_minmax_;
+    DevBuf d_selcnt_, d_kcls_, d_qflags_, d_splitters_, d_ccounts_, d_c2l_, d_tgt_list_, d_tgt_rank_, d_list_off_, d_qlists_;
     DevBuf d_radix_state_, d_radix_partial_, d_radix_global_, d_scales_;
-    DevBuf d_codes_, d_catcodes_, d_rows_[2];
+    DevBuf d_catcodes_, d_rows_[2];
     DevBuf d_hist_prev_, d_am_v_, d_am_i_, d_stage_const_, d_stage_a_, d_stage_b_, d_results_;
     PinnedBuf pin_const_, pin_a_, pin_b_, pin_res_, pin_thr_, pin_acc_, pin_cat_, pin_cat_dict_;
     DevBuf d_hist_partials_, d_hist_, d_hist_local_, d_hist_recv_, d_gather_, d_scores_, d_parent_;
@@ -349,8 +410,6 @@ class Engine {
     DevBuf d_dict_off_, d_dict_hash_, d_dict_id_, d_dict_words_, d_pcells_;
     PinnedBuf pin_model_stage_;           // the slices sync_model_to_device appends, staged for one kern::stage_copy launch
     hipEvent_t ev_model_stage_ = nullptr; // behind that launch: the block is not refilled before it has been read
-    DevBuf d_root_le_;
-    const uint32_t *root_le_ = nullptr;   // this step's #{keys <= threshold} table (radix selection, one GPU), null otherwise
     DevBuf d_cat_keys_, d_cat_first_, d_cat_meta_, d_cat_lslot_, d_sdict_, d_cat_xchg_, d_cat_slotq_, d_cat_clsq_;
     PinnedBuf pin_cat_cls_;
     DevBuf d_cat_rank_, d_cat_rank_cnt_, d_cat_rank_tot_;   // kern::cat_rank: scratch, count and total per distinct cell (more distinct cells than candidates)

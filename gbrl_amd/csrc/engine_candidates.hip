@@ -630,8 +630,10 @@ int64_t *Engine::quantile_cum_device(const std::vector<int64_t> &cum, long long 
     return d_cum;
 }
 void Engine::numeric_thresholds(const float *dobs, int N, int F, int B, long long n_global, const uint32_t *d_kt, float *d_thr,
-                                uint32_t *d_thrkeys, int pass1_chunks, uint16_t *d_codes_out, bool *codes_written) {
+                                uint32_t *d_thrkeys, DevBuf &root_le_buf, const uint32_t **root_le_out, int pass1_chunks, uint16_t *d_codes_out,
+                                bool *codes_written) {
     if (codes_written) *codes_written = false;
+    if (root_le_out) *root_le_out = nullptr;
     hipStream_t s = stream_;
     const gbrl_hip_metadata &md = model.meta;
     uint32_t *d_qflags = static_cast<uint32_t *>(d_qflags_.ensure(sizeof(uint32_t) * 4));  // [0,1] allocator, [2] overflow
@@ -718,9 +720,9 @@ void Engine::numeric_thresholds(const float *dobs, int N, int F, int B, long lon
                     comm.partial_global = static_cast<uint32_t *>(d_radix_global_.ensure(kern::radix_global_partial_bytes(F)));
                 }
                 // (one GPU: the selection also reports #{keys <= threshold}, from which the ROOT's class counts follow -- grow_tree, root_le)
-                uint32_t *d_le = has_coll_ ? nullptr : static_cast<uint32_t *>(d_root_le_.ensure(sizeof(uint32_t) * (static_cast<size_t>(F) * B + F)));
+                uint32_t *d_le = has_coll_ ? nullptr : static_cast<uint32_t *>(root_le_buf.ensure(sizeof(uint32_t) * (static_cast<size_t>(F) * B + F)));
                 const int rc = kern::radix_select(d_kt, N, F, d_cum, B, d_rs, d_rp, d_rl, d_thrkeys, s, has_coll_ ? &comm : nullptr, pass1_chunks, d_le);
-                root_le_ = d_le;
+                if (root_le_out) *root_le_out = d_le;
                 if (rc != 0) throw HipError(rc == 2 ? "allreduce failed" : "radix select failed");
                 last_quantile_fallback_ = false;
             } else {

@@ -1,0 +1,204 @@
+// engine_prepared.hip -- a batch binned once and stepped on many times (see engine.h, PreparedDataset):
+//   Engine::prepare_dataset   the numeric preparation of step() (Engine::prepare_numeric, engine_step.hip: key transpose, thresholds, class codes,
+//                             the fused kern::small_prep with want_stats = false) into buffers the data set owns
+//   Engine::step_prepared     gradient statistics (Engine::run_grad_stats), the GrowCtx from the data set, grow_tree, append_tree -- no transpose,
+//                             no candidates, no binning.  A row subset gathers the subset's 32-byte code records (kern::gather_code_records) into
+//                             the engine's workspace and grows on them with the DATA SET'S thresholds; keys, feature-major codes and the root's
+//                             count table are handed over as null there (legal inputs of every growth path: the partition then reads the
+//                             codes, the root histogram counts its rows).
+//   PreparedDataset::codes_to_host   the codes on the host, all rows or a gathered subset
+// None of the growth kernels is touched: integer histograms do not depend on which of the optional buffers a path reads.
+#include "engine_step_detail.h"
+
+#include <memory>
+
+namespace gbrl {
+
+// numeric-only, one GPU: categorical candidates depend on the step's gradients, sharded thresholds need the exchange
+void Engine::check_prepared_model(const char *what) const {
+    const gbrl_hip_metadata &md = model.meta;
+    if (has_coll_ || rccl_comm_ != nullptr)
+        throw Unsupported(std::string(what) + ": not available on a model with a communicator or collective hooks (the thresholds of a row-sharded batch need the exchange)");
+    if (md.iteration > 0 && md.n_cat_features > 0)
+        throw Unsupported(std::string(what) + ": not available on a model with categorical columns (their split candidates depend on the step's gradients)");
+}
+
+PreparedDataset *Engine::prepare_dataset(const float *obs, bool obs_dev, int n, int n_num) {
+    const gbrl_hip_metadata &md = model.meta;
+    check_prepared_model("prepare_dataset");
+    if (md.iteration > 0 && n_num != md.n_num_features) throw InvalidArgument("Incompatible dataset");
+    if (n_num != md.input_dim) throw InvalidArgument("Total number of features != correct input dim");
+    if (n <= 0 || n_num <= 0 || obs == nullptr) throw InvalidArgument("Cannot call prepare_dataset without obs!");
+    if (md.max_depth > kern::kMaxPath) throw Unsupported("max_depth > 32 is not supported");
+    if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
+    if ((n_num + kern::kCodeGroup - 1) / kern::kCodeGroup > 65535) throw Unsupported("prepare_dataset: more than 65535 groups of 16 features");
+    ensure_device();
+    prof_step_entry_ = std::chrono::steady_clock::now();
+    ev_used_ = 0;
+    ev_names_.clear();
+    exch_bytes_ = 0;
+    exch_calls_ = 0;
+    read_step_hooks();
+    hipStream_t s = stream_;
+    const int N = n, F = n_num, B = md.n_bins;
+    std::unique_ptr<PreparedDataset> ds(new PreparedDataset());
+    ds->n = N; ds->F = F; ds->n_bins = B; ds->generator_type = md.generator_type; ds->device = device_ordinal_;
+    phase_begin();
+    const float *dobs = obs;
+    if (!obs_dev) {
+        dobs = static_cast<float *>(d_obs_.ensure(sizeof(float) * N * F));
+        hip_check(hipMemcpyAsync(const_cast<float *>(dobs), obs, sizeof(float) * N * F, hipMemcpyHostToDevice, s), "H2D obs");
+    }
+    phase_end("inputs");
+    prof_marks_[0] = std::chrono::steady_clock::now();
+    ds->prep = prepare_numeric(ds->buf, dobs, N, F, 0, N, fused_prep_applies(N, F, N), nullptr);
+    ds->h_thr.resize(static_cast<size_t>(F) * B);
+    hip_check(hipMemcpyAsync(ds->h_thr.data(), ds->prep.d_thr, sizeof(float) * ds->h_thr.size(), hipMemcpyDeviceToHost, s), "D2H thr");
+    hip_check(hipStreamSynchronize(s), "sync");   // the caller's obs is not needed from here on
+    hip_check(hipGetLastError(), "prepare_dataset kernels");
+    phases_resolve();
+    return ds.release();
+}
+
+namespace {
+// Device copy of an index vector, every entry known to lie in [0, n) BEFORE anything reads through it: a host vector is checked on the host
+// (check_host_rows, before the device is touched), a device vector by kern::rows_minmax, read back.
+const int32_t *checked_rows(DevBuf &copy, DevBuf &mm_buf, const int32_t *rows, bool rows_dev, int m, int n, hipStream_t s) {
+    if (!rows_dev) {
+        int32_t *d = static_cast<int32_t *>(copy.ensure(sizeof(int32_t) * static_cast<size_t>(m)));
+        hip_check(hipMemcpyAsync(d, rows, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyHostToDevice, s), "H2D rows");
+        return d;
+    }
+    int32_t *d_mm = static_cast<int32_t *>(mm_buf.ensure(2 * sizeof(int32_t)));
+    kern::rows_minmax(rows, m, d_mm, s);
+    int32_t mm[2] = {0, 0};
+    hip_check(hipMemcpyAsync(mm, d_mm, sizeof(mm), hipMemcpyDeviceToHost, s), "D2H rows min/max");
+    hip_check(hipStreamSynchronize(s), "sync");
+    const int lo = mm[0], hi = ~mm[1];
+    if (lo < 0 || hi >= n)
+        throw InvalidArgument("rows: index " + std::to_string(lo < 0 ? lo : hi) + " is outside [0, " + std::to_string(n) + ")");
+    return rows;
+}
+void check_host_rows(const int32_t *rows, int m, int n) {
+    for (int j = 0; j < m; ++j)
+        if (rows[j] < 0 || rows[j] >= n)
+            throw InvalidArgument("rows: index " + std::to_string(rows[j]) + " (entry " + std::to_string(j) + ") is outside [0, " + std::to_string(n) + ")");
+}
+}  // namespace
+
+void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m) {
+    gbrl_hip_metadata &md = model.meta;
+    if (ds == nullptr) throw InvalidArgument("step_prepared: null data set");
+    check_prepared_model("step_prepared");
+    {
+        int dev = device_ordinal_;
+        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = -1;   // (an unlatched model runs on the calling thread's current device)
+        if (dev >= 0 && dev != ds->device)
+            throw Unsupported("step_prepared: the data set lives on device " + std::to_string(ds->device) + ", the model on device " + std::to_string(dev));
+    }
+    if (ds->n_bins != md.n_bins) throw InvalidArgument("step_prepared: the data set was binned with n_bins = " + std::to_string(ds->n_bins) + ", the model has " + std::to_string(md.n_bins));
+    if (ds->generator_type != md.generator_type) throw InvalidArgument("step_prepared: the data set's generator_type differs from the model's");
+    if (ds->F != md.input_dim) throw InvalidArgument("Total number of features != correct input dim");
+    if (md.iteration > 0 && ds->F != md.n_num_features) throw InvalidArgument("Incompatible dataset");
+    if (grads == nullptr) throw InvalidArgument("Cannot call step without grads!");
+    if (m <= 0) throw InvalidArgument("step_prepared: no rows (m must be positive)");
+    if (rows == nullptr && m != ds->n)
+        throw InvalidArgument("step_prepared: grads has " + std::to_string(m) + " rows, the data set " + std::to_string(ds->n) + " (pass rows to step on a subset)");
+    if (md.max_depth > kern::kMaxPath) throw Unsupported("max_depth > 32 is not supported");
+    if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
+    if (md.output_dim > 512) throw Unsupported("output_dim > 512");
+    if (rows != nullptr && !rows_dev) check_host_rows(rows, m, ds->n);
+    // GBRL::step, gbrl.cpp:946-958 (the latch is taken back when the step fails: the model is unchanged after any failure)
+    const int32_t keep_num = md.n_num_features, keep_cat = md.n_cat_features;
+    if (md.iteration == 0) { md.n_num_features = ds->F; md.n_cat_features = 0; }
+    try {
+        ensure_device();
+        prof_step_entry_ = std::chrono::steady_clock::now();
+        ev_used_ = 0;
+        ev_names_.clear();
+        exch_bytes_ = 0;
+        exch_calls_ = 0;
+        hipStream_t s = stream_;
+        const int N = m, F = ds->F, D = md.output_dim;
+        const bool cosine = md.split_score_func == GBRL_HIP_SCORE_COSINE;
+        long long n_global = N;
+        // ---- inputs on the device ---------------------------------------------------------------------------------
+        phase_begin();
+        const float *dgrads = grads;
+        if (!grads_dev) {
+            dgrads = static_cast<float *>(d_grads_.ensure(sizeof(float) * N * D));
+            hip_check(hipMemcpyAsync(const_cast<float *>(dgrads), grads, sizeof(float) * N * D, hipMemcpyHostToDevice, s), "H2D grads");
+        }
+        const int32_t *d_rows = rows ? checked_rows(d_sub_rows_, d_rows_mm_, rows, rows_dev, m, ds->n, s) : nullptr;
+        phase_end("inputs");
+        prof_marks_[0] = std::chrono::steady_clock::now();
+        // ---- 1. gradient statistics and quantisation (A2) ----------------------------------------------------------
+        phase_begin();
+        float *d_meanden = static_cast<float *>(d_meanden_.ensure(sizeof(float) * 2 * D));
+        double *d_stat = static_cast<double *>(d_stat_.ensure(sizeof(double) * 4 * D));
+        kern::StepScales *d_scales = static_cast<kern::StepScales *>(d_scales_.ensure(sizeof(kern::StepScales)));
+        int32_t *d_qg = static_cast<int32_t *>(d_qg_.ensure(sizeof(int32_t) * static_cast<size_t>(N) * D));
+        const bool no_small_stats = [] { const char *e = hooks::raw(hooks::NO_SMALL_STATS); return e && e[0] == '1'; }();   /* read per call: the tests flip it */
+        FusedStats gs{dgrads, D, cosine, d_stat, d_meanden, d_scales, d_qg, chunk_rows_of(n_global), !no_small_stats};
+        run_grad_stats(gs, N, n_global);
+        phase_end("grad_stats");
+        // ---- the subset's code records (the thresholds stay the data set's) ---------------------------------------
+        NumericPrep np = ds->prep;
+        if (d_rows) {
+            phase_begin();
+            const int G = ds->code_groups();
+            uint16_t *sub = static_cast<uint16_t *>(prep_ws_.codes.ensure(sizeof(uint16_t) * static_cast<size_t>(G) * N * kern::kCodeGroup));
+            kern::gather_code_records(ds->prep.d_codes, ds->n, G, d_rows, N, sub, s);
+            phase_end("gather_codes");
+            np.d_codes = sub;
+            np.d_kt = nullptr; np.d_codes_fm = nullptr; np.root_le = nullptr;
+        }
+        prof_marks_[1] = prof_marks_[2] = std::chrono::steady_clock::now();
+        prep_launches_ = 0;
+        // ---- feature slots, candidate order, weights, growth, leaf sums ------------------------------------------
+        const std::vector<CatCandidate> cat_cands;
+        const std::vector<int> cat_classes;
+        StepData sd{};
+        sd.N = N; sd.F = F; sd.Fc = 0; sd.n_global = n_global; sd.chunk_rows = gs.chunk_rows; sd.prep = np; sd.stats = &gs;
+        sd.cat_cands = &cat_cands; sd.cat_classes = &cat_classes;
+        std::vector<HNode> nodes;
+        std::vector<int> frontier;
+        std::vector<int64_t> acc;
+        double leaf_scale = 1.0;
+        grow_step_tree(sd, nodes, frontier, acc, leaf_scale);
+        hip_check(hipGetLastError(), "step kernels");
+        append_tree(model, nodes, frontier, acc, leaf_scale, cat_cands);
+        phases_resolve();
+    } catch (...) {
+        if (md.iteration == 0) { md.n_num_features = keep_num; md.n_cat_features = keep_cat; }
+        throw;
+    }
+}
+
+void PreparedDataset::codes_to_host(const int32_t *rows, bool rows_dev, int m, uint16_t *out) const {
+    if (out == nullptr) throw InvalidArgument("dataset_codes: no place for the codes");
+    if (rows == nullptr) m = n;
+    if (m <= 0) throw InvalidArgument("dataset_codes: no rows (m must be positive)");
+    if (rows != nullptr && !rows_dev) check_host_rows(rows, m, n);
+    struct Scope {   // the data set's device for this call, the caller's afterwards
+        int prev = -1;
+        explicit Scope(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; hip_check(hipSetDevice(dev), "hipSetDevice"); }
+        ~Scope() { if (prev >= 0) (void)hipSetDevice(prev); }
+    } scope(device);
+    hipStream_t s = nullptr;
+    const int G = code_groups();
+    const size_t bytes = sizeof(uint16_t) * static_cast<size_t>(G) * m * kern::kCodeGroup;
+    const uint16_t *src = prep.d_codes;
+    DevBuf sub, rows_copy, mm;
+    if (rows != nullptr) {
+        const int32_t *d_rows = checked_rows(rows_copy, mm, rows, rows_dev, m, n, s);
+        uint16_t *dst = static_cast<uint16_t *>(sub.ensure(bytes));
+        kern::gather_code_records(prep.d_codes, n, G, d_rows, m, dst, s);
+        hip_check(hipGetLastError(), "gather_code_records launch");
+        src = dst;
+    }
+    hip_check(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, s), "D2H codes");
+    hip_check(hipStreamSynchronize(s), "sync");
+}
+
+}  // namespace gbrl

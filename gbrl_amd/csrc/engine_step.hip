@@ -142,161 +142,107 @@ md.iteration += 1;  // fitter.cpp:114
 
 }  // namespace detail
 
-// ======================================================================================================== step
-void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *grads, bool grads_dev, int n,
-                  int n_num, int n_cat) {
-    gbrl_hip_metadata &md = model.meta;
-    // GBRL::step, gbrl.cpp:946-958
-    if (md.iteration == 0) { md.n_num_features = n_num; md.n_cat_features = n_cat; }
-    if (n_num != md.n_num_features || n_cat != md.n_cat_features) throw InvalidArgument("Incompatible dataset");
-    if (n_num + n_cat != md.input_dim) throw InvalidArgument("Total number of features != correct input dim");
-    if (n <= 0 || grads == nullptr) throw InvalidArgument("Cannot call step without grads!");
-    if (n_num > 0 && obs == nullptr) throw InvalidArgument("Cannot call step without obs!");
-    if (n_cat > 0 && cat == nullptr) throw InvalidArgument("Cannot call step without cat_obs!");
-    if (md.max_depth > kern::kMaxPath) throw Unsupported("max_depth > 32 is not supported");
-    if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
-    ensure_device();
-    prof_step_entry_ = std::chrono::steady_clock::now();
-    ev_used_ = 0;
-    ev_names_.clear();
-    exch_bytes_ = 0;
-    exch_calls_ = 0;
+// ======================================================================================== the stages step() and step_prepared() share
+namespace {
+// thresholds and scales reach the host through ONE pinned block: [F * B floats | 64-byte aligned StepScales]
+char *pinned_thr_block(PinnedBuf &pin, size_t n_thr, float *&h_thr, kern::StepScales *&h_scales) {
+    char *pin_ts = static_cast<char *>(pin.ensure(sizeof(float) * std::max<size_t>(1, n_thr) + sizeof(kern::StepScales) + 64));
+    h_thr = reinterpret_cast<float *>(pin_ts);
+    h_scales = reinterpret_cast<kern::StepScales *>(pin_ts + ((sizeof(float) * std::max<size_t>(1, n_thr) + 63) & ~static_cast<size_t>(63)));
+    return pin_ts;
+}
+}  // namespace
+
+void Engine::read_step_hooks() {
     if (const char *e = hooks::raw(hooks::FORCE_BISECTION)) force_bisection_ = e[0] == '1';   // test hook
     if (const char *e = hooks::raw(hooks::HOST_CATEGORICAL)) force_host_categorical_ = e[0] == '1';   // test hook: host scan of every cell
     if (const char *e = hooks::raw(hooks::QUANTILE_RADIX)) force_radix_ = e[0] == '1';   // test hook: radix multi-select also for small batches
     if (const char *e = hooks::raw(hooks::QUANTILE_SAMPLE)) force_sample_select_ = e[0] == '1';   // test hook: the sample/splitter selection on one GPU
+}
+
+// RL-sized steps on one GPU: statistics, quantisation, split candidates and class codes in ONE launch (kern::small_prep);
+// GBRL_HIP_NO_SMALL_PREP=1 (tests / measurement): the separate launches
+bool Engine::fused_prep_applies(int N, int F, long long n_global) const {
+    const bool no_small_prep = [] { const char *e = hooks::raw(hooks::NO_SMALL_PREP); return e && e[0] == '1'; }();   /* read per call: the tests flip it */
+    const bool no_sort_codes = [] { const char *e = hooks::raw(hooks::SORT_NO_CODES); return e && e[0] == '1'; }();   /* read per call: the tests flip it */
+    const bool uniform_gen = model.meta.generator_type == GBRL_HIP_GEN_UNIFORM;
+    return !has_coll_ && n_global == N && F > 0 && fixed_thr_.empty() && !candidates_only_ && !no_small_prep && !no_sort_codes && !force_bisection_ &&
+           !force_sample_select_ && !force_radix_ && N <= (uniform_gen ? 8192 : kern::sort_quantiles_max_rows());
+}
+
+// ---- 1. gradient statistics and quantisation (A2) ---------------------------------------------------------------------
+// sums -> mean -> centred squares -> std, maxima, scales: all on the device (k_stats_mean / k_stats_finish); the host reads the scales
+// together with the thresholds (one synchronisation for both).  Row-sharded runs sum the column sums (fp64) and take the maxima (fp32,
+// exact) over ranks between the kernels; the arithmetic stays on the device, so one GPU and N GPUs execute the same instructions on the
+// same global sums.  Row-sharded: n_global arrives with the first message, and g.chunk_rows follows it.
+void Engine::run_grad_stats(FusedStats &g, int N, long long &n_global) {
     hipStream_t s = stream_;
-    const int N = n, F = n_num, Fc = n_cat, D = md.output_dim, B = md.n_bins, MD = md.max_depth;
-    const bool cosine = md.split_score_func == GBRL_HIP_SCORE_COSINE;
-    const bool oblivious = model.oblivious();
-    const int world = has_coll_ ? coll_.world_size : 1;
-
-    // global row count (rows are sharded over ranks): it travels with the first gradient-statistics message below (round 6: no exchange and no
-    // idle device for it); until then n_global holds this rank's count and nothing reads it
-    long long n_global = N;
-
-    // ---- inputs on the device -------------------------------------------------------------------------------------
-    phase_begin();
-    const float *dobs = obs;
-    if (F > 0 && !obs_dev) {
-        dobs = static_cast<float *>(d_obs_.ensure(sizeof(float) * N * F));
-        hip_check(hipMemcpyAsync(const_cast<float *>(dobs), obs, sizeof(float) * N * F, hipMemcpyHostToDevice, s), "H2D obs");
-    }
-    const float *dgrads = grads;
-    if (!grads_dev) {
-        dgrads = static_cast<float *>(d_grads_.ensure(sizeof(float) * N * D));
-        hip_check(hipMemcpyAsync(const_cast<float *>(dgrads), grads, sizeof(float) * N * D, hipMemcpyHostToDevice, s), "H2D grads");
-    }
-    // categorical cells on the device: the distinct categories of the batch are found there (device_categorical_candidates);
-    // the host-side scan of every cell is only the fallback
-    const char *dcells = cat;
-    if (Fc > 0 && !cat_dev) {
-        char *t = static_cast<char *>(d_pcells_.ensure(static_cast<size_t>(N) * Fc * kCat));
-        hip_check(hipMemcpyAsync(t, cat, static_cast<size_t>(N) * Fc * kCat, hipMemcpyHostToDevice, s), "H2D cat cells");
-        dcells = t;
-    }
-    phase_end("inputs");
-    prof_marks_[0] = std::chrono::steady_clock::now();
-    // the scan for the batch's distinct categorical cells goes first: its result is read by the HOST (device_categorical_candidates)
-    const bool cat_early = Fc > 0 && !fixed_cat_valid_ && (has_coll_ || !force_host_categorical_);
-    cat_launched_ = false;   // (a step that threw between the two stages must not be resumed)
-    if (cat_early) {
-        std::vector<CatCandidate> none;
-        std::vector<int> none_classes(Fc, 0);
-        (void)device_categorical_candidates(dcells, cat_dev ? nullptr : cat, N, Fc, B, none, none_classes, /*launch_only=*/true);
-    }
-
-    // ---- 1. gradient statistics and quantisation (A2) -----------------------------------------------------------------
-    phase_begin();
+    const int D = g.D, world = has_coll_ ? coll_.world_size : 1;
+    const bool cosine = g.cosine;
+    const float *dgrads = g.dgrads;
+    double *d_stat = g.d_stat;
+    float *d_meanden = g.d_meanden;
+    kern::StepScales *d_scales = g.d_scales;
+    int32_t *d_qg = g.d_qg;
     const size_t n_el = static_cast<size_t>(N) * D;
-    float *d_meanden = static_cast<float *>(d_meanden_.ensure(sizeof(float) * 2 * D));
     const float *d_mean = nullptr, *d_den = nullptr;
-    double *d_stat = static_cast<double *>(d_stat_.ensure(sizeof(double) * 4 * D));
+    g.done = true;
+    // RL-sized batch on one GPU: statistics and quantisation in ONE launch with the same reduction tree (kern::small_stats)
+    if (!has_coll_ && g.fuse && n_global == N && kern::small_stats(dgrads, N, D, !cosine, g.chunk_rows, d_stat, d_meanden, d_scales, d_qg, s)) return;
     const int nblk = kern::column_sums_blocks(N, D);
     double *d_part = static_cast<double *>(d_partials_f64_.ensure(sizeof(double) * nblk * 2 * D));
-    if (D > 512) throw Unsupported("output_dim > 512");
-    // LDS accumulators are int32 and one block adds at most `chunk_rows` rows into a cell: the power-of-two scale keeps
-    // chunk_rows * max|q| < 2^31 (exactness of the wrapped int32 sums, kernels.hip k_hist_build).
-    // A histogram block accumulates one chunk of one node's rows.  Chunks are sized per level so that the whole level is ONE
-    // balanced round of <= 32 chunks x (feature groups) blocks (k_hist_build keeps one block per CU); `chunk_rows` is the cap
-    // the fixed-point scale is derived from.  Leaf sums: int64 fixed point with n_global * max|g| * 2^lbits < 2^62.
-    // It depends on the GLOBAL row count only (clamped to [4096, 65536]), so the scale -- and with it every integer sum -- is
-    // the same for any sharding of the same rows.
-    auto chunk_rows_of = [](long long n) { return static_cast<int>(std::min<long long>(65536, std::max<long long>(4096, 2 * ((n + 31) / 32)))); };
-    int chunk_rows = chunk_rows_of(n_global);      // (row-sharded: set again once the global count is known)
-    kern::StepScales *d_scales = static_cast<kern::StepScales *>(d_scales_.ensure(sizeof(kern::StepScales)));
-    bool stats_fused = false;
-    int32_t *d_qg = static_cast<int32_t *>(d_qg_.ensure(sizeof(int32_t) * n_el));
-    // RL-sized steps on one GPU: statistics, quantisation, split candidates and class codes in ONE launch (kern::small_prep, below, where the
-    // candidate buffers exist); GBRL_HIP_NO_SMALL_PREP=1 (tests / measurement): the separate launches
-    const bool no_small_prep = [] { const char *e = hooks::raw(hooks::NO_SMALL_PREP); return e && e[0] == '1'; }();   /* read per call: the tests flip it */
-    const bool no_small_stats = [] { const char *e = hooks::raw(hooks::NO_SMALL_STATS); return e && e[0] == '1'; }();   /* read per call: the tests flip it */
-    const bool no_sort_codes = [] { const char *e = hooks::raw(hooks::SORT_NO_CODES); return e && e[0] == '1'; }();   /* read per call: the tests flip it */
-    const bool uniform_gen = md.generator_type == GBRL_HIP_GEN_UNIFORM;
-    const bool prep_candidate = !has_coll_ && n_global == N && F > 0 && fixed_thr_.empty() && !candidates_only_ && !no_small_prep && !no_sort_codes &&
-                                !force_bisection_ && !force_sample_select_ && !force_radix_ && N <= (uniform_gen ? 8192 : kern::sort_quantiles_max_rows());
-    auto run_stats = [&]() {
-        // sums -> mean -> centred squares -> std, maxima, scales: all on the device (k_stats_mean / k_stats_finish); the host
-        // reads the scales together with the thresholds (one synchronisation for both).  Row-sharded runs sum the column
-        // sums (fp64) and take the maxima (fp32, exact) over ranks between the kernels; the arithmetic stays on the device,
-        // so one GPU and N GPUs execute the same instructions on the same global sums.
-        double *d_stat2 = d_stat + 2 * D;
-        // one message per statistics round: the sums and every rank's maxima (gathered through the sum, kern::stats_pack)
-        // (+ one word: this rank's row count in the first round -- integers below 2^53 add exactly in float64)
-        const size_t smsg_words = static_cast<size_t>(D) * (world + 1) + 1;
-        double *d_smsg = has_coll_ ? static_cast<double *>(d_maxbits_.ensure(sizeof(double) * smsg_words)) : nullptr;
-        auto exchange_stats = [&](double *st, bool with_row_count) {
-            if (!has_coll_) return;
-            kern::stats_pack(st, D, world, coll_.rank, d_smsg, s, with_row_count ? static_cast<double>(N) : 0.0);
-            exchange(Red::SumF64, d_smsg, smsg_words);
-            kern::stats_unpack(d_smsg, D, world, st, s);
-            if (with_row_count) {
-                // the host needs the global count from here on (chunk length -> fixed-point scale, target ranks of the selection, leaf scale)
-                double hv = 0.0;
-                hip_check(hipMemcpyAsync(&hv, d_smsg + smsg_words - 1, sizeof(hv), hipMemcpyDeviceToHost, s), "D2H n");
-                hip_check(hipStreamSynchronize(s), "sync");
-                n_global = static_cast<long long>(hv);
-                chunk_rows = chunk_rows_of(n_global);
-            }
-        };
-        // RL-sized batch on one GPU: statistics and quantisation in ONE launch with the same reduction tree (kern::small_stats)
-        if (!has_coll_ && !no_small_stats && n_global == N && kern::small_stats(dgrads, N, D, !cosine, chunk_rows, d_stat, d_meanden, d_scales, d_qg, s)) {
-            stats_fused = true;
-            if (!cosine) { d_mean = d_meanden; d_den = d_meanden + D; }
-        } else {
-        kern::column_sums(dgrads, N, D, nullptr, d_part, nblk, d_stat, s);
-        exchange_stats(d_stat, true);
-        if (!cosine) {
-            kern::stats_mean(d_stat, n_global, D, d_meanden, s);
-            kern::column_sums(dgrads, N, D, d_meanden, d_part, nblk, d_stat2, s);
-            exchange_stats(d_stat2, false);
-            kern::stats_finish(d_stat, d_stat2, n_global, D, chunk_rows, d_meanden, d_scales, s);
-            d_mean = d_meanden;
-            d_den = d_meanden + D;
-        } else {
-            kern::stats_finish(d_stat, nullptr, n_global, D, chunk_rows, d_meanden, d_scales, s);
+    double *d_stat2 = d_stat + 2 * D;
+    // one message per statistics round: the sums and every rank's maxima (gathered through the sum, kern::stats_pack)
+    // (+ one word: this rank's row count in the first round -- integers below 2^53 add exactly in float64)
+    const size_t smsg_words = static_cast<size_t>(D) * (world + 1) + 1;
+    double *d_smsg = has_coll_ ? static_cast<double *>(d_maxbits_.ensure(sizeof(double) * smsg_words)) : nullptr;
+    auto exchange_stats = [&](double *st, bool with_row_count) {
+        if (!has_coll_) return;
+        kern::stats_pack(st, D, world, coll_.rank, d_smsg, s, with_row_count ? static_cast<double>(N) : 0.0);
+        exchange(Red::SumF64, d_smsg, smsg_words);
+        kern::stats_unpack(d_smsg, D, world, st, s);
+        if (with_row_count) {
+            // the host needs the global count from here on (chunk length -> fixed-point scale, target ranks of the selection, leaf scale)
+            double hv = 0.0;
+            hip_check(hipMemcpyAsync(&hv, d_smsg + smsg_words - 1, sizeof(hv), hipMemcpyDeviceToHost, s), "D2H n");
+            hip_check(hipStreamSynchronize(s), "sync");
+            n_global = static_cast<long long>(hv);
+            g.chunk_rows = chunk_rows_of(n_global);
         }
-        }
-        if (!stats_fused) kern::quantize_grads(dgrads, n_el, D, d_mean, d_den, d_scales, d_qg, s);
     };
-    if (!prep_candidate) run_stats();
-    phase_end("grad_stats");
+    kern::column_sums(dgrads, N, D, nullptr, d_part, nblk, d_stat, s);
+    exchange_stats(d_stat, true);
+    if (!cosine) {
+        kern::stats_mean(d_stat, n_global, D, d_meanden, s);
+        kern::column_sums(dgrads, N, D, d_meanden, d_part, nblk, d_stat2, s);
+        exchange_stats(d_stat2, false);
+        kern::stats_finish(d_stat, d_stat2, n_global, D, g.chunk_rows, d_meanden, d_scales, s);
+        d_mean = d_meanden;
+        d_den = d_meanden + D;
+    } else {
+        kern::stats_finish(d_stat, nullptr, n_global, D, g.chunk_rows, d_meanden, d_scales, s);
+    }
+    kern::quantize_grads(dgrads, n_el, D, d_mean, d_den, d_scales, d_qg, s);
+}
 
-    // ---- 2. split candidates ----------------------------------------------------------------------------------------
+// ---- 2. split candidates and 3. numeric class codes: the numeric preparation of a batch, written into `pb` -------------------------
+// (phases transpose / candidates / binning).  step() calls it with its own workspace and its gradient statistics (`fs`: the fused
+// preparation kernel computes them in its launch when the shape qualifies, and they are enqueued behind it when it does not);
+// prepare_dataset() with the data set's buffers and fs == nullptr (kern::small_prep with want_stats = false).
+NumericPrep Engine::prepare_numeric(PrepBuffers &pb, const float *dobs, int N, int F, int Fc, long long n_global, bool prep_candidate, FusedStats *fs) {
+    const gbrl_hip_metadata &md = model.meta;
+    hipStream_t s = stream_;
+    const int B = md.n_bins;
+    const bool uniform_gen = md.generator_type == GBRL_HIP_GEN_UNIFORM;
     phase_begin();
-    // thresholds and scales reach the host through ONE pinned block, copied behind the binning kernel: nothing waits for them
-    // until the first level's result block has arrived
     const size_t n_thr = static_cast<size_t>(F) * B;
-    char *pin_ts = static_cast<char *>(pin_thr_.ensure(sizeof(float) * std::max<size_t>(1, n_thr) + sizeof(kern::StepScales) + 64));
-    float *h_thr = reinterpret_cast<float *>(pin_ts);
-    kern::StepScales *h_scales_pin = reinterpret_cast<kern::StepScales *>(pin_ts + ((sizeof(float) * std::max<size_t>(1, n_thr) + 63) & ~static_cast<size_t>(63)));
-    float *d_thr = static_cast<float *>(d_thr_.ensure(sizeof(float) * std::max<size_t>(1, n_thr)));
-    uint32_t *d_thrkeys = static_cast<uint32_t *>(d_thrkeys_.ensure(sizeof(uint32_t) * std::max<size_t>(1, n_thr)));
+    float *d_thr = static_cast<float *>(pb.thr.ensure(sizeof(float) * std::max<size_t>(1, n_thr)));
+    uint32_t *d_thrkeys = static_cast<uint32_t *>(pb.thrkeys.ensure(sizeof(uint32_t) * std::max<size_t>(1, n_thr)));
     uint32_t *d_kt = nullptr;
     int pass1_chunks = 0;
     if (F > 0 && !prep_candidate) {
         // order-preserving keys, feature-major: every later pass over the observations (selection, binning) streams columns
-        d_kt = static_cast<uint32_t *>(d_kt_.ensure(sizeof(uint32_t) * static_cast<size_t>(N) * F));
+        d_kt = static_cast<uint32_t *>(pb.kt.ensure(sizeof(uint32_t) * static_cast<size_t>(N) * F));
         // quantile candidates by radix selection (the branch numeric_thresholds will take): the first digit is counted while the keys
         // pass through LDS (k_transpose_count), which saves one of the selection's passes over the keys
         const bool radix_path = fixed_thr_.empty() && md.generator_type != GBRL_HIP_GEN_UNIFORM && !force_bisection_ && !force_sample_select_ &&
@@ -312,30 +258,33 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
     const int n_slots_codes = F + Fc;
     const int n_code_groups = (n_slots_codes + kern::kCodeGroup - 1) / kern::kCodeGroup;
     const size_t code_elems = static_cast<size_t>(std::max(1, n_code_groups)) * N * kern::kCodeGroup;
-    uint16_t *d_codes = static_cast<uint16_t *>(d_codes_.ensure(sizeof(uint16_t) * code_elems));
+    uint16_t *d_codes = static_cast<uint16_t *>(pb.codes.ensure(sizeof(uint16_t) * code_elems));
     // Only the padding slots behind the last categorical column are written by nobody (the numeric writers fill whole groups of 16, padding
     // included, the categorical ones every (row, column)): no clearing when the slots fill their groups exactly (configs[4]: 192 + 64).
     if (Fc > 0 && (F + Fc) % kern::kCodeGroup != 0) hip_check(hipMemsetAsync(d_codes, 0, sizeof(uint16_t) * code_elems, s), "memset codes");
     bool codes_from_sort = false;
-    root_le_ = nullptr;
+    const uint32_t *root_le = nullptr;
     bool prep_done = false;
     const uint16_t *d_codes_fm = nullptr;   // feature-major copy of the numeric codes (kern::small_prep writes it for kern::small_grow)
     int prep_launches = 3;   // (diagnostic, reported as a pseudo-phase at profiling level 2: 1 = the fused preparation kernel ran)
     if (prep_candidate) {
         const int64_t *d_cum = uniform_gen ? nullptr : quantile_cum_device(quantile_target_ranks(n_global, B), n_global, B);
         bool stats_done = false;
-        uint16_t *d_fm = static_cast<uint16_t *>(d_codes_fm_.ensure(sizeof(uint16_t) * static_cast<size_t>(N) * F));
-        prep_done = kern::small_prep(dobs, N, F, B, uniform_gen, d_cum, d_thr, d_thrkeys, d_codes, d_fm, dgrads, D, !cosine, chunk_rows, d_stat, d_meanden, d_scales, d_qg,
-                                     !no_small_stats, &stats_done, s);
+        uint16_t *d_fm = static_cast<uint16_t *>(pb.codes_fm.ensure(sizeof(uint16_t) * static_cast<size_t>(N) * F));
+        prep_done = kern::small_prep(dobs, N, F, B, uniform_gen, d_cum, d_thr, d_thrkeys, d_codes, d_fm, fs ? fs->dgrads : nullptr, fs ? fs->D : 1, fs ? !fs->cosine : false,
+                                     fs ? fs->chunk_rows : 0, fs ? fs->d_stat : nullptr, fs ? fs->d_meanden : nullptr, fs ? fs->d_scales : nullptr, fs ? fs->d_qg : nullptr,
+                                     fs != nullptr && fs->fuse, &stats_done, s);
         if (prep_done) { codes_from_sort = true; last_quantile_fallback_ = false; prep_launches = 1; d_codes_fm = d_fm; }
-        if (stats_done) stats_fused = true;
-        else run_stats();
+        if (fs) {
+            if (stats_done) fs->done = true;
+            else run_grad_stats(*fs, N, n_global);
+        }
         if (!prep_done) {   // the shape did not qualify after all: the separate launches, keys first
-            d_kt = static_cast<uint32_t *>(d_kt_.ensure(sizeof(uint32_t) * static_cast<size_t>(N) * F));
+            d_kt = static_cast<uint32_t *>(pb.kt.ensure(sizeof(uint32_t) * static_cast<size_t>(N) * F));
             kern::transpose_keys(dobs, N, F, d_kt, s);
         }
     }
-    if (F > 0 && !prep_done) numeric_thresholds(dobs, N, F, B, n_global, d_kt, d_thr, d_thrkeys, pass1_chunks, d_codes, &codes_from_sort);
+    if (F > 0 && !prep_done) numeric_thresholds(dobs, N, F, B, n_global, d_kt, d_thr, d_thrkeys, pb.root_le, &root_le, pass1_chunks, d_codes, &codes_from_sort);
     phase_end("candidates");
     prof_marks_[1] = std::chrono::steady_clock::now();
     prep_launches_ = F > 0 ? prep_launches : 0;
@@ -343,62 +292,24 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
     phase_begin();
     if (F > 0 && !codes_from_sort) kern::bin_cols(d_kt, N, F, d_thrkeys, B, d_codes, s);
     phase_end("binning");
+    NumericPrep np;
+    np.d_thr = d_thr; np.d_thrkeys = d_thrkeys; np.d_codes = d_codes; np.d_kt = d_kt; np.d_codes_fm = d_codes_fm; np.root_le = root_le;
+    return np;
+}
 
-    // categorical candidates (A5): distinct cells found on the device, inserted into the reference's container in the
-    // reference's insertion order on the host => same candidate order (Q8).  Falls back to the host scan of every cell when
-    // the batch holds more distinct categories than candidates are kept (the reference then ranks them by mean gradient norm).
-    std::vector<CatCandidate> cat_cands;
-    std::vector<uint16_t> h_catcodes;
-    std::vector<int> cat_classes(Fc, 0);
-    bool cat_codes_on_device = false;
-    if (Fc > 0) {
-        if (fixed_cat_valid_) {   // fit(): candidates of the whole data set (fitter.cpp:152-164); the dictionary is still on the device
-            cat_cands = fixed_cat_cands_;
-            cat_classes = fixed_cat_classes_;
-            cat_codes_on_device = true;
-        } else {
-            cat_codes_on_device = (has_coll_ || !force_host_categorical_) &&
-                                  device_categorical_candidates(dcells, cat_dev ? nullptr : cat, N, Fc, B, cat_cands, cat_classes, /*launch_only=*/false, dgrads, D);
-        }
-        if (!cat_codes_on_device) {
-            std::vector<char> cat_host_buf;
-            const char *hcat = cat;
-            std::vector<float> grads_host_buf;
-            const float *hgrads = grads;
-            if (cat_dev) {
-                cat_host_buf.resize(static_cast<size_t>(N) * Fc * kCat);
-                hip_check(hipMemcpy(cat_host_buf.data(), cat, cat_host_buf.size(), hipMemcpyDeviceToHost), "D2H cat");
-                hcat = cat_host_buf.data();
-            }
-            if (grads_dev) {
-                grads_host_buf.resize(static_cast<size_t>(N) * D);
-                hip_check(hipMemcpy(grads_host_buf.data(), grads, grads_host_buf.size() * 4, hipMemcpyDeviceToHost), "D2H grads");
-                hgrads = grads_host_buf.data();
-            }
-            cat_cands.clear();
-            std::fill(cat_classes.begin(), cat_classes.end(), 0);
-            if (has_coll_) sharded_categorical_ranking(hcat, hgrads, N, Fc, D, B, cat_cands, h_catcodes, cat_classes);
-            else categorical_candidates(hcat, hgrads, N, Fc, D, B, cat_cands, h_catcodes, cat_classes);
-        }
-    }
+// ---- feature slots, candidate order, weights; then 4. growth (level-synchronous; Engine::grow_tree) and 5. leaf sums ------------------
+void Engine::grow_step_tree(const StepData &sd, std::vector<HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc, double &leaf_scale) {
+    const gbrl_hip_metadata &md = model.meta;
+    const int N = sd.N, F = sd.F, Fc = sd.Fc, D = md.output_dim, B = md.n_bins, MD = md.max_depth;
+    const bool cosine = md.split_score_func == GBRL_HIP_SCORE_COSINE;
+    const bool oblivious = model.oblivious();
+    const std::vector<CatCandidate> &cat_cands = *sd.cat_cands;
+    const std::vector<int> &cat_classes = *sd.cat_classes;
+    const size_t n_thr = static_cast<size_t>(F) * B;
+    float *h_thr = nullptr;
+    kern::StepScales *h_scales_pin = nullptr;
+    char *pin_ts = pinned_thr_block(pin_thr_, n_thr, h_thr, h_scales_pin);
 
-    prof_marks_[2] = std::chrono::steady_clock::now();
-    if (candidates_only_) {   // fit(): only the candidates of this (whole) data set are wanted
-        if (n_thr) hip_check(hipMemcpyAsync(h_thr, d_thr, sizeof(float) * n_thr, hipMemcpyDeviceToHost, s), "D2H thr");
-        hip_check(hipStreamSynchronize(s), "sync");
-        fixed_thr_.assign(h_thr, h_thr + n_thr);
-        if (Fc > 0) {
-            verify_pending_categories();
-            if (cat_clash_) { cat_clash_ = false; cat_items_.clear(); cat_tab_key_.clear(); cat_tab_id_.clear(); throw HipError("two different categories of one feature share a 64-bit hash: fit() refused"); }
-            if (!cat_codes_on_device)   // (the host scan: GBRL_HIP_HOST_CATEGORICAL=1, or the device scan declined -- more than 2^21 distinct cells)
-                throw Unsupported("fit(): the categorical candidates of the whole data set need the device scan (GBRL_HIP_HOST_CATEGORICAL=1, or more than 2^21 distinct categories)");
-            fixed_cat_cands_ = cat_cands;
-            fixed_cat_classes_ = cat_classes;
-            fixed_cat_valid_ = true;
-        }
-        phases_resolve();
-        return;
-    }
     // ---- feature slots, candidate order, weights ---------------------------------------------------------------------
     const int n_slots = F + Fc;
     int NB = F > 0 ? B + 1 : 1;
@@ -487,6 +398,171 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
         if (shared_tables) step_const_.valid = true;
     }
 
+    // thresholds and scales reach the pinned block through ONE launch (device-written host memory) instead of two copy-engine transfers:
+    // kern::publish_pair at the top of the level loop (grow_tree); the one-launch growth publishes the scales itself and hands the
+    // winners' thresholds over with its result blocks
+    static_assert(sizeof(kern::StepScales) % 4 == 0, "copied as 32-bit words");
+    void *pin_dev = nullptr;
+    hip_check(hipHostGetDevicePointer(&pin_dev, pin_ts, 0), "hipHostGetDevicePointer");
+
+    prof_marks_[3] = std::chrono::steady_clock::now();
+    // ---- 4. growth (level-synchronous; Engine::grow_tree) and 5. leaf sums --------------------------------------------------
+    GrowCtx gc{};
+    gc.N = N; gc.F = F; gc.Fc = Fc; gc.D = D; gc.B = B; gc.MD = MD; gc.NB = NB; gc.FG = FG; gc.Fp = Fp; gc.n_groups = n_groups;
+    gc.n_slots = n_slots; gc.n_cand = n_cand; gc.chunk_rows = sd.chunk_rows; gc.n_global = sd.n_global; gc.cosine = cosine; gc.oblivious = oblivious;
+    gc.slots = &slots; gc.cand_w = &cand_w; gc.cand_ref = &cand_ref; gc.ref_to_internal = &ref_to_internal; gc.cand_slot = &cand_slot;
+    gc.const_cacheable = const_cacheable; gc.cat_cands = &cat_cands;
+    gc.prefix_cacheable = prefix_cacheable; gc.n_num_cand = n_num_cand; gc.cand_cap = (F + Fc) * B;
+    gc.pub_thr_dev = static_cast<char *>(pin_dev); gc.pub_scales_dev = static_cast<char *>(pin_dev) + (reinterpret_cast<char *>(h_scales_pin) - pin_ts); gc.pub_thr_bytes = sizeof(float) * n_thr;
+    const NumericPrep &np = sd.prep;
+    gc.h_thr = h_thr; gc.h_scales = h_scales_pin; gc.d_thr = np.d_thr; gc.d_thrkeys = np.d_thrkeys; gc.root_le = (Fc == 0 && !has_coll_) ? np.root_le : nullptr; gc.d_kt = np.d_kt; gc.d_codes = np.d_codes; gc.d_codes_fm = np.d_codes_fm;
+    gc.d_qg = sd.stats->d_qg; gc.dgrads = sd.stats->dgrads; gc.d_meanden = cosine ? nullptr : sd.stats->d_meanden; gc.d_scales = sd.stats->d_scales;
+    grow_tree(gc, nodes, frontier, acc, leaf_scale);
+}
+
+// ======================================================================================================== step
+void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *grads, bool grads_dev, int n,
+                  int n_num, int n_cat) {
+    gbrl_hip_metadata &md = model.meta;
+    // GBRL::step, gbrl.cpp:946-958
+    if (md.iteration == 0) { md.n_num_features = n_num; md.n_cat_features = n_cat; }
+    if (n_num != md.n_num_features || n_cat != md.n_cat_features) throw InvalidArgument("Incompatible dataset");
+    if (n_num + n_cat != md.input_dim) throw InvalidArgument("Total number of features != correct input dim");
+    if (n <= 0 || grads == nullptr) throw InvalidArgument("Cannot call step without grads!");
+    if (n_num > 0 && obs == nullptr) throw InvalidArgument("Cannot call step without obs!");
+    if (n_cat > 0 && cat == nullptr) throw InvalidArgument("Cannot call step without cat_obs!");
+    if (md.max_depth > kern::kMaxPath) throw Unsupported("max_depth > 32 is not supported");
+    if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
+    ensure_device();
+    prof_step_entry_ = std::chrono::steady_clock::now();
+    ev_used_ = 0;
+    ev_names_.clear();
+    exch_bytes_ = 0;
+    exch_calls_ = 0;
+    read_step_hooks();
+    hipStream_t s = stream_;
+    const int N = n, F = n_num, Fc = n_cat, D = md.output_dim, B = md.n_bins;
+    const bool cosine = md.split_score_func == GBRL_HIP_SCORE_COSINE;
+
+    // global row count (rows are sharded over ranks): it travels with the first gradient-statistics message below (round 6: no exchange and no
+    // idle device for it); until then n_global holds this rank's count and nothing reads it
+    long long n_global = N;
+
+    // ---- inputs on the device -------------------------------------------------------------------------------------
+    phase_begin();
+    const float *dobs = obs;
+    if (F > 0 && !obs_dev) {
+        dobs = static_cast<float *>(d_obs_.ensure(sizeof(float) * N * F));
+        hip_check(hipMemcpyAsync(const_cast<float *>(dobs), obs, sizeof(float) * N * F, hipMemcpyHostToDevice, s), "H2D obs");
+    }
+    const float *dgrads = grads;
+    if (!grads_dev) {
+        dgrads = static_cast<float *>(d_grads_.ensure(sizeof(float) * N * D));
+        hip_check(hipMemcpyAsync(const_cast<float *>(dgrads), grads, sizeof(float) * N * D, hipMemcpyHostToDevice, s), "H2D grads");
+    }
+    // categorical cells on the device: the distinct categories of the batch are found there (device_categorical_candidates);
+    // the host-side scan of every cell is only the fallback
+    const char *dcells = cat;
+    if (Fc > 0 && !cat_dev) {
+        char *t = static_cast<char *>(d_pcells_.ensure(static_cast<size_t>(N) * Fc * kCat));
+        hip_check(hipMemcpyAsync(t, cat, static_cast<size_t>(N) * Fc * kCat, hipMemcpyHostToDevice, s), "H2D cat cells");
+        dcells = t;
+    }
+    phase_end("inputs");
+    prof_marks_[0] = std::chrono::steady_clock::now();
+    // the scan for the batch's distinct categorical cells goes first: its result is read by the HOST (device_categorical_candidates)
+    const bool cat_early = Fc > 0 && !fixed_cat_valid_ && (has_coll_ || !force_host_categorical_);
+    cat_launched_ = false;   // (a step that threw between the two stages must not be resumed)
+    if (cat_early) {
+        std::vector<CatCandidate> none;
+        std::vector<int> none_classes(Fc, 0);
+        (void)device_categorical_candidates(dcells, cat_dev ? nullptr : cat, N, Fc, B, none, none_classes, /*launch_only=*/true);
+    }
+
+    // ---- 1. gradient statistics and quantisation (A2): Engine::run_grad_stats -------------------------------------------------
+    phase_begin();
+    float *d_meanden = static_cast<float *>(d_meanden_.ensure(sizeof(float) * 2 * D));
+    double *d_stat = static_cast<double *>(d_stat_.ensure(sizeof(double) * 4 * D));
+    if (D > 512) throw Unsupported("output_dim > 512");
+    // LDS accumulators are int32 and one block adds at most `chunk_rows` rows into a cell: the power-of-two scale keeps
+    // chunk_rows * max|q| < 2^31 (exactness of the wrapped int32 sums, kernels.hip k_hist_build).  Leaf sums: int64 fixed point with
+    // n_global * max|g| * 2^lbits < 2^62.
+    kern::StepScales *d_scales = static_cast<kern::StepScales *>(d_scales_.ensure(sizeof(kern::StepScales)));
+    int32_t *d_qg = static_cast<int32_t *>(d_qg_.ensure(sizeof(int32_t) * static_cast<size_t>(N) * D));
+    const bool no_small_stats = [] { const char *e = hooks::raw(hooks::NO_SMALL_STATS); return e && e[0] == '1'; }();   /* read per call: the tests flip it */
+    // (row-sharded: the chunk length is set again once the global count is known)
+    FusedStats gs{dgrads, D, cosine, d_stat, d_meanden, d_scales, d_qg, chunk_rows_of(n_global), !no_small_stats};
+    // RL-sized steps on one GPU: the statistics ride in the fused preparation kernel's launch (prepare_numeric)
+    const bool prep_candidate = fused_prep_applies(N, F, n_global);
+    if (!prep_candidate) run_grad_stats(gs, N, n_global);
+    phase_end("grad_stats");
+
+    // ---- 2. split candidates and 3. numeric class codes: Engine::prepare_numeric, into this engine's workspace ----------------
+    // thresholds and scales reach the host through ONE pinned block, copied behind the binning kernel: nothing waits for them
+    // until the first level's result block has arrived
+    const size_t n_thr = static_cast<size_t>(F) * B;
+    float *h_thr = nullptr;
+    kern::StepScales *h_scales_pin = nullptr;
+    (void)pinned_thr_block(pin_thr_, n_thr, h_thr, h_scales_pin);
+    const NumericPrep np = prepare_numeric(prep_ws_, dobs, N, F, Fc, n_global, prep_candidate, &gs);
+    float *d_thr = np.d_thr;
+    uint16_t *d_codes = np.d_codes;
+
+    // categorical candidates (A5): distinct cells found on the device, inserted into the reference's container in the
+    // reference's insertion order on the host => same candidate order (Q8).  Falls back to the host scan of every cell when
+    // the batch holds more distinct categories than candidates are kept (the reference then ranks them by mean gradient norm).
+    std::vector<CatCandidate> cat_cands;
+    std::vector<uint16_t> h_catcodes;
+    std::vector<int> cat_classes(Fc, 0);
+    bool cat_codes_on_device = false;
+    if (Fc > 0) {
+        if (fixed_cat_valid_) {   // fit(): candidates of the whole data set (fitter.cpp:152-164); the dictionary is still on the device
+            cat_cands = fixed_cat_cands_;
+            cat_classes = fixed_cat_classes_;
+            cat_codes_on_device = true;
+        } else {
+            cat_codes_on_device = (has_coll_ || !force_host_categorical_) &&
+                                  device_categorical_candidates(dcells, cat_dev ? nullptr : cat, N, Fc, B, cat_cands, cat_classes, /*launch_only=*/false, dgrads, D);
+        }
+        if (!cat_codes_on_device) {
+            std::vector<char> cat_host_buf;
+            const char *hcat = cat;
+            std::vector<float> grads_host_buf;
+            const float *hgrads = grads;
+            if (cat_dev) {
+                cat_host_buf.resize(static_cast<size_t>(N) * Fc * kCat);
+                hip_check(hipMemcpy(cat_host_buf.data(), cat, cat_host_buf.size(), hipMemcpyDeviceToHost), "D2H cat");
+                hcat = cat_host_buf.data();
+            }
+            if (grads_dev) {
+                grads_host_buf.resize(static_cast<size_t>(N) * D);
+                hip_check(hipMemcpy(grads_host_buf.data(), grads, grads_host_buf.size() * 4, hipMemcpyDeviceToHost), "D2H grads");
+                hgrads = grads_host_buf.data();
+            }
+            cat_cands.clear();
+            std::fill(cat_classes.begin(), cat_classes.end(), 0);
+            if (has_coll_) sharded_categorical_ranking(hcat, hgrads, N, Fc, D, B, cat_cands, h_catcodes, cat_classes);
+            else categorical_candidates(hcat, hgrads, N, Fc, D, B, cat_cands, h_catcodes, cat_classes);
+        }
+    }
+
+    prof_marks_[2] = std::chrono::steady_clock::now();
+    if (candidates_only_) {   // fit(): only the candidates of this (whole) data set are wanted
+        if (n_thr) hip_check(hipMemcpyAsync(h_thr, d_thr, sizeof(float) * n_thr, hipMemcpyDeviceToHost, s), "D2H thr");
+        hip_check(hipStreamSynchronize(s), "sync");
+        fixed_thr_.assign(h_thr, h_thr + n_thr);
+        if (Fc > 0) {
+            verify_pending_categories();
+            if (cat_clash_) { cat_clash_ = false; cat_items_.clear(); cat_tab_key_.clear(); cat_tab_id_.clear(); throw HipError("two different categories of one feature share a 64-bit hash: fit() refused"); }
+            if (!cat_codes_on_device)   // (the host scan: GBRL_HIP_HOST_CATEGORICAL=1, or the device scan declined -- more than 2^21 distinct cells)
+                throw Unsupported("fit(): the categorical candidates of the whole data set need the device scan (GBRL_HIP_HOST_CATEGORICAL=1, or more than 2^21 distinct categories)");
+            fixed_cat_cands_ = cat_cands;
+            fixed_cat_classes_ = cat_classes;
+            fixed_cat_valid_ = true;
+        }
+        phases_resolve();
+        return;
+    }
     // ---- 3. class codes (group-major: [slot/16][row][slot%16], u16) ---------------------------------------------------
     if (Fc > 0) phase_begin();
     if (Fc > 0 && cat_codes_on_device) {
@@ -500,28 +576,15 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
         kern::scatter_cat_codes_grouped(d_cc2, N, Fc, F, d_codes, s);
     }
     if (Fc > 0) phase_end("cat_codes");
-    // thresholds and scales reach the pinned block through ONE launch (device-written host memory) instead of two copy-engine transfers:
-    // kern::publish_pair at the top of the level loop (grow_tree); the one-launch growth publishes the scales itself and hands the
-    // winners' thresholds over with its result blocks
-    static_assert(sizeof(kern::StepScales) % 4 == 0, "copied as 32-bit words");
-    void *pin_dev = nullptr;
-    hip_check(hipHostGetDevicePointer(&pin_dev, pin_ts, 0), "hipHostGetDevicePointer");
-
-    prof_marks_[3] = std::chrono::steady_clock::now();
-    // ---- 4. growth (level-synchronous; Engine::grow_tree) and 5. leaf sums --------------------------------------------------
-    GrowCtx gc{};
-    gc.N = N; gc.F = F; gc.Fc = Fc; gc.D = D; gc.B = B; gc.MD = MD; gc.NB = NB; gc.FG = FG; gc.Fp = Fp; gc.n_groups = n_groups;
-    gc.n_slots = n_slots; gc.n_cand = n_cand; gc.chunk_rows = chunk_rows; gc.n_global = n_global; gc.cosine = cosine; gc.oblivious = oblivious;
-    gc.slots = &slots; gc.cand_w = &cand_w; gc.cand_ref = &cand_ref; gc.ref_to_internal = &ref_to_internal; gc.cand_slot = &cand_slot;
-    gc.const_cacheable = const_cacheable; gc.cat_cands = &cat_cands;
-    gc.prefix_cacheable = prefix_cacheable; gc.n_num_cand = n_num_cand; gc.cand_cap = (F + Fc) * B;
-    gc.pub_thr_dev = static_cast<char *>(pin_dev); gc.pub_scales_dev = static_cast<char *>(pin_dev) + (reinterpret_cast<char *>(h_scales_pin) - pin_ts); gc.pub_thr_bytes = sizeof(float) * n_thr;
-    gc.h_thr = h_thr; gc.h_scales = h_scales_pin; gc.d_thr = d_thr; gc.d_thrkeys = d_thrkeys; gc.root_le = (Fc == 0 && !has_coll_) ? root_le_ : nullptr; gc.d_kt = d_kt; gc.d_codes = d_codes; gc.d_codes_fm = d_codes_fm; gc.d_qg = d_qg; gc.dgrads = dgrads; gc.d_meanden = cosine ? nullptr : d_meanden; gc.d_scales = d_scales;
+    // ---- feature slots, candidate order, weights, 4. growth and 5. leaf sums: Engine::grow_step_tree ----------------------------
+    StepData sd{};
+    sd.N = N; sd.F = F; sd.Fc = Fc; sd.n_global = n_global; sd.chunk_rows = gs.chunk_rows; sd.prep = np; sd.stats = &gs;
+    sd.cat_cands = &cat_cands; sd.cat_classes = &cat_classes;
     std::vector<HNode> nodes;
     std::vector<int> frontier;
     std::vector<int64_t> acc;
     double leaf_scale = 1.0;
-    grow_tree(gc, nodes, frontier, acc, leaf_scale);
+    grow_step_tree(sd, nodes, frontier, acc, leaf_scale);
     verify_pending_categories();
     if (cat_clash_) {
         // Two different cells of one feature share a 64-bit hash (2^-64 per pair of cells).  The tree just grown used the wrong
@@ -538,7 +601,6 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
         return;
     }
     append_tree(model, nodes, frontier, acc, leaf_scale, cat_cands);
-    (void)world;
     hip_check(hipGetLastError(), "step kernels");
     phases_resolve();
 }

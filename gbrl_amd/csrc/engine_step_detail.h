@@ -2,7 +2,9 @@
 //   engine_candidates.hip  split candidates: categorical cells on the device, sharded ranking, numeric thresholds (A3-A5)
 //   engine_grow.hip        Engine::grow_tree: the choice of the growth path, the one-launch growth of RL-sized steps, the host tree's bookkeeping
 //   engine_grow_levels.hip Engine::grow_levels: the level loops and the final leaves (A6-A10); engine_grow_detail.h has what these two share
-//   engine_step.hip        Engine::step / Engine::fit, the host scan of categorical cells, the tree joining the ensemble (A1, A2, A10-A11)
+//   engine_step.hip        Engine::step / Engine::fit, the host scan of categorical cells, the tree joining the ensemble (A1, A2, A10-A11), and
+//                          the stages step() shares with step_prepared(): run_grad_stats, prepare_numeric, grow_step_tree
+//   engine_prepared.hip    Engine::prepare_dataset / Engine::step_prepared: a batch binned once and stepped on many times
 #pragma once
 #include "engine.h"
 #include "hooks.h"
@@ -85,9 +87,45 @@ struct GrowCtx {
     kern::StepScales *d_scales;
 };
 
+// A histogram block accumulates one chunk of one node's rows.  Chunks are sized per level so that the whole level is ONE balanced round of
+// <= 32 chunks x (feature groups) blocks (k_hist_build keeps one block per CU); `chunk_rows` is the cap the fixed-point scale is derived from.
+// It depends on the GLOBAL row count only (clamped to [4096, 65536]), so the scale -- and with it every integer sum -- is the same for any
+// sharding of the same rows.
+inline int chunk_rows_of(long long n) { return static_cast<int>(std::min<long long>(65536, std::max<long long>(4096, 2 * ((n + 31) / 32)))); }
+
+// The gradient statistics of a step (A2) and where they land: Engine::run_grad_stats fills them, Engine::prepare_numeric hands them to the fused
+// preparation kernel when step() asks for it (`fuse`), and calls `run` behind that launch when the kernel did not cover them.
+struct FusedStats {
+    const float *dgrads;
+    int D;
+    bool cosine;
+    double *d_stat;             // [4 D]
+    float *d_meanden;           // [2 D]
+    kern::StepScales *d_scales;
+    int32_t *d_qg;              // [N][D]
+    int chunk_rows;
+    bool fuse;                  // !GBRL_HIP_NO_SMALL_STATS
+    bool done = false;          // the statistics have been enqueued
+};
+
+// Everything Engine::grow_step_tree needs about a batch: the numeric preparation (the engine's workspace, or a PreparedDataset's buffers), the
+// gradient statistics, and this step's categorical candidates (none for a prepared data set).
+struct StepData {
+    int N, F, Fc;
+    long long n_global;
+    int chunk_rows;
+    NumericPrep prep;
+    const FusedStats *stats;
+    const std::vector<CatCandidate> *cat_cands;
+    const std::vector<int> *cat_classes;
+};
+
 }  // namespace detail
 
 using detail::CatCandidate;
+using detail::chunk_rows_of;
+using detail::FusedStats;
+using detail::StepData;
 using detail::GrowCtx;
 using detail::HCond;
 using detail::HNode;

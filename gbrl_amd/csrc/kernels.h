@@ -189,6 +189,12 @@ int transpose_keys_count(const float *obs, int n, int F, uint32_t *kt, uint32_t 
 void bin_cols(const uint32_t *kt, int n, int F, const uint32_t *thr_keys, int B, uint16_t *codes, hipStream_t s);
 void scatter_cat_codes_grouped(const uint16_t *cat_codes, int n, int Fc, int F, uint16_t *codes, hipStream_t s);
 constexpr int kCodeGroup = 16;  // code layout: groups of 16 feature slots, [group][row][16]
+// row subsets of a prepared data set (gather_codes.hip): out[g][j][0..16) = codes[g][rows[j]][0..16) for g < n_groups, j < m -- whole 32-byte records,
+// 16 bytes per lane.  Every rows[j] must lie in [0, n): the caller checks (a host vector on the host, a device vector with rows_minmax).
+void gather_code_records(const uint16_t *codes /*[n_groups][n][16]*/, int n, int n_groups /*<= 65535*/, const int32_t *rows /*[m], device*/, int m,
+                         uint16_t *out /*[n_groups][m][16]*/, hipStream_t s);
+// mm[0] = min rows[j], mm[1] = min ~rows[j] (= ~max) of a device index vector, m >= 1
+void rows_minmax(const int32_t *rows, int m, int32_t *mm /*[2], device*/, hipStream_t s);
 
 // ---- split-score histograms (A6) ----
 size_t hist_lds_bytes(int NB, int D, int FG);

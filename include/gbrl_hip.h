@@ -298,6 +298,48 @@ int gbrl_hip_refit_leaves(gbrl_hip_model *m, const float *obs, int obs_on_device
                           const float *targets, int targets_on_device, int n_samples, int n_num_features, int n_cat_features,
                           int start_tree, int stop_tree, double decay_rate, double *loss_out);
 
+/* ---- prepared data sets (new: LightGBM's Dataset, XGBoost's QuantileDMatrix) -------------------------------------------- */
+/* A step turns the observation matrix into ordered keys, split thresholds and class codes before it looks at a gradient.  A prepared data set is
+ * that work done ONCE for a batch of numeric observations: several epochs over one rollout buffer, an actor and a critic on the same observations,
+ * or a supervised loop then step on it with new gradients each time.
+ *   gbrl_hip_dataset_create(m, obs, obs_on_device, n, n_num)  runs exactly what gbrl_hip_step runs for numeric columns, on the same code paths
+ *     (key transpose; uniform thresholds, the LDS sort, the radix multi-select, the sample-splitter path and its fallbacks; class codes; the
+ *     fused preparation of RL-sized batches), into buffers the data set owns, and waits for the stream: `obs` is not needed afterwards.  It
+ *     records n, F = n_num, the model's n_bins and generator_type and the device.  The model is not changed.  NULL on failure
+ *     (gbrl_hip_last_error, gbrl_hip_dataset_last_status).
+ *   gbrl_hip_step_prepared(m, ds, grads, grads_on_device, rows, rows_on_device, n_rows)  gradient statistics, growth, append -- no transpose, no
+ *     candidates, no binning.  Legal for ANY model on the data set's device whose n_bins and generator_type equal the data set's and whose
+ *     input_dim == F; it only reads the data set, so several models may share one.  It latches n_num_features = F, n_cat_features = 0 at
+ *     iteration 0 and honours the model's parity mode, as gbrl_hip_step does.
+ *     rows == NULL: n_rows must be n, grads is float32 [n, output_dim], and the model ends up BYTE FOR BYTE as gbrl_hip_step(obs, NULL, grads)
+ *     would leave it (ensemble arrays, metadata, the saved file).
+ *     rows != NULL: int32 [n_rows], host or device, duplicates allowed (bootstrap), every entry in [0, n); grads is [n_rows, output_dim] in the
+ *     order of rows.  The tree is grown on those rows with THE DATA SET'S thresholds -- LightGBM's Dataset.subset, and what gbrl_hip_fit does
+ *     with the candidates of the whole data set -- not with the quantiles of the subset.  The growth path is chosen by n_rows as a step on
+ *     n_rows rows would choose it.  rows = 0, 1, ..., n - 1 gives the bytes of rows == NULL.  An out-of-range index is found before anything
+ *     reads through it (a host vector on the host, a device vector by a min / max kernel, read back): GBRL_HIP_E_INVALID, no tree is grown.
+ *   gbrl_hip_dataset_thresholds  out[F * n_bins], host.   gbrl_hip_dataset_codes  out uint16 [G][n_rows][16], host, G = ceil(F / 16): the
+ *     group-major class codes (code of feature f and row r at [f / 16][r][f % 16] = #{k : threshold[f][k] < obs[r][f]}); rows == NULL: every
+ *     row (n_rows is ignored), else the gathered records of rows.  Diagnostics: they run on the null stream of the data set's device.
+ * Refused before the device is touched -- GBRL_HIP_E_UNSUPPORTED: a model with categorical columns (n_cat_features > 0: categorical candidates
+ * depend on the step's gradients), a model with collective hooks or an RCCL communicator (the thresholds would need the exchange), a data set
+ * from another device, and the limits of gbrl_hip_step (max_depth, n_bins, output_dim) with its messages; GBRL_HIP_E_INVALID: n_bins,
+ * generator_type or F differing from the model's, grads NULL or n_rows not n without rows, n_rows <= 0, a NULL or destroyed data set.
+ * After ANY failure the model is unchanged.  A data set may outlive the model that made it. */
+typedef struct gbrl_hip_dataset gbrl_hip_dataset;
+typedef struct {
+    int32_t n_rows, n_features, n_bins, generator_type, device, code_groups;
+    uint64_t nbytes;   /* device bytes held + the host copy of the thresholds */
+} gbrl_hip_dataset_desc;
+gbrl_hip_dataset *gbrl_hip_dataset_create(gbrl_hip_model *m, const float *obs, int obs_on_device, int n_samples, int n_num_features);
+int gbrl_hip_dataset_last_status(void);   /* status of the calling thread's last gbrl_hip_dataset_create */
+void gbrl_hip_dataset_destroy(gbrl_hip_dataset *ds);
+int gbrl_hip_dataset_info(const gbrl_hip_dataset *ds, gbrl_hip_dataset_desc *out);
+int gbrl_hip_dataset_thresholds(const gbrl_hip_dataset *ds, float *out /*[F*B]*/);
+int gbrl_hip_dataset_codes(const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, uint16_t *out /*[G][n_rows][16], host*/);
+int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *grads, int grads_on_device, const int32_t *rows,
+                           int rows_on_device, int n_rows);
+
 /* ---- row-sharded multi-GPU (new; the reference is single-GPU) ------------------------------------------ */
 /* One process per GPU, each holding a contiguous block of rows.  When hooks are installed, step() calls them at
  * its exchange points so that every rank grows the identical tree; predict() needs no exchange.  Buffers are
