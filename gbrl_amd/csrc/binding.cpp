@@ -17,6 +17,7 @@
 #include <memory>
 #include <sstream>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/gbrl_hip.h"
@@ -220,6 +221,72 @@ BatchShape infer_batch(const Input &o, const Input &c, int in_dim) {
     return {n, n_num, n_cat};
 }
 
+// ---- the three blocks every predict-family method is made of
+// obs and cat_obs of function `fn` (ids: cat_obs holds int32 dictionary ids, the _encoded methods) and the batch they announce.  A call with a
+// base or targets names it as `extra`: it is read between the observations and the shape inference, so that a missing one is reported first.
+struct Batch { Input o, c, extra; BatchShape s; };
+Batch read_batch(py::object &obs, py::object &cat, const std::string &fn, int in_dim, bool ids = false, py::object *extra = nullptr, const char *extra_name = nullptr) {
+    Batch b;
+    b.o = read_input(obs, "obs", true, fn, false);
+    b.c = read_input(cat, "cat_obs", true, fn, ids ? 2 : 1);
+    if (!b.o.ptr && !b.c.ptr) fail("Cannot call " + fn + " without observations!");
+    if (extra) {
+        b.extra = read_input(*extra, extra_name, false, fn, false);
+        if (!b.extra.ptr) fail("Cannot call " + fn + " without " + extra_name + "!");
+    }
+    b.s = infer_batch(b.o, b.c, in_dim);
+    return b;
+}
+
+// `a` (base or targets) is [n, D], or [n] when D == 1
+void check_rows_by_outputs(const Input &a, const char *name, int n, int D) {
+    const bool shape_ok = (a.shape.size() == 2 && a.shape[0] == static_cast<size_t>(n) && a.shape[1] == static_cast<size_t>(D)) ||
+                          (a.shape.size() == 1 && D == 1 && a.shape[0] == static_cast<size_t>(n));
+    if (shape_ok) return;
+    std::stringstream ss;
+    ss << "Expected " << name << " of shape (" << n << ", " << D << ")" << (D == 1 ? " or (" + std::to_string(n) + ",)" : std::string()) << ", but got (";
+    for (size_t i = 0; i < a.shape.size(); ++i) ss << (i ? ", " : "") << a.shape[i];
+    ss << ")";
+    fail(ss.str());
+}
+
+// The result of a call, `count` elements: on the MODEL's device for "cuda" delivery (one rank per GPU: not necessarily device 0; the capsule says
+// so), new[] on the host otherwise.  Freed when the call fails; release() hands it to a DLPack capsule or a NumPy array.
+template <typename T>
+class Result {
+   public:
+    Result(PyGBRL &self, size_t count) : dev_(self.device == 1) {
+        if (dev_) {
+            dev_id_ = gbrl_hip_device_ordinal(self.h);
+            if (dev_id_ < 0) fail(gbrl_hip_last_error());
+            p_ = static_cast<T *>(gbrl_hip_device_alloc_on(dev_id_, sizeof(T) * count));
+            if (!p_) fail(gbrl_hip_last_error());
+        } else {
+            p_ = new T[count];
+        }
+    }
+    Result(const Result &) = delete;
+    Result &operator=(const Result &) = delete;
+    ~Result() {   // still owned: the call has failed
+        if (!p_) return;
+        if (dev_) gbrl_hip_device_free(p_); else delete[] p_;
+    }
+    T *get() const { return p_; }
+    bool on_device() const { return dev_; }
+    py::object release(const std::vector<int64_t> &shape, bool dlpack_on_host = false) {
+        T *p = p_;
+        p_ = nullptr;
+        if (dev_ || dlpack_on_host) return make_dlpack(p, shape, dev_, dev_id_, /*int32=*/std::is_same<T, int32_t>::value);
+        py::capsule owner(p, [](void *q) { delete[] static_cast<T *>(q); });
+        return py::array_t<T>(std::vector<py::ssize_t>(shape.begin(), shape.end()), p, owner);
+    }
+
+   private:
+    T *p_ = nullptr;
+    bool dev_;
+    int dev_id_ = 0;
+};
+
 py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object start_obj, py::object stop_obj,
                         bool return_torch, const uint64_t *ids_token = nullptr /* non-null: `cat` holds int32 dictionary ids (predict_encoded) */) {
     const gbrl_hip_metadata md = self.meta();
@@ -236,44 +303,25 @@ py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::obje
         ss << "stop_tree_idx is out of bounds! Got " << stop << ", but valid range is [0, " << md.n_trees << "]";
         fail(ss.str());
     }
-    Input o = read_input(obs, "obs", true, "predict", false);
-    Input c = read_input(cat, "cat_obs", true, "predict", ids_token ? 2 : 1);
-    if (!o.ptr && !c.ptr) fail("Cannot call predict without observations!");
-    const BatchShape bs = infer_batch(o, c, md.input_dim);
-    const int n = bs.n, n_num = bs.n_num, n_cat = bs.n_cat;
+    const Batch b = read_batch(obs, cat, "predict", md.input_dim, ids_token != nullptr);
+    const Input &o = b.o, &c = b.c;
+    const int n = b.s.n, n_num = b.s.n_num, n_cat = b.s.n_cat;
     const int D = md.output_dim;
     std::vector<int64_t> shape;
     if (D == 1) shape = {n}; else shape = {n, D};  // binding.cpp:281-286
-    const bool dev_out = self.device == 1;
-    float *out = nullptr;
-    int dev_id = 0;
-    if (dev_out) {
-        // the buffer lives on the MODEL's device (one rank per GPU: not necessarily device 0) and the capsule says so
-        dev_id = gbrl_hip_device_ordinal(self.h);
-        if (dev_id < 0) fail(gbrl_hip_last_error());
-        out = static_cast<float *>(gbrl_hip_device_alloc_on(dev_id, sizeof(float) * static_cast<size_t>(n) * D));
-        if (!out) fail(gbrl_hip_last_error());
-    } else {
-        out = new float[static_cast<size_t>(n) * D];
-    }
+    Result<float> out(self, static_cast<size_t>(n) * D);
     int rc;
     {
         py::gil_scoped_release release;  // binding.cpp:934
         if (ids_token)
             rc = gbrl_hip_predict_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device, *ids_token,
-                                          n, n_num, n_cat, start, stop, out, dev_out);
+                                          n, n_num, n_cat, start, stop, out.get(), out.on_device());
         else
-        rc = gbrl_hip_predict(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr),
-                              c.on_device, n, n_num, n_cat, start, stop, out, dev_out);
+            rc = gbrl_hip_predict(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr),
+                                  c.on_device, n, n_num, n_cat, start, stop, out.get(), out.on_device());
     }
-    if (rc != GBRL_HIP_OK) {
-        if (dev_out) gbrl_hip_device_free(out); else delete[] out;
-        fail(gbrl_hip_last_error());
-    }
-    if (dev_out || return_torch) return make_dlpack(out, shape, dev_out, dev_id);
-    py::capsule owner(out, [](void *p) { delete[] static_cast<float *>(p); });
-    std::vector<py::ssize_t> shp(shape.begin(), shape.end());
-    return py::array_t<float>(shp, out, owner);
+    check(rc);
+    return out.release(shape, return_torch);
 }
 
 // Extension: predict_continue(obs, categorical_obs, base, start, stop) / predict_continue_encoded(obs, ids, token, base, start, stop): `base`, the
@@ -285,22 +333,10 @@ py::object predict_continue_impl(PyGBRL &self, py::object &obs, py::object &cat,
     const gbrl_hip_metadata md = self.meta();
     const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
     const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
-    Input o = read_input(obs, "obs", true, "predict_continue", false);
-    Input c = read_input(cat, "cat_obs", true, "predict_continue", ids_token ? 2 : 1);
-    if (!o.ptr && !c.ptr) fail("Cannot call predict_continue without observations!");
-    Input b = read_input(base, "base", false, "predict_continue", false);
-    if (!b.ptr) fail("Cannot call predict_continue without base!");
-    const BatchShape bs = infer_batch(o, c, md.input_dim);
-    const int n = bs.n, n_num = bs.n_num, n_cat = bs.n_cat, D = md.output_dim;
-    const bool shape_ok = (b.shape.size() == 2 && b.shape[0] == static_cast<size_t>(n) && b.shape[1] == static_cast<size_t>(D)) ||
-                          (b.shape.size() == 1 && D == 1 && b.shape[0] == static_cast<size_t>(n));
-    if (!shape_ok) {
-        std::stringstream ss;
-        ss << "Expected base of shape (" << n << ", " << D << ")" << (D == 1 ? " or (" + std::to_string(n) + ",)" : std::string()) << ", but got (";
-        for (size_t i = 0; i < b.shape.size(); ++i) ss << (i ? ", " : "") << b.shape[i];
-        ss << ")";
-        fail(ss.str());
-    }
+    const Batch batch = read_batch(obs, cat, "predict_continue", md.input_dim, ids_token != nullptr, &base, "base");
+    const Input &o = batch.o, &c = batch.c, &b = batch.extra;
+    const int n = batch.s.n, n_num = batch.s.n_num, n_cat = batch.s.n_cat, D = md.output_dim;
+    check_rows_by_outputs(b, "base", n, D);
     const bool in_place = py::isinstance<py::tuple>(base);
     float *out = in_place ? static_cast<float *>(const_cast<void *>(b.ptr)) : new float[static_cast<size_t>(n) * D];
     const int out_dev = in_place && b.on_device;
@@ -350,60 +386,30 @@ std::vector<int32_t> read_stops(py::object &stops_obj, int n_trees) {
 
 py::object predict_staged_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &stops_obj) {
     const gbrl_hip_metadata md = self.meta();
-    Input o = read_input(obs, "obs", true, "predict_staged", false);
-    Input c = read_input(cat, "cat_obs", true, "predict_staged", 1);
-    if (!o.ptr && !c.ptr) fail("Cannot call predict_staged without observations!");
-    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const Batch b = read_batch(obs, cat, "predict_staged", md.input_dim);
+    const Input &o = b.o, &c = b.c;
     const std::vector<int32_t> stops = read_stops(stops_obj, md.n_trees);
-    const int n = bs.n, D = md.output_dim, S = static_cast<int>(stops.size());
+    const int n = b.s.n, D = md.output_dim, S = static_cast<int>(stops.size());
     std::vector<int64_t> shape;
     if (D == 1) shape = {S, n}; else shape = {S, n, D};
-    const size_t total = static_cast<size_t>(S) * n * D;
-    const bool dev_out = self.device == 1;
-    float *out = nullptr;
-    int dev_id = 0;
-    if (dev_out) {
-        dev_id = gbrl_hip_device_ordinal(self.h);
-        if (dev_id < 0) fail(gbrl_hip_last_error());
-        out = static_cast<float *>(gbrl_hip_device_alloc_on(dev_id, sizeof(float) * total));
-        if (!out) fail(gbrl_hip_last_error());
-    } else {
-        out = new float[total];
-    }
+    Result<float> out(self, static_cast<size_t>(S) * n * D);
     int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_predict_staged(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, bs.n_num,
-                                     bs.n_cat, stops.data(), S, out, dev_out);
+        rc = gbrl_hip_predict_staged(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, b.s.n_num,
+                                     b.s.n_cat, stops.data(), S, out.get(), out.on_device());
     }
-    if (rc != GBRL_HIP_OK) {
-        if (dev_out) gbrl_hip_device_free(out); else delete[] out;
-        fail(gbrl_hip_last_error());
-    }
-    if (dev_out) return make_dlpack(out, shape, true, dev_id);
-    py::capsule owner(out, [](void *p) { delete[] static_cast<float *>(p); });
-    std::vector<py::ssize_t> shp(shape.begin(), shape.end());
-    return py::array_t<float>(shp, out, owner);
+    check(rc);
+    return out.release(shape);
 }
 
 py::object staged_loss_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, py::object &stops_obj) {
     const gbrl_hip_metadata md = self.meta();
-    Input o = read_input(obs, "obs", true, "staged_loss", false);
-    Input c = read_input(cat, "cat_obs", true, "staged_loss", 1);
-    if (!o.ptr && !c.ptr) fail("Cannot call staged_loss without observations!");
-    Input y = read_input(targets, "targets", false, "staged_loss", false);
-    if (!y.ptr) fail("Cannot call staged_loss without targets!");
-    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const Batch b = read_batch(obs, cat, "staged_loss", md.input_dim, false, &targets, "targets");
+    const Input &o = b.o, &c = b.c, &y = b.extra;
+    const BatchShape &bs = b.s;
     const int n = bs.n, D = md.output_dim;
-    const bool shape_ok = (y.shape.size() == 2 && y.shape[0] == static_cast<size_t>(n) && y.shape[1] == static_cast<size_t>(D)) ||
-                          (y.shape.size() == 1 && D == 1 && y.shape[0] == static_cast<size_t>(n));
-    if (!shape_ok) {
-        std::stringstream ss;
-        ss << "Expected targets of shape (" << n << ", " << D << ")" << (D == 1 ? " or (" + std::to_string(n) + ",)" : std::string()) << ", but got (";
-        for (size_t i = 0; i < y.shape.size(); ++i) ss << (i ? ", " : "") << y.shape[i];
-        ss << ")";
-        fail(ss.str());
-    }
+    check_rows_by_outputs(y, "targets", n, D);
     const std::vector<int32_t> stops = read_stops(stops_obj, md.n_trees);
     py::array_t<double> loss(static_cast<py::ssize_t>(stops.size()));
     double *lp = loss.mutable_data();
@@ -424,22 +430,11 @@ double refit_leaves_impl(PyGBRL &self, py::object &obs, py::object &cat, py::obj
     const gbrl_hip_metadata md = self.meta();
     const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
     const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
-    Input o = read_input(obs, "obs", true, "refit_leaves", false);
-    Input c = read_input(cat, "cat_obs", true, "refit_leaves", 1);
-    if (!o.ptr && !c.ptr) fail("Cannot call refit_leaves without observations!");
-    Input y = read_input(targets, "targets", true, "refit_leaves", false);
-    if (!y.ptr) fail("Cannot call refit_leaves without targets!");
-    const BatchShape bs = infer_batch(o, c, md.input_dim);
+    const Batch b = read_batch(obs, cat, "refit_leaves", md.input_dim, false, &targets, "targets");
+    const Input &o = b.o, &c = b.c, &y = b.extra;
+    const BatchShape &bs = b.s;
     const int n = bs.n, D = md.output_dim;
-    const bool shape_ok = (y.shape.size() == 2 && y.shape[0] == static_cast<size_t>(n) && y.shape[1] == static_cast<size_t>(D)) ||
-                          (y.shape.size() == 1 && D == 1 && y.shape[0] == static_cast<size_t>(n));
-    if (!shape_ok) {
-        std::stringstream ss;
-        ss << "Expected targets of shape (" << n << ", " << D << ")" << (D == 1 ? " or (" + std::to_string(n) + ",)" : std::string()) << ", but got (";
-        for (size_t i = 0; i < y.shape.size(); ++i) ss << (i ? ", " : "") << y.shape[i];
-        ss << ")";
-        fail(ss.str());
-    }
+    check_rows_by_outputs(y, "targets", n, D);
     double loss = 0.0;
     int rc;
     {
@@ -460,11 +455,9 @@ py::object leaves_impl(PyGBRL &self, py::object &obs, py::object &cat, py::objec
     const char *fn = counts ? "leaf_counts" : "predict_leaves";
     const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
     const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
-    Input o = read_input(obs, "obs", true, fn, false);
-    Input c = read_input(cat, "cat_obs", true, fn, ids_token ? 2 : 1);
-    if (!o.ptr && !c.ptr) fail(std::string("Cannot call ") + fn + " without observations!");
-    const BatchShape bs = infer_batch(o, c, md.input_dim);
-    const int n = bs.n, n_num = bs.n_num, n_cat = bs.n_cat;
+    const Batch b = read_batch(obs, cat, fn, md.input_dim, ids_token != nullptr);
+    const Input &o = b.o, &c = b.c;
+    const int n = b.s.n, n_num = b.s.n_num, n_cat = b.s.n_cat;
     // the engine checks the same (c_api callers); here too because the result is allocated before the C call
     if (md.n_trees == 0) fail(std::string(fn) + ": the model has no trees");
     const int resolved = stop == 0 ? md.n_trees : stop;
@@ -491,36 +484,19 @@ py::object leaves_impl(PyGBRL &self, py::object &obs, py::object &cat, py::objec
     }
     const int T = resolved - start;
     if (static_cast<int64_t>(n) * T >= (int64_t(1) << 31)) fail("predict_leaves: n_samples x trees >= 2^31 indices: slice the tree range");
-    const size_t total = static_cast<size_t>(n) * T;
-    const bool dev_out = self.device == 1;
-    int32_t *out = nullptr;
-    int dev_id = 0;
-    if (dev_out) {
-        dev_id = gbrl_hip_device_ordinal(self.h);
-        if (dev_id < 0) fail(gbrl_hip_last_error());
-        out = static_cast<int32_t *>(gbrl_hip_device_alloc_on(dev_id, sizeof(int32_t) * total));
-        if (!out) fail(gbrl_hip_last_error());
-    } else {
-        out = new int32_t[total];
-    }
+    Result<int32_t> out(self, static_cast<size_t>(n) * T);
     int rc;
     {
         py::gil_scoped_release release;
         if (ids_token)
             rc = gbrl_hip_predict_leaves_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device,
-                                                 *ids_token, n, n_num, n_cat, start, stop, out, dev_out);
+                                                 *ids_token, n, n_num, n_cat, start, stop, out.get(), out.on_device());
         else
             rc = gbrl_hip_predict_leaves(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, n_num,
-                                         n_cat, start, stop, out, dev_out);
+                                         n_cat, start, stop, out.get(), out.on_device());
     }
-    if (rc != GBRL_HIP_OK) {
-        if (dev_out) gbrl_hip_device_free(out); else delete[] out;
-        fail(gbrl_hip_last_error());
-    }
-    const std::vector<int64_t> shape = {n, T};
-    if (dev_out) return make_dlpack(out, shape, true, dev_id, /*int32=*/true);
-    py::capsule owner(out, [](void *p) { delete[] static_cast<int32_t *>(p); });
-    return py::array_t<int32_t>(std::vector<py::ssize_t>{n, T}, out, owner);
+    check(rc);
+    return out.release({n, T});
 }
 
 // Extension: (ids, token) = encode_categorical(categorical_obs): int32 dictionary ids [n, n_cat] of a batch of cells -- a DLPack capsule on the
@@ -529,31 +505,15 @@ py::tuple encode_categorical_impl(PyGBRL &self, py::object &cat) {
     Input c = read_input(cat, "cat_obs", false, "encode_categorical", 1);
     if (!c.ptr) fail("Cannot call encode_categorical without cat_obs!");
     const int n = static_cast<int>(c.shape[0]), n_cat = c.shape.size() > 1 ? static_cast<int>(c.shape[1]) : 1;
-    const bool dev_out = self.device == 1;
-    int32_t *ids = nullptr;
-    int dev_id = 0;
-    if (dev_out) {
-        dev_id = gbrl_hip_device_ordinal(self.h);
-        if (dev_id < 0) fail(gbrl_hip_last_error());
-        ids = static_cast<int32_t *>(gbrl_hip_device_alloc_on(dev_id, sizeof(int32_t) * static_cast<size_t>(n) * n_cat));
-        if (!ids) fail(gbrl_hip_last_error());
-    } else {
-        ids = new int32_t[static_cast<size_t>(n) * n_cat];
-    }
+    Result<int32_t> ids(self, static_cast<size_t>(n) * n_cat);
     uint64_t token = 0;
     int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_encode_categorical(self.h, static_cast<const char *>(c.ptr), c.on_device, n, n_cat, ids, dev_out, &token);
+        rc = gbrl_hip_encode_categorical(self.h, static_cast<const char *>(c.ptr), c.on_device, n, n_cat, ids.get(), ids.on_device(), &token);
     }
-    if (rc != GBRL_HIP_OK) {
-        if (dev_out) gbrl_hip_device_free(ids); else delete[] ids;
-        fail(gbrl_hip_last_error());
-    }
-    const std::vector<int64_t> shape = {n, n_cat};
-    if (dev_out) return py::make_tuple(make_dlpack(ids, shape, true, dev_id, /*int32=*/true), token);
-    py::capsule owner(ids, [](void *p) { delete[] static_cast<int32_t *>(p); });
-    return py::make_tuple(py::array_t<int32_t>(std::vector<py::ssize_t>{n, n_cat}, ids, owner), token);
+    check(rc);
+    return py::make_tuple(ids.release({n, n_cat}), token);
 }
 
 void step_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &grads) {

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <array>
+#include <initializer_list>
 #include <chrono>
 #include <cstring>
 #include <string>
@@ -227,18 +228,31 @@ class Engine {
     void invalidate_mirror();   // values of existing trees have changed (refit_leaves): the append-only mirror is uploaded again, the dictionary stays
     void sync_cat_dict();   // the host half of it: cat_dict_ / cat_ids_host_ follow the model (no device needed)
     int32_t *encode_categorical_batch(const char *cat, bool cat_dev, int n, int n_cat);
-    struct ContinueBase { const float *base; bool on_device; };   // predict_continue: the held prediction (nullptr in predict_core: an ordinary predict)
-    // predict_staged / staged_loss: the checkpoints (host) and, in loss mode, the targets and where the losses go (nullptr in predict_core: no stages)
-    struct StagedPlan { const int32_t *stops; int n_stops; bool loss; const float *targets; bool targets_dev; double *loss_out; };
-    // predict_leaves / leaf_counts: where the int32 indices or the int64 counts go (nullptr in predict_core: a call that sums values)
-    struct LeavesPlan { bool counts; int32_t *out; bool out_dev; int64_t *counts_out; };
-    // refit_leaves: the range is checked by the caller; predict_core stages the inputs and the mirror, runs the refit and books it
-    struct RefitPlan { const float *targets; bool targets_dev; double decay; double *loss_out; };
-    void refit_run(const kern::PredictModel &pm, const float *dobs, const int32_t *dcat, const float *dtargets, int n, int n_num, int n_cat, int start_tree,
-                   int stop, const RefitPlan &plan);   // engine_refit.hip: called by predict_core with the inputs staged and the mirror in step
-    void predict_core(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token,
-                      int n, int n_num, int n_cat, int start_tree, int stop_tree, float *out, bool out_dev, const ContinueBase *cont = nullptr,
-                      const StagedPlan *staged = nullptr, const LeavesPlan *leaves = nullptr, const RefitPlan *refit = nullptr);
+    // ---- the stages of a predict-family call, in the order every public call runs them (the head of engine_predict.hip has the list) ----
+    // the observations as the caller handed them over: cells, or pre-encoded ids with their dictionary token (cat_ids != nullptr: cat is ignored)
+    struct PredictBatch { const float *obs; bool obs_dev; const char *cat; bool cat_dev; const int32_t *cat_ids; bool ids_dev; const uint64_t *token; int n, n_num, n_cat; };
+    struct StagedBatch { const float *obs; const int32_t *cat; };   // the same batch on the device: observations and dictionary ids
+    struct ReadBack { void *host; const void *dev; size_t bytes; const char *what; };   // a result bound for the host (host == nullptr: it stays on the device)
+    // GBRL::predict's data set checks, first-use bookkeeping of the feature counts included.  has_result: the call's result pointer is there;
+    // width_limit: the call reads leaf values, which the kernels hold for up to 128 outputs
+    void check_batch(const PredictBatch &b, bool has_result, bool width_limit);
+    void check_dict_token(const PredictBatch &b);   // pre-encoded ids are valid only for the dictionary they were made from (host state: no device needed)
+    void check_stops(const int32_t *stops, int n_stops) const;
+    int check_leaves_range(int start_tree, int stop_tree) const;   // predict_leaves / leaf_counts: the resolved stop of a range the ensemble holds
+    int check_refit(int start_tree, int stop_tree, const float *targets, double decay_rate, const double *loss_out) const;   // likewise (engine_refit.hip)
+    StagedBatch stage_batch(const PredictBatch &b);   // device, event pool, mirror; opens the `inputs` phase: observations up, ids checked and uploaded or cells encoded
+    const float *stage_targets(const float *targets, bool on_device, int n);   // [n][D] targets on the device
+    kern::StagedStops stage_stops(const int32_t *stops, int n_stops);
+    template <typename T>
+    T *upload(DevBuf &buf, const T *host, size_t count, const char *what) {   // a host array into a grow-only device buffer, on the stream
+        T *d = static_cast<T *>(buf.ensure(sizeof(T) * count));
+        hip_check(hipMemcpyAsync(d, host, sizeof(T) * count, hipMemcpyHostToDevice, stream_), what);
+        return d;
+    }
+    kern::PredictModel mirror_view();   // what the kernels read of the model and its mirror; predict() adds the routes it alone offers
+    void finish(const char *launch, const char *phase, std::initializer_list<ReadBack> results);   // launch error, end of the key phase, read-backs, ONE wait, phase times
+    void run_predict(const PredictBatch &b, int start_tree, int stop_tree, float *out, bool out_dev);   // predict / predict_encoded
+    void run_continue(const PredictBatch &b, int start_tree, int stop_tree, const float *base, bool base_dev, float *out, bool out_dev);
     uint64_t cat_dict_token();
     void grow_tree(const detail::GrowCtx &c, std::vector<detail::HNode> &nodes, std::vector<int> &frontier, std::vector<int64_t> &acc,
                    double &leaf_scale);

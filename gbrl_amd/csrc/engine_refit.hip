@@ -1,5 +1,5 @@
-// engine_refit.hip -- GBRL::refit_leaves (see engine.h): the call's own argument checks, and the run that predict_core hands over once it has
-// staged the inputs and synchronised the device mirror (engine_predict.hip keeps input handling, encoding and the mirror for every call).
+// engine_refit.hip -- GBRL::refit_leaves (see engine.h).  The call goes through the stages of engine_predict.hip like every predict-family call; what
+// is its own is the order of its checks, its kernels, its three read-backs and the booking of the new values.
 #include "engine.h"
 #include "hooks.h"
 
@@ -10,15 +10,12 @@
 
 namespace gbrl {
 
-// Extension: the leaf values of [start_tree, stop_tree) fitted again on this batch (kern::refit_leaves).  The checks that are the call's own come
-// first -- a model without trees must not be touched by predict_core's first-use bookkeeping; input handling, encoding and the mirror are predict_core's,
-// which hands the staged inputs to refit_run below.
-void Engine::refit_leaves(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num, int n_cat,
-                          int start_tree, int stop_tree, double decay_rate, double *loss_out) {
+// The checks that are refit_leaves' own; returns the resolved stop (stop_tree == 0: n_trees).
+int Engine::check_refit(int start_tree, int stop_tree, const float *targets, double decay_rate, const double *loss_out) const {
     const gbrl_hip_metadata &md = model.meta;
     if (md.n_trees == 0) throw InvalidArgument("refit_leaves: the model has no trees");
-    const int resolved = stop_tree == 0 ? md.n_trees : stop_tree;
-    if (start_tree < 0 || stop_tree < 0 || resolved > md.n_trees || start_tree >= resolved)
+    const int stop = stop_tree == 0 ? md.n_trees : stop_tree;
+    if (start_tree < 0 || stop_tree < 0 || stop > md.n_trees || start_tree >= stop)
         throw InvalidArgument("refit_leaves: invalid tree range [" + std::to_string(start_tree) + ", " + std::to_string(stop_tree) + ") for " + std::to_string(md.n_trees) + " trees");
     if (targets == nullptr) throw InvalidArgument("Cannot call refit_leaves without targets!");
     if (loss_out == nullptr) throw InvalidArgument("refit_leaves: no place for the loss");
@@ -30,20 +27,26 @@ void Engine::refit_leaves(const float *obs, bool obs_dev, const char *cat, bool 
     // refused when one lies in [start - 1, stop): inside the range, or right in front of it, where the prefix prediction would apply an OLD value
     // of tree `start`.  Further in front the walk touches unchanged trees only.  (An oblivious stump is routed to and simply keeps its value.)
     if (!model.oblivious())
-        for (int t = std::max(0, start_tree - 1); t < resolved; ++t) {
+        for (int t = std::max(0, start_tree - 1); t < stop; ++t) {
             const int l0 = model.tree_indices[t], l1 = t + 1 < md.n_trees ? model.tree_indices[t + 1] : md.n_leaves;
             for (int l = l0; l < l1; ++l)
                 if (model.depths[l] == 0)
                     throw Unsupported("refit_leaves: greedy tree " + std::to_string(t) + " has a leaf of depth 0, which no row reaches: the prediction walks on into the next tree there, whose new values are not known yet");
         }
-    const RefitPlan plan{targets, targets_dev, decay_rate, loss_out};
-    predict_core(obs, obs_dev, cat, cat_dev, nullptr, false, nullptr, n, n_num, n_cat, start_tree, resolved, nullptr, false, nullptr, nullptr, nullptr, &plan);
+    return stop;
 }
 
-// The device half: pm is the mirror's view, dobs / dcat / dtargets are on the device, [start_tree, stop) is resolved and checked.
-void Engine::refit_run(const kern::PredictModel &pm, const float *dobs, const int32_t *dcat, const float *dtargets, int n, int n_num, int n_cat,
-                       int start_tree, int stop, const RefitPlan &plan) {
+// Extension: the leaf values of [start_tree, stop_tree) fitted again on this batch (kern::refit_leaves).  The checks that are the call's own come
+// first -- a model without trees must not be touched by check_batch's first-use bookkeeping.
+void Engine::refit_leaves(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num, int n_cat,
+                          int start_tree, int stop_tree, double decay_rate, double *loss_out) {
     const gbrl_hip_metadata &md = model.meta;
+    const int stop = check_refit(start_tree, stop_tree, targets, decay_rate, loss_out);
+    const PredictBatch b{obs, obs_dev, cat, cat_dev, nullptr, false, nullptr, n, n_num, n_cat};
+    check_batch(b, /*has_result=*/true, /*width_limit=*/true);
+    const StagedBatch d = stage_batch(b);
+    const float *dtargets = stage_targets(targets, targets_dev, n);
+    phase_end("inputs"); phase_begin(/*key=*/true);
     hipStream_t s = stream_;
     const int D = md.output_dim;
     // the whole range is ONE enqueue: nothing is read back between the trees, the host waits once, and the model -- host copy and mirror -- is
@@ -61,19 +64,15 @@ void Engine::refit_run(const kern::PredictModel &pm, const float *dobs, const in
     double *dsum = static_cast<double *>(d_staged_sums_.ensure(sizeof(double)));
     hip_check(hipMemsetAsync(dacc, 0, acc_bytes, s), "zero leaf sums");
     hip_check(hipMemsetAsync(dgmax, 0, sizeof(uint32_t) * (T + 1), s), "zero gradient maxima");
-    const int streamed = kern::refit_leaves(pm, model.tree_indices.data(), dobs, n_num, dcat, n_cat, n, start_tree, stop, plan.decay, dtargets, dP, dleaf, dacc, dvals, dgmax,
+    const int streamed = kern::refit_leaves(mirror_view(), model.tree_indices.data(), d.obs, n_num, d.cat, n_cat, n, start_tree, stop, decay_rate, dtargets, dP, dleaf, dacc, dvals, dgmax,
                                             hooks::on(hooks::REFIT_GENERIC), s);
     kern::staged_loss_of_predictions(dP, dtargets, n, D, dpart, dsum, s);
-    hip_check(hipGetLastError(), "refit_leaves launch");
-    phase_end("refit", /*key=*/true);
     std::vector<float> hvals(NL * D);
     std::vector<uint32_t> hgmax(T + 1);
     double sum = 0.0;
-    hip_check(hipMemcpyAsync(hvals.data(), dvals, sizeof(float) * NL * D, hipMemcpyDeviceToHost, s), "D2H refitted values");
-    hip_check(hipMemcpyAsync(hgmax.data(), dgmax, sizeof(uint32_t) * (T + 1), hipMemcpyDeviceToHost, s), "D2H gradient maxima");
-    hip_check(hipMemcpyAsync(&sum, dsum, sizeof(double), hipMemcpyDeviceToHost, s), "D2H loss sum");
-    hip_check(hipStreamSynchronize(s), "sync");
-    phases_resolve();
+    finish("refit_leaves launch", "refit", {{hvals.data(), dvals, sizeof(float) * NL * D, "D2H refitted values"},
+                                            {hgmax.data(), dgmax, sizeof(uint32_t) * (T + 1), "D2H gradient maxima"},
+                                            {&sum, dsum, sizeof(double), "D2H loss sum"}});
     if (profiling_) phases_.emplace_back("refit_streamed_trees", static_cast<float>(streamed));   // (not a time: trees whose sums the streaming kernel took)
     for (size_t i = 0; i <= T; ++i)
         if (hgmax[i] >= 0x7f800000u)
@@ -82,7 +81,7 @@ void Engine::refit_run(const kern::PredictModel &pm, const float *dobs, const in
     std::copy(hvals.begin(), hvals.end(), model.values.begin() + static_cast<long>(l0 * D));
     ++model.version;
     invalidate_mirror();
-    *plan.loss_out = std::sqrt(0.5 * sum / static_cast<double>(n));   // staged_loss's expression
+    *loss_out = std::sqrt(0.5 * sum / static_cast<double>(n));   // staged_loss's expression
 }
 
 }  // namespace gbrl
