@@ -660,6 +660,66 @@ py::array dataset_codes_impl(PyDataset &self, py::object &rows) {
     return std::move(out);
 }
 
+// Extension: the walk over a data set's bin codes (include/gbrl_hip.h).  condition_bins(thresholds) -> int32 array shaped like feature_values.
+py::array_t<int32_t> condition_bins_impl(PyGBRL &self, py::object &thresholds) {
+    const gbrl_hip_metadata md = self.meta();
+    Input t = read_input(thresholds, "thresholds", false, "condition_bins", false);
+    if (t.on_device) fail("condition_bins takes a NumPy array");
+    if (t.shape.size() != 2) fail("thresholds must be a float32 array of shape (n_features, n_bins)");
+    const py::ssize_t S = md.grow_policy == GBRL_HIP_GROW_OBLIVIOUS ? md.n_trees : md.n_leaves;
+    py::array_t<int32_t> out({S, static_cast<py::ssize_t>(md.max_depth)});
+    check(gbrl_hip_condition_bins(self.h, static_cast<const float *>(t.ptr), static_cast<int>(t.shape[0]), static_cast<int>(t.shape[1]), out.mutable_data()));
+    return out;
+}
+
+// predict_continue_prepared(ds, base, start, stop, rows=None): predict_continue's conventions for base and the range, step_prepared's for rows
+py::object predict_continue_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &base, py::object start_obj, py::object stop_obj, py::object &rows) {
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
+    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    Input b = read_input(base, "base", false, "predict_continue_prepared", false);
+    if (!b.ptr) fail("Cannot call predict_continue_prepared without base!");
+    Input r = read_rows(rows, "predict_continue_prepared");
+    const int D = md.output_dim;
+    int m = b.shape.empty() ? 0 : static_cast<int>(b.shape[0]);
+    if (!rows.is_none()) m = static_cast<int>(r.shape[0]);
+    else if (ds) m = ds_obj.cast<const PyDataset &>().info().n_rows;
+    check_rows_by_outputs(b, "base", m, D);
+    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
+    const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
+    const bool in_place = py::isinstance<py::tuple>(base);
+    float *out = in_place ? static_cast<float *>(const_cast<void *>(b.ptr)) : new float[std::max<size_t>(static_cast<size_t>(m) * D, 1)];
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_predict_continue_prepared(self.h, ds, rp, r.ptr ? r.on_device : 0, m, static_cast<const float *>(b.ptr), b.on_device, start, stop, out);
+    }
+    if (rc != GBRL_HIP_OK) {
+        if (!in_place) delete[] out;
+        fail(gbrl_hip_last_error());
+    }
+    if (in_place) return py::none();
+    py::capsule owner(out, [](void *p) { delete[] static_cast<float *>(p); });
+    std::vector<py::ssize_t> shp(b.shape.begin(), b.shape.end());
+    return py::array_t<float>(shp, out, owner);
+}
+
+float fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations) {
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    Input t = read_input(targets, "targets", false, "fit", false);
+    if (ds && t.ptr) check_rows_by_outputs(t, "targets", ds_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
+    float loss = 0.0f;
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_fit_prepared(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, &loss);
+    }
+    check(rc);
+    return loss;
+}
+
 float fit_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, int iterations, bool shuffle,
                const std::string &loss_type) {
     if (loss_type != "MultiRMSE") fail("Invalid loss function! Options are: MultiRMSE");   // stringTolossType, types.cpp:52-56
@@ -856,6 +916,23 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "transpose, candidates and binning phases.  rows (int32 vector of length m, duplicates allowed, entries in [0, ds.n_rows)): the tree is grown on\n"
           "those rows, grads [m, output_dim] in their order, with the DATA SET'S thresholds (as fit() uses whole-data-set candidates), not the subset's\n"
           "quantiles.  Any model on the same device with the data set's n_bins and generator_type and input_dim == ds.n_features may step on it.");
+    g.def("condition_bins", &condition_bins_impl, py::arg("thresholds"),
+          "condition_bins(thresholds) -> int32 array shaped like get_ensemble_data()['feature_values']\n\n"
+          "thresholds: float32 [n_features, n_bins], e.g. PreparedDataset.thresholds().  A used numeric condition x[f] > v gets bin = number of thresholds of f\n"
+          "below v, so that x > v <=> code > bin for the data set's codes; unused and categorical slots get -1.  A used value that is not among its feature's\n"
+          "thresholds is refused (the message names the tree and the condition).  Host only: no device is needed.");
+    g.def("predict_continue_prepared", &predict_continue_prepared_impl, py::arg("ds"), py::arg("base"), py::arg("start_tree_idx") = 0,
+          py::arg("stop_tree_idx") = 0, py::arg("rows") = py::none(),
+          "predict_continue_prepared(ds, base, start_tree_idx=0, stop_tree_idx=0, rows=None)\n\n"
+          "predict_continue(obs[rows], None, base, start_tree_idx, stop_tree_idx) bit for bit, read from the data set's bin codes: obs need not exist any more.\n"
+          "base / range / return as predict_continue (a NumPy base gives a new array, a device tuple is updated in place); rows as step_prepared.\n"
+          "Every tree of the range must compare against the data set's thresholds (trees grown on it by step_prepared / fit_prepared do).");
+    g.def("fit_prepared", &fit_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("iterations"),
+          "fit_prepared(ds, targets, iterations) -> float\n\n"
+          "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
+          "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
+          "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
+          "prepare_dataset.");
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);
     }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("return_torch") = false);

@@ -514,6 +514,33 @@ int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const 
     });
 }
 
+// ---- the walk over a data set's bin codes
+int gbrl_hip_condition_bins(const gbrl_hip_model *m, const float *thresholds, int n_features, int n_bins, int32_t *out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.condition_bins(thresholds, n_features, n_bins, out);
+    });
+}
+
+int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
+                                       const float *base, int base_on_device, int start_tree, int stop_tree, float *out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("predict_continue_prepared");
+        m->engine.predict_continue_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, base, base_on_device != 0, start_tree, stop_tree, out,
+                                            base_on_device != 0);
+    });
+}
+
+int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations, float *loss_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_fit_prepared(targets, iterations);
+        const float loss = m->engine.fit_prepared(&live_dataset(ds), targets, targets_on_device != 0, iterations);
+        if (loss_out) *loss_out = loss;
+    });
+}
+
 int gbrl_hip_leaf_counts_chunk(void) { return gbrl::kern::leaf_counts_chunk(); }
 
 static_assert(static_cast<int>(gbrl::Engine::ParityMode::Default) == GBRL_HIP_PARITY_DEFAULT && static_cast<int>(gbrl::Engine::ParityMode::Reference) == GBRL_HIP_PARITY_REFERENCE &&

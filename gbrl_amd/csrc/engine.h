@@ -86,6 +86,7 @@ struct NumericPrep {
 class PreparedDataset {
    public:
     int n = 0, F = 0, n_bins = 0, generator_type = 0, device = -1;
+    uint64_t id = 0;               // unique per data set of the process (a handle's address can come back): what an engine's code tables are keyed on
     PrepBuffers buf;
     NumericPrep prep;              // pointers into buf
     std::vector<float> h_thr;      // host copy of the thresholds [F][B]
@@ -142,6 +143,28 @@ class Engine {
     // before anything reads through it; after any failure the model is unchanged.
     PreparedDataset *prepare_dataset(const float *obs, bool obs_dev, int n, int n_num);
     void step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m);
+    // Extension (engine_fit_prepared.hip): the walk over a data set's bin codes.  code(r, f) = #{b : thr[f][b] < obs[r, f]}, so a numeric condition
+    // x[f] > v whose v is one of thr[f][*] is code > bin with bin = #{b : thr[f][b] < v} (include/gbrl_hip.h has the argument).
+    // condition_bins: host only.  out has the length and indexing of feature_values; a used numeric slot (d < depths[split row]) gets its bin,
+    // every other slot -1.  thresholds [F][B]; F / B that are not the model's: InvalidArgument; a used numeric condition whose value is not
+    // among its feature's thresholds (float ==; NaN never is): Unsupported, naming the tree and the condition.
+    void condition_bins(const float *thresholds, int F, int B, int32_t *out) const;
+    // predict_continue_prepared: out [m][D] = base carried through [start_tree, stop_tree) for the data set rows rows[0..m) (rows == nullptr: every
+    // row, m == ds->n) -- bit for bit predict_continue on the observations the data set was made from.  Ranges and base / out as predict_continue,
+    // rows as step_prepared.  Refused before the device is touched: what step_prepared refuses about the model and the data set, output_dim > 128,
+    // a tree of the range (greedy: through the first tree with a split behind the range's trailing depth-0 trees, which the walk runs into) with a
+    // condition that is not among the data set's thresholds (Unsupported).  The model is never changed.
+    void predict_continue_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *base, bool base_dev, int start_tree,
+                                   int stop_tree, float *out, bool out_dev);
+    // fit_prepared: fit()'s loop (shuffle = false) with nothing recomputed -- the running prediction of every row is held and advanced by the
+    // trees grown since its batch last saw it (one launch that also writes the MultiRMSE gradient), the tree is grown by step_prepared's body.
+    // A fresh model gets bias = column means of the targets; a model with trees keeps its bias and continues from ALL its trees (unlike fit()),
+    // every one of which must be expressible on the data set (Unsupported before anything changes).  Returns fit()'s loss.
+    float fit_prepared(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations);
+    // what the two calls above refuse without looking at the data set, in their order (the C ABI runs it before it resolves the handle, so that
+    // these refusals do not depend on a data set being at hand): the model checks of step_prepared, then fit_prepared's own arguments
+    void precheck_prepared(const char *what) const { check_prepared_model(what); }
+    void precheck_fit_prepared(const float *targets, int iterations) const;
     void predict(const float *obs, bool obs_dev, const char *cat, bool cat_dev, int n, int n_num, int n_cat, int start_tree,
                  int stop_tree, float *out, bool out_dev);
     // Extension (not in the reference, which compares the 128-byte cells inside every predict call): the dictionary ids of a batch of
@@ -288,6 +311,15 @@ class Engine {
     void read_step_hooks();                                              // the per-call test hooks that choose the selection path
     bool fused_prep_applies(int N, int F, long long n_global) const;     // kern::small_prep is tried for this shape
     void check_prepared_model(const char *what) const;                   // numeric-only, one GPU, step()'s limits: raised before the device is touched
+    void check_prepared_dataset(const char *what, const PreparedDataset *ds) const;   // the data set is there and is this model's: device, n_bins, generator, width
+    // step_prepared behind its argument checks and input staging: statistics, growth, append on device gradients and (nullable) device rows
+    void step_prepared_run(const PreparedDataset *ds, const float *dgrads, const int32_t *d_rows, int m);
+    void begin_step_profile();   // a step's phase list starts here
+    // ---- conditions as bin indices of ONE data set (engine_fit_prepared.hip): host tables appended split row by split row, their device copies
+    // appended behind sync_model_to_device().  Dropped when another data set is named or the ensemble has shrunk.
+    void sync_code_bins(const PreparedDataset &ds);                      // host only: code_bins_host_ covers every split row of the model
+    void check_code_range(const PreparedDataset &ds, const char *what, int start_tree, int stop_tree);   // Unsupported: an inexpressible condition the walk of the range reads
+    kern::CodeTables sync_code_tables(const PreparedDataset &ds);        // device: needs sync_model_to_device()
     // numeric preparation of a batch into `pb` (phases transpose / candidates / binning); fs: the gradient statistics that step() lets the
     // fused preparation kernel compute in its launch (nullptr: want_stats = false)
     NumericPrep prepare_numeric(PrepBuffers &pb, const float *dobs, int N, int F, int Fc, long long n_global, bool prep_candidate, detail::FusedStats *fs);
@@ -355,6 +387,11 @@ class Engine {
     size_t leafacc_clean_bytes_ = 0;
     PrepBuffers prep_ws_;             // step()'s numeric preparation; step_prepared(rows) gathers the subset's codes into prep_ws_.codes
     DevBuf d_sub_rows_, d_rows_mm_;   // step_prepared(rows): device copy of a host index vector, min / max of a device one
+    uint64_t code_ds_id_ = 0;         // the data set the code tables below are for (0: none)
+    size_t code_splits_ = 0, code_up_splits_ = 0, code_nodes_ = 0, code_up_nodes_ = 0;   // split rows / greedy node records converted on the host, and on the device
+    std::vector<int32_t> code_bins_host_, code_pack_host_, code_nodes_host_;   // bins [S][MD] (-1 unused or categorical, -2 inexpressible), cond_pack and grd_nodes with the bin as their second word
+    DevBuf m_code_bins_, m_code_pack_, m_code_nodes_;
+    DevBuf d_fp_pred_, d_fp_grads_, d_fp_iota_, d_fp_targets_;   // fit_prepared: held prediction [n][D], batch gradients, 0..n-1, staged targets
     DevBuf d_am_s_, d_near_list_, d_near_ent_, d_near_rep_, d_near_nr_, d_near_maps_, d_near_pos_, d_near_nrb_, d_near_vals_, d_near_means_, d_near_sums_, d_near_chains_, d_near_rowsort_, d_near_tiles_;   // near-tie replay (kern::near_tie_replay): runner-up per arg-max block, candidate lists, ordered row lists, replayed scores
     bool small_grow_off_ = false;     // latched after a failed launch / an abandoned grid barrier of the one-launch kernel: this engine keeps to the level loop
     long long small_grow_fallbacks_ = 0;   // trees the level loop grew after such a failure (diagnostics)

@@ -43,6 +43,8 @@ PreparedDataset *Engine::prepare_dataset(const float *obs, bool obs_dev, int n, 
     const int N = n, F = n_num, B = md.n_bins;
     std::unique_ptr<PreparedDataset> ds(new PreparedDataset());
     ds->n = N; ds->F = F; ds->n_bins = B; ds->generator_type = md.generator_type; ds->device = device_ordinal_;
+    static std::atomic<uint64_t> next_id{1};
+    ds->id = next_id.fetch_add(1, std::memory_order_relaxed);
     phase_begin();
     const float *dobs = obs;
     if (!obs_dev) {
@@ -60,9 +62,7 @@ PreparedDataset *Engine::prepare_dataset(const float *obs, bool obs_dev, int n, 
     return ds.release();
 }
 
-namespace {
-// Device copy of an index vector, every entry known to lie in [0, n) BEFORE anything reads through it: a host vector is checked on the host
-// (check_host_rows, before the device is touched), a device vector by kern::rows_minmax, read back.
+namespace detail {
 const int32_t *checked_rows(DevBuf &copy, DevBuf &mm_buf, const int32_t *rows, bool rows_dev, int m, int n, hipStream_t s) {
     if (!rows_dev) {
         int32_t *d = static_cast<int32_t *>(copy.ensure(sizeof(int32_t) * static_cast<size_t>(m)));
@@ -84,22 +84,37 @@ void check_host_rows(const int32_t *rows, int m, int n) {
         if (rows[j] < 0 || rows[j] >= n)
             throw InvalidArgument("rows: index " + std::to_string(rows[j]) + " (entry " + std::to_string(j) + ") is outside [0, " + std::to_string(n) + ")");
 }
-}  // namespace
+}  // namespace detail
 
-void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m) {
-    gbrl_hip_metadata &md = model.meta;
-    if (ds == nullptr) throw InvalidArgument("step_prepared: null data set");
-    check_prepared_model("step_prepared");
+// the data set is there and is this model's (step_prepared's checks; `what` prefixes the messages)
+void Engine::check_prepared_dataset(const char *what, const PreparedDataset *ds) const {
+    const gbrl_hip_metadata &md = model.meta;
+    const std::string w(what);
+    if (ds == nullptr) throw InvalidArgument(w + ": null data set");
+    check_prepared_model(what);
     {
         int dev = device_ordinal_;
         if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = -1;   // (an unlatched model runs on the calling thread's current device)
         if (dev >= 0 && dev != ds->device)
-            throw Unsupported("step_prepared: the data set lives on device " + std::to_string(ds->device) + ", the model on device " + std::to_string(dev));
+            throw Unsupported(w + ": the data set lives on device " + std::to_string(ds->device) + ", the model on device " + std::to_string(dev));
     }
-    if (ds->n_bins != md.n_bins) throw InvalidArgument("step_prepared: the data set was binned with n_bins = " + std::to_string(ds->n_bins) + ", the model has " + std::to_string(md.n_bins));
-    if (ds->generator_type != md.generator_type) throw InvalidArgument("step_prepared: the data set's generator_type differs from the model's");
+    if (ds->n_bins != md.n_bins) throw InvalidArgument(w + ": the data set was binned with n_bins = " + std::to_string(ds->n_bins) + ", the model has " + std::to_string(md.n_bins));
+    if (ds->generator_type != md.generator_type) throw InvalidArgument(w + ": the data set's generator_type differs from the model's");
     if (ds->F != md.input_dim) throw InvalidArgument("Total number of features != correct input dim");
     if (md.iteration > 0 && ds->F != md.n_num_features) throw InvalidArgument("Incompatible dataset");
+}
+
+void Engine::begin_step_profile() {
+    prof_step_entry_ = std::chrono::steady_clock::now();
+    ev_used_ = 0;
+    ev_names_.clear();
+    exch_bytes_ = 0;
+    exch_calls_ = 0;
+}
+
+void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m) {
+    gbrl_hip_metadata &md = model.meta;
+    check_prepared_dataset("step_prepared", ds);
     if (grads == nullptr) throw InvalidArgument("Cannot call step without grads!");
     if (m <= 0) throw InvalidArgument("step_prepared: no rows (m must be positive)");
     if (rows == nullptr && m != ds->n)
@@ -108,29 +123,33 @@ void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool g
     if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
     if (md.output_dim > 512) throw Unsupported("output_dim > 512");
     if (rows != nullptr && !rows_dev) check_host_rows(rows, m, ds->n);
+    ensure_device();
+    begin_step_profile();
+    hipStream_t s = stream_;
+    const int N = m, D = md.output_dim;
+    // ---- inputs on the device ---------------------------------------------------------------------------------
+    phase_begin();
+    const float *dgrads = grads;
+    if (!grads_dev) {
+        dgrads = static_cast<float *>(d_grads_.ensure(sizeof(float) * N * D));
+        hip_check(hipMemcpyAsync(const_cast<float *>(dgrads), grads, sizeof(float) * N * D, hipMemcpyHostToDevice, s), "H2D grads");
+    }
+    const int32_t *d_rows = rows ? checked_rows(d_sub_rows_, d_rows_mm_, rows, rows_dev, m, ds->n, s) : nullptr;
+    phase_end("inputs");
+    step_prepared_run(ds, dgrads, d_rows, m);
+}
+
+// One boosting step on device inputs that have been checked (fit_prepared's loop body too): the phase list is the caller's (begin_step_profile).
+void Engine::step_prepared_run(const PreparedDataset *ds, const float *dgrads, const int32_t *d_rows, int m) {
+    gbrl_hip_metadata &md = model.meta;
     // GBRL::step, gbrl.cpp:946-958 (the latch is taken back when the step fails: the model is unchanged after any failure)
     const int32_t keep_num = md.n_num_features, keep_cat = md.n_cat_features;
     if (md.iteration == 0) { md.n_num_features = ds->F; md.n_cat_features = 0; }
     try {
-        ensure_device();
-        prof_step_entry_ = std::chrono::steady_clock::now();
-        ev_used_ = 0;
-        ev_names_.clear();
-        exch_bytes_ = 0;
-        exch_calls_ = 0;
         hipStream_t s = stream_;
         const int N = m, F = ds->F, D = md.output_dim;
         const bool cosine = md.split_score_func == GBRL_HIP_SCORE_COSINE;
         long long n_global = N;
-        // ---- inputs on the device ---------------------------------------------------------------------------------
-        phase_begin();
-        const float *dgrads = grads;
-        if (!grads_dev) {
-            dgrads = static_cast<float *>(d_grads_.ensure(sizeof(float) * N * D));
-            hip_check(hipMemcpyAsync(const_cast<float *>(dgrads), grads, sizeof(float) * N * D, hipMemcpyHostToDevice, s), "H2D grads");
-        }
-        const int32_t *d_rows = rows ? checked_rows(d_sub_rows_, d_rows_mm_, rows, rows_dev, m, ds->n, s) : nullptr;
-        phase_end("inputs");
         prof_marks_[0] = std::chrono::steady_clock::now();
         // ---- 1. gradient statistics and quantisation (A2) ----------------------------------------------------------
         phase_begin();

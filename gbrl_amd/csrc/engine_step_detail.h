@@ -5,6 +5,7 @@
 //   engine_step.hip        Engine::step / Engine::fit, the host scan of categorical cells, the tree joining the ensemble (A1, A2, A10-A11), and
 //                          the stages step() shares with step_prepared(): run_grad_stats, prepare_numeric, grow_step_tree
 //   engine_prepared.hip    Engine::prepare_dataset / Engine::step_prepared: a batch binned once and stepped on many times
+//   engine_fit_prepared.hip  Engine::predict_continue_prepared / Engine::fit_prepared: the walk over a data set's bin codes, fit()'s loop on it
 #pragma once
 #include "engine.h"
 #include "hooks.h"
@@ -183,6 +184,11 @@ void categorical_candidates(const char *hcat, const float *hgrads, int N, int Fc
                             std::vector<uint16_t> &h_catcodes, std::vector<int> &cat_classes);
 void append_tree(Model &model, const std::vector<HNode> &nodes, const std::vector<int> &frontier, const std::vector<int64_t> &acc,
                  double leaf_scale, const std::vector<CatCandidate> &cat_cands);
+// Row subsets of a prepared data set (engine_prepared.hip).  checked_rows: device copy of an index vector, every entry known to lie in [0, n)
+// BEFORE anything reads through it: a host vector is checked on the host (check_host_rows, before the device is touched), a device vector by
+// kern::rows_minmax, read back.
+const int32_t *checked_rows(DevBuf &copy, DevBuf &mm_buf, const int32_t *rows, bool rows_dev, int m, int n, hipStream_t s);
+void check_host_rows(const int32_t *rows, int m, int n);
 
 }  // namespace detail
 
@@ -192,5 +198,7 @@ using detail::spin_until_published;
 using detail::quantile_target_ranks;
 using detail::categorical_candidates;
 using detail::append_tree;
+using detail::checked_rows;
+using detail::check_host_rows;
 
 }  // namespace gbrl

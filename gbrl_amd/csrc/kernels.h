@@ -563,6 +563,19 @@ void predict(const PredictModel &pm, const float *obs, int F, const int32_t *cat
 // device pointers and may be the same buffer.  generic: the one-thread-per-row kernel only (GBRL_HIP_CONTINUE_GENERIC=1).  Always launches.
 void predict_continue(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
                       const float *base, float *out, bool generic, hipStream_t s);
+// The same chain with the row read from a prepared data set's bin codes (predict_continue_codes.hip): the bits of predict_continue on the
+// observations the data set was made from, for a model whose numeric conditions all compare against that data set's thresholds.
+//   CodeTables  device tables of the engine's mirror with the threshold word replaced by the condition's bin (x > v <=> code > bin): `bins`
+//               indexed like feature_values, `cond_pack` like PredictModel::cond_pack, `grd_nodes` like PredictModel::grd_nodes (same offsets)
+//   CodeRows    the rows to walk: row j of the call is data set row rows[row0 + j] (rows != nullptr, device, every entry in [0, n_rows)) or
+//               row0 + j; codes [groups][n_rows][16] u16
+// base / out (may be the same buffer) / targets / grad_out are device [m][D], indexed by j.  targets != nullptr: grad_out = fl32(out - targets)
+// of the new out in the same pass (kern::sub_arrays' bits).  generic: the one-thread-per-row kernel only.  Always launches (m > 0).
+struct CodeTables { const int32_t *bins, *cond_pack, *grd_nodes; };
+struct CodeRows { const uint16_t *codes; int n_rows, groups; const int32_t *rows; int row0; };
+void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
+                            float *out, const float *targets, float *grad_out, bool generic, hipStream_t s);
+void tile_rows(const float *row /*[D], device*/, int D, int n, float *out /*[n][D]*/, hipStream_t s);   // out[r] = row: fit_prepared's held prediction starts as the bias
 // Every prefix [0, stops[s]) of the ensemble in one walk (predict_staged.hip): stage s has the bits of predict_continue(tiled bias, 0, stops[s]);
 // stops[s] == 0 is the bias alone.  `stops` is a device array, strictly ascending, 0 <= stops[s] <= n_trees (the caller has checked);
 // last_stop = stops[n_stops - 1].  Predict mode (targets == nullptr): out[s][r][j], device [n_stops][n][D].  Loss mode (targets != nullptr,

@@ -1,0 +1,146 @@
+// predict_continue_codes.hip -- gfx950 kernels behind GBRL::predict_continue_prepared and GBRL::fit_prepared: predict_continue.hip's chain with the
+// row read from a prepared data set's bin codes instead of the observations.  Every condition of a tree grown on a data set compares against one
+// of that data set's thresholds, and code(r, f) = #{b : thr[f][b] < obs[r, f]}, so `x > v` is `code > bin` with bin = #{b : thr[f][b] < v}
+// (Engine::condition_bins has the argument; a model with a condition outside the thresholds never gets here).  The walk, the grouping of trees,
+// the rates and the owner rule are predict_rowwalk.h's, instantiated with a code row: the bits are predict_continue's.
+//
+//   k_continue_codes          lane = row, one wave per block.  The block's 64 rows are staged from the group-major records [G][N][16] u16 into an
+//                             LDS tile of G * 8 words per row at an odd word stride (stream_stage_code_tile: 16-byte loads, two lanes per record);
+//                             a row costs 32 G bytes against the float walk's 4 F -- half of it when F is a multiple of 16.  With `rows` lane j
+//                             stages the records of rows[row0 + j]; without, of row0 + j.  base / out / targets / grad_out are indexed by j.
+//   k_continue_codes_general  one thread per row, the records read in place: D in 65..128, optimizers that share outputs, a greedy depth-0
+//                             tree, F too wide for the tile, a refused LDS opt-in, and the cross-check behind GBRL_HIP_CONTINUE_GENERIC=1.
+//   fused tail                targets != nullptr: grad_out[j][d] = fl32(out[j][d] - targets[j][d]) for the NEW out -- one float32 subtraction,
+//                             kern::sub_arrays' bits -- in the same pass (fit_prepared's MultiRMSE gradient).
+#include "kernels.h"
+#include "kernels_common.h"
+#include "predict_rowwalk.h"
+
+namespace gbrl {
+namespace kern {
+
+namespace {
+
+__global__ __launch_bounds__(256) void k_sub_rows(const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ out, size_t n) {
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * blockDim.x) out[i] = __fsub_rn(a[i], b[i]);
+}
+
+__global__ __launch_bounds__(256) void k_tile_rows(const float *__restrict__ row, int D, size_t n_el, float *__restrict__ out) {
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n_el; i += static_cast<size_t>(gridDim.x) * blockDim.x) out[i] = row[i % D];
+}
+
+// ------------------------------------------------------------------------------------------------------------ general kernel
+template <int DMAX>
+__global__ __launch_bounds__(256) void k_continue_codes_general(ChainModel cm, CodeRows cr, int m, int start_tree, int stop_tree, const float *base, float *out,
+                                                                const float *__restrict__ targets, float *__restrict__ grad_out) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const int D = cm.D;
+    float p[DMAX];
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d) p[d] = d < D ? base[static_cast<size_t>(j) * D + d] : 0.0f;
+    const size_t src = static_cast<size_t>(cr.rows ? cr.rows[cr.row0 + j] : cr.row0 + j);
+    const GeneralCodeRow r{cr.codes + src * kCodeGroup, static_cast<size_t>(cr.n_rows) * kCodeGroup};
+    for (int t = start_tree; t < stop_tree; ++t)
+        if (!general_chain_tree<DMAX>(cm, r, t, p)) break;   // a greedy search ran off the ensemble: the walk ends
+#pragma unroll
+    for (int d = 0; d < DMAX; ++d)
+        if (d < D) {
+            out[static_cast<size_t>(j) * D + d] = p[d];
+            if (targets != nullptr) grad_out[static_cast<size_t>(j) * D + d] = __fsub_rn(p[d], targets[static_cast<size_t>(j) * D + d]);
+        }
+}
+
+// ------------------------------------------------------------------------------------------------------------ streaming kernel
+template <int DMAX, bool GREEDY>
+__global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, StreamOwner<DMAX> own, uint64_t cover, CodeRows cr, int m, int start_tree,
+                                                                int stop_tree, const float *base, float *out, const float *__restrict__ targets,
+                                                                float *__restrict__ grad_out, int vec_values, int vec_io, int vec_grad) {
+    extern __shared__ __align__(16) uint32_t cctile[];   // [kStreamRows][stream_code_stride(G)]
+    const int lane = threadIdx.x;
+    const int D = cm.D;
+    const int r0 = blockIdx.x * kStreamRows;
+    const int rows = min(kStreamRows, m - r0);
+    const bool live = lane < rows;
+    const size_t row = static_cast<size_t>(r0) + lane;
+    float p[DMAX];
+    if (live) {
+        stream_load_row<DMAX>(base + row * D, D, vec_io != 0, p);
+    } else {
+#pragma unroll
+        for (int d = 0; d < DMAX; ++d) p[d] = 0.0f;
+    }
+    const int at = cr.row0 + r0 + (live ? lane : 0);   // (a lane without a row names the block's first: a valid record, never stored)
+    const int my_row = cr.rows ? cr.rows[at] : at;
+    stream_stage_code_tile(cctile, cr.codes, static_cast<size_t>(cr.n_rows), cr.groups, my_row, rows, lane);
+    __syncthreads();
+    if (live) {
+        const StreamCodeRow x{reinterpret_cast<const uint16_t *>(cctile + lane * stream_code_stride(cr.groups))};
+        for (int t0 = start_tree; t0 < stop_tree; t0 += kStreamGroup<DMAX>)
+            stream_chain_group<DMAX, GREEDY>(cm, own, cover, x, static_cast<const int32_t *>(nullptr), t0, stop_tree, vec_values, p);
+        stream_store_row<DMAX>(out + row * D, D, vec_io != 0, p);
+        if (targets != nullptr) {
+            float y[DMAX];
+            stream_load_row<DMAX>(targets + row * D, D, vec_grad != 0, y);
+#pragma unroll
+            for (int d = 0; d < DMAX; ++d) y[d] = __fsub_rn(p[d], y[d]);
+            stream_store_row<DMAX>(grad_out + row * D, D, vec_grad != 0, y);
+        }
+    }
+}
+
+template <int DMAX, bool GREEDY>
+bool launch_continue_codes(const ChainModel &cm, const PredictModel &pm, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
+                           float *out, const float *targets, float *grad_out, hipStream_t s) {
+    const size_t lds = stream_code_tile_bytes(cr.groups);
+    if (lds > kStreamLdsBudget) return false;   // rows too wide for an LDS tile
+    static StreamLdsOptIn optin;
+    if (!optin.ok(k_continue_codes<DMAX, GREEDY>, lds)) return false;
+    const bool d4 = (pm.D & 3) == 0;
+    const int vec_values = d4 && (reinterpret_cast<uintptr_t>(pm.values) & 15) == 0;
+    const int vec_io = d4 && ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int vec_grad = d4 && ((reinterpret_cast<uintptr_t>(targets) | reinterpret_cast<uintptr_t>(grad_out)) & 15) == 0;
+    hipLaunchKernelGGL((k_continue_codes<DMAX, GREEDY>), dim3((m + kStreamRows - 1) / kStreamRows), dim3(kStreamRows), lds, s, cm, stream_owner<DMAX>(pm),
+                       pm.coef_cover, cr, m, start_tree, stop_tree, base, out, targets, grad_out, vec_values, vec_io, vec_grad);
+    return true;
+}
+
+}  // namespace
+
+void tile_rows(const float *row, int D, int n, float *out, hipStream_t s) {
+    const size_t n_el = static_cast<size_t>(n) * D;
+    if (n_el == 0) return;
+    hipLaunchKernelGGL(k_tile_rows, dim3(static_cast<unsigned>(std::min<size_t>((n_el + 255) / 256, 4096))), dim3(256), 0, s, row, D, n_el, out);
+}
+
+void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
+                            float *out, const float *targets, float *grad_out, bool generic, hipStream_t s) {
+    if (m <= 0) return;
+    if (stop_tree <= start_tree || pm.n_opts <= 0) {   // no tree to apply, or no optimizer that owns an output: the base as it is
+        const size_t n_el = static_cast<size_t>(m) * pm.D;
+        if (out != base) (void)hipMemcpyAsync(out, base, sizeof(float) * n_el, hipMemcpyDeviceToDevice, s);
+        if (targets != nullptr) {
+            const unsigned blocks = static_cast<unsigned>(std::min<size_t>((n_el + 255) / 256, 4096));
+            hipLaunchKernelGGL(k_sub_rows, dim3(blocks), dim3(256), 0, s, out, targets, grad_out, n_el);
+        }
+        return;
+    }
+    // the model view of the float walk with the threshold words replaced by bins (the packed conditions, the greedy node records, the general table)
+    ChainModel cm = chain_model(pm);
+    cm.walk.cond_pack = ct.cond_pack;
+    cm.walk.grd_nodes = ct.grd_nodes;
+    cm.walk.feature_bins = ct.bins;
+    if (chain_streamable(pm, generic) && with_stream_dmax(pm.D, [&](auto dmax) {
+            constexpr int DMAX = decltype(dmax)::value;
+            return pm.oblivious ? launch_continue_codes<DMAX, false>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, s)
+                                : launch_continue_codes<DMAX, true>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, s);
+        }))
+        return;
+    with_general_dmax(pm.D, [&](auto dmax) {
+        hipLaunchKernelGGL((k_continue_codes_general<decltype(dmax)::value>), dim3((m + 255) / 256), dim3(256), 0, s, cm, cr, m, start_tree, stop_tree, base,
+                           out, targets, grad_out);
+    });
+}
+
+}  // namespace kern
+}  // namespace gbrl

@@ -1,7 +1,10 @@
-// predict_rowwalk.h -- the one row walk behind predict_continue.hip, predict_staged.hip, predict_leaves.hip and refit.hip.  All four route a
+// predict_rowwalk.h -- the one row walk behind predict_continue.hip, predict_continue_codes.hip, predict_staged.hip, predict_leaves.hip and refit.hip.  All route a
 // row to the same leaf and, where they apply values, run the same chain p = fma(-rate(t, optimizer of the output), value(leaf), p), because
 // every piece of that exists once, here:
 //   model views    LeavesModel (routing: leaves_model) and ChainModel (routing + values, rates, bias: chain_model); the rate rule is chain_rates
+//   row accessors  how a walk reads a numeric condition of its row: floats against the threshold (GeneralRow, a float tile row) or a prepared
+//                  data set's bin codes against the condition's bin (GeneralCodeRow, StreamCodeRow; x > v <=> code > bin, engine_fit_prepared.hip).
+//                  Every walk below takes the row as a template parameter; the staging of a code tile is stream_stage_code_tile
 //   general side   one thread per row, rows in global memory, anything the file format can hold: general_test, general_leaf (the reference's
 //                  walk; greedy: leaf by leaf, Q7), general_apply (every optimizer that owns the output, in order) and general_chain_tree
 //                  (one tree of the chain: k_continue_general's loop body, and k_staged_general's between two checkpoints)
@@ -34,6 +37,7 @@ struct LeavesModel {
     const float *feature_values;
     const uint8_t *is_numerics, *inequality_directions;
     int n_leaves, max_depth, oblivious;
+    const int32_t *feature_bins;   // code walks only: the bin of every numeric condition, indexed like feature_values (null otherwise)
 };
 
 // rate(t, o) = rate[t * rate_stride + o]: PredictModel::rate (stride n_opts) for an ensemble with a Linear schedule (absolute tree index),
@@ -71,12 +75,25 @@ inline ChainModel chain_model(const PredictModel &pm) { return ChainModel{pm.val
 struct GeneralRow {
     const float *x;
     const int32_t *xc;
+    __device__ __forceinline__ bool numeric(const LeavesModel &cm, int f, int c) const { return x[f] > cm.feature_values[c]; }
+    __device__ __forceinline__ bool categorical(const LeavesModel &cm, int f, int c) const { return xc != nullptr && xc[f] == cm.cat_ids[c]; }
 };
-__device__ __forceinline__ bool general_test(const LeavesModel &cm, const GeneralRow &r, int c) {
+// a row of a prepared data set: its 32-byte code records, one per group of 16 features, `group_stride` u16 apart ([G][N][16]); numeric-only
+struct GeneralCodeRow {
+    const uint16_t *rec;
+    size_t group_stride;
+    __device__ __forceinline__ bool numeric(const LeavesModel &cm, int f, int c) const {
+        return static_cast<int>(rec[static_cast<size_t>(f >> 4) * group_stride + (f & 15)]) > cm.feature_bins[c];
+    }
+    __device__ __forceinline__ bool categorical(const LeavesModel &, int, int) const { return false; }
+};
+template <typename Row>
+__device__ __forceinline__ bool general_test(const LeavesModel &cm, const Row &r, int c) {
     const int f = cm.feature_indices[c];
-    return cm.is_numerics[c] ? (r.x[f] > cm.feature_values[c]) : (r.xc != nullptr && r.xc[f] == cm.cat_ids[c]);
+    return cm.is_numerics[c] ? r.numeric(cm, f, c) : r.categorical(cm, f, c);
 }
-__device__ __forceinline__ int general_leaf(const LeavesModel &cm, const GeneralRow &r, int t) {
+template <typename Row>
+__device__ __forceinline__ int general_leaf(const LeavesModel &cm, const Row &r, int t) {
     const int md = cm.max_depth;
     if (cm.oblivious) {
         const int depth = cm.depths[t], cond = t * md;
@@ -114,8 +131,8 @@ __device__ __forceinline__ void general_apply(const ChainModel &cm, int t, int l
 // counter's rate, the counter moves on and the search restarts at tree_indices[t + 1]; a search that passes the last leaf ends the walk.  So
 // per tree it finds general_leaf(t) -- a later tree's leaf when none of tree t's passes (a depth-0 leaf never does, Q7), still applied at
 // tree t's rate -- and -1 ends the walk for good.  Returns false then; a caller that suspends the walk at a checkpoint must not resume it.
-template <int DMAX>
-__device__ __forceinline__ bool general_chain_tree(const ChainModel &cm, const GeneralRow &r, int t, float (&p)[DMAX]) {
+template <int DMAX, typename Row>
+__device__ __forceinline__ bool general_chain_tree(const ChainModel &cm, const Row &r, int t, float (&p)[DMAX]) {
     const int leaf = general_leaf(cm.walk, r, t);
     if (leaf < 0) return false;
     general_apply<DMAX>(cm, t, leaf, p);
@@ -190,11 +207,48 @@ __device__ __forceinline__ void stream_stage_tile(float *tile, const float *__re
     }
 }
 
+// A block's rows of a prepared data set into a code tile: tile[kStreamRows][stream_code_stride(G)] 4-byte words, a row = its G records of 16 u16
+// codes back to back.  The stride is odd, so a wave that reads one feature of its 64 rows (a 2-byte read: banks are per word, modulo 32 within
+// each half of the wave) never meets a bank twice.  The records are group-major in memory, [G][N][16]: lane `lane` names the data set row of
+// tile row `lane` (my_row; any valid row for a lane without one), and the G * 128 half-records travel as 16-byte loads, two lanes per record,
+// 16 in flight per lane.  The caller synchronises the block afterwards.
+__device__ __forceinline__ int stream_code_stride(int G) { return (G * 8) | 1; }
+__device__ __forceinline__ void stream_stage_code_tile(uint32_t *tile, const uint16_t *__restrict__ codes, size_t N, int G, int my_row, int rows, int lane) {
+    const int ws = stream_code_stride(G);
+    const uint4 *src4 = reinterpret_cast<const uint4 *>(codes);
+    const int tot = G * 2 * kStreamRows;   // half-records of the block: [group][tile row][half]
+    constexpr int UL = 16;
+    for (int i0 = lane; i0 < tot; i0 += kStreamRows * UL) {
+        uint4 v[UL];
+#pragma unroll
+        for (int u = 0; u < UL; ++u) {
+            const int i = i0 + u * kStreamRows;
+            const int j = (i & (2 * kStreamRows - 1)) >> 1;
+            const int src_row = __shfl(my_row, j);   // (every lane takes part: i0 < tot is wave-uniform, tot is a multiple of 64)
+            v[u] = (i < tot && j < rows) ? src4[((static_cast<size_t>(i >> 7) * N + static_cast<size_t>(src_row)) << 1) + (i & 1)] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < UL; ++u) {
+            const int i = i0 + u * kStreamRows;
+            if (i < tot) {
+                const int j = (i & (2 * kStreamRows - 1)) >> 1;
+                uint32_t *dst = tile + j * ws + (i >> 7) * 8 + (i & 1) * 4;
+                dst[0] = v[u].x; dst[1] = v[u].y; dst[2] = v[u].z; dst[3] = v[u].w;
+            }
+        }
+    }
+}
+
+// the lane's row in the LDS tile: floats against a condition's threshold bits, or the u16 codes of a code tile against its bin
+__device__ __forceinline__ bool stream_numeric(const float *x, int f, int tv) { return x[f] > __int_as_float(tv); }
+struct StreamCodeRow { const uint16_t *c; };
+__device__ __forceinline__ bool stream_numeric(const StreamCodeRow &x, int f, int bin) { return static_cast<int>(x.c[f]) > bin; }
+
 // the walk of tree t (wave-uniform t); x is the lane's row in the LDS tile
-template <bool GREEDY>
-__device__ __forceinline__ int stream_leaf(const LeavesModel &cm, const float *x, const int32_t *xc, int t) {
-    // feature word >= 0: numeric feature against a threshold; < 0: ~categorical feature against a dictionary id
-    auto pass = [&](int fi, int tv) -> bool { return fi >= 0 ? (x[fi] > __int_as_float(tv)) : (xc != nullptr && xc[~fi] == tv); };
+template <bool GREEDY, typename Row>
+__device__ __forceinline__ int stream_leaf(const LeavesModel &cm, const Row &x, const int32_t *xc, int t) {
+    // feature word >= 0: numeric feature against a threshold (a code row: against a bin); < 0: ~categorical feature against a dictionary id
+    auto pass = [&](int fi, int tv) -> bool { return fi >= 0 ? stream_numeric(x, fi, tv) : (xc != nullptr && xc[~fi] == tv); };
     const int md = cm.max_depth;
     if (!GREEDY) {
         const int depth = cm.depths[t];
@@ -229,8 +283,8 @@ StreamOwner<DMAX> stream_owner(const PredictModel &pm) {
 
 // the trees [t0, min(t0 + kStreamGroup, t_end)) (wave-uniform) on the outputs p of the lane's row: all walked, then the values of all their
 // leaves gathered, then applied tree by tree.  An output outside `cover` is skipped, not multiplied by a zero rate.
-template <int DMAX, bool GREEDY>
-__device__ __forceinline__ void stream_chain_group(const ChainModel &cm, const StreamOwner<DMAX> &own, uint64_t cover, const float *x,
+template <int DMAX, bool GREEDY, typename Row>
+__device__ __forceinline__ void stream_chain_group(const ChainModel &cm, const StreamOwner<DMAX> &own, uint64_t cover, const Row &x,
                                                    const int32_t *xc, int t0, int t_end, int vec_values, float (&p)[DMAX]) {
     constexpr int kG = kStreamGroup<DMAX>;
     const int D = cm.D;
@@ -264,6 +318,7 @@ inline bool chain_streamable(const PredictModel &pm, bool generic) { return leav
 
 constexpr size_t kStreamLdsBudget = 156 * 1024;   // the dynamic LDS the streaming kernels opt in to
 inline size_t stream_tile_bytes(int F) { return static_cast<size_t>(kStreamRows) * (F | 1) * sizeof(float); }
+inline size_t stream_code_tile_bytes(int G) { return static_cast<size_t>(kStreamRows) * ((G * 8) | 1) * sizeof(uint32_t); }
 
 // Dynamic LDS above the default 64 KiB needs an opt-in per kernel and device; one of these per kernel (a function-local static).
 // ok(): false when this device refused the opt-in and `lds` needs it -- the caller takes its general kernel.

@@ -340,6 +340,38 @@ int gbrl_hip_dataset_codes(const gbrl_hip_dataset *ds, const int32_t *rows, int 
 int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *grads, int grads_on_device, const int32_t *rows,
                            int rows_on_device, int n_rows);
 
+/* ---- the walk over a data set's bin codes (new): continue and fit without the observations ------------------------------------------ */
+/* code(r, f) = #{b : thr[f][b] < obs[r][f]} (-0.0 == +0.0; NaN below every threshold).  For a numeric condition x[f] > v whose v equals some
+ * thr[f][b] let bin = #{b : thr[f][b] < v}; then x > v <=> code > bin: if x > v, every threshold below v and v itself are below x
+ * (code >= bin + 1); if x <= v, only thresholds below v can be below x (code <= bin).  Duplicated thresholds and any order are fine; NaN has
+ * code 0 and never passes, as x > v does.  The rule does NOT hold for a v that is not one of feature f's thresholds: such a model is refused.
+ *   gbrl_hip_condition_bins(m, thresholds[F * B], F, B, out)  host only.  out has the length and indexing of feature_values
+ *     (gbrl_hip_get_ensemble); a used numeric slot (d < depths[split row]) gets its bin, every other slot -1.  F or B that are not the model's
+ *     numeric feature count and n_bins: GBRL_HIP_E_INVALID.  A used numeric condition whose value is not among its feature's thresholds (float
+ *     ==; a NaN value never is): GBRL_HIP_E_UNSUPPORTED, the message names the tree and the condition.
+ *   gbrl_hip_predict_continue_prepared(m, ds, rows, rows_on_device, n_rows, base, base_on_device, start_tree, stop_tree, out)
+ *     out[j] = base[j] carried through the trees [start_tree, stop_tree) for data set row rows[j] (rows == NULL: row j, n_rows must be n) --
+ *     BIT FOR BIT gbrl_hip_predict_continue on the observations the data set was made from, which need not exist any more.  base / out
+ *     float32 [n_rows, output_dim], `out` where `base` is (host or device); out may be base (updated in place).  Ranges as gbrl_hip_predict_continue (stop 0 =
+ *     n_trees, start == stop: out = base), rows as gbrl_hip_step_prepared.  Refused before the device is touched: what gbrl_hip_step_prepared
+ *     refuses about the model and the data set, output_dim > 128, a bad range, and (GBRL_HIP_E_UNSUPPORTED) a tree of the range with a
+ *     condition the codes cannot express -- for a greedy model also the trees a trailing one-leaf tree of the range lets the walk run into.
+ *     The model is never changed.
+ *   gbrl_hip_fit_prepared(m, ds, targets, targets_on_device, iterations, loss_out)  gbrl_hip_fit(shuffle = 0) on the data set's rows with
+ *     nothing recomputed: the running prediction of every row is held and advanced by the trees grown since its batch was last visited (one
+ *     launch, which also writes the MultiRMSE gradient), then gbrl_hip_step_prepared's body grows the tree.  targets float32 [n, output_dim].
+ *     Batches are gbrl_hip_fit's: contiguous ranges of batch_size rows in row order, wrapping to row 0; there is no shuffle (permute before
+ *     gbrl_hip_dataset_create).  A model without trees gets bias = column means of the targets and ends up BYTE FOR BYTE as gbrl_hip_fit
+ *     leaves it, with the same loss.  A model WITH trees keeps its bias and continues from all of them -- unlike gbrl_hip_fit, whose iteration
+ *     i predicts from the trees [0, i) only and which resets the bias -- and every existing tree must be expressible on the data set
+ *     (GBRL_HIP_E_UNSUPPORTED before anything changes).  Argument errors (the data set checks of gbrl_hip_step_prepared, iterations < 0, NULL
+ *     targets, batch_size <= 0) leave the model unchanged; a failure in iteration i leaves the i trees already grown, as gbrl_hip_fit does. */
+int gbrl_hip_condition_bins(const gbrl_hip_model *m, const float *thresholds /*[F*B]*/, int n_features, int n_bins, int32_t *out);
+int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
+                                       const float *base, int base_on_device, int start_tree, int stop_tree, float *out);
+int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
+                          float *loss_out);
+
 /* ---- row-sharded multi-GPU (new; the reference is single-GPU) ------------------------------------------ */
 /* One process per GPU, each holding a contiguous block of rows.  When hooks are installed, step() calls them at
  * its exchange points so that every rank grows the identical tree; predict() needs no exchange.  Buffers are
