@@ -589,7 +589,7 @@ Input read_rows(py::object &rows, const std::string &fn) {
     return r;
 }
 
-std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs) {
+std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs, py::object reference = py::none()) {
     // categorical cells cannot be prepared: their split candidates depend on the step's gradients
     bool cells = false;
     if (py::isinstance<py::array>(obs)) cells = py::array(obs).dtype().kind() == 'S';
@@ -604,7 +604,19 @@ std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs) {
     } else if (o.shape.size() == 2) { n = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]);
     } else fail("obs must have one or two dimensions");
     gbrl_hip_dataset *d = nullptr;
-    {
+    if (!reference.is_none()) {   // bound to the reference's thresholds: the width is the reference's
+        const PyDataset &ref = reference.cast<const PyDataset &>();
+        gbrl_hip_dataset_desc rd{};
+        if (gbrl_hip_dataset_info(ref.h, &rd) == GBRL_HIP_OK && n_num != rd.n_features) {
+            std::stringstream ss;
+            ss << "prepare_dataset: obs has " << n_num << " features, the reference " << rd.n_features;
+            fail(ss.str());
+        }
+        {
+            py::gil_scoped_release release;
+            d = gbrl_hip_dataset_create_like(self.h, ref.h, static_cast<const float *>(o.ptr), o.on_device, n);
+        }
+    } else {
         py::gil_scoped_release release;
         d = gbrl_hip_dataset_create(self.h, static_cast<const float *>(o.ptr), o.on_device, n, n_num);
     }
@@ -718,6 +730,41 @@ float fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, in
     }
     check(rc);
     return loss;
+}
+
+// fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0): a float without a validation
+// set (the other three at their defaults), else a dict
+py::object fit_prepared_valid_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
+                                   int early_stopping_rounds, double min_delta) {
+    if (valid_obj.is_none()) {
+        if (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0)
+            fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
+        return py::float_(fit_prepared_impl(self, ds_obj, targets, iterations));
+    }
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const gbrl_hip_dataset *dsv = valid_obj.cast<const PyDataset &>().h;
+    Input t = read_input(targets, "targets", false, "fit", false);
+    if (ds && t.ptr) check_rows_by_outputs(t, "targets", ds_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
+    Input tv = read_input(valid_targets, "valid_targets", true, "fit", false);
+    if (tv.ptr) check_rows_by_outputs(tv, "valid_targets", valid_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
+    std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0);
+    float loss = 0.0f;
+    int rc, done = 0, best = 0;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_fit_prepared_valid(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, dsv, static_cast<const float *>(tv.ptr),
+                                         tv.on_device, early_stopping_rounds, min_delta, &loss, curve.data(), &done, &best);
+    }
+    check(rc);
+    py::array_t<double> vl(static_cast<py::ssize_t>(done) + 1);
+    std::copy(curve.begin(), curve.begin() + done + 1, vl.mutable_data());
+    py::dict out;
+    out["loss"] = py::float_(loss);
+    out["valid_loss"] = vl;
+    out["iterations"] = py::int_(done);
+    out["best_n_trees"] = py::int_(best);
+    return std::move(out);
 }
 
 float fit_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, int iterations, bool shuffle,
@@ -863,6 +910,9 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     pds.def_property_readonly("n_bins", [](const PyDataset &d) { return d.info().n_bins; });
     pds.def_property_readonly("generator_type", [](const PyDataset &d) { return std::string(d.info().generator_type == GBRL_HIP_GEN_UNIFORM ? "Uniform" : "Quantile"); });
     pds.def_property_readonly("nbytes", [](const PyDataset &d) { return static_cast<size_t>(d.info().nbytes); });
+    pds.def_property_readonly("thresholds_id", [](const PyDataset &d) { return gbrl_hip_dataset_thresholds_id(d.h); },
+                              "the id of the data set the thresholds were selected for: its own for a data set made without a reference, the reference's (through "
+                              "any chain) for a bound one.  Data sets with the same id share a model's code tables, and fit_prepared(valid=) asks for it.");
     pds.def("_handle", [](const PyDataset &d) { return reinterpret_cast<uintptr_t>(d.h); }, "the gbrl_hip_dataset* of this data set (tests that call the C ABI)");
     pds.def("thresholds", [](const PyDataset &d) {
         const gbrl_hip_dataset_desc i = d.info();
@@ -906,10 +956,24 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     }, py::return_value_policy::take_ownership);
     g.def("to_device", [](PyGBRL &self, const std::string &d) { self.device = parse_device(d); }, py::arg("device"));
     g.def("step", &step_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("grads"));
-    g.def("prepare_dataset", &prepare_dataset_impl, py::arg("obs"),
-          "prepare_dataset(obs) -> PreparedDataset\n\n"
-          "The numeric preparation of step(obs, None, grads) -- key transpose, split thresholds, class codes, on step's own code paths -- done once and kept on\n"
-          "the device.  obs is not needed after the call.  Numeric columns only: categorical split candidates depend on the step's gradients.");
+    {
+        // prepare_dataset(obs) keeps its generated signature line (tools and tests compare it); the form with `reference` is a second overload
+        // described in words below that line, as the constructor's parity_mode is
+        g.def("prepare_dataset", [](PyGBRL &self, py::object &obs) { return prepare_dataset_impl(self, obs); }, py::arg("obs"));
+        const std::string sig = py::str(g.attr("prepare_dataset").attr("__doc__"));
+        const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
+            "prepare_dataset(obs, reference=None) -> PreparedDataset\n\n"
+            "The numeric preparation of step(obs, None, grads) -- key transpose, split thresholds, class codes, on step's own code paths -- done once and kept on\n"
+            "the device.  obs is not needed after the call.  Numeric columns only: categorical split candidates depend on the step's gradients.\n"
+            "reference=ds: a data set BOUND to ds's thresholds (LightGBM's Dataset(reference=train)) -- the codes of obs under them, computed in one pass over obs\n"
+            "(no transpose, no selection), with its own copies of the thresholds: ds may be destroyed afterwards.  thresholds() returns ds's bytes and\n"
+            "thresholds_id is ds's.  It is a full data set: codes(), predict_continue_prepared, step_prepared and fit_prepared work on it, a model grown on ds\n"
+            "is accepted on it, and a step on it grows with ds's thresholds.  Refused: a reference whose n_bins, generator_type, width or device is not the model's.";
+        py::options opt;
+        opt.disable_function_signatures();
+        g.def("prepare_dataset", [](PyGBRL &self, py::object &obs, py::object reference) { return prepare_dataset_impl(self, obs, reference); },
+              doc.c_str(), py::arg("obs"), py::arg("reference"));
+    }
     g.def("step_prepared", &step_prepared_impl, py::arg("ds"), py::arg("grads"), py::arg("rows") = py::none(),
           "step_prepared(ds, grads, rows=None)\n\n"
           "One boosting step on a prepared data set: with rows=None the model ends up byte for byte as step(obs, None, grads) would leave it, without the\n"
@@ -927,12 +991,28 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "predict_continue(obs[rows], None, base, start_tree_idx, stop_tree_idx) bit for bit, read from the data set's bin codes: obs need not exist any more.\n"
           "base / range / return as predict_continue (a NumPy base gives a new array, a device tuple is updated in place); rows as step_prepared.\n"
           "Every tree of the range must compare against the data set's thresholds (trees grown on it by step_prepared / fit_prepared do).");
-    g.def("fit_prepared", &fit_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("iterations"),
-          "fit_prepared(ds, targets, iterations) -> float\n\n"
-          "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
-          "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
-          "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
-          "prepare_dataset.");
+    {
+        // likewise: fit_prepared(ds, targets, iterations) -> float keeps its generated line; the validation form is the second overload
+        g.def("fit_prepared", &fit_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
+        const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
+        const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
+            "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0) -> float | dict\n\n"
+            "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
+            "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
+            "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
+            "prepare_dataset.\n"
+            "valid=dsv (a data set with ds's thresholds_id: prepare_dataset(Xv, reference=ds), or ds itself) and valid_targets: returns a dict -- 'loss' (the float\n"
+            "above), 'valid_loss' (float64 [iterations + 1]: entry k is staged_loss(Xv, None, valid_targets, stops=[T0 + k])[0] bit for bit, T0 the tree count at\n"
+            "entry, evaluated on the device after every iteration), 'iterations' (those run) and 'best_n_trees' (T0 + index of the minimum: the stop_tree_idx to\n"
+            "predict with).  Entry k improves iff valid_loss[k] < valid_loss[best] - min_delta; with early_stopping_rounds = R > 0 the loop ends after iteration k\n"
+            "when k - best >= R; R = 0 records only.  All trees grown stay in the model (no truncation), which is byte for byte what fit_prepared(ds, targets,\n"
+            "iterations run) leaves.  Refused before anything changes: another thresholds_id, valid_targets missing, early_stopping_rounds < 0, min_delta negative\n"
+            "or NaN; without valid= the other three must be at their defaults.";
+        py::options opt;
+        opt.disable_function_signatures();
+        g.def("fit_prepared", &fit_prepared_valid_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
+              py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0);
+    }
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);
     }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("return_torch") = false);

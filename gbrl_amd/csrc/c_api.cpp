@@ -541,6 +541,46 @@ int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const f
     });
 }
 
+// ---- data sets that share thresholds; validation and early stopping
+gbrl_hip_dataset *gbrl_hip_dataset_create_like(gbrl_hip_model *m, const gbrl_hip_dataset *reference, const float *obs, int obs_on_device, int n_samples) {
+    gbrl_hip_dataset *ds = nullptr;
+    g_ds_status = guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("prepare_dataset");
+        // (the registry lock is not held over the device work: destroying the reference during this call is the caller's race, as for a step)
+        std::unique_ptr<gbrl::PreparedDataset> p(m->engine.prepare_dataset_like(&live_dataset(reference), obs, obs_on_device != 0, n_samples));
+        ds = new gbrl_hip_dataset{std::move(p)};
+        std::lock_guard<std::mutex> lk(ds_registry().mu);
+        ds_registry().live.insert(ds);
+    });
+    return ds;
+}
+
+uint64_t gbrl_hip_dataset_thresholds_id(const gbrl_hip_dataset *ds) {
+    uint64_t id = 0;
+    (void)guarded([&] { id = live_dataset(ds).thresholds_id; });
+    return id;
+}
+
+int gbrl_hip_fit_prepared_valid(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
+                                const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                double min_delta, float *loss_out, double *valid_loss_out, int *iterations_done, int *best_n_trees) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_fit_prepared(targets, iterations);
+        m->engine.precheck_fit_valid(valid_targets, early_stopping_rounds, min_delta);
+        gbrl::Engine::FitValid v{&live_dataset(valid_ds), valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0};
+        const float loss = m->engine.fit_prepared_valid(&live_dataset(ds), targets, targets_on_device != 0, iterations, v);
+        if (loss_out) *loss_out = loss;
+        if (iterations_done) *iterations_done = v.done;
+        if (best_n_trees) *best_n_trees = v.best_n_trees;
+    });
+}
+
+int gbrl_hip_early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best) {
+    return guarded([&] { gbrl::Engine::early_stop_scan(curve, n, rounds, min_delta, stop_after, best); });
+}
+
 int gbrl_hip_leaf_counts_chunk(void) { return gbrl::kern::leaf_counts_chunk(); }
 
 static_assert(static_cast<int>(gbrl::Engine::ParityMode::Default) == GBRL_HIP_PARITY_DEFAULT && static_cast<int>(gbrl::Engine::ParityMode::Reference) == GBRL_HIP_PARITY_REFERENCE &&

@@ -86,7 +86,10 @@ struct NumericPrep {
 class PreparedDataset {
    public:
     int n = 0, F = 0, n_bins = 0, generator_type = 0, device = -1;
-    uint64_t id = 0;               // unique per data set of the process (a handle's address can come back): what an engine's code tables are keyed on
+    uint64_t id = 0;               // unique per data set of the process (a handle's address can come back)
+    uint64_t thresholds_id = 0;    // the id of the data set the thresholds were selected for: its own id, or -- bound to a reference
+                                   // (Engine::prepare_dataset_like), through any chain -- the reference's.  What an engine's code tables are keyed on:
+                                   // the bins of a condition depend on the thresholds and on nothing else.
     PrepBuffers buf;
     NumericPrep prep;              // pointers into buf
     std::vector<float> h_thr;      // host copy of the thresholds [F][B]
@@ -142,6 +145,12 @@ class Engine {
     // [m][D] in the order of rows.  Numeric-only, one GPU.  Every argument error is raised before the device is touched, an out-of-range index
     // before anything reads through it; after any failure the model is unchanged.
     PreparedDataset *prepare_dataset(const float *obs, bool obs_dev, int n, int n_num);
+    // Extension: a data set BOUND to another one's thresholds (LightGBM's Dataset(reference=train)).  obs [n][ref->F] is binned against the
+    // reference's threshold keys in one pass (kern::bin_like: no transpose, no selection); the result owns its codes and its own copies of the
+    // thresholds, their keys and the host thresholds -- the reference may be destroyed -- and inherits the reference's thresholds_id.  It holds
+    // no keys, no feature-major codes and no root table: a step on it hands them over as null, as a subset step does.  Refused before the
+    // device is touched: what check_prepared_dataset refuses about (model, reference), n <= 0, null obs.  The model is never changed.
+    PreparedDataset *prepare_dataset_like(const PreparedDataset *ref, const float *obs, bool obs_dev, int n);
     void step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m);
     // Extension (engine_fit_prepared.hip): the walk over a data set's bin codes.  code(r, f) = #{b : thr[f][b] < obs[r, f]}, so a numeric condition
     // x[f] > v whose v is one of thr[f][*] is code > bin with bin = #{b : thr[f][b] < v} (include/gbrl_hip.h has the argument).
@@ -161,6 +170,22 @@ class Engine {
     // A fresh model gets bias = column means of the targets; a model with trees keeps its bias and continues from ALL its trees (unlike fit()),
     // every one of which must be expressible on the data set (Unsupported before anything changes).  Returns fit()'s loss.
     float fit_prepared(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations);
+    // fit_prepared watching a validation set that shares ds's thresholds (valid->thresholds_id == ds->thresholds_id; valid may be ds).  T0 = the
+    // tree count at entry (a fresh model: after the bias is set).  valid_loss_out[k], k = 0 .. done, is the MultiRMSE of the first T0 + k trees
+    // on the validation rows -- staged_loss's expression and summation order, bit for bit -- from a prediction held on the device and advanced
+    // after EVERY iteration by one launch that also writes the loss partials.  rounds > 0: the loop ends after iteration k when k - best >=
+    // rounds (early_stop_scan's rule); rounds == 0: record only.  All trees grown stay; the model after `done` iterations is byte for byte
+    // what fit_prepared(ds, targets, done) leaves, and the returned loss is its return value.  Refused before anything changes: another
+    // thresholds id, null valid targets, rounds < 0, min_delta negative or NaN, and what fit_prepared refuses.
+    struct FitValid {
+        const PreparedDataset *ds; const float *targets; bool targets_dev; int rounds; double min_delta;
+        double *loss_out /*[iterations + 1]*/; int done, best_n_trees;
+    };
+    float fit_prepared_valid(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid &v);
+    // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
+    // min_delta (a NaN never improves); *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = best at that point
+    static void early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
+    void precheck_fit_valid(const float *valid_targets, int rounds, double min_delta) const;
     // what the two calls above refuse without looking at the data set, in their order (the C ABI runs it before it resolves the handle, so that
     // these refusals do not depend on a data set being at hand): the model checks of step_prepared, then fit_prepared's own arguments
     void precheck_prepared(const char *what) const { check_prepared_model(what); }
@@ -315,8 +340,10 @@ class Engine {
     // step_prepared behind its argument checks and input staging: statistics, growth, append on device gradients and (nullable) device rows
     void step_prepared_run(const PreparedDataset *ds, const float *dgrads, const int32_t *d_rows, int m);
     void begin_step_profile();   // a step's phase list starts here
-    // ---- conditions as bin indices of ONE data set (engine_fit_prepared.hip): host tables appended split row by split row, their device copies
-    // appended behind sync_model_to_device().  Dropped when another data set is named or the ensemble has shrunk.
+    // ---- conditions as bin indices of ONE threshold table (engine_fit_prepared.hip): host tables appended split row by split row, their device
+    // copies appended behind sync_model_to_device().  Keyed on the data set's thresholds_id: data sets that share thresholds share the tables
+    // (a fit that alternates between a training and a validation set appends the new trees' rows only).  Dropped when a data set with other
+    // thresholds is named or the ensemble has shrunk.
     void sync_code_bins(const PreparedDataset &ds);                      // host only: code_bins_host_ covers every split row of the model
     void check_code_range(const PreparedDataset &ds, const char *what, int start_tree, int stop_tree);   // Unsupported: an inexpressible condition the walk of the range reads
     kern::CodeTables sync_code_tables(const PreparedDataset &ds);        // device: needs sync_model_to_device()
@@ -387,11 +414,17 @@ class Engine {
     size_t leafacc_clean_bytes_ = 0;
     PrepBuffers prep_ws_;             // step()'s numeric preparation; step_prepared(rows) gathers the subset's codes into prep_ws_.codes
     DevBuf d_sub_rows_, d_rows_mm_;   // step_prepared(rows): device copy of a host index vector, min / max of a device one
-    uint64_t code_ds_id_ = 0;         // the data set the code tables below are for (0: none)
+    uint64_t code_ds_id_ = 0;         // the thresholds id the code tables below are for (0: none)
     size_t code_splits_ = 0, code_up_splits_ = 0, code_nodes_ = 0, code_up_nodes_ = 0;   // split rows / greedy node records converted on the host, and on the device
     std::vector<int32_t> code_bins_host_, code_pack_host_, code_nodes_host_;   // bins [S][MD] (-1 unused or categorical, -2 inexpressible), cond_pack and grd_nodes with the bin as their second word
     DevBuf m_code_bins_, m_code_pack_, m_code_nodes_;
     DevBuf d_fp_pred_, d_fp_grads_, d_fp_iota_, d_fp_targets_;   // fit_prepared: held prediction [n][D], batch gradients, 0..n-1, staged targets
+    DevBuf d_fp_vpred_, d_fp_vtargets_, d_fp_vpart_, d_fp_vsums_;   // its validation rows: held prediction [n_v][D], staged targets, loss partials, one sum per iteration
+    float fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v);
+    // rows [start, start + bn) of a data set's held prediction P (valid through `through` trees) advanced to every tree the model has, with the
+    // gradient tail (targets, grad_out) and / or the loss tail (loss_targets, loss_part) of kern::predict_continue_codes; targets are [n][D]
+    void advance_held(const PreparedDataset &ds, float *P, int &through, int start, int bn, const float *targets, float *grad_out,
+                      const float *loss_targets, double *loss_part, bool generic);
     DevBuf d_am_s_, d_near_list_, d_near_ent_, d_near_rep_, d_near_nr_, d_near_maps_, d_near_pos_, d_near_nrb_, d_near_vals_, d_near_means_, d_near_sums_, d_near_chains_, d_near_rowsort_, d_near_tiles_;   // near-tie replay (kern::near_tie_replay): runner-up per arg-max block, candidate lists, ordered row lists, replayed scores
     bool small_grow_off_ = false;     // latched after a failed launch / an abandoned grid barrier of the one-launch kernel: this engine keeps to the level loop
     long long small_grow_fallbacks_ = 0;   // trees the level loop grew after such a failure (diagnostics)

@@ -5,6 +5,8 @@
 //                                      their second word (appended like the originals: a loop that adds a tree per iteration converts that tree only)
 //   Engine::predict_continue_prepared  predict_continue without the observations (kern::predict_continue_codes)
 //   Engine::fit_prepared               fit()'s loop with the running prediction held and the batch never binned again
+//   Engine::fit_prepared_valid         the same loop watching a validation set that shares the thresholds: a second held prediction advanced after
+//                                      every iteration (advance_held, the loss tail of the code walk), Engine::early_stop_scan's rule
 //
 // The rule.  code(r, f) = #{b : thr[f][b] < obs[r, f]} (-0.0 == +0.0; NaN lies below every threshold: code 0).  For a condition x > v whose v
 // equals some thr[f][b] let bin = #{b : thr[f][b] < v}.  x > v: every threshold below v, and v itself, is below x, so code >= bin + 1.
@@ -72,8 +74,8 @@ void Engine::condition_bins(const float *thresholds, int F, int B, int32_t *out)
 
 void Engine::sync_code_bins(const PreparedDataset &ds) {
     const size_t S = model.split_rows(), MD = model.meta.max_depth;
-    if (code_ds_id_ != ds.id || code_splits_ > S) {   // another data set, or the ensemble has shrunk: nothing of the tables is kept
-        code_ds_id_ = ds.id;
+    if (code_ds_id_ != ds.thresholds_id || code_splits_ > S) {   // other thresholds, or the ensemble has shrunk: nothing of the tables is kept
+        code_ds_id_ = ds.thresholds_id;
         code_splits_ = code_up_splits_ = code_nodes_ = code_up_nodes_ = 0;
         code_bins_host_.clear(); code_pack_host_.clear(); code_nodes_host_.clear();
     }
@@ -183,7 +185,7 @@ void Engine::predict_continue_prepared(const PreparedDataset *ds, const int32_t 
     }
     phase_end("inputs"); phase_begin(/*key=*/true);
     kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, start_tree, stop, dbase, dout,
-                                 nullptr, nullptr, hooks::on(hooks::CONTINUE_GENERIC), stream_);
+                                 nullptr, nullptr, nullptr, nullptr, hooks::on(hooks::CONTINUE_GENERIC), stream_);
     finish("predict_continue_prepared launch", "predict", {{out_dev ? nullptr : out, dout, out_bytes, "D2H preds"}});
 }
 
@@ -198,21 +200,75 @@ void Engine::precheck_fit_prepared(const float *targets, int iterations) const {
     if (md.output_dim > 128) throw Unsupported("predict: output_dim > 128");
 }
 
+void Engine::precheck_fit_valid(const float *valid_targets, int rounds, double min_delta) const {
+    if (valid_targets == nullptr) throw InvalidArgument("fit_prepared: a validation set needs valid_targets");
+    if (rounds < 0) throw InvalidArgument("fit_prepared: early_stopping_rounds must be >= 0");
+    if (!(min_delta >= 0.0)) throw InvalidArgument("fit_prepared: min_delta must be >= 0 (and not NaN)");
+}
+
+void Engine::early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best) {
+    if (curve == nullptr || stop_after == nullptr || best == nullptr) throw InvalidArgument("early_stop_scan: null argument");
+    if (n <= 0) throw InvalidArgument("early_stop_scan: an empty curve");
+    if (rounds < 0) throw InvalidArgument("early_stop_scan: rounds must be >= 0");
+    if (!(min_delta >= 0.0)) throw InvalidArgument("early_stop_scan: min_delta must be >= 0 (and not NaN)");
+    int b = 0, k = 1;
+    for (; k < n; ++k) {
+        if (curve[k] < curve[b] - min_delta) b = k;   // (false for a NaN on either side)
+        if (rounds > 0 && k - b >= rounds) break;
+    }
+    *stop_after = k < n ? k : n - 1;
+    *best = b;
+}
+
+// P[start .. start + bn) of a data set's held prediction from `through` trees to every tree the model has; with targets, g = P - y for those rows in
+// the same pass; with loss_targets, the loss partials of the new P (bn rows, from partial 0).  A walk that ended in a trailing run of one-leaf
+// greedy trees applied nothing for them (it ran off the ensemble): it resumes at the first of them.
+void Engine::advance_held(const PreparedDataset &ds, float *P, int &through, int start, int bn, const float *targets, float *grad_out,
+                          const float *loss_targets, double *loss_part, bool generic) {
+    const int T = model.meta.n_trees, D = model.meta.output_dim;
+    int from = through;
+    while (from > 0 && runs_on(model, from - 1)) --from;
+    check_code_range(ds, "fit_prepared", from, T);
+    sync_model_to_device();
+    const kern::CodeTables ct = sync_code_tables(ds);
+    float *p = P + static_cast<size_t>(start) * D;
+    const size_t at = static_cast<size_t>(start) * D;
+    kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{ds.prep.d_codes, ds.n, ds.code_groups(), nullptr, start}, bn, from, T, p, p,
+                                 targets ? targets + at : nullptr, grad_out, loss_targets ? loss_targets + at : nullptr, loss_part, generic, stream_);
+    through = T;
+}
+
 float Engine::fit_prepared(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations) {
+    return fit_prepared_loop(ds, targets, targets_dev, iterations, nullptr);
+}
+
+float Engine::fit_prepared_valid(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid &v) {
+    return fit_prepared_loop(ds, targets, targets_dev, iterations, &v);
+}
+
+float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v) {
     gbrl_hip_metadata &md = model.meta;
     precheck_fit_prepared(targets, iterations);
+    if (v) precheck_fit_valid(v->targets, v->rounds, v->min_delta);
     check_prepared_dataset("fit_prepared", ds);
+    if (v) {
+        check_prepared_dataset("fit_prepared", v->ds);
+        if (v->ds->thresholds_id != ds->thresholds_id)
+            throw InvalidArgument("fit_prepared: the validation set does not share the training set's thresholds (create it with prepare_dataset(obs, reference=ds))");
+        if (v->loss_out == nullptr) throw InvalidArgument("fit_prepared: no place for the validation losses");
+    }
     const bool fresh = md.n_trees == 0;
     if (!fresh) check_code_range(*ds, "fit_prepared", 0, md.n_trees);   // a warm start continues from every tree the model has
     ensure_device();
     hipStream_t s = stream_;
     const int n = ds->n, D = md.output_dim;
-    const float *dtar = targets;
-    if (!targets_dev) {
-        float *t = static_cast<float *>(d_fp_targets_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
-        hip_check(hipMemcpyAsync(t, targets, sizeof(float) * static_cast<size_t>(n) * D, hipMemcpyHostToDevice, s), "H2D targets");
-        dtar = t;
-    }
+    auto staged = [&](DevBuf &buf, const float *host_or_dev, bool on_dev, int rows) -> const float * {
+        if (on_dev) return host_or_dev;
+        float *t = static_cast<float *>(buf.ensure(sizeof(float) * static_cast<size_t>(rows) * D));
+        hip_check(hipMemcpyAsync(t, host_or_dev, sizeof(float) * static_cast<size_t>(rows) * D, hipMemcpyHostToDevice, s), "H2D targets");
+        return t;
+    };
+    const float *dtar = staged(d_fp_targets_, targets, targets_dev, n);
     // column sums and the loss: Engine::fit's own expressions (engine_step.hip)
     float *d_zero = static_cast<float *>(d_fit_zero_.ensure(sizeof(float) * D));
     hip_check(hipMemsetAsync(d_zero, 0, sizeof(float) * D, s), "memset");
@@ -256,21 +312,35 @@ float Engine::fit_prepared(const PreparedDataset *ds, const float *targets, bool
         d_iota = d;
     }
     const bool generic = hooks::on(hooks::CONTINUE_GENERIC);
-    // P[start .. start + bn) from the batch's count to every tree the model has, and g = P - y for those rows in the same pass.  A walk that
-    // ended in a trailing run of one-leaf greedy trees applied nothing for them (it ran off the ensemble): it resumes at the first of them.
-    auto advance = [&](int start, int bn, float *grad_out) {
-        const int T = md.n_trees;
-        int from = through[start / bs];
-        while (from > 0 && runs_on(model, from - 1)) --from;
-        check_code_range(*ds, "fit_prepared", from, T);
-        sync_model_to_device();
-        const kern::CodeTables ct = sync_code_tables(*ds);
-        float *p = P + static_cast<size_t>(start) * D;
-        kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{ds->prep.d_codes, n, ds->code_groups(), nullptr, start}, bn, from, T, p, p,
-                                     dtar + static_cast<size_t>(start) * D, grad_out, generic, s);
-        through[start / bs] = T;
+    auto advance = [&](int start, int bn, float *grad_out) { advance_held(*ds, P, through[start / bs], start, bn, dtar, grad_out, nullptr, nullptr, generic); };
+    // ---- the validation rows: a held prediction of their own, evaluated after every iteration by one launch + the finishing sum
+    const int T0 = md.n_trees;
+    const int nv = v ? v->ds->n : 0, nbv = v ? kern::staged_loss_partials(nv) : 0;
+    const float *dvtar = nullptr;
+    float *Pv = nullptr;
+    double *d_vpart = nullptr, *d_vsums = nullptr;
+    int through_v = 0, best = 0;
+    auto curve_of = [&](double sum) { return std::sqrt(0.5 * sum / static_cast<double>(nv)); };   // staged_loss's expression
+    auto evaluate = [&](int k) {   // valid_loss[k]: on the device; with a stopping rule also on the host (one 8-byte read-back)
+        advance_held(*v->ds, Pv, through_v, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic);
+        kern::staged_loss_finish(d_vpart, nbv, d_vsums + k, s);
+        if (v->rounds > 0) {
+            double sum = 0.0;
+            hip_check(hipMemcpyAsync(&sum, d_vsums + k, sizeof(double), hipMemcpyDeviceToHost, s), "D2H validation loss");
+            hip_check(hipStreamSynchronize(s), "sync");
+            v->loss_out[k] = curve_of(sum);
+        }
     };
-    int start = 0;
+    if (v) {
+        dvtar = staged(d_fp_vtargets_, v->targets, v->targets_dev, nv);
+        Pv = static_cast<float *>(d_fp_vpred_.ensure(sizeof(float) * static_cast<size_t>(nv) * D));
+        d_vpart = static_cast<double *>(d_fp_vpart_.ensure(sizeof(double) * nbv));
+        d_vsums = static_cast<double *>(d_fp_vsums_.ensure(sizeof(double) * (static_cast<size_t>(iterations) + 1)));
+        kern::tile_rows(m_bias_.as<float>(), D, nv, Pv, s);
+        v->done = 0; v->best_n_trees = T0;
+        evaluate(0);
+    }
+    int start = 0, done = 0;
     int bn = start + bs < n ? bs : n - start;                                   // fitter.cpp:120
     for (int i = 0; i < iterations; ++i) {
         begin_step_profile();
@@ -281,6 +351,27 @@ float Engine::fit_prepared(const PreparedDataset *ds, const float *targets, bool
         start += bn;                                                            // fitter.cpp:228-231
         if (start >= n) start = 0;
         bn = start + bs < n ? bs : n - start;
+        done = i + 1;
+        if (v) {
+            v->done = done;
+            evaluate(done);
+            if (v->rounds > 0) {
+                int stop_after = 0;
+                early_stop_scan(v->loss_out, done + 1, v->rounds, v->min_delta, &stop_after, &best);
+                if (done - best >= v->rounds) break;
+            }
+        }
+    }
+    if (v) {
+        if (v->rounds == 0) {   // the sums stayed on the device
+            std::vector<double> sums(static_cast<size_t>(done) + 1);
+            hip_check(hipMemcpyAsync(sums.data(), d_vsums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, s), "D2H validation losses");
+            hip_check(hipStreamSynchronize(s), "sync");
+            for (int k = 0; k <= done; ++k) v->loss_out[k] = curve_of(sums[k]);
+        }
+        int stop_after = 0;
+        early_stop_scan(v->loss_out, done + 1, v->rounds, v->min_delta, &stop_after, &best);
+        v->best_n_trees = T0 + best;
     }
     // every batch to the end; the loss on the whole data set (fitter.cpp:246-251)
     for (int b0 = 0; b0 < n; b0 += bs) advance(b0, std::min(bs, n - b0), G + static_cast<size_t>(b0) * D);

@@ -1,6 +1,7 @@
 // engine_prepared.hip -- a batch binned once and stepped on many times (see engine.h, PreparedDataset):
 //   Engine::prepare_dataset   the numeric preparation of step() (Engine::prepare_numeric, engine_step.hip: key transpose, thresholds, class codes,
 //                             the fused kern::small_prep with want_stats = false) into buffers the data set owns
+//   Engine::prepare_dataset_like   a data set bound to another one's thresholds: kern::bin_like on the new rows, copies of the thresholds
 //   Engine::step_prepared     gradient statistics (Engine::run_grad_stats), the GrowCtx from the data set, grow_tree, append_tree -- no transpose,
 //                             no candidates, no binning.  A row subset gathers the subset's 32-byte code records (kern::gather_code_records) into
 //                             the engine's workspace and grows on them with the DATA SET'S thresholds; keys, feature-major codes and the root's
@@ -23,6 +24,51 @@ void Engine::check_prepared_model(const char *what) const {
         throw Unsupported(std::string(what) + ": not available on a model with categorical columns (their split candidates depend on the step's gradients)");
 }
 
+namespace {
+uint64_t next_dataset_id() {
+    static std::atomic<uint64_t> next_id{1};
+    return next_id.fetch_add(1, std::memory_order_relaxed);
+}
+}  // namespace
+
+// A data set bound to `ref`'s thresholds: the codes of obs under them (kern::bin_like), own copies of the thresholds, their keys and the host
+// thresholds.  No keys, no feature-major codes, no root table: the growth paths take them as null (step_prepared_run).
+PreparedDataset *Engine::prepare_dataset_like(const PreparedDataset *ref, const float *obs, bool obs_dev, int n) {
+    check_prepared_dataset("prepare_dataset", ref);
+    if (n <= 0 || obs == nullptr) throw InvalidArgument("Cannot call prepare_dataset without obs!");
+    ensure_device();
+    ev_used_ = 0;
+    ev_names_.clear();
+    hipStream_t s = stream_;
+    const int N = n, F = ref->F, B = ref->n_bins;
+    std::unique_ptr<PreparedDataset> ds(new PreparedDataset());
+    ds->n = N; ds->F = F; ds->n_bins = B; ds->generator_type = ref->generator_type; ds->device = device_ordinal_;
+    ds->id = next_dataset_id();
+    ds->thresholds_id = ref->thresholds_id;
+    ds->h_thr = ref->h_thr;
+    phase_begin();
+    const float *dobs = obs;
+    if (!obs_dev) {
+        dobs = static_cast<float *>(d_obs_.ensure(sizeof(float) * static_cast<size_t>(N) * F));
+        hip_check(hipMemcpyAsync(const_cast<float *>(dobs), obs, sizeof(float) * static_cast<size_t>(N) * F, hipMemcpyHostToDevice, s), "H2D obs");
+    }
+    const size_t n_thr = static_cast<size_t>(F) * B;
+    float *d_thr = static_cast<float *>(ds->buf.thr.ensure(sizeof(float) * n_thr));
+    uint32_t *d_thrkeys = static_cast<uint32_t *>(ds->buf.thrkeys.ensure(sizeof(uint32_t) * n_thr));
+    hip_check(hipMemcpyAsync(d_thr, ref->prep.d_thr, sizeof(float) * n_thr, hipMemcpyDeviceToDevice, s), "D2D thr");
+    hip_check(hipMemcpyAsync(d_thrkeys, ref->prep.d_thrkeys, sizeof(uint32_t) * n_thr, hipMemcpyDeviceToDevice, s), "D2D thr keys");
+    phase_end("inputs"); phase_begin(/*key=*/true);
+    const size_t G = static_cast<size_t>(ds->code_groups());
+    uint16_t *d_codes = static_cast<uint16_t *>(ds->buf.codes.ensure(sizeof(uint16_t) * G * N * kern::kCodeGroup));
+    kern::bin_like(dobs, N, F, d_thrkeys, B, d_codes, s);
+    hip_check(hipGetLastError(), "bin_like launch");
+    phase_end("bin_like", /*key=*/true);
+    hip_check(hipStreamSynchronize(s), "sync");   // the caller's obs and the reference are not needed from here on
+    phases_resolve();
+    ds->prep.d_thr = d_thr; ds->prep.d_thrkeys = d_thrkeys; ds->prep.d_codes = d_codes;
+    return ds.release();
+}
+
 PreparedDataset *Engine::prepare_dataset(const float *obs, bool obs_dev, int n, int n_num) {
     const gbrl_hip_metadata &md = model.meta;
     check_prepared_model("prepare_dataset");
@@ -43,8 +89,7 @@ PreparedDataset *Engine::prepare_dataset(const float *obs, bool obs_dev, int n, 
     const int N = n, F = n_num, B = md.n_bins;
     std::unique_ptr<PreparedDataset> ds(new PreparedDataset());
     ds->n = N; ds->F = F; ds->n_bins = B; ds->generator_type = md.generator_type; ds->device = device_ordinal_;
-    static std::atomic<uint64_t> next_id{1};
-    ds->id = next_id.fetch_add(1, std::memory_order_relaxed);
+    ds->id = ds->thresholds_id = next_dataset_id();
     phase_begin();
     const float *dobs = obs;
     if (!obs_dev) {

@@ -193,6 +193,10 @@ constexpr int kCodeGroup = 16;  // code layout: groups of 16 feature slots, [gro
 // 16 bytes per lane.  Every rows[j] must lie in [0, n): the caller checks (a host vector on the host, a device vector with rows_minmax).
 void gather_code_records(const uint16_t *codes /*[n_groups][n][16]*/, int n, int n_groups /*<= 65535*/, const int32_t *rows /*[m], device*/, int m,
                          uint16_t *out /*[n_groups][m][16]*/, hipStream_t s);
+// rows binned against thresholds that already exist (bin_like.hip): codes[g][r][fl] = min(B, #{b : thr_keys[f][b] < float_to_key(obs[r][f])}),
+// f = 16 g + fl, padding slots (f >= F) zero -- bin_cols' records from row-major float32 obs [n][F] in one pass, no transposed key copy.
+// thr_keys [F][B] ascending per feature.  The keys of a group are searched in LDS while 16 * B * 4 bytes fit the opt-in, else in global memory.
+void bin_like(const float *obs, int n, int F, const uint32_t *thr_keys, int B, uint16_t *codes /*[ceil(F/16)][n][16]*/, hipStream_t s);
 // mm[0] = min rows[j], mm[1] = min ~rows[j] (= ~max) of a device index vector, m >= 1
 void rows_minmax(const int32_t *rows, int m, int32_t *mm /*[2], device*/, hipStream_t s);
 
@@ -570,11 +574,14 @@ void predict_continue(const PredictModel &pm, const float *obs, int F, const int
 //   CodeRows    the rows to walk: row j of the call is data set row rows[row0 + j] (rows != nullptr, device, every entry in [0, n_rows)) or
 //               row0 + j; codes [groups][n_rows][16] u16
 // base / out (may be the same buffer) / targets / grad_out are device [m][D], indexed by j.  targets != nullptr: grad_out = fl32(out - targets)
-// of the new out in the same pass (kern::sub_arrays' bits).  generic: the one-thread-per-row kernel only.  Always launches (m > 0).
+// of the new out in the same pass (kern::sub_arrays' bits).  loss_targets != nullptr (device [m][D], independent of the gradient tail):
+// loss_part[j / 64] = the wave's sum of the rows' sum_d (double)fl32(out - loss_targets)^2 for the new out -- the partials
+// loss_partials_of_predictions writes for these predictions (staged_loss_partials(m) doubles; staged_loss_finish sums them).
+// generic: the one-thread-per-row kernel only.  Always launches (m > 0).
 struct CodeTables { const int32_t *bins, *cond_pack, *grd_nodes; };
 struct CodeRows { const uint16_t *codes; int n_rows, groups; const int32_t *rows; int row0; };
 void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
-                            float *out, const float *targets, float *grad_out, bool generic, hipStream_t s);
+                            float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic, hipStream_t s);
 void tile_rows(const float *row /*[D], device*/, int D, int n, float *out /*[n][D]*/, hipStream_t s);   // out[r] = row: fit_prepared's held prediction starts as the bias
 // Every prefix [0, stops[s]) of the ensemble in one walk (predict_staged.hip): stage s has the bits of predict_continue(tiled bias, 0, stops[s]);
 // stops[s] == 0 is the bias alone.  `stops` is a device array, strictly ascending, 0 <= stops[s] <= n_trees (the caller has checked);
@@ -589,6 +596,9 @@ void predict_staged(const PredictModel &pm, const float *obs, int F, const int32
 // The loss stage of predict_staged for predictions the caller already holds (device [n][D]): *sum = what sums[s] is for a stage with these
 // bits -- the same row sums, butterflies and finishing tree.  part: scratch for staged_loss_partials(n) doubles.
 void staged_loss_of_predictions(const float *preds, const float *targets, int n, int D, double *part, double *sum, hipStream_t s);
+// its two halves: the partials alone (one per 64 consecutive rows), and the finishing sum of nb partials that any of the loss kernels wrote
+void loss_partials_of_predictions(const float *preds, const float *targets, int n, int D, double *part, hipStream_t s);
+void staged_loss_finish(const double *part, int nb, double *sum, hipStream_t s);
 // Where a row lands (predict_leaves.hip): the GLOBAL leaf index -- the row of `values` -- that each tree of [start_tree, stop_tree) routes a row to.
 // Oblivious: tree_indices[t] + the bits of the tree's conditions.  Greedy: the first leaf in storage order from tree_indices[t] on whose conditions
 // all hold; a depth-0 leaf never passes (Q7), and -1 when the search runs off the ensemble.  No leaf value is read: no limit on output_dim.

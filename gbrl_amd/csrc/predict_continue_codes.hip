@@ -12,9 +12,15 @@
 //                             tree, F too wide for the tile, a refused LDS opt-in, and the cross-check behind GBRL_HIP_CONTINUE_GENERIC=1.
 //   fused tail                targets != nullptr: grad_out[j][d] = fl32(out[j][d] - targets[j][d]) for the NEW out -- one float32 subtraction,
 //                             kern::sub_arrays' bits -- in the same pass (fit_prepared's MultiRMSE gradient).
+//   loss tail                 loss_targets != nullptr: the row's sum_d (double)fl32(out - y)^2 for the NEW out, reduced over the wave's 64 rows by
+//                             predict_loss.h's butterfly and written to loss_part[j / 64] -- what k_loss_of_predictions writes for these
+//                             predictions, without the second pass over them (fit_prepared's validation rows).  The streaming kernel's block is
+//                             one wave (kStreamRows == kStagedRows): one partial per block; the general kernel's four waves write four.  The two
+//                             tails are independent options.
 #include "kernels.h"
 #include "kernels_common.h"
 #include "predict_rowwalk.h"
+#include "predict_loss.h"
 
 namespace gbrl {
 namespace kern {
@@ -32,30 +38,42 @@ __global__ __launch_bounds__(256) void k_tile_rows(const float *__restrict__ row
 // ------------------------------------------------------------------------------------------------------------ general kernel
 template <int DMAX>
 __global__ __launch_bounds__(256) void k_continue_codes_general(ChainModel cm, CodeRows cr, int m, int start_tree, int stop_tree, const float *base, float *out,
-                                                                const float *__restrict__ targets, float *__restrict__ grad_out) {
+                                                                const float *__restrict__ targets, float *__restrict__ grad_out,
+                                                                const float *__restrict__ loss_targets, double *__restrict__ loss_part, int loss_nb) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= m) return;
+    const bool live = j < m;
+    if (!live && loss_targets == nullptr) return;   // (with the loss tail whole waves stay for the butterfly)
     const int D = cm.D;
     float p[DMAX];
+    if (live) {
 #pragma unroll
-    for (int d = 0; d < DMAX; ++d) p[d] = d < D ? base[static_cast<size_t>(j) * D + d] : 0.0f;
-    const size_t src = static_cast<size_t>(cr.rows ? cr.rows[cr.row0 + j] : cr.row0 + j);
-    const GeneralCodeRow r{cr.codes + src * kCodeGroup, static_cast<size_t>(cr.n_rows) * kCodeGroup};
-    for (int t = start_tree; t < stop_tree; ++t)
-        if (!general_chain_tree<DMAX>(cm, r, t, p)) break;   // a greedy search ran off the ensemble: the walk ends
+        for (int d = 0; d < DMAX; ++d) p[d] = d < D ? base[static_cast<size_t>(j) * D + d] : 0.0f;
+        const size_t src = static_cast<size_t>(cr.rows ? cr.rows[cr.row0 + j] : cr.row0 + j);
+        const GeneralCodeRow r{cr.codes + src * kCodeGroup, static_cast<size_t>(cr.n_rows) * kCodeGroup};
+        for (int t = start_tree; t < stop_tree; ++t)
+            if (!general_chain_tree<DMAX>(cm, r, t, p)) break;   // a greedy search ran off the ensemble: the walk ends
 #pragma unroll
-    for (int d = 0; d < DMAX; ++d)
-        if (d < D) {
-            out[static_cast<size_t>(j) * D + d] = p[d];
-            if (targets != nullptr) grad_out[static_cast<size_t>(j) * D + d] = __fsub_rn(p[d], targets[static_cast<size_t>(j) * D + d]);
-        }
+        for (int d = 0; d < DMAX; ++d)
+            if (d < D) {
+                out[static_cast<size_t>(j) * D + d] = p[d];
+                if (targets != nullptr) grad_out[static_cast<size_t>(j) * D + d] = __fsub_rn(p[d], targets[static_cast<size_t>(j) * D + d]);
+            }
+    }
+    if (loss_targets != nullptr) {
+        double acc = 0.0;
+        if (live) acc = staged_row_loss<DMAX>(p, loss_targets + static_cast<size_t>(j) * D, D);
+        acc = staged_wave_sum(acc);
+        const int wave = j / kStagedRows;   // 256 = 4 x 64: a wave holds the rows of one partial
+        if ((threadIdx.x & (kStagedRows - 1)) == 0 && wave < loss_nb) loss_part[wave] = acc;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------ streaming kernel
 template <int DMAX, bool GREEDY>
 __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, StreamOwner<DMAX> own, uint64_t cover, CodeRows cr, int m, int start_tree,
                                                                 int stop_tree, const float *base, float *out, const float *__restrict__ targets,
-                                                                float *__restrict__ grad_out, int vec_values, int vec_io, int vec_grad) {
+                                                                float *__restrict__ grad_out, const float *__restrict__ loss_targets,
+                                                                double *__restrict__ loss_part, int vec_values, int vec_io, int vec_grad, int vec_loss) {
     extern __shared__ __align__(16) uint32_t cctile[];   // [kStreamRows][stream_code_stride(G)]
     const int lane = threadIdx.x;
     const int D = cm.D;
@@ -87,11 +105,22 @@ __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, S
             stream_store_row<DMAX>(grad_out + row * D, D, vec_grad != 0, y);
         }
     }
+    if (loss_targets != nullptr) {   // (block-uniform; the block is one wave: one partial)
+        double acc = 0.0;
+        if (live) {
+            float y[DMAX];
+            stream_load_row<DMAX>(loss_targets + row * D, D, vec_loss != 0, y);
+            acc = staged_row_loss<DMAX>(p, y, D);
+        }
+        acc = staged_wave_sum(acc);
+        if (lane == 0) loss_part[blockIdx.x] = acc;
+    }
 }
 
 template <int DMAX, bool GREEDY>
 bool launch_continue_codes(const ChainModel &cm, const PredictModel &pm, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
-                           float *out, const float *targets, float *grad_out, hipStream_t s) {
+                           float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, hipStream_t s) {
+    static_assert(kStreamRows == kStagedRows, "a block of the streaming kernel writes exactly one loss partial");
     const size_t lds = stream_code_tile_bytes(cr.groups);
     if (lds > kStreamLdsBudget) return false;   // rows too wide for an LDS tile
     static StreamLdsOptIn optin;
@@ -100,8 +129,10 @@ bool launch_continue_codes(const ChainModel &cm, const PredictModel &pm, const C
     const int vec_values = d4 && (reinterpret_cast<uintptr_t>(pm.values) & 15) == 0;
     const int vec_io = d4 && ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     const int vec_grad = d4 && ((reinterpret_cast<uintptr_t>(targets) | reinterpret_cast<uintptr_t>(grad_out)) & 15) == 0;
+    const int vec_loss = d4 && (reinterpret_cast<uintptr_t>(loss_targets) & 15) == 0;
     hipLaunchKernelGGL((k_continue_codes<DMAX, GREEDY>), dim3((m + kStreamRows - 1) / kStreamRows), dim3(kStreamRows), lds, s, cm, stream_owner<DMAX>(pm),
-                       pm.coef_cover, cr, m, start_tree, stop_tree, base, out, targets, grad_out, vec_values, vec_io, vec_grad);
+                       pm.coef_cover, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, vec_values, vec_io, vec_grad,
+                       vec_loss);
     return true;
 }
 
@@ -114,7 +145,8 @@ void tile_rows(const float *row, int D, int n, float *out, hipStream_t s) {
 }
 
 void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
-                            float *out, const float *targets, float *grad_out, bool generic, hipStream_t s) {
+                            float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
+                            hipStream_t s) {
     if (m <= 0) return;
     if (stop_tree <= start_tree || pm.n_opts <= 0) {   // no tree to apply, or no optimizer that owns an output: the base as it is
         const size_t n_el = static_cast<size_t>(m) * pm.D;
@@ -123,6 +155,7 @@ void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const 
             const unsigned blocks = static_cast<unsigned>(std::min<size_t>((n_el + 255) / 256, 4096));
             hipLaunchKernelGGL(k_sub_rows, dim3(blocks), dim3(256), 0, s, out, targets, grad_out, n_el);
         }
+        if (loss_targets != nullptr) loss_partials_of_predictions(out, loss_targets, m, pm.D, loss_part, s);
         return;
     }
     // the model view of the float walk with the threshold words replaced by bins (the packed conditions, the greedy node records, the general table)
@@ -132,13 +165,13 @@ void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const 
     cm.walk.feature_bins = ct.bins;
     if (chain_streamable(pm, generic) && with_stream_dmax(pm.D, [&](auto dmax) {
             constexpr int DMAX = decltype(dmax)::value;
-            return pm.oblivious ? launch_continue_codes<DMAX, false>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, s)
-                                : launch_continue_codes<DMAX, true>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, s);
+            return pm.oblivious ? launch_continue_codes<DMAX, false>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, s)
+                                : launch_continue_codes<DMAX, true>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, s);
         }))
         return;
     with_general_dmax(pm.D, [&](auto dmax) {
         hipLaunchKernelGGL((k_continue_codes_general<decltype(dmax)::value>), dim3((m + 255) / 256), dim3(256), 0, s, cm, cr, m, start_tree, stop_tree, base,
-                           out, targets, grad_out);
+                           out, targets, grad_out, loss_targets, loss_part, staged_loss_partials(m));
     });
 }
 

@@ -21,11 +21,12 @@
 //                     the same bytes through either.  Also the cross-check behind GBRL_HIP_STAGED_GENERIC=1.
 //   k_staged_finish   one block per stage: part[s][0 .. nb) summed in a fixed order (a strided serial sum per thread, then a fixed LDS tree).
 //                     No floating-point atomics anywhere: two identical calls return identical bytes.
-// This file keeps the checkpoints, the loss butterfly, k_staged_finish and k_loss_of_predictions; the model view, both walks, the family
+// This file keeps the checkpoints, k_staged_finish and k_loss_of_predictions (the row sum and the butterfly are predict_loss.h's); the model view, both walks, the family
 // choice and the LDS opt-in are predict_rowwalk.h's, shared with predict_continue.hip, predict_leaves.hip and refit.hip.
 #include "kernels.h"
 #include "kernels_common.h"
 #include "predict_rowwalk.h"
+#include "predict_loss.h"
 
 namespace gbrl {
 namespace kern {
@@ -42,28 +43,6 @@ struct StagedIo {
     double *part;           // [n_stops][nb], nb = ceil(n / 64)
     int nb;
 };
-
-constexpr int kStagedRows = kStreamRows;   // rows per wave = rows per loss partial, in both kernels
-
-// sum of the wave's 64 values in a fixed order (xor butterfly: every lane ends with the same bits); called by whole waves only
-__device__ __forceinline__ double staged_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// sum_j (double)g_j^2 of one row, j ascending; g_j = fl32(p_j - y_j) (loss.cpp:42-56).  (double)g * (double)g is exact.
-template <int DMAX>
-__device__ __forceinline__ double staged_row_loss(const float (&p)[DMAX], const float *y, int D) {
-    double acc = 0.0;
-#pragma unroll
-    for (int j = 0; j < DMAX; ++j)
-        if (j < D) {
-            const double g = static_cast<double>(__fsub_rn(p[j], y[j]));
-            acc = fma(g, g, acc);
-        }
-    return acc;
-}
 
 // ------------------------------------------------------------------------------------------------------------ general kernel
 template <int DMAX, bool LOSS>
@@ -213,10 +192,17 @@ void staged_dispatch(const ChainModel &cm, const StagedIo &io, const PredictMode
 
 int staged_loss_partials(int n) { return (n + kStagedRows - 1) / kStagedRows; }
 
-void staged_loss_of_predictions(const float *preds, const float *targets, int n, int D, double *part, double *sum, hipStream_t s) {
-    const int nb = staged_loss_partials(n);
-    hipLaunchKernelGGL(k_loss_of_predictions, dim3((n + 255) / 256), dim3(256), 0, s, preds, targets, n, D, part, nb);
+void loss_partials_of_predictions(const float *preds, const float *targets, int n, int D, double *part, hipStream_t s) {
+    hipLaunchKernelGGL(k_loss_of_predictions, dim3((n + 255) / 256), dim3(256), 0, s, preds, targets, n, D, part, staged_loss_partials(n));
+}
+
+void staged_loss_finish(const double *part, int nb, double *sum, hipStream_t s) {
     hipLaunchKernelGGL(k_staged_finish, dim3(1), dim3(kFinishThreads), 0, s, part, nb, sum);
+}
+
+void staged_loss_of_predictions(const float *preds, const float *targets, int n, int D, double *part, double *sum, hipStream_t s) {
+    loss_partials_of_predictions(preds, targets, n, D, part, s);
+    staged_loss_finish(part, staged_loss_partials(n), sum, s);
 }
 
 void predict_staged(const PredictModel &pm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, const StagedStops &st, float *out,

@@ -365,8 +365,48 @@ int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const 
  *     leaves it, with the same loss.  A model WITH trees keeps its bias and continues from all of them -- unlike gbrl_hip_fit, whose iteration
  *     i predicts from the trees [0, i) only and which resets the bias -- and every existing tree must be expressible on the data set
  *     (GBRL_HIP_E_UNSUPPORTED before anything changes).  Argument errors (the data set checks of gbrl_hip_step_prepared, iterations < 0, NULL
- *     targets, batch_size <= 0) leave the model unchanged; a failure in iteration i leaves the i trees already grown, as gbrl_hip_fit does. */
+ *     targets, batch_size <= 0) leave the model unchanged; a failure in iteration i leaves the i trees already grown, as gbrl_hip_fit does.
+ *
+ * Data sets that share thresholds (new: LightGBM's Dataset(reference=train)).  A data set's codes only mean something against its own
+ * thresholds, so a held-out batch binned by gbrl_hip_dataset_create gets quantiles of its own and a model grown on the training set is refused
+ * on it.  A BOUND data set puts new rows on thresholds that already exist.
+ *   gbrl_hip_dataset_create_like(m, reference, obs, obs_on_device, n)  obs float32 [n, F of the reference].  The result holds the codes of obs
+ *     under the reference's thresholds -- code(r, f) = #{b : thr[f][b] < obs[r][f]} by the rule above, computed on the ordered keys against the
+ *     reference's threshold keys in ONE pass over obs (no transpose, no selection); rows outside the reference's range get 0 or n_bins; records
+ *     [G][n][16] u16 with the padding slots zero -- and its own copies of the thresholds, their keys and the host thresholds: the reference may
+ *     be destroyed afterwards.  gbrl_hip_dataset_thresholds returns the reference's bytes; nbytes counts the codes and the threshold copies
+ *     (a bound data set holds no keys, no feature-major codes and no root table).  It is a full data set: gbrl_hip_dataset_codes,
+ *     gbrl_hip_predict_continue_prepared, gbrl_hip_step_prepared and gbrl_hip_fit_prepared work on it; a step on it grows with the
+ *     reference's thresholds, byte for byte as a subset step (rows != NULL) on the same records does.  Refused before the device is touched
+ *     (GBRL_HIP_E_INVALID): a NULL or destroyed reference, n <= 0, NULL obs; and everything gbrl_hip_step_prepared refuses about (model,
+ *     reference).  NULL on failure, status as gbrl_hip_dataset_create.  The model is never changed.
+ *   gbrl_hip_dataset_thresholds_id(ds)  a data set made without a reference gets a fresh id; a bound one inherits its reference's, through any
+ *     chain.  0 for a NULL or destroyed data set.  The model's code tables (the bins of its conditions) are keyed on this id: calls that
+ *     alternate between data sets that share thresholds append the new trees' rows only.
+ *
+ * Validation and early stopping.
+ *   gbrl_hip_fit_prepared_valid(m, ds, targets, .., iterations, valid_ds, valid_targets, .., early_stopping_rounds, min_delta, loss_out,
+ *     valid_loss_out, iterations_done, best_n_trees)  gbrl_hip_fit_prepared watching valid_ds, which must share ds's thresholds id (it may be
+ *     ds itself).  Let T0 be the tree count at entry (a model without trees: after the bias has been set).  valid_loss_out[k], k = 0 ..
+ *     *iterations_done (room for iterations + 1 doubles), is the MultiRMSE of the first T0 + k trees on the validation rows: BIT FOR BIT
+ *     gbrl_hip_staged_loss(.., stops = {T0 + k}) on the matrix valid_ds was binned from (sqrt(0.5 * S / n_v) in float64, S from one partial per
+ *     64 consecutive rows).  The validation prediction is held on the device and advanced after EVERY iteration, whatever batch_size is, by one
+ *     launch that also writes the loss partials.  Rule: best = index of the minimum so far, from k = 0; entry k improves iff valid_loss[k] <
+ *     valid_loss[best] - min_delta (a NaN never improves); with early_stopping_rounds = R > 0 the loop ends after iteration k when k - best >=
+ *     R; R = 0 records only.  All trees grown stay (there is no truncation); *best_n_trees = T0 + best is the stop_tree to predict with.  The
+ *     model after *iterations_done iterations is BYTE FOR BYTE what gbrl_hip_fit_prepared(m, ds, targets, *iterations_done) leaves and
+ *     *loss_out is its loss.  Refused before anything changes (GBRL_HIP_E_INVALID): a valid_ds with another thresholds id (create it with
+ *     gbrl_hip_dataset_create_like), NULL valid_targets, early_stopping_rounds < 0, min_delta negative or NaN, NULL valid_loss_out; and what
+ *     gbrl_hip_fit_prepared refuses.
+ *   gbrl_hip_early_stop_scan(curve, n, rounds, min_delta, stop_after, best)  the rule above on a curve of n >= 1 entries, host only (the loop
+ *     itself calls it): *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = the best index at that point. */
 int gbrl_hip_condition_bins(const gbrl_hip_model *m, const float *thresholds /*[F*B]*/, int n_features, int n_bins, int32_t *out);
+gbrl_hip_dataset *gbrl_hip_dataset_create_like(gbrl_hip_model *m, const gbrl_hip_dataset *reference, const float *obs, int obs_on_device, int n_samples);
+uint64_t gbrl_hip_dataset_thresholds_id(const gbrl_hip_dataset *ds);
+int gbrl_hip_fit_prepared_valid(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
+                                const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                double min_delta, float *loss_out, double *valid_loss_out /*[iterations + 1]*/, int *iterations_done, int *best_n_trees);
+int gbrl_hip_early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
 int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
                                        const float *base, int base_on_device, int start_tree, int stop_tree, float *out);
 int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
