@@ -672,6 +672,41 @@ py::array dataset_codes_impl(PyDataset &self, py::object &rows) {
     return std::move(out);
 }
 
+// Extension: the row sampler (include/gbrl_hip.h, "Row subsampling").  PreparedDataset.sample_rows -> int32 [m] on the data set's device, handed
+// out as predict hands out device results (a DLPack capsule; the buffer holds stop - start entries, of which the first m are the tensor).
+py::object dataset_sample_rows_impl(PyDataset &self, double subsample, uint64_t seed, int draw, int start, py::object stop_obj) {
+    const gbrl_hip_dataset_desc d = self.info();
+    const int stop = stop_obj.is_none() ? d.n_rows : stop_obj.cast<int>();
+    if (start < 0 || stop > d.n_rows || stop <= start) {
+        std::stringstream ss;
+        ss << "sample_rows: rows [" << start << ", " << stop << ") are not a non-empty range inside [0, " << d.n_rows << ")";
+        fail(ss.str());
+    }
+    const int n = stop - start;
+    int32_t *p = static_cast<int32_t *>(gbrl_hip_device_alloc_on(d.device, sizeof(int32_t) * static_cast<size_t>(n)));
+    if (!p) fail(gbrl_hip_last_error());
+    int rc, m = 0;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_dataset_sample_rows(self.h, start, n, subsample, seed, draw, p, 1, &m);
+    }
+    if (rc != GBRL_HIP_OK) {
+        gbrl_hip_device_free(p);
+        fail(gbrl_hip_last_error());
+    }
+    return make_dlpack(p, {static_cast<int64_t>(m)}, true, d.device, /*int32=*/true);
+}
+
+py::array_t<int32_t> sample_rows_host_impl(int n, double subsample, uint64_t seed, int draw, int row0) {
+    std::vector<int32_t> rows(static_cast<size_t>(std::max(n, 0)));
+    int32_t none = 0;
+    int m = 0;
+    check(gbrl_hip_sample_rows_host(row0, n, subsample, seed, draw, rows.empty() ? &none : rows.data(), &m));
+    py::array_t<int32_t> out(static_cast<py::ssize_t>(m));
+    std::copy(rows.begin(), rows.begin() + m, out.mutable_data());
+    return out;
+}
+
 // Extension: the walk over a data set's bin codes (include/gbrl_hip.h).  condition_bins(thresholds) -> int32 array shaped like feature_values.
 py::array_t<int32_t> condition_bins_impl(PyGBRL &self, py::object &thresholds) {
     const gbrl_hip_metadata md = self.meta();
@@ -732,17 +767,28 @@ float fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, in
     return loss;
 }
 
-// fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0): a float without a validation
-// set (the other three at their defaults), else a dict
+// fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, seed=0): a float
+// without a validation set (the three validation arguments at their defaults), else a dict; subsample / seed go with either
 py::object fit_prepared_valid_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
-                                   int early_stopping_rounds, double min_delta) {
+                                   int early_stopping_rounds, double min_delta, double subsample, uint64_t seed) {
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     if (valid_obj.is_none()) {
         if (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0)
             fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
-        return py::float_(fit_prepared_impl(self, ds_obj, targets, iterations));
+        if (subsample == 1.0) return py::float_(fit_prepared_impl(self, ds_obj, targets, iterations));
+        Input t = read_input(targets, "targets", false, "fit", false);
+        if (ds && t.ptr) check_rows_by_outputs(t, "targets", ds_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
+        float loss = 0.0f;
+        int rc;
+        {
+            py::gil_scoped_release release;
+            rc = gbrl_hip_fit_prepared_sampled(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, nullptr, nullptr, 0, 0, 0.0, subsample,
+                                               seed, &loss, nullptr, nullptr, nullptr);
+        }
+        check(rc);
+        return py::float_(loss);
     }
-    const gbrl_hip_metadata md = self.meta();
-    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     const gbrl_hip_dataset *dsv = valid_obj.cast<const PyDataset &>().h;
     Input t = read_input(targets, "targets", false, "fit", false);
     if (ds && t.ptr) check_rows_by_outputs(t, "targets", ds_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
@@ -753,8 +799,8 @@ py::object fit_prepared_valid_impl(PyGBRL &self, py::object ds_obj, py::object &
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_valid(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, dsv, static_cast<const float *>(tv.ptr),
-                                         tv.on_device, early_stopping_rounds, min_delta, &loss, curve.data(), &done, &best);
+        rc = gbrl_hip_fit_prepared_sampled(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, dsv, static_cast<const float *>(tv.ptr),
+                                           tv.on_device, early_stopping_rounds, min_delta, subsample, seed, &loss, curve.data(), &done, &best);
     }
     check(rc);
     py::array_t<double> vl(static_cast<py::ssize_t>(done) + 1);
@@ -924,6 +970,18 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "codes(rows=None) -> uint16 [ceil(n_features / 16), m, 16]: the class codes, group-major; code of feature f and row r at [f // 16, r, f % 16] = number of\n"
             "thresholds of f below obs[r, f].  rows (int32 vector, NumPy or (ptr, (m,), 'torch.int32', 'cuda'), duplicates allowed): the records of those rows,\n"
             "gathered on the device.");
+    pds.def("sample_rows", &dataset_sample_rows_impl, py::arg("subsample"), py::arg("seed") = 0, py::arg("draw") = 0, py::arg("start") = 0,
+            py::arg("stop") = py::none(),
+            "sample_rows(subsample, seed=0, draw=0, start=0, stop=None) -> DLPack capsule, int32 [m] on the data set's device\n\n"
+            "The rows of [start, stop) (stop=None: n_rows) that the row sampler keeps, ascending, as absolute indices: row r is kept iff the 24-bit hash\n"
+            "of (seed, draw, r) is below floor(subsample * 2**24) -- gbrl_cpp.sample_rows_host(stop - start, subsample, seed, draw, start) exactly, drawn on\n"
+            "the device without atomics (two calls give the same bytes), without replacement.  subsample in [2**-24, 1], seed in [0, 2**64), draw >= 0.\n"
+            "torch.from_dlpack(capsule) is usable as rows= of step_prepared and predict_continue_prepared ((t.data_ptr(), (m,), 'torch.int32', 'cuda'));\n"
+            "fit_prepared(subsample=) uses draw = the model's tree count before the step.  m may be 0: a tensor of shape (0,).");
+    m.def("sample_rows_host", &sample_rows_host_impl, py::arg("n"), py::arg("subsample"), py::arg("seed") = 0, py::arg("draw") = 0, py::arg("row0") = 0,
+          "sample_rows_host(n, subsample, seed=0, draw=0, row0=0) -> int32 NumPy array [m]\n\n"
+          "The row sampler's rule on the host (no device is needed): the rows of [row0, row0 + n) that (seed, draw) keeps at `subsample`, ascending.\n"
+          "PreparedDataset.sample_rows returns the same list from the device.");
     py::class_<PyGBRL> g(m, "GBRL");
     g.def(py::init<int, int, int, int, int, int, int, float, std::string, std::string, bool, int, std::string, int, std::string, std::string>(),
           py::arg("input_dim") = 1, py::arg("output_dim") = 1, py::arg("policy_dim") = 1, py::arg("max_depth") = 4,
@@ -996,7 +1054,7 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         g.def("fit_prepared", &fit_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
-            "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0) -> float | dict\n\n"
+            "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, seed=0) -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
             "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
@@ -1007,11 +1065,19 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "predict with).  Entry k improves iff valid_loss[k] < valid_loss[best] - min_delta; with early_stopping_rounds = R > 0 the loop ends after iteration k\n"
             "when k - best >= R; R = 0 records only.  All trees grown stay in the model (no truncation), which is byte for byte what fit_prepared(ds, targets,\n"
             "iterations run) leaves.  Refused before anything changes: another thresholds_id, valid_targets missing, early_stopping_rounds < 0, min_delta negative\n"
-            "or NaN; without valid= the other three must be at their defaults.";
+            "or NaN; without valid= the other three must be at their defaults.\n"
+            "subsample=p < 1.0 (with or without valid=), seed an int in [0, 2**64): stochastic gradient boosting.  Every tree is grown on a sample of its batch:\n"
+            "row r is kept iff the 24-bit hash of (seed, draw, r) is below floor(p * 2**24) (gbrl_cpp.sample_rows_host, PreparedDataset.sample_rows), with draw =\n"
+            "the model's tree count before the step, so a fit that is continued continues the sequence and two runs with one seed give the same bytes.  The\n"
+            "rows are drawn and their gradient rows gathered on the device in one pass; the tree is what step_prepared(ds, g[rows - start], rows=rows) grows.\n"
+            "A draw that keeps no row of the batch takes the whole batch.  A fresh draw per tree, never with replacement.  The returned loss and valid_loss are\n"
+            "on all rows, as without sampling.  subsample == 1.0 is the unsampled loop itself, whatever seed is.  Refused before anything changes: a subsample\n"
+            "that is NaN or outside [2**-24, 1].";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_valid_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
-              py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0);
+              py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
+              py::arg("seed") = 0);
     }
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);

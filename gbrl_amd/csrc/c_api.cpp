@@ -581,6 +581,51 @@ int gbrl_hip_early_stop_scan(const double *curve, int n, int rounds, double min_
     return guarded([&] { gbrl::Engine::early_stop_scan(curve, n, rounds, min_delta, stop_after, best); });
 }
 
+// ---- row subsampling: the sampler on the host, on a data set's rows, fused with a gather (test helper), and fit_prepared on samples
+int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, int *count) {
+    return guarded([&] { gbrl::Engine::sample_rows_host(row0, n, subsample, seed, draw, out, count); });
+}
+
+int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, int out_on_device,
+                                 int *count) {
+    return guarded([&] { gbrl::Engine::sample_rows(&live_dataset(ds), row0, n, subsample, seed, draw, out, out_on_device != 0, count); });
+}
+
+int gbrl_hip_sample_gather(int row0, int n, double subsample, uint64_t seed, int draw, const float *grads, int output_dim, int32_t *rows_out,
+                           float *grads_out, int *count) {
+    return guarded([&] { gbrl::Engine::sample_gather(row0, n, subsample, seed, draw, grads, output_dim, rows_out, grads_out, count); });
+}
+
+void gbrl_hip_sample_rows_geometry(int *rows_per_block, int *scan_width) {
+    if (rows_per_block) *rows_per_block = gbrl::kern::kSampleRowsPerBlock;
+    if (scan_width) *scan_width = gbrl::kern::kSampleScanWidth;
+}
+
+int gbrl_hip_fit_prepared_sampled(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
+                                  const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                  double min_delta, double subsample, uint64_t seed, float *loss_out, double *valid_loss_out, int *iterations_done,
+                                  int *best_n_trees) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_fit_prepared(targets, iterations);
+        gbrl::Engine::check_subsample("fit_prepared", subsample);
+        if (valid_ds == nullptr) {
+            if (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr)
+                throw gbrl::InvalidArgument("fit_prepared: valid_targets, early_stopping_rounds, min_delta and valid_loss_out need a validation set");
+            const float loss = m->engine.fit_prepared_sampled(&live_dataset(ds), targets, targets_on_device != 0, iterations, nullptr, subsample, seed);
+            if (loss_out) *loss_out = loss;
+            if (iterations_done) *iterations_done = iterations;
+            return;
+        }
+        m->engine.precheck_fit_valid(valid_targets, early_stopping_rounds, min_delta);
+        gbrl::Engine::FitValid v{&live_dataset(valid_ds), valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0};
+        const float loss = m->engine.fit_prepared_sampled(&live_dataset(ds), targets, targets_on_device != 0, iterations, &v, subsample, seed);
+        if (loss_out) *loss_out = loss;
+        if (iterations_done) *iterations_done = v.done;
+        if (best_n_trees) *best_n_trees = v.best_n_trees;
+    });
+}
+
 int gbrl_hip_leaf_counts_chunk(void) { return gbrl::kern::leaf_counts_chunk(); }
 
 static_assert(static_cast<int>(gbrl::Engine::ParityMode::Default) == GBRL_HIP_PARITY_DEFAULT && static_cast<int>(gbrl::Engine::ParityMode::Reference) == GBRL_HIP_PARITY_REFERENCE &&

@@ -182,6 +182,24 @@ class Engine {
         double *loss_out /*[iterations + 1]*/; int done, best_n_trees;
     };
     float fit_prepared_valid(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid &v);
+    // Extension: row subsampling (stochastic gradient boosting).  The sampler is sample_core.h's pure function of (seed, draw, row): a row is
+    // kept iff its 24-bit hash is below floor(subsample * 2^24); the sample of [row0, row0 + n) is the ascending list of its kept absolute indices.
+    // sample_rows_host: the rule itself on the host, out [n], *count = m.  sample_rows: the same list from the device kernels (kern::sample_rows)
+    // on the data set's device and the null stream, as codes_to_host runs; out (int32 [n], host or device) gets the m kept rows, which may be
+    // none.  Refused (InvalidArgument): row0 < 0, n <= 0, draw < 0, a subsample that is NaN or outside [2^-24, 1], null outputs, a range whose
+    // last row is above 2^31 - 1, and for the data set call a range outside [0, ds.n).
+    static void check_subsample(const char *what, double subsample);
+    static void sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, int *count);
+    static void sample_rows(const PreparedDataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, bool out_dev, int *count);
+    // The engine's fused sampler + gather on the CURRENT device and the null stream (what fit_prepared's loop enqueues per iteration; the tests
+    // reach it through gbrl_hip_sample_gather): device G [n][D] -> device rows_out [n], G_out [n][D], *count = m.
+    static void sample_gather(int row0, int n, double subsample, uint64_t seed, int draw, const float *G, int D, int32_t *rows_out, float *G_out, int *count);
+    // fit_prepared / fit_prepared_valid (v may be null) growing every tree on a sample of its batch.  subsample == 1.0 IS the unsampled loop: no
+    // sampler launch, no gather, no phase.  Otherwise iteration i, after the held prediction and the gradient of the batch [start, start + bn)
+    // are up to date, draws the rows of the batch with draw = the tree count before the step (a continued fit continues the sequence), gathers
+    // their gradient rows in the same pass, reads m back (4 bytes) and grows on (rows, gathered gradients).  A draw that keeps no row takes the
+    // whole batch, as the unsampled iteration does.  Batches, validation, stopping, the final advance and the loss are the unsampled loop's.
+    float fit_prepared_sampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed);
     // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
     // min_delta (a NaN never improves); *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = best at that point
     static void early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
@@ -420,7 +438,9 @@ class Engine {
     DevBuf m_code_bins_, m_code_pack_, m_code_nodes_;
     DevBuf d_fp_pred_, d_fp_grads_, d_fp_iota_, d_fp_targets_;   // fit_prepared: held prediction [n][D], batch gradients, 0..n-1, staged targets
     DevBuf d_fp_vpred_, d_fp_vtargets_, d_fp_vpart_, d_fp_vsums_;   // its validation rows: held prediction [n_v][D], staged targets, loss partials, one sum per iteration
-    float fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v);
+    DevBuf d_fp_srows_, d_fp_sgrads_, d_fp_sscratch_;   // its sampled iterations: the kept rows of the batch, their gradient rows, block counts + m
+    float fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample = 1.0,
+                            uint64_t seed = 0);
     // rows [start, start + bn) of a data set's held prediction P (valid through `through` trees) advanced to every tree the model has, with the
     // gradient tail (targets, grad_out) and / or the loss tail (loss_targets, loss_part) of kern::predict_continue_codes; targets are [n][D]
     void advance_held(const PreparedDataset &ds, float *P, int &through, int start, int bn, const float *targets, float *grad_out,

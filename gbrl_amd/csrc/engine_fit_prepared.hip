@@ -7,12 +7,15 @@
 //   Engine::fit_prepared               fit()'s loop with the running prediction held and the batch never binned again
 //   Engine::fit_prepared_valid         the same loop watching a validation set that shares the thresholds: a second held prediction advanced after
 //                                      every iteration (advance_held, the loss tail of the code walk), Engine::early_stop_scan's rule
+//   Engine::fit_prepared_sampled       the same loop growing every tree on a sample of its batch (sample_core.h): kern::sample_rows draws the rows
+//                                      and gathers their gradient rows in one pass, 4 bytes come back, step_prepared's body grows on the subset
 //
 // The rule.  code(r, f) = #{b : thr[f][b] < obs[r, f]} (-0.0 == +0.0; NaN lies below every threshold: code 0).  For a condition x > v whose v
 // equals some thr[f][b] let bin = #{b : thr[f][b] < v}.  x > v: every threshold below v, and v itself, is below x, so code >= bin + 1.
 // x <= v: only thresholds below v can be below x, so code <= bin.  Hence x > v <=> code > bin, with duplicated thresholds and in any order.
 // It does not hold for a v that is not among the feature's thresholds: such a condition is refused (Unsupported), never approximated.
 #include "engine_step_detail.h"
+#include "sample_core.h"
 
 namespace gbrl {
 
@@ -246,9 +249,14 @@ float Engine::fit_prepared_valid(const PreparedDataset *ds, const float *targets
     return fit_prepared_loop(ds, targets, targets_dev, iterations, &v);
 }
 
-float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v) {
+float Engine::fit_prepared_sampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed) {
+    return fit_prepared_loop(ds, targets, targets_dev, iterations, v, subsample, seed);
+}
+
+float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed) {
     gbrl_hip_metadata &md = model.meta;
     precheck_fit_prepared(targets, iterations);
+    check_subsample("fit_prepared", subsample);
     if (v) precheck_fit_valid(v->targets, v->rounds, v->min_delta);
     check_prepared_dataset("fit_prepared", ds);
     if (v) {
@@ -340,6 +348,17 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
         v->done = 0; v->best_n_trees = T0;
         evaluate(0);
     }
+    // ---- a sampled fit: the kept rows of a batch, their gradient rows, the block counts of the sampler (subsample == 1.0: none of it exists)
+    const bool sampled = subsample < 1.0;
+    const uint32_t keep_thr = kern::sample_threshold(subsample);
+    int32_t *d_srows = nullptr, *d_sscratch = nullptr;
+    float *Gs = nullptr;
+    if (sampled) {
+        const int cap = std::min(bs, n);
+        d_srows = static_cast<int32_t *>(d_fp_srows_.ensure(sizeof(int32_t) * static_cast<size_t>(cap)));
+        Gs = static_cast<float *>(d_fp_sgrads_.ensure(sizeof(float) * static_cast<size_t>(cap) * D));
+        d_sscratch = static_cast<int32_t *>(d_fp_sscratch_.ensure(sizeof(int32_t) * (static_cast<size_t>(kern::sample_rows_blocks(cap)) + 1)));
+    }
     int start = 0, done = 0;
     int bn = start + bs < n ? bs : n - start;                                   // fitter.cpp:120
     for (int i = 0; i < iterations; ++i) {
@@ -347,7 +366,19 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
         phase_begin();
         advance(start, bn, G);
         phase_end("continue_codes");
-        step_prepared_run(ds, G, bn == n ? nullptr : d_iota + start, bn);
+        const float *g = G;
+        const int32_t *rows = bn == n ? nullptr : d_iota + start;
+        int m = bn;
+        if (sampled) {   // draw = the tree count before the step; a draw that keeps no row takes the whole batch
+            phase_begin();
+            kern::sample_rows(start, bn, keep_thr, seed, md.n_trees, G, D, d_srows, Gs, d_sscratch, s);
+            int32_t kept = 0;
+            hip_check(hipMemcpyAsync(&kept, d_sscratch, sizeof(kept), hipMemcpyDeviceToHost, s), "D2H sample count");
+            phase_end("sample_rows");
+            hip_check(hipStreamSynchronize(s), "sync");
+            if (kept > 0) { g = Gs; rows = d_srows; m = kept; }
+        }
+        step_prepared_run(ds, g, rows, m);
         start += bn;                                                            // fitter.cpp:228-231
         if (start >= n) start = 0;
         bn = start + bs < n ? bs : n - start;

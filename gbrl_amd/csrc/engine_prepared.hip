@@ -8,9 +8,13 @@
 //                             count table are handed over as null there (legal inputs of every growth path: the partition then reads the
 //                             codes, the root histogram counts its rows).
 //   PreparedDataset::codes_to_host   the codes on the host, all rows or a gathered subset
+//   Engine::sample_rows_host / sample_rows / sample_gather   the row sampler of sample_core.h: the rule on the host, kern::sample_rows on a data
+//                             set's row range, and with the gathered rows of a matrix (what fit_prepared's sampled iterations enqueue)
 // None of the growth kernels is touched: integer histograms do not depend on which of the optional buffers a path reads.
 #include "engine_step_detail.h"
+#include "sample_core.h"
 
+#include <limits>
 #include <memory>
 
 namespace gbrl {
@@ -239,16 +243,20 @@ void Engine::step_prepared_run(const PreparedDataset *ds, const float *dgrads, c
     }
 }
 
+namespace {
+struct DeviceScope {   // a data set's device for one call, the caller's afterwards
+    int prev = -1;
+    explicit DeviceScope(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; hip_check(hipSetDevice(dev), "hipSetDevice"); }
+    ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+}  // namespace
+
 void PreparedDataset::codes_to_host(const int32_t *rows, bool rows_dev, int m, uint16_t *out) const {
     if (out == nullptr) throw InvalidArgument("dataset_codes: no place for the codes");
     if (rows == nullptr) m = n;
     if (m <= 0) throw InvalidArgument("dataset_codes: no rows (m must be positive)");
     if (rows != nullptr && !rows_dev) check_host_rows(rows, m, n);
-    struct Scope {   // the data set's device for this call, the caller's afterwards
-        int prev = -1;
-        explicit Scope(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; hip_check(hipSetDevice(dev), "hipSetDevice"); }
-        ~Scope() { if (prev >= 0) (void)hipSetDevice(prev); }
-    } scope(device);
+    DeviceScope scope(device);
     hipStream_t s = nullptr;
     const int G = code_groups();
     const size_t bytes = sizeof(uint16_t) * static_cast<size_t>(G) * m * kern::kCodeGroup;
@@ -263,6 +271,64 @@ void PreparedDataset::codes_to_host(const int32_t *rows, bool rows_dev, int m, u
     }
     hip_check(hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, s), "D2H codes");
     hip_check(hipStreamSynchronize(s), "sync");
+}
+
+// ---- the row sampler (sample_core.h) on a row range: the host rule, the device kernels on a data set, the fused gather of fit_prepared's loop
+void Engine::check_subsample(const char *what, double subsample) {
+    if (!kern::sample_fraction_ok(subsample))
+        throw InvalidArgument(std::string(what) + ": subsample must be in [2^-24, 1] (and not NaN), got " + std::to_string(subsample));
+}
+
+namespace {
+void check_sample_range(const char *what, int row0, int n, double subsample, int draw, const void *out, const int *count) {
+    const std::string w(what);
+    if (out == nullptr || count == nullptr) throw InvalidArgument(w + ": null output");
+    if (row0 < 0) throw InvalidArgument(w + ": row0 must be >= 0");
+    if (n <= 0) throw InvalidArgument(w + ": no rows (n must be positive)");
+    if (draw < 0) throw InvalidArgument(w + ": draw must be >= 0");
+    Engine::check_subsample(what, subsample);
+    if (row0 > std::numeric_limits<int32_t>::max() - (n - 1)) throw InvalidArgument(w + ": the range ends above row 2^31 - 1");
+}
+}  // namespace
+
+void Engine::sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, int *count) {
+    check_sample_range("sample_rows_host", row0, n, subsample, draw, out, count);
+    const uint32_t thr = kern::sample_threshold(subsample);
+    int m = 0;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t row = static_cast<uint32_t>(row0) + static_cast<uint32_t>(i);
+        if (kern::sample_keeps(seed, draw, row, thr)) out[m++] = static_cast<int32_t>(row);
+    }
+    *count = m;
+}
+
+void Engine::sample_gather(int row0, int n, double subsample, uint64_t seed, int draw, const float *G, int D, int32_t *rows_out, float *G_out, int *count) {
+    check_sample_range("sample_gather", row0, n, subsample, draw, rows_out, count);
+    if ((G == nullptr) != (G_out == nullptr)) throw InvalidArgument("sample_gather: G and G_out go together");
+    if (G != nullptr && (D < 1 || D > 512)) throw InvalidArgument("sample_gather: D must be in [1, 512]");
+    hipStream_t s = nullptr;
+    DevBuf scratch;
+    int32_t *d_scratch = static_cast<int32_t *>(scratch.ensure(sizeof(int32_t) * (static_cast<size_t>(kern::sample_rows_blocks(n)) + 1)));
+    kern::sample_rows(row0, n, kern::sample_threshold(subsample), seed, draw, G, D, rows_out, G_out, d_scratch, s);
+    hip_check(hipGetLastError(), "sample_rows launch");
+    int32_t m = 0;
+    hip_check(hipMemcpyAsync(&m, d_scratch, sizeof(m), hipMemcpyDeviceToHost, s), "D2H sample count");
+    hip_check(hipStreamSynchronize(s), "sync");
+    *count = m;
+}
+
+void Engine::sample_rows(const PreparedDataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, bool out_dev, int *count) {
+    if (ds == nullptr) throw InvalidArgument("sample_rows: null data set");
+    check_sample_range("sample_rows", row0, n, subsample, draw, out, count);
+    if (row0 >= ds->n || n > ds->n - row0)
+        throw InvalidArgument("sample_rows: rows [" + std::to_string(row0) + ", " + std::to_string(static_cast<long long>(row0) + n) + ") are outside [0, " + std::to_string(ds->n) + ")");
+    DeviceScope scope(ds->device);
+    DevBuf rows;
+    int32_t *d_rows = out_dev ? out : static_cast<int32_t *>(rows.ensure(sizeof(int32_t) * static_cast<size_t>(n)));
+    int m = 0;
+    sample_gather(row0, n, subsample, seed, draw, nullptr, 0, d_rows, nullptr, &m);
+    if (!out_dev && m > 0) hip_check(hipMemcpy(out, d_rows, sizeof(int32_t) * static_cast<size_t>(m), hipMemcpyDeviceToHost), "D2H sampled rows");
+    *count = m;
 }
 
 }  // namespace gbrl

@@ -199,6 +199,14 @@ void gather_code_records(const uint16_t *codes /*[n_groups][n][16]*/, int n, int
 void bin_like(const float *obs, int n, int F, const uint32_t *thr_keys, int B, uint16_t *codes /*[ceil(F/16)][n][16]*/, hipStream_t s);
 // mm[0] = min rows[j], mm[1] = min ~rows[j] (= ~max) of a device index vector, m >= 1
 void rows_minmax(const int32_t *rows, int m, int32_t *mm /*[2], device*/, hipStream_t s);
+// the row sampler on the device (sample_rows.hip; the rule is sample_core.h's): rows_out[0 .. m) = the kept rows of [row0, row0 + n), ascending,
+// as absolute indices; scratch[0] = m; with G (device [n][D], row r - row0 for row r) also G_out[j][:] = G[rows_out[j] - row0][:] in the same
+// pass.  Three launches (count, a one-block scan of the block counts, write), positions from ranks only: the bytes do not depend on scheduling.
+// rows_out / G_out need room for n rows unless the caller knows m; scratch holds sample_rows_blocks(n) + 1 words.  row0 + n <= 2^31.
+constexpr int kSampleRowsPerBlock = 2048, kSampleScanWidth = 512;
+int sample_rows_blocks(int n);
+void sample_rows(int row0, int n, uint32_t thr /*sample_threshold(subsample)*/, uint64_t seed, int32_t draw, const float *G /*nullable*/, int D,
+                 int32_t *rows_out, float *G_out /*nullable*/, int32_t *scratch, hipStream_t s);
 
 // ---- split-score histograms (A6) ----
 size_t hist_lds_bytes(int NB, int D, int FG);

@@ -399,7 +399,48 @@ int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const 
  *     gbrl_hip_dataset_create_like), NULL valid_targets, early_stopping_rounds < 0, min_delta negative or NaN, NULL valid_loss_out; and what
  *     gbrl_hip_fit_prepared refuses.
  *   gbrl_hip_early_stop_scan(curve, n, rounds, min_delta, stop_after, best)  the rule above on a curve of n >= 1 entries, host only (the loop
- *     itself calls it): *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = the best index at that point. */
+ *     itself calls it): *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = the best index at that point.
+ *
+ * Row subsampling (new: stochastic gradient boosting -- LightGBM's bagging_fraction, XGBoost's and scikit-learn's subsample).  The sampler is
+ * a pure function of (seed, draw, row), in unsigned 64-bit arithmetic that wraps:
+ *     x = (uint64(draw) << 32) | uint32(row);  z = x + (seed + 1) * 0x9E3779B97F4A7C15;
+ *     z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31;  u = z >> 40   (24 bits)
+ *     row is kept  <=>  u < (uint32) floor(subsample * 2^24)        subsample in [2^-24, 1]; 1.0 keeps every row
+ * row is the ABSOLUTE row index in the data set, draw >= 0 is the caller's to choose.  The sample of the rows [row0, row0 + n) is the ascending
+ * list of the kept indices: no replacement, the same list on the host and on the device, independent of how a range is cut.
+ *   gbrl_hip_sample_rows_host(row0, n, subsample, seed, draw, out, count)  the rule itself on the host: out[0 .. *count) (room for n), no device.
+ *   gbrl_hip_dataset_sample_rows(ds, row0, n, subsample, seed, draw, out, out_on_device, count)  the same list from the device kernels, on the
+ *     data set's device and the null stream: a count launch, a one-block scan of the block counts and a write launch that places every kept
+ *     row at its rank (no atomics: two calls give the same bytes).  out has room for n int32, on the host or on the data set's device; *count
+ *     may be 0.  The result is a legal `rows` of gbrl_hip_step_prepared and gbrl_hip_predict_continue_prepared when *count > 0.
+ *     Both calls refuse (GBRL_HIP_E_INVALID): row0 < 0, n <= 0, draw < 0, a subsample that is NaN or outside [2^-24, 1], NULL out or count, a
+ *     range that ends above row 2^31 - 1; the data set call also a NULL or destroyed data set and a range outside [0, n_rows).
+ *   gbrl_hip_fit_prepared_sampled(m, ds, targets, .., iterations, valid_ds, valid_targets, .., early_stopping_rounds, min_delta, subsample, seed,
+ *     loss_out, valid_loss_out, iterations_done, best_n_trees)  gbrl_hip_fit_prepared_valid growing every tree on a sample of its batch.  With
+ *     valid_ds == NULL the validation arguments must be NULL / 0 and it is gbrl_hip_fit_prepared (*best_n_trees is not written).  With
+ *     subsample == 1.0 it runs the unsampled loop itself: no sampler launch, no gather, the same bytes, loss and phases, whatever seed is.
+ *     Otherwise iteration i, once the held prediction and the gradient of its batch [start, start + bn) are up to date, draws the rows of the
+ *     batch with draw = the tree count BEFORE the step (so a fit that is continued continues the sequence), gathers their gradient rows in the
+ *     pass that writes the indices, reads the count back (4 bytes) and grows the tree as gbrl_hip_step_prepared(rows) does, with the data set's
+ *     thresholds.  A draw that keeps no row of the batch takes the whole batch, as the unsampled iteration does.  A fresh draw per tree (there
+ *     is no bagging_freq), never with replacement.  Batches, validation, the stopping rule and the returned loss (on ALL rows of ds) are the
+ *     unsampled loop's.  Refused before anything changes (GBRL_HIP_E_INVALID): a bad subsample, and what the two calls above refuse.
+ *   gbrl_hip_sample_gather(row0, n, subsample, seed, draw, grads, output_dim, rows_out, grads_out, count)  test access to the launch sequence of
+ *     a sampled iteration, on the calling thread's current device and the null stream: grads float32 [n, output_dim] (row r - row0 for row r),
+ *     rows_out int32 [n] and grads_out [n, output_dim] are DEVICE buffers; grads_out[j] = grads[rows_out[j] - row0] (16-byte accesses when
+ *     output_dim % 4 == 0 and both matrices are 16-byte aligned, 4-byte accesses otherwise).  grads and grads_out may both be NULL.
+ *   gbrl_hip_sample_rows_geometry(rows_per_block, scan_width)  the rows one block of the sampler owns and the block counts one slice of its scan
+ *     takes (diagnostic; no device needed): the sizes at which the kernels take another path. */
+int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
+int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
+                                 int out_on_device, int *count);
+int gbrl_hip_fit_prepared_sampled(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
+                                  const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                  double min_delta, double subsample, uint64_t seed, float *loss_out, double *valid_loss_out /*[iterations + 1]*/,
+                                  int *iterations_done, int *best_n_trees);
+int gbrl_hip_sample_gather(int row0, int n, double subsample, uint64_t seed, int draw, const float *grads, int output_dim, int32_t *rows_out,
+                           float *grads_out, int *count);
+void gbrl_hip_sample_rows_geometry(int *rows_per_block, int *scan_width);
 int gbrl_hip_condition_bins(const gbrl_hip_model *m, const float *thresholds /*[F*B]*/, int n_features, int n_bins, int32_t *out);
 gbrl_hip_dataset *gbrl_hip_dataset_create_like(gbrl_hip_model *m, const gbrl_hip_dataset *reference, const float *obs, int obs_on_device, int n_samples);
 uint64_t gbrl_hip_dataset_thresholds_id(const gbrl_hip_dataset *ds);
