@@ -589,6 +589,23 @@ Input read_rows(py::object &rows, const std::string &fn) {
     return r;
 }
 
+// cols=: a one-dimensional vector of column indices in host memory (a NumPy integer array or a sequence of ints); the C ABI checks its contents
+std::vector<int32_t> read_cols(py::object &cols, const std::string &fn) {
+    py::array any = py::array::ensure(cols);
+    if (!any) { PyErr_Clear(); fail(fn + ": cols must be a vector of integers"); }
+    if (any.ndim() != 1) fail(fn + ": cols must be one-dimensional");
+    if (any.size() == 0) return {};   // (an empty list has no integer dtype; the caller refuses "no column")
+    if (any.dtype().kind() != 'i' && any.dtype().kind() != 'u') fail(fn + ": cols must be a vector of integers");
+    auto a = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(any);
+    if (!a) { PyErr_Clear(); fail(fn + ": cols must be a vector of integers"); }
+    std::vector<int32_t> out(static_cast<size_t>(a.shape(0)));
+    for (size_t i = 0; i < out.size(); ++i) {
+        const int64_t v = a.at(static_cast<py::ssize_t>(i));
+        out[i] = v < INT32_MIN ? INT32_MIN : v > INT32_MAX ? INT32_MAX : static_cast<int32_t>(v);   // (out of any range either way)
+    }
+    return out;
+}
+
 std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs, py::object reference = py::none()) {
     // categorical cells cannot be prepared: their split candidates depend on the step's gradients
     bool cells = false;
@@ -624,7 +641,7 @@ std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs, p
     return std::unique_ptr<PyDataset>(new PyDataset(d));
 }
 
-void step_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &grads, py::object &rows) {
+void step_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &grads, py::object &rows, py::object cols = py::none()) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     Input g = read_input(grads, "grads", false, "step_prepared", false);
@@ -648,28 +665,51 @@ void step_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &grads, py::
     }
     static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
     const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
+    std::vector<int32_t> cv;
+    if (!cols.is_none()) cv = read_cols(cols, "step_prepared");
+    static const int32_t kNoCols = 0;   // an empty cols vector is "no column", not "every column"
     int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_step_prepared(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, rp, r.ptr ? r.on_device : 0, n);
+        if (cols.is_none()) rc = gbrl_hip_step_prepared(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, rp, r.ptr ? r.on_device : 0, n);
+        else rc = gbrl_hip_step_prepared_cols(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, rp, r.ptr ? r.on_device : 0, n,
+                                              cv.empty() ? &kNoCols : cv.data(), static_cast<int>(cv.size()));
     }
     check(rc);
 }
 
-py::array dataset_codes_impl(PyDataset &self, py::object &rows) {
+py::array dataset_codes_impl(PyDataset &self, py::object &rows, py::object &cols) {
     const gbrl_hip_dataset_desc d = self.info();
     Input r = read_rows(rows, "codes");
     const int m = rows.is_none() ? d.n_rows : static_cast<int>(r.shape[0]);
     if (m <= 0) fail("dataset_codes: no rows (m must be positive)");
-    py::array_t<uint16_t> out({static_cast<py::ssize_t>(d.code_groups), static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(16)});
+    std::vector<int32_t> cv;
+    if (!cols.is_none()) {
+        cv = read_cols(cols, "codes");
+        if (cv.empty()) fail("dataset_codes: cols must name between 1 and " + std::to_string(d.n_features) + " columns, got 0");
+    }
+    const py::ssize_t groups = cols.is_none() ? d.code_groups : static_cast<py::ssize_t>((cv.size() + 15) / 16);
+    py::array_t<uint16_t> out({groups, static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(16)});
     uint16_t *op = out.mutable_data();
     int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_dataset_codes(self.h, static_cast<const int32_t *>(r.ptr), r.on_device, m, op);
+        if (cols.is_none()) rc = gbrl_hip_dataset_codes(self.h, static_cast<const int32_t *>(r.ptr), r.on_device, m, op);
+        else rc = gbrl_hip_dataset_codes_cols(self.h, static_cast<const int32_t *>(r.ptr), r.on_device, m, cv.data(), static_cast<int>(cv.size()), op);
     }
     check(rc);
     return std::move(out);
+}
+
+// Extension: the column rule (include/gbrl_hip.h, "Column subsampling"), host only
+py::array_t<int32_t> sample_cols_host_impl(int F, double colsample, uint64_t seed, int draw) {
+    std::vector<int32_t> cols(static_cast<size_t>(std::max(F, 0)));
+    int32_t none = 0;
+    int k = 0;
+    check(gbrl_hip_sample_cols_host(F, colsample, seed, draw, cols.empty() ? &none : cols.data(), &k));
+    py::array_t<int32_t> out(static_cast<py::ssize_t>(k));
+    std::copy(cols.begin(), cols.begin() + k, out.mutable_data());
+    return out;
 }
 
 // Extension: the row sampler (include/gbrl_hip.h, "Row subsampling").  PreparedDataset.sample_rows -> int32 [m] on the data set's device, handed
@@ -767,24 +807,24 @@ float fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, in
     return loss;
 }
 
-// fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, seed=0): a float
-// without a validation set (the three validation arguments at their defaults), else a dict; subsample / seed go with either
+// fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0):
+// a float without a validation set (the three validation arguments at their defaults), else a dict; subsample / colsample / seed go with either
 py::object fit_prepared_valid_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
-                                   int early_stopping_rounds, double min_delta, double subsample, uint64_t seed) {
+                                   int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     if (valid_obj.is_none()) {
         if (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0)
             fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
-        if (subsample == 1.0) return py::float_(fit_prepared_impl(self, ds_obj, targets, iterations));
+        if (subsample == 1.0 && colsample == 1.0) return py::float_(fit_prepared_impl(self, ds_obj, targets, iterations));
         Input t = read_input(targets, "targets", false, "fit", false);
         if (ds && t.ptr) check_rows_by_outputs(t, "targets", ds_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
         float loss = 0.0f;
         int rc;
         {
             py::gil_scoped_release release;
-            rc = gbrl_hip_fit_prepared_sampled(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, nullptr, nullptr, 0, 0, 0.0, subsample,
-                                               seed, &loss, nullptr, nullptr, nullptr);
+            rc = gbrl_hip_fit_prepared_colsampled(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, nullptr, nullptr, 0, 0, 0.0, subsample,
+                                                  colsample, seed, &loss, nullptr, nullptr, nullptr);
         }
         check(rc);
         return py::float_(loss);
@@ -799,8 +839,8 @@ py::object fit_prepared_valid_impl(PyGBRL &self, py::object ds_obj, py::object &
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_sampled(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, dsv, static_cast<const float *>(tv.ptr),
-                                           tv.on_device, early_stopping_rounds, min_delta, subsample, seed, &loss, curve.data(), &done, &best);
+        rc = gbrl_hip_fit_prepared_colsampled(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, dsv, static_cast<const float *>(tv.ptr),
+                                              tv.on_device, early_stopping_rounds, min_delta, subsample, colsample, seed, &loss, curve.data(), &done, &best);
     }
     check(rc);
     py::array_t<double> vl(static_cast<py::ssize_t>(done) + 1);
@@ -966,10 +1006,16 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         check(gbrl_hip_dataset_thresholds(d.h, out.mutable_data()));
         return out;
     }, "thresholds() -> float32 [n_features, n_bins]: the split candidates of the batch");
-    pds.def("codes", &dataset_codes_impl, py::arg("rows") = py::none(),
-            "codes(rows=None) -> uint16 [ceil(n_features / 16), m, 16]: the class codes, group-major; code of feature f and row r at [f // 16, r, f % 16] = number of\n"
-            "thresholds of f below obs[r, f].  rows (int32 vector, NumPy or (ptr, (m,), 'torch.int32', 'cuda'), duplicates allowed): the records of those rows,\n"
-            "gathered on the device.");
+    pds.def("codes", &dataset_codes_impl, py::arg("rows") = py::none(), py::arg("cols") = py::none(),
+            "codes(rows=None, cols=None) -> uint16 [ceil(n_features / 16), m, 16]: the class codes, group-major; code of feature f and row r at [f // 16, r, f % 16] =\n"
+            "number of thresholds of f below obs[r, f].  rows (int32 vector, NumPy or (ptr, (m,), 'torch.int32', 'cuda'), duplicates allowed): the records of those\n"
+            "rows, gathered on the device.  cols (host vector of ints, strictly ascending, in [0, n_features)): the records of that column subset re-packed into\n"
+            "ceil(len(cols) / 16) groups -- the code of column cols[s] at [s // 16, j, s % 16], padding slots 0 -- what step_prepared(cols=) grows on.");
+    pds.def("sample_cols", [](PyDataset &self, double colsample, uint64_t seed, int draw) { return sample_cols_host_impl(self.info().n_features, colsample, seed, draw); },
+            py::arg("colsample"), py::arg("seed") = 0, py::arg("draw") = 0,
+            "sample_cols(colsample, seed=0, draw=0) -> int32 NumPy array [k]\n\n"
+            "gbrl_cpp.sample_cols_host(n_features, colsample, seed, draw): the columns fit_prepared(colsample=) grows the tree of `draw` on, usable as cols= of\n"
+            "step_prepared and codes.");
     pds.def("sample_rows", &dataset_sample_rows_impl, py::arg("subsample"), py::arg("seed") = 0, py::arg("draw") = 0, py::arg("start") = 0,
             py::arg("stop") = py::none(),
             "sample_rows(subsample, seed=0, draw=0, start=0, stop=None) -> DLPack capsule, int32 [m] on the data set's device\n\n"
@@ -982,6 +1028,10 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "sample_rows_host(n, subsample, seed=0, draw=0, row0=0) -> int32 NumPy array [m]\n\n"
           "The row sampler's rule on the host (no device is needed): the rows of [row0, row0 + n) that (seed, draw) keeps at `subsample`, ascending.\n"
           "PreparedDataset.sample_rows returns the same list from the device.");
+    m.def("sample_cols_host", &sample_cols_host_impl, py::arg("F"), py::arg("colsample"), py::arg("seed") = 0, py::arg("draw") = 0,
+          "sample_cols_host(F, colsample, seed=0, draw=0) -> int32 NumPy array [k]\n\n"
+          "The column rule on the host (no device is needed): k = max(1, floor(colsample * F + 0.5)) of the columns 0 .. F - 1, those with the k smallest pairs\n"
+          "(u_f, f), u_f the row sampler's 24-bit hash of (seed ^ 0x636F6C73616D706C, draw, f); ascending.  colsample in (0, 1]; 1.0 gives arange(F).");
     py::class_<PyGBRL> g(m, "GBRL");
     g.def(py::init<int, int, int, int, int, int, int, float, std::string, std::string, bool, int, std::string, int, std::string, std::string>(),
           py::arg("input_dim") = 1, py::arg("output_dim") = 1, py::arg("policy_dim") = 1, py::arg("max_depth") = 4,
@@ -1032,12 +1082,27 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         g.def("prepare_dataset", [](PyGBRL &self, py::object &obs, py::object reference) { return prepare_dataset_impl(self, obs, reference); },
               doc.c_str(), py::arg("obs"), py::arg("reference"));
     }
-    g.def("step_prepared", &step_prepared_impl, py::arg("ds"), py::arg("grads"), py::arg("rows") = py::none(),
-          "step_prepared(ds, grads, rows=None)\n\n"
-          "One boosting step on a prepared data set: with rows=None the model ends up byte for byte as step(obs, None, grads) would leave it, without the\n"
-          "transpose, candidates and binning phases.  rows (int32 vector of length m, duplicates allowed, entries in [0, ds.n_rows)): the tree is grown on\n"
-          "those rows, grads [m, output_dim] in their order, with the DATA SET'S thresholds (as fit() uses whole-data-set candidates), not the subset's\n"
-          "quantiles.  Any model on the same device with the data set's n_bins and generator_type and input_dim == ds.n_features may step on it.");
+    {
+        // step_prepared(ds, grads, rows=None) keeps its generated signature line (tests compare it); the form with cols is a second overload described
+        // in words below that line, as prepare_dataset's reference is
+        g.def("step_prepared", [](PyGBRL &self, py::object ds, py::object &grads, py::object &rows) { step_prepared_impl(self, ds, grads, rows); }, py::arg("ds"),
+              py::arg("grads"), py::arg("rows") = py::none());
+        const std::string sig = py::str(g.attr("step_prepared").attr("__doc__"));
+        const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
+            "step_prepared(ds, grads, rows=None, cols=None)\n\n"
+            "One boosting step on a prepared data set: with rows=None the model ends up byte for byte as step(obs, None, grads) would leave it, without the\n"
+            "transpose, candidates and binning phases.  rows (int32 vector of length m, duplicates allowed, entries in [0, ds.n_rows)): the tree is grown on\n"
+            "those rows, grads [m, output_dim] in their order, with the DATA SET'S thresholds (as fit() uses whole-data-set candidates), not the subset's\n"
+            "quantiles.  Any model on the same device with the data set's n_bins and generator_type and input_dim == ds.n_features may step on it.\n"
+            "cols (host vector of ints, strictly ascending, entries in [0, ds.n_features), at least one): the tree is grown on those columns only -- their\n"
+            "histograms are the only ones built.  The model is what a model of input_dim len(cols) with feature weights w[cols] grows on\n"
+            "prepare_dataset(obs[:, cols]), with its conditions naming the data set's columns (feature index cols[f']).  The subset's code records (and\n"
+            "rows, in the same pass) are gathered on the device: phase 'gather_cols'.  cols naming every column is the call without cols.  Refused before\n"
+            "anything changes: unsorted, repeated or out-of-range entries, an empty vector.";
+        py::options opt;
+        opt.disable_function_signatures();
+        g.def("step_prepared", &step_prepared_impl, doc.c_str(), py::arg("ds"), py::arg("grads"), py::arg("rows") = py::none(), py::arg("cols"));
+    }
     g.def("condition_bins", &condition_bins_impl, py::arg("thresholds"),
           "condition_bins(thresholds) -> int32 array shaped like get_ensemble_data()['feature_values']\n\n"
           "thresholds: float32 [n_features, n_bins], e.g. PreparedDataset.thresholds().  A used numeric condition x[f] > v gets bin = number of thresholds of f\n"
@@ -1054,7 +1119,8 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         g.def("fit_prepared", &fit_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
-            "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, seed=0) -> float | dict\n\n"
+            "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0)\n"
+            "    -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
             "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
@@ -1072,12 +1138,18 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "rows are drawn and their gradient rows gathered on the device in one pass; the tree is what step_prepared(ds, g[rows - start], rows=rows) grows.\n"
             "A draw that keeps no row of the batch takes the whole batch.  A fresh draw per tree, never with replacement.  The returned loss and valid_loss are\n"
             "on all rows, as without sampling.  subsample == 1.0 is the unsampled loop itself, whatever seed is.  Refused before anything changes: a subsample\n"
-            "that is NaN or outside [2**-24, 1].";
+            "that is NaN or outside [2**-24, 1].\n"
+            "colsample=q < 1.0 (with or without subsample and valid=): every tree is grown on k = max(1, floor(q * n_features + 0.5)) of the columns, those\n"
+            "gbrl_cpp.sample_cols_host(n_features, q, seed, draw) / ds.sample_cols(q, seed, draw) names at draw = the tree count before the step, with the\n"
+            "row sampler's seed; the tree is what step_prepared(..., cols=those) grows, and rows and columns are gathered in one pass.  Trees carry the\n"
+            "data set's feature indices; the held prediction, valid_loss and the loss see all columns.  colsample == 1.0 (and a draw of every column, as\n"
+            "with one feature) is the call without it: fit_prepared(..., subsample=1.0, seed=0) and fit_prepared(..., subsample=1.0, colsample=1.0, seed=0)\n"
+            "run the same code.  Refused before anything changes: a colsample that is NaN or outside (0, 1].";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_valid_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
-              py::arg("seed") = 0);
+              py::arg("colsample") = 1.0, py::arg("seed") = 0);
     }
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);

@@ -514,6 +514,34 @@ int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const 
     });
 }
 
+// ---- column subsets of a data set (gather_cols.hip): a step on them, their codes, the column rule on the host, the kernel's geometry
+int gbrl_hip_step_prepared_cols(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *grads, int grads_on_device, const int32_t *rows,
+                                int rows_on_device, int n_rows, const int32_t *cols, int n_cols) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        if (cols == nullptr) throw gbrl::InvalidArgument("step_prepared: null cols");
+        m->engine.step_prepared(&live_dataset(ds), grads, grads_on_device != 0, rows, rows_on_device != 0, n_rows, cols, n_cols);
+    });
+}
+
+int gbrl_hip_dataset_codes_cols(const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const int32_t *cols, int n_cols,
+                                uint16_t *out) {
+    return guarded([&] {
+        const gbrl::PreparedDataset &d = live_dataset(ds);
+        if (cols == nullptr) throw gbrl::InvalidArgument("dataset_codes: null cols");
+        d.codes_to_host(rows, rows_on_device != 0, n_rows, out, cols, n_cols);
+    });
+}
+
+int gbrl_hip_sample_cols_host(int n_features, double colsample, uint64_t seed, int draw, int32_t *out, int *count) {
+    return guarded([&] { gbrl::Engine::sample_cols_host(n_features, colsample, seed, draw, out, count); });
+}
+
+void gbrl_hip_gather_cols_geometry(int *rows_per_tile, int *max_staged_groups) {
+    if (rows_per_tile) *rows_per_tile = gbrl::kern::kGatherColsRows;
+    if (max_staged_groups) *max_staged_groups = gbrl::kern::kGatherColsMaxStaged;
+}
+
 // ---- the walk over a data set's bin codes
 int gbrl_hip_condition_bins(const gbrl_hip_model *m, const float *thresholds, int n_features, int n_bins, int32_t *out) {
     return guarded([&] {
@@ -605,21 +633,30 @@ int gbrl_hip_fit_prepared_sampled(gbrl_hip_model *m, const gbrl_hip_dataset *ds,
                                   const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
                                   double min_delta, double subsample, uint64_t seed, float *loss_out, double *valid_loss_out, int *iterations_done,
                                   int *best_n_trees) {
+    return gbrl_hip_fit_prepared_colsampled(m, ds, targets, targets_on_device, iterations, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds,
+                                            min_delta, subsample, 1.0, seed, loss_out, valid_loss_out, iterations_done, best_n_trees);
+}
+
+int gbrl_hip_fit_prepared_colsampled(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
+                                     const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                     double min_delta, double subsample, double colsample, uint64_t seed, float *loss_out, double *valid_loss_out,
+                                     int *iterations_done, int *best_n_trees) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");
         m->engine.precheck_fit_prepared(targets, iterations);
         gbrl::Engine::check_subsample("fit_prepared", subsample);
+        gbrl::Engine::check_colsample("fit_prepared", colsample);
         if (valid_ds == nullptr) {
             if (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr)
                 throw gbrl::InvalidArgument("fit_prepared: valid_targets, early_stopping_rounds, min_delta and valid_loss_out need a validation set");
-            const float loss = m->engine.fit_prepared_sampled(&live_dataset(ds), targets, targets_on_device != 0, iterations, nullptr, subsample, seed);
+            const float loss = m->engine.fit_prepared_colsampled(&live_dataset(ds), targets, targets_on_device != 0, iterations, nullptr, subsample, colsample, seed);
             if (loss_out) *loss_out = loss;
             if (iterations_done) *iterations_done = iterations;
             return;
         }
         m->engine.precheck_fit_valid(valid_targets, early_stopping_rounds, min_delta);
         gbrl::Engine::FitValid v{&live_dataset(valid_ds), valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0};
-        const float loss = m->engine.fit_prepared_sampled(&live_dataset(ds), targets, targets_on_device != 0, iterations, &v, subsample, seed);
+        const float loss = m->engine.fit_prepared_colsampled(&live_dataset(ds), targets, targets_on_device != 0, iterations, &v, subsample, colsample, seed);
         if (loss_out) *loss_out = loss;
         if (iterations_done) *iterations_done = v.done;
         if (best_n_trees) *best_n_trees = v.best_n_trees;

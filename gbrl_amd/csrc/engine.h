@@ -100,7 +100,8 @@ class PreparedDataset {
     }
     // the codes on the host (diagnostics; the data set's device, the null stream): out [G][m][16]; rows == nullptr: every row (m = n), else what
     // kern::gather_code_records gives for rows (int32 [m], host or device, every entry in [0, n) or InvalidArgument)
-    void codes_to_host(const int32_t *rows, bool rows_dev, int m, uint16_t *out) const;
+    // cols (host, as Engine::step_prepared's): out [ceil(n_cols / 16)][m][16], the subset's records from kern::gather_code_columns
+    void codes_to_host(const int32_t *rows, bool rows_dev, int m, uint16_t *out, const int32_t *cols = nullptr, int n_cols = 0) const;
 };
 
 namespace detail {
@@ -151,7 +152,15 @@ class Engine {
     // no keys, no feature-major codes and no root table: a step on it hands them over as null, as a subset step does.  Refused before the
     // device is touched: what check_prepared_dataset refuses about (model, reference), n <= 0, null obs.  The model is never changed.
     PreparedDataset *prepare_dataset_like(const PreparedDataset *ref, const float *obs, bool obs_dev, int n);
-    void step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m);
+    // cols (host int32 [n_cols], strictly ascending, entries in [0, ds->F), 1 <= n_cols <= F; anything else is InvalidArgument before anything
+    // changes): the tree is grown on those columns only.  The records of the subset (and of rows, in the same pass: kern::gather_code_columns), the
+    // thresholds and their keys are gathered into the workspace, the growth paths run on F' = n_cols features with the candidate weight the full
+    // step gives feature cols[f'], and every condition's feature index is rewritten through cols before the tree is appended: the model is what
+    // a model of input_dim F' with feature weights w[cols] grows on prepare_dataset(obs[:, cols]), with A's indices == cols[B's].  Ascending
+    // order keeps the tie rule (the lowest candidate index wins).  cols covering every column is the call without cols.
+    void step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m, const int32_t *cols = nullptr,
+                       int n_cols = 0);
+    static void check_cols(const char *what, const int32_t *cols, int n_cols, int F);   // the rule above (cols non-null)
     // Extension (engine_fit_prepared.hip): the walk over a data set's bin codes.  code(r, f) = #{b : thr[f][b] < obs[r, f]}, so a numeric condition
     // x[f] > v whose v is one of thr[f][*] is code > bin with bin = #{b : thr[f][b] < v} (include/gbrl_hip.h has the argument).
     // condition_bins: host only.  out has the length and indexing of feature_values; a used numeric slot (d < depths[split row]) gets its bin,
@@ -199,7 +208,17 @@ class Engine {
     // are up to date, draws the rows of the batch with draw = the tree count before the step (a continued fit continues the sequence), gathers
     // their gradient rows in the same pass, reads m back (4 bytes) and grows on (rows, gathered gradients).  A draw that keeps no row takes the
     // whole batch, as the unsampled iteration does.  Batches, validation, stopping, the final advance and the loss are the unsampled loop's.
-    float fit_prepared_sampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed);
+    // (the call is fit_prepared_colsampled below, which adds the column fraction)
+    // Extension: column subsampling (colsample_bytree / feature_fraction).  The rule is sample_core.h's: k = max(1, floor(colsample * F + 0.5))
+    // columns, the k smallest (u_f, f) with u_f the 24-bit hash of (seed ^ "colsampl", draw, f), ascending.  Host only.  sample_cols_host: out
+    // [F], *count = k.  Refused (InvalidArgument): F < 1, draw < 0, a colsample that is NaN or outside (0, 1], null outputs.
+    static void check_colsample(const char *what, double colsample);
+    static void sample_cols_host(int F, double colsample, uint64_t seed, int draw, int32_t *out, int *count);
+    // The sampled loop above growing every tree on a column subset as well: per iteration the columns of draw = the tree count before the step
+    // (the row sampler's seed and draw), step_prepared's cols path on them.  colsample == 1.0, or a draw that keeps every column (F == 1): the
+    // loop above itself.  The held prediction, validation, the stopping rule and the loss see all rows and all columns.
+    float fit_prepared_colsampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, double colsample,
+                                  uint64_t seed);
     // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
     // min_delta (a NaN never improves); *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = best at that point
     static void early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
@@ -356,7 +375,7 @@ class Engine {
     void check_prepared_model(const char *what) const;                   // numeric-only, one GPU, step()'s limits: raised before the device is touched
     void check_prepared_dataset(const char *what, const PreparedDataset *ds) const;   // the data set is there and is this model's: device, n_bins, generator, width
     // step_prepared behind its argument checks and input staging: statistics, growth, append on device gradients and (nullable) device rows
-    void step_prepared_run(const PreparedDataset *ds, const float *dgrads, const int32_t *d_rows, int m);
+    void step_prepared_run(const PreparedDataset *ds, const float *dgrads, const int32_t *d_rows, int m, const int32_t *cols = nullptr, int n_cols = 0);
     void begin_step_profile();   // a step's phase list starts here
     // ---- conditions as bin indices of ONE threshold table (engine_fit_prepared.hip): host tables appended split row by split row, their device
     // copies appended behind sync_model_to_device().  Keyed on the data set's thresholds_id: data sets that share thresholds share the tables
@@ -432,6 +451,8 @@ class Engine {
     size_t leafacc_clean_bytes_ = 0;
     PrepBuffers prep_ws_;             // step()'s numeric preparation; step_prepared(rows) gathers the subset's codes into prep_ws_.codes
     DevBuf d_sub_rows_, d_rows_mm_;   // step_prepared(rows): device copy of a host index vector, min / max of a device one
+    DevBuf d_cols_plan_;              // step_prepared(cols): the gather plan (kern::gather_cols_plan); the subset's thresholds and keys go to prep_ws_
+    std::vector<int32_t> cols_plan_host_, fit_cols_;   // its host copy (alive until the step has waited for the stream); fit_prepared's column draw
     uint64_t code_ds_id_ = 0;         // the thresholds id the code tables below are for (0: none)
     size_t code_splits_ = 0, code_up_splits_ = 0, code_nodes_ = 0, code_up_nodes_ = 0;   // split rows / greedy node records converted on the host, and on the device
     std::vector<int32_t> code_bins_host_, code_pack_host_, code_nodes_host_;   // bins [S][MD] (-1 unused or categorical, -2 inexpressible), cond_pack and grd_nodes with the bin as their second word
@@ -440,7 +461,7 @@ class Engine {
     DevBuf d_fp_vpred_, d_fp_vtargets_, d_fp_vpart_, d_fp_vsums_;   // its validation rows: held prediction [n_v][D], staged targets, loss partials, one sum per iteration
     DevBuf d_fp_srows_, d_fp_sgrads_, d_fp_sscratch_;   // its sampled iterations: the kept rows of the batch, their gradient rows, block counts + m
     float fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample = 1.0,
-                            uint64_t seed = 0);
+                            uint64_t seed = 0, double colsample = 1.0);
     // rows [start, start + bn) of a data set's held prediction P (valid through `through` trees) advanced to every tree the model has, with the
     // gradient tail (targets, grad_out) and / or the loss tail (loss_targets, loss_part) of kern::predict_continue_codes; targets are [n][D]
     void advance_held(const PreparedDataset &ds, float *P, int &through, int start, int bn, const float *targets, float *grad_out,

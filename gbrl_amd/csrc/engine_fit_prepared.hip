@@ -7,8 +7,9 @@
 //   Engine::fit_prepared               fit()'s loop with the running prediction held and the batch never binned again
 //   Engine::fit_prepared_valid         the same loop watching a validation set that shares the thresholds: a second held prediction advanced after
 //                                      every iteration (advance_held, the loss tail of the code walk), Engine::early_stop_scan's rule
-//   Engine::fit_prepared_sampled       the same loop growing every tree on a sample of its batch (sample_core.h): kern::sample_rows draws the rows
+//   Engine::fit_prepared_colsampled    the same loop growing every tree on a sample of its batch (sample_core.h): kern::sample_rows draws the rows
 //                                      and gathers their gradient rows in one pass, 4 bytes come back, step_prepared's body grows on the subset
+//                                      ... and on a sample of the columns: the host rule of sample_core.h per iteration, step_prepared's cols path
 //
 // The rule.  code(r, f) = #{b : thr[f][b] < obs[r, f]} (-0.0 == +0.0; NaN lies below every threshold: code 0).  For a condition x > v whose v
 // equals some thr[f][b] let bin = #{b : thr[f][b] < v}.  x > v: every threshold below v, and v itself, is below x, so code >= bin + 1.
@@ -249,14 +250,17 @@ float Engine::fit_prepared_valid(const PreparedDataset *ds, const float *targets
     return fit_prepared_loop(ds, targets, targets_dev, iterations, &v);
 }
 
-float Engine::fit_prepared_sampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed) {
-    return fit_prepared_loop(ds, targets, targets_dev, iterations, v, subsample, seed);
+float Engine::fit_prepared_colsampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, double colsample,
+                                      uint64_t seed) {
+    return fit_prepared_loop(ds, targets, targets_dev, iterations, v, subsample, seed, colsample);
 }
 
-float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed) {
+float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed,
+                                double colsample) {
     gbrl_hip_metadata &md = model.meta;
     precheck_fit_prepared(targets, iterations);
     check_subsample("fit_prepared", subsample);
+    check_colsample("fit_prepared", colsample);
     if (v) precheck_fit_valid(v->targets, v->rounds, v->min_delta);
     check_prepared_dataset("fit_prepared", ds);
     if (v) {
@@ -359,6 +363,8 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
         Gs = static_cast<float *>(d_fp_sgrads_.ensure(sizeof(float) * static_cast<size_t>(cap) * D));
         d_sscratch = static_cast<int32_t *>(d_fp_sscratch_.ensure(sizeof(int32_t) * (static_cast<size_t>(kern::sample_rows_blocks(cap)) + 1)));
     }
+    // ---- a column-sampled fit: a draw of k < F columns per tree (colsample == 1.0, or k == F: step_prepared_run never sees cols)
+    const bool colsampled = colsample < 1.0 && kern::sample_cols_count(ds->F, colsample) < ds->F;
     int start = 0, done = 0;
     int bn = start + bs < n ? bs : n - start;                                   // fitter.cpp:120
     for (int i = 0; i < iterations; ++i) {
@@ -378,7 +384,12 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
             hip_check(hipStreamSynchronize(s), "sync");
             if (kept > 0) { g = Gs; rows = d_srows; m = kept; }
         }
-        step_prepared_run(ds, g, rows, m);
+        if (colsampled) {   // draw = the tree count before the step, the row sampler's seed
+            kern::sample_cols(ds->F, colsample, seed, md.n_trees, fit_cols_);
+            step_prepared_run(ds, g, rows, m, fit_cols_.data(), static_cast<int>(fit_cols_.size()));
+        } else {
+            step_prepared_run(ds, g, rows, m);
+        }
         start += bn;                                                            // fitter.cpp:228-231
         if (start >= n) start = 0;
         bn = start + bs < n ? bs : n - start;

@@ -7,7 +7,10 @@
 //                             the engine's workspace and grows on them with the DATA SET'S thresholds; keys, feature-major codes and the root's
 //                             count table are handed over as null there (legal inputs of every growth path: the partition then reads the
 //                             codes, the root histogram counts its rows).
-//   PreparedDataset::codes_to_host   the codes on the host, all rows or a gathered subset
+//                             A column subset (cols) gathers the subset's columns of those records -- rows and columns in one pass,
+//                             kern::gather_code_columns -- and the subset's thresholds and keys, grows on F' = n_cols features with the full
+//                             step's candidate weights and rewrites the conditions' feature indices through cols before the tree is appended.
+//   PreparedDataset::codes_to_host   the codes on the host, all rows or a gathered subset of rows and / or columns
 //   Engine::sample_rows_host / sample_rows / sample_gather   the row sampler of sample_core.h: the rule on the host, kern::sample_rows on a data
 //                             set's row range, and with the gathered rows of a matrix (what fit_prepared's sampled iterations enqueue)
 // None of the growth kernels is touched: integer histograms do not depend on which of the optional buffers a path reads.
@@ -161,7 +164,18 @@ void Engine::begin_step_profile() {
     exch_calls_ = 0;
 }
 
-void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m) {
+void Engine::check_cols(const char *what, const int32_t *cols, int n_cols, int F) {
+    const std::string w(what);
+    if (n_cols < 1 || n_cols > F) throw InvalidArgument(w + ": cols must name between 1 and " + std::to_string(F) + " columns, got " + std::to_string(n_cols));
+    for (int i = 0; i < n_cols; ++i) {
+        if (cols[i] < 0 || cols[i] >= F)
+            throw InvalidArgument(w + ": cols: index " + std::to_string(cols[i]) + " (entry " + std::to_string(i) + ") is outside [0, " + std::to_string(F) + ")");
+        if (i > 0 && cols[i] <= cols[i - 1])
+            throw InvalidArgument(w + ": cols must be strictly ascending (entry " + std::to_string(i) + " is " + std::to_string(cols[i]) + " after " + std::to_string(cols[i - 1]) + ")");
+    }
+}
+
+void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m, const int32_t *cols, int n_cols) {
     gbrl_hip_metadata &md = model.meta;
     check_prepared_dataset("step_prepared", ds);
     if (grads == nullptr) throw InvalidArgument("Cannot call step without grads!");
@@ -172,6 +186,10 @@ void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool g
     if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
     if (md.output_dim > 512) throw Unsupported("output_dim > 512");
     if (rows != nullptr && !rows_dev) check_host_rows(rows, m, ds->n);
+    if (cols != nullptr) {
+        check_cols("step_prepared", cols, n_cols, ds->F);
+        if (n_cols == ds->F) cols = nullptr;   // every column, in order: the call without cols
+    }
     ensure_device();
     begin_step_profile();
     hipStream_t s = stream_;
@@ -185,18 +203,19 @@ void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool g
     }
     const int32_t *d_rows = rows ? checked_rows(d_sub_rows_, d_rows_mm_, rows, rows_dev, m, ds->n, s) : nullptr;
     phase_end("inputs");
-    step_prepared_run(ds, dgrads, d_rows, m);
+    step_prepared_run(ds, dgrads, d_rows, m, cols, n_cols);
 }
 
 // One boosting step on device inputs that have been checked (fit_prepared's loop body too): the phase list is the caller's (begin_step_profile).
-void Engine::step_prepared_run(const PreparedDataset *ds, const float *dgrads, const int32_t *d_rows, int m) {
+// cols (host, checked, a proper subset; null: every column): the step grows on those columns.
+void Engine::step_prepared_run(const PreparedDataset *ds, const float *dgrads, const int32_t *d_rows, int m, const int32_t *cols, int n_cols) {
     gbrl_hip_metadata &md = model.meta;
     // GBRL::step, gbrl.cpp:946-958 (the latch is taken back when the step fails: the model is unchanged after any failure)
     const int32_t keep_num = md.n_num_features, keep_cat = md.n_cat_features;
     if (md.iteration == 0) { md.n_num_features = ds->F; md.n_cat_features = 0; }
     try {
         hipStream_t s = stream_;
-        const int N = m, F = ds->F, D = md.output_dim;
+        const int N = m, F = cols ? n_cols : ds->F, D = md.output_dim;
         const bool cosine = md.split_score_func == GBRL_HIP_SCORE_COSINE;
         long long n_global = N;
         prof_marks_[0] = std::chrono::steady_clock::now();
@@ -212,7 +231,21 @@ void Engine::step_prepared_run(const PreparedDataset *ds, const float *dgrads, c
         phase_end("grad_stats");
         // ---- the subset's code records (the thresholds stay the data set's) ---------------------------------------
         NumericPrep np = ds->prep;
-        if (d_rows) {
+        if (cols) {
+            // rows and columns in one pass over the codes; the subset's rows of the threshold table and of its keys beside them
+            phase_begin();
+            const kern::GatherColsPlan plan = kern::gather_cols_plan(cols, n_cols, cols_plan_host_);
+            const int32_t *d_plan = upload(d_cols_plan_, cols_plan_host_.data(), plan.n_words, "H2D column plan");
+            const size_t n_thr = static_cast<size_t>(n_cols) * ds->n_bins;
+            uint16_t *sub = static_cast<uint16_t *>(prep_ws_.codes.ensure(sizeof(uint16_t) * static_cast<size_t>(plan.n_out_groups) * N * kern::kCodeGroup));
+            float *thr = static_cast<float *>(prep_ws_.thr.ensure(sizeof(float) * n_thr));
+            uint32_t *thrkeys = static_cast<uint32_t *>(prep_ws_.thrkeys.ensure(sizeof(uint32_t) * n_thr));
+            kern::gather_code_columns(ds->prep.d_codes, ds->n, d_rows, N, d_plan, plan, sub, s);
+            kern::gather_threshold_rows(ds->prep.d_thr, ds->prep.d_thrkeys, ds->n_bins, d_plan, plan, thr, thrkeys, s);
+            phase_end("gather_cols");
+            np = NumericPrep{};
+            np.d_codes = sub; np.d_thr = thr; np.d_thrkeys = thrkeys;
+        } else if (d_rows) {
             phase_begin();
             const int G = ds->code_groups();
             uint16_t *sub = static_cast<uint16_t *>(prep_ws_.codes.ensure(sizeof(uint16_t) * static_cast<size_t>(G) * N * kern::kCodeGroup));
@@ -228,13 +261,16 @@ void Engine::step_prepared_run(const PreparedDataset *ds, const float *dgrads, c
         const std::vector<int> cat_classes;
         StepData sd{};
         sd.N = N; sd.F = F; sd.Fc = 0; sd.n_global = n_global; sd.chunk_rows = gs.chunk_rows; sd.prep = np; sd.stats = &gs;
-        sd.cat_cands = &cat_cands; sd.cat_classes = &cat_classes;
+        sd.cat_cands = &cat_cands; sd.cat_classes = &cat_classes; sd.cols = cols;
         std::vector<HNode> nodes;
         std::vector<int> frontier;
         std::vector<int64_t> acc;
         double leaf_scale = 1.0;
         grow_step_tree(sd, nodes, frontier, acc, leaf_scale);
         hip_check(hipGetLastError(), "step kernels");
+        if (cols)   // the tree names the data set's columns
+            for (HNode &nd : nodes)
+                for (HCond &c : nd.path) c.feat_idx = cols[c.feat_idx];
         append_tree(model, nodes, frontier, acc, leaf_scale, cat_cands);
         phases_resolve();
     } catch (...) {
@@ -251,18 +287,29 @@ struct DeviceScope {   // a data set's device for one call, the caller's afterwa
 };
 }  // namespace
 
-void PreparedDataset::codes_to_host(const int32_t *rows, bool rows_dev, int m, uint16_t *out) const {
+void PreparedDataset::codes_to_host(const int32_t *rows, bool rows_dev, int m, uint16_t *out, const int32_t *cols, int n_cols) const {
     if (out == nullptr) throw InvalidArgument("dataset_codes: no place for the codes");
     if (rows == nullptr) m = n;
     if (m <= 0) throw InvalidArgument("dataset_codes: no rows (m must be positive)");
     if (rows != nullptr && !rows_dev) check_host_rows(rows, m, n);
+    if (cols != nullptr) Engine::check_cols("dataset_codes", cols, n_cols, F);
     DeviceScope scope(device);
     hipStream_t s = nullptr;
-    const int G = code_groups();
+    const int G = cols ? (n_cols + kern::kCodeGroup - 1) / kern::kCodeGroup : code_groups();
     const size_t bytes = sizeof(uint16_t) * static_cast<size_t>(G) * m * kern::kCodeGroup;
     const uint16_t *src = prep.d_codes;
-    DevBuf sub, rows_copy, mm;
-    if (rows != nullptr) {
+    DevBuf sub, rows_copy, mm, plan_buf;
+    std::vector<int32_t> plan_words;   // (alive until the wait below)
+    if (cols != nullptr) {
+        const int32_t *d_rows = rows ? checked_rows(rows_copy, mm, rows, rows_dev, m, n, s) : nullptr;
+        const kern::GatherColsPlan plan = kern::gather_cols_plan(cols, n_cols, plan_words);
+        int32_t *d_plan = static_cast<int32_t *>(plan_buf.ensure(sizeof(int32_t) * plan.n_words));
+        hip_check(hipMemcpyAsync(d_plan, plan_words.data(), sizeof(int32_t) * plan.n_words, hipMemcpyHostToDevice, s), "H2D column plan");
+        uint16_t *dst = static_cast<uint16_t *>(sub.ensure(bytes));
+        kern::gather_code_columns(prep.d_codes, n, d_rows, m, d_plan, plan, dst, s);
+        hip_check(hipGetLastError(), "gather_code_columns launch");
+        src = dst;
+    } else if (rows != nullptr) {
         const int32_t *d_rows = checked_rows(rows_copy, mm, rows, rows_dev, m, n, s);
         uint16_t *dst = static_cast<uint16_t *>(sub.ensure(bytes));
         kern::gather_code_records(prep.d_codes, n, G, d_rows, m, dst, s);
@@ -290,6 +337,22 @@ void check_sample_range(const char *what, int row0, int n, double subsample, int
     if (row0 > std::numeric_limits<int32_t>::max() - (n - 1)) throw InvalidArgument(w + ": the range ends above row 2^31 - 1");
 }
 }  // namespace
+
+void Engine::check_colsample(const char *what, double colsample) {
+    if (!kern::sample_cols_fraction_ok(colsample))
+        throw InvalidArgument(std::string(what) + ": colsample must be in (0, 1] (and not NaN), got " + std::to_string(colsample));
+}
+
+void Engine::sample_cols_host(int F, double colsample, uint64_t seed, int draw, int32_t *out, int *count) {
+    if (out == nullptr || count == nullptr) throw InvalidArgument("sample_cols_host: null output");
+    if (F < 1) throw InvalidArgument("sample_cols_host: no columns (F must be positive)");
+    if (draw < 0) throw InvalidArgument("sample_cols_host: draw must be >= 0");
+    check_colsample("sample_cols_host", colsample);
+    std::vector<int32_t> cols;
+    kern::sample_cols(F, colsample, seed, draw, cols);
+    std::copy(cols.begin(), cols.end(), out);
+    *count = static_cast<int>(cols.size());
+}
 
 void Engine::sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, int *count) {
     check_sample_range("sample_rows_host", row0, n, subsample, draw, out, count);

@@ -331,10 +331,13 @@ void Engine::grow_step_tree(const StepData &sd, std::vector<HNode> &nodes, std::
     std::vector<int> ref_to_internal_local;
     // numeric-only steps: these constants depend on (F, n_bins, policy, feature weights, feature mapping) only -- built once, kept in
     // Engine::step_const_ together with their uploaded copy (grow_tree)
-    const bool const_cacheable = Fc == 0 && F > 0;
+    // A column subset (sd.cols) builds its tables locally, and overwrites the device staging block on its way: the cached upload is dropped,
+    // the host tables of the full step stay.
+    const bool const_cacheable = Fc == 0 && F > 0 && sd.cols == nullptr;
     // mixed steps: the numeric candidates come first in every table and are the same from step to step -- only the categorical
     // tails (this batch's candidates) are rebuilt and uploaded (51 200 numeric against ~2 000 categorical entries at configs[4])
     const bool prefix_cacheable = Fc > 0 && F > 0;
+    if (sd.cols != nullptr) step_const_.dev_base = nullptr;
     bool reuse = false;
     if (const_cacheable || prefix_cacheable) {
         StepConstCache &cc = step_const_;
@@ -378,7 +381,8 @@ void Engine::grow_step_tree(const StepData &sd, std::vector<HNode> &nodes, std::
                     const int j = slots[f].cand_base + k;
                     cand_ref[j] = f * B + k;
                     // feature weight: greedy indexes by feature_idx, oblivious by the reverse mapping (fitter.cpp:331 vs 432-434, Q6)
-                    const int wi = oblivious ? model.reverse_num[f] : f;
+                    const int mf = sd.cols ? sd.cols[f] : f;
+                    const int wi = oblivious ? model.reverse_num[mf] : mf;
                     cand_w[j] = (wi >= 0 && wi < md.input_dim) ? model.feature_weights[wi] : 0.0f;
                 }
             for (int j = 0; j < n_num_cand; ++j) ref_to_internal[cand_ref[j]] = j;

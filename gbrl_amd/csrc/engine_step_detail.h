@@ -119,6 +119,7 @@ struct StepData {
     const FusedStats *stats;
     const std::vector<CatCandidate> *cat_cands;
     const std::vector<int> *cat_classes;
+    const int32_t *cols = nullptr;      // step_prepared(cols): feature f of this step is the model's feature cols[f] (its candidate weight; host, F entries)
 };
 
 }  // namespace detail

@@ -4,7 +4,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace gbrl {
 namespace kern {
@@ -199,6 +201,23 @@ void gather_code_records(const uint16_t *codes /*[n_groups][n][16]*/, int n, int
 void bin_like(const float *obs, int n, int F, const uint32_t *thr_keys, int B, uint16_t *codes /*[ceil(F/16)][n][16]*/, hipStream_t s);
 // mm[0] = min rows[j], mm[1] = min ~rows[j] (= ~max) of a device index vector, m >= 1
 void rows_minmax(const int32_t *rows, int m, int32_t *mm /*[2], device*/, hipStream_t s);
+// column subsets of a prepared data set (gather_cols.hip): out[g'][j][i] = codes[cols[16 g' + i] / 16][rows ? rows[j] : j][cols[16 g' + i] % 16],
+// the padding slots of the last output group zero.  cols (host, strictly ascending, every entry in [0, 16 * source groups)) is turned into a plan
+// on the host -- the output groups cut into chunks of at most kGatherColsMaxStaged source groups, the source groups of every chunk, the tile
+// offset of every output slot, cols itself -- which the caller uploads (n_words int32, 16-byte aligned) before the launch.  One kernel for every
+// shape; a block owns kGatherColsRows rows.  rows as gather_code_records.
+constexpr int kGatherColsRows = 64, kGatherColsMaxStaged = 16;
+struct GatherColsPlan {
+    int n_cols, n_out_groups, n_chunks, max_staged;   // max_staged: the most source groups a chunk stages
+    int chunks_at, groups_at, offs_at, cols_at;       // word offsets into the plan
+    size_t n_words, staged_groups;                    // staged_groups: source groups staged per row tile over all chunks (the records a row reads)
+};
+GatherColsPlan gather_cols_plan(const int32_t *cols, int n_cols, std::vector<int32_t> &words);
+void gather_code_columns(const uint16_t *codes /*[groups][n][16]*/, int n, const int32_t *rows /*[m], device, nullable*/, int m, const int32_t *d_plan,
+                         const GatherColsPlan &p, uint16_t *out /*[p.n_out_groups][m][16]*/, hipStream_t s);
+// thr_out[f'][b] = thr[cols[f']][b] and the same for the keys ([F][B] tables, cols from the plan)
+void gather_threshold_rows(const float *thr, const uint32_t *thr_keys, int B, const int32_t *d_plan, const GatherColsPlan &p, float *thr_out, uint32_t *keys_out,
+                           hipStream_t s);
 // the row sampler on the device (sample_rows.hip; the rule is sample_core.h's): rows_out[0 .. m) = the kept rows of [row0, row0 + n), ascending,
 // as absolute indices; scratch[0] = m; with G (device [n][D], row r - row0 for row r) also G_out[j][:] = G[rows_out[j] - row0][:] in the same
 // pass.  Three launches (count, a one-block scan of the block counts, write), positions from ranks only: the bytes do not depend on scheduling.

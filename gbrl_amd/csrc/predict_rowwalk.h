@@ -4,7 +4,7 @@
 //   model views    LeavesModel (routing: leaves_model) and ChainModel (routing + values, rates, bias: chain_model); the rate rule is chain_rates
 //   row accessors  how a walk reads a numeric condition of its row: floats against the threshold (GeneralRow, a float tile row) or a prepared
 //                  data set's bin codes against the condition's bin (GeneralCodeRow, StreamCodeRow; x > v <=> code > bin, engine_fit_prepared.hip).
-//                  Every walk below takes the row as a template parameter; the staging of a code tile is stream_stage_code_tile
+//                  Every walk below takes the row as a template parameter; the staging of a code tile is stream_stage_code_tile / _groups
 //   general side   one thread per row, rows in global memory, anything the file format can hold: general_test, general_leaf (the reference's
 //                  walk; greedy: leaf by leaf, Q7), general_apply (every optimizer that owns the output, in order) and general_chain_tree
 //                  (one tree of the chain: k_continue_general's loop body, and k_staged_general's between two checkpoints)
@@ -212,8 +212,12 @@ __device__ __forceinline__ void stream_stage_tile(float *tile, const float *__re
 // each half of the wave) never meets a bank twice.  The records are group-major in memory, [G][N][16]: lane `lane` names the data set row of
 // tile row `lane` (my_row; any valid row for a lane without one), and the G * 128 half-records travel as 16-byte loads, two lanes per record,
 // 16 in flight per lane.  The caller synchronises the block afterwards.
+// stream_stage_code_groups is the same staging for a LIST of groups: tile group i holds the records of data set group group_of(i) (gather_cols.hip
+// stages only the groups that hold a selected column).
 __device__ __forceinline__ int stream_code_stride(int G) { return (G * 8) | 1; }
-__device__ __forceinline__ void stream_stage_code_tile(uint32_t *tile, const uint16_t *__restrict__ codes, size_t N, int G, int my_row, int rows, int lane) {
+template <typename GroupOf>
+__device__ __forceinline__ void stream_stage_code_groups(uint32_t *tile, const uint16_t *__restrict__ codes, size_t N, int G, GroupOf group_of, int my_row, int rows,
+                                                         int lane) {
     const int ws = stream_code_stride(G);
     const uint4 *src4 = reinterpret_cast<const uint4 *>(codes);
     const int tot = G * 2 * kStreamRows;   // half-records of the block: [group][tile row][half]
@@ -225,7 +229,7 @@ __device__ __forceinline__ void stream_stage_code_tile(uint32_t *tile, const uin
             const int i = i0 + u * kStreamRows;
             const int j = (i & (2 * kStreamRows - 1)) >> 1;
             const int src_row = __shfl(my_row, j);   // (every lane takes part: i0 < tot is wave-uniform, tot is a multiple of 64)
-            v[u] = (i < tot && j < rows) ? src4[((static_cast<size_t>(i >> 7) * N + static_cast<size_t>(src_row)) << 1) + (i & 1)] : make_uint4(0u, 0u, 0u, 0u);
+            v[u] = (i < tot && j < rows) ? src4[((static_cast<size_t>(group_of(i >> 7)) * N + static_cast<size_t>(src_row)) << 1) + (i & 1)] : make_uint4(0u, 0u, 0u, 0u);
         }
 #pragma unroll
         for (int u = 0; u < UL; ++u) {
@@ -237,6 +241,9 @@ __device__ __forceinline__ void stream_stage_code_tile(uint32_t *tile, const uin
             }
         }
     }
+}
+__device__ __forceinline__ void stream_stage_code_tile(uint32_t *tile, const uint16_t *__restrict__ codes, size_t N, int G, int my_row, int rows, int lane) {
+    stream_stage_code_groups(tile, codes, N, G, [](int g) { return g; }, my_row, rows, lane);
 }
 
 // the lane's row in the LDS tile: floats against a condition's threshold bits, or the u16 codes of a code tile against its bin

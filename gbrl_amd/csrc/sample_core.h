@@ -11,9 +11,19 @@
 //   the row is kept  <=>  u < thr                       (subsample == 1: u < 2^24 always -- no special case)
 //
 // The sample of a row range is the ascending list of its kept rows: without replacement, independent of how the range is cut into launches.
+//
+// The column rule of fit_prepared(colsample=) and PreparedDataset.sample_cols (host only: F is a few thousand at most).  For F columns, a
+// fraction colsample in (0, 1] (not NaN), a seed and a draw:
+//   k   = max(1, floor(colsample * F + 0.5))            in double; never above F
+//   u_f = sample_u24(seed ^ 0x636F6C73616D706C, draw, f)   ("colsampl": a stream of its own beside the row sampler's)
+//   the kept columns are the k smallest pairs (u_f, f), returned ascending in f
+// Exactly k columns whatever the hash does (a Bernoulli rule varies too much at F = 16 and needs an empty-draw case); colsample == 1 keeps all.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -38,6 +48,24 @@ GBRL_SAMPLE_HD inline bool sample_keeps(uint64_t seed, int32_t draw, uint32_t ro
 // a fraction the sampler takes: not NaN, in [2^-24, 1]
 inline bool sample_fraction_ok(double subsample) { return subsample >= 1.0 / 16777216.0 && subsample <= 1.0; }
 inline uint32_t sample_threshold(double subsample) { return static_cast<uint32_t>(subsample * 16777216.0); }   // (floor: the product is positive)
+
+
+// the column rule (see the head of the file)
+constexpr uint64_t kSampleColsStream = 0x636F6C73616D706Cull;
+inline bool sample_cols_fraction_ok(double colsample) { return colsample > 0.0 && colsample <= 1.0; }   // (false for a NaN)
+inline int sample_cols_count(int F, double colsample) {
+    const double k = static_cast<double>(static_cast<long long>(colsample * static_cast<double>(F) + 0.5));   // (floor: the sum is positive)
+    return static_cast<int>(std::min<double>(F, std::max(1.0, k)));
+}
+inline void sample_cols(int F, double colsample, uint64_t seed, int32_t draw, std::vector<int32_t> &out) {
+    const int k = sample_cols_count(F, colsample);
+    std::vector<std::pair<uint32_t, int32_t>> u(static_cast<size_t>(F));
+    for (int f = 0; f < F; ++f) u[f] = {sample_u24(seed ^ kSampleColsStream, draw, static_cast<uint32_t>(f)), f};
+    std::partial_sort(u.begin(), u.begin() + k, u.end());
+    out.resize(static_cast<size_t>(k));
+    for (int i = 0; i < k; ++i) out[i] = u[i].second;
+    std::sort(out.begin(), out.end());
+}
 
 }  // namespace kern
 }  // namespace gbrl

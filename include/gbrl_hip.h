@@ -430,7 +430,34 @@ int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const 
  *     rows_out int32 [n] and grads_out [n, output_dim] are DEVICE buffers; grads_out[j] = grads[rows_out[j] - row0] (16-byte accesses when
  *     output_dim % 4 == 0 and both matrices are 16-byte aligned, 4-byte accesses otherwise).  grads and grads_out may both be NULL.
  *   gbrl_hip_sample_rows_geometry(rows_per_block, scan_width)  the rows one block of the sampler owns and the block counts one slice of its scan
- *     takes (diagnostic; no device needed): the sizes at which the kernels take another path. */
+ *     takes (diagnostic; no device needed): the sizes at which the kernels take another path.
+ *
+ * Column subsampling (new: the other half of stochastic gradient boosting -- LightGBM's feature_fraction, XGBoost's colsample_bytree,
+ * scikit-learn's max_features per tree).  A weight of 0 (gbrl_hip_set_feature_weights) only removes a column's candidates from the arg-max; a
+ * column subset skips the column's histogram.  The column rule is a definition, on the host, with the row sampler's 24-bit hash u(seed, draw, x):
+ *     k   = max(1, floor(colsample * F + 0.5))                  in double; colsample in (0, 1], NaN refused; 1.0 keeps every column
+ *     u_f = u(seed ^ 0x636F6C73616D706C, draw, f)               f = 0 .. F - 1
+ *     the kept columns are the k smallest pairs (u_f, f), returned ascending in f            (always exactly k columns)
+ *   gbrl_hip_sample_cols_host(n_features, colsample, seed, draw, out, count)  the rule: out[0 .. *count) (room for n_features), no device.  Refused
+ *     (GBRL_HIP_E_INVALID): n_features < 1, draw < 0, a colsample that is NaN or outside (0, 1], NULL out or count.
+ *   gbrl_hip_step_prepared_cols(m, ds, grads, grads_on_device, rows, rows_on_device, n_rows, cols, n_cols)  gbrl_hip_step_prepared growing on the
+ *     columns cols only: a HOST int32 vector, strictly ascending, entries in [0, n_features), 1 <= n_cols <= n_features; anything else is refused
+ *     (GBRL_HIP_E_INVALID) before anything changes.  The 32-byte code records are re-packed into ceil(n_cols / 16) groups -- rows, when given, in the
+ *     same pass -- with the thresholds of those columns, and every growth path runs on n_cols features.  The model is what a model of input_dim
+ *     n_cols with feature weights w[cols] grows on a data set of obs[:, cols], except that its conditions name the data set's columns (feature
+ *     index cols[f']): ascending order keeps the tie rule (the lowest candidate index wins), and the candidate weight of column c is what the
+ *     full step uses for feature c.  The model still latches n_num_features = n_features.  cols naming every column is gbrl_hip_step_prepared:
+ *     no gather, the same bytes and phases.  Phase `gather_cols` (gbrl_hip_last_phase_times); `gather_codes` stays the row-only gather.
+ *   gbrl_hip_dataset_codes_cols(ds, rows, rows_on_device, n_rows, cols, n_cols, out)  gbrl_hip_dataset_codes for a column subset: out
+ *     [ceil(n_cols / 16)][m][16], out[g][j][i] = the code of column cols[16 g + i] and row rows[j] (rows NULL: every row), padding slots 0.
+ *   gbrl_hip_fit_prepared_colsampled(.., subsample, colsample, seed, ..)  gbrl_hip_fit_prepared_sampled plus colsample; the older fit_prepared calls
+ *     are this call with colsample == 1.0, which runs their code itself whatever seed is.  Otherwise iteration i draws its columns with the rule
+ *     above at draw = the tree count BEFORE the step and the row sampler's seed, and grows as gbrl_hip_step_prepared_cols does (on the sampled
+ *     rows when subsample < 1: one pass over the codes).  A draw of all columns (n_features == 1, or a fraction that rounds to it) is the step
+ *     without cols.  The held prediction, validation, the stopping rule and the loss see all rows and all columns; trees carry data set
+ *     feature indices and thresholds.  Refused before anything changes: a bad colsample, and what gbrl_hip_fit_prepared_sampled refuses.
+ *   gbrl_hip_gather_cols_geometry(rows_per_tile, max_staged_groups)  the rows one block of the column gather owns, and the source groups it
+ *     stages at a time: a subset that touches more is walked in chunks by the same kernel (diagnostic; no device needed). */
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
@@ -441,6 +468,16 @@ int gbrl_hip_fit_prepared_sampled(gbrl_hip_model *m, const gbrl_hip_dataset *ds,
 int gbrl_hip_sample_gather(int row0, int n, double subsample, uint64_t seed, int draw, const float *grads, int output_dim, int32_t *rows_out,
                            float *grads_out, int *count);
 void gbrl_hip_sample_rows_geometry(int *rows_per_block, int *scan_width);
+int gbrl_hip_sample_cols_host(int n_features, double colsample, uint64_t seed, int draw, int32_t *out /*[n_features]*/, int *count);
+int gbrl_hip_step_prepared_cols(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *grads, int grads_on_device, const int32_t *rows,
+                                int rows_on_device, int n_rows, const int32_t *cols /*host*/, int n_cols);
+int gbrl_hip_dataset_codes_cols(const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const int32_t *cols /*host*/, int n_cols,
+                                uint16_t *out /*[ceil(n_cols / 16)][m][16]*/);
+int gbrl_hip_fit_prepared_colsampled(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
+                                     const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                     double min_delta, double subsample, double colsample, uint64_t seed, float *loss_out,
+                                     double *valid_loss_out /*[iterations + 1]*/, int *iterations_done, int *best_n_trees);
+void gbrl_hip_gather_cols_geometry(int *rows_per_tile, int *max_staged_groups);
 int gbrl_hip_condition_bins(const gbrl_hip_model *m, const float *thresholds /*[F*B]*/, int n_features, int n_bins, int32_t *out);
 gbrl_hip_dataset *gbrl_hip_dataset_create_like(gbrl_hip_model *m, const gbrl_hip_dataset *reference, const float *obs, int obs_on_device, int n_samples);
 uint64_t gbrl_hip_dataset_thresholds_id(const gbrl_hip_dataset *ds);
