@@ -141,6 +141,11 @@ int parse_parity_mode(const std::string &s) {
     return parse_enum(s, {{"default", GBRL_HIP_PARITY_DEFAULT}, {"reference", GBRL_HIP_PARITY_REFERENCE}, {"exact_argmax", GBRL_HIP_PARITY_EXACT_ARGMAX}},
                       "Invalid parity mode! Options are: default/reference/exact_argmax");
 }
+// objective names of fit_prepared(objective=), objective_gradient and objective_gradient_host (GBRL_HIP_OBJ_*, include/gbrl_hip.h)
+int parse_objective(const std::string &s) {
+    return parse_enum(s, {{"rmse", GBRL_HIP_OBJ_RMSE}, {"logistic", GBRL_HIP_OBJ_LOGISTIC}, {"softmax", GBRL_HIP_OBJ_SOFTMAX}},
+                      "Invalid objective! Options are: rmse/logistic/softmax");
+}
 const char *parity_mode_name(int mode) {
     return mode == GBRL_HIP_PARITY_REFERENCE ? "reference" : (mode == GBRL_HIP_PARITY_EXACT_ARGMAX ? "exact_argmax" : "default");
 }
@@ -809,10 +814,53 @@ float fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, in
 
 // fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0):
 // a float without a validation set (the three validation arguments at their defaults), else a dict; subsample / colsample / seed go with either
+// the targets of an objective: float32 [n, D] ([n] when D == 1) for rmse and logistic, int32 [n] labels for softmax
+Input read_objective_targets(py::object &targets, const char *name, bool none_allowed, const std::string &fn, int objective, int n, int D, bool check_shape) {
+    if (objective != GBRL_HIP_OBJ_SOFTMAX) {
+        Input t = read_input(targets, name, none_allowed, fn, false);
+        if (check_shape && t.ptr) check_rows_by_outputs(t, name, n, D);
+        return t;
+    }
+    Input t = read_input(targets, name, none_allowed, fn, 2);
+    if (check_shape && t.ptr && !(t.shape.size() == 1 && t.shape[0] == static_cast<size_t>(n))) {
+        std::stringstream ss;
+        ss << "Expected " << name << " of the softmax objective as int32 class labels of shape (" << n << ",)";
+        fail(ss.str());
+    }
+    return t;
+}
+
 py::object fit_prepared_valid_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
-                                   int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed) {
+                                   int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const int objective = parse_objective(objective_name);
+    if (objective != GBRL_HIP_OBJ_RMSE) {   // (rmse: the code below as it was)
+        if (valid_obj.is_none() && (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0))
+            fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
+        const gbrl_hip_dataset *dsv = valid_obj.is_none() ? nullptr : valid_obj.cast<const PyDataset &>().h;
+        Input t = read_objective_targets(targets, "targets", false, "fit", objective, ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, md.output_dim, ds != nullptr);
+        Input tv;
+        if (dsv) tv = read_objective_targets(valid_targets, "valid_targets", true, "fit", objective, valid_obj.cast<const PyDataset &>().info().n_rows, md.output_dim, true);
+        std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0);
+        float loss = 0.0f;
+        int rc, done = 0, best = 0;
+        {
+            py::gil_scoped_release release;
+            rc = gbrl_hip_fit_prepared_objective(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                                 colsample, seed, objective, &loss, dsv ? curve.data() : nullptr, &done, &best);
+        }
+        check(rc);
+        if (!dsv) return py::float_(loss);
+        py::array_t<double> vl(static_cast<py::ssize_t>(done) + 1);
+        std::copy(curve.begin(), curve.begin() + done + 1, vl.mutable_data());
+        py::dict out;
+        out["loss"] = py::float_(loss);
+        out["valid_loss"] = vl;
+        out["iterations"] = py::int_(done);
+        out["best_n_trees"] = py::int_(best);
+        return std::move(out);
+    }
     if (valid_obj.is_none()) {
         if (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0)
             fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
@@ -850,6 +898,72 @@ py::object fit_prepared_valid_impl(PyGBRL &self, py::object ds_obj, py::object &
     out["valid_loss"] = vl;
     out["iterations"] = py::int_(done);
     out["best_n_trees"] = py::int_(best);
+    return std::move(out);
+}
+
+// objective_gradient(pred, targets, objective) -> (grad, loss): NumPy in, NumPy out; a device tuple gives a DLPack capsule on the model's device
+py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name) {
+    const gbrl_hip_metadata md = self.meta();
+    const int objective = parse_objective(objective_name), D = md.output_dim;
+    Input p = read_input(pred, "pred", false, "objective_gradient", false);
+    if (!p.ptr) fail("Cannot call objective_gradient without pred!");
+    const int n = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
+    check_rows_by_outputs(p, "pred", n, D);
+    Input t = read_objective_targets(targets, "targets", false, "objective_gradient", objective, n, D, true);
+    if (!t.ptr) fail("Cannot call objective_gradient without targets!");
+    const size_t n_el = std::max<size_t>(static_cast<size_t>(n) * D, 1);
+    float *g = nullptr;
+    int dev_id = 0;
+    if (p.on_device) {
+        dev_id = gbrl_hip_device_ordinal(self.h);
+        if (dev_id < 0) fail(gbrl_hip_last_error());
+        g = static_cast<float *>(gbrl_hip_device_alloc_on(dev_id, sizeof(float) * n_el));
+        if (!g) fail(gbrl_hip_last_error());
+    } else {
+        g = new float[n_el];
+    }
+    double loss = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_objective_gradient(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, n, objective, g, &loss);
+    }
+    if (rc != GBRL_HIP_OK) {
+        if (p.on_device) gbrl_hip_device_free(g); else delete[] g;
+        fail(gbrl_hip_last_error());
+    }
+    std::vector<int64_t> shape(p.shape.begin(), p.shape.end());
+    if (p.on_device) return py::make_tuple(make_dlpack(g, shape, true, dev_id), py::float_(loss));
+    py::capsule owner(g, [](void *q) { delete[] static_cast<float *>(q); });
+    return py::make_tuple(py::array_t<float>(std::vector<py::ssize_t>(shape.begin(), shape.end()), g, owner), py::float_(loss));
+}
+
+// the gradient rule on the host (include/gbrl_hip.h, "Classification objectives"): no device, no model
+py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &targets, const std::string &objective_name) {
+    const int objective = parse_objective(objective_name);
+    Input p = read_input(pred, "pred", false, "objective_gradient_host", false);
+    if (p.on_device) fail("objective_gradient_host takes NumPy arrays");
+    if (p.shape.empty() || p.shape.size() > 2) fail("pred must be a float32 array of shape (n, D) or (n,)");
+    const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
+    Input t = read_objective_targets(targets, "targets", false, "objective_gradient_host", objective, n, D, true);
+    if (t.on_device) fail("objective_gradient_host takes NumPy arrays");
+    py::array_t<float> out(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
+    float none = 0.0f;
+    check(gbrl_hip_objective_gradient_host(static_cast<const float *>(p.ptr), t.ptr, n, D, objective, out.size() ? out.mutable_data() : &none));
+    return out;
+}
+
+py::object objective_exp_host_impl(py::array_t<float, py::array::c_style | py::array::forcecast> t, bool rounded) {
+    const std::vector<py::ssize_t> shape(t.shape(), t.shape() + t.ndim());
+    float none = 0.0f;
+    if (rounded) {
+        py::array_t<float> out(shape);
+        check(gbrl_hip_objective_exp_host(t.size() ? t.data() : &none, static_cast<int>(t.size()), nullptr, t.size() ? out.mutable_data() : &none));
+        return std::move(out);
+    }
+    py::array_t<double> out(shape);
+    double none64 = 0.0;
+    check(gbrl_hip_objective_exp_host(t.size() ? t.data() : &none, static_cast<int>(t.size()), t.size() ? out.mutable_data() : &none64, nullptr));
     return std::move(out);
 }
 
@@ -1028,6 +1142,15 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "sample_rows_host(n, subsample, seed=0, draw=0, row0=0) -> int32 NumPy array [m]\n\n"
           "The row sampler's rule on the host (no device is needed): the rows of [row0, row0 + n) that (seed, draw) keeps at `subsample`, ascending.\n"
           "PreparedDataset.sample_rows returns the same list from the device.");
+    m.def("objective_gradient_host", &objective_gradient_host_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"),
+          "objective_gradient_host(pred, targets, objective) -> float32 NumPy array shaped like pred\n\n"
+          "The gradient rule of fit_prepared(objective=) on the host (no device is needed): 'logistic': sigmoid(p) - y, targets float32 like pred;\n"
+          "'softmax': softmax(p) - onehot(y), targets int32 [n] labels in [0, D), D >= 2; 'rmse': p - y.  Every float32 step is the one definition the\n"
+          "kernels use (an exponential written out in fmaf, correctly rounded division): the device gives the same bits.");
+    m.def("objective_exp_host", &objective_exp_host_impl, py::arg("t"), py::arg("rounded") = false,
+          "objective_exp_host(t, rounded=False) -> NumPy array shaped like t\n\n"
+          "obj_exp of the objectives (include/gbrl_hip.h): exp(t) for t <= 0 in explicit float32 steps, +0 below -104 -- the value p * 2^k itself as\n"
+          "float64, or with rounded=True that value rounded once to float32 (obj_exp_f32: what the gradients use).  Diagnostic, host only.");
     m.def("sample_cols_host", &sample_cols_host_impl, py::arg("F"), py::arg("colsample"), py::arg("seed") = 0, py::arg("draw") = 0,
           "sample_cols_host(F, colsample, seed=0, draw=0) -> int32 NumPy array [k]\n\n"
           "The column rule on the host (no device is needed): k = max(1, floor(colsample * F + 0.5)) of the columns 0 .. F - 1, those with the k smallest pairs\n"
@@ -1119,8 +1242,8 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         g.def("fit_prepared", &fit_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
-            "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0)\n"
-            "    -> float | dict\n\n"
+            "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,\n"
+            "             objective='rmse') -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
             "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
@@ -1144,13 +1267,26 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "row sampler's seed; the tree is what step_prepared(..., cols=those) grows, and rows and columns are gathered in one pass.  Trees carry the\n"
             "data set's feature indices; the held prediction, valid_loss and the loss see all columns.  colsample == 1.0 (and a draw of every column, as\n"
             "with one feature) is the call without it: fit_prepared(..., subsample=1.0, seed=0) and fit_prepared(..., subsample=1.0, colsample=1.0, seed=0)\n"
-            "run the same code.  Refused before anything changes: a colsample that is NaN or outside (0, 1].";
+            "run the same code.  Refused before anything changes: a colsample that is NaN or outside (0, 1].\n"
+            "objective='logistic' | 'softmax' (with everything above): the loop with that loss in place of MultiRMSE.  logistic: targets float32 [n, D], D\n"
+            "independent outputs, g = sigmoid(p) - y.  softmax: targets int32 [n] class labels in [0, D), D >= 2, g = softmax(p) - onehot(y).  The gradient is\n"
+            "gbrl_cpp.objective_gradient_host / GBRL.objective_gradient bit for bit, written by the launch that advances the held prediction.  A fresh model's\n"
+            "bias is the log odds of the column means (clamped to [1/2n, 1 - 1/2n]) or the log class frequencies (an empty class counts 0.5 rows).  'loss' and\n"
+            "'valid_loss' are the mean loss per row (not a square root); predict returns raw scores: apply sigmoid / softmax yourself.  objective='rmse' is\n"
+            "the call without the keyword.  Refused before anything changes: an unknown objective, softmax on a model with one output, float targets\n"
+            "where labels are wanted and the reverse, a label outside [0, D).";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_valid_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
-              py::arg("colsample") = 1.0, py::arg("seed") = 0);
+              py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse");
     }
+    g.def("objective_gradient", &objective_gradient_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"),
+          "objective_gradient(pred, targets, objective) -> (grad, loss)\n\n"
+          "The gradient dL/dp [n, output_dim] and the loss of the raw scores pred under objective 'rmse' | 'logistic' | 'softmax', computed on the model's\n"
+          "device by the device functions fit_prepared(objective=) runs: grad is gbrl_cpp.objective_gradient_host(pred, targets, objective) bit for bit.\n"
+          "targets: float32 [n, output_dim] (rmse, logistic) or int32 [n] labels (softmax).  NumPy in, NumPy out; a device tuple for pred gives a DLPack\n"
+          "capsule.  loss: the mean row loss in float64 (rmse: the MultiRMSE expression), reduced in a fixed order: two calls give the same bits.");
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);
     }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("return_torch") = false);

@@ -16,6 +16,7 @@
 
 #include "../../include/gbrl_hip.h"
 #include "engine.h"
+#include "objective_core.h"
 #include "hooks.h"
 #include "explain.h"
 #include "rccl_dyn.h"
@@ -641,25 +642,60 @@ int gbrl_hip_fit_prepared_colsampled(gbrl_hip_model *m, const gbrl_hip_dataset *
                                      const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
                                      double min_delta, double subsample, double colsample, uint64_t seed, float *loss_out, double *valid_loss_out,
                                      int *iterations_done, int *best_n_trees) {
+    return gbrl_hip_fit_prepared_objective(m, ds, targets, targets_on_device, iterations, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds,
+                                           min_delta, subsample, colsample, seed, GBRL_HIP_OBJ_RMSE, loss_out, valid_loss_out, iterations_done, best_n_trees);
+}
+
+// ---- classification objectives: fit_prepared with one, the gradient and loss of a prediction matrix, the gradient rule on the host
+static_assert(gbrl::kern::kObjRmse == GBRL_HIP_OBJ_RMSE && gbrl::kern::kObjLogistic == GBRL_HIP_OBJ_LOGISTIC && gbrl::kern::kObjSoftmax == GBRL_HIP_OBJ_SOFTMAX,
+              "the kernels' objectives are the header's");
+int gbrl_hip_fit_prepared_objective(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                                    const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                    double min_delta, double subsample, double colsample, uint64_t seed, int objective, float *loss_out,
+                                    double *valid_loss_out, int *iterations_done, int *best_n_trees) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");
         m->engine.precheck_fit_prepared(targets, iterations);
         gbrl::Engine::check_subsample("fit_prepared", subsample);
         gbrl::Engine::check_colsample("fit_prepared", colsample);
+        gbrl::Engine::check_objective("fit_prepared", objective, m->engine.model.meta.output_dim);
         if (valid_ds == nullptr) {
             if (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr)
                 throw gbrl::InvalidArgument("fit_prepared: valid_targets, early_stopping_rounds, min_delta and valid_loss_out need a validation set");
-            const float loss = m->engine.fit_prepared_colsampled(&live_dataset(ds), targets, targets_on_device != 0, iterations, nullptr, subsample, colsample, seed);
+            const float loss = m->engine.fit_prepared_objective(&live_dataset(ds), targets, targets_on_device != 0, iterations, nullptr, subsample, colsample, seed, objective);
             if (loss_out) *loss_out = loss;
             if (iterations_done) *iterations_done = iterations;
             return;
         }
         m->engine.precheck_fit_valid(valid_targets, early_stopping_rounds, min_delta);
         gbrl::Engine::FitValid v{&live_dataset(valid_ds), valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0};
-        const float loss = m->engine.fit_prepared_colsampled(&live_dataset(ds), targets, targets_on_device != 0, iterations, &v, subsample, colsample, seed);
+        const float loss = m->engine.fit_prepared_objective(&live_dataset(ds), targets, targets_on_device != 0, iterations, &v, subsample, colsample, seed, objective);
         if (loss_out) *loss_out = loss;
         if (iterations_done) *iterations_done = v.done;
         if (best_n_trees) *best_n_trees = v.best_n_trees;
+    });
+}
+
+int gbrl_hip_objective_gradient(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective,
+                                float *grad_out, double *loss_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.objective_gradient(pred, pred_on_device != 0, targets, targets_on_device != 0, n, objective, grad_out, loss_out);
+    });
+}
+
+int gbrl_hip_objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out) {
+    return guarded([&] { gbrl::Engine::objective_gradient_host(pred, targets, n, D, objective, grad_out); });
+}
+
+int gbrl_hip_objective_exp_host(const float *t, int n, double *out, float *out_f32) {
+    return guarded([&] {
+        if (t == nullptr || (out == nullptr && out_f32 == nullptr)) throw gbrl::InvalidArgument("objective_exp_host: null argument");
+        if (n < 0) throw gbrl::InvalidArgument("objective_exp_host: n must be >= 0");
+        for (int i = 0; i < n; ++i) {
+            if (out) out[i] = gbrl::kern::obj_exp(t[i]);
+            if (out_f32) out_f32[i] = gbrl::kern::obj_exp_f32(t[i]);
+        }
     });
 }
 

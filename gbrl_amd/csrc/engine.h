@@ -187,7 +187,7 @@ class Engine {
     // what fit_prepared(ds, targets, done) leaves, and the returned loss is its return value.  Refused before anything changes: another
     // thresholds id, null valid targets, rounds < 0, min_delta negative or NaN, and what fit_prepared refuses.
     struct FitValid {
-        const PreparedDataset *ds; const float *targets; bool targets_dev; int rounds; double min_delta;
+        const PreparedDataset *ds; const void *targets; bool targets_dev; int rounds; double min_delta;
         double *loss_out /*[iterations + 1]*/; int done, best_n_trees;
     };
     float fit_prepared_valid(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid &v);
@@ -219,14 +219,30 @@ class Engine {
     // loop above itself.  The held prediction, validation, the stopping rule and the loss see all rows and all columns.
     float fit_prepared_colsampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, double colsample,
                                   uint64_t seed);
+    // Extension: classification objectives (objective_core.h has the definitions, kern::kObjRmse / kObjLogistic / kObjSoftmax the values).
+    // fit_prepared_objective is the loop above with the objective's gradient and loss in place of MultiRMSE's: kObjRmse runs that loop itself.
+    // logistic: targets float32 [n][D]; softmax: targets int32 [n], labels in [0, D) (v->targets likewise).  A fresh model's bias is, in double,
+    // logistic: log(c / (1 - c)) with c = clamp(column mean, 1 / 2n, 1 - 1 / 2n); softmax: log(max(n_c, 0.5) / n), n_c counted on the device
+    // (kern::label_counts, which also finds a label out of range).  valid_loss_out[k] and the returned loss are sum / rows in float64, the row
+    // losses reduced as MultiRMSE's are.  Refused before anything changes: an unknown objective, softmax with output_dim < 2, a label outside
+    // [0, D) (InvalidArgument naming the first one found), and what the loop above refuses.
+    static void check_objective(const char *what, int objective, int D);
+    float fit_prepared_objective(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, FitValid *v, double subsample, double colsample,
+                                 uint64_t seed, int objective);
+    // objective_gradient: grad_out [n][D] = dL/dp and / or *loss_out = the loss of pred [n][D] against targets under the objective, on the model's
+    // device and stream with D = output_dim (kern::objective_rows: the device functions of the code walk's tails).  grad_out is where pred is
+    // (device iff pred_dev); either output may be null, not both.  kObjRmse: g = fl32(p - y) and staged_loss's expression.
+    void objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out);
+    // the gradient rule on the host (no device): the same bits
+    static void objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out);
     // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
     // min_delta (a NaN never improves); *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = best at that point
     static void early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
-    void precheck_fit_valid(const float *valid_targets, int rounds, double min_delta) const;
+    void precheck_fit_valid(const void *valid_targets, int rounds, double min_delta) const;
     // what the two calls above refuse without looking at the data set, in their order (the C ABI runs it before it resolves the handle, so that
     // these refusals do not depend on a data set being at hand): the model checks of step_prepared, then fit_prepared's own arguments
     void precheck_prepared(const char *what) const { check_prepared_model(what); }
-    void precheck_fit_prepared(const float *targets, int iterations) const;
+    void precheck_fit_prepared(const void *targets, int iterations) const;
     void predict(const float *obs, bool obs_dev, const char *cat, bool cat_dev, int n, int n_num, int n_cat, int start_tree,
                  int stop_tree, float *out, bool out_dev);
     // Extension (not in the reference, which compares the 128-byte cells inside every predict call): the dictionary ids of a batch of
@@ -460,12 +476,16 @@ class Engine {
     DevBuf d_fp_pred_, d_fp_grads_, d_fp_iota_, d_fp_targets_;   // fit_prepared: held prediction [n][D], batch gradients, 0..n-1, staged targets
     DevBuf d_fp_vpred_, d_fp_vtargets_, d_fp_vpart_, d_fp_vsums_;   // its validation rows: held prediction [n_v][D], staged targets, loss partials, one sum per iteration
     DevBuf d_fp_srows_, d_fp_sgrads_, d_fp_sscratch_;   // its sampled iterations: the kept rows of the batch, their gradient rows, block counts + m
-    float fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample = 1.0,
-                            uint64_t seed = 0, double colsample = 1.0);
+    DevBuf d_obj_pred_, d_obj_targets_, d_obj_grad_, d_obj_part_, d_obj_sum_, d_obj_counts_;   // objective_gradient: staged inputs, the gradient, loss partials and sum; class counts + first bad row
+    float fit_prepared_loop(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, FitValid *v, double subsample = 1.0,
+                            uint64_t seed = 0, double colsample = 1.0, int objective = 0);
+    // class counts of device labels [n] (counts, when given: [D]); a label outside [0, D) is InvalidArgument naming the first such row
+    void check_labels(const char *what, const int32_t *d_labels, int n, int D, std::vector<int32_t> *counts);
     // rows [start, start + bn) of a data set's held prediction P (valid through `through` trees) advanced to every tree the model has, with the
     // gradient tail (targets, grad_out) and / or the loss tail (loss_targets, loss_part) of kern::predict_continue_codes; targets are [n][D]
+    // (softmax: one int32 label per row behind the float pointers)
     void advance_held(const PreparedDataset &ds, float *P, int &through, int start, int bn, const float *targets, float *grad_out,
-                      const float *loss_targets, double *loss_part, bool generic);
+                      const float *loss_targets, double *loss_part, bool generic, int objective = 0);
     DevBuf d_am_s_, d_near_list_, d_near_ent_, d_near_rep_, d_near_nr_, d_near_maps_, d_near_pos_, d_near_nrb_, d_near_vals_, d_near_means_, d_near_sums_, d_near_chains_, d_near_rowsort_, d_near_tiles_;   // near-tie replay (kern::near_tie_replay): runner-up per arg-max block, candidate lists, ordered row lists, replayed scores
     bool small_grow_off_ = false;     // latched after a failed launch / an abandoned grid barrier of the one-launch kernel: this engine keeps to the level loop
     long long small_grow_fallbacks_ = 0;   // trees the level loop grew after such a failure (diagnostics)

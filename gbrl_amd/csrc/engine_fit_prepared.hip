@@ -16,6 +16,7 @@
 // x <= v: only thresholds below v can be below x, so code <= bin.  Hence x > v <=> code > bin, with duplicated thresholds and in any order.
 // It does not hold for a v that is not among the feature's thresholds: such a condition is refused (Unsupported), never approximated.
 #include "engine_step_detail.h"
+#include "objective_core.h"
 #include "sample_core.h"
 
 namespace gbrl {
@@ -193,7 +194,7 @@ void Engine::predict_continue_prepared(const PreparedDataset *ds, const int32_t 
     finish("predict_continue_prepared launch", "predict", {{out_dev ? nullptr : out, dout, out_bytes, "D2H preds"}});
 }
 
-void Engine::precheck_fit_prepared(const float *targets, int iterations) const {
+void Engine::precheck_fit_prepared(const void *targets, int iterations) const {
     const gbrl_hip_metadata &md = model.meta;
     check_prepared_model("fit_prepared");
     if (targets == nullptr) throw InvalidArgument("Cannot call fit without targets!");
@@ -204,7 +205,7 @@ void Engine::precheck_fit_prepared(const float *targets, int iterations) const {
     if (md.output_dim > 128) throw Unsupported("predict: output_dim > 128");
 }
 
-void Engine::precheck_fit_valid(const float *valid_targets, int rounds, double min_delta) const {
+void Engine::precheck_fit_valid(const void *valid_targets, int rounds, double min_delta) const {
     if (valid_targets == nullptr) throw InvalidArgument("fit_prepared: a validation set needs valid_targets");
     if (rounds < 0) throw InvalidArgument("fit_prepared: early_stopping_rounds must be >= 0");
     if (!(min_delta >= 0.0)) throw InvalidArgument("fit_prepared: min_delta must be >= 0 (and not NaN)");
@@ -228,7 +229,7 @@ void Engine::early_stop_scan(const double *curve, int n, int rounds, double min_
 // the same pass; with loss_targets, the loss partials of the new P (bn rows, from partial 0).  A walk that ended in a trailing run of one-leaf
 // greedy trees applied nothing for them (it ran off the ensemble): it resumes at the first of them.
 void Engine::advance_held(const PreparedDataset &ds, float *P, int &through, int start, int bn, const float *targets, float *grad_out,
-                          const float *loss_targets, double *loss_part, bool generic) {
+                          const float *loss_targets, double *loss_part, bool generic, int objective) {
     const int T = model.meta.n_trees, D = model.meta.output_dim;
     int from = through;
     while (from > 0 && runs_on(model, from - 1)) --from;
@@ -236,9 +237,9 @@ void Engine::advance_held(const PreparedDataset &ds, float *P, int &through, int
     sync_model_to_device();
     const kern::CodeTables ct = sync_code_tables(ds);
     float *p = P + static_cast<size_t>(start) * D;
-    const size_t at = static_cast<size_t>(start) * D;
+    const size_t at = static_cast<size_t>(start) * (objective == kern::kObjSoftmax ? 1 : D);   // (softmax: a label per row)
     kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{ds.prep.d_codes, ds.n, ds.code_groups(), nullptr, start}, bn, from, T, p, p,
-                                 targets ? targets + at : nullptr, grad_out, loss_targets ? loss_targets + at : nullptr, loss_part, generic, stream_);
+                                 targets ? targets + at : nullptr, grad_out, loss_targets ? loss_targets + at : nullptr, loss_part, generic, stream_, objective);
     through = T;
 }
 
@@ -255,10 +256,95 @@ float Engine::fit_prepared_colsampled(const PreparedDataset *ds, const float *ta
     return fit_prepared_loop(ds, targets, targets_dev, iterations, v, subsample, seed, colsample);
 }
 
-float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed,
-                                double colsample) {
+float Engine::fit_prepared_objective(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, FitValid *v, double subsample,
+                                     double colsample, uint64_t seed, int objective) {
+    return fit_prepared_loop(ds, targets, targets_dev, iterations, v, subsample, seed, colsample, objective);
+}
+
+void Engine::check_objective(const char *what, int objective, int D) {
+    if (objective != kern::kObjRmse && objective != kern::kObjLogistic && objective != kern::kObjSoftmax)
+        throw InvalidArgument(std::string(what) + ": unknown objective " + std::to_string(objective) + " (rmse = 0, logistic = 1, softmax = 2)");
+    if (objective == kern::kObjSoftmax && D < 2)
+        throw InvalidArgument(std::string(what) + ": the softmax objective needs output_dim >= 2, the model has " + std::to_string(D));
+}
+
+void Engine::check_labels(const char *what, const int32_t *d_labels, int n, int D, std::vector<int32_t> *counts) {
+    hipStream_t s = stream_;
+    std::vector<int32_t> h(static_cast<size_t>(D) + 1, 0);
+    h[D] = 0x7fffffff;
+    int32_t *d = upload(d_obj_counts_, h.data(), h.size(), "H2D label counts");
+    kern::label_counts(d_labels, n, D, d, s);
+    hip_check(hipMemcpyAsync(h.data(), d, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, s), "D2H label counts");
+    hip_check(hipStreamSynchronize(s), "sync");
+    if (h[D] != 0x7fffffff) {
+        int32_t bad = 0;
+        hip_check(hipMemcpyAsync(&bad, d_labels + h[D], sizeof(bad), hipMemcpyDeviceToHost, s), "D2H label");
+        hip_check(hipStreamSynchronize(s), "sync");
+        throw InvalidArgument(std::string(what) + ": label " + std::to_string(bad) + " (row " + std::to_string(h[D]) + ") is outside [0, " + std::to_string(D) + ")");
+    }
+    if (counts) counts->assign(h.begin(), h.begin() + D);
+}
+
+void Engine::objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out) {
+    if (pred == nullptr || targets == nullptr || grad_out == nullptr) throw InvalidArgument("objective_gradient_host: null argument");
+    if (n <= 0) throw InvalidArgument("objective_gradient_host: no rows (n must be positive)");
+    if (D < 1) throw InvalidArgument("objective_gradient_host: output_dim must be positive");
+    check_objective("objective_gradient_host", objective, D);
+    const size_t n_el = static_cast<size_t>(n) * D;
+    if (objective == kern::kObjSoftmax) {
+        const int32_t *labels = static_cast<const int32_t *>(targets);
+        for (int r = 0; r < n; ++r)
+            if (labels[r] < 0 || labels[r] >= D)
+                throw InvalidArgument("objective_gradient_host: label " + std::to_string(labels[r]) + " (row " + std::to_string(r) + ") is outside [0, " + std::to_string(D) + ")");
+        if (grad_out != pred) std::memmove(grad_out, pred, sizeof(float) * n_el);
+        for (int r = 0; r < n; ++r) {
+            float *row = grad_out + static_cast<size_t>(r) * D;
+            kern::obj_softmax_grad_row(row, D, labels[r]);
+        }
+        return;
+    }
+    const float *y = static_cast<const float *>(targets);
+    if (objective == kern::kObjLogistic)
+        for (size_t i = 0; i < n_el; ++i) grad_out[i] = kern::obj_logistic_grad(pred[i], y[i]);
+    else
+        for (size_t i = 0; i < n_el; ++i) grad_out[i] = pred[i] - y[i];
+}
+
+void Engine::objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out) {
+    const int D = model.meta.output_dim;
+    if (pred == nullptr || targets == nullptr) throw InvalidArgument("objective_gradient: null argument");
+    if (grad_out == nullptr && loss_out == nullptr) throw InvalidArgument("objective_gradient: no place for a result");
+    if (n <= 0) throw InvalidArgument("objective_gradient: no rows (n must be positive)");
+    if (D > 128) throw Unsupported("objective_gradient: output_dim > 128");
+    check_objective("objective_gradient", objective, D);
+    ensure_device();
+    hipStream_t s = stream_;
+    const size_t n_el = static_cast<size_t>(n) * D, tar_el = objective == kern::kObjSoftmax ? static_cast<size_t>(n) : n_el;
+    const float *dp = pred_dev ? pred : upload(d_obj_pred_, pred, n_el, "H2D predictions");
+    const float *dt = targets_dev ? static_cast<const float *>(targets) : upload(d_obj_targets_, static_cast<const float *>(targets), tar_el, "H2D targets");
+    if (objective == kern::kObjSoftmax) check_labels("objective_gradient", reinterpret_cast<const int32_t *>(dt), n, D, nullptr);
+    float *dg = grad_out == nullptr ? nullptr : (pred_dev ? grad_out : static_cast<float *>(d_obj_grad_.ensure(sizeof(float) * n_el)));
+    const int nb = kern::staged_loss_partials(n);
+    double *dpart = loss_out ? static_cast<double *>(d_obj_part_.ensure(sizeof(double) * nb)) : nullptr;
+    double *dsum = loss_out ? static_cast<double *>(d_obj_sum_.ensure(sizeof(double))) : nullptr;
+    kern::objective_rows(objective, dp, dt, n, D, dg, dpart, s);
+    double sum = 0.0;
+    if (loss_out) {
+        kern::staged_loss_finish(dpart, nb, dsum, s);
+        hip_check(hipMemcpyAsync(&sum, dsum, sizeof(double), hipMemcpyDeviceToHost, s), "D2H loss");
+    }
+    if (grad_out && !pred_dev) hip_check(hipMemcpyAsync(grad_out, dg, sizeof(float) * n_el, hipMemcpyDeviceToHost, s), "D2H gradient");
+    hip_check(hipGetLastError(), "objective_gradient kernels");
+    hip_check(hipStreamSynchronize(s), "sync");
+    if (loss_out) *loss_out = objective == kern::kObjRmse ? std::sqrt(0.5 * sum / static_cast<double>(n)) : sum / static_cast<double>(n);
+}
+
+float Engine::fit_prepared_loop(const PreparedDataset *ds, const void *targets_any, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed,
+                                double colsample, int objective) {
     gbrl_hip_metadata &md = model.meta;
+    const float *targets = static_cast<const float *>(targets_any);   // (softmax: int32 labels behind it, one per row)
     precheck_fit_prepared(targets, iterations);
+    check_objective("fit_prepared", objective, md.output_dim);
     check_subsample("fit_prepared", subsample);
     check_colsample("fit_prepared", colsample);
     if (v) precheck_fit_valid(v->targets, v->rounds, v->min_delta);
@@ -274,13 +360,21 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
     ensure_device();
     hipStream_t s = stream_;
     const int n = ds->n, D = md.output_dim;
+    const bool labels = objective == kern::kObjSoftmax;
+    const size_t tar_row = labels ? 1 : static_cast<size_t>(D);   // 4-byte entries of a row's targets
     auto staged = [&](DevBuf &buf, const float *host_or_dev, bool on_dev, int rows) -> const float * {
         if (on_dev) return host_or_dev;
-        float *t = static_cast<float *>(buf.ensure(sizeof(float) * static_cast<size_t>(rows) * D));
-        hip_check(hipMemcpyAsync(t, host_or_dev, sizeof(float) * static_cast<size_t>(rows) * D, hipMemcpyHostToDevice, s), "H2D targets");
+        float *t = static_cast<float *>(buf.ensure(sizeof(float) * static_cast<size_t>(rows) * tar_row));
+        hip_check(hipMemcpyAsync(t, host_or_dev, sizeof(float) * static_cast<size_t>(rows) * tar_row, hipMemcpyHostToDevice, s), "H2D targets");
         return t;
     };
     const float *dtar = staged(d_fp_targets_, targets, targets_dev, n);
+    const float *dvtar = v ? staged(d_fp_vtargets_, static_cast<const float *>(v->targets), v->targets_dev, v->ds->n) : nullptr;
+    std::vector<int32_t> class_counts;
+    if (labels) {   // refused before anything changes: a label outside [0, D), in either set
+        check_labels("fit_prepared", reinterpret_cast<const int32_t *>(dtar), n, D, &class_counts);
+        if (v) check_labels("fit_prepared (valid_targets)", reinterpret_cast<const int32_t *>(dvtar), v->ds->n, D, nullptr);
+    }
     // column sums and the loss: Engine::fit's own expressions (engine_step.hip)
     float *d_zero = static_cast<float *>(d_fit_zero_.ensure(sizeof(float) * D));
     hip_check(hipMemsetAsync(d_zero, 0, sizeof(float) * D, s), "memset");
@@ -301,8 +395,19 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
     };
     if (fresh) {
         // bias = column means of the targets (gbrl.cpp:1075-1077); the feature counts as step_prepared latches them
-        column_stat(dtar, n, nullptr);
-        for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(hs[d] / static_cast<double>(n));
+        if (objective == kern::kObjRmse) {
+            column_stat(dtar, n, nullptr);
+            for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(hs[d] / static_cast<double>(n));
+        } else if (objective == kern::kObjLogistic) {   // the log odds of the column mean, kept off 0 and 1 by half a row
+            column_stat(dtar, n, nullptr);
+            const double lo = 0.5 / static_cast<double>(n);
+            for (int d = 0; d < D; ++d) {
+                const double c = std::min(std::max(hs[d] / static_cast<double>(n), lo), 1.0 - lo);
+                model.bias[d] = static_cast<float>(std::log(c / (1.0 - c)));
+            }
+        } else {                                        // the log prior, an empty class counted as half a row
+            for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(std::log(std::max(static_cast<double>(class_counts[d]), 0.5) / static_cast<double>(n)));
+        }
         ++model.version;
         if (md.iteration == 0) { md.n_num_features = ds->F; md.n_cat_features = 0; }
     }
@@ -324,17 +429,20 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
         d_iota = d;
     }
     const bool generic = hooks::on(hooks::CONTINUE_GENERIC);
-    auto advance = [&](int start, int bn, float *grad_out) { advance_held(*ds, P, through[start / bs], start, bn, dtar, grad_out, nullptr, nullptr, generic); };
+    auto advance = [&](int start, int bn, float *grad_out) {
+        advance_held(*ds, P, through[start / bs], start, bn, grad_out ? dtar : nullptr, grad_out, nullptr, nullptr, generic, objective);
+    };
     // ---- the validation rows: a held prediction of their own, evaluated after every iteration by one launch + the finishing sum
     const int T0 = md.n_trees;
     const int nv = v ? v->ds->n : 0, nbv = v ? kern::staged_loss_partials(nv) : 0;
-    const float *dvtar = nullptr;
     float *Pv = nullptr;
     double *d_vpart = nullptr, *d_vsums = nullptr;
     int through_v = 0, best = 0;
-    auto curve_of = [&](double sum) { return std::sqrt(0.5 * sum / static_cast<double>(nv)); };   // staged_loss's expression
+    auto curve_of = [&](double sum) {   // staged_loss's expression; an objective's mean loss
+        return objective == kern::kObjRmse ? std::sqrt(0.5 * sum / static_cast<double>(nv)) : sum / static_cast<double>(nv);
+    };
     auto evaluate = [&](int k) {   // valid_loss[k]: on the device; with a stopping rule also on the host (one 8-byte read-back)
-        advance_held(*v->ds, Pv, through_v, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic);
+        advance_held(*v->ds, Pv, through_v, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, objective);
         kern::staged_loss_finish(d_vpart, nbv, d_vsums + k, s);
         if (v->rounds > 0) {
             double sum = 0.0;
@@ -344,7 +452,6 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
         }
     };
     if (v) {
-        dvtar = staged(d_fp_vtargets_, v->targets, v->targets_dev, nv);
         Pv = static_cast<float *>(d_fp_vpred_.ensure(sizeof(float) * static_cast<size_t>(nv) * D));
         d_vpart = static_cast<double *>(d_fp_vpart_.ensure(sizeof(double) * nbv));
         d_vsums = static_cast<double *>(d_fp_vsums_.ensure(sizeof(double) * (static_cast<size_t>(iterations) + 1)));
@@ -416,6 +523,18 @@ float Engine::fit_prepared_loop(const PreparedDataset *ds, const float *targets,
         v->best_n_trees = T0 + best;
     }
     // every batch to the end; the loss on the whole data set (fitter.cpp:246-251)
+    if (objective != kern::kObjRmse) {   // the objective's loss of the held prediction: the stand-alone kernel, the loss tail's partials and sum
+        for (int b0 = 0; b0 < n; b0 += bs) advance(b0, std::min(bs, n - b0), nullptr);
+        const int nb = kern::staged_loss_partials(n);
+        double *d_part = static_cast<double *>(d_obj_part_.ensure(sizeof(double) * nb)), *d_sum = static_cast<double *>(d_obj_sum_.ensure(sizeof(double)));
+        kern::objective_rows(objective, P, dtar, n, D, nullptr, d_part, s);
+        kern::staged_loss_finish(d_part, nb, d_sum, s);
+        double sum = 0.0;
+        hip_check(hipMemcpyAsync(&sum, d_sum, sizeof(double), hipMemcpyDeviceToHost, s), "D2H loss");
+        hip_check(hipGetLastError(), "fit_prepared kernels");
+        hip_check(hipStreamSynchronize(s), "sync");
+        return static_cast<float>(sum / static_cast<double>(n));
+    }
     for (int b0 = 0; b0 < n; b0 += bs) advance(b0, std::min(bs, n - b0), G + static_cast<size_t>(b0) * D);
     hip_check(hipGetLastError(), "fit_prepared kernels");
     return rmse(G, n);

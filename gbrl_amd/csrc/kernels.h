@@ -608,7 +608,19 @@ void predict_continue(const PredictModel &pm, const float *obs, int F, const int
 struct CodeTables { const int32_t *bins, *cond_pack, *grd_nodes; };
 struct CodeRows { const uint16_t *codes; int n_rows, groups; const int32_t *rows; int row0; };
 void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
-                            float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic, hipStream_t s);
+                            float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic, hipStream_t s,
+                            int objective = 0);
+// objective (kObjRmse / kObjLogistic / kObjSoftmax of objective_core.h) selects the two tails: logistic takes the same [m][D] float targets and
+// writes dL/dp of the sigmoid cross-entropy, its loss tail sums that loss; softmax takes ONE int32 label per row -- targets / loss_targets then
+// point at int32 [m] -- and writes softmax(p) - onehot.  A range without a tree runs the stand-alone kernel below on the copied base.
+//
+// The objectives on a prediction matrix (objective.hip): the device functions of the tails applied to pred [n][D] (device).  targets: float32
+// [n][D] (rmse, logistic) or int32 [n] (softmax; every label in [0, D): the caller checks, label_counts below).  grad_out (device [n][D]) and
+// loss_part (staged_loss_partials(n) doubles, one per 64 rows, finished by staged_loss_finish) may each be null.  D <= 128.
+void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s);
+// counts[c] += rows with label c (integer atomics; counts is device int32 [D + 1], ZEROED by the caller on `s` except counts[D] = INT32_MAX);
+// counts[D] = the smallest row index whose label is outside [0, D)
+void label_counts(const int32_t *labels, int n, int D, int32_t *counts, hipStream_t s);
 void tile_rows(const float *row /*[D], device*/, int D, int n, float *out /*[n][D]*/, hipStream_t s);   // out[r] = row: fit_prepared's held prediction starts as the bias
 // Every prefix [0, stops[s]) of the ensemble in one walk (predict_staged.hip): stage s has the bits of predict_continue(tiled bias, 0, stops[s]);
 // stops[s] == 0 is the bias alone.  `stops` is a device array, strictly ascending, 0 <= stops[s] <= n_trees (the caller has checked);

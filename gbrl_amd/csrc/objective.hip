@@ -1,0 +1,81 @@
+// objective.hip -- gfx950 kernels behind GBRL::objective_gradient and the parts of fit_prepared(objective=) that are not the code walk:
+//
+//   k_objective_rows   the objective's gradient and / or loss of a prediction matrix [n][D]: one lane per row, 256 threads, the row in p[DMAX]
+//                      registers (16-byte loads where D % 4 == 0 and the pointers allow it, as stream_load_row decides), then the device functions
+//                      of predict_continue_codes.hip's two tails (predict_loss.h: objective_grad_store, objective_loss_regs) -- the same bits as the
+//                      fused tails.  Loss: one float64 partial per wave of 64 rows through staged_wave_sum, finished by k_staged_finish.
+//   k_label_counts     class counts of an int32 label vector by integer atomics (an LDS histogram per block, then one global add per class), and
+//                      the smallest row whose label is outside [0, D): fit_prepared's softmax bias and the range check, one pass, D + 1 ints back.
+#include "kernels.h"
+#include "kernels_common.h"
+#include "predict_loss.h"
+
+namespace gbrl {
+namespace kern {
+
+namespace {
+
+template <int DMAX, int OBJ>
+__global__ __launch_bounds__(256) void k_objective_rows(const float *__restrict__ pred, const float *__restrict__ targets, int n, int D, float *__restrict__ grad_out,
+                                                        double *__restrict__ loss_part, int loss_nb, int vec_pred, int vec_tar, int vec_grad) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = j < n;
+    if (!live && loss_part == nullptr) return;   // (with the loss whole waves stay for the butterfly)
+    float p[DMAX];
+    if (live) {
+        stream_load_row<DMAX>(pred + static_cast<size_t>(j) * D, D, vec_pred != 0, p);
+        if (grad_out != nullptr)
+            objective_grad_store<OBJ, DMAX>(p, objective_target_row<OBJ>(targets, j, D), D, vec_tar != 0, vec_grad != 0, grad_out + static_cast<size_t>(j) * D);
+    }
+    if (loss_part != nullptr) {
+        double acc = 0.0;
+        if (live) acc = objective_loss_regs<OBJ, DMAX>(p, pred + static_cast<size_t>(j) * D, objective_target_row<OBJ>(targets, j, D), D, vec_tar != 0);
+        acc = staged_wave_sum(acc);
+        const int wave = j / kStagedRows;   // 256 = 4 x 64: a wave holds the rows of one partial
+        if ((threadIdx.x & (kStagedRows - 1)) == 0 && wave < loss_nb) loss_part[wave] = acc;
+    }
+}
+
+constexpr int kLabelClasses = 128;   // output_dim <= 128 wherever labels are taken
+
+__global__ __launch_bounds__(256) void k_label_counts(const int32_t *__restrict__ labels, int n, int D, int32_t *__restrict__ counts) {
+    __shared__ int32_t hist[kLabelClasses];
+    __shared__ int32_t bad;
+    for (int c = threadIdx.x; c < kLabelClasses; c += blockDim.x) hist[c] = 0;
+    if (threadIdx.x == 0) bad = 0x7fffffff;
+    __syncthreads();
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < static_cast<size_t>(n); i += static_cast<size_t>(gridDim.x) * blockDim.x) {
+        const int32_t y = labels[i];
+        if (y >= 0 && y < D) atomicAdd(&hist[y], 1);
+        else atomicMin(&bad, static_cast<int32_t>(i));
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < D; c += blockDim.x)
+        if (hist[c] != 0) atomicAdd(&counts[c], hist[c]);
+    if (threadIdx.x == 0 && bad != 0x7fffffff) atomicMin(&counts[D], bad);
+}
+
+}  // namespace
+
+void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s) {
+    if (n <= 0 || (grad_out == nullptr && loss_part == nullptr)) return;
+    const bool d4 = (D & 3) == 0;
+    const int vec_pred = d4 && (reinterpret_cast<uintptr_t>(pred) & 15) == 0;
+    const int vec_tar = d4 && (reinterpret_cast<uintptr_t>(targets) & 15) == 0;
+    const int vec_grad = d4 && (reinterpret_cast<uintptr_t>(grad_out) & 15) == 0;
+    with_objective(objective, [&](auto obj) {
+        with_general_dmax(D, [&](auto dmax) {
+            hipLaunchKernelGGL((k_objective_rows<decltype(dmax)::value, decltype(obj)::value>), dim3((n + 255) / 256), dim3(256), 0, s, pred,
+                               static_cast<const float *>(targets), n, D, grad_out, loss_part, staged_loss_partials(n), vec_pred, vec_tar, vec_grad);
+        });
+    });
+}
+
+void label_counts(const int32_t *labels, int n, int D, int32_t *counts, hipStream_t s) {
+    if (n <= 0) return;
+    const unsigned blocks = static_cast<unsigned>(std::min<size_t>((static_cast<size_t>(n) + 255) / 256, 1024));
+    hipLaunchKernelGGL(k_label_counts, dim3(blocks), dim3(256), 0, s, labels, n, D, counts);
+}
+
+}  // namespace kern
+}  // namespace gbrl

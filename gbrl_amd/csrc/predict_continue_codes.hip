@@ -12,6 +12,10 @@
 //                             tree, F too wide for the tile, a refused LDS opt-in, and the cross-check behind GBRL_HIP_CONTINUE_GENERIC=1.
 //   fused tail                targets != nullptr: grad_out[j][d] = fl32(out[j][d] - targets[j][d]) for the NEW out -- one float32 subtraction,
 //                             kern::sub_arrays' bits -- in the same pass (fit_prepared's MultiRMSE gradient).
+//   objective                 both kernels take the objective as a template parameter (objective_core.h; predict_loss.h has the register forms): rmse is the
+//                             code below as it always was; logistic reads the same [m][D] float targets and writes obj_logistic_grad; softmax reads
+//                             ONE int32 label per row (targets / loss_targets are then int32 [m] behind the float pointer) and runs the per-lane loops
+//                             max / exp / sum / divide over p[] -- a lane owns a row, no cross-lane traffic.  The loss tail sums the objective's row loss.
 //   loss tail                 loss_targets != nullptr: the row's sum_d (double)fl32(out - y)^2 for the NEW out, reduced over the wave's 64 rows by
 //                             predict_loss.h's butterfly and written to loss_part[j / 64] -- what k_loss_of_predictions writes for these
 //                             predictions, without the second pass over them (fit_prepared's validation rows).  The streaming kernel's block is
@@ -36,7 +40,7 @@ __global__ __launch_bounds__(256) void k_tile_rows(const float *__restrict__ row
 }
 
 // ------------------------------------------------------------------------------------------------------------ general kernel
-template <int DMAX>
+template <int DMAX, int OBJ>
 __global__ __launch_bounds__(256) void k_continue_codes_general(ChainModel cm, CodeRows cr, int m, int start_tree, int stop_tree, const float *base, float *out,
                                                                 const float *__restrict__ targets, float *__restrict__ grad_out,
                                                                 const float *__restrict__ loss_targets, double *__restrict__ loss_part, int loss_nb) {
@@ -52,16 +56,26 @@ __global__ __launch_bounds__(256) void k_continue_codes_general(ChainModel cm, C
         const GeneralCodeRow r{cr.codes + src * kCodeGroup, static_cast<size_t>(cr.n_rows) * kCodeGroup};
         for (int t = start_tree; t < stop_tree; ++t)
             if (!general_chain_tree<DMAX>(cm, r, t, p)) break;   // a greedy search ran off the ensemble: the walk ends
+        if constexpr (OBJ == kObjRmse) {
 #pragma unroll
-        for (int d = 0; d < DMAX; ++d)
-            if (d < D) {
-                out[static_cast<size_t>(j) * D + d] = p[d];
-                if (targets != nullptr) grad_out[static_cast<size_t>(j) * D + d] = __fsub_rn(p[d], targets[static_cast<size_t>(j) * D + d]);
-            }
+            for (int d = 0; d < DMAX; ++d)
+                if (d < D) {
+                    out[static_cast<size_t>(j) * D + d] = p[d];
+                    if (targets != nullptr) grad_out[static_cast<size_t>(j) * D + d] = __fsub_rn(p[d], targets[static_cast<size_t>(j) * D + d]);
+                }
+        } else {
+            stream_store_row<DMAX>(out + static_cast<size_t>(j) * D, D, false, p);
+            if (targets != nullptr)
+                objective_grad_store<OBJ, DMAX>(p, objective_target_row<OBJ>(targets, j, D), D, false, false, grad_out + static_cast<size_t>(j) * D);
+        }
     }
     if (loss_targets != nullptr) {
         double acc = 0.0;
-        if (live) acc = staged_row_loss<DMAX>(p, loss_targets + static_cast<size_t>(j) * D, D);
+        if constexpr (OBJ == kObjRmse) {
+            if (live) acc = staged_row_loss<DMAX>(p, loss_targets + static_cast<size_t>(j) * D, D);
+        } else {
+            if (live) acc = objective_loss_regs<OBJ, DMAX>(p, out + static_cast<size_t>(j) * D, objective_target_row<OBJ>(loss_targets, j, D), D, false);
+        }
         acc = staged_wave_sum(acc);
         const int wave = j / kStagedRows;   // 256 = 4 x 64: a wave holds the rows of one partial
         if ((threadIdx.x & (kStagedRows - 1)) == 0 && wave < loss_nb) loss_part[wave] = acc;
@@ -69,7 +83,7 @@ __global__ __launch_bounds__(256) void k_continue_codes_general(ChainModel cm, C
 }
 
 // ------------------------------------------------------------------------------------------------------------ streaming kernel
-template <int DMAX, bool GREEDY>
+template <int DMAX, bool GREEDY, int OBJ>
 __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, StreamOwner<DMAX> own, uint64_t cover, CodeRows cr, int m, int start_tree,
                                                                 int stop_tree, const float *base, float *out, const float *__restrict__ targets,
                                                                 float *__restrict__ grad_out, const float *__restrict__ loss_targets,
@@ -97,40 +111,50 @@ __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, S
         for (int t0 = start_tree; t0 < stop_tree; t0 += kStreamGroup<DMAX>)
             stream_chain_group<DMAX, GREEDY>(cm, own, cover, x, static_cast<const int32_t *>(nullptr), t0, stop_tree, vec_values, p);
         stream_store_row<DMAX>(out + row * D, D, vec_io != 0, p);
-        if (targets != nullptr) {
-            float y[DMAX];
-            stream_load_row<DMAX>(targets + row * D, D, vec_grad != 0, y);
+        if constexpr (OBJ == kObjRmse) {
+            if (targets != nullptr) {
+                float y[DMAX];
+                stream_load_row<DMAX>(targets + row * D, D, vec_grad != 0, y);
 #pragma unroll
-            for (int d = 0; d < DMAX; ++d) y[d] = __fsub_rn(p[d], y[d]);
-            stream_store_row<DMAX>(grad_out + row * D, D, vec_grad != 0, y);
+                for (int d = 0; d < DMAX; ++d) y[d] = __fsub_rn(p[d], y[d]);
+                stream_store_row<DMAX>(grad_out + row * D, D, vec_grad != 0, y);
+            }
+        } else {
+            if (targets != nullptr)
+                objective_grad_store<OBJ, DMAX>(p, objective_target_row<OBJ>(targets, row, D), D, vec_grad != 0, vec_grad != 0, grad_out + row * D);
         }
     }
     if (loss_targets != nullptr) {   // (block-uniform; the block is one wave: one partial)
         double acc = 0.0;
-        if (live) {
-            float y[DMAX];
-            stream_load_row<DMAX>(loss_targets + row * D, D, vec_loss != 0, y);
-            acc = staged_row_loss<DMAX>(p, y, D);
+        if constexpr (OBJ == kObjRmse) {
+            if (live) {
+                float y[DMAX];
+                stream_load_row<DMAX>(loss_targets + row * D, D, vec_loss != 0, y);
+                acc = staged_row_loss<DMAX>(p, y, D);
+            }
+        } else {
+            if (live) acc = objective_loss_regs<OBJ, DMAX>(p, out + row * D, objective_target_row<OBJ>(loss_targets, row, D), D, vec_loss != 0);
         }
         acc = staged_wave_sum(acc);
         if (lane == 0) loss_part[blockIdx.x] = acc;
     }
 }
 
-template <int DMAX, bool GREEDY>
+template <int DMAX, bool GREEDY, int OBJ>
 bool launch_continue_codes(const ChainModel &cm, const PredictModel &pm, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
                            float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, hipStream_t s) {
     static_assert(kStreamRows == kStagedRows, "a block of the streaming kernel writes exactly one loss partial");
     const size_t lds = stream_code_tile_bytes(cr.groups);
     if (lds > kStreamLdsBudget) return false;   // rows too wide for an LDS tile
     static StreamLdsOptIn optin;
-    if (!optin.ok(k_continue_codes<DMAX, GREEDY>, lds)) return false;
+    if (!optin.ok(k_continue_codes<DMAX, GREEDY, OBJ>, lds)) return false;
     const bool d4 = (pm.D & 3) == 0;
     const int vec_values = d4 && (reinterpret_cast<uintptr_t>(pm.values) & 15) == 0;
     const int vec_io = d4 && ((reinterpret_cast<uintptr_t>(base) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    const int vec_grad = d4 && ((reinterpret_cast<uintptr_t>(targets) | reinterpret_cast<uintptr_t>(grad_out)) & 15) == 0;
+    // (softmax targets are one label per row: only grad_out's address counts, and the loss tail loads no vector)
+    const int vec_grad = d4 && (((OBJ == kObjSoftmax ? 0 : reinterpret_cast<uintptr_t>(targets)) | reinterpret_cast<uintptr_t>(grad_out)) & 15) == 0;
     const int vec_loss = d4 && (reinterpret_cast<uintptr_t>(loss_targets) & 15) == 0;
-    hipLaunchKernelGGL((k_continue_codes<DMAX, GREEDY>), dim3((m + kStreamRows - 1) / kStreamRows), dim3(kStreamRows), lds, s, cm, stream_owner<DMAX>(pm),
+    hipLaunchKernelGGL((k_continue_codes<DMAX, GREEDY, OBJ>), dim3((m + kStreamRows - 1) / kStreamRows), dim3(kStreamRows), lds, s, cm, stream_owner<DMAX>(pm),
                        pm.coef_cover, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, vec_values, vec_io, vec_grad,
                        vec_loss);
     return true;
@@ -146,11 +170,16 @@ void tile_rows(const float *row, int D, int n, float *out, hipStream_t s) {
 
 void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
                             float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
-                            hipStream_t s) {
+                            hipStream_t s, int objective) {
     if (m <= 0) return;
     if (stop_tree <= start_tree || pm.n_opts <= 0) {   // no tree to apply, or no optimizer that owns an output: the base as it is
         const size_t n_el = static_cast<size_t>(m) * pm.D;
         if (out != base) (void)hipMemcpyAsync(out, base, sizeof(float) * n_el, hipMemcpyDeviceToDevice, s);
+        if (objective != kObjRmse) {   // the stand-alone kernel of the objective: the tails' device functions on the matrix
+            if (targets != nullptr) objective_rows(objective, out, targets, m, pm.D, grad_out, nullptr, s);
+            if (loss_targets != nullptr) objective_rows(objective, out, loss_targets, m, pm.D, nullptr, loss_part, s);
+            return;
+        }
         if (targets != nullptr) {
             const unsigned blocks = static_cast<unsigned>(std::min<size_t>((n_el + 255) / 256, 4096));
             hipLaunchKernelGGL(k_sub_rows, dim3(blocks), dim3(256), 0, s, out, targets, grad_out, n_el);
@@ -163,15 +192,19 @@ void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const 
     cm.walk.cond_pack = ct.cond_pack;
     cm.walk.grd_nodes = ct.grd_nodes;
     cm.walk.feature_bins = ct.bins;
-    if (chain_streamable(pm, generic) && with_stream_dmax(pm.D, [&](auto dmax) {
-            constexpr int DMAX = decltype(dmax)::value;
-            return pm.oblivious ? launch_continue_codes<DMAX, false>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, s)
-                                : launch_continue_codes<DMAX, true>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, s);
-        }))
-        return;
-    with_general_dmax(pm.D, [&](auto dmax) {
-        hipLaunchKernelGGL((k_continue_codes_general<decltype(dmax)::value>), dim3((m + 255) / 256), dim3(256), 0, s, cm, cr, m, start_tree, stop_tree, base,
-                           out, targets, grad_out, loss_targets, loss_part, staged_loss_partials(m));
+    with_objective(objective, [&](auto obj) {
+        constexpr int OBJ = decltype(obj)::value;
+        if (chain_streamable(pm, generic) && with_stream_dmax(pm.D, [&](auto dmax) {
+                constexpr int DMAX = decltype(dmax)::value;
+                return pm.oblivious
+                           ? launch_continue_codes<DMAX, false, OBJ>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, s)
+                           : launch_continue_codes<DMAX, true, OBJ>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, s);
+            }))
+            return;
+        with_general_dmax(pm.D, [&](auto dmax) {
+            hipLaunchKernelGGL((k_continue_codes_general<decltype(dmax)::value, OBJ>), dim3((m + 255) / 256), dim3(256), 0, s, cm, cr, m, start_tree, stop_tree,
+                               base, out, targets, grad_out, loss_targets, loss_part, staged_loss_partials(m));
+        });
     });
 }
 

@@ -457,7 +457,45 @@ int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const 
  *     without cols.  The held prediction, validation, the stopping rule and the loss see all rows and all columns; trees carry data set
  *     feature indices and thresholds.  Refused before anything changes: a bad colsample, and what gbrl_hip_fit_prepared_sampled refuses.
  *   gbrl_hip_gather_cols_geometry(rows_per_tile, max_staged_groups)  the rows one block of the column gather owns, and the source groups it
- *     stages at a time: a subset that touches more is walked in chunks by the same kernel (diagnostic; no device needed). */
+ *     stages at a time: a subset that touches more is walked in chunks by the same kernel (diagnostic; no device needed).
+ *
+ * Classification objectives (new: fit_prepared beyond MultiRMSE).  The trees and the outputs are what they were -- D raw scores, p moves by
+ * -lr * value along the mean gradient of a leaf -- only the gradient rule g = dL/dp and the loss change.  Every float32 step below is ONE
+ * definition shared by the host and the device (csrc/objective_core.h): the same bits on either.
+ *   obj_exp(t), t <= 0: k = rint(t log2 e); r = t - k ln2 in two parts (fmaf); exp(r) = 1 + (r + r^2 P(r)), P of degree 5 in fmaf; times 2^k through
+ *     the exponent bits.  No libm, no fast intrinsic, no contraction.  t < -104 gives +0.  The value p 2^k is within 2^-22 relative of exp(t) on
+ *     all of [-104, 0]; the rules below use it rounded once to float32 (obj_exp_f32: subnormal below t = -87.34), written obj_exp for short.
+ *   GBRL_HIP_OBJ_LOGISTIC, output_dim >= 1, targets float32 [n, D]: e = obj_exp(-|p|); s = p >= 0 ? 1 / (1 + e) : e / (1 + e) (correctly rounded
+ *     division); g = fl32(s - y).  Row loss, float64 from the float32 p: sum_d [max(p, 0) - y p + log1p(exp(-|p|))].
+ *   GBRL_HIP_OBJ_SOFTMAX, output_dim >= 2, targets int32 [n], labels in [0, D): m = max_c p_c; t_c = fl32(p_c - m) (0 where p_c == m, so that a
+ *     score of +inf is the maximum and not inf - inf); e_c = obj_exp(t_c); S = float32 sum of e_c, c ascending; q_c = e_c / S;
+ *     g_c = fl32(q_c - [c == y]).  Row loss, float64: log(sum_c exp((double)p_c - m)) + m - p_y.
+ *   GBRL_HIP_OBJ_RMSE: g = fl32(p - y) and the MultiRMSE expression, as ever.
+ *   The float64 row losses are reduced as MultiRMSE's are (one partial per 64 rows, a fixed tree: no floating-point atomics).  The loss of a set
+ *   is sum / n in float64 -- not a square root -- for the two new objectives.
+ *   gbrl_hip_fit_prepared_objective(.., seed, objective, ..)  gbrl_hip_fit_prepared_colsampled plus the objective; the two targets are float32
+ *     [n, D] (rmse, logistic) or int32 [n] (softmax).  The older calls are this one with GBRL_HIP_OBJ_RMSE, which runs their code itself.  A
+ *     fresh model (n_trees == 0) gets, computed on the host in double: logistic bias_d = (float)log(c / (1 - c)), c = clamp(mean_d(y), 1 / 2n,
+ *     1 - 1 / 2n); softmax bias_c = (float)log(max(n_c, 0.5) / n), n_c the rows of class c, counted on the device with integer atomics.
+ *     The launch that advances the held prediction writes the objective's gradient; the validation launch its loss partials;
+ *     valid_loss_out[k] = sum / n_valid; *loss_out = (float)(sum / n) over all rows.  Batches, sampling, warm starts and the stopping rule are
+ *     untouched.  Refused before anything changes (GBRL_HIP_E_INVALID): an unknown objective, softmax with output_dim < 2, a label outside
+ *     [0, D) in either set (the message names the first one found), and what gbrl_hip_fit_prepared_colsampled refuses.
+ *   gbrl_hip_objective_gradient(m, pred, pred_on_device, targets, targets_on_device, n, objective, grad_out, loss_out)  the same device
+ *     functions on a prediction matrix [n, output_dim], on the model's device and stream: grad_out [n, D] (where pred is: a device buffer iff
+ *     pred_on_device) and / or *loss_out (host; sum / n, or the MultiRMSE expression for rmse).  Either output may be NULL, not both.
+ *   gbrl_hip_objective_gradient_host(pred, targets, n, D, objective, grad_out)  the gradient rule with no device: the same bits.
+ *   gbrl_hip_objective_exp_host(t, n, out, out_f32)  out[i] = obj_exp(t[i]), the unrounded value p 2^k as a double, and / or out_f32[i] = that
+ *     value rounded once to float32 (obj_exp_f32: the e of the rules above), on the host (diagnostic: what the accuracy test sweeps); t[i] <= 0. */
+enum { GBRL_HIP_OBJ_RMSE = 0, GBRL_HIP_OBJ_LOGISTIC = 1, GBRL_HIP_OBJ_SOFTMAX = 2 };
+int gbrl_hip_fit_prepared_objective(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                                    const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                    double min_delta, double subsample, double colsample, uint64_t seed, int objective, float *loss_out,
+                                    double *valid_loss_out /*[iterations + 1]*/, int *iterations_done, int *best_n_trees);
+int gbrl_hip_objective_gradient(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective,
+                                float *grad_out /*[n, output_dim]*/, double *loss_out);
+int gbrl_hip_objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out /*[n, D]*/);
+int gbrl_hip_objective_exp_host(const float *t, int n, double *out /*[n] or NULL*/, float *out_f32 /*[n] or NULL*/);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
