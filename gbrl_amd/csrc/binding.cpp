@@ -797,23 +797,6 @@ py::object predict_continue_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
     return py::array_t<float>(shp, out, owner);
 }
 
-float fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations) {
-    const gbrl_hip_metadata md = self.meta();
-    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
-    Input t = read_input(targets, "targets", false, "fit", false);
-    if (ds && t.ptr) check_rows_by_outputs(t, "targets", ds_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
-    float loss = 0.0f;
-    int rc;
-    {
-        py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, &loss);
-    }
-    check(rc);
-    return loss;
-}
-
-// fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0):
-// a float without a validation set (the three validation arguments at their defaults), else a dict; subsample / colsample / seed go with either
 // the targets of an objective: float32 [n, D] ([n] when D == 1) for rmse and logistic, int32 [n] labels for softmax
 Input read_objective_targets(py::object &targets, const char *name, bool none_allowed, const std::string &fn, int objective, int n, int D, bool check_shape) {
     if (objective != GBRL_HIP_OBJ_SOFTMAX) {
@@ -830,67 +813,30 @@ Input read_objective_targets(py::object &targets, const char *name, bool none_al
     return t;
 }
 
-py::object fit_prepared_valid_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
-                                   int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name) {
+// fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,
+// objective='rmse'): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
+// with either.  A missing valid_targets is left to the C ABI's message.
+py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
+                             int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     const int objective = parse_objective(objective_name);
-    if (objective != GBRL_HIP_OBJ_RMSE) {   // (rmse: the code below as it was)
-        if (valid_obj.is_none() && (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0))
-            fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
-        const gbrl_hip_dataset *dsv = valid_obj.is_none() ? nullptr : valid_obj.cast<const PyDataset &>().h;
-        Input t = read_objective_targets(targets, "targets", false, "fit", objective, ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, md.output_dim, ds != nullptr);
-        Input tv;
-        if (dsv) tv = read_objective_targets(valid_targets, "valid_targets", true, "fit", objective, valid_obj.cast<const PyDataset &>().info().n_rows, md.output_dim, true);
-        std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0);
-        float loss = 0.0f;
-        int rc, done = 0, best = 0;
-        {
-            py::gil_scoped_release release;
-            rc = gbrl_hip_fit_prepared_objective(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
-                                                 colsample, seed, objective, &loss, dsv ? curve.data() : nullptr, &done, &best);
-        }
-        check(rc);
-        if (!dsv) return py::float_(loss);
-        py::array_t<double> vl(static_cast<py::ssize_t>(done) + 1);
-        std::copy(curve.begin(), curve.begin() + done + 1, vl.mutable_data());
-        py::dict out;
-        out["loss"] = py::float_(loss);
-        out["valid_loss"] = vl;
-        out["iterations"] = py::int_(done);
-        out["best_n_trees"] = py::int_(best);
-        return std::move(out);
-    }
-    if (valid_obj.is_none()) {
-        if (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0)
-            fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
-        if (subsample == 1.0 && colsample == 1.0) return py::float_(fit_prepared_impl(self, ds_obj, targets, iterations));
-        Input t = read_input(targets, "targets", false, "fit", false);
-        if (ds && t.ptr) check_rows_by_outputs(t, "targets", ds_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
-        float loss = 0.0f;
-        int rc;
-        {
-            py::gil_scoped_release release;
-            rc = gbrl_hip_fit_prepared_colsampled(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, nullptr, nullptr, 0, 0, 0.0, subsample,
-                                                  colsample, seed, &loss, nullptr, nullptr, nullptr);
-        }
-        check(rc);
-        return py::float_(loss);
-    }
-    const gbrl_hip_dataset *dsv = valid_obj.cast<const PyDataset &>().h;
-    Input t = read_input(targets, "targets", false, "fit", false);
-    if (ds && t.ptr) check_rows_by_outputs(t, "targets", ds_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
-    Input tv = read_input(valid_targets, "valid_targets", true, "fit", false);
-    if (tv.ptr) check_rows_by_outputs(tv, "valid_targets", valid_obj.cast<const PyDataset &>().info().n_rows, md.output_dim);
+    if (valid_obj.is_none() && (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0))
+        fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
+    const gbrl_hip_dataset *dsv = valid_obj.is_none() ? nullptr : valid_obj.cast<const PyDataset &>().h;
+    Input t = read_objective_targets(targets, "targets", false, "fit", objective, ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, md.output_dim, ds != nullptr);
+    Input tv;
+    if (dsv) tv = read_objective_targets(valid_targets, "valid_targets", true, "fit", objective, valid_obj.cast<const PyDataset &>().info().n_rows, md.output_dim, true);
     std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0);
     float loss = 0.0f;
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_colsampled(self.h, ds, static_cast<const float *>(t.ptr), t.on_device, iterations, dsv, static_cast<const float *>(tv.ptr),
-                                              tv.on_device, early_stopping_rounds, min_delta, subsample, colsample, seed, &loss, curve.data(), &done, &best);
+        rc = gbrl_hip_fit_prepared_objective(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                             colsample, seed, objective, &loss, dsv ? curve.data() : nullptr, &done, &best);
     }
     check(rc);
+    if (!dsv) return py::float_(loss);
     py::array_t<double> vl(static_cast<py::ssize_t>(done) + 1);
     std::copy(curve.begin(), curve.begin() + done + 1, vl.mutable_data());
     py::dict out;
@@ -1239,7 +1185,10 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "Every tree of the range must compare against the data set's thresholds (trees grown on it by step_prepared / fit_prepared do).");
     {
         // likewise: fit_prepared(ds, targets, iterations) -> float keeps its generated line; the validation form is the second overload
-        g.def("fit_prepared", &fit_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
+        g.def("fit_prepared", [](PyGBRL &self, py::object ds, py::object &targets, int iterations) -> float {
+            py::object none = py::none();
+            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse").cast<float>();
+        }, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
             "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,\n"
@@ -1277,7 +1226,7 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "where labels are wanted and the reverse, a label outside [0, D).";
         py::options opt;
         opt.disable_function_signatures();
-        g.def("fit_prepared", &fit_prepared_valid_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
+        g.def("fit_prepared", &fit_prepared_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
               py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse");
     }

@@ -561,13 +561,30 @@ int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset
     });
 }
 
-int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations, float *loss_out) {
+// The one body of the five gbrl_hip_fit_prepared* spellings.  valid_required (gbrl_hip_fit_prepared_valid): a NULL valid_ds is a null data set;
+// otherwise it means "no validation", the other validation arguments must then be at their defaults, *iterations_done = iterations and
+// *best_n_trees is left alone.  Every refusal that needs no data set comes before a handle is resolved, the validation handle before the
+// training handle, and nothing is written on a refusal.
+static int fit_prepared_call(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations, bool valid_required,
+                             const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds, double min_delta,
+                             const gbrl::FitOptions &opt, float *loss_out, double *valid_loss_out, int *iterations_done, int *best_n_trees) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");
-        m->engine.precheck_fit_prepared(targets, iterations);
-        const float loss = m->engine.fit_prepared(&live_dataset(ds), targets, targets_on_device != 0, iterations);
+        gbrl::Engine::FitValid v{nullptr, valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0};
+        gbrl::Engine::FitValid *valid = valid_required || valid_ds != nullptr ? &v : nullptr;
+        m->engine.precheck_fit(targets, iterations, opt, valid);
+        if (!valid && (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr))
+            throw gbrl::InvalidArgument("fit_prepared: valid_targets, early_stopping_rounds, min_delta and valid_loss_out need a validation set");
+        if (valid) v.ds = &live_dataset(valid_ds);
+        const float loss = m->engine.fit_prepared(&live_dataset(ds), targets, targets_on_device != 0, iterations, opt, valid);
         if (loss_out) *loss_out = loss;
+        if (iterations_done) *iterations_done = valid ? v.done : iterations;
+        if (valid && best_n_trees) *best_n_trees = v.best_n_trees;
     });
+}
+
+int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations, float *loss_out) {
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, nullptr, nullptr, 0, 0, 0.0, {}, loss_out, nullptr, nullptr, nullptr);
 }
 
 // ---- data sets that share thresholds; validation and early stopping
@@ -594,16 +611,8 @@ uint64_t gbrl_hip_dataset_thresholds_id(const gbrl_hip_dataset *ds) {
 int gbrl_hip_fit_prepared_valid(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
                                 const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
                                 double min_delta, float *loss_out, double *valid_loss_out, int *iterations_done, int *best_n_trees) {
-    return guarded([&] {
-        if (!m) throw gbrl::InvalidArgument("null model");
-        m->engine.precheck_fit_prepared(targets, iterations);
-        m->engine.precheck_fit_valid(valid_targets, early_stopping_rounds, min_delta);
-        gbrl::Engine::FitValid v{&live_dataset(valid_ds), valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0};
-        const float loss = m->engine.fit_prepared_valid(&live_dataset(ds), targets, targets_on_device != 0, iterations, v);
-        if (loss_out) *loss_out = loss;
-        if (iterations_done) *iterations_done = v.done;
-        if (best_n_trees) *best_n_trees = v.best_n_trees;
-    });
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, true, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {}, loss_out, valid_loss_out, iterations_done, best_n_trees);
 }
 
 int gbrl_hip_early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best) {
@@ -634,16 +643,16 @@ int gbrl_hip_fit_prepared_sampled(gbrl_hip_model *m, const gbrl_hip_dataset *ds,
                                   const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
                                   double min_delta, double subsample, uint64_t seed, float *loss_out, double *valid_loss_out, int *iterations_done,
                                   int *best_n_trees) {
-    return gbrl_hip_fit_prepared_colsampled(m, ds, targets, targets_on_device, iterations, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds,
-                                            min_delta, subsample, 1.0, seed, loss_out, valid_loss_out, iterations_done, best_n_trees);
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, 1.0, seed, GBRL_HIP_OBJ_RMSE}, loss_out, valid_loss_out, iterations_done, best_n_trees);
 }
 
 int gbrl_hip_fit_prepared_colsampled(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
                                      const gbrl_hip_dataset *valid_ds, const float *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
                                      double min_delta, double subsample, double colsample, uint64_t seed, float *loss_out, double *valid_loss_out,
                                      int *iterations_done, int *best_n_trees) {
-    return gbrl_hip_fit_prepared_objective(m, ds, targets, targets_on_device, iterations, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds,
-                                           min_delta, subsample, colsample, seed, GBRL_HIP_OBJ_RMSE, loss_out, valid_loss_out, iterations_done, best_n_trees);
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, colsample, seed, GBRL_HIP_OBJ_RMSE}, loss_out, valid_loss_out, iterations_done, best_n_trees);
 }
 
 // ---- classification objectives: fit_prepared with one, the gradient and loss of a prediction matrix, the gradient rule on the host
@@ -653,27 +662,8 @@ int gbrl_hip_fit_prepared_objective(gbrl_hip_model *m, const gbrl_hip_dataset *d
                                     const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
                                     double min_delta, double subsample, double colsample, uint64_t seed, int objective, float *loss_out,
                                     double *valid_loss_out, int *iterations_done, int *best_n_trees) {
-    return guarded([&] {
-        if (!m) throw gbrl::InvalidArgument("null model");
-        m->engine.precheck_fit_prepared(targets, iterations);
-        gbrl::Engine::check_subsample("fit_prepared", subsample);
-        gbrl::Engine::check_colsample("fit_prepared", colsample);
-        gbrl::Engine::check_objective("fit_prepared", objective, m->engine.model.meta.output_dim);
-        if (valid_ds == nullptr) {
-            if (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr)
-                throw gbrl::InvalidArgument("fit_prepared: valid_targets, early_stopping_rounds, min_delta and valid_loss_out need a validation set");
-            const float loss = m->engine.fit_prepared_objective(&live_dataset(ds), targets, targets_on_device != 0, iterations, nullptr, subsample, colsample, seed, objective);
-            if (loss_out) *loss_out = loss;
-            if (iterations_done) *iterations_done = iterations;
-            return;
-        }
-        m->engine.precheck_fit_valid(valid_targets, early_stopping_rounds, min_delta);
-        gbrl::Engine::FitValid v{&live_dataset(valid_ds), valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0};
-        const float loss = m->engine.fit_prepared_objective(&live_dataset(ds), targets, targets_on_device != 0, iterations, &v, subsample, colsample, seed, objective);
-        if (loss_out) *loss_out = loss;
-        if (iterations_done) *iterations_done = v.done;
-        if (best_n_trees) *best_n_trees = v.best_n_trees;
-    });
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, colsample, seed, objective}, loss_out, valid_loss_out, iterations_done, best_n_trees);
 }
 
 int gbrl_hip_objective_gradient(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective,

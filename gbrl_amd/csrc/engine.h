@@ -127,6 +127,9 @@ struct CatCandidate {
 struct CatItem { int feat; int next; uint64_t lhash; size_t std_hash; char name[128]; };
 }  // namespace detail
 
+// The options of Engine::fit_prepared; the defaults are the plain MultiRMSE loop on every row and column.
+struct FitOptions { double subsample = 1.0, colsample = 1.0; uint64_t seed = 0; int objective = 0 /* kern::kObjRmse */; };
+
 class Engine {
    public:
     explicit Engine(const gbrl_hip_config &cfg);
@@ -174,23 +177,37 @@ class Engine {
     // condition that is not among the data set's thresholds (Unsupported).  The model is never changed.
     void predict_continue_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *base, bool base_dev, int start_tree,
                                    int stop_tree, float *out, bool out_dev);
-    // fit_prepared: fit()'s loop (shuffle = false) with nothing recomputed -- the running prediction of every row is held and advanced by the
-    // trees grown since its batch last saw it (one launch that also writes the MultiRMSE gradient), the tree is grown by step_prepared's body.
-    // A fresh model gets bias = column means of the targets; a model with trees keeps its bias and continues from ALL its trees (unlike fit()),
-    // every one of which must be expressible on the data set (Unsupported before anything changes).  Returns fit()'s loss.
-    float fit_prepared(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations);
-    // fit_prepared watching a validation set that shares ds's thresholds (valid->thresholds_id == ds->thresholds_id; valid may be ds).  T0 = the
-    // tree count at entry (a fresh model: after the bias is set).  valid_loss_out[k], k = 0 .. done, is the MultiRMSE of the first T0 + k trees
-    // on the validation rows -- staged_loss's expression and summation order, bit for bit -- from a prediction held on the device and advanced
-    // after EVERY iteration by one launch that also writes the loss partials.  rounds > 0: the loop ends after iteration k when k - best >=
-    // rounds (early_stop_scan's rule); rounds == 0: record only.  All trees grown stay; the model after `done` iterations is byte for byte
-    // what fit_prepared(ds, targets, done) leaves, and the returned loss is its return value.  Refused before anything changes: another
-    // thresholds id, null valid targets, rounds < 0, min_delta negative or NaN, and what fit_prepared refuses.
+    // fit_prepared: fit()'s loop (shuffle = false) on a data set with nothing recomputed.  Each iteration takes the next batch_size rows (wrapping to
+    // row 0), advances their held prediction by the trees grown since the batch last saw it -- one launch that also writes the objective's gradient
+    // -- and grows one tree by step_prepared's body; at the end every batch is advanced and the loss on all rows returned (fit()'s MultiRMSE; an
+    // objective's sum / rows in float64, the row losses reduced as MultiRMSE's are).  A fresh model first gets its bias; a model with trees keeps
+    // it and continues from ALL its trees (unlike fit()).
+    //   objective  (objective_core.h; kern::kObjRmse / kObjLogistic / kObjSoftmax)  rmse, logistic: targets float32 [n][D]; softmax: int32 [n] labels
+    //              in [0, D), valid->targets likewise.  The bias, in double: the column means; log(c / (1 - c)), c = clamp(column mean, 1 / 2n,
+    //              1 - 1 / 2n); log(max(n_c, 0.5) / n), n_c counted on the device (kern::label_counts, which also finds a label out of range).
+    //   subsample  < 1: the tree grows on a sample of its batch, drawn once prediction and gradient are up to date with draw = the tree count before
+    //              the step (a continued fit continues the sequence); the gradient rows are gathered in the same pass and m is read back (4 bytes).
+    //              A draw that keeps no row takes the whole batch.  == 1 IS the unsampled loop: no sampler launch, no gather, no phase.
+    //   colsample  < 1: and on sample_cols_host's columns for the same seed and draw, by step_prepared's cols path; == 1, or a draw of every column
+    //              (F == 1): nothing of it runs.  The held prediction, validation, the stopping rule and the loss see all rows and columns.
+    //   valid      a set with ds's thresholds_id (it may be ds).  loss_out[k], k = 0 .. done, is the loss of the first T0 + k trees (T0: the count at
+    //              entry) on its rows -- rmse: staged_loss's expression and summation order, bit for bit -- from a second held prediction advanced
+    //              after EVERY iteration by one launch that also writes the loss partials.  rounds > 0: the loop ends after iteration k when k - best
+    //              >= rounds (early_stop_scan's rule); rounds == 0: record only.  All trees grown stay: model and loss are what the call without
+    //              valid gives for `done` iterations.  best_n_trees = T0 + best.
+    // Refused before anything changes, in this order: precheck_fit's list; ds, then valid->ds, absent or not this model's (check_prepared_dataset);
+    // another thresholds id; null valid->loss_out; a tree whose conditions the codes cannot express (Unsupported); softmax: a label outside [0, D)
+    // in either set (InvalidArgument naming the first one found).
     struct FitValid {
         const PreparedDataset *ds; const void *targets; bool targets_dev; int rounds; double min_delta;
         double *loss_out /*[iterations + 1]*/; int done, best_n_trees;
     };
-    float fit_prepared_valid(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid &v);
+    float fit_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, const FitOptions &opt = {}, FitValid *valid = nullptr);
+    // What fit_prepared refuses without a data set in hand, in this order (the C ABI runs it before it resolves the handles, so that these
+    // refusals do not depend on a data set being at hand; valid->ds is not looked at): the model checks of step_prepared; null targets;
+    // iterations < 0; batch_size <= 0; max_depth > 32, n_bins outside [1, 65534], output_dim > 128 (Unsupported); check_subsample;
+    // check_colsample; check_objective; with valid: null targets, rounds < 0, min_delta negative or NaN.
+    void precheck_fit(const void *targets, int iterations, const FitOptions &opt, const FitValid *valid) const;
     // Extension: row subsampling (stochastic gradient boosting).  The sampler is sample_core.h's pure function of (seed, draw, row): a row is
     // kept iff its 24-bit hash is below floor(subsample * 2^24); the sample of [row0, row0 + n) is the ascending list of its kept absolute indices.
     // sample_rows_host: the rule itself on the host, out [n], *count = m.  sample_rows: the same list from the device kernels (kern::sample_rows)
@@ -203,32 +220,13 @@ class Engine {
     // The engine's fused sampler + gather on the CURRENT device and the null stream (what fit_prepared's loop enqueues per iteration; the tests
     // reach it through gbrl_hip_sample_gather): device G [n][D] -> device rows_out [n], G_out [n][D], *count = m.
     static void sample_gather(int row0, int n, double subsample, uint64_t seed, int draw, const float *G, int D, int32_t *rows_out, float *G_out, int *count);
-    // fit_prepared / fit_prepared_valid (v may be null) growing every tree on a sample of its batch.  subsample == 1.0 IS the unsampled loop: no
-    // sampler launch, no gather, no phase.  Otherwise iteration i, after the held prediction and the gradient of the batch [start, start + bn)
-    // are up to date, draws the rows of the batch with draw = the tree count before the step (a continued fit continues the sequence), gathers
-    // their gradient rows in the same pass, reads m back (4 bytes) and grows on (rows, gathered gradients).  A draw that keeps no row takes the
-    // whole batch, as the unsampled iteration does.  Batches, validation, stopping, the final advance and the loss are the unsampled loop's.
-    // (the call is fit_prepared_colsampled below, which adds the column fraction)
     // Extension: column subsampling (colsample_bytree / feature_fraction).  The rule is sample_core.h's: k = max(1, floor(colsample * F + 0.5))
     // columns, the k smallest (u_f, f) with u_f the 24-bit hash of (seed ^ "colsampl", draw, f), ascending.  Host only.  sample_cols_host: out
     // [F], *count = k.  Refused (InvalidArgument): F < 1, draw < 0, a colsample that is NaN or outside (0, 1], null outputs.
     static void check_colsample(const char *what, double colsample);
     static void sample_cols_host(int F, double colsample, uint64_t seed, int draw, int32_t *out, int *count);
-    // The sampled loop above growing every tree on a column subset as well: per iteration the columns of draw = the tree count before the step
-    // (the row sampler's seed and draw), step_prepared's cols path on them.  colsample == 1.0, or a draw that keeps every column (F == 1): the
-    // loop above itself.  The held prediction, validation, the stopping rule and the loss see all rows and all columns.
-    float fit_prepared_colsampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, double colsample,
-                                  uint64_t seed);
-    // Extension: classification objectives (objective_core.h has the definitions, kern::kObjRmse / kObjLogistic / kObjSoftmax the values).
-    // fit_prepared_objective is the loop above with the objective's gradient and loss in place of MultiRMSE's: kObjRmse runs that loop itself.
-    // logistic: targets float32 [n][D]; softmax: targets int32 [n], labels in [0, D) (v->targets likewise).  A fresh model's bias is, in double,
-    // logistic: log(c / (1 - c)) with c = clamp(column mean, 1 / 2n, 1 - 1 / 2n); softmax: log(max(n_c, 0.5) / n), n_c counted on the device
-    // (kern::label_counts, which also finds a label out of range).  valid_loss_out[k] and the returned loss are sum / rows in float64, the row
-    // losses reduced as MultiRMSE's are.  Refused before anything changes: an unknown objective, softmax with output_dim < 2, a label outside
-    // [0, D) (InvalidArgument naming the first one found), and what the loop above refuses.
+    // Extension: classification objectives.  Refused (InvalidArgument): an unknown objective, softmax with D < 2.
     static void check_objective(const char *what, int objective, int D);
-    float fit_prepared_objective(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, FitValid *v, double subsample, double colsample,
-                                 uint64_t seed, int objective);
     // objective_gradient: grad_out [n][D] = dL/dp and / or *loss_out = the loss of pred [n][D] against targets under the objective, on the model's
     // device and stream with D = output_dim (kern::objective_rows: the device functions of the code walk's tails).  grad_out is where pred is
     // (device iff pred_dev); either output may be null, not both.  kObjRmse: g = fl32(p - y) and staged_loss's expression.
@@ -238,11 +236,8 @@ class Engine {
     // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
     // min_delta (a NaN never improves); *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = best at that point
     static void early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
-    void precheck_fit_valid(const void *valid_targets, int rounds, double min_delta) const;
-    // what the two calls above refuse without looking at the data set, in their order (the C ABI runs it before it resolves the handle, so that
-    // these refusals do not depend on a data set being at hand): the model checks of step_prepared, then fit_prepared's own arguments
+    // the model checks of step_prepared, for the C ABI calls that run them before they resolve a data set handle
     void precheck_prepared(const char *what) const { check_prepared_model(what); }
-    void precheck_fit_prepared(const void *targets, int iterations) const;
     void predict(const float *obs, bool obs_dev, const char *cat, bool cat_dev, int n, int n_num, int n_cat, int start_tree,
                  int stop_tree, float *out, bool out_dev);
     // Extension (not in the reference, which compares the 128-byte cells inside every predict call): the dictionary ids of a batch of
@@ -477,15 +472,30 @@ class Engine {
     DevBuf d_fp_vpred_, d_fp_vtargets_, d_fp_vpart_, d_fp_vsums_;   // its validation rows: held prediction [n_v][D], staged targets, loss partials, one sum per iteration
     DevBuf d_fp_srows_, d_fp_sgrads_, d_fp_sscratch_;   // its sampled iterations: the kept rows of the batch, their gradient rows, block counts + m
     DevBuf d_obj_pred_, d_obj_targets_, d_obj_grad_, d_obj_part_, d_obj_sum_, d_obj_counts_;   // objective_gradient: staged inputs, the gradient, loss partials and sum; class counts + first bad row
-    float fit_prepared_loop(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, FitValid *v, double subsample = 1.0,
-                            uint64_t seed = 0, double colsample = 1.0, int objective = 0);
+    struct Held;     // engine_fit_prepared.hip: a data set's rows carried through the model's trees, batch by batch
+    struct FitRun;   // engine_fit_prepared.hip: the state of one fit_prepared call and the stages that work on it
     // class counts of device labels [n] (counts, when given: [D]); a label outside [0, D) is InvalidArgument naming the first such row
     void check_labels(const char *what, const int32_t *d_labels, int n, int D, std::vector<int32_t> *counts);
-    // rows [start, start + bn) of a data set's held prediction P (valid through `through` trees) advanced to every tree the model has, with the
-    // gradient tail (targets, grad_out) and / or the loss tail (loss_targets, loss_part) of kern::predict_continue_codes; targets are [n][D]
-    // (softmax: one int32 label per row behind the float pointers)
-    void advance_held(const PreparedDataset &ds, float *P, int &through, int start, int bn, const float *targets, float *grad_out,
-                      const float *loss_targets, double *loss_part, bool generic, int objective = 0);
+    // rows [start, start + bn) of a held prediction (one batch of it, or a part of one) advanced to every tree the model has, with the gradient
+    // tail (targets, grad_out) and / or the loss tail (loss_targets, loss_part) of kern::predict_continue_codes; targets are [n][D] (softmax:
+    // one int32 label per row behind the float pointers)
+    void advance_held(Held &h, int start, int bn, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
+                      int objective);
+    // the partials of a loss tail summed into *d_sum (kern::staged_loss_finish) and, with host_sum, its 8 bytes on their way to the host: they
+    // are there after the caller's wait for the stream
+    void finish_loss_sum(const double *d_part, int n_part, double *d_sum, double *host_sum);
+    // Column sums in float64 of device rows [rows][D] and the MultiRMSE built on them, as fit() and fit_prepared() compute the bias and the loss
+    // (engine_step.hip).  Its construction enqueues the memset of the zero center.
+    struct ColumnStats {
+        explicit ColumnStats(Engine &e);
+        const std::vector<double> &sums(const float *g, int rows, const float *center);   // column sums (center null) or sums of squares about center; waits for the stream
+        float rmse(const float *grads_dev, int rows);                                      // MultiRMSE, loss.cpp:42-56: sqrt(0.5 * sum g^2 / rows)
+        Engine &e_;
+        const int D_;
+        float *d_zero_;
+        double *d_stat_;
+        std::vector<double> hs_;
+    };
     DevBuf d_am_s_, d_near_list_, d_near_ent_, d_near_rep_, d_near_nr_, d_near_maps_, d_near_pos_, d_near_nrb_, d_near_vals_, d_near_means_, d_near_sums_, d_near_chains_, d_near_rowsort_, d_near_tiles_;   // near-tie replay (kern::near_tie_replay): runner-up per arg-max block, candidate lists, ordered row lists, replayed scores
     bool small_grow_off_ = false;     // latched after a failed launch / an abandoned grid barrier of the one-launch kernel: this engine keeps to the level loop
     long long small_grow_fallbacks_ = 0;   // trees the level loop grew after such a failure (diagnostics)

@@ -4,12 +4,14 @@
 //   sync_code_tables                   device copies of the bins and of the mirror's packed conditions / greedy node records with the bin as
 //                                      their second word (appended like the originals: a loop that adds a tree per iteration converts that tree only)
 //   Engine::predict_continue_prepared  predict_continue without the observations (kern::predict_continue_codes)
-//   Engine::fit_prepared               fit()'s loop with the running prediction held and the batch never binned again
-//   Engine::fit_prepared_valid         the same loop watching a validation set that shares the thresholds: a second held prediction advanced after
-//                                      every iteration (advance_held, the loss tail of the code walk), Engine::early_stop_scan's rule
-//   Engine::fit_prepared_colsampled    the same loop growing every tree on a sample of its batch (sample_core.h): kern::sample_rows draws the rows
-//                                      and gathers their gradient rows in one pass, 4 bytes come back, step_prepared's body grows on the subset
-//                                      ... and on a sample of the columns: the host rule of sample_core.h per iteration, step_prepared's cols path
+//   Engine::objective_gradient[_host]  the gradient and the loss of an objective (objective_core.h) for a prediction matrix, on the device and on the host
+//   Engine::fit_prepared               fit()'s loop with the running prediction held and the batch never binned again (advance_held: the code walk
+//                                      with its gradient tail), in named stages over one FitRun.  Its options: an objective in place of MultiRMSE;
+//                                      a validation set that shares the thresholds -- a second held prediction advanced after every iteration by
+//                                      the walk's loss tail, Engine::early_stop_scan's rule; every tree grown on a sample of its batch
+//                                      (sample_core.h: kern::sample_rows draws the rows and gathers their gradient rows in one pass, 4 bytes come
+//                                      back, step_prepared's body grows on the subset) and on a sample of the columns (the host rule of
+//                                      sample_core.h per iteration, step_prepared's cols path)
 //
 // The rule.  code(r, f) = #{b : thr[f][b] < obs[r, f]} (-0.0 == +0.0; NaN lies below every threshold: code 0).  For a condition x > v whose v
 // equals some thr[f][b] let bin = #{b : thr[f][b] < v}.  x > v: every threshold below v, and v itself, is below x, so code >= bin + 1.
@@ -194,73 +196,7 @@ void Engine::predict_continue_prepared(const PreparedDataset *ds, const int32_t 
     finish("predict_continue_prepared launch", "predict", {{out_dev ? nullptr : out, dout, out_bytes, "D2H preds"}});
 }
 
-void Engine::precheck_fit_prepared(const void *targets, int iterations) const {
-    const gbrl_hip_metadata &md = model.meta;
-    check_prepared_model("fit_prepared");
-    if (targets == nullptr) throw InvalidArgument("Cannot call fit without targets!");
-    if (iterations < 0) throw InvalidArgument("iterations must be >= 0");
-    if (md.batch_size <= 0) throw InvalidArgument("batch_size must be positive");
-    if (md.max_depth > kern::kMaxPath) throw Unsupported("max_depth > 32 is not supported");
-    if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
-    if (md.output_dim > 128) throw Unsupported("predict: output_dim > 128");
-}
-
-void Engine::precheck_fit_valid(const void *valid_targets, int rounds, double min_delta) const {
-    if (valid_targets == nullptr) throw InvalidArgument("fit_prepared: a validation set needs valid_targets");
-    if (rounds < 0) throw InvalidArgument("fit_prepared: early_stopping_rounds must be >= 0");
-    if (!(min_delta >= 0.0)) throw InvalidArgument("fit_prepared: min_delta must be >= 0 (and not NaN)");
-}
-
-void Engine::early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best) {
-    if (curve == nullptr || stop_after == nullptr || best == nullptr) throw InvalidArgument("early_stop_scan: null argument");
-    if (n <= 0) throw InvalidArgument("early_stop_scan: an empty curve");
-    if (rounds < 0) throw InvalidArgument("early_stop_scan: rounds must be >= 0");
-    if (!(min_delta >= 0.0)) throw InvalidArgument("early_stop_scan: min_delta must be >= 0 (and not NaN)");
-    int b = 0, k = 1;
-    for (; k < n; ++k) {
-        if (curve[k] < curve[b] - min_delta) b = k;   // (false for a NaN on either side)
-        if (rounds > 0 && k - b >= rounds) break;
-    }
-    *stop_after = k < n ? k : n - 1;
-    *best = b;
-}
-
-// P[start .. start + bn) of a data set's held prediction from `through` trees to every tree the model has; with targets, g = P - y for those rows in
-// the same pass; with loss_targets, the loss partials of the new P (bn rows, from partial 0).  A walk that ended in a trailing run of one-leaf
-// greedy trees applied nothing for them (it ran off the ensemble): it resumes at the first of them.
-void Engine::advance_held(const PreparedDataset &ds, float *P, int &through, int start, int bn, const float *targets, float *grad_out,
-                          const float *loss_targets, double *loss_part, bool generic, int objective) {
-    const int T = model.meta.n_trees, D = model.meta.output_dim;
-    int from = through;
-    while (from > 0 && runs_on(model, from - 1)) --from;
-    check_code_range(ds, "fit_prepared", from, T);
-    sync_model_to_device();
-    const kern::CodeTables ct = sync_code_tables(ds);
-    float *p = P + static_cast<size_t>(start) * D;
-    const size_t at = static_cast<size_t>(start) * (objective == kern::kObjSoftmax ? 1 : D);   // (softmax: a label per row)
-    kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{ds.prep.d_codes, ds.n, ds.code_groups(), nullptr, start}, bn, from, T, p, p,
-                                 targets ? targets + at : nullptr, grad_out, loss_targets ? loss_targets + at : nullptr, loss_part, generic, stream_, objective);
-    through = T;
-}
-
-float Engine::fit_prepared(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations) {
-    return fit_prepared_loop(ds, targets, targets_dev, iterations, nullptr);
-}
-
-float Engine::fit_prepared_valid(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid &v) {
-    return fit_prepared_loop(ds, targets, targets_dev, iterations, &v);
-}
-
-float Engine::fit_prepared_colsampled(const PreparedDataset *ds, const float *targets, bool targets_dev, int iterations, FitValid *v, double subsample, double colsample,
-                                      uint64_t seed) {
-    return fit_prepared_loop(ds, targets, targets_dev, iterations, v, subsample, seed, colsample);
-}
-
-float Engine::fit_prepared_objective(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, FitValid *v, double subsample,
-                                     double colsample, uint64_t seed, int objective) {
-    return fit_prepared_loop(ds, targets, targets_dev, iterations, v, subsample, seed, colsample, objective);
-}
-
+// ---- objectives: the checks, the gradient rule on the host, the gradient and the loss of a prediction matrix on the device
 void Engine::check_objective(const char *what, int objective, int D) {
     if (objective != kern::kObjRmse && objective != kern::kObjLogistic && objective != kern::kObjSoftmax)
         throw InvalidArgument(std::string(what) + ": unknown objective " + std::to_string(objective) + " (rmse = 0, logistic = 1, softmax = 2)");
@@ -310,6 +246,18 @@ void Engine::objective_gradient_host(const float *pred, const void *targets, int
         for (size_t i = 0; i < n_el; ++i) grad_out[i] = pred[i] - y[i];
 }
 
+namespace {
+// the mean loss of an objective from the sum of its row losses: rmse is staged_loss's expression
+double mean_loss(int objective, double sum, int rows) {
+    return objective == kern::kObjRmse ? std::sqrt(0.5 * sum / static_cast<double>(rows)) : sum / static_cast<double>(rows);
+}
+}  // namespace
+
+void Engine::finish_loss_sum(const double *d_part, int n_part, double *d_sum, double *host_sum) {
+    kern::staged_loss_finish(d_part, n_part, d_sum, stream_);
+    if (host_sum) hip_check(hipMemcpyAsync(host_sum, d_sum, sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H loss");
+}
+
 void Engine::objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out) {
     const int D = model.meta.output_dim;
     if (pred == nullptr || targets == nullptr) throw InvalidArgument("objective_gradient: null argument");
@@ -329,215 +277,271 @@ void Engine::objective_gradient(const float *pred, bool pred_dev, const void *ta
     double *dsum = loss_out ? static_cast<double *>(d_obj_sum_.ensure(sizeof(double))) : nullptr;
     kern::objective_rows(objective, dp, dt, n, D, dg, dpart, s);
     double sum = 0.0;
-    if (loss_out) {
-        kern::staged_loss_finish(dpart, nb, dsum, s);
-        hip_check(hipMemcpyAsync(&sum, dsum, sizeof(double), hipMemcpyDeviceToHost, s), "D2H loss");
-    }
+    if (loss_out) finish_loss_sum(dpart, nb, dsum, &sum);
     if (grad_out && !pred_dev) hip_check(hipMemcpyAsync(grad_out, dg, sizeof(float) * n_el, hipMemcpyDeviceToHost, s), "D2H gradient");
     hip_check(hipGetLastError(), "objective_gradient kernels");
     hip_check(hipStreamSynchronize(s), "sync");
-    if (loss_out) *loss_out = objective == kern::kObjRmse ? std::sqrt(0.5 * sum / static_cast<double>(n)) : sum / static_cast<double>(n);
+    if (loss_out) *loss_out = mean_loss(objective, sum, n);
 }
 
-float Engine::fit_prepared_loop(const PreparedDataset *ds, const void *targets_any, bool targets_dev, int iterations, FitValid *v, double subsample, uint64_t seed,
-                                double colsample, int objective) {
-    gbrl_hip_metadata &md = model.meta;
-    const float *targets = static_cast<const float *>(targets_any);   // (softmax: int32 labels behind it, one per row)
-    precheck_fit_prepared(targets, iterations);
-    check_objective("fit_prepared", objective, md.output_dim);
-    check_subsample("fit_prepared", subsample);
-    check_colsample("fit_prepared", colsample);
-    if (v) precheck_fit_valid(v->targets, v->rounds, v->min_delta);
-    check_prepared_dataset("fit_prepared", ds);
-    if (v) {
-        check_prepared_dataset("fit_prepared", v->ds);
-        if (v->ds->thresholds_id != ds->thresholds_id)
-            throw InvalidArgument("fit_prepared: the validation set does not share the training set's thresholds (create it with prepare_dataset(obs, reference=ds))");
-        if (v->loss_out == nullptr) throw InvalidArgument("fit_prepared: no place for the validation losses");
+// ---- the fit: the stopping rule, the refusals that need no data set, a held prediction, and the stages of Engine::fit_prepared in its order
+void Engine::early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best) {
+    if (curve == nullptr || stop_after == nullptr || best == nullptr) throw InvalidArgument("early_stop_scan: null argument");
+    if (n <= 0) throw InvalidArgument("early_stop_scan: an empty curve");
+    if (rounds < 0) throw InvalidArgument("early_stop_scan: rounds must be >= 0");
+    if (!(min_delta >= 0.0)) throw InvalidArgument("early_stop_scan: min_delta must be >= 0 (and not NaN)");
+    int b = 0, k = 1;
+    for (; k < n; ++k) {
+        if (curve[k] < curve[b] - min_delta) b = k;   // (false for a NaN on either side)
+        if (rounds > 0 && k - b >= rounds) break;
     }
-    const bool fresh = md.n_trees == 0;
-    if (!fresh) check_code_range(*ds, "fit_prepared", 0, md.n_trees);   // a warm start continues from every tree the model has
-    ensure_device();
-    hipStream_t s = stream_;
-    const int n = ds->n, D = md.output_dim;
-    const bool labels = objective == kern::kObjSoftmax;
-    const size_t tar_row = labels ? 1 : static_cast<size_t>(D);   // 4-byte entries of a row's targets
-    auto staged = [&](DevBuf &buf, const float *host_or_dev, bool on_dev, int rows) -> const float * {
-        if (on_dev) return host_or_dev;
-        float *t = static_cast<float *>(buf.ensure(sizeof(float) * static_cast<size_t>(rows) * tar_row));
-        hip_check(hipMemcpyAsync(t, host_or_dev, sizeof(float) * static_cast<size_t>(rows) * tar_row, hipMemcpyHostToDevice, s), "H2D targets");
-        return t;
-    };
-    const float *dtar = staged(d_fp_targets_, targets, targets_dev, n);
-    const float *dvtar = v ? staged(d_fp_vtargets_, static_cast<const float *>(v->targets), v->targets_dev, v->ds->n) : nullptr;
-    std::vector<int32_t> class_counts;
-    if (labels) {   // refused before anything changes: a label outside [0, D), in either set
-        check_labels("fit_prepared", reinterpret_cast<const int32_t *>(dtar), n, D, &class_counts);
-        if (v) check_labels("fit_prepared (valid_targets)", reinterpret_cast<const int32_t *>(dvtar), v->ds->n, D, nullptr);
+    *stop_after = k < n ? k : n - 1;
+    *best = b;
+}
+
+void Engine::precheck_fit(const void *targets, int iterations, const FitOptions &opt, const FitValid *valid) const {
+    const gbrl_hip_metadata &md = model.meta;
+    check_prepared_model("fit_prepared");
+    if (targets == nullptr) throw InvalidArgument("Cannot call fit without targets!");
+    if (iterations < 0) throw InvalidArgument("iterations must be >= 0");
+    if (md.batch_size <= 0) throw InvalidArgument("batch_size must be positive");
+    if (md.max_depth > kern::kMaxPath) throw Unsupported("max_depth > 32 is not supported");
+    if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
+    if (md.output_dim > 128) throw Unsupported("predict: output_dim > 128");
+    check_subsample("fit_prepared", opt.subsample);
+    check_colsample("fit_prepared", opt.colsample);
+    check_objective("fit_prepared", opt.objective, md.output_dim);
+    if (valid == nullptr) return;
+    if (valid->targets == nullptr) throw InvalidArgument("fit_prepared: a validation set needs valid_targets");
+    if (valid->rounds < 0) throw InvalidArgument("fit_prepared: early_stopping_rounds must be >= 0");
+    if (!(valid->min_delta >= 0.0)) throw InvalidArgument("fit_prepared: min_delta must be >= 0 (and not NaN)");
+}
+
+// A data set's rows carried through the model's trees: the rows of batch b (bs rows each, the last one shorter) of P hold the trees [0, through[b]).
+struct Engine::Held {
+    const PreparedDataset *ds = nullptr;
+    float *P = nullptr;   // [ds->n][D], device
+    int bs = 1;
+    std::vector<int> through;
+    void start(const PreparedDataset *data, float *pred, int batch_rows) {   // the caller has tiled the bias: through 0 trees everywhere
+        ds = data; P = pred; bs = batch_rows;
+        through.assign((data->n + batch_rows - 1) / batch_rows, 0);
     }
-    // column sums and the loss: Engine::fit's own expressions (engine_step.hip)
-    float *d_zero = static_cast<float *>(d_fit_zero_.ensure(sizeof(float) * D));
-    hip_check(hipMemsetAsync(d_zero, 0, sizeof(float) * D, s), "memset");
-    double *d_stat = static_cast<double *>(d_stat_.ensure(sizeof(double) * 4 * D));
-    std::vector<double> hs(2 * D);
-    auto column_stat = [&](const float *g, int rows, const float *center) {   // column sums (center null) or sums of squares
-        const int nblk = kern::column_sums_blocks(rows, D);
-        double *d_part = static_cast<double *>(d_partials_f64_.ensure(sizeof(double) * nblk * 2 * D));
-        kern::column_sums(g, rows, D, center, d_part, nblk, d_stat, s);
-        hip_check(hipMemcpyAsync(hs.data(), d_stat, sizeof(double) * 2 * D, hipMemcpyDeviceToHost, s), "D2H stat");
-        hip_check(hipStreamSynchronize(s), "sync");
-    };
-    auto rmse = [&](const float *grads_dev, int rows) {                       // MultiRMSE, loss.cpp:42-56: sqrt(0.5 * sum g^2 / rows)
-        column_stat(grads_dev, rows, d_zero);
-        double tot = 0.0;
-        for (int d = 0; d < D; ++d) tot += hs[d];
-        return sqrtf(0.5f * static_cast<float>(tot) * (1.0f / static_cast<float>(rows)));
-    };
-    if (fresh) {
-        // bias = column means of the targets (gbrl.cpp:1075-1077); the feature counts as step_prepared latches them
-        if (objective == kern::kObjRmse) {
-            column_stat(dtar, n, nullptr);
-            for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(hs[d] / static_cast<double>(n));
-        } else if (objective == kern::kObjLogistic) {   // the log odds of the column mean, kept off 0 and 1 by half a row
-            column_stat(dtar, n, nullptr);
+};
+
+// A walk that ended in a trailing run of one-leaf greedy trees applied nothing for them (it ran off the ensemble): it resumes at the first of them.
+void Engine::advance_held(Held &h, int start, int bn, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
+                          int objective) {
+    const int T = model.meta.n_trees, D = model.meta.output_dim;
+    int &through = h.through[start / h.bs];
+    int from = through;
+    while (from > 0 && runs_on(model, from - 1)) --from;
+    check_code_range(*h.ds, "fit_prepared", from, T);
+    sync_model_to_device();
+    const kern::CodeTables ct = sync_code_tables(*h.ds);
+    float *p = h.P + static_cast<size_t>(start) * D;
+    const size_t at = static_cast<size_t>(start) * (objective == kern::kObjSoftmax ? 1 : D);   // (softmax: a label per row)
+    kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{h.ds->prep.d_codes, h.ds->n, h.ds->code_groups(), nullptr, start}, bn, from, T, p, p,
+                                 targets ? targets + at : nullptr, grad_out, loss_targets ? loss_targets + at : nullptr, loss_part, generic, stream_, objective);
+    through = T;
+}
+
+// One fit_prepared call behind its argument checks: what the stages share, and the stages in the order Engine::fit_prepared runs them.
+struct Engine::FitRun {
+    Engine &e;
+    const PreparedDataset *const ds;
+    const FitOptions opt;
+    FitValid *const v;
+    const int iterations, n, D, bs, T0;   // T0: the tree count at entry
+    const bool generic = hooks::on(hooks::CONTINUE_GENERIC);
+    const float *dtar = nullptr, *dvtar = nullptr;   // the targets on the device (softmax: int32 labels behind them, one per row)
+    std::vector<int32_t> class_counts;               // softmax: rows per class of the training set
+    Held train, watched;                             // the training rows, in batches of bs; the validation rows, as one batch
+    float *G = nullptr;                              // [n][D]: the gradient of the current batch from row 0, of every row for the final loss
+    const int32_t *d_iota = nullptr;                 // 0 .. n - 1: the row ranges step_prepared's body gathers (bs < n)
+    double *d_vpart = nullptr, *d_vsums = nullptr;   // the validation rows' loss partials, one sum per iteration from k = 0
+    bool sampled = false, colsampled = false;
+    int32_t *d_srows = nullptr, *d_sscratch = nullptr;   // a sampled iteration: the kept rows of the batch, the sampler's block counts + m
+    float *Gs = nullptr;                                  // and their gradient rows
+    int start = 0, bn = 0;                               // the batch cursor
+
+    FitRun(Engine &eng, const PreparedDataset *data, int iters, const FitOptions &o, FitValid *valid)
+        : e(eng), ds(data), opt(o), v(valid), iterations(iters), n(data->n), D(eng.model.meta.output_dim), bs(eng.model.meta.batch_size), T0(eng.model.meta.n_trees) {
+        bn = start + bs < n ? bs : n - start;                                       // fitter.cpp:120
+    }
+
+    const float *stage(DevBuf &buf, const void *host_or_dev, bool on_dev, int rows) {
+        const float *t = static_cast<const float *>(host_or_dev);
+        return on_dev ? t : e.upload(buf, t, static_cast<size_t>(rows) * (opt.objective == kern::kObjSoftmax ? 1 : D), "H2D targets");
+    }
+    // Both target arrays on the device; softmax: a label outside [0, D), in either set, is refused before anything changes.
+    void stage_targets(const void *targets, bool targets_dev) {
+        dtar = stage(e.d_fp_targets_, targets, targets_dev, n);
+        if (v) dvtar = stage(e.d_fp_vtargets_, v->targets, v->targets_dev, v->ds->n);
+        if (opt.objective != kern::kObjSoftmax) return;
+        e.check_labels("fit_prepared", reinterpret_cast<const int32_t *>(dtar), n, D, &class_counts);
+        if (v) e.check_labels("fit_prepared (valid_targets)", reinterpret_cast<const int32_t *>(dvtar), v->ds->n, D, nullptr);
+    }
+    // A fresh model's bias by objective, and the feature counts as step_prepared latches them.
+    void set_bias(ColumnStats &stats) {
+        Model &model = e.model;
+        if (opt.objective == kern::kObjSoftmax) {   // the log prior, an empty class counted as half a row
+            for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(std::log(std::max(static_cast<double>(class_counts[d]), 0.5) / static_cast<double>(n)));
+        } else {
+            const std::vector<double> &hs = stats.sums(dtar, n, nullptr);
             const double lo = 0.5 / static_cast<double>(n);
             for (int d = 0; d < D; ++d) {
-                const double c = std::min(std::max(hs[d] / static_cast<double>(n), lo), 1.0 - lo);
-                model.bias[d] = static_cast<float>(std::log(c / (1.0 - c)));
+                const double mean = hs[d] / static_cast<double>(n);
+                if (opt.objective == kern::kObjRmse) {   // the column means of the targets (gbrl.cpp:1075-1077)
+                    model.bias[d] = static_cast<float>(mean);
+                } else {                                  // logistic: the log odds of the column mean, kept off 0 and 1 by half a row
+                    const double c = std::min(std::max(mean, lo), 1.0 - lo);
+                    model.bias[d] = static_cast<float>(std::log(c / (1.0 - c)));
+                }
             }
-        } else {                                        // the log prior, an empty class counted as half a row
-            for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(std::log(std::max(static_cast<double>(class_counts[d]), 0.5) / static_cast<double>(n)));
         }
         ++model.version;
-        if (md.iteration == 0) { md.n_num_features = ds->F; md.n_cat_features = 0; }
+        if (model.meta.iteration == 0) { model.meta.n_num_features = ds->F; model.meta.n_cat_features = 0; }
     }
-    // the held prediction: the tiled bias, valid through 0 trees for every batch
-    sync_model_to_device();
-    float *P = static_cast<float *>(d_fp_pred_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
-    float *G = static_cast<float *>(d_fp_grads_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
-    kern::tile_rows(m_bias_.as<float>(), D, n, P, s);
-    const int bs = md.batch_size;
-    const int n_batches = (n + bs - 1) / bs;   // (the batches of one cycle start at multiples of bs)
-    std::vector<int> through(n_batches, 0);    // per batch: its rows of P hold the trees [0, through)
-    const int32_t *d_iota = nullptr;
-    if (bs < n) {   // the row ranges step_prepared's body gathers
-        std::vector<int32_t> iota(n);
-        std::iota(iota.begin(), iota.end(), 0);
-        int32_t *d = static_cast<int32_t *>(d_fp_iota_.ensure(sizeof(int32_t) * n));
-        hip_check(hipMemcpyAsync(d, iota.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s), "H2D iota");
-        hip_check(hipStreamSynchronize(s), "sync");   // iota goes out of scope
-        d_iota = d;
-    }
-    const bool generic = hooks::on(hooks::CONTINUE_GENERIC);
-    auto advance = [&](int start, int bn, float *grad_out) {
-        advance_held(*ds, P, through[start / bs], start, bn, grad_out ? dtar : nullptr, grad_out, nullptr, nullptr, generic, objective);
-    };
-    // ---- the validation rows: a held prediction of their own, evaluated after every iteration by one launch + the finishing sum
-    const int T0 = md.n_trees;
-    const int nv = v ? v->ds->n : 0, nbv = v ? kern::staged_loss_partials(nv) : 0;
-    float *Pv = nullptr;
-    double *d_vpart = nullptr, *d_vsums = nullptr;
-    int through_v = 0, best = 0;
-    auto curve_of = [&](double sum) {   // staged_loss's expression; an objective's mean loss
-        return objective == kern::kObjRmse ? std::sqrt(0.5 * sum / static_cast<double>(nv)) : sum / static_cast<double>(nv);
-    };
-    auto evaluate = [&](int k) {   // valid_loss[k]: on the device; with a stopping rule also on the host (one 8-byte read-back)
-        advance_held(*v->ds, Pv, through_v, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, objective);
-        kern::staged_loss_finish(d_vpart, nbv, d_vsums + k, s);
-        if (v->rounds > 0) {
-            double sum = 0.0;
-            hip_check(hipMemcpyAsync(&sum, d_vsums + k, sizeof(double), hipMemcpyDeviceToHost, s), "D2H validation loss");
-            hip_check(hipStreamSynchronize(s), "sync");
-            v->loss_out[k] = curve_of(sum);
+    // The held predictions start as the tiled bias, through 0 trees everywhere.
+    void hold_predictions() {
+        hipStream_t s = e.stream_;
+        e.sync_model_to_device();
+        train.start(ds, static_cast<float *>(e.d_fp_pred_.ensure(sizeof(float) * static_cast<size_t>(n) * D)), bs);
+        G = static_cast<float *>(e.d_fp_grads_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+        kern::tile_rows(e.m_bias_.as<float>(), D, n, train.P, s);
+        if (bs < n) {
+            std::vector<int32_t> iota(n);
+            std::iota(iota.begin(), iota.end(), 0);
+            d_iota = e.upload(e.d_fp_iota_, iota.data(), iota.size(), "H2D iota");
+            hip_check(hipStreamSynchronize(s), "sync");   // iota goes out of scope
         }
-    };
-    if (v) {
-        Pv = static_cast<float *>(d_fp_vpred_.ensure(sizeof(float) * static_cast<size_t>(nv) * D));
-        d_vpart = static_cast<double *>(d_fp_vpart_.ensure(sizeof(double) * nbv));
-        d_vsums = static_cast<double *>(d_fp_vsums_.ensure(sizeof(double) * (static_cast<size_t>(iterations) + 1)));
-        kern::tile_rows(m_bias_.as<float>(), D, nv, Pv, s);
-        v->done = 0; v->best_n_trees = T0;
-        evaluate(0);
+        if (v == nullptr) return;
+        const int nv = v->ds->n;
+        watched.start(v->ds, static_cast<float *>(e.d_fp_vpred_.ensure(sizeof(float) * static_cast<size_t>(nv) * D)), nv);
+        d_vpart = static_cast<double *>(e.d_fp_vpart_.ensure(sizeof(double) * kern::staged_loss_partials(nv)));
+        d_vsums = static_cast<double *>(e.d_fp_vsums_.ensure(sizeof(double) * (static_cast<size_t>(iterations) + 1)));
+        kern::tile_rows(e.m_bias_.as<float>(), D, nv, watched.P, s);
+        v->best_n_trees = T0;
     }
-    // ---- a sampled fit: the kept rows of a batch, their gradient rows, the block counts of the sampler (subsample == 1.0: none of it exists)
-    const bool sampled = subsample < 1.0;
-    const uint32_t keep_thr = kern::sample_threshold(subsample);
-    int32_t *d_srows = nullptr, *d_sscratch = nullptr;
-    float *Gs = nullptr;
-    if (sampled) {
+    // ---- the validation watch
+    // loss_out[k] after k iterations: one launch + the finishing sum on the device; with a stopping rule also on the host (one 8-byte read-back)
+    void evaluate(int k) {
+        const int nv = v->ds->n;
+        v->done = k;
+        e.advance_held(watched, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, opt.objective);
+        double sum = 0.0;
+        e.finish_loss_sum(d_vpart, kern::staged_loss_partials(nv), d_vsums + k, v->rounds > 0 ? &sum : nullptr);
+        if (v->rounds > 0) {
+            hip_check(hipStreamSynchronize(e.stream_), "sync");
+            v->loss_out[k] = mean_loss(opt.objective, sum, nv);
+        }
+    }
+    int best_of_curve() const {
+        int stop_after = 0, best = 0;
+        early_stop_scan(v->loss_out, v->done + 1, v->rounds, v->min_delta, &stop_after, &best);
+        return best;
+    }
+    bool stops_early() const { return v->rounds > 0 && v->done - best_of_curve() >= v->rounds; }
+    void finish_watch() {
+        if (v->rounds == 0) {   // the sums stayed on the device
+            std::vector<double> sums(static_cast<size_t>(v->done) + 1);
+            hip_check(hipMemcpyAsync(sums.data(), d_vsums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, e.stream_), "D2H validation losses");
+            hip_check(hipStreamSynchronize(e.stream_), "sync");
+            for (int k = 0; k <= v->done; ++k) v->loss_out[k] = mean_loss(opt.objective, sums[k], v->ds->n);
+        }
+        v->best_n_trees = T0 + best_of_curve();
+    }
+    // ---- the iterations
+    // The workspace of the draws.  subsample == 1.0: no sampler exists; colsample == 1.0, or k == F: step_prepared_run never sees cols.
+    void prepare_draws() {
+        sampled = opt.subsample < 1.0;
+        colsampled = opt.colsample < 1.0 && kern::sample_cols_count(ds->F, opt.colsample) < ds->F;
+        if (!sampled) return;
         const int cap = std::min(bs, n);
-        d_srows = static_cast<int32_t *>(d_fp_srows_.ensure(sizeof(int32_t) * static_cast<size_t>(cap)));
-        Gs = static_cast<float *>(d_fp_sgrads_.ensure(sizeof(float) * static_cast<size_t>(cap) * D));
-        d_sscratch = static_cast<int32_t *>(d_fp_sscratch_.ensure(sizeof(int32_t) * (static_cast<size_t>(kern::sample_rows_blocks(cap)) + 1)));
+        d_srows = static_cast<int32_t *>(e.d_fp_srows_.ensure(sizeof(int32_t) * static_cast<size_t>(cap)));
+        Gs = static_cast<float *>(e.d_fp_sgrads_.ensure(sizeof(float) * static_cast<size_t>(cap) * D));
+        d_sscratch = static_cast<int32_t *>(e.d_fp_sscratch_.ensure(sizeof(int32_t) * (static_cast<size_t>(kern::sample_rows_blocks(cap)) + 1)));
     }
-    // ---- a column-sampled fit: a draw of k < F columns per tree (colsample == 1.0, or k == F: step_prepared_run never sees cols)
-    const bool colsampled = colsample < 1.0 && kern::sample_cols_count(ds->F, colsample) < ds->F;
-    int start = 0, done = 0;
-    int bn = start + bs < n ? bs : n - start;                                   // fitter.cpp:120
-    for (int i = 0; i < iterations; ++i) {
-        begin_step_profile();
-        phase_begin();
-        advance(start, bn, G);
-        phase_end("continue_codes");
+    // One tree on the batch under the cursor.  Both draws are those of the tree count before the step.
+    void iterate() {
+        hipStream_t s = e.stream_;
+        const int trees = e.model.meta.n_trees;
+        e.begin_step_profile();
+        e.phase_begin();
+        e.advance_held(train, start, bn, dtar, G, nullptr, nullptr, generic, opt.objective);
+        e.phase_end("continue_codes");
         const float *g = G;
         const int32_t *rows = bn == n ? nullptr : d_iota + start;
         int m = bn;
-        if (sampled) {   // draw = the tree count before the step; a draw that keeps no row takes the whole batch
-            phase_begin();
-            kern::sample_rows(start, bn, keep_thr, seed, md.n_trees, G, D, d_srows, Gs, d_sscratch, s);
+        if (sampled) {   // a draw that keeps no row takes the whole batch
+            e.phase_begin();
+            kern::sample_rows(start, bn, kern::sample_threshold(opt.subsample), opt.seed, trees, G, D, d_srows, Gs, d_sscratch, s);
             int32_t kept = 0;
             hip_check(hipMemcpyAsync(&kept, d_sscratch, sizeof(kept), hipMemcpyDeviceToHost, s), "D2H sample count");
-            phase_end("sample_rows");
+            e.phase_end("sample_rows");
             hip_check(hipStreamSynchronize(s), "sync");
             if (kept > 0) { g = Gs; rows = d_srows; m = kept; }
         }
-        if (colsampled) {   // draw = the tree count before the step, the row sampler's seed
-            kern::sample_cols(ds->F, colsample, seed, md.n_trees, fit_cols_);
-            step_prepared_run(ds, g, rows, m, fit_cols_.data(), static_cast<int>(fit_cols_.size()));
+        if (colsampled) {
+            kern::sample_cols(ds->F, opt.colsample, opt.seed, trees, e.fit_cols_);
+            e.step_prepared_run(ds, g, rows, m, e.fit_cols_.data(), static_cast<int>(e.fit_cols_.size()));
         } else {
-            step_prepared_run(ds, g, rows, m);
+            e.step_prepared_run(ds, g, rows, m);
         }
-        start += bn;                                                            // fitter.cpp:228-231
+        start += bn;                                                                // fitter.cpp:228-231
         if (start >= n) start = 0;
         bn = start + bs < n ? bs : n - start;
-        done = i + 1;
-        if (v) {
-            v->done = done;
-            evaluate(done);
-            if (v->rounds > 0) {
-                int stop_after = 0;
-                early_stop_scan(v->loss_out, done + 1, v->rounds, v->min_delta, &stop_after, &best);
-                if (done - best >= v->rounds) break;
-            }
-        }
     }
-    if (v) {
-        if (v->rounds == 0) {   // the sums stayed on the device
-            std::vector<double> sums(static_cast<size_t>(done) + 1);
-            hip_check(hipMemcpyAsync(sums.data(), d_vsums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, s), "D2H validation losses");
-            hip_check(hipStreamSynchronize(s), "sync");
-            for (int k = 0; k <= done; ++k) v->loss_out[k] = curve_of(sums[k]);
+    // Every batch to the end; the loss on the whole data set (fitter.cpp:246-251).  rmse: from the gradient of every row, written by the same
+    // launches, as fit() computes it; an objective: from the held prediction by the stand-alone kernel, the loss tail's partials and sum.
+    float final_loss(ColumnStats &stats) {
+        const bool rmse = opt.objective == kern::kObjRmse;
+        for (int b0 = 0; b0 < n; b0 += bs)
+            e.advance_held(train, b0, std::min(bs, n - b0), rmse ? dtar : nullptr, rmse ? G + static_cast<size_t>(b0) * D : nullptr, nullptr, nullptr, generic, opt.objective);
+        if (rmse) {
+            hip_check(hipGetLastError(), "fit_prepared kernels");
+            return stats.rmse(G, n);
         }
-        int stop_after = 0;
-        early_stop_scan(v->loss_out, done + 1, v->rounds, v->min_delta, &stop_after, &best);
-        v->best_n_trees = T0 + best;
-    }
-    // every batch to the end; the loss on the whole data set (fitter.cpp:246-251)
-    if (objective != kern::kObjRmse) {   // the objective's loss of the held prediction: the stand-alone kernel, the loss tail's partials and sum
-        for (int b0 = 0; b0 < n; b0 += bs) advance(b0, std::min(bs, n - b0), nullptr);
         const int nb = kern::staged_loss_partials(n);
-        double *d_part = static_cast<double *>(d_obj_part_.ensure(sizeof(double) * nb)), *d_sum = static_cast<double *>(d_obj_sum_.ensure(sizeof(double)));
-        kern::objective_rows(objective, P, dtar, n, D, nullptr, d_part, s);
-        kern::staged_loss_finish(d_part, nb, d_sum, s);
+        double *d_part = static_cast<double *>(e.d_obj_part_.ensure(sizeof(double) * nb)), *d_sum = static_cast<double *>(e.d_obj_sum_.ensure(sizeof(double)));
+        kern::objective_rows(opt.objective, train.P, dtar, n, D, nullptr, d_part, e.stream_);
         double sum = 0.0;
-        hip_check(hipMemcpyAsync(&sum, d_sum, sizeof(double), hipMemcpyDeviceToHost, s), "D2H loss");
+        e.finish_loss_sum(d_part, nb, d_sum, &sum);
         hip_check(hipGetLastError(), "fit_prepared kernels");
-        hip_check(hipStreamSynchronize(s), "sync");
-        return static_cast<float>(sum / static_cast<double>(n));
+        hip_check(hipStreamSynchronize(e.stream_), "sync");
+        return static_cast<float>(mean_loss(opt.objective, sum, n));
     }
-    for (int b0 = 0; b0 < n; b0 += bs) advance(b0, std::min(bs, n - b0), G + static_cast<size_t>(b0) * D);
-    hip_check(hipGetLastError(), "fit_prepared kernels");
-    return rmse(G, n);
+};
+
+float Engine::fit_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, const FitOptions &opt, FitValid *valid) {
+    precheck_fit(targets, iterations, opt, valid);
+    check_prepared_dataset("fit_prepared", ds);
+    if (valid) {
+        check_prepared_dataset("fit_prepared", valid->ds);
+        if (valid->ds->thresholds_id != ds->thresholds_id)
+            throw InvalidArgument("fit_prepared: the validation set does not share the training set's thresholds (create it with prepare_dataset(obs, reference=ds))");
+        if (valid->loss_out == nullptr) throw InvalidArgument("fit_prepared: no place for the validation losses");
+    }
+    const bool fresh = model.meta.n_trees == 0;
+    if (!fresh) check_code_range(*ds, "fit_prepared", 0, model.meta.n_trees);   // a warm start continues from every tree the model has
+    ensure_device();
+    FitRun run(*this, ds, iterations, opt, valid);
+    run.stage_targets(targets, targets_dev);
+    ColumnStats stats(*this);
+    if (fresh) run.set_bias(stats);
+    run.hold_predictions();
+    if (valid) run.evaluate(0);
+    run.prepare_draws();
+    for (int i = 0; i < iterations; ++i) {
+        run.iterate();
+        if (valid == nullptr) continue;
+        run.evaluate(i + 1);
+        if (run.stops_early()) break;
+    }
+    if (valid) run.finish_watch();
+    return run.final_loss(stats);
 }
 
 }  // namespace gbrl
+

@@ -610,6 +610,29 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
 }
 
 // ===================================================================================================== fit
+Engine::ColumnStats::ColumnStats(Engine &e) : e_(e), D_(e.model.meta.output_dim), hs_(2 * D_) {
+    d_zero_ = static_cast<float *>(e_.d_fit_zero_.ensure(sizeof(float) * D_));
+    hip_check(hipMemsetAsync(d_zero_, 0, sizeof(float) * D_, e_.stream_), "memset");
+    d_stat_ = static_cast<double *>(e_.d_stat_.ensure(sizeof(double) * 4 * D_));
+}
+
+const std::vector<double> &Engine::ColumnStats::sums(const float *g, int rows, const float *center) {
+    hipStream_t s = e_.stream_;
+    const int nblk = kern::column_sums_blocks(rows, D_);
+    double *d_part = static_cast<double *>(e_.d_partials_f64_.ensure(sizeof(double) * nblk * 2 * D_));
+    kern::column_sums(g, rows, D_, center, d_part, nblk, d_stat_, s);
+    hip_check(hipMemcpyAsync(hs_.data(), d_stat_, sizeof(double) * 2 * D_, hipMemcpyDeviceToHost, s), "D2H stat");
+    hip_check(hipStreamSynchronize(s), "sync");
+    return hs_;
+}
+
+float Engine::ColumnStats::rmse(const float *grads_dev, int rows) {
+    sums(grads_dev, rows, d_zero_);
+    double tot = 0.0;
+    for (int d = 0; d < D_; ++d) tot += hs_[d];
+    return sqrtf(0.5f * static_cast<float>(tot) * (1.0f / static_cast<float>(rows)));
+}
+
 float Engine::fit(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num,
                   int n_cat, int iterations, bool shuffle) {
     gbrl_hip_metadata &md = model.meta;
@@ -666,25 +689,9 @@ float Engine::fit(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
         dobs = o2;
         dtar = t2;
     }
-    float *d_zero = static_cast<float *>(d_fit_zero_.ensure(sizeof(float) * D));
-    hip_check(hipMemsetAsync(d_zero, 0, sizeof(float) * D, s), "memset");
-    double *d_stat = static_cast<double *>(d_stat_.ensure(sizeof(double) * 4 * D));
-    std::vector<double> hs(2 * D);
-    auto column_stat = [&](const float *g, int rows, const float *center) {   // column sums (center null) or sums of squares
-        const int nblk = kern::column_sums_blocks(rows, D);
-        double *d_part = static_cast<double *>(d_partials_f64_.ensure(sizeof(double) * nblk * 2 * D));
-        kern::column_sums(g, rows, D, center, d_part, nblk, d_stat, s);
-        hip_check(hipMemcpyAsync(hs.data(), d_stat, sizeof(double) * 2 * D, hipMemcpyDeviceToHost, s), "D2H stat");
-        hip_check(hipStreamSynchronize(s), "sync");
-    };
-    auto rmse = [&](const float *grads_dev, int rows) {                       // MultiRMSE, loss.cpp:42-56: sqrt(0.5 * sum g^2 / rows)
-        column_stat(grads_dev, rows, d_zero);
-        double tot = 0.0;
-        for (int d = 0; d < D; ++d) tot += hs[d];
-        return sqrtf(0.5f * static_cast<float>(tot) * (1.0f / static_cast<float>(rows)));
-    };
+    ColumnStats stats(*this);
     // bias = column means of the targets (gbrl.cpp:1075-1077)
-    column_stat(dtar, n, nullptr);
+    const std::vector<double> &hs = stats.sums(dtar, n, nullptr);
     for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(hs[d] / static_cast<double>(n));
     ++model.version;
 
@@ -731,7 +738,7 @@ float Engine::fit(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
     in_fit_ = false;
     float *d_full_grads = static_cast<float *>(d_fit_grads_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
     kern::sub_arrays(d_preds, dtar, d_full_grads, static_cast<size_t>(n) * D, s);
-    return rmse(d_full_grads, n);
+    return stats.rmse(d_full_grads, n);
 }
 
 }  // namespace gbrl
