@@ -146,6 +146,10 @@ int parse_objective(const std::string &s) {
     return parse_enum(s, {{"rmse", GBRL_HIP_OBJ_RMSE}, {"logistic", GBRL_HIP_OBJ_LOGISTIC}, {"softmax", GBRL_HIP_OBJ_SOFTMAX}},
                       "Invalid objective! Options are: rmse/logistic/softmax");
 }
+// metric names of fit_prepared(eval_metric=), eval_metric and eval_metric_host (GBRL_HIP_METRIC_*, include/gbrl_hip.h)
+int parse_metric(const std::string &s) {
+    return parse_enum(s, {{"error", GBRL_HIP_METRIC_ERROR}, {"auc", GBRL_HIP_METRIC_AUC}}, "Invalid metric! Options are: error/auc");
+}
 const char *parity_mode_name(int mode) {
     return mode == GBRL_HIP_PARITY_REFERENCE ? "reference" : (mode == GBRL_HIP_PARITY_EXACT_ARGMAX ? "exact_argmax" : "default");
 }
@@ -814,26 +818,29 @@ Input read_objective_targets(py::object &targets, const char *name, bool none_al
 }
 
 // fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,
-// objective='rmse'): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
+// objective='rmse', eval_metric=None): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
 // with either.  A missing valid_targets is left to the C ABI's message.
 py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
-                             int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name) {
+                             int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name,
+                             py::object metric_obj) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     const int objective = parse_objective(objective_name);
+    const int metric = metric_obj.is_none() ? GBRL_HIP_METRIC_NONE : parse_metric(metric_obj.cast<std::string>());
     if (valid_obj.is_none() && (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0))
         fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
     const gbrl_hip_dataset *dsv = valid_obj.is_none() ? nullptr : valid_obj.cast<const PyDataset &>().h;
     Input t = read_objective_targets(targets, "targets", false, "fit", objective, ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, md.output_dim, ds != nullptr);
     Input tv;
     if (dsv) tv = read_objective_targets(valid_targets, "valid_targets", true, "fit", objective, valid_obj.cast<const PyDataset &>().info().n_rows, md.output_dim, true);
-    std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0);
+    std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0), mcurve(metric != GBRL_HIP_METRIC_NONE ? curve.size() : 0, 0.0);
     float loss = 0.0f;
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_objective(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
-                                             colsample, seed, objective, &loss, dsv ? curve.data() : nullptr, &done, &best);
+        rc = gbrl_hip_fit_prepared_metric(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                          colsample, seed, objective, metric, &loss, dsv ? curve.data() : nullptr, dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr,
+                                          &done, &best);
     }
     check(rc);
     if (!dsv) return py::float_(loss);
@@ -844,7 +851,56 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     out["valid_loss"] = vl;
     out["iterations"] = py::int_(done);
     out["best_n_trees"] = py::int_(best);
+    if (metric != GBRL_HIP_METRIC_NONE) {
+        py::array_t<double> vm(static_cast<py::ssize_t>(done) + 1);
+        std::copy(mcurve.begin(), mcurve.begin() + done + 1, vm.mutable_data());
+        out["valid_metric"] = vm;
+        out["eval_metric"] = metric_obj;
+    }
     return std::move(out);
+}
+
+// the counts of a metric as int64: [D, 3] = (2U_d, P_d, N_d) for auc, [D] (softmax: [1]) for error
+py::array_t<int64_t> metric_counts_array(int objective, int metric, int D) {
+    const py::ssize_t C = objective == GBRL_HIP_OBJ_SOFTMAX ? 1 : D;
+    if (metric == GBRL_HIP_METRIC_AUC) return py::array_t<int64_t>(std::vector<py::ssize_t>{C, 3});
+    return py::array_t<int64_t>(std::vector<py::ssize_t>{C});
+}
+
+// eval_metric(pred, targets, objective, metric) -> (value, counts): NumPy arrays or device tuples in, a float and an int64 NumPy array out
+py::tuple eval_metric_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, const std::string &metric_name) {
+    const gbrl_hip_metadata md = self.meta();
+    const int objective = parse_objective(objective_name), metric = parse_metric(metric_name), D = md.output_dim;
+    Input p = read_input(pred, "pred", false, "eval_metric", false);
+    if (!p.ptr) fail("Cannot call eval_metric without pred!");
+    const int n = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
+    check_rows_by_outputs(p, "pred", n, D);
+    Input t = read_objective_targets(targets, "targets", false, "eval_metric", objective, n, D, true);
+    if (!t.ptr) fail("Cannot call eval_metric without targets!");
+    py::array_t<int64_t> counts = metric_counts_array(objective, metric, D);
+    double value = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_eval_metric(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, n, objective, metric, &value, counts.mutable_data());
+    }
+    check(rc);
+    return py::make_tuple(py::float_(value), counts);
+}
+
+// the definitions on the host (include/gbrl_hip.h, "Classifier metrics"): no device, no model
+py::tuple eval_metric_host_impl(py::object &pred, py::object &targets, const std::string &objective_name, const std::string &metric_name) {
+    const int objective = parse_objective(objective_name), metric = parse_metric(metric_name);
+    Input p = read_input(pred, "pred", false, "eval_metric_host", false);
+    if (p.on_device) fail("eval_metric_host takes NumPy arrays");
+    if (p.shape.empty() || p.shape.size() > 2) fail("pred must be a float32 array of shape (n, D) or (n,)");
+    const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
+    Input t = read_objective_targets(targets, "targets", false, "eval_metric_host", objective, n, D, true);
+    if (t.on_device) fail("eval_metric_host takes NumPy arrays");
+    py::array_t<int64_t> counts = metric_counts_array(objective, metric, std::max(D, 1));
+    double value = 0.0;
+    check(gbrl_hip_eval_metric_host(static_cast<const float *>(p.ptr), t.ptr, n, D, objective, metric, &value, counts.mutable_data()));
+    return py::make_tuple(py::float_(value), counts);
 }
 
 // objective_gradient(pred, targets, objective) -> (grad, loss): NumPy in, NumPy out; a device tuple gives a DLPack capsule on the model's device
@@ -1093,6 +1149,14 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "The gradient rule of fit_prepared(objective=) on the host (no device is needed): 'logistic': sigmoid(p) - y, targets float32 like pred;\n"
           "'softmax': softmax(p) - onehot(y), targets int32 [n] labels in [0, D), D >= 2; 'rmse': p - y.  Every float32 step is the one definition the\n"
           "kernels use (an exponential written out in fmaf, correctly rounded division): the device gives the same bits.");
+    m.def("eval_metric_host", &eval_metric_host_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("metric"),
+          "eval_metric_host(pred, targets, objective, metric) -> (value, counts)\n\n"
+          "The classifier metrics of fit_prepared(eval_metric=) on the host (no device is needed), as include/gbrl_hip.h defines them.  metric 'error':\n"
+          "objective 'softmax' (int32 labels [n]) counts the rows whose arg-max (lowest index among equal maxima) is not the label, counts int64 [1];\n"
+          "'logistic' (float32 targets like pred) counts the cells with (p > 0) != (y > 0.5) per column, counts int64 [D]; value = wrong / cells.\n"
+          "metric 'auc' ('logistic' only): per column the exact AUC with ties counted half, from counts int64 [D, 3] = (2U, P, N): AUC = 2U / (2 P N),\n"
+          "value = their mean.  Scores compare through one key (-0.0 == +0.0; a NaN is ordered by its bits: defined, meaningless).  Refused: an unknown\n"
+          "name, a metric with 'rmse', 'auc' with 'softmax', a column of one class (named).");
     m.def("objective_exp_host", &objective_exp_host_impl, py::arg("t"), py::arg("rounded") = false,
           "objective_exp_host(t, rounded=False) -> NumPy array shaped like t\n\n"
           "obj_exp of the objectives (include/gbrl_hip.h): exp(t) for t <= 0 in explicit float32 steps, +0 below -104 -- the value p * 2^k itself as\n"
@@ -1187,12 +1251,12 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         // likewise: fit_prepared(ds, targets, iterations) -> float keeps its generated line; the validation form is the second overload
         g.def("fit_prepared", [](PyGBRL &self, py::object ds, py::object &targets, int iterations) -> float {
             py::object none = py::none();
-            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse").cast<float>();
+            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none).cast<float>();
         }, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
             "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,\n"
-            "             objective='rmse') -> float | dict\n\n"
+            "             objective='rmse', eval_metric=None) -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
             "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
@@ -1223,13 +1287,25 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "bias is the log odds of the column means (clamped to [1/2n, 1 - 1/2n]) or the log class frequencies (an empty class counts 0.5 rows).  'loss' and\n"
             "'valid_loss' are the mean loss per row (not a square root); predict returns raw scores: apply sigmoid / softmax yourself.  objective='rmse' is\n"
             "the call without the keyword.  Refused before anything changes: an unknown objective, softmax on a model with one output, float targets\n"
-            "where labels are wanted and the reverse, a label outside [0, D).";
+            "where labels are wanted and the reverse, a label outside [0, D).\n"
+            "eval_metric='error' | 'auc' (with valid= and a classification objective): the dict gains 'valid_metric' (float64 [iterations + 1]: entry k is\n"
+            "gbrl_cpp.eval_metric_host of the validation rows' prediction after k iterations, exactly -- the integers are counted on the device behind the\n"
+            "validation launch) and 'eval_metric'.  The stopping rule and 'best_n_trees' then follow that curve in place of 'valid_loss' (the error as it is,\n"
+            "the AUC negated), 'valid_loss' is recorded as ever, and the model is byte for byte what the call without the keyword leaves after the same\n"
+            "number of iterations.  'error': the share of wrong arg-max rows (softmax) or of cells with (p > 0) != (y > 0.5) (logistic); 'auc' (logistic):\n"
+            "the mean over the columns of the exact AUC, ties counted half.  Refused before anything changes: eval_metric without valid=, an unknown\n"
+            "name, a metric with 'rmse', 'auc' with 'softmax', a column of valid_targets with one class.";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
-              py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse");
+              py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse", py::arg("eval_metric") = py::none());
     }
+    g.def("eval_metric", &eval_metric_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("metric"),
+          "eval_metric(pred, targets, objective, metric) -> (value, counts)\n\n"
+          "gbrl_cpp.eval_metric_host(pred, targets, objective, metric) computed on the model's device: the same integers (counts, int64) and therefore the\n"
+          "same value, bit for bit.  pred [n, output_dim] and targets are NumPy arrays or device tuples.  'error' is one launch; 'auc' sorts the score\n"
+          "columns with a segmented radix sort, prefix-counts the negatives and sums ranks with integer atomics: two calls give the same bytes.");
     g.def("objective_gradient", &objective_gradient_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"),
           "objective_gradient(pred, targets, objective) -> (grad, loss)\n\n"
           "The gradient dL/dp [n, output_dim] and the loss of the raw scores pred under objective 'rmse' | 'logistic' | 'softmax', computed on the model's\n"

@@ -17,6 +17,7 @@
 #include "../../include/gbrl_hip.h"
 #include "engine.h"
 #include "objective_core.h"
+#include "metric_core.h"
 #include "hooks.h"
 #include "explain.h"
 #include "rccl_dyn.h"
@@ -561,19 +562,20 @@ int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset
     });
 }
 
-// The one body of the five gbrl_hip_fit_prepared* spellings.  valid_required (gbrl_hip_fit_prepared_valid): a NULL valid_ds is a null data set;
+// The one body of the six gbrl_hip_fit_prepared* spellings.  valid_required (gbrl_hip_fit_prepared_valid): a NULL valid_ds is a null data set;
 // otherwise it means "no validation", the other validation arguments must then be at their defaults, *iterations_done = iterations and
 // *best_n_trees is left alone.  Every refusal that needs no data set comes before a handle is resolved, the validation handle before the
 // training handle, and nothing is written on a refusal.
 static int fit_prepared_call(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations, bool valid_required,
                              const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds, double min_delta,
-                             const gbrl::FitOptions &opt, float *loss_out, double *valid_loss_out, int *iterations_done, int *best_n_trees) {
+                             const gbrl::FitOptions &opt, float *loss_out, double *valid_loss_out, int *iterations_done, int *best_n_trees,
+                             double *valid_metric_out = nullptr) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");
-        gbrl::Engine::FitValid v{nullptr, valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0};
+        gbrl::Engine::FitValid v{nullptr, valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0, valid_metric_out};
         gbrl::Engine::FitValid *valid = valid_required || valid_ds != nullptr ? &v : nullptr;
         m->engine.precheck_fit(targets, iterations, opt, valid);
-        if (!valid && (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr))
+        if (!valid && (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr || valid_metric_out != nullptr))
             throw gbrl::InvalidArgument("fit_prepared: valid_targets, early_stopping_rounds, min_delta and valid_loss_out need a validation set");
         if (valid) v.ds = &live_dataset(valid_ds);
         const float loss = m->engine.fit_prepared(&live_dataset(ds), targets, targets_on_device != 0, iterations, opt, valid);
@@ -664,6 +666,29 @@ int gbrl_hip_fit_prepared_objective(gbrl_hip_model *m, const gbrl_hip_dataset *d
                                     double *valid_loss_out, int *iterations_done, int *best_n_trees) {
     return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
                              {subsample, colsample, seed, objective}, loss_out, valid_loss_out, iterations_done, best_n_trees);
+}
+
+// ---- classifier metrics: fit_prepared watched by one, the metric of a prediction matrix on the device and on the host
+static_assert(gbrl::kern::kMetricNone == GBRL_HIP_METRIC_NONE && gbrl::kern::kMetricError == GBRL_HIP_METRIC_ERROR && gbrl::kern::kMetricAuc == GBRL_HIP_METRIC_AUC,
+              "the kernels' metrics are the header's");
+int gbrl_hip_fit_prepared_metric(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                                 const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                 double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, float *loss_out,
+                                 double *valid_loss_out, double *valid_metric_out, int *iterations_done, int *best_n_trees) {
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, colsample, seed, objective, metric}, loss_out, valid_loss_out, iterations_done, best_n_trees, valid_metric_out);
+}
+
+int gbrl_hip_eval_metric(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective, int metric,
+                         double *value_out, int64_t *counts_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.eval_metric(pred, pred_on_device != 0, targets, targets_on_device != 0, n, objective, metric, value_out, counts_out);
+    });
+}
+
+int gbrl_hip_eval_metric_host(const float *pred, const void *targets, int n, int D, int objective, int metric, double *value_out, int64_t *counts_out) {
+    return guarded([&] { gbrl::Engine::eval_metric_host(pred, targets, n, D, objective, metric, value_out, counts_out); });
 }
 
 int gbrl_hip_objective_gradient(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective,

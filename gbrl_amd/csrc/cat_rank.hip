@@ -7,7 +7,7 @@
 // totals here equal that serial loop BIT FOR BIT:
 //   (a) k_rank_norms   : norm[i] = fma chain over the raw gradients of row i (calculate_squared_norm, math_ops.cpp:726-749, contracted)
 //   (b) k_rank_keys    : list index q of every cell through the scan's own hash tables (categorical.hip) + count[q]
-//   (c) k_radix_*      : stable LSD radix sort (8-bit digits) of the cells by q.  The cells start in (row, feature) order and one q belongs
+//   (c) radix_sort_pass: stable LSD radix sort (8-bit digits, radix_sort.hip) of the cells by q.  The cells start in (row, feature) order and one q belongs
 //                        to one feature, so after a STABLE sort the rows of a category are contiguous and ascending
 //   (d) k_rank_short   : one thread per category adds its rows' norms one by one; categories with more than kRankLong rows go through
 //                        kern::seq_sums (seqsum.hip), which evaluates a sequential float32 sum in parallel, bit for bit
@@ -27,9 +27,7 @@ namespace kern {
 namespace {
 
 constexpr int kRankLong = 1024;           // rows of one category above which its chain goes through seq_sums
-constexpr int kRadixThreads = 256;        // four waves
-constexpr int kRadixRounds = 8;           // elements per thread and tile
-constexpr int kRadixTile = kRadixThreads * kRadixRounds;
+constexpr int kRadixTile = kRadixSortTile;   // (radix_sort.hip: the elements one block of a sort pass owns)
 constexpr int kRankMaxProbes = 512;       // (kCatMaxProbes of categorical.hip: the probe that inserted a cell finds it again)
 
 __device__ __forceinline__ uint64_t rank_cell_hash(const char *cell) {
@@ -78,81 +76,6 @@ __global__ __launch_bounds__(256) void k_rank_keys(const char *__restrict__ cell
     else atomicAdd(&count[q], 1);
     qkey[i] = static_cast<uint32_t>(q);
     rowv[i] = i / static_cast<uint32_t>(Fc);
-}
-
-// ---- stable LSD radix sort of (key, value) pairs, 8 bits per pass: per-tile digit counts, one exclusive scan (digit-major, so that the
-// scan IS the output offset of every (digit, tile)), stable scatter -------------------------------------------------------------------
-__global__ __launch_bounds__(kRadixThreads) void k_radix_hist(const uint32_t *__restrict__ key, uint32_t n, int shift, uint32_t n_tiles,
-                                                              uint32_t *__restrict__ hist) {
-    __shared__ uint32_t h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t t0 = blockIdx.x * static_cast<uint32_t>(kRadixTile);
-    for (int r = 0; r < kRadixRounds; ++r) {
-        const uint32_t i = t0 + r * kRadixThreads + threadIdx.x;
-        if (i < n) atomicAdd(&h[(key[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[static_cast<size_t>(threadIdx.x) * n_tiles + blockIdx.x] = h[threadIdx.x];
-}
-__global__ __launch_bounds__(1024) void k_radix_scan(uint32_t *__restrict__ hist, uint32_t total) {
-    __shared__ uint32_t part[1024];
-    const uint32_t per = (total + 1023u) / 1024u, b = threadIdx.x * per, e = min(total, b + per);
-    uint32_t s = 0;
-    for (uint32_t i = b; i < e; ++i) s += hist[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const uint32_t add = threadIdx.x >= static_cast<uint32_t>(o) ? part[threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t run = part[threadIdx.x] - s;
-    for (uint32_t i = b; i < e; ++i) { const uint32_t c = hist[i]; hist[i] = run; run += c; }
-}
-// One tile per block, in kRadixRounds rounds of 256 consecutive elements.  Inside a round the position of an element is
-//   run[digit] (everything before this round) + the counts of the digit in the lower waves + its rank among the wave's lanes with the digit,
-// the latter from ballots over the digit's bits (wave64: the lanes below mine that hold my digit).
-__global__ __launch_bounds__(kRadixThreads) void k_radix_scatter(const uint32_t *__restrict__ key, const uint32_t *__restrict__ val, uint32_t n,
-                                                                 int shift, uint32_t n_tiles, const uint32_t *__restrict__ hist,
-                                                                 uint32_t *__restrict__ key_out, uint32_t *__restrict__ val_out) {
-    constexpr int kWaves = kRadixThreads / kWave;
-    __shared__ uint32_t run[256];
-    __shared__ uint32_t wcnt[kWaves][256];
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-    run[tid] = hist[static_cast<size_t>(tid) * n_tiles + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) wcnt[w][tid] = 0;
-    __syncthreads();
-    const uint32_t t0 = blockIdx.x * static_cast<uint32_t>(kRadixTile);
-    for (int r = 0; r < kRadixRounds; ++r) {
-        const uint32_t i = t0 + r * kRadixThreads + tid;
-        const bool valid = i < n;
-        const uint32_t k = valid ? key[i] : 0u, v = valid ? val[i] : 0u;
-        const uint32_t d = (k >> shift) & 255u;
-        unsigned long long peers = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool one = (d >> bit) & 1u;
-            const unsigned long long m = __ballot(valid && one);
-            peers &= one ? m : ~m;
-        }
-        const int below = __popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && below == 0) wcnt[wave][d] = static_cast<uint32_t>(__popcll(peers));
-        __syncthreads();
-        if (valid) {
-            uint32_t pos = run[d] + static_cast<uint32_t>(below);
-            for (int w = 0; w < wave; ++w) pos += wcnt[w][d];
-            if (pos < n) { key_out[pos] = k; val_out[pos] = v; }   // (pos < n always: the offsets are a permutation of [0, n))
-        }
-        __syncthreads();
-        uint32_t add = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) { add += wcnt[w][tid]; wcnt[w][tid] = 0; }
-        run[tid] += add;
-        __syncthreads();
-    }
 }
 
 // the sorted cells: first position of every category, the norms in sorted order, and the categories whose chain is long.  A long
@@ -238,7 +161,7 @@ struct RankLayout {
 };
 RankLayout rank_layout(int N, size_t n_cells, int n_q) {
     RankLayout L{};
-    L.n_tiles = static_cast<uint32_t>((n_cells + kRadixTile - 1) / kRadixTile);
+    L.n_tiles = radix_sort_tiles(n_cells);
     L.n_slots = static_cast<int>((n_cells + kRankLong - 1) / kRankLong);
     L.seq_blocks = static_cast<uint32_t>(n_cells / 256 + static_cast<size_t>(L.n_slots) + 2);
     size_t o = 0;
@@ -292,9 +215,7 @@ void cat_rank(const char *cells, int N, int Fc, const float *grads, int D, const
     int bits = 1;
     while (bits < 32 && (static_cast<uint32_t>(n_q - 1) >> bits)) ++bits;
     for (int shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(k_radix_hist, dim3(L.n_tiles), dim3(kRadixThreads), 0, s, qa, n_cells, shift, L.n_tiles, hist);
-        hipLaunchKernelGGL(k_radix_scan, dim3(1), dim3(1024), 0, s, hist, 256u * L.n_tiles);
-        hipLaunchKernelGGL(k_radix_scatter, dim3(L.n_tiles), dim3(kRadixThreads), 0, s, qa, ra, n_cells, shift, L.n_tiles, hist, qb, rb);
+        radix_sort_pass(qa, ra, n_cells, 1, shift, hist, qb, rb, s);
         std::swap(qa, qb);
         std::swap(ra, rb);
     }

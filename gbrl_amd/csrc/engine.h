@@ -128,7 +128,7 @@ struct CatItem { int feat; int next; uint64_t lhash; size_t std_hash; char name[
 }  // namespace detail
 
 // The options of Engine::fit_prepared; the defaults are the plain MultiRMSE loop on every row and column.
-struct FitOptions { double subsample = 1.0, colsample = 1.0; uint64_t seed = 0; int objective = 0 /* kern::kObjRmse */; };
+struct FitOptions { double subsample = 1.0, colsample = 1.0; uint64_t seed = 0; int objective = 0 /* kern::kObjRmse */; int metric = 0 /* kern::kMetricNone */; };
 
 class Engine {
    public:
@@ -195,18 +195,24 @@ class Engine {
     //              after EVERY iteration by one launch that also writes the loss partials.  rounds > 0: the loop ends after iteration k when k - best
     //              >= rounds (early_stop_scan's rule); rounds == 0: record only.  All trees grown stay: model and loss are what the call without
     //              valid gives for `done` iterations.  best_n_trees = T0 + best.
+    //   metric     (metric_core.h; kern::kMetricError / kMetricAuc, with valid)  metric_out[k] is eval_metric_host of the validation rows' held
+    //              prediction after k iterations, from integers counted on the device behind the loss launch (rounds == 0: they stay there
+    //              until the end, as the loss sums do).  The stopping rule and best_n_trees then follow the metric curve -- the error as it is,
+    //              the AUC negated -- in place of loss_out, which is recorded as ever.  It reads the held prediction only: the model is byte
+    //              for byte what the call without it leaves after `done` iterations.
     // Refused before anything changes, in this order: precheck_fit's list; ds, then valid->ds, absent or not this model's (check_prepared_dataset);
     // another thresholds id; null valid->loss_out; a tree whose conditions the codes cannot express (Unsupported); softmax: a label outside [0, D)
     // in either set (InvalidArgument naming the first one found).
     struct FitValid {
         const PreparedDataset *ds; const void *targets; bool targets_dev; int rounds; double min_delta;
         double *loss_out /*[iterations + 1]*/; int done, best_n_trees;
+        double *metric_out = nullptr /*[iterations + 1]; with FitOptions::metric*/;
     };
     float fit_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, const FitOptions &opt = {}, FitValid *valid = nullptr);
     // What fit_prepared refuses without a data set in hand, in this order (the C ABI runs it before it resolves the handles, so that these
     // refusals do not depend on a data set being at hand; valid->ds is not looked at): the model checks of step_prepared; null targets;
     // iterations < 0; batch_size <= 0; max_depth > 32, n_bins outside [1, 65534], output_dim > 128 (Unsupported); check_subsample;
-    // check_colsample; check_objective; with valid: null targets, rounds < 0, min_delta negative or NaN.
+    // check_colsample; check_objective; a metric without valid, check_metric; with valid: null targets, rounds < 0, min_delta negative or NaN.
     void precheck_fit(const void *targets, int iterations, const FitOptions &opt, const FitValid *valid) const;
     // Extension: row subsampling (stochastic gradient boosting).  The sampler is sample_core.h's pure function of (seed, draw, row): a row is
     // kept iff its 24-bit hash is below floor(subsample * 2^24); the sample of [row0, row0 + n) is the ascending list of its kept absolute indices.
@@ -231,6 +237,14 @@ class Engine {
     // device and stream with D = output_dim (kern::objective_rows: the device functions of the code walk's tails).  grad_out is where pred is
     // (device iff pred_dev); either output may be null, not both.  kObjRmse: g = fl32(p - y) and staged_loss's expression.
     void objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out);
+    // Extension: classifier metrics (metric_core.h has the definitions).  eval_metric: the error rate or the exact AUC of pred [n][D] against
+    // targets under the objective, on the model's device and stream: integer counts from kern::metric_error / kern::metric_auc, the value from
+    // them on the host.  counts (nullable): [D][3] = (2U_d, P_d, N_d) for auc, [D] (softmax: [1]) for error.  eval_metric_host: the same by
+    // std::sort on the host, no device.  Refused (InvalidArgument): an unknown metric, a metric with rmse, a label outside [0, D), a column
+    // without a positive or without a negative row (auc; the column is named); (Unsupported): auc with softmax, n * D >= 2^31 - 2048 (auc).
+    static void check_metric(const char *what, int objective, int metric);
+    void eval_metric(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, int metric, double *value, int64_t *counts);
+    static void eval_metric_host(const float *pred, const void *targets, int n, int D, int objective, int metric, double *value, int64_t *counts);
     // the gradient rule on the host (no device): the same bits
     static void objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out);
     // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
@@ -472,6 +486,7 @@ class Engine {
     DevBuf d_fp_vpred_, d_fp_vtargets_, d_fp_vpart_, d_fp_vsums_;   // its validation rows: held prediction [n_v][D], staged targets, loss partials, one sum per iteration
     DevBuf d_fp_srows_, d_fp_sgrads_, d_fp_sscratch_;   // its sampled iterations: the kept rows of the batch, their gradient rows, block counts + m
     DevBuf d_obj_pred_, d_obj_targets_, d_obj_grad_, d_obj_part_, d_obj_sum_, d_obj_counts_;   // objective_gradient: staged inputs, the gradient, loss partials and sum; class counts + first bad row
+    DevBuf d_met_counts_, d_met_scratch_, d_fp_vmetric_;   // eval_metric: the integer counters, the AUC pipeline's scratch; fit_prepared: the metric's counters per iteration
     struct Held;     // engine_fit_prepared.hip: a data set's rows carried through the model's trees, batch by batch
     struct FitRun;   // engine_fit_prepared.hip: the state of one fit_prepared call and the stages that work on it
     // class counts of device labels [n] (counts, when given: [D]); a label outside [0, D) is InvalidArgument naming the first such row

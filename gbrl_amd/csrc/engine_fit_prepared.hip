@@ -11,7 +11,9 @@
 //                                      the walk's loss tail, Engine::early_stop_scan's rule; every tree grown on a sample of its batch
 //                                      (sample_core.h: kern::sample_rows draws the rows and gathers their gradient rows in one pass, 4 bytes come
 //                                      back, step_prepared's body grows on the subset) and on a sample of the columns (the host rule of
-//                                      sample_core.h per iteration, step_prepared's cols path)
+//                                      sample_core.h per iteration, step_prepared's cols path); a classifier's metric of the validation rows
+//                                      per iteration, which then decides the stopping rule and best_n_trees in place of the loss
+//   Engine::eval_metric[_host]         the error rate and the exact AUC of a prediction matrix (metric_core.h), on the device and on the host
 //
 // The rule.  code(r, f) = #{b : thr[f][b] < obs[r, f]} (-0.0 == +0.0; NaN lies below every threshold: code 0).  For a condition x > v whose v
 // equals some thr[f][b] let bin = #{b : thr[f][b] < v}.  x > v: every threshold below v, and v itself, is below x, so code >= bin + 1.
@@ -19,6 +21,7 @@
 // It does not hold for a v that is not among the feature's thresholds: such a condition is refused (Unsupported), never approximated.
 #include "engine_step_detail.h"
 #include "objective_core.h"
+#include "metric_core.h"
 #include "sample_core.h"
 
 namespace gbrl {
@@ -284,6 +287,106 @@ void Engine::objective_gradient(const float *pred, bool pred_dev, const void *ta
     if (loss_out) *loss_out = mean_loss(objective, sum, n);
 }
 
+// ---- classifier metrics: the checks, the host rule, the device pipeline (kern::metric_error / kern::metric_auc) and the value from its integers
+void Engine::check_metric(const char *what, int objective, int metric) {
+    if (metric != kern::kMetricError && metric != kern::kMetricAuc)
+        throw InvalidArgument(std::string(what) + ": unknown metric " + std::to_string(metric) + " (error = 1, auc = 2)");
+    if (objective == kern::kObjRmse) throw InvalidArgument(std::string(what) + ": the rmse objective has no metric (error and auc are for logistic and softmax)");
+    if (metric == kern::kMetricAuc && objective == kern::kObjSoftmax)
+        throw Unsupported(std::string(what) + ": auc with the softmax objective (a multi-class AUC) is not supported");
+}
+
+namespace {
+// a column of one class has no AUC
+void check_auc_column(const char *what, int d, uint64_t P, uint64_t N) {
+    if (P == 0 || N == 0)
+        throw InvalidArgument(std::string(what) + ": column " + std::to_string(d) + " of the targets has no " + (P == 0 ? "positive" : "negative") +
+                              " row (a target above 0.5 is positive): its AUC is not defined");
+}
+void metric_counts_out(const std::vector<uint64_t> &c, int64_t *counts) {
+    if (counts) for (size_t i = 0; i < c.size(); ++i) counts[i] = static_cast<int64_t>(c[i]);
+}
+}  // namespace
+
+void Engine::eval_metric_host(const float *pred, const void *targets, int n, int D, int objective, int metric, double *value, int64_t *counts) {
+    if (pred == nullptr || targets == nullptr) throw InvalidArgument("eval_metric_host: null argument");
+    if (value == nullptr && counts == nullptr) throw InvalidArgument("eval_metric_host: no place for a result");
+    if (n <= 0) throw InvalidArgument("eval_metric_host: no rows (n must be positive)");
+    if (D < 1) throw InvalidArgument("eval_metric_host: output_dim must be positive");
+    check_objective("eval_metric_host", objective, D);
+    check_metric("eval_metric_host", objective, metric);
+    const bool softmax = objective == kern::kObjSoftmax;
+    const int C = kern::metric_count_columns(softmax, D);
+    std::vector<uint64_t> c(static_cast<size_t>(C) * kern::metric_count_width(metric), 0);
+    if (softmax) {
+        const int32_t *labels = static_cast<const int32_t *>(targets);
+        for (int r = 0; r < n; ++r) {
+            if (labels[r] < 0 || labels[r] >= D)
+                throw InvalidArgument("eval_metric_host: label " + std::to_string(labels[r]) + " (row " + std::to_string(r) + ") is outside [0, " + std::to_string(D) + ")");
+            c[0] += kern::metric_argmax(pred + static_cast<size_t>(r) * D, D) != labels[r] ? 1 : 0;
+        }
+    } else if (metric == kern::kMetricError) {
+        const float *y = static_cast<const float *>(targets);
+        for (int r = 0; r < n; ++r)
+            for (int d = 0; d < D; ++d) c[d] += kern::metric_logistic_wrong(pred[static_cast<size_t>(r) * D + d], y[static_cast<size_t>(r) * D + d]) ? 1 : 0;
+    } else {
+        const float *y = static_cast<const float *>(targets);
+        std::vector<uint32_t> pos, neg;
+        for (int d = 0; d < D; ++d) {
+            pos.clear(); neg.clear();
+            for (int r = 0; r < n; ++r) {
+                const size_t at = static_cast<size_t>(r) * D + d;
+                (kern::metric_positive(y[at]) ? pos : neg).push_back(kern::metric_key(pred[at]));
+            }
+            check_auc_column("eval_metric_host", d, pos.size(), neg.size());
+            std::sort(neg.begin(), neg.end());
+            uint64_t u2 = 0;
+            for (const uint32_t k : pos)
+                u2 += static_cast<uint64_t>(std::lower_bound(neg.begin(), neg.end(), k) - neg.begin()) +
+                      static_cast<uint64_t>(std::upper_bound(neg.begin(), neg.end(), k) - neg.begin());
+            c[3 * d] = u2; c[3 * d + 1] = pos.size(); c[3 * d + 2] = neg.size();
+        }
+    }
+    if (value) *value = kern::metric_value(metric, c.data(), C, static_cast<uint64_t>(n) * (softmax ? 1 : D));
+    metric_counts_out(c, counts);
+}
+
+void Engine::eval_metric(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, int metric, double *value, int64_t *counts) {
+    const int D = model.meta.output_dim;
+    if (pred == nullptr || targets == nullptr) throw InvalidArgument("eval_metric: null argument");
+    if (value == nullptr && counts == nullptr) throw InvalidArgument("eval_metric: no place for a result");
+    if (n <= 0) throw InvalidArgument("eval_metric: no rows (n must be positive)");
+    if (D > 128) throw Unsupported("eval_metric: output_dim > 128");
+    check_objective("eval_metric", objective, D);
+    check_metric("eval_metric", objective, metric);
+    const bool softmax = objective == kern::kObjSoftmax, auc = metric == kern::kMetricAuc;
+    if (auc && !kern::metric_auc_fits(n, D)) throw Unsupported("eval_metric: auc needs n * output_dim < 2^31 - 2048");
+    ensure_device();
+    hipStream_t s = stream_;
+    const size_t n_el = static_cast<size_t>(n) * D, tar_el = softmax ? static_cast<size_t>(n) : n_el;
+    const float *dp = pred_dev ? pred : upload(d_obj_pred_, pred, n_el, "H2D predictions");
+    const float *dt = targets_dev ? static_cast<const float *>(targets) : upload(d_obj_targets_, static_cast<const float *>(targets), tar_el, "H2D targets");
+    if (softmax) check_labels("eval_metric", reinterpret_cast<const int32_t *>(dt), n, D, nullptr);
+    const int C = kern::metric_count_columns(softmax, D);
+    std::vector<unsigned long long> h(static_cast<size_t>(C) * 2, 0);   // the counters, and behind them the positives per column (auc)
+    unsigned long long *dc = static_cast<unsigned long long *>(d_met_counts_.ensure(sizeof(unsigned long long) * h.size()));
+    hip_check(hipMemsetAsync(dc, 0, sizeof(unsigned long long) * h.size(), s), "zero metric counters");
+    if (auc) kern::metric_auc(dp, dt, n, D, d_met_scratch_.ensure(kern::metric_auc_scratch_bytes(n, D)), dc + C, dc, s);
+    else kern::metric_error(objective, dp, dt, n, D, dc, s);
+    hip_check(hipGetLastError(), "eval_metric kernels");
+    hip_check(hipMemcpyAsync(h.data(), dc, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, s), "D2H metric counters");
+    hip_check(hipStreamSynchronize(s), "sync");
+    std::vector<uint64_t> c(static_cast<size_t>(C) * kern::metric_count_width(metric), 0);
+    for (int d = 0; d < C; ++d) {
+        if (!auc) { c[d] = h[d]; continue; }
+        const uint64_t P = h[C + d], N = static_cast<uint64_t>(n) - P;
+        check_auc_column("eval_metric", d, P, N);
+        c[3 * d] = h[d]; c[3 * d + 1] = P; c[3 * d + 2] = N;
+    }
+    if (value) *value = kern::metric_value(metric, c.data(), C, static_cast<uint64_t>(n) * (softmax ? 1 : D));
+    metric_counts_out(c, counts);
+}
+
 // ---- the fit: the stopping rule, the refusals that need no data set, a held prediction, and the stages of Engine::fit_prepared in its order
 void Engine::early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best) {
     if (curve == nullptr || stop_after == nullptr || best == nullptr) throw InvalidArgument("early_stop_scan: null argument");
@@ -311,6 +414,10 @@ void Engine::precheck_fit(const void *targets, int iterations, const FitOptions 
     check_subsample("fit_prepared", opt.subsample);
     check_colsample("fit_prepared", opt.colsample);
     check_objective("fit_prepared", opt.objective, md.output_dim);
+    if (opt.metric != kern::kMetricNone) {
+        if (valid == nullptr) throw InvalidArgument("fit_prepared: eval_metric needs a validation set (valid=)");
+        check_metric("fit_prepared", opt.objective, opt.metric);
+    }
     if (valid == nullptr) return;
     if (valid->targets == nullptr) throw InvalidArgument("fit_prepared: a validation set needs valid_targets");
     if (valid->rounds < 0) throw InvalidArgument("fit_prepared: early_stopping_rounds must be >= 0");
@@ -360,13 +467,22 @@ struct Engine::FitRun {
     float *G = nullptr;                              // [n][D]: the gradient of the current batch from row 0, of every row for the final loss
     const int32_t *d_iota = nullptr;                 // 0 .. n - 1: the row ranges step_prepared's body gathers (bs < n)
     double *d_vpart = nullptr, *d_vsums = nullptr;   // the validation rows' loss partials, one sum per iteration from k = 0
+    // a metric of the validation rows: mC integer counters per iteration from k = 0 (wrong cells per column, or 2U per column), the positives of
+    // every validation column (auc), one iteration's counters on the host (a stopping rule reads them back), and the curve the rule sees
+    const int mC;
+    unsigned long long *d_vmetric = nullptr;
+    void *d_mscratch = nullptr;
+    std::vector<uint64_t> vpos;
+    std::vector<unsigned long long> h_mrow;
+    std::vector<double> score;
     bool sampled = false, colsampled = false;
     int32_t *d_srows = nullptr, *d_sscratch = nullptr;   // a sampled iteration: the kept rows of the batch, the sampler's block counts + m
     float *Gs = nullptr;                                  // and their gradient rows
     int start = 0, bn = 0;                               // the batch cursor
 
     FitRun(Engine &eng, const PreparedDataset *data, int iters, const FitOptions &o, FitValid *valid)
-        : e(eng), ds(data), opt(o), v(valid), iterations(iters), n(data->n), D(eng.model.meta.output_dim), bs(eng.model.meta.batch_size), T0(eng.model.meta.n_trees) {
+        : e(eng), ds(data), opt(o), v(valid), iterations(iters), n(data->n), D(eng.model.meta.output_dim), bs(eng.model.meta.batch_size), T0(eng.model.meta.n_trees),
+          mC(kern::metric_count_columns(o.objective == kern::kObjSoftmax, eng.model.meta.output_dim)) {
         bn = start + bs < n ? bs : n - start;                                       // fitter.cpp:120
     }
 
@@ -378,9 +494,23 @@ struct Engine::FitRun {
     void stage_targets(const void *targets, bool targets_dev) {
         dtar = stage(e.d_fp_targets_, targets, targets_dev, n);
         if (v) dvtar = stage(e.d_fp_vtargets_, v->targets, v->targets_dev, v->ds->n);
+        if (opt.metric == kern::kMetricAuc) count_positives();
         if (opt.objective != kern::kObjSoftmax) return;
         e.check_labels("fit_prepared", reinterpret_cast<const int32_t *>(dtar), n, D, &class_counts);
         if (v) e.check_labels("fit_prepared (valid_targets)", reinterpret_cast<const int32_t *>(dvtar), v->ds->n, D, nullptr);
+    }
+    // auc: the positives of every validation column; a column of one class is refused before anything changes
+    void count_positives() {
+        hipStream_t s = e.stream_;
+        const int nv = v->ds->n;
+        std::vector<unsigned long long> h(D, 0);
+        unsigned long long *dc = static_cast<unsigned long long *>(e.d_met_counts_.ensure(sizeof(unsigned long long) * h.size()));
+        hip_check(hipMemsetAsync(dc, 0, sizeof(unsigned long long) * h.size(), s), "zero metric counters");
+        kern::metric_positives(dvtar, nv, D, dc, s);
+        hip_check(hipMemcpyAsync(h.data(), dc, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost, s), "D2H positives");
+        hip_check(hipStreamSynchronize(s), "sync");
+        vpos.assign(h.begin(), h.end());
+        for (int d = 0; d < D; ++d) check_auc_column("fit_prepared (valid_targets)", d, vpos[d], static_cast<uint64_t>(nv) - vpos[d]);
     }
     // A fresh model's bias by objective, and the feature counts as step_prepared latches them.
     void set_bias(ColumnStats &stats) {
@@ -423,23 +553,55 @@ struct Engine::FitRun {
         d_vsums = static_cast<double *>(e.d_fp_vsums_.ensure(sizeof(double) * (static_cast<size_t>(iterations) + 1)));
         kern::tile_rows(e.m_bias_.as<float>(), D, nv, watched.P, s);
         v->best_n_trees = T0;
+        if (opt.metric == kern::kMetricNone) return;
+        const size_t words = (static_cast<size_t>(iterations) + 1) * mC;
+        d_vmetric = static_cast<unsigned long long *>(e.d_fp_vmetric_.ensure(sizeof(unsigned long long) * words));
+        hip_check(hipMemsetAsync(d_vmetric, 0, sizeof(unsigned long long) * words, s), "zero metric counters");
+        if (opt.metric == kern::kMetricAuc) d_mscratch = e.d_met_scratch_.ensure(kern::metric_auc_scratch_bytes(nv, D));
+        h_mrow.assign(mC, 0);
+        score.assign(static_cast<size_t>(iterations) + 1, 0.0);
     }
     // ---- the validation watch
-    // loss_out[k] after k iterations: one launch + the finishing sum on the device; with a stopping rule also on the host (one 8-byte read-back)
+    // loss_out[k] after k iterations: one launch + the finishing sum on the device, then the metric's integers of the same held prediction; with
+    // a stopping rule both also on the host (one read-back: 8 bytes and the metric's counters, one wait)
     void evaluate(int k) {
         const int nv = v->ds->n;
         v->done = k;
         e.advance_held(watched, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, opt.objective);
         double sum = 0.0;
         e.finish_loss_sum(d_vpart, kern::staged_loss_partials(nv), d_vsums + k, v->rounds > 0 ? &sum : nullptr);
+        if (opt.metric != kern::kMetricNone) measure(k);
         if (v->rounds > 0) {
             hip_check(hipStreamSynchronize(e.stream_), "sync");
             v->loss_out[k] = mean_loss(opt.objective, sum, nv);
+            if (opt.metric != kern::kMetricNone) record_metric(k, h_mrow.data());
         }
+    }
+    // the metric of the watched prediction into the counters of entry k; it reads the prediction and never writes it
+    void measure(int k) {
+        hipStream_t s = e.stream_;
+        const int nv = v->ds->n;
+        unsigned long long *row = d_vmetric + static_cast<size_t>(k) * mC;
+        if (opt.metric == kern::kMetricAuc) kern::metric_auc(watched.P, dvtar, nv, D, d_mscratch, nullptr, row, s);
+        else kern::metric_error(opt.objective, watched.P, dvtar, nv, D, row, s);
+        if (v->rounds > 0) hip_check(hipMemcpyAsync(h_mrow.data(), row, sizeof(unsigned long long) * mC, hipMemcpyDeviceToHost, s), "D2H metric counters");
+    }
+    // metric_out[k] from entry k's integers, and what the stopping rule sees of it: the error as it is, the AUC negated (exact)
+    void record_metric(int k, const unsigned long long *row) {
+        const int nv = v->ds->n;
+        const bool auc = opt.metric == kern::kMetricAuc;
+        std::vector<uint64_t> c(static_cast<size_t>(mC) * kern::metric_count_width(opt.metric));
+        for (int d = 0; d < mC; ++d) {
+            if (!auc) { c[d] = row[d]; continue; }
+            c[3 * d] = row[d]; c[3 * d + 1] = vpos[d]; c[3 * d + 2] = static_cast<uint64_t>(nv) - vpos[d];
+        }
+        const double value = kern::metric_value(opt.metric, c.data(), mC, static_cast<uint64_t>(nv) * (opt.objective == kern::kObjSoftmax ? 1 : D));
+        v->metric_out[k] = value;
+        score[k] = auc ? -value : value;
     }
     int best_of_curve() const {
         int stop_after = 0, best = 0;
-        early_stop_scan(v->loss_out, v->done + 1, v->rounds, v->min_delta, &stop_after, &best);
+        early_stop_scan(opt.metric != kern::kMetricNone ? score.data() : v->loss_out, v->done + 1, v->rounds, v->min_delta, &stop_after, &best);
         return best;
     }
     bool stops_early() const { return v->rounds > 0 && v->done - best_of_curve() >= v->rounds; }
@@ -449,6 +611,12 @@ struct Engine::FitRun {
             hip_check(hipMemcpyAsync(sums.data(), d_vsums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, e.stream_), "D2H validation losses");
             hip_check(hipStreamSynchronize(e.stream_), "sync");
             for (int k = 0; k <= v->done; ++k) v->loss_out[k] = mean_loss(opt.objective, sums[k], v->ds->n);
+            if (opt.metric != kern::kMetricNone) {   // and so did the metric's integers
+                std::vector<unsigned long long> rows((static_cast<size_t>(v->done) + 1) * mC);
+                hip_check(hipMemcpyAsync(rows.data(), d_vmetric, sizeof(unsigned long long) * rows.size(), hipMemcpyDeviceToHost, e.stream_), "D2H validation metric");
+                hip_check(hipStreamSynchronize(e.stream_), "sync");
+                for (int k = 0; k <= v->done; ++k) record_metric(k, rows.data() + static_cast<size_t>(k) * mC);
+            }
         }
         v->best_n_trees = T0 + best_of_curve();
     }
@@ -522,6 +690,9 @@ float Engine::fit_prepared(const PreparedDataset *ds, const void *targets, bool 
         if (valid->ds->thresholds_id != ds->thresholds_id)
             throw InvalidArgument("fit_prepared: the validation set does not share the training set's thresholds (create it with prepare_dataset(obs, reference=ds))");
         if (valid->loss_out == nullptr) throw InvalidArgument("fit_prepared: no place for the validation losses");
+        if (opt.metric != kern::kMetricNone && valid->metric_out == nullptr) throw InvalidArgument("fit_prepared: no place for the validation metric");
+        if (opt.metric == kern::kMetricAuc && !kern::metric_auc_fits(valid->ds->n, model.meta.output_dim))
+            throw Unsupported("fit_prepared: auc needs validation rows * output_dim < 2^31 - 2048");
     }
     const bool fresh = model.meta.n_trees == 0;
     if (!fresh) check_code_range(*ds, "fit_prepared", 0, model.meta.n_trees);   // a warm start continues from every tree the model has

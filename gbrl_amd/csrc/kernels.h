@@ -579,6 +579,24 @@ void cat_rank(const char *cells, int N, int Fc, const float *grads, int D, const
 // diagnostics: host arrays in, (feature, first row, count, total) of every distinct pair out; returns their number, -2: more than cap, -1: failed
 int cat_rank_selftest(const char *cells, int n, int Fc, const float *grads, int D, int cap, int32_t *feat, int32_t *first_row, int32_t *count,
                       float *total);
+// radix_sort.hip: one pass (8 bits at `shift`) of a stable LSD radix sort of (key, value) pairs over `segments` arrays of n elements each,
+// laid out [segments][n]: every segment is sorted on its own, from (key, val) into (key_out, val_out).  hist is scratch for
+// segments * 256 * radix_sort_tiles(n) words.  Three launches on s; segments * n < 2^31 - kRadixSortTile, segments <= 65535.
+constexpr int kRadixSortTile = 2048;   // elements one block owns: 256 threads x 8 rounds
+uint32_t radix_sort_tiles(size_t n);
+void radix_sort_pass(const uint32_t *key, const uint32_t *val, uint32_t n, int segments, int shift, uint32_t *hist, uint32_t *key_out, uint32_t *val_out,
+                     hipStream_t s);
+// metric.hip: the integers of the classifier metrics (metric_core.h) of a prediction matrix P [n][D] (device), added to counters the caller
+// has ZEROED on s.  D <= 128.
+//   metric_error      wrong [D] (softmax: [1]; T is then int32 [n], every label in [0, D)) += wrong cells per column
+//   metric_positives  pos [D] += rows with Y[r][d] > 0.5
+//   metric_auc        u2 [D] += 2U_d; pos (nullable) as metric_positives.  metric_auc_fits: n * D < 2^31 - kRadixSortTile.  scratch holds
+//                     metric_auc_scratch_bytes(n, D): 16 n D bytes of key / flag ping-pong, the sort's histograms, n + 1 prefix words per column
+void metric_error(int objective, const float *P, const void *T, int n, int D, unsigned long long *wrong, hipStream_t s);
+bool metric_auc_fits(int n, int D);
+size_t metric_auc_scratch_bytes(int n, int D);
+void metric_positives(const float *Y, int n, int D, unsigned long long *pos, hipStream_t s);
+void metric_auc(const float *P, const float *Y, int n, int D, void *scratch, unsigned long long *pos, unsigned long long *u2, hipStream_t s);
 // class codes of a step batch from the scan's own tables: cls_of_q[slot_q[slot of the cell]] (see k_cat_step_codes_table)
 void cat_step_codes_table(const char *cells, int n, int Fc, int F, const uint64_t *keys, const int32_t *slot_q, const int32_t *cls_of_q,
                           int log2_cap, uint16_t *codes, hipStream_t s);

@@ -496,6 +496,47 @@ int gbrl_hip_objective_gradient(gbrl_hip_model *m, const float *pred, int pred_o
                                 float *grad_out /*[n, output_dim]*/, double *loss_out);
 int gbrl_hip_objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out /*[n, D]*/);
 int gbrl_hip_objective_exp_host(const float *t, int n, double *out /*[n] or NULL*/, float *out_f32 /*[n] or NULL*/);
+/* Classifier metrics (new: what a fitted classifier is watched and stopped on, beyond its mean log loss).  Both are INTEGERS before they are
+ * numbers (csrc/metric_core.h, shared by the host rule and the kernels): the counts of the device, of the host rule and of a brute force are
+ * equal or wrong -- there is no tolerance -- and every floating-point step is taken on the host from the integers: the same bits.
+ *   GBRL_HIP_METRIC_ERROR, GBRL_HIP_OBJ_SOFTMAX: row r is wrong iff argmax_c p[r][c] != label[r], the arg-max being the lowest index among
+ *     equal maxima, compared as floats.  E = wrong rows; value = (double)E / n.  counts [1] = E.
+ *   GBRL_HIP_METRIC_ERROR, GBRL_HIP_OBJ_LOGISTIC: cell (r, d) is wrong iff (p[r][d] > 0) != (y[r][d] > 0.5) -- a score of exactly 0 predicts
+ *     the negative class, a target of exactly 0.5 is negative.  E_d = wrong cells of column d; value = (double)(sum_d E_d) / (n D).
+ *     counts [D] = E_d.
+ *   GBRL_HIP_METRIC_AUC, GBRL_HIP_OBJ_LOGISTIC, per output column d: positives are the rows with y[r][d] > 0.5 (P_d of them), the other
+ *     N_d rows are negatives.  Scores compare through one order-preserving key: -0.0 is first made +0.0; then u = bits(p) and
+ *     key = u ^ (u >> 31 ? 0xffffffff : 0x80000000).  A NaN is therefore ordered by its bits: defined, and meaningless.
+ *     2U_d = sum over positives i of (#{negatives j : key_j < key_i} + #{negatives j : key_j <= key_i}), a uint64 (ties count half);
+ *     AUC_d = (double)(2U_d) / (2.0 * (double)P_d * (double)N_d); value = (sum_d AUC_d, d ascending, in double) / D.
+ *     counts [D][3] = (2U_d, P_d, N_d).  On the device: the D score columns are sorted by key in four passes of a segmented radix sort,
+ *     the negatives are prefix-counted along every sorted column, and every positive adds the prefix at the two ends of its run of equal
+ *     keys; integer atomics only.
+ *   Refused, GBRL_HIP_E_INVALID: an unknown metric; a metric with GBRL_HIP_OBJ_RMSE; a column with P_d == 0 or N_d == 0 (auc: the message names
+ *     the column); a label outside [0, D).  GBRL_HIP_E_UNSUPPORTED: auc with softmax (a multi-class AUC is a separate decision); auc on
+ *     n * D >= 2^31 - 2048 cells; output_dim > 128.
+ *   Out of scope: multi-class AUC, metrics for rmse (MAE and the like), a model truncated at best_n_trees, row-sharded models.
+ *   gbrl_hip_eval_metric(m, pred, pred_on_device, targets, targets_on_device, n, objective, metric, value_out, counts_out)  the metric of a
+ *     prediction matrix [n, output_dim] (targets as for the objective) on the model's device and stream.  value_out and counts_out (host)
+ *     may each be NULL, not both.
+ *   gbrl_hip_eval_metric_host(pred, targets, n, D, objective, metric, value_out, counts_out)  the definition itself, by std::sort on the
+ *     host: no device.  It shares the key and the final division with the device path and nothing else.
+ *   gbrl_hip_fit_prepared_metric(.., objective, metric, loss_out, valid_loss_out, valid_metric_out, ..)  gbrl_hip_fit_prepared_objective plus
+ *     the metric; the older calls are this one with GBRL_HIP_METRIC_NONE.  With a metric, valid_metric_out[k], k = 0 .. *iterations_done, is
+ *     gbrl_hip_eval_metric_host of the validation rows' prediction after k iterations, and the stopping rule and *best_n_trees follow that
+ *     curve in place of the loss curve: the error as it is, the AUC negated.  valid_loss_out is recorded as ever.  The metric only reads the
+ *     held validation prediction: the model is byte for byte what the call without it leaves after the same number of iterations.
+ *     Refused before anything changes: a metric without a validation set, the refusals above (a single-class column of valid_targets
+ *     included), a NULL valid_metric_out with a metric. */
+enum { GBRL_HIP_METRIC_NONE = 0, GBRL_HIP_METRIC_ERROR = 1, GBRL_HIP_METRIC_AUC = 2 };
+int gbrl_hip_fit_prepared_metric(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                                 const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                 double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, float *loss_out,
+                                 double *valid_loss_out /*[iterations + 1]*/, double *valid_metric_out /*[iterations + 1]*/, int *iterations_done,
+                                 int *best_n_trees);
+int gbrl_hip_eval_metric(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective,
+                         int metric, double *value_out, int64_t *counts_out);
+int gbrl_hip_eval_metric_host(const float *pred, const void *targets, int n, int D, int objective, int metric, double *value_out, int64_t *counts_out);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
