@@ -150,6 +150,10 @@ int parse_objective(const std::string &s) {
 int parse_metric(const std::string &s) {
     return parse_enum(s, {{"error", GBRL_HIP_METRIC_ERROR}, {"auc", GBRL_HIP_METRIC_AUC}}, "Invalid metric! Options are: error/auc");
 }
+// leaf rule names of fit_prepared(leaf_update=) (GBRL_HIP_LEAF_*, include/gbrl_hip.h)
+int parse_leaf_update(const std::string &s) {
+    return parse_enum(s, {{"gradient", GBRL_HIP_LEAF_GRADIENT}, {"newton", GBRL_HIP_LEAF_NEWTON}}, "Invalid leaf_update! Options are: gradient/newton");
+}
 const char *parity_mode_name(int mode) {
     return mode == GBRL_HIP_PARITY_REFERENCE ? "reference" : (mode == GBRL_HIP_PARITY_EXACT_ARGMAX ? "exact_argmax" : "default");
 }
@@ -818,14 +822,14 @@ Input read_objective_targets(py::object &targets, const char *name, bool none_al
 }
 
 // fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,
-// objective='rmse', eval_metric=None): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
+// objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
 // with either.  A missing valid_targets is left to the C ABI's message.
 py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
                              int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name,
-                             py::object metric_obj) {
+                             py::object metric_obj, const std::string &leaf_update_name = "gradient", double leaf_l2 = 1.0) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
-    const int objective = parse_objective(objective_name);
+    const int objective = parse_objective(objective_name), leaf_update = parse_leaf_update(leaf_update_name);
     const int metric = metric_obj.is_none() ? GBRL_HIP_METRIC_NONE : parse_metric(metric_obj.cast<std::string>());
     if (valid_obj.is_none() && (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0))
         fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
@@ -838,9 +842,9 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_metric(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
-                                          colsample, seed, objective, metric, &loss, dsv ? curve.data() : nullptr, dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr,
-                                          &done, &best);
+        rc = gbrl_hip_fit_prepared_leaf(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                        colsample, seed, objective, metric, leaf_update, leaf_l2, &loss, dsv ? curve.data() : nullptr,
+                                        dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best);
     }
     check(rc);
     if (!dsv) return py::float_(loss);
@@ -858,6 +862,76 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
         out["eval_metric"] = metric_obj;
     }
     return std::move(out);
+}
+
+// Extension: Newton leaf values (include/gbrl_hip.h, "Newton leaf values").
+// newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1) -> {'sums': int64 [leaves, 2 D + 1], 'bits', 'values': float32 [leaves, D]}
+py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &pred, py::object &targets, const std::string &objective_name, double leaf_l2,
+                                     py::object &rows, int tree) {
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const int objective = parse_objective(objective_name), D = md.output_dim;
+    Input p = read_input(pred, "pred", false, "newton_leaves_prepared", false);
+    if (!p.ptr) fail("Cannot call newton_leaves_prepared without pred!");
+    Input r = read_rows(rows, "newton_leaves_prepared");
+    int m = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
+    if (!rows.is_none()) m = static_cast<int>(r.shape[0]);
+    else if (ds) m = ds_obj.cast<const PyDataset &>().info().n_rows;
+    check_rows_by_outputs(p, "pred", m, D);
+    Input t = read_objective_targets(targets, "targets", false, "newton_leaves_prepared", objective, m, D, true);
+    if (!t.ptr) fail("Cannot call newton_leaves_prepared without targets!");
+    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
+    const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
+    // the leaves of the tree (an index outside the model is left to the C ABI's message: one leaf's room is enough for a call that is refused)
+    const py::ssize_t T = md.n_trees;
+    py::ssize_t leaves = 1;
+    if (tree >= -1 && tree < T && T > 0) {
+        std::vector<int32_t> ti(static_cast<size_t>(T));
+        const py::ssize_t tt = tree == -1 ? T - 1 : tree;
+        check(gbrl_hip_get_ensemble(self.h, ti.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        leaves = (tt + 1 < T ? ti[tt + 1] : md.n_leaves) - ti[tt];
+    }
+    py::array_t<int64_t> sums({leaves, static_cast<py::ssize_t>(2 * D + 1)});
+    py::array_t<float> values({leaves, static_cast<py::ssize_t>(D)});
+    int bits = 0, rc;
+    int64_t *sp = sums.mutable_data();
+    float *vp = values.mutable_data();
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_newton_leaves_prepared(self.h, ds, rp, r.ptr ? r.on_device : 0, m, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, objective,
+                                             tree, leaf_l2, sp, &bits, vp);
+    }
+    check(rc);
+    py::dict out;
+    out["sums"] = sums;
+    out["bits"] = py::int_(bits);
+    out["values"] = values;
+    return out;
+}
+
+// the hessian rule on the host: no device, no model (the targets do not enter: accepted and ignored, so that the call reads like the gradient's)
+py::array_t<float> objective_hessian_host_impl(py::object &pred, py::object targets, const std::string &objective_name) {
+    const int objective = parse_objective(objective_name);
+    Input p = read_input(pred, "pred", false, "objective_hessian_host", false);
+    if (p.on_device) fail("objective_hessian_host takes NumPy arrays");
+    if (p.shape.empty() || p.shape.size() > 2) fail("pred must be a float32 array of shape (n, D) or (n,)");
+    const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
+    py::array_t<float> out(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
+    float none = 0.0f;
+    check(gbrl_hip_objective_hessian_host(static_cast<const float *>(p.ptr), n, D, objective, out.size() ? out.mutable_data() : &none));
+    return out;
+}
+
+// the value rule on the host: sums int64 [leaves, 2 D + 1], old_values float32 [leaves, D], depths int32 [leaves] -> float32 [leaves, D]
+py::array_t<float> newton_values_host_impl(py::array_t<int64_t, py::array::c_style | py::array::forcecast> sums, int bits,
+                                           py::array_t<float, py::array::c_style | py::array::forcecast> old_values,
+                                           py::array_t<int32_t, py::array::c_style | py::array::forcecast> depths, double leaf_l2) {
+    if (old_values.ndim() != 2 || sums.ndim() != 2 || depths.ndim() != 1) fail("newton_values_host: sums [leaves, 2 D + 1], old_values [leaves, D], depths [leaves]");
+    const py::ssize_t L = old_values.shape(0), D = old_values.shape(1);
+    if (sums.shape(0) != L || sums.shape(1) != 2 * D + 1 || depths.shape(0) != L) fail("newton_values_host: sums [leaves, 2 D + 1], old_values [leaves, D], depths [leaves]");
+    py::array_t<float> out({L, D});
+    check(gbrl_hip_newton_values_host(sums.data(), static_cast<int>(L), static_cast<int>(D), bits, old_values.data(), depths.data(), leaf_l2, out.mutable_data()));
+    return out;
 }
 
 // the counts of a metric as int64: [D, 3] = (2U_d, P_d, N_d) for auc, [D] (softmax: [1]) for error
@@ -1149,6 +1223,17 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "The gradient rule of fit_prepared(objective=) on the host (no device is needed): 'logistic': sigmoid(p) - y, targets float32 like pred;\n"
           "'softmax': softmax(p) - onehot(y), targets int32 [n] labels in [0, D), D >= 2; 'rmse': p - y.  Every float32 step is the one definition the\n"
           "kernels use (an exponential written out in fmaf, correctly rounded division): the device gives the same bits.");
+    m.def("objective_hessian_host", &objective_hessian_host_impl, py::arg("pred"), py::arg("targets") = py::none(), py::arg("objective") = "logistic",
+          "objective_hessian_host(pred, targets, objective) -> float32 NumPy array shaped like pred\n\n"
+          "The hessian rule of fit_prepared(leaf_update='newton') on the host (no device is needed): 'logistic': fl32(fl32(1 / (1 + e)) * fl32(e / (1 + e))),\n"
+          "e = exp(-|p|) as the gradient computes it; 'softmax': q (1 - q) per class, q as the gradient computes it (the diagonal); 'rmse': 1.  The targets\n"
+          "do not enter (None is fine).");
+    m.def("newton_values_host", &newton_values_host_impl, py::arg("sums"), py::arg("bits"), py::arg("old_values"), py::arg("depths"), py::arg("leaf_l2") = 1.0,
+          "newton_values_host(sums, bits, old_values, depths, leaf_l2=1.0) -> float32 [leaves, D]\n\n"
+          "The leaf value rule of newton_leaves_prepared on the host: v = (float)((Sg / 2**bits) / (Sh / 2**bits + leaf_l2)) in float64; a leaf with cnt == 0,\n"
+          "depth 0 or a denominator that is not positive keeps old_values.  sums int64 [leaves, 2 D + 1] = (Sg, Sh, cnt).");
+    m.def("newton_sum_bits", [](int64_t rows) { return gbrl_hip_newton_sum_bits(rows); }, py::arg("m"),
+          "newton_sum_bits(m) -> min(40, 62 - bit_length(m)): the bits of the quantum newton_leaves_prepared sums m rows in.");
     m.def("eval_metric_host", &eval_metric_host_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("metric"),
           "eval_metric_host(pred, targets, objective, metric) -> (value, counts)\n\n"
           "The classifier metrics of fit_prepared(eval_metric=) on the host (no device is needed), as include/gbrl_hip.h defines them.  metric 'error':\n"
@@ -1251,12 +1336,12 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         // likewise: fit_prepared(ds, targets, iterations) -> float keeps its generated line; the validation form is the second overload
         g.def("fit_prepared", [](PyGBRL &self, py::object ds, py::object &targets, int iterations) -> float {
             py::object none = py::none();
-            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none).cast<float>();
+            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0).cast<float>();
         }, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
             "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,\n"
-            "             objective='rmse', eval_metric=None) -> float | dict\n\n"
+            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0) -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
             "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
@@ -1294,13 +1379,31 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "the AUC negated), 'valid_loss' is recorded as ever, and the model is byte for byte what the call without the keyword leaves after the same\n"
             "number of iterations.  'error': the share of wrong arg-max rows (softmax) or of cells with (p > 0) != (y > 0.5) (logistic); 'auc' (logistic):\n"
             "the mean over the columns of the exact AUC, ties counted half.  Refused before anything changes: eval_metric without valid=, an unknown\n"
-            "name, a metric with 'rmse', 'auc' with 'softmax', a column of valid_targets with one class.";
+            "name, a metric with 'rmse', 'auc' with 'softmax', a column of valid_targets with one class.\n"
+            "leaf_update='newton' (with 'logistic' or 'softmax' and everything above), leaf_l2 >= 0: the tree is grown on the gradient as ever, then every leaf\n"
+            "stores sum g / (sum h + leaf_l2) over the rows the tree was grown on in place of the mean of g -- h = s (1 - s), or q (1 - q) per class -- the\n"
+            "step scikit-learn, XGBoost and LightGBM take.  The sums are exact integers taken on the device over the bin codes (newton_leaves_prepared's\n"
+            "kernel, one launch and one read-back per tree), the division is done on the host in float64: the model is byte for byte the loop\n"
+            "objective_gradient -> step_prepared -> newton_leaves_prepared -> predict_continue_prepared.  'gradient' is the call without the keyword.\n"
+            "Refused before anything changes: an unknown leaf_update, 'newton' with 'rmse', a leaf_l2 that is negative, NaN or infinite, and with\n"
+            "'newton' and 'logistic' a target outside [0, 1].";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
-              py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse", py::arg("eval_metric") = py::none());
+              py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse", py::arg("eval_metric") = py::none(),
+              py::arg("leaf_update") = "gradient", py::arg("leaf_l2") = 1.0);
     }
+    g.def("newton_leaves_prepared", &newton_leaves_prepared_impl, py::arg("ds"), py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("leaf_l2") = 1.0,
+          py::arg("rows") = py::none(), py::arg("tree") = -1,
+          "newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1) -> dict\n\n"
+          "The leaves of ONE tree (tree=-1: the last) set to sum g / (sum h + leaf_l2) over the data set rows `rows` (None: every row): what\n"
+          "fit_prepared(leaf_update='newton') does after every step.  pred [m, output_dim] is the prediction over the trees before that tree and, like\n"
+          "targets (float32 [m, output_dim]; int32 [m] labels for 'softmax'), is indexed by position.  Returns 'sums' (int64 [leaves, 2 D + 1]: Sg, Sh, cnt\n"
+          "per leaf, with q(x) = llrint(x * 2**bits)), 'bits' and 'values' (float32 [leaves, D], what the model now holds:\n"
+          "gbrl_cpp.newton_values_host(sums, bits, old values, depths, leaf_l2)).  Integer sums: two calls, and both kernel families, give the same bytes.\n"
+          "A leaf without rows, of depth 0 or with sum h + leaf_l2 <= 0 keeps its value.  Refused with the model unchanged: 'rmse', a bad leaf_l2, a tree\n"
+          "outside the model, a logistic target outside [0, 1], a prediction that is not finite.");
     g.def("eval_metric", &eval_metric_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("metric"),
           "eval_metric(pred, targets, objective, metric) -> (value, counts)\n\n"
           "gbrl_cpp.eval_metric_host(pred, targets, objective, metric) computed on the model's device: the same integers (counts, int64) and therefore the\n"

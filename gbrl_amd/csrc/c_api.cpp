@@ -18,6 +18,7 @@
 #include "engine.h"
 #include "objective_core.h"
 #include "metric_core.h"
+#include "newton_core.h"
 #include "hooks.h"
 #include "explain.h"
 #include "rccl_dyn.h"
@@ -678,6 +679,39 @@ int gbrl_hip_fit_prepared_metric(gbrl_hip_model *m, const gbrl_hip_dataset *ds, 
     return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
                              {subsample, colsample, seed, objective, metric}, loss_out, valid_loss_out, iterations_done, best_n_trees, valid_metric_out);
 }
+
+// ---- Newton leaf values: fit_prepared with them, one tree's leaves on a data set, the hessian and the value rule on the host
+static_assert(gbrl::kern::kLeafGradient == GBRL_HIP_LEAF_GRADIENT && gbrl::kern::kLeafNewton == GBRL_HIP_LEAF_NEWTON, "the kernels' leaf updates are the header's");
+int gbrl_hip_fit_prepared_leaf(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                               const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                               double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update, double leaf_l2,
+                               float *loss_out, double *valid_loss_out, double *valid_metric_out, int *iterations_done, int *best_n_trees) {
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, colsample, seed, objective, metric, leaf_update, leaf_l2}, loss_out, valid_loss_out, iterations_done, best_n_trees,
+                             valid_metric_out);
+}
+
+int gbrl_hip_newton_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,
+                                    int pred_on_device, const void *targets, int targets_on_device, int objective, int tree, double leaf_l2, int64_t *sums_out,
+                                    int *bits_out, float *values_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("newton_leaves_prepared");
+        m->engine.newton_leaves_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, pred, pred_on_device != 0, targets, targets_on_device != 0, objective,
+                                         tree, leaf_l2, sums_out, bits_out, values_out);
+    });
+}
+
+int gbrl_hip_objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out) {
+    return guarded([&] { gbrl::Engine::objective_hessian_host(pred, n, D, objective, hess_out); });
+}
+
+int gbrl_hip_newton_values_host(const int64_t *sums, int n_leaves, int D, int bits, const float *old_values, const int32_t *depths, double leaf_l2,
+                                float *values_out) {
+    return guarded([&] { gbrl::Engine::newton_values_host(sums, n_leaves, D, bits, old_values, depths, leaf_l2, values_out); });
+}
+
+int gbrl_hip_newton_sum_bits(int64_t m) { return gbrl::kern::newton_sum_bits(static_cast<long long>(m)); }
 
 int gbrl_hip_eval_metric(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective, int metric,
                          double *value_out, int64_t *counts_out) {

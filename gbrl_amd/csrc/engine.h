@@ -128,7 +128,10 @@ struct CatItem { int feat; int next; uint64_t lhash; size_t std_hash; char name[
 }  // namespace detail
 
 // The options of Engine::fit_prepared; the defaults are the plain MultiRMSE loop on every row and column.
-struct FitOptions { double subsample = 1.0, colsample = 1.0; uint64_t seed = 0; int objective = 0 /* kern::kObjRmse */; int metric = 0 /* kern::kMetricNone */; };
+struct FitOptions {
+    double subsample = 1.0, colsample = 1.0; uint64_t seed = 0; int objective = 0 /* kern::kObjRmse */; int metric = 0 /* kern::kMetricNone */;
+    int leaf_update = 0 /* kern::kLeafGradient; 1: kern::kLeafNewton */; double leaf_l2 = 1.0;
+};
 
 class Engine {
    public:
@@ -200,6 +203,10 @@ class Engine {
     //              until the end, as the loss sums do).  The stopping rule and best_n_trees then follow the metric curve -- the error as it is,
     //              the AUC negated -- in place of loss_out, which is recorded as ever.  It reads the held prediction only: the model is byte
     //              for byte what the call without it leaves after `done` iterations.
+    //   leaf_update  (newton_core.h; kern::kLeafGradient / kLeafNewton)  newton: right after the step every leaf of the new tree gets sum g / (sum h +
+    //              leaf_l2) over the rows the tree was grown on -- the batch, or the kept rows of a sampled iteration -- by newton_leaves_prepared's
+    //              body on the held prediction (one launch, one read-back, the tree's value slice of the mirror sent again); the held predictions,
+    //              the validation walk and the loss then see those values.  gradient enqueues nothing: the loop is the one without the option.
     // Refused before anything changes, in this order: precheck_fit's list; ds, then valid->ds, absent or not this model's (check_prepared_dataset);
     // another thresholds id; null valid->loss_out; a tree whose conditions the codes cannot express (Unsupported); softmax: a label outside [0, D)
     // in either set (InvalidArgument naming the first one found).
@@ -212,7 +219,7 @@ class Engine {
     // What fit_prepared refuses without a data set in hand, in this order (the C ABI runs it before it resolves the handles, so that these
     // refusals do not depend on a data set being at hand; valid->ds is not looked at): the model checks of step_prepared; null targets;
     // iterations < 0; batch_size <= 0; max_depth > 32, n_bins outside [1, 65534], output_dim > 128 (Unsupported); check_subsample;
-    // check_colsample; check_objective; a metric without valid, check_metric; with valid: null targets, rounds < 0, min_delta negative or NaN.
+    // check_colsample; check_objective; check_leaf_update; a metric without valid, check_metric; with valid: null targets, rounds < 0, min_delta negative or NaN.
     void precheck_fit(const void *targets, int iterations, const FitOptions &opt, const FitValid *valid) const;
     // Extension: row subsampling (stochastic gradient boosting).  The sampler is sample_core.h's pure function of (seed, draw, row): a row is
     // kept iff its 24-bit hash is below floor(subsample * 2^24); the sample of [row0, row0 + n) is the ascending list of its kept absolute indices.
@@ -245,6 +252,24 @@ class Engine {
     static void check_metric(const char *what, int objective, int metric);
     void eval_metric(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, int metric, double *value, int64_t *counts);
     static void eval_metric_host(const float *pred, const void *targets, int n, int D, int objective, int metric, double *value, int64_t *counts);
+    // Extension: Newton leaf values (newton_core.h has the rule, include/gbrl_hip.h the contract).  newton_leaves_prepared: the leaves of ONE tree
+    // (tree == -1: the last) get v = (sum g) / (sum h + leaf_l2) over the data set rows rows[0..m) (rows == nullptr: every row, m == ds->n), g and h
+    // the objective's at pred [m][D] -- the caller's prediction over the trees [0, tree), indexed by position like targets ([m][D] float32, or int32
+    // [m] labels for softmax).  The sums are exact int64 (kern::newton_leaf_sums) and the value is computed from them on the host in double; a leaf
+    // without rows, of depth 0, or with sum h + leaf_l2 <= 0 keeps its value.  sums_out (nullable) int64 [leaves][2 D + 1] = (Sg, Sh, cnt),
+    // *bits_out the bits of the quantum, values_out (nullable) float32 [leaves][D] what the model now holds.  Only model.values of that tree
+    // changes, and only its slice of the device mirror is sent again.  Refused before anything changes: what predict_continue_prepared refuses
+    // about the model, the data set and rows; output_dim > 128; the rmse objective (its Newton step is the gradient mean: InvalidArgument); a
+    // leaf_l2 that is negative, NaN or infinite; a tree outside the model; a softmax label outside [0, D).  Refused after the launch, the model
+    // unchanged (InvalidArgument): a logistic target outside [0, 1] (a NaN counts), a prediction that is not finite.
+    void newton_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *pred, bool pred_dev, const void *targets,
+                                bool targets_dev, int objective, int tree, double leaf_l2, int64_t *sums_out, int *bits_out, float *values_out);
+    static void check_leaf_update(const char *what, int objective, int leaf_update, double leaf_l2);   // unknown update, newton with rmse, a bad leaf_l2
+    // the hessian rule on the host (no device): out [n][D] = obj_logistic_hess(p) / the diagonal softmax hessian q (1 - q); targets are not read
+    static void objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out);
+    // the value rule on the host (no device): sums int64 [leaves][2 D + 1], old_values float32 [leaves][D], depths int32 [leaves] -> values_out [leaves][D]
+    static void newton_values_host(const int64_t *sums, int n_leaves, int D, int bits, const float *old_values, const int32_t *depths, double leaf_l2,
+                                   float *values_out);
     // the gradient rule on the host (no device): the same bits
     static void objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out);
     // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
@@ -335,6 +360,7 @@ class Engine {
    private:
     void ensure_device();
     void sync_model_to_device();
+    void rewind_values(int t);  // the values of tree t alone have changed (newton_leaves_prepared): the next sync appends them again from that tree on
     void invalidate_mirror();   // values of existing trees have changed (refit_leaves): the append-only mirror is uploaded again, the dictionary stays
     void sync_cat_dict();   // the host half of it: cat_dict_ / cat_ids_host_ follow the model (no device needed)
     int32_t *encode_categorical_batch(const char *cat, bool cat_dev, int n, int n_cat);
@@ -499,6 +525,12 @@ class Engine {
     // the partials of a loss tail summed into *d_sum (kern::staged_loss_finish) and, with host_sum, its 8 bytes on their way to the host: they
     // are there after the caller's wait for the stream
     void finish_loss_sum(const double *d_part, int n_part, double *d_sum, double *host_sum);
+    // newton_leaves_prepared behind its argument checks and input staging (fit_prepared's loop body too): device pred / targets, indexed by the
+    // position or (abs_index) by the data set row; the phase newton_leaves joins the caller's phase list
+    void newton_leaves_run(const char *what, const PreparedDataset *ds, const kern::CodeRows &cr, int m, const float *d_pred, const void *d_targets, bool abs_index,
+                           int objective, int t, double leaf_l2, bool generic, int64_t *sums_out, int *bits_out, float *values_out);
+    DevBuf d_newton_acc_;                         // its int64 sums [leaves][2 D + 1] and the flag word
+    std::vector<unsigned long long> newton_host_;   // ... read back
     // Column sums in float64 of device rows [rows][D] and the MultiRMSE built on them, as fit() and fit_prepared() compute the bias and the loss
     // (engine_step.hip).  Its construction enqueues the memset of the zero center.
     struct ColumnStats {
@@ -551,6 +583,8 @@ class Engine {
     DevBuf m_tree_indices_, m_depths_, m_feature_indices_, m_feature_values_, m_values_, m_is_numerics_, m_ineq_,
         m_cat_ids_, m_bias_, m_opt_start_, m_opt_stop_, m_opt_lr_, m_cond_pack_, m_grd_nodes_, m_grd_off_, m_values_sw_, m_cond_ra_;
     size_t up_trees_ = 0, up_leaves_ = 0, up_splits_ = 0;  // how much of the append-only arrays is already on the device
+    static constexpr size_t kNoRedo = ~static_cast<size_t>(0);
+    size_t values_redo_tree_ = kNoRedo;   // rewind_values: the first tree whose pre-swizzled value records are stale
     // Linear schedules: rate[t][optimizer] for every tree (gbrl::scheduler_lr), appended as trees join -- a tree's rate never changes --
     // and rebuilt when the optimizers have changed.  Not built while every optimizer is Const.
     DevBuf m_rate_;

@@ -13,6 +13,9 @@
 //                                      back, step_prepared's body grows on the subset) and on a sample of the columns (the host rule of
 //                                      sample_core.h per iteration, step_prepared's cols path); a classifier's metric of the validation rows
 //                                      per iteration, which then decides the stopping rule and best_n_trees in place of the loss
+//   Engine::newton_leaves_prepared     one tree's leaves set to sum g / (sum h + leaf_l2) over a data set's rows (newton_core.h; kern::newton_leaf_sums), the
+//                                      rules on the host beside it (objective_hessian_host, newton_values_host); fit_prepared(leaf_update = newton) runs its
+//                                      body after every step
 //   Engine::eval_metric[_host]         the error rate and the exact AUC of a prediction matrix (metric_core.h), on the device and on the host
 //
 // The rule.  code(r, f) = #{b : thr[f][b] < obs[r, f]} (-0.0 == +0.0; NaN lies below every threshold: code 0).  For a condition x > v whose v
@@ -22,6 +25,7 @@
 #include "engine_step_detail.h"
 #include "objective_core.h"
 #include "metric_core.h"
+#include "newton_core.h"
 #include "sample_core.h"
 
 namespace gbrl {
@@ -287,6 +291,130 @@ void Engine::objective_gradient(const float *pred, bool pred_dev, const void *ta
     if (loss_out) *loss_out = mean_loss(objective, sum, n);
 }
 
+// ---- Newton leaf values: the checks, the rules on the host, one tree's sums on the device and the values from them
+void Engine::check_leaf_update(const char *what, int objective, int leaf_update, double leaf_l2) {
+    if (leaf_update != kern::kLeafGradient && leaf_update != kern::kLeafNewton)
+        throw InvalidArgument(std::string(what) + ": unknown leaf_update " + std::to_string(leaf_update) + " (gradient = 0, newton = 1)");
+    if (!(leaf_l2 >= 0.0) || std::isinf(leaf_l2))
+        throw InvalidArgument(std::string(what) + ": leaf_l2 must be finite and >= 0 (and not NaN), got " + std::to_string(leaf_l2));
+    if (leaf_update == kern::kLeafNewton && objective == kern::kObjRmse)
+        throw InvalidArgument(std::string(what) + ": newton leaf values with the rmse objective are the gradient means the step already stores (use logistic or softmax)");
+}
+
+void Engine::objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out) {
+    if (pred == nullptr || hess_out == nullptr) throw InvalidArgument("objective_hessian_host: null argument");
+    if (n <= 0) throw InvalidArgument("objective_hessian_host: no rows (n must be positive)");
+    if (D < 1) throw InvalidArgument("objective_hessian_host: output_dim must be positive");
+    check_objective("objective_hessian_host", objective, D);
+    const size_t n_el = static_cast<size_t>(n) * D;
+    if (objective == kern::kObjRmse) {
+        std::fill(hess_out, hess_out + n_el, 1.0f);
+    } else if (objective == kern::kObjLogistic) {
+        for (size_t i = 0; i < n_el; ++i) hess_out[i] = kern::obj_logistic_hess(pred[i]);
+    } else {
+        std::vector<float> row(D);
+        for (int r = 0; r < n; ++r) {
+            std::copy(pred + static_cast<size_t>(r) * D, pred + static_cast<size_t>(r + 1) * D, row.begin());
+            float *h = hess_out + static_cast<size_t>(r) * D;
+            kern::obj_softmax_grad_hess_row(row, h, D, 0);
+        }
+    }
+}
+
+void Engine::newton_values_host(const int64_t *sums, int n_leaves, int D, int bits, const float *old_values, const int32_t *depths, double leaf_l2, float *values_out) {
+    if (sums == nullptr || old_values == nullptr || depths == nullptr || values_out == nullptr) throw InvalidArgument("newton_values_host: null argument");
+    if (n_leaves <= 0 || D < 1) throw InvalidArgument("newton_values_host: leaves and output_dim must be positive");
+    if (bits < 0 || bits > 62) throw InvalidArgument("newton_values_host: bits must be in [0, 62]");
+    check_leaf_update("newton_values_host", kern::kObjLogistic, kern::kLeafNewton, leaf_l2);
+    const double scale = std::ldexp(1.0, bits);
+    const size_t W = 2 * static_cast<size_t>(D) + 1;
+    for (int l = 0; l < n_leaves; ++l)
+        for (int d = 0; d < D; ++d)
+            values_out[static_cast<size_t>(l) * D + d] = kern::newton_leaf_value(sums[l * W + d], sums[l * W + D + d], sums[l * W + 2 * D], depths[l], scale, leaf_l2,
+                                                                                  old_values[static_cast<size_t>(l) * D + d]);
+}
+
+void Engine::newton_leaves_run(const char *what, const PreparedDataset *ds, const kern::CodeRows &cr, int m, const float *d_pred, const void *d_targets, bool abs_index,
+                               int objective, int t, double leaf_l2, bool generic, int64_t *sums_out, int *bits_out, float *values_out) {
+    const gbrl_hip_metadata &md = model.meta;
+    hipStream_t s = stream_;
+    const int D = md.output_dim, T = md.n_trees;
+    const size_t leaf0 = static_cast<size_t>(model.tree_indices[t]);
+    const size_t NL = (t + 1 < T ? static_cast<size_t>(model.tree_indices[t + 1]) : static_cast<size_t>(md.n_leaves)) - leaf0;
+    const size_t W = 2 * static_cast<size_t>(D) + 1, words = NL * W + 1;
+    check_code_range(*ds, what, t, t + 1);
+    sync_model_to_device();
+    const kern::CodeTables ct = sync_code_tables(*ds);
+    const bool timed = profiling_ >= 2;
+    phase_begin();
+    unsigned long long *dacc = static_cast<unsigned long long *>(d_newton_acc_.ensure(sizeof(unsigned long long) * words));
+    hip_check(hipMemsetAsync(dacc, 0, sizeof(unsigned long long) * words, s), "zero leaf sums");
+    const int bits = kern::newton_sum_bits(m);
+    const bool streamed =
+        kern::newton_leaf_sums(mirror_view(), ct, cr, m, t, static_cast<int>(leaf0), static_cast<int>(NL), d_pred, d_targets, abs_index, objective, bits, dacc, generic, s);
+    newton_host_.resize(words);
+    hip_check(hipMemcpyAsync(newton_host_.data(), dacc, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, s), "D2H leaf sums");
+    phase_end("newton_leaves");
+    hip_check(hipStreamSynchronize(s), "sync");
+    if (timed) {   // the phase joins the list the caller's phases are in (a step's list has been resolved already)
+        float ms = 0.f;
+        hip_check(hipEventElapsedTime(&ms, ev_pool_[ev_used_ - 1].first, ev_pool_[ev_used_ - 1].second), "hipEventElapsedTime");
+        --ev_used_;
+        ev_names_.pop_back();
+        phases_.emplace_back("newton_leaves", ms);
+        phases_.emplace_back("newton_streamed", streamed ? 1.f : 0.f);   // (not a time: 1 = the streaming kernel took the sums)
+    }
+    const unsigned long long flag = newton_host_[words - 1];
+    if (flag & kern::kNewtonBadTarget)
+        throw InvalidArgument(std::string(what) + ": a logistic target is outside [0, 1] (or NaN): newton leaf values need targets in [0, 1]; the model is unchanged");
+    if (flag & kern::kNewtonBadPred)
+        throw InvalidArgument(std::string(what) + ": a prediction is not finite: no newton leaf values; the model is unchanged");
+    const double scale = std::ldexp(1.0, bits);
+    for (size_t l = 0; l < NL; ++l) {
+        const long long *a = reinterpret_cast<const long long *>(newton_host_.data()) + l * W;
+        const int depth = model.oblivious() ? model.depths[t] : model.depths[leaf0 + l];
+        float *v = model.values.data() + (leaf0 + l) * D;
+        for (int d = 0; d < D; ++d) v[d] = kern::newton_leaf_value(a[d], a[D + d], a[2 * D], depth, scale, leaf_l2, v[d]);
+    }
+    ++model.version;
+    rewind_values(t);
+    if (sums_out) std::memcpy(sums_out, newton_host_.data(), sizeof(int64_t) * NL * W);
+    if (bits_out) *bits_out = bits;
+    if (values_out) std::memcpy(values_out, model.values.data() + leaf0 * D, sizeof(float) * NL * D);
+}
+
+void Engine::newton_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *pred, bool pred_dev, const void *targets,
+                                    bool targets_dev, int objective, int tree, double leaf_l2, int64_t *sums_out, int *bits_out, float *values_out) {
+    const gbrl_hip_metadata &md = model.meta;
+    const int D = md.output_dim, T = md.n_trees;
+    check_prepared_dataset("newton_leaves_prepared", ds);
+    if (D > 128) throw Unsupported("newton_leaves_prepared: output_dim > 128");
+    if (pred == nullptr) throw InvalidArgument("newton_leaves_prepared: no prediction");
+    if (targets == nullptr) throw InvalidArgument("Cannot call newton_leaves_prepared without targets!");
+    check_objective("newton_leaves_prepared", objective, D);
+    check_leaf_update("newton_leaves_prepared", objective, kern::kLeafNewton, leaf_l2);
+    if (T == 0) throw InvalidArgument("newton_leaves_prepared: the model has no trees");
+    if (tree < -1 || tree >= T) throw InvalidArgument("newton_leaves_prepared: tree " + std::to_string(tree) + " is outside the model's " + std::to_string(T) + " trees (-1: the last)");
+    const int t = tree == -1 ? T - 1 : tree;
+    if (m <= 0) throw InvalidArgument("newton_leaves_prepared: no rows (m must be positive)");
+    if (rows == nullptr && m != ds->n)
+        throw InvalidArgument("newton_leaves_prepared: pred has " + std::to_string(m) + " rows, the data set " + std::to_string(ds->n) + " (pass rows to sum over a subset)");
+    if (rows != nullptr && !rows_dev) check_host_rows(rows, m, ds->n);
+    check_code_range(*ds, "newton_leaves_prepared", t, t + 1);
+    ensure_device();
+    ev_used_ = 0;
+    ev_names_.clear();
+    phases_.clear();
+    hipStream_t s = stream_;
+    const int32_t *d_rows = rows ? checked_rows(d_sub_rows_, d_rows_mm_, rows, rows_dev, m, ds->n, s) : nullptr;
+    const size_t n_el = static_cast<size_t>(m) * D, tar_el = objective == kern::kObjSoftmax ? static_cast<size_t>(m) : n_el;
+    const float *dp = pred_dev ? pred : upload(d_obj_pred_, pred, n_el, "H2D predictions");
+    const float *dt = targets_dev ? static_cast<const float *>(targets) : upload(d_obj_targets_, static_cast<const float *>(targets), tar_el, "H2D targets");
+    if (objective == kern::kObjSoftmax) check_labels("newton_leaves_prepared", reinterpret_cast<const int32_t *>(dt), m, D, nullptr);
+    newton_leaves_run("newton_leaves_prepared", ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, dp, dt, /*abs_index=*/false, objective, t,
+                      leaf_l2, hooks::on(hooks::CONTINUE_GENERIC), sums_out, bits_out, values_out);
+}
+
 // ---- classifier metrics: the checks, the host rule, the device pipeline (kern::metric_error / kern::metric_auc) and the value from its integers
 void Engine::check_metric(const char *what, int objective, int metric) {
     if (metric != kern::kMetricError && metric != kern::kMetricAuc)
@@ -414,6 +542,7 @@ void Engine::precheck_fit(const void *targets, int iterations, const FitOptions 
     check_subsample("fit_prepared", opt.subsample);
     check_colsample("fit_prepared", opt.colsample);
     check_objective("fit_prepared", opt.objective, md.output_dim);
+    check_leaf_update("fit_prepared", opt.objective, opt.leaf_update, opt.leaf_l2);
     if (opt.metric != kern::kMetricNone) {
         if (valid == nullptr) throw InvalidArgument("fit_prepared: eval_metric needs a validation set (valid=)");
         check_metric("fit_prepared", opt.objective, opt.metric);
@@ -490,14 +619,26 @@ struct Engine::FitRun {
         const float *t = static_cast<const float *>(host_or_dev);
         return on_dev ? t : e.upload(buf, t, static_cast<size_t>(rows) * (opt.objective == kern::kObjSoftmax ? 1 : D), "H2D targets");
     }
-    // Both target arrays on the device; softmax: a label outside [0, D), in either set, is refused before anything changes.
+    // Both target arrays on the device; newton with logistic: a training target outside [0, 1] is refused; softmax: a label outside [0, D), in either set, is refused before anything changes.
     void stage_targets(const void *targets, bool targets_dev) {
         dtar = stage(e.d_fp_targets_, targets, targets_dev, n);
         if (v) dvtar = stage(e.d_fp_vtargets_, v->targets, v->targets_dev, v->ds->n);
         if (opt.metric == kern::kMetricAuc) count_positives();
+        if (opt.leaf_update == kern::kLeafNewton && opt.objective == kern::kObjLogistic) check_unit_targets();
         if (opt.objective != kern::kObjSoftmax) return;
         e.check_labels("fit_prepared", reinterpret_cast<const int32_t *>(dtar), n, D, &class_counts);
         if (v) e.check_labels("fit_prepared (valid_targets)", reinterpret_cast<const int32_t *>(dvtar), v->ds->n, D, nullptr);
+    }
+    // newton + logistic: a training target outside [0, 1] (a NaN counts) is refused before anything changes (the sums' kernel would flag it too)
+    void check_unit_targets() {
+        hipStream_t s = e.stream_;
+        unsigned long long flag = 0;
+        unsigned long long *d = static_cast<unsigned long long *>(e.d_newton_acc_.ensure(sizeof(unsigned long long)));
+        hip_check(hipMemsetAsync(d, 0, sizeof(unsigned long long), s), "zero target flag");
+        kern::newton_check_targets(dtar, static_cast<size_t>(n) * D, d, s);
+        hip_check(hipMemcpyAsync(&flag, d, sizeof(flag), hipMemcpyDeviceToHost, s), "D2H target flag");
+        hip_check(hipStreamSynchronize(s), "sync");
+        if (flag) throw InvalidArgument("fit_prepared: a logistic target is outside [0, 1] (or NaN): newton leaf values need targets in [0, 1]");
     }
     // auc: the positives of every validation column; a column of one class is refused before anything changes
     void count_positives() {
@@ -656,6 +797,11 @@ struct Engine::FitRun {
             e.step_prepared_run(ds, g, rows, m, e.fit_cols_.data(), static_cast<int>(e.fit_cols_.size()));
         } else {
             e.step_prepared_run(ds, g, rows, m);
+        }
+        if (opt.leaf_update == kern::kLeafNewton) {   // the new tree's leaves from the rows it was grown on, at the held prediction over the trees before it
+            const bool kept = rows == d_srows && rows != nullptr;
+            e.newton_leaves_run("fit_prepared", ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), kept ? d_srows : nullptr, kept ? 0 : start}, m, train.P,
+                                dtar, /*abs_index=*/true, opt.objective, e.model.meta.n_trees - 1, opt.leaf_l2, generic, nullptr, nullptr, nullptr);
         }
         start += bn;                                                                // fitter.cpp:228-231
         if (start >= n) start = 0;

@@ -56,9 +56,18 @@ void Engine::sync_cat_dict() {
 // the reset branch of sync_cat_dict(): the conditions have not changed, so ids encoded before the refit and the dictionary token stay valid.
 void Engine::invalidate_mirror() {
     up_trees_ = up_leaves_ = up_splits_ = 0;
+    values_redo_tree_ = kNoRedo;
     grd_up_nodes_ = 0;
     rate_trees_ = 0;
     mirror_version_ = ~0ull;
+}
+
+// The values of tree t alone have changed (newton_leaves_prepared; inside fit_prepared t is the tree the step has just appended): the upload mark of
+// the values goes back to the tree's first leaf and the next sync_model_to_device() appends them again from there -- m_values_ from that leaf
+// on, the pre-swizzled value records from that tree on.  Conditions, node records, code tables and the dictionary hold no value and stay.
+void Engine::rewind_values(int t) {
+    up_leaves_ = std::min(up_leaves_, static_cast<size_t>(model.tree_indices[t]));
+    values_redo_tree_ = std::min(values_redo_tree_, static_cast<size_t>(t));
 }
 
 void Engine::sync_model_to_device() {
@@ -67,6 +76,7 @@ void Engine::sync_model_to_device() {
     const size_t T = md.n_trees, L = md.n_leaves, S = model.split_rows(), MD = md.max_depth, D = md.output_dim;
     if (mirror_version_ == model.version) return;
     sync_cat_dict();
+    const size_t vt0 = std::min(up_trees_, values_redo_tree_);   // the value records are rebuilt from here (rewind_values; else only the new trees)
     // The appended slices (one new tree after a step: a dozen pieces of a few hundred bytes) are collected here and leave together at the end
     // (flush_segments): staged in ONE pinned block and copied by one kernel launch, instead of a hipMemcpyAsync from pageable memory per
     // piece plus a stream synchronisation -- 0.1 ms per predict-after-step in an RL loop (round 4).
@@ -149,7 +159,7 @@ void Engine::sync_model_to_device() {
         int32_t inf_bits;
         const float inf = std::numeric_limits<float>::infinity();
         std::memcpy(&inf_bits, &inf, sizeof(inf_bits));
-        for (size_t t = up_trees_; t < T; ++t) {
+        for (size_t t = vt0; t < T; ++t) {
             const size_t depth = static_cast<size_t>(model.depths[t]);
             int32_t *cr = &cond_ra_host_[t * 2 * MX];
             for (size_t d = 0; d < MX - depth; ++d) { cr[2 * d] = 0; cr[2 * d + 1] = inf_bits; }
@@ -167,7 +177,7 @@ void Engine::sync_model_to_device() {
         for (size_t t = T; t < T + kPadTrees; ++t)
             for (size_t d = 0; d < MX; ++d) { cond_ra_host_[(t * MX + d) * 2] = inf_pad[0]; cond_ra_host_[(t * MX + d) * 2 + 1] = inf_pad[1]; }
         append(m_cond_ra_, cond_ra_host_.data(), 4, up_trees_ * 2 * MX, (T + kPadTrees) * 2 * MX);
-        append_padded(m_values_sw_, values_sw_host_.data(), up_trees_, T, VT, vpad);
+        append_padded(m_values_sw_, values_sw_host_.data(), vt0, T, VT, vpad);
     }
     // Greedy ensembles: rebuild every new tree as a binary tree from its leaves' paths (leaves are stored depth-first, left
     // first; fitter.cpp:364-365), for the descent of k_predict_grd.  A tree whose leaves do not form a proper binary tree (a
@@ -233,8 +243,8 @@ void Engine::sync_model_to_device() {
             const size_t vpad = kPadTrees * RECF + (size_t(64) << 10) / sizeof(float);
             if (up_trees_ == 0) values_sw_host_.clear();
             values_sw_host_.resize(T * RECF + vpad);
-            std::fill(values_sw_host_.begin() + static_cast<long>(up_trees_ * RECF), values_sw_host_.end(), 0.0f);
-            for (size_t t = up_trees_; t < T; ++t) {
+            std::fill(values_sw_host_.begin() + static_cast<long>(vt0 * RECF), values_sw_host_.end(), 0.0f);
+            for (size_t t = vt0; t < T; ++t) {
                 float *rec = &values_sw_host_[t * RECF];
                 const size_t l0 = static_cast<size_t>(model.tree_indices[t]), l1 = t + 1 < T ? static_cast<size_t>(model.tree_indices[t + 1]) : L;
                 for (size_t leaf = 0; leaf < l1 - l0 && leaf < LS; ++leaf)
@@ -242,10 +252,11 @@ void Engine::sync_model_to_device() {
                 const size_t n0 = static_cast<size_t>(grd_off_host_[t]), n1 = static_cast<size_t>(grd_off_host_[t + 1]);
                 if (n1 - n0 <= LS) std::memcpy(rec + VT, &grd_nodes_host_[n0 * 4], (n1 - n0) * 16);
             }
-            append_padded(m_values_sw_, values_sw_host_.data(), up_trees_, T, RECF, vpad);
+            append_padded(m_values_sw_, values_sw_host_.data(), vt0, T, RECF, vpad);
         }
     }
     up_trees_ = T; up_leaves_ = L; up_splits_ = S;
+    values_redo_tree_ = kNoRedo;
     // small, mutable state: always refreshed
     append(m_bias_, model.bias.data(), 4, 0, D);
     std::vector<int32_t> os, oe;

@@ -640,6 +640,14 @@ void objective_rows(int objective, const float *pred, const void *targets, int n
 // counts[D] = the smallest row index whose label is outside [0, D)
 void label_counts(const int32_t *labels, int n, int D, int32_t *counts, hipStream_t s);
 void tile_rows(const float *row /*[D], device*/, int D, int n, float *out /*[n][D]*/, hipStream_t s);   // out[r] = row: fit_prepared's held prediction starts as the bias
+// Newton leaf sums (newton.hip; newton_core.h has the rule): the rows of cr routed through `tree` (leaves [leaf0, leaf0 + n_leaves)) by the code walk,
+// acc[l][2 D + 1] += (q(g)[D], q(h)[D], 1) with q(x) = llrint((double)x * 2^bits), g and h the objective's (kObjLogistic: targets float32 [.][D];
+// kObjSoftmax: int32 labels in [0, D), checked by the caller) at pred -- the prediction over the trees [0, tree).  pred and targets are indexed by
+// the position j < m, or with abs_index by the data set row position j names.  acc (device, n_leaves * (2 D + 1) + 1 words, ZEROED by the caller on
+// `s`): the last word collects kNewtonBadTarget / kNewtonBadPred.  D <= 128.  Returns true when the streaming kernel took the launch.
+void newton_check_targets(const float *targets, size_t n_el, unsigned long long *flag /*device, zeroed by the caller*/, hipStream_t s);   // *flag |= kNewtonBadTarget: an entry outside [0, 1] (a NaN counts)
+bool newton_leaf_sums(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int tree, int leaf0, int n_leaves, const float *pred,
+                      const void *targets, bool abs_index, int objective, int bits, unsigned long long *acc, bool generic, hipStream_t s);
 // Every prefix [0, stops[s]) of the ensemble in one walk (predict_staged.hip): stage s has the bits of predict_continue(tiled bias, 0, stops[s]);
 // stops[s] == 0 is the bias alone.  `stops` is a device array, strictly ascending, 0 <= stops[s] <= n_trees (the caller has checked);
 // last_stop = stops[n_stops - 1].  Predict mode (targets == nullptr): out[s][r][j], device [n_stops][n][D].  Loss mode (targets != nullptr,

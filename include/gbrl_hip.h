@@ -537,6 +537,54 @@ int gbrl_hip_fit_prepared_metric(gbrl_hip_model *m, const gbrl_hip_dataset *ds, 
 int gbrl_hip_eval_metric(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective,
                          int metric, double *value_out, int64_t *counts_out);
 int gbrl_hip_eval_metric_host(const float *pred, const void *targets, int n, int D, int objective, int metric, double *value_out, int64_t *counts_out);
+/* Newton leaf values (new: the second-order step a classifier's leaves take in scikit-learn, XGBoost and LightGBM).  A tree is grown on the
+ * gradient g = dL/dp as ever; with GBRL_HIP_LEAF_NEWTON every leaf then stores v = (sum g) / (sum h + leaf_l2) over the rows the tree was grown
+ * on instead of the mean of g, h = d2L/dp2 (softmax: the diagonal).  Predictions move by -rate * v, the sign convention is unchanged.
+ * csrc/newton_core.h defines all of it once for the host and the kernels:
+ *   hessian   logistic: e = exp32(-|p|), den = 1 + e as in the gradient; h = fl32(fl32(1 / den) * fl32(e / den)), both quotients correctly
+ *             rounded -- no 1 - s cancels, h(p) == h(-p) bit for bit, h(0) = 0.25.  softmax: q_c exactly as the gradient computes it,
+ *             h_c = fl32(q_c * fl32(1 - q_c)).  The gradient is gbrl_hip_objective_gradient_host's, bit for bit.
+ *   sums      bits = min(40, 62 - bit_length(m)) for m summed rows; q(x) = llrint((double)x * 2^bits) for g and h alike; per leaf the int64
+ *             Sg[D], Sh[D] and cnt.  |g| <= 1 and h <= 0.25: no sum reaches 2^62.  Integer adds on the device: every run, and both kernel
+ *             families, give the same bytes.
+ *   value     on the host in double: G = Sg / 2^bits, H = Sh / 2^bits, den = H + leaf_l2, v = (float)(G / den).  A leaf keeps the value it
+ *             has when cnt == 0, when its depth is 0, or when !(den > 0).
+ *   gbrl_hip_newton_leaves_prepared(m, ds, rows, rows_on_device, n_rows, pred, pred_on_device, targets, targets_on_device, objective, tree,
+ *     leaf_l2, sums_out, bits_out, values_out)  the rule applied to ONE tree (tree == -1: the last) over the data set rows rows[0 .. n_rows)
+ *     (NULL: every row, n_rows == the data set's).  pred [n_rows, output_dim] is the caller's prediction over the trees [0, tree) and, like
+ *     targets ([n_rows, output_dim] float32, or int32 [n_rows] labels for softmax), is indexed by position.  sums_out (host, may be NULL)
+ *     int64 [leaves, 2 output_dim + 1] = (Sg, Sh, cnt) per leaf of the tree; *bits_out (may be NULL); values_out (host, may be NULL) float32
+ *     [leaves, output_dim], what the model holds afterwards.  Only that tree's values change; only its slice of the device mirror is sent
+ *     again.  Refused before anything changes: what gbrl_hip_predict_continue_prepared refuses about the model, the data set and rows;
+ *     output_dim > 128; GBRL_HIP_OBJ_RMSE (GBRL_HIP_E_INVALID: its Newton step is the gradient mean the step stores); a leaf_l2 that is
+ *     negative, NaN or infinite; a tree outside the model; a label outside [0, output_dim).  Found by the kernel and refused with the model
+ *     unchanged (GBRL_HIP_E_INVALID): a logistic target outside [0, 1] (a NaN counts), a prediction that is not finite.
+ *   gbrl_hip_objective_hessian_host(pred, n, D, objective, hess_out)  the hessian rule on the host, no device (rmse: 1).
+ *   gbrl_hip_newton_values_host(sums, n_leaves, D, bits, old_values, depths, leaf_l2, values_out)  the value rule on the host, no device:
+ *     sums int64 [n_leaves, 2 D + 1], old_values float32 [n_leaves, D], depths int32 [n_leaves].
+ *   gbrl_hip_newton_sum_bits(m)  the bits of the quantum for m rows.
+ *   gbrl_hip_fit_prepared_leaf(.., objective, metric, leaf_update, leaf_l2, ..)  gbrl_hip_fit_prepared_metric plus the leaf rule; the older
+ *     calls are this one with GBRL_HIP_LEAF_GRADIENT and leaf_l2 = 1.  GBRL_HIP_LEAF_NEWTON: right after every step the new tree's leaves get
+ *     gbrl_hip_newton_leaves_prepared's values from the rows the tree was grown on (the batch; the kept rows of a sampled iteration, the whole
+ *     batch when the draw kept none) at the held prediction; the held predictions, the validation curve and the returned loss see them.  The
+ *     model is byte for byte the loop objective_gradient -> step_prepared -> newton_leaves_prepared -> predict_continue_prepared written by
+ *     hand.  GBRL_HIP_LEAF_GRADIENT enqueues nothing new.  Refused before anything changes (GBRL_HIP_E_INVALID): an unknown leaf_update,
+ *     newton with GBRL_HIP_OBJ_RMSE, a bad leaf_l2, and with newton and logistic a training target outside [0, 1].
+ *   Out of scope: Newton values in fit(), step() and refit_leaves, hessian-weighted split scores, min_child_weight, the full softmax hessian,
+ *     row-sharded models. */
+enum { GBRL_HIP_LEAF_GRADIENT = 0, GBRL_HIP_LEAF_NEWTON = 1 };
+int gbrl_hip_newton_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,
+                                    int pred_on_device, const void *targets, int targets_on_device, int objective, int tree, double leaf_l2,
+                                    int64_t *sums_out /*[leaves, 2 output_dim + 1]*/, int *bits_out, float *values_out /*[leaves, output_dim]*/);
+int gbrl_hip_objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out /*[n, D]*/);
+int gbrl_hip_newton_values_host(const int64_t *sums, int n_leaves, int D, int bits, const float *old_values, const int32_t *depths, double leaf_l2,
+                                float *values_out /*[n_leaves, D]*/);
+int gbrl_hip_newton_sum_bits(int64_t m);
+int gbrl_hip_fit_prepared_leaf(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                               const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                               double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update,
+                               double leaf_l2, float *loss_out, double *valid_loss_out /*[iterations + 1]*/,
+                               double *valid_metric_out /*[iterations + 1]*/, int *iterations_done, int *best_n_trees);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
