@@ -821,30 +821,47 @@ Input read_objective_targets(py::object &targets, const char *name, bool none_al
     return t;
 }
 
+// row weights (include/gbrl_hip.h, "Row weights"): None, or float32 [n] as a NumPy array or a device tuple
+Input read_weights(py::object &weights, const char *name, const std::string &fn, int n, bool check_shape) {
+    if (weights.is_none()) return Input{};
+    Input w = read_input(weights, name, false, fn, false);
+    if (!w.ptr) fail("Cannot call " + fn + " with a null " + name + " pointer!");
+    if (check_shape && !(w.shape.size() == 1 && w.shape[0] == static_cast<size_t>(n))) {
+        std::stringstream ss;
+        ss << "Expected " << name << " as a float32 vector of shape (" << n << ",), one weight per row";
+        fail(ss.str());
+    }
+    return w;
+}
+
 // fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,
-// objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
+// objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
 // with either.  A missing valid_targets is left to the C ABI's message.
 py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
                              int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name,
-                             py::object metric_obj, const std::string &leaf_update_name = "gradient", double leaf_l2 = 1.0) {
+                             py::object metric_obj, const std::string &leaf_update_name, double leaf_l2, py::object &weights, py::object &valid_weights) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     const int objective = parse_objective(objective_name), leaf_update = parse_leaf_update(leaf_update_name);
     const int metric = metric_obj.is_none() ? GBRL_HIP_METRIC_NONE : parse_metric(metric_obj.cast<std::string>());
     if (valid_obj.is_none() && (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0))
         fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
+    if (valid_obj.is_none() && !valid_weights.is_none()) fail("fit_prepared: valid_weights need a validation set (valid=)");
     const gbrl_hip_dataset *dsv = valid_obj.is_none() ? nullptr : valid_obj.cast<const PyDataset &>().h;
+    Input w = read_weights(weights, "weights", "fit_prepared", ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, ds != nullptr), wv;
+    if (dsv) wv = read_weights(valid_weights, "valid_weights", "fit_prepared", valid_obj.cast<const PyDataset &>().info().n_rows, true);
     Input t = read_objective_targets(targets, "targets", false, "fit", objective, ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, md.output_dim, ds != nullptr);
     Input tv;
     if (dsv) tv = read_objective_targets(valid_targets, "valid_targets", true, "fit", objective, valid_obj.cast<const PyDataset &>().info().n_rows, md.output_dim, true);
     std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0), mcurve(metric != GBRL_HIP_METRIC_NONE ? curve.size() : 0, 0.0);
-    float loss = 0.0f;
+    float loss = 0.0f, weight_max = 0.0f;
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_leaf(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
-                                        colsample, seed, objective, metric, leaf_update, leaf_l2, &loss, dsv ? curve.data() : nullptr,
-                                        dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best);
+        rc = gbrl_hip_fit_prepared_weighted(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                            colsample, seed, objective, metric, leaf_update, leaf_l2, static_cast<const float *>(w.ptr), w.on_device,
+                                            static_cast<const float *>(wv.ptr), wv.on_device, &loss, dsv ? curve.data() : nullptr,
+                                            dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max);
     }
     check(rc);
     if (!dsv) return py::float_(loss);
@@ -861,13 +878,14 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
         out["valid_metric"] = vm;
         out["eval_metric"] = metric_obj;
     }
+    if (w.ptr) out["weight_max"] = py::float_(weight_max);
     return std::move(out);
 }
 
 // Extension: Newton leaf values (include/gbrl_hip.h, "Newton leaf values").
-// newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1) -> {'sums': int64 [leaves, 2 D + 1], 'bits', 'values': float32 [leaves, D]}
+// newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1, weights=None, weight_max=None) -> {'sums': int64 [leaves, 2 D + 1], 'bits', 'values': float32 [leaves, D]}
 py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &pred, py::object &targets, const std::string &objective_name, double leaf_l2,
-                                     py::object &rows, int tree) {
+                                     py::object &rows, int tree, py::object &weights, py::object weight_max_obj) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     const int objective = parse_objective(objective_name), D = md.output_dim;
@@ -880,6 +898,10 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
     check_rows_by_outputs(p, "pred", m, D);
     Input t = read_objective_targets(targets, "targets", false, "newton_leaves_prepared", objective, m, D, true);
     if (!t.ptr) fail("Cannot call newton_leaves_prepared without targets!");
+    Input w = read_weights(weights, "weights", "newton_leaves_prepared", m, true);
+    if (!w.ptr && !weight_max_obj.is_none()) fail("newton_leaves_prepared: weight_max needs weights");
+    const float weight_max = weight_max_obj.is_none() ? -1.0f : weight_max_obj.cast<float>();
+    if (!weight_max_obj.is_none() && !(weight_max >= 0.0f)) fail("newton_leaves_prepared: weight_max must be in [0, 65536] (and not NaN)");
     static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
     const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
     // the leaves of the tree (an index outside the model is left to the C ABI's message: one leaf's room is enough for a call that is refused)
@@ -898,8 +920,8 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
     float *vp = values.mutable_data();
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_newton_leaves_prepared(self.h, ds, rp, r.ptr ? r.on_device : 0, m, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, objective,
-                                             tree, leaf_l2, sp, &bits, vp);
+        rc = gbrl_hip_newton_leaves_prepared_weighted(self.h, ds, rp, r.ptr ? r.on_device : 0, m, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device,
+                                                      objective, tree, leaf_l2, static_cast<const float *>(w.ptr), w.on_device, weight_max, sp, &bits, vp);
     }
     check(rc);
     py::dict out;
@@ -910,15 +932,18 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
 }
 
 // the hessian rule on the host: no device, no model (the targets do not enter: accepted and ignored, so that the call reads like the gradient's)
-py::array_t<float> objective_hessian_host_impl(py::object &pred, py::object targets, const std::string &objective_name) {
+py::array_t<float> objective_hessian_host_impl(py::object &pred, py::object targets, const std::string &objective_name, py::object &weights) {
     const int objective = parse_objective(objective_name);
     Input p = read_input(pred, "pred", false, "objective_hessian_host", false);
     if (p.on_device) fail("objective_hessian_host takes NumPy arrays");
     if (p.shape.empty() || p.shape.size() > 2) fail("pred must be a float32 array of shape (n, D) or (n,)");
     const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
+    Input w = read_weights(weights, "weights", "objective_hessian_host", n, true);
+    if (w.on_device) fail("objective_hessian_host takes NumPy arrays");
     py::array_t<float> out(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
     float none = 0.0f;
-    check(gbrl_hip_objective_hessian_host(static_cast<const float *>(p.ptr), n, D, objective, out.size() ? out.mutable_data() : &none));
+    check(gbrl_hip_objective_hessian_host_weighted(static_cast<const float *>(p.ptr), static_cast<const float *>(w.ptr), n, D, objective,
+                                                   out.size() ? out.mutable_data() : &none));
     return out;
 }
 
@@ -977,8 +1002,8 @@ py::tuple eval_metric_host_impl(py::object &pred, py::object &targets, const std
     return py::make_tuple(py::float_(value), counts);
 }
 
-// objective_gradient(pred, targets, objective) -> (grad, loss): NumPy in, NumPy out; a device tuple gives a DLPack capsule on the model's device
-py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name) {
+// objective_gradient(pred, targets, objective, weights=None) -> (grad, loss): NumPy in, NumPy out; a device tuple gives a DLPack capsule on the model's device
+py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights) {
     const gbrl_hip_metadata md = self.meta();
     const int objective = parse_objective(objective_name), D = md.output_dim;
     Input p = read_input(pred, "pred", false, "objective_gradient", false);
@@ -987,6 +1012,7 @@ py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &ta
     check_rows_by_outputs(p, "pred", n, D);
     Input t = read_objective_targets(targets, "targets", false, "objective_gradient", objective, n, D, true);
     if (!t.ptr) fail("Cannot call objective_gradient without targets!");
+    Input w = read_weights(weights, "weights", "objective_gradient", n, true);
     const size_t n_el = std::max<size_t>(static_cast<size_t>(n) * D, 1);
     float *g = nullptr;
     int dev_id = 0;
@@ -1002,7 +1028,8 @@ py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &ta
     int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_objective_gradient(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, n, objective, g, &loss);
+        rc = gbrl_hip_objective_gradient_weighted(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, static_cast<const float *>(w.ptr),
+                                                  w.on_device, n, objective, g, &loss);
     }
     if (rc != GBRL_HIP_OK) {
         if (p.on_device) gbrl_hip_device_free(g); else delete[] g;
@@ -1015,7 +1042,7 @@ py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &ta
 }
 
 // the gradient rule on the host (include/gbrl_hip.h, "Classification objectives"): no device, no model
-py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &targets, const std::string &objective_name) {
+py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights) {
     const int objective = parse_objective(objective_name);
     Input p = read_input(pred, "pred", false, "objective_gradient_host", false);
     if (p.on_device) fail("objective_gradient_host takes NumPy arrays");
@@ -1023,9 +1050,12 @@ py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &ta
     const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
     Input t = read_objective_targets(targets, "targets", false, "objective_gradient_host", objective, n, D, true);
     if (t.on_device) fail("objective_gradient_host takes NumPy arrays");
+    Input w = read_weights(weights, "weights", "objective_gradient_host", n, true);
+    if (w.on_device) fail("objective_gradient_host takes NumPy arrays");
     py::array_t<float> out(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
     float none = 0.0f;
-    check(gbrl_hip_objective_gradient_host(static_cast<const float *>(p.ptr), t.ptr, n, D, objective, out.size() ? out.mutable_data() : &none));
+    check(gbrl_hip_objective_gradient_host_weighted(static_cast<const float *>(p.ptr), t.ptr, static_cast<const float *>(w.ptr), n, D, objective,
+                                                    out.size() ? out.mutable_data() : &none));
     return out;
 }
 
@@ -1218,22 +1248,30 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "sample_rows_host(n, subsample, seed=0, draw=0, row0=0) -> int32 NumPy array [m]\n\n"
           "The row sampler's rule on the host (no device is needed): the rows of [row0, row0 + n) that (seed, draw) keeps at `subsample`, ascending.\n"
           "PreparedDataset.sample_rows returns the same list from the device.");
-    m.def("objective_gradient_host", &objective_gradient_host_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"),
-          "objective_gradient_host(pred, targets, objective) -> float32 NumPy array shaped like pred\n\n"
+    m.def("objective_gradient_host", &objective_gradient_host_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("weights") = py::none(),
+          "objective_gradient_host(pred, targets, objective, weights=None) -> float32 NumPy array shaped like pred\n\n"
           "The gradient rule of fit_prepared(objective=) on the host (no device is needed): 'logistic': sigmoid(p) - y, targets float32 like pred;\n"
           "'softmax': softmax(p) - onehot(y), targets int32 [n] labels in [0, D), D >= 2; 'rmse': p - y.  Every float32 step is the one definition the\n"
-          "kernels use (an exponential written out in fmaf, correctly rounded division): the device gives the same bits.");
+          "kernels use (an exponential written out in fmaf, correctly rounded division): the device gives the same bits.  weights (float32 [n], every\n"
+          "entry finite and in [0, 65536]): fl32(w * g) row by row, one float32 multiply behind the rule; all-ones weights change no bit.");
     m.def("objective_hessian_host", &objective_hessian_host_impl, py::arg("pred"), py::arg("targets") = py::none(), py::arg("objective") = "logistic",
-          "objective_hessian_host(pred, targets, objective) -> float32 NumPy array shaped like pred\n\n"
+          py::arg("weights") = py::none(),
+          "objective_hessian_host(pred, targets, objective, weights=None) -> float32 NumPy array shaped like pred\n\n"
           "The hessian rule of fit_prepared(leaf_update='newton') on the host (no device is needed): 'logistic': fl32(fl32(1 / (1 + e)) * fl32(e / (1 + e))),\n"
           "e = exp(-|p|) as the gradient computes it; 'softmax': q (1 - q) per class, q as the gradient computes it (the diagonal); 'rmse': 1.  The targets\n"
-          "do not enter (None is fine).");
+          "do not enter (None is fine).  weights (float32 [n]): fl32(w * h) row by row.");
     m.def("newton_values_host", &newton_values_host_impl, py::arg("sums"), py::arg("bits"), py::arg("old_values"), py::arg("depths"), py::arg("leaf_l2") = 1.0,
           "newton_values_host(sums, bits, old_values, depths, leaf_l2=1.0) -> float32 [leaves, D]\n\n"
           "The leaf value rule of newton_leaves_prepared on the host: v = (float)((Sg / 2**bits) / (Sh / 2**bits + leaf_l2)) in float64; a leaf with cnt == 0,\n"
           "depth 0 or a denominator that is not positive keeps old_values.  sums int64 [leaves, 2 D + 1] = (Sg, Sh, cnt).");
-    m.def("newton_sum_bits", [](int64_t rows) { return gbrl_hip_newton_sum_bits(rows); }, py::arg("m"),
-          "newton_sum_bits(m) -> min(40, 62 - bit_length(m)): the bits of the quantum newton_leaves_prepared sums m rows in.");
+    m.def("newton_sum_bits", [](int64_t rows, py::object weight_max) {
+              if (weight_max.is_none()) return gbrl_hip_newton_sum_bits(rows);
+              const int bits = gbrl_hip_newton_sum_bits_weighted(rows, weight_max.cast<float>());
+              if (bits < 0) fail(gbrl_hip_last_error());
+              return bits;
+          }, py::arg("m"), py::arg("weight_max") = py::none(),
+          "newton_sum_bits(m, weight_max=None) -> min(40, 62 - bit_length(m) - e): the bits of the quantum newton_leaves_prepared sums m rows in; e is the\n"
+          "smallest integer >= 0 with weight_max <= 2**e (None, or a weight_max up to 1: e = 0).  Refused: a weight_max that is NaN, negative or above 65536.");
     m.def("eval_metric_host", &eval_metric_host_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("metric"),
           "eval_metric_host(pred, targets, objective, metric) -> (value, counts)\n\n"
           "The classifier metrics of fit_prepared(eval_metric=) on the host (no device is needed), as include/gbrl_hip.h defines them.  metric 'error':\n"
@@ -1336,12 +1374,12 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         // likewise: fit_prepared(ds, targets, iterations) -> float keeps its generated line; the validation form is the second overload
         g.def("fit_prepared", [](PyGBRL &self, py::object ds, py::object &targets, int iterations) -> float {
             py::object none = py::none();
-            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0).cast<float>();
+            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0, none, none).cast<float>();
         }, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
             "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,\n"
-            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0) -> float | dict\n\n"
+            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None) -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
             "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
@@ -1386,35 +1424,53 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "kernel, one launch and one read-back per tree), the division is done on the host in float64: the model is byte for byte the loop\n"
             "objective_gradient -> step_prepared -> newton_leaves_prepared -> predict_continue_prepared.  'gradient' is the call without the keyword.\n"
             "Refused before anything changes: an unknown leaf_update, 'newton' with 'rmse', a leaf_l2 that is negative, NaN or infinite, and with\n"
-            "'newton' and 'logistic' a target outside [0, 1].";
+            "'newton' and 'logistic' a target outside [0, 1].\n"
+            "weights=w (float32 [n], NumPy or a device tuple; with everything above): one weight per data set row, every entry finite and in [0, 65536], their\n"
+            "float64 sum W > 0.  The launch that advances the held prediction stores fl32(w * g): the tree is grown on the weighted gradient.  'loss' is\n"
+            "sum w L / W (rmse: sqrt(0.5 sum w L / W)) -- objective_gradient(pred, targets, objective, weights=w)'s loss bit for bit -- and a fresh model's bias is\n"
+            "the weighted mean (its log odds; the weighted log class frequencies).  'newton' leaves store sum w g / (sum w h + leaf_l2), the sums' quantum with room\n"
+            "for the largest weight ('weight_max' of the dict; gbrl_cpp.newton_sum_bits(m, weight_max)).  valid_weights=wv (float32 [valid rows]) weigh\n"
+            "'valid_loss' alone.  All-ones weights give the model, the valid_loss and the loss of the call without the keyword (the rmse loss to one float32 ulp:\n"
+            "it is summed by rows).  What weights do NOT do: the split scores see weighted gradients, but their row counts (L2's sum^2 / count,\n"
+            "min_data_in_leaf) are unchanged; a gradient leaf stores the mean of w g over its rows, so weights act as gradient multipliers and weights with\n"
+            "mean 1 keep the step size; a zero-weight row still counts as a row of its leaf (to drop rows use subsample or step_prepared(rows=)); the metrics\n"
+            "stay unweighted.  Refused before anything changes: an entry that is NaN, negative, infinite or above 65536 (the row is named), W == 0, a wrong\n"
+            "length or dtype, valid_weights without valid=, valid_weights with eval_metric (not supported).";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
               py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse", py::arg("eval_metric") = py::none(),
-              py::arg("leaf_update") = "gradient", py::arg("leaf_l2") = 1.0);
+              py::arg("leaf_update") = "gradient", py::arg("leaf_l2") = 1.0, py::arg("weights") = py::none(), py::arg("valid_weights") = py::none());
     }
     g.def("newton_leaves_prepared", &newton_leaves_prepared_impl, py::arg("ds"), py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("leaf_l2") = 1.0,
-          py::arg("rows") = py::none(), py::arg("tree") = -1,
-          "newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1) -> dict\n\n"
+          py::arg("rows") = py::none(), py::arg("tree") = -1, py::arg("weights") = py::none(), py::arg("weight_max") = py::none(),
+          "newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1, weights=None, weight_max=None) -> dict\n\n"
           "The leaves of ONE tree (tree=-1: the last) set to sum g / (sum h + leaf_l2) over the data set rows `rows` (None: every row): what\n"
           "fit_prepared(leaf_update='newton') does after every step.  pred [m, output_dim] is the prediction over the trees before that tree and, like\n"
           "targets (float32 [m, output_dim]; int32 [m] labels for 'softmax'), is indexed by position.  Returns 'sums' (int64 [leaves, 2 D + 1]: Sg, Sh, cnt\n"
           "per leaf, with q(x) = llrint(x * 2**bits)), 'bits' and 'values' (float32 [leaves, D], what the model now holds:\n"
           "gbrl_cpp.newton_values_host(sums, bits, old values, depths, leaf_l2)).  Integer sums: two calls, and both kernel families, give the same bytes.\n"
           "A leaf without rows, of depth 0 or with sum h + leaf_l2 <= 0 keeps its value.  Refused with the model unchanged: 'rmse', a bad leaf_l2, a tree\n"
-          "outside the model, a logistic target outside [0, 1], a prediction that is not finite.");
+          "outside the model, a logistic target outside [0, 1], a prediction that is not finite.\n"
+          "weights (float32 [m], indexed by position like pred): the sums take q(fl32(w * g)) and q(fl32(w * h)), cnt counts rows, and bits =\n"
+          "gbrl_cpp.newton_sum_bits(m, weight_max).  weight_max=None: the largest of the weights given; a loop over sampled rows passes the maximum of the\n"
+          "whole data set's weights and gets fit_prepared's bits.  Refused: a bad weight (the row is named), a weight_max below the largest weight given or\n"
+          "above 65536, weight_max without weights.");
     g.def("eval_metric", &eval_metric_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("metric"),
           "eval_metric(pred, targets, objective, metric) -> (value, counts)\n\n"
           "gbrl_cpp.eval_metric_host(pred, targets, objective, metric) computed on the model's device: the same integers (counts, int64) and therefore the\n"
           "same value, bit for bit.  pred [n, output_dim] and targets are NumPy arrays or device tuples.  'error' is one launch; 'auc' sorts the score\n"
           "columns with a segmented radix sort, prefix-counts the negatives and sums ranks with integer atomics: two calls give the same bytes.");
-    g.def("objective_gradient", &objective_gradient_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"),
-          "objective_gradient(pred, targets, objective) -> (grad, loss)\n\n"
+    g.def("objective_gradient", &objective_gradient_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("weights") = py::none(),
+          "objective_gradient(pred, targets, objective, weights=None) -> (grad, loss)\n\n"
           "The gradient dL/dp [n, output_dim] and the loss of the raw scores pred under objective 'rmse' | 'logistic' | 'softmax', computed on the model's\n"
           "device by the device functions fit_prepared(objective=) runs: grad is gbrl_cpp.objective_gradient_host(pred, targets, objective) bit for bit.\n"
           "targets: float32 [n, output_dim] (rmse, logistic) or int32 [n] labels (softmax).  NumPy in, NumPy out; a device tuple for pred gives a DLPack\n"
-          "capsule.  loss: the mean row loss in float64 (rmse: the MultiRMSE expression), reduced in a fixed order: two calls give the same bits.");
+          "capsule.  loss: the mean row loss in float64 (rmse: the MultiRMSE expression), reduced in a fixed order: two calls give the same bits.\n"
+          "weights (float32 [n], NumPy or a device tuple, every entry finite and in [0, 65536], sum > 0): grad = fl32(w * g) row by row and loss =\n"
+          "sum w L / W with W the float64 sum of the weights in a fixed order (rmse: sqrt(0.5 sum w L / W)); the weight is one more float per row in the\n"
+          "same launch.  Refused: a bad entry (the row is named), weights that sum to 0, a wrong length or dtype.");
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);
     }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("return_torch") = false);

@@ -563,24 +563,29 @@ int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset
     });
 }
 
-// The one body of the six gbrl_hip_fit_prepared* spellings.  valid_required (gbrl_hip_fit_prepared_valid): a NULL valid_ds is a null data set;
+// The one body of the seven gbrl_hip_fit_prepared* spellings.  valid_required (gbrl_hip_fit_prepared_valid): a NULL valid_ds is a null data set;
 // otherwise it means "no validation", the other validation arguments must then be at their defaults, *iterations_done = iterations and
 // *best_n_trees is left alone.  Every refusal that needs no data set comes before a handle is resolved, the validation handle before the
 // training handle, and nothing is written on a refusal.
 static int fit_prepared_call(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations, bool valid_required,
                              const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds, double min_delta,
                              const gbrl::FitOptions &opt, float *loss_out, double *valid_loss_out, int *iterations_done, int *best_n_trees,
-                             double *valid_metric_out = nullptr) {
+                             double *valid_metric_out = nullptr, const float *valid_weights = nullptr, int valid_weights_on_device = 0,
+                             float *weight_max_out = nullptr) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");
-        gbrl::Engine::FitValid v{nullptr, valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0, valid_metric_out};
+        gbrl::Engine::FitValid v{nullptr, valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0, valid_metric_out,
+                                 valid_weights, valid_weights_on_device != 0};
         gbrl::Engine::FitValid *valid = valid_required || valid_ds != nullptr ? &v : nullptr;
         m->engine.precheck_fit(targets, iterations, opt, valid);
         if (!valid && (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr || valid_metric_out != nullptr))
             throw gbrl::InvalidArgument("fit_prepared: valid_targets, early_stopping_rounds, min_delta and valid_loss_out need a validation set");
+        if (!valid && valid_weights != nullptr) throw gbrl::InvalidArgument("fit_prepared: valid_weights need a validation set (valid=)");
         if (valid) v.ds = &live_dataset(valid_ds);
-        const float loss = m->engine.fit_prepared(&live_dataset(ds), targets, targets_on_device != 0, iterations, opt, valid);
+        float weight_max = 0.0f;
+        const float loss = m->engine.fit_prepared(&live_dataset(ds), targets, targets_on_device != 0, iterations, opt, valid, &weight_max);
         if (loss_out) *loss_out = loss;
+        if (weight_max_out) *weight_max_out = weight_max;
         if (iterations_done) *iterations_done = valid ? v.done : iterations;
         if (valid && best_n_trees) *best_n_trees = v.best_n_trees;
     });
@@ -691,19 +696,52 @@ int gbrl_hip_fit_prepared_leaf(gbrl_hip_model *m, const gbrl_hip_dataset *ds, co
                              valid_metric_out);
 }
 
-int gbrl_hip_newton_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,
-                                    int pred_on_device, const void *targets, int targets_on_device, int objective, int tree, double leaf_l2, int64_t *sums_out,
-                                    int *bits_out, float *values_out) {
+// ---- row weights: the weighted spellings; the older ones forward without weights
+static_assert(gbrl::kern::kWeightMax == GBRL_HIP_WEIGHT_MAX, "the kernels' largest weight is the header's");
+int gbrl_hip_fit_prepared_weighted(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                                   const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                   double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update, double leaf_l2,
+                                   const float *weights, int weights_on_device, const float *valid_weights, int valid_weights_on_device, float *loss_out,
+                                   double *valid_loss_out, double *valid_metric_out, int *iterations_done, int *best_n_trees, float *weight_max_out) {
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, colsample, seed, objective, metric, leaf_update, leaf_l2, weights, weights_on_device != 0}, loss_out, valid_loss_out,
+                             iterations_done, best_n_trees, valid_metric_out, valid_weights, valid_weights_on_device, weight_max_out);
+}
+
+int gbrl_hip_newton_leaves_prepared_weighted(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,
+                                             int pred_on_device, const void *targets, int targets_on_device, int objective, int tree, double leaf_l2,
+                                             const float *weights, int weights_on_device, float weight_max, int64_t *sums_out, int *bits_out, float *values_out) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");
         m->engine.precheck_prepared("newton_leaves_prepared");
         m->engine.newton_leaves_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, pred, pred_on_device != 0, targets, targets_on_device != 0, objective,
-                                         tree, leaf_l2, sums_out, bits_out, values_out);
+                                         tree, leaf_l2, sums_out, bits_out, values_out, weights, weights_on_device != 0, weight_max);
     });
 }
 
+int gbrl_hip_newton_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,
+                                    int pred_on_device, const void *targets, int targets_on_device, int objective, int tree, double leaf_l2, int64_t *sums_out,
+                                    int *bits_out, float *values_out) {
+    return gbrl_hip_newton_leaves_prepared_weighted(m, ds, rows, rows_on_device, n_rows, pred, pred_on_device, targets, targets_on_device, objective, tree, leaf_l2,
+                                                    nullptr, 0, -1.0f, sums_out, bits_out, values_out);
+}
+
+int gbrl_hip_objective_hessian_host_weighted(const float *pred, const float *weights, int n, int D, int objective, float *hess_out) {
+    return guarded([&] { gbrl::Engine::objective_hessian_host(pred, n, D, objective, hess_out, weights); });
+}
+
 int gbrl_hip_objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out) {
-    return guarded([&] { gbrl::Engine::objective_hessian_host(pred, n, D, objective, hess_out); });
+    return gbrl_hip_objective_hessian_host_weighted(pred, nullptr, n, D, objective, hess_out);
+}
+
+int gbrl_hip_newton_sum_bits_weighted(int64_t m, float weight_max) {
+    int bits = 0;
+    const int rc = guarded([&] {
+        if (gbrl::kern::obj_weight_bad(weight_max))
+            throw gbrl::InvalidArgument("newton_sum_bits: weight_max must be a finite number in [0, 65536], got " + std::to_string(weight_max));
+        bits = gbrl::kern::newton_sum_bits(static_cast<long long>(m), weight_max);
+    });
+    return rc == GBRL_HIP_OK ? bits : rc;
 }
 
 int gbrl_hip_newton_values_host(const int64_t *sums, int n_leaves, int D, int bits, const float *old_values, const int32_t *depths, double leaf_l2,
@@ -725,16 +763,25 @@ int gbrl_hip_eval_metric_host(const float *pred, const void *targets, int n, int
     return guarded([&] { gbrl::Engine::eval_metric_host(pred, targets, n, D, objective, metric, value_out, counts_out); });
 }
 
-int gbrl_hip_objective_gradient(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective,
-                                float *grad_out, double *loss_out) {
+int gbrl_hip_objective_gradient_weighted(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, const float *weights,
+                                         int weights_on_device, int n, int objective, float *grad_out, double *loss_out) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");
-        m->engine.objective_gradient(pred, pred_on_device != 0, targets, targets_on_device != 0, n, objective, grad_out, loss_out);
+        m->engine.objective_gradient(pred, pred_on_device != 0, targets, targets_on_device != 0, n, objective, grad_out, loss_out, weights, weights_on_device != 0);
     });
 }
 
+int gbrl_hip_objective_gradient(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, int n, int objective,
+                                float *grad_out, double *loss_out) {
+    return gbrl_hip_objective_gradient_weighted(m, pred, pred_on_device, targets, targets_on_device, nullptr, 0, n, objective, grad_out, loss_out);
+}
+
+int gbrl_hip_objective_gradient_host_weighted(const float *pred, const void *targets, const float *weights, int n, int D, int objective, float *grad_out) {
+    return guarded([&] { gbrl::Engine::objective_gradient_host(pred, targets, n, D, objective, grad_out, weights); });
+}
+
 int gbrl_hip_objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out) {
-    return guarded([&] { gbrl::Engine::objective_gradient_host(pred, targets, n, D, objective, grad_out); });
+    return gbrl_hip_objective_gradient_host_weighted(pred, targets, nullptr, n, D, objective, grad_out);
 }
 
 int gbrl_hip_objective_exp_host(const float *t, int n, double *out, float *out_f32) {

@@ -131,6 +131,7 @@ struct CatItem { int feat; int next; uint64_t lhash; size_t std_hash; char name[
 struct FitOptions {
     double subsample = 1.0, colsample = 1.0; uint64_t seed = 0; int objective = 0 /* kern::kObjRmse */; int metric = 0 /* kern::kMetricNone */;
     int leaf_update = 0 /* kern::kLeafGradient; 1: kern::kLeafNewton */; double leaf_l2 = 1.0;
+    const float *weights = nullptr /* float32 [n], one per data set row; nullptr: the loop without weights */; bool weights_dev = false;
 };
 
 class Engine {
@@ -207,6 +208,16 @@ class Engine {
     //              leaf_l2) over the rows the tree was grown on -- the batch, or the kept rows of a sampled iteration -- by newton_leaves_prepared's
     //              body on the held prediction (one launch, one read-back, the tree's value slice of the mirror sent again); the held predictions,
     //              the validation walk and the loss then see those values.  gradient enqueues nothing: the loop is the one without the option.
+    //   weights    (objective_core.h, newton_core.h: row weights)  FitOptions::weights float32 [n], FitValid::weights [valid->ds->n].  The held
+    //              prediction's launch stores fl32(w * g): the tree is grown on the weighted gradient, with the row counts of the split scores and
+    //              min_data_in_leaf unchanged, and a gradient leaf stores the mean of w g over its rows.  newton: sum w g / (sum w h + leaf_l2), the
+    //              quantum with room for the largest training weight of the data set.  The loss is sum w L / W, W the float64 sum of the weights in
+    //              a fixed order (kern::weight_stats); a weighted rmse run takes it from the held prediction by the weighted objective_rows
+    //              partials (the column sums of G hold (w g)^2).  A fresh model's bias: sum w y / W per column (kern::column_sums_weighted: the
+    //              order of column_sums, so all-ones weights give the unweighted bits); its log odds, the clamp 0.5 / n kept; log(max(W_c, 0.5 W / n)
+    //              / W), W_c the weight of class c.  valid->weights weigh valid->loss_out only; the metrics count rows (with a metric: Unsupported).
+    //              A weight vector is checked once per call before anything changes (a NaN, negative, infinite entry or one above kWeightMax,
+    //              naming the first row; W == 0).  No weights: the kernels and arguments of the call as it always was.
     // Refused before anything changes, in this order: precheck_fit's list; ds, then valid->ds, absent or not this model's (check_prepared_dataset);
     // another thresholds id; null valid->loss_out; a tree whose conditions the codes cannot express (Unsupported); softmax: a label outside [0, D)
     // in either set (InvalidArgument naming the first one found).
@@ -214,8 +225,10 @@ class Engine {
         const PreparedDataset *ds; const void *targets; bool targets_dev; int rounds; double min_delta;
         double *loss_out /*[iterations + 1]*/; int done, best_n_trees;
         double *metric_out = nullptr /*[iterations + 1]; with FitOptions::metric*/;
+        const float *weights = nullptr /*float32 [ds->n]: loss_out is the weighted loss*/; bool weights_dev = false;
     };
-    float fit_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, const FitOptions &opt = {}, FitValid *valid = nullptr);
+    float fit_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, const FitOptions &opt = {}, FitValid *valid = nullptr,
+                       float *weight_max_out = nullptr);
     // What fit_prepared refuses without a data set in hand, in this order (the C ABI runs it before it resolves the handles, so that these
     // refusals do not depend on a data set being at hand; valid->ds is not looked at): the model checks of step_prepared; null targets;
     // iterations < 0; batch_size <= 0; max_depth > 32, n_bins outside [1, 65534], output_dim > 128 (Unsupported); check_subsample;
@@ -243,7 +256,14 @@ class Engine {
     // objective_gradient: grad_out [n][D] = dL/dp and / or *loss_out = the loss of pred [n][D] against targets under the objective, on the model's
     // device and stream with D = output_dim (kern::objective_rows: the device functions of the code walk's tails).  grad_out is where pred is
     // (device iff pred_dev); either output may be null, not both.  kObjRmse: g = fl32(p - y) and staged_loss's expression.
-    void objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out);
+    // weights (nullable, float32 [n]): grad_out = fl32(w * g), the loss sum w L / W (rmse: sqrt(0.5 sum w L / W)); checked as fit_prepared checks them.
+    void objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out,
+                            const float *weights = nullptr, bool weights_dev = false);
+    // Extension: row weights.  The checks of a weight vector on the host (InvalidArgument naming the first refused row); on the device the same
+    // through kern::weight_stats, with the largest weight and W = the float64 sum in its fixed order (need_sum: W == 0 is refused too).
+    static void check_weights_host(const char *what, const float *weights, int n);
+    struct WeightStats { float max = 0.0f; double sum = 0.0; };
+    WeightStats check_weights(const char *what, const float *d_weights, int n, bool need_sum);
     // Extension: classifier metrics (metric_core.h has the definitions).  eval_metric: the error rate or the exact AUC of pred [n][D] against
     // targets under the objective, on the model's device and stream: integer counts from kern::metric_error / kern::metric_auc, the value from
     // them on the host.  counts (nullable): [D][3] = (2U_d, P_d, N_d) for auc, [D] (softmax: [1]) for error.  eval_metric_host: the same by
@@ -262,16 +282,21 @@ class Engine {
     // about the model, the data set and rows; output_dim > 128; the rmse objective (its Newton step is the gradient mean: InvalidArgument); a
     // leaf_l2 that is negative, NaN or infinite; a tree outside the model; a softmax label outside [0, D).  Refused after the launch, the model
     // unchanged (InvalidArgument): a logistic target outside [0, 1] (a NaN counts), a prediction that is not finite.
+    // weights (nullable, float32 [m], indexed by position): Sg += q(fl32(w g)), Sh += q(fl32(w h)), bits = newton_sum_bits(m, weight_max); weight_max < 0:
+    // the largest of the weights given; otherwise it must be at least that and at most kWeightMax (a caller's loop over sampled rows passes the
+    // maximum of the whole data set and gets fit_prepared's bits).  A weight_max >= 0 without weights is refused.
     void newton_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *pred, bool pred_dev, const void *targets,
-                                bool targets_dev, int objective, int tree, double leaf_l2, int64_t *sums_out, int *bits_out, float *values_out);
+                                bool targets_dev, int objective, int tree, double leaf_l2, int64_t *sums_out, int *bits_out, float *values_out,
+                                const float *weights = nullptr, bool weights_dev = false, float weight_max = -1.0f);
     static void check_leaf_update(const char *what, int objective, int leaf_update, double leaf_l2);   // unknown update, newton with rmse, a bad leaf_l2
     // the hessian rule on the host (no device): out [n][D] = obj_logistic_hess(p) / the diagonal softmax hessian q (1 - q); targets are not read
-    static void objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out);
+    static void objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out, const float *weights = nullptr /*[n]: fl32(w * h)*/);
     // the value rule on the host (no device): sums int64 [leaves][2 D + 1], old_values float32 [leaves][D], depths int32 [leaves] -> values_out [leaves][D]
     static void newton_values_host(const int64_t *sums, int n_leaves, int D, int bits, const float *old_values, const int32_t *depths, double leaf_l2,
                                    float *values_out);
     // the gradient rule on the host (no device): the same bits
-    static void objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out);
+    static void objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out,
+                                        const float *weights = nullptr /*[n]: fl32(w * g)*/);
     // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
     // min_delta (a NaN never improves); *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = best at that point
     static void early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
@@ -511,6 +536,7 @@ class Engine {
     DevBuf d_fp_pred_, d_fp_grads_, d_fp_iota_, d_fp_targets_;   // fit_prepared: held prediction [n][D], batch gradients, 0..n-1, staged targets
     DevBuf d_fp_vpred_, d_fp_vtargets_, d_fp_vpart_, d_fp_vsums_;   // its validation rows: held prediction [n_v][D], staged targets, loss partials, one sum per iteration
     DevBuf d_fp_srows_, d_fp_sgrads_, d_fp_sscratch_;   // its sampled iterations: the kept rows of the batch, their gradient rows, block counts + m
+    DevBuf d_obj_weights_, d_fp_weights_, d_fp_vweights_, d_wstat_, d_wpart_, d_wsum_;   // row weights: staged vectors; kern::weight_stats' two ints, partials and sum
     DevBuf d_obj_pred_, d_obj_targets_, d_obj_grad_, d_obj_part_, d_obj_sum_, d_obj_counts_;   // objective_gradient: staged inputs, the gradient, loss partials and sum; class counts + first bad row
     DevBuf d_met_counts_, d_met_scratch_, d_fp_vmetric_;   // eval_metric: the integer counters, the AUC pipeline's scratch; fit_prepared: the metric's counters per iteration
     struct Held;     // engine_fit_prepared.hip: a data set's rows carried through the model's trees, batch by batch
@@ -520,15 +546,17 @@ class Engine {
     // rows [start, start + bn) of a held prediction (one batch of it, or a part of one) advanced to every tree the model has, with the gradient
     // tail (targets, grad_out) and / or the loss tail (loss_targets, loss_part) of kern::predict_continue_codes; targets are [n][D] (softmax:
     // one int32 label per row behind the float pointers)
+    // weights (nullable): device [n], one per row of the held data set, for whichever tail is on
     void advance_held(Held &h, int start, int bn, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
-                      int objective);
+                      int objective, const float *weights = nullptr);
     // the partials of a loss tail summed into *d_sum (kern::staged_loss_finish) and, with host_sum, its 8 bytes on their way to the host: they
     // are there after the caller's wait for the stream
     void finish_loss_sum(const double *d_part, int n_part, double *d_sum, double *host_sum);
     // newton_leaves_prepared behind its argument checks and input staging (fit_prepared's loop body too): device pred / targets, indexed by the
     // position or (abs_index) by the data set row; the phase newton_leaves joins the caller's phase list
     void newton_leaves_run(const char *what, const PreparedDataset *ds, const kern::CodeRows &cr, int m, const float *d_pred, const void *d_targets, bool abs_index,
-                           int objective, int t, double leaf_l2, bool generic, int64_t *sums_out, int *bits_out, float *values_out);
+                           int objective, int t, double leaf_l2, bool generic, int64_t *sums_out, int *bits_out, float *values_out,
+                           const float *d_weights = nullptr, float weight_max = 0.0f);   // (weights indexed like d_pred)
     DevBuf d_newton_acc_;                         // its int64 sums [leaves][2 D + 1] and the flag word
     std::vector<unsigned long long> newton_host_;   // ... read back
     // Column sums in float64 of device rows [rows][D] and the MultiRMSE built on them, as fit() and fit_prepared() compute the bias and the loss
@@ -536,6 +564,8 @@ class Engine {
     struct ColumnStats {
         explicit ColumnStats(Engine &e);
         const std::vector<double> &sums(const float *g, int rows, const float *center);   // column sums (center null) or sums of squares about center; waits for the stream
+        // sum_i factor[i] * g[i, d] in the same order (kern::column_sums_weighted); g null: the one-hot matrix of labels
+        const std::vector<double> &weighted_sums(const float *g, const int32_t *labels, const float *factor, int rows);
         float rmse(const float *grads_dev, int rows);                                      // MultiRMSE, loss.cpp:42-56: sqrt(0.5 * sum g^2 / rows)
         Engine &e_;
         const int D_;

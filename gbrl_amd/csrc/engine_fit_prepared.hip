@@ -16,6 +16,9 @@
 //   Engine::newton_leaves_prepared     one tree's leaves set to sum g / (sum h + leaf_l2) over a data set's rows (newton_core.h; kern::newton_leaf_sums), the
 //                                      rules on the host beside it (objective_hessian_host, newton_values_host); fit_prepared(leaf_update = newton) runs its
 //                                      body after every step
+//   Engine::check_weights[_host]       row weights (objective_core.h, newton_core.h): a weight vector's refusals, its maximum and its float64 sum in a fixed order
+//                                      (kern::weight_stats), once per call and vector; the weighted forms of the gradient, the loss, the bias and the Newton
+//                                      sums ride in the launches above as one more per-row operand
 //   Engine::eval_metric[_host]         the error rate and the exact AUC of a prediction matrix (metric_core.h), on the device and on the host
 //
 // The rule.  code(r, f) = #{b : thr[f][b] < obs[r, f]} (-0.0 == +0.0; NaN lies below every threshold: code 0).  For a condition x > v whose v
@@ -228,11 +231,47 @@ void Engine::check_labels(const char *what, const int32_t *d_labels, int n, int 
     if (counts) counts->assign(h.begin(), h.begin() + D);
 }
 
-void Engine::objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out) {
+void Engine::check_weights_host(const char *what, const float *weights, int n) {
+    for (int r = 0; r < n; ++r)
+        if (kern::obj_weight_bad(weights[r]))
+            throw InvalidArgument(std::string(what) + ": weight " + std::to_string(weights[r]) + " (row " + std::to_string(r) + ") is not a finite number in [0, 65536]");
+}
+
+Engine::WeightStats Engine::check_weights(const char *what, const float *d_weights, int n, bool need_sum) {
+    hipStream_t s = stream_;
+    int32_t h[2] = {0x7fffffff, 0};
+    int32_t *d = upload(d_wstat_, h, 2, "H2D weight statistics");
+    double *d_part = static_cast<double *>(d_wpart_.ensure(sizeof(double) * kern::staged_loss_partials(n)));
+    double *d_sum = static_cast<double *>(d_wsum_.ensure(sizeof(double)));
+    kern::weight_stats(d_weights, n, d, d_part, d_sum, s);
+    WeightStats st;
+    hip_check(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s), "D2H weight statistics");
+    hip_check(hipMemcpyAsync(&st.sum, d_sum, sizeof(double), hipMemcpyDeviceToHost, s), "D2H weight sum");
+    hip_check(hipStreamSynchronize(s), "sync");
+    if (h[0] != 0x7fffffff) {
+        float bad = 0.0f;
+        hip_check(hipMemcpyAsync(&bad, d_weights + h[0], sizeof(bad), hipMemcpyDeviceToHost, s), "D2H weight");
+        hip_check(hipStreamSynchronize(s), "sync");
+        throw InvalidArgument(std::string(what) + ": weight " + std::to_string(bad) + " (row " + std::to_string(h[0]) + ") is not a finite number in [0, 65536]");
+    }
+    std::memcpy(&st.max, &h[1], sizeof(float));
+    if (need_sum && !(st.sum > 0.0)) throw InvalidArgument(std::string(what) + ": the weights sum to 0: no weighted loss or bias is defined");
+    return st;
+}
+
+namespace {
+void weigh_rows(float *x, const float *weights, int n, int D) {
+    for (int r = 0; r < n; ++r)
+        for (int d = 0; d < D; ++d) x[static_cast<size_t>(r) * D + d] = kern::obj_weighted(weights[r], x[static_cast<size_t>(r) * D + d]);
+}
+}  // namespace
+
+void Engine::objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out, const float *weights) {
     if (pred == nullptr || targets == nullptr || grad_out == nullptr) throw InvalidArgument("objective_gradient_host: null argument");
     if (n <= 0) throw InvalidArgument("objective_gradient_host: no rows (n must be positive)");
     if (D < 1) throw InvalidArgument("objective_gradient_host: output_dim must be positive");
     check_objective("objective_gradient_host", objective, D);
+    if (weights) check_weights_host("objective_gradient_host", weights, n);
     const size_t n_el = static_cast<size_t>(n) * D;
     if (objective == kern::kObjSoftmax) {
         const int32_t *labels = static_cast<const int32_t *>(targets);
@@ -244,6 +283,7 @@ void Engine::objective_gradient_host(const float *pred, const void *targets, int
             float *row = grad_out + static_cast<size_t>(r) * D;
             kern::obj_softmax_grad_row(row, D, labels[r]);
         }
+        if (weights) weigh_rows(grad_out, weights, n, D);
         return;
     }
     const float *y = static_cast<const float *>(targets);
@@ -251,13 +291,13 @@ void Engine::objective_gradient_host(const float *pred, const void *targets, int
         for (size_t i = 0; i < n_el; ++i) grad_out[i] = kern::obj_logistic_grad(pred[i], y[i]);
     else
         for (size_t i = 0; i < n_el; ++i) grad_out[i] = pred[i] - y[i];
+    if (weights) weigh_rows(grad_out, weights, n, D);
 }
 
 namespace {
 // the mean loss of an objective from the sum of its row losses: rmse is staged_loss's expression
-double mean_loss(int objective, double sum, int rows) {
-    return objective == kern::kObjRmse ? std::sqrt(0.5 * sum / static_cast<double>(rows)) : sum / static_cast<double>(rows);
-}
+// (rows: the row count, or with weights their float64 sum W)
+double mean_loss(int objective, double sum, double rows) { return objective == kern::kObjRmse ? std::sqrt(0.5 * sum / rows) : sum / rows; }
 }  // namespace
 
 void Engine::finish_loss_sum(const double *d_part, int n_part, double *d_sum, double *host_sum) {
@@ -265,7 +305,8 @@ void Engine::finish_loss_sum(const double *d_part, int n_part, double *d_sum, do
     if (host_sum) hip_check(hipMemcpyAsync(host_sum, d_sum, sizeof(double), hipMemcpyDeviceToHost, stream_), "D2H loss");
 }
 
-void Engine::objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out) {
+void Engine::objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out,
+                                const float *weights, bool weights_dev) {
     const int D = model.meta.output_dim;
     if (pred == nullptr || targets == nullptr) throw InvalidArgument("objective_gradient: null argument");
     if (grad_out == nullptr && loss_out == nullptr) throw InvalidArgument("objective_gradient: no place for a result");
@@ -278,17 +319,19 @@ void Engine::objective_gradient(const float *pred, bool pred_dev, const void *ta
     const float *dp = pred_dev ? pred : upload(d_obj_pred_, pred, n_el, "H2D predictions");
     const float *dt = targets_dev ? static_cast<const float *>(targets) : upload(d_obj_targets_, static_cast<const float *>(targets), tar_el, "H2D targets");
     if (objective == kern::kObjSoftmax) check_labels("objective_gradient", reinterpret_cast<const int32_t *>(dt), n, D, nullptr);
+    const float *dw = weights == nullptr ? nullptr : (weights_dev ? weights : upload(d_obj_weights_, weights, static_cast<size_t>(n), "H2D weights"));
+    const double rows = dw ? check_weights("objective_gradient", dw, n, true).sum : static_cast<double>(n);
     float *dg = grad_out == nullptr ? nullptr : (pred_dev ? grad_out : static_cast<float *>(d_obj_grad_.ensure(sizeof(float) * n_el)));
     const int nb = kern::staged_loss_partials(n);
     double *dpart = loss_out ? static_cast<double *>(d_obj_part_.ensure(sizeof(double) * nb)) : nullptr;
     double *dsum = loss_out ? static_cast<double *>(d_obj_sum_.ensure(sizeof(double))) : nullptr;
-    kern::objective_rows(objective, dp, dt, n, D, dg, dpart, s);
+    kern::objective_rows(objective, dp, dt, n, D, dg, dpart, s, dw);
     double sum = 0.0;
     if (loss_out) finish_loss_sum(dpart, nb, dsum, &sum);
     if (grad_out && !pred_dev) hip_check(hipMemcpyAsync(grad_out, dg, sizeof(float) * n_el, hipMemcpyDeviceToHost, s), "D2H gradient");
     hip_check(hipGetLastError(), "objective_gradient kernels");
     hip_check(hipStreamSynchronize(s), "sync");
-    if (loss_out) *loss_out = mean_loss(objective, sum, n);
+    if (loss_out) *loss_out = mean_loss(objective, sum, rows);
 }
 
 // ---- Newton leaf values: the checks, the rules on the host, one tree's sums on the device and the values from them
@@ -301,11 +344,12 @@ void Engine::check_leaf_update(const char *what, int objective, int leaf_update,
         throw InvalidArgument(std::string(what) + ": newton leaf values with the rmse objective are the gradient means the step already stores (use logistic or softmax)");
 }
 
-void Engine::objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out) {
+void Engine::objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out, const float *weights) {
     if (pred == nullptr || hess_out == nullptr) throw InvalidArgument("objective_hessian_host: null argument");
     if (n <= 0) throw InvalidArgument("objective_hessian_host: no rows (n must be positive)");
     if (D < 1) throw InvalidArgument("objective_hessian_host: output_dim must be positive");
     check_objective("objective_hessian_host", objective, D);
+    if (weights) check_weights_host("objective_hessian_host", weights, n);
     const size_t n_el = static_cast<size_t>(n) * D;
     if (objective == kern::kObjRmse) {
         std::fill(hess_out, hess_out + n_el, 1.0f);
@@ -319,6 +363,7 @@ void Engine::objective_hessian_host(const float *pred, int n, int D, int objecti
             kern::obj_softmax_grad_hess_row(row, h, D, 0);
         }
     }
+    if (weights) weigh_rows(hess_out, weights, n, D);
 }
 
 void Engine::newton_values_host(const int64_t *sums, int n_leaves, int D, int bits, const float *old_values, const int32_t *depths, double leaf_l2, float *values_out) {
@@ -335,7 +380,8 @@ void Engine::newton_values_host(const int64_t *sums, int n_leaves, int D, int bi
 }
 
 void Engine::newton_leaves_run(const char *what, const PreparedDataset *ds, const kern::CodeRows &cr, int m, const float *d_pred, const void *d_targets, bool abs_index,
-                               int objective, int t, double leaf_l2, bool generic, int64_t *sums_out, int *bits_out, float *values_out) {
+                               int objective, int t, double leaf_l2, bool generic, int64_t *sums_out, int *bits_out, float *values_out, const float *d_weights,
+                               float weight_max) {
     const gbrl_hip_metadata &md = model.meta;
     hipStream_t s = stream_;
     const int D = md.output_dim, T = md.n_trees;
@@ -349,9 +395,9 @@ void Engine::newton_leaves_run(const char *what, const PreparedDataset *ds, cons
     phase_begin();
     unsigned long long *dacc = static_cast<unsigned long long *>(d_newton_acc_.ensure(sizeof(unsigned long long) * words));
     hip_check(hipMemsetAsync(dacc, 0, sizeof(unsigned long long) * words, s), "zero leaf sums");
-    const int bits = kern::newton_sum_bits(m);
-    const bool streamed =
-        kern::newton_leaf_sums(mirror_view(), ct, cr, m, t, static_cast<int>(leaf0), static_cast<int>(NL), d_pred, d_targets, abs_index, objective, bits, dacc, generic, s);
+    const int bits = d_weights ? kern::newton_sum_bits(m, weight_max) : kern::newton_sum_bits(m);
+    const bool streamed = kern::newton_leaf_sums(mirror_view(), ct, cr, m, t, static_cast<int>(leaf0), static_cast<int>(NL), d_pred, d_targets, abs_index, objective,
+                                                 bits, dacc, generic, s, d_weights);
     newton_host_.resize(words);
     hip_check(hipMemcpyAsync(newton_host_.data(), dacc, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, s), "D2H leaf sums");
     phase_end("newton_leaves");
@@ -384,7 +430,8 @@ void Engine::newton_leaves_run(const char *what, const PreparedDataset *ds, cons
 }
 
 void Engine::newton_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *pred, bool pred_dev, const void *targets,
-                                    bool targets_dev, int objective, int tree, double leaf_l2, int64_t *sums_out, int *bits_out, float *values_out) {
+                                    bool targets_dev, int objective, int tree, double leaf_l2, int64_t *sums_out, int *bits_out, float *values_out,
+                                    const float *weights, bool weights_dev, float weight_max) {
     const gbrl_hip_metadata &md = model.meta;
     const int D = md.output_dim, T = md.n_trees;
     check_prepared_dataset("newton_leaves_prepared", ds);
@@ -400,6 +447,9 @@ void Engine::newton_leaves_prepared(const PreparedDataset *ds, const int32_t *ro
     if (rows == nullptr && m != ds->n)
         throw InvalidArgument("newton_leaves_prepared: pred has " + std::to_string(m) + " rows, the data set " + std::to_string(ds->n) + " (pass rows to sum over a subset)");
     if (rows != nullptr && !rows_dev) check_host_rows(rows, m, ds->n);
+    if (weights == nullptr && weight_max >= 0.0f) throw InvalidArgument("newton_leaves_prepared: weight_max needs weights");
+    if (weights != nullptr && (weight_max != weight_max || weight_max > kern::kWeightMax))
+        throw InvalidArgument("newton_leaves_prepared: weight_max must be at most 65536 (and not NaN), got " + std::to_string(weight_max));
     check_code_range(*ds, "newton_leaves_prepared", t, t + 1);
     ensure_device();
     ev_used_ = 0;
@@ -411,8 +461,15 @@ void Engine::newton_leaves_prepared(const PreparedDataset *ds, const int32_t *ro
     const float *dp = pred_dev ? pred : upload(d_obj_pred_, pred, n_el, "H2D predictions");
     const float *dt = targets_dev ? static_cast<const float *>(targets) : upload(d_obj_targets_, static_cast<const float *>(targets), tar_el, "H2D targets");
     if (objective == kern::kObjSoftmax) check_labels("newton_leaves_prepared", reinterpret_cast<const int32_t *>(dt), m, D, nullptr);
+    const float *dw = weights == nullptr ? nullptr : (weights_dev ? weights : upload(d_obj_weights_, weights, static_cast<size_t>(m), "H2D weights"));
+    if (dw) {   // (the sums divide by no W: weights that are all zero are fine here)
+        const float largest = check_weights("newton_leaves_prepared", dw, m, false).max;
+        if (weight_max < 0.0f) weight_max = largest;
+        else if (weight_max < largest)
+            throw InvalidArgument("newton_leaves_prepared: weight_max " + std::to_string(weight_max) + " is below the largest weight given, " + std::to_string(largest));
+    }
     newton_leaves_run("newton_leaves_prepared", ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, dp, dt, /*abs_index=*/false, objective, t,
-                      leaf_l2, hooks::on(hooks::CONTINUE_GENERIC), sums_out, bits_out, values_out);
+                      leaf_l2, hooks::on(hooks::CONTINUE_GENERIC), sums_out, bits_out, values_out, dw, dw ? weight_max : 0.0f);
 }
 
 // ---- classifier metrics: the checks, the host rule, the device pipeline (kern::metric_error / kern::metric_auc) and the value from its integers
@@ -548,6 +605,8 @@ void Engine::precheck_fit(const void *targets, int iterations, const FitOptions 
         check_metric("fit_prepared", opt.objective, opt.metric);
     }
     if (valid == nullptr) return;
+    if (valid->weights != nullptr && opt.metric != kern::kMetricNone)
+        throw Unsupported("fit_prepared: valid_weights with eval_metric is not supported (the metrics count rows; weighted metrics are not implemented)");
     if (valid->targets == nullptr) throw InvalidArgument("fit_prepared: a validation set needs valid_targets");
     if (valid->rounds < 0) throw InvalidArgument("fit_prepared: early_stopping_rounds must be >= 0");
     if (!(valid->min_delta >= 0.0)) throw InvalidArgument("fit_prepared: min_delta must be >= 0 (and not NaN)");
@@ -567,7 +626,7 @@ struct Engine::Held {
 
 // A walk that ended in a trailing run of one-leaf greedy trees applied nothing for them (it ran off the ensemble): it resumes at the first of them.
 void Engine::advance_held(Held &h, int start, int bn, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
-                          int objective) {
+                          int objective, const float *weights) {
     const int T = model.meta.n_trees, D = model.meta.output_dim;
     int &through = h.through[start / h.bs];
     int from = through;
@@ -578,7 +637,8 @@ void Engine::advance_held(Held &h, int start, int bn, const float *targets, floa
     float *p = h.P + static_cast<size_t>(start) * D;
     const size_t at = static_cast<size_t>(start) * (objective == kern::kObjSoftmax ? 1 : D);   // (softmax: a label per row)
     kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{h.ds->prep.d_codes, h.ds->n, h.ds->code_groups(), nullptr, start}, bn, from, T, p, p,
-                                 targets ? targets + at : nullptr, grad_out, loss_targets ? loss_targets + at : nullptr, loss_part, generic, stream_, objective);
+                                 targets ? targets + at : nullptr, grad_out, loss_targets ? loss_targets + at : nullptr, loss_part, generic, stream_, objective,
+                                 weights ? weights + start : nullptr);
     through = T;
 }
 
@@ -591,6 +651,9 @@ struct Engine::FitRun {
     const int iterations, n, D, bs, T0;   // T0: the tree count at entry
     const bool generic = hooks::on(hooks::CONTINUE_GENERIC);
     const float *dtar = nullptr, *dvtar = nullptr;   // the targets on the device (softmax: int32 labels behind them, one per row)
+    const float *dw = nullptr, *dvw = nullptr;       // the row weights of the two sets on the device (null: none)
+    float wmax = 0.0f;                               // the largest training weight: what the Newton quantum makes room for
+    double W, Wv = 0.0;                              // what the two losses and the bias divide by: the weights' float64 sums, or the row counts
     std::vector<int32_t> class_counts;               // softmax: rows per class of the training set
     Held train, watched;                             // the training rows, in batches of bs; the validation rows, as one batch
     float *G = nullptr;                              // [n][D]: the gradient of the current batch from row 0, of every row for the final loss
@@ -611,7 +674,7 @@ struct Engine::FitRun {
 
     FitRun(Engine &eng, const PreparedDataset *data, int iters, const FitOptions &o, FitValid *valid)
         : e(eng), ds(data), opt(o), v(valid), iterations(iters), n(data->n), D(eng.model.meta.output_dim), bs(eng.model.meta.batch_size), T0(eng.model.meta.n_trees),
-          mC(kern::metric_count_columns(o.objective == kern::kObjSoftmax, eng.model.meta.output_dim)) {
+          W(static_cast<double>(data->n)), mC(kern::metric_count_columns(o.objective == kern::kObjSoftmax, eng.model.meta.output_dim)) {
         bn = start + bs < n ? bs : n - start;                                       // fitter.cpp:120
     }
 
@@ -623,6 +686,16 @@ struct Engine::FitRun {
     void stage_targets(const void *targets, bool targets_dev) {
         dtar = stage(e.d_fp_targets_, targets, targets_dev, n);
         if (v) dvtar = stage(e.d_fp_vtargets_, v->targets, v->targets_dev, v->ds->n);
+        if (v) Wv = static_cast<double>(v->ds->n);
+        if (opt.weights) {
+            dw = opt.weights_dev ? opt.weights : e.upload(e.d_fp_weights_, opt.weights, static_cast<size_t>(n), "H2D weights");
+            const WeightStats st = e.check_weights("fit_prepared (weights)", dw, n, true);
+            wmax = st.max; W = st.sum;
+        }
+        if (v && v->weights) {
+            dvw = v->weights_dev ? v->weights : e.upload(e.d_fp_vweights_, v->weights, static_cast<size_t>(v->ds->n), "H2D validation weights");
+            Wv = e.check_weights("fit_prepared (valid_weights)", dvw, v->ds->n, true).sum;
+        }
         if (opt.metric == kern::kMetricAuc) count_positives();
         if (opt.leaf_update == kern::kLeafNewton && opt.objective == kern::kObjLogistic) check_unit_targets();
         if (opt.objective != kern::kObjSoftmax) return;
@@ -654,15 +727,20 @@ struct Engine::FitRun {
         for (int d = 0; d < D; ++d) check_auc_column("fit_prepared (valid_targets)", d, vpos[d], static_cast<uint64_t>(nv) - vpos[d]);
     }
     // A fresh model's bias by objective, and the feature counts as step_prepared latches them.
+    // With weights: sum w y / W per column and the weight W_c of a class, from column_sums' own reduction with the weight as a per-row factor.
     void set_bias(ColumnStats &stats) {
         Model &model = e.model;
-        if (opt.objective == kern::kObjSoftmax) {   // the log prior, an empty class counted as half a row
+        if (opt.objective == kern::kObjSoftmax && dw) {   // the weighted log prior, an empty class counted as half a mean row
+            const std::vector<double> &hs = stats.weighted_sums(nullptr, reinterpret_cast<const int32_t *>(dtar), dw, n);
+            const double floor_w = 0.5 * W / static_cast<double>(n);
+            for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(std::log(std::max(hs[d], floor_w) / W));
+        } else if (opt.objective == kern::kObjSoftmax) {   // the log prior, an empty class counted as half a row
             for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(std::log(std::max(static_cast<double>(class_counts[d]), 0.5) / static_cast<double>(n)));
         } else {
-            const std::vector<double> &hs = stats.sums(dtar, n, nullptr);
+            const std::vector<double> &hs = dw ? stats.weighted_sums(dtar, nullptr, dw, n) : stats.sums(dtar, n, nullptr);
             const double lo = 0.5 / static_cast<double>(n);
             for (int d = 0; d < D; ++d) {
-                const double mean = hs[d] / static_cast<double>(n);
+                const double mean = hs[d] / W;
                 if (opt.objective == kern::kObjRmse) {   // the column means of the targets (gbrl.cpp:1075-1077)
                     model.bias[d] = static_cast<float>(mean);
                 } else {                                  // logistic: the log odds of the column mean, kept off 0 and 1 by half a row
@@ -708,13 +786,13 @@ struct Engine::FitRun {
     void evaluate(int k) {
         const int nv = v->ds->n;
         v->done = k;
-        e.advance_held(watched, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, opt.objective);
+        e.advance_held(watched, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, opt.objective, dvw);
         double sum = 0.0;
         e.finish_loss_sum(d_vpart, kern::staged_loss_partials(nv), d_vsums + k, v->rounds > 0 ? &sum : nullptr);
         if (opt.metric != kern::kMetricNone) measure(k);
         if (v->rounds > 0) {
             hip_check(hipStreamSynchronize(e.stream_), "sync");
-            v->loss_out[k] = mean_loss(opt.objective, sum, nv);
+            v->loss_out[k] = mean_loss(opt.objective, sum, Wv);
             if (opt.metric != kern::kMetricNone) record_metric(k, h_mrow.data());
         }
     }
@@ -751,7 +829,7 @@ struct Engine::FitRun {
             std::vector<double> sums(static_cast<size_t>(v->done) + 1);
             hip_check(hipMemcpyAsync(sums.data(), d_vsums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, e.stream_), "D2H validation losses");
             hip_check(hipStreamSynchronize(e.stream_), "sync");
-            for (int k = 0; k <= v->done; ++k) v->loss_out[k] = mean_loss(opt.objective, sums[k], v->ds->n);
+            for (int k = 0; k <= v->done; ++k) v->loss_out[k] = mean_loss(opt.objective, sums[k], Wv);
             if (opt.metric != kern::kMetricNone) {   // and so did the metric's integers
                 std::vector<unsigned long long> rows((static_cast<size_t>(v->done) + 1) * mC);
                 hip_check(hipMemcpyAsync(rows.data(), d_vmetric, sizeof(unsigned long long) * rows.size(), hipMemcpyDeviceToHost, e.stream_), "D2H validation metric");
@@ -778,7 +856,7 @@ struct Engine::FitRun {
         const int trees = e.model.meta.n_trees;
         e.begin_step_profile();
         e.phase_begin();
-        e.advance_held(train, start, bn, dtar, G, nullptr, nullptr, generic, opt.objective);
+        e.advance_held(train, start, bn, dtar, G, nullptr, nullptr, generic, opt.objective, dw);
         e.phase_end("continue_codes");
         const float *g = G;
         const int32_t *rows = bn == n ? nullptr : d_iota + start;
@@ -801,16 +879,17 @@ struct Engine::FitRun {
         if (opt.leaf_update == kern::kLeafNewton) {   // the new tree's leaves from the rows it was grown on, at the held prediction over the trees before it
             const bool kept = rows == d_srows && rows != nullptr;
             e.newton_leaves_run("fit_prepared", ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), kept ? d_srows : nullptr, kept ? 0 : start}, m, train.P,
-                                dtar, /*abs_index=*/true, opt.objective, e.model.meta.n_trees - 1, opt.leaf_l2, generic, nullptr, nullptr, nullptr);
+                                dtar, /*abs_index=*/true, opt.objective, e.model.meta.n_trees - 1, opt.leaf_l2, generic, nullptr, nullptr, nullptr, dw, wmax);
         }
         start += bn;                                                                // fitter.cpp:228-231
         if (start >= n) start = 0;
         bn = start + bs < n ? bs : n - start;
     }
     // Every batch to the end; the loss on the whole data set (fitter.cpp:246-251).  rmse: from the gradient of every row, written by the same
-    // launches, as fit() computes it; an objective: from the held prediction by the stand-alone kernel, the loss tail's partials and sum.
+    // launches, as fit() computes it; an objective: from the held prediction by the stand-alone kernel, the loss tail's partials and sum.  With
+    // weights rmse takes the second way too (G would hold w g, and sum (w g)^2 is not the weighted loss): objective_gradient's loss, bit for bit.
     float final_loss(ColumnStats &stats) {
-        const bool rmse = opt.objective == kern::kObjRmse;
+        const bool rmse = opt.objective == kern::kObjRmse && dw == nullptr;
         for (int b0 = 0; b0 < n; b0 += bs)
             e.advance_held(train, b0, std::min(bs, n - b0), rmse ? dtar : nullptr, rmse ? G + static_cast<size_t>(b0) * D : nullptr, nullptr, nullptr, generic, opt.objective);
         if (rmse) {
@@ -819,16 +898,17 @@ struct Engine::FitRun {
         }
         const int nb = kern::staged_loss_partials(n);
         double *d_part = static_cast<double *>(e.d_obj_part_.ensure(sizeof(double) * nb)), *d_sum = static_cast<double *>(e.d_obj_sum_.ensure(sizeof(double)));
-        kern::objective_rows(opt.objective, train.P, dtar, n, D, nullptr, d_part, e.stream_);
+        kern::objective_rows(opt.objective, train.P, dtar, n, D, nullptr, d_part, e.stream_, dw);
         double sum = 0.0;
         e.finish_loss_sum(d_part, nb, d_sum, &sum);
         hip_check(hipGetLastError(), "fit_prepared kernels");
         hip_check(hipStreamSynchronize(e.stream_), "sync");
-        return static_cast<float>(mean_loss(opt.objective, sum, n));
+        return static_cast<float>(mean_loss(opt.objective, sum, W));
     }
 };
 
-float Engine::fit_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, const FitOptions &opt, FitValid *valid) {
+float Engine::fit_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, const FitOptions &opt, FitValid *valid,
+                           float *weight_max_out) {
     precheck_fit(targets, iterations, opt, valid);
     check_prepared_dataset("fit_prepared", ds);
     if (valid) {
@@ -845,6 +925,7 @@ float Engine::fit_prepared(const PreparedDataset *ds, const void *targets, bool 
     ensure_device();
     FitRun run(*this, ds, iterations, opt, valid);
     run.stage_targets(targets, targets_dev);
+    if (weight_max_out) *weight_max_out = run.wmax;
     ColumnStats stats(*this);
     if (fresh) run.set_bias(stats);
     run.hold_predictions();

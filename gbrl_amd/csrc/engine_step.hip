@@ -626,6 +626,16 @@ const std::vector<double> &Engine::ColumnStats::sums(const float *g, int rows, c
     return hs_;
 }
 
+const std::vector<double> &Engine::ColumnStats::weighted_sums(const float *g, const int32_t *labels, const float *factor, int rows) {
+    hipStream_t s = e_.stream_;
+    const int nblk = kern::column_sums_blocks(rows, D_);
+    double *d_part = static_cast<double *>(e_.d_partials_f64_.ensure(sizeof(double) * nblk * 2 * D_));
+    kern::column_sums_weighted(g, labels, factor, rows, D_, d_part, nblk, d_stat_, s);
+    hip_check(hipMemcpyAsync(hs_.data(), d_stat_, sizeof(double) * 2 * D_, hipMemcpyDeviceToHost, s), "D2H stat");
+    hip_check(hipStreamSynchronize(s), "sync");
+    return hs_;
+}
+
 float Engine::ColumnStats::rmse(const float *grads_dev, int rows) {
     sums(grads_dev, rows, d_zero_);
     double tot = 0.0;

@@ -73,6 +73,11 @@ constexpr int kPartitionRows = 4096;  // rows per partition block (chunk size th
 // block_partials: n_blocks * 2D doubles.  Deterministic (fixed reduction tree).
 void column_sums(const float *g, int n, int D, const float *center /*nullable [D]*/, double *block_partials,
                  int n_blocks, double *out /*[2D]*/, hipStream_t s);
+// The same reduction -- grid, order, finishing tree -- with a per-row factor: out[d] = sum_i (double)factor[i] * (double)g[i,d] (the product of two
+// float32 is exact in float64: a factor of 1 leaves every bit of the plain sums).  g == nullptr: the matrix is the one-hot of labels (int32 [n],
+// every entry in [0, D)), so out[d] is the factor summed over the rows of class d.  out[D..2D) stays the maxima of |g|.  fit_prepared's weighted bias.
+void column_sums_weighted(const float *g, const int32_t *labels, const float *factor /*[n]*/, int n, int D, double *block_partials, int n_blocks,
+                          double *out /*[2D]*/, hipStream_t s);
 int column_sums_blocks(int n, int D);
 // max |standardised g| as float bits in out[0]; mean/inv_std nullable (Cosine: raw grads)
 // Device-side statistics chain (one GPU): mean from the column sums; then std + 1e-8, the maxima and both fixed-point scales.
@@ -627,15 +632,23 @@ struct CodeTables { const int32_t *bins, *cond_pack, *grd_nodes; };
 struct CodeRows { const uint16_t *codes; int n_rows, groups; const int32_t *rows; int row0; };
 void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
                             float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic, hipStream_t s,
-                            int objective = 0);
+                            int objective = 0, const float *weights = nullptr);
 // objective (kObjRmse / kObjLogistic / kObjSoftmax of objective_core.h) selects the two tails: logistic takes the same [m][D] float targets and
 // writes dL/dp of the sigmoid cross-entropy, its loss tail sums that loss; softmax takes ONE int32 label per row -- targets / loss_targets then
 // point at int32 [m] -- and writes softmax(p) - onehot.  A range without a tree runs the stand-alone kernel below on the copied base.
+// weights (nullable, device float32 [m], indexed by j; every entry checked by the caller, weight_stats below): the gradient tail stores
+// fl32(w * g) and the loss tail sums (double)w * the row loss (objective_core.h).  nullptr launches the kernels of the call without weights.
 //
 // The objectives on a prediction matrix (objective.hip): the device functions of the tails applied to pred [n][D] (device).  targets: float32
 // [n][D] (rmse, logistic) or int32 [n] (softmax; every label in [0, D): the caller checks, label_counts below).  grad_out (device [n][D]) and
 // loss_part (staged_loss_partials(n) doubles, one per 64 rows, finished by staged_loss_finish) may each be null.  D <= 128.
-void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s);
+void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s,
+                    const float *weights = nullptr /*device [n]: the weighted forms*/);
+// What the engine needs to know of a weight vector (device float32 [n]) in one pass: stat[0] = the smallest row whose weight is a NaN, negative,
+// infinite or above kWeightMax (INT32_MAX: none), stat[1] = the bits of the largest entry (non-negative floats order like their bits; a refused
+// entry does not enter); part[j / 64] = the wave's sum of (double)w in the loss partials' fixed order, finished into *sum by staged_loss_finish: two
+// calls give the same bits.  stat is device int32 [2], set to {INT32_MAX, 0} by the caller on `s`; part holds staged_loss_partials(n) doubles.
+void weight_stats(const float *weights, int n, int32_t *stat, double *part, double *sum, hipStream_t s);
 // counts[c] += rows with label c (integer atomics; counts is device int32 [D + 1], ZEROED by the caller on `s` except counts[D] = INT32_MAX);
 // counts[D] = the smallest row index whose label is outside [0, D)
 void label_counts(const int32_t *labels, int n, int D, int32_t *counts, hipStream_t s);
@@ -645,9 +658,11 @@ void tile_rows(const float *row /*[D], device*/, int D, int n, float *out /*[n][
 // kObjSoftmax: int32 labels in [0, D), checked by the caller) at pred -- the prediction over the trees [0, tree).  pred and targets are indexed by
 // the position j < m, or with abs_index by the data set row position j names.  acc (device, n_leaves * (2 D + 1) + 1 words, ZEROED by the caller on
 // `s`): the last word collects kNewtonBadTarget / kNewtonBadPred.  D <= 128.  Returns true when the streaming kernel took the launch.
+// weights (nullable, device float32, indexed like pred): q(fl32(w * g)) and q(fl32(w * h)) are summed; bits is then newton_sum_bits(m, weight_max).
 void newton_check_targets(const float *targets, size_t n_el, unsigned long long *flag /*device, zeroed by the caller*/, hipStream_t s);   // *flag |= kNewtonBadTarget: an entry outside [0, 1] (a NaN counts)
 bool newton_leaf_sums(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int tree, int leaf0, int n_leaves, const float *pred,
-                      const void *targets, bool abs_index, int objective, int bits, unsigned long long *acc, bool generic, hipStream_t s);
+                      const void *targets, bool abs_index, int objective, int bits, unsigned long long *acc, bool generic, hipStream_t s,
+                      const float *weights = nullptr);
 // Every prefix [0, stops[s]) of the ensemble in one walk (predict_staged.hip): stage s has the bits of predict_continue(tiled bias, 0, stops[s]);
 // stops[s] == 0 is the bias alone.  `stops` is a device array, strictly ascending, 0 <= stops[s] <= n_trees (the caller has checked);
 // last_stop = stops[n_stops - 1].  Predict mode (targets == nullptr): out[s][r][j], device [n_stops][n][D].  Loss mode (targets != nullptr,

@@ -28,17 +28,30 @@ namespace {
 // A2  gradient statistics: out[d] = sum_i (g[i,d] - center[d])^2  (center != null)  or  sum_i g[i,d]
 // Block size is a multiple of D so that every thread owns one column; per-block partials are combined by a single
 // block in a fixed order => deterministic.
+// FACTOR: the same loop and tree with a per-row factor, out[d] = sum_i (double)factor[i] * (double)g[i,d] (an exact product: a factor of 1 keeps
+// every bit); g == nullptr stands for the one-hot matrix of `labels`.  The plain instantiation reads neither pointer.
 // ------------------------------------------------------------------------------------------------------------
+template <bool FACTOR>
 __global__ void k_column_sums(const float *__restrict__ g, size_t n_el, int D, const float *__restrict__ center,
-                              double *__restrict__ partials /*[blocks][2D]: sums then maxima*/) {
+                              double *__restrict__ partials /*[blocks][2D]: sums then maxima*/, const float *__restrict__ factor,
+                              const int32_t *__restrict__ labels) {
     extern __shared__ double sh[];  // [2*bs]
     const int bs = blockDim.x;
     const int col = threadIdx.x % D;
     const float c = center ? center[col] : 0.0f;
     double acc = 0.0;
     float mx = 0.0f;
-    auto take = [&](float v) {
-        if (center) {
+    auto at = [&](size_t e) -> float {   // element e of the matrix
+        if constexpr (FACTOR) {
+            if (g == nullptr) return labels[e / D] == col ? 1.0f : 0.0f;
+        }
+        return g[e];
+    };
+    auto take = [&](float v, size_t e) {
+        if constexpr (FACTOR) {
+            acc += static_cast<double>(factor[e / D]) * static_cast<double>(v);
+            mx = fmaxf(mx, fabsf(v));
+        } else if (center) {
             const float dv = v - c;  // fp32 subtraction like the reference (math_ops.cpp:498)
             acc += static_cast<double>(dv) * static_cast<double>(dv);
             mx = fmaxf(mx, fabsf(dv));
@@ -53,11 +66,11 @@ __global__ void k_column_sums(const float *__restrict__ g, size_t n_el, int D, c
     for (; e + 7 * stride < n_el; e += 8 * stride) {
         float v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = g[e + u * stride];
+        for (int u = 0; u < 8; ++u) v[u] = at(e + u * stride);
 #pragma unroll
-        for (int u = 0; u < 8; ++u) take(v[u]);
+        for (int u = 0; u < 8; ++u) take(v[u], e + u * stride);
     }
-    for (; e < n_el; e += stride) take(g[e]);
+    for (; e < n_el; e += stride) take(at(e), e);
     sh[threadIdx.x] = acc;
     sh[bs + threadIdx.x] = static_cast<double>(mx);
     __syncthreads();
@@ -1482,8 +1495,16 @@ int column_sums_blocks(int n, int D) { return grid_for(static_cast<size_t>(n) * 
 void column_sums(const float *g, int n, int D, const float *center, double *block_partials, int n_blocks, double *out,
                  hipStream_t s) {
     const int bs = D <= 256 ? (256 / D) * D : D;  // multiple of D so a thread owns one column
-    hipLaunchKernelGGL(k_column_sums, dim3(n_blocks), dim3(bs), 2 * bs * sizeof(double), s, g, static_cast<size_t>(n) * D, D,
-                       center, block_partials);
+    hipLaunchKernelGGL(k_column_sums<false>, dim3(n_blocks), dim3(bs), 2 * bs * sizeof(double), s, g, static_cast<size_t>(n) * D, D,
+                       center, block_partials, static_cast<const float *>(nullptr), static_cast<const int32_t *>(nullptr));
+    hipLaunchKernelGGL(k_column_sums_final, dim3(2 * D), dim3(256), 0, s, block_partials, n_blocks, D, out);
+}
+
+void column_sums_weighted(const float *g, const int32_t *labels, const float *factor, int n, int D, double *block_partials, int n_blocks, double *out,
+                          hipStream_t s) {
+    const int bs = D <= 256 ? (256 / D) * D : D;  // column_sums' geometry
+    hipLaunchKernelGGL(k_column_sums<true>, dim3(n_blocks), dim3(bs), 2 * bs * sizeof(double), s, g, static_cast<size_t>(n) * D, D,
+                       static_cast<const float *>(nullptr), block_partials, factor, labels);
     hipLaunchKernelGGL(k_column_sums_final, dim3(2 * D), dim3(256), 0, s, block_partials, n_blocks, D, out);
 }
 

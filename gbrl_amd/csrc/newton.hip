@@ -22,6 +22,9 @@
 //
 //   pred / targets are indexed by the position j of the call, or (abs_index) by the data set row the position names: fit_prepared's held
 //   prediction and targets are [n][D] of the whole data set while a sampled iteration sums over a row list.
+//   WEIGHTED (a template flag of both sums kernels) with weights float32, indexed like pred: the row's weight is loaded with p[] and the targets,
+//   and g, h become fl32(w * g), fl32(w * h) in front of the quantisation (newton_core.h: the caller's bits make room for the largest weight).
+//   cnt counts rows as before.  Without the flag the pointer is never read.
 //   The flag word behind the accumulators collects what the caller refuses: kNewtonBadTarget (a logistic target outside [0, 1]; a NaN counts),
 //   kNewtonBadPred (a prediction that is not finite).  The caller zeroes accumulators and flag and reads both back in one copy.
 #include "kernels.h"
@@ -62,9 +65,10 @@ __global__ __launch_bounds__(256) void k_newton_check_targets(const float *__res
 }
 
 // ------------------------------------------------------------------------------------------------------------ general kernel
-template <int OBJ>
+template <int OBJ, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_newton_sums_general(LeavesModel cm, NewtonTree nt, CodeRows cr, int m, int D, const float *__restrict__ pred,
-                                                             const float *__restrict__ targets, int abs_index, double scale) {
+                                                             const float *__restrict__ targets, int abs_index, double scale,
+                                                             const float *__restrict__ weights) {
 #pragma clang fp contract(off)
     const size_t j = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const bool live = j < static_cast<size_t>(m);   // (dead lanes stay for the ballots)
@@ -81,6 +85,8 @@ __global__ __launch_bounds__(256) void k_newton_sums_general(LeavesModel cm, New
     const size_t pr = abs_index ? src : jj;
     const float *p = pred + pr * D;
     const float *y = targets + pr * (OBJ == kObjSoftmax ? 1 : D);
+    float w = 1.0f;
+    if constexpr (WEIGHTED) w = weights[pr];
     int label = 0;
     float mx = 0.0f, S = 1.0f;
     if constexpr (OBJ == kObjSoftmax) {   // obj_softmax_grad_row's first two loops
@@ -108,6 +114,10 @@ __global__ __launch_bounds__(256) void k_newton_sums_general(LeavesModel cm, New
             obj_logistic_grad_hess(pd, yd, g, h);
         }
         if (live && newton_bad_pred(pd)) flag |= kNewtonBadPred;
+        if constexpr (WEIGHTED) {
+            g = obj_weighted(w, g);
+            h = obj_weighted(w, h);
+        }
         const long long qg = l >= 0 ? newton_quantise(g, scale) : 0ll, qh = l >= 0 ? newton_quantise(h, scale) : 0ll;
         // one add per distinct leaf of the wave: every lane of the leaf contributes to a butterfly, the lowest of them adds the result
         unsigned long long todo = in_tree;
@@ -137,10 +147,10 @@ __global__ __launch_bounds__(256) void k_newton_sums_general(LeavesModel cm, New
 }
 
 // ------------------------------------------------------------------------------------------------------------ streaming kernel
-template <int DMAX, bool GREEDY, int OBJ>
+template <int DMAX, bool GREEDY, int OBJ, bool WEIGHTED>
 __global__ __launch_bounds__(kNewtonRows) void k_newton_sums(LeavesModel cm, NewtonTree nt, CodeRows cr, int m, int n_tiles, int D,
                                                              const float *__restrict__ pred, const float *__restrict__ targets, int abs_index, double scale,
-                                                             int vec_p, int vec_y) {
+                                                             int vec_p, int vec_y, const float *__restrict__ weights) {
     extern __shared__ __align__(16) uint32_t ntile[];   // [kNewtonRows][stream_code_stride(G)] words, then [n_leaves][2 D + 1] int64
     const int lane = threadIdx.x;
     const int ws = stream_code_stride(cr.groups);
@@ -163,6 +173,8 @@ __global__ __launch_bounds__(kNewtonRows) void k_newton_sums(LeavesModel cm, New
         int label = 0;
         if constexpr (OBJ == kObjSoftmax) label = reinterpret_cast<const int32_t *>(targets)[pr];
         else stream_load_row<DMAX>(targets + pr * D, D, vec_y != 0, h);
+        float w = 1.0f;
+        if constexpr (WEIGHTED) w = weights[pr];
         __syncthreads();   // the previous tile has been read (and, the first time, the accumulators are zero)
         stream_stage_code_tile(ntile, cr.codes, static_cast<size_t>(cr.n_rows), cr.groups, my_row, rows, lane);
         __syncthreads();
@@ -186,6 +198,13 @@ __global__ __launch_bounds__(kNewtonRows) void k_newton_sums(LeavesModel cm, New
 #pragma unroll
             for (int j = 0; j < DMAX; ++j)
                 if (j < D) obj_logistic_grad_hess(g[j], h[j], g[j], h[j]);
+        }
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int j = 0; j < DMAX; ++j) {
+                g[j] = obj_weighted(w, g[j]);
+                h[j] = obj_weighted(w, h[j]);
+            }
         }
         if (few) {
             for (int k = 0; k < nt.n_leaves; ++k) {
@@ -224,35 +243,35 @@ __global__ __launch_bounds__(kNewtonRows) void k_newton_sums(LeavesModel cm, New
     if (flag) atomicOr(&nt.acc[na], static_cast<unsigned long long>(flag));
 }
 
-template <int DMAX, bool GREEDY, int OBJ>
+template <int DMAX, bool GREEDY, int OBJ, bool WEIGHTED>
 bool launch_newton_sums(const LeavesModel &cm, const NewtonTree &nt, const CodeRows &cr, int m, int D, const float *pred, const float *targets, int abs_index,
-                        double scale, hipStream_t s) {
+                        double scale, const float *weights, hipStream_t s) {
     const size_t lds = stream_code_tile_bytes(cr.groups) + static_cast<size_t>(nt.n_leaves) * (2 * D + 1) * sizeof(unsigned long long);
     if (lds > kStreamLdsBudget) return false;   // rows too wide, or a tree with too many accumulators, for the LDS of a CU
     static StreamLdsOptIn optin;
-    if (!optin.ok(k_newton_sums<DMAX, GREEDY, OBJ>, lds)) return false;
+    if (!optin.ok(k_newton_sums<DMAX, GREEDY, OBJ, WEIGHTED>, lds)) return false;
     const int n_tiles = (m + kNewtonRows - 1) / kNewtonRows;
     const int per_cu = static_cast<int>(std::min<size_t>(kNewtonBlocksPerCu, std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1))));
     const int blocks = std::min(n_tiles, stream_cu_count() * per_cu);
     const bool d4 = (D & 3) == 0;
     const int vec_p = d4 && (reinterpret_cast<uintptr_t>(pred) & 15) == 0;
     const int vec_y = d4 && OBJ != kObjSoftmax && (reinterpret_cast<uintptr_t>(targets) & 15) == 0;
-    hipLaunchKernelGGL((k_newton_sums<DMAX, GREEDY, OBJ>), dim3(blocks), dim3(kNewtonRows), lds, s, cm, nt, cr, m, n_tiles, D, pred, targets, abs_index, scale,
-                       vec_p, vec_y);
+    hipLaunchKernelGGL((k_newton_sums<DMAX, GREEDY, OBJ, WEIGHTED>), dim3(blocks), dim3(kNewtonRows), lds, s, cm, nt, cr, m, n_tiles, D, pred, targets, abs_index,
+                       scale, vec_p, vec_y, weights);
     return true;
 }
 
-template <int OBJ>
+template <int OBJ, bool WEIGHTED>
 bool newton_sums_obj(const PredictModel &pm, const LeavesModel &cm, const NewtonTree &nt, const CodeRows &cr, int m, const float *pred, const float *targets,
-                     int abs_index, double scale, bool generic, hipStream_t s) {
+                     int abs_index, double scale, bool generic, const float *weights, hipStream_t s) {
     const int D = pm.D;
     if (leaves_streamable(pm, generic) && D <= 64 && with_stream_dmax(D, [&](auto dmax) {
             constexpr int DMAX = decltype(dmax)::value;
-            return pm.oblivious ? launch_newton_sums<DMAX, false, OBJ>(cm, nt, cr, m, D, pred, targets, abs_index, scale, s)
-                                : launch_newton_sums<DMAX, true, OBJ>(cm, nt, cr, m, D, pred, targets, abs_index, scale, s);
+            return pm.oblivious ? launch_newton_sums<DMAX, false, OBJ, WEIGHTED>(cm, nt, cr, m, D, pred, targets, abs_index, scale, weights, s)
+                                : launch_newton_sums<DMAX, true, OBJ, WEIGHTED>(cm, nt, cr, m, D, pred, targets, abs_index, scale, weights, s);
         }))
         return true;
-    hipLaunchKernelGGL((k_newton_sums_general<OBJ>), dim3((m + 255) / 256), dim3(256), 0, s, cm, nt, cr, m, D, pred, targets, abs_index, scale);
+    hipLaunchKernelGGL((k_newton_sums_general<OBJ, WEIGHTED>), dim3((m + 255) / 256), dim3(256), 0, s, cm, nt, cr, m, D, pred, targets, abs_index, scale, weights);
     return false;
 }
 
@@ -264,7 +283,7 @@ void newton_check_targets(const float *targets, size_t n_el, unsigned long long 
 }
 
 bool newton_leaf_sums(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int tree, int leaf0, int n_leaves, const float *pred,
-                      const void *targets, bool abs_index, int objective, int bits, unsigned long long *acc, bool generic, hipStream_t s) {
+                      const void *targets, bool abs_index, int objective, int bits, unsigned long long *acc, bool generic, hipStream_t s, const float *weights) {
     if (m <= 0 || n_leaves <= 0) return false;
     LeavesModel cm = leaves_model(pm);   // the routing view of the float walk with the threshold words replaced by bins
     cm.cond_pack = ct.cond_pack;
@@ -273,8 +292,12 @@ bool newton_leaf_sums(const PredictModel &pm, const CodeTables &ct, const CodeRo
     const NewtonTree nt{tree, leaf0, n_leaves, acc};
     const double scale = std::ldexp(1.0, bits);
     const float *y = static_cast<const float *>(targets);
-    return objective == kObjSoftmax ? newton_sums_obj<kObjSoftmax>(pm, cm, nt, cr, m, pred, y, abs_index ? 1 : 0, scale, generic, s)
-                                    : newton_sums_obj<kObjLogistic>(pm, cm, nt, cr, m, pred, y, abs_index ? 1 : 0, scale, generic, s);
+    const int ai = abs_index ? 1 : 0;
+    if (weights != nullptr)
+        return objective == kObjSoftmax ? newton_sums_obj<kObjSoftmax, true>(pm, cm, nt, cr, m, pred, y, ai, scale, generic, weights, s)
+                                        : newton_sums_obj<kObjLogistic, true>(pm, cm, nt, cr, m, pred, y, ai, scale, generic, weights, s);
+    return objective == kObjSoftmax ? newton_sums_obj<kObjSoftmax, false>(pm, cm, nt, cr, m, pred, y, ai, scale, generic, nullptr, s)
+                                    : newton_sums_obj<kObjLogistic, false>(pm, cm, nt, cr, m, pred, y, ai, scale, generic, nullptr, s);
 }
 
 }  // namespace kern

@@ -9,6 +9,10 @@
 //                scikit-learn, XGBoost and LightGBM take it.
 //   sums         bits = newton_sum_bits(m) = min(40, 62 - bit_length(m)) for m summed rows;  the quantum q(x) = llrint((double)x * 2^bits), the same
 //                bits for g and h.  |g| <= 1 and h <= 0.25, so |sum| <= m * 2^bits < 2^62.  Per leaf: Sg[D], Sh[D], cnt -- int64, exact, order-free.
+//   row weights  g_w = fl32(w * g), h_w = fl32(w * h) (objective_core.h: obj_weighted) are what is quantised: Sg += q(g_w), Sh += q(h_w), cnt counts rows
+//                as before.  The quantum makes room for the weight: bits = newton_sum_bits(m, weight_max) = min(40, 62 - bit_length(m) - e), e the smallest
+//                integer >= 0 with weight_max <= 2^e, so |g_w| <= 2^e and |sum| < 2^62 still; e = 0 (weight_max <= 1) is the rule above.  weight_max is an
+//                INPUT of the rule (fit_prepared: the maximum over the training weights of the whole data set), never something a kernel discovers.
 //   value        G = Sg / 2^bits, H = Sh / 2^bits, den = H + leaf_l2 in double;  v = (float)(G / den).  A leaf keeps the value the step gave it when
 //                cnt == 0, when its depth is 0 (refit_leaves' rule for a leaf no row reaches) or when !(den > 0).  Predictions move by -rate * v.
 #pragma once
@@ -110,6 +114,19 @@ GBRL_OBJ_HD inline int newton_sum_bits(long long m) {
     int len = 0;
     for (unsigned long long v = m > 0 ? static_cast<unsigned long long>(m) : 0ull; v != 0; v >>= 1) ++len;
     const int b = 62 - len;
+    return b < 40 ? b : 40;
+}
+
+// ... with row weights up to weight_max (finite, in [0, kWeightMax]: the caller has checked): e fewer bits, weight_max <= 2^e
+GBRL_OBJ_HD inline int newton_weight_exponent(float weight_max) {
+    int e = 0;
+    for (float cap = 1.0f; cap < weight_max; cap = cap + cap) ++e;   // (exact doublings; at most 16 of them)
+    return e;
+}
+GBRL_OBJ_HD inline int newton_sum_bits(long long m, float weight_max) {
+    int len = 0;
+    for (unsigned long long v = m > 0 ? static_cast<unsigned long long>(m) : 0ull; v != 0; v >>= 1) ++len;
+    const int b = 62 - len - newton_weight_exponent(weight_max);
     return b < 40 ? b : 40;
 }
 

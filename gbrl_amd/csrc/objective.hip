@@ -4,6 +4,10 @@
 //                      registers (16-byte loads where D % 4 == 0 and the pointers allow it, as stream_load_row decides), then the device functions
 //                      of predict_continue_codes.hip's two tails (predict_loss.h: objective_grad_store, objective_loss_regs) -- the same bits as the
 //                      fused tails.  Loss: one float64 partial per wave of 64 rows through staged_wave_sum, finished by k_staged_finish.
+//                      WEIGHTED (a template flag) with weights float32 [n]: the row's weight is loaded with the row; the gradient is fl32(w * g) and
+//                      the row loss (double)w * L in front of the butterfly.  Without the flag the pointer is never read.
+//   k_weight_stats     a weight vector in one pass: the first row whose weight is refused, the largest weight, and the sum of the weights as
+//                      float64 partials per wave in the loss partials' order (finished by k_staged_finish: fixed order, the same bits every call).
 //   k_label_counts     class counts of an int32 label vector by integer atomics (an LDS histogram per block, then one global add per class), and
 //                      the smallest row whose label is outside [0, D): fit_prepared's softmax bias and the range check, one pass, D + 1 ints back.
 #include "kernels.h"
@@ -15,25 +19,41 @@ namespace kern {
 
 namespace {
 
-template <int DMAX, int OBJ>
+template <int DMAX, int OBJ, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_objective_rows(const float *__restrict__ pred, const float *__restrict__ targets, int n, int D, float *__restrict__ grad_out,
-                                                        double *__restrict__ loss_part, int loss_nb, int vec_pred, int vec_tar, int vec_grad) {
+                                                        double *__restrict__ loss_part, int loss_nb, int vec_pred, int vec_tar, int vec_grad,
+                                                        const float *__restrict__ weights) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = j < n;
     if (!live && loss_part == nullptr) return;   // (with the loss whole waves stay for the butterfly)
     float p[DMAX];
+    float w = 1.0f;
+    if constexpr (WEIGHTED) w = live ? weights[j] : 0.0f;
     if (live) {
         stream_load_row<DMAX>(pred + static_cast<size_t>(j) * D, D, vec_pred != 0, p);
         if (grad_out != nullptr)
-            objective_grad_store<OBJ, DMAX>(p, objective_target_row<OBJ>(targets, j, D), D, vec_tar != 0, vec_grad != 0, grad_out + static_cast<size_t>(j) * D);
+            objective_grad_store<OBJ, DMAX, WEIGHTED>(p, objective_target_row<OBJ>(targets, j, D), D, vec_tar != 0, vec_grad != 0,
+                                                      grad_out + static_cast<size_t>(j) * D, w);
     }
     if (loss_part != nullptr) {
         double acc = 0.0;
         if (live) acc = objective_loss_regs<OBJ, DMAX>(p, pred + static_cast<size_t>(j) * D, objective_target_row<OBJ>(targets, j, D), D, vec_tar != 0);
+        if constexpr (WEIGHTED) acc = obj_weighted_loss(w, acc);
         acc = staged_wave_sum(acc);
         const int wave = j / kStagedRows;   // 256 = 4 x 64: a wave holds the rows of one partial
         if ((threadIdx.x & (kStagedRows - 1)) == 0 && wave < loss_nb) loss_part[wave] = acc;
     }
+}
+
+__global__ __launch_bounds__(256) void k_weight_stats(const float *__restrict__ weights, int n, int32_t *__restrict__ stat, double *__restrict__ part, int nb) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;   // (whole waves stay for the butterfly)
+    const float w = j < n ? weights[j] : 0.0f;
+    const bool bad = obj_weight_bad(w);
+    if (bad) atomicMin(&stat[0], j);
+    else if (w > 0.0f) atomicMax(&stat[1], static_cast<int32_t>(__float_as_uint(w)));   // (in [0, 65536]: the bits are a non-negative int32 in the floats' order)
+    const double sum = staged_wave_sum(bad ? 0.0 : static_cast<double>(w));
+    const int wave = j / kStagedRows;
+    if ((threadIdx.x & (kStagedRows - 1)) == 0 && wave < nb) part[wave] = sum;
 }
 
 constexpr int kLabelClasses = 128;   // output_dim <= 128 wherever labels are taken
@@ -57,18 +77,29 @@ __global__ __launch_bounds__(256) void k_label_counts(const int32_t *__restrict_
 
 }  // namespace
 
-void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s) {
+void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s, const float *weights) {
     if (n <= 0 || (grad_out == nullptr && loss_part == nullptr)) return;
     const bool d4 = (D & 3) == 0;
     const int vec_pred = d4 && (reinterpret_cast<uintptr_t>(pred) & 15) == 0;
     const int vec_tar = d4 && (reinterpret_cast<uintptr_t>(targets) & 15) == 0;
     const int vec_grad = d4 && (reinterpret_cast<uintptr_t>(grad_out) & 15) == 0;
-    with_objective(objective, [&](auto obj) {
+    auto run = [&](auto obj, auto weighted) {
         with_general_dmax(D, [&](auto dmax) {
-            hipLaunchKernelGGL((k_objective_rows<decltype(dmax)::value, decltype(obj)::value>), dim3((n + 255) / 256), dim3(256), 0, s, pred,
-                               static_cast<const float *>(targets), n, D, grad_out, loss_part, staged_loss_partials(n), vec_pred, vec_tar, vec_grad);
+            hipLaunchKernelGGL((k_objective_rows<decltype(dmax)::value, decltype(obj)::value, decltype(weighted)::value>), dim3((n + 255) / 256), dim3(256), 0, s,
+                               pred, static_cast<const float *>(targets), n, D, grad_out, loss_part, staged_loss_partials(n), vec_pred, vec_tar, vec_grad, weights);
         });
+    };
+    with_objective(objective, [&](auto obj) {
+        if (weights != nullptr) run(obj, std::true_type{});
+        else run(obj, std::false_type{});
     });
+}
+
+void weight_stats(const float *weights, int n, int32_t *stat, double *part, double *sum, hipStream_t s) {
+    if (n <= 0) return;
+    const int nb = staged_loss_partials(n);
+    hipLaunchKernelGGL(k_weight_stats, dim3((n + 255) / 256), dim3(256), 0, s, weights, n, stat, part, nb);
+    staged_loss_finish(part, nb, sum, s);
 }
 
 void label_counts(const int32_t *labels, int n, int D, int32_t *counts, hipStream_t s) {

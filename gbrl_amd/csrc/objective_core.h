@@ -18,6 +18,11 @@
 //   "rmse"                  g = fl32(p - y): what fit_prepared has always done (predict_loss.h has its loss).
 //
 // g is dL/dp: trees fit g and predictions move by -lr * value, as with p - y.
+//
+//   row weights             weights float32 [n], every entry finite and in [0, kWeightMax], W = sum_r (double)w_r > 0 where a loss or a bias is taken.
+//                           g_w = fl32(w * g) with g exactly as above: one float32 multiply behind the rule, so w == 1 changes no bit (obj_weighted).
+//                           The loss is sum_r (double)w_r * L_r over W in place of sum_r L_r over the row count: L_r the float64 row loss as
+//                           before, one float64 multiply per row (obj_weighted_loss) in front of the reduction, whose order is unchanged.
 #pragma once
 
 #include <cstdint>
@@ -91,6 +96,27 @@ GBRL_OBJ_HD inline float obj_exp_f32(float t) {
     const float p = obj_exp_parts(t, k);
     if (k >= -100) return p * obj_bits_float(static_cast<uint32_t>(127 + k) << 23);   // exact scaling
     return (p * obj_bits_float(static_cast<uint32_t>(227 + k) << 23)) * 0x1p-100f;    // one rounding, into the subnormals
+}
+
+// row weights: the largest weight, what is refused (a NaN, a negative, an infinite or a larger entry), the weighted gradient / hessian entry
+// fl32(w * x) and the weighted row loss (double)w * L
+constexpr float kWeightMax = 65536.0f;
+GBRL_OBJ_HD inline bool obj_weight_bad(float w) { return !(w >= 0.0f && w <= kWeightMax); }
+GBRL_OBJ_HD inline float obj_weighted(float w, float x) {
+#pragma clang fp contract(off)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __fmul_rn(w, x);
+#else
+    return w * x;
+#endif
+}
+GBRL_OBJ_HD inline double obj_weighted_loss(float w, double loss) {
+#pragma clang fp contract(off)
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __dmul_rn(static_cast<double>(w), loss);
+#else
+    return static_cast<double>(w) * loss;
+#endif
 }
 
 // logistic: dL/dp of one output

@@ -83,14 +83,19 @@ __device__ __forceinline__ double softmax_row_loss(const float (&p)[DMAX], int l
 }
 
 // The gradient row of an objective from the scores p and the row's targets, stored to g_row.  y_row: float32 [D] of the row (rmse, logistic: read
-// four at a time) or its int32 label (softmax: one entry, the row's probabilities in a second register row).
-template <int OBJ, int DMAX>
-__device__ __forceinline__ void objective_grad_store(const float (&p)[DMAX], const float *y_row, int D, bool vec_y, bool vec_g, float *g_row) {
+// four at a time) or its int32 label (softmax: one entry, the row's probabilities in a second register row).  WEIGHTED: every entry is
+// obj_weighted(w, g), w the row's weight, one float32 multiply behind the rule; without it w is not read and the code is what it was.
+template <int OBJ, int DMAX, bool WEIGHTED = false>
+__device__ __forceinline__ void objective_grad_store(const float (&p)[DMAX], const float *y_row, int D, bool vec_y, bool vec_g, float *g_row, float w = 1.0f) {
     if constexpr (OBJ == kObjSoftmax) {
         float g[DMAX];
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) g[d] = p[d];
         obj_softmax_grad_regs<DMAX>(g, D, *reinterpret_cast<const int32_t *>(y_row));
+        if constexpr (WEIGHTED) {
+#pragma unroll
+            for (int d = 0; d < DMAX; ++d) g[d] = obj_weighted(w, g[d]);
+        }
         stream_store_row<DMAX>(g_row, D, vec_g, g);
     } else {
 #pragma unroll
@@ -105,6 +110,9 @@ __device__ __forceinline__ void objective_grad_store(const float (&p)[DMAX], con
                     g.w = 4 * q + 3 < D ? obj_logistic_grad(p[4 * q + 3], y.w) : 0.0f;
                 } else {
                     g.x = __fsub_rn(p[4 * q], y.x); g.y = __fsub_rn(p[4 * q + 1], y.y); g.z = __fsub_rn(p[4 * q + 2], y.z); g.w = __fsub_rn(p[4 * q + 3], y.w);
+                }
+                if constexpr (WEIGHTED) {
+                    g.x = obj_weighted(w, g.x); g.y = obj_weighted(w, g.y); g.z = obj_weighted(w, g.z); g.w = obj_weighted(w, g.w);
                 }
                 if (vec_g) {
                     reinterpret_cast<float4 *>(g_row)[q] = g;

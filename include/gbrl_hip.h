@@ -585,6 +585,64 @@ int gbrl_hip_fit_prepared_leaf(gbrl_hip_model *m, const gbrl_hip_dataset *ds, co
                                double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update,
                                double leaf_l2, float *loss_out, double *valid_loss_out /*[iterations + 1]*/,
                                double *valid_metric_out /*[iterations + 1]*/, int *iterations_done, int *best_n_trees);
+/* Row weights (new: LightGBM's weight, XGBoost's and scikit-learn's sample_weight, for fit_prepared and its public pieces).  weights is float32
+ * [n], one per data set row; every entry finite and in [0, 65536] (GBRL_HIP_WEIGHT_MAX); W = sum_r (double)w_r, reduced in float64 in a fixed
+ * order (two calls give the same bits), must be > 0 where a loss or a bias is taken.  csrc/objective_core.h and csrc/newton_core.h define the
+ * rule once for the host and the kernels, contraction off:
+ *   gradient  g_w = fl32(w * g), g bit for bit the unweighted gradient (rmse: fl32(p - y)).  The tree is grown on g_w.  w == 1 changes no bit.
+ *   hessian   h_w = fl32(w * h).
+ *   loss      sum_r (double)w_r * L_r in place of sum_r L_r and W in place of the row count, the formulas otherwise unchanged (rmse:
+ *             sqrt(0.5 * sum / W)).  L_r is the float64 row loss as before; the product is one float64 multiply in front of the wave butterfly;
+ *             the partials and the finishing sum keep their fixed order.
+ *   bias      of a fresh model.  rmse: sum_r w_r y_rd / W per column; logistic: the log odds of that mean, the clamp 0.5 / n kept; softmax:
+ *             log(max(W_c, 0.5 * W / n) / W), W_c the weight of class c.  The sums are the column sums' own reduction with the weight as a per-row
+ *             factor (the product of two float32 is exact in float64): all-ones weights give the unweighted bias bits.
+ *   newton    Sg += q(g_w), Sh += q(h_w), cnt counts rows; bits = min(40, 62 - bit_length(m) - e), e the smallest integer >= 0 with weight_max <=
+ *             2^e: |g_w| <= 2^e, so |sum| < 2^62 still, and e = 0 is the unweighted rule.  weight_max is an INPUT of the rule: fit_prepared uses
+ *             the maximum over the training weights of the whole data set; gbrl_hip_newton_leaves_prepared_weighted takes it (negative: the
+ *             maximum of the weights given), so that a caller's loop over sampled rows reproduces the fit's bits.  The value rule is unchanged.
+ *   What weights do NOT do.  Split scores see weighted gradients, but their row counts (L2's sum^2 / count, min_data_in_leaf) are unchanged.  A
+ *             gradient leaf stores the mean of w g over its rows: weights act as gradient multipliers, and weights with mean 1 keep the step
+ *             size.  A Newton leaf stores the properly weighted ratio sum w g / (sum w h + leaf_l2).  A zero-weight row still counts as a row of
+ *             its leaf: to drop rows use rows / subsample.  Hessian- or weight-aware split scores, min_child_weight, weighted metrics, weights
+ *             in fit(), step() and refit_leaves, and row-sharded models are out of scope.
+ *   gbrl_hip_fit_prepared_weighted(.., leaf_update, leaf_l2, weights, weights_on_device, valid_weights, valid_weights_on_device, loss_out, ..,
+ *     best_n_trees, weight_max_out)  gbrl_hip_fit_prepared_leaf plus the training weights [n] and the validation weights [valid rows] (each
+ *     may be NULL); the older calls are this one with both NULL and enqueue the kernels and arguments they always did.  The weight rides in the
+ *     launches that advance the held predictions and sum the Newton leaves as one more float per row; a weighted rmse run takes its training
+ *     loss from the held prediction (gbrl_hip_objective_gradient_weighted's loss, bit for bit), not from the column sums of the gradient.
+ *     valid_weights weigh valid_loss_out only.  *weight_max_out (may be NULL): the largest training weight, 0 without weights.  The model is
+ *     byte for byte the loop objective_gradient_weighted -> step_prepared -> newton_leaves_prepared_weighted(weight_max) ->
+ *     predict_continue_prepared.  Refused before anything changes (GBRL_HIP_E_INVALID): an entry of either vector that is NaN, negative,
+ *     infinite or above 65536 (the message names the first such row), W == 0, valid_weights without valid_ds; (GBRL_HIP_E_UNSUPPORTED):
+ *     valid_weights with a metric -- the metrics are exact integer counts of rows.  Training weights with a metric are fine.
+ *   gbrl_hip_objective_gradient_weighted(m, pred, .., targets, .., weights, weights_on_device, n, objective, grad_out, loss_out)
+ *     gbrl_hip_objective_gradient with weights [n] (NULL: that call): grad_out = g_w, *loss_out the weighted loss.  Refused: a bad entry, W == 0.
+ *   gbrl_hip_newton_leaves_prepared_weighted(.., leaf_l2, weights, weights_on_device, weight_max, sums_out, bits_out, values_out)
+ *     gbrl_hip_newton_leaves_prepared with weights [n_rows], indexed by position.  Refused before anything changes: a bad entry; a weight_max
+ *     below the largest weight given, above 65536 or NaN; a weight_max >= 0 without weights.  (No W is taken: all-zero weights leave every leaf
+ *     with its regularised value 0 / leaf_l2.)
+ *   gbrl_hip_objective_gradient_host_weighted / gbrl_hip_objective_hessian_host_weighted(.., weights, ..)  the two rules on the host with weights
+ *     [n] (NULL: the unweighted call); a bad entry is refused.  gbrl_hip_newton_sum_bits_weighted(m, weight_max): the bits, or GBRL_HIP_E_INVALID
+ *     for a weight_max that is NaN, negative or above 65536. */
+#define GBRL_HIP_WEIGHT_MAX 65536.0f
+int gbrl_hip_fit_prepared_weighted(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                                   const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                   double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update,
+                                   double leaf_l2, const float *weights /*[n]*/, int weights_on_device, const float *valid_weights /*[valid rows]*/,
+                                   int valid_weights_on_device, float *loss_out, double *valid_loss_out /*[iterations + 1]*/,
+                                   double *valid_metric_out /*[iterations + 1]*/, int *iterations_done, int *best_n_trees, float *weight_max_out);
+int gbrl_hip_objective_gradient_weighted(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device,
+                                         const float *weights /*[n]*/, int weights_on_device, int n, int objective, float *grad_out /*[n, output_dim]*/,
+                                         double *loss_out);
+int gbrl_hip_newton_leaves_prepared_weighted(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
+                                             const float *pred, int pred_on_device, const void *targets, int targets_on_device, int objective, int tree,
+                                             double leaf_l2, const float *weights /*[n_rows]*/, int weights_on_device, float weight_max,
+                                             int64_t *sums_out /*[leaves, 2 output_dim + 1]*/, int *bits_out, float *values_out /*[leaves, output_dim]*/);
+int gbrl_hip_objective_gradient_host_weighted(const float *pred, const void *targets, const float *weights /*[n]*/, int n, int D, int objective,
+                                              float *grad_out /*[n, D]*/);
+int gbrl_hip_objective_hessian_host_weighted(const float *pred, const float *weights /*[n]*/, int n, int D, int objective, float *hess_out /*[n, D]*/);
+int gbrl_hip_newton_sum_bits_weighted(int64_t m, float weight_max);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
