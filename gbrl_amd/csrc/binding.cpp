@@ -760,6 +760,104 @@ py::array_t<int32_t> sample_rows_host_impl(int n, double subsample, uint64_t see
     return out;
 }
 
+// Extension: one-side sampling (include/gbrl_hip.h, "One-side sampling").  The gradient rows of a range: float32 [n, D] or [n] (D = 1).
+struct GossGrads { Input g; int n = 0, D = 1; bool flat = false; };
+GossGrads read_goss_grads(py::object &grads, const std::string &fn) {
+    GossGrads r;
+    r.g = read_input(grads, "grads", false, fn, false);
+    if (!r.g.ptr) fail("Cannot call " + fn + " without grads!");
+    if (r.g.shape.empty() || r.g.shape.size() > 2) fail("grads must be a float32 array of shape (n, D) or (n,)");
+    r.flat = r.g.shape.size() == 1;
+    r.n = static_cast<int>(r.g.shape[0]);
+    r.D = r.flat ? 1 : static_cast<int>(r.g.shape[1]);
+    return r;
+}
+
+// gbrl_cpp.goss_rows_host(grads, top_rate, other_rate, seed=0, draw=0, row0=0) -> (rows int32 [m], factor float32 [m])
+py::tuple goss_rows_host_impl(py::object &grads, double top_rate, double other_rate, uint64_t seed, int draw, int row0) {
+    GossGrads in = read_goss_grads(grads, "goss_rows_host");
+    if (in.g.on_device) fail("goss_rows_host takes a NumPy array");
+    std::vector<int32_t> rows(static_cast<size_t>(std::max(in.n, 1)));
+    std::vector<float> factor(rows.size());
+    int m = 0;
+    check(gbrl_hip_goss_rows_host(static_cast<const float *>(in.g.ptr), in.D, row0, in.n, top_rate, other_rate, seed, draw, rows.data(), factor.data(), nullptr, &m));
+    py::array_t<int32_t> ro(static_cast<py::ssize_t>(m));
+    py::array_t<float> fo(static_cast<py::ssize_t>(m));
+    std::copy(rows.begin(), rows.begin() + m, ro.mutable_data());
+    std::copy(factor.begin(), factor.begin() + m, fo.mutable_data());
+    return py::make_tuple(ro, fo);
+}
+
+// PreparedDataset.sample_goss(grads, top_rate, other_rate, seed=0, draw=0, start=0, stop=None) -> {'rows', 'factor', 'grads', 'n_top', 'tau_bits'}:
+// NumPy arrays for a NumPy grads, DLPack capsules on the data set's device for a device tuple (each buffer holds stop - start rows, of which the
+// first m are the tensor), as sample_rows hands its rows out.
+py::dict dataset_sample_goss_impl(PyDataset &self, py::object &grads, double top_rate, double other_rate, uint64_t seed, int draw, int start, py::object stop_obj) {
+    const gbrl_hip_dataset_desc d = self.info();
+    const int stop = stop_obj.is_none() ? d.n_rows : stop_obj.cast<int>();
+    if (start < 0 || stop > d.n_rows || stop <= start) {
+        std::stringstream ss;
+        ss << "sample_goss: rows [" << start << ", " << stop << ") are not a non-empty range inside [0, " << d.n_rows << ")";
+        fail(ss.str());
+    }
+    const int n = stop - start;
+    GossGrads in = read_goss_grads(grads, "sample_goss");
+    if (in.n != n) {
+        std::stringstream ss;
+        ss << "sample_goss: grads has " << in.n << " rows, the range [" << start << ", " << stop << ") has " << n;
+        fail(ss.str());
+    }
+    const size_t n_el = static_cast<size_t>(n) * static_cast<size_t>(std::max(in.D, 1));
+    const bool dev = in.g.on_device;
+    int32_t *rp = nullptr;
+    float *fp = nullptr, *gp = nullptr;
+    std::vector<int32_t> hrows;
+    std::vector<float> hfactor, hgrads;
+    if (dev) {
+        rp = static_cast<int32_t *>(gbrl_hip_device_alloc_on(d.device, sizeof(int32_t) * static_cast<size_t>(n)));
+        fp = static_cast<float *>(gbrl_hip_device_alloc_on(d.device, sizeof(float) * static_cast<size_t>(n)));
+        gp = static_cast<float *>(gbrl_hip_device_alloc_on(d.device, sizeof(float) * n_el));
+        if (!rp || !fp || !gp) {
+            if (rp) gbrl_hip_device_free(rp);
+            if (fp) gbrl_hip_device_free(fp);
+            if (gp) gbrl_hip_device_free(gp);
+            fail(gbrl_hip_last_error());
+        }
+    } else {
+        hrows.resize(static_cast<size_t>(n)); hfactor.resize(static_cast<size_t>(n)); hgrads.resize(n_el);
+        rp = hrows.data(); fp = hfactor.data(); gp = hgrads.data();
+    }
+    int rc, m = 0, n_top = 0;
+    uint32_t tau = 0;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_dataset_sample_goss(self.h, static_cast<const float *>(in.g.ptr), in.D, start, n, top_rate, other_rate, seed, draw, rp, fp, gp, dev ? 1 : 0, &m,
+                                          &n_top, &tau);
+    }
+    if (rc != GBRL_HIP_OK) {
+        if (dev) { gbrl_hip_device_free(rp); gbrl_hip_device_free(fp); gbrl_hip_device_free(gp); }
+        fail(gbrl_hip_last_error());
+    }
+    py::dict out;
+    std::vector<int64_t> gshape{static_cast<int64_t>(m)};
+    if (!in.flat) gshape.push_back(in.D);
+    if (dev) {
+        out["rows"] = make_dlpack(rp, {static_cast<int64_t>(m)}, true, d.device, /*int32=*/true);
+        out["factor"] = make_dlpack(fp, {static_cast<int64_t>(m)}, true, d.device);
+        out["grads"] = make_dlpack(gp, gshape, true, d.device);
+    } else {
+        py::array_t<int32_t> ro(static_cast<py::ssize_t>(m));
+        py::array_t<float> fo(static_cast<py::ssize_t>(m));
+        py::array_t<float> go(std::vector<py::ssize_t>(gshape.begin(), gshape.end()));
+        std::copy(hrows.begin(), hrows.begin() + m, ro.mutable_data());
+        std::copy(hfactor.begin(), hfactor.begin() + m, fo.mutable_data());
+        std::copy(hgrads.begin(), hgrads.begin() + static_cast<size_t>(m) * in.D, go.mutable_data());
+        out["rows"] = ro; out["factor"] = fo; out["grads"] = go;
+    }
+    out["n_top"] = py::int_(n_top);
+    out["tau_bits"] = py::int_(tau);
+    return out;
+}
+
 // Extension: the walk over a data set's bin codes (include/gbrl_hip.h).  condition_bins(thresholds) -> int32 array shaped like feature_values.
 py::array_t<int32_t> condition_bins_impl(PyGBRL &self, py::object &thresholds) {
     const gbrl_hip_metadata md = self.meta();
@@ -839,8 +937,17 @@ Input read_weights(py::object &weights, const char *name, const std::string &fn,
 // with either.  A missing valid_targets is left to the C ABI's message.
 py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
                              int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name,
-                             py::object metric_obj, const std::string &leaf_update_name, double leaf_l2, py::object &weights, py::object &valid_weights) {
+                             py::object metric_obj, const std::string &leaf_update_name, double leaf_l2, py::object &weights, py::object &valid_weights,
+                             py::object goss_obj) {
     const gbrl_hip_metadata md = self.meta();
+    double goss_top = 0.0, goss_other = 0.0;
+    if (!goss_obj.is_none()) {   // goss=(top_rate, other_rate); an other_rate of 0 is refused here, since 0 means "off" below
+        py::sequence g = py::isinstance<py::sequence>(goss_obj) ? goss_obj.cast<py::sequence>() : py::sequence();
+        if (!py::isinstance<py::sequence>(goss_obj) || g.size() != 2) fail("fit_prepared: goss must be None or a pair (top_rate, other_rate)");
+        goss_top = g[0].cast<double>();
+        goss_other = g[1].cast<double>();
+        if (goss_other == 0.0) fail("fit_prepared: goss needs other_rate in (0, 1], got 0");
+    }
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     const int objective = parse_objective(objective_name), leaf_update = parse_leaf_update(leaf_update_name);
     const int metric = metric_obj.is_none() ? GBRL_HIP_METRIC_NONE : parse_metric(metric_obj.cast<std::string>());
@@ -858,10 +965,10 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_weighted(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
-                                            colsample, seed, objective, metric, leaf_update, leaf_l2, static_cast<const float *>(w.ptr), w.on_device,
-                                            static_cast<const float *>(wv.ptr), wv.on_device, &loss, dsv ? curve.data() : nullptr,
-                                            dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max);
+        rc = gbrl_hip_fit_prepared_goss(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                        colsample, seed, objective, metric, leaf_update, leaf_l2, static_cast<const float *>(w.ptr), w.on_device,
+                                        static_cast<const float *>(wv.ptr), wv.on_device, goss_top, goss_other, &loss, dsv ? curve.data() : nullptr,
+                                        dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max);
     }
     check(rc);
     if (!dsv) return py::float_(loss);
@@ -1244,10 +1351,29 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "the device without atomics (two calls give the same bytes), without replacement.  subsample in [2**-24, 1], seed in [0, 2**64), draw >= 0.\n"
             "torch.from_dlpack(capsule) is usable as rows= of step_prepared and predict_continue_prepared ((t.data_ptr(), (m,), 'torch.int32', 'cuda'));\n"
             "fit_prepared(subsample=) uses draw = the model's tree count before the step.  m may be 0: a tensor of shape (0,).");
+    pds.def("sample_goss", &dataset_sample_goss_impl, py::arg("grads"), py::arg("top_rate"), py::arg("other_rate"), py::arg("seed") = 0, py::arg("draw") = 0,
+            py::arg("start") = 0, py::arg("stop") = py::none(),
+            "sample_goss(grads, top_rate, other_rate, seed=0, draw=0, start=0, stop=None) -> dict\n\n"
+            "Gradient-based one-side sampling of the data set rows [start, stop) (stop=None: n_rows) on the device: grads float32 [stop - start, D] (or\n"
+            "[stop - start]) are their gradient rows.  Returns 'rows' (int32 [m], absolute, ascending), 'factor' (float32 [m]: 1 for a top row, else\n"
+            "fl32((1 - top_rate) / other_rate)), 'grads' (float32 [m, D] shaped like the input: the kept gradient rows with the factor applied), 'n_top'\n"
+            "(floor(top_rate * rows)) and 'tau_bits' (the key of the n_top-th largest score; 0x80000000 when n_top == 0) -- gbrl_cpp.goss_rows_host(grads, ...,\n"
+            "row0=start) byte for byte.  A NumPy grads gives NumPy arrays; a device tuple gives DLPack capsules on the data set's device (torch.from_dlpack),\n"
+            "usable as step_prepared(ds, grads, rows=rows).  The k-th largest score is selected exactly by a radix count on the device; a kept row's position\n"
+            "is its rank: two calls return the same bytes.  fit_prepared(goss=) uses draw = the model's tree count before the step.  m may be 0.");
     m.def("sample_rows_host", &sample_rows_host_impl, py::arg("n"), py::arg("subsample"), py::arg("seed") = 0, py::arg("draw") = 0, py::arg("row0") = 0,
           "sample_rows_host(n, subsample, seed=0, draw=0, row0=0) -> int32 NumPy array [m]\n\n"
           "The row sampler's rule on the host (no device is needed): the rows of [row0, row0 + n) that (seed, draw) keeps at `subsample`, ascending.\n"
           "PreparedDataset.sample_rows returns the same list from the device.");
+    m.def("goss_rows_host", &goss_rows_host_impl, py::arg("grads"), py::arg("top_rate"), py::arg("other_rate"), py::arg("seed") = 0, py::arg("draw") = 0,
+          py::arg("row0") = 0,
+          "goss_rows_host(grads, top_rate, other_rate, seed=0, draw=0, row0=0) -> (rows int32 [m], factor float32 [m])\n\n"
+          "The one-side sampling rule on the host (no device is needed; include/gbrl_hip.h, 'One-side sampling').  grads float32 [n, D] (or [n]) are the\n"
+          "gradient rows of the rows [row0, row0 + n).  score = the float32 sum over d of fl32(g * g), added in order; key = its bits & 0x7FFFFFFF; the k =\n"
+          "floor(top_rate * n) rows with the largest keys are top (equal keys by row order: exactly k), factor 1; every other row is kept iff the 24-bit hash\n"
+          "of (seed ^ 0x676F737372657374, draw, row) is below floor(other_rate / (1 - top_rate) * 2**24), factor fl32((1 - top_rate) / other_rate).  rows are\n"
+          "absolute and ascending.  PreparedDataset.sample_goss returns the same lists, and the gathered gradients, from the device.  Refused: a NaN rate,\n"
+          "top_rate outside [0, 1), other_rate outside (0, 1], top_rate + other_rate > 1, other_rate / (1 - top_rate) < 2**-24, row0 < 0, no rows, draw < 0.");
     m.def("objective_gradient_host", &objective_gradient_host_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("weights") = py::none(),
           "objective_gradient_host(pred, targets, objective, weights=None) -> float32 NumPy array shaped like pred\n\n"
           "The gradient rule of fit_prepared(objective=) on the host (no device is needed): 'logistic': sigmoid(p) - y, targets float32 like pred;\n"
@@ -1374,12 +1500,13 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         // likewise: fit_prepared(ds, targets, iterations) -> float keeps its generated line; the validation form is the second overload
         g.def("fit_prepared", [](PyGBRL &self, py::object ds, py::object &targets, int iterations) -> float {
             py::object none = py::none();
-            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0, none, none).cast<float>();
+            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0, none, none, none).cast<float>();
         }, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
             "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,\n"
-            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None) -> float | dict\n\n"
+            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None, goss=None)\n"
+            "             -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
             "keeps its bias and continues from all of them (unlike fit()); they must compare against the data set's thresholds.  No shuffle: permute before\n"
@@ -1435,13 +1562,24 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "min_data_in_leaf) are unchanged; a gradient leaf stores the mean of w g over its rows, so weights act as gradient multipliers and weights with\n"
             "mean 1 keep the step size; a zero-weight row still counts as a row of its leaf (to drop rows use subsample or step_prepared(rows=)); the metrics\n"
             "stay unweighted.  Refused before anything changes: an entry that is NaN, negative, infinite or above 65536 (the row is named), W == 0, a wrong\n"
-            "length or dtype, valid_weights without valid=, valid_weights with eval_metric (not supported).";
+            "length or dtype, valid_weights without valid=, valid_weights with eval_metric (not supported).\n"
+            "goss=(top_rate, other_rate) (with everything above but subsample < 1): gradient-based one-side sampling, LightGBM's data_sample_strategy='goss'.\n"
+            "Every tree is grown on ds.sample_goss(g, top_rate, other_rate, seed, draw, start, stop) of its batch, draw = the tree count before the step: the\n"
+            "floor(top_rate * rows) rows with the largest float32 sum of squared gradient entries (ties by row order, exactly that many), and of the rest those\n"
+            "whose 24-bit hash is below floor(other_rate / (1 - top_rate) * 2**24) -- a Bernoulli draw like subsample's, not LightGBM's draw of an exact count --\n"
+            "with their gradient rows multiplied by fl32((1 - top_rate) / other_rate).  The k-th largest norm is selected on the device and never visits the\n"
+            "host.  With weights= the scores are those of fl32(w * g).  'newton' leaves sum over the kept rows with the weights fl32(w * factor) and weight_max =\n"
+            "fl32(max w * amp) and are unbiased; a 'gradient' leaf stores the mean of the amplified gradients over the kept rows, about 1 / (top_rate + other_rate)\n"
+            "times the batch mean, so such a fit steps that much further per tree (lower the learning rate).  A draw that keeps no row takes the whole batch unamplified.  goss=None is the call without the keyword.  Refused before anything\n"
+            "changes: a NaN rate, top_rate outside [0, 1), other_rate outside (0, 1], top_rate + other_rate > 1, other_rate / (1 - top_rate) < 2**-24, goss with\n"
+            "subsample < 1, and a largest weight (1 without weights=) whose product with the amplification is above 65536.";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
               py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse", py::arg("eval_metric") = py::none(),
-              py::arg("leaf_update") = "gradient", py::arg("leaf_l2") = 1.0, py::arg("weights") = py::none(), py::arg("valid_weights") = py::none());
+              py::arg("leaf_update") = "gradient", py::arg("leaf_l2") = 1.0, py::arg("weights") = py::none(), py::arg("valid_weights") = py::none(),
+              py::arg("goss") = py::none());
     }
     g.def("newton_leaves_prepared", &newton_leaves_prepared_impl, py::arg("ds"), py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("leaf_l2") = 1.0,
           py::arg("rows") = py::none(), py::arg("tree") = -1, py::arg("weights") = py::none(), py::arg("weight_max") = py::none(),

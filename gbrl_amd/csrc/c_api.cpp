@@ -563,7 +563,7 @@ int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset
     });
 }
 
-// The one body of the seven gbrl_hip_fit_prepared* spellings.  valid_required (gbrl_hip_fit_prepared_valid): a NULL valid_ds is a null data set;
+// The one body of the eight gbrl_hip_fit_prepared* spellings.  valid_required (gbrl_hip_fit_prepared_valid): a NULL valid_ds is a null data set;
 // otherwise it means "no validation", the other validation arguments must then be at their defaults, *iterations_done = iterations and
 // *best_n_trees is left alone.  Every refusal that needs no data set comes before a handle is resolved, the validation handle before the
 // training handle, and nothing is written on a refusal.
@@ -706,6 +706,30 @@ int gbrl_hip_fit_prepared_weighted(gbrl_hip_model *m, const gbrl_hip_dataset *ds
     return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
                              {subsample, colsample, seed, objective, metric, leaf_update, leaf_l2, weights, weights_on_device != 0}, loss_out, valid_loss_out,
                              iterations_done, best_n_trees, valid_metric_out, valid_weights, valid_weights_on_device, weight_max_out);
+}
+
+// ---- one-side sampling: the rule on the host, the device kernels on a data set's rows, fit_prepared with the draw
+int gbrl_hip_goss_rows_host(const float *grads, int output_dim, int row0, int n, double top_rate, double other_rate, uint64_t seed, int draw, int32_t *rows_out,
+                            float *factor_out, float *grads_out, int *count) {
+    return guarded([&] { gbrl::Engine::goss_rows_host(grads, output_dim, row0, n, top_rate, other_rate, seed, draw, rows_out, factor_out, grads_out, count); });
+}
+
+int gbrl_hip_dataset_sample_goss(const gbrl_hip_dataset *ds, const float *grads, int output_dim, int row0, int n, double top_rate, double other_rate, uint64_t seed,
+                                 int draw, int32_t *rows_out, float *factor_out, float *grads_out, int on_device, int *count, int *n_top, uint32_t *tau_bits) {
+    return guarded([&] {
+        gbrl::Engine::sample_goss(&live_dataset(ds), grads, output_dim, row0, n, top_rate, other_rate, seed, draw, rows_out, factor_out, grads_out, on_device != 0, count,
+                                  n_top, tau_bits);
+    });
+}
+
+int gbrl_hip_fit_prepared_goss(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                               const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds, double min_delta,
+                               double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update, double leaf_l2, const float *weights,
+                               int weights_on_device, const float *valid_weights, int valid_weights_on_device, double goss_top, double goss_other, float *loss_out,
+                               double *valid_loss_out, double *valid_metric_out, int *iterations_done, int *best_n_trees, float *weight_max_out) {
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, colsample, seed, objective, metric, leaf_update, leaf_l2, weights, weights_on_device != 0, goss_top, goss_other}, loss_out,
+                             valid_loss_out, iterations_done, best_n_trees, valid_metric_out, valid_weights, valid_weights_on_device, weight_max_out);
 }
 
 int gbrl_hip_newton_leaves_prepared_weighted(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,

@@ -132,6 +132,7 @@ struct FitOptions {
     double subsample = 1.0, colsample = 1.0; uint64_t seed = 0; int objective = 0 /* kern::kObjRmse */; int metric = 0 /* kern::kMetricNone */;
     int leaf_update = 0 /* kern::kLeafGradient; 1: kern::kLeafNewton */; double leaf_l2 = 1.0;
     const float *weights = nullptr /* float32 [n], one per data set row; nullptr: the loop without weights */; bool weights_dev = false;
+    double goss_top = 0.0, goss_other = 0.0 /* 0: off; else sample_core.h's one-side sampling takes the place of the subsample draw */;
 };
 
 class Engine {
@@ -192,6 +193,12 @@ class Engine {
     //   subsample  < 1: the tree grows on a sample of its batch, drawn once prediction and gradient are up to date with draw = the tree count before
     //              the step (a continued fit continues the sequence); the gradient rows are gathered in the same pass and m is read back (4 bytes).
     //              A draw that keeps no row takes the whole batch.  == 1 IS the unsampled loop: no sampler launch, no gather, no phase.
+    //   goss       goss_other > 0 (sample_core.h: one-side sampling): the draw of the iteration is kern::sample_goss over the batch, on G as the held
+    //              prediction's launch left it (with weights: the scores are those of fl32(w * g)), draw = the tree count before the step; tau stays on
+    //              the device and m is read back (4 bytes), as for subsample.  A draw that keeps no row takes the whole batch unamplified.  newton: the
+    //              sums run over the kept rows with the effective weights e_r = fl32(w_r * factor_r) (w_r = 1 without weights), written by absolute row
+    //              by the sampler's write pass; the quantum's weight_max is fl32(wmax * amp).  Refused: check_goss's list, goss with subsample < 1, and
+    //              fl32(wmax * amp) > kWeightMax once the weights are known, before any tree is grown.  goss_other == 0 enqueues nothing new.
     //   colsample  < 1: and on sample_cols_host's columns for the same seed and draw, by step_prepared's cols path; == 1, or a draw of every column
     //              (F == 1): nothing of it runs.  The held prediction, validation, the stopping rule and the loss see all rows and columns.
     //   valid      a set with ds's thresholds_id (it may be ds).  loss_out[k], k = 0 .. done, is the loss of the first T0 + k trees (T0: the count at
@@ -232,7 +239,7 @@ class Engine {
     // What fit_prepared refuses without a data set in hand, in this order (the C ABI runs it before it resolves the handles, so that these
     // refusals do not depend on a data set being at hand; valid->ds is not looked at): the model checks of step_prepared; null targets;
     // iterations < 0; batch_size <= 0; max_depth > 32, n_bins outside [1, 65534], output_dim > 128 (Unsupported); check_subsample;
-    // check_colsample; check_objective; check_leaf_update; a metric without valid, check_metric; with valid: null targets, rounds < 0, min_delta negative or NaN.
+    // check_colsample; with goss_other != 0: check_goss, goss with subsample < 1; check_objective; check_leaf_update; a metric without valid, check_metric; with valid: null targets, rounds < 0, min_delta negative or NaN.
     void precheck_fit(const void *targets, int iterations, const FitOptions &opt, const FitValid *valid) const;
     // Extension: row subsampling (stochastic gradient boosting).  The sampler is sample_core.h's pure function of (seed, draw, row): a row is
     // kept iff its 24-bit hash is below floor(subsample * 2^24); the sample of [row0, row0 + n) is the ascending list of its kept absolute indices.
@@ -243,6 +250,17 @@ class Engine {
     static void check_subsample(const char *what, double subsample);
     static void sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, int *count);
     static void sample_rows(const PreparedDataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, bool out_dev, int *count);
+    // Extension: one-side sampling (GOSS; sample_core.h has the rule).  goss_rows_host: the rule on the host for the rows [row0, row0 + n) with gradient rows
+    // G [n][D]: rows_out / factor_out [n] get the m kept rows and their factors (1 or amp), G_out (nullable, [n][D]) their gradient rows with the
+    // factor applied, *count = m.  sample_goss: the same from the device kernels (kern::sample_goss) on the data set's device and the null stream; G,
+    // rows_out, factor_out and G_out are all host or all device (io_dev); *n_top = floor(top_rate * n), *tau_bits = the k-th largest key (kGossNoTau
+    // for k == 0), read back from the device.  Refused (InvalidArgument): check_goss's list (a NaN rate, top_rate outside [0, 1), other_rate outside
+    // (0, 1], top_rate + other_rate > 1, other_rate / (1 - top_rate) < 2^-24), what sample_rows refuses about the range and the draw, D outside [1, 512].
+    static void check_goss(const char *what, double top_rate, double other_rate);
+    static void goss_rows_host(const float *G, int D, int row0, int n, double top_rate, double other_rate, uint64_t seed, int draw, int32_t *rows_out,
+                               float *factor_out, float *G_out, int *count);
+    static void sample_goss(const PreparedDataset *ds, const float *G, int D, int row0, int n, double top_rate, double other_rate, uint64_t seed, int draw,
+                            int32_t *rows_out, float *factor_out, float *G_out, bool io_dev, int *count, int *n_top, uint32_t *tau_bits);
     // The engine's fused sampler + gather on the CURRENT device and the null stream (what fit_prepared's loop enqueues per iteration; the tests
     // reach it through gbrl_hip_sample_gather): device G [n][D] -> device rows_out [n], G_out [n][D], *count = m.
     static void sample_gather(int row0, int n, double subsample, uint64_t seed, int draw, const float *G, int D, int32_t *rows_out, float *G_out, int *count);
@@ -535,6 +553,7 @@ class Engine {
     DevBuf m_code_bins_, m_code_pack_, m_code_nodes_;
     DevBuf d_fp_pred_, d_fp_grads_, d_fp_iota_, d_fp_targets_;   // fit_prepared: held prediction [n][D], batch gradients, 0..n-1, staged targets
     DevBuf d_fp_vpred_, d_fp_vtargets_, d_fp_vpart_, d_fp_vsums_;   // its validation rows: held prediction [n_v][D], staged targets, loss partials, one sum per iteration
+    DevBuf d_fp_gscratch_, d_fp_sfactor_, d_fp_eff_;   // its one-side draws: the selection's scratch (kern::goss_scratch), the kept rows' factors, the effective weights by absolute row
     DevBuf d_fp_srows_, d_fp_sgrads_, d_fp_sscratch_;   // its sampled iterations: the kept rows of the batch, their gradient rows, block counts + m
     DevBuf d_obj_weights_, d_fp_weights_, d_fp_vweights_, d_wstat_, d_wpart_, d_wsum_;   // row weights: staged vectors; kern::weight_stats' two ints, partials and sum
     DevBuf d_obj_pred_, d_obj_targets_, d_obj_grad_, d_obj_part_, d_obj_sum_, d_obj_counts_;   // objective_gradient: staged inputs, the gradient, loss partials and sum; class counts + first bad row

@@ -13,6 +13,8 @@
 //                                      back, step_prepared's body grows on the subset) and on a sample of the columns (the host rule of
 //                                      sample_core.h per iteration, step_prepared's cols path); a classifier's metric of the validation rows
 //                                      per iteration, which then decides the stopping rule and best_n_trees in place of the loss
+//                                      ; with goss the row draw is kern::goss_select + kern::goss_sample_passes (one-side sampling: the largest
+//                                      gradients and an amplified draw of the rest; tau stays on the device) in place of kern::sample_rows
 //   Engine::newton_leaves_prepared     one tree's leaves set to sum g / (sum h + leaf_l2) over a data set's rows (newton_core.h; kern::newton_leaf_sums), the
 //                                      rules on the host beside it (objective_hessian_host, newton_values_host); fit_prepared(leaf_update = newton) runs its
 //                                      body after every step
@@ -598,6 +600,10 @@ void Engine::precheck_fit(const void *targets, int iterations, const FitOptions 
     if (md.output_dim > 128) throw Unsupported("predict: output_dim > 128");
     check_subsample("fit_prepared", opt.subsample);
     check_colsample("fit_prepared", opt.colsample);
+    if (opt.goss_other != 0.0) {   // (0 means off; a NaN is not 0: it reaches check_goss)
+        check_goss("fit_prepared", opt.goss_top, opt.goss_other);
+        if (opt.subsample < 1.0) throw InvalidArgument("fit_prepared: goss and subsample < 1 are two draws of one iteration's rows: use one of them");
+    }
     check_objective("fit_prepared", opt.objective, md.output_dim);
     check_leaf_update("fit_prepared", opt.objective, opt.leaf_update, opt.leaf_l2);
     if (opt.metric != kern::kMetricNone) {
@@ -668,13 +674,15 @@ struct Engine::FitRun {
     std::vector<unsigned long long> h_mrow;
     std::vector<double> score;
     bool sampled = false, colsampled = false;
+    const bool goss;                                      // one-side sampling takes the place of the subsample draw
     int32_t *d_srows = nullptr, *d_sscratch = nullptr;   // a sampled iteration: the kept rows of the batch, the sampler's block counts + m
     float *Gs = nullptr;                                  // and their gradient rows
+    float *d_sfactor = nullptr, *d_eff = nullptr;         // goss: the kept rows' factors; newton: their effective weights fl32(w * factor) by absolute row
     int start = 0, bn = 0;                               // the batch cursor
 
     FitRun(Engine &eng, const PreparedDataset *data, int iters, const FitOptions &o, FitValid *valid)
         : e(eng), ds(data), opt(o), v(valid), iterations(iters), n(data->n), D(eng.model.meta.output_dim), bs(eng.model.meta.batch_size), T0(eng.model.meta.n_trees),
-          W(static_cast<double>(data->n)), mC(kern::metric_count_columns(o.objective == kern::kObjSoftmax, eng.model.meta.output_dim)) {
+          W(static_cast<double>(data->n)), mC(kern::metric_count_columns(o.objective == kern::kObjSoftmax, eng.model.meta.output_dim)), goss(o.goss_other != 0.0) {
         bn = start + bs < n ? bs : n - start;                                       // fitter.cpp:120
     }
 
@@ -696,6 +704,8 @@ struct Engine::FitRun {
             dvw = v->weights_dev ? v->weights : e.upload(e.d_fp_vweights_, v->weights, static_cast<size_t>(v->ds->n), "H2D validation weights");
             Wv = e.check_weights("fit_prepared (valid_weights)", dvw, v->ds->n, true).sum;
         }
+        if (goss && kern::obj_weighted(dw ? wmax : 1.0f, kern::goss_plan(n, opt.goss_top, opt.goss_other).amp) > kern::kWeightMax)
+            throw InvalidArgument("fit_prepared: the largest weight times goss's amplification (1 - top_rate) / other_rate is above 65536: the Newton quantum has no room for it");
         if (opt.metric == kern::kMetricAuc) count_positives();
         if (opt.leaf_update == kern::kLeafNewton && opt.objective == kern::kObjLogistic) check_unit_targets();
         if (opt.objective != kern::kObjSoftmax) return;
@@ -844,11 +854,17 @@ struct Engine::FitRun {
     void prepare_draws() {
         sampled = opt.subsample < 1.0;
         colsampled = opt.colsample < 1.0 && kern::sample_cols_count(ds->F, opt.colsample) < ds->F;
-        if (!sampled) return;
+        if (!sampled && !goss) return;
         const int cap = std::min(bs, n);
         d_srows = static_cast<int32_t *>(e.d_fp_srows_.ensure(sizeof(int32_t) * static_cast<size_t>(cap)));
         Gs = static_cast<float *>(e.d_fp_sgrads_.ensure(sizeof(float) * static_cast<size_t>(cap) * D));
-        d_sscratch = static_cast<int32_t *>(e.d_fp_sscratch_.ensure(sizeof(int32_t) * (static_cast<size_t>(kern::sample_rows_blocks(cap)) + 1)));
+        if (!goss) {
+            d_sscratch = static_cast<int32_t *>(e.d_fp_sscratch_.ensure(sizeof(int32_t) * (static_cast<size_t>(kern::sample_rows_blocks(cap)) + 1)));
+            return;
+        }
+        d_sscratch = static_cast<int32_t *>(e.d_fp_gscratch_.ensure(sizeof(int32_t) * kern::goss_scratch_words(cap)));
+        d_sfactor = static_cast<float *>(e.d_fp_sfactor_.ensure(sizeof(float) * static_cast<size_t>(cap)));
+        if (opt.leaf_update == kern::kLeafNewton) d_eff = static_cast<float *>(e.d_fp_eff_.ensure(sizeof(float) * static_cast<size_t>(n)));
     }
     // One tree on the batch under the cursor.  Both draws are those of the tree count before the step.
     void iterate() {
@@ -869,6 +885,18 @@ struct Engine::FitRun {
             e.phase_end("sample_rows");
             hip_check(hipStreamSynchronize(s), "sync");
             if (kept > 0) { g = Gs; rows = d_srows; m = kept; }
+        } else if (goss) {   // likewise; the selection's tau stays on the device
+            e.phase_begin();
+            const kern::GossPlan plan = kern::goss_plan(bn, opt.goss_top, opt.goss_other);
+            const kern::GossScratch gs = kern::goss_scratch(d_sscratch, bn);
+            kern::goss_select(bn, plan.k, G, D, gs, s);
+            e.phase_end("goss_select"); e.phase_begin();
+            kern::goss_sample_passes(start, bn, plan.thr, plan.amp, opt.seed, trees, gs, G, D, d_srows, d_sfactor, Gs, dw, d_eff, s);
+            int32_t kept = 0;
+            hip_check(hipMemcpyAsync(&kept, d_sscratch, sizeof(kept), hipMemcpyDeviceToHost, s), "D2H sample count");
+            e.phase_end("sample_goss");
+            hip_check(hipStreamSynchronize(s), "sync");
+            if (kept > 0) { g = Gs; rows = d_srows; m = kept; }
         }
         if (colsampled) {
             kern::sample_cols(ds->F, opt.colsample, opt.seed, trees, e.fit_cols_);
@@ -878,8 +906,11 @@ struct Engine::FitRun {
         }
         if (opt.leaf_update == kern::kLeafNewton) {   // the new tree's leaves from the rows it was grown on, at the held prediction over the trees before it
             const bool kept = rows == d_srows && rows != nullptr;
+            const bool amplified = kept && goss;   // the kept rows of a one-side draw carry fl32(w * factor), with room for fl32(wmax * amp)
+            const float amp = amplified ? kern::goss_plan(bn, opt.goss_top, opt.goss_other).amp : 1.0f;
             e.newton_leaves_run("fit_prepared", ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), kept ? d_srows : nullptr, kept ? 0 : start}, m, train.P,
-                                dtar, /*abs_index=*/true, opt.objective, e.model.meta.n_trees - 1, opt.leaf_l2, generic, nullptr, nullptr, nullptr, dw, wmax);
+                                dtar, /*abs_index=*/true, opt.objective, e.model.meta.n_trees - 1, opt.leaf_l2, generic, nullptr, nullptr, nullptr,
+                                amplified ? d_eff : dw, amplified ? kern::obj_weighted(dw ? wmax : 1.0f, amp) : wmax);
         }
         start += bn;                                                                // fitter.cpp:228-231
         if (start >= n) start = 0;

@@ -13,6 +13,7 @@
 //   PreparedDataset::codes_to_host   the codes on the host, all rows or a gathered subset of rows and / or columns
 //   Engine::sample_rows_host / sample_rows / sample_gather   the row sampler of sample_core.h: the rule on the host, kern::sample_rows on a data
 //                             set's row range, and with the gathered rows of a matrix (what fit_prepared's sampled iterations enqueue)
+//   Engine::goss_rows_host / sample_goss   one-side sampling of sample_core.h: the rule on the host, kern::sample_goss on a data set's row range
 // None of the growth kernels is touched: integer histograms do not depend on which of the optional buffers a path reads.
 #include "engine_step_detail.h"
 #include "sample_core.h"
@@ -378,6 +379,66 @@ void Engine::sample_gather(int row0, int n, double subsample, uint64_t seed, int
     hip_check(hipMemcpyAsync(&m, d_scratch, sizeof(m), hipMemcpyDeviceToHost, s), "D2H sample count");
     hip_check(hipStreamSynchronize(s), "sync");
     *count = m;
+}
+
+// ---- one-side sampling (sample_core.h): the checks, the rule on the host, the device kernels on a data set's rows
+void Engine::check_goss(const char *what, double a, double b) {
+    if (!kern::goss_rates_ok(a, b))
+        throw InvalidArgument(std::string(what) + ": goss needs top_rate in [0, 1), other_rate in (0, 1], top_rate + other_rate <= 1 and other_rate / (1 - top_rate) >= 2^-24 "
+                              "(and no NaN), got (" + std::to_string(a) + ", " + std::to_string(b) + ")");
+}
+
+void Engine::goss_rows_host(const float *G, int D, int row0, int n, double a, double b, uint64_t seed, int draw, int32_t *rows_out, float *factor_out, float *G_out,
+                            int *count) {
+    if (factor_out == nullptr) throw InvalidArgument("goss_rows_host: null output");
+    check_sample_range("goss_rows_host", row0, n, 1.0, draw, rows_out, count);
+    check_goss("goss_rows_host", a, b);
+    if (G == nullptr) throw InvalidArgument("goss_rows_host: no gradients");
+    if (D < 1 || D > 512) throw InvalidArgument("goss_rows_host: D must be in [1, 512]");
+    *count = kern::goss_rows(G, D, row0, n, a, b, seed, draw, rows_out, factor_out, G_out, nullptr, nullptr);
+}
+
+void Engine::sample_goss(const PreparedDataset *ds, const float *G, int D, int row0, int n, double a, double b, uint64_t seed, int draw, int32_t *rows_out,
+                         float *factor_out, float *G_out, bool io_dev, int *count, int *n_top, uint32_t *tau_bits) {
+    if (ds == nullptr) throw InvalidArgument("sample_goss: null data set");
+    if (factor_out == nullptr || G_out == nullptr) throw InvalidArgument("sample_goss: null output");
+    check_sample_range("sample_goss", row0, n, 1.0, draw, rows_out, count);
+    check_goss("sample_goss", a, b);
+    if (G == nullptr) throw InvalidArgument("sample_goss: no gradients");
+    if (D < 1 || D > 512) throw InvalidArgument("sample_goss: D must be in [1, 512]");
+    if (row0 >= ds->n || n > ds->n - row0)
+        throw InvalidArgument("sample_goss: rows [" + std::to_string(row0) + ", " + std::to_string(static_cast<long long>(row0) + n) + ") are outside [0, " + std::to_string(ds->n) + ")");
+    DeviceScope scope(ds->device);
+    hipStream_t s = nullptr;
+    const size_t n_el = static_cast<size_t>(n) * D;
+    DevBuf scratch, g_in, rows, factor, g_out;
+    const kern::GossScratch gs = kern::goss_scratch(static_cast<int32_t *>(scratch.ensure(sizeof(int32_t) * kern::goss_scratch_words(n))), n);
+    const float *dG = G;
+    int32_t *d_rows = rows_out;
+    float *d_factor = factor_out, *d_gout = G_out;
+    if (!io_dev) {
+        float *up = static_cast<float *>(g_in.ensure(sizeof(float) * n_el));
+        hip_check(hipMemcpyAsync(up, G, sizeof(float) * n_el, hipMemcpyHostToDevice, s), "H2D gradients");
+        dG = up;
+        d_rows = static_cast<int32_t *>(rows.ensure(sizeof(int32_t) * static_cast<size_t>(n)));
+        d_factor = static_cast<float *>(factor.ensure(sizeof(float) * static_cast<size_t>(n)));
+        d_gout = static_cast<float *>(g_out.ensure(sizeof(float) * n_el));
+    }
+    const kern::GossPlan plan = kern::goss_plan(n, a, b);
+    kern::sample_goss(row0, n, plan.k, plan.thr, plan.amp, seed, draw, dG, D, d_rows, d_factor, d_gout, nullptr, nullptr, gs, s);
+    hip_check(hipGetLastError(), "sample_goss launch");
+    int32_t h[6] = {0, 0, 0, 0, 0, 0};   // m, all ties, then the selection's state
+    hip_check(hipMemcpyAsync(h, gs.m_out, sizeof(h), hipMemcpyDeviceToHost, s), "D2H sample count");
+    hip_check(hipStreamSynchronize(s), "sync");
+    const size_t m = static_cast<size_t>(h[0]);
+    if (!io_dev && m > 0) {
+        hip_check(hipMemcpy(rows_out, d_rows, sizeof(int32_t) * m, hipMemcpyDeviceToHost), "D2H sampled rows");
+        hip_check(hipMemcpy(factor_out, d_factor, sizeof(float) * m, hipMemcpyDeviceToHost), "D2H factors");
+        hip_check(hipMemcpy(G_out, d_gout, sizeof(float) * m * D, hipMemcpyDeviceToHost), "D2H sampled gradients");
+    }
+    *count = h[0];
+    if (n_top) *n_top = plan.k;
+    if (tau_bits) *tau_bits = static_cast<uint32_t>(h[2]);
 }
 
 void Engine::sample_rows(const PreparedDataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out, bool out_dev, int *count) {

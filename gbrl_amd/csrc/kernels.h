@@ -231,6 +231,21 @@ constexpr int kSampleRowsPerBlock = 2048, kSampleScanWidth = 512;
 int sample_rows_blocks(int n);
 void sample_rows(int row0, int n, uint32_t thr /*sample_threshold(subsample)*/, uint64_t seed, int32_t draw, const float *G /*nullable*/, int D,
                  int32_t *rows_out, float *G_out /*nullable*/, int32_t *scratch, hipStream_t s);
+// one-side sampling on the device (goss.hip, sample_rows.hip; the rule is sample_core.h's).  sample_goss enqueues, on one stream: the scores and keys
+// of G's rows with the count of their first digit, the MSD radix selection of the k-th largest key (integer counts only; tau, #{key > tau} and the
+// ties to take stay in device memory: gs.state), the tie counts per sampler block and their scan, then the sampler's count / scan / write with the
+// one-side keep rule.  rows_out / factor_out [m], G_out [m][D] (room for n), gs.m_out[0] = m; weights (nullable, by absolute row) and eff_out (nullable,
+// by absolute row: fl32(w * factor) of every kept row) serve fit_prepared's Newton sums.  Nothing waits for the host; the bytes do not depend on scheduling.
+constexpr int kGossDigitBits = 8, kGossDigits = 1 << kGossDigitBits, kGossPasses = 32 / kGossDigitBits;
+struct GossScratch { int32_t *m_out /*[2]: m, all ties*/; uint32_t *state /*[4]: tau, #{key > tau}, take, k*/; uint32_t *hist /*[passes][digits]*/; int32_t *tie_off, *blk /*[blocks] each*/; uint32_t *keys /*[n]*/; };
+size_t goss_scratch_words(int n);
+GossScratch goss_scratch(int32_t *words, int n);
+void sample_goss(int row0, int n, int k /*floor(top_rate * n)*/, uint32_t thr, float amp, uint64_t seed, int32_t draw, const float *G, int D, int32_t *rows_out,
+                 float *factor_out, float *G_out /*nullable*/, const float *weights /*nullable*/, float *eff_out /*nullable*/, const GossScratch &gs, hipStream_t s);
+// the two halves of sample_goss (fit_prepared times them apart): scores, keys, selection and tie counts; then the tie scan and the sampler's passes
+void goss_select(int n, int k, const float *G, int D, const GossScratch &gs, hipStream_t s);
+void goss_sample_passes(int row0, int n, uint32_t thr, float amp, uint64_t seed, int32_t draw, const GossScratch &gs, const float *G, int D, int32_t *rows_out,
+                        float *factor_out, float *G_out, const float *weights, float *eff_out, hipStream_t s);
 
 // ---- split-score histograms (A6) ----
 size_t hist_lds_bytes(int NB, int D, int FG);

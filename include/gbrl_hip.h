@@ -432,6 +432,46 @@ int gbrl_hip_step_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const 
  *   gbrl_hip_sample_rows_geometry(rows_per_block, scan_width)  the rows one block of the sampler owns and the block counts one slice of its scan
  *     takes (diagnostic; no device needed): the sizes at which the kernels take another path.
  *
+ * One-side sampling (new: gradient-based one-side sampling, GOSS -- LightGBM's data_sample_strategy = "goss").  Of the rows [row0, row0 + n) with
+ * gradient rows G float32 [n, D] it keeps the rows with the largest gradients and a hash draw of the rest, whose gradients it amplifies so that the
+ * histogram sums stay unbiased.  One definition for the host and the device (csrc/sample_core.h), with top_rate = a and other_rate = b:
+ *     score   s_r = 0; for d = 0 .. D-1: s_r = fl32(s_r + fl32(g_rd * g_rd))     float32, a separate multiply and add (never contracted)
+ *     key     bits(s_r) & 0x7FFFFFFF          non-negative floats order like their bits; an infinity or a NaN ranks by its bits
+ *     top     k = floor(a * n) in double; tau = the k-th largest key, exactly.  A row is TOP iff its key is above tau, or equals tau and the row is
+ *             among the first k - #{key > tau} such rows in row order: exactly k top rows whatever the ties (on the first tree of a softmax fit every
+ *             row of a class has the same gradient).  k == 0: no top rows; tau is then reported as 0x80000000, above every key.
+ *     other   a row that is not top is kept iff u(seed ^ 0x676F737372657374, draw, row) < min(2^24, floor(p * 2^24)), p = b / (1 - a) in double; u is
+ *             the row sampler's 24-bit hash, the constant ("gossrest") a stream of its own beside the row and column samplers'.  A Bernoulli draw
+ *             like subsample's, NOT LightGBM's sequential draw of an exact count: the number of other rows varies around b * n.
+ *     amp     fl32((1 - a) / b), the quotient in double.  A kept other row's gradient entries become fl32(amp * g) (the weight rule, one float32
+ *             multiply); a top row's entries are copied, so no bit of them changes.
+ *     sample  the ascending list of the kept ABSOLUTE rows, their factor (1 or amp) and their gathered gradient rows with the factor applied.
+ *   Refused by every call below (GBRL_HIP_E_INVALID, before anything is enqueued): a NaN rate, a outside [0, 1), b outside (0, 1], a + b > 1 (in
+ *     double), p < 2^-24, and what gbrl_hip_sample_rows_host refuses about the range and the draw; NULL gradients or outputs, D outside [1, 512].
+ *   gbrl_hip_goss_rows_host(grads, output_dim, row0, n, top_rate, other_rate, seed, draw, rows_out, factor_out, grads_out, count)  the rule on the
+ *     host, no device: rows_out int32 / factor_out float32 [n] get the *count kept rows, grads_out (may be NULL) [n, output_dim] their gradient rows.
+ *   gbrl_hip_dataset_sample_goss(ds, grads, output_dim, row0, n, top_rate, other_rate, seed, draw, rows_out, factor_out, grads_out, on_device, count,
+ *     n_top, tau_bits)  the same bytes from the device kernels, on the data set's device and the null stream; grads and the three outputs (room for n
+ *     rows each) are all on the host or all on that device.  One pass computes scores and keys and counts their first digit; an MSD radix count over
+ *     the 32-bit keys (8 bits a pass, integer counts only) finds tau and the ties to take and leaves them in device memory; the tie counts of the
+ *     sampler's blocks are scanned; then the row sampler's count / scan / write passes run with the keep rule above -- a kept row's position is its
+ *     rank, no atomic hands out a position, two calls give the same bytes.  *n_top = k, *tau_bits = tau (either may be NULL).  Also refused: a NULL
+ *     or destroyed data set, a range outside [0, n_rows).
+ *   gbrl_hip_fit_prepared_goss(.., weights, .., goss_top, goss_other, loss_out, ..)  gbrl_hip_fit_prepared_weighted plus the two rates; the older
+ *     calls are this one with goss_other == 0, which enqueues nothing new.  With goss_other > 0 the one-side draw takes the place of the subsample
+ *     draw: over the batch [start, start + bn), draw = the tree count BEFORE the step, on the gradient as the held prediction's launch left it (with
+ *     weights the scores are those of fl32(w * g), as in LightGBM).  tau never visits the host; the only wait is the 4-byte read-back of the count.
+ *     A draw that keeps no row takes the whole batch unamplified.  newton: the sums run over the kept rows with the effective weights e_r =
+ *     fl32(w_r * factor_r) (w_r = 1 without weights) and weight_max = fl32(wmax * amp).  colsample, validation, metrics, warm starts and batch_size
+ *     < n work as with subsample.  The model is byte for byte the loop objective_gradient -> sample_goss -> step_prepared(rows) ->
+ *     newton_leaves_prepared_weighted(rows, e, weight_max) -> predict_continue_prepared.  Also refused before anything changes: goss with subsample
+ *     < 1; fl32(wmax * amp) > 65536 (wmax = 1 without weights), once the weights are known and before any tree is grown.  There is no warm-up of
+ *     1 / learning_rate unsampled iterations, and GOSS does not reach fit() or step().
+ *     What it does NOT do: like a row weight, the factor is a gradient multiplier.  The histogram SUMS are unbiased, but a gradient leaf stores
+ *     the mean of the amplified gradients over the KEPT rows (the row counts are unchanged), about 1 / (top_rate + other_rate) times the batch
+ *     mean: with leaf_update = gradient a GOSS fit steps that much further per tree (lower the learning rate accordingly).  A Newton leaf stores
+ *     sum e g / (sum e h + leaf_l2), which the amplification leaves unbiased, as in LightGBM.
+ *
  * Column subsampling (new: the other half of stochastic gradient boosting -- LightGBM's feature_fraction, XGBoost's colsample_bytree,
  * scikit-learn's max_features per tree).  A weight of 0 (gbrl_hip_set_feature_weights) only removes a column's candidates from the arg-max; a
  * column subset skips the column's histogram.  The column rule is a definition, on the host, with the row sampler's 24-bit hash u(seed, draw, x):
@@ -643,6 +683,18 @@ int gbrl_hip_objective_gradient_host_weighted(const float *pred, const void *tar
                                               float *grad_out /*[n, D]*/);
 int gbrl_hip_objective_hessian_host_weighted(const float *pred, const float *weights /*[n]*/, int n, int D, int objective, float *hess_out /*[n, D]*/);
 int gbrl_hip_newton_sum_bits_weighted(int64_t m, float weight_max);
+int gbrl_hip_goss_rows_host(const float *grads /*[n, output_dim]*/, int output_dim, int row0, int n, double top_rate, double other_rate, uint64_t seed, int draw,
+                            int32_t *rows_out /*[n]*/, float *factor_out /*[n]*/, float *grads_out /*[n, output_dim], may be NULL*/, int *count);
+int gbrl_hip_dataset_sample_goss(const gbrl_hip_dataset *ds, const float *grads /*[n, output_dim]*/, int output_dim, int row0, int n, double top_rate,
+                                 double other_rate, uint64_t seed, int draw, int32_t *rows_out /*[n]*/, float *factor_out /*[n]*/,
+                                 float *grads_out /*[n, output_dim]*/, int on_device, int *count, int *n_top, uint32_t *tau_bits);
+int gbrl_hip_fit_prepared_goss(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                               const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                               double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update,
+                               double leaf_l2, const float *weights /*[n]*/, int weights_on_device, const float *valid_weights /*[valid rows]*/,
+                               int valid_weights_on_device, double goss_top, double goss_other, float *loss_out,
+                               double *valid_loss_out /*[iterations + 1]*/, double *valid_metric_out /*[iterations + 1]*/, int *iterations_done,
+                               int *best_n_trees, float *weight_max_out);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
