@@ -143,8 +143,8 @@ int parse_parity_mode(const std::string &s) {
 }
 // objective names of fit_prepared(objective=), objective_gradient and objective_gradient_host (GBRL_HIP_OBJ_*, include/gbrl_hip.h)
 int parse_objective(const std::string &s) {
-    return parse_enum(s, {{"rmse", GBRL_HIP_OBJ_RMSE}, {"logistic", GBRL_HIP_OBJ_LOGISTIC}, {"softmax", GBRL_HIP_OBJ_SOFTMAX}},
-                      "Invalid objective! Options are: rmse/logistic/softmax");
+    return parse_enum(s, {{"rmse", GBRL_HIP_OBJ_RMSE}, {"logistic", GBRL_HIP_OBJ_LOGISTIC}, {"softmax", GBRL_HIP_OBJ_SOFTMAX}, {"quantile", GBRL_HIP_OBJ_QUANTILE}},
+                      "Invalid objective! Options are: rmse/logistic/softmax/quantile");
 }
 // metric names of fit_prepared(eval_metric=), eval_metric and eval_metric_host (GBRL_HIP_METRIC_*, include/gbrl_hip.h)
 int parse_metric(const std::string &s) {
@@ -152,7 +152,8 @@ int parse_metric(const std::string &s) {
 }
 // leaf rule names of fit_prepared(leaf_update=) (GBRL_HIP_LEAF_*, include/gbrl_hip.h)
 int parse_leaf_update(const std::string &s) {
-    return parse_enum(s, {{"gradient", GBRL_HIP_LEAF_GRADIENT}, {"newton", GBRL_HIP_LEAF_NEWTON}}, "Invalid leaf_update! Options are: gradient/newton");
+    return parse_enum(s, {{"gradient", GBRL_HIP_LEAF_GRADIENT}, {"newton", GBRL_HIP_LEAF_NEWTON}, {"quantile", GBRL_HIP_LEAF_QUANTILE}},
+                      "Invalid leaf_update! Options are: gradient/newton/quantile");
 }
 const char *parity_mode_name(int mode) {
     return mode == GBRL_HIP_PARITY_REFERENCE ? "reference" : (mode == GBRL_HIP_PARITY_EXACT_ARGMAX ? "exact_argmax" : "default");
@@ -932,14 +933,39 @@ Input read_weights(py::object &weights, const char *name, const std::string &fn,
     return w;
 }
 
+// the levels of the quantile objective (include/gbrl_hip.h, "Quantile regression"): None (empty), a scalar broadcast to the D outputs, or a sequence of D;
+// the levels themselves are checked behind the C ABI, which names the output
+std::vector<float> read_alpha(const py::object &alpha, int D, const std::string &fn) {
+    std::vector<float> a;
+    if (alpha.is_none()) return a;
+    if (py::isinstance<py::float_>(alpha) || py::isinstance<py::int_>(alpha)) {
+        a.assign(static_cast<size_t>(std::max(D, 1)), alpha.cast<float>());
+        return a;
+    }
+    py::array_t<float, py::array::c_style | py::array::forcecast> arr = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(alpha);
+    if (!arr) fail(fn + ": alpha must be a number or a sequence of numbers");
+    if (arr.ndim() == 0) {
+        a.assign(static_cast<size_t>(std::max(D, 1)), *arr.data());
+        return a;
+    }
+    if (arr.ndim() != 1 || arr.shape(0) != D) {
+        std::stringstream ss;
+        ss << fn << ": alpha must be a scalar or hold one level per output (" << D << ")";
+        fail(ss.str());
+    }
+    a.assign(arr.data(), arr.data() + D);
+    return a;
+}
+
 // fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,
 // objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
 // with either.  A missing valid_targets is left to the C ABI's message.
 py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
                              int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name,
                              py::object metric_obj, const std::string &leaf_update_name, double leaf_l2, py::object &weights, py::object &valid_weights,
-                             py::object goss_obj) {
+                             py::object goss_obj, py::object alpha_obj) {
     const gbrl_hip_metadata md = self.meta();
+    const std::vector<float> alpha = read_alpha(alpha_obj, md.output_dim, "fit_prepared");
     double goss_top = 0.0, goss_other = 0.0;
     if (!goss_obj.is_none()) {   // goss=(top_rate, other_rate); an other_rate of 0 is refused here, since 0 means "off" below
         py::sequence g = py::isinstance<py::sequence>(goss_obj) ? goss_obj.cast<py::sequence>() : py::sequence();
@@ -965,10 +991,10 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_goss(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
-                                        colsample, seed, objective, metric, leaf_update, leaf_l2, static_cast<const float *>(w.ptr), w.on_device,
-                                        static_cast<const float *>(wv.ptr), wv.on_device, goss_top, goss_other, &loss, dsv ? curve.data() : nullptr,
-                                        dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max);
+        rc = gbrl_hip_fit_prepared_quantile(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                            colsample, seed, objective, metric, leaf_update, leaf_l2, static_cast<const float *>(w.ptr), w.on_device,
+                                            static_cast<const float *>(wv.ptr), wv.on_device, goss_top, goss_other, alpha.empty() ? nullptr : alpha.data(), &loss,
+                                            dsv ? curve.data() : nullptr, dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max);
     }
     check(rc);
     if (!dsv) return py::float_(loss);
@@ -1035,6 +1061,68 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
     out["sums"] = sums;
     out["bits"] = py::int_(bits);
     out["values"] = values;
+    return out;
+}
+
+// Extension: quantile regression (include/gbrl_hip.h, "Quantile regression").
+// quantile_leaves_prepared(ds, pred, targets, alpha, rows=None, tree=-1) -> {'values': float32 [leaves, D], 'counts': int64 [leaves], 'ranks': int64 [leaves, D]}
+py::dict quantile_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &pred, py::object &targets, py::object alpha_obj, py::object &rows, int tree) {
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const int D = md.output_dim;
+    const std::vector<float> alpha = read_alpha(alpha_obj, D, "quantile_leaves_prepared");
+    Input p = read_input(pred, "pred", false, "quantile_leaves_prepared", false);
+    if (!p.ptr) fail("Cannot call quantile_leaves_prepared without pred!");
+    Input r = read_rows(rows, "quantile_leaves_prepared");
+    int m = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
+    if (!rows.is_none()) m = static_cast<int>(r.shape[0]);
+    else if (ds) m = ds_obj.cast<const PyDataset &>().info().n_rows;
+    check_rows_by_outputs(p, "pred", m, D);
+    Input t = read_objective_targets(targets, "targets", false, "quantile_leaves_prepared", GBRL_HIP_OBJ_QUANTILE, m, D, true);
+    if (!t.ptr) fail("Cannot call quantile_leaves_prepared without targets!");
+    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
+    const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
+    // the leaves of the tree (an index outside the model is left to the C ABI's message: one leaf's room is enough for a call that is refused)
+    const py::ssize_t T = md.n_trees;
+    py::ssize_t leaves = 1;
+    if (tree >= -1 && tree < T && T > 0) {
+        std::vector<int32_t> ti(static_cast<size_t>(T));
+        const py::ssize_t tt = tree == -1 ? T - 1 : tree;
+        check(gbrl_hip_get_ensemble(self.h, ti.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        leaves = (tt + 1 < T ? ti[tt + 1] : md.n_leaves) - ti[tt];
+    }
+    py::array_t<float> values({leaves, static_cast<py::ssize_t>(D)});
+    py::array_t<int64_t> counts(std::vector<py::ssize_t>{leaves}), ranks({leaves, static_cast<py::ssize_t>(D)});
+    float *vp = values.mutable_data();
+    int64_t *cp = counts.mutable_data(), *kp = ranks.mutable_data();
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_quantile_leaves_prepared(self.h, ds, rp, r.ptr ? r.on_device : 0, m, static_cast<const float *>(p.ptr), p.on_device,
+                                               static_cast<const float *>(t.ptr), t.on_device, alpha.empty() ? nullptr : alpha.data(), tree, vp, cp, kp);
+    }
+    check(rc);
+    py::dict out;
+    out["values"] = values;
+    out["counts"] = counts;
+    out["ranks"] = ranks;
+    return out;
+}
+
+// the rule on the host: x float32 [m, D] (or [m]), leaves int32 [m] -> {'values', 'counts', 'ranks'}
+py::dict leaf_quantile_host_impl(py::array_t<float, py::array::c_style | py::array::forcecast> x, py::array_t<int32_t, py::array::c_style | py::array::forcecast> leaves,
+                                 int n_leaves, py::object alpha_obj) {
+    if (x.ndim() < 1 || x.ndim() > 2 || leaves.ndim() != 1 || leaves.shape(0) != x.shape(0)) fail("leaf_quantile_host: x float32 [m, D] (or [m]), leaves int32 [m]");
+    const py::ssize_t m = x.shape(0), D = x.ndim() == 2 ? x.shape(1) : 1, L = std::max(n_leaves, 1);
+    const std::vector<float> alpha = read_alpha(alpha_obj, static_cast<int>(D), "leaf_quantile_host");
+    py::array_t<float> values({L, D});
+    py::array_t<int64_t> counts(std::vector<py::ssize_t>{L}), ranks({L, D});
+    check(gbrl_hip_leaf_quantile_host(x.data(), leaves.data(), static_cast<int>(m), static_cast<int>(D), n_leaves, alpha.empty() ? nullptr : alpha.data(),
+                                      values.mutable_data(), counts.mutable_data(), ranks.mutable_data()));
+    py::dict out;
+    out["values"] = values;
+    out["counts"] = counts;
+    out["ranks"] = ranks;
     return out;
 }
 
@@ -1110,9 +1198,10 @@ py::tuple eval_metric_host_impl(py::object &pred, py::object &targets, const std
 }
 
 // objective_gradient(pred, targets, objective, weights=None) -> (grad, loss): NumPy in, NumPy out; a device tuple gives a DLPack capsule on the model's device
-py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights) {
+py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights, py::object alpha_obj) {
     const gbrl_hip_metadata md = self.meta();
     const int objective = parse_objective(objective_name), D = md.output_dim;
+    const std::vector<float> alpha = read_alpha(alpha_obj, D, "objective_gradient");
     Input p = read_input(pred, "pred", false, "objective_gradient", false);
     if (!p.ptr) fail("Cannot call objective_gradient without pred!");
     const int n = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
@@ -1120,6 +1209,7 @@ py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &ta
     Input t = read_objective_targets(targets, "targets", false, "objective_gradient", objective, n, D, true);
     if (!t.ptr) fail("Cannot call objective_gradient without targets!");
     Input w = read_weights(weights, "weights", "objective_gradient", n, true);
+    if (w.ptr && (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty())) fail("objective_gradient: row weights with the quantile objective (alpha=) are not supported");
     const size_t n_el = std::max<size_t>(static_cast<size_t>(n) * D, 1);
     float *g = nullptr;
     int dev_id = 0;
@@ -1135,8 +1225,12 @@ py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &ta
     int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_objective_gradient_weighted(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, static_cast<const float *>(w.ptr),
-                                                  w.on_device, n, objective, g, &loss);
+        if (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty())
+            rc = gbrl_hip_objective_gradient_quantile(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, alpha.empty() ? nullptr : alpha.data(),
+                                                      n, objective, g, &loss);
+        else
+            rc = gbrl_hip_objective_gradient_weighted(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, static_cast<const float *>(w.ptr),
+                                                      w.on_device, n, objective, g, &loss);
     }
     if (rc != GBRL_HIP_OK) {
         if (p.on_device) gbrl_hip_device_free(g); else delete[] g;
@@ -1149,7 +1243,7 @@ py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &ta
 }
 
 // the gradient rule on the host (include/gbrl_hip.h, "Classification objectives"): no device, no model
-py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights) {
+py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights, py::object alpha_obj) {
     const int objective = parse_objective(objective_name);
     Input p = read_input(pred, "pred", false, "objective_gradient_host", false);
     if (p.on_device) fail("objective_gradient_host takes NumPy arrays");
@@ -1159,8 +1253,15 @@ py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &ta
     if (t.on_device) fail("objective_gradient_host takes NumPy arrays");
     Input w = read_weights(weights, "weights", "objective_gradient_host", n, true);
     if (w.on_device) fail("objective_gradient_host takes NumPy arrays");
+    const std::vector<float> alpha = read_alpha(alpha_obj, D, "objective_gradient_host");
     py::array_t<float> out(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
     float none = 0.0f;
+    if (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty()) {
+        if (w.ptr) fail("objective_gradient_host: row weights with the quantile objective (alpha=) are not supported");
+        check(gbrl_hip_objective_gradient_host_quantile(static_cast<const float *>(p.ptr), t.ptr, alpha.empty() ? nullptr : alpha.data(), n, D, objective,
+                                                        out.size() ? out.mutable_data() : &none));
+        return out;
+    }
     check(gbrl_hip_objective_gradient_host_weighted(static_cast<const float *>(p.ptr), t.ptr, static_cast<const float *>(w.ptr), n, D, objective,
                                                     out.size() ? out.mutable_data() : &none));
     return out;
@@ -1375,11 +1476,37 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "absolute and ascending.  PreparedDataset.sample_goss returns the same lists, and the gathered gradients, from the device.  Refused: a NaN rate,\n"
           "top_rate outside [0, 1), other_rate outside (0, 1], top_rate + other_rate > 1, other_rate / (1 - top_rate) < 2**-24, row0 < 0, no rows, draw < 0.");
     m.def("objective_gradient_host", &objective_gradient_host_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("weights") = py::none(),
-          "objective_gradient_host(pred, targets, objective, weights=None) -> float32 NumPy array shaped like pred\n\n"
+          py::arg("alpha") = py::none(),
+          "objective_gradient_host(pred, targets, objective, weights=None, alpha=None) -> float32 NumPy array shaped like pred\n\n"
           "The gradient rule of fit_prepared(objective=) on the host (no device is needed): 'logistic': sigmoid(p) - y, targets float32 like pred;\n"
           "'softmax': softmax(p) - onehot(y), targets int32 [n] labels in [0, D), D >= 2; 'rmse': p - y.  Every float32 step is the one definition the\n"
           "kernels use (an exponential written out in fmaf, correctly rounded division): the device gives the same bits.  weights (float32 [n], every\n"
-          "entry finite and in [0, 65536]): fl32(w * g) row by row, one float32 multiply behind the rule; all-ones weights change no bit.");
+          "entry finite and in [0, 65536]): fl32(w * g) row by row, one float32 multiply behind the rule; all-ones weights change no bit.\n"
+          "'quantile' with alpha (a level in (0, 1), or one per output): x = fl32(p - y), g = 1 - alpha where x > 0, -alpha where x < 0, 0 where x == 0; it takes no\n"
+          "weights, and alpha goes with no other objective.");
+    m.def("leaf_quantile_host", &leaf_quantile_host_impl, py::arg("x"), py::arg("leaves"), py::arg("n_leaves"), py::arg("alpha"),
+          "leaf_quantile_host(x, leaves, n_leaves, alpha) -> {'values': float32 [n_leaves, D], 'counts': int64 [n_leaves], 'ranks': int64 [n_leaves, D]}\n\n"
+          "The leaf rule of fit_prepared(leaf_update='quantile') and GBRL.quantile_leaves_prepared on the host (no device is needed): x float32 [m, D] are the\n"
+          "residuals fl32(p - y), leaves int32 [m] the leaf of every row (an entry outside [0, n_leaves) joins no leaf).  values[leaf, d] is the k-th LARGEST\n"
+          "x[:, d] among the rows of the leaf, k = gbrl_cpp.quantile_rank(rows of the leaf, alpha[d]): an element of the data bit for bit, -0.0 taken as +0.0.\n"
+          "An empty leaf has count 0, rank 0 and the value 0.  alpha: a level in (0, 1) or one per output.  Refused: a bad level, an x that is not finite.");
+    m.def("quantile_rank", [](int64_t rows, float a) {
+              int64_t k = 0;
+              check(gbrl_hip_quantile_rank(rows, a, &k));
+              return k;
+          }, py::arg("m"), py::arg("a"),
+          "quantile_rank(m, a) -> clamp(ceil(a * m), 1, m) with the product taken exactly (a is the float32 M * 2**-s: 64-bit integers and a shift, never a\n"
+          "double product, which can round across an integer): the rank, counted from the smallest residual y - p, that level a selects among m rows.\n"
+          "Refused: m outside [1, 2**31 - 1], a level that is not a finite float32 strictly inside (0, 1).");
+    m.def("leaf_quantile_geometry", []() {
+              int leaves = 0, rows = 0;
+              gbrl_hip_leaf_quantile_geometry(&leaves, &rows);
+              py::dict d;
+              d["max_select_leaves"] = leaves;
+              d["rows_per_chunk"] = rows;
+              return d;
+          }, "leaf_quantile_geometry() -> {'max_select_leaves', 'rows_per_chunk'}: the largest tree quantile_leaves_prepared's select path takes (larger trees are\n"
+             "sorted) and the rows one block of its count pass takes at a time, for tests that straddle them.");
     m.def("objective_hessian_host", &objective_hessian_host_impl, py::arg("pred"), py::arg("targets") = py::none(), py::arg("objective") = "logistic",
           py::arg("weights") = py::none(),
           "objective_hessian_host(pred, targets, objective, weights=None) -> float32 NumPy array shaped like pred\n\n"
@@ -1500,12 +1627,12 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         // likewise: fit_prepared(ds, targets, iterations) -> float keeps its generated line; the validation form is the second overload
         g.def("fit_prepared", [](PyGBRL &self, py::object ds, py::object &targets, int iterations) -> float {
             py::object none = py::none();
-            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0, none, none, none).cast<float>();
+            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0, none, none, none, none).cast<float>();
         }, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
             "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,\n"
-            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None, goss=None)\n"
+            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None, goss=None, alpha=None)\n"
             "             -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
@@ -1572,15 +1699,38 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "fl32(max w * amp) and are unbiased; a 'gradient' leaf stores the mean of the amplified gradients over the kept rows, about 1 / (top_rate + other_rate)\n"
             "times the batch mean, so such a fit steps that much further per tree (lower the learning rate).  A draw that keeps no row takes the whole batch unamplified.  goss=None is the call without the keyword.  Refused before anything\n"
             "changes: a NaN rate, top_rate outside [0, 1), other_rate outside (0, 1], top_rate + other_rate > 1, other_rate / (1 - top_rate) < 2**-24, goss with\n"
-            "subsample < 1, and a largest weight (1 without weights=) whose product with the amplification is above 65536.";
+            "subsample < 1, and a largest weight (1 without weights=) whose product with the amplification is above 65536.\n"
+            "objective='quantile', alpha=a (a level in (0, 1), broadcast, or a sequence of one level per output; with valid=, subsample, colsample and goss):\n"
+            "quantile regression, LightGBM's objective='quantile'.  targets float32 [n, D]; g = 1 - alpha_d where fl32(p - y) > 0, -alpha_d where it is < 0, 0 at\n"
+            "0; 'loss' and 'valid_loss' are the mean pinball loss per row; a fresh model's bias is the k-th smallest target of every column, k =\n"
+            "gbrl_cpp.quantile_rank(n, alpha_d).  leaf_update='quantile': the tree is grown on that gradient, then every leaf stores, per output, the k-th largest\n"
+            "residual fl32(p - y) of the rows the tree was grown on, k from the leaf's row count -- minus the alpha-quantile of y - p (NumPy's\n"
+            "method='inverted_cdf'), a minimiser of the leaf's pinball sum, what LightGBM and scikit-learn renew their leaves with -- where a 'gradient' leaf, a\n"
+            "mean of values in [-alpha, 1 - alpha], moves the fit by at most the learning rate per tree.  The order statistic is selected exactly on the device\n"
+            "(quantile_leaves_prepared's kernels, one enqueue and one read-back per tree): the model is byte for byte the loop objective_gradient ->\n"
+            "step_prepared -> quantile_leaves_prepared -> predict_continue_prepared.  Refused before anything changes: 'quantile' without alpha, alpha with\n"
+            "another objective, a level outside (0, 1) or NaN (the output is named), a wrong length, leaf_update='quantile' with another objective,\n"
+            "leaf_update='newton' with 'quantile' (its hessian is zero), eval_metric with it, a training target that is not finite; not supported:\n"
+            "weights= / valid_weights= with it, goss= with leaf_update='quantile' (both would need a weighted quantile).";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
               py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse", py::arg("eval_metric") = py::none(),
               py::arg("leaf_update") = "gradient", py::arg("leaf_l2") = 1.0, py::arg("weights") = py::none(), py::arg("valid_weights") = py::none(),
-              py::arg("goss") = py::none());
+              py::arg("goss") = py::none(), py::arg("alpha") = py::none());
     }
+    g.def("quantile_leaves_prepared", &quantile_leaves_prepared_impl, py::arg("ds"), py::arg("pred"), py::arg("targets"), py::arg("alpha"), py::arg("rows") = py::none(),
+          py::arg("tree") = -1,
+          "quantile_leaves_prepared(ds, pred, targets, alpha, rows=None, tree=-1) -> dict\n\n"
+          "The leaves of ONE tree (tree=-1: the last) set, per output d, to the k-th largest residual fl32(pred - targets) among the data set rows `rows` (None:\n"
+          "every row) the tree routes to the leaf, k = gbrl_cpp.quantile_rank(rows of the leaf, alpha[d]): what fit_prepared(leaf_update='quantile') does after\n"
+          "every step.  pred [m, output_dim] is the prediction over the trees before that tree and, like targets (float32 [m, output_dim]), is indexed by\n"
+          "position.  alpha: a level in (0, 1) or one per output.  Returns 'values' (float32 [leaves, D], what the model now holds), 'counts' (int64 [leaves])\n"
+          "and 'ranks' (int64 [leaves, D]; 0 for an empty leaf).  The value is an element of the data, bit for bit (gbrl_cpp.leaf_quantile_host is the rule):\n"
+          "a radix select per (leaf, output) for trees of up to gbrl_cpp.leaf_quantile_geometry()['max_select_leaves'] leaves, a sort by key and leaf beyond --\n"
+          "the same bytes.  A leaf without rows or of depth 0 keeps its value.  Refused with the model unchanged: a bad level, a tree outside the model, a\n"
+          "prediction, target or residual that is not finite.");
     g.def("newton_leaves_prepared", &newton_leaves_prepared_impl, py::arg("ds"), py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("leaf_l2") = 1.0,
           py::arg("rows") = py::none(), py::arg("tree") = -1, py::arg("weights") = py::none(), py::arg("weight_max") = py::none(),
           "newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1, weights=None, weight_max=None) -> dict\n\n"
@@ -1601,14 +1751,17 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "same value, bit for bit.  pred [n, output_dim] and targets are NumPy arrays or device tuples.  'error' is one launch; 'auc' sorts the score\n"
           "columns with a segmented radix sort, prefix-counts the negatives and sums ranks with integer atomics: two calls give the same bytes.");
     g.def("objective_gradient", &objective_gradient_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("weights") = py::none(),
-          "objective_gradient(pred, targets, objective, weights=None) -> (grad, loss)\n\n"
+          py::arg("alpha") = py::none(),
+          "objective_gradient(pred, targets, objective, weights=None, alpha=None) -> (grad, loss)\n\n"
           "The gradient dL/dp [n, output_dim] and the loss of the raw scores pred under objective 'rmse' | 'logistic' | 'softmax', computed on the model's\n"
           "device by the device functions fit_prepared(objective=) runs: grad is gbrl_cpp.objective_gradient_host(pred, targets, objective) bit for bit.\n"
           "targets: float32 [n, output_dim] (rmse, logistic) or int32 [n] labels (softmax).  NumPy in, NumPy out; a device tuple for pred gives a DLPack\n"
           "capsule.  loss: the mean row loss in float64 (rmse: the MultiRMSE expression), reduced in a fixed order: two calls give the same bits.\n"
           "weights (float32 [n], NumPy or a device tuple, every entry finite and in [0, 65536], sum > 0): grad = fl32(w * g) row by row and loss =\n"
           "sum w L / W with W the float64 sum of the weights in a fixed order (rmse: sqrt(0.5 sum w L / W)); the weight is one more float per row in the\n"
-          "same launch.  Refused: a bad entry (the row is named), weights that sum to 0, a wrong length or dtype.");
+          "same launch.  Refused: a bad entry (the row is named), weights that sum to 0, a wrong length or dtype.\n"
+          "'quantile' with alpha (a level in (0, 1) or one per output): the pinball step of gbrl_cpp.objective_gradient_host(..., alpha=) and the mean pinball\n"
+          "loss sum_d (u >= 0 ? alpha_d u : (alpha_d - 1) u), u = y - p in float64; no weights with it, alpha with no other objective.");
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);
     }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("return_torch") = false);

@@ -19,6 +19,7 @@
 #include "objective_core.h"
 #include "metric_core.h"
 #include "newton_core.h"
+#include "quantile_core.h"
 #include "hooks.h"
 #include "explain.h"
 #include "rccl_dyn.h"
@@ -730,6 +731,56 @@ int gbrl_hip_fit_prepared_goss(gbrl_hip_model *m, const gbrl_hip_dataset *ds, co
     return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
                              {subsample, colsample, seed, objective, metric, leaf_update, leaf_l2, weights, weights_on_device != 0, goss_top, goss_other}, loss_out,
                              valid_loss_out, iterations_done, best_n_trees, valid_metric_out, valid_weights, valid_weights_on_device, weight_max_out);
+}
+
+// ---- quantile regression: fit_prepared with the levels, one tree's leaf quantiles on a data set, the rules on the host
+static_assert(gbrl::kern::kObjQuantile == GBRL_HIP_OBJ_QUANTILE && gbrl::kern::kLeafQuantile == GBRL_HIP_LEAF_QUANTILE, "the kernels' quantile codes are the header's");
+int gbrl_hip_fit_prepared_quantile(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                                   const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                   double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update, double leaf_l2,
+                                   const float *weights, int weights_on_device, const float *valid_weights, int valid_weights_on_device, double goss_top,
+                                   double goss_other, const float *alpha, float *loss_out, double *valid_loss_out, double *valid_metric_out, int *iterations_done,
+                                   int *best_n_trees, float *weight_max_out) {
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, colsample, seed, objective, metric, leaf_update, leaf_l2, weights, weights_on_device != 0, goss_top, goss_other, alpha},
+                             loss_out, valid_loss_out, iterations_done, best_n_trees, valid_metric_out, valid_weights, valid_weights_on_device, weight_max_out);
+}
+
+int gbrl_hip_quantile_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,
+                                      int pred_on_device, const float *targets, int targets_on_device, const float *alpha, int tree, float *values_out,
+                                      int64_t *counts_out, int64_t *ranks_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("quantile_leaves_prepared");
+        m->engine.quantile_leaves_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, pred, pred_on_device != 0, targets, targets_on_device != 0, alpha, tree,
+                                           values_out, counts_out, ranks_out);
+    });
+}
+
+int gbrl_hip_leaf_quantile_host(const float *x, const int32_t *leaves, int m, int D, int n_leaves, const float *alpha, float *values_out, int64_t *counts_out,
+                                int64_t *ranks_out) {
+    return guarded([&] { gbrl::Engine::leaf_quantile_host(x, leaves, m, D, n_leaves, alpha, values_out, counts_out, ranks_out); });
+}
+
+int gbrl_hip_quantile_rank(int64_t m, float a, int64_t *rank_out) {
+    return guarded([&] {
+        if (rank_out == nullptr) throw gbrl::InvalidArgument("quantile_rank: null argument");
+        *rank_out = gbrl::Engine::quantile_rank(m, a);
+    });
+}
+
+void gbrl_hip_leaf_quantile_geometry(int *max_select_leaves, int *rows_per_chunk) { gbrl::kern::leaf_quantile_geometry(max_select_leaves, rows_per_chunk); }
+
+int gbrl_hip_objective_gradient_quantile(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, const float *alpha,
+                                         int n, int objective, float *grad_out, double *loss_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.objective_gradient(pred, pred_on_device != 0, targets, targets_on_device != 0, n, objective, grad_out, loss_out, nullptr, false, alpha);
+    });
+}
+
+int gbrl_hip_objective_gradient_host_quantile(const float *pred, const void *targets, const float *alpha, int n, int D, int objective, float *grad_out) {
+    return guarded([&] { gbrl::Engine::objective_gradient_host(pred, targets, n, D, objective, grad_out, nullptr, alpha); });
 }
 
 int gbrl_hip_newton_leaves_prepared_weighted(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,

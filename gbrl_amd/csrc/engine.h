@@ -130,9 +130,10 @@ struct CatItem { int feat; int next; uint64_t lhash; size_t std_hash; char name[
 // The options of Engine::fit_prepared; the defaults are the plain MultiRMSE loop on every row and column.
 struct FitOptions {
     double subsample = 1.0, colsample = 1.0; uint64_t seed = 0; int objective = 0 /* kern::kObjRmse */; int metric = 0 /* kern::kMetricNone */;
-    int leaf_update = 0 /* kern::kLeafGradient; 1: kern::kLeafNewton */; double leaf_l2 = 1.0;
+    int leaf_update = 0 /* kern::kLeafGradient; 1: kern::kLeafNewton; 2: kern::kLeafQuantile */; double leaf_l2 = 1.0;
     const float *weights = nullptr /* float32 [n], one per data set row; nullptr: the loop without weights */; bool weights_dev = false;
     double goss_top = 0.0, goss_other = 0.0 /* 0: off; else sample_core.h's one-side sampling takes the place of the subsample draw */;
+    const float *alpha = nullptr /* host float32 [D]: the levels of kern::kObjQuantile (quantile_core.h); required with it, refused without it */;
 };
 
 class Engine {
@@ -275,8 +276,26 @@ class Engine {
     // device and stream with D = output_dim (kern::objective_rows: the device functions of the code walk's tails).  grad_out is where pred is
     // (device iff pred_dev); either output may be null, not both.  kObjRmse: g = fl32(p - y) and staged_loss's expression.
     // weights (nullable, float32 [n]): grad_out = fl32(w * g), the loss sum w L / W (rmse: sqrt(0.5 sum w L / W)); checked as fit_prepared checks them.
+    // alpha (host float32 [D]): the levels of kObjQuantile -- required with it, refused with another objective, as are weights with kObjQuantile.
     void objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out,
-                            const float *weights = nullptr, bool weights_dev = false);
+                            const float *weights = nullptr, bool weights_dev = false, const float *alpha = nullptr);
+    // Extension: quantile regression (quantile_core.h has the rule, include/gbrl_hip.h the contract).  check_alpha: alpha with another objective,
+    // kObjQuantile without alpha, weights with kObjQuantile (Unsupported), a level that is not finite and strictly inside (0, 1) (the output is named).
+    static void check_alpha(const char *what, int objective, const float *alpha, int D, bool weighted);
+    // quantile_leaves_prepared: the leaves of ONE tree (tree == -1: the last) get v[leaf][d] = the k-th largest x = fl32(pred - targets) among the
+    // data set rows rows[0..m) (rows == nullptr: every row, m == ds->n) the tree routes to the leaf, k = quantile_rank(rows of the leaf, alpha[d]);
+    // pred and targets are [m][D], indexed by position.  A leaf without rows or of depth 0 keeps its value.  values_out (nullable) float32 [leaves][D]
+    // what the model now holds, counts_out (nullable) int64 [leaves], ranks_out (nullable) int64 [leaves][D] (0 for an empty leaf).  Only model.values
+    // of that tree changes, and only its slice of the device mirror is sent again.  Refused before anything changes: what newton_leaves_prepared
+    // refuses about the model, the data set, rows, the tree and output_dim; a bad level.  Refused after the launch, the model unchanged
+    // (InvalidArgument): a prediction, a target or a residual that is not finite.
+    void quantile_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *pred, bool pred_dev, const float *targets,
+                                  bool targets_dev, const float *alpha, int tree, float *values_out, int64_t *counts_out, int64_t *ranks_out);
+    // the rule on the host (no device): x float32 [m][D], leaves int32 [m] (an entry outside [0, n_leaves) joins no leaf) -> values_out float32
+    // [n_leaves][D] (0 for an empty leaf), counts_out int64 [n_leaves], ranks_out int64 [n_leaves][D]; any output may be null
+    static void leaf_quantile_host(const float *x, const int32_t *leaves, int m, int D, int n_leaves, const float *alpha, float *values_out, int64_t *counts_out,
+                                   int64_t *ranks_out);
+    static int64_t quantile_rank(int64_t m, float a);   // clamp(ceil(a * m), 1, m), the product exact; a bad level or m < 1 is refused
     // Extension: row weights.  The checks of a weight vector on the host (InvalidArgument naming the first refused row); on the device the same
     // through kern::weight_stats, with the largest weight and W = the float64 sum in its fixed order (need_sum: W == 0 is refused too).
     static void check_weights_host(const char *what, const float *weights, int n);
@@ -314,7 +333,7 @@ class Engine {
                                    float *values_out);
     // the gradient rule on the host (no device): the same bits
     static void objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out,
-                                        const float *weights = nullptr /*[n]: fl32(w * g)*/);
+                                        const float *weights = nullptr /*[n]: fl32(w * g)*/, const float *alpha = nullptr /*[D]: kObjQuantile's levels*/);
     // the stopping rule on a curve (host only): best = index of the minimum so far from k = 0, entry k improves iff curve[k] < curve[best] -
     // min_delta (a NaN never improves); *stop_after = the first k with k - best >= rounds (rounds > 0), else n - 1; *best = best at that point
     static void early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
@@ -567,7 +586,7 @@ class Engine {
     // one int32 label per row behind the float pointers)
     // weights (nullable): device [n], one per row of the held data set, for whichever tail is on
     void advance_held(Held &h, int start, int bn, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
-                      int objective, const float *weights = nullptr);
+                      int objective, const float *weights = nullptr, const float *d_alpha = nullptr /*device [D]: kObjQuantile's levels*/);
     // the partials of a loss tail summed into *d_sum (kern::staged_loss_finish) and, with host_sum, its 8 bytes on their way to the host: they
     // are there after the caller's wait for the stream
     void finish_loss_sum(const double *d_part, int n_part, double *d_sum, double *host_sum);
@@ -576,6 +595,11 @@ class Engine {
     void newton_leaves_run(const char *what, const PreparedDataset *ds, const kern::CodeRows &cr, int m, const float *d_pred, const void *d_targets, bool abs_index,
                            int objective, int t, double leaf_l2, bool generic, int64_t *sums_out, int *bits_out, float *values_out,
                            const float *d_weights = nullptr, float weight_max = 0.0f);   // (weights indexed like d_pred)
+    // quantile_leaves_prepared likewise: d_alpha is the device table of the levels; the phase quantile_leaves joins the caller's phase list
+    void quantile_leaves_run(const char *what, const PreparedDataset *ds, const kern::CodeRows &cr, int m, const float *d_pred, const float *d_targets,
+                             bool abs_index, const float *d_alpha, int t, bool generic, float *values_out, int64_t *counts_out, int64_t *ranks_out);
+    DevBuf d_lq_res_, d_lq_scratch_, d_lq_alpha_;   // its result block (keys, ranks, counts, flag), its workspace, the levels
+    std::vector<uint32_t> lq_host_;                 // ... the result block read back
     DevBuf d_newton_acc_;                         // its int64 sums [leaves][2 D + 1] and the flag word
     std::vector<unsigned long long> newton_host_;   // ... read back
     // Column sums in float64 of device rows [rows][D] and the MultiRMSE built on them, as fit() and fit_prepared() compute the bias and the loss

@@ -18,6 +18,9 @@
 //   Engine::newton_leaves_prepared     one tree's leaves set to sum g / (sum h + leaf_l2) over a data set's rows (newton_core.h; kern::newton_leaf_sums), the
 //                                      rules on the host beside it (objective_hessian_host, newton_values_host); fit_prepared(leaf_update = newton) runs its
 //                                      body after every step
+//   Engine::quantile_leaves_prepared   one tree's leaves set to the level's order statistic of the residuals of their rows (quantile_core.h; kern::leaf_quantile),
+//                                      the rule on the host beside it (leaf_quantile_host, quantile_rank); fit_prepared(leaf_update = quantile) runs its body
+//                                      after every step, and objective = quantile adds the pinball gradient and loss to the tails
 //   Engine::check_weights[_host]       row weights (objective_core.h, newton_core.h): a weight vector's refusals, its maximum and its float64 sum in a fixed order
 //                                      (kern::weight_stats), once per call and vector; the weighted forms of the gradient, the loss, the bias and the Newton
 //                                      sums ride in the launches above as one more per-row operand
@@ -31,6 +34,7 @@
 #include "objective_core.h"
 #include "metric_core.h"
 #include "newton_core.h"
+#include "quantile_core.h"
 #include "sample_core.h"
 
 namespace gbrl {
@@ -210,10 +214,23 @@ void Engine::predict_continue_prepared(const PreparedDataset *ds, const int32_t 
 
 // ---- objectives: the checks, the gradient rule on the host, the gradient and the loss of a prediction matrix on the device
 void Engine::check_objective(const char *what, int objective, int D) {
-    if (objective != kern::kObjRmse && objective != kern::kObjLogistic && objective != kern::kObjSoftmax)
-        throw InvalidArgument(std::string(what) + ": unknown objective " + std::to_string(objective) + " (rmse = 0, logistic = 1, softmax = 2)");
+    if (objective != kern::kObjRmse && objective != kern::kObjLogistic && objective != kern::kObjSoftmax && objective != kern::kObjQuantile)
+        throw InvalidArgument(std::string(what) + ": unknown objective " + std::to_string(objective) + " (rmse = 0, logistic = 1, softmax = 2, quantile = 3)");
     if (objective == kern::kObjSoftmax && D < 2)
         throw InvalidArgument(std::string(what) + ": the softmax objective needs output_dim >= 2, the model has " + std::to_string(D));
+}
+
+void Engine::check_alpha(const char *what, int objective, const float *alpha, int D, bool weighted) {
+    if (objective != kern::kObjQuantile) {
+        if (alpha != nullptr) throw InvalidArgument(std::string(what) + ": alpha is the level table of the quantile objective; this objective takes none");
+        return;
+    }
+    if (alpha == nullptr) throw InvalidArgument(std::string(what) + ": the quantile objective needs alpha, one level per output");
+    for (int d = 0; d < D; ++d)
+        if (kern::quantile_bad_level(alpha[d]))
+            throw InvalidArgument(std::string(what) + ": alpha[" + std::to_string(d) + "] = " + std::to_string(alpha[d]) + " (output " + std::to_string(d) +
+                                  ") is not a finite level strictly inside (0, 1)");
+    if (weighted) throw Unsupported(std::string(what) + ": row weights with the quantile objective are not supported (bias and leaves would need a weighted quantile)");
 }
 
 void Engine::check_labels(const char *what, const int32_t *d_labels, int n, int D, std::vector<int32_t> *counts) {
@@ -268,13 +285,19 @@ void weigh_rows(float *x, const float *weights, int n, int D) {
 }
 }  // namespace
 
-void Engine::objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out, const float *weights) {
+void Engine::objective_gradient_host(const float *pred, const void *targets, int n, int D, int objective, float *grad_out, const float *weights, const float *alpha) {
     if (pred == nullptr || targets == nullptr || grad_out == nullptr) throw InvalidArgument("objective_gradient_host: null argument");
     if (n <= 0) throw InvalidArgument("objective_gradient_host: no rows (n must be positive)");
     if (D < 1) throw InvalidArgument("objective_gradient_host: output_dim must be positive");
     check_objective("objective_gradient_host", objective, D);
+    check_alpha("objective_gradient_host", objective, alpha, D, weights != nullptr);
     if (weights) check_weights_host("objective_gradient_host", weights, n);
     const size_t n_el = static_cast<size_t>(n) * D;
+    if (objective == kern::kObjQuantile) {
+        const float *y = static_cast<const float *>(targets);
+        for (size_t i = 0; i < n_el; ++i) grad_out[i] = kern::obj_quantile_grad(pred[i], y[i], alpha[i % D]);
+        return;
+    }
     if (objective == kern::kObjSoftmax) {
         const int32_t *labels = static_cast<const int32_t *>(targets);
         for (int r = 0; r < n; ++r)
@@ -308,13 +331,14 @@ void Engine::finish_loss_sum(const double *d_part, int n_part, double *d_sum, do
 }
 
 void Engine::objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out,
-                                const float *weights, bool weights_dev) {
+                                const float *weights, bool weights_dev, const float *alpha) {
     const int D = model.meta.output_dim;
     if (pred == nullptr || targets == nullptr) throw InvalidArgument("objective_gradient: null argument");
     if (grad_out == nullptr && loss_out == nullptr) throw InvalidArgument("objective_gradient: no place for a result");
     if (n <= 0) throw InvalidArgument("objective_gradient: no rows (n must be positive)");
     if (D > 128) throw Unsupported("objective_gradient: output_dim > 128");
     check_objective("objective_gradient", objective, D);
+    check_alpha("objective_gradient", objective, alpha, D, weights != nullptr);
     ensure_device();
     hipStream_t s = stream_;
     const size_t n_el = static_cast<size_t>(n) * D, tar_el = objective == kern::kObjSoftmax ? static_cast<size_t>(n) : n_el;
@@ -327,7 +351,8 @@ void Engine::objective_gradient(const float *pred, bool pred_dev, const void *ta
     const int nb = kern::staged_loss_partials(n);
     double *dpart = loss_out ? static_cast<double *>(d_obj_part_.ensure(sizeof(double) * nb)) : nullptr;
     double *dsum = loss_out ? static_cast<double *>(d_obj_sum_.ensure(sizeof(double))) : nullptr;
-    kern::objective_rows(objective, dp, dt, n, D, dg, dpart, s, dw);
+    const float *da = alpha ? upload(d_lq_alpha_, alpha, static_cast<size_t>(D), "H2D levels") : nullptr;
+    kern::objective_rows(objective, dp, dt, n, D, dg, dpart, s, dw, da);
     double sum = 0.0;
     if (loss_out) finish_loss_sum(dpart, nb, dsum, &sum);
     if (grad_out && !pred_dev) hip_check(hipMemcpyAsync(grad_out, dg, sizeof(float) * n_el, hipMemcpyDeviceToHost, s), "D2H gradient");
@@ -338,12 +363,16 @@ void Engine::objective_gradient(const float *pred, bool pred_dev, const void *ta
 
 // ---- Newton leaf values: the checks, the rules on the host, one tree's sums on the device and the values from them
 void Engine::check_leaf_update(const char *what, int objective, int leaf_update, double leaf_l2) {
-    if (leaf_update != kern::kLeafGradient && leaf_update != kern::kLeafNewton)
-        throw InvalidArgument(std::string(what) + ": unknown leaf_update " + std::to_string(leaf_update) + " (gradient = 0, newton = 1)");
+    if (leaf_update != kern::kLeafGradient && leaf_update != kern::kLeafNewton && leaf_update != kern::kLeafQuantile)
+        throw InvalidArgument(std::string(what) + ": unknown leaf_update " + std::to_string(leaf_update) + " (gradient = 0, newton = 1, quantile = 2)");
     if (!(leaf_l2 >= 0.0) || std::isinf(leaf_l2))
         throw InvalidArgument(std::string(what) + ": leaf_l2 must be finite and >= 0 (and not NaN), got " + std::to_string(leaf_l2));
     if (leaf_update == kern::kLeafNewton && objective == kern::kObjRmse)
         throw InvalidArgument(std::string(what) + ": newton leaf values with the rmse objective are the gradient means the step already stores (use logistic or softmax)");
+    if (leaf_update == kern::kLeafNewton && objective == kern::kObjQuantile)
+        throw InvalidArgument(std::string(what) + ": newton leaf values with the quantile objective do not exist (its hessian is zero): use leaf_update = quantile");
+    if (leaf_update == kern::kLeafQuantile && objective != kern::kObjQuantile)
+        throw InvalidArgument(std::string(what) + ": quantile leaf values belong to the quantile objective");
 }
 
 void Engine::objective_hessian_host(const float *pred, int n, int D, int objective, float *hess_out, const float *weights) {
@@ -351,6 +380,8 @@ void Engine::objective_hessian_host(const float *pred, int n, int D, int objecti
     if (n <= 0) throw InvalidArgument("objective_hessian_host: no rows (n must be positive)");
     if (D < 1) throw InvalidArgument("objective_hessian_host: output_dim must be positive");
     check_objective("objective_hessian_host", objective, D);
+    if (objective == kern::kObjQuantile)
+        throw InvalidArgument("objective_hessian_host: the quantile objective has no hessian to offer (it is zero); its leaf step is leaf_update = quantile");
     if (weights) check_weights_host("objective_hessian_host", weights, n);
     const size_t n_el = static_cast<size_t>(n) * D;
     if (objective == kern::kObjRmse) {
@@ -474,11 +505,133 @@ void Engine::newton_leaves_prepared(const PreparedDataset *ds, const int32_t *ro
                       leaf_l2, hooks::on(hooks::CONTINUE_GENERIC), sums_out, bits_out, values_out, dw, dw ? weight_max : 0.0f);
 }
 
+// ---- leaf quantiles: the rule on the host, one tree's order statistics on the device and the values from them
+int64_t Engine::quantile_rank(int64_t m, float a) {
+    if (m < 1 || m > 0x7fffffffll) throw InvalidArgument("quantile_rank: m must be in [1, 2^31 - 1], got " + std::to_string(m));
+    if (kern::quantile_bad_level(a)) throw InvalidArgument("quantile_rank: the level " + std::to_string(a) + " is not a finite number strictly inside (0, 1)");
+    return kern::quantile_rank(m, a);
+}
+
+void Engine::leaf_quantile_host(const float *x, const int32_t *leaves, int m, int D, int n_leaves, const float *alpha, float *values_out, int64_t *counts_out,
+                                int64_t *ranks_out) {
+    if (x == nullptr || leaves == nullptr) throw InvalidArgument("leaf_quantile_host: null argument");
+    if (m <= 0) throw InvalidArgument("leaf_quantile_host: no rows (m must be positive)");
+    if (D < 1 || n_leaves < 1) throw InvalidArgument("leaf_quantile_host: leaves and output_dim must be positive");
+    check_alpha("leaf_quantile_host", kern::kObjQuantile, alpha, D, false);
+    for (size_t i = 0; i < static_cast<size_t>(m) * D; ++i)
+        if (kern::quantile_not_finite(x[i])) throw InvalidArgument("leaf_quantile_host: x[" + std::to_string(i / D) + "][" + std::to_string(i % D) + "] is not finite");
+    std::vector<std::vector<int32_t>> members(n_leaves);
+    for (int r = 0; r < m; ++r)
+        if (leaves[r] >= 0 && leaves[r] < n_leaves) members[leaves[r]].push_back(r);
+    std::vector<uint32_t> keys;
+    for (int l = 0; l < n_leaves; ++l) {
+        const std::vector<int32_t> &rows = members[l];
+        const long long cnt = static_cast<long long>(rows.size());
+        if (counts_out) counts_out[l] = cnt;
+        for (int d = 0; d < D; ++d) {
+            const size_t at = static_cast<size_t>(l) * D + d;
+            const long long k = kern::quantile_rank(cnt, alpha[d]);
+            if (ranks_out) ranks_out[at] = k;
+            if (values_out == nullptr) continue;
+            if (cnt == 0) { values_out[at] = 0.0f; continue; }
+            keys.clear();
+            for (const int32_t r : rows) keys.push_back(kern::quantile_key(x[static_cast<size_t>(r) * D + d]));
+            std::nth_element(keys.begin(), keys.begin() + (cnt - k), keys.end());   // ascending: the k-th largest is element cnt - k
+            values_out[at] = kern::quantile_key_value(keys[cnt - k]);
+        }
+    }
+}
+
+void Engine::quantile_leaves_run(const char *what, const PreparedDataset *ds, const kern::CodeRows &cr, int m, const float *d_pred, const float *d_targets,
+                                 bool abs_index, const float *d_alpha, int t, bool generic, float *values_out, int64_t *counts_out, int64_t *ranks_out) {
+    const gbrl_hip_metadata &md = model.meta;
+    hipStream_t s = stream_;
+    const int D = md.output_dim, T = md.n_trees;
+    const size_t leaf0 = static_cast<size_t>(model.tree_indices[t]);
+    const size_t NL = (t + 1 < T ? static_cast<size_t>(model.tree_indices[t + 1]) : static_cast<size_t>(md.n_leaves)) - leaf0;
+    const size_t nld = NL * D, words = kern::leaf_quantile_result_words(static_cast<int>(NL), D);
+    check_code_range(*ds, what, t, t + 1);
+    const kern::LeafQuantilePlan plan = kern::leaf_quantile_plan(m, D, static_cast<int>(NL), generic);
+    if (!plan.select && !kern::leaf_quantile_fits(m, D))
+        throw Unsupported(std::string(what) + ": quantile leaves of a tree with more than " + std::to_string([] { int l = 0; kern::leaf_quantile_geometry(&l, nullptr); return l; }()) +
+                          " leaves need rows * output_dim < 2^31 - 2048");
+    sync_model_to_device();
+    const kern::CodeTables ct = sync_code_tables(*ds);
+    const bool timed = profiling_ >= 2;
+    phase_begin();
+    uint32_t *dres = static_cast<uint32_t *>(d_lq_res_.ensure(sizeof(uint32_t) * words));
+    void *scratch = d_lq_scratch_.ensure(plan.scratch_bytes);
+    hip_check(hipMemsetAsync(dres, 0, sizeof(uint32_t) * words, s), "zero leaf quantiles");
+    kern::leaf_quantile(mirror_view(), ct, cr, m, t, static_cast<int>(leaf0), static_cast<int>(NL), d_pred, d_targets, abs_index, d_alpha, plan, scratch, dres, s);
+    lq_host_.resize(words);
+    hip_check(hipMemcpyAsync(lq_host_.data(), dres, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, s), "D2H leaf quantiles");
+    phase_end("quantile_leaves");
+    hip_check(hipGetLastError(), "quantile_leaves kernels");
+    hip_check(hipStreamSynchronize(s), "sync");
+    if (timed) {   // the phase joins the list the caller's phases are in (a step's list has been resolved already)
+        float ms = 0.f;
+        hip_check(hipEventElapsedTime(&ms, ev_pool_[ev_used_ - 1].first, ev_pool_[ev_used_ - 1].second), "hipEventElapsedTime");
+        --ev_used_;
+        ev_names_.pop_back();
+        phases_.emplace_back("quantile_leaves", ms);
+        phases_.emplace_back("quantile_select", plan.select ? 1.f : 0.f);   // (not a time: 1 = the select path took the call)
+    }
+    const uint32_t *keys = lq_host_.data(), *ranks = keys + nld, *counts = ranks + nld;
+    const uint32_t flag = counts[NL];
+    if (flag & kern::kQuantileBadTarget) throw InvalidArgument(std::string(what) + ": a target is not finite: no quantile leaf values; the model is unchanged");
+    if (flag & kern::kQuantileBadPred) throw InvalidArgument(std::string(what) + ": a prediction is not finite: no quantile leaf values; the model is unchanged");
+    if (flag & kern::kQuantileBadResidual)
+        throw InvalidArgument(std::string(what) + ": a residual fl32(prediction - target) is not finite: no quantile leaf values; the model is unchanged");
+    for (size_t l = 0; l < NL; ++l) {
+        const int depth = model.oblivious() ? model.depths[t] : model.depths[leaf0 + l];
+        if (counts[l] == 0 || depth <= 0) continue;   // (newton_core.h's rule: such a leaf keeps the value the step gave it)
+        float *v = model.values.data() + (leaf0 + l) * D;
+        for (int d = 0; d < D; ++d) v[d] = kern::quantile_key_value(keys[l * D + d]);
+    }
+    ++model.version;
+    rewind_values(t);
+    if (values_out) std::memcpy(values_out, model.values.data() + leaf0 * D, sizeof(float) * nld);
+    if (counts_out) for (size_t l = 0; l < NL; ++l) counts_out[l] = counts[l];
+    if (ranks_out) for (size_t i = 0; i < nld; ++i) ranks_out[i] = ranks[i];
+}
+
+void Engine::quantile_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *pred, bool pred_dev, const float *targets,
+                                      bool targets_dev, const float *alpha, int tree, float *values_out, int64_t *counts_out, int64_t *ranks_out) {
+    const gbrl_hip_metadata &md = model.meta;
+    const int D = md.output_dim, T = md.n_trees;
+    check_prepared_dataset("quantile_leaves_prepared", ds);
+    if (D > 128) throw Unsupported("quantile_leaves_prepared: output_dim > 128");
+    if (pred == nullptr) throw InvalidArgument("quantile_leaves_prepared: no prediction");
+    if (targets == nullptr) throw InvalidArgument("Cannot call quantile_leaves_prepared without targets!");
+    check_alpha("quantile_leaves_prepared", kern::kObjQuantile, alpha, D, false);
+    if (T == 0) throw InvalidArgument("quantile_leaves_prepared: the model has no trees");
+    if (tree < -1 || tree >= T) throw InvalidArgument("quantile_leaves_prepared: tree " + std::to_string(tree) + " is outside the model's " + std::to_string(T) + " trees (-1: the last)");
+    const int t = tree == -1 ? T - 1 : tree;
+    if (m <= 0) throw InvalidArgument("quantile_leaves_prepared: no rows (m must be positive)");
+    if (rows == nullptr && m != ds->n)
+        throw InvalidArgument("quantile_leaves_prepared: pred has " + std::to_string(m) + " rows, the data set " + std::to_string(ds->n) + " (pass rows to select over a subset)");
+    if (rows != nullptr && !rows_dev) check_host_rows(rows, m, ds->n);
+    check_code_range(*ds, "quantile_leaves_prepared", t, t + 1);
+    ensure_device();
+    ev_used_ = 0;
+    ev_names_.clear();
+    phases_.clear();
+    hipStream_t s = stream_;
+    const int32_t *d_rows = rows ? checked_rows(d_sub_rows_, d_rows_mm_, rows, rows_dev, m, ds->n, s) : nullptr;
+    const size_t n_el = static_cast<size_t>(m) * D;
+    const float *dp = pred_dev ? pred : upload(d_obj_pred_, pred, n_el, "H2D predictions");
+    const float *dt = targets_dev ? targets : upload(d_obj_targets_, targets, n_el, "H2D targets");
+    const float *da = upload(d_lq_alpha_, alpha, static_cast<size_t>(D), "H2D levels");
+    quantile_leaves_run("quantile_leaves_prepared", ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, dp, dt, /*abs_index=*/false, da, t,
+                        hooks::on(hooks::CONTINUE_GENERIC), values_out, counts_out, ranks_out);
+}
+
 // ---- classifier metrics: the checks, the host rule, the device pipeline (kern::metric_error / kern::metric_auc) and the value from its integers
 void Engine::check_metric(const char *what, int objective, int metric) {
     if (metric != kern::kMetricError && metric != kern::kMetricAuc)
         throw InvalidArgument(std::string(what) + ": unknown metric " + std::to_string(metric) + " (error = 1, auc = 2)");
-    if (objective == kern::kObjRmse) throw InvalidArgument(std::string(what) + ": the rmse objective has no metric (error and auc are for logistic and softmax)");
+    if (objective == kern::kObjRmse || objective == kern::kObjQuantile)
+        throw InvalidArgument(std::string(what) + ": the " + (objective == kern::kObjRmse ? "rmse" : "quantile") + " objective has no metric (error and auc are for logistic and softmax)");
     if (metric == kern::kMetricAuc && objective == kern::kObjSoftmax)
         throw Unsupported(std::string(what) + ": auc with the softmax objective (a multi-class AUC) is not supported");
 }
@@ -606,6 +759,9 @@ void Engine::precheck_fit(const void *targets, int iterations, const FitOptions 
     }
     check_objective("fit_prepared", opt.objective, md.output_dim);
     check_leaf_update("fit_prepared", opt.objective, opt.leaf_update, opt.leaf_l2);
+    check_alpha("fit_prepared", opt.objective, opt.alpha, md.output_dim, opt.weights != nullptr || (valid != nullptr && valid->weights != nullptr));
+    if (opt.leaf_update == kern::kLeafQuantile && opt.goss_other != 0.0)
+        throw Unsupported("fit_prepared: goss with quantile leaf values is not supported (the amplified rows would need a weighted quantile)");
     if (opt.metric != kern::kMetricNone) {
         if (valid == nullptr) throw InvalidArgument("fit_prepared: eval_metric needs a validation set (valid=)");
         check_metric("fit_prepared", opt.objective, opt.metric);
@@ -632,7 +788,7 @@ struct Engine::Held {
 
 // A walk that ended in a trailing run of one-leaf greedy trees applied nothing for them (it ran off the ensemble): it resumes at the first of them.
 void Engine::advance_held(Held &h, int start, int bn, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
-                          int objective, const float *weights) {
+                          int objective, const float *weights, const float *d_alpha) {
     const int T = model.meta.n_trees, D = model.meta.output_dim;
     int &through = h.through[start / h.bs];
     int from = through;
@@ -644,7 +800,7 @@ void Engine::advance_held(Held &h, int start, int bn, const float *targets, floa
     const size_t at = static_cast<size_t>(start) * (objective == kern::kObjSoftmax ? 1 : D);   // (softmax: a label per row)
     kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{h.ds->prep.d_codes, h.ds->n, h.ds->code_groups(), nullptr, start}, bn, from, T, p, p,
                                  targets ? targets + at : nullptr, grad_out, loss_targets ? loss_targets + at : nullptr, loss_part, generic, stream_, objective,
-                                 weights ? weights + start : nullptr);
+                                 weights ? weights + start : nullptr, d_alpha);
     through = T;
 }
 
@@ -658,6 +814,7 @@ struct Engine::FitRun {
     const bool generic = hooks::on(hooks::CONTINUE_GENERIC);
     const float *dtar = nullptr, *dvtar = nullptr;   // the targets on the device (softmax: int32 labels behind them, one per row)
     const float *dw = nullptr, *dvw = nullptr;       // the row weights of the two sets on the device (null: none)
+    const float *d_alpha = nullptr;                  // quantile: the levels on the device
     float wmax = 0.0f;                               // the largest training weight: what the Newton quantum makes room for
     double W, Wv = 0.0;                              // what the two losses and the bias divide by: the weights' float64 sums, or the row counts
     std::vector<int32_t> class_counts;               // softmax: rows per class of the training set
@@ -695,6 +852,7 @@ struct Engine::FitRun {
         dtar = stage(e.d_fp_targets_, targets, targets_dev, n);
         if (v) dvtar = stage(e.d_fp_vtargets_, v->targets, v->targets_dev, v->ds->n);
         if (v) Wv = static_cast<double>(v->ds->n);
+        if (opt.alpha) d_alpha = e.upload(e.d_lq_alpha_, opt.alpha, static_cast<size_t>(D), "H2D levels");
         if (opt.weights) {
             dw = opt.weights_dev ? opt.weights : e.upload(e.d_fp_weights_, opt.weights, static_cast<size_t>(n), "H2D weights");
             const WeightStats st = e.check_weights("fit_prepared (weights)", dw, n, true);
@@ -708,6 +866,7 @@ struct Engine::FitRun {
             throw InvalidArgument("fit_prepared: the largest weight times goss's amplification (1 - top_rate) / other_rate is above 65536: the Newton quantum has no room for it");
         if (opt.metric == kern::kMetricAuc) count_positives();
         if (opt.leaf_update == kern::kLeafNewton && opt.objective == kern::kObjLogistic) check_unit_targets();
+        if (opt.objective == kern::kObjQuantile) check_finite_targets();
         if (opt.objective != kern::kObjSoftmax) return;
         e.check_labels("fit_prepared", reinterpret_cast<const int32_t *>(dtar), n, D, &class_counts);
         if (v) e.check_labels("fit_prepared (valid_targets)", reinterpret_cast<const int32_t *>(dvtar), v->ds->n, D, nullptr);
@@ -722,6 +881,18 @@ struct Engine::FitRun {
         hip_check(hipMemcpyAsync(&flag, d, sizeof(flag), hipMemcpyDeviceToHost, s), "D2H target flag");
         hip_check(hipStreamSynchronize(s), "sync");
         if (flag) throw InvalidArgument("fit_prepared: a logistic target is outside [0, 1] (or NaN): newton leaf values need targets in [0, 1]");
+    }
+    // quantile: a training target that is not finite is refused before anything changes (the bias and the leaf kernels would flag it too, a warm start
+    // only after its first step)
+    void check_finite_targets() {
+        hipStream_t s = e.stream_;
+        uint32_t flag = 0;
+        uint32_t *d = static_cast<uint32_t *>(e.d_lq_res_.ensure(sizeof(uint32_t)));
+        hip_check(hipMemsetAsync(d, 0, sizeof(uint32_t), s), "zero target flag");
+        kern::leaf_quantile_check_targets(dtar, static_cast<size_t>(n) * D, d, s);
+        hip_check(hipMemcpyAsync(&flag, d, sizeof(flag), hipMemcpyDeviceToHost, s), "D2H target flag");
+        hip_check(hipStreamSynchronize(s), "sync");
+        if (flag) throw InvalidArgument("fit_prepared: a target is not finite: the quantile objective needs finite targets");
     }
     // auc: the positives of every validation column; a column of one class is refused before anything changes
     void count_positives() {
@@ -740,7 +911,21 @@ struct Engine::FitRun {
     // With weights: sum w y / W per column and the weight W_c of a class, from column_sums' own reduction with the weight as a per-row factor.
     void set_bias(ColumnStats &stats) {
         Model &model = e.model;
-        if (opt.objective == kern::kObjSoftmax && dw) {   // the weighted log prior, an empty class counted as half a mean row
+        if (opt.objective == kern::kObjQuantile) {   // quantile_core.h: one leaf of every row at p = 0 -- the k-th smallest target of the column, k from n
+            hipStream_t s = e.stream_;
+            const size_t words = kern::leaf_quantile_result_words(1, D);
+            uint32_t *dres = static_cast<uint32_t *>(e.d_lq_res_.ensure(sizeof(uint32_t) * words));
+            void *scratch = e.d_lq_scratch_.ensure(kern::leaf_quantile_bias_scratch_bytes(n, D));
+            hip_check(hipMemsetAsync(dres, 0, sizeof(uint32_t) * words, s), "zero bias quantiles");
+            kern::leaf_quantile_bias(dtar, n, D, d_alpha, scratch, dres, s);
+            e.lq_host_.resize(words);
+            hip_check(hipMemcpyAsync(e.lq_host_.data(), dres, sizeof(uint32_t) * words, hipMemcpyDeviceToHost, s), "D2H bias quantiles");
+            hip_check(hipGetLastError(), "fit_prepared kernels");
+            hip_check(hipStreamSynchronize(s), "sync");
+            if (e.lq_host_[words - 1] & kern::kQuantileBadTarget)
+                throw InvalidArgument("fit_prepared: a target is not finite: the quantile objective needs finite targets");
+            for (int d = 0; d < D; ++d) model.bias[d] = -kern::quantile_key_value(e.lq_host_[d]);
+        } else if (opt.objective == kern::kObjSoftmax && dw) {   // the weighted log prior, an empty class counted as half a mean row
             const std::vector<double> &hs = stats.weighted_sums(nullptr, reinterpret_cast<const int32_t *>(dtar), dw, n);
             const double floor_w = 0.5 * W / static_cast<double>(n);
             for (int d = 0; d < D; ++d) model.bias[d] = static_cast<float>(std::log(std::max(hs[d], floor_w) / W));
@@ -796,7 +981,7 @@ struct Engine::FitRun {
     void evaluate(int k) {
         const int nv = v->ds->n;
         v->done = k;
-        e.advance_held(watched, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, opt.objective, dvw);
+        e.advance_held(watched, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, opt.objective, dvw, d_alpha);
         double sum = 0.0;
         e.finish_loss_sum(d_vpart, kern::staged_loss_partials(nv), d_vsums + k, v->rounds > 0 ? &sum : nullptr);
         if (opt.metric != kern::kMetricNone) measure(k);
@@ -872,7 +1057,7 @@ struct Engine::FitRun {
         const int trees = e.model.meta.n_trees;
         e.begin_step_profile();
         e.phase_begin();
-        e.advance_held(train, start, bn, dtar, G, nullptr, nullptr, generic, opt.objective, dw);
+        e.advance_held(train, start, bn, dtar, G, nullptr, nullptr, generic, opt.objective, dw, d_alpha);
         e.phase_end("continue_codes");
         const float *g = G;
         const int32_t *rows = bn == n ? nullptr : d_iota + start;
@@ -912,6 +1097,11 @@ struct Engine::FitRun {
                                 dtar, /*abs_index=*/true, opt.objective, e.model.meta.n_trees - 1, opt.leaf_l2, generic, nullptr, nullptr, nullptr,
                                 amplified ? d_eff : dw, amplified ? kern::obj_weighted(dw ? wmax : 1.0f, amp) : wmax);
         }
+        if (opt.leaf_update == kern::kLeafQuantile) {   // likewise: the level's order statistic of the residuals of the rows the tree was grown on
+            const bool kept = rows == d_srows && rows != nullptr;
+            e.quantile_leaves_run("fit_prepared", ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), kept ? d_srows : nullptr, kept ? 0 : start}, m, train.P,
+                                  dtar, /*abs_index=*/true, d_alpha, e.model.meta.n_trees - 1, generic, nullptr, nullptr, nullptr);
+        }
         start += bn;                                                                // fitter.cpp:228-231
         if (start >= n) start = 0;
         bn = start + bs < n ? bs : n - start;
@@ -922,14 +1112,14 @@ struct Engine::FitRun {
     float final_loss(ColumnStats &stats) {
         const bool rmse = opt.objective == kern::kObjRmse && dw == nullptr;
         for (int b0 = 0; b0 < n; b0 += bs)
-            e.advance_held(train, b0, std::min(bs, n - b0), rmse ? dtar : nullptr, rmse ? G + static_cast<size_t>(b0) * D : nullptr, nullptr, nullptr, generic, opt.objective);
+            e.advance_held(train, b0, std::min(bs, n - b0), rmse ? dtar : nullptr, rmse ? G + static_cast<size_t>(b0) * D : nullptr, nullptr, nullptr, generic, opt.objective, nullptr, d_alpha);
         if (rmse) {
             hip_check(hipGetLastError(), "fit_prepared kernels");
             return stats.rmse(G, n);
         }
         const int nb = kern::staged_loss_partials(n);
         double *d_part = static_cast<double *>(e.d_obj_part_.ensure(sizeof(double) * nb)), *d_sum = static_cast<double *>(e.d_obj_sum_.ensure(sizeof(double)));
-        kern::objective_rows(opt.objective, train.P, dtar, n, D, nullptr, d_part, e.stream_, dw);
+        kern::objective_rows(opt.objective, train.P, dtar, n, D, nullptr, d_part, e.stream_, dw, d_alpha);
         double sum = 0.0;
         e.finish_loss_sum(d_part, nb, d_sum, &sum);
         hip_check(hipGetLastError(), "fit_prepared kernels");

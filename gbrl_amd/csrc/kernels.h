@@ -647,18 +647,20 @@ struct CodeTables { const int32_t *bins, *cond_pack, *grd_nodes; };
 struct CodeRows { const uint16_t *codes; int n_rows, groups; const int32_t *rows; int row0; };
 void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
                             float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic, hipStream_t s,
-                            int objective = 0, const float *weights = nullptr);
+                            int objective = 0, const float *weights = nullptr, const float *alpha = nullptr);
 // objective (kObjRmse / kObjLogistic / kObjSoftmax of objective_core.h) selects the two tails: logistic takes the same [m][D] float targets and
 // writes dL/dp of the sigmoid cross-entropy, its loss tail sums that loss; softmax takes ONE int32 label per row -- targets / loss_targets then
 // point at int32 [m] -- and writes softmax(p) - onehot.  A range without a tree runs the stand-alone kernel below on the copied base.
 // weights (nullable, device float32 [m], indexed by j; every entry checked by the caller, weight_stats below): the gradient tail stores
 // fl32(w * g) and the loss tail sums (double)w * the row loss (objective_core.h).  nullptr launches the kernels of the call without weights.
+// kObjQuantile (quantile_core.h): float targets [m][D] as rmse, alpha the device table of its D levels (required; weights are not taken): the gradient
+// tail writes the pinball step, the loss tail sums the pinball loss.
 //
 // The objectives on a prediction matrix (objective.hip): the device functions of the tails applied to pred [n][D] (device).  targets: float32
 // [n][D] (rmse, logistic) or int32 [n] (softmax; every label in [0, D): the caller checks, label_counts below).  grad_out (device [n][D]) and
 // loss_part (staged_loss_partials(n) doubles, one per 64 rows, finished by staged_loss_finish) may each be null.  D <= 128.
 void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s,
-                    const float *weights = nullptr /*device [n]: the weighted forms*/);
+                    const float *weights = nullptr /*device [n]: the weighted forms*/, const float *alpha = nullptr /*device [D]: kObjQuantile's levels*/);
 // What the engine needs to know of a weight vector (device float32 [n]) in one pass: stat[0] = the smallest row whose weight is a NaN, negative,
 // infinite or above kWeightMax (INT32_MAX: none), stat[1] = the bits of the largest entry (non-negative floats order like their bits; a refused
 // entry does not enter); part[j / 64] = the wave's sum of (double)w in the loss partials' fixed order, finished into *sum by staged_loss_finish: two
@@ -678,6 +680,26 @@ void newton_check_targets(const float *targets, size_t n_el, unsigned long long 
 bool newton_leaf_sums(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int tree, int leaf0, int n_leaves, const float *pred,
                       const void *targets, bool abs_index, int objective, int bits, unsigned long long *acc, bool generic, hipStream_t s,
                       const float *weights = nullptr);
+// Leaf quantiles (leaf_quantile.hip; quantile_core.h has the rule): the rows of cr routed through `tree` (leaves [leaf0, leaf0 + n_leaves)) by the code
+// walk; per (leaf, output d) the k-th largest x = fl32(pred - targets) among the leaf's rows, k = quantile_rank(rows of the leaf, alpha[d]).  pred and
+// targets (device float32 [.][D]) are indexed by the position j < m, or with abs_index by the data set row position j names; alpha is device float32 [D]
+// (every level checked by the caller).  res (device uint32, leaf_quantile_result_words(n_leaves, D) words, ZEROED by the caller on `s`): the selected keys
+// [n_leaves][D] (quantile_key_value gives the float; 0 for an empty leaf), the ranks [n_leaves][D], the rows per leaf [n_leaves], and the flag word
+// (kQuantileBadPred / kQuantileBadTarget / kQuantileBadResidual).  The plan decides the path once per call: the select path (an MSD radix select per
+// (leaf, output), trees of up to max_select_leaves leaves) or the general path (radix_sort.hip: by key, then stably by leaf id; needs leaf_quantile_fits:
+// m * D < 2^31 - kRadixSortTile) -- generic forces the latter.  Two different algorithms, the same bytes.  scratch holds plan.scratch_bytes.  D <= 128.
+struct LeafQuantilePlan { bool select = false; size_t scratch_bytes = 0; };
+inline size_t leaf_quantile_result_words(int n_leaves, int D) { return 2 * static_cast<size_t>(n_leaves) * D + n_leaves + 1; }
+void leaf_quantile_geometry(int *max_select_leaves, int *rows_per_chunk);
+bool leaf_quantile_fits(int m, int D);
+LeafQuantilePlan leaf_quantile_plan(int m, int D, int n_leaves, bool generic);
+void leaf_quantile(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int tree, int leaf0, int n_leaves, const float *pred,
+                   const float *targets, bool abs_index, const float *alpha, const LeafQuantilePlan &plan, void *scratch, uint32_t *res, hipStream_t s);
+// ... and the bias of a fresh model by the same rule: one leaf of every row of targets [n][D] at p = 0, the select path's passes.  res as above with
+// n_leaves = 1 (ZEROED by the caller): bias_d = -quantile_key_value(res[d]); the flag word collects kQuantileBadTarget.
+void leaf_quantile_check_targets(const float *targets, size_t n_el, uint32_t *flag /*device, zeroed by the caller*/, hipStream_t s);   // *flag |= kQuantileBadTarget: an entry that is not finite
+size_t leaf_quantile_bias_scratch_bytes(int n, int D);
+void leaf_quantile_bias(const float *targets, int n, int D, const float *alpha, void *scratch, uint32_t *res, hipStream_t s);
 // Every prefix [0, stops[s]) of the ensemble in one walk (predict_staged.hip): stage s has the bits of predict_continue(tiled bias, 0, stops[s]);
 // stops[s] == 0 is the bias alone.  `stops` is a device array, strictly ascending, 0 <= stops[s] <= n_trees (the caller has checked);
 // last_stop = stops[n_stops - 1].  Predict mode (targets == nullptr): out[s][r][j], device [n_stops][n][D].  Loss mode (targets != nullptr,

@@ -5,7 +5,8 @@
 //                      of predict_continue_codes.hip's two tails (predict_loss.h: objective_grad_store, objective_loss_regs) -- the same bits as the
 //                      fused tails.  Loss: one float64 partial per wave of 64 rows through staged_wave_sum, finished by k_staged_finish.
 //                      WEIGHTED (a template flag) with weights float32 [n]: the row's weight is loaded with the row; the gradient is fl32(w * g) and
-//                      the row loss (double)w * L in front of the butterfly.  Without the flag the pointer is never read.
+//                      the row loss (double)w * L in front of the butterfly.  Without the flag the pointer is never read -- except by the
+//                      kObjQuantile instantiations (quantile_core.h; they take no weights), whose level table alpha [D] arrives in that argument: hence its name, row_operand.
 //   k_weight_stats     a weight vector in one pass: the first row whose weight is refused, the largest weight, and the sum of the weights as
 //                      float64 partials per wave in the loss partials' order (finished by k_staged_finish: fixed order, the same bits every call).
 //   k_label_counts     class counts of an int32 label vector by integer atomics (an LDS histogram per block, then one global add per class), and
@@ -22,22 +23,22 @@ namespace {
 template <int DMAX, int OBJ, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_objective_rows(const float *__restrict__ pred, const float *__restrict__ targets, int n, int D, float *__restrict__ grad_out,
                                                         double *__restrict__ loss_part, int loss_nb, int vec_pred, int vec_tar, int vec_grad,
-                                                        const float *__restrict__ weights) {
+                                                        const float *__restrict__ row_operand) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = j < n;
     if (!live && loss_part == nullptr) return;   // (with the loss whole waves stay for the butterfly)
     float p[DMAX];
     float w = 1.0f;
-    if constexpr (WEIGHTED) w = live ? weights[j] : 0.0f;
+    if constexpr (WEIGHTED) w = live ? row_operand[j] : 0.0f;
     if (live) {
         stream_load_row<DMAX>(pred + static_cast<size_t>(j) * D, D, vec_pred != 0, p);
         if (grad_out != nullptr)
             objective_grad_store<OBJ, DMAX, WEIGHTED>(p, objective_target_row<OBJ>(targets, j, D), D, vec_tar != 0, vec_grad != 0,
-                                                      grad_out + static_cast<size_t>(j) * D, w);
+                                                      grad_out + static_cast<size_t>(j) * D, w, row_operand);
     }
     if (loss_part != nullptr) {
         double acc = 0.0;
-        if (live) acc = objective_loss_regs<OBJ, DMAX>(p, pred + static_cast<size_t>(j) * D, objective_target_row<OBJ>(targets, j, D), D, vec_tar != 0);
+        if (live) acc = objective_loss_regs<OBJ, DMAX>(p, pred + static_cast<size_t>(j) * D, objective_target_row<OBJ>(targets, j, D), D, vec_tar != 0, row_operand);
         if constexpr (WEIGHTED) acc = obj_weighted_loss(w, acc);
         acc = staged_wave_sum(acc);
         const int wave = j / kStagedRows;   // 256 = 4 x 64: a wave holds the rows of one partial
@@ -77,7 +78,8 @@ __global__ __launch_bounds__(256) void k_label_counts(const int32_t *__restrict_
 
 }  // namespace
 
-void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s, const float *weights) {
+void objective_rows(int objective, const float *pred, const void *targets, int n, int D, float *grad_out, double *loss_part, hipStream_t s, const float *weights,
+                    const float *alpha) {
     if (n <= 0 || (grad_out == nullptr && loss_part == nullptr)) return;
     const bool d4 = (D & 3) == 0;
     const int vec_pred = d4 && (reinterpret_cast<uintptr_t>(pred) & 15) == 0;
@@ -86,11 +88,13 @@ void objective_rows(int objective, const float *pred, const void *targets, int n
     auto run = [&](auto obj, auto weighted) {
         with_general_dmax(D, [&](auto dmax) {
             hipLaunchKernelGGL((k_objective_rows<decltype(dmax)::value, decltype(obj)::value, decltype(weighted)::value>), dim3((n + 255) / 256), dim3(256), 0, s,
-                               pred, static_cast<const float *>(targets), n, D, grad_out, loss_part, staged_loss_partials(n), vec_pred, vec_tar, vec_grad, weights);
+                               pred, static_cast<const float *>(targets), n, D, grad_out, loss_part, staged_loss_partials(n), vec_pred, vec_tar, vec_grad,
+                               decltype(obj)::value == kObjQuantile ? alpha : weights);
         });
     };
     with_objective(objective, [&](auto obj) {
-        if (weights != nullptr) run(obj, std::true_type{});
+        if constexpr (decltype(obj)::value == kObjQuantile) run(obj, std::false_type{});   // (no weighted form: the caller has refused weights)
+        else if (weights != nullptr) run(obj, std::true_type{});
         else run(obj, std::false_type{});
     });
 }

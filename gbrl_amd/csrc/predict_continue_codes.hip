@@ -21,7 +21,7 @@
 //                             predictions, without the second pass over them (fit_prepared's validation rows).  The streaming kernel's block is
 //                             one wave (kStreamRows == kStagedRows): one partial per block; the general kernel's four waves write four.  The two
 //                             tails are independent options.
-//   weights                   WEIGHTED (a template flag of both kernels) with weights float32 [m], indexed by j like the targets: the row's weight
+//   weights (row_operand)     WEIGHTED (a template flag of both kernels) with weights float32 [m], indexed by j like the targets: the row's weight
 //                             is loaded with its prediction, so it is in flight with the code tile; the gradient tail stores fl32(w * g) and the
 //                             loss tail multiplies the row loss by (double)w in front of the butterfly (objective_core.h has the rule).  One
 //                             vector for the call: it weighs whichever tails are on.  Without the flag the pointer is never read.
@@ -48,14 +48,14 @@ template <int DMAX, int OBJ, bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_continue_codes_general(ChainModel cm, CodeRows cr, int m, int start_tree, int stop_tree, const float *base, float *out,
                                                                 const float *__restrict__ targets, float *__restrict__ grad_out,
                                                                 const float *__restrict__ loss_targets, double *__restrict__ loss_part, int loss_nb,
-                                                                const float *__restrict__ weights) {
+                                                                const float *__restrict__ row_operand) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = j < m;
     if (!live && loss_targets == nullptr) return;   // (with the loss tail whole waves stay for the butterfly)
     const int D = cm.D;
     float p[DMAX];
     float w = 1.0f;
-    if constexpr (WEIGHTED) w = live ? weights[j] : 0.0f;
+    if constexpr (WEIGHTED) w = live ? row_operand[j] : 0.0f;
     if (live) {
 #pragma unroll
         for (int d = 0; d < DMAX; ++d) p[d] = d < D ? base[static_cast<size_t>(j) * D + d] : 0.0f;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void k_continue_codes_general(ChainModel cm, C
         } else {
             stream_store_row<DMAX>(out + static_cast<size_t>(j) * D, D, false, p);
             if (targets != nullptr)
-                objective_grad_store<OBJ, DMAX, WEIGHTED>(p, objective_target_row<OBJ>(targets, j, D), D, false, false, grad_out + static_cast<size_t>(j) * D, w);
+                objective_grad_store<OBJ, DMAX, WEIGHTED>(p, objective_target_row<OBJ>(targets, j, D), D, false, false, grad_out + static_cast<size_t>(j) * D, w, row_operand);
         }
     }
     if (loss_targets != nullptr) {
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void k_continue_codes_general(ChainModel cm, C
         if constexpr (OBJ == kObjRmse) {
             if (live) acc = staged_row_loss<DMAX>(p, loss_targets + static_cast<size_t>(j) * D, D);
         } else {
-            if (live) acc = objective_loss_regs<OBJ, DMAX>(p, out + static_cast<size_t>(j) * D, objective_target_row<OBJ>(loss_targets, j, D), D, false);
+            if (live) acc = objective_loss_regs<OBJ, DMAX>(p, out + static_cast<size_t>(j) * D, objective_target_row<OBJ>(loss_targets, j, D), D, false, row_operand);
         }
         if constexpr (WEIGHTED) acc = obj_weighted_loss(w, acc);
         acc = staged_wave_sum(acc);
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, S
                                                                 int stop_tree, const float *base, float *out, const float *__restrict__ targets,
                                                                 float *__restrict__ grad_out, const float *__restrict__ loss_targets,
                                                                 double *__restrict__ loss_part, int vec_values, int vec_io, int vec_grad, int vec_loss,
-                                                                const float *__restrict__ weights) {
+                                                                const float *__restrict__ row_operand) {
     extern __shared__ __align__(16) uint32_t cctile[];   // [kStreamRows][stream_code_stride(G)]
     const int lane = threadIdx.x;
     const int D = cm.D;
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, S
     const size_t row = static_cast<size_t>(r0) + lane;
     float p[DMAX];
     float w = 1.0f;
-    if constexpr (WEIGHTED) w = live ? weights[row] : 0.0f;   // (one coalesced float per lane, in flight with the row and the tile)
+    if constexpr (WEIGHTED) w = live ? row_operand[row] : 0.0f;   // (one coalesced float per lane, in flight with the row and the tile)
     if (live) {
         stream_load_row<DMAX>(base + row * D, D, vec_io != 0, p);
     } else {
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, S
             }
         } else {
             if (targets != nullptr)
-                objective_grad_store<OBJ, DMAX, WEIGHTED>(p, objective_target_row<OBJ>(targets, row, D), D, vec_grad != 0, vec_grad != 0, grad_out + row * D, w);
+                objective_grad_store<OBJ, DMAX, WEIGHTED>(p, objective_target_row<OBJ>(targets, row, D), D, vec_grad != 0, vec_grad != 0, grad_out + row * D, w, row_operand);
         }
     }
     if (loss_targets != nullptr) {   // (block-uniform; the block is one wave: one partial)
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, S
                 acc = staged_row_loss<DMAX>(p, y, D);
             }
         } else {
-            if (live) acc = objective_loss_regs<OBJ, DMAX>(p, out + row * D, objective_target_row<OBJ>(loss_targets, row, D), D, vec_loss != 0);
+            if (live) acc = objective_loss_regs<OBJ, DMAX>(p, out + row * D, objective_target_row<OBJ>(loss_targets, row, D), D, vec_loss != 0, row_operand);
         }
         if constexpr (WEIGHTED) acc = obj_weighted_loss(w, acc);
         acc = staged_wave_sum(acc);
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(kStreamRows) void k_continue_codes(ChainModel cm, S
 
 template <int DMAX, bool GREEDY, int OBJ, bool WEIGHTED>
 bool launch_continue_codes(const ChainModel &cm, const PredictModel &pm, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
-                           float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, const float *weights,
+                           float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, const float *row_operand,
                            hipStream_t s) {
     static_assert(kStreamRows == kStagedRows, "a block of the streaming kernel writes exactly one loss partial");
     const size_t lds = stream_code_tile_bytes(cr.groups);
@@ -172,7 +172,7 @@ bool launch_continue_codes(const ChainModel &cm, const PredictModel &pm, const C
     const int vec_loss = d4 && (reinterpret_cast<uintptr_t>(loss_targets) & 15) == 0;
     hipLaunchKernelGGL((k_continue_codes<DMAX, GREEDY, OBJ, WEIGHTED>), dim3((m + kStreamRows - 1) / kStreamRows), dim3(kStreamRows), lds, s, cm,
                        stream_owner<DMAX>(pm), pm.coef_cover, cr, m, start_tree, stop_tree, base, out, targets, grad_out, loss_targets, loss_part, vec_values,
-                       vec_io, vec_grad, vec_loss, weights);
+                       vec_io, vec_grad, vec_loss, row_operand);
     return true;
 }
 
@@ -186,14 +186,14 @@ void tile_rows(const float *row, int D, int n, float *out, hipStream_t s) {
 
 void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *base,
                             float *out, const float *targets, float *grad_out, const float *loss_targets, double *loss_part, bool generic,
-                            hipStream_t s, int objective, const float *weights) {
+                            hipStream_t s, int objective, const float *weights, const float *alpha) {
     if (m <= 0) return;
     if (stop_tree <= start_tree || pm.n_opts <= 0) {   // no tree to apply, or no optimizer that owns an output: the base as it is
         const size_t n_el = static_cast<size_t>(m) * pm.D;
         if (out != base) (void)hipMemcpyAsync(out, base, sizeof(float) * n_el, hipMemcpyDeviceToDevice, s);
         if (objective != kObjRmse || weights != nullptr) {   // the stand-alone kernel of the objective: the tails' device functions on the matrix
-            if (targets != nullptr) objective_rows(objective, out, targets, m, pm.D, grad_out, nullptr, s, weights);
-            if (loss_targets != nullptr) objective_rows(objective, out, loss_targets, m, pm.D, nullptr, loss_part, s, weights);
+            if (targets != nullptr) objective_rows(objective, out, targets, m, pm.D, grad_out, nullptr, s, weights, alpha);
+            if (loss_targets != nullptr) objective_rows(objective, out, loss_targets, m, pm.D, nullptr, loss_part, s, weights, alpha);
             return;
         }
         if (targets != nullptr) {
@@ -211,21 +211,23 @@ void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const 
     auto run = [&](auto obj, auto weighted) {
         constexpr int OBJ = decltype(obj)::value;
         constexpr bool WEIGHTED = decltype(weighted)::value;
+        const float *const row_operand = OBJ == kObjQuantile ? alpha : weights;   // WEIGHTED: the weights [m]; kObjQuantile (never WEIGHTED): its level table [D]
         if (chain_streamable(pm, generic) && with_stream_dmax(pm.D, [&](auto dmax) {
                 constexpr int DMAX = decltype(dmax)::value;
                 return pm.oblivious ? launch_continue_codes<DMAX, false, OBJ, WEIGHTED>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out,
-                                                                                        loss_targets, loss_part, weights, s)
+                                                                                        loss_targets, loss_part, row_operand, s)
                                     : launch_continue_codes<DMAX, true, OBJ, WEIGHTED>(cm, pm, cr, m, start_tree, stop_tree, base, out, targets, grad_out,
-                                                                                       loss_targets, loss_part, weights, s);
+                                                                                       loss_targets, loss_part, row_operand, s);
             }))
             return;
         with_general_dmax(pm.D, [&](auto dmax) {
             hipLaunchKernelGGL((k_continue_codes_general<decltype(dmax)::value, OBJ, WEIGHTED>), dim3((m + 255) / 256), dim3(256), 0, s, cm, cr, m, start_tree,
-                               stop_tree, base, out, targets, grad_out, loss_targets, loss_part, staged_loss_partials(m), weights);
+                               stop_tree, base, out, targets, grad_out, loss_targets, loss_part, staged_loss_partials(m), row_operand);
         });
     };
     with_objective(objective, [&](auto obj) {
-        if (weights != nullptr) run(obj, std::true_type{});
+        if constexpr (decltype(obj)::value == kObjQuantile) run(obj, std::false_type{});   // (no weighted form: the caller has refused weights)
+        else if (weights != nullptr) run(obj, std::true_type{});
         else run(obj, std::false_type{});
     });
 }

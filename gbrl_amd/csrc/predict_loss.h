@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "objective_core.h"
+#include "quantile_core.h"
 #include "predict_rowwalk.h"
 
 namespace gbrl {
@@ -85,8 +86,10 @@ __device__ __forceinline__ double softmax_row_loss(const float (&p)[DMAX], int l
 // The gradient row of an objective from the scores p and the row's targets, stored to g_row.  y_row: float32 [D] of the row (rmse, logistic: read
 // four at a time) or its int32 label (softmax: one entry, the row's probabilities in a second register row).  WEIGHTED: every entry is
 // obj_weighted(w, g), w the row's weight, one float32 multiply behind the rule; without it w is not read and the code is what it was.
+// kObjQuantile (quantile_core.h; never WEIGHTED): alpha is the device table of the D levels, read only by that instantiation.
 template <int OBJ, int DMAX, bool WEIGHTED = false>
-__device__ __forceinline__ void objective_grad_store(const float (&p)[DMAX], const float *y_row, int D, bool vec_y, bool vec_g, float *g_row, float w = 1.0f) {
+__device__ __forceinline__ void objective_grad_store(const float (&p)[DMAX], const float *y_row, int D, bool vec_y, bool vec_g, float *g_row, float w = 1.0f,
+                                                     const float *alpha = nullptr) {
     if constexpr (OBJ == kObjSoftmax) {
         float g[DMAX];
 #pragma unroll
@@ -108,6 +111,11 @@ __device__ __forceinline__ void objective_grad_store(const float (&p)[DMAX], con
                     g.y = 4 * q + 1 < D ? obj_logistic_grad(p[4 * q + 1], y.y) : 0.0f;
                     g.z = 4 * q + 2 < D ? obj_logistic_grad(p[4 * q + 2], y.z) : 0.0f;
                     g.w = 4 * q + 3 < D ? obj_logistic_grad(p[4 * q + 3], y.w) : 0.0f;
+                } else if constexpr (OBJ == kObjQuantile) {
+                    g.x = obj_quantile_grad(p[4 * q], y.x, alpha[4 * q]);
+                    g.y = 4 * q + 1 < D ? obj_quantile_grad(p[4 * q + 1], y.y, alpha[4 * q + 1]) : 0.0f;
+                    g.z = 4 * q + 2 < D ? obj_quantile_grad(p[4 * q + 2], y.z, alpha[4 * q + 2]) : 0.0f;
+                    g.w = 4 * q + 3 < D ? obj_quantile_grad(p[4 * q + 3], y.w, alpha[4 * q + 3]) : 0.0f;
                 } else {
                     g.x = __fsub_rn(p[4 * q], y.x); g.y = __fsub_rn(p[4 * q + 1], y.y); g.z = __fsub_rn(p[4 * q + 2], y.z); g.w = __fsub_rn(p[4 * q + 3], y.w);
                 }
@@ -129,9 +137,27 @@ __device__ __forceinline__ void objective_grad_store(const float (&p)[DMAX], con
 // ... and its loss.  p_row: the row as the lane itself has stored it (or read it).  The widest family (DMAX = 128) sums the logistic loss from
 // there in a rolled loop -- the same terms in the same order: 128 unrolled float64 exp / log1p beside p[128] do not fit the register file.
 template <int OBJ, int DMAX>
-__device__ __forceinline__ double objective_loss_regs(const float (&p)[DMAX], const float *p_row, const float *y_row, int D, bool vec4) {
+__device__ __forceinline__ double objective_loss_regs(const float (&p)[DMAX], const float *p_row, const float *y_row, int D, bool vec4,
+                                                      const float *alpha = nullptr) {
     if constexpr (OBJ == kObjSoftmax) {
         return softmax_row_loss<DMAX>(p, *reinterpret_cast<const int32_t *>(y_row), D);
+    } else if constexpr (OBJ == kObjQuantile && DMAX > 64) {   // the pinball terms, j ascending (quantile_core.h: every step rounded on its own)
+        double acc = 0.0;
+#pragma unroll 1
+        for (int j = 0; j < D; ++j) acc = quantile_loss_add(acc, quantile_loss_term(p_row[j], y_row[j], alpha[j]));
+        return acc;
+    } else if constexpr (OBJ == kObjQuantile) {   // the same terms in the same order from the registers, the targets read four at a time
+        double acc = 0.0;
+#pragma unroll
+        for (int q = 0; q < DMAX / 4; ++q)
+            if (4 * q < D) {
+                const float4 y = objective_load4(y_row, q, D, vec4);
+                const float yy[4] = {y.x, y.y, y.z, y.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (4 * q + k < D) acc = quantile_loss_add(acc, quantile_loss_term(p[4 * q + k], yy[k], alpha[4 * q + k]));
+            }
+        return acc;
     } else if constexpr (OBJ == kObjLogistic && DMAX > 64) {
         double acc = 0.0;
 #pragma unroll 1
@@ -168,6 +194,7 @@ template <typename Fn>
 auto with_objective(int objective, Fn &&f) {
     if (objective == kObjLogistic) return f(std::integral_constant<int, kObjLogistic>{});
     if (objective == kObjSoftmax) return f(std::integral_constant<int, kObjSoftmax>{});
+    if (objective == kObjQuantile) return f(std::integral_constant<int, kObjQuantile>{});
     return f(std::integral_constant<int, kObjRmse>{});
 }
 

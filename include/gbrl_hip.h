@@ -695,6 +695,64 @@ int gbrl_hip_fit_prepared_goss(gbrl_hip_model *m, const gbrl_hip_dataset *ds, co
                                int valid_weights_on_device, double goss_top, double goss_other, float *loss_out,
                                double *valid_loss_out /*[iterations + 1]*/, double *valid_metric_out /*[iterations + 1]*/, int *iterations_done,
                                int *best_n_trees, float *weight_max_out);
+/* Quantile regression (new: LightGBM's objective="quantile", scikit-learn's loss="quantile", XGBoost's reg:quantileerror).  csrc/quantile_core.h
+ * defines all of it once for the host and the kernels; like the AUC and the Newton sums the result is integers before it is a number, and every
+ * selected value is one of the inputs, bit for bit.
+ *   levels      alpha float32 [output_dim], one per output, every entry finite and strictly inside (0, 1); anything else is GBRL_HIP_E_INVALID naming
+ *               the output.
+ *   GBRL_HIP_OBJ_QUANTILE, output_dim >= 1, targets float32 [n, D]: x = fl32(p - y) (the bits of the rmse gradient); g = x > 0 ? fl32(1 - a_d) :
+ *               (x < 0 ? -a_d : 0).  Row loss in float64 from the float32 inputs: u = (double)y - (double)p, sum_d (u >= 0 ? a_d u : (a_d - 1) u); loss and
+ *               valid_loss are the mean row loss, reduced in the fixed order of the other objectives.  g is dL/dp.
+ *   rank        a leaf of m >= 1 rows: k = clamp(ceil(a_d m), 1, m), the product EXACT (a_d = M 2^-s, M < 2^24, m < 2^31: 64-bit integers and a shift; a
+ *               shift that leaves the word gives 1).  A double product can round across an integer and is not the rule.
+ *   leaf value  GBRL_HIP_LEAF_QUANTILE: v[leaf][d] = the k-th LARGEST x among the rows of the leaf (-0 counts as +0), no arithmetic on it.  Predictions
+ *               move by -rate v; -v is the k-th smallest residual y - p: NumPy's quantile(method="inverted_cdf"), a minimiser of the leaf's pinball sum
+ *               -- where a gradient leaf, the mean of values in [-a, 1 - a], moves a fit by at most the learning rate per tree.  A leaf without rows or
+ *               of depth 0 keeps the value the step gave it.
+ *   bias        of a fresh model: the same rule on one leaf of every row at p = 0: bias_d = the k-th smallest y_d, k from n.
+ *   gbrl_hip_fit_prepared_quantile(.., goss_top, goss_other, alpha, loss_out, ..)  gbrl_hip_fit_prepared_goss plus alpha (host [D]); the older entries are
+ *     this one with NULL and enqueue exactly what they did.  GBRL_HIP_LEAF_QUANTILE: right after every step the new tree's leaves get
+ *     gbrl_hip_quantile_leaves_prepared's values from the rows the tree was grown on (the batch; the kept rows of a subsampled iteration), one enqueue
+ *     and one read-back, only that tree's values sent again: the model is byte for byte the loop objective_gradient -> step_prepared ->
+ *     quantile_leaves_prepared -> predict_continue_prepared written by hand.  Refused before anything changes: GBRL_HIP_OBJ_QUANTILE without alpha, alpha
+ *     with another objective, a bad level, GBRL_HIP_LEAF_QUANTILE with another objective, GBRL_HIP_LEAF_NEWTON with GBRL_HIP_OBJ_QUANTILE (the hessian
+ *     is zero), a metric with it, a training target that is not finite (a fresh model or a warm start); (GBRL_HIP_E_UNSUPPORTED) weights or valid_weights with it, goss with
+ *     GBRL_HIP_LEAF_QUANTILE (both would need a weighted quantile; goss with gradient leaves works as with any objective).
+ *   gbrl_hip_quantile_leaves_prepared(m, ds, rows, rows_on_device, n_rows, pred, .., targets, .., alpha, tree, values_out, counts_out, ranks_out)  the
+ *     leaves of ONE tree (-1: the last) from the data set rows `rows` (NULL: all of them); pred and targets [n_rows, D] are indexed by position.  Two
+ *     kernel paths (an MSD radix select per (leaf, output) for trees of up to max_select_leaves leaves; a sort by key and leaf id beyond, and behind
+ *     GBRL_HIP_CONTINUE_GENERIC=1) return the same bytes.  values_out [leaves, D] what the model now holds, counts_out int64 [leaves], ranks_out int64
+ *     [leaves, D] (0 for an empty leaf); each may be NULL.  Refused before anything changes: whatever gbrl_hip_newton_leaves_prepared refuses about the
+ *     model, the data set, rows, the tree and output_dim, and a bad level; after the launch, the model unchanged: a prediction, a target or a residual
+ *     that is not finite.
+ *   gbrl_hip_leaf_quantile_host(x [m, D], leaves [m], m, D, n_leaves, alpha, values_out, counts_out, ranks_out)  the rule with no device (an entry of
+ *     leaves outside [0, n_leaves) joins no leaf; an empty leaf has the value 0).  gbrl_hip_quantile_rank(m, a, rank_out)  the rank function.
+ *   gbrl_hip_leaf_quantile_geometry(max_select_leaves, rows_per_chunk)  the largest tree of the select path and the rows one block of its count pass
+ *     takes at a time, for tests that straddle them.
+ *   gbrl_hip_objective_gradient_quantile / gbrl_hip_objective_gradient_host_quantile(.., alpha, ..)  the objective calls with the levels (NULL: those
+ *     calls); the same bits on both sides.
+ *   Out of scope: weighted and interpolated quantiles, Huber and L1 as objectives of their own, quantile leaves in fit(), step() and refit_leaves,
+ *     crossing-quantile repair. */
+enum { GBRL_HIP_OBJ_QUANTILE = 3 };
+enum { GBRL_HIP_LEAF_QUANTILE = 2 };
+int gbrl_hip_fit_prepared_quantile(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                                   const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                                   double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update,
+                                   double leaf_l2, const float *weights /*[n]*/, int weights_on_device, const float *valid_weights /*[valid rows]*/,
+                                   int valid_weights_on_device, double goss_top, double goss_other, const float *alpha /*host [output_dim], may be NULL*/,
+                                   float *loss_out, double *valid_loss_out /*[iterations + 1]*/, double *valid_metric_out /*[iterations + 1]*/,
+                                   int *iterations_done, int *best_n_trees, float *weight_max_out);
+int gbrl_hip_quantile_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *pred,
+                                      int pred_on_device, const float *targets, int targets_on_device, const float *alpha /*host [output_dim]*/, int tree,
+                                      float *values_out /*[leaves, D]*/, int64_t *counts_out /*[leaves]*/, int64_t *ranks_out /*[leaves, D]*/);
+int gbrl_hip_leaf_quantile_host(const float *x /*[m, D]*/, const int32_t *leaves /*[m]*/, int m, int D, int n_leaves, const float *alpha /*[D]*/,
+                                float *values_out /*[n_leaves, D]*/, int64_t *counts_out /*[n_leaves]*/, int64_t *ranks_out /*[n_leaves, D]*/);
+int gbrl_hip_quantile_rank(int64_t m, float a, int64_t *rank_out);
+void gbrl_hip_leaf_quantile_geometry(int *max_select_leaves, int *rows_per_chunk);
+int gbrl_hip_objective_gradient_quantile(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device,
+                                         const float *alpha /*host [output_dim]*/, int n, int objective, float *grad_out, double *loss_out);
+int gbrl_hip_objective_gradient_host_quantile(const float *pred, const void *targets, const float *alpha /*[D]*/, int n, int D, int objective,
+                                              float *grad_out /*[n, D]*/);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
