@@ -4,7 +4,7 @@ to the host rule; here
      predict_continue_prepared written from the public pieces, through both kernel paths: a fresh model, a warm start, batches, row and column
      sampling, a validation set with early stopping;
   2. the same with leaf_update="gradient" against its loop (without the leaf call), one-side sampling among the cases;
-  3. a fresh model's bias is the k-th smallest target of every column, k = gbrl_cpp.quantile_rank(n, alpha_d);
+  3. a fresh model's bias is the k-th smallest target of every column, k = gbrl_cpp.quantile_rank(n, alpha_d), also where a block of the count pass takes several chunks;
   4. two runs give the same bytes;
   5. at batch_size = n without sampling the loss after 10 trees is strictly below the loss of the bias alone;
   6. what is refused leaves the model as it was: a fresh model, and a warm start whose targets hold a NaN or an infinity.
@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import gbrl_amd
+import quantile_cases as Q   # tests/golden (conftest.py puts it on the path)
 
 pytestmark = pytest.mark.gpu
 
@@ -247,6 +248,33 @@ def test_the_bias_is_the_order_statistic_of_every_column(n, D):
     want = np.array([np.sort(y[:, d])[cpp.quantile_rank(n, float(alpha[d])) - 1] for d in range(D)], f32)
     got = np.asarray(m.get_bias(), f32).reshape(D)
     assert (got + f32(0)).tobytes() == (want + f32(0)).tobytes(), (got, want)   # (+ 0: a zero of either sign is the same bias)
+
+
+MAX_COUNT_BLOCKS = 32   # kMaxCountBlocks of leaf_quantile.hip: beyond 32 chunks of rows_per_chunk rows a block of the count pass takes a second chunk
+
+
+@pytest.mark.parametrize("D", [1, 3])
+@pytest.mark.parametrize("n", [2049, 65537, 70001])
+@pytest.mark.parametrize("draw", ["shared_prefix_ties", "continuous"])
+def test_the_bias_where_the_count_pass_takes_more_chunks(draw, n, D):
+    """one chunk and a row; 32 chunks and a row (block 0 takes two); 35 chunks (three blocks take two).  The ties are 40 targets that share
+    their upper 16 bits (tests/golden/quantile_cases.py): the last two digits decide"""
+    R = cpp.leaf_quantile_geometry()["rows_per_chunk"]
+    assert n > R and (n == 2049 or n > MAX_COUNT_BLOCKS * R)
+    X, T = _data(n, 9, D, seed=n + D)
+    if draw == "shared_prefix_ties":
+        T = _shape(Q.values("shared_prefix_ties", n, D, seed=n), D)
+        assert all(len(np.unique(T.reshape(n, D)[:, d])) == Q.TIE_KEYS for d in range(D))
+    else:   # the last row, alone in its chunk at 2049 and 65537, is the smallest target of every column: without it every rank moves
+        T = T.copy()
+        T[-1] = T.min(axis=0) - f32(1)
+    alpha = _levels(D) if D > 1 else np.array([0.3], f32)
+    m = _model(9, D, batch_size=n)
+    m.fit_prepared(m.prepare_dataset(X), T, 1, objective="quantile", alpha=alpha, leaf_update="quantile")
+    y = T.reshape(n, D)
+    want = np.array([np.sort(y[:, d])[cpp.quantile_rank(n, float(alpha[d])) - 1] for d in range(D)], f32)
+    got = np.asarray(m.get_bias(), f32).reshape(D)
+    assert (got + f32(0)).tobytes() == (want + f32(0)).tobytes(), (got, want)
 
 
 # ---- 4. reproducible ----------------------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 gbrl_cpp.eval_metric_host to a NumPy brute force; here the device's integers are the host rule's, integer for integer, and the value the same
 double.  The sizes sit around the sort's tile of 2048 elements (one tile, its edge, three tiles) and around the 64 lanes of a wave; the score
 families cover both branches of the key, heavy ties (five values with both zeros and both infinities), one value everywhere, a perfect
-separation and a run of 5000 equal keys across tile boundaries."""
+separation and a run of 5000 equal keys across tile boundaries.  Columns of 32768, 32769 and 70001 rows (and a run of 40000 equal keys) are where
+the sort's scan fills one slice of 4096 counts exactly and where it carries its sum into a second and a third."""
 import numpy as np
 import pytest
 
@@ -65,6 +66,21 @@ def _same(got, want, what):
 @pytest.mark.parametrize("D", [1, 3, 8])
 @pytest.mark.parametrize("n", SIZES)
 def test_device_counts_are_the_host_counts(n, D):
+    _counts_are_the_host_counts(n, D)
+
+
+SORT_TILE, SCAN_SLICE = 2048, 4096   # radix_sort.hip: the elements of a tile, the words of a column's 256 per tile that its scan takes per trip
+
+
+@pytest.mark.parametrize("D", [1, 3])
+@pytest.mark.parametrize("n,slices", [(32768, 1), (32769, 2), (70001, 3)])
+def test_device_counts_where_the_scan_takes_another_slice(n, slices, D):
+    """16 tiles x 256 digits fill one slice of the sort's scan; from 32769 rows on it carries its running sum from slice to slice"""
+    assert -(-256 * -(-n // SORT_TILE) // SCAN_SLICE) == slices and (n > 16 * SORT_TILE) == (slices > 1)
+    _counts_are_the_host_counts(n, D)
+
+
+def _counts_are_the_host_counts(n, D):
     rng = np.random.default_rng(8000 + 31 * n + D)
     m = _model(D)
     y = _targets(rng, n, D)
@@ -104,6 +120,22 @@ def test_a_run_of_equal_keys_across_tiles():
     p = np.empty((n, D), np.float32)
     for d, below in enumerate((600, 1145, 0)):
         col = np.concatenate([-1.0 - rng.permutation(below), np.full(5000, 0.125), 1.0 + rng.permutation(n - 5000 - below)]).astype(np.float32)
+        p[:, d] = rng.permutation(col)
+    want = host(p, y, "logistic", "auc")
+    _same(_model(D).eval_metric(p, y, "logistic", "auc"), want, "tie run")
+    assert 0.0 < want[0] < 1.0
+
+
+def test_a_run_of_equal_keys_across_scan_slices():
+    """one value at 40000 consecutive sorted positions of a column of 70001 rows (35 tiles, three slices of the scan: the run fills one digit's
+    counts of some twenty tiles), distinct scores below and above it; the other columns have the run at other offsets"""
+    rng = np.random.default_rng(8501)
+    n, D, run = 70001, 3, 40000
+    assert n > 16 * SORT_TILE and run > 16 * SORT_TILE
+    y = _targets(rng, n, D)
+    p = np.empty((n, D), np.float32)
+    for d, below in enumerate((600, 30001, 0)):
+        col = np.concatenate([-1.0 - rng.permutation(below), np.full(run, 0.125), 1.0 + rng.permutation(n - run - below)]).astype(np.float32)
         p[:, d] = rng.permutation(col)
     want = host(p, y, "logistic", "auc")
     _same(_model(D).eval_metric(p, y, "logistic", "auc"), want, "tie run")

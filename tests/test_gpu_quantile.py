@@ -5,7 +5,10 @@ step_prepared, the rows are routed with predict_leaves on the observations, the 
   2. the model holds those values for that tree and every other tree is untouched; predict sees them (the mirror was sent again);
   3. rows= (duplicates, a subset that misses a leaf) indexes pred and targets by position; tree=0 of two trees takes the tiled bias;
   4. what the kernel refuses (a target or a prediction that is not finite) leaves the model bytes as they were;
-  5. GBRL.objective_gradient(..., 'quantile', alpha=) gives the host gradient's bytes and the float64 pinball loss within the summation bound.
+  5. GBRL.objective_gradient(..., 'quantile', alpha=) gives the host gradient's bytes and the float64 pinball loss within the summation bound;
+  6. 1. again on the key families of tests/golden/quantile_cases.py (keys that share a prefix down to the last digit, denormals, the largest
+     floats), with the rank on the edge of a tie run, at the row counts where the count pass, the target pass and the sort's scan take another
+     trip (up to 131073 rows), at 128 outputs and on a tree whose leaf ids need two bytes; every such test asserts the path and the geometry it is for.
 """
 import math
 import os
@@ -14,6 +17,7 @@ import numpy as np
 import pytest
 
 import gbrl_amd
+import quantile_cases as Q   # tests/golden (conftest.py puts it on the path)
 
 pytestmark = pytest.mark.gpu
 
@@ -95,8 +99,15 @@ def _tree_span(m, tree):
     return ens, leaf0, leaf1
 
 
-def _check(m, ds_n, Xn, pred, T, D, tree, policy, alpha, rows=None, paths=("0", "1")):
-    """both kernel paths against the host rule; returns (values the model holds afterwards, counts)"""
+def _check(m, ds_n, Xn, pred, T, D, tree, policy, alpha, rows=None, paths=("0", "1"), select=None):
+    """both kernel paths against the host rule; returns (values the model holds afterwards, counts).  select = True / False: the calls are
+    profiled, and the one without GBRL_HIP_CONTINUE_GENERIC must say that the select path took it (True) or the sort (False); the other the sort"""
+    if select is not None:
+        m.set_profiling(2)
+        try:
+            return _check(m, ds_n, Xn, pred, T, D, tree, policy, alpha, rows=rows, paths=tuple((g, select and g == "0") for g in paths))
+        finally:
+            m.set_profiling(0)
     sel = np.arange(Xn.shape[0]) if rows is None else rows
     ens0, leaf0, leaf1 = _tree_span(m, tree)
     NL = leaf1 - leaf0
@@ -112,8 +123,11 @@ def _check(m, ds_n, Xn, pred, T, D, tree, policy, alpha, rows=None, paths=("0", 
     kw = {} if rows is None else {"rows": np.asarray(rows, np.int32)}
     got = []
     for generic in paths:   # the select path (where the tree fits it) and the general one
+        generic, took_select = generic if isinstance(generic, tuple) else (generic, None)
         with _env("GBRL_HIP_CONTINUE_GENERIC", generic):
             r = m.quantile_leaves_prepared(ds_n, _shape(pred, D), _shape(T.reshape(n, D), D), alpha, tree=tree, **kw)
+        if took_select is not None:
+            assert dict(m.last_phase_times())["quantile_select"] == (1.0 if took_select else 0.0), "generic = %s took the other path" % generic
         assert sorted(r) == ["counts", "ranks", "values"]
         assert r["values"].dtype == f32 and r["values"].shape == (NL, D) and r["counts"].dtype == np.int64 and r["counts"].shape == (NL,)
         assert r["ranks"].dtype == np.int64 and r["ranks"].shape == (NL, D)
@@ -273,6 +287,218 @@ def test_the_kernel_path_is_the_one_named(depth, generic, select):
         m.set_profiling(0)
     assert "quantile_leaves" in phases and phases["quantile_leaves"] > 0.0
     assert phases["quantile_select"] == select
+
+
+# ---- the key families of tests/golden/quantile_cases.py and the row counts at which the kernels' loops take another trip ----------------------------------
+# tests/test_quantile_host.py holds the host rule to np.sort on every family; pred = 0 and targets = -x make fl32(pred - targets) the family's x.
+MAX_COUNT_BLOCKS = 32    # kMaxCountBlocks of leaf_quantile.hip: the count pass has at most this many blocks per output, each striding over the chunks
+SORT_TILE = 2048         # kRadixSortTile: the elements of one tile of radix_sort.hip
+SCAN_SLICE = 4096        # kScanSlice: the words k_radix_scan takes per trip, of the 256 per tile of a segment
+_BOUND = {}
+
+
+def _bound(m, ds, n, F):
+    """n rows of fresh observations and their data set on the thresholds of ds"""
+    key = (id(ds), n)
+    if key not in _BOUND:
+        if len(_BOUND) >= 3:
+            _BOUND.clear()
+        Xn = np.random.default_rng(n).standard_normal((n, F)).astype(f32)
+        _BOUND[key] = (ds, Xn, m.prepare_dataset(Xn, reference=ds))
+    return _BOUND[key][1:]
+
+
+def _last_row_decides(targets):
+    """the last row gets the largest residual of every column (above every value of the distinct family): where it is alone in its chunk or
+    its tile, a pass that loses it moves every rank of its leaf, and with distinct keys every value"""
+    out = targets.copy()
+    out[-1] = -np.array([0x50000001], np.uint32).view(f32)[0]
+    return out
+
+
+def _geometry(n):
+    """(count blocks per output, chunks block 0 takes, slices of the sort's scan) at n rows"""
+    chunks = -(-n // GEO["rows_per_chunk"])
+    blocks = min(chunks, MAX_COUNT_BLOCKS)
+    return blocks, -(-chunks // blocks), -(-256 * -(-n // SORT_TILE) // SCAN_SLICE)
+
+
+@pytest.mark.parametrize("policy", ["oblivious", "greedy"])
+@pytest.mark.parametrize("name", Q.FAMILIES)
+def test_key_families_are_the_host_rules(name, policy):
+    D, n = 3, 2049
+    m, ds, X, T, before = _case(17, D, policy, 3)
+    Xn, ds_n = _bound(m, ds, n, 17)
+    pred, targets = Q.family(name, n, D, seed=1)
+    want, counts = _check(m, ds_n, Xn, pred, targets, D, 0, policy, _levels(D), select=True)
+    assert (counts > 0).sum() >= 2
+    if name == "denormal_by_subtraction":   # the values are denormals, not zeros: nothing was flushed
+        live = want[counts > 0]
+        assert (np.abs(live) < Q.SMALLEST_NORMAL).all() and (live != 0).any()
+
+
+@pytest.mark.parametrize("policy", ["oblivious", "greedy"])
+@pytest.mark.parametrize("c", [64, 256])
+def test_the_rank_on_the_edge_of_a_tie_run(c, policy):
+    """every leaf has c (then c + 1) rows, the larger half of them b and the others a < b, two neighbouring floats: at the levels 1/4, 1/2, 3/4
+    the k-th largest is inside the run of b, on its edge (the last b at c rows, the first a at c + 1 rows with c / 2 of b, the last b again with
+    c / 2 + 1 of b) and inside the run of a.  Only the last digit tells a from b"""
+    D = 3
+    alpha = np.array([0.25, 0.5, 0.75], f32)
+    m, ds, X, T, before = _case(17, D, policy, 3)
+    ens, leaf0, leaf1 = _tree_span(m, 0)
+    leaves = np.asarray(m.predict_leaves(X, None, 0, 1)).reshape(-1) - leaf0
+    present = np.unique(leaves)
+    assert len(present) >= 2 and c % 4 == 0
+    a, b = np.array([0x3f800010, 0x3f800011], np.uint32).view(f32)
+    assert a < b
+    rng = np.random.default_rng(c)
+    for per_leaf, n_b in ((c, c // 2), (c + 1, c // 2), (c + 1, c // 2 + 1)):
+        rows = rng.permutation(np.concatenate([rng.choice(np.nonzero(leaves == l)[0], per_leaf) for l in present])).astype(np.int32)
+        x = np.empty((len(rows), D), f32)
+        for l in present:
+            at = np.nonzero(leaves[rows] == l)[0]
+            assert len(at) == per_leaf
+            for d in range(D):
+                col = np.full(per_leaf, a, f32)
+                col[rng.permutation(per_leaf)[:n_b]] = b
+                x[at, d] = col
+        want, counts = _check(m, ds, X, np.zeros_like(x), np.ascontiguousarray(-x), D, 0, policy, alpha, rows=rows, select=True)
+        k = [cpp.quantile_rank(per_leaf, float(v)) for v in alpha]
+        assert k[1] in (n_b, n_b + 1) and k[0] < n_b < k[2]            # the middle rank is the last b or the first a
+        expect = np.array([b if kk <= n_b else a for kk in k], f32)
+        assert expect[0] == b and expect[2] == a and expect[1] == (b if k[1] == n_b else a)
+        for l in present:
+            assert counts[l] == per_leaf and want[l].tobytes() == expect.tobytes(), (per_leaf, n_b, l, want[l], expect)
+
+
+LOOP_SIZES = {   # rows: (count blocks, chunks of block 0, scan slices) -- what _geometry must say, or the sizes no longer reach what they are here for
+    2047: (1, 1, 1), 2048: (1, 1, 1), 4097: (3, 1, 1), 6145: (4, 1, 1),
+    32768: (16, 1, 1),      # the largest column one scan slice covers: 16 tiles x 256 digits
+    32769: (17, 1, 2),      # the scan carries its sum into a second slice
+    65535: (32, 1, 2), 65536: (32, 1, 2),   # every count block one chunk
+    65537: (32, 2, 3),      # block 0 strides to a second chunk of one row
+    131073: (32, 3, 5),     # every block a second full chunk, block 0 a third of one row
+}
+
+
+@pytest.mark.parametrize("n", sorted(LOOP_SIZES))
+@pytest.mark.parametrize("name", ["distinct", "shared_prefix_ties"])
+def test_row_counts_that_reach_every_loop(name, n):
+    D, R = 3, GEO["rows_per_chunk"]
+    assert sorted(LOOP_SIZES) == [R - 1, R, 2 * R + 1, 3 * R + 1, 16 * SORT_TILE, 16 * SORT_TILE + 1, MAX_COUNT_BLOCKS * R - 1, MAX_COUNT_BLOCKS * R,
+                                  MAX_COUNT_BLOCKS * R + 1, 2 * MAX_COUNT_BLOCKS * R + 1]
+    assert _geometry(n) == LOOP_SIZES[n]
+    if n >= 65537:
+        assert n > MAX_COUNT_BLOCKS * R          # a block of the count pass takes more than one chunk
+    if n >= 32769:
+        assert n > 16 * SORT_TILE and 256 * 16 == SCAN_SLICE   # the scan makes more than one trip
+    m, ds, X, T, before = _case(17, D, "oblivious", 3)
+    Xn, ds_n = _bound(m, ds, n, 17)
+    pred, targets = Q.family(name, n, D, seed=2)
+    if name == "distinct":
+        targets = _last_row_decides(targets)
+    want, counts = _check(m, ds_n, Xn, pred, targets, D, 0, "oblivious", _levels(D), select=True)
+    assert (counts > 0).sum() >= 2 and counts.sum() == n
+
+
+BIG = 65537   # MAX_COUNT_BLOCKS * rows_per_chunk + 1: the smallest size at which a count block takes a second chunk
+
+
+def test_a_greedy_tree_of_64_leaves_at_a_second_chunk():
+    """the largest tree of the select path (its counters need the LDS opt-in) where block 0 takes two chunks"""
+    D = 3
+    assert BIG > MAX_COUNT_BLOCKS * GEO["rows_per_chunk"]
+    m, ds, X, T, before = _case(17, D, "greedy", 6, n_grow=4000)
+    ens, leaf0, leaf1 = _tree_span(m, 0)
+    assert leaf1 - leaf0 == GEO["max_select_leaves"] == 64, "the tree has %d leaves" % (leaf1 - leaf0)
+    Xn, ds_n = _bound(m, ds, BIG, 17)
+    for name in ("distinct", "shared_prefix_ties"):
+        pred, targets = Q.family(name, BIG, D, seed=3)
+        if name == "distinct":
+            targets = _last_row_decides(targets)
+        want, counts = _check(m, ds_n, Xn, pred, targets, D, 0, "greedy", _levels(D), select=True)
+        assert (counts > 0).sum() > 32
+
+
+def test_one_output_at_a_second_chunk():
+    D = 1
+    assert BIG > MAX_COUNT_BLOCKS * GEO["rows_per_chunk"]
+    m, ds, X, T, before = _case(17, D, "oblivious", 3)
+    Xn, ds_n = _bound(m, ds, BIG, 17)
+    for name in ("distinct", "shared_prefix_ties"):
+        pred, targets = Q.family(name, BIG, D, seed=4)
+        if name == "distinct":
+            targets = _last_row_decides(targets)
+        _check(m, ds_n, Xn, pred, targets, D, 0, "oblivious", _levels(D), select=True)
+
+
+def test_rows_from_a_larger_data_set_at_a_second_chunk():
+    """rows= draws 65537 positions with duplicates from 70001 rows; then from the rows of every leaf but one: that leaf keeps its value and counts 0"""
+    D, n_all = 3, 70001
+    assert BIG > MAX_COUNT_BLOCKS * GEO["rows_per_chunk"]
+    m, ds, X, T, before = _case(17, D, "oblivious", 3)
+    Xall, ds_all = _bound(m, ds, n_all, 17)
+    rng = np.random.default_rng(BIG)
+    rows = rng.integers(0, n_all, BIG).astype(np.int32)
+    assert len(np.unique(rows)) < BIG and rows.max() >= BIG
+    pred, targets = Q.family("distinct", BIG, D, seed=5)
+    targets = _last_row_decides(targets)
+    want, counts = _check(m, ds_all, Xall, pred, targets, D, 0, "oblivious", _levels(D), rows=rows, select=True)
+    assert counts.sum() == BIG
+    ens, leaf0, leaf1 = _tree_span(m, 0)
+    leaves = np.asarray(m.predict_leaves(Xall, None, 0, 1)).reshape(-1) - leaf0
+    present = np.unique(leaves)
+    assert len(present) >= 2
+    gone = int(present[0])
+    pool = np.nonzero(leaves != gone)[0]
+    rows = pool[rng.integers(0, len(pool), BIG)].astype(np.int32)
+    old = np.asarray(ens["values"], f32).reshape(-1, D)[leaf0 + gone].copy()
+    pred, targets = Q.family("shared_prefix_ties", BIG, D, seed=6)
+    want, counts = _check(m, ds_all, Xall, pred, targets, D, 0, "oblivious", _levels(D), rows=rows, select=True)
+    assert counts[gone] == 0 and counts.sum() == BIG and want[gone].tobytes() == old.tobytes()
+
+
+@pytest.mark.parametrize("policy", ["oblivious", "greedy"])
+def test_the_widest_model(policy):
+    D, n = 128, 2049
+    m, ds, X, T, before = _case(16, D, policy, 3)
+    Xn, ds_n = _bound(m, ds, n, 16)
+    pred, targets = Q.family("distinct", n, D, seed=7)
+    want, counts = _check(m, ds_n, Xn, pred, targets, D, 0, policy, _levels(D), select=True)
+    assert (counts > 0).sum() >= 2
+    pred, targets = Q.family("shared_prefix_ties", n, D, seed=7)
+    _check(m, ds_n, Xn, pred, targets, D, 0, policy, _levels(D), select=True)
+
+
+@pytest.mark.parametrize("generic", ["0", "1"])
+def test_one_output_more_than_the_widest_is_refused(generic, tmp_path):
+    D, n = 129, 65
+    m = _model(16, D, "oblivious", 3)
+    X = np.random.default_rng(D).standard_normal((n, 16)).astype(f32)
+    ds = m.prepare_dataset(X)
+    keep = _file(m, tmp_path)
+    pred, targets = Q.family("distinct", n, D, seed=8)
+    with _env("GBRL_HIP_CONTINUE_GENERIC", generic):
+        with pytest.raises(RuntimeError, match="output_dim"):
+            m.quantile_leaves_prepared(ds, pred, targets, _levels(D))
+    assert _file(m, tmp_path) == keep
+
+
+def test_a_tree_of_more_than_255_leaves():
+    """the leaf ids need a second byte: the sort by id makes two passes (lq_id_passes).  Depth 9 on 4000 rows is the smallest of the grids
+    depth {9, 10} x rows {4000, 8000, 20000} and reaches 380 leaves"""
+    D, n = 3, 4000
+    m, ds, X, T, before = _case(8, D, "greedy", 9, n_grow=n)
+    ens, leaf0, leaf1 = _tree_span(m, 0)
+    assert leaf1 - leaf0 >= 256, "the tree has %d leaves: the sort by leaf id would make one pass" % (leaf1 - leaf0)
+    pred, targets = Q.family("distinct", n, D, seed=9)
+    want, counts = _check(m, ds, X, pred, targets, D, 0, "greedy", _levels(D), select=False)
+    assert (counts[256:] > 0).any() and (counts[:256] > 0).any()
+    sub = np.random.default_rng(9).permutation(n)[:700].astype(np.int32)   # many leaves without a row
+    pred, targets = Q.family("shared_prefix_ties", 700, D, seed=9)
+    want, counts = _check(m, ds, X, pred, targets, D, 0, "greedy", _levels(D), rows=sub, select=False)
+    assert (counts == 0).any() and (counts[256:] > 0).any()
 
 
 @pytest.mark.parametrize("n,D", [(1, 1), (65, 3), (200, 8), (257, 65)])

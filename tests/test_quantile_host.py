@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import gbrl_amd
+import quantile_cases as Q   # tests/golden (conftest.py puts it on the path)
 
 cpp = gbrl_amd.gbrl_cpp
 E_INVALID = -1
@@ -123,6 +124,49 @@ def test_leaf_rule_is_the_order_statistic(m):
         for d in range(D):
             if len(u):
                 assert -np.float64(r["values"][l, d]) == np.quantile(u[:, d], float(alpha[d]), method="inverted_cdf")
+
+
+@pytest.mark.parametrize("n_leaves", [1, 8])
+@pytest.mark.parametrize("m", [257, 5000])
+@pytest.mark.parametrize("name", Q.FAMILIES)
+def test_leaf_rule_on_the_key_families(name, m, n_leaves):
+    """the families tests/test_gpu_quantile.py holds the kernels to (tests/golden/quantile_cases.py): the host rule is np.sort's order statistic on
+    every one of them, so it is a reference there; the residuals are finite, and the families are what their names say"""
+    D = 3
+    pred, targets = Q.family(name, m, D, seed=m + n_leaves)
+    x = Q.residual(pred, targets)
+    assert x.dtype == f32 and x.shape == (m, D) and pred.dtype == f32 and targets.dtype == f32
+    bits = x.view(np.uint32)
+    if name == "denormal_by_subtraction":
+        assert (np.abs(pred) >= Q.SMALLEST_NORMAL).all() and (np.abs(targets) >= Q.SMALLEST_NORMAL).all() and (np.abs(x) < Q.SMALLEST_NORMAL).all()
+        assert (x > 0).any() and (x < 0).any() and all(len(np.unique(x[:, d])) > 100 for d in range(D))
+    else:
+        assert not pred.any() and x.tobytes() == (Q.values(name, m, D, seed=m + n_leaves) + f32(0)).tobytes()   # (+ 0: the zeros are +0)
+    if name == "distinct":
+        assert all(len(np.unique(x[:, d])) == m for d in range(D)) and (x > 0).any() and (x < 0).any()
+    if name in ("last_byte", "third_byte", "second_byte"):
+        shift = {"last_byte": 0, "third_byte": 8, "second_byte": 16}[name]
+        r = ((bits & np.uint32(0x7fffffff)) - np.uint32(0x3f800000)) >> np.uint32(shift)
+        assert (r < 256).all() and ((r << np.uint32(shift)) + np.uint32(0x3f800000) == (bits & np.uint32(0x7fffffff))).all()
+        assert all(len(np.unique(bits[:, d])) == min(m, 512) for d in range(D))
+    if name == "shared_prefix_ties":
+        assert ((bits >> np.uint32(16)) == 0x3f80).all() and all(len(np.unique(bits[:, d])) == Q.TIE_KEYS for d in range(D))
+    if name == "zeros_and_denormals":
+        assert (np.abs(x) <= Q.SMALLEST_NORMAL).all() and all(len(np.unique(bits[:, d])) == 7 for d in range(D))   # (-0 has become +0)
+    if name == "huge":
+        assert np.abs(x).max() == np.finfo(f32).max and (np.abs(x) >= f32(2.0 ** 127)).all() and (x > 0).any() and (x < 0).any()
+    if name == "negative_only":
+        assert (x < 0).all()
+    if name == "all_equal":
+        assert len(np.unique(bits)) == 1
+    rng = np.random.default_rng(m)
+    leaves = np.zeros(m, np.int32) if n_leaves == 1 else rng.integers(0, n_leaves, m).astype(np.int32)
+    alpha = np.array([0.05, 0.5, 0.95], f32)
+    r = cpp.leaf_quantile_host(x, leaves, n_leaves, alpha)
+    values, counts, ranks = _sorted_rule(x, leaves, n_leaves, alpha)
+    assert (counts > 0).all()
+    assert r["counts"].tobytes() == counts.tobytes() and r["ranks"].tobytes() == ranks.tobytes()
+    assert r["values"].tobytes() == values.tobytes(), (r["values"], values)
 
 
 def test_leaf_rule_extreme_ranks_and_scalar_level():
