@@ -143,8 +143,9 @@ int parse_parity_mode(const std::string &s) {
 }
 // objective names of fit_prepared(objective=), objective_gradient and objective_gradient_host (GBRL_HIP_OBJ_*, include/gbrl_hip.h)
 int parse_objective(const std::string &s) {
-    return parse_enum(s, {{"rmse", GBRL_HIP_OBJ_RMSE}, {"logistic", GBRL_HIP_OBJ_LOGISTIC}, {"softmax", GBRL_HIP_OBJ_SOFTMAX}, {"quantile", GBRL_HIP_OBJ_QUANTILE}},
-                      "Invalid objective! Options are: rmse/logistic/softmax/quantile");
+    return parse_enum(s, {{"rmse", GBRL_HIP_OBJ_RMSE}, {"logistic", GBRL_HIP_OBJ_LOGISTIC}, {"softmax", GBRL_HIP_OBJ_SOFTMAX}, {"quantile", GBRL_HIP_OBJ_QUANTILE},
+                          {"pairwise", GBRL_HIP_OBJ_PAIRWISE}, {"lambdarank", GBRL_HIP_OBJ_LAMBDARANK}},
+                      "Invalid objective! Options are: rmse/logistic/softmax/quantile/pairwise/lambdarank");
 }
 // metric names of fit_prepared(eval_metric=), eval_metric and eval_metric_host (GBRL_HIP_METRIC_*, include/gbrl_hip.h)
 int parse_metric(const std::string &s) {
@@ -906,7 +907,8 @@ py::object predict_continue_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
 
 // the targets of an objective: float32 [n, D] ([n] when D == 1) for rmse and logistic, int32 [n] labels for softmax
 Input read_objective_targets(py::object &targets, const char *name, bool none_allowed, const std::string &fn, int objective, int n, int D, bool check_shape) {
-    if (objective != GBRL_HIP_OBJ_SOFTMAX) {
+    const bool ranking = objective == GBRL_HIP_OBJ_PAIRWISE || objective == GBRL_HIP_OBJ_LAMBDARANK;   // int32 relevance labels [n]
+    if (objective != GBRL_HIP_OBJ_SOFTMAX && !ranking) {
         Input t = read_input(targets, name, none_allowed, fn, false);
         if (check_shape && t.ptr) check_rows_by_outputs(t, name, n, D);
         return t;
@@ -914,7 +916,7 @@ Input read_objective_targets(py::object &targets, const char *name, bool none_al
     Input t = read_input(targets, name, none_allowed, fn, 2);
     if (check_shape && t.ptr && !(t.shape.size() == 1 && t.shape[0] == static_cast<size_t>(n))) {
         std::stringstream ss;
-        ss << "Expected " << name << " of the softmax objective as int32 class labels of shape (" << n << ",)";
+        ss << "Expected " << name << " of the " << (ranking ? "ranking objective as int32 relevance labels" : "softmax objective as int32 class labels") << " of shape (" << n << ",)";
         fail(ss.str());
     }
     return t;
@@ -960,11 +962,18 @@ std::vector<float> read_alpha(const py::object &alpha, int D, const std::string 
 // fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,
 // objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
 // with either.  A missing valid_targets is left to the C ABI's message.
+std::vector<int32_t> read_group(py::object &group, const std::string &fn, const char *name = "group");
+int read_ndcg_at(py::object &ndcg_at, const std::string &fn);
 py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
                              int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name,
                              py::object metric_obj, const std::string &leaf_update_name, double leaf_l2, py::object &weights, py::object &valid_weights,
-                             py::object goss_obj, py::object alpha_obj) {
+                             py::object goss_obj, py::object alpha_obj, py::object group_obj, py::object ndcg_at_obj, py::object valid_group_obj) {
     const gbrl_hip_metadata md = self.meta();
+    // the ranking keywords (include/gbrl_hip.h, "Ranking objectives"): None stays NULL, so that a group with another objective is refused behind the C ABI
+    std::vector<int32_t> group, valid_group;
+    if (!group_obj.is_none()) group = read_group(group_obj, "fit_prepared");
+    if (!valid_group_obj.is_none()) valid_group = read_group(valid_group_obj, "fit_prepared", "valid_group");
+    const int ndcg_at = read_ndcg_at(ndcg_at_obj, "fit_prepared");
     const std::vector<float> alpha = read_alpha(alpha_obj, md.output_dim, "fit_prepared");
     double goss_top = 0.0, goss_other = 0.0;
     if (!goss_obj.is_none()) {   // goss=(top_rate, other_rate); an other_rate of 0 is refused here, since 0 means "off" below
@@ -980,6 +989,7 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     if (valid_obj.is_none() && (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0))
         fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
     if (valid_obj.is_none() && !valid_weights.is_none()) fail("fit_prepared: valid_weights need a validation set (valid=)");
+    if (valid_obj.is_none() && !valid_group_obj.is_none()) fail("fit_prepared: valid_group needs a validation set (valid=)");
     const gbrl_hip_dataset *dsv = valid_obj.is_none() ? nullptr : valid_obj.cast<const PyDataset &>().h;
     Input w = read_weights(weights, "weights", "fit_prepared", ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, ds != nullptr), wv;
     if (dsv) wv = read_weights(valid_weights, "valid_weights", "fit_prepared", valid_obj.cast<const PyDataset &>().info().n_rows, true);
@@ -991,10 +1001,12 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     int rc, done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_quantile(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
-                                            colsample, seed, objective, metric, leaf_update, leaf_l2, static_cast<const float *>(w.ptr), w.on_device,
-                                            static_cast<const float *>(wv.ptr), wv.on_device, goss_top, goss_other, alpha.empty() ? nullptr : alpha.data(), &loss,
-                                            dsv ? curve.data() : nullptr, dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max);
+        rc = gbrl_hip_fit_prepared_rank(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                        colsample, seed, objective, metric, leaf_update, leaf_l2, static_cast<const float *>(w.ptr), w.on_device,
+                                        static_cast<const float *>(wv.ptr), wv.on_device, goss_top, goss_other, alpha.empty() ? nullptr : alpha.data(),
+                                        group.empty() ? nullptr : group.data(), static_cast<int>(group.size()), ndcg_at,
+                                        valid_group.empty() ? nullptr : valid_group.data(), static_cast<int>(valid_group.size()), &loss,
+                                        dsv ? curve.data() : nullptr, dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max);
     }
     check(rc);
     if (!dsv) return py::float_(loss);
@@ -1018,10 +1030,49 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
 // Extension: Newton leaf values (include/gbrl_hip.h, "Newton leaf values").
 // newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1, weights=None, weight_max=None) -> {'sums': int64 [leaves, 2 D + 1], 'bits', 'values': float32 [leaves, D]}
 py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &pred, py::object &targets, const std::string &objective_name, double leaf_l2,
-                                     py::object &rows, int tree, py::object &weights, py::object weight_max_obj) {
+                                     py::object &rows, int tree, py::object &weights, py::object weight_max_obj, py::object group_obj, py::object ndcg_at_obj) {
     const gbrl_hip_metadata md = self.meta();
     const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
     const int objective = parse_objective(objective_name), D = md.output_dim;
+    const bool ranking = objective == GBRL_HIP_OBJ_PAIRWISE || objective == GBRL_HIP_OBJ_LAMBDARANK;
+    if (!ranking && (!group_obj.is_none() || !ndcg_at_obj.is_none())) fail("newton_leaves_prepared: group and ndcg_at belong to the ranking objectives 'pairwise' and 'lambdarank'");
+    if (ranking) {   // g and h of rank_gradient over every row of the data set, summed from their buffers
+        const std::string fn = "newton_leaves_prepared";
+        if (!rows.is_none()) fail("newton_leaves_prepared: rows with a ranking objective is not supported (a row list cuts queries apart)");
+        if (!weights.is_none() || !weight_max_obj.is_none()) fail("newton_leaves_prepared: weights with a ranking objective are not supported");
+        const std::vector<int32_t> grp = read_group(group_obj, fn);
+        const int ndcg_at = read_ndcg_at(ndcg_at_obj, fn);
+        Input p = read_input(pred, "pred", false, fn, false);
+        if (!p.ptr) fail("Cannot call newton_leaves_prepared without pred!");
+        const int n = ds ? ds_obj.cast<const PyDataset &>().info().n_rows : (p.shape.empty() ? 0 : static_cast<int>(p.shape[0]));
+        check_rows_by_outputs(p, "pred", n, 1);
+        Input l = read_objective_targets(targets, "targets", false, fn, objective, n, 1, true);
+        if (!l.ptr) fail("Cannot call newton_leaves_prepared without targets!");
+        const py::ssize_t T = md.n_trees;
+        py::ssize_t leaves = 1;
+        if (tree >= -1 && tree < T && T > 0) {
+            std::vector<int32_t> ti(static_cast<size_t>(T));
+            const py::ssize_t tt = tree == -1 ? T - 1 : tree;
+            check(gbrl_hip_get_ensemble(self.h, ti.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+            leaves = (tt + 1 < T ? ti[tt + 1] : md.n_leaves) - ti[tt];
+        }
+        py::array_t<int64_t> sums({leaves, static_cast<py::ssize_t>(3)});
+        py::array_t<float> values({leaves, static_cast<py::ssize_t>(1)});
+        int bits = 0, rc;
+        int64_t *sp = sums.mutable_data();
+        float *vp = values.mutable_data();
+        {
+            py::gil_scoped_release release;
+            rc = gbrl_hip_newton_leaves_prepared_rank(self.h, ds, static_cast<const float *>(p.ptr), p.on_device, static_cast<const int32_t *>(l.ptr), l.on_device,
+                                                      grp.data(), static_cast<int>(grp.size()), objective, ndcg_at, tree, leaf_l2, sp, &bits, vp);
+        }
+        check(rc);
+        py::dict out;
+        out["sums"] = sums;
+        out["bits"] = py::int_(bits);
+        out["values"] = values;
+        return out;
+    }
     Input p = read_input(pred, "pred", false, "newton_leaves_prepared", false);
     if (!p.ptr) fail("Cannot call newton_leaves_prepared without pred!");
     Input r = read_rows(rows, "newton_leaves_prepared");
@@ -1198,7 +1249,16 @@ py::tuple eval_metric_host_impl(py::object &pred, py::object &targets, const std
 }
 
 // objective_gradient(pred, targets, objective, weights=None) -> (grad, loss): NumPy in, NumPy out; a device tuple gives a DLPack capsule on the model's device
-py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights, py::object alpha_obj) {
+py::dict rank_gradient_impl(PyGBRL &self, py::object &pred, py::object &labels, py::object &group, const std::string &objective_name, py::object ndcg_at_obj);
+bool rank_objective_name(const std::string &s);
+py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights, py::object alpha_obj,
+                                  py::object group, py::object ndcg_at) {
+    if (rank_objective_name(objective_name)) {   // the ranking objectives: targets are the int32 labels, the rows of a query are named by group
+        if (!weights.is_none() || !alpha_obj.is_none()) fail("objective_gradient: weights and alpha do not go with a ranking objective");
+        py::dict r = rank_gradient_impl(self, pred, targets, group, objective_name, ndcg_at);
+        return py::make_tuple(r["grad"], r["loss"]);
+    }
+    if (!group.is_none() || !ndcg_at.is_none()) fail("objective_gradient: group and ndcg_at belong to the ranking objectives 'pairwise' and 'lambdarank'");
     const gbrl_hip_metadata md = self.meta();
     const int objective = parse_objective(objective_name), D = md.output_dim;
     const std::vector<float> alpha = read_alpha(alpha_obj, D, "objective_gradient");
@@ -1264,6 +1324,150 @@ py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &ta
     }
     check(gbrl_hip_objective_gradient_host_weighted(static_cast<const float *>(p.ptr), t.ptr, static_cast<const float *>(w.ptr), n, D, objective,
                                                     out.size() ? out.mutable_data() : &none));
+    return out;
+}
+
+// ---- ranking objectives on query groups (include/gbrl_hip.h, "Ranking objectives")
+bool rank_objective_name(const std::string &s) { return s == "pairwise" || s == "lambdarank"; }
+int parse_rank_objective(const std::string &s) {
+    return parse_enum(s, {{"pairwise", GBRL_HIP_OBJ_PAIRWISE}, {"lambdarank", GBRL_HIP_OBJ_LAMBDARANK}},
+                      "Invalid objective! The ranking objectives are: pairwise/lambdarank");
+}
+int read_ndcg_at(py::object &ndcg_at, const std::string &fn) {
+    if (ndcg_at.is_none()) return 0;
+    const long long k = ndcg_at.cast<long long>();
+    if (k < 0 || k > 0x7fffffffLL) fail(fn + ": ndcg_at must be positive (or 0 / None for no truncation), got " + std::to_string(k));
+    return static_cast<int>(k);
+}
+// group: the query sizes, any integer sequence -> int32 (a size that does not fit is refused here, naming the query)
+std::vector<int32_t> read_group(py::object &group, const std::string &fn, const char *name) {
+    const std::string gname(name);
+    if (group.is_none()) fail(fn + ": a ranking objective needs " + gname + ", the sizes of the queries' consecutive row runs");
+    py::array_t<int64_t, py::array::c_style | py::array::forcecast> g = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(group);
+    if (!g || g.ndim() != 1) fail(fn + ": " + gname + " must be a one-dimensional sequence of integers");
+    std::vector<int32_t> out(static_cast<size_t>(g.size()));
+    for (py::ssize_t q = 0; q < g.size(); ++q) {
+        const int64_t v = g.data()[q];
+        if (v < 1 || v > 0x7fffffffLL) fail(fn + ": " + gname + "[" + std::to_string(q) + "] = " + std::to_string(v) + " (query " + std::to_string(q) + ") is outside [1, 1024]");
+        out[static_cast<size_t>(q)] = static_cast<int32_t>(v);
+    }
+    if (out.empty()) fail(fn + ": a ranking objective needs " + gname + ", the sizes of the queries' consecutive row runs");
+    return out;
+}
+Input read_rank_labels(py::object &labels, const std::string &fn, int n) {
+    if (py::isinstance<py::array>(labels) && !py::isinstance<py::array_t<int32_t>>(labels)) fail(fn + ": labels must be an int32 array of shape (n,)");
+    Input l = read_input(labels, "labels", false, fn, 2);
+    if (!l.ptr) fail("Cannot call " + fn + " without labels!");
+    if (l.shape.size() != 1 || l.shape[0] != static_cast<size_t>(n)) fail(fn + ": labels must be an int32 array of shape (" + std::to_string(n) + ",)");
+    return l;
+}
+int rank_rows_of(const Input &p, const std::string &fn) {
+    const bool ok = (p.shape.size() == 1 && p.shape[0] > 0) || (p.shape.size() == 2 && p.shape[1] == 1 && p.shape[0] > 0);
+    if (!ok) fail(fn + ": pred must be float32 of shape (n,) or (n, 1): a ranking objective scores a row with one number");
+    return static_cast<int>(p.shape[0]);
+}
+
+// rank_gradient(pred, labels, group, objective, ndcg_at) -> dict: NumPy in, NumPy out; a device tuple for pred gives DLPack capsules for grad, hess and positions
+py::dict rank_gradient_impl(PyGBRL &self, py::object &pred, py::object &labels, py::object &group, const std::string &objective_name, py::object ndcg_at_obj) {
+    const std::string fn = "rank_gradient";
+    const int objective = parse_rank_objective(objective_name);
+    const int ndcg_at = read_ndcg_at(ndcg_at_obj, fn);
+    Input p = read_input(pred, "pred", false, fn, false);
+    if (!p.ptr) fail("Cannot call rank_gradient without pred!");
+    const int n = rank_rows_of(p, fn);
+    Input l = read_rank_labels(labels, fn, n);
+    const std::vector<int32_t> grp = read_group(group, fn);
+    const int Q = static_cast<int>(grp.size());
+    py::array_t<double> ndcg(std::vector<py::ssize_t>{Q});
+    double loss = 0.0;
+    int64_t pairs = 0;
+    const std::vector<int64_t> shape(p.shape.begin(), p.shape.end());
+    py::dict out;
+    if (p.on_device) {
+        const int dev_id = gbrl_hip_device_ordinal(self.h);
+        if (dev_id < 0) fail(gbrl_hip_last_error());
+        struct DevMem {
+            void *p = nullptr;
+            ~DevMem() { if (p) gbrl_hip_device_free(p); }
+        } g, h, pos;
+        g.p = gbrl_hip_device_alloc_on(dev_id, sizeof(float) * n);
+        h.p = gbrl_hip_device_alloc_on(dev_id, sizeof(float) * n);
+        pos.p = gbrl_hip_device_alloc_on(dev_id, sizeof(int32_t) * n);
+        if (!g.p || !h.p || !pos.p) fail(gbrl_hip_last_error());
+        int rc;
+        {
+            py::gil_scoped_release release;
+            rc = gbrl_hip_rank_gradient(self.h, static_cast<const float *>(p.ptr), 1, static_cast<const int32_t *>(l.ptr), l.on_device, grp.data(), Q, n, objective, ndcg_at,
+                                        static_cast<float *>(g.p), static_cast<float *>(h.p), &loss, ndcg.mutable_data(), static_cast<int32_t *>(pos.p), &pairs);
+        }
+        check(rc);
+        out["grad"] = make_dlpack(g.p, shape, true, dev_id); g.p = nullptr;
+        out["hess"] = make_dlpack(h.p, shape, true, dev_id); h.p = nullptr;
+        out["positions"] = make_dlpack(pos.p, {n}, true, dev_id, /*int32=*/true); pos.p = nullptr;
+    } else {
+        py::array_t<float> g(std::vector<py::ssize_t>(shape.begin(), shape.end())), h(std::vector<py::ssize_t>(shape.begin(), shape.end()));
+        py::array_t<int32_t> pos(std::vector<py::ssize_t>{n});
+        int rc;
+        {
+            py::gil_scoped_release release;
+            rc = gbrl_hip_rank_gradient(self.h, static_cast<const float *>(p.ptr), 0, static_cast<const int32_t *>(l.ptr), l.on_device, grp.data(), Q, n, objective, ndcg_at,
+                                        g.mutable_data(), h.mutable_data(), &loss, ndcg.mutable_data(), pos.mutable_data(), &pairs);
+        }
+        check(rc);
+        out["grad"] = g;
+        out["hess"] = h;
+        out["positions"] = pos;
+    }
+    out["loss"] = py::float_(loss);
+    out["ndcg"] = ndcg;
+    out["pairs"] = py::int_(pairs);
+    return out;
+}
+
+// the rule on the host: no device, no model
+py::dict rank_gradient_host_impl(py::object &scores, py::object &labels, py::object &group, const std::string &objective_name, py::object ndcg_at_obj) {
+    const std::string fn = "rank_gradient_host";
+    const int objective = parse_rank_objective(objective_name);
+    const int ndcg_at = read_ndcg_at(ndcg_at_obj, fn);
+    Input p = read_input(scores, "scores", false, fn, false);
+    if (p.on_device) fail("rank_gradient_host takes NumPy arrays");
+    const int n = rank_rows_of(p, fn);
+    Input l = read_rank_labels(labels, fn, n);
+    if (l.on_device) fail("rank_gradient_host takes NumPy arrays");
+    const std::vector<int32_t> grp = read_group(group, fn);
+    const int Q = static_cast<int>(grp.size());
+    py::array_t<float> g(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end())), h(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
+    py::array_t<int32_t> pos(std::vector<py::ssize_t>{n});
+    py::array_t<double> ndcg(std::vector<py::ssize_t>{Q});
+    double loss = 0.0;
+    int64_t pairs = 0;
+    const bool with_loss = objective == GBRL_HIP_OBJ_LAMBDARANK;
+    check(gbrl_hip_rank_gradient_host(static_cast<const float *>(p.ptr), static_cast<const int32_t *>(l.ptr), grp.data(), Q, n, objective, ndcg_at, g.mutable_data(),
+                                      h.mutable_data(), with_loss ? &loss : nullptr, ndcg.mutable_data(), pos.mutable_data(), &pairs));
+    py::dict out;
+    out["grad"] = g;
+    out["hess"] = h;
+    if (with_loss) out["loss"] = py::float_(loss);
+    out["ndcg"] = ndcg;
+    out["positions"] = pos;
+    out["pairs"] = py::int_(pairs);
+    return out;
+}
+
+py::array_t<double> rank_discounts_impl() {
+    int cap = 0;
+    gbrl_hip_rank_geometry(&cap, nullptr);
+    py::array_t<double> out(std::vector<py::ssize_t>{cap});
+    check(gbrl_hip_rank_discounts(out.mutable_data()));
+    return out;
+}
+
+py::dict rank_geometry_impl() {
+    int cap = 0, label = 0;
+    gbrl_hip_rank_geometry(&cap, &label);
+    py::dict out;
+    out["max_query"] = cap;
+    out["max_label"] = label;
     return out;
 }
 
@@ -1484,6 +1688,18 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "entry finite and in [0, 65536]): fl32(w * g) row by row, one float32 multiply behind the rule; all-ones weights change no bit.\n"
           "'quantile' with alpha (a level in (0, 1), or one per output): x = fl32(p - y), g = 1 - alpha where x > 0, -alpha where x < 0, 0 where x == 0; it takes no\n"
           "weights, and alpha goes with no other objective.");
+    m.def("rank_gradient_host", &rank_gradient_host_impl, py::arg("scores"), py::arg("labels"), py::arg("group"), py::arg("objective"), py::arg("ndcg_at") = py::none(),
+          "rank_gradient_host(scores, labels, group, objective, ndcg_at=None) -> {'grad', 'hess', 'ndcg', 'positions', 'pairs'} (and 'loss' for 'lambdarank')\n\n"
+          "The rule of GBRL.rank_gradient on the host (no device is needed), the one definition the kernels compile too: scores float32 [n], labels int32 [n]\n"
+          "in [0, 30], group the query sizes.  positions: pos(i) = #{j of the query: s_j > s_i, or s_j == s_i and j < i}.  For rows i, j of a query with\n"
+          "l_i > l_j: delta = fl32(s_i - s_j), rho = objective_gradient_host(-delta, 0, 'logistic'), eta = objective_hessian_host(delta, None, 'logistic');\n"
+          "omega = 1 ('pairwise') or (|gain_i - gain_j| * |disc[pos_i] - disc[pos_j]|) * inv with inv = 1 / maxDCG of the query ('lambdarank'; gain(l) =\n"
+          "2**l - 1, disc = rank_discounts(), entries at ndcg_at and beyond counted as 0); row i: g -= rho * omega, h += eta * omega; row j: g += rho * omega,\n"
+          "h += eta * omega, in float64 from +0.0 with the partners in ascending row order, rounded once to float32.  ndcg: DCG * inv per query (1 where\n"
+          "maxDCG is 0).  'loss' is 1 - mean(ndcg) for 'lambdarank'; the pairwise loss is a float64 libm expression computed on the device only.");
+    m.def("rank_discounts", &rank_discounts_impl,
+          "rank_discounts() -> float64 [1024]: disc[t] = 1 / log2(t + 2), the ONE table the host rule and the kernels of the ranking objectives read");
+    m.def("rank_geometry", &rank_geometry_impl, "rank_geometry() -> {'max_query': 1024, 'max_label': 30}: the largest query and relevance label of the ranking objectives");
     m.def("leaf_quantile_host", &leaf_quantile_host_impl, py::arg("x"), py::arg("leaves"), py::arg("n_leaves"), py::arg("alpha"),
           "leaf_quantile_host(x, leaves, n_leaves, alpha) -> {'values': float32 [n_leaves, D], 'counts': int64 [n_leaves], 'ranks': int64 [n_leaves, D]}\n\n"
           "The leaf rule of fit_prepared(leaf_update='quantile') and GBRL.quantile_leaves_prepared on the host (no device is needed): x float32 [m, D] are the\n"
@@ -1627,12 +1843,13 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         // likewise: fit_prepared(ds, targets, iterations) -> float keeps its generated line; the validation form is the second overload
         g.def("fit_prepared", [](PyGBRL &self, py::object ds, py::object &targets, int iterations) -> float {
             py::object none = py::none();
-            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0, none, none, none, none).cast<float>();
+            return fit_prepared_impl(self, ds, targets, iterations, none, none, 0, 0.0, 1.0, 1.0, 0, "rmse", none, "gradient", 1.0, none, none, none, none, none, none, none).cast<float>();
         }, py::arg("ds"), py::arg("targets"), py::arg("iterations"));
         const std::string sig = py::str(g.attr("fit_prepared").attr("__doc__"));
         const std::string doc = sig.substr(0, sig.find('\n')) + "\n\n"
             "fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,\n"
-            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None, goss=None, alpha=None)\n"
+            "             objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None, goss=None, alpha=None,\n"
+            "             group=None, ndcg_at=None, valid_group=None)\n"
             "             -> float | dict\n\n"
             "fit(obs, None, targets, iterations, shuffle=False) on the data set's rows with nothing recomputed: the running prediction is held and advanced by the\n"
             "new trees only, the batch is never binned again.  A fresh model ends up byte for byte as fit() leaves it, with the same loss.  A model with trees\n"
@@ -1711,14 +1928,30 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             "step_prepared -> quantile_leaves_prepared -> predict_continue_prepared.  Refused before anything changes: 'quantile' without alpha, alpha with\n"
             "another objective, a level outside (0, 1) or NaN (the output is named), a wrong length, leaf_update='quantile' with another objective,\n"
             "leaf_update='newton' with 'quantile' (its hessian is zero), eval_metric with it, a training target that is not finite; not supported:\n"
-            "weights= / valid_weights= with it, goss= with leaf_update='quantile' (both would need a weighted quantile).";
+            "weights= / valid_weights= with it, goss= with leaf_update='quantile' (both would need a weighted quantile).\n"
+            "objective='pairwise' | 'lambdarank', group=sizes (with valid=, colsample, early stopping, warm starts and leaf_update='newton'): learning to rank,\n"
+            "LightGBM's lambdarank with group=, XGBoost's rank:pairwise and rank:ndcg.  The model has output_dim == 1; targets are int32 relevance labels [n] in\n"
+            "[0, 30]; group holds the sizes of the queries' consecutive row runs, each in [1, 1024], summing to n; valid_group likewise for valid=.  The\n"
+            "gradient of a row is a sum over the other rows of its query (GBRL.rank_gradient has the rule): 'pairwise' weighs every pair with different labels\n"
+            "by 1 -- a query of two rows with labels (1, 0) is the Bradley-Terry preference step -log sigmoid(s_0 - s_1) -- 'lambdarank' by the NDCG change of\n"
+            "swapping the two rows; ndcg_at=K counts the discounts of positions K and beyond as 0 (lambdarank only).  Per iteration the held prediction is\n"
+            "advanced with no fused gradient, the rank kernels write g (and h), the tree is grown on g, 'newton' leaves store sum g / (sum h + leaf_l2) from\n"
+            "those buffers (bits = gbrl_cpp.newton_sum_bits(n, largest query)): the model is byte for byte the loop predict_continue_prepared -> rank_gradient\n"
+            "-> step_prepared -> newton_leaves_prepared(group=).  'loss' is rank_gradient's loss of every row, 'valid_loss'[k] that of the validation prediction\n"
+            "after k trees: 1 - mean NDCG (lambdarank) or the mean pair loss (pairwise), lower is better.  A fresh model's bias is 0.  Not LightGBM's: no\n"
+            "sigmoid parameter, no lambdarank_norm, no position bias, no label_gain.  Refused before anything changes: output_dim != 1, no group, group /\n"
+            "valid_group / ndcg_at with another objective, a size outside [1, 1024] (the query is named), sizes that do not sum to the rows, a label outside\n"
+            "[0, 30] (the row is named), batch_size < n (a batch must hold whole queries), subsample < 1, goss=, weights= / valid_weights=, alpha=, eval_metric=,\n"
+            "leaf_update='quantile', valid= without valid_group, ndcg_at < 0 or with 'pairwise', 'pairwise' on a training set without two different labels in any\n"
+            "query.";
         py::options opt;
         opt.disable_function_signatures();
         g.def("fit_prepared", &fit_prepared_impl, doc.c_str(), py::arg("ds"), py::arg("targets"), py::arg("iterations"), py::arg("valid") = py::none(),
               py::arg("valid_targets") = py::none(), py::arg("early_stopping_rounds") = 0, py::arg("min_delta") = 0.0, py::arg("subsample") = 1.0,
               py::arg("colsample") = 1.0, py::arg("seed") = 0, py::arg("objective") = "rmse", py::arg("eval_metric") = py::none(),
               py::arg("leaf_update") = "gradient", py::arg("leaf_l2") = 1.0, py::arg("weights") = py::none(), py::arg("valid_weights") = py::none(),
-              py::arg("goss") = py::none(), py::arg("alpha") = py::none());
+              py::arg("goss") = py::none(), py::arg("alpha") = py::none(), py::arg("group") = py::none(), py::arg("ndcg_at") = py::none(),
+              py::arg("valid_group") = py::none());
     }
     g.def("quantile_leaves_prepared", &quantile_leaves_prepared_impl, py::arg("ds"), py::arg("pred"), py::arg("targets"), py::arg("alpha"), py::arg("rows") = py::none(),
           py::arg("tree") = -1,
@@ -1732,8 +1965,11 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "the same bytes.  A leaf without rows or of depth 0 keeps its value.  Refused with the model unchanged: a bad level, a tree outside the model, a\n"
           "prediction, target or residual that is not finite.");
     g.def("newton_leaves_prepared", &newton_leaves_prepared_impl, py::arg("ds"), py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("leaf_l2") = 1.0,
-          py::arg("rows") = py::none(), py::arg("tree") = -1, py::arg("weights") = py::none(), py::arg("weight_max") = py::none(),
-          "newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1, weights=None, weight_max=None) -> dict\n\n"
+          py::arg("rows") = py::none(), py::arg("tree") = -1, py::arg("weights") = py::none(), py::arg("weight_max") = py::none(), py::arg("group") = py::none(),
+          py::arg("ndcg_at") = py::none(),
+          "newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1, weights=None, weight_max=None, group=None, ndcg_at=None) -> dict\n\n"
+          "objective 'pairwise' | 'lambdarank' with group= (and ndcg_at=): targets are the int32 relevance labels, g and h are rank_gradient's over every row\n"
+          "of the data set (no rows=, no weights=), summed from the buffers its kernels wrote with bits = newton_sum_bits(n, largest query).  Otherwise:\n"
           "The leaves of ONE tree (tree=-1: the last) set to sum g / (sum h + leaf_l2) over the data set rows `rows` (None: every row): what\n"
           "fit_prepared(leaf_update='newton') does after every step.  pred [m, output_dim] is the prediction over the trees before that tree and, like\n"
           "targets (float32 [m, output_dim]; int32 [m] labels for 'softmax'), is indexed by position.  Returns 'sums' (int64 [leaves, 2 D + 1]: Sg, Sh, cnt\n"
@@ -1751,8 +1987,8 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "same value, bit for bit.  pred [n, output_dim] and targets are NumPy arrays or device tuples.  'error' is one launch; 'auc' sorts the score\n"
           "columns with a segmented radix sort, prefix-counts the negatives and sums ranks with integer atomics: two calls give the same bytes.");
     g.def("objective_gradient", &objective_gradient_impl, py::arg("pred"), py::arg("targets"), py::arg("objective"), py::arg("weights") = py::none(),
-          py::arg("alpha") = py::none(),
-          "objective_gradient(pred, targets, objective, weights=None, alpha=None) -> (grad, loss)\n\n"
+          py::arg("alpha") = py::none(), py::arg("group") = py::none(), py::arg("ndcg_at") = py::none(),
+          "objective_gradient(pred, targets, objective, weights=None, alpha=None, group=None, ndcg_at=None) -> (grad, loss)\n\n"
           "The gradient dL/dp [n, output_dim] and the loss of the raw scores pred under objective 'rmse' | 'logistic' | 'softmax', computed on the model's\n"
           "device by the device functions fit_prepared(objective=) runs: grad is gbrl_cpp.objective_gradient_host(pred, targets, objective) bit for bit.\n"
           "targets: float32 [n, output_dim] (rmse, logistic) or int32 [n] labels (softmax).  NumPy in, NumPy out; a device tuple for pred gives a DLPack\n"
@@ -1761,7 +1997,24 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "sum w L / W with W the float64 sum of the weights in a fixed order (rmse: sqrt(0.5 sum w L / W)); the weight is one more float per row in the\n"
           "same launch.  Refused: a bad entry (the row is named), weights that sum to 0, a wrong length or dtype.\n"
           "'quantile' with alpha (a level in (0, 1) or one per output): the pinball step of gbrl_cpp.objective_gradient_host(..., alpha=) and the mean pinball\n"
-          "loss sum_d (u >= 0 ? alpha_d u : (alpha_d - 1) u), u = y - p in float64; no weights with it, alpha with no other objective.");
+          "loss sum_d (u >= 0 ? alpha_d u : (alpha_d - 1) u), u = y - p in float64; no weights with it, alpha with no other objective.\n"
+          "'pairwise' | 'lambdarank' with group= (and ndcg_at= for lambdarank): targets are the int32 relevance labels [n] and the call is\n"
+          "rank_gradient(pred, targets, group, objective, ndcg_at), of which it returns (grad, loss); group and ndcg_at go with no other objective.");
+    g.def("rank_gradient", &rank_gradient_impl, py::arg("pred"), py::arg("labels"), py::arg("group"), py::arg("objective") = "lambdarank", py::arg("ndcg_at") = py::none(),
+          "rank_gradient(pred, labels, group, objective='lambdarank', ndcg_at=None) -> {'grad', 'hess', 'loss', 'ndcg', 'positions', 'pairs'}\n\n"
+          "The ranking objectives 'pairwise' | 'lambdarank' on query groups, computed on the model's device (output_dim == 1): every figure but the loss is\n"
+          "gbrl_cpp.rank_gradient_host(pred, labels, group, objective, ndcg_at) bit for bit.  pred float32 [n] (or [n, 1]) are the scores, labels int32 [n] the\n"
+          "relevance grades in [0, 30], group the sizes of the queries' consecutive row runs (each in [1, 1024], summing to n; gbrl_cpp.rank_geometry()).\n"
+          "'grad' = dL/dp and 'hess' float32 shaped like pred, 'positions' int32 [n] the 0-based rank of a row inside its query (higher scores first, ties by\n"
+          "row order), 'ndcg' float64 [Q] per query, 'pairs' the number P of pairs with different labels inside a query, 'loss' a float: lambdarank\n"
+          "1 - mean(ndcg), pairwise the mean of log(1 + exp(-(s_i - s_j))) over the P pairs with l_i > l_j (0 when P == 0), reduced in a fixed order: two calls\n"
+          "give the same bits.  A pair with l_i > l_j adds rho = sigmoid(s_j - s_i) times omega to row j's gradient and takes it from row i's, and\n"
+          "sigmoid'(s_i - s_j) times omega to both hessians; omega is 1 (pairwise: two rows with labels (1, 0) are the Bradley-Terry step) or\n"
+          "|gain_i - gain_j| * |disc[pos_i] - disc[pos_j]| / maxDCG (lambdarank), gain(l) = 2**l - 1, disc = gbrl_cpp.rank_discounts(); ndcg_at=K counts the\n"
+          "discount of positions K and beyond as 0 (lambdarank only).  Every row sums its partners in float64, in row order, without atomics.  NumPy in,\n"
+          "NumPy out; a device tuple for pred gives DLPack capsules for grad, hess and positions.  Not LightGBM's lambdarank: no sigmoid parameter (it is\n"
+          "1), no lambdarank_norm, no position bias, no label_gain table.  Refused: a model with output_dim != 1, a size outside [1, 1024] (the query is\n"
+          "named), sizes that do not sum to n, a label outside [0, 30] (the row is named), ndcg_at < 0 or with 'pairwise', a score that is not finite.");
     g.def("predict", [](PyGBRL &self, py::object &obs, py::object &cat, py::object start, py::object stop, bool return_torch) {
         return predict_impl(self, obs, cat, start, stop, return_torch);
     }, py::arg("obs"), py::arg("categorical_obs"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("return_torch") = false);

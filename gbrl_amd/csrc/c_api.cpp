@@ -20,6 +20,7 @@
 #include "metric_core.h"
 #include "newton_core.h"
 #include "quantile_core.h"
+#include "rank_core.h"
 #include "hooks.h"
 #include "explain.h"
 #include "rccl_dyn.h"
@@ -572,13 +573,14 @@ static int fit_prepared_call(gbrl_hip_model *m, const gbrl_hip_dataset *ds, cons
                              const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds, double min_delta,
                              const gbrl::FitOptions &opt, float *loss_out, double *valid_loss_out, int *iterations_done, int *best_n_trees,
                              double *valid_metric_out = nullptr, const float *valid_weights = nullptr, int valid_weights_on_device = 0,
-                             float *weight_max_out = nullptr) {
+                             float *weight_max_out = nullptr, const int32_t *valid_group = nullptr, int valid_n_groups = 0) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");
         gbrl::Engine::FitValid v{nullptr, valid_targets, valid_targets_on_device != 0, early_stopping_rounds, min_delta, valid_loss_out, 0, 0, valid_metric_out,
-                                 valid_weights, valid_weights_on_device != 0};
+                                 valid_weights, valid_weights_on_device != 0, valid_group, valid_n_groups};
         gbrl::Engine::FitValid *valid = valid_required || valid_ds != nullptr ? &v : nullptr;
         m->engine.precheck_fit(targets, iterations, opt, valid);
+        if (!valid && (valid_group != nullptr || valid_n_groups != 0)) throw gbrl::InvalidArgument("fit_prepared: valid_group needs a validation set (valid=)");
         if (!valid && (valid_targets != nullptr || early_stopping_rounds != 0 || min_delta != 0.0 || valid_loss_out != nullptr || valid_metric_out != nullptr))
             throw gbrl::InvalidArgument("fit_prepared: valid_targets, early_stopping_rounds, min_delta and valid_loss_out need a validation set");
         if (!valid && valid_weights != nullptr) throw gbrl::InvalidArgument("fit_prepared: valid_weights need a validation set (valid=)");
@@ -771,7 +773,62 @@ int gbrl_hip_quantile_rank(int64_t m, float a, int64_t *rank_out) {
 
 void gbrl_hip_leaf_quantile_geometry(int *max_select_leaves, int *rows_per_chunk) { gbrl::kern::leaf_quantile_geometry(max_select_leaves, rows_per_chunk); }
 
-int gbrl_hip_objective_gradient_quantile(gbrl_hip_model *m, const float *pred, int pred_on_device, const void *targets, int targets_on_device, const float *alpha,
+// ---- ranking objectives: fit_prepared with query groups, one tree's Newton leaves, the gradient on the device and on the host, the table, the caps
+static_assert(gbrl::kern::kObjPairwise == GBRL_HIP_OBJ_PAIRWISE && gbrl::kern::kObjLambdarank == GBRL_HIP_OBJ_LAMBDARANK, "the kernels' ranking codes are the header's");
+int gbrl_hip_fit_prepared_rank(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                               const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds, double min_delta,
+                               double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update, double leaf_l2, const float *weights,
+                               int weights_on_device, const float *valid_weights, int valid_weights_on_device, double goss_top, double goss_other, const float *alpha,
+                               const int32_t *group, int n_groups, int ndcg_at, const int32_t *valid_group, int valid_n_groups, float *loss_out,
+                               double *valid_loss_out, double *valid_metric_out, int *iterations_done, int *best_n_trees, float *weight_max_out) {
+    return fit_prepared_call(m, ds, targets, targets_on_device, iterations, false, valid_ds, valid_targets, valid_targets_on_device, early_stopping_rounds, min_delta,
+                             {subsample, colsample, seed, objective, metric, leaf_update, leaf_l2, weights, weights_on_device != 0, goss_top, goss_other, alpha, group,
+                              n_groups, ndcg_at},
+                             loss_out, valid_loss_out, iterations_done, best_n_trees, valid_metric_out, valid_weights, valid_weights_on_device, weight_max_out, valid_group,
+                             valid_n_groups);
+}
+
+int gbrl_hip_newton_leaves_prepared_rank(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *pred, int pred_on_device, const int32_t *labels,
+                                         int labels_on_device, const int32_t *group, int n_groups, int objective, int ndcg_at, int tree, double leaf_l2,
+                                         int64_t *sums_out, int *bits_out, float *values_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("newton_leaves_prepared");
+        m->engine.newton_leaves_prepared_rank(&live_dataset(ds), pred, pred_on_device != 0, labels, labels_on_device != 0, group, n_groups, objective, ndcg_at, tree,
+                                              leaf_l2, sums_out, bits_out, values_out);
+    });
+}
+
+int gbrl_hip_rank_gradient(gbrl_hip_model *m, const float *pred, int pred_on_device, const int32_t *labels, int labels_on_device, const int32_t *group, int n_groups,
+                           int n, int objective, int ndcg_at, float *grad_out, float *hess_out, double *loss_out, double *ndcg_out, int32_t *positions_out,
+                           int64_t *pairs_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.rank_gradient(pred, pred_on_device != 0, labels, labels_on_device != 0, group, n_groups, n, objective, ndcg_at, grad_out, hess_out, loss_out,
+                                ndcg_out, positions_out, pairs_out);
+    });
+}
+
+int gbrl_hip_rank_gradient_host(const float *pred, const int32_t *labels, const int32_t *group, int n_groups, int n, int objective, int ndcg_at, float *grad_out,
+                                float *hess_out, double *loss_out, double *ndcg_out, int32_t *positions_out, int64_t *pairs_out) {
+    return guarded([&] {
+        gbrl::Engine::rank_gradient_host(pred, labels, group, n_groups, n, objective, ndcg_at, grad_out, hess_out, loss_out, ndcg_out, positions_out, pairs_out);
+    });
+}
+
+int gbrl_hip_rank_discounts(double *out) {
+    return guarded([&] {
+        if (out == nullptr) throw gbrl::InvalidArgument("rank_discounts: null argument");
+        std::memcpy(out, gbrl::Engine::rank_discounts(), sizeof(double) * gbrl::kern::kRankMaxQuery);
+    });
+}
+
+void gbrl_hip_rank_geometry(int *max_query, int *max_label) {
+    if (max_query) *max_query = gbrl::kern::kRankMaxQuery;
+    if (max_label) *max_label = gbrl::kern::kRankMaxLabel;
+}
+
+int gbrl_hip_objective_gradient_quantile(gbrl_hip_model *m,const float *pred, int pred_on_device, const void *targets, int targets_on_device, const float *alpha,
                                          int n, int objective, float *grad_out, double *loss_out) {
     return guarded([&] {
         if (!m) throw gbrl::InvalidArgument("null model");

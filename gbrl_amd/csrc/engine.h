@@ -134,6 +134,8 @@ struct FitOptions {
     const float *weights = nullptr /* float32 [n], one per data set row; nullptr: the loop without weights */; bool weights_dev = false;
     double goss_top = 0.0, goss_other = 0.0 /* 0: off; else sample_core.h's one-side sampling takes the place of the subsample draw */;
     const float *alpha = nullptr /* host float32 [D]: the levels of kern::kObjQuantile (quantile_core.h); required with it, refused without it */;
+    const int32_t *group = nullptr /* host int32 [n_groups]: the query sizes of a ranking objective (rank_core.h); required with one, refused without */;
+    int n_groups = 0; int ndcg_at = 0 /* kern::kObjLambdarank: discounts from this position on count as 0; 0: no truncation */;
 };
 
 class Engine {
@@ -234,6 +236,7 @@ class Engine {
         double *loss_out /*[iterations + 1]*/; int done, best_n_trees;
         double *metric_out = nullptr /*[iterations + 1]; with FitOptions::metric*/;
         const float *weights = nullptr /*float32 [ds->n]: loss_out is the weighted loss*/; bool weights_dev = false;
+        const int32_t *group = nullptr /*host int32 [n_groups]: the validation set's query sizes (a ranking objective)*/; int n_groups = 0;
     };
     float fit_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int iterations, const FitOptions &opt = {}, FitValid *valid = nullptr,
                        float *weight_max_out = nullptr);
@@ -279,6 +282,27 @@ class Engine {
     // alpha (host float32 [D]): the levels of kObjQuantile -- required with it, refused with another objective, as are weights with kObjQuantile.
     void objective_gradient(const float *pred, bool pred_dev, const void *targets, bool targets_dev, int n, int objective, float *grad_out, double *loss_out,
                             const float *weights = nullptr, bool weights_dev = false, const float *alpha = nullptr);
+    // Extension: ranking objectives on query groups (rank_core.h has the rule, include/gbrl_hip.h the contract; engine_rank.hip).  rank_gradient:
+    // scores pred float32 [n] of a model with output_dim 1, labels int32 [n], group HOST int32 [n_groups] -- the sizes of consecutive row runs --
+    // under kObjPairwise or kObjLambdarank, on the model's device and stream (kern::rank_queries, kern::rank_rows).  grad_out, hess_out float32 [n]
+    // and pos_out int32 [n] are where pred is (device iff pred_dev); ndcg_out float64 [n_groups] and pairs_out are host; every output may be null.
+    // Refused before a kernel runs (InvalidArgument): output_dim != 1, another objective, no group, a size outside [1, kRankMaxQuery] (the first such
+    // query is named), sizes that do not sum to n, ndcg_at < 0, ndcg_at > 0 with kObjPairwise; after the label pass: a label outside
+    // [0, kRankMaxLabel] (the first such row is named); after the launch: a score that is not finite.  rank_gradient_host: the rule without a
+    // device; no loss for kObjPairwise (a device-only float64 expression, as the logistic loss is), so loss_out is then refused.
+    static void check_rank_group(const char *what, const int32_t *group, int n_groups, int n /* < 0: not known yet, the sum is not checked */, int objective,
+                                 int ndcg_at, int D, const char *name = "group");
+    void rank_gradient(const float *pred, bool pred_dev, const int32_t *labels, bool labels_dev, const int32_t *group, int n_groups, int n, int objective,
+                       int ndcg_at, float *grad_out, float *hess_out, double *loss_out, double *ndcg_out, int32_t *pos_out, int64_t *pairs_out);
+    static void rank_gradient_host(const float *pred, const int32_t *labels, const int32_t *group, int n_groups, int n, int objective, int ndcg_at,
+                                   float *grad_out, float *hess_out, double *loss_out, double *ndcg_out, int32_t *pos_out, int64_t *pairs_out);
+    static const double *rank_discounts();   // the table of kRankMaxQuery discounts, built once
+    // newton_leaves_prepared for a ranking objective: g and h are rank_gradient's at pred [n] (labels int32 [n], group host) over EVERY row of the data
+    // set (a row list would cut queries apart), written to device buffers and summed per leaf by kern::newton_leaf_sums' buffer form (kObjGiven);
+    // bits = newton_sum_bits(n, (float)largest group), since |g| and h are below the query size.  Refusals: newton_leaves_prepared's about the model, the
+    // data set and the tree, rank_gradient's about the rest.
+    void newton_leaves_prepared_rank(const PreparedDataset *ds, const float *pred, bool pred_dev, const int32_t *labels, bool labels_dev, const int32_t *group,
+                                     int n_groups, int objective, int ndcg_at, int tree, double leaf_l2, int64_t *sums_out, int *bits_out, float *values_out);
     // Extension: quantile regression (quantile_core.h has the rule, include/gbrl_hip.h the contract).  check_alpha: alpha with another objective,
     // kObjQuantile without alpha, weights with kObjQuantile (Unsupported), a level that is not finite and strictly inside (0, 1) (the output is named).
     static void check_alpha(const char *what, int objective, const float *alpha, int D, bool weighted);
@@ -600,6 +624,18 @@ class Engine {
                              bool abs_index, const float *d_alpha, int t, bool generic, float *values_out, int64_t *counts_out, int64_t *ranks_out);
     DevBuf d_lq_res_, d_lq_scratch_, d_lq_alpha_;   // its result block (keys, ranks, counts, flag), its workspace, the levels
     std::vector<uint32_t> lq_host_;                 // ... the result block read back
+    // rank_gradient: staged scores, labels and offsets; the discount table; per row qid, pos, beats, ideal and DCG terms, gradient and hessian; per
+    // query maxDCG, 1 / maxDCG and NDCG; loss partials and sums; the three statistics words
+    DevBuf d_rk_pred_, d_rk_labels_, d_rk_off_, d_rk_disc_, d_rk_qid_, d_rk_pos_, d_rk_beats_, d_rk_ideal_, d_rk_term_, d_rk_grad_, d_rk_hess_, d_rk_maxdcg_,
+        d_rk_inv_, d_rk_ndcg_, d_rk_part_, d_rk_qpart_, d_rk_sums_, d_rk_stat_;
+    // a label vector with its query groups on the device (rank_prepare): 0 rank_gradient's, 1 fit_prepared's training set, 2 its validation set
+    struct RankSet { DevBuf off, qid, max_dcg, inv; int n = 0, Q = 0, max_group = 0; long long pairs = 0; };
+    RankSet rk_sets_[3];
+    DevBuf d_fp_hess_;   // fit_prepared with a ranking objective and newton leaves: the hessian beside d_fp_grads_
+    void rank_prepare(const char *what, RankSet &set, const int32_t *d_labels, const int32_t *group, int n_groups, int n, int ndcg_at);
+    void rank_eval(const RankSet &set, int objective, int ndcg_at, const float *d_scores, const int32_t *d_labels, int32_t *d_pos, float *dg, float *dh,
+                   bool want_loss, double *d_sum, double *host_sum, double *d_ndcg, bool timed = false /* a phase per kernel (set_profiling(2)) */);
+    static double rank_loss(const RankSet &set, int objective, double sum);
     DevBuf d_newton_acc_;                         // its int64 sums [leaves][2 D + 1] and the flag word
     std::vector<unsigned long long> newton_host_;   // ... read back
     // Column sums in float64 of device rows [rows][D] and the MultiRMSE built on them, as fit() and fit_prepared() compute the bias and the loss

@@ -15,6 +15,9 @@
 //                                      per iteration, which then decides the stopping rule and best_n_trees in place of the loss
 //                                      ; with goss the row draw is kern::goss_select + kern::goss_sample_passes (one-side sampling: the largest
 //                                      gradients and an amplified draw of the rest; tau stays on the device) in place of kern::sample_rows
+//                                      ; with a ranking objective (rank_core.h; engine_rank.hip) the walk runs without a gradient tail, the rank
+//                                      kernels write the gradient (and hessian) of every row from the rows of its query, newton leaves take their
+//                                      sums from those buffers, and both losses come from the same kernels
 //   Engine::newton_leaves_prepared     one tree's leaves set to sum g / (sum h + leaf_l2) over a data set's rows (newton_core.h; kern::newton_leaf_sums), the
 //                                      rules on the host beside it (objective_hessian_host, newton_values_host); fit_prepared(leaf_update = newton) runs its
 //                                      body after every step
@@ -35,6 +38,7 @@
 #include "metric_core.h"
 #include "newton_core.h"
 #include "quantile_core.h"
+#include "rank_core.h"
 #include "sample_core.h"
 
 namespace gbrl {
@@ -214,6 +218,9 @@ void Engine::predict_continue_prepared(const PreparedDataset *ds, const int32_t 
 
 // ---- objectives: the checks, the gradient rule on the host, the gradient and the loss of a prediction matrix on the device
 void Engine::check_objective(const char *what, int objective, int D) {
+    if (kern::rank_objective(objective))
+        throw InvalidArgument(std::string(what) + ": the ranking objectives (pairwise = 4, lambdarank = 5) sum over the rows of a query, which this call does not know: " +
+                              "rank_gradient takes them with group");
     if (objective != kern::kObjRmse && objective != kern::kObjLogistic && objective != kern::kObjSoftmax && objective != kern::kObjQuantile)
         throw InvalidArgument(std::string(what) + ": unknown objective " + std::to_string(objective) + " (rmse = 0, logistic = 1, softmax = 2, quantile = 3)");
     if (objective == kern::kObjSoftmax && D < 2)
@@ -428,7 +435,8 @@ void Engine::newton_leaves_run(const char *what, const PreparedDataset *ds, cons
     phase_begin();
     unsigned long long *dacc = static_cast<unsigned long long *>(d_newton_acc_.ensure(sizeof(unsigned long long) * words));
     hip_check(hipMemsetAsync(dacc, 0, sizeof(unsigned long long) * words, s), "zero leaf sums");
-    const int bits = d_weights ? kern::newton_sum_bits(m, weight_max) : kern::newton_sum_bits(m);
+    // (kObjGiven: a ranking objective's g and h from buffers, below the largest query's size, which arrives as weight_max)
+    const int bits = d_weights || objective == kern::kObjGiven ? kern::newton_sum_bits(m, weight_max) : kern::newton_sum_bits(m);
     const bool streamed = kern::newton_leaf_sums(mirror_view(), ct, cr, m, t, static_cast<int>(leaf0), static_cast<int>(NL), d_pred, d_targets, abs_index, objective,
                                                  bits, dacc, generic, s, d_weights);
     newton_host_.resize(words);
@@ -757,9 +765,29 @@ void Engine::precheck_fit(const void *targets, int iterations, const FitOptions 
         check_goss("fit_prepared", opt.goss_top, opt.goss_other);
         if (opt.subsample < 1.0) throw InvalidArgument("fit_prepared: goss and subsample < 1 are two draws of one iteration's rows: use one of them");
     }
-    check_objective("fit_prepared", opt.objective, md.output_dim);
-    check_leaf_update("fit_prepared", opt.objective, opt.leaf_update, opt.leaf_l2);
-    check_alpha("fit_prepared", opt.objective, opt.alpha, md.output_dim, opt.weights != nullptr || (valid != nullptr && valid->weights != nullptr));
+    const bool ranking = kern::rank_objective(opt.objective);
+    if (ranking) {   // the ranking objectives: their own list (rank_core.h; a gradient is a sum over the rows of a query)
+        check_rank_group("fit_prepared", opt.group, opt.n_groups, -1, opt.objective, opt.ndcg_at, md.output_dim);
+        if (opt.subsample < 1.0) throw InvalidArgument("fit_prepared: subsample < 1 with a ranking objective is not supported (a draw of rows cuts queries apart)");
+        if (opt.goss_other != 0.0) throw InvalidArgument("fit_prepared: goss with a ranking objective is not supported (a draw of rows cuts queries apart)");
+        if (opt.weights != nullptr || (valid != nullptr && valid->weights != nullptr))
+            throw InvalidArgument("fit_prepared: weights and valid_weights with a ranking objective are not supported");
+        if (opt.alpha != nullptr) throw InvalidArgument("fit_prepared: alpha is the level table of the quantile objective; a ranking objective takes none");
+        if (opt.metric != kern::kMetricNone) throw InvalidArgument("fit_prepared: eval_metric with a ranking objective is not supported (valid_loss is 1 - NDCG or the pairwise loss)");
+        if (opt.leaf_update == kern::kLeafQuantile) throw InvalidArgument("fit_prepared: quantile leaf values belong to the quantile objective");
+        check_leaf_update("fit_prepared", kern::kObjLogistic, opt.leaf_update, opt.leaf_l2);   // (an unknown rule, a bad leaf_l2)
+        if (valid != nullptr) {
+            if (valid->group == nullptr || valid->n_groups <= 0)
+                throw InvalidArgument("fit_prepared: a validation set of a ranking objective needs valid_group, the sizes of its queries");
+            check_rank_group("fit_prepared", valid->group, valid->n_groups, -1, opt.objective, opt.ndcg_at, md.output_dim, "valid_group");
+        }
+    } else {
+        if (opt.group != nullptr || opt.n_groups != 0 || opt.ndcg_at != 0 || (valid != nullptr && (valid->group != nullptr || valid->n_groups != 0)))
+            throw InvalidArgument("fit_prepared: group, valid_group and ndcg_at belong to the ranking objectives (pairwise, lambdarank)");
+        check_objective("fit_prepared", opt.objective, md.output_dim);
+        check_leaf_update("fit_prepared", opt.objective, opt.leaf_update, opt.leaf_l2);
+        check_alpha("fit_prepared", opt.objective, opt.alpha, md.output_dim, opt.weights != nullptr || (valid != nullptr && valid->weights != nullptr));
+    }
     if (opt.leaf_update == kern::kLeafQuantile && opt.goss_other != 0.0)
         throw Unsupported("fit_prepared: goss with quantile leaf values is not supported (the amplified rows would need a weighted quantile)");
     if (opt.metric != kern::kMetricNone) {
@@ -836,10 +864,13 @@ struct Engine::FitRun {
     float *Gs = nullptr;                                  // and their gradient rows
     float *d_sfactor = nullptr, *d_eff = nullptr;         // goss: the kept rows' factors; newton: their effective weights fl32(w * factor) by absolute row
     int start = 0, bn = 0;                               // the batch cursor
+    const bool ranking;                                  // a ranking objective: targets are int32 labels, the gradient comes from the rank kernels
+    float *H = nullptr;                                  // ... its hessian [n] beside G (newton leaves)
 
     FitRun(Engine &eng, const PreparedDataset *data, int iters, const FitOptions &o, FitValid *valid)
         : e(eng), ds(data), opt(o), v(valid), iterations(iters), n(data->n), D(eng.model.meta.output_dim), bs(eng.model.meta.batch_size), T0(eng.model.meta.n_trees),
-          W(static_cast<double>(data->n)), mC(kern::metric_count_columns(o.objective == kern::kObjSoftmax, eng.model.meta.output_dim)), goss(o.goss_other != 0.0) {
+          W(static_cast<double>(data->n)), mC(kern::metric_count_columns(o.objective == kern::kObjSoftmax, eng.model.meta.output_dim)), goss(o.goss_other != 0.0),
+          ranking(kern::rank_objective(o.objective)) {
         bn = start + bs < n ? bs : n - start;                                       // fitter.cpp:120
     }
 
@@ -853,6 +884,13 @@ struct Engine::FitRun {
         if (v) dvtar = stage(e.d_fp_vtargets_, v->targets, v->targets_dev, v->ds->n);
         if (v) Wv = static_cast<double>(v->ds->n);
         if (opt.alpha) d_alpha = e.upload(e.d_lq_alpha_, opt.alpha, static_cast<size_t>(D), "H2D levels");
+        if (ranking) {   // the labels of both sets checked, their queries on the device; all of it before anything changes
+            e.rank_prepare("fit_prepared", e.rk_sets_[1], reinterpret_cast<const int32_t *>(dtar), opt.group, opt.n_groups, n, opt.ndcg_at);
+            if (opt.objective == kern::kObjPairwise && e.rk_sets_[1].pairs == 0)
+                throw InvalidArgument("fit_prepared: no query of the training set holds two different labels: the pairwise objective has no pair to learn from");
+            if (v) e.rank_prepare("fit_prepared (valid_targets)", e.rk_sets_[2], reinterpret_cast<const int32_t *>(dvtar), v->group, v->n_groups, v->ds->n, opt.ndcg_at);
+            return;
+        }
         if (opt.weights) {
             dw = opt.weights_dev ? opt.weights : e.upload(e.d_fp_weights_, opt.weights, static_cast<size_t>(n), "H2D weights");
             const WeightStats st = e.check_weights("fit_prepared (weights)", dw, n, true);
@@ -911,7 +949,9 @@ struct Engine::FitRun {
     // With weights: sum w y / W per column and the weight W_c of a class, from column_sums' own reduction with the weight as a per-row factor.
     void set_bias(ColumnStats &stats) {
         Model &model = e.model;
-        if (opt.objective == kern::kObjQuantile) {   // quantile_core.h: one leaf of every row at p = 0 -- the k-th smallest target of the column, k from n
+        if (ranking) {   // both ranking losses are invariant to a shift of the scores
+            model.bias[0] = 0.0f;
+        } else if (opt.objective == kern::kObjQuantile) {   // quantile_core.h: one leaf of every row at p = 0 -- the k-th smallest target of the column, k from n
             hipStream_t s = e.stream_;
             const size_t words = kern::leaf_quantile_result_words(1, D);
             uint32_t *dres = static_cast<uint32_t *>(e.d_lq_res_.ensure(sizeof(uint32_t) * words));
@@ -953,6 +993,7 @@ struct Engine::FitRun {
         e.sync_model_to_device();
         train.start(ds, static_cast<float *>(e.d_fp_pred_.ensure(sizeof(float) * static_cast<size_t>(n) * D)), bs);
         G = static_cast<float *>(e.d_fp_grads_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+        if (ranking && opt.leaf_update == kern::kLeafNewton) H = static_cast<float *>(e.d_fp_hess_.ensure(sizeof(float) * static_cast<size_t>(n)));
         kern::tile_rows(e.m_bias_.as<float>(), D, n, train.P, s);
         if (bs < n) {
             std::vector<int32_t> iota(n);
@@ -975,19 +1016,34 @@ struct Engine::FitRun {
         h_mrow.assign(mC, 0);
         score.assign(static_cast<size_t>(iterations) + 1, 0.0);
     }
+    // a loss from the sum its kernels left: the mean row loss, or a ranking objective's rule (rank_core.h)
+    double loss_of(double sum, bool valid_set) const {
+        if (ranking) return rank_loss(e.rk_sets_[valid_set ? 2 : 1], opt.objective, sum);
+        return mean_loss(opt.objective, sum, valid_set ? Wv : W);
+    }
     // ---- the validation watch
     // loss_out[k] after k iterations: one launch + the finishing sum on the device, then the metric's integers of the same held prediction; with
     // a stopping rule both also on the host (one read-back: 8 bytes and the metric's counters, one wait)
     void evaluate(int k) {
         const int nv = v->ds->n;
         v->done = k;
-        e.advance_held(watched, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, opt.objective, dvw, d_alpha);
         double sum = 0.0;
+        if (ranking) {   // the walk without a tail, then the rule's loss of the held scores (rank_gradient's, bit for bit)
+            e.advance_held(watched, 0, nv, nullptr, nullptr, nullptr, nullptr, generic, kern::kObjRmse);
+            e.rank_eval(e.rk_sets_[2], opt.objective, opt.ndcg_at, watched.P, reinterpret_cast<const int32_t *>(dvtar), nullptr, nullptr, nullptr, true, d_vsums + k,
+                        v->rounds > 0 ? &sum : nullptr, nullptr);
+            if (v->rounds > 0) {
+                hip_check(hipStreamSynchronize(e.stream_), "sync");
+                v->loss_out[k] = loss_of(sum, true);
+            }
+            return;
+        }
+        e.advance_held(watched, 0, nv, nullptr, nullptr, dvtar, d_vpart, generic, opt.objective, dvw, d_alpha);
         e.finish_loss_sum(d_vpart, kern::staged_loss_partials(nv), d_vsums + k, v->rounds > 0 ? &sum : nullptr);
         if (opt.metric != kern::kMetricNone) measure(k);
         if (v->rounds > 0) {
             hip_check(hipStreamSynchronize(e.stream_), "sync");
-            v->loss_out[k] = mean_loss(opt.objective, sum, Wv);
+            v->loss_out[k] = loss_of(sum, true);
             if (opt.metric != kern::kMetricNone) record_metric(k, h_mrow.data());
         }
     }
@@ -1024,7 +1080,7 @@ struct Engine::FitRun {
             std::vector<double> sums(static_cast<size_t>(v->done) + 1);
             hip_check(hipMemcpyAsync(sums.data(), d_vsums, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, e.stream_), "D2H validation losses");
             hip_check(hipStreamSynchronize(e.stream_), "sync");
-            for (int k = 0; k <= v->done; ++k) v->loss_out[k] = mean_loss(opt.objective, sums[k], Wv);
+            for (int k = 0; k <= v->done; ++k) v->loss_out[k] = loss_of(sums[k], true);
             if (opt.metric != kern::kMetricNone) {   // and so did the metric's integers
                 std::vector<unsigned long long> rows((static_cast<size_t>(v->done) + 1) * mC);
                 hip_check(hipMemcpyAsync(rows.data(), d_vmetric, sizeof(unsigned long long) * rows.size(), hipMemcpyDeviceToHost, e.stream_), "D2H validation metric");
@@ -1057,8 +1113,18 @@ struct Engine::FitRun {
         const int trees = e.model.meta.n_trees;
         e.begin_step_profile();
         e.phase_begin();
-        e.advance_held(train, start, bn, dtar, G, nullptr, nullptr, generic, opt.objective, dw, d_alpha);
+        if (ranking) e.advance_held(train, start, bn, nullptr, nullptr, nullptr, nullptr, generic, kern::kObjRmse);   // (no fused gradient: predict_continue_prepared's launch)
+        else e.advance_held(train, start, bn, dtar, G, nullptr, nullptr, generic, opt.objective, dw, d_alpha);
         e.phase_end("continue_codes");
+        if (ranking) {   // the gradient (and hessian) of every row from the rows of its query; one batch holds them all
+            e.phase_begin();
+            e.rank_eval(e.rk_sets_[1], opt.objective, opt.ndcg_at, train.P, reinterpret_cast<const int32_t *>(dtar), nullptr, G, H, false, nullptr, nullptr, nullptr);
+            unsigned long long flag = 0;
+            hip_check(hipMemcpyAsync(&flag, e.d_rk_stat_.as<unsigned long long>(), sizeof(flag), hipMemcpyDeviceToHost, s), "D2H rank flags");
+            e.phase_end("rank_gradient");
+            hip_check(hipStreamSynchronize(s), "sync");
+            if (flag & kern::kRankBadPred) throw InvalidArgument("fit_prepared: a prediction is not finite: no ranking gradient; the model keeps the trees grown so far");
+        }
         const float *g = G;
         const int32_t *rows = bn == n ? nullptr : d_iota + start;
         int m = bn;
@@ -1089,7 +1155,10 @@ struct Engine::FitRun {
         } else {
             e.step_prepared_run(ds, g, rows, m);
         }
-        if (opt.leaf_update == kern::kLeafNewton) {   // the new tree's leaves from the rows it was grown on, at the held prediction over the trees before it
+        if (opt.leaf_update == kern::kLeafNewton && ranking) {   // the sums of the g and h the tree was grown on, from their buffers; room for the largest query
+            e.newton_leaves_run("fit_prepared", ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), nullptr, 0}, n, G, H, /*abs_index=*/true, kern::kObjGiven,
+                                e.model.meta.n_trees - 1, opt.leaf_l2, generic, nullptr, nullptr, nullptr, nullptr, static_cast<float>(e.rk_sets_[1].max_group));
+        } else if (opt.leaf_update == kern::kLeafNewton) {   // the new tree's leaves from the rows it was grown on, at the held prediction over the trees before it
             const bool kept = rows == d_srows && rows != nullptr;
             const bool amplified = kept && goss;   // the kept rows of a one-side draw carry fl32(w * factor), with room for fl32(wmax * amp)
             const float amp = amplified ? kern::goss_plan(bn, opt.goss_top, opt.goss_other).amp : 1.0f;
@@ -1112,7 +1181,16 @@ struct Engine::FitRun {
     float final_loss(ColumnStats &stats) {
         const bool rmse = opt.objective == kern::kObjRmse && dw == nullptr;
         for (int b0 = 0; b0 < n; b0 += bs)
-            e.advance_held(train, b0, std::min(bs, n - b0), rmse ? dtar : nullptr, rmse ? G + static_cast<size_t>(b0) * D : nullptr, nullptr, nullptr, generic, opt.objective, nullptr, d_alpha);
+            e.advance_held(train, b0, std::min(bs, n - b0), rmse ? dtar : nullptr, rmse ? G + static_cast<size_t>(b0) * D : nullptr, nullptr, nullptr, generic,
+                           ranking ? kern::kObjRmse : opt.objective, nullptr, d_alpha);
+        if (ranking) {   // the rule's loss of the held scores
+            double *d_sum = static_cast<double *>(e.d_obj_sum_.ensure(sizeof(double)));
+            double sum = 0.0;
+            e.rank_eval(e.rk_sets_[1], opt.objective, opt.ndcg_at, train.P, reinterpret_cast<const int32_t *>(dtar), nullptr, nullptr, nullptr, true, d_sum, &sum, nullptr);
+            hip_check(hipGetLastError(), "fit_prepared kernels");
+            hip_check(hipStreamSynchronize(e.stream_), "sync");
+            return static_cast<float>(loss_of(sum, false));
+        }
         if (rmse) {
             hip_check(hipGetLastError(), "fit_prepared kernels");
             return stats.rmse(G, n);
@@ -1140,6 +1218,13 @@ float Engine::fit_prepared(const PreparedDataset *ds, const void *targets, bool 
         if (opt.metric != kern::kMetricNone && valid->metric_out == nullptr) throw InvalidArgument("fit_prepared: no place for the validation metric");
         if (opt.metric == kern::kMetricAuc && !kern::metric_auc_fits(valid->ds->n, model.meta.output_dim))
             throw Unsupported("fit_prepared: auc needs validation rows * output_dim < 2^31 - 2048");
+    }
+    if (kern::rank_objective(opt.objective)) {   // what needs the row counts: whole queries in the one batch, sizes that cover the rows
+        check_rank_group("fit_prepared", opt.group, opt.n_groups, ds->n, opt.objective, opt.ndcg_at, model.meta.output_dim);
+        if (valid) check_rank_group("fit_prepared", valid->group, valid->n_groups, valid->ds->n, opt.objective, opt.ndcg_at, model.meta.output_dim, "valid_group");
+        if (model.meta.batch_size < ds->n)
+            throw InvalidArgument("fit_prepared: batch_size " + std::to_string(model.meta.batch_size) + " < " + std::to_string(ds->n) +
+                                  " rows: a batch of a ranking objective must hold whole queries (set batch_size >= the row count)");
     }
     const bool fresh = model.meta.n_trees == 0;
     if (!fresh) check_code_range(*ds, "fit_prepared", 0, model.meta.n_trees);   // a warm start continues from every tree the model has

@@ -670,6 +670,20 @@ void weight_stats(const float *weights, int n, int32_t *stat, double *part, doub
 // counts[D] = the smallest row index whose label is outside [0, D)
 void label_counts(const int32_t *labels, int n, int D, int32_t *counts, hipStream_t s);
 void tile_rows(const float *row /*[D], device*/, int D, int n, float *out /*[n][D]*/, hipStream_t s);   // out[r] = row: fit_prepared's held prediction starts as the bias
+// Ranking objectives (rank.hip; rank_core.h has the rule).  off: device int32 [Q + 1], the queries' first rows (off[0] = 0, off[Q] = n, every size in
+// [1, kRankMaxQuery]: the caller has checked); disc: device float64 [kRankMaxQuery], rank_discount_table's.  stat: device unsigned long long [3] =
+// {flag word, first row with a label outside [0, kRankMaxLabel], pair count P}, set to {0, ~0, 0} by the caller on `s`.
+// rank_queries (once per label vector): qid int32 [n] the row's query, max_dcg / inv float64 [Q], stat[1], stat[2]; ideal float64 [n] and beats int32
+// [n] are scratch.  rank_rows (per score vector; labels checked): pos int32 [n], term float64 [n] (scratch: the DCG terms), then -- each where its
+// output is not null -- g_out / h_out float32 [n], pair_part (kObjPairwise only: staged_loss_partials(n) doubles, the loss sums of the pairs each row
+// wins), ndcg float64 [Q] with ndcg_part (staged_loss_partials(Q) doubles); both partial vectors are finished by staged_loss_finish.  stat[0] collects
+// kRankBadPred.
+void rank_queries(const int32_t *labels, const int32_t *off, int n, int Q, const double *disc, int ndcg_at, int32_t *qid, double *ideal, int32_t *beats,
+                  double *max_dcg, double *inv, unsigned long long *stat, hipStream_t s);
+void rank_rows(int objective, const float *scores, const int32_t *labels, const int32_t *off, const int32_t *qid, const double *max_dcg, const double *inv, int n,
+               int Q, const double *disc, int ndcg_at, int32_t *pos, double *term, float *g_out, float *h_out, double *pair_part, double *ndcg, double *ndcg_part,
+               unsigned long long *stat, hipStream_t s, int stages = 7 /* kRankStage*: a caller that times the kernels one by one launches them one by one */);
+constexpr int kRankStagePositions = 1, kRankStagePairs = 2, kRankStageNdcg = 4;
 // Newton leaf sums (newton.hip; newton_core.h has the rule): the rows of cr routed through `tree` (leaves [leaf0, leaf0 + n_leaves)) by the code walk,
 // acc[l][2 D + 1] += (q(g)[D], q(h)[D], 1) with q(x) = llrint((double)x * 2^bits), g and h the objective's (kObjLogistic: targets float32 [.][D];
 // kObjSoftmax: int32 labels in [0, D), checked by the caller) at pred -- the prediction over the trees [0, tree).  pred and targets are indexed by

@@ -25,6 +25,8 @@
 //   WEIGHTED (a template flag of both sums kernels) with weights float32, indexed like pred: the row's weight is loaded with p[] and the targets,
 //   and g, h become fl32(w * g), fl32(w * h) in front of the quantisation (newton_core.h: the caller's bits make room for the largest weight).
 //   cnt counts rows as before.  Without the flag the pointer is never read.
+//   OBJ == kObjGiven (newton_core.h; the ranking objectives): pred and targets are two float32 buffers [.][D] that hold g and h themselves; both
+//   kernels load them as they load p and y and skip the objective's arithmetic and its checks.  Every other instantiation is what it was.
 //   The flag word behind the accumulators collects what the caller refuses: kNewtonBadTarget (a logistic target outside [0, 1]; a NaN counts),
 //   kNewtonBadPred (a prediction that is not finite).  The caller zeroes accumulators and flag and reads both back in one copy.
 #include "kernels.h"
@@ -108,12 +110,16 @@ __global__ __launch_bounds__(256) void k_newton_sums_general(LeavesModel cm, New
             const float q = obj_div(obj_exp_f32(pd == mx ? 0.0f : pd - mx), S);
             h = obj_softmax_hess_of(q);
             g = obj_softmax_grad_of(q, d == label);
+        } else if constexpr (OBJ == kObjGiven) {   // pred holds g, targets h
+            g = pd;
+            h = y[d];
         } else {
             const float yd = y[d];
             if (live && newton_bad_target(yd)) flag |= kNewtonBadTarget;
             obj_logistic_grad_hess(pd, yd, g, h);
         }
-        if (live && newton_bad_pred(pd)) flag |= kNewtonBadPred;
+        if constexpr (OBJ != kObjGiven)
+            if (live && newton_bad_pred(pd)) flag |= kNewtonBadPred;
         if constexpr (WEIGHTED) {
             g = obj_weighted(w, g);
             h = obj_weighted(w, h);
@@ -185,15 +191,19 @@ __global__ __launch_bounds__(kNewtonRows) void k_newton_sums(LeavesModel cm, New
             if (l < 0 || l >= nt.n_leaves) l = -1;
         }
         bool bad_p = false, bad_y = false;
+        if constexpr (OBJ != kObjGiven) {
 #pragma unroll
-        for (int j = 0; j < DMAX; ++j)
-            if (j < D) {
-                bad_p = bad_p || newton_bad_pred(g[j]);
-                if constexpr (OBJ != kObjSoftmax) bad_y = bad_y || newton_bad_target(h[j]);
-            }
+            for (int j = 0; j < DMAX; ++j)
+                if (j < D) {
+                    bad_p = bad_p || newton_bad_pred(g[j]);
+                    if constexpr (OBJ != kObjSoftmax) bad_y = bad_y || newton_bad_target(h[j]);
+                }
+        }
         if (live) flag |= (bad_p ? kNewtonBadPred : 0) | (bad_y ? kNewtonBadTarget : 0);
         if constexpr (OBJ == kObjSoftmax) {
             obj_softmax_grad_hess_regs<DMAX>(g, h, D, label);
+        } else if constexpr (OBJ == kObjGiven) {
+            // g[] and h[] are what the two loads brought
         } else {
 #pragma unroll
             for (int j = 0; j < DMAX; ++j)
@@ -293,6 +303,7 @@ bool newton_leaf_sums(const PredictModel &pm, const CodeTables &ct, const CodeRo
     const double scale = std::ldexp(1.0, bits);
     const float *y = static_cast<const float *>(targets);
     const int ai = abs_index ? 1 : 0;
+    if (objective == kObjGiven) return newton_sums_obj<kObjGiven, false>(pm, cm, nt, cr, m, pred, y, ai, scale, generic, nullptr, s);
     if (weights != nullptr)
         return objective == kObjSoftmax ? newton_sums_obj<kObjSoftmax, true>(pm, cm, nt, cr, m, pred, y, ai, scale, generic, weights, s)
                                         : newton_sums_obj<kObjLogistic, true>(pm, cm, nt, cr, m, pred, y, ai, scale, generic, weights, s);

@@ -24,6 +24,9 @@ namespace kern {
 
 constexpr int kLeafGradient = 0, kLeafNewton = 1;   // GBRL_HIP_LEAF_* (include/gbrl_hip.h)
 constexpr int kNewtonBadTarget = 1, kNewtonBadPred = 2;   // bits of the kernels' flag word
+// not an objective of the C ABI: the sums' kernels read g and h per row from two float32 buffers (in the places of pred and targets) that another
+// kernel wrote -- a ranking gradient is a sum over the row's query (rank_core.h) and cannot be computed from (p, y) inline
+constexpr int kObjGiven = -1;
 
 // logistic: gradient and hessian of one output from one exp (g has obj_logistic_grad's bits)
 GBRL_OBJ_HD inline void obj_logistic_grad_hess(float p, float y, float &g, float &h) {

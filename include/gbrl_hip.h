@@ -753,6 +753,75 @@ int gbrl_hip_objective_gradient_quantile(gbrl_hip_model *m, const float *pred, i
                                          const float *alpha /*host [output_dim]*/, int n, int objective, float *grad_out, double *loss_out);
 int gbrl_hip_objective_gradient_host_quantile(const float *pred, const void *targets, const float *alpha /*[D]*/, int n, int D, int objective,
                                               float *grad_out /*[n, D]*/);
+/* Ranking objectives on query groups (new: LightGBM's lambdarank with group=, XGBoost's rank:pairwise and rank:ndcg; a query of two rows with labels
+ * (1, 0) under the pairwise objective is the Bradley-Terry step -log sigmoid(s_0 - s_1) of reward modelling).  csrc/rank_core.h defines all of it once
+ * for the host and the kernels (csrc/rank.hip); a ranking gradient is a sum over the other rows of the row's query, so these objectives have calls of
+ * their own and every call without query groups refuses their codes.
+ *   inputs      scores float32 [n] of a model with output_dim == 1; labels int32 [n], every entry in [0, 30]; group int32 [Q] in host memory, the sizes
+ *               of consecutive row runs, each in [1, 1024] (gbrl_hip_rank_geometry), summing to n.
+ *   position    pos(i) = #{j in the query of i: s_j > s_i, or s_j == s_i and j < i}: 0-based, the float compare (-0 == +0).
+ *   discounts   disc[t] = 1 / log2(t + 2), t in [0, 1024), float64: ONE table built on the host (gbrl_hip_rank_discounts) that host rule and kernels both
+ *               read.  ndcg_at = K > 0: disc[t] counts as 0 for t >= K; 0: no truncation.  gain(l) = 2^l - 1, exact.
+ *   ideal DCG   the query's labels in descending order: maxDCG_q = sum_t gain(l_(t)) * disc[t], t ascending, every product and sum rounded on its own;
+ *               inv_q = maxDCG_q > 0 ? 1 / maxDCG_q : 0.
+ *   pairs       rows i, j of one query with l_i > l_j: delta = fl32(s_i - s_j), rho = sig(-delta), eta = fl32(sig(delta) * sig(-delta)): the logistic
+ *               gradient and hessian bits (gbrl_hip_objective_gradient_host at (-delta, 0), gbrl_hip_objective_hessian_host at delta).
+ *   weight      GBRL_HIP_OBJ_PAIRWISE: omega = 1.  GBRL_HIP_OBJ_LAMBDARANK: omega = (|gain(l_i) - gain(l_j)| * |disc[pos i] - disc[pos j]|) * inv_q, two
+ *               products in that order; a pair with omega == 0 (both rows beyond K) is skipped.
+ *   sums        lam = (double)rho * omega, kap = (double)eta * omega; row i (the better one): g -= lam, h += kap; row j: g += lam, h += kap.  Every row
+ *               keeps its own two float64 sums from +0.0, partners in ascending row order, each rounded once to float32 at the end.  No atomics: the
+ *               bits do not depend on the launch geometry.  g is dL/dp.
+ *   ndcg        DCG_q = sum over the query's rows, ascending, of gain(l) * disc[pos]; ndcg_q = maxDCG_q > 0 ? DCG_q * inv_q : 1: bit-exact between host
+ *               and device.
+ *   loss        lambdarank: 1 - (sum_q ndcg_q) / Q.  pairwise: the mean over the P label-ordered pairs of the logistic row loss at (p = delta, y = 1),
+ *               a device-only float64 expression like the logistic loss (0 when P == 0).  Both in the fixed reduction order of the other losses: two
+ *               calls give the same bits.
+ *   gbrl_hip_rank_gradient(m, pred, pred_on_device, labels, labels_on_device, group, n_groups, n, objective, ndcg_at, grad_out, hess_out, loss_out,
+ *     ndcg_out, positions_out, pairs_out)  on the model's device.  grad_out, hess_out [n] float32 and positions_out [n] int32 are where pred is;
+ *     ndcg_out float64 [n_groups], loss_out and pairs_out (P, an exact count) are host; each may be NULL.  Refused, GBRL_HIP_E_INVALID, before a kernel
+ *     runs: output_dim != 1, another objective, no group, a size outside [1, 1024] (the first such query is named), sizes that do not sum to n,
+ *     ndcg_at < 0, ndcg_at > 0 with pairwise; after the label pass: a label outside [0, 30] (the first such row is named); after the launch: a score
+ *     that is not finite.  The model is never changed.
+ *   gbrl_hip_rank_gradient_host(pred, labels, group, n_groups, n, objective, ndcg_at, ..)  the rule with no device: the same bytes; loss_out must be NULL
+ *     for pairwise.  gbrl_hip_rank_discounts(out [1024])  the table.  gbrl_hip_rank_geometry(max_query, max_label)  the caps.
+ *   Not LightGBM's lambdarank: no sigmoid parameter (it is 1), no lambdarank_norm, no position-bias terms, no label_gain table.
+ *   Out of scope: queries above 1024 rows, output_dim > 1, query or row weights, the ranking objectives inside gbrl_hip_fit_prepared* and
+ *     subsample, goss and weights with a ranking objective, ranking in fit(), step() and refit_leaves, MAP and XE-NDCG.
+ *   gbrl_hip_fit_prepared_rank(.., alpha, group, n_groups, ndcg_at, valid_group, valid_n_groups, loss_out, ..)  gbrl_hip_fit_prepared_quantile plus the query
+ *     sizes of the two sets; the older entries are this one with NULL and enqueue exactly what they did.  targets and valid_targets are the int32 labels.
+ *     Per iteration: the held prediction advanced with no fused gradient (gbrl_hip_predict_continue_prepared's launch), the rank kernels into the gradient
+ *     (and the hessian for GBRL_HIP_LEAF_NEWTON), the step, the Newton sums from those two buffers (bits = newton_sum_bits(n, largest query), since |g| and h
+ *     are below the query size), the validation loss by the same kernels.  A fresh model's bias is 0 (both losses are invariant to a shift).  The model is
+ *     byte for byte the loop predict_continue_prepared -> rank_gradient -> step_prepared -> newton_leaves_prepared_rank written by hand; loss_out is the
+ *     rule's loss of every row, valid_loss_out[k] gbrl_hip_rank_gradient's loss of the validation prediction after k trees (lower is better: the stopping
+ *     rule is unchanged).  Refused before anything changes, GBRL_HIP_E_INVALID: output_dim != 1, no group, group / valid_group / ndcg_at with another
+ *     objective, a size outside [1, 1024] (the query is named), sizes that do not sum to the rows, a label outside [0, 30] (the row is named),
+ *     batch_size < n (a batch must hold whole queries), subsample < 1, goss, weights or valid_weights, alpha, a metric, GBRL_HIP_LEAF_QUANTILE, a validation
+ *     set without valid_group, ndcg_at < 0 or with pairwise, pairwise on a training set without a pair (P == 0).  Found by the kernel during the
+ *     iterations: a prediction that is not finite (the model keeps the trees grown so far).
+ *   gbrl_hip_newton_leaves_prepared_rank(m, ds, pred, .., labels, .., group, n_groups, objective, ndcg_at, tree, leaf_l2, sums_out, bits_out, values_out)
+ *     gbrl_hip_newton_leaves_prepared for a ranking objective, over every row of the data set (a row list would cut queries apart). */
+enum { GBRL_HIP_OBJ_PAIRWISE = 4, GBRL_HIP_OBJ_LAMBDARANK = 5 };
+int gbrl_hip_rank_gradient(gbrl_hip_model *m, const float *pred, int pred_on_device, const int32_t *labels, int labels_on_device, const int32_t *group /*host*/,
+                           int n_groups, int n, int objective, int ndcg_at, float *grad_out /*[n]*/, float *hess_out /*[n]*/, double *loss_out,
+                           double *ndcg_out /*host [n_groups]*/, int32_t *positions_out /*[n]*/, int64_t *pairs_out);
+int gbrl_hip_rank_gradient_host(const float *pred, const int32_t *labels, const int32_t *group, int n_groups, int n, int objective, int ndcg_at,
+                                float *grad_out /*[n]*/, float *hess_out /*[n]*/, double *loss_out, double *ndcg_out /*[n_groups]*/,
+                                int32_t *positions_out /*[n]*/, int64_t *pairs_out);
+int gbrl_hip_rank_discounts(double *out /*[max_query]*/);
+int gbrl_hip_fit_prepared_rank(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int iterations,
+                               const gbrl_hip_dataset *valid_ds, const void *valid_targets, int valid_targets_on_device, int early_stopping_rounds,
+                               double min_delta, double subsample, double colsample, uint64_t seed, int objective, int metric, int leaf_update, double leaf_l2,
+                               const float *weights /*[n]*/, int weights_on_device, const float *valid_weights /*[valid rows]*/, int valid_weights_on_device,
+                               double goss_top, double goss_other, const float *alpha /*host [output_dim], may be NULL*/,
+                               const int32_t *group /*host [n_groups], may be NULL*/, int n_groups, int ndcg_at,
+                               const int32_t *valid_group /*host [valid_n_groups], may be NULL*/, int valid_n_groups, float *loss_out,
+                               double *valid_loss_out /*[iterations + 1]*/, double *valid_metric_out /*[iterations + 1]*/, int *iterations_done,
+                               int *best_n_trees, float *weight_max_out);
+int gbrl_hip_newton_leaves_prepared_rank(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *pred, int pred_on_device, const int32_t *labels,
+                                         int labels_on_device, const int32_t *group /*host*/, int n_groups, int objective, int ndcg_at, int tree, double leaf_l2,
+                                         int64_t *sums_out /*[leaves, 3]*/, int *bits_out, float *values_out /*[leaves, 1]*/);
+void gbrl_hip_rank_geometry(int *max_query, int *max_label);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
