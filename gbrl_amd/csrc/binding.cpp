@@ -604,6 +604,21 @@ Input read_rows(py::object &rows, const std::string &fn) {
     return r;
 }
 
+// A rows= argument as the C ABI takes it: the pointer (None: null, every row), where it lives, and m -- the vector's length, else the data set's
+// rows, else those of the call's first array.
+struct RowsArg {
+    const int32_t *ptr;
+    int on_device, m;
+};
+RowsArg read_rows_arg(py::object &rows, const std::string &fn, py::object &ds_obj, const Input &first) {
+    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
+    const Input r = read_rows(rows, fn);
+    int m = first.shape.empty() ? 0 : static_cast<int>(first.shape[0]);
+    if (!rows.is_none()) m = static_cast<int>(r.shape[0]);
+    else if (!ds_obj.is_none()) m = ds_obj.cast<const PyDataset &>().info().n_rows;
+    return {rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows), r.ptr ? r.on_device : 0, m};
+}
+
 // cols=: a one-dimensional vector of column indices in host memory (a NumPy integer array or a sequence of ints); the C ABI checks its contents
 std::vector<int32_t> read_cols(py::object &cols, const std::string &fn) {
     py::array any = py::array::ensure(cols);
@@ -669,25 +684,20 @@ void step_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &grads, py::
         ss << "Gradient output dim " << gdim << " != correct output dim " << md.output_dim;
         fail(ss.str());
     }
-    Input r = read_rows(rows, "step_prepared");
-    if (!rows.is_none()) {
-        const int m = static_cast<int>(r.shape[0]);
-        if (m != n) {
-            std::stringstream ss;
-            ss << "Number of rows " << m << " != number of gradient samples " << n;
-            fail(ss.str());
-        }
+    const RowsArg r = read_rows_arg(rows, "step_prepared", ds_obj, g);
+    if (!rows.is_none() && r.m != n) {
+        std::stringstream ss;
+        ss << "Number of rows " << r.m << " != number of gradient samples " << n;
+        fail(ss.str());
     }
-    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
-    const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
     std::vector<int32_t> cv;
     if (!cols.is_none()) cv = read_cols(cols, "step_prepared");
     static const int32_t kNoCols = 0;   // an empty cols vector is "no column", not "every column"
     int rc;
     {
         py::gil_scoped_release release;
-        if (cols.is_none()) rc = gbrl_hip_step_prepared(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, rp, r.ptr ? r.on_device : 0, n);
-        else rc = gbrl_hip_step_prepared_cols(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, rp, r.ptr ? r.on_device : 0, n,
+        if (cols.is_none()) rc = gbrl_hip_step_prepared(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, r.ptr, r.on_device, n);
+        else rc = gbrl_hip_step_prepared_cols(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, r.ptr, r.on_device, n,
                                               cv.empty() ? &kNoCols : cv.data(), static_cast<int>(cv.size()));
     }
     check(rc);
@@ -880,20 +890,15 @@ py::object predict_continue_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
     const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
     Input b = read_input(base, "base", false, "predict_continue_prepared", false);
     if (!b.ptr) fail("Cannot call predict_continue_prepared without base!");
-    Input r = read_rows(rows, "predict_continue_prepared");
-    const int D = md.output_dim;
-    int m = b.shape.empty() ? 0 : static_cast<int>(b.shape[0]);
-    if (!rows.is_none()) m = static_cast<int>(r.shape[0]);
-    else if (ds) m = ds_obj.cast<const PyDataset &>().info().n_rows;
+    const RowsArg r = read_rows_arg(rows, "predict_continue_prepared", ds_obj, b);
+    const int D = md.output_dim, m = r.m;
     check_rows_by_outputs(b, "base", m, D);
-    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
-    const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
     const bool in_place = py::isinstance<py::tuple>(base);
     float *out = in_place ? static_cast<float *>(const_cast<void *>(b.ptr)) : new float[std::max<size_t>(static_cast<size_t>(m) * D, 1)];
     int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_predict_continue_prepared(self.h, ds, rp, r.ptr ? r.on_device : 0, m, static_cast<const float *>(b.ptr), b.on_device, start, stop, out);
+        rc = gbrl_hip_predict_continue_prepared(self.h, ds, r.ptr, r.on_device, m, static_cast<const float *>(b.ptr), b.on_device, start, stop, out);
     }
     if (rc != GBRL_HIP_OK) {
         if (!in_place) delete[] out;
@@ -991,11 +996,12 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     if (valid_obj.is_none() && !valid_weights.is_none()) fail("fit_prepared: valid_weights need a validation set (valid=)");
     if (valid_obj.is_none() && !valid_group_obj.is_none()) fail("fit_prepared: valid_group needs a validation set (valid=)");
     const gbrl_hip_dataset *dsv = valid_obj.is_none() ? nullptr : valid_obj.cast<const PyDataset &>().h;
-    Input w = read_weights(weights, "weights", "fit_prepared", ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, ds != nullptr), wv;
-    if (dsv) wv = read_weights(valid_weights, "valid_weights", "fit_prepared", valid_obj.cast<const PyDataset &>().info().n_rows, true);
-    Input t = read_objective_targets(targets, "targets", false, "fit", objective, ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, md.output_dim, ds != nullptr);
+    const int n = ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, nv = dsv ? valid_obj.cast<const PyDataset &>().info().n_rows : 0;
+    Input w = read_weights(weights, "weights", "fit_prepared", n, ds != nullptr), wv;
+    if (dsv) wv = read_weights(valid_weights, "valid_weights", "fit_prepared", nv, true);
+    Input t = read_objective_targets(targets, "targets", false, "fit", objective, n, md.output_dim, ds != nullptr);
     Input tv;
-    if (dsv) tv = read_objective_targets(valid_targets, "valid_targets", true, "fit", objective, valid_obj.cast<const PyDataset &>().info().n_rows, md.output_dim, true);
+    if (dsv) tv = read_objective_targets(valid_targets, "valid_targets", true, "fit", objective, nv, md.output_dim, true);
     std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0), mcurve(metric != GBRL_HIP_METRIC_NONE ? curve.size() : 0, 0.0);
     float loss = 0.0f, weight_max = 0.0f;
     int rc, done = 0, best = 0;
@@ -1027,6 +1033,41 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     return std::move(out);
 }
 
+// the leaves of a tree (-1: the last).  An index outside the model is left to the C ABI's message: one leaf's room is enough for a call that is refused
+py::ssize_t tree_leaf_count(PyGBRL &self, const gbrl_hip_metadata &md, int tree) {
+    const py::ssize_t T = md.n_trees;
+    if (tree < -1 || tree >= T || T == 0) return 1;
+    std::vector<int32_t> ti(static_cast<size_t>(T));
+    const py::ssize_t tt = tree == -1 ? T - 1 : tree;
+    check(gbrl_hip_get_ensemble(self.h, ti.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+    return (tt + 1 < T ? ti[tt + 1] : md.n_leaves) - ti[tt];
+}
+
+// the results of the leaves calls: room for `leaves` leaves of D outputs, call(...) -> the C ABI's status, the dict
+template <typename Call>
+py::dict newton_leaves_result(py::ssize_t leaves, py::ssize_t D, Call &&call) {
+    py::array_t<int64_t> sums({leaves, 2 * D + 1});
+    py::array_t<float> values({leaves, D});
+    int bits = 0;
+    check(call(sums.mutable_data(), &bits, values.mutable_data()));
+    py::dict out;
+    out["sums"] = sums;
+    out["bits"] = py::int_(bits);
+    out["values"] = values;
+    return out;
+}
+template <typename Call>
+py::dict leaf_quantile_result(py::ssize_t leaves, py::ssize_t D, Call &&call) {
+    py::array_t<float> values({leaves, D});
+    py::array_t<int64_t> counts(std::vector<py::ssize_t>{leaves}), ranks({leaves, D});
+    check(call(values.mutable_data(), counts.mutable_data(), ranks.mutable_data()));
+    py::dict out;
+    out["values"] = values;
+    out["counts"] = counts;
+    out["ranks"] = ranks;
+    return out;
+}
+
 // Extension: Newton leaf values (include/gbrl_hip.h, "Newton leaf values").
 // newton_leaves_prepared(ds, pred, targets, objective, leaf_l2=1.0, rows=None, tree=-1, weights=None, weight_max=None) -> {'sums': int64 [leaves, 2 D + 1], 'bits', 'values': float32 [leaves, D]}
 py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &pred, py::object &targets, const std::string &objective_name, double leaf_l2,
@@ -1048,37 +1089,16 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
         check_rows_by_outputs(p, "pred", n, 1);
         Input l = read_objective_targets(targets, "targets", false, fn, objective, n, 1, true);
         if (!l.ptr) fail("Cannot call newton_leaves_prepared without targets!");
-        const py::ssize_t T = md.n_trees;
-        py::ssize_t leaves = 1;
-        if (tree >= -1 && tree < T && T > 0) {
-            std::vector<int32_t> ti(static_cast<size_t>(T));
-            const py::ssize_t tt = tree == -1 ? T - 1 : tree;
-            check(gbrl_hip_get_ensemble(self.h, ti.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-            leaves = (tt + 1 < T ? ti[tt + 1] : md.n_leaves) - ti[tt];
-        }
-        py::array_t<int64_t> sums({leaves, static_cast<py::ssize_t>(3)});
-        py::array_t<float> values({leaves, static_cast<py::ssize_t>(1)});
-        int bits = 0, rc;
-        int64_t *sp = sums.mutable_data();
-        float *vp = values.mutable_data();
-        {
+        return newton_leaves_result(tree_leaf_count(self, md, tree), 1, [&](int64_t *sp, int *bits, float *vp) {
             py::gil_scoped_release release;
-            rc = gbrl_hip_newton_leaves_prepared_rank(self.h, ds, static_cast<const float *>(p.ptr), p.on_device, static_cast<const int32_t *>(l.ptr), l.on_device,
-                                                      grp.data(), static_cast<int>(grp.size()), objective, ndcg_at, tree, leaf_l2, sp, &bits, vp);
-        }
-        check(rc);
-        py::dict out;
-        out["sums"] = sums;
-        out["bits"] = py::int_(bits);
-        out["values"] = values;
-        return out;
+            return gbrl_hip_newton_leaves_prepared_rank(self.h, ds, static_cast<const float *>(p.ptr), p.on_device, static_cast<const int32_t *>(l.ptr), l.on_device,
+                                                        grp.data(), static_cast<int>(grp.size()), objective, ndcg_at, tree, leaf_l2, sp, bits, vp);
+        });
     }
     Input p = read_input(pred, "pred", false, "newton_leaves_prepared", false);
     if (!p.ptr) fail("Cannot call newton_leaves_prepared without pred!");
-    Input r = read_rows(rows, "newton_leaves_prepared");
-    int m = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
-    if (!rows.is_none()) m = static_cast<int>(r.shape[0]);
-    else if (ds) m = ds_obj.cast<const PyDataset &>().info().n_rows;
+    const RowsArg r = read_rows_arg(rows, "newton_leaves_prepared", ds_obj, p);
+    const int m = r.m;
     check_rows_by_outputs(p, "pred", m, D);
     Input t = read_objective_targets(targets, "targets", false, "newton_leaves_prepared", objective, m, D, true);
     if (!t.ptr) fail("Cannot call newton_leaves_prepared without targets!");
@@ -1086,33 +1106,11 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
     if (!w.ptr && !weight_max_obj.is_none()) fail("newton_leaves_prepared: weight_max needs weights");
     const float weight_max = weight_max_obj.is_none() ? -1.0f : weight_max_obj.cast<float>();
     if (!weight_max_obj.is_none() && !(weight_max >= 0.0f)) fail("newton_leaves_prepared: weight_max must be in [0, 65536] (and not NaN)");
-    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
-    const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
-    // the leaves of the tree (an index outside the model is left to the C ABI's message: one leaf's room is enough for a call that is refused)
-    const py::ssize_t T = md.n_trees;
-    py::ssize_t leaves = 1;
-    if (tree >= -1 && tree < T && T > 0) {
-        std::vector<int32_t> ti(static_cast<size_t>(T));
-        const py::ssize_t tt = tree == -1 ? T - 1 : tree;
-        check(gbrl_hip_get_ensemble(self.h, ti.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-        leaves = (tt + 1 < T ? ti[tt + 1] : md.n_leaves) - ti[tt];
-    }
-    py::array_t<int64_t> sums({leaves, static_cast<py::ssize_t>(2 * D + 1)});
-    py::array_t<float> values({leaves, static_cast<py::ssize_t>(D)});
-    int bits = 0, rc;
-    int64_t *sp = sums.mutable_data();
-    float *vp = values.mutable_data();
-    {
+    return newton_leaves_result(tree_leaf_count(self, md, tree), D, [&](int64_t *sp, int *bits, float *vp) {
         py::gil_scoped_release release;
-        rc = gbrl_hip_newton_leaves_prepared_weighted(self.h, ds, rp, r.ptr ? r.on_device : 0, m, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device,
-                                                      objective, tree, leaf_l2, static_cast<const float *>(w.ptr), w.on_device, weight_max, sp, &bits, vp);
-    }
-    check(rc);
-    py::dict out;
-    out["sums"] = sums;
-    out["bits"] = py::int_(bits);
-    out["values"] = values;
-    return out;
+        return gbrl_hip_newton_leaves_prepared_weighted(self.h, ds, r.ptr, r.on_device, m, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device,
+                                                        objective, tree, leaf_l2, static_cast<const float *>(w.ptr), w.on_device, weight_max, sp, bits, vp);
+    });
 }
 
 // Extension: quantile regression (include/gbrl_hip.h, "Quantile regression").
@@ -1124,40 +1122,16 @@ py::dict quantile_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::obje
     const std::vector<float> alpha = read_alpha(alpha_obj, D, "quantile_leaves_prepared");
     Input p = read_input(pred, "pred", false, "quantile_leaves_prepared", false);
     if (!p.ptr) fail("Cannot call quantile_leaves_prepared without pred!");
-    Input r = read_rows(rows, "quantile_leaves_prepared");
-    int m = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
-    if (!rows.is_none()) m = static_cast<int>(r.shape[0]);
-    else if (ds) m = ds_obj.cast<const PyDataset &>().info().n_rows;
+    const RowsArg r = read_rows_arg(rows, "quantile_leaves_prepared", ds_obj, p);
+    const int m = r.m;
     check_rows_by_outputs(p, "pred", m, D);
     Input t = read_objective_targets(targets, "targets", false, "quantile_leaves_prepared", GBRL_HIP_OBJ_QUANTILE, m, D, true);
     if (!t.ptr) fail("Cannot call quantile_leaves_prepared without targets!");
-    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
-    const int32_t *rp = rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows);
-    // the leaves of the tree (an index outside the model is left to the C ABI's message: one leaf's room is enough for a call that is refused)
-    const py::ssize_t T = md.n_trees;
-    py::ssize_t leaves = 1;
-    if (tree >= -1 && tree < T && T > 0) {
-        std::vector<int32_t> ti(static_cast<size_t>(T));
-        const py::ssize_t tt = tree == -1 ? T - 1 : tree;
-        check(gbrl_hip_get_ensemble(self.h, ti.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
-        leaves = (tt + 1 < T ? ti[tt + 1] : md.n_leaves) - ti[tt];
-    }
-    py::array_t<float> values({leaves, static_cast<py::ssize_t>(D)});
-    py::array_t<int64_t> counts(std::vector<py::ssize_t>{leaves}), ranks({leaves, static_cast<py::ssize_t>(D)});
-    float *vp = values.mutable_data();
-    int64_t *cp = counts.mutable_data(), *kp = ranks.mutable_data();
-    int rc;
-    {
+    return leaf_quantile_result(tree_leaf_count(self, md, tree), D, [&](float *vp, int64_t *cp, int64_t *kp) {
         py::gil_scoped_release release;
-        rc = gbrl_hip_quantile_leaves_prepared(self.h, ds, rp, r.ptr ? r.on_device : 0, m, static_cast<const float *>(p.ptr), p.on_device,
-                                               static_cast<const float *>(t.ptr), t.on_device, alpha.empty() ? nullptr : alpha.data(), tree, vp, cp, kp);
-    }
-    check(rc);
-    py::dict out;
-    out["values"] = values;
-    out["counts"] = counts;
-    out["ranks"] = ranks;
-    return out;
+        return gbrl_hip_quantile_leaves_prepared(self.h, ds, r.ptr, r.on_device, m, static_cast<const float *>(p.ptr), p.on_device,
+                                                 static_cast<const float *>(t.ptr), t.on_device, alpha.empty() ? nullptr : alpha.data(), tree, vp, cp, kp);
+    });
 }
 
 // the rule on the host: x float32 [m, D] (or [m]), leaves int32 [m] -> {'values', 'counts', 'ranks'}
@@ -1166,15 +1140,9 @@ py::dict leaf_quantile_host_impl(py::array_t<float, py::array::c_style | py::arr
     if (x.ndim() < 1 || x.ndim() > 2 || leaves.ndim() != 1 || leaves.shape(0) != x.shape(0)) fail("leaf_quantile_host: x float32 [m, D] (or [m]), leaves int32 [m]");
     const py::ssize_t m = x.shape(0), D = x.ndim() == 2 ? x.shape(1) : 1, L = std::max(n_leaves, 1);
     const std::vector<float> alpha = read_alpha(alpha_obj, static_cast<int>(D), "leaf_quantile_host");
-    py::array_t<float> values({L, D});
-    py::array_t<int64_t> counts(std::vector<py::ssize_t>{L}), ranks({L, D});
-    check(gbrl_hip_leaf_quantile_host(x.data(), leaves.data(), static_cast<int>(m), static_cast<int>(D), n_leaves, alpha.empty() ? nullptr : alpha.data(),
-                                      values.mutable_data(), counts.mutable_data(), ranks.mutable_data()));
-    py::dict out;
-    out["values"] = values;
-    out["counts"] = counts;
-    out["ranks"] = ranks;
-    return out;
+    return leaf_quantile_result(L, D, [&](float *vp, int64_t *cp, int64_t *kp) {
+        return gbrl_hip_leaf_quantile_host(x.data(), leaves.data(), static_cast<int>(m), static_cast<int>(D), n_leaves, alpha.empty() ? nullptr : alpha.data(), vp, cp, kp);
+    });
 }
 
 // the hessian rule on the host: no device, no model (the targets do not enter: accepted and ignored, so that the call reads like the gradient's)

@@ -172,7 +172,7 @@ class Engine {
     void step_prepared(const PreparedDataset *ds, const float *grads, bool grads_dev, const int32_t *rows, bool rows_dev, int m, const int32_t *cols = nullptr,
                        int n_cols = 0);
     static void check_cols(const char *what, const int32_t *cols, int n_cols, int F);   // the rule above (cols non-null)
-    // Extension (engine_fit_prepared.hip): the walk over a data set's bin codes.  code(r, f) = #{b : thr[f][b] < obs[r, f]}, so a numeric condition
+    // Extension (engine_codes.hip): the walk over a data set's bin codes.  code(r, f) = #{b : thr[f][b] < obs[r, f]}, so a numeric condition
     // x[f] > v whose v is one of thr[f][*] is code > bin with bin = #{b : thr[f][b] < v} (include/gbrl_hip.h has the argument).
     // condition_bins: host only.  out has the length and indexing of feature_values; a used numeric slot (d < depths[split row]) gets its bin,
     // every other slot -1.  thresholds [F][B]; F / B that are not the model's: InvalidArgument; a used numeric condition whose value is not
@@ -297,7 +297,7 @@ class Engine {
     static void rank_gradient_host(const float *pred, const int32_t *labels, const int32_t *group, int n_groups, int n, int objective, int ndcg_at,
                                    float *grad_out, float *hess_out, double *loss_out, double *ndcg_out, int32_t *pos_out, int64_t *pairs_out);
     static const double *rank_discounts();   // the table of kRankMaxQuery discounts, built once
-    // newton_leaves_prepared for a ranking objective: g and h are rank_gradient's at pred [n] (labels int32 [n], group host) over EVERY row of the data
+    // newton_leaves_prepared for a ranking objective (engine_leaves.hip): g and h are rank_gradient's at pred [n] (labels int32 [n], group host) over EVERY row of the data
     // set (a row list would cut queries apart), written to device buffers and summed per leaf by kern::newton_leaf_sums' buffer form (kObjGiven);
     // bits = newton_sum_bits(n, (float)largest group), since |g| and h are below the query size.  Refusals: newton_leaves_prepared's about the model, the
     // data set and the tree, rank_gradient's about the rest.
@@ -514,7 +514,7 @@ class Engine {
     // step_prepared behind its argument checks and input staging: statistics, growth, append on device gradients and (nullable) device rows
     void step_prepared_run(const PreparedDataset *ds, const float *dgrads, const int32_t *d_rows, int m, const int32_t *cols = nullptr, int n_cols = 0);
     void begin_step_profile();   // a step's phase list starts here
-    // ---- conditions as bin indices of ONE threshold table (engine_fit_prepared.hip): host tables appended split row by split row, their device
+    // ---- conditions as bin indices of ONE threshold table (engine_codes.hip): host tables appended split row by split row, their device
     // copies appended behind sync_model_to_device().  Keyed on the data set's thresholds_id: data sets that share thresholds share the tables
     // (a fit that alternates between a training and a validation set appends the new trees' rows only).  Dropped when a data set with other
     // thresholds is named or the ensemble has shrunk.
@@ -603,6 +603,25 @@ class Engine {
     DevBuf d_met_counts_, d_met_scratch_, d_fp_vmetric_;   // eval_metric: the integer counters, the AUC pipeline's scratch; fit_prepared: the metric's counters per iteration
     struct Held;     // engine_fit_prepared.hip: a data set's rows carried through the model's trees, batch by batch
     struct FitRun;   // engine_fit_prepared.hip: the state of one fit_prepared call and the stages that work on it
+    // ---- what the calls on a data set share (engine_codes.hip)
+    void reset_events() { ev_used_ = 0; ev_names_.clear(); phases_.clear(); }   // a public call starts with an empty event pool and phase list
+    template <typename T>
+    const T *staged(DevBuf &buf, const T *x, bool on_dev, size_t count, const char *what) {   // an array that may already be on the device
+        return on_dev ? x : upload(buf, x, count, what);
+    }
+    template <typename T>
+    T *zeroed(DevBuf &buf, size_t count, const char *what) {   // count words of a grow-only device buffer, zeroed on the stream
+        T *d = static_cast<T *>(buf.ensure(sizeof(T) * count));
+        hip_check(hipMemsetAsync(d, 0, sizeof(T) * count, stream_), what);
+        return d;
+    }
+    // a few words back from the device, and the wait for them; phase: a phase that ends behind the copy and before the wait
+    void read_back(void *host, const void *dev, size_t bytes, const char *what, const char *phase = nullptr);
+    // the rows of a data set a call works on (null: all of them), on the device and known to lie in [0, ds->n) (checked_rows)
+    const int32_t *subset_rows(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m);
+    int resolve_tree(const char *what, int tree) const;   // a leaves call's tree (-1: the last), refused when the model has none or not that one
+    // the phase that has just ended joins the list the caller's phases are in (a step's list has been resolved already), with a marker that is not a time
+    void join_tail_phase(const char *name, const char *marker, bool value);
     // class counts of device labels [n] (counts, when given: [D]); a label outside [0, D) is InvalidArgument naming the first such row
     void check_labels(const char *what, const int32_t *d_labels, int n, int D, std::vector<int32_t> *counts);
     // rows [start, start + bn) of a held prediction (one batch of it, or a part of one) advanced to every tree the model has, with the gradient

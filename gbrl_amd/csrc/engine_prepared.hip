@@ -132,6 +132,11 @@ const int32_t *checked_rows(DevBuf &copy, DevBuf &mm_buf, const int32_t *rows, b
         throw InvalidArgument("rows: index " + std::to_string(lo < 0 ? lo : hi) + " is outside [0, " + std::to_string(n) + ")");
     return rows;
 }
+void check_row_count(const char *what, const char *noun, const int32_t *rows, int m, int n, const char *verb) {
+    if (m <= 0) throw InvalidArgument(std::string(what) + ": no rows (m must be positive)");
+    if (rows == nullptr && m != n)
+        throw InvalidArgument(std::string(what) + ": " + noun + " has " + std::to_string(m) + " rows, the data set " + std::to_string(n) + " (pass rows to " + verb + " a subset)");
+}
 void check_host_rows(const int32_t *rows, int m, int n) {
     for (int j = 0; j < m; ++j)
         if (rows[j] < 0 || rows[j] >= n)
@@ -180,9 +185,7 @@ void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool g
     gbrl_hip_metadata &md = model.meta;
     check_prepared_dataset("step_prepared", ds);
     if (grads == nullptr) throw InvalidArgument("Cannot call step without grads!");
-    if (m <= 0) throw InvalidArgument("step_prepared: no rows (m must be positive)");
-    if (rows == nullptr && m != ds->n)
-        throw InvalidArgument("step_prepared: grads has " + std::to_string(m) + " rows, the data set " + std::to_string(ds->n) + " (pass rows to step on a subset)");
+    check_row_count("step_prepared", "grads", rows, m, ds->n, "step on");
     if (md.max_depth > kern::kMaxPath) throw Unsupported("max_depth > 32 is not supported");
     if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
     if (md.output_dim > 512) throw Unsupported("output_dim > 512");
@@ -202,7 +205,7 @@ void Engine::step_prepared(const PreparedDataset *ds, const float *grads, bool g
         dgrads = static_cast<float *>(d_grads_.ensure(sizeof(float) * N * D));
         hip_check(hipMemcpyAsync(const_cast<float *>(dgrads), grads, sizeof(float) * N * D, hipMemcpyHostToDevice, s), "H2D grads");
     }
-    const int32_t *d_rows = rows ? checked_rows(d_sub_rows_, d_rows_mm_, rows, rows_dev, m, ds->n, s) : nullptr;
+    const int32_t *d_rows = subset_rows(ds, rows, rows_dev, m);
     phase_end("inputs");
     step_prepared_run(ds, dgrads, d_rows, m, cols, n_cols);
 }

@@ -1,8 +1,6 @@
 // engine_rank.hip -- the ranking objectives on query groups (see engine.h; rank_core.h has the rule, rank.hip the kernels):
 //   Engine::check_rank_group     what is refused about the objective, the model's width, the group sizes and ndcg_at before anything runs
 //   Engine::rank_gradient_host   the rule on the host, query by query: the reference the kernels are held to, byte for byte
-//   Engine::newton_leaves_prepared_rank  one tree's Newton leaves from a ranking objective's g and h: rank_gradient's kernels into two device buffers,
-//                                then newton_leaves_prepared's body on them (kern::newton_leaf_sums' buffer form, kObjGiven)
 //   Engine::rank_gradient        the same on the model's device: the label pass once (kern::rank_queries), then positions, pairs and NDCG
 //                                (kern::rank_rows); two waits -- one after the label pass, whose refusal names a row, one for the results
 #include "engine.h"
@@ -133,12 +131,10 @@ void Engine::rank_prepare(const char *what, RankSet &set, const int32_t *d_label
     double *inv = static_cast<double *>(set.inv.ensure(sizeof(double) * Q));
     kern::rank_queries(d_labels, doff, n, Q, ddisc, ndcg_at, qid, ideal, beats, max_dcg, inv, dstat, s);
     hip_check(hipGetLastError(), "rank label pass");
-    hip_check(hipMemcpyAsync(stat, dstat, sizeof(stat), hipMemcpyDeviceToHost, s), "D2H rank statistics");
-    hip_check(hipStreamSynchronize(s), "sync");   // (off goes out of scope)
+    read_back(stat, dstat, sizeof(stat), "D2H rank statistics");   // (the wait: off goes out of scope)
     if (stat[1] != ~0ull) {
         int32_t bad = 0;
-        hip_check(hipMemcpyAsync(&bad, d_labels + stat[1], sizeof(bad), hipMemcpyDeviceToHost, s), "D2H label");
-        hip_check(hipStreamSynchronize(s), "sync");
+        read_back(&bad, d_labels + stat[1], sizeof(bad), "D2H label");
         throw InvalidArgument(bad_label_message(what, bad, static_cast<long long>(stat[1])));
     }
     set.pairs = static_cast<long long>(stat[2]);
@@ -187,8 +183,8 @@ void Engine::rank_gradient(const float *pred, bool pred_dev, const int32_t *labe
     ensure_device();
     hipStream_t s = stream_;
     const int Q = n_groups;
-    const float *dp = pred_dev ? pred : upload(d_rk_pred_, pred, static_cast<size_t>(n), "H2D scores");
-    const int32_t *dl = labels_dev ? labels : upload(d_rk_labels_, labels, static_cast<size_t>(n), "H2D labels");
+    const float *dp = staged(d_rk_pred_, pred, pred_dev, static_cast<size_t>(n), "H2D scores");
+    const int32_t *dl = staged(d_rk_labels_, labels, labels_dev, static_cast<size_t>(n), "H2D labels");
     RankSet &set = rk_sets_[0];
     const bool timed = profiling_ >= 2;
     ev_used_ = 0;
@@ -215,41 +211,6 @@ void Engine::rank_gradient(const float *pred, bool pred_dev, const int32_t *labe
     if (flag & kern::kRankBadPred) throw InvalidArgument(std::string(what) + kBadScore);
     if (pairs_out) *pairs_out = set.pairs;
     if (loss_out) *loss_out = rank_loss(set, objective, sum);
-}
-
-void Engine::newton_leaves_prepared_rank(const PreparedDataset *ds, const float *pred, bool pred_dev, const int32_t *labels, bool labels_dev, const int32_t *group,
-                                         int n_groups, int objective, int ndcg_at, int tree, double leaf_l2, int64_t *sums_out, int *bits_out, float *values_out) {
-    const char *what = "newton_leaves_prepared";
-    const gbrl_hip_metadata &md = model.meta;
-    const int T = md.n_trees;
-    check_prepared_dataset(what, ds);
-    if (pred == nullptr) throw InvalidArgument("newton_leaves_prepared: no prediction");
-    if (labels == nullptr) throw InvalidArgument("Cannot call newton_leaves_prepared without targets!");
-    const int n = ds->n;
-    check_rank_group(what, group, n_groups, n, objective, ndcg_at, md.output_dim);
-    check_leaf_update(what, kern::kObjLogistic, kern::kLeafNewton, leaf_l2);   // (a bad leaf_l2)
-    if (T == 0) throw InvalidArgument("newton_leaves_prepared: the model has no trees");
-    if (tree < -1 || tree >= T) throw InvalidArgument("newton_leaves_prepared: tree " + std::to_string(tree) + " is outside the model's " + std::to_string(T) + " trees (-1: the last)");
-    const int t = tree == -1 ? T - 1 : tree;
-    check_code_range(*ds, what, t, t + 1);
-    ensure_device();
-    ev_used_ = 0;
-    ev_names_.clear();
-    phases_.clear();
-    hipStream_t s = stream_;
-    const float *dp = pred_dev ? pred : upload(d_rk_pred_, pred, static_cast<size_t>(n), "H2D scores");
-    const int32_t *dl = labels_dev ? labels : upload(d_rk_labels_, labels, static_cast<size_t>(n), "H2D labels");
-    RankSet &set = rk_sets_[0];
-    rank_prepare(what, set, dl, group, n_groups, n, ndcg_at);
-    float *dg = static_cast<float *>(d_rk_grad_.ensure(sizeof(float) * n)), *dh = static_cast<float *>(d_rk_hess_.ensure(sizeof(float) * n));
-    rank_eval(set, objective, ndcg_at, dp, dl, nullptr, dg, dh, false, nullptr, nullptr, nullptr);
-    hip_check(hipGetLastError(), "newton_leaves_prepared rank kernels");
-    unsigned long long flag = 0;
-    hip_check(hipMemcpyAsync(&flag, d_rk_stat_.as<unsigned long long>(), sizeof(flag), hipMemcpyDeviceToHost, s), "D2H rank flags");
-    hip_check(hipStreamSynchronize(s), "sync");
-    if (flag & kern::kRankBadPred) throw InvalidArgument("newton_leaves_prepared: a prediction is not finite: no newton leaf values; the model is unchanged");
-    newton_leaves_run(what, ds, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), nullptr, 0}, n, dg, dh, /*abs_index=*/false, kern::kObjGiven, t, leaf_l2,
-                      hooks::on(hooks::CONTINUE_GENERIC), sums_out, bits_out, values_out, nullptr, static_cast<float>(set.max_group));
 }
 
 }  // namespace gbrl

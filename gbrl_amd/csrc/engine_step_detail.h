@@ -5,7 +5,10 @@
 //   engine_step.hip        Engine::step / Engine::fit, the host scan of categorical cells, the tree joining the ensemble (A1, A2, A10-A11), and
 //                          the stages step() shares with step_prepared(): run_grad_stats, prepare_numeric, grow_step_tree
 //   engine_prepared.hip    Engine::prepare_dataset / Engine::step_prepared: a batch binned once and stepped on many times
-//   engine_fit_prepared.hip  Engine::predict_continue_prepared / Engine::fit_prepared: the walk over a data set's bin codes, fit()'s loop on it
+//   engine_codes.hip       Engine::condition_bins / predict_continue_prepared: a data set's bin codes in the model's terms, the walk over them
+//   engine_objective.hip   Engine::objective_gradient[_host] / eval_metric[_host]: an objective's checks, gradient, loss and metric of a prediction matrix
+//   engine_leaves.hip      Engine::newton_leaves_prepared[_rank] / quantile_leaves_prepared: one tree's leaf values from a data set's rows
+//   engine_fit_prepared.hip  Engine::fit_prepared: fit()'s loop on a data set, in stages over one FitRun (engine_codes_detail.h: what these four share)
 #pragma once
 #include "engine.h"
 #include "hooks.h"
@@ -187,9 +190,10 @@ void append_tree(Model &model, const std::vector<HNode> &nodes, const std::vecto
                  double leaf_scale, const std::vector<CatCandidate> &cat_cands);
 // Row subsets of a prepared data set (engine_prepared.hip).  checked_rows: device copy of an index vector, every entry known to lie in [0, n)
 // BEFORE anything reads through it: a host vector is checked on the host (check_host_rows, before the device is touched), a device vector by
-// kern::rows_minmax, read back.
+// kern::rows_minmax, read back.  check_row_count: m rows of `noun` against the data set's n before either ("... (pass rows to `verb` a subset)").
 const int32_t *checked_rows(DevBuf &copy, DevBuf &mm_buf, const int32_t *rows, bool rows_dev, int m, int n, hipStream_t s);
 void check_host_rows(const int32_t *rows, int m, int n);
+void check_row_count(const char *what, const char *noun, const int32_t *rows, int m, int n, const char *verb);
 
 }  // namespace detail
 
@@ -201,5 +205,6 @@ using detail::categorical_candidates;
 using detail::append_tree;
 using detail::checked_rows;
 using detail::check_host_rows;
+using detail::check_row_count;
 
 }  // namespace gbrl

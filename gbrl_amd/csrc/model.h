@@ -55,6 +55,10 @@ struct Model {
 
     bool oblivious() const { return meta.grow_policy == GBRL_HIP_GROW_OBLIVIOUS; }
     size_t split_rows() const { return oblivious() ? meta.n_trees : meta.n_leaves; }
+    // the leaves of tree t: the first one's row of `values`, their count, the depth of leaf l of the tree
+    size_t first_leaf(int t) const { return static_cast<size_t>(tree_indices[t]); }
+    size_t leaf_count(int t) const { return static_cast<size_t>(t + 1 < meta.n_trees ? tree_indices[t + 1] : meta.n_leaves) - first_leaf(t); }
+    int leaf_depth(int t, size_t l) const { return oblivious() ? depths[t] : depths[first_leaf(t) + l]; }
 
     // reserve room for one more tree with `n_leaves_new` leaves; maintains the reference's capacity book-keeping
     void begin_tree();

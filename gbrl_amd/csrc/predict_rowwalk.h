@@ -3,7 +3,7 @@
 // every piece of that exists once, here:
 //   model views    LeavesModel (routing: leaves_model) and ChainModel (routing + values, rates, bias: chain_model); the rate rule is chain_rates
 //   row accessors  how a walk reads a numeric condition of its row: floats against the threshold (GeneralRow, a float tile row) or a prepared
-//                  data set's bin codes against the condition's bin (GeneralCodeRow, StreamCodeRow; x > v <=> code > bin, engine_fit_prepared.hip).
+//                  data set's bin codes against the condition's bin (GeneralCodeRow, StreamCodeRow; x > v <=> code > bin, engine_codes.hip).
 //                  Every walk below takes the row as a template parameter; the staging of a code tile is stream_stage_code_tile / _groups
 //   general side   one thread per row, rows in global memory, anything the file format can hold: general_test, general_leaf (the reference's
 //                  walk; greedy: leaf by leaf, Q7), general_apply (every optimizer that owns the output, in order) and general_chain_tree
