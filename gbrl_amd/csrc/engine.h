@@ -1,5 +1,5 @@
 // engine.h -- device engine: owns the host model, its device mirror, the per-step workspace and the HIP stream, and
-// drives the kernels of kernels.hip for GBRL::step / GBRL::predict.
+// drives the kernels of the step_*.hip units for GBRL::step / GBRL::predict.
 #pragma once
 
 #include <hip/hip_runtime.h>

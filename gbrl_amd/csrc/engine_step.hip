@@ -489,7 +489,7 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
     double *d_stat = static_cast<double *>(d_stat_.ensure(sizeof(double) * 4 * D));
     if (D > 512) throw Unsupported("output_dim > 512");
     // LDS accumulators are int32 and one block adds at most `chunk_rows` rows into a cell: the power-of-two scale keeps
-    // chunk_rows * max|q| < 2^31 (exactness of the wrapped int32 sums, kernels.hip k_hist_build).  Leaf sums: int64 fixed point with
+    // chunk_rows * max|q| < 2^31 (exactness of the wrapped int32 sums, step_hist_build.hip k_hist_build).  Leaf sums: int64 fixed point with
     // n_global * max|g| * 2^lbits < 2^62.
     kern::StepScales *d_scales = static_cast<kern::StepScales *>(d_scales_.ensure(sizeof(kern::StepScales)));
     int32_t *d_qg = static_cast<int32_t *>(d_qg_.ensure(sizeof(int32_t) * static_cast<size_t>(N) * D));

@@ -106,7 +106,7 @@ void qsel_update(uint32_t *prefix, uint32_t *trial, const int64_t *counts, const
 void sub_arrays(const float *a, const float *b, float *out, size_t n, hipStream_t s);
 void gather_rows(const float *src, const int32_t *perm, float *dst, int n, int width, hipStream_t s);
 void f64_to_f32(const double *in, float *out, int n, hipStream_t s);
-// row-sharded statistics: [D sums | P x D maxima, one row per rank] summed over ranks = sums + gathered maxima (kernels.hip)
+// row-sharded statistics: [D sums | P x D maxima, one row per rank] summed over ranks = sums + gathered maxima (step_stats.hip)
 // (+ one trailing word, `extra`, summed like the rest: this rank's row count in the first round)
 void stats_pack(const double *st, int D, int P, int rank, double *msg, hipStream_t s, double extra = 0.0);
 void stats_unpack(const double *msg, int D, int P, double *st, hipStream_t s);

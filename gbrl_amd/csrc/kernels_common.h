@@ -1,4 +1,4 @@
-// kernels_common.h -- device helpers shared by the kernel translation units (kernels.hip, predict.hip, categorical.hip).
+// kernels_common.h -- device helpers shared by the kernel translation units (the step_*.hip units, predict.hip, categorical.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

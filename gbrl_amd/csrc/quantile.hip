@@ -12,7 +12,7 @@
 //   5. k_extract          second sweep: keys of listed classes are appended to their lists (~6 % of the data)
 //   6. k_select           one wave per target: exact order statistic inside its (small) list by 32-step bisection
 // Everything is exact; the sample only balances the classes.  If a list would overflow its budget the engine falls back
-// to the 32-pass bisection of kernels.hip (same results, slower).
+// to the 32-pass bisection of step_binning.hip (same results, slower).
 #include "kernels.h"
 #include "hooks.h"
 #include "kernels_common.h"

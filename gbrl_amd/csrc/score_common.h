@@ -1,4 +1,4 @@
-// score_common.h -- split-score arithmetic shared by k_score (kernels.hip) and the one-launch RL-sized growth kernel (small_grow.hip):
+// score_common.h -- split-score arithmetic shared by k_score (step_score.hip) and the one-launch RL-sized growth kernel (small_grow.hip):
 // both evaluate a candidate from exact integer sums with the SAME fp64 expression, so a step grows the same bytes whichever path it takes.
 #pragma once
 

@@ -1,4 +1,4 @@
-// small_prep.h -- device bodies of the RL-sized preparation kernels, shared by their stand-alone launches (k_small_stats in kernels.hip,
+// small_prep.h -- device bodies of the RL-sized preparation kernels, shared by their stand-alone launches (k_small_stats in step_stats.hip,
 // k_sort_quantiles in quantile.hip) and by the fused preparation kernel (k_small_prep, small_prep.hip: statistics, quantisation, split
 // candidates and class codes of a step of a few thousand rows in ONE launch).  One body, so that a step computes the same bits whichever
 // launch runs it.

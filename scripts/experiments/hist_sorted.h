@@ -1,6 +1,6 @@
 // hist_sorted.h -- split-score histogram build WITHOUT one LDS atomic per (row, feature, output).
 //
-// k_hist_build (kernels.hip) spends D + 1 = 9 `ds_add_u32` per (row, feature): the LDS write path moves 64 B/clk/CU, one
+// k_hist_build (step_hist_build.hip) spends D + 1 = 9 `ds_add_u32` per (row, feature): the LDS write path moves 64 B/clk/CU, one
 // wave-instruction per ~4.5 clk, which caps it at 0.50 ms per depth-6 tree at config 2.  This kernel replaces
 // the scatter by a gather: per sub-chunk of kSortRows rows of the block's chunk and per feature of the block's group,
 //   1. a counting sort of the rows by class in LDS: ONE returning `ds_add_rtn_u32` per (row, feature) on the class counter

@@ -7,7 +7,7 @@
 //   5 ROW-MAJOR layout (round 6): [row][128] uint16 -- a gathered row's eight 32-byte records are the two 128-byte lines of that row, shared by the
 //     eight group blocks of a chunk through their XCD's L2, instead of one line per group with three other rows' records in it -- timing only
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -I gbrl_amd/csrc [-DVARIANT=n] scripts/hist_bench.hip gbrl_amd/csrc/hooks.cpp -o scripts/bin/hist_bench
-#include "../gbrl_amd/csrc/kernels.hip"
+#include "../gbrl_amd/csrc/step_hist_build.hip"
 #ifndef VARIANT
 #define VARIANT 0
 #endif

@@ -443,7 +443,7 @@ def test_full_size_properties_config3_shape():
 @pytest.mark.parametrize("N", [70001, 70000, 3001, 262148])   # 70000: n % 4 == 0 and n >= 65536 -> the transpose counts the first radix digit (k_transpose_count); 262148: a partial last strip inside one wave of the radix passes
 def test_fast_quantile_path_equals_bisection_path(N, monkeypatch):
     """The exact selections -- LDS sort of the whole column (small batches), MSD radix multi-select (radix_select.hip),
-    sample-splitter selection (quantile.hip) and 32-pass bisection (kernels.hip) -- give identical trees, also on columns built
+    sample-splitter selection (quantile.hip) and 32-pass bisection (step_binning.hip) -- give identical trees, also on columns built
     to stress each of them."""
     import gbrl_amd
     rng = np.random.default_rng(11)
