@@ -16,13 +16,12 @@
 
 #include "kernels.h"
 #include "model.h"
+#include "cat_candidates_host.h"   // HipError, Unsupported; detail::CatCandidate, CatMemory
 
 namespace gbrl {
 
-struct HipError : std::runtime_error { using std::runtime_error::runtime_error; };
 struct NoDeviceError : std::runtime_error { using std::runtime_error::runtime_error; };
 struct InvalidArgument : std::runtime_error { using std::runtime_error::runtime_error; };
-struct Unsupported : std::runtime_error { using std::runtime_error::runtime_error; };
 
 void hip_check(hipError_t e, const char *what);
 
@@ -115,16 +114,23 @@ struct LevelWork;
 struct Level;
 class TreeBuilder;
 class Stager;
-// a categorical split candidate: class `cls` of feature `feat` is the category `name` (the raw 128-byte cell, types.h:55-58)
-struct CatCandidate {
-    int feat;
-    std::array<char, 128> name;
-    int cls;
-    CatCandidate(int f, const char *cell, int c) : feat(f), cls(c) { std::memcpy(name.data(), cell, 128); }
+struct ThrArgs; struct StepInputs; struct CatStage; struct CatList; enum class ThrRoute;   // engine_step_detail.h
+// The device scan for a step's distinct categorical cells (engine_cat_candidates.hip): its buffers, what the next step starts from, the
+// round that is on the stream, and the form its result takes for the class-code kernels.
+struct CatScan {
+    DevBuf keys, first, meta, lslot, slotq, clsq;   // per-feature tables (hash | first row), flags + counter, the list's table slots, slot -> record, record -> class
+    DevBuf rank, rank_cnt, rank_tot, sdict, xchg;   // kern::cat_rank: scratch, count and total per distinct cell; the step's dictionary; scratch of the row-sharded exchanges
+    PinnedBuf pin, pin_cls, pin_dict;               // the published block; the class of every record; the dictionary as the host packs it
+    std::vector<char> host;                         // the published block, copied out of the pinned mapping
+    uint32_t pub_seq = 0;                           // sequence word of k_cat_publish's completion flag
+    int log2_hint = 20, publish_guess = 256;        // the next step starts with: log2 of the per-feature table size (20: the full size); records published with the header (the last count + 25 %)
+    bool launched = false;                          // a first round is on the stream, not yet collected
+    int log2_cap = 0, full_log2 = 0, list_cap = 0, pub_cap = 0;   // that round: table size, the worst case's, capacity of the list and of the publish
+    // ordinary steps on one GPU: the class codes come from the scan's own tables (k_cat_step_codes_table) instead of a dictionary
+    struct { bool valid = false; const uint64_t *keys = nullptr; const int32_t *slot_q = nullptr, *cls_of_q = nullptr; int log2_cap = 0; } table;
+    // the step's candidate dictionary inside sdict (one upload): per categorical feature the entries sorted by raw hash
+    struct { const int32_t *off = nullptr, *cls = nullptr; const uint64_t *hash = nullptr, *words = nullptr; } dict;
 };
-// A distinct (categorical feature, cell) pair the engine has met in some step: the hash of its key in the reference's candidate
-// container (std::hash of cell + "_" + feature, split_candidate_generator.cpp:121) is computed once.
-struct CatItem { int feat; int next; uint64_t lhash; size_t std_hash; char name[128]; };
 }  // namespace detail
 
 // The options of Engine::fit_prepared; the defaults are the plain MultiRMSE loop on every row and column.
@@ -498,14 +504,29 @@ class Engine {
     void finish_leaves(const detail::GrowCtx &c, const detail::GrowDims &dims, const detail::LevelWork &w, detail::TreeBuilder &tb, detail::Stager &sta,
                        std::vector<int64_t> &acc, double &leaf_scale);
     uint32_t next_seq() { const uint32_t seq = ++level_seq_; return seq ? seq : ++level_seq_; }   // 0 is never published
-    bool device_categorical_candidates(const char *dcells, const char *hcells, int N, int Fc, int B,
-                                       std::vector<detail::CatCandidate> &cat_cands, std::vector<int> &cat_classes, bool launch_only = false,
-                                       const float *dgrads = nullptr, int D = 0);   // dgrads: the batch's raw gradients (device), for the mean-gradient ranking
+    // ---- a step's categorical candidates (engine_cat_candidates.hip): the scan is enqueued before the numeric preparation and collected behind it ----
+    bool enqueue_categorical_scan(const char *dcells, int N, int Fc, int B);   // false: declined at its sizes, nothing enqueued
+    bool collect_categorical_candidates(const char *dcells, int N, int Fc, int B, const float *dgrads, int D, std::vector<detail::CatCandidate> &cat_cands,
+                                        std::vector<int> &cat_classes);   // false: declined, the host rules decide; dgrads: raw gradients (device), for the ranking
+    bool cat_rank_round(const char *dcells, int N, int Fc, const float *dgrads, int D, int n_distinct, detail::CatList &list);
+    void cat_gather_sharded(detail::CatList &list, std::vector<int> &order, int &n_distinct, std::vector<char> &store);
     void sharded_categorical_ranking(const char *hcat, const float *hgrads, int N, int Fc, int D, int B, std::vector<detail::CatCandidate> &cat_cands,
                                      std::vector<uint16_t> &h_catcodes, std::vector<int> &cat_classes);
-    void numeric_thresholds(const float *dobs, int N, int F, int B, long long n_global, const uint32_t *d_kt, float *d_thr,
-                            uint32_t *d_thrkeys, DevBuf &root_le_buf, const uint32_t **root_le_out, int pass1_chunks = 0, uint16_t *d_codes_out = nullptr,
-                            bool *codes_written = nullptr);
+    void verify_pending_categories();   // the byte comparisons the replay deferred; a difference sets cat_clash_
+    // ---- a step's numeric thresholds (engine_candidates.hip): one function per route ----
+    void numeric_thresholds(const float *dobs, int N, int F, int B, long long n_global, const uint32_t *d_kt, float *d_thr, uint32_t *d_thrkeys,
+                            DevBuf &root_le_buf, const uint32_t **root_le_out, int pass1_chunks = 0, uint16_t *d_codes_out = nullptr, bool *codes_written = nullptr);
+    bool radix_select_applies(int B, long long n_global) const;
+    detail::ThrRoute threshold_route(int N, int B, long long n_global) const;   // the route choice, written once
+    void thresholds_fixed(const detail::ThrArgs &a), thresholds_uniform(const detail::ThrArgs &a), thresholds_bisection(const detail::ThrArgs &a), thresholds_sample(const detail::ThrArgs &a);
+    bool thresholds_lds_sort(const detail::ThrArgs &a, uint16_t *d_codes_out);   // true: it wrote the class codes too
+    const uint32_t *thresholds_radix(const detail::ThrArgs &a, DevBuf &root_le_buf, int pass1_chunks);   // returns #{keys <= threshold} (one GPU), else null
+    // ---- step() in stages (engine_step.hip) ----
+    bool step_pass(detail::StepInputs &in, bool host_categorical);   // one attempt at the step; false: a categorical hash clash, nothing booked
+    void stage_step_inputs(detail::StepInputs &in);
+    detail::CatStage categorical_stage(const detail::StepInputs &in, bool host_categorical);
+    void finish_candidates_only(const detail::CatStage &cs, int Fc, const float *d_thr, size_t n_thr);
+    void launch_cat_codes(const detail::StepInputs &in, const detail::CatStage &cs, uint16_t *d_codes);
     // ---- the stages step() and step_prepared() share (engine_step.hip) ----
     void read_step_hooks();                                              // the per-call test hooks that choose the selection path
     bool fused_prep_applies(int N, int F, long long n_global) const;     // kern::small_prep is tried for this shape
@@ -543,6 +564,10 @@ class Engine {
     void *rccl_comm_ = nullptr;          // non-null: the exchanges below are RCCL calls on stream_
     enum class Red { SumI64, SumF64, MaxF32, MinF32 };
     void exchange(Red op, void *dev_buf, size_t count);   // all-reduce in place; stream-ordered (RCCL) or host-synchronous (hooks)
+    void allreduce_host(Red op, void *host, size_t count, DevBuf &scratch);   // the same on a host array: up, exchange, down, synchronise
+    bool all_ranks_agree(bool mine, DevBuf &scratch);      // true on every rank when `mine` is true on any: every rank takes the same path
+    // every rank's records (int64 words), rank after rank; more than `cap` records in all: Unsupported
+    std::vector<int64_t> all_gather_records(const std::vector<int64_t> &mine, int words_per_record, size_t cap);
     // recv[0 .. count) = sum over ranks of their send[rank * count .. (rank + 1) * count)  (int64).  RCCL: ncclReduceScatter on the
     // stream (half the bytes of an all-reduce over the xGMI ring); hooks: all-reduce of the whole send buffer, then the own slice.
     void reduce_scatter_i64(int64_t *send, int64_t *recv, size_t count);
@@ -553,6 +578,7 @@ class Engine {
     int profiling_ = 0;
     unsigned key_calls_ = 0;   // key-kernel launches seen at profiling level 1 (every seventh carries an event pair)
     bool force_bisection_ = false, force_sample_select_ = false, force_host_categorical_ = false, force_radix_ = false, last_quantile_fallback_ = false;
+    bool cat_clashed_ = false;   // a step of this model met a categorical hash clash: it stays on the host scan, whatever the hook says
     // fit(): numeric thresholds computed once from the whole data set and reused by every batch's step()
     std::vector<float> fixed_thr_;
     std::vector<detail::CatCandidate> fixed_cat_cands_;
@@ -562,7 +588,6 @@ class Engine {
     bool in_fit_ = false;   // predict() called from fit(): keep one accumulation chain per row in tree order (no tree-range split)
     std::vector<std::pair<std::string, float>> phases_;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool_;
-    bool cat_launched_ = false;       // device_categorical_candidates(launch_only) has enqueued the first round of the scan
     hipEvent_t ev_level_ = nullptr;   // marks the per-level result read-back (GBRL_HIP_EVENT_RESULTS=1: the copy-engine path)
     // Per-step constants of numeric-only steps (feature slots, candidate weights / reference order / slot lookup): they depend on
     // (F, n_bins, growth policy, feature weights, feature mapping) only, so they are built and uploaded once and reused while those
@@ -697,7 +722,7 @@ class Engine {
     DevBuf d_radix_state_, d_radix_partial_, d_radix_global_, d_scales_;
     DevBuf d_catcodes_, d_rows_[2];
     DevBuf d_hist_prev_, d_am_v_, d_am_i_, d_stage_const_, d_stage_a_, d_stage_b_, d_results_;
-    PinnedBuf pin_const_, pin_a_, pin_b_, pin_res_, pin_thr_, pin_acc_, pin_cat_, pin_cat_dict_;
+    PinnedBuf pin_const_, pin_a_, pin_b_, pin_res_, pin_thr_, pin_acc_;
     DevBuf d_hist_partials_, d_hist_, d_hist_local_, d_hist_recv_, d_gather_, d_scores_, d_parent_;
     DevBuf d_splits_, d_cursors_, d_leafacc_, d_plan_, d_res_all_;
     PinnedBuf pin_res_all_, pin_cum_;
@@ -742,27 +767,10 @@ class Engine {
     DevBuf d_dict_off_, d_dict_hash_, d_dict_id_, d_dict_words_, d_pcells_;
     PinnedBuf pin_model_stage_;           // the slices sync_model_to_device appends, staged for one kern::stage_copy launch
     hipEvent_t ev_model_stage_ = nullptr; // behind that launch: the block is not refilled before it has been read
-    DevBuf d_cat_keys_, d_cat_first_, d_cat_meta_, d_cat_lslot_, d_sdict_, d_cat_xchg_, d_cat_slotq_, d_cat_clsq_;
-    PinnedBuf pin_cat_cls_;
-    DevBuf d_cat_rank_, d_cat_rank_cnt_, d_cat_rank_tot_;   // kern::cat_rank: scratch, count and total per distinct cell (more distinct cells than candidates)
-    uint32_t cat_pub_seq_ = 0;                          // sequence word of k_cat_publish's completion flag
-    // ordinary steps on one GPU: the class codes come from the scan's own tables (k_cat_step_codes_table) instead of a dictionary
-    struct { bool valid = false; const uint64_t *keys = nullptr; const int32_t *slot_q = nullptr, *cls_of_q = nullptr; int log2_cap = 0; } cat_table_;
-    // the step's candidate dictionary inside d_sdict_ (one upload): per categorical feature the entries sorted by raw hash
-    const int32_t *sdict_off_ = nullptr, *sdict_cls_ = nullptr;
-    const uint64_t *sdict_hash_ = nullptr, *sdict_words_ = nullptr;
-    int cat_log2_hint_ = 20;                            // log2 of the per-feature table size the next step starts with (20: the full size)
-    int cat_publish_guess_ = 256;                       // records the next step publishes with its header (the last count + 25 %)
-    void verify_pending_categories();
-    std::vector<std::pair<int, const char *>> cat_pending_;   // (item, published cell) pairs whose bytes are still to be compared this step
-    bool cat_clash_ = false;
+    detail::CatScan cat_;             // the device scan for a step's distinct categorical cells, and where its class codes come from
+    detail::CatMemory cat_mem_;       // every distinct (feature, cell) met so far; the replay of the reference's candidate container
+    bool cat_clash_ = false;          // this step's deferred comparisons found two categories of one feature under one 64-bit hash
     long long cat_clash_redos_ = 0;   // steps grown a second time on the host scan after a 64-bit hash clash (diagnostics)
-    std::vector<detail::CatItem> cat_items_;            // every distinct (feature, cell) met so far
-    std::vector<uint64_t> cat_tab_key_;                 // (raw hash, feature) -> head of the chain through CatItem::next: open-addressed
-    std::vector<int32_t> cat_tab_id_;                   //   table (keys | item ids, -1 = empty), at most half full
-    std::vector<char> cat_host_;                        // the published distinct-cell block, copied out of the pinned mapping
-    std::vector<uint32_t> cat_seen_;                    // per item: tag of the last replay that inserted it
-    uint32_t cat_seen_tag_ = 0;
     DevBuf d_fit_cells_, d_fit_cells2_;
     DevBuf d_fit_obs_, d_fit_targets_, d_fit_obs2_, d_fit_targets2_, d_fit_perm_, d_fit_preds_, d_fit_grads_, d_fit_zero_;
 };

@@ -216,6 +216,37 @@ void Engine::exchange(Red op, void *dev_buf, size_t count) {
     }
     if (rc != 0) throw HipError("allreduce failed");
 }
+// exchange() of a host array: up, all-reduce, down, synchronise.  (No synchronisation between the copy up and the exchange: the hooks
+// transport synchronises the stream itself before it reduces, RCCL is stream-ordered.)
+void Engine::allreduce_host(Red op, void *host, size_t count, DevBuf &scratch) {
+    const size_t bytes = count * (op == Red::MaxF32 || op == Red::MinF32 ? 4 : 8);
+    void *d = scratch.ensure(bytes);
+    hip_check(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, stream_), "H2D");
+    exchange(op, d, count);
+    hip_check(hipMemcpyAsync(host, d, bytes, hipMemcpyDeviceToHost, stream_), "D2H");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+}
+bool Engine::all_ranks_agree(bool mine, DevBuf &scratch) {
+    int64_t hv = mine ? 1 : 0;
+    allreduce_host(Red::SumI64, &hv, 1, scratch);
+    return hv != 0;
+}
+// All-gather through the sum exchange: the record counts first, then every rank writes its block into a zeroed buffer at its offset.
+std::vector<int64_t> Engine::all_gather_records(const std::vector<int64_t> &mine, int words_per_record, size_t cap) {
+    const int world = coll_.world_size, rank = coll_.rank;
+    const size_t W = static_cast<size_t>(words_per_record);
+    std::vector<int64_t> cnt(world + 1, 0);
+    cnt[rank] = static_cast<int64_t>(mine.size() / W);
+    allreduce_host(Red::SumI64, cnt.data(), cnt.size(), cat_.xchg);
+    size_t total = 0, off = 0;
+    for (int r = 0; r < world; ++r) { if (r < rank) off += static_cast<size_t>(cnt[r]); total += static_cast<size_t>(cnt[r]); }
+    if (total > cap) throw Unsupported("too many distinct categories for a row-sharded step");
+    std::vector<int64_t> all(std::max<size_t>(total * W, 1), 0);
+    std::copy(mine.begin(), mine.end(), all.begin() + static_cast<long>(off * W));
+    allreduce_host(Red::SumI64, all.data(), all.size(), cat_.xchg);
+    all.resize(total * W);
+    return all;
+}
 int Engine::radix_exchange_trampoline(void *self, int64_t *dev_buf, size_t count) {
     try {
         static_cast<Engine *>(self)->exchange(Red::SumI64, dev_buf, count);

@@ -15,55 +15,6 @@ namespace gbrl {
 
 namespace detail {
 
-// ---- A5: categorical candidates on the host, exactly as processCategoricalCandidates (split_candidate_generator.cpp:117-163):
-// same container, same insertion order => same candidate order (Q8).  cat_classes[f] = number of candidate categories of
-// feature f (class ids 1..), h_catcodes[i*Fc+f] = class of the cell (0: not a candidate).
-void categorical_candidates(const char *hcat, const float *hgrads, int N, int Fc, int D, int B, std::vector<CatCandidate> &cat_cands,
-                            std::vector<uint16_t> &h_catcodes, std::vector<int> &cat_classes) {
-    struct Info { float total = 0.f; int count = 0; int feat = 0; std::string name; };
-    std::vector<float> norms(N, 0.0f);
-    for (int i = 0; i < N; ++i) {  // calculate_squared_norm (math_ops.cpp:726-749), contracted like the reference build
-        float acc = 0.0f;
-        for (int d = 0; d < D; ++d) { const float g = hgrads[static_cast<size_t>(i) * D + d]; acc = fmaf(g, g, acc); }
-        norms[i] = acc;
-    }
-    std::unordered_map<std::string, Info> uniq;
-    for (int f = 0; f < Fc; ++f)
-        for (int i = 0; i < N; ++i) {
-            std::string name(hcat + (static_cast<size_t>(i) * Fc + f) * kCat, kCat);
-            Info &ci = uniq[name + "_" + std::to_string(f)];
-            ci.total += norms[i];
-            ci.count += 1;
-            ci.feat = f;
-            ci.name = name;
-        }
-    std::vector<std::pair<std::string, float>> vec;
-    for (const auto &kv : uniq) vec.emplace_back(kv.first, kv.second.total / kv.second.count);
-    int n_unique = static_cast<int>(vec.size());
-    if (n_unique > Fc * B) {
-        std::sort(vec.begin(), vec.end(), [](const std::pair<std::string, float> &a, const std::pair<std::string, float> &b) {
-            return a.second > b.second;
-        });
-        n_unique = Fc * B;
-    }
-    std::unordered_map<std::string, int> cls_of;  // key -> class id within its feature
-    for (int i = 0; i < n_unique; ++i) {
-        const Info &ci = uniq[vec[i].first];
-        const int cls = ++cat_classes[ci.feat];
-        if (cls > 65534) throw Unsupported("more than 65534 candidate categories in one feature");
-        cat_cands.emplace_back(ci.feat, ci.name.data(), cls);
-        cls_of[vec[i].first] = cls;
-    }
-    h_catcodes.assign(static_cast<size_t>(N) * Fc, 0);
-    for (int i = 0; i < N; ++i)
-        for (int f = 0; f < Fc; ++f) {
-            std::string key(hcat + (static_cast<size_t>(i) * Fc + f) * kCat, kCat);
-            key += "_" + std::to_string(f);
-            auto it = cls_of.find(key);
-            if (it != cls_of.end()) h_catcodes[static_cast<size_t>(i) * Fc + f] = static_cast<uint16_t>(it->second);
-        }
-}
-
 // ---- A10/A11: the grown tree joins the ensemble (update_ensemble_per_leaf / per_tree, fitter.cpp:493-542) with exact leaf
 // means of the raw gradients (acc[node] = int64 fixed-point sums | count; fitter.cpp:545-582).
 void append_tree(Model &model, const std::vector<HNode> &nodes, const std::vector<int> &frontier, const std::vector<int64_t> &acc,
@@ -245,8 +196,7 @@ NumericPrep Engine::prepare_numeric(PrepBuffers &pb, const float *dobs, int N, i
         d_kt = static_cast<uint32_t *>(pb.kt.ensure(sizeof(uint32_t) * static_cast<size_t>(N) * F));
         // quantile candidates by radix selection (the branch numeric_thresholds will take): the first digit is counted while the keys
         // pass through LDS (k_transpose_count), which saves one of the selection's passes over the keys
-        const bool radix_path = fixed_thr_.empty() && md.generator_type != GBRL_HIP_GEN_UNIFORM && !force_bisection_ && !force_sample_select_ &&
-                                B <= kern::radix_max_targets() && n_global < (1ll << 32);
+        const bool radix_path = fixed_thr_.empty() && md.generator_type != GBRL_HIP_GEN_UNIFORM && !force_bisection_ && radix_select_applies(B, n_global);
         if (radix_path)
             pass1_chunks = kern::transpose_keys_count(dobs, N, F, d_kt, static_cast<uint32_t *>(d_radix_partial_.ensure(kern::radix_partial_bytes(F))), s);
         if (pass1_chunks == 0) kern::transpose_keys(dobs, N, F, d_kt, s);
@@ -438,50 +388,149 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
     if (md.max_depth > kern::kMaxPath) throw Unsupported("max_depth > 32 is not supported");
     if (md.n_bins < 1 || md.n_bins > 65534) throw Unsupported("n_bins must be in [1, 65534]");
     ensure_device();
-    prof_step_entry_ = std::chrono::steady_clock::now();
+    read_step_hooks();
+    detail::StepInputs in{obs, obs_dev, cat, cat_dev, grads, grads_dev, n, n_num, n_cat};
+    const bool host_categorical = force_host_categorical_ || cat_clashed_;
+    if (step_pass(in, host_categorical)) return;
+    // Two different cells of one feature share a 64-bit hash (2^-64 per pair of cells).  The tree just grown used the wrong dictionary id for
+    // one of them, but nothing has been booked yet (append_tree is what changes the model): the remembered cells are forgotten, THIS model
+    // stays on the host scan of every cell from here on -- it compares bytes, so the pair cannot clash again -- and the tree is grown once
+    // more from the same inputs.
+    if (host_categorical) throw HipError("two different categories of one feature share a 64-bit hash on the host scan (internal error)");
+    if (has_coll_) throw HipError("two different categories of one feature share a 64-bit hash: step refused (row-sharded run: set GBRL_HIP_HOST_CATEGORICAL=1 on every rank)");
+    cat_clashed_ = true;
+    ++cat_clash_redos_;
+    if (!step_pass(in, /*host_categorical=*/true)) throw HipError("two different categories of one feature share a 64-bit hash on the host scan (internal error)");
+}
+
+// ---- inputs on the device ---------------------------------------------------------------------------------------------
+void Engine::stage_step_inputs(detail::StepInputs &in) {
+    hipStream_t s = stream_;
+    const int N = in.N, F = in.F, Fc = in.Fc, D = model.meta.output_dim;
+    phase_begin();
+    in.dobs = in.obs;
+    if (F > 0 && !in.obs_dev) {
+        in.dobs = static_cast<float *>(d_obs_.ensure(sizeof(float) * N * F));
+        hip_check(hipMemcpyAsync(const_cast<float *>(in.dobs), in.obs, sizeof(float) * N * F, hipMemcpyHostToDevice, s), "H2D obs");
+    }
+    in.dgrads = in.grads;
+    if (!in.grads_dev) {
+        in.dgrads = static_cast<float *>(d_grads_.ensure(sizeof(float) * N * D));
+        hip_check(hipMemcpyAsync(const_cast<float *>(in.dgrads), in.grads, sizeof(float) * N * D, hipMemcpyHostToDevice, s), "H2D grads");
+    }
+    // categorical cells on the device: the distinct categories of the batch are found there (enqueue_categorical_scan);
+    // the host-side scan of every cell is only the fallback
+    in.dcells = in.cat;
+    if (Fc > 0 && !in.cat_dev) {
+        char *t = static_cast<char *>(d_pcells_.ensure(static_cast<size_t>(N) * Fc * kCat));
+        hip_check(hipMemcpyAsync(t, in.cat, static_cast<size_t>(N) * Fc * kCat, hipMemcpyHostToDevice, s), "H2D cat cells");
+        in.dcells = t;
+    }
+    phase_end("inputs");
+}
+
+// ---- categorical candidates (A5) ----------------------------------------------------------------------------------------
+// fit(): the candidates of the whole data set (fitter.cpp:152-164), their dictionary still on the device.  Else the distinct cells found by
+// the scan enqueued earlier, replayed on the host; and when that is switched off or declines -- more distinct categories than candidates
+// are kept in a row-sharded step, sizes beyond the scan -- the reference's rule on every cell, on the host.
+detail::CatStage Engine::categorical_stage(const detail::StepInputs &in, bool host_categorical) {
+    const int N = in.N, Fc = in.Fc, D = model.meta.output_dim, B = model.meta.n_bins;
+    detail::CatStage cs;
+    cs.classes.assign(Fc, 0);
+    if (Fc <= 0) return cs;
+    if (fixed_cat_valid_) {
+        cs.cands = fixed_cat_cands_;
+        cs.classes = fixed_cat_classes_;
+        cs.codes = detail::CatStage::Dict;
+        return cs;
+    }
+    if ((has_coll_ || !host_categorical) && collect_categorical_candidates(in.dcells, N, Fc, B, in.dgrads, D, cs.cands, cs.classes)) {
+        cs.codes = cat_.table.valid ? detail::CatStage::Table : detail::CatStage::Dict;
+        return cs;
+    }
+    std::vector<char> cat_host_buf;
+    const char *hcat = in.cat;
+    std::vector<float> grads_host_buf;
+    const float *hgrads = in.grads;
+    if (in.cat_dev) {
+        cat_host_buf.resize(static_cast<size_t>(N) * Fc * kCat);
+        hip_check(hipMemcpy(cat_host_buf.data(), in.cat, cat_host_buf.size(), hipMemcpyDeviceToHost), "D2H cat");
+        hcat = cat_host_buf.data();
+    }
+    if (in.grads_dev) {
+        grads_host_buf.resize(static_cast<size_t>(N) * D);
+        hip_check(hipMemcpy(grads_host_buf.data(), in.grads, grads_host_buf.size() * 4, hipMemcpyDeviceToHost), "D2H grads");
+        hgrads = grads_host_buf.data();
+    }
+    cs.cands.clear();
+    std::fill(cs.classes.begin(), cs.classes.end(), 0);
+    if (has_coll_) sharded_categorical_ranking(hcat, hgrads, N, Fc, D, B, cs.cands, cs.h_codes, cs.classes);
+    else detail::categorical_candidates(hcat, hgrads, N, Fc, D, B, cs.cands, cs.h_codes, cs.classes);
+    cs.codes = detail::CatStage::Host;
+    return cs;
+}
+
+// fit(): only the candidates of this (whole) data set are wanted
+void Engine::finish_candidates_only(const detail::CatStage &cs, int Fc, const float *d_thr, size_t n_thr) {
+    float *h_thr = nullptr;
+    kern::StepScales *h_scales_pin = nullptr;
+    (void)pinned_thr_block(pin_thr_, n_thr, h_thr, h_scales_pin);
+    if (n_thr) hip_check(hipMemcpyAsync(h_thr, d_thr, sizeof(float) * n_thr, hipMemcpyDeviceToHost, stream_), "D2H thr");
+    hip_check(hipStreamSynchronize(stream_), "sync");
+    fixed_thr_.assign(h_thr, h_thr + n_thr);
+    if (Fc > 0) {
+        verify_pending_categories();
+        if (cat_clash_) { cat_clash_ = false; cat_mem_.forget(); throw HipError("two different categories of one feature share a 64-bit hash: fit() refused"); }
+        if (cs.codes == detail::CatStage::Host)   // (the host scan: GBRL_HIP_HOST_CATEGORICAL=1, or the device scan declined -- more than 2^21 distinct cells)
+            throw Unsupported("fit(): the categorical candidates of the whole data set need the device scan (GBRL_HIP_HOST_CATEGORICAL=1, or more than 2^21 distinct categories)");
+        fixed_cat_cands_ = cs.cands;
+        fixed_cat_classes_ = cs.classes;
+        fixed_cat_valid_ = true;
+    }
+    phases_resolve();
+}
+
+// ---- 3. categorical class codes (group-major: [slot/16][row][slot%16], u16) --------------------------------------------
+void Engine::launch_cat_codes(const detail::StepInputs &in, const detail::CatStage &cs, uint16_t *d_codes) {
+    hipStream_t s = stream_;
+    const int N = in.N, F = in.F, Fc = in.Fc;
+    if (Fc <= 0) return;
+    phase_begin();
+    switch (cs.codes) {
+        case detail::CatStage::Table:
+            kern::cat_step_codes_table(in.dcells, N, Fc, F, cat_.table.keys, cat_.table.slot_q, cat_.table.cls_of_q, cat_.table.log2_cap, d_codes, s);
+            break;
+        case detail::CatStage::Dict:
+            kern::cat_step_codes(in.dcells, N, Fc, F, cat_.dict.off, cat_.dict.hash, cat_.dict.cls, cat_.dict.words, d_codes, s);
+            break;
+        default: {
+            uint16_t *d_cc2 = static_cast<uint16_t *>(d_catcodes_.ensure(sizeof(uint16_t) * cs.h_codes.size()));
+            hip_check(hipMemcpyAsync(d_cc2, cs.h_codes.data(), sizeof(uint16_t) * cs.h_codes.size(), hipMemcpyHostToDevice, s), "H2D cat codes");
+            kern::scatter_cat_codes_grouped(d_cc2, N, Fc, F, d_codes, s);
+        }
+    }
+    phase_end("cat_codes");
+}
+
+// One attempt at the step, from the staging of its inputs to the tree joining the ensemble.  false: the categorical replay took one cell
+// for another under the same 64-bit hash -- the tree is dropped, nothing has been booked, and step() makes a second pass on the host scan.
+bool Engine::step_pass(detail::StepInputs &in, bool host_categorical) {
+    const gbrl_hip_metadata &md = model.meta;
+    const int N = in.N, F = in.F, Fc = in.Fc, D = md.output_dim, B = md.n_bins;
+    const bool cosine = md.split_score_func == GBRL_HIP_SCORE_COSINE;
+    prof_step_entry_ = std::chrono::steady_clock::now();   // the per-step diagnostics: a second pass reports itself alone
     ev_used_ = 0;
     ev_names_.clear();
     exch_bytes_ = 0;
     exch_calls_ = 0;
-    read_step_hooks();
-    hipStream_t s = stream_;
-    const int N = n, F = n_num, Fc = n_cat, D = md.output_dim, B = md.n_bins;
-    const bool cosine = md.split_score_func == GBRL_HIP_SCORE_COSINE;
-
-    // global row count (rows are sharded over ranks): it travels with the first gradient-statistics message below (round 6: no exchange and no
+    // global row count (rows are sharded over ranks): it travels with the first gradient-statistics message below (no exchange and no
     // idle device for it); until then n_global holds this rank's count and nothing reads it
     long long n_global = N;
-
-    // ---- inputs on the device -------------------------------------------------------------------------------------
-    phase_begin();
-    const float *dobs = obs;
-    if (F > 0 && !obs_dev) {
-        dobs = static_cast<float *>(d_obs_.ensure(sizeof(float) * N * F));
-        hip_check(hipMemcpyAsync(const_cast<float *>(dobs), obs, sizeof(float) * N * F, hipMemcpyHostToDevice, s), "H2D obs");
-    }
-    const float *dgrads = grads;
-    if (!grads_dev) {
-        dgrads = static_cast<float *>(d_grads_.ensure(sizeof(float) * N * D));
-        hip_check(hipMemcpyAsync(const_cast<float *>(dgrads), grads, sizeof(float) * N * D, hipMemcpyHostToDevice, s), "H2D grads");
-    }
-    // categorical cells on the device: the distinct categories of the batch are found there (device_categorical_candidates);
-    // the host-side scan of every cell is only the fallback
-    const char *dcells = cat;
-    if (Fc > 0 && !cat_dev) {
-        char *t = static_cast<char *>(d_pcells_.ensure(static_cast<size_t>(N) * Fc * kCat));
-        hip_check(hipMemcpyAsync(t, cat, static_cast<size_t>(N) * Fc * kCat, hipMemcpyHostToDevice, s), "H2D cat cells");
-        dcells = t;
-    }
-    phase_end("inputs");
+    stage_step_inputs(in);
     prof_marks_[0] = std::chrono::steady_clock::now();
-    // the scan for the batch's distinct categorical cells goes first: its result is read by the HOST (device_categorical_candidates)
-    const bool cat_early = Fc > 0 && !fixed_cat_valid_ && (has_coll_ || !force_host_categorical_);
-    cat_launched_ = false;   // (a step that threw between the two stages must not be resumed)
-    if (cat_early) {
-        std::vector<CatCandidate> none;
-        std::vector<int> none_classes(Fc, 0);
-        (void)device_categorical_candidates(dcells, cat_dev ? nullptr : cat, N, Fc, B, none, none_classes, /*launch_only=*/true);
-    }
+    // the scan for the batch's distinct categorical cells goes first: its result is read by the HOST (collect_categorical_candidates)
+    cat_.launched = false;
+    if (Fc > 0 && !fixed_cat_valid_ && (has_coll_ || !host_categorical)) (void)enqueue_categorical_scan(in.dcells, N, Fc, B);
 
     // ---- 1. gradient statistics and quantisation (A2): Engine::run_grad_stats -------------------------------------------------
     phase_begin();
@@ -495,95 +544,24 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
     int32_t *d_qg = static_cast<int32_t *>(d_qg_.ensure(sizeof(int32_t) * static_cast<size_t>(N) * D));
     const bool no_small_stats = [] { const char *e = hooks::raw(hooks::NO_SMALL_STATS); return e && e[0] == '1'; }();   /* read per call: the tests flip it */
     // (row-sharded: the chunk length is set again once the global count is known)
-    FusedStats gs{dgrads, D, cosine, d_stat, d_meanden, d_scales, d_qg, chunk_rows_of(n_global), !no_small_stats};
+    FusedStats gs{in.dgrads, D, cosine, d_stat, d_meanden, d_scales, d_qg, chunk_rows_of(n_global), !no_small_stats};
     // RL-sized steps on one GPU: the statistics ride in the fused preparation kernel's launch (prepare_numeric)
     const bool prep_candidate = fused_prep_applies(N, F, n_global);
     if (!prep_candidate) run_grad_stats(gs, N, n_global);
     phase_end("grad_stats");
 
     // ---- 2. split candidates and 3. numeric class codes: Engine::prepare_numeric, into this engine's workspace ----------------
-    // thresholds and scales reach the host through ONE pinned block, copied behind the binning kernel: nothing waits for them
-    // until the first level's result block has arrived
-    const size_t n_thr = static_cast<size_t>(F) * B;
-    float *h_thr = nullptr;
-    kern::StepScales *h_scales_pin = nullptr;
-    (void)pinned_thr_block(pin_thr_, n_thr, h_thr, h_scales_pin);
-    const NumericPrep np = prepare_numeric(prep_ws_, dobs, N, F, Fc, n_global, prep_candidate, &gs);
-    float *d_thr = np.d_thr;
-    uint16_t *d_codes = np.d_codes;
-
-    // categorical candidates (A5): distinct cells found on the device, inserted into the reference's container in the
-    // reference's insertion order on the host => same candidate order (Q8).  Falls back to the host scan of every cell when
-    // the batch holds more distinct categories than candidates are kept (the reference then ranks them by mean gradient norm).
-    std::vector<CatCandidate> cat_cands;
-    std::vector<uint16_t> h_catcodes;
-    std::vector<int> cat_classes(Fc, 0);
-    bool cat_codes_on_device = false;
-    if (Fc > 0) {
-        if (fixed_cat_valid_) {   // fit(): candidates of the whole data set (fitter.cpp:152-164); the dictionary is still on the device
-            cat_cands = fixed_cat_cands_;
-            cat_classes = fixed_cat_classes_;
-            cat_codes_on_device = true;
-        } else {
-            cat_codes_on_device = (has_coll_ || !force_host_categorical_) &&
-                                  device_categorical_candidates(dcells, cat_dev ? nullptr : cat, N, Fc, B, cat_cands, cat_classes, /*launch_only=*/false, dgrads, D);
-        }
-        if (!cat_codes_on_device) {
-            std::vector<char> cat_host_buf;
-            const char *hcat = cat;
-            std::vector<float> grads_host_buf;
-            const float *hgrads = grads;
-            if (cat_dev) {
-                cat_host_buf.resize(static_cast<size_t>(N) * Fc * kCat);
-                hip_check(hipMemcpy(cat_host_buf.data(), cat, cat_host_buf.size(), hipMemcpyDeviceToHost), "D2H cat");
-                hcat = cat_host_buf.data();
-            }
-            if (grads_dev) {
-                grads_host_buf.resize(static_cast<size_t>(N) * D);
-                hip_check(hipMemcpy(grads_host_buf.data(), grads, grads_host_buf.size() * 4, hipMemcpyDeviceToHost), "D2H grads");
-                hgrads = grads_host_buf.data();
-            }
-            cat_cands.clear();
-            std::fill(cat_classes.begin(), cat_classes.end(), 0);
-            if (has_coll_) sharded_categorical_ranking(hcat, hgrads, N, Fc, D, B, cat_cands, h_catcodes, cat_classes);
-            else categorical_candidates(hcat, hgrads, N, Fc, D, B, cat_cands, h_catcodes, cat_classes);
-        }
-    }
-
+    // (thresholds and scales reach the host through ONE pinned block, copied behind the binning kernel: nothing waits for them
+    // until the first level's result block has arrived)
+    const NumericPrep np = prepare_numeric(prep_ws_, in.dobs, N, F, Fc, n_global, prep_candidate, &gs);
+    const detail::CatStage cs = categorical_stage(in, host_categorical);
     prof_marks_[2] = std::chrono::steady_clock::now();
-    if (candidates_only_) {   // fit(): only the candidates of this (whole) data set are wanted
-        if (n_thr) hip_check(hipMemcpyAsync(h_thr, d_thr, sizeof(float) * n_thr, hipMemcpyDeviceToHost, s), "D2H thr");
-        hip_check(hipStreamSynchronize(s), "sync");
-        fixed_thr_.assign(h_thr, h_thr + n_thr);
-        if (Fc > 0) {
-            verify_pending_categories();
-            if (cat_clash_) { cat_clash_ = false; cat_items_.clear(); cat_tab_key_.clear(); cat_tab_id_.clear(); throw HipError("two different categories of one feature share a 64-bit hash: fit() refused"); }
-            if (!cat_codes_on_device)   // (the host scan: GBRL_HIP_HOST_CATEGORICAL=1, or the device scan declined -- more than 2^21 distinct cells)
-                throw Unsupported("fit(): the categorical candidates of the whole data set need the device scan (GBRL_HIP_HOST_CATEGORICAL=1, or more than 2^21 distinct categories)");
-            fixed_cat_cands_ = cat_cands;
-            fixed_cat_classes_ = cat_classes;
-            fixed_cat_valid_ = true;
-        }
-        phases_resolve();
-        return;
-    }
-    // ---- 3. class codes (group-major: [slot/16][row][slot%16], u16) ---------------------------------------------------
-    if (Fc > 0) phase_begin();
-    if (Fc > 0 && cat_codes_on_device) {
-        if (cat_table_.valid && !fixed_cat_valid_)
-            kern::cat_step_codes_table(dcells, N, Fc, F, cat_table_.keys, cat_table_.slot_q, cat_table_.cls_of_q, cat_table_.log2_cap, d_codes, s);
-        else
-            kern::cat_step_codes(dcells, N, Fc, F, sdict_off_, sdict_hash_, sdict_cls_, sdict_words_, d_codes, s);
-    } else if (Fc > 0) {
-        uint16_t *d_cc2 = static_cast<uint16_t *>(d_catcodes_.ensure(sizeof(uint16_t) * h_catcodes.size()));
-        hip_check(hipMemcpyAsync(d_cc2, h_catcodes.data(), sizeof(uint16_t) * h_catcodes.size(), hipMemcpyHostToDevice, s), "H2D cat codes");
-        kern::scatter_cat_codes_grouped(d_cc2, N, Fc, F, d_codes, s);
-    }
-    if (Fc > 0) phase_end("cat_codes");
+    if (candidates_only_) { finish_candidates_only(cs, Fc, np.d_thr, static_cast<size_t>(F) * B); return true; }
+    launch_cat_codes(in, cs, np.d_codes);
     // ---- feature slots, candidate order, weights, 4. growth and 5. leaf sums: Engine::grow_step_tree ----------------------------
     StepData sd{};
     sd.N = N; sd.F = F; sd.Fc = Fc; sd.n_global = n_global; sd.chunk_rows = gs.chunk_rows; sd.prep = np; sd.stats = &gs;
-    sd.cat_cands = &cat_cands; sd.cat_classes = &cat_classes;
+    sd.cat_cands = &cs.cands; sd.cat_classes = &cs.classes;
     std::vector<HNode> nodes;
     std::vector<int> frontier;
     std::vector<int64_t> acc;
@@ -591,22 +569,14 @@ void Engine::step(const float *obs, bool obs_dev, const char *cat, bool cat_dev,
     grow_step_tree(sd, nodes, frontier, acc, leaf_scale);
     verify_pending_categories();
     if (cat_clash_) {
-        // Two different cells of one feature share a 64-bit hash (2^-64 per pair of cells).  The tree just grown used the wrong
-        // dictionary id for one of them, but nothing has been booked yet (append_tree below is what changes the model): forget the remembered
-        // cells, switch THIS model to the host scan of every cell -- it compares bytes, so the pair cannot clash again -- and grow the tree
-        // once more from the same inputs.  (Before round 6 the step threw, and every later step that held both cells threw again.)
         cat_clash_ = false;
-        cat_items_.clear(); cat_tab_key_.clear(); cat_tab_id_.clear(); std::fill(cat_seen_.begin(), cat_seen_.end(), 0u);
-        if (force_host_categorical_) throw HipError("two different categories of one feature share a 64-bit hash on the host scan (internal error)");
-        if (has_coll_) throw HipError("two different categories of one feature share a 64-bit hash: step refused (row-sharded run: set GBRL_HIP_HOST_CATEGORICAL=1 on every rank)");
-        force_host_categorical_ = true;
-        ++cat_clash_redos_;
-        step(obs, obs_dev, cat, cat_dev, grads, grads_dev, n, n_num, n_cat);
-        return;
+        cat_mem_.forget();
+        return false;
     }
-    append_tree(model, nodes, frontier, acc, leaf_scale, cat_cands);
+    append_tree(model, nodes, frontier, acc, leaf_scale, cs.cands);
     hip_check(hipGetLastError(), "step kernels");
     phases_resolve();
+    return true;
 }
 
 // ===================================================================================================== fit

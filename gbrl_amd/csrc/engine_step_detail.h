@@ -1,8 +1,10 @@
-// engine_step_detail.h -- what the translation units of step() share (round 6: engine_step.hip was one 2 500-line file):
-//   engine_candidates.hip  split candidates: categorical cells on the device, sharded ranking, numeric thresholds (A3-A5)
+// engine_step_detail.h -- what the translation units of step() share:
+//   engine_candidates.hip  numeric split candidates: the threshold route and one function per route (A3, A4)
+//   engine_cat_candidates.hip  categorical split candidates: the device scan in stages, the forms of its result, the sharded ranking (A5);
+//                          cat_candidates_host.h has their host half (the reference's rule, the replay of its container), which needs no device
 //   engine_grow.hip        Engine::grow_tree: the choice of the growth path, the one-launch growth of RL-sized steps, the host tree's bookkeeping
 //   engine_grow_levels.hip Engine::grow_levels: the level loops and the final leaves (A6-A10); engine_grow_detail.h has what these two share
-//   engine_step.hip        Engine::step / Engine::fit, the host scan of categorical cells, the tree joining the ensemble (A1, A2, A10-A11), and
+//   engine_step.hip        Engine::step in stages / Engine::fit, the tree joining the ensemble (A1, A2, A10-A11), and
 //                          the stages step() shares with step_prepared(): run_grad_stats, prepare_numeric, grow_step_tree
 //   engine_prepared.hip    Engine::prepare_dataset / Engine::step_prepared: a batch binned once and stepped on many times
 //   engine_codes.hip       Engine::condition_bins / predict_continue_prepared: a data set's bin codes in the model's terms, the walk over them
@@ -16,7 +18,6 @@
 #include <numeric>
 #include <random>
 #include "cat_hash.h"
-#include "hash_order_replay.h"
 
 #include <algorithm>
 #include <atomic>
@@ -125,6 +126,41 @@ struct StepData {
     const int32_t *cols = nullptr;      // step_prepared(cols): feature f of this step is the model's feature cols[f] (its candidate weight; host, F entries)
 };
 
+// A view of the distinct cells a publish delivered (engine_cat_candidates.hip): hdr = [list overflow, hash collision, distinct cells, records
+// delivered]; per record its raw hash, feature, row of first occurrence and 128 bytes (in ordinary memory, or still in the pinned block), and
+// -- CatPub modes with statistics only -- kern::cat_rank's count and float32 total.  Row-sharded: the gathered global list (no first rows).
+struct CatList {
+    const int32_t *hdr, *feat, *first;
+    const uint64_t *hash;
+    const char *names;
+    const int32_t *count;
+    const float *total;
+    bool names_in_pinned;
+};
+// what a publish carries: the records; the records and the ranking statistics; only the statistics of records that a publish with the same
+// capacity has already delivered (their feature, first row, hash and cell stay where they are)
+enum class CatPub { Records, RecordsAndStats, StatsOnly };
+
+// Engine::numeric_thresholds: the batch and where its thresholds go; the routes, chosen once by Engine::threshold_route
+struct ThrArgs { const float *dobs; int N, F, B; long long n_global; const uint32_t *d_kt; float *d_thr; uint32_t *d_thrkeys; };
+enum class ThrRoute { Fixed, Uniform, Bisection, LdsSort, Radix, Sample };
+
+// Engine::step: the batch as the caller handed it over, and where its three inputs lie on the device
+struct StepInputs {
+    const float *obs; bool obs_dev; const char *cat; bool cat_dev; const float *grads; bool grads_dev;
+    int N, F, Fc;
+    const float *dobs = nullptr, *dgrads = nullptr;
+    const char *dcells = nullptr;
+};
+// Engine::categorical_stage: this step's candidates and classes, and where the class codes come from -- the scan's tables, a dictionary
+// on the device, or codes the host rules computed
+struct CatStage {
+    enum Codes { None, Table, Dict, Host } codes = None;
+    std::vector<CatCandidate> cands;
+    std::vector<int> classes;
+    std::vector<uint16_t> h_codes;
+};
+
 }  // namespace detail
 
 using detail::CatCandidate;
@@ -183,9 +219,7 @@ inline bool device_levels_requested() { return hooks::on(hooks::DEVICE_LEVELS); 
 void spin_until_published(volatile uint32_t *flag, uint32_t seq, hipStream_t s, const char *what);
 // split_candidate_generator.cpp:216-249 (engine_candidates.hip)
 std::vector<int64_t> quantile_target_ranks(long long n_global, int B);
-// A5 on the host / A10-A11 (engine_step.hip)
-void categorical_candidates(const char *hcat, const float *hgrads, int N, int Fc, int D, int B, std::vector<CatCandidate> &cat_cands,
-                            std::vector<uint16_t> &h_catcodes, std::vector<int> &cat_classes);
+// A10-A11 (engine_step.hip)
 void append_tree(Model &model, const std::vector<HNode> &nodes, const std::vector<int> &frontier, const std::vector<int64_t> &acc,
                  double leaf_scale, const std::vector<CatCandidate> &cat_cands);
 // Row subsets of a prepared data set (engine_prepared.hip).  checked_rows: device copy of an index vector, every entry known to lie in [0, n)

@@ -9,6 +9,11 @@ set_profiling(0) and once with set_profiling(2).  A line per run: the sha256 of 
   - (D, n_bins) = (17, 256), (24, 256), (31, 64): the wide and quad histogram kernels;  (40, 64), (63, 256): the run-time-D kernel at 2 features per block;
   - 5 categorical columns beside the 19 numeric ones;  257 rows (the small-step path);
   - oblivious growth with GBRL_HIP_DEVICE_LEVELS=1 (the device-side level planner), in a child process: a hook is read once per call, set before the start.
+Categorical candidates, once each behind the first pass ("categorical: "): the Fc=5 case on the host scan (GBRL_HIP_HOST_CATEGORICAL=1); 40 categories per
+column at n_bins 4 (more distinct cells than Fc * n_bins: the on-device ranking and the cut); no numeric column at all; 6 categories per column in the first
+step and 300 in the second (the tables regrow; at n_bins 64 the 1500 cells are ranked, at n_bins 512 the list is published again as it is); fit() with categorical columns (the candidates-only step and the dictionary form
+of the result).  The Quantile cases of the level-loop pass also under GBRL_HIP_QUANTILE_RADIX=1 and GBRL_HIP_QUANTILE_SAMPLE=1 ("radix: ", "sample: "), so
+that every threshold route is reached.
 A batch of 4100 rows is RL-sized: by default its statistics, preparation and whole tree growth run in the fused small-batch kernels (small_prep.hip,
 small_grow.hip) and the level loop's kernels -- histogram build / reduce, score, arg-max, resolve, partition, leaf sums, the planner -- never start.  So the
 whole grid runs again with GBRL_HIP_NO_SMALL_GROW=1 GBRL_HIP_NO_SMALL_PREP=1 GBRL_HIP_NO_SMALL_STATS=1 ("level loop"), which sends the same shapes through
@@ -50,6 +55,23 @@ LEVEL_LOOP = ("GBRL_HIP_NO_SMALL_GROW", "GBRL_HIP_NO_SMALL_PREP", "GBRL_HIP_NO_S
 PASSES = (("", ()), ("level loop: ", LEVEL_LOOP), ("bisection: ", LEVEL_LOOP + ("GBRL_HIP_FORCE_BISECTION",)))
 
 
+def tokens(seed, N, Fc, n_tokens):
+    """[N][Fc] S128 cells, n_tokens categories per column (cases.TOKENS stops at 32)."""
+    import numpy as np
+    names = np.array(["k%04d" % i for i in range(n_tokens)], dtype="S128")
+    return names[np.random.default_rng(seed).integers(0, n_tokens, size=(N, Fc))]
+
+
+def categorical_cases():
+    base = dict(seed=0, N=4100, F=19, Fc=5, D=8, depth=4, n_bins=64, score="L2", gen="Quantile", policy="greedy", trees=2)
+    yield dict(base, name="Fc=5 host scan"), {"GBRL_HIP_HOST_CATEGORICAL": "1"}
+    yield dict(base, name="overflow Fc=3 n_bins=4", Fc=3, n_bins=4, cells=[40, 40]), {}
+    yield dict(base, name="F=0 Fc=5", F=0), {}
+    yield dict(base, name="cardinality jump", cells=[6, 300]), {}
+    yield dict(base, name="cardinality jump n_bins=512", cells=[6, 300], n_bins=512), {}
+    yield dict(base, name="fit Fc=5", fit=True), {}
+
+
 def run(gbrl_amd, K, case, tag):
     import numpy as np
     X, Xc, G, y = K.make_inputs(case)
@@ -61,8 +83,11 @@ def run(gbrl_amd, K, case, tag):
         for o in K.optimizers(case):
             m.set_optimizer(**o)
         m.set_feature_mapping(np.arange(F + Fc, dtype=np.int32), np.array([True] * F + [False] * Fc, dtype=bool))
-        for _ in range(case["trees"]):
-            m.step(X, Xc, np.ascontiguousarray(G.copy()))
+        if case.get("fit"):
+            m.fit(X, Xc, np.ascontiguousarray(G.copy()), 3, False, "MultiRMSE")
+        for t in range(0 if case.get("fit") else case["trees"]):
+            cells = tokens(t, case["N"], Fc, case["cells"][t]) if "cells" in case else Xc
+            m.step(X, cells, np.ascontiguousarray(G.copy()))
         with tempfile.TemporaryDirectory() as d:
             p = os.path.join(d, "m.gbrl_model")
             assert m.save(p) == 0
@@ -88,6 +113,19 @@ def main(root, child):
         for case in cases():
             if case["gen"] == "Quantile" or "GBRL_HIP_FORCE_BISECTION" not in hooks:
                 run(gbrl_amd, K, case, tag)
+        if not hooks:
+            for case, env in categorical_cases():
+                os.environ.update(env)
+                run(gbrl_amd, K, case, "categorical: ")
+                for k in env:
+                    del os.environ[k]
+        if tag == "level loop: ":
+            for route, hook in (("radix: ", "GBRL_HIP_QUANTILE_RADIX"), ("sample: ", "GBRL_HIP_QUANTILE_SAMPLE")):
+                os.environ[hook] = "1"
+                for case in cases():
+                    if case["gen"] == "Quantile":
+                        run(gbrl_amd, K, case, route)
+                del os.environ[hook]
         sys.stdout.flush()
         status |= subprocess.run([sys.executable, os.path.abspath(__file__), root, "--device-levels"], env=dict(os.environ, GBRL_HIP_DEVICE_LEVELS="1")).returncode
     return status

@@ -642,3 +642,30 @@ def test_a_categorical_hash_clash_regrows_the_step_on_the_host_scan(monkeypatch)
     for k in a:
         assert np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes(), k
     assert pref.tobytes() == pred.tobytes()
+
+
+def test_a_model_that_has_clashed_keeps_to_the_host_scan_whatever_the_hook_says(monkeypatch):
+    """The clash of the test above with `GBRL_HIP_HOST_CATEGORICAL=0` set throughout and `GBRL_HIP_TEST_CAT_CLASH=1` left on from the second
+    step: the regrown step is a second pass inside step() that does not read the hooks again, and "this model has clashed" is a flag of
+    its own -- so the hook's 0 does not send the third and fourth steps back to the scan that clashed (they would be regrown too:
+    `cat_clash_redos` 3).  One redo, same ensemble and prediction as an undisturbed model, byte for byte."""
+    import gbrl_amd
+    case = _case("clash", seed=91, N=1200, F=5, Fc=3, D=2, depth=4, n_bins=32, policy="greedy", gen="Quantile", trees=4, n_tokens=6)
+    X, Xc, G, y = K.make_inputs(case)
+    monkeypatch.delenv("GBRL_HIP_TEST_CAT_CLASH", raising=False)
+    monkeypatch.delenv("GBRL_HIP_HOST_CATEGORICAL", raising=False)
+    ref = gbrl_amd.GBRL(**K.ctor_kwargs(case))
+    pref = np.asarray(K.drive(ref, case, X, Xc, G, y))
+    monkeypatch.setenv("GBRL_HIP_HOST_CATEGORICAL", "0")
+    m = gbrl_amd.GBRL(**K.ctor_kwargs(case))
+    m.set_profiling(2)
+    K.drive(m, dict(case, trees=1), X, Xc, G, y)         # first step: every cell is new, nothing pending
+    monkeypatch.setenv("GBRL_HIP_TEST_CAT_CLASH", "1")
+    for _ in range(3):
+        m.step(X, Xc, np.ascontiguousarray(G))           # second step: regrown on the host scan; third and fourth: the host scan, nothing pending
+    assert dict(m.last_phase_times()).get("cat_clash_redos", 0) == 1
+    pred = np.asarray(m.predict(X, Xc, 0, 0))
+    a, b = ref.get_ensemble_data(), m.get_ensemble_data()
+    for k in a:
+        assert np.asarray(a[k]).tobytes() == np.asarray(b[k]).tobytes(), k
+    assert pref.tobytes() == pred.tobytes()

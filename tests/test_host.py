@@ -306,6 +306,20 @@ def test_candidate_order_replay_equals_the_libstdcxx_container(tmp_path):
     assert out.returncode == 0 and "0 mismatches" in out.stdout, out.stdout + out.stderr
 
 
+def test_categorical_host_core_equals_the_reference_rule_on_random_batches(tmp_path):
+    """cat_candidates_host.h without a device (tests/cxx/cat_candidates_check.cpp): what a scan would publish for 160 random batches -- 1 to
+    3000 rows, 1 to 8 columns, cardinalities from 1 to a cell per row, cells that differ only behind the first NUL, most with more distinct
+    cells than Fc * n_bins -- goes through first_occurrence_order, one CatMemory's replay (remembered cells, deferred comparisons, forget),
+    keep_top_by_mean and assign_classes; candidates (feature, bytes, class, order) and per-cell codes equal categorical_candidates' on the
+    same batch, and a forced pair of different cells under one (feature, hash) is reported by verify_pending."""
+    import subprocess
+    exe = tmp_path / "cat_candidates_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "gbrl_amd", "csrc"), os.path.join(ROOT, "tests", "cxx", "cat_candidates_check.cpp"),
+                    "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and " 0 mismatches" in out.stdout, out.stdout + out.stderr
+
+
 def test_register_tile_asm_header_is_current_and_the_compiler_keeps_out_of_the_bank(tmp_path):
     """predict_reg.hip keeps a row tile in a bank of VGPRs that the compiler must never allocate (amdgpu_num_vgpr caps it below the
     bank; the bank is only named in clobber lists).  (1) The generated assembly text is the generator's current output.  (2) Audit of
