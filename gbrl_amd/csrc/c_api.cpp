@@ -1084,6 +1084,29 @@ int gbrl_hip_shap_plan(int max_depth, int output_dim, int *threads, int *samples
     return GBRL_HIP_OK;
 }
 
+int gbrl_hip_hist_plan(int n_classes, int output_dim, int n_rows, int fg_in, gbrl_hip_hist_plan_t *plan) {
+    if (!plan || n_classes < 1 || n_classes > 65535 || output_dim < 1 || n_rows < 1 || fg_in < 0 || fg_in > 16 || (fg_in & (fg_in - 1)) != 0) return GBRL_HIP_E_INVALID;
+    return guarded([&] {
+        const int FG = fg_in ? fg_in : gbrl::kern::hist_feature_group(n_classes, output_dim);
+        const gbrl::kern::HistPlan r = gbrl::kern::hist_plan(output_dim, FG, n_rows);
+        plan->fg = FG; plan->kind = r.kind; plan->param = r.param; plan->pipe = r.pipe; plan->direct_ok = r.direct_ok; plan->countless_ok = r.countless_ok;
+        plan->hist_lds_bytes = gbrl::kern::hist_lds_bytes(n_classes, output_dim, FG);
+    });
+}
+
+int gbrl_hip_hist_probe(gbrl_hip_hist_probe_t *a) {
+    if (!a) return GBRL_HIP_E_INVALID;
+    return guarded([&] {
+        gbrl::kern::HistProbe p{a->codes, a->qg, a->rows, a->chunks, a->root_le, a->slot_map, a->hist, a->hist_elems, a->root_n, a->n_rows, a->output_dim, a->m, a->n_chunks,
+                                a->n_nodes, a->n_feature_slots, a->fg, a->n_classes, a->mode, a->count_rows, a->root_F, a->root_B, a->chunks_per_slot, a->scatter_fs, 0, 0, 0, 0, 0};
+        const char *why = "";
+        const int rc = gbrl::kern::hist_selftest(p, &why);
+        if (rc == gbrl::kern::kHistProbeInvalid) throw gbrl::InvalidArgument(why);
+        if (rc != gbrl::kern::kHistProbeOk) throw gbrl::HipError("histogram kernels failed (no HIP device?)");
+        a->kind = p.kind; a->param = p.param; a->pipe = p.pipe; a->counted = p.counted; a->wrote_direct = p.direct;
+    });
+}
+
 int gbrl_hip_cat_rank_stats(const char *cells, int n, int n_cat, const float *grads, int output_dim, int cap, int32_t *feature,
                             int32_t *first_row, int32_t *count, float *total, int *n_distinct) {
     if (!cells || !grads || !feature || !first_row || !count || !total || !n_distinct || n < 1 || n_cat < 1 || output_dim < 1 || cap < 1) return GBRL_HIP_E_INVALID;

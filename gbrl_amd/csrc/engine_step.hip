@@ -264,11 +264,8 @@ void Engine::grow_step_tree(const StepData &sd, std::vector<HNode> &nodes, std::
     const int n_slots = F + Fc;
     int NB = F > 0 ? B + 1 : 1;
     for (int c = 0; c < Fc; ++c) NB = std::max(NB, cat_classes[c] + 1);
-    int FG = 16;
-    while (FG > 1 && kern::hist_lds_bytes(NB, D, FG) > 160 * 1024 - 512) FG >>= 1;
-    // more than 16 outputs: k_hist_build_wide spreads the D + 1 fields of a row over the 16 / FG parts of a 16-lane row (<= 16 each)
-    while (D > 16 && FG > 4 && (16 / FG) * 16 < D + 1) FG >>= 1;
-    if (kern::hist_lds_bytes(NB, D, FG) > 160 * 1024 - 512)
+    const int FG = kern::hist_feature_group(NB, D);
+    if (kern::hist_lds_bytes(NB, D, FG) > kern::kHistLdsLimit)
         throw Unsupported("(classes per feature) x (output_dim + 1) does not fit the 160 KiB LDS");
     if (static_cast<size_t>(NB + 2) * (D + 1) * 8 > 150 * 1024) throw Unsupported("score kernel LDS limit");
     const int Fp = ((n_slots + FG - 1) / FG) * FG;

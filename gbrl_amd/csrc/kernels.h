@@ -266,6 +266,29 @@ bool hist_build(const uint16_t *codes, int n_rows, const int32_t *qg, int D, con
                 bool count_rows = true /* false: the rows' count field is NOT accumulated (FG == 16, D <= 16 kernels only; returns as if
                 true otherwise -- check hist_countless_supported): the root's class counts come from the selection, hist_reduce root_le */);
 bool hist_countless_supported(int D, int FG, int n_rows);
+constexpr size_t kHistLdsLimit = 160 * 1024 - 512;   // the largest LDS tile (hist_lds_bytes) a build block may ask for
+// Features per block (16, 8, 4, 2 or 1) of a step with NB classes per feature and D outputs: the largest group whose LDS tile fits, halved further
+// while more than 16 outputs leave a 16-lane row too few parts for the D + 1 fields.  The FG = 1 tile may still exceed kHistLdsLimit: callers check.
+int hist_feature_group(int NB, int D);
+// diagnostics (gbrl_hip_hist_plan): what hist_build does with a shape -- the route's kind (0 run-time D, 1 compile-time D, 2 wide, 3 quad), its
+// parameter and abilities, read from the same rule and the same hooks as a launch; no HIP call
+struct HistPlan { int kind, param; bool pipe, direct_ok, countless_ok; };
+HistPlan hist_plan(int D, int FG, int n_rows);
+// diagnostics (gbrl_hip_hist_probe): one hist_build (+ hist_reduce) on host arrays.  Everything is validated on the host before the first HIP call.
+struct HistProbe {
+    const uint16_t *codes;     // [ceil(Fp / 16)][n_rows][16], Fp = n_fslots rounded up to FG
+    const int32_t *qg;         // [n_rows][D]
+    const int32_t *rows;       // [m]
+    const int32_t *chunks;     // [n_chunks][3] = (slot, start, len): slots ascending; behind the last entry with rows, len = 0 entries only
+    const uint32_t *root_le;   // nullable [root_F][root_B]
+    const int32_t *slot_map;   // nullable [n_nodes]
+    int64_t *hist;             // in: the caller's sentinel; out: what the kernels stored over it.  hist_elems values
+    long long hist_elems, root_n;
+    int n_rows, D, m, n_chunks, n_nodes, n_fslots, FG, NB, mode /*0: partials + hist_reduce, 1: HistDirect*/, count_rows, root_F, root_B, chunks_per_slot, scatter_fs;
+    int kind, param, pipe, counted, direct;   // out: the kernel launched (route kind and parameter, pipelined form, COUNT form), and whether the build stored the histograms itself
+};
+enum { kHistProbeOk = 0, kHistProbeInvalid = 1, kHistProbeDevice = 2 };
+int hist_selftest(HistProbe &p, const char **why /*what was refused (static text)*/);
 // hist[slot_map ? slot_map[k] : k] = sum of the partials of chunk-slot k
 void hist_reduce(const int32_t *partials, const int32_t *slot_chunk_begin /*[n_slots+1]*/, const int32_t *slot_map, int n_slots,
                  int n_groups, int FG, int NB, int D, int Fp, int64_t *hist, hipStream_t s,

@@ -1,13 +1,16 @@
 // step_hist_build.hip -- the split-score histogram build of GBRL::step: the three LDS-atomic kernels (compile-time / run-time D at 16 features
-// per block, "wide" at 8, "quad" at 4), the one rule that routes a shape to a kernel, and the one launcher.  The stand-alone harnesses
+// per block, "wide" at 8, "quad" at 4), the one rule that routes a shape to a kernel, the one launcher, and the diagnostics that show both to the
+// tests (hist_plan, hist_selftest).  The stand-alone harnesses
 // scripts/hist_bench.hip and scripts/hist_sorted_bench.hip include this file.  (The arithmetic policy of these integer sums: step_score.hip.)
 #include "kernels.h"
 #include "hooks.h"
 
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <type_traits>
 #include <utility>
+#include <vector>
 
 namespace gbrl {
 namespace kern {
@@ -460,39 +463,183 @@ bool dispatch_int(int v, F &&f) { return dispatch_int<Lo>(v, f, std::make_intege
 bool hist_direct_supported(int FG) { return hist_route(1, FG, 1).direct_ok; }   // (by FG alone)
 bool hist_countless_supported(int D, int FG, int n_rows) { return hist_route(D, FG, n_rows).countless_ok; }
 
-bool hist_build(const uint16_t *codes, int n_rows, const int32_t *qg, int D, const int32_t *rows, const Chunk *chunks,
-                int n_chunks, int n_groups, int FG, int NB, int32_t *partials, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
-                const HistDirect *direct, bool count_rows) {
-    int shift = 0;
-    while ((1 << shift) < FG) ++shift;
-    const HistArgs a{codes, n_rows, qg, D, rows, chunks, n_chunks, n_groups, FG, shift, NB, partials, direct ? *direct : HistDirect{}, hist_lds_bytes(NB, D, FG),
-                     s, ev_start, ev_stop};
+int hist_feature_group(int NB, int D) {
+    int FG = 16;
+    while (FG > 1 && hist_lds_bytes(NB, D, FG) > kHistLdsLimit) FG >>= 1;
+    // more than 16 outputs: k_hist_build_wide spreads the D + 1 fields of a row over the 16 / FG parts of a 16-lane row (<= 16 each)
+    while (D > 16 && FG > 4 && (16 / FG) * 16 < D + 1) FG >>= 1;
+    return FG;
+}
+
+HistPlan hist_plan(int D, int FG, int n_rows) {
     const HistRoute r = hist_route(D, FG, n_rows);
-    const bool direct_out = a.direct.hist != nullptr;   // what k_hist_build answers; the wide and quad kernels only write partials
+    return HistPlan{static_cast<int>(r.kind), r.param, r.pipe, r.direct_ok, r.countless_ok};
+}
+
+namespace {
+
+// What launch_route launched: the route of the kernel that ran (the one asked for, unless its parameter lies outside the instantiations) with
+// `pipe` = the PIPE form ran, and whether the kernel accumulates the count field (COUNT).
+struct HistLaunched { HistRoute route; bool counted; };
+HistLaunched launch_route(const HistArgs &a, const HistRoute &r, bool count_rows) {
     switch (r.kind) {
-    case HistRoute::FIXED_D:
+    case HistRoute::FIXED_D: {
+        bool pipe = false, counted = true;
         if (dispatch_int<1, 16>(r.param, [&](auto c) {
                 constexpr int DD = decltype(c)::value;
-                if (r.pipe && !count_rows) launch_hist<k_hist_build<DD, GBRL_HIST_U, true, HistLoads, false>>(a);
-                else if (r.pipe) launch_hist<k_hist_build<DD, GBRL_HIST_U, true>>(a);
+                if (r.pipe && !count_rows) { launch_hist<k_hist_build<DD, GBRL_HIST_U, true, HistLoads, false>>(a); pipe = true; counted = false; }
+                else if (r.pipe) { launch_hist<k_hist_build<DD, GBRL_HIST_U, true>>(a); pipe = true; }
                 else launch_hist<k_hist_build<DD, GBRL_HIST_U, false>>(a);
-            })) return direct_out;
+            })) {
+            HistRoute ran = r;
+            ran.pipe = pipe;
+            return {ran, counted};
+        }
         break;
+    }
     case HistRoute::WIDE:
-        if (dispatch_int<1, 16>(r.param, [&](auto c) { launch_hist<k_hist_build_wide<2, decltype(c)::value, 4>>(a); })) return false;
+        if (dispatch_int<1, 16>(r.param, [&](auto c) { launch_hist<k_hist_build_wide<2, decltype(c)::value, 4>>(a); })) return {r, true};
         break;
     case HistRoute::QUAD:
         if (dispatch_int<1, 16>(r.param, [&](auto c) {
                 constexpr int R = decltype(c)::value;
                 launch_hist<k_hist_build_quad<R, (R <= 8 ? 4 : 2)>>(a);
-            })) return false;
+            })) return {r, true};
         break;
     case HistRoute::GENERIC:
         break;
     }
     // the run-time-D kernel: the generic route, and the way out should a route's parameter ever lie outside its kernel's instantiations
     launch_hist<k_hist_build<0, 4, false>>(a);
+    return {HistRoute{HistRoute::GENERIC, 0, false, r.direct_ok, false}, true};
+}
+
+HistLaunched hist_build_routed(const uint16_t *codes, int n_rows, const int32_t *qg, int D, const int32_t *rows, const Chunk *chunks,
+                            int n_chunks, int n_groups, int FG, int NB, int32_t *partials, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
+                            const HistDirect *direct, bool count_rows, bool *direct_out) {
+    int shift = 0;
+    while ((1 << shift) < FG) ++shift;
+    const HistArgs a{codes, n_rows, qg, D, rows, chunks, n_chunks, n_groups, FG, shift, NB, partials, direct ? *direct : HistDirect{}, hist_lds_bytes(NB, D, FG),
+                     s, ev_start, ev_stop};
+    const HistLaunched ran = launch_route(a, hist_route(D, FG, n_rows), count_rows);
+    // k_hist_build answers a HistDirect; the wide and quad kernels only write partials
+    *direct_out = a.direct.hist != nullptr && (ran.route.kind == HistRoute::FIXED_D || ran.route.kind == HistRoute::GENERIC);
+    return ran;
+}
+
+}  // namespace
+
+bool hist_build(const uint16_t *codes, int n_rows, const int32_t *qg, int D, const int32_t *rows, const Chunk *chunks,
+                int n_chunks, int n_groups, int FG, int NB, int32_t *partials, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop,
+                const HistDirect *direct, bool count_rows) {
+    bool direct_out = false;
+    (void)hist_build_routed(codes, n_rows, qg, D, rows, chunks, n_chunks, n_groups, FG, NB, partials, s, ev_start, ev_stop, direct, count_rows, &direct_out);
     return direct_out;
+}
+
+// ------------------------------------------------------------------------------------------------------------ diagnostics
+
+// gbrl_hip_hist_probe: host arrays in, the int64 histograms out -- one hist_build, and hist_reduce behind it unless the build stored the histograms
+// itself.  The caller's `hist` goes to the device first and comes back afterwards, so a cell no kernel stored keeps the caller's value; the partials
+// start from a non-zero pattern, so a partial that the reduce reads and no block wrote shows.  Every index a kernel will form is checked here first.
+int hist_selftest(HistProbe &p, const char **why) {
+    const auto refuse = [&](const char *text) { *why = text; return static_cast<int>(kHistProbeInvalid); };
+    *why = "";
+    if (!p.codes || !p.qg || !p.hist || (p.m > 0 && !p.rows) || (p.n_chunks > 0 && !p.chunks)) return refuse("hist_probe: null array");
+    if (p.n_rows < 1 || p.n_rows > (1 << 26) || p.D < 1 || p.D > 512 || p.m < 0 || p.m > (1 << 24) || p.n_chunks < 0 || p.n_chunks > (1 << 16) || p.n_nodes < 1 ||
+        p.n_nodes > 65535 /* hist_reduce: one grid z per node */ || p.n_fslots < 1 || p.n_fslots > 4096 || p.NB < 1 || p.NB > 65535 || p.chunks_per_slot < 1 || p.scatter_fs < 0)
+        return refuse("hist_probe: a size is out of range");
+    const int FG = p.FG, NB = p.NB, D = p.D;
+    if (FG != 1 && FG != 2 && FG != 4 && FG != 8 && FG != 16) return refuse("hist_probe: FG must be 1, 2, 4, 8 or 16");
+    if (hist_lds_bytes(NB, D, FG) > kHistLdsLimit) return refuse("hist_probe: (classes per feature) x (output_dim + 1) x FG does not fit the LDS");
+    if (p.mode != 0 && p.mode != 1) return refuse("hist_probe: mode must be 0 or 1");
+    const HistRoute route = hist_route(D, FG, p.n_rows);
+    const int Fp = ((p.n_fslots + FG - 1) / FG) * FG, n_groups = Fp / FG;
+    const size_t feat = static_cast<size_t>(NB) * (D + 1), n_acc = feat * FG;
+    const size_t n_codes = static_cast<size_t>((Fp + kCodeGroup - 1) / kCodeGroup) * p.n_rows * kCodeGroup;
+    if (n_codes > (size_t{1} << 28) || static_cast<size_t>(p.n_rows) * D > (size_t{1} << 28)) return refuse("hist_probe: a size is out of range");
+    for (size_t i = 0; i < n_codes; ++i)
+        if (p.codes[i] >= NB) return refuse("hist_probe: a class code is not below n_classes");
+    for (int i = 0; i < p.m; ++i)
+        if (p.rows[i] < 0 || p.rows[i] >= p.n_rows) return refuse("hist_probe: a row index is outside [0, n_rows)");
+    // chunk table: the entries with rows first, slots ascending; behind them only len = 0 entries (what the device planner leaves)
+    int n_real = 0;
+    for (int i = 0; i < p.n_chunks; ++i) {
+        const int32_t slot = p.chunks[3 * i], start = p.chunks[3 * i + 1], len = p.chunks[3 * i + 2];
+        if (slot < 0 || slot >= p.n_nodes || start < 0 || len < 0 || start > p.m || len > p.m - start) return refuse("hist_probe: a chunk lies outside the row list or the nodes");
+        if (len > 0) n_real = i + 1;
+    }
+    for (int i = 1; i < n_real; ++i)
+        if (p.chunks[3 * i] < p.chunks[3 * (i - 1)]) return refuse("hist_probe: chunk slots must ascend");
+    if (p.mode == 1) {
+        if (!route.direct_ok) return refuse("hist_probe: this FG has no direct store");
+        if (p.n_chunks != p.n_nodes) return refuse("hist_probe: the direct store needs every node to be one chunk");
+        for (int i = 0; i < p.n_chunks; ++i)
+            if (p.chunks[3 * i] != i) return refuse("hist_probe: the direct store needs every node to be one chunk");
+        if (p.scatter_fs > 0 || p.root_le || !p.count_rows) return refuse("hist_probe: the direct store has no scatter layout and no root counts");
+    } else {
+        for (int i = 0; i < n_real; ++i)
+            if (p.chunks[3 * i + 2] == 0) return refuse("hist_probe: an empty chunk in front of a chunk with rows (a node without rows has no chunk)");
+    }
+    if ((!p.count_rows || p.root_le) && !route.countless_ok) return refuse("hist_probe: this shape has no count-less build");
+    if (p.root_le && (p.root_F < 0 || p.root_F > Fp || p.root_B < 1 || p.root_B > 65534 || p.root_n < 0)) return refuse("hist_probe: root_le sizes out of range");
+    // the histogram buffer: node slots [n_hist_slots][Fp][class][D+1], or the scatter layout [ceil(Fp / fs)][n_nodes][fs][class][D+1]
+    if (p.hist_elems < 1) return refuse("hist_probe: hist_elems does not match the layout");
+    if (p.scatter_fs > 0) {
+        const size_t want = static_cast<size_t>((Fp + p.scatter_fs - 1) / p.scatter_fs) * p.n_nodes * p.scatter_fs * feat;
+        if (static_cast<size_t>(p.hist_elems) != want) return refuse("hist_probe: hist_elems does not match the layout");
+    } else if (static_cast<size_t>(p.hist_elems) % (Fp * feat) != 0) {
+        return refuse("hist_probe: hist_elems does not match the layout");
+    }
+    const size_t n_hist_slots = p.scatter_fs > 0 ? static_cast<size_t>(p.n_nodes) : static_cast<size_t>(p.hist_elems) / (Fp * feat);
+    if (p.slot_map) {
+        std::vector<char> seen(n_hist_slots, 0);
+        for (int k = 0; k < p.n_nodes; ++k) {
+            const int32_t t = p.slot_map[k];
+            if (t < 0 || static_cast<size_t>(t) >= n_hist_slots || seen[t]) return refuse("hist_probe: slot_map must name distinct histogram slots");
+            seen[t] = 1;
+        }
+    } else if (n_hist_slots < static_cast<size_t>(p.n_nodes)) {
+        return refuse("hist_probe: hist_elems does not match the layout");
+    }
+    const size_t n_part = static_cast<size_t>(std::max(1, p.n_chunks)) * n_groups * n_acc;
+    if (n_part > (size_t{1} << 29) || static_cast<size_t>(p.hist_elems) > (size_t{1} << 28)) return refuse("hist_probe: a size is out of range");
+
+    // ---- device half
+    std::vector<Chunk> ck(std::max(1, p.n_chunks), Chunk{0, 0, 0, 0});
+    for (int i = 0; i < p.n_chunks; ++i) ck[i] = Chunk{p.chunks[3 * i], p.chunks[3 * i + 1], p.chunks[3 * i + 2], 0};
+    std::vector<int32_t> begin(p.n_nodes + 1, 0);   // begin[k] = entries with rows whose slot is below k
+    for (int i = 0; i < n_real; ++i) ++begin[ck[i].slot + 1];
+    for (int k = 0; k < p.n_nodes; ++k) begin[k + 1] += begin[k];
+    struct Dev { void *p = nullptr; ~Dev() { if (p) (void)hipFree(p); } };
+    Dev dcodes, dqg, drows, dck, dbegin, dle, dmap, dhist, dpart;
+    const auto up = [](Dev &d, const void *src, size_t bytes) {
+        if (hipMalloc(&d.p, std::max<size_t>(16, bytes)) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return bytes == 0 || hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!up(dcodes, p.codes, n_codes * sizeof(uint16_t)) || !up(dqg, p.qg, sizeof(int32_t) * p.n_rows * D) || !up(drows, p.rows, sizeof(int32_t) * p.m) ||
+        !up(dck, ck.data(), sizeof(Chunk) * ck.size()) || !up(dbegin, begin.data(), sizeof(int32_t) * begin.size()) ||
+        !up(dhist, p.hist, sizeof(int64_t) * p.hist_elems) || (p.root_le && !up(dle, p.root_le, sizeof(uint32_t) * p.root_F * p.root_B)) ||
+        (p.slot_map && !up(dmap, p.slot_map, sizeof(int32_t) * p.n_nodes)))
+        return kHistProbeDevice;
+    if (hipMalloc(&dpart.p, n_part * sizeof(int32_t)) != hipSuccess || hipMemset(dpart.p, 0x5b, n_part * sizeof(int32_t)) != hipSuccess) { (void)hipGetLastError(); return kHistProbeDevice; }
+    HistDirect hd;
+    hd.hist = static_cast<int64_t *>(dhist.p); hd.slot_map = static_cast<const int32_t *>(dmap.p); hd.Fp = Fp;
+    bool wrote = false;
+    HistLaunched ran{route, p.count_rows != 0 || !route.pipe};   // (no chunk, no launch: what a launch would take)
+    if (p.n_chunks > 0)
+        ran = hist_build_routed(static_cast<const uint16_t *>(dcodes.p), p.n_rows, static_cast<const int32_t *>(dqg.p), D, static_cast<const int32_t *>(drows.p),
+                                static_cast<const Chunk *>(dck.p), p.n_chunks, n_groups, FG, NB, static_cast<int32_t *>(dpart.p), nullptr, nullptr, nullptr,
+                                p.mode == 1 ? &hd : nullptr, p.count_rows != 0, &wrote);
+    if (hipGetLastError() != hipSuccess /* a refused launch */ || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return kHistProbeDevice; }
+    if (!wrote) {
+        hist_reduce(static_cast<const int32_t *>(dpart.p), static_cast<const int32_t *>(dbegin.p), static_cast<const int32_t *>(dmap.p), p.n_nodes, n_groups, FG, NB, D, Fp,
+                    static_cast<int64_t *>(dhist.p), nullptr, p.chunks_per_slot, p.scatter_fs, static_cast<const uint32_t *>(dle.p), p.root_F, p.root_B, p.root_n);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { (void)hipGetLastError(); return kHistProbeDevice; }
+    }
+    if (hipMemcpy(p.hist, dhist.p, sizeof(int64_t) * p.hist_elems, hipMemcpyDeviceToHost) != hipSuccess) return kHistProbeDevice;
+    p.kind = static_cast<int>(ran.route.kind); p.param = ran.route.param; p.pipe = ran.route.pipe ? 1 : 0; p.counted = ran.counted ? 1 : 0; p.direct = wrote ? 1 : 0;
+    return kHistProbeOk;
 }
 
 }  // namespace kern

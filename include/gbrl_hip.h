@@ -959,6 +959,57 @@ int gbrl_hip_cat_rank_stats(const char *cells, int n, int n_cat, const float *gr
  * outputs do not fit the block): tree_shap / ensemble_shap then evaluate on the host.  No HIP call: it runs without a device. */
 int gbrl_hip_shap_plan(int max_depth, int output_dim, int *threads, int *samples_per_block);
 
+/* Diagnostics for the tests: what a step with `n_classes` classes per feature (n_bins + 1, or the largest categorical class count + 1) and
+ * `output_dim` outputs on `n_rows` rows does in its split-score histogram build (csrc/step_hist_build.hip).  fg_in = 0: fg is the engine's own
+ * choice of features per block (kern::hist_feature_group); 1, 2, 4, 8 or 16: used as given.  The rest is the answer of the one rule every
+ * launch goes through (hist_route), hooks GBRL_HIP_HIST_GENERIC and GBRL_HIP_HIST_PIPE read as a real call reads them:
+ *   kind   0 the run-time-D kernel, 1 k_hist_build<D> (compile-time D), 2 k_hist_build_wide<2, H>, 3 k_hist_build_quad<R>
+ *   param  kind 1: D;  kind 2: H = ceil((D + 1) / 2);  kind 3: R = ceil((D + 1) / 4);  kind 0: 0
+ *   pipe   kind 1 only: the software-pipelined main loop
+ *   direct_ok     a block may store its node's int64 histogram itself (every node one chunk)
+ *   countless_ok  a build that leaves the count field out exists (the root's counts then come from root_le)
+ *   hist_lds_bytes  the LDS tile of one block, n_classes * (output_dim + 1) * fg * 4; a step needs it to be at most 160 KiB - 512
+ * No HIP call: it runs without a device.  Nothing in the product calls it. */
+typedef struct gbrl_hip_hist_plan_t {
+    int fg, kind, param, pipe, direct_ok, countless_ok;
+    size_t hist_lds_bytes;
+} gbrl_hip_hist_plan_t;
+int gbrl_hip_hist_plan(int n_classes, int output_dim, int n_rows, int fg_in, gbrl_hip_hist_plan_t *plan);
+
+/* Diagnostics for the tests: ONE histogram build on arrays given explicitly, and the reduce behind it -- the kernels of csrc/step_hist_build.hip
+ * and csrc/step_hist_reduce.hip exactly as a step launches them.  Host pointers.  With Fp = n_feature_slots rounded up to a multiple of fg:
+ *   codes   uint16 [ceil(Fp / 16)][n_rows][16]   the class of every (row, feature slot); every value below n_classes, padding included
+ *   qg      int32  [n_rows][output_dim]          the quantised gradients
+ *   rows    int32  [m]                           the row list (row indices, repeats allowed)
+ *   chunks  int32  [n_chunks][3]                 (node, start, len): rows[start .. start + len) belong to `node`.  Nodes ascending; a node without
+ *                                                rows has no entry (mode 0).  Entries with len = 0 may follow the last entry that has rows.
+ *   mode    0: every chunk's int32 partial sums, then hist_reduce.  1: HistDirect -- entry i is ALL of node i (len 0 included, n_chunks = n_nodes)
+ *              and the build stores the histograms; only where the plan says direct_ok.
+ *   count_rows  0: the build without the count field (only where the plan says countless_ok)
+ *   root_le     nullable uint32 [root_F][root_B], #{keys <= threshold}: the count of class c of a feature below root_F becomes
+ *               le[c] - le[c-1] (class root_B: root_n - le[root_B-1]); only where the plan says countless_ok
+ *   chunks_per_slot   below 48: one thread per element sums a node's chunks; from 48: four
+ *   scatter_fs  > 0: hist is the send layout [ceil(Fp / fs)][n_nodes][fs][n_classes][output_dim + 1] of a reduce-scatter by feature
+ *   slot_map    nullable int32 [n_nodes]: node k's histogram goes to slot slot_map[k] (distinct)
+ *   hist        int64 [hist_elems]: [slots][Fp][n_classes][output_dim + 1] (field output_dim = the count), slots >= n_nodes or what slot_map
+ *               names -- or the scatter layout.  Copied to the device before the kernels run and back afterwards: a cell that no kernel stored
+ *               keeps the caller's value.  The partial sums start from a non-zero pattern.
+ * Out, of the kernel that ran: kind, param, pipe (as gbrl_hip_hist_plan), counted (1: it accumulates the count field); and wrote_direct.
+ * n_nodes <= 65535.
+ * Everything is checked on the host before the first HIP call -- codes, row indices, chunk ranges, fg, the LDS tile, the modes against the plan,
+ * slot_map, hist_elems against the layout: GBRL_HIP_E_INVALID, and no device is touched.  Nothing in the product calls it. */
+typedef struct gbrl_hip_hist_probe_t {
+    const uint16_t *codes;
+    const int32_t *qg, *rows, *chunks;
+    const uint32_t *root_le;
+    const int32_t *slot_map;
+    int64_t *hist;
+    long long hist_elems, root_n;
+    int n_rows, output_dim, m, n_chunks, n_nodes, n_feature_slots, fg, n_classes, mode, count_rows, root_F, root_B, chunks_per_slot, scatter_fs;
+    int kind, param, pipe, counted, wrote_direct;
+} gbrl_hip_hist_probe_t;
+int gbrl_hip_hist_probe(gbrl_hip_hist_probe_t *args);
+
 /* ---- device / stream contract (new; the reference pins everything to device 0 and the null stream, cuda_types.cu:32-106) -- */
 /* The device the model computes on: the ordinal given at creation, or -- for -1 -- the calling thread's current device at the
  * first call that needs it (it is latched by this call too).  -1 when no HIP device is usable.  A caller that hands out

@@ -6,7 +6,8 @@
 //     ([pair][row][2][16] instead of [group][row][16]) -- timing only: the same buffer read at other addresses, modulo the class count
 //   5 ROW-MAJOR layout (round 6): [row][128] uint16 -- a gathered row's eight 32-byte records are the two 128-byte lines of that row, shared by the
 //     eight group blocks of a chunk through their XCD's L2, instead of one line per group with three other rows' records in it -- timing only
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 -I gbrl_amd/csrc [-DVARIANT=n] scripts/hist_bench.hip gbrl_amd/csrc/hooks.cpp -o scripts/bin/hist_bench
+// hipcc --offload-arch=gfx950 -O3 -std=c++17 -I gbrl_amd/csrc [-DVARIANT=n] scripts/hist_bench.hip gbrl_amd/csrc/step_hist_reduce.hip gbrl_amd/csrc/hooks.cpp -o scripts/bin/hist_bench
+// (step_hist_reduce.hip: the diagnostic kern::hist_selftest of the included file calls hist_reduce)
 #include "../gbrl_amd/csrc/step_hist_build.hip"
 #ifndef VARIANT
 #define VARIANT 0

@@ -1,6 +1,6 @@
 // Microbenchmark: the sorted-run, register-accumulating histogram kernel (gbrl_amd/csrc/hist_sorted.h)
 // against the production LDS-atomic kernel k_hist_build on the same inputs, partials compared bit for bit.
-// hipcc --offload-arch=gfx950 -O3 -std=c++17 -I gbrl_amd/csrc scripts/hist_sorted_bench.hip gbrl_amd/csrc/hooks.cpp -o scripts/bin/hist_sorted_bench
+// hipcc --offload-arch=gfx950 -O3 -std=c++17 -I gbrl_amd/csrc scripts/hist_sorted_bench.hip gbrl_amd/csrc/step_hist_reduce.hip gbrl_amd/csrc/hooks.cpp -o scripts/bin/hist_sorted_bench
 //   hist_sorted_bench [frac=1] [chunk_rows=32768] [skew=0]
 //     frac > 1: a gathered subset of N / frac rows (levels >= 1); skew = 1: class sizes far from uniform (codes ~ u^3)
 #include "../gbrl_amd/csrc/step_hist_build.hip"
