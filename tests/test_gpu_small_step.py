@@ -22,7 +22,8 @@ pytestmark = pytest.mark.gpu
 HOOKS = ("GBRL_HIP_NO_SMALL_STATS", "GBRL_HIP_SORT_NO_CODES", "GBRL_HIP_NO_DIRECT_HIST", "GBRL_HIP_NO_SMALL_GROW", "GBRL_HIP_NO_SMALL_PREP")
 
 
-def _grow(case, monkeypatch, env):
+def _grow(case, monkeypatch, env, phases=False):
+    """The ensemble and the predictions of the case under `env`; with `phases`, also the phase table of one more step (taken after both were read)."""
     import gbrl_amd
     for k in HOOKS + ("GBRL_HIP_SMALL_GROW_BLOCKS",):
         monkeypatch.delenv(k, raising=False)
@@ -30,8 +31,14 @@ def _grow(case, monkeypatch, env):
         monkeypatch.setenv(k, v)
     X, Xc, G, y = K.make_inputs(case)
     m = gbrl_amd.GBRL(**K.ctor_kwargs(case))
+    if phases:
+        m.set_profiling(2)
     pred = K.drive(m, case, X, Xc, G, y)
-    return m.get_ensemble_data(), np.asarray(pred)
+    if not phases:
+        return m.get_ensemble_data(), np.asarray(pred)
+    ens, pred = {k: np.array(v) for k, v in m.get_ensemble_data().items()}, np.array(pred)
+    m.step(X, Xc, np.ascontiguousarray(G))     # (drive ends with a predict: the phase table is the last call's)
+    return ens, pred, dict(m.last_phase_times())
 
 
 @pytest.mark.parametrize("N", [2, 37, 256, 1000, 4096])
@@ -103,21 +110,34 @@ SMALL_GROW_SHAPES = [
 @pytest.mark.parametrize("shape", SMALL_GROW_SHAPES, ids=lambda t: "-".join(str(x) for x in t))
 def test_one_launch_growth_keeps_every_bit(shape, N, monkeypatch):
     """The tree of `k_small_grow` against the level loop's: every array of the ensemble and the predictions, byte for byte.  4097 and 8192
-    rows take the int64 LDS accumulators, 1 .. 3 rows mostly empty nodes, depth 8 the largest node table."""
+    rows take the int64 LDS accumulators, 1 .. 3 rows mostly empty nodes, depth 8 the largest node table.  At 4096 and 8192 rows the
+    256-bin oblivious shape holds 14 and 6 of its 32 last-level nodes' histograms in LDS at a time (`sg_layout`), so the node-batch loop
+    runs more than once.
+
+    The same bytes prove nothing about the kernel when it handed the tree to the level loop (a failed launch, an abandoned grid barrier), so the
+    default run and the 3-block run also show that it did not: no fallback, and a step that had candidates to score (`score_select` is the
+    level loop's phase for them) ran the one launch -- every shape here fits the kernel's LDS (`small_grow_supported`)."""
     policy, score, gen, D, F, Fc, B, depth, mdl = shape
     case = dict(name="sg", seed=900 + N + 7 * D + depth, N=N, F=F, Fc=Fc, D=D, depth=depth, n_bins=B, score=score, gen=gen, policy=policy, trees=3,
                 min_data_in_leaf=mdl, discrete_cols=[0] if F > 2 else [], constant_cols=[1] if F > 4 else [])
     if F > 0 and D == 1:
         case["loop"] = "rmse"
+
+    def ran_in_one_launch(ph, what):
+        assert ph.get("small_grow_fallbacks", 0) == 0, (what, ph)
+        assert "small_grow" in ph or "score_select" not in ph, (what, ph)
+
     loop, ploop = _grow(case, monkeypatch, {"GBRL_HIP_NO_SMALL_GROW": "1", "GBRL_HIP_NO_SMALL_PREP": "1"})
-    one, pone = _grow(case, monkeypatch, {})
+    one, pone, ph = _grow(case, monkeypatch, {}, phases=True)
     _same_bytes(loop, one, "small_grow")
     assert ploop.tobytes() == pone.tobytes()
+    ran_in_one_launch(ph, "small_grow")
     sep, psep = _grow(case, monkeypatch, {"GBRL_HIP_NO_SMALL_PREP": "1"})     # the growth kernel behind the separate preparation launches
     _same_bytes(loop, sep, "small_grow, separate preparation")
     # fewer blocks than slots (several slots per block, the codes reloaded per slot) must not matter either
-    few, pfew = _grow(case, monkeypatch, {"GBRL_HIP_SMALL_GROW_BLOCKS": "3"})
+    few, pfew, ph = _grow(case, monkeypatch, {"GBRL_HIP_SMALL_GROW_BLOCKS": "3"}, phases=True)
     _same_bytes(loop, few, "small_grow, 3 blocks")
+    ran_in_one_launch(ph, "small_grow, 3 blocks")
 
 
 @pytest.mark.parametrize("name", [c["name"] for c in K.CASES if c["N"] <= 8192 and not c.get("long_loop")])
