@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "model.h"
 #include "cat_candidates_host.h"   // HipError, Unsupported; detail::CatCandidate, CatMemory
+#include "mirror_records.h"        // detail::GreedyNodes, RateTable, CatDict: the host half of the device mirror
 
 namespace gbrl {
 
@@ -455,6 +456,7 @@ class Engine {
     void rewind_values(int t);  // the values of tree t alone have changed (newton_leaves_prepared): the next sync appends them again from that tree on
     void invalidate_mirror();   // values of existing trees have changed (refit_leaves): the append-only mirror is uploaded again, the dictionary stays
     void sync_cat_dict();   // the host half of it: cat_dict_ / cat_ids_host_ follow the model (no device needed)
+    // (the mirror, its dictionary and mirror_view are engine_mirror.hip's)
     int32_t *encode_categorical_batch(const char *cat, bool cat_dev, int n, int n_cat);
     // ---- the stages of a predict-family call, in the order every public call runs them (the head of engine_predict.hip has the list) ----
     // the observations as the caller handed them over: cells, or pre-encoded ids with their dictionary token (cat_ids != nullptr: cat is ignored)
@@ -735,20 +737,33 @@ class Engine {
     DevBuf d_staged_stops_, d_staged_targets_, d_staged_part_, d_staged_sums_;   // predict_staged / staged_loss: stops table, staged targets, loss partials and sums
     DevBuf m_tree_indices_, m_depths_, m_feature_indices_, m_feature_values_, m_values_, m_is_numerics_, m_ineq_,
         m_cat_ids_, m_bias_, m_opt_start_, m_opt_stop_, m_opt_lr_, m_cond_pack_, m_grd_nodes_, m_grd_off_, m_values_sw_, m_cond_ra_;
-    size_t up_trees_ = 0, up_leaves_ = 0, up_splits_ = 0;  // how much of the append-only arrays is already on the device
+    DevBuf m_rate_;   // Linear schedules: rate[t][optimizer] for every tree (detail::RateTable).  Not built while every optimizer is Const.
+    // The upload marks.  The mirror only ever appends: a mark says how much of a host array the device holds, sync_model_to_device() (the one
+    // place that advances them, after its flush) extends the host arrays from the marks and appends [mark, current size) to the device.
+    //   up_trees_          trees:      m_tree_indices_, m_cond_ra_, the greedy node records built (grd_), and with values_redo_tree_ m_values_sw_
+    //   up_leaves_         leaves:     m_values_, m_ineq_
+    //   up_splits_         split rows: m_depths_, m_feature_*, m_is_numerics_, m_cat_ids_, m_cond_pack_ (and cond_pack_host_ is built from it)
+    //   values_redo_tree_  the first tree whose record in m_values_sw_ is stale although up_trees_ covers it (kNoRedo: none)
+    //   grd_up_nodes_      greedy node records in m_grd_nodes_
+    //   rate_trees_        rows of m_rate_ (0 while no schedule is Linear; detail::RateTable starts over by itself when the optimizers change)
+    // Who takes them back:  rewind_values(t) -- the values of tree t alone have changed -- lowers up_leaves_ to the tree's first leaf and
+    // values_redo_tree_ to t, nothing else holds a value.  invalidate_mirror() -- values of any tree may have changed -- zeroes every mark but
+    // keeps the dictionary (dict_splits_, cat_dict_): ids and tokens stay valid.  A shrunken ensemble (sync_cat_dict: a mark beyond the model)
+    // zeroes up_* and grd_up_nodes_ and drops the dictionary too; rate_trees_ beyond the model makes the table start over.  up_trees_ == 0 is
+    // what resets grd_ and the host copies of the records.
+    size_t up_trees_ = 0, up_leaves_ = 0, up_splits_ = 0;
     static constexpr size_t kNoRedo = ~static_cast<size_t>(0);
-    size_t values_redo_tree_ = kNoRedo;   // rewind_values: the first tree whose pre-swizzled value records are stale
-    // Linear schedules: rate[t][optimizer] for every tree (gbrl::scheduler_lr), appended as trees join -- a tree's rate never changes --
-    // and rebuilt when the optimizers have changed.  Not built while every optimizer is Const.
-    DevBuf m_rate_;
-    std::vector<float> rate_host_;
-    std::vector<gbrl_hip_optimizer> rate_opts_;   // the optimizers the table was built from
+    size_t values_redo_tree_ = kNoRedo;
+    size_t grd_up_nodes_ = 0;
     size_t rate_trees_ = 0;
-    uint64_t mirror_version_ = ~0ull;
+    uint64_t mirror_version_ = ~0ull;   // the model version all of it was synchronised for
     uint64_t dict_model_version_ = ~0ull; size_t dict_splits_ = 0;   // sync_cat_dict(): the model version / split rows cat_dict_ covers
-    // dictionary of the categorical strings that occur in the model's conditions: (cat feature, string) -> id >= 1
-    std::vector<int32_t> cat_ids_host_, cond_pack_host_, grd_nodes_host_, grd_off_host_, cond_ra_host_;
-    std::vector<float> values_sw_host_;   // second-generation oblivious predict: see kern::PredictModel::values_sw
+    // the host copies the marks count in, built by mirror_records.h
+    detail::CatDict cat_dict_;            // the categorical strings that occur in the model's conditions: (cat feature, string) -> id >= 1
+    std::vector<int32_t> cat_ids_host_, cond_pack_host_, cond_ra_host_;
+    std::vector<float> values_sw_host_;   // second-generation predict: see kern::PredictModel::values_sw
+    detail::GreedyNodes grd_;
+    detail::RateTable rate_;
     // packed-code predict (kern::predict_pc): the ensemble's code book -- per numeric feature the sorted distinct thresholds, per
     // mentioned category a bit slot, per tree level a (word, shift, T) record -- rebuilt when the model has changed
     bool ensure_pc_book(int n_num, int n_cat);
@@ -756,10 +771,6 @@ class Engine {
     size_t pc_version_ = static_cast<size_t>(-1);
     int pc_f_ = -1, pc_fc_ = -1, pc_wn_ = 0, pc_nw_ = 0, pc_row_words_ = 0, pc_iters_ = 1;
     bool pc_ok_ = false;
-    bool grd_ok_ = true;
-    int grd_max_nodes_ = 0, grd_max_leaves_ = 1;
-    size_t grd_up_nodes_ = 0;
-    std::vector<std::pair<int, std::string>> cat_dict_;
     uint64_t dict_token_ = 0; size_t dict_token_size_ = static_cast<size_t>(-1);   // cat_dict_token(): cached per dictionary size (entries are only appended)
     DevBuf d_pcat_in_;   // pre-encoded ids handed over in host memory
     size_t dict_version_ = static_cast<size_t>(-1);   // cat_dict_.size() the device dictionary was built from

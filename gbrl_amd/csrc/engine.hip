@@ -1,6 +1,6 @@
 // engine.hip -- Engine infrastructure: grow-only device / pinned buffers, device selection, the exchange points of the
 // row-sharded mode (native RCCL or caller hooks) and the per-phase timing events.  The step / fit orchestration is in
-// engine_step.hip, model mirroring and predict in engine_predict.hip (see engine.h).
+// engine_step.hip, the device mirror of the model in engine_mirror.hip, predict in engine_predict.hip (see engine.h).
 #include "engine.h"
 #include "hooks.h"
 

@@ -111,7 +111,7 @@ kern::CodeTables Engine::sync_code_tables(const PreparedDataset &ds) {
             sent = true;
         }
     };
-    // the packed conditions of the mirror (cond_pack_host_, built by sync_model_to_device) with the threshold word replaced by the bin
+    // the packed conditions of the mirror (cond_pack_host_, detail::packed_condition) with the threshold word replaced by the bin
     code_pack_host_.resize(S * MD * 2, 0);
     for (size_t c = code_up_splits_ * MD; c < S * MD; ++c) {
         code_pack_host_[2 * c] = cond_pack_host_[2 * c];
@@ -123,12 +123,12 @@ kern::CodeTables Engine::sync_code_tables(const PreparedDataset &ds) {
     code_up_splits_ = S;
     // the greedy node records likewise (same offsets: grd_node_off is the mirror's)
     if (!model.oblivious()) {
-        const size_t n_nodes = grd_nodes_host_.size() / 4;
+        const size_t n_nodes = grd_.nodes.size() / 4;
         if (code_nodes_ > n_nodes) code_nodes_ = code_up_nodes_ = 0;
         code_nodes_host_.resize(n_nodes * 4);
         for (size_t k = code_nodes_; k < n_nodes; ++k) {
             int32_t *nd = &code_nodes_host_[k * 4];
-            std::memcpy(nd, &grd_nodes_host_[k * 4], 16);
+            std::memcpy(nd, &grd_.nodes[k * 4], 16);
             if (nd[0] >= 0) {
                 float v;
                 std::memcpy(&v, &nd[1], sizeof(v));

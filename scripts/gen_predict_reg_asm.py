@@ -157,7 +157,7 @@ class Variant:
 
 # ======================================================================================================================
 # Packed-code variant ("pc"): rows wider than the fp32 bank, or with categorical columns, are first rewritten as packed codes
-# (engine_predict.hip / k_pack_codes): a numeric feature becomes a 16-bit field holding 0xffff - #{ensemble thresholds below x},
+# (mirror_records.h / k_pack_codes): a numeric feature becomes a 16-bit field holding 0xffff - #{ensemble thresholds below x},
 # a categorical column one INVERTED one-hot bit per category the ensemble mentions.  Every condition is then
 #     D = word << shift          (field / bit to the top, zeros below)
 #     mask = D < T               (numeric: T = (0xffff - rank) << 16;  categorical: T = 0x80000000, i.e. "the bit is clear")

@@ -320,6 +320,25 @@ def test_categorical_host_core_equals_the_reference_rule_on_random_batches(tmp_p
     assert out.returncode == 0 and " 0 mismatches" in out.stdout, out.stdout + out.stderr
 
 
+def test_mirror_records_equal_the_model_rules_on_random_ensembles(tmp_path):
+    """mirror_records.h without a device (tests/cxx/mirror_records_check.cpp, built with the address and undefined-behaviour sanitizers):
+    on random ensembles of both grow policies -- max_depth 1 to 8, 1 to 17 outputs, 1 to 40 trees, numeric and categorical conditions,
+    shallow and depth-0 oblivious trees, random proper greedy shapes -- the descent over the greedy node records ends at the leaf the
+    model's per-leaf conditions select; every malformed shape is refused with the tree's nodes dropped and the trees in front untouched;
+    the oblivious and greedy records un-swizzle to model.values with their conditions, nodes and padding in place; records built tree by
+    tree under the engine's upload marks (with rewind_values and invalidate_mirror in between) equal records built in one go, and so does
+    the image a device would hold; the rate table is scheduler_lr, appended only; the packed-code book's tests agree with the conditions
+    on packed rows, and every inexpressible ensemble is refused."""
+    import subprocess
+    exe = tmp_path / "mirror_records_check"
+    csrc = os.path.join(ROOT, "gbrl_amd", "csrc")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", csrc,
+                    os.path.join(ROOT, "tests", "cxx", "mirror_records_check.cpp"), os.path.join(csrc, "model.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and "all sections passed" in out.stdout, out.stdout + out.stderr
+    assert len(out.stdout.strip().split("\n")) == 8, out.stdout
+
+
 def test_register_tile_asm_header_is_current_and_the_compiler_keeps_out_of_the_bank(tmp_path):
     """predict_reg.hip keeps a row tile in a bank of VGPRs that the compiler must never allocate (amdgpu_num_vgpr caps it below the
     bank; the bank is only named in clobber lists).  (1) The generated assembly text is the generator's current output.  (2) Audit of
