@@ -1453,6 +1453,106 @@ py::object objective_exp_host_impl(py::array_t<float, py::array::c_style | py::a
     return std::move(out);
 }
 
+// ---- feature importance (include/gbrl_hip.h, "Feature importance")
+// permutation_host(n, seed=0, col=0, repeat=0) -> int32 [n]: the rule on the host, no device
+py::array_t<int32_t> permutation_host_impl(int n, uint64_t seed, int col, int repeat) {
+    py::array_t<int32_t> out(static_cast<py::ssize_t>(std::max(n, 0)));
+    int32_t none = 0;
+    check(gbrl_hip_permutation_host(n, seed, col, repeat, n > 0 ? out.mutable_data() : &none));
+    return out;
+}
+
+py::dict permutation_geometry_impl() {
+    int variants = 0, rows = 0;
+    gbrl_hip_permutation_geometry(&variants, &rows);
+    py::dict out;
+    out["launch_variants"] = variants;
+    out["tile_rows"] = rows;
+    return out;
+}
+
+// permutation_importance_prepared(ds, targets, objective='rmse', n_repeats=5, seed=0, cols=None, n_trees=None, alpha=None) -> dict
+py::dict permutation_importance_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, const std::string &objective_name, int n_repeats, uint64_t seed,
+                                              py::object &cols, py::object n_trees_obj, py::object alpha_obj) {
+    const std::string fn = "permutation_importance_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const int objective = parse_objective(objective_name), D = md.output_dim;
+    if (n_repeats < 1) fail(fn + ": n_repeats must be >= 1, got " + std::to_string(n_repeats));
+    int n_trees = -1;   // None: every tree
+    if (!n_trees_obj.is_none()) {
+        const long long k = n_trees_obj.cast<long long>();
+        if (k < 1 || k > md.n_trees)
+            fail(fn + ": n_trees " + std::to_string(k) + " is outside [1, " + std::to_string(md.n_trees) + "], the model's trees (None / -1: all)");
+        n_trees = static_cast<int>(k);
+    }
+    const int n = ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, F = ds ? ds_obj.cast<const PyDataset &>().info().n_features : 0;
+    std::vector<int32_t> cv;
+    if (!cols.is_none()) {
+        cv = read_cols(cols, fn);
+        if (cv.empty()) fail(fn + ": cols must name between 1 and " + std::to_string(F) + " columns, got 0");
+    } else {
+        cv.resize(static_cast<size_t>(F));
+        for (int f = 0; f < F; ++f) cv[f] = f;
+    }
+    const std::vector<float> alpha = read_alpha(alpha_obj, D, fn);
+    const bool ranking = objective == GBRL_HIP_OBJ_PAIRWISE || objective == GBRL_HIP_OBJ_LAMBDARANK;   // (refused behind the C ABI: no shape of theirs is checked here)
+    Input t = read_objective_targets(targets, "targets", false, fn, objective, n, D, ds != nullptr && !ranking);
+    if (!t.ptr) fail("Cannot call " + fn + " without targets!");
+    const py::ssize_t C = static_cast<py::ssize_t>(cv.size()), R = n_repeats;
+    py::array_t<double> loss({std::max<py::ssize_t>(C, 1), R});
+    double baseline = 0.0;
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_permutation_importance_prepared(self.h, ds, t.ptr, t.on_device, objective, alpha.empty() ? nullptr : alpha.data(), n_repeats, seed,
+                                                      cols.is_none() ? nullptr : cv.data(), static_cast<int>(cv.size()), n_trees, &baseline, loss.mutable_data());
+    }
+    check(rc);
+    py::array_t<double> importance({C, R}), mean(C), sd(C);
+    py::array_t<int32_t> cols_out(C);
+    const double *L = loss.data();
+    for (py::ssize_t c = 0; c < C; ++c) {
+        cols_out.mutable_data()[c] = cv[static_cast<size_t>(c)];
+        double s = 0.0;
+        for (py::ssize_t r = 0; r < R; ++r) {
+            importance.mutable_data()[c * R + r] = L[c * R + r] - baseline;
+            s += importance.data()[c * R + r];
+        }
+        const double mu = s / static_cast<double>(R);
+        double q = 0.0;
+        for (py::ssize_t r = 0; r < R; ++r) q += (importance.data()[c * R + r] - mu) * (importance.data()[c * R + r] - mu);
+        mean.mutable_data()[c] = mu;
+        sd.mutable_data()[c] = std::sqrt(q / static_cast<double>(R));   // the population form, as numpy.std
+    }
+    py::dict out;
+    out["baseline"] = py::float_(baseline);
+    out["loss"] = loss;
+    out["importance"] = importance;
+    out["mean"] = mean;
+    out["std"] = sd;
+    out["cols"] = cols_out;
+    return out;
+}
+
+// feature_importance(kind='split' | 'cover', leaf_counts=None) -> float64 [input_dim], from the host copy of the model
+py::array_t<double> feature_importance_impl(PyGBRL &self, const std::string &kind_name, py::object leaf_counts) {
+    const gbrl_hip_metadata md = self.meta();
+    const int kind = parse_enum(kind_name, {{"split", GBRL_HIP_IMPORTANCE_SPLIT}, {"cover", GBRL_HIP_IMPORTANCE_COVER}}, "Invalid kind! Options are: split/cover");
+    py::array_t<int64_t, py::array::c_style | py::array::forcecast> counts;
+    if (kind == GBRL_HIP_IMPORTANCE_COVER) {
+        if (leaf_counts.is_none()) fail("feature_importance: kind 'cover' needs leaf_counts, the int64 vector GBRL.leaf_counts returns");
+        counts = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(leaf_counts);
+        if (!counts) { PyErr_Clear(); fail("feature_importance: leaf_counts must be a vector of integers"); }
+        if (counts.ndim() != 1 || counts.shape(0) != md.n_leaves)
+            fail("feature_importance: leaf_counts must hold one count per leaf of the ensemble (" + std::to_string(md.n_leaves) + ")");
+    }
+    py::array_t<double> out(static_cast<py::ssize_t>(md.input_dim));
+    double none = 0.0;
+    check(gbrl_hip_feature_importance(self.h, kind, kind == GBRL_HIP_IMPORTANCE_COVER ? counts.data() : nullptr, md.input_dim > 0 ? out.mutable_data() : &none));
+    return out;
+}
+
 float fit_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, int iterations, bool shuffle,
                const std::string &loss_type) {
     if (loss_type != "MultiRMSE") fail("Invalid loss function! Options are: MultiRMSE");   // stringTolossType, types.cpp:52-56
@@ -1668,6 +1768,15 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     m.def("rank_discounts", &rank_discounts_impl,
           "rank_discounts() -> float64 [1024]: disc[t] = 1 / log2(t + 2), the ONE table the host rule and the kernels of the ranking objectives read");
     m.def("rank_geometry", &rank_geometry_impl, "rank_geometry() -> {'max_query': 1024, 'max_label': 30}: the largest query and relevance label of the ranking objectives");
+    m.def("permutation_host", &permutation_host_impl, py::arg("n"), py::arg("seed") = 0, py::arg("col") = 0, py::arg("repeat") = 0,
+          "permutation_host(n, seed=0, col=0, repeat=0) -> int32 [n]\n\n"
+          "The row permutation of GBRL.permutation_importance_prepared on the host (no device is needed), the one definition the kernels compile too: a\n"
+          "bijection pi of [0, n), computed element by element with no state; row i of the variant (col, repeat) reads column col from row pi[i].  A\n"
+          "cycle-walking balanced Feistel network: b = max(2, bit_length(n - 1)) rounded up to even, four rounds (L, R) <- (R, L ^ (F_k(R) & (2**(b/2) - 1)))\n"
+          "with F_k the row sampler's 24-bit hash keyed by seed ^ 'permutat', col and the round, applied again while the result is >= n.");
+    m.def("permutation_geometry", &permutation_geometry_impl,
+          "permutation_geometry() -> {'launch_variants': 64, 'tile_rows': 64}: the (column, repeat) variants one launch of permutation_importance_prepared\n"
+          "walks, and the rows of its tile (= the rows per loss partial)");
     m.def("leaf_quantile_host", &leaf_quantile_host_impl, py::arg("x"), py::arg("leaves"), py::arg("n_leaves"), py::arg("alpha"),
           "leaf_quantile_host(x, leaves, n_leaves, alpha) -> {'values': float32 [n_leaves, D], 'counts': int64 [n_leaves], 'ranks': int64 [n_leaves, D]}\n\n"
           "The leaf rule of fit_prepared(leaf_update='quantile') and GBRL.quantile_leaves_prepared on the host (no device is needed): x float32 [m, D] are the\n"
@@ -2014,6 +2123,26 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         return leaves_impl(self, obs, ids, start, stop, true, &token);
     }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0);
     g.def_static("leaf_counts_chunk", []() { return gbrl_hip_leaf_counts_chunk(); });   // leaf counters one launch of leaf_counts holds on chip
+    // extension: global feature importance -- two counts from the host copy of the model, and the permuted losses of a data set's columns
+    g.def("feature_importance", &feature_importance_impl, py::arg("kind") = "split", py::arg("leaf_counts") = py::none(),
+          "feature_importance(kind='split', leaf_counts=None) -> float64 [input_dim]\n\n"
+          "Counts from the model's structure (no device is needed).  A decision is a level of an oblivious tree (counted once, not once per node) or a\n"
+          "distinct internal node of a greedy tree.  'split': the decisions that test the feature.  'cover': sum over leaves of leaf_counts[leaf] * (the\n"
+          "conditions on the leaf's path that test the feature) -- the rows reaching every decision on it; leaf_counts is the int64 [n_leaves] vector\n"
+          "leaf_counts(obs, categorical_obs) returns.  The feature axis is ensemble_shap's: a condition counts at its raw feature index as\n"
+          "get_ensemble_data()['feature_indices'] holds it, numeric and categorical alike (a categorical condition WITHOUT the numeric-feature offset),\n"
+          "and feature_mapping is not applied.  Every value is an integer.  Gain importance is not offered: the model file stores no split gain.");
+    g.def("permutation_importance_prepared", &permutation_importance_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("objective") = "rmse",
+          py::arg("n_repeats") = 5, py::arg("seed") = 0, py::arg("cols") = py::none(), py::arg("n_trees") = py::none(), py::arg("alpha") = py::none(),
+          "permutation_importance_prepared(ds, targets, objective='rmse', n_repeats=5, seed=0, cols=None, n_trees=None, alpha=None) -> dict\n\n"
+          "How much the loss of the trees [0, n_trees) on the data set's rows grows when one column is shuffled.  'baseline': the loss on ds as it is, in\n"
+          "the units of fit_prepared's valid_loss for the objective; 'loss' float64 [n_cols, n_repeats]: the same loss with column cols[c] read from row\n"
+          "gbrl_cpp.permutation_host(n, seed, cols[c], r)[i] -- bit for bit the valid_loss[0] of fit_prepared(ds, y, 0, valid=prepare_dataset(Xp,\n"
+          "reference=ds), valid_targets=y) on the shuffled observations Xp, none of which is built here; 'importance' = loss - baseline; 'mean' and 'std'\n"
+          "(numpy.std's population form) over the repeats; 'cols'.  cols=None: every column; n_trees=None: all trees (pass best_n_trees of an\n"
+          "early-stopped fit).  objective: 'rmse', 'logistic', 'softmax' (int32 labels) or 'quantile' (with alpha).  A column no tree of the range tests\n"
+          "reports the baseline's bits.  The model and the data set are not changed.  Refused before the device is touched: n_repeats < 1, bad cols or\n"
+          "n_trees, missing or misshapen targets, a model without trees, the ranking objectives, and what predict_continue_prepared refuses.");
     // extension: every ensemble prefix in one walk -- the prediction, or the MultiRMSE loss against targets, after every stops[s] trees
     g.def("predict_staged", &predict_staged_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("stops") = py::none());
     g.def("staged_loss", &staged_loss_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("stops") = py::none());

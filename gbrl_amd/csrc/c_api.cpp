@@ -828,6 +828,35 @@ void gbrl_hip_rank_geometry(int *max_query, int *max_label) {
     if (max_label) *max_label = gbrl::kern::kRankMaxLabel;
 }
 
+// ---- feature importance: the permutation rule on the host, the permuted losses of a data set (engine_importance.hip), the two counts (explain.cpp)
+int gbrl_hip_permutation_host(int n, uint64_t seed, int col, int repeat, int32_t *out) {
+    return guarded([&] { gbrl::Engine::permutation_host(n, seed, col, repeat, out); });
+}
+
+int gbrl_hip_permutation_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int objective,
+                                             const float *alpha, int n_repeats, uint64_t seed, const int32_t *cols, int n_cols, int n_trees, double *baseline_out,
+                                             double *loss_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("permutation_importance_prepared");
+        m->engine.permutation_importance_prepared(&live_dataset(ds), targets, targets_on_device != 0, objective, alpha, n_repeats, seed, cols, n_cols, n_trees,
+                                                  baseline_out, loss_out);
+    });
+}
+
+void gbrl_hip_permutation_geometry(int *launch_variants, int *tile_rows) {
+    if (launch_variants) *launch_variants = gbrl::kern::kPermLaunchVariants;
+    if (tile_rows) *tile_rows = gbrl::kern::perm_tile_rows();
+}
+
+static_assert(GBRL_HIP_IMPORTANCE_SPLIT == gbrl::kFeatureSplit && GBRL_HIP_IMPORTANCE_COVER == gbrl::kFeatureCover, "the importance kinds are the header's");
+int gbrl_hip_feature_importance(const gbrl_hip_model *m, int kind, const int64_t *leaf_counts, double *out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        gbrl::feature_importance(m->engine.model, kind, leaf_counts, out);
+    });
+}
+
 int gbrl_hip_objective_gradient_quantile(gbrl_hip_model *m,const float *pred, int pred_on_device, const void *targets, int targets_on_device, const float *alpha,
                                          int n, int objective, float *grad_out, double *loss_out) {
     return guarded([&] {

@@ -192,6 +192,19 @@ class Engine {
     // condition that is not among the data set's thresholds (Unsupported).  The model is never changed.
     void predict_continue_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *base, bool base_dev, int start_tree,
                                    int stop_tree, float *out, bool out_dev);
+    // Extension (engine_importance.hip; perm_core.h has the permutation, perm_loss.hip the kernels): permutation importance on a data set.
+    // *baseline_out = the loss of the trees [0, n_trees) on ds's rows against targets, walked from the bias, in the units of fit_prepared's
+    // loss_out for the objective (mean_loss over ds->n rows); loss_out [n_cols][n_repeats] (host) = the same loss with column cols[c] read from
+    // row perm(ds->n, seed, cols[c], r)(i) -- bit for bit fit_prepared's validation loss on a data set that holds the shuffled column.  cols
+    // (host, check_cols' rule; nullptr: every column, n_cols ignored); n_trees in [1, model's] or -1 for all.  objective: rmse, logistic,
+    // softmax, quantile (alpha then, host [D]); targets as fit_prepared's (host or device).  A column no condition of the walked trees tests is
+    // not launched: its entries are the baseline.  At most kern::kPermLaunchVariants variants per launch; nothing but loss partials is stored.
+    // Refused before the device is touched: n_repeats < 1, check_cols, n_trees, null targets or outputs, a model without trees, check_objective
+    // (the ranking objectives), check_alpha, and what predict_continue_prepared refuses about the model and the data set.  A softmax label
+    // outside [0, D) is refused once the labels are on the device.  Model and data set are never changed.
+    void permutation_importance_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int objective, const float *alpha, int n_repeats,
+                                         uint64_t seed, const int32_t *cols, int n_cols, int n_trees, double *baseline_out, double *loss_out);
+    static void permutation_host(int n, uint64_t seed, int col, int repeat, int32_t *out);   // the rule on the host: out [n] = perm(n, seed, col, repeat)
     // fit_prepared: fit()'s loop (shuffle = false) on a data set with nothing recomputed.  Each iteration takes the next batch_size rows (wrapping to
     // row 0), advances their held prediction by the trees grown since the batch last saw it -- one launch that also writes the objective's gradient
     // -- and grows one tree by step_prepared's body; at the end every batch is advanced and the loss on all rows returned (fit()'s MultiRMSE; an
@@ -627,6 +640,7 @@ class Engine {
     DevBuf d_fp_srows_, d_fp_sgrads_, d_fp_sscratch_;   // its sampled iterations: the kept rows of the batch, their gradient rows, block counts + m
     DevBuf d_obj_weights_, d_fp_weights_, d_fp_vweights_, d_wstat_, d_wpart_, d_wsum_;   // row weights: staged vectors; kern::weight_stats' two ints, partials and sum
     DevBuf d_obj_pred_, d_obj_targets_, d_obj_grad_, d_obj_part_, d_obj_sum_, d_obj_counts_;   // objective_gradient: staged inputs, the gradient, loss partials and sum; class counts + first bad row
+    DevBuf d_pi_targets_, d_pi_variants_, d_pi_part_, d_pi_sums_;   // permutation_importance_prepared: staged targets, the variant list, one launch's loss partials, one sum per variant
     DevBuf d_met_counts_, d_met_scratch_, d_fp_vmetric_;   // eval_metric: the integer counters, the AUC pipeline's scratch; fit_prepared: the metric's counters per iteration
     struct Held;     // engine_fit_prepared.hip: a data set's rows carried through the model's trees, batch by batch
     struct FitRun;   // engine_fit_prepared.hip: the state of one fit_prepared call and the stages that work on it

@@ -19,6 +19,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <set>
 #include <stdexcept>
 #include <thread>
 #include <vector>
@@ -493,6 +494,43 @@ std::string tree_text(const Model &m, int tree_idx) {
     }
     o << "******************\n";
     return std::move(o.s);
+}
+
+void feature_importance(const Model &m, int kind, const int64_t *leaf_counts, double *out) {
+    const gbrl_hip_metadata &md = m.meta;
+    if (kind != kFeatureSplit && kind != kFeatureCover) throw std::runtime_error("feature_importance: unknown kind (split = 0, cover = 1)");
+    if (kind == kFeatureCover && leaf_counts == nullptr) throw std::runtime_error("feature_importance: kind 'cover' needs leaf_counts, the rows per leaf");
+    if (out == nullptr) throw std::runtime_error("feature_importance: null output");
+    const int in = md.input_dim, depth_cap = md.max_depth;
+    std::fill(out, out + in, 0.0);
+    auto feature = [&](size_t c) {
+        const int f = m.feature_indices[c];
+        if (f < 0 || f >= in) throw std::runtime_error("feature_importance: a condition tests feature " + std::to_string(f) + ", outside the model's input_dim");
+        return f;
+    };
+    std::set<std::vector<uint8_t>> seen;   // greedy: the direction prefixes of one tree's internal nodes met so far
+    for (int t = 0; t < md.n_trees; ++t) {
+        const int first = m.tree_indices[t], end = t == md.n_trees - 1 ? md.n_leaves : m.tree_indices[t + 1];
+        if (kind == kFeatureSplit && m.oblivious()) {   // a level counts once
+            for (int d = 0; d < m.depths[t]; ++d) out[feature(static_cast<size_t>(t) * depth_cap + d)] += 1.0;
+            continue;
+        }
+        seen.clear();
+        for (int leaf = first; leaf < end; ++leaf) {
+            const int row = m.oblivious() ? t : leaf;
+            const size_t cond = static_cast<size_t>(row) * depth_cap, path = static_cast<size_t>(leaf) * depth_cap;
+            if (kind == kFeatureCover) {
+                if (leaf_counts[leaf] < 0) throw std::runtime_error("feature_importance: leaf_counts[" + std::to_string(leaf) + "] is negative");
+                for (int d = 0; d < m.depths[row]; ++d) out[feature(cond + d)] += static_cast<double>(leaf_counts[leaf]);
+                continue;
+            }
+            // the node at depth d above this leaf is named by the directions taken to reach it: count it when the prefix is new
+            for (int d = 0; d < m.depths[row]; ++d) {
+                const std::vector<uint8_t> prefix(m.inequality_directions.begin() + path, m.inequality_directions.begin() + path + d);
+                if (seen.insert(prefix).second) out[feature(cond + d)] += 1.0;
+            }
+        }
+    }
 }
 
 std::string metadata_text(const Model &m, const char *device_name) {

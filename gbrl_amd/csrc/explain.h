@@ -53,6 +53,18 @@ bool export_header(const Model &m, const std::string &model_name, const std::str
 
 // stdout text of GBRL::print_tree (gbrl.cpp:1357-1391 + print_leaf node.cpp:492-553); tree_idx -1 = last tree
 std::string tree_text(const Model &m, int tree_idx);
+// Extension: two counts per feature from the ensemble's structure, out [input_dim] float64 (every value an integer).  A DECISION is a level of an
+// oblivious tree (counted once, not once per node of the level) or a distinct internal node of a greedy tree (its conditions are stored per leaf:
+// the path prefixes are deduplicated by their directions).
+//   kFeatureSplit  out[f] = the decisions that test feature f
+//   kFeatureCover  out[f] = sum over leaves of leaf_counts[leaf] * (conditions on the leaf's path that test f): the rows that reach every decision
+//                  on f, under the same counting of decisions; leaf_counts int64 [n_leaves] as GBRL::leaf_counts returns it
+// The feature axis is ensemble_shap's: entry f collects the conditions whose raw feature_indices entry is f, numeric and categorical alike -- a
+// categorical condition WITHOUT the n_num_features offset (explain.cpp's head has the convention) -- and feature_mapping is not applied.
+// Throws std::runtime_error: an unknown kind, kFeatureCover without leaf_counts, a negative count, a feature index outside [0, input_dim).
+constexpr int kFeatureSplit = 0, kFeatureCover = 1;
+void feature_importance(const Model &m, int kind, const int64_t *leaf_counts, double *out);
+
 // stdout text of GBRL::print_ensemble_metadata (gbrl.cpp:1254-1267)
 std::string metadata_text(const Model &m, const char *device_name);
 

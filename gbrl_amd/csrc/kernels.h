@@ -679,6 +679,20 @@ void predict_continue_codes(const PredictModel &pm, const CodeTables &ct, const 
 // kObjQuantile (quantile_core.h): float targets [m][D] as rmse, alpha the device table of its D levels (required; weights are not taken): the gradient
 // tail writes the pinball step, the loss tail sums the pinball loss.
 //
+// The loss of "one column shuffled" variants of a data set's rows (perm_loss.hip; perm_core.h has the permutation), none of them materialised.
+// A variant is (col, repeat): row i reads column col from row perm(n, seed, col, repeat)(i) and every other column from itself; col < 0 is the
+// data set as it is (the baseline).  For each of the n_variants entries of `variants` (device) the trees [0, n_trees) are walked from the model's
+// bias over all n rows of `codes` ([groups][n][16] u16) and loss_part[v][j / 64] = the wave's sum of the objective's row losses: the partials the
+// loss tail of predict_continue_codes writes for that variant's rows (n_variants x staged_loss_partials(n) doubles; staged_loss_finish_rows sums
+// them).  No prediction is stored.  targets / alpha as predict_continue_codes' loss_targets / alpha (no weights).  n_variants <= kPermLaunchVariants
+// per launch keeps the partials bounded; n_trees >= 1 and a model with an optimizer: the caller checks.  generic: the one-thread-per-row kernel only
+// (GBRL_HIP_PERM_GENERIC=1; same bytes).  Always launches (n > 0, n_variants > 0).
+constexpr int kPermLaunchVariants = 64;
+struct PermVariant { int32_t col, repeat; };
+void perm_loss(const PredictModel &pm, const CodeTables &ct, const uint16_t *codes, int n, int groups, int n_trees, int objective, const float *targets,
+               const float *alpha, uint64_t seed, const PermVariant *variants, int n_variants, double *loss_part, bool generic, hipStream_t s);
+int perm_tile_rows();   // rows of the streaming kernel's LDS tile = rows per loss partial
+//
 // The objectives on a prediction matrix (objective.hip): the device functions of the tails applied to pred [n][D] (device).  targets: float32
 // [n][D] (rmse, logistic) or int32 [n] (softmax; every label in [0, D): the caller checks, label_counts below).  grad_out (device [n][D]) and
 // loss_part (staged_loss_partials(n) doubles, one per 64 rows, finished by staged_loss_finish) may each be null.  D <= 128.
@@ -753,6 +767,8 @@ void staged_loss_of_predictions(const float *preds, const float *targets, int n,
 // its two halves: the partials alone (one per 64 consecutive rows), and the finishing sum of nb partials that any of the loss kernels wrote
 void loss_partials_of_predictions(const float *preds, const float *targets, int n, int D, double *part, hipStream_t s);
 void staged_loss_finish(const double *part, int nb, double *sum, hipStream_t s);
+// ... of n_rows vectors of nb partials each, part[r][0 .. nb) -> sums[r]: the same kernel, one block per vector (predict_staged's own finishing launch)
+void staged_loss_finish_rows(const double *part, int nb, int n_rows, double *sums, hipStream_t s);
 // Where a row lands (predict_leaves.hip): the GLOBAL leaf index -- the row of `values` -- that each tree of [start_tree, stop_tree) routes a row to.
 // Oblivious: tree_indices[t] + the bits of the tree's conditions.  Greedy: the first leaf in storage order from tree_indices[t] on whose conditions
 // all hold; a depth-0 leaf never passes (Q7), and -1 when the search runs off the ensemble.  No leaf value is read: no limit on output_dim.

@@ -200,6 +200,10 @@ void staged_loss_finish(const double *part, int nb, double *sum, hipStream_t s) 
     hipLaunchKernelGGL(k_staged_finish, dim3(1), dim3(kFinishThreads), 0, s, part, nb, sum);
 }
 
+void staged_loss_finish_rows(const double *part, int nb, int n_rows, double *sums, hipStream_t s) {
+    hipLaunchKernelGGL(k_staged_finish, dim3(n_rows), dim3(kFinishThreads), 0, s, part, nb, sums);
+}
+
 void staged_loss_of_predictions(const float *preds, const float *targets, int n, int D, double *part, double *sum, hipStream_t s) {
     loss_partials_of_predictions(preds, targets, n, D, part, s);
     staged_loss_finish(part, staged_loss_partials(n), sum, s);

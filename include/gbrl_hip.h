@@ -822,6 +822,43 @@ int gbrl_hip_newton_leaves_prepared_rank(gbrl_hip_model *m, const gbrl_hip_datas
                                          int labels_on_device, const int32_t *group /*host*/, int n_groups, int objective, int ndcg_at, int tree, double leaf_l2,
                                          int64_t *sums_out /*[leaves, 3]*/, int *bits_out, float *values_out /*[leaves, 1]*/);
 void gbrl_hip_rank_geometry(int *max_query, int *max_label);
+/* Feature importance (new: scikit-learn's feature_importances_ and inspection.permutation_importance, LightGBM's feature_importance, XGBoost's
+ * get_score).  Two counts from the host copy of the model and the permutation importance of a data set's columns on the device.
+ *   permutation   csrc/perm_core.h defines it once for the host and the kernels (csrc/perm_loss.hip): pi = perm(n, seed, col, repeat) is a bijection of
+ *                 [0, n), computed element by element with no state -- a cycle-walking balanced Feistel network of four rounds over 2 * h bits,
+ *                 h = ceil(max(2, bit_length(n - 1)) / 2), with the row sampler's hash as round function on a stream of its own ("permutat"); the
+ *                 header's opening comment has every constant.  Row i of the variant (col, repeat) reads column col from row pi(i).
+ *   gbrl_hip_permutation_host(n, seed, col, repeat, out [n])  the rule with no device.  Refused: n < 1, col < 0, repeat < 0, NULL out.
+ *   gbrl_hip_permutation_importance_prepared(m, ds, targets, targets_on_device, objective, alpha, n_repeats, seed, cols, n_cols, n_trees, baseline_out,
+ *     loss_out)  on the model's device.  *baseline_out = the loss of the trees [0, n_trees) (n_trees == -1: all) on the data set's rows, walked from the
+ *     bias, in the units of valid_loss_out of gbrl_hip_fit_prepared_* for the objective (rmse: sqrt(0.5 sum / n); otherwise sum / n); loss_out (host
+ *     float64 [n_cols][n_repeats]) = the same loss with column cols[c] shuffled by perm(n, seed, cols[c], r): bit for bit the validation loss of a
+ *     zero-iteration gbrl_hip_fit_prepared_* call on a data set made from the shuffled observations with ds as its reference (binning is per cell).
+ *     No variant is materialised: one launch walks up to 64 variants (gbrl_hip_permutation_geometry) over a row tile staged once, patches one 2-byte
+ *     code per row on chip, and stores one float64 partial per 64 rows; the partials are summed in the loss paths' fixed order.  cols: host int32,
+ *     strictly ascending entries in [0, n_features); NULL: every column.  objective: GBRL_HIP_OBJ_RMSE / LOGISTIC / SOFTMAX / QUANTILE with targets
+ *     (host or device) and alpha (host [output_dim], quantile only) as gbrl_hip_fit_prepared_quantile takes them.  A column that no condition of the
+ *     walked trees tests is not launched: its entries are the baseline's bits.  Refused before the device is touched, GBRL_HIP_E_INVALID: n_repeats
+ *     < 1, cols that break the rule, n_trees outside [1, n_trees of the model] and not -1, NULL targets or outputs, a model without trees, the
+ *     ranking objectives (their loss needs query groups), alpha without quantile or quantile without alpha; and whatever
+ *     gbrl_hip_predict_continue_prepared refuses about the model and the data set (GBRL_HIP_E_UNSUPPORTED for a tree the thresholds cannot express,
+ *     the tree is named).  After the label pass: a softmax label outside [0, output_dim).  Model and data set are left byte for byte as they were.
+ *   gbrl_hip_feature_importance(m, kind, leaf_counts, out [input_dim])  no device.  A decision is a level of an oblivious tree (once, not once per node)
+ *     or a distinct internal node of a greedy tree (conditions are stored per leaf: path prefixes are deduplicated).  GBRL_HIP_IMPORTANCE_SPLIT:
+ *     out[f] = decisions that test feature f.  GBRL_HIP_IMPORTANCE_COVER: out[f] = sum over leaves of leaf_counts[leaf] * (conditions on the leaf's path
+ *     that test f), leaf_counts the int64 [n_leaves] vector of gbrl_hip_leaf_counts: the rows that reach every decision on f.  The feature axis is
+ *     gbrl_hip_ensemble_shap's: a condition counts at its raw feature index, a categorical one WITHOUT the n_num_features offset, feature_mapping not
+ *     applied.  Every value is an integer in float64.  Refused: an unknown kind, cover without leaf_counts, a negative count.
+ *   Out of scope: weights, the ranking objectives, categorical columns and row-sharded models (the data-set family has neither), gain importance (the
+ *     file format stores no split gain), permuting groups of columns together. */
+enum { GBRL_HIP_IMPORTANCE_SPLIT = 0, GBRL_HIP_IMPORTANCE_COVER = 1 };
+int gbrl_hip_permutation_host(int n, uint64_t seed, int col, int repeat, int32_t *out /*[n]*/);
+int gbrl_hip_permutation_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int objective,
+                                             const float *alpha /*host [output_dim], may be NULL*/, int n_repeats, uint64_t seed,
+                                             const int32_t *cols /*host [n_cols], may be NULL*/, int n_cols, int n_trees, double *baseline_out,
+                                             double *loss_out /*host [n_cols][n_repeats]*/);
+void gbrl_hip_permutation_geometry(int *launch_variants, int *tile_rows);
+int gbrl_hip_feature_importance(const gbrl_hip_model *m, int kind, const int64_t *leaf_counts /*[n_leaves], may be NULL for split*/, double *out /*[input_dim]*/);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
