@@ -23,6 +23,7 @@
 //   The result block res (uint32 words, ZEROED by the caller on `s`): keys [n_leaves][D], ranks [n_leaves][D], counts [n_leaves], flag -- one read-back.
 #include "kernels.h"
 #include "kernels_common.h"
+#include "leaf_accum.h"
 #include "predict_rowwalk.h"
 #include "quantile_core.h"
 
@@ -38,12 +39,10 @@ constexpr int kRowsPerChunk = 2048;     // rows one block of the count pass take
 constexpr int kMaxCountBlocks = 32;     // chunk blocks per output column: the partials stay small (blocks x D x leaves KiB per pass)
 constexpr int kRouteLdsLeaves = kMaxSelectLeaves;   // leaf counters of the route pass kept in LDS: the select path's trees
 
-struct LqTree { int t, leaf0, n_leaves; };
-
 __device__ __forceinline__ uint32_t lq_leaf_id(int l, int n_leaves) { return l < 0 ? static_cast<uint32_t>(n_leaves) : static_cast<uint32_t>(l); }
 
 // ------------------------------------------------------------------------------------------------------------ route and key pass
-__global__ __launch_bounds__(256) void k_lq_route(LeavesModel cm, LqTree tr, CodeRows cr, int m, int D, const float *__restrict__ pred,
+__global__ __launch_bounds__(256) void k_lq_route(LeavesModel cm, TreeSpan tr, CodeRows cr, int m, int D, const float *__restrict__ pred,
                                                   const float *__restrict__ targets, int abs_index, int32_t *__restrict__ leaf_out,
                                                   uint32_t *__restrict__ keys, uint32_t *__restrict__ id_cols, uint32_t *__restrict__ counts,
                                                   uint32_t *__restrict__ flag_out) {
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(256) void k_lq_route(LeavesModel cm, LqTree tr, Cod
     __shared__ uint32_t lcnt[kRouteLdsLeaves];
     const bool in_lds = tr.n_leaves <= kRouteLdsLeaves;   // (uniform)
     if (in_lds) {
-        for (int i = threadIdx.x; i < tr.n_leaves; i += blockDim.x) lcnt[i] = 0u;
+        leaf_acc_zero(lcnt, tr.n_leaves, threadIdx.x, blockDim.x);
         __syncthreads();
     }
     const size_t j = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -62,8 +61,7 @@ __global__ __launch_bounds__(256) void k_lq_route(LeavesModel cm, LqTree tr, Cod
     const int lane = threadIdx.x & (kWave - 1);
     int l = -1;
     if (live) {
-        l = general_leaf(cm, r, tr.t) - tr.leaf0;
-        if (l < 0 || l >= tr.n_leaves) l = -1;   // the search left the tree: the row joins no leaf
+        l = local_leaf(general_leaf(cm, r, tr.t), tr.leaf0, tr.n_leaves);
         leaf_out[j] = l;
     }
     const size_t pr = abs_index ? src : jj;
@@ -86,19 +84,11 @@ __global__ __launch_bounds__(256) void k_lq_route(LeavesModel cm, LqTree tr, Cod
     if (in_lds) {
         if (l >= 0) atomicAdd(&lcnt[l], 1u);
         __syncthreads();
-        for (int i = threadIdx.x; i < tr.n_leaves; i += blockDim.x) {
-            const uint32_t c = lcnt[i];
-            if (c) atomicAdd(&counts[i], c);
-        }
+        leaf_acc_flush(lcnt, counts, tr.n_leaves, threadIdx.x, blockDim.x);
     } else {   // one add per distinct leaf of the wave
-        unsigned long long todo = __ballot(l >= 0);
-        while (todo) {   // (wave-uniform)
-            const int first = __ffsll(static_cast<long long>(todo)) - 1;
-            const int k = __shfl(l, first, kWave);
-            const unsigned long long same = __ballot(l == k);
-            if (lane == first) atomicAdd(&counts[k], static_cast<uint32_t>(__popcll(same)));
-            todo &= ~same;
-        }
+        for_each_wave_leaf(l, lane, [&](int k, bool, unsigned long long same, bool leader) {
+            if (leader) atomicAdd(&counts[k], static_cast<uint32_t>(__popcll(same)));
+        });
     }
     if (flag) atomicOr(flag_out, flag);
 }
@@ -314,7 +304,7 @@ void leaf_quantile(const PredictModel &pm, const CodeTables &ct, const CodeRows 
     uint32_t *w = static_cast<uint32_t *>(scratch);
     int32_t *leaf = reinterpret_cast<int32_t *>(w); w += lq_align(static_cast<size_t>(m));
     uint32_t *keys = w; w += lq_align(cells);
-    const LqTree tr{tree, leaf0, n_leaves};
+    const TreeSpan tr{tree, leaf0, n_leaves};
     if (plan.select) {
         uint32_t *prefix = w; w += lq_align(nld);
         uint32_t *rem = w; w += lq_align(nld);

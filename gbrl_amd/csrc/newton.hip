@@ -4,17 +4,13 @@
 //   A row is routed through tree t by the code walk of predict_rowwalk.h (a leaf gets exactly the rows predict_leaves reports), its prediction
 //   p[] -- the trees [0, t) -- and its targets give g and h per output (objective_core.h / newton_core.h: the bits of the host functions), and
 //   q(g), q(h) = llrint((double)x * 2^bits) and a 1 are added to the leaf's int64 accumulators acc[leaf][2 D + 1] = (Sg[D], Sh[D], cnt).
-//   Integer adds only: exact and order-free, so every run and both kernel families produce the same bytes.
+//   The accumulators are leaf_accum.h's, in both of its schemes:
 //
-//   k_newton_sums<DMAX, GREEDY, OBJ>   k_continue_codes' geometry with refit.hip's accumulators: one wave per block, lane = row, the 64 code records
-//                staged by stream_stage_code_tile, p[] (and the logistic targets) in registers and in flight together with the tile, the tree's
-//                (2 D + 1) x leaves accumulators in LDS behind the tile (the tile is a multiple of 256 bytes), tiles in a grid-stride loop, one
-//                64-bit global atomic per non-zero accumulator at the block's end: global atomics are blocks x leaves x (2 D + 1), not rows.
-//                Up to kNewtonWaveLeaves leaves 16 or more lanes meet on every address; there the wave reduces a leaf's contributions with a
-//                butterfly and lane 0 adds the result with a plain LDS add.  Deeper trees use one 64-bit LDS atomic per (lane, output).
-//   k_newton_sums_general<OBJ>         one thread per row, the records read in place, p[] and the targets read from global memory output by output in
+//   k_newton_sums<DMAX, GREEDY, OBJ>   streaming, in k_continue_codes' geometry, W = 2 D + 1: the 64 code records staged by stream_stage_code_tile
+//                (the tile is a multiple of 256 bytes), p[] (and the logistic targets) in registers and in flight together with the tile.
+//   k_newton_sums_general<OBJ>         general: the records read in place, p[] and the targets read from global memory output by output in
 //                rolled loops (softmax: the row's maximum and sum first, then every exp again -- the same bits; nothing is held in a register
-//                row, so D up to 128 needs no scratch), accumulators in global memory, one add per distinct leaf and wave (ballot + butterfly).
+//                row, so D up to 128 needs no scratch).
 //                D > 64, rows too wide for the tile, accumulators that do not fit in LDS, a refused LDS opt-in, a greedy model without node
 //                records, and the cross-check behind GBRL_HIP_CONTINUE_GENERIC=1.
 //
@@ -31,6 +27,7 @@
 //   kNewtonBadPred (a prediction that is not finite).  The caller zeroes accumulators and flag and reads both back in one copy.
 #include "kernels.h"
 #include "kernels_common.h"
+#include "leaf_accum.h"
 #include "predict_rowwalk.h"
 #include "newton_core.h"
 
@@ -43,20 +40,11 @@ namespace kern {
 namespace {
 
 constexpr int kNewtonRows = kStreamRows;   // rows per block of the streaming kernel = one wave
-constexpr int kNewtonWaveLeaves = 4;       // up to this many leaves: reduce within the wave (refit.hip's kRefitWaveLeaves)
 constexpr int kNewtonBlocksPerCu = 4;      // one-wave blocks per CU: every block flushes leaves x (2 D + 1) global atomics once
 
-struct NewtonTree {
-    int t, leaf0, n_leaves;      // the tree, its first global leaf, its leaves
+struct NewtonTree : TreeSpan {
     unsigned long long *acc;     // [n_leaves][2 D + 1], then the flag word
 };
-
-// sum over the wave (every lane ends with it); integers: exact, order-free
-__device__ __forceinline__ long long newton_wave_sum(long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
 
 // a logistic target outside [0, 1] anywhere in the matrix (fit_prepared refuses it before anything changes)
 __global__ __launch_bounds__(256) void k_newton_check_targets(const float *__restrict__ targets, size_t n_el, unsigned long long *__restrict__ flag) {
@@ -80,10 +68,7 @@ __global__ __launch_bounds__(256) void k_newton_sums_general(LeavesModel cm, New
     const int lane = threadIdx.x & (kWave - 1);
     const int W = 2 * D + 1;
     int l = -1;
-    if (live) {
-        l = general_leaf(cm, r, nt.t) - nt.leaf0;
-        if (l < 0 || l >= nt.n_leaves) l = -1;   // the search left the tree: the row joins no sum
-    }
+    if (live) l = local_leaf(general_leaf(cm, r, nt.t), nt.leaf0, nt.n_leaves);
     const size_t pr = abs_index ? src : jj;
     const float *p = pred + pr * D;
     const float *y = targets + pr * (OBJ == kObjSoftmax ? 1 : D);
@@ -101,7 +86,6 @@ __global__ __launch_bounds__(256) void k_newton_sums_general(LeavesModel cm, New
         for (int c = 0; c < D; ++c) S = S + obj_exp_f32(p[c] == mx ? 0.0f : p[c] - mx);
     }
     unsigned flag = 0;
-    const unsigned long long in_tree = __ballot(l >= 0);
 #pragma unroll 1
     for (int d = 0; d < D; ++d) {
         const float pd = p[d];
@@ -125,30 +109,18 @@ __global__ __launch_bounds__(256) void k_newton_sums_general(LeavesModel cm, New
             h = obj_weighted(w, h);
         }
         const long long qg = l >= 0 ? newton_quantise(g, scale) : 0ll, qh = l >= 0 ? newton_quantise(h, scale) : 0ll;
-        // one add per distinct leaf of the wave: every lane of the leaf contributes to a butterfly, the lowest of them adds the result
-        unsigned long long todo = in_tree;
-        while (todo) {   // (wave-uniform)
-            const int first = __ffsll(static_cast<long long>(todo)) - 1;
-            const int k = __shfl(l, first, kWave);
-            const bool mine = l == k;
-            const unsigned long long same = __ballot(mine);
-            const long long sg = newton_wave_sum(mine ? qg : 0ll), sh = newton_wave_sum(mine ? qh : 0ll);
-            if (lane == first) {
+        for_each_wave_leaf(l, lane, [&](int k, bool mine, unsigned long long, bool leader) {
+            const long long sg = wave_sum(mine ? qg : 0ll), sh = wave_sum(mine ? qh : 0ll);
+            if (leader) {
                 unsigned long long *a = nt.acc + static_cast<size_t>(k) * W;
                 if (sg != 0) atomicAdd(&a[d], static_cast<unsigned long long>(sg));
                 if (sh != 0) atomicAdd(&a[D + d], static_cast<unsigned long long>(sh));
             }
-            todo &= ~same;
-        }
+        });
     }
-    unsigned long long todo = in_tree;
-    while (todo) {
-        const int first = __ffsll(static_cast<long long>(todo)) - 1;
-        const int k = __shfl(l, first, kWave);
-        const unsigned long long same = __ballot(l == k);
-        if (lane == first) atomicAdd(&nt.acc[static_cast<size_t>(k) * W + 2 * D], static_cast<unsigned long long>(__popcll(same)));
-        todo &= ~same;
-    }
+    for_each_wave_leaf(l, lane, [&](int k, bool, unsigned long long same, bool leader) {
+        if (leader) atomicAdd(&nt.acc[static_cast<size_t>(k) * W + 2 * D], static_cast<unsigned long long>(__popcll(same)));
+    });
     if (flag) atomicOr(&nt.acc[static_cast<size_t>(nt.n_leaves) * W], static_cast<unsigned long long>(flag));
 }
 
@@ -160,11 +132,8 @@ __global__ __launch_bounds__(kNewtonRows) void k_newton_sums(LeavesModel cm, New
     extern __shared__ __align__(16) uint32_t ntile[];   // [kNewtonRows][stream_code_stride(G)] words, then [n_leaves][2 D + 1] int64
     const int lane = threadIdx.x;
     const int ws = stream_code_stride(cr.groups);
-    const int W = 2 * D + 1;
-    const int na = nt.n_leaves * W;
-    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(ntile + static_cast<size_t>(kNewtonRows) * ws);
-    for (int i = lane; i < na; i += kNewtonRows) lacc[i] = 0ull;
-    const bool few = nt.n_leaves <= kNewtonWaveLeaves;   // (uniform)
+    const LeafAccLds<2> lacc{reinterpret_cast<unsigned long long *>(ntile + static_cast<size_t>(kNewtonRows) * ws), nt.n_leaves, 2 * D + 1};
+    lacc.zero(lane);
     unsigned flag = 0;
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {   // (uniform over the block)
         const int r0 = tile * kNewtonRows;
@@ -187,8 +156,7 @@ __global__ __launch_bounds__(kNewtonRows) void k_newton_sums(LeavesModel cm, New
         int l = -1;
         if (live) {
             const StreamCodeRow x{reinterpret_cast<const uint16_t *>(ntile + lane * ws)};
-            l = stream_leaf<GREEDY>(cm, x, static_cast<const int32_t *>(nullptr), nt.t) - nt.leaf0;
-            if (l < 0 || l >= nt.n_leaves) l = -1;
+            l = local_leaf(stream_leaf<GREEDY>(cm, x, static_cast<const int32_t *>(nullptr), nt.t), nt.leaf0, nt.n_leaves);
         }
         bool bad_p = false, bad_y = false;
         if constexpr (OBJ != kObjGiven) {
@@ -216,57 +184,25 @@ __global__ __launch_bounds__(kNewtonRows) void k_newton_sums(LeavesModel cm, New
                 h[j] = obj_weighted(w, h[j]);
             }
         }
-        if (few) {
-            for (int k = 0; k < nt.n_leaves; ++k) {
-                const bool mine = l == k;
-                const unsigned long long same = __ballot(mine);
-                if (same == 0ull) continue;   // (wave-uniform)
-                unsigned long long *a = lacc + k * W;
-#pragma unroll
-                for (int j = 0; j < DMAX; ++j)
-                    if (j < D) {
-                        const long long sg = newton_wave_sum(mine ? newton_quantise(g[j], scale) : 0ll);
-                        const long long sh = newton_wave_sum(mine ? newton_quantise(h[j], scale) : 0ll);
-                        if (lane == 0) {
-                            a[j] += static_cast<unsigned long long>(sg);
-                            a[D + j] += static_cast<unsigned long long>(sh);
-                        }
-                    }
-                if (lane == 0) a[2 * D] += static_cast<unsigned long long>(__popcll(same));
-            }
-        } else if (l >= 0) {
-            unsigned long long *a = lacc + l * W;
-#pragma unroll
-            for (int j = 0; j < DMAX; ++j)
-                if (j < D) {
-                    atomicAdd(&a[j], static_cast<unsigned long long>(newton_quantise(g[j], scale)));
-                    atomicAdd(&a[D + j], static_cast<unsigned long long>(newton_quantise(h[j], scale)));
-                }
-            atomicAdd(&a[2 * D], 1ull);
-        }
+        lacc.template add<DMAX>(l, lane, D, [&](int v, int j) { return newton_quantise(v == 0 ? g[j] : h[j], scale); });
     }
-    __syncthreads();
-    for (int i = lane; i < na; i += kNewtonRows) {
-        const unsigned long long v = lacc[i];
-        if (v) atomicAdd(&nt.acc[i], v);
-    }
-    if (flag) atomicOr(&nt.acc[na], static_cast<unsigned long long>(flag));
+    lacc.flush(nt.acc, lane);
+    if (flag) atomicOr(&nt.acc[nt.n_leaves * lacc.W], static_cast<unsigned long long>(flag));
 }
 
 template <int DMAX, bool GREEDY, int OBJ, bool WEIGHTED>
 bool launch_newton_sums(const LeavesModel &cm, const NewtonTree &nt, const CodeRows &cr, int m, int D, const float *pred, const float *targets, int abs_index,
                         double scale, const float *weights, hipStream_t s) {
-    const size_t lds = stream_code_tile_bytes(cr.groups) + static_cast<size_t>(nt.n_leaves) * (2 * D + 1) * sizeof(unsigned long long);
-    if (lds > kStreamLdsBudget) return false;   // rows too wide, or a tree with too many accumulators, for the LDS of a CU
-    static StreamLdsOptIn optin;
-    if (!optin.ok(k_newton_sums<DMAX, GREEDY, OBJ, WEIGHTED>, lds)) return false;
     const int n_tiles = (m + kNewtonRows - 1) / kNewtonRows;
-    const int per_cu = static_cast<int>(std::min<size_t>(kNewtonBlocksPerCu, std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1))));
-    const int blocks = std::min(n_tiles, stream_cu_count() * per_cu);
+    const LeafAccPlan plan = leaf_acc_plan(stream_code_tile_bytes(cr.groups), static_cast<size_t>(nt.n_leaves) * (2 * D + 1) * sizeof(unsigned long long),
+                                           n_tiles, kNewtonBlocksPerCu, stream_cu_count());
+    if (!plan.fits) return false;   // rows too wide, or a tree with too many accumulators, for the LDS of a CU
+    static StreamLdsOptIn optin;
+    if (!optin.ok(k_newton_sums<DMAX, GREEDY, OBJ, WEIGHTED>, plan.lds)) return false;
     const bool d4 = (D & 3) == 0;
     const int vec_p = d4 && (reinterpret_cast<uintptr_t>(pred) & 15) == 0;
     const int vec_y = d4 && OBJ != kObjSoftmax && (reinterpret_cast<uintptr_t>(targets) & 15) == 0;
-    hipLaunchKernelGGL((k_newton_sums<DMAX, GREEDY, OBJ, WEIGHTED>), dim3(blocks), dim3(kNewtonRows), lds, s, cm, nt, cr, m, n_tiles, D, pred, targets, abs_index,
+    hipLaunchKernelGGL((k_newton_sums<DMAX, GREEDY, OBJ, WEIGHTED>), dim3(plan.blocks), dim3(kNewtonRows), plan.lds, s, cm, nt, cr, m, n_tiles, D, pred, targets, abs_index,
                        scale, vec_p, vec_y, weights);
     return true;
 }
@@ -299,7 +235,7 @@ bool newton_leaf_sums(const PredictModel &pm, const CodeTables &ct, const CodeRo
     cm.cond_pack = ct.cond_pack;
     cm.grd_nodes = ct.grd_nodes;
     cm.feature_bins = ct.bins;
-    const NewtonTree nt{tree, leaf0, n_leaves, acc};
+    const NewtonTree nt{{tree, leaf0, n_leaves}, acc};
     const double scale = std::ldexp(1.0, bits);
     const float *y = static_cast<const float *>(targets);
     const int ai = abs_index ? 1 : 0;

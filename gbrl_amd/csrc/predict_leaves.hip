@@ -27,9 +27,8 @@
 //                            issues one global add per distinct leaf and wave.
 #include "kernels.h"
 #include "kernels_common.h"
+#include "leaf_accum.h"
 #include "predict_rowwalk.h"
-
-#include <algorithm>
 
 namespace gbrl {
 namespace kern {
@@ -60,15 +59,10 @@ __global__ __launch_bounds__(256) void k_leaf_counts_general(LeavesModel cm, con
     const int lane = threadIdx.x & (kWave - 1);
     for (int t = start_tree; t < stop_tree; ++t) {   // (uniform over the block)
         const int leaf = live ? general_leaf(cm, r, t) : -1;
-        // one add per distinct leaf of the wave: the lowest lane that holds it adds the number of lanes that do
-        unsigned long long todo = __ballot(leaf >= 0);
-        while (todo) {   // (wave-uniform)
-            const int src = __ffsll(static_cast<long long>(todo)) - 1;
-            const int l = __shfl(leaf, src, kWave);
-            const unsigned long long same = __ballot(leaf == l);
-            if (lane == src) atomicAdd(&counts[l], static_cast<uint32_t>(__popcll(same)));
-            todo &= ~same;
-        }
+        // the global leaf is the counter: the lowest lane that holds it adds the number of lanes that do
+        for_each_wave_leaf(leaf, lane, [&](int l, bool, unsigned long long same, bool leader) {
+            if (leader) atomicAdd(&counts[l], static_cast<uint32_t>(__popcll(same)));
+        });
     }
 }
 
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(kLeavesRows) void k_leaf_counts(LeavesModel cm, con
     const int lane = threadIdx.x;
     const int xs = F | 1;
     uint32_t *cnt = reinterpret_cast<uint32_t *>(ctile_ + static_cast<size_t>(kLeavesRows) * xs);
-    for (int i = lane; i < n_counters; i += kLeavesRows) cnt[i] = 0u;
+    leaf_acc_zero(cnt, n_counters, lane, kLeavesRows);
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {   // (uniform over the block)
         const int r0 = tile * kLeavesRows;
         const int rows = min(kLeavesRows, n - r0);
@@ -141,10 +135,7 @@ __global__ __launch_bounds__(kLeavesRows) void k_leaf_counts(LeavesModel cm, con
         }
     }
     __syncthreads();
-    for (int i = lane; i < n_counters; i += kLeavesRows) {
-        const uint32_t v = cnt[i];
-        if (v) atomicAdd(&counts[leaf_base + i], v);
-    }
+    leaf_acc_flush(cnt, counts + leaf_base, n_counters, lane, kLeavesRows);
 }
 
 template <bool GREEDY>
@@ -163,15 +154,12 @@ bool launch_leaves(const LeavesModel &cm, const float *obs, int F, const int32_t
 template <bool GREEDY>
 bool launch_leaf_counts(const LeavesModel &cm, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree, int stop_tree,
                         int leaf_base, int n_counters, uint32_t *counts, hipStream_t s) {
-    const size_t lds = stream_tile_bytes(F) + static_cast<size_t>(n_counters) * sizeof(uint32_t);
-    if (lds > kStreamLdsBudget) return false;   // rows too wide for an LDS tile beside the counters
-    static StreamLdsOptIn optin;
-    if (!optin.ok(k_leaf_counts<GREEDY>, lds)) return false;
     const int n_tiles = (n + kLeavesRows - 1) / kLeavesRows;
-    // as many blocks as the chip holds at once (160 KiB of LDS per CU, at most 8 one-wave blocks counted per CU): each then flushes once
-    const int per_cu = static_cast<int>(std::min<size_t>(8, std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1))));
-    const int blocks = std::min(n_tiles, stream_cu_count() * per_cu);
-    hipLaunchKernelGGL((k_leaf_counts<GREEDY>), dim3(blocks), dim3(kLeavesRows), lds, s, cm, obs, F, cat_codes, Fc, n, n_tiles, start_tree, stop_tree,
+    const LeafAccPlan plan = leaf_acc_plan(stream_tile_bytes(F), static_cast<size_t>(n_counters) * sizeof(uint32_t), n_tiles, 8, stream_cu_count());
+    if (!plan.fits) return false;   // rows too wide for an LDS tile beside the counters
+    static StreamLdsOptIn optin;
+    if (!optin.ok(k_leaf_counts<GREEDY>, plan.lds)) return false;
+    hipLaunchKernelGGL((k_leaf_counts<GREEDY>), dim3(plan.blocks), dim3(kLeavesRows), plan.lds, s, cm, obs, F, cat_codes, Fc, n, n_tiles, start_tree, stop_tree,
                        leaf_base, n_counters, counts);
     return true;
 }

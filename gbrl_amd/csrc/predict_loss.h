@@ -15,12 +15,8 @@ namespace {
 
 constexpr int kStagedRows = kStreamRows;   // rows per wave = rows per loss partial, in every kernel
 
-// sum of the wave's 64 values in a fixed order (xor butterfly: every lane ends with the same bits); called by whole waves only
-__device__ __forceinline__ double staged_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+// sum of the wave's 64 values in a fixed order (leaf_accum.h's xor butterfly, offsets 32 down to 1: every lane ends with the same bits); whole waves only
+__device__ __forceinline__ double staged_wave_sum(double v) { return wave_sum(v); }
 
 // sum_j (double)g_j^2 of one row, j ascending; g_j = fl32(p_j - y_j) (loss.cpp:42-56).  (double)g * (double)g is exact.
 template <int DMAX>

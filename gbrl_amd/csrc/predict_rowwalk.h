@@ -26,6 +26,7 @@
 
 #include "kernels.h"
 #include "kernels_common.h"
+#include "leaf_accum.h"
 
 namespace gbrl {
 namespace kern {
@@ -323,7 +324,7 @@ inline bool leaves_streamable(const PredictModel &pm, bool generic) {
 // ... and for a chain: every output owned by at most one optimizer (owner[] and coef_cover are valid), a row's outputs in registers
 inline bool chain_streamable(const PredictModel &pm, bool generic) { return leaves_streamable(pm, generic) && pm.coef_ok && pm.D <= 64; }
 
-constexpr size_t kStreamLdsBudget = 156 * 1024;   // the dynamic LDS the streaming kernels opt in to
+// (kStreamLdsBudget, the dynamic LDS the streaming kernels opt in to, is leaf_accum.h's: its launch plan is tested without a device)
 inline size_t stream_tile_bytes(int F) { return static_cast<size_t>(kStreamRows) * (F | 1) * sizeof(float); }
 inline size_t stream_code_tile_bytes(int G) { return static_cast<size_t>(kStreamRows) * ((G * 8) | 1) * sizeof(uint32_t); }
 

@@ -4,16 +4,10 @@
 //   accumulate   routes every row through tree t (the walks of predict_rowwalk.h, so a leaf gets exactly the rows predict_leaves reports),
 //                stores the row's global leaf to leaf_idx[n] and adds q = llrint((double)fl32(P - y) * 2^lbits) per output, and 1, to the leaf's
 //                int64 accumulators.  2^lbits comes from gmax[t], the bits of max |g| the previous apply pass left on the device, through
-//                leaf_sum_bits_dev -- the step's own rule.  Integer adds only: exact and order-free, so every run and both kernel families
-//                produce the same bytes.
-//     k_refit_accum<DMAX, GREEDY>   k_continue / k_leaf_counts' layout: one wave per block, 64 rows in LDS at stride F | 1, the tree's
-//                (D + 1) x leaves accumulators in LDS behind the tile, tiles in a grid-stride loop, one 64-bit global atomic per non-zero
-//                accumulator at the block's end -- global atomics are blocks x leaves x (D + 1), not rows.  The LDS is private to the wave.
-//                A tree of at most kRefitWaveLeaves leaves puts 16 or more lanes on every address; there the wave reduces each leaf's
-//                contributions with a butterfly and lane 0 adds the result with a plain LDS add.  Deeper trees use ds_add_u64 per lane.
-//     k_refit_accum_general         one thread per row, rows from global memory, accumulators in global memory, one add per distinct leaf
-//                and wave (ballot + butterfly).  Rows too wide for LDS, greedy ensembles without node records, more than 64 outputs, trees
-//                whose accumulators do not fit behind the tile, GBRL_HIP_REFIT_GENERIC=1.
+//                leaf_sum_bits_dev -- the step's own rule.  The accumulators are leaf_accum.h's, in both of its schemes:
+//     k_refit_accum<DMAX, GREEDY>   streaming, in k_continue / k_leaf_counts' layout (64 rows in LDS at stride F | 1), W = D + 1.
+//     k_refit_accum_general         general, rows from global memory.  Rows too wide for LDS, greedy ensembles without node records, more than
+//                64 outputs, trees whose accumulators do not fit behind the tile, GBRL_HIP_REFIT_GENERIC=1.
 //   finalize     k_refit_finalize: new value per (leaf, output) from the sums, the count, the old value and decay, into new_values.
 //   apply        k_refit_apply: P = fma(-rate, new value, P) through leaf_idx (the rows X are not read again), then max |fl32(P - y)| of the
 //                next tree (behind the last tree: of the final prediction) by an integer atomicMax on the float bits (a maximum is
@@ -25,9 +19,8 @@
 // predict_continue.hip, predict_staged.hip and predict_leaves.hip.
 #include "kernels.h"
 #include "kernels_common.h"
+#include "leaf_accum.h"
 #include "predict_rowwalk.h"
-
-#include <algorithm>
 
 namespace gbrl {
 namespace kern {
@@ -35,11 +28,9 @@ namespace kern {
 namespace {
 
 constexpr int kRefitRows = kStreamRows;   // rows per block of the streaming kernel = one wave
-constexpr int kRefitWaveLeaves = 4;       // up to this many leaves: reduce within the wave (>= 16 lanes per address otherwise)
 constexpr int kRefitBlocksPerCu = 4;      // one-wave blocks per CU: every block flushes leaves x (D + 1) global atomics once
 
-struct RefitTree {
-    int t, leaf0, n_leaves;          // the tree, its first global leaf, its leaves
+struct RefitTree : TreeSpan {
     const uint32_t *gmax;            // bits of max |g| before this tree
     uint32_t *gmax_next;             // where the apply pass leaves the next tree's (behind the last tree: max |g| of the final prediction)
     unsigned long long *acc;         // [n_leaves][D + 1]
@@ -55,12 +46,6 @@ __device__ __forceinline__ double refit_scale(int n, const uint32_t *gmax) {
     return ldexp(1.0, leaf_sum_bits_dev(static_cast<long long>(n), __uint_as_float(*gmax)));
 }
 __device__ __forceinline__ long long refit_quantise(float g, double scale) { return __double2ll_rn(__dmul_rn(static_cast<double>(g), scale)); }
-// sum over the wave (every lane ends with it); integers: exact, order-free
-__device__ __forceinline__ long long refit_wave_sum(long long v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
 // maximum over the block, then one atomic per block
 __device__ __forceinline__ void refit_block_max(uint32_t m, uint32_t *dst) {
     __shared__ uint32_t sh[4];
@@ -100,25 +85,17 @@ __global__ __launch_bounds__(256) void k_refit_accum_general(LeavesModel cm, Ref
     if (live) {
         const int leaf = general_leaf(cm, r, rt.t);
         leaf_idx[row] = leaf;
-        l = leaf - rt.leaf0;
-        if (l < 0 || l >= rt.n_leaves) l = -1;   // the search left the tree: the row joins no sum
+        l = local_leaf(leaf, rt.leaf0, rt.n_leaves);
     }
     const float *p = P + rr * D, *y = Y + rr * D;
-    // one add per distinct leaf of the wave: every lane of the leaf contributes to a butterfly, the lowest of them adds the result
-    unsigned long long todo = __ballot(l >= 0);
-    while (todo) {   // (wave-uniform)
-        const int src = __ffsll(static_cast<long long>(todo)) - 1;
-        const int k = __shfl(l, src, kWave);
-        const bool mine = l == k;
-        const unsigned long long same = __ballot(mine);
+    for_each_wave_leaf(l, lane, [&](int k, bool mine, unsigned long long same, bool leader) {
         unsigned long long *a = rt.acc + static_cast<size_t>(k) * (D + 1);
         for (int j = 0; j < D; ++j) {
-            const long long q = refit_wave_sum(mine ? refit_quantise(__fsub_rn(p[j], y[j]), scale) : 0ll);
-            if (lane == src && q != 0) atomicAdd(&a[j], static_cast<unsigned long long>(q));
+            const long long q = wave_sum(mine ? refit_quantise(__fsub_rn(p[j], y[j]), scale) : 0ll);
+            if (leader && q != 0) atomicAdd(&a[j], static_cast<unsigned long long>(q));
         }
-        if (lane == src) atomicAdd(&a[D], static_cast<unsigned long long>(__popcll(same)));
-        todo &= ~same;
-    }
+        if (leader) atomicAdd(&a[D], static_cast<unsigned long long>(__popcll(same)));
+    });
 }
 
 template <int DMAX, bool GREEDY>
@@ -129,11 +106,9 @@ __global__ __launch_bounds__(kRefitRows) void k_refit_accum(LeavesModel cm, Refi
     extern __shared__ float rtile[];   // [kRefitRows][F | 1] floats, then [n_leaves][D + 1] int64 (the tile is a multiple of 256 bytes)
     const int lane = threadIdx.x;
     const int xs = F | 1;
-    const int na = rt.n_leaves * (D + 1);
-    unsigned long long *lacc = reinterpret_cast<unsigned long long *>(rtile + static_cast<size_t>(kRefitRows) * xs);
-    for (int i = lane; i < na; i += kRefitRows) lacc[i] = 0ull;
+    const LeafAccLds<1> lacc{reinterpret_cast<unsigned long long *>(rtile + static_cast<size_t>(kRefitRows) * xs), rt.n_leaves, D + 1};
+    lacc.zero(lane);
     const double scale = refit_scale(n, rt.gmax);
-    const bool few = rt.n_leaves <= kRefitWaveLeaves;   // (uniform)
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {   // (uniform over the block)
         const int r0 = tile * kRefitRows;
         const int rows = min(kRefitRows, n - r0);
@@ -149,38 +124,13 @@ __global__ __launch_bounds__(kRefitRows) void k_refit_accum(LeavesModel cm, Refi
         if (live) {
             const int leaf = stream_leaf<GREEDY>(cm, rtile + lane * xs, cat_codes ? cat_codes + row * Fc : nullptr, rt.t);
             leaf_idx[row] = leaf;
-            l = leaf - rt.leaf0;
-            if (l < 0 || l >= rt.n_leaves) l = -1;
+            l = local_leaf(leaf, rt.leaf0, rt.n_leaves);
         }
 #pragma unroll
         for (int j = 0; j < DMAX; ++j) g[j] = __fsub_rn(g[j], y[j]);
-        if (few) {
-            for (int k = 0; k < rt.n_leaves; ++k) {
-                const bool mine = l == k;
-                const unsigned long long same = __ballot(mine);
-                if (same == 0ull) continue;   // (wave-uniform)
-                unsigned long long *a = lacc + k * (D + 1);
-#pragma unroll
-                for (int j = 0; j < DMAX; ++j)
-                    if (j < D) {
-                        const long long q = refit_wave_sum(mine ? refit_quantise(g[j], scale) : 0ll);
-                        if (lane == 0) a[j] += static_cast<unsigned long long>(q);
-                    }
-                if (lane == 0) a[D] += static_cast<unsigned long long>(__popcll(same));
-            }
-        } else if (l >= 0) {
-            unsigned long long *a = lacc + l * (D + 1);
-#pragma unroll
-            for (int j = 0; j < DMAX; ++j)
-                if (j < D) atomicAdd(&a[j], static_cast<unsigned long long>(refit_quantise(g[j], scale)));
-            atomicAdd(&a[D], 1ull);
-        }
+        lacc.template add<DMAX>(l, lane, D, [&](int, int j) { return refit_quantise(g[j], scale); });
     }
-    __syncthreads();
-    for (int i = lane; i < na; i += kRefitRows) {
-        const unsigned long long v = lacc[i];
-        if (v) atomicAdd(&rt.acc[i], v);
-    }
+    lacc.flush(rt.acc, lane);
 }
 
 // ------------------------------------------------------------------------------------------------------------ finalize
@@ -227,15 +177,14 @@ __global__ __launch_bounds__(256) void k_refit_apply(RefitTree rt, ChainRates rr
 template <int DMAX, bool GREEDY>
 bool launch_refit_accum(const LeavesModel &cm, const RefitTree &rt, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int D, const float *P,
                         const float *Y, int32_t *leaf_idx, hipStream_t s) {
-    const size_t lds = stream_tile_bytes(F) + static_cast<size_t>(rt.n_leaves) * (D + 1) * sizeof(unsigned long long);
-    if (lds > kStreamLdsBudget) return false;   // rows too wide, or a tree with too many accumulators, for the LDS of a CU
-    static StreamLdsOptIn optin;
-    if (!optin.ok(k_refit_accum<DMAX, GREEDY>, lds)) return false;
     const int n_tiles = (n + kRefitRows - 1) / kRefitRows;
-    const int per_cu = static_cast<int>(std::min<size_t>(kRefitBlocksPerCu, std::max<size_t>(1, (160 * 1024) / std::max<size_t>(lds, 1))));
-    const int blocks = std::min(n_tiles, stream_cu_count() * per_cu);
+    const LeafAccPlan plan = leaf_acc_plan(stream_tile_bytes(F), static_cast<size_t>(rt.n_leaves) * (D + 1) * sizeof(unsigned long long), n_tiles,
+                                           kRefitBlocksPerCu, stream_cu_count());
+    if (!plan.fits) return false;   // rows too wide, or a tree with too many accumulators, for the LDS of a CU
+    static StreamLdsOptIn optin;
+    if (!optin.ok(k_refit_accum<DMAX, GREEDY>, plan.lds)) return false;
     const int vec_io = (D & 3) == 0 && ((reinterpret_cast<uintptr_t>(P) | reinterpret_cast<uintptr_t>(Y)) & 15) == 0;
-    hipLaunchKernelGGL((k_refit_accum<DMAX, GREEDY>), dim3(blocks), dim3(kRefitRows), lds, s, cm, rt, obs, F, cat_codes, Fc, n, n_tiles, D, P, Y, leaf_idx,
+    hipLaunchKernelGGL((k_refit_accum<DMAX, GREEDY>), dim3(plan.blocks), dim3(kRefitRows), plan.lds, s, cm, rt, obs, F, cat_codes, Fc, n, n_tiles, D, P, Y, leaf_idx,
                        vec_io);
     return true;
 }

@@ -339,6 +339,21 @@ def test_mirror_records_equal_the_model_rules_on_random_ensembles(tmp_path):
     assert len(out.stdout.strip().split("\n")) == 8, out.stdout
 
 
+def test_leaf_accumulator_launch_plan_keeps_the_launchers_numbers(tmp_path):
+    """leaf_accum.h's host side without a device (tests/cxx/leaf_accum_check.cpp, built with the address and undefined-behaviour
+    sanitizers): leaf_acc_plan says "fits" up to kStreamLdsBudget and not one byte further -- the only place the fallback edge of the
+    refit, Newton and leaf-count launchers is pinned exactly; blocks per CU are never 0, blocks never exceed the tiles and are at
+    least 1 when there is a tile; and for a table of shapes the plan gives the LDS bytes and block counts that each launcher's own
+    expressions gave, evaluated by hand."""
+    import subprocess
+    exe = tmp_path / "leaf_accum_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "gbrl_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cxx", "leaf_accum_check.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and "all sections passed" in out.stdout, out.stdout + out.stderr
+    assert len(out.stdout.strip().split("\n")) == 4, out.stdout
+
+
 def test_register_tile_asm_header_is_current_and_the_compiler_keeps_out_of_the_bank(tmp_path):
     """predict_reg.hip keeps a row tile in a bank of VGPRs that the compiler must never allocate (amdgpu_num_vgpr caps it below the
     bank; the bank is only named in clobber lists).  (1) The generated assembly text is the generator's current output.  (2) Audit of
