@@ -1136,6 +1136,26 @@ int gbrl_hip_hist_probe(gbrl_hip_hist_probe_t *a) {
     });
 }
 
+int gbrl_hip_score_probe(gbrl_hip_score_probe_t *a) {
+    if (!a) return GBRL_HIP_E_INVALID;
+    return guarded([&] {
+        const char *why = "";
+        const int rc = gbrl::kern::score_selftest(*a, &why);
+        if (rc == gbrl::kern::kHistProbeInvalid) throw gbrl::InvalidArgument(why);
+        if (rc != gbrl::kern::kHistProbeOk) throw gbrl::HipError("score kernels failed (no HIP device?)");
+    });
+}
+
+int gbrl_hip_rows_probe(gbrl_hip_rows_probe_t *a) {
+    if (!a) return GBRL_HIP_E_INVALID;
+    return guarded([&] {
+        const char *why = "";
+        const int rc = gbrl::kern::rows_selftest(*a, &why);
+        if (rc == gbrl::kern::kHistProbeInvalid) throw gbrl::InvalidArgument(why);
+        if (rc != gbrl::kern::kHistProbeOk) throw gbrl::HipError("row kernels failed (no HIP device?)");
+    });
+}
+
 int gbrl_hip_cat_rank_stats(const char *cells, int n, int n_cat, const float *grads, int output_dim, int cap, int32_t *feature,
                             int32_t *first_row, int32_t *count, float *total, int *n_distinct) {
     if (!cells || !grads || !feature || !first_row || !count || !total || !n_distinct || n < 1 || n_cat < 1 || output_dim < 1 || cap < 1) return GBRL_HIP_E_INVALID;

@@ -8,6 +8,9 @@
 #include <cstdint>
 #include <vector>
 
+struct gbrl_hip_score_probe_t;   // include/gbrl_hip.h (diagnostics)
+struct gbrl_hip_rows_probe_t;
+
 namespace gbrl {
 namespace kern {
 
@@ -289,6 +292,10 @@ struct HistProbe {
 };
 enum { kHistProbeOk = 0, kHistProbeInvalid = 1, kHistProbeDevice = 2 };
 int hist_selftest(HistProbe &p, const char **why /*what was refused (static text)*/);
+// diagnostics (gbrl_hip_score_probe, gbrl_hip_rows_probe): the kernels of step_score.hip / step_partition.hip on host arrays, through the launchers a
+// step uses.  The same return codes; everything is validated on the host before the first HIP call.
+int score_selftest(::gbrl_hip_score_probe_t &p, const char **why);
+int rows_selftest(::gbrl_hip_rows_probe_t &p, const char **why);
 // hist[slot_map ? slot_map[k] : k] = sum of the partials of chunk-slot k
 void hist_reduce(const int32_t *partials, const int32_t *slot_chunk_begin /*[n_slots+1]*/, const int32_t *slot_map, int n_slots,
                  int n_groups, int FG, int NB, int D, int Fp, int64_t *hist, hipStream_t s,

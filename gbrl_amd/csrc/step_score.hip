@@ -8,8 +8,11 @@
 #include "kernels.h"
 #include "kernels_common.h"
 #include "score_common.h"
+#include "../../include/gbrl_hip.h"
 
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 namespace gbrl {
 namespace kern {
@@ -496,6 +499,131 @@ void resolve_splits(const float *part_v, const int32_t *part_i, int n_parts, int
                        ref_to_internal, cand_slot, slots, hist_local, hist_global, Fp, NB, D, out, counts4, max_front, seg_start, cursors, thr_keys, B,
                        static_cast<char *>(pub), pub_flag, pub_seq, pub_done, hist_prev, sub_par, sub_sib,
                        near ? near->part_s : nullptr, near ? near->part_n : nullptr, near ? near->rel : 0.0f, near ? near->parent : nullptr, near ? near->is_root : nullptr, near ? near->cosine : 1, near ? near->rows : 0);
+}
+
+// ------------------------------------------------------------------------------------------------------------ diagnostics
+
+// gbrl_hip_score_probe: host arrays in, host arrays out -- score_candidates and, on request, argmax (the oblivious form, the only one a step
+// reaches) and resolve_splits behind it, launched as a step launches them (pub = nullptr).  Every output array goes to the device holding the
+// caller's values and comes back afterwards, so a cell no kernel stored keeps them.  Every index a kernel will form is checked here first.
+int score_selftest(::gbrl_hip_score_probe_t &p, const char **why) {
+    const auto refuse = [&](const char *text) { *why = text; return static_cast<int>(kHistProbeInvalid); };
+    *why = "";
+    const int NB = p.n_classes, D = p.output_dim, W = D + 1, Fp = p.Fp, B = p.B, n_cand = p.n_cand, n_nodes = p.n_nodes;
+    if (p.n_hist_nodes < 1 || p.n_hist_nodes > 4096 || p.n_prev_nodes < 0 || p.n_prev_nodes > 4096 || n_nodes < 1 || n_nodes > p.n_hist_nodes || Fp < 1 || Fp > 4096 || NB < 2 || NB > 65535 ||
+        D < 1 || D > 512 || p.n_table_slots < 1 || p.n_table_slots > Fp || B < 1 || B > 65535 || n_cand < 1 || n_cand > (1 << 22) || p.sbits < 0 || p.sbits > 40 || p.min_data < 0 ||
+        p.max_front < n_nodes || p.max_front > 65536 || p.n_parts < 0 || p.n_parts > (1 << 20))
+        return refuse("score_probe: a size is out of range");
+    if (p.do_score < 0 || p.do_score > 2 || (p.do_argmax != 0 && p.do_argmax != 1) || (p.do_resolve != 0 && p.do_resolve != 1) || (p.do_score == 2 && p.do_argmax) ||
+        (p.do_score == 2 && p.oblivious) || (p.do_argmax && !p.oblivious && p.do_resolve))
+        return refuse("score_probe: do_score is 0, 1 or 2, do_argmax and do_resolve 0 or 1; the fused greedy form has no argmax stage and argmax is the oblivious form");
+    if (static_cast<size_t>(NB + 2) * W * sizeof(int64_t) > 150 * 1024) return refuse("score_probe: (n_classes + 2) x (output_dim + 1) x 8 bytes does not fit the LDS");
+    const size_t node_elems = static_cast<size_t>(Fp) * NB * W;
+    if (node_elems * std::max(p.n_hist_nodes, p.n_prev_nodes) > (size_t{1} << 28) || static_cast<size_t>(n_nodes) * n_cand > (size_t{1} << 26))
+        return refuse("score_probe: a size is out of range");
+    if (!p.hist || !p.slots || !p.thr || !p.path_len || !p.path_slot || !p.path_bin || !p.path_val || !p.cand_w || !p.cand_ref || !p.ref_to_internal || !p.cand_slot || !p.is_root ||
+        !p.parent)
+        return refuse("score_probe: null array");
+    const bool uses_parts = p.do_score == 2 || p.do_argmax || p.do_resolve;
+    if ((p.do_score == 1 || p.do_argmax) && !p.scores) return refuse("score_probe: null array");
+    if (uses_parts && (!p.part_v || !p.part_i || p.n_parts < 1)) return refuse("score_probe: null array");
+    if (p.part_n && !p.part_s) return refuse("score_probe: part_n needs part_s");
+    if (p.do_resolve && (!p.best_idx || !p.best_score || !p.counts4 || !p.splits || !p.cursors)) return refuse("score_probe: null array");
+    if (p.do_resolve && p.near && !p.part_s) return refuse("score_probe: near-tie detection needs part_s");
+    if (p.slot0 < 0 || p.n_slots < 1 || p.n_slots > p.n_table_slots - p.slot0) return refuse("score_probe: the launch window leaves the slot table");
+    if (p.do_score == 2 && p.n_parts != p.n_slots) return refuse("score_probe: n_parts must be n_slots after the fused greedy form");
+    if (p.do_argmax && p.n_parts != argmax_parts(n_cand)) return refuse("score_probe: n_parts must be ceil(n_cand / 256) after argmax");
+    for (int f = 0; f < p.n_table_slots; ++f) {
+        const int32_t is_cat = p.slots[4 * f], nc = p.slots[4 * f + 1], base = p.slots[4 * f + 2];
+        if ((is_cat != 0 && is_cat != 1) || nc < 0 || base < 0 || base > n_cand || nc > n_cand - base) return refuse("score_probe: a slot's candidates leave [0, n_cand)");
+        if (nc + 1 > NB || (!is_cat && nc > B)) return refuse("score_probe: a slot has more candidates than classes or thresholds");
+    }
+    if (p.sub_par) {
+        if (!p.sub_sib) return refuse("score_probe: sub_par without sub_sib");
+        for (int k = 0; k < n_nodes; ++k) {
+            if (p.sub_par[k] >= 0 && (!p.hist_prev || p.sub_par[k] >= p.n_prev_nodes)) return refuse("score_probe: sub_par names a node outside hist_prev");
+            if (p.sub_par[k] >= 0 && p.sub_sib[k] >= p.n_hist_nodes) return refuse("score_probe: sub_sib names a node outside hist");
+        }
+    }
+    for (int k = 0; k < n_nodes; ++k)
+        if (p.path_len[k] < 0 || p.path_len[k] > kMaxPath) return refuse("score_probe: path_len above 32");
+    {
+        std::vector<char> seen(n_cand, 0);
+        for (int j = 0; j < n_cand; ++j) {
+            const int32_t r = p.cand_ref[j];
+            if (r < 0 || r >= n_cand || seen[r]) return refuse("score_probe: cand_ref is no permutation of [0, n_cand)");
+            seen[r] = 1;
+        }
+    }
+    for (int j = 0; j < n_cand; ++j) {
+        const int32_t i = p.ref_to_internal[j], f = p.cand_slot[j];
+        if (i < 0 || i >= n_cand) return refuse("score_probe: ref_to_internal leaves [0, n_cand)");
+        if (f < 0 || f >= p.n_table_slots || j < p.slots[4 * f + 2] || j >= p.slots[4 * f + 2] + p.slots[4 * f + 1]) return refuse("score_probe: cand_slot does not name the slot that holds the candidate");
+    }
+    const size_t n_part = uses_parts ? static_cast<size_t>(n_nodes) * p.n_parts : 0;
+    if (p.do_resolve && p.do_score != 2 && !p.do_argmax) {   // part_* as given: an index that can win must be a candidate
+        const int rows_read = p.oblivious ? 1 : n_nodes;
+        for (size_t q = 0; q < static_cast<size_t>(rows_read) * p.n_parts; ++q)
+            if ((p.part_i[q] < 0 || p.part_i[q] >= n_cand) && !(p.part_i[q] == 0x7fffffff && p.part_v[q] == -INFINITY)) return refuse("score_probe: a given part_i is no candidate");
+    }
+
+    // ---- device half
+    struct Dev { void *p = nullptr; ~Dev() { if (p) (void)hipFree(p); } };
+    const auto up = [](Dev &d, const void *src, size_t bytes) {
+        if (hipMalloc(&d.p, std::max<size_t>(16, bytes)) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return !src || bytes == 0 || hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+    };
+    const auto down = [](void *dst, const Dev &d, size_t bytes) { return !dst || bytes == 0 || hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost) == hipSuccess; };
+    Dev dhist, dprev, dglob, dpar, dsib, dslots, dthr, dkeys, dplen, dpslot, dpbin, dpval, dw, dref, dr2i, dcslot, droot, dseg, dsc, dscores, dparent, dpv, dps, dbs, dnr, dpi, dpn, dbi,
+        dsplits, dcur, dcnt;
+    StepScales sc{};
+    sc.inv_scale = std::ldexp(1.0, -p.sbits); sc.leaf_scale = 1.0; sc.scale = std::ldexp(1.0f, p.sbits); sc.sbits = p.sbits;
+    const size_t nk = static_cast<size_t>(n_nodes), n_sc = nk * n_cand, mf = static_cast<size_t>(p.max_front);
+    bool ok = up(dhist, p.hist, 8 * node_elems * p.n_hist_nodes) && (!p.hist_prev || up(dprev, p.hist_prev, 8 * node_elems * p.n_prev_nodes)) &&
+              (!p.hist_global || up(dglob, p.hist_global, 8 * node_elems * nk)) && (!p.sub_par || (up(dpar, p.sub_par, 4 * nk) && up(dsib, p.sub_sib, 4 * nk))) &&
+              up(dslots, p.slots, sizeof(FeatureSlot) * p.n_table_slots) && up(dthr, p.thr, 4 * static_cast<size_t>(p.n_table_slots) * B) &&
+              (!p.thr_keys || up(dkeys, p.thr_keys, 4 * static_cast<size_t>(p.n_table_slots) * B)) && up(dplen, p.path_len, 4 * nk) && up(dpslot, p.path_slot, 4 * nk * kMaxPath) &&
+              up(dpbin, p.path_bin, 4 * nk * kMaxPath) && up(dpval, p.path_val, 4 * nk * kMaxPath) && up(dw, p.cand_w, 4 * static_cast<size_t>(n_cand)) &&
+              up(dref, p.cand_ref, 4 * static_cast<size_t>(n_cand)) && up(dr2i, p.ref_to_internal, 4 * static_cast<size_t>(n_cand)) && up(dcslot, p.cand_slot, 4 * static_cast<size_t>(n_cand)) &&
+              up(droot, p.is_root, 4 * nk) && (!p.seg_start || up(dseg, p.seg_start, 4 * nk)) && up(dsc, &sc, sizeof(sc)) && (!p.scores || up(dscores, p.scores, 4 * n_sc)) &&
+              up(dparent, p.parent, 4 * nk) && (!p.cand_nr || up(dnr, p.cand_nr, 4 * n_sc)) && (!n_part || (up(dpv, p.part_v, 4 * n_part) && up(dpi, p.part_i, 4 * n_part))) &&
+              (!n_part || !p.part_s || up(dps, p.part_s, 4 * n_part)) && (!n_part || !p.part_n || up(dpn, p.part_n, 4 * n_part));
+    if (ok && p.do_resolve)
+        ok = up(dbi, p.best_idx, 4 * mf) && up(dbs, p.best_score, 4 * mf) && up(dcnt, p.counts4, 8 * 4 * mf) && up(dsplits, p.splits, sizeof(NodeSplit) * nk) && up(dcur, p.cursors, 8 * nk);
+    if (!ok) return kHistProbeDevice;
+    const auto ran = [] { const bool good = hipGetLastError() == hipSuccess /* a refused launch */ && hipDeviceSynchronize() == hipSuccess; if (!good) (void)hipGetLastError(); return good; };
+    const FeatureSlot *slots = static_cast<const FeatureSlot *>(dslots.p);
+    const bool greedy = p.do_score == 2;
+    if (p.do_score) {
+        score_candidates(static_cast<int64_t *>(dhist.p), static_cast<const int64_t *>(dprev.p), static_cast<const int32_t *>(dpar.p), static_cast<const int32_t *>(dsib.p), n_nodes, Fp, NB, D,
+                         slots, p.n_slots, static_cast<const float *>(dthr.p), B, n_cand, p.min_data, p.cosine ? 1 : 0, static_cast<const StepScales *>(dsc.p),
+                         static_cast<const int32_t *>(dplen.p), static_cast<const int32_t *>(dpslot.p), static_cast<const float *>(dpval.p), static_cast<const int32_t *>(dpbin.p),
+                         static_cast<float *>(dscores.p), static_cast<float *>(dparent.p), static_cast<const float *>(dw.p), static_cast<const int32_t *>(dref.p),
+                         static_cast<const int32_t *>(droot.p), greedy ? static_cast<float *>(dpv.p) : nullptr, static_cast<int32_t *>(dpi.p), nullptr, p.slot0, p.keep_derived != 0,
+                         greedy ? static_cast<float *>(dps.p) : nullptr, greedy ? static_cast<int32_t *>(dpn.p) : nullptr, greedy ? nullptr : static_cast<int32_t *>(dnr.p));
+        if (!ran()) return kHistProbeDevice;
+    }
+    if (p.do_argmax) {
+        argmax(static_cast<const float *>(dscores.p), n_nodes, n_cand, static_cast<const float *>(dw.p), static_cast<const int32_t *>(dref.p), static_cast<const float *>(dparent.p),
+               static_cast<const int32_t *>(droot.p), true, static_cast<float *>(dpv.p), static_cast<int32_t *>(dpi.p), nullptr, nullptr, nullptr, static_cast<float *>(dps.p));
+        if (!ran()) return kHistProbeDevice;
+    }
+    if (p.do_resolve) {
+        const NearDetect near{static_cast<const float *>(dps.p), static_cast<const int32_t *>(dpn.p), p.near_rel, static_cast<const float *>(dparent.p), static_cast<const int32_t *>(droot.p),
+                              p.cosine ? 1 : 0, p.near_rows};
+        const bool derive = p.keep_derived == 0 && p.sub_par;   // the last level: the derived slices were not written back
+        resolve_splits(static_cast<const float *>(dpv.p), static_cast<const int32_t *>(dpi.p), p.n_parts, static_cast<int32_t *>(dbi.p), static_cast<float *>(dbs.p), p.oblivious != 0, n_nodes,
+                       static_cast<const int32_t *>(dr2i.p), static_cast<const int32_t *>(dcslot.p), slots, static_cast<const int64_t *>(dhist.p), static_cast<const int64_t *>(dglob.p), Fp, NB, D,
+                       static_cast<NodeSplit *>(dsplits.p), static_cast<int64_t *>(dcnt.p), p.max_front, static_cast<const int32_t *>(dseg.p), static_cast<int32_t *>(dcur.p),
+                       static_cast<const uint32_t *>(dkeys.p), B, nullptr, nullptr, nullptr, 0, nullptr, derive ? static_cast<const int64_t *>(dprev.p) : nullptr,
+                       derive ? static_cast<const int32_t *>(dpar.p) : nullptr, derive ? static_cast<const int32_t *>(dsib.p) : nullptr, p.near ? &near : nullptr);
+        if (!ran()) return kHistProbeDevice;
+    }
+    ok = down(p.hist, dhist, 8 * node_elems * p.n_hist_nodes) && down(p.scores, dscores, 4 * n_sc) && down(p.parent, dparent, 4 * nk) && down(p.cand_nr, dnr, 4 * n_sc);
+    if (ok && n_part) ok = down(p.part_v, dpv, 4 * n_part) && down(p.part_i, dpi, 4 * n_part) && down(p.part_s, dps, 4 * n_part) && down(p.part_n, dpn, 4 * n_part);
+    if (ok && p.do_resolve)
+        ok = down(p.best_idx, dbi, 4 * mf) && down(p.best_score, dbs, 4 * mf) && down(p.counts4, dcnt, 8 * 4 * mf) && down(p.splits, dsplits, sizeof(NodeSplit) * nk) && down(p.cursors, dcur, 8 * nk);
+    return ok ? kHistProbeOk : kHistProbeDevice;
 }
 
 }  // namespace kern

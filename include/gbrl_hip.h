@@ -1047,6 +1047,70 @@ typedef struct gbrl_hip_hist_probe_t {
 } gbrl_hip_hist_probe_t;
 int gbrl_hip_hist_probe(gbrl_hip_hist_probe_t *args);
 
+/* Diagnostics for the tests: what a tree level does with its histograms -- the kernels of csrc/step_score.hip through the launchers a step uses
+ * (score_candidates, argmax, resolve_splits; the pinned publish path is not driven).  Host pointers.  With W = output_dim + 1:
+ *   hist        int64 [n_hist_nodes][Fp][n_classes][W]   the level's histograms, IN and OUT (a derived node's slice is written back)
+ *   hist_prev   nullable int64 [n_prev_nodes][Fp][n_classes][W]; sub_par / sub_sib nullable int32 [n_nodes]: sub_par[k] >= 0 makes node k
+ *               hist_prev[sub_par[k]] - hist[sub_sib[k]] (sub_sib[k] < 0: the parent alone)
+ *   hist_global nullable int64 [n_nodes][Fp][n_classes][W]: resolve_splits counts a second pair from it
+ *   slots       int32 [n_table_slots][4] = (is_cat, n_cand, cand_base, 0);  thr float [n_table_slots][B];  thr_keys nullable uint32, the same shape
+ *   path_len    int32 [n_nodes];  path_slot, path_bin int32 and path_val float [n_nodes][32]
+ *   cand_w float, cand_ref, ref_to_internal, cand_slot int32 [n_cand];  is_root int32 [n_nodes];  seg_start nullable int32 [n_nodes]
+ *   inv_scale = 2^-sbits;  slot0, n_slots: the slots launched;  keep_derived as score_candidates takes it
+ * What runs:
+ *   do_score   0: nothing;  1: scores mode -> scores, parent, cand_nr (nullable);  2: the fused greedy form -> parent, part_v, part_i and,
+ *              where given, part_s, part_n, all [n_nodes][n_slots]
+ *   do_argmax  1 (with do_score 0 or 1): k_argmax_stage1 in the oblivious form on `scores` -> part_v, part_i, part_s (nullable) [n_parts]
+ *   do_resolve 1: resolve_splits on part_* (as left by the steps above, or as given) -> best_idx, best_score [max_front], counts4 int64
+ *              [4][max_front], splits int32 [n_nodes][8] (NodeSplit), cursors int32 [n_nodes][2].  near != 0: the NearDetect fields
+ *              (part_s, part_n, near_rel, parent, is_root, cosine, near_rows).  keep_derived = 0 hands it hist_prev, sub_par and sub_sib.
+ *   n_parts    entries per node of part_*: n_slots after do_score 2, ceil(n_cand / 256) after do_argmax, free otherwise
+ * Every array named as an output (and hist) goes to the device holding the caller's values and comes back afterwards: a cell no kernel
+ * stored keeps them.  Everything a kernel will index is checked on the host first -- null arrays, sizes, the LDS tile
+ * (n_classes + 2) * W * 8 <= 150 KiB, every slot's candidates inside [0, n_cand) and its classes inside n_classes, sub_par / sub_sib, path_len <= 32,
+ * cand_ref a permutation, ref_to_internal and cand_slot, the launch window, given part_i: GBRL_HIP_E_INVALID with a text that names the
+ * reason, and no device is touched.  Nothing in the product calls it. */
+typedef struct gbrl_hip_score_probe_t {
+    int64_t *hist;
+    const int64_t *hist_prev, *hist_global;
+    const int32_t *sub_par, *sub_sib, *slots;
+    const float *thr;
+    const uint32_t *thr_keys;
+    const int32_t *path_len, *path_slot, *path_bin;
+    const float *path_val, *cand_w;
+    const int32_t *cand_ref, *ref_to_internal, *cand_slot, *is_root, *seg_start;
+    float *scores, *parent, *part_v, *part_s, *best_score;
+    int32_t *cand_nr, *part_i, *part_n, *best_idx, *splits, *cursors;
+    int64_t *counts4;
+    long long near_rows;
+    float near_rel;
+    int n_hist_nodes, n_prev_nodes, n_nodes, Fp, n_classes, output_dim, n_table_slots, B, n_cand, sbits, min_data, cosine, slot0, n_slots, keep_derived;
+    int do_score, do_argmax, do_resolve, n_parts, oblivious, near, max_front;
+} gbrl_hip_score_probe_t;
+int gbrl_hip_score_probe(gbrl_hip_score_probe_t *args);
+
+/* Diagnostics for the tests: ONE launch of a row kernel of csrc/step_partition.hip on host arrays.  op 0: partition_rows, 1: count_right,
+ * 2: leaf_sums.
+ *   rows     int32 [m] row indices (repeats allowed);  chunks int32 [n_chunks][3] = (slot, start, len), len <= 4096 for op 0
+ *   codes    uint16 [ceil(n_feature_slots / 16)][n_rows][16] (ops 0, 1);  kt nullable uint32 [n_feature_slots][n_rows]: numeric splits read the keys
+ *   splits   int32 [n_slots][8] (NodeSplit: do_split, fslot, bin, is_cat, seg_start, n_left, thr_key, 0) (ops 0, 1)
+ *   grads    float [n_rows][output_dim], scaled by 2^lbits (op 2)
+ *   rows_out int32 [m] and cursors int32 [n_slots][2] (op 0);  acc int64 [n_slots] (op 1: rows going right) or [n_slots][output_dim + 1] (op 2)
+ * rows_out, cursors and acc go to the device holding the caller's values -- the kernels ADD to cursors and acc -- and come back afterwards.
+ * Checked on the host first: null arrays, sizes, row indices, chunks inside the row list, every split's slot; for op 0 also that the segments
+ * of the splitting nodes lie inside the list and apart, that their cursors start at 0, and that every n_left is the count the host itself
+ * finds (a destination would leave the segment otherwise): GBRL_HIP_E_INVALID, and no device is touched.  Nothing in the product calls it. */
+typedef struct gbrl_hip_rows_probe_t {
+    const int32_t *rows, *chunks, *splits;
+    const uint16_t *codes;
+    const uint32_t *kt;
+    const float *grads;
+    int32_t *rows_out, *cursors;
+    int64_t *acc;
+    int op, n_rows, m, n_chunks, n_slots, n_feature_slots, output_dim, lbits;
+} gbrl_hip_rows_probe_t;
+int gbrl_hip_rows_probe(gbrl_hip_rows_probe_t *args);
+
 /* ---- device / stream contract (new; the reference pins everything to device 0 and the null stream, cuda_types.cu:32-106) -- */
 /* The device the model computes on: the ordinal given at creation, or -- for -1 -- the calling thread's current device at the
  * first call that needs it (it is latched by this call too).  -1 when no HIP device is usable.  A caller that hands out
