@@ -18,6 +18,7 @@
 #include <sstream>
 #include <string>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/gbrl_hip.h"
@@ -1553,6 +1554,181 @@ py::array_t<double> feature_importance_impl(PyGBRL &self, const std::string &kin
     return out;
 }
 
+// ---- partial dependence and ICE (include/gbrl_hip.h, "Partial dependence")
+int read_n_trees(py::object &n_trees_obj) {   // None: every tree (-1); anything else is checked behind the C ABI
+    if (n_trees_obj.is_none()) return -1;
+    const long long k = n_trees_obj.cast<long long>();
+    return k < INT32_MIN ? INT32_MIN : k > INT32_MAX ? INT32_MAX : static_cast<int>(k);
+}
+
+// partial_dependence_codes(thresholds, col, n_trees=None) -> int32 [k + 1]: the break rule on the host, no device
+py::array_t<int32_t> partial_dependence_codes_impl(PyGBRL &self, py::object &thresholds, int col, py::object n_trees_obj) {
+    Input t = read_input(thresholds, "thresholds", false, "partial_dependence_codes", false);
+    if (t.on_device) fail("partial_dependence_codes takes a NumPy array");
+    if (t.shape.size() != 2) fail("thresholds must be the [n_features, n_bins] array PreparedDataset.thresholds() returns");
+    std::vector<int32_t> buf(t.shape[1] + 1);
+    int count = 0;
+    check(gbrl_hip_partial_dependence_codes(self.h, static_cast<const float *>(t.ptr), static_cast<int>(t.shape[0]), static_cast<int>(t.shape[1]), col,
+                                            read_n_trees(n_trees_obj), buf.data(), &count));
+    py::array_t<int32_t> out(static_cast<py::ssize_t>(count));
+    std::copy(buf.begin(), buf.begin() + count, out.mutable_data());
+    return out;
+}
+
+py::dict partial_dependence_geometry_impl(int m, int D) {
+    int rows = 0, launch = 0, most = 0;
+    uint64_t budget = 0;
+    gbrl_hip_partial_dependence_geometry(m, D, &rows, &launch, &most, &budget);
+    py::dict out;
+    out["partial_rows"] = rows;
+    out["launch_variants"] = launch;
+    out["max_launch_variants"] = most;
+    out["scratch_budget"] = py::int_(budget);
+    return out;
+}
+
+// partial_dependence_prepared(ds, features, n_trees=None, rows=None, ice=False, max_cells=4096) -> dict
+py::dict partial_dependence_prepared_impl(PyGBRL &self, py::object ds_obj, py::object features, py::object n_trees_obj, py::object &rows, bool ice, long long max_cells) {
+    const std::string fn = "partial_dependence_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    if (ds_obj.is_none()) fail(fn + ": null data set");
+    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
+    const gbrl_hip_dataset_desc info = pds.info();
+    const int F = info.n_features, B = info.n_bins, D = md.output_dim, n_trees = read_n_trees(n_trees_obj);
+    // ---- the entries: an int column, or a pair of two distinct columns
+    struct Entry { int c0, c1; };
+    std::vector<Entry> entries;
+    if (!py::isinstance<py::sequence>(features) || py::isinstance<py::str>(features)) fail(fn + ": features must be a sequence of columns and (c0, c1) pairs");
+    auto column = [&](py::handle h, size_t e) {
+        if (!py::isinstance<py::int_>(h) && !(py::hasattr(h, "__index__") && !py::isinstance<py::float_>(h))) fail(fn + ": entry " + std::to_string(e) + " of features is neither a column nor a pair of columns");
+        const long long c = py::reinterpret_steal<py::object>(PyNumber_Index(h.ptr())).cast<long long>();
+        if (c < 0 || c >= F) fail(fn + ": entry " + std::to_string(e) + " of features names column " + std::to_string(c) + ", outside [0, " + std::to_string(F) + ")");
+        return static_cast<int>(c);
+    };
+    size_t e = 0;
+    for (py::handle h : features.cast<py::sequence>()) {
+        if (py::isinstance<py::sequence>(h) && !py::isinstance<py::str>(h)) {
+            py::sequence pr = py::reinterpret_borrow<py::sequence>(h);
+            if (py::len(pr) != 2) fail(fn + ": entry " + std::to_string(e) + " of features has " + std::to_string(py::len(pr)) + " columns: a pair has two");
+            const int c0 = column(pr[0], e), c1 = column(pr[1], e);
+            if (c0 == c1) fail(fn + ": entry " + std::to_string(e) + " of features names column " + std::to_string(c0) + " twice: a pair needs two distinct columns");
+            entries.push_back({c0, c1});
+        } else {
+            entries.push_back({column(h, e), -1});
+        }
+        ++e;
+    }
+    if (entries.empty()) fail(fn + ": features is empty: name at least one column or pair");
+    if (max_cells < 1) fail(fn + ": max_cells must be >= 1, got " + std::to_string(max_cells));
+    // ---- the breaks of every named column (host only), from the data set's thresholds
+    std::vector<float> thr(static_cast<size_t>(F) * B);
+    check(gbrl_hip_dataset_thresholds(pds.h, thr.data()));
+    std::unordered_map<int, std::vector<int32_t>> codes;
+    auto codes_of = [&](int c) -> const std::vector<int32_t> & {
+        auto it = codes.find(c);
+        if (it != codes.end()) return it->second;
+        std::vector<int32_t> buf(static_cast<size_t>(B) + 1);
+        int count = 0;
+        check(gbrl_hip_partial_dependence_codes(self.h, thr.data(), F, B, c, n_trees, buf.data(), &count));
+        buf.resize(static_cast<size_t>(count));
+        return codes.emplace(c, std::move(buf)).first->second;
+    };
+    // ---- the cells: variant 0 is the baseline, then every entry's cells in order
+    std::vector<int32_t> variants{-1, 0, -1, 0};
+    std::vector<size_t> first(entries.size());
+    for (size_t i = 0; i < entries.size(); ++i) {
+        const Entry &en = entries[i];
+        const std::vector<int32_t> &a = codes_of(en.c0);
+        static const std::vector<int32_t> one{0};
+        const std::vector<int32_t> &b = en.c1 >= 0 ? codes_of(en.c1) : one;
+        const long long cells = static_cast<long long>(a.size()) * static_cast<long long>(b.size());
+        if (cells > max_cells) {
+            std::stringstream ss;
+            ss << fn << ": entry " << i << " of features (";
+            if (en.c1 >= 0) ss << "columns " << en.c0 << " and " << en.c1 << ") has " << a.size() << " x " << b.size() << " = ";
+            else ss << "column " << en.c0 << ") has ";
+            ss << cells << " cells, max_cells is " << max_cells;
+            fail(ss.str());
+        }
+        first[i] = variants.size() / 4;
+        variants.resize(variants.size() + 4 * static_cast<size_t>(cells));   // pd_core.h's cell list: one column, or the row-major product of a pair
+        check(gbrl_hip_partial_dependence_cells(en.c0, a.data(), static_cast<int>(a.size()), en.c1, en.c1 >= 0 ? b.data() : nullptr, en.c1 >= 0 ? static_cast<int>(b.size()) : 0,
+                                                variants.data() + 4 * first[i]));
+    }
+    const size_t V = variants.size() / 4;
+    if (V > static_cast<size_t>(INT32_MAX)) fail(fn + ": " + std::to_string(V) + " variants do not fit the call's int32 count");   // (the 2^20 bound is the engine's: it counts what it launches)
+    Input none;
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
+    const py::ssize_t m = std::max(r.m, 0);
+    if (ice && static_cast<unsigned long long>(V) * static_cast<unsigned long long>(m) * static_cast<unsigned long long>(D) >= (1ull << 31))
+        fail(fn + ": the ICE rows of " + std::to_string(V) + " variants x " + std::to_string(m) + " rows x " + std::to_string(D) +
+             " outputs are 2^31 elements or more: pass rows= to evaluate fewer rows, or fewer features per call");
+    py::array_t<double> sums({static_cast<py::ssize_t>(V), static_cast<py::ssize_t>(D)});
+    py::array_t<float> ice_all;
+    if (ice) ice_all = py::array_t<float>({static_cast<py::ssize_t>(V), m, static_cast<py::ssize_t>(D)});
+    int rc;
+    {
+        double *sp = sums.mutable_data();
+        float *ip = ice && ice_all.size() > 0 ? ice_all.mutable_data() : nullptr;
+        py::gil_scoped_release release;
+        rc = gbrl_hip_partial_dependence_prepared(self.h, pds.h, variants.data(), static_cast<int>(V), r.ptr, r.on_device, r.m, n_trees, sp, ip, 0);
+    }
+    check(rc);
+    // ---- the result: sums / m, shaped per entry
+    const double *S = sums.data();
+    py::array_t<double> baseline(static_cast<py::ssize_t>(D));
+    for (int d = 0; d < D; ++d) baseline.mutable_data()[d] = S[d] / static_cast<double>(m);
+    py::list l_features, l_codes, l_values, l_pd, l_ice;
+    for (size_t i = 0; i < entries.size(); ++i) {
+        const Entry &en = entries[i];
+        auto codes_arr = [&](int c) {
+            const std::vector<int32_t> &a = codes.at(c);
+            py::array_t<int32_t> out(static_cast<py::ssize_t>(a.size()));
+            std::copy(a.begin(), a.end(), out.mutable_data());
+            return out;
+        };
+        auto values_arr = [&](int c) {   // the threshold segment j >= 1 begins just above: thr[c][codes[j] - 1]
+            const std::vector<int32_t> &a = codes.at(c);
+            py::array_t<float> out(static_cast<py::ssize_t>(a.size() - 1));
+            for (size_t j = 1; j < a.size(); ++j) out.mutable_data()[j - 1] = thr[static_cast<size_t>(c) * B + static_cast<size_t>(a[j] - 1)];
+            return out;
+        };
+        const py::ssize_t k0 = static_cast<py::ssize_t>(codes.at(en.c0).size()), k1 = en.c1 >= 0 ? static_cast<py::ssize_t>(codes.at(en.c1).size()) : 1;
+        std::vector<py::ssize_t> shape{k0};
+        if (en.c1 >= 0) shape.push_back(k1);
+        std::vector<py::ssize_t> pd_shape(shape), ice_shape(shape);
+        pd_shape.push_back(D);
+        ice_shape.push_back(m); ice_shape.push_back(D);
+        py::array_t<double> pd(pd_shape);
+        const double *src = S + first[i] * static_cast<size_t>(D);
+        for (py::ssize_t q = 0; q < k0 * k1 * D; ++q) pd.mutable_data()[q] = src[q] / static_cast<double>(m);
+        if (en.c1 >= 0) {
+            l_features.append(py::make_tuple(en.c0, en.c1));
+            l_codes.append(py::make_tuple(codes_arr(en.c0), codes_arr(en.c1)));
+            l_values.append(py::make_tuple(values_arr(en.c0), values_arr(en.c1)));
+        } else {
+            l_features.append(py::int_(en.c0));
+            l_codes.append(codes_arr(en.c0));
+            l_values.append(values_arr(en.c0));
+        }
+        l_pd.append(pd);
+        if (ice) {
+            py::array_t<float> block(ice_shape);
+            std::copy_n(ice_all.data() + first[i] * static_cast<size_t>(m) * D, static_cast<size_t>(k0 * k1 * m) * D, block.mutable_data());
+            l_ice.append(block);
+        }
+    }
+    py::dict out;
+    out["features"] = l_features;
+    out["rows"] = py::int_(m);
+    out["baseline"] = baseline;
+    out["codes"] = l_codes;
+    out["values"] = l_values;
+    out["pd"] = l_pd;
+    if (ice) out["ice"] = l_ice;
+    return out;
+}
+
 float fit_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, int iterations, bool shuffle,
                const std::string &loss_type) {
     if (loss_type != "MultiRMSE") fail("Invalid loss function! Options are: MultiRMSE");   // stringTolossType, types.cpp:52-56
@@ -1774,6 +1950,10 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "bijection pi of [0, n), computed element by element with no state; row i of the variant (col, repeat) reads column col from row pi[i].  A\n"
           "cycle-walking balanced Feistel network: b = max(2, bit_length(n - 1)) rounded up to even, four rounds (L, R) <- (R, L ^ (F_k(R) & (2**(b/2) - 1)))\n"
           "with F_k the row sampler's 24-bit hash keyed by seed ^ 'permutat', col and the round, applied again while the result is >= n.");
+    m.def("partial_dependence_geometry", &partial_dependence_geometry_impl, py::arg("m") = 1, py::arg("D") = 1,
+          "partial_dependence_geometry(m=1, D=1) -> {'partial_rows': 64, 'launch_variants': ..., 'max_launch_variants': 64, 'scratch_budget': 67108864}: the\n"
+          "rows one float64 partial of partial_dependence_prepared sums, the variants one launch takes over m rows of D outputs (its partials, 8 *\n"
+          "variants * D * ceil(m / 64) bytes, stay under the budget; never below 1), the most any launch takes, and the budget in bytes.");
     m.def("permutation_geometry", &permutation_geometry_impl,
           "permutation_geometry() -> {'launch_variants': 64, 'tile_rows': 64}: the (column, repeat) variants one launch of permutation_importance_prepared\n"
           "walks, and the rows of its tile (= the rows per loss partial)");
@@ -2143,6 +2323,27 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "early-stopped fit).  objective: 'rmse', 'logistic', 'softmax' (int32 labels) or 'quantile' (with alpha).  A column no tree of the range tests\n"
           "reports the baseline's bits.  The model and the data set are not changed.  Refused before the device is touched: n_repeats < 1, bad cols or\n"
           "n_trees, missing or misshapen targets, a model without trees, the ranking objectives, and what predict_continue_prepared refuses.");
+    g.def("partial_dependence_codes", &partial_dependence_codes_impl, py::arg("thresholds"), py::arg("col"), py::arg("n_trees") = py::none(),
+          "partial_dependence_codes(thresholds, col, n_trees=None) -> int32 [k + 1]\n\n"
+          "The codes of column col at which the trees [0, n_trees) can change their answer (no device is needed): [0] + [bin + 1 for the sorted distinct\n"
+          "bins, condition_bins' rule for thresholds, of the numeric conditions on col that the walk reads].  Segment j is the code range [codes[j],\n"
+          "codes[j + 1] - 1], the last one runs to n_bins; every code of a segment answers every walked condition on col alike.  A column the walk never\n"
+          "tests gives [0].  thresholds: PreparedDataset.thresholds().");
+    g.def("partial_dependence_prepared", &partial_dependence_prepared_impl, py::arg("ds"), py::arg("features"), py::arg("n_trees") = py::none(),
+          py::arg("rows") = py::none(), py::arg("ice") = false, py::arg("max_cells") = 4096,
+          "partial_dependence_prepared(ds, features, n_trees=None, rows=None, ice=False, max_cells=4096) -> dict\n\n"
+          "Partial dependence (and, with ice=True, the ICE curves) of the trees [0, n_trees), walked from the bias, on the data set's rows (rows=None: every\n"
+          "row; an int32 vector or device tuple as step_prepared takes it, duplicates allowed).  features: a sequence whose entries are a column or a pair\n"
+          "(c0, c1) of distinct columns.  The curve is exact and needs no grid: a cell holds its column(s) at the first code of a segment of\n"
+          "partial_dependence_codes for every row; a pair's cells are the row-major product of its columns' codes.  Returns 'features', 'rows' (m),\n"
+          "'baseline' float64 [D] (no column held), and one item per entry in 'codes' (int32 [k + 1]; a tuple of two for a pair), 'values' (float32 [k]:\n"
+          "segment j >= 1 begins just above values[j - 1] = thresholds[c][codes[j] - 1]), 'pd' (float64 [k + 1, D] or [k0 + 1, k1 + 1, D]) and, with ice=True,\n"
+          "'ice' (float32 [k + 1, m, D] or [k0 + 1, k1 + 1, m, D]).  The curve at an arbitrary code g is pd[np.searchsorted(codes, g, side='right') - 1].\n"
+          "An ICE block is bit for bit predict_continue_prepared(dsc, tile(bias), 0, n_trees) on a data set dsc that really holds the cell's codes; pd is\n"
+          "the float64 sum of those rows in a fixed order, divided by m: two calls return the same bytes.  The cell of a column no tree of the range tests\n"
+          "is the baseline and reports its bits.  The model and the data set are not changed.  Refused before the device is touched: an empty features, a\n"
+          "column outside the data set's, a pair that names a column twice, an entry with more than max_cells cells, more than 2^20 launched variants, ICE rows of 2^31\n"
+          "elements or more (pass rows=), a bad n_trees, a model without trees, and what predict_continue_prepared refuses.");
     // extension: every ensemble prefix in one walk -- the prediction, or the MultiRMSE loss against targets, after every stops[s] trees
     g.def("predict_staged", &predict_staged_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("stops") = py::none());
     g.def("staged_loss", &staged_loss_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("stops") = py::none());

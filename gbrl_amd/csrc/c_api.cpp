@@ -21,6 +21,7 @@
 #include "newton_core.h"
 #include "quantile_core.h"
 #include "rank_core.h"
+#include "pd_core.h"
 #include "hooks.h"
 #include "explain.h"
 #include "rccl_dyn.h"
@@ -847,6 +848,43 @@ int gbrl_hip_permutation_importance_prepared(gbrl_hip_model *m, const gbrl_hip_d
 void gbrl_hip_permutation_geometry(int *launch_variants, int *tile_rows) {
     if (launch_variants) *launch_variants = gbrl::kern::kPermLaunchVariants;
     if (tile_rows) *tile_rows = gbrl::kern::perm_tile_rows();
+}
+
+// ---- partial dependence: the break rule on the host, the variants' sums and ICE rows of a data set (engine_pd.hip; pd_core.h has the plan)
+int gbrl_hip_partial_dependence_codes(const gbrl_hip_model *m, const float *thresholds, int n_features, int n_bins, int col, int n_trees, int32_t *out, int *count) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.partial_dependence_codes(thresholds, n_features, n_bins, col, n_trees, out, count);
+    });
+}
+
+int gbrl_hip_partial_dependence_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *variants, int n_variants, const int32_t *rows, int rows_on_device,
+                                         int n_rows, int n_trees, double *sums_out, float *ice_out, int ice_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("partial_dependence_prepared");
+        m->engine.partial_dependence_prepared(&live_dataset(ds), variants, n_variants, rows, rows_on_device != 0, n_rows, n_trees, sums_out, ice_out, ice_on_device != 0);
+    });
+}
+
+int gbrl_hip_partial_dependence_cells(int col0, const int32_t *codes0, int n0, int col1, const int32_t *codes1, int n1, int32_t *out) {
+    return guarded([&] {
+        if (codes0 == nullptr || out == nullptr || n0 < 1 || col0 < 0) throw gbrl::InvalidArgument("partial_dependence_cells: a column >= 0, its codes and a place for the cells are needed");
+        if (col1 >= 0 && (codes1 == nullptr || n1 < 1)) throw gbrl::InvalidArgument("partial_dependence_cells: the second column has no codes");
+        if (col1 >= 0 && col1 == col0) throw gbrl::InvalidArgument("partial_dependence_cells: a pair needs two distinct columns");
+        std::vector<gbrl::kern::PdVariant> cells;
+        cells.reserve(static_cast<size_t>(gbrl::kern::pd_cell_count(n0, col1 < 0 ? 0 : n1)));
+        gbrl::kern::pd_append_cells(cells, col0, codes0, n0, col1 < 0 ? -1 : col1, codes1, col1 < 0 ? 0 : n1);
+        static_assert(sizeof(gbrl::kern::PdVariant) == 4 * sizeof(int32_t), "a variant is four int32");
+        std::memcpy(out, cells.data(), cells.size() * sizeof(gbrl::kern::PdVariant));
+    });
+}
+
+void gbrl_hip_partial_dependence_geometry(int n_rows, int output_dim, int *rows_per_partial, int *launch_variants, int *max_launch_variants, uint64_t *scratch_budget_bytes) {
+    if (rows_per_partial) *rows_per_partial = gbrl::kern::kPdPartialRows;
+    if (launch_variants) *launch_variants = gbrl::kern::pd_launch_variants(n_rows < 1 ? 1 : n_rows, output_dim);
+    if (max_launch_variants) *max_launch_variants = gbrl::kern::kPdMaxLaunchVariants;
+    if (scratch_budget_bytes) *scratch_budget_bytes = gbrl::kern::kPdScratchBudget;
 }
 
 static_assert(GBRL_HIP_IMPORTANCE_SPLIT == gbrl::kFeatureSplit && GBRL_HIP_IMPORTANCE_COVER == gbrl::kFeatureCover, "the importance kinds are the header's");

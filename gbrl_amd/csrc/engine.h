@@ -205,6 +205,30 @@ class Engine {
     void permutation_importance_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int objective, const float *alpha, int n_repeats,
                                          uint64_t seed, const int32_t *cols, int n_cols, int n_trees, double *baseline_out, double *loss_out);
     static void permutation_host(int n, uint64_t seed, int col, int repeat, int32_t *out);   // the rule on the host: out [n] = perm(n, seed, col, repeat)
+    // Extension (engine_pd.hip; pd_core.h has the break rule and the launch plan, pd_rows.hip the kernels): partial dependence and ICE on a data set.
+    // partial_dependence_codes: host only.  out [*count] (room for B + 1 entries) = [0] + [bin + 1 for the sorted distinct bins of the numeric
+    // conditions on column col that the walk of the trees [0, n_trees) reads] (n_trees == -1: all; greedy: through the trees a trailing run of
+    // one-leaf trees runs on into, as check_code_range counts them), the bins being condition_bins' for thresholds [F][B].  Segment j is the code
+    // range [out[j], out[j + 1] - 1], the last one runs to B; every code of a segment answers every walked condition on col alike.  A column no
+    // walked condition tests: [0].  Only the column's walked conditions are converted.  Refused: null arguments, F / B that are not the model's
+    // (InvalidArgument, as condition_bins), col outside [0, F), a model without trees, n_trees outside [1, model's], a walked condition on col whose
+    // value is not among thr[col][*] (Unsupported, naming the tree).
+    void partial_dependence_codes(const float *thresholds, int F, int B, int col, int n_trees, int32_t *out, int *count) const;
+    // partial_dependence_prepared: for each of the V variants {col0, code0, col1, code1} (host; col1 == -1: one column; col0 == -1: the baseline, col1
+    // then -1 too) the trees [0, n_trees) are walked from the bias over the rows rows[0..m) of ds (rows == nullptr: every row, m == ds->n; host or
+    // device, duplicates allowed, as step_prepared's) with column col0 (and col1) read as the constant code for every row.  sums_out (host float64
+    // [V][D]) = the sum over the rows of (double)p[r][d] in a fixed order: one partial per 64 consecutive positions of the row list
+    // (predict_loss.h's butterfly), finished by kern::staged_loss_finish_rows -- two calls give the same bytes.  ice_out (nullable; host or device
+    // float32 [V][m][D]) = the rows themselves, bit for bit predict_continue_prepared from a tiled bias over [0, n_trees) on a data set that holds
+    // those codes.  A column of a variant that no walked condition tests is dropped from it; a variant left without a column IS the baseline: it is
+    // not launched and reports the baseline's bits, and so does every variant of a model in which no optimizer owns an output.  At most
+    // kern::pd_launch_variants(m, D) variants per launch (the partial scratch stays under pd_core.h's budget), ONE read-back of the sums.
+    // Refused before the device is touched (InvalidArgument unless noted): what predict_continue_prepared refuses about the model, the data set and
+    // rows (output_dim > 128: Unsupported), a model without trees, n_trees outside [1, model's] and not -1, V < 1 or null variants / sums_out, a
+    // column outside [0, F) (or below -1), col0 == col1, col0 == -1 with col1 >= 0, a code outside [0, B], more than 2^20 launched variants,
+    // V * m * D >= 2^31 with ice_out (Unsupported: pass rows).  Model and data set are never written.
+    void partial_dependence_prepared(const PreparedDataset *ds, const int32_t *variants /*[V][4]*/, int V, const int32_t *rows, bool rows_dev, int m, int n_trees,
+                                     double *sums_out, float *ice_out, bool ice_dev);
     // fit_prepared: fit()'s loop (shuffle = false) on a data set with nothing recomputed.  Each iteration takes the next batch_size rows (wrapping to
     // row 0), advances their held prediction by the trees grown since the batch last saw it -- one launch that also writes the objective's gradient
     // -- and grows one tree by step_prepared's body; at the end every batch is advanced and the loss on all rows returned (fit()'s MultiRMSE; an
@@ -641,6 +665,7 @@ class Engine {
     DevBuf d_obj_weights_, d_fp_weights_, d_fp_vweights_, d_wstat_, d_wpart_, d_wsum_;   // row weights: staged vectors; kern::weight_stats' two ints, partials and sum
     DevBuf d_obj_pred_, d_obj_targets_, d_obj_grad_, d_obj_part_, d_obj_sum_, d_obj_counts_;   // objective_gradient: staged inputs, the gradient, loss partials and sum; class counts + first bad row
     DevBuf d_pi_targets_, d_pi_variants_, d_pi_part_, d_pi_sums_;   // permutation_importance_prepared: staged targets, the variant list, one launch's loss partials, one sum per variant
+    DevBuf d_pd_variants_, d_pd_slots_, d_pd_part_, d_pd_sums_, d_pd_ice_;   // partial_dependence_prepared: the launched variants and their ICE slots, one launch's partials, D sums per variant, ICE rows bound for the host (released when the call ends)
     DevBuf d_met_counts_, d_met_scratch_, d_fp_vmetric_;   // eval_metric: the integer counters, the AUC pipeline's scratch; fit_prepared: the metric's counters per iteration
     struct Held;     // engine_fit_prepared.hip: a data set's rows carried through the model's trees, batch by batch
     struct FitRun;   // engine_fit_prepared.hip: the state of one fit_prepared call and the stages that work on it

@@ -1,5 +1,6 @@
 // engine_codes_detail.h -- the few helpers more than one of the data-set units needs (engine_step_detail.h has the list of the units):
 //   runs_on           engine_codes.hip, engine_fit_prepared.hip
+//   walked_split_rows / walked_columns   engine_importance.hip, engine_pd.hip
 //   mean_loss         engine_objective.hip, engine_fit_prepared.hip
 //   check_auc_column  engine_objective.hip, engine_fit_prepared.hip
 //   metric_counts     engine_objective.hip, engine_fit_prepared.hip
@@ -13,6 +14,27 @@ namespace detail {
 
 // greedy: a tree of one leaf -- the walk of such a tree finds no leaf of its own and runs on into the next tree (Q7)
 inline bool runs_on(const Model &model, int t) { return !model.oblivious() && model.leaf_count(t) == 1; }
+
+// the split rows the walk of the trees [0, stop) reads (greedy: through the trees a trailing run of one-leaf trees runs on into, as check_code_range counts them)
+inline size_t walked_split_rows(const Model &model, int stop) {
+    const int T = model.meta.n_trees;
+    int end = stop;
+    while (end < T && runs_on(model, end - 1)) ++end;
+    return model.oblivious() ? static_cast<size_t>(end) : static_cast<size_t>(end < T ? model.tree_indices[end] : model.meta.n_leaves);
+}
+
+// used[f] = 1 for every column f < F that a numeric condition of those split rows tests: ONE rule for "the walk reads this column"
+inline std::vector<uint8_t> walked_columns(const Model &model, int stop, int F) {
+    std::vector<uint8_t> used(static_cast<size_t>(F), 0);
+    const size_t MD = model.meta.max_depth, s1 = walked_split_rows(model, stop);
+    for (size_t s = 0; s < s1; ++s)
+        for (size_t d = 0; d < MD && static_cast<int>(d) < model.depths[s]; ++d) {
+            const size_t c = s * MD + d;
+            const int f = model.feature_indices[c];
+            if (model.is_numerics[c] && f >= 0 && f < F) used[f] = 1;
+        }
+    return used;
+}
 
 // the mean loss of an objective from the sum of its row losses: rmse is staged_loss's expression
 // (rows: the row count, or with weights their float64 sum W)
@@ -39,6 +61,8 @@ inline std::vector<uint64_t> metric_counts(int metric, int C, const unsigned lon
 }  // namespace detail
 
 using detail::runs_on;
+using detail::walked_split_rows;
+using detail::walked_columns;
 using detail::mean_loss;
 using detail::check_auc_column;
 using detail::metric_counts;

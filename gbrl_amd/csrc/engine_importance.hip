@@ -44,19 +44,7 @@ void Engine::permutation_importance_prepared(const PreparedDataset *ds, const vo
     if (total > (1ll << 24)) throw InvalidArgument(w + ": " + std::to_string(total) + " variants (columns x n_repeats): at most 2^24 in one call");
     check_code_range(*ds, what, 0, stop);
     // the columns the walk of [0, stop) reads (greedy: through the trees a trailing run of one-leaf trees runs on into, as check_code_range counts them)
-    std::vector<uint8_t> used(static_cast<size_t>(F), 0);
-    {
-        int end = stop;
-        while (end < T && runs_on(model, end - 1)) ++end;
-        const size_t MD = md.max_depth;
-        const size_t s1 = model.oblivious() ? static_cast<size_t>(end) : static_cast<size_t>(end < T ? model.tree_indices[end] : md.n_leaves);
-        for (size_t s = 0; s < s1; ++s)
-            for (size_t d = 0; d < MD && static_cast<int>(d) < model.depths[s]; ++d) {
-                const size_t c = s * MD + d;
-                const int f = model.feature_indices[c];
-                if (model.is_numerics[c] && f >= 0 && f < F) used[f] = 1;
-            }
-    }
+    const std::vector<uint8_t> used = walked_columns(model, stop, F);
     ensure_device();
     reset_events();
     sync_model_to_device();

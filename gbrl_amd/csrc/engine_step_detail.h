@@ -12,6 +12,7 @@
 //   engine_leaves.hip      Engine::newton_leaves_prepared[_rank] / quantile_leaves_prepared: one tree's leaf values from a data set's rows
 //   engine_fit_prepared.hip  Engine::fit_prepared: fit()'s loop on a data set, in stages over one FitRun (engine_codes_detail.h: what these four share)
 //   engine_importance.hip  Engine::permutation_importance_prepared / permutation_host: the loss of a data set's rows with one column shuffled
+//   engine_pd.hip          Engine::partial_dependence_prepared / partial_dependence_codes: the predictions of a data set's rows with columns held constant
 #pragma once
 #include "engine.h"
 #include "hooks.h"

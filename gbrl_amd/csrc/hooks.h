@@ -34,6 +34,7 @@ namespace hooks {
     X(NO_SMALL_GROW) \
     X(NO_SMALL_PREP) \
     X(NO_SMALL_STATS) \
+    X(PD_GENERIC) \
     X(PERM_GENERIC) \
     X(PREDICT_CHAIN) \
     X(PREDICT_GENERIC) \

@@ -700,6 +700,19 @@ void perm_loss(const PredictModel &pm, const CodeTables &ct, const uint16_t *cod
                const float *alpha, uint64_t seed, const PermVariant *variants, int n_variants, double *loss_part, bool generic, hipStream_t s);
 int perm_tile_rows();   // rows of the streaming kernel's LDS tile = rows per loss partial
 //
+// The predictions of "columns held constant" variants of a data set's rows (pd_rows.hip; pd_core.h has PdVariant, the break rule and the launch
+// plan), none of them materialised.  A variant (col0, code0, col1, code1) reads column col0 -- and col1 when >= 0 -- of every row as that constant
+// code (in [0, n_bins]: the caller checks) and every other column from the row; col0 < 0 is the data set as it is.  For each of the n_variants
+// entries of `variants` (device) the trees [0, n_trees) are walked from the model's bias over the m rows of cr (predict_continue_codes' CodeRows) and
+// part[(v * D + d) * nb + j / 64] = the wave's sum of (double)p[j][d], nb = ceil(m / 64): n_variants x D x nb doubles, summed by
+// staged_loss_finish_rows(part, nb, n_variants * D, ...).  ice != nullptr (device): the row itself goes to ice[(slots[v] * m + j) * D + d] -- the
+// bits predict_continue_codes writes from a tiled bias for a data set that holds those codes; slots is device int32 [n_variants] (read only then).
+// n_variants <= pd_launch_variants(m, D) per launch keeps the partials under pd_core.h's budget; n_trees >= 1: the caller checks.  generic: the
+// one-thread-per-row kernel only (GBRL_HIP_PD_GENERIC=1; same bytes).  Always launches (m > 0, n_variants > 0).
+struct PdVariant;
+void pd_rows(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int n_trees, const PdVariant *variants, const int32_t *slots, int n_variants,
+             double *part, float *ice, bool generic, hipStream_t s);
+//
 // The objectives on a prediction matrix (objective.hip): the device functions of the tails applied to pred [n][D] (device).  targets: float32
 // [n][D] (rmse, logistic) or int32 [n] (softmax; every label in [0, D): the caller checks, label_counts below).  grad_out (device [n][D]) and
 // loss_part (staged_loss_partials(n) doubles, one per 64 rows, finished by staged_loss_finish) may each be null.  D <= 128.

@@ -859,6 +859,51 @@ int gbrl_hip_permutation_importance_prepared(gbrl_hip_model *m, const gbrl_hip_d
                                              double *loss_out /*host [n_cols][n_repeats]*/);
 void gbrl_hip_permutation_geometry(int *launch_variants, int *tile_rows);
 int gbrl_hip_feature_importance(const gbrl_hip_model *m, int kind, const int64_t *leaf_counts /*[n_leaves], may be NULL for split*/, double *out /*[input_dim]*/);
+/* Partial dependence and ICE curves on a data set, one and two columns (new: scikit-learn's inspection.partial_dependence).  csrc/pd_core.h has the
+ * host rules, csrc/pd_rows.hip the kernels.
+ *   breaks     A tree ensemble on binned data is a step function of each column.  bins(c) = the sorted distinct bins (gbrl_hip_condition_bins' rule for
+ *              the thresholds) of the numeric conditions on column c that the walk of the trees [0, n_trees) reads -- the conditions
+ *              gbrl_hip_permutation_importance_prepared counts a used column by, a greedy range's run-on trees included.  codes(c) = [0] + [b + 1 for b
+ *              in bins(c)], ascending, k + 1 entries; segment j is the code range [codes[j], codes[j + 1] - 1], the last one runs to n_bins; every code
+ *              of a segment answers every walked condition on c alike, so its first code stands for it; in x, segment j >= 1 begins just above
+ *              thresholds[c][codes[j] - 1].  A column the walk never tests: [0].
+ *   gbrl_hip_partial_dependence_codes(m, thresholds, n_features, n_bins, col, n_trees, out, count)  the rule with no device: out (room for n_bins + 1
+ *     entries) = codes(col), *count = k + 1.  n_trees == -1: all.  Only the walked conditions on col are converted.  Refused: NULL thresholds, out or
+ *     count, n_features / n_bins that are not the model's, col outside [0, n_features), a model without trees, n_trees outside [1, n_trees of the model]
+ *     (GBRL_HIP_E_INVALID); a walked condition on col whose value is not among its thresholds (GBRL_HIP_E_UNSUPPORTED, the tree is named).
+ *   gbrl_hip_partial_dependence_prepared(m, ds, variants, n_variants, rows, rows_on_device, n_rows, n_trees, sums_out, ice_out, ice_on_device)  on the
+ *     model's device.  variants: host int32 [n_variants][4] = {col0, code0, col1, code1}; col1 == -1: one column; col0 == -1 (col1 then -1 too): the data
+ *     set as it is, the baseline.  A variant holds its columns at the constant codes (any code in [0, n_bins]) for every row and leaves every other
+ *     column as the row has it.  rows: host or device int32 [n_rows], duplicates allowed, every entry in [0, rows of ds) (gbrl_hip_step_prepared's);
+ *     NULL: every row, n_rows == rows of ds.  For each variant the trees [0, n_trees) are walked from the bias: ice_out (may be NULL; host or device
+ *     float32 [n_variants][n_rows][output_dim]) = the rows, bit for bit gbrl_hip_predict_continue_prepared from a tiled bias over [0, n_trees) on a data
+ *     set that really holds those codes; sums_out (host float64 [n_variants][output_dim]) = the sum over the rows of (double)p[r][d] in a FIXED order:
+ *     one partial per 64 consecutive positions of the row list (the loss paths' wave butterfly), finished by the loss paths' finishing kernel.  Two
+ *     calls give the same bytes.  The partial dependence is sums_out / n_rows.  No variant is materialised: a launch stages a row tile once, writes up to
+ *     two 2-byte codes per row on chip for each of its variants and puts them back; the float64 partials of a launch (8 * variants * output_dim *
+ *     ceil(n_rows / 64) bytes) are kept under a fixed budget by cutting the variants per launch (gbrl_hip_partial_dependence_geometry).  A column of a
+ *     variant that no walked condition tests is dropped; a variant left without a column is not launched and reports the baseline's bits, as does every
+ *     variant of a model in which no optimizer owns an output.  Refused before the device is touched, GBRL_HIP_E_INVALID unless noted: what
+ *     gbrl_hip_predict_continue_prepared refuses about the model, the data set and rows (GBRL_HIP_E_UNSUPPORTED: output_dim > 128, a tree the thresholds
+ *     cannot express, which is named), a model without trees, n_trees outside [1, n_trees of the model] and not -1, NULL variants or sums_out,
+ *     n_variants < 1, a column outside [0, n_features) and not -1, col0 == col1, col1 without col0, a code outside [0, n_bins], more than 2^20 launched
+ *     variants, and with ice_out n_variants * n_rows * output_dim >= 2^31 (GBRL_HIP_E_UNSUPPORTED: pass rows).  Model and data set are left byte for
+ *     byte as they were.
+ *   gbrl_hip_partial_dependence_cells(col0, codes0, n0, col1, codes1, n1, out)  the cells of one entry as variants, no device: col1 < 0: {col0, codes0[i],
+ *     -1, 0} for every i; otherwise the row-major product, {col0, codes0[i], col1, codes1[j]} at out[(i * n1 + j) * 4] -- the order of the Python
+ *     result's cell axes.  out holds n0 * max(n1, 1) variants.  Refused: col0 < 0, col1 == col0, missing codes, NULL out.
+ *   gbrl_hip_partial_dependence_geometry(n_rows, output_dim, ...)  rows per partial (64), the variants one launch takes at that shape (1..64), the most
+ *     any launch takes (64), the scratch budget in bytes (64 MiB).
+ *   Out of scope: categorical columns and row-sharded models (the data-set family has neither), user grids, weighted means, centred and derivative ICE. */
+int gbrl_hip_partial_dependence_codes(const gbrl_hip_model *m, const float *thresholds /*[F*B]*/, int n_features, int n_bins, int col, int n_trees,
+                                      int32_t *out /*[n_bins + 1]*/, int *count);
+int gbrl_hip_partial_dependence_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *variants /*host [n_variants][4]*/, int n_variants,
+                                         const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows, int n_trees, double *sums_out /*host [n_variants][output_dim]*/,
+                                         float *ice_out /*[n_variants][n_rows][output_dim], may be NULL*/, int ice_on_device);
+int gbrl_hip_partial_dependence_cells(int col0, const int32_t *codes0, int n0, int col1, const int32_t *codes1 /*may be NULL when col1 < 0*/, int n1,
+                                      int32_t *out /*[n0 * max(n1, 1)][4]*/);
+void gbrl_hip_partial_dependence_geometry(int n_rows, int output_dim, int *rows_per_partial, int *launch_variants, int *max_launch_variants,
+                                          uint64_t *scratch_budget_bytes);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
