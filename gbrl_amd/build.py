@@ -20,7 +20,7 @@ EXT = os.path.join(HERE, "gbrl_cpp" + sysconfig.get_config_var("EXT_SUFFIX"))
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 
 LIB_SRCS = ["step_stats.hip", "step_binning.hip", "step_hist_build.hip", "step_hist_reduce.hip", "step_exchange.hip", "step_score.hip", "step_partition.hip", "step_plan.hip", "bin_like.hip", "small_grow.hip", "small_prep.hip", "neartie.hip", "seqsum.hip", "predict.hip", "predict_obl2.hip", "predict_grd_stream.hip", "predict_reg.hip", "predict_chain.hip", "predict_sched.hip", "predict_continue.hip", "predict_continue_codes.hip", "perm_loss.hip", "pd_rows.hip", "predict_staged.hip", "predict_leaves.hip", "refit.hip", "newton.hip", "leaf_quantile.hip", "rank.hip", "categorical.hip", "cat_rank.hip", "radix_sort.hip", "metric.hip", "quantile.hip", "radix_select.hip", "gather_codes.hip", "gather_cols.hip", "sample_rows.hip", "goss.hip", "objective.hip", "engine.hip", "engine_step.hip", "engine_prepared.hip", "engine_codes.hip", "engine_objective.hip", "engine_leaves.hip", "engine_fit_prepared.hip", "engine_importance.hip", "engine_pd.hip", "engine_candidates.hip", "engine_cat_candidates.hip", "engine_grow.hip", "engine_grow_levels.hip", "engine_mirror.hip", "engine_predict.hip", "engine_refit.hip", "engine_rank.hip", "engine_explain.hip", "shap.hip", "c_api.cpp", "model.cpp", "rccl_dyn.cpp", "explain.cpp", "hooks.cpp"]
-LIB_DEPS = LIB_SRCS + ["kernels.h", "kernels_common.h", "predict_rowwalk.h", "leaf_accum.h", "predict_loss.h", "score_common.h", "neartie_core.h", "sample_core.h", "perm_core.h", "pd_core.h", "objective_core.h", "newton_core.h", "quantile_core.h", "rank_core.h", "metric_core.h", "seqsum_core.h", "small_prep.h", "predict_reg_asm.h", "engine.h", "model.h", "explain.h", "cat_hash.h", "cat_candidates_host.h", "mirror_records.h", "hash_order_replay.h", "rccl_dyn.h", "hooks.h", "engine_step_detail.h", "engine_codes_detail.h", "engine_grow_detail.h", os.path.join("..", "..", "include", "gbrl_hip.h")]
+LIB_DEPS = LIB_SRCS + ["kernels.h", "kernels_common.h", "predict_rowwalk.h", "leaf_accum.h", "predict_loss.h", "score_common.h", "neartie_core.h", "sample_core.h", "perm_core.h", "pd_core.h", "shap_core.h", "objective_core.h", "newton_core.h", "quantile_core.h", "rank_core.h", "metric_core.h", "seqsum_core.h", "small_prep.h", "predict_reg_asm.h", "engine.h", "model.h", "explain.h", "cat_hash.h", "cat_candidates_host.h", "mirror_records.h", "hash_order_replay.h", "rccl_dyn.h", "hooks.h", "engine_step_detail.h", "engine_codes_detail.h", "engine_grow_detail.h", os.path.join("..", "..", "include", "gbrl_hip.h")]
 EXT_SRCS = ["binding.cpp"]
 
 

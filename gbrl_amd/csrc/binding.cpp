@@ -1838,6 +1838,133 @@ py::array_t<float> shap_impl(PyGBRL &self, bool whole_ensemble, int tree_idx, py
     return out;
 }
 
+// shap_prepared / shap_importance_prepared: the three polynomial arrays as ensemble_shap takes them (float32 NumPy), here with exactly max_depth's counts
+struct ShapPolyArgs {
+    HostArray nv, bp, of;
+    const float *norm() const { return static_cast<const float *>(nv.ptr); }
+    const float *base() const { return static_cast<const float *>(bp.ptr); }
+    const float *offset() const { return static_cast<const float *>(of.ptr); }
+};
+ShapPolyArgs read_shap_poly(const std::string &fn, int max_depth, py::object &norm_values, py::object &base_poly, py::object &offset) {
+    ShapPolyArgs a{host_array<py::array_t<float>>(norm_values), host_array<py::array_t<float>>(base_poly), host_array<py::array_t<float>>(offset)};
+    const size_t depth = static_cast<size_t>(max_depth);
+    auto count = [](const HostArray &x) { size_t k = 1; for (py::ssize_t d : x.shape) k *= static_cast<size_t>(d); return k; };
+    const struct { const HostArray &x; const char *name; size_t want; std::string shape; } all[] = {
+        {a.nv, "norm_values", (depth + 1) * depth, "(" + std::to_string(depth + 1) + ", " + std::to_string(depth) + ")"},
+        {a.bp, "base_poly", depth, "(" + std::to_string(depth) + ",)"},
+        {a.of, "offset", depth * depth, "(" + std::to_string(depth) + ", " + std::to_string(depth) + ")"}};
+    for (const auto &e : all) {
+        if (!e.x.ptr) fail(fn + ": " + e.name + " is missing (the three polynomial arrays ensemble_shap takes, built for the model's max_depth)");
+        if (count(e.x) != e.want)
+            fail(fn + ": " + e.name + " has " + std::to_string(count(e.x)) + " elements, the model's max_depth " + std::to_string(depth) + " needs shape " + e.shape);
+    }
+    return a;
+}
+
+// shap_prepared(ds, norm_values, base_poly, offset, rows=None, tree_idx=None) -> float32 [m, F, D]: NumPy for a "cpu" model, a DLPack capsule on the
+// model's device for a "cuda" one, as predict delivers
+py::object shap_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &norm_values, py::object &base_poly, py::object &offset, py::object &rows,
+                              py::object tree_idx_obj) {
+    const std::string fn = "shap_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    if (ds_obj.is_none()) {   // the library's own refusal: what it refuses about the model comes before the missing data set
+        check(gbrl_hip_shap_prepared(self.h, nullptr, nullptr, 0, 0, -1, nullptr, nullptr, nullptr, nullptr, 0));
+        fail(fn + ": null data set");
+    }
+    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
+    const gbrl_hip_dataset_desc info = pds.info();
+    const ShapPolyArgs poly = read_shap_poly(fn, md.max_depth, norm_values, base_poly, offset);
+    int tree_idx = -1;
+    if (!tree_idx_obj.is_none()) {
+        const long long t = tree_idx_obj.cast<long long>();
+        if (t < 0 || t >= md.n_trees)   // (-1 means "all" behind the C ABI only: None says it here)
+            fail(md.n_trees == 0 ? fn + ": the model has no trees"
+                                 : fn + ": tree_idx " + std::to_string(t) + " is outside [0, " + std::to_string(md.n_trees) + "), the model's trees (None: all)");
+        tree_idx = static_cast<int>(t);
+    }
+    Input none;
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
+    const int64_t m = std::max(r.m, 0), F = info.n_features, D = md.output_dim;
+    // the engine refuses the same (C callers); here too because a "cuda" model allocates its result on the device before the C call
+    if (static_cast<unsigned long long>(m) * static_cast<unsigned long long>(F) * static_cast<unsigned long long>(D) >= (1ull << 31))
+        fail(fn + ": the matrix of " + std::to_string(m) + " rows x " + std::to_string(F) + " features x " + std::to_string(D) +
+             " outputs has 2^31 elements or more: pass rows= to explain fewer rows, or use shap_importance_prepared");
+    Result<float> out(self, std::max<size_t>(static_cast<size_t>(m * F * D), 1));
+    int rc;
+    {
+        py::gil_scoped_release release;
+        rc = gbrl_hip_shap_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, tree_idx, poly.norm(), poly.base(), poly.offset(), out.get(), out.on_device());
+    }
+    check(rc);
+    return out.release({m, F, D});
+}
+
+// shap_importance_prepared(ds, norm_values, base_poly, offset, rows=None, chunk_rows=None) -> dict
+py::dict shap_importance_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &norm_values, py::object &base_poly, py::object &offset, py::object &rows,
+                                       py::object chunk_rows_obj) {
+    const std::string fn = "shap_importance_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    if (ds_obj.is_none()) {   // (as shap_prepared)
+        check(gbrl_hip_shap_importance_prepared(self.h, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr));
+        fail(fn + ": null data set");
+    }
+    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
+    const gbrl_hip_dataset_desc info = pds.info();
+    const ShapPolyArgs poly = read_shap_poly(fn, md.max_depth, norm_values, base_poly, offset);
+    int chunk_rows = 0;
+    if (!chunk_rows_obj.is_none()) {
+        const long long c = chunk_rows_obj.cast<long long>();
+        if (c <= 0 || c > INT32_MAX || c % 64 != 0) fail(fn + ": chunk_rows " + std::to_string(c) + " is not a positive multiple of 64 (None: the default)");
+        chunk_rows = static_cast<int>(c);
+    }
+    Input none;
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
+    const py::ssize_t F = info.n_features, D = md.output_dim;
+    py::array_t<double> sum({F, D}), sum_abs({F, D});
+    int used = 0, rc;
+    {
+        double *sp = sum.mutable_data(), *ap = sum_abs.mutable_data();
+        py::gil_scoped_release release;
+        rc = gbrl_hip_shap_importance_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, poly.norm(), poly.base(), poly.offset(), chunk_rows, sp, ap, &used);
+    }
+    check(rc);
+    py::array_t<double> mean({F, D}), mean_abs({F, D});
+    for (py::ssize_t i = 0; i < F * D; ++i) {
+        mean.mutable_data()[i] = sum.data()[i] / static_cast<double>(r.m);
+        mean_abs.mutable_data()[i] = sum_abs.data()[i] / static_cast<double>(r.m);
+    }
+    py::dict out;
+    out["sum"] = sum;
+    out["sum_abs"] = sum_abs;
+    out["mean"] = mean;
+    out["mean_abs"] = mean_abs;
+    out["n_rows"] = py::int_(r.m);
+    out["chunk_rows"] = py::int_(used);
+    return out;
+}
+
+// shap_sums_host(phi) -> (sum, sum_abs) float64 [F, D] ([C] for a two-dimensional phi): shap_core.h's reduction rule, no device
+py::tuple shap_sums_host_impl(py::array_t<float, py::array::c_style | py::array::forcecast> phi) {
+    if (phi.ndim() != 2 && phi.ndim() != 3) fail("shap_sums_host: phi must be float32 [m, F, D] or [m, C]");
+    std::vector<py::ssize_t> shape(phi.shape() + 1, phi.shape() + phi.ndim());
+    int64_t cols = 1;
+    for (py::ssize_t d : shape) cols *= d;
+    py::array_t<double> sum(shape), sum_abs(shape);
+    check(gbrl_hip_shap_sums_host(phi.data(), phi.shape(0), cols, sum.mutable_data(), sum_abs.mutable_data()));
+    return py::make_tuple(sum, sum_abs);
+}
+
+py::dict shap_geometry_impl(int F, int D) {
+    int tile = 0, chunk = 0;
+    uint64_t budget = 0;
+    gbrl_hip_shap_geometry(F, D, &tile, &chunk, &budget);
+    py::dict out;
+    out["tile_rows"] = tile;
+    out["default_chunk_rows"] = chunk;
+    out["scratch_budget"] = py::int_(budget);
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(gbrl_cpp, m) {
@@ -1957,6 +2084,15 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     m.def("permutation_geometry", &permutation_geometry_impl,
           "permutation_geometry() -> {'launch_variants': 64, 'tile_rows': 64}: the (column, repeat) variants one launch of permutation_importance_prepared\n"
           "walks, and the rows of its tile (= the rows per loss partial)");
+    m.def("shap_sums_host", &shap_sums_host_impl, py::arg("phi"),
+          "shap_sums_host(phi) -> (sum, sum_abs), float64 shaped like phi[0]\n\n"
+          "The reduction rule of GBRL.shap_importance_prepared on the host (no device is needed): phi float32 [m, F, D] (or [m, C]).  Rows fall into tiles of\n"
+          "64; per column a tile's partial is the sequential float64 sum, from 0.0, of its rows in order (sum_abs: of fabs of the float32); the total is the\n"
+          "sequential sum of the tile partials in order.  A NaN in a column propagates into that column's two totals and into no other.");
+    m.def("shap_geometry", &shap_geometry_impl, py::arg("F") = 1, py::arg("D") = 1,
+          "shap_geometry(F=1, D=1) -> {'tile_rows': 64, 'default_chunk_rows': ..., 'scratch_budget': 67108864}: the rows one float64 partial of\n"
+          "shap_importance_prepared sums, and its default chunk_rows for F features and D outputs: the largest multiple of 64 whose float32 scratch\n"
+          "[chunk_rows, F, D] stays within the budget, and at least 64");
     m.def("leaf_quantile_host", &leaf_quantile_host_impl, py::arg("x"), py::arg("leaves"), py::arg("n_leaves"), py::arg("alpha"),
           "leaf_quantile_host(x, leaves, n_leaves, alpha) -> {'values': float32 [n_leaves, D], 'counts': int64 [n_leaves], 'ranks': int64 [n_leaves, D]}\n\n"
           "The leaf rule of fit_prepared(leaf_update='quantile') and GBRL.quantile_leaves_prepared on the host (no device is needed): x float32 [m, D] are the\n"
@@ -2510,6 +2646,24 @@ PYBIND11_MODULE(gbrl_cpp, m) {
                               py::object &offset) {
         return shap_impl(self, true, 0, obs, categorical_obs, norm_values, base_poly, offset);
     }, py::arg("obs"), py::arg("categorical_obs"), py::arg("norm_values"), py::arg("base_poly"), py::arg("offset"));
+    g.def("shap_prepared", &shap_prepared_impl, py::arg("ds"), py::arg("norm_values"), py::arg("base_poly"), py::arg("offset"), py::arg("rows") = py::none(),
+          py::arg("tree_idx") = py::none(),
+          "shap_prepared(ds, norm_values, base_poly, offset, rows=None, tree_idx=None) -> float32 [m, F, D]\n\n"
+          "The SHAP values of the rows of a prepared data set (rows: step_prepared's int32 vector, host or device, duplicates allowed; None: every row),\n"
+          "computed from its bin codes on the device: NumPy for a 'cpu' model, a DLPack capsule on the model's device for a 'cuda' one.  Bit for bit\n"
+          "ensemble_shap(X[rows], None, norm_values, base_poly, offset) -- with tree_idx=t, tree_shap(t, ...) -- for the X the codes were made from: a\n"
+          "condition x > v is decided as code > bin, everything else is the same arithmetic.  The three polynomial arrays are ensemble_shap's.  Refused\n"
+          "before the device is touched: what predict_continue_prepared refuses, a model with categorical columns or without trees, tree_idx outside the\n"
+          "model, a missing or misshapen polynomial array, a (max_depth, output_dim) without a launch plan, and m * F * D >= 2^31 (pass rows=, or use\n"
+          "shap_importance_prepared).");
+    g.def("shap_importance_prepared", &shap_importance_prepared_impl, py::arg("ds"), py::arg("norm_values"), py::arg("base_poly"), py::arg("offset"),
+          py::arg("rows") = py::none(), py::arg("chunk_rows") = py::none(),
+          "shap_importance_prepared(ds, norm_values, base_poly, offset, rows=None, chunk_rows=None) -> dict\n\n"
+          "'sum', 'sum_abs', 'mean', 'mean_abs': float64 [F, D], the sums over the m rows of the SHAP values of shap_prepared and of their absolute values,\n"
+          "and those sums / m ('mean_abs' is the mean |SHAP| importance); 'n_rows' = m; 'chunk_rows' = the value used.  The [m, F, D] matrix is never held\n"
+          "whole: chunk_rows rows at a time (a positive multiple of 64; None: the largest whose float32 scratch stays within 64 MiB) are evaluated and\n"
+          "reduced on the device.  The sums follow gbrl_cpp.shap_sums_host's rule on that matrix byte for byte, whatever chunk_rows is.  Refusals as\n"
+          "shap_prepared's, without the 2^31 limit.");
     g.def("plot_tree", [](PyGBRL &self, int tree_idx, const std::string &filename) {
         check(gbrl_hip_plot_tree(self.h, tree_idx, filename.c_str()));
     }, py::arg("tree_idx") = -1, py::arg("filename"));

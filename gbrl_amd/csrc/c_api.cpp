@@ -22,6 +22,7 @@
 #include "quantile_core.h"
 #include "rank_core.h"
 #include "pd_core.h"
+#include "shap_core.h"
 #include "hooks.h"
 #include "explain.h"
 #include "rccl_dyn.h"
@@ -885,6 +886,41 @@ void gbrl_hip_partial_dependence_geometry(int n_rows, int output_dim, int *rows_
     if (launch_variants) *launch_variants = gbrl::kern::pd_launch_variants(n_rows < 1 ? 1 : n_rows, output_dim);
     if (max_launch_variants) *max_launch_variants = gbrl::kern::kPdMaxLaunchVariants;
     if (scratch_budget_bytes) *scratch_budget_bytes = gbrl::kern::kPdScratchBudget;
+}
+
+// ---- SHAP values on a data set: the matrix, its column sums, the reduction rule on the host (engine_explain.hip; shap_core.h has the rule and the plan)
+int gbrl_hip_shap_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int tree_idx,
+                           const float *norm_values, const float *base_poly, const float *offset, float *out, int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("shap_prepared");
+        m->engine.shap_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, tree_idx, norm_values, base_poly, offset, out, out_on_device != 0);
+    });
+}
+
+int gbrl_hip_shap_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
+                                      const float *norm_values, const float *base_poly, const float *offset, int chunk_rows, double *sum_out, double *abs_out,
+                                      int *chunk_rows_used) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("shap_importance_prepared");
+        m->engine.shap_importance_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, norm_values, base_poly, offset, chunk_rows, sum_out, abs_out,
+                                           chunk_rows_used);
+    });
+}
+
+int gbrl_hip_shap_sums_host(const float *phi, int64_t n_rows, int64_t n_cols, double *sum_out, double *abs_out) {
+    return guarded([&] {
+        if (sum_out == nullptr || abs_out == nullptr || n_rows < 0 || n_cols < 0 || (phi == nullptr && n_rows > 0 && n_cols > 0))
+            throw gbrl::InvalidArgument("shap_sums_host: a matrix [n_rows][n_cols] and a place for the two sums are needed");
+        gbrl::kern::shap_sums_host(phi, n_rows, static_cast<size_t>(n_cols), sum_out, abs_out);
+    });
+}
+
+void gbrl_hip_shap_geometry(int n_features, int output_dim, int *tile_rows, int *default_chunk_rows, uint64_t *budget_bytes) {
+    if (tile_rows) *tile_rows = gbrl::kern::kShapTileRows;
+    if (default_chunk_rows) *default_chunk_rows = gbrl::kern::shap_default_chunk_rows(n_features, output_dim);
+    if (budget_bytes) *budget_bytes = gbrl::kern::kShapScratchBudget;
 }
 
 static_assert(GBRL_HIP_IMPORTANCE_SPLIT == gbrl::kFeatureSplit && GBRL_HIP_IMPORTANCE_COVER == gbrl::kFeatureCover, "the importance kinds are the header's");

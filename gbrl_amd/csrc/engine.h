@@ -465,8 +465,21 @@ class Engine {
     // [n][n_num + n_cat][D] is overwritten.  Returns false when it was NOT computed (no HIP device, max_depth / output_dim beyond
     // the kernel's LDS budget, GBRL_HIP_SHAP_HOST=1): the caller then evaluates on the host (explain.cpp), which gives the same bits.
     // With GBRL_HIP_SHAP_DEVICE_ONLY=1 (test hook) the first two raise instead, so a result that came back was computed by k_shap.
+    // Under set_profiling the phase `shap` is k_shap alone (the name the data-set calls give it too).
     bool shap_on_device(int tree_idx, const float *obs, const char *cat, int n, const float *norm, const float *base_poly,
                         const float *offset, float *out);
+    // The same values from a prepared data set's bin codes (include/gbrl_hip.h, "SHAP values on a data set"): a numeric condition x > v is decided as
+    // code > bin, everything else is k_shap's, so the result is shap_on_device's on the observations the codes were made from, byte for byte.
+    // rows / rows_dev / m as step_prepared's (null: every row); tree_idx -1: every tree, summed in tree order.  norm / base_poly / offset: host,
+    // built for max_depth.  out: float32 [m][F][D], host or device, overwritten.  There is no host evaluation behind it: a (max_depth, output_dim)
+    // without a launch plan is Unsupported.  Refused before the device is touched: check_shap_prepared's list, and m * F * D >= 2^31.
+    void shap_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int tree_idx, const float *norm, const float *base_poly,
+                       const float *offset, float *out, bool out_dev);
+    // sum_out / abs_out: host float64 [F][D], the sums over the m rows of phi and of |phi| for the whole ensemble by shap_core.h's rule (tiles of 64
+    // positions, sequential float64): the bytes do not depend on chunk_rows (0: the default; else a positive multiple of 64), the matrix is never held
+    // whole.  *chunk_rows_used (nullable): the chunk size the call worked with.
+    void shap_importance_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *norm, const float *base_poly,
+                                  const float *offset, int chunk_rows, double *sum_out, double *abs_out, int *chunk_rows_used);
 
     void set_collective(const gbrl_hip_collective *hooks);
     // Native exchange: an RCCL communicator of this engine's own, collectives enqueued on its stream (no host sync).
@@ -755,6 +768,23 @@ class Engine {
     DevBuf d_shap_ops_, d_shap_nodes_, d_shap_values_, d_shap_poly_, d_shap_out_;
     int shap_n_ops_ = 0;
     uint64_t shap_prog_version_ = ~0ull;
+    // the codes form (engine_explain.hip): a program, polynomial arrays and result buffers of its own, cached under (model.version, thresholds id)
+    DevBuf d_shapc_ops_, d_shapc_nodes_, d_shapc_values_, d_shapc_poly_, d_shapc_out_, d_shapc_scratch_, d_shapc_part_, d_shapc_sums_;   // out: the host-bound matrix (released when the call ends); scratch: one chunk of the importance call (kept); part [tiles][2][F D] (released); sums [2][F D]
+    int shapc_n_ops_ = 0;
+    uint64_t shapc_prog_version_ = ~0ull, shapc_ds_id_ = 0;
+    struct ShapPoly { const float *norm, *base, *offset; };                  // device
+    struct ShapPreparedRun { const int32_t *rows; ShapPoly poly; };          // device: the row list (null: every row) and the polynomial arrays
+    int upload_shap_program(int t0, int t1, const int32_t *bins /*null: the float form*/, DevBuf &ops, DevBuf &nodes, DevBuf &values);   // returns the op count
+    ShapPoly upload_shap_poly(DevBuf &buf, const float *norm, const float *base_poly, const float *offset);
+    // what both data-set calls refuse, in order: check_prepared_dataset's list (categorical columns and a row-sharded model among it), output_dim > 128,
+    // a missing polynomial array, a model without trees, tree_idx outside it, check_row_count / check_host_rows, a shape without a launch plan, a tree
+    // the thresholds cannot express (check_code_range)
+    void check_shap_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int tree_idx, const float *norm,
+                             const float *base_poly, const float *offset);
+    ShapPreparedRun stage_shap_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int tree_idx, const float *norm,
+                                        const float *base_poly, const float *offset);
+    void launch_shap_codes(const PreparedDataset *ds, const ShapPreparedRun &r, int p0, int count, float *out);
+    void finish_shap_prepared(const char *launch, void *host, const void *dev, size_t bytes, const char *what);
 
     // ---- per-step workspace (grow-only, reused across steps) ----
     DevBuf d_obs_, d_grads_, d_qg_, d_stat_, d_partials_f64_, d_meanden_, d_maxbits_;

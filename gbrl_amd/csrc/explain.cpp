@@ -76,8 +76,8 @@ struct TreeBuilder {
             XNode &nd = out.nodes[n];
             nd.feature = m.feature_indices[c];
             nd.numeric = m.is_numerics[c] != 0;
+            nd.cond = static_cast<int>(c);
             if (nd.numeric) nd.threshold = m.feature_values[c];
-            else nd.cond = static_cast<int>(c);
         } else {
             const int leaf = next_leaf++;
             const int uniq = distinct_count(m.feature_indices.data() + static_cast<size_t>(row) * md, tree_depth);

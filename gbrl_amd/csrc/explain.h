@@ -20,7 +20,8 @@ struct ShapNode {
     int n_unique = 0;           // max over the leaves below of the number of distinct feature indices on their path
     bool numeric = true;
     float threshold = INFINITY;
-    int cond = -1;              // categorical condition: index of its 128-byte value in Model::categorical_values (row*max_depth+depth)
+    int cond = -1;              // the condition's slot row*max_depth+depth: a categorical one's 128-byte value in Model::categorical_values, a
+                                // numeric one's bin in a table shaped like feature_values (Engine::condition_bins); -1 for a leaf
     float weight = 1.0f;        // edge weight from the parent (cumulated with the parent's when tied)
     int pred = -1;              // leaves: offset of the leaf's [D] cover-weighted value in ShapTree::leaf_value
 };

@@ -836,6 +836,16 @@ int shap_block_threads(int max_depth, int D);   // 0: this (max_depth, D) does n
 void shap_values(const ShapOp *ops, int n_ops, const ShapNodeRec *nodes, const float *leaf_value, const float *obs, int n_num,
                  const int32_t *cat_ids, int n_cat, int n_samples, int D, int max_depth, const float *norm, const float *base,
                  const float *offset, float *out, hipStream_t s);
+// The same kernel with the numeric cells read from a prepared data set's bin codes: sample j of the m is row cr.rows[cr.row0 + j] (or cr.row0 + j)
+// of cr.codes, and a node record's `threshold` holds the condition's BIN (int32, bit cast; x > v <=> code > bin).  No categorical conditions.  out
+// [m][n_features][D] is accumulated into (zero it first).  shap_block_threads(max_depth, D) != 0: the caller checks.
+void shap_values_codes(const ShapOp *ops, int n_ops, const ShapNodeRec *nodes, const float *leaf_value, const CodeRows &cr, int n_features, int m, int D,
+                       int max_depth, const float *norm, const float *base, const float *offset, float *out, hipStream_t s);
+// The column sums of values [rows][n_cols] (device, n_cols = features x outputs) by shap_core.h's rule.  shap_reduce_tiles: one float64 partial per 64
+// consecutive rows, column and kind into part[tile0 + t][2][n_cols] (t = the tile of the chunk; kind 0 the sum, 1 the sum of fabs).  shap_reduce_finish:
+// sums [2][n_cols] = the partials of all `tiles` tiles added in ascending order.
+void shap_reduce_tiles(const float *phi, int rows, int n_cols, double *part, int tile0, hipStream_t s);
+void shap_reduce_finish(const double *part, int tiles, int n_cols, double *sums, hipStream_t s);
 
 }  // namespace kern
 }  // namespace gbrl

@@ -6,8 +6,14 @@
 // stacks C, G [max_depth+1][max_depth] live in LDS with the thread as the fastest index (conflict-free); node records and the
 // polynomial vectors are uniform reads (scalar cache).  The arithmetic is the host evaluation's, rounding for rounding
 // (explain.cpp Walker: same order of additions, same two fused multiply-adds, IEEE divisions), so both give the same bits.
+//
+// k_shap is a template over what a sample's numeric cells are read through: the float observations (tree_shap / ensemble_shap), or a prepared
+// data set's bin codes (shap_prepared / shap_importance_prepared), where the node records hold the bin and the decision is code > bin.  The body
+// is one text; everything but the decision is the same instructions.  k_shap_tile_sums / k_shap_finish reduce a chunk of values to the float64
+// column sums of shap_core.h's rule.
 #include "kernels.h"
 #include "kernels_common.h"
+#include "shap_core.h"
 
 #pragma clang fp contract(off)
 
@@ -18,8 +24,39 @@ namespace {
 
 constexpr int kShapMaxThreads = 256;
 
+// ---- what k_shap reads a sample's numeric cells through: `x[feature] > nd.threshold` is the only expression that touches them
+// the observations themselves, float32 [n_samples][n_num] (null: a model without numeric features)
+struct ShapFloatRows {
+    const float *obs;
+    int n_num;
+    using Row = const float *;
+    __device__ __forceinline__ Row row(long long s) const { return obs ? obs + s * n_num : nullptr; }
+};
+// a prepared data set's bin codes: sample s is data set row rows[row0 + s] (or row0 + s), its cell of feature f the 2-byte code at
+// [f / 16][row][f % 16].  The node records of this form hold the condition's bin in the four bytes of `threshold` (bit cast), and
+// `x[f] > nd.threshold` is `code > bin` -- the same answer as the float comparison for every float (engine_codes.hip has the rule).
+// All D lanes of a sample read the same address.
+struct ShapCode {
+    int code;
+    __device__ __forceinline__ bool operator>(float bin_bits) const { return code > __float_as_int(bin_bits); }
+};
+struct ShapCodeRow {
+    const uint16_t *rec;     // the row's record of group 0
+    size_t group_stride;     // n_rows * 16
+    __device__ __forceinline__ ShapCode operator[](int f) const { return ShapCode{static_cast<int>(rec[static_cast<size_t>(f >> 4) * group_stride + (f & 15)])}; }
+};
+struct ShapCodeRows {
+    CodeRows cr;
+    using Row = ShapCodeRow;
+    __device__ __forceinline__ Row row(long long s) const {
+        const size_t src = static_cast<size_t>(cr.rows ? cr.rows[cr.row0 + s] : cr.row0 + s);
+        return ShapCodeRow{cr.codes + src * kCodeGroup, static_cast<size_t>(cr.n_rows) * kCodeGroup};
+    }
+};
+
+template <typename Rows>
 __global__ __launch_bounds__(kShapMaxThreads) void k_shap(const ShapOp *__restrict__ ops, int n_ops, const ShapNodeRec *__restrict__ nodes,
-                                                       const float *__restrict__ leaf_value, const float *__restrict__ obs, int n_num,
+                                                       const float *__restrict__ leaf_value, const Rows rows, int n_num,
                                                        const int32_t *__restrict__ cat_ids, int n_cat, int n_samples, int D, int md,
                                                        const float *__restrict__ norm, const float *__restrict__ base,
                                                        const float *__restrict__ offset, float *__restrict__ out) {
@@ -34,7 +71,7 @@ __global__ __launch_bounds__(kShapMaxThreads) void k_shap(const ShapOp *__restri
     float *C = lds + t, *G = lds + tile * nt + t;
     float *Q = lds + 2 * tile * nt + t, *QA = Q + (md + 1) * nt;
     auto at = [nt](float *p, int idx) -> float & { return p[idx * nt]; };
-    const float *x = obs ? obs + (live ? s : 0) * n_num : nullptr;
+    const typename Rows::Row x = rows.row(live ? s : 0);
     const int32_t *xc = cat_ids ? cat_ids + (live ? s : 0) * n_cat : nullptr;
     float *phi = out + (live ? s : 0) * static_cast<long long>(n_num + n_cat) * D + j;
     uint32_t act = 0, pass = 0;      // bit k: state of the open node at level k (at most one node per level is open)
@@ -114,20 +151,71 @@ int shap_block_threads(int md, int D) {
     return 0;
 }
 
-void shap_values(const ShapOp *ops, int n_ops, const ShapNodeRec *nodes, const float *leaf_value, const float *obs, int n_num,
-                 const int32_t *cat_ids, int n_cat, int n_samples, int D, int md, const float *norm, const float *base,
-                 const float *offset, float *out, hipStream_t s) {
+namespace {
+
+template <typename Rows>
+void launch_shap(const ShapOp *ops, int n_ops, const ShapNodeRec *nodes, const float *leaf_value, const Rows &rows, int n_num, const int32_t *cat_ids,
+                 int n_cat, int n_samples, int D, int md, const float *norm, const float *base, const float *offset, float *out, hipStream_t s) {
     if (n_samples <= 0 || n_ops <= 0) return;
     const int nt = shap_block_threads(md, D);
-    static PerDeviceOnce attr_set;
+    static PerDeviceOnce attr_set;   // (one per instantiation)
     if (attr_set.first()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_shap), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_shap<Rows>), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
     }
     const int per_block = nt / D;
     const unsigned blocks = static_cast<unsigned>((n_samples + per_block - 1) / per_block);
     const size_t lds = sizeof(float) * nt * (2 * (md + 1) * md + 2 * (md + 1));
-    hipLaunchKernelGGL(k_shap, dim3(blocks), dim3(nt), lds, s, ops, n_ops, nodes, leaf_value, obs, n_num, cat_ids, n_cat, n_samples, D, md,
+    hipLaunchKernelGGL(k_shap<Rows>, dim3(blocks), dim3(nt), lds, s, ops, n_ops, nodes, leaf_value, rows, n_num, cat_ids, n_cat, n_samples, D, md,
                        norm, base, offset, out);
+}
+
+// ---- the reduction of a [rows][C] chunk of values (shap_core.h has the rule)
+constexpr int kShapSumThreads = 256;
+
+// one thread per (column, tile): the threads of a block read consecutive columns of one row (coalesced) and walk the tile's rows in order.
+// part [tiles of the call][2][C]; tile0: the first tile of this chunk
+__global__ __launch_bounds__(kShapSumThreads) void k_shap_tile_sums(const float *__restrict__ phi, int rows, int C, double *__restrict__ part, int tile0) {
+    const int t = blockIdx.x;
+    const int r0 = t * kShapTileRows, n = min(kShapTileRows, rows - r0);
+    double *dst = part + static_cast<size_t>(tile0 + t) * 2 * C;
+    for (int c = blockIdx.y * kShapSumThreads + threadIdx.x; c < C; c += gridDim.y * kShapSumThreads) {
+        double s, a;
+        shap_tile_sums(phi + static_cast<size_t>(r0) * C + c, static_cast<size_t>(C), n, &s, &a);
+        dst[c] = s;
+        dst[C + c] = a;
+    }
+}
+
+// one thread per (kind, column): the tile partials in ascending order.  sums [2][C]: the sums, then the sums of the absolute values
+__global__ __launch_bounds__(kShapSumThreads) void k_shap_finish(const double *__restrict__ part, int tiles, int C2, double *__restrict__ sums) {
+    for (int c = blockIdx.x * kShapSumThreads + threadIdx.x; c < C2; c += gridDim.x * kShapSumThreads)
+        sums[c] = shap_finish_sums(part + c, static_cast<size_t>(C2), tiles);
+}
+
+}  // namespace
+
+void shap_values(const ShapOp *ops, int n_ops, const ShapNodeRec *nodes, const float *leaf_value, const float *obs, int n_num,
+                 const int32_t *cat_ids, int n_cat, int n_samples, int D, int md, const float *norm, const float *base,
+                 const float *offset, float *out, hipStream_t s) {
+    launch_shap(ops, n_ops, nodes, leaf_value, ShapFloatRows{obs, n_num}, n_num, cat_ids, n_cat, n_samples, D, md, norm, base, offset, out, s);
+}
+
+void shap_values_codes(const ShapOp *ops, int n_ops, const ShapNodeRec *nodes, const float *leaf_value, const CodeRows &cr, int n_features, int m, int D,
+                       int md, const float *norm, const float *base, const float *offset, float *out, hipStream_t s) {
+    launch_shap(ops, n_ops, nodes, leaf_value, ShapCodeRows{cr}, n_features, nullptr, 0, m, D, md, norm, base, offset, out, s);
+}
+
+void shap_reduce_tiles(const float *phi, int rows, int n_cols, double *part, int tile0, hipStream_t s) {
+    if (rows <= 0 || n_cols <= 0) return;
+    const unsigned col_blocks = static_cast<unsigned>(std::min<long long>(65535, (static_cast<long long>(n_cols) + kShapSumThreads - 1) / kShapSumThreads));
+    hipLaunchKernelGGL(k_shap_tile_sums, dim3(static_cast<unsigned>(shap_tiles(rows)), col_blocks), dim3(kShapSumThreads), 0, s, phi, rows, n_cols, part, tile0);
+}
+
+void shap_reduce_finish(const double *part, int tiles, int n_cols, double *sums, hipStream_t s) {
+    if (n_cols <= 0) return;
+    const long long C2 = 2ll * n_cols;
+    const unsigned blocks = static_cast<unsigned>(std::min<long long>(1 << 20, (C2 + kShapSumThreads - 1) / kShapSumThreads));
+    hipLaunchKernelGGL(k_shap_finish, dim3(blocks), dim3(kShapSumThreads), 0, s, part, tiles, static_cast<int>(C2), sums);
 }
 
 }  // namespace kern

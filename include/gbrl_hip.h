@@ -904,6 +904,44 @@ int gbrl_hip_partial_dependence_cells(int col0, const int32_t *codes0, int n0, i
                                       int32_t *out /*[n0 * max(n1, 1)][4]*/);
 void gbrl_hip_partial_dependence_geometry(int n_rows, int output_dim, int *rows_per_partial, int *launch_variants, int *max_launch_variants,
                                           uint64_t *scratch_budget_bytes);
+/* SHAP values on a data set: the matrix and its mean |SHAP| reduction (new: LightGBM's pred_contrib on a Dataset).  csrc/shap_core.h has the host rules,
+ * csrc/shap.hip the kernels.
+ *   decisions  A numeric condition x[f] > v is evaluated as code(row, f) > bin, bin by gbrl_hip_condition_bins' rule for the data set's thresholds (keyed
+ *              on the thresholds id like every other data-set call).  Everything else is gbrl_hip_ensemble_shap's device evaluation, rounding for
+ *              rounding: the program, the edge weights, the arithmetic and its order.  x > v <=> code > bin for every float (NaN, infinities and signed
+ *              zeros included), so the values equal gbrl_hip_ensemble_shap / gbrl_hip_tree_shap on the observations the codes were made from, byte
+ *              for byte.
+ *   reduction  Positions p = 0 .. n_rows - 1 of the row list fall into tiles t = p / 64.  For each (feature, output) a tile's partial is the sequential
+ *              float64 sum, from 0.0, ascending in p, of (double)phi[p][f][d]; a second partial does the same with fabs of the float32.  The total is the
+ *              sequential ascending sum of the tile partials from 0.0 (no fused multiply-add anywhere: there is no product).  The result does not depend on
+ *              chunk_rows, on rows == NULL against 0 .. n - 1, or on how many launches ran.  A NaN in a column propagates into that column's two totals.
+ *   gbrl_hip_shap_prepared(m, ds, rows, rows_on_device, n_rows, tree_idx, norm_values, base_poly, offset, out, out_on_device)  on the model's device.
+ *     rows: host or device int32 [n_rows], duplicates allowed, every entry in [0, rows of ds) (gbrl_hip_step_prepared's); NULL: every row, n_rows == rows
+ *     of ds.  tree_idx == -1: every tree, summed in tree order; else that tree alone.  norm_values [(max_depth + 1)][max_depth], base_poly [max_depth],
+ *     offset [max_depth][max_depth]: host, as gbrl_hip_ensemble_shap takes them.  out: host or device float32 [n_rows][n_features][output_dim], overwritten.
+ *   gbrl_hip_shap_importance_prepared(m, ds, rows, rows_on_device, n_rows, norm_values, base_poly, offset, chunk_rows, sum_out, abs_out, chunk_rows_used)
+ *     sum_out / abs_out: host float64 [n_features][output_dim], the reduction of the whole ensemble's values over the rows; mean |SHAP| is abs_out /
+ *     n_rows.  The matrix is never held whole: chunk_rows positions at a time are evaluated into a float32 scratch [chunk_rows][n_features][output_dim]
+ *     (never more rows than n_rows rounded up to a tile), every chunk is reduced to its tile partials [tiles][2][n_features * output_dim], one finishing
+ *     launch adds them and 2 * n_features * output_dim doubles are read back.  chunk_rows: a positive multiple of 64; 0: the largest multiple of 64 whose
+ *     scratch stays within 64 MiB (partial dependence's budget), and at least 64.  *chunk_rows_used (may be NULL): the value the call worked with.
+ *   Both are refused before the device is touched, GBRL_HIP_E_INVALID unless noted: what gbrl_hip_predict_continue_prepared refuses about the model, the
+ *     data set and rows (GBRL_HIP_E_UNSUPPORTED: a row-sharded model, a model with categorical columns, output_dim > 128, a tree the thresholds cannot
+ *     express, which is named); a NULL polynomial array or result; a model without trees; tree_idx outside [0, n_trees) and not -1; a (max_depth,
+ *     output_dim) the kernel has no launch plan for (GBRL_HIP_E_UNSUPPORTED, both are named: the codes live on the device, there is no host evaluation to
+ *     hand over to; gbrl_hip_shap_plan tells); chunk_rows negative or no multiple of 64; for gbrl_hip_shap_prepared n_rows * n_features * output_dim >=
+ *     2^31 (GBRL_HIP_E_UNSUPPORTED: pass rows, or use the importance call).  Model and data set are left byte for byte as they were.
+ *   gbrl_hip_shap_sums_host(phi, n_rows, n_cols, sum_out, abs_out)  the reduction rule with no device: phi host float32 [n_rows][n_cols], both results
+ *     float64 [n_cols].
+ *   gbrl_hip_shap_geometry(n_features, output_dim, ...)  rows per tile (64), the default chunk_rows at that shape, the scratch budget in bytes (64 MiB).
+ *   Out of scope: categorical columns, interaction values, weighted means, a tree range other than all trees or one tree. */
+int gbrl_hip_shap_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows, int tree_idx /*-1: all*/,
+                           const float *norm_values, const float *base_poly, const float *offset, float *out /*[n_rows][n_features][output_dim]*/, int out_on_device);
+int gbrl_hip_shap_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows,
+                                      const float *norm_values, const float *base_poly, const float *offset, int chunk_rows /*0: default*/,
+                                      double *sum_out /*host [n_features][output_dim]*/, double *abs_out /*likewise*/, int *chunk_rows_used /*may be NULL*/);
+int gbrl_hip_shap_sums_host(const float *phi /*host [n_rows][n_cols]*/, int64_t n_rows, int64_t n_cols, double *sum_out /*[n_cols]*/, double *abs_out /*[n_cols]*/);
+void gbrl_hip_shap_geometry(int n_features, int output_dim, int *tile_rows, int *default_chunk_rows, uint64_t *budget_bytes);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
