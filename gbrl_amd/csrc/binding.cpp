@@ -9,316 +9,19 @@
 //   * the DLPack capsule carries kDLROCM (10): torch-ROCm rejects the reference's hard-coded kDLCUDA.
 //   * export / SHAP / print are served from the host copy of the ensemble (csrc/explain.cpp); plot_tree raises the
 //     reference's own no-Graphviz error (this image has no Graphviz).
-#include <pybind11/numpy.h>
-#include <algorithm>
-#include <pybind11/pybind11.h>
+#include "binding_common.h"
 
-#include <cstring>
-#include <memory>
-#include <sstream>
-#include <string>
-#include <type_traits>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/gbrl_hip.h"
-
-namespace py = pybind11;
+using namespace gbrl_py;
 
 namespace {
-
-// ---- DLPack ABI (public spec, "dltensor" capsule protocol) -- the minimal declarations needed to hand a buffer over
-enum { kDLCPU_ = 1, kDLROCM_ = 10 };
-struct DLDevice_ { int32_t device_type; int32_t device_id; };
-struct DLDataType_ { uint8_t code; uint8_t bits; uint16_t lanes; };
-struct DLTensor_ {
-    void *data; DLDevice_ device; int32_t ndim; DLDataType_ dtype; int64_t *shape; int64_t *strides; uint64_t byte_offset;
-};
-struct DLManagedTensor_ {
-    DLTensor_ dl_tensor; void *manager_ctx; void (*deleter)(DLManagedTensor_ *);
-};
-
-void dl_deleter(DLManagedTensor_ *self) {
-    if (self->dl_tensor.device.device_type == kDLROCM_) gbrl_hip_device_free(self->dl_tensor.data);
-    else delete[] static_cast<float *>(self->dl_tensor.data);
-    delete[] self->dl_tensor.shape;
-    delete self;
-}
-
-void capsule_destructor(PyObject *cap) {
-    // an unconsumed capsule still owns the tensor (consumers rename it to "used_dltensor")
-    if (PyCapsule_IsValid(cap, "dltensor")) {
-        auto *mt = static_cast<DLManagedTensor_ *>(PyCapsule_GetPointer(cap, "dltensor"));
-        if (mt && mt->deleter) mt->deleter(mt);
-    }
-}
-
-py::object make_dlpack(void *data, const std::vector<int64_t> &shape, bool on_device, int device_id, bool int32 = false) {
-    auto *mt = new DLManagedTensor_;
-    mt->dl_tensor.data = data;
-    mt->dl_tensor.device = {on_device ? kDLROCM_ : kDLCPU_, on_device ? device_id : 0};
-    mt->dl_tensor.ndim = static_cast<int32_t>(shape.size());
-    mt->dl_tensor.dtype = {static_cast<uint8_t>(int32 ? 0 /*kDLInt*/ : 2 /*kDLFloat*/), 32, 1};
-    mt->dl_tensor.shape = new int64_t[shape.size()];
-    std::copy(shape.begin(), shape.end(), mt->dl_tensor.shape);
-    mt->dl_tensor.strides = nullptr;
-    mt->dl_tensor.byte_offset = 0;
-    mt->manager_ctx = nullptr;
-    mt->deleter = dl_deleter;
-    return py::reinterpret_steal<py::object>(PyCapsule_New(mt, "dltensor", capsule_destructor));
-}
-
-[[noreturn]] void fail(const std::string &msg) { throw std::runtime_error(msg); }
-void check(int status) {
-    if (status != GBRL_HIP_OK) fail(gbrl_hip_last_error());
-}
-
-struct Input {
-    const void *ptr = nullptr;
-    std::vector<size_t> shape;
-    bool on_device = false;
-    py::object keep;  // keeps a converted NumPy array alive for the duration of the call
-};
-
-// handle_input_info (binding.cpp:156-190): None | NumPy array | (data_ptr, shape, dtype, device)
-// `categorical`: 0 = float32 values, 1 = 128-byte cells, 2 = int32 dictionary ids (encode_categorical / predict_encoded, an extension)
-Input read_input(py::object &obj, const std::string &name, bool none_allowed, const std::string &fn, int categorical) {
-    Input in;
-    if (obj.is_none()) {
-        if (!none_allowed) fail("Cannot call " + fn + " without " + name + "!");
-        return in;
-    }
-    if (py::isinstance<py::array>(obj)) {
-        py::array arr = py::array::ensure(obj, py::array::c_style | py::array::forcecast);
-        if (!arr) fail("Could not convert object to a contiguous NumPy array");
-        py::buffer_info info = arr.request();
-        const std::string want = categorical == 1 ? "128s" : categorical == 2 ? py::format_descriptor<int32_t>::format() : py::format_descriptor<float>::format();
-        if (info.format != want) {
-            std::stringstream ss;
-            ss << "Expected array of format '" << want << "', but got '" << info.format << "'";
-            fail(ss.str());
-        }
-        in.ptr = info.ptr;
-        in.shape.assign(info.shape.begin(), info.shape.end());
-        in.keep = arr;
-        return in;
-    }
-    if (py::isinstance<py::tuple>(obj)) {
-        py::tuple t = obj.cast<py::tuple>();
-        if (t.size() != 4) fail("Expected a tuple of size 4: (data_ptr, shape, dtype, device)");
-        const uintptr_t raw = t[0].cast<uintptr_t>();
-        in.ptr = (raw == 0 || raw == static_cast<uintptr_t>(-1)) ? nullptr : reinterpret_cast<const void *>(raw);
-        for (py::handle d : t[1].cast<py::tuple>()) in.shape.push_back(d.cast<size_t>());
-        const std::string dtype = t[2].cast<std::string>();
-        if (categorical == 2) {
-            if (dtype != "torch.int32") fail("Expected dtype torch.int32, but got " + dtype);
-        } else if (categorical) {
-            // extension over the reference (which takes categorical cells as NumPy S128 arrays only): a device-resident cell
-            // matrix, [n, n_cat] cells of 128 bytes each (e.g. a torch.uint8 tensor [n, n_cat, 128]), announced as dtype "S128"
-            if (dtype != "S128" && dtype != "|S128") fail("Unsupported data type: " + dtype);
-        } else if (dtype != "torch.float32") {
-            fail("Expected dtype torch.float32, but got " + dtype);
-        }
-        const std::string dev = t[3].cast<std::string>();
-        if (dev == "cpu") in.on_device = false;
-        else if (dev == "cuda" || dev == "gpu") in.on_device = true;
-        else fail("Invalid device! Options are: cpu/cuda");
-        return in;
-    }
-    fail("Unknown " + name + " type! Must be a NumPy array or tuple.");
-}
-
-int parse_enum(const std::string &s, std::initializer_list<std::pair<const char *, int>> opts, const char *err) {
-    for (const auto &o : opts)
-        if (s == o.first) return o.second;
-    fail(err);
-}
-int parse_device(const std::string &s) {  // stringTodeviceType, types.cpp:58-62
-    return parse_enum(s, {{"cpu", 0}, {"cuda", 1}, {"gpu", 1}}, "Invalid device! Options are: cpu/cuda");
-}
-
-// parity mode names of GBRL(parity_mode=...), set_parity_mode and get_parity_mode (gbrl_hip_parity_mode, include/gbrl_hip.h)
-int parse_parity_mode(const std::string &s) {
-    return parse_enum(s, {{"default", GBRL_HIP_PARITY_DEFAULT}, {"reference", GBRL_HIP_PARITY_REFERENCE}, {"exact_argmax", GBRL_HIP_PARITY_EXACT_ARGMAX}},
-                      "Invalid parity mode! Options are: default/reference/exact_argmax");
-}
-// objective names of fit_prepared(objective=), objective_gradient and objective_gradient_host (GBRL_HIP_OBJ_*, include/gbrl_hip.h)
-int parse_objective(const std::string &s) {
-    return parse_enum(s, {{"rmse", GBRL_HIP_OBJ_RMSE}, {"logistic", GBRL_HIP_OBJ_LOGISTIC}, {"softmax", GBRL_HIP_OBJ_SOFTMAX}, {"quantile", GBRL_HIP_OBJ_QUANTILE},
-                          {"pairwise", GBRL_HIP_OBJ_PAIRWISE}, {"lambdarank", GBRL_HIP_OBJ_LAMBDARANK}},
-                      "Invalid objective! Options are: rmse/logistic/softmax/quantile/pairwise/lambdarank");
-}
-// metric names of fit_prepared(eval_metric=), eval_metric and eval_metric_host (GBRL_HIP_METRIC_*, include/gbrl_hip.h)
-int parse_metric(const std::string &s) {
-    return parse_enum(s, {{"error", GBRL_HIP_METRIC_ERROR}, {"auc", GBRL_HIP_METRIC_AUC}}, "Invalid metric! Options are: error/auc");
-}
-// leaf rule names of fit_prepared(leaf_update=) (GBRL_HIP_LEAF_*, include/gbrl_hip.h)
-int parse_leaf_update(const std::string &s) {
-    return parse_enum(s, {{"gradient", GBRL_HIP_LEAF_GRADIENT}, {"newton", GBRL_HIP_LEAF_NEWTON}, {"quantile", GBRL_HIP_LEAF_QUANTILE}},
-                      "Invalid leaf_update! Options are: gradient/newton/quantile");
-}
-const char *parity_mode_name(int mode) {
-    return mode == GBRL_HIP_PARITY_REFERENCE ? "reference" : (mode == GBRL_HIP_PARITY_EXACT_ARGMAX ? "exact_argmax" : "default");
-}
-
-class PyGBRL {
-   public:
-    gbrl_hip_model *h = nullptr;
-    int device = 0;  // 0 = "cpu" delivery (NumPy), 1 = "cuda" delivery (DLPack / kDLROCM)
-
-    PyGBRL(int input_dim, int output_dim, int policy_dim, int max_depth, int min_data_in_leaf, int n_bins, int par_th,
-           float cv_beta, const std::string &split_score_func, const std::string &generator_type, bool use_cv,
-           int batch_size, const std::string &grow_policy, int verbose, const std::string &dev, const std::string &name,
-           const std::string &parity_mode = "default") {
-        gbrl_hip_config c{};
-        c.input_dim = input_dim; c.output_dim = output_dim; c.policy_dim = policy_dim; c.max_depth = max_depth;
-        c.min_data_in_leaf = min_data_in_leaf; c.n_bins = n_bins; c.par_th = par_th; c.cv_beta = cv_beta;
-        // string parsing as types.cpp:31-62
-        c.split_score_func = parse_enum(split_score_func, {{"L2", 0}, {"l2", 0}, {"Cosine", 1}, {"cosine", 1}},
-                                        "Invalid score function! Options are: Cosine/L2");
-        c.generator_type = parse_enum(generator_type, {{"uniform", 0}, {"Uniform", 0}, {"quantile", 1}, {"Quantile", 1}},
-                                      "Invalid generator function! Options are: Uniform/Quantile");
-        c.grow_policy = parse_enum(grow_policy, {{"greedy", 0}, {"Greedy", 0}, {"oblivious", 1}, {"Oblivious", 1}},
-                                   "Invalid generator function! Options are: Greedy/Oblivious");
-        c.use_control_variates = use_cv ? 1 : 0;
-        c.batch_size = batch_size; c.verbose = verbose; c.device_ordinal = -1; c.learner_name = name.c_str();
-        device = parse_device(dev);
-        const int parity = parse_parity_mode(parity_mode);
-        h = gbrl_hip_create(&c);
-        if (!h) fail(gbrl_hip_last_error());
-        if (gbrl_hip_set_parity_mode(h, parity, 0) != GBRL_HIP_OK) { gbrl_hip_destroy(h); h = nullptr; fail(gbrl_hip_last_error()); }
-    }
-    explicit PyGBRL(const PyGBRL &o) : device(o.device) {
-        h = gbrl_hip_clone(o.h);
-        if (!h) fail(gbrl_hip_last_error());
-    }
-    explicit PyGBRL(gbrl_hip_model *loaded) : h(loaded), device(0) {}
-    ~PyGBRL() { gbrl_hip_destroy(h); }
-
-    gbrl_hip_metadata meta() const {
-        gbrl_hip_metadata m{};
-        gbrl_hip_get_metadata(h, &m);
-        return m;
-    }
-};
-
-// rows, numeric and categorical feature counts of a predict batch: shape inference for 1-D inputs as binding.cpp:820-923
-struct BatchShape { int n, n_num, n_cat; };
-BatchShape infer_batch(const Input &o, const Input &c, int in_dim) {
-    int n = 0, n_num = 0, n_cat = 0;
-    auto neq = [&](size_t a, size_t b) {
-        if (a != b) {
-            std::stringstream ss;
-            ss << "Number of samples is not equal between obs and categorical obs " << a << " != " << b;
-            fail(ss.str());
-        }
-    };
-    if (o.ptr && c.ptr) {
-        if (o.shape.size() == 1 && c.shape.size() == 1) {
-            if (static_cast<int>(o.shape[0] + c.shape[0]) == in_dim) { n = 1; n_num = static_cast<int>(o.shape[0]); n_cat = static_cast<int>(c.shape[0]); }
-            else { neq(o.shape[0], c.shape[0]); n = static_cast<int>(o.shape[0]); n_num = 1; n_cat = 1; }
-        } else if (o.shape.size() == 1) { neq(o.shape[0], c.shape[0]); n = static_cast<int>(o.shape[0]); n_num = 1; n_cat = static_cast<int>(c.shape[1]);
-        } else if (c.shape.size() == 1) { neq(o.shape[0], c.shape[0]); n = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]); n_cat = 1;
-        } else { neq(o.shape[0], c.shape[0]); n = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]); n_cat = static_cast<int>(c.shape[1]); }
-    } else if (o.ptr) {
-        if (o.shape.size() == 1) {
-            if (static_cast<int>(o.shape[0]) == in_dim) { n = 1; n_num = in_dim; } else { n = static_cast<int>(o.shape[0]); n_num = 1; }
-        } else { n = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]); }
-    } else {
-        if (c.shape.size() == 1) {
-            if (static_cast<int>(c.shape[0]) == in_dim) { n = 1; n_cat = in_dim; } else { n = static_cast<int>(c.shape[0]); n_cat = 1; }
-        } else { n = static_cast<int>(c.shape[0]); n_cat = static_cast<int>(c.shape[1]); }
-    }
-    if (n_num + n_cat != in_dim) {
-        std::stringstream ss;
-        ss << "Total number of features " << n_num + n_cat << " != input dim " << in_dim;
-        fail(ss.str());
-    }
-    return {n, n_num, n_cat};
-}
-
-// ---- the three blocks every predict-family method is made of
-// obs and cat_obs of function `fn` (ids: cat_obs holds int32 dictionary ids, the _encoded methods) and the batch they announce.  A call with a
-// base or targets names it as `extra`: it is read between the observations and the shape inference, so that a missing one is reported first.
-struct Batch { Input o, c, extra; BatchShape s; };
-Batch read_batch(py::object &obs, py::object &cat, const std::string &fn, int in_dim, bool ids = false, py::object *extra = nullptr, const char *extra_name = nullptr) {
-    Batch b;
-    b.o = read_input(obs, "obs", true, fn, false);
-    b.c = read_input(cat, "cat_obs", true, fn, ids ? 2 : 1);
-    if (!b.o.ptr && !b.c.ptr) fail("Cannot call " + fn + " without observations!");
-    if (extra) {
-        b.extra = read_input(*extra, extra_name, false, fn, false);
-        if (!b.extra.ptr) fail("Cannot call " + fn + " without " + extra_name + "!");
-    }
-    b.s = infer_batch(b.o, b.c, in_dim);
-    return b;
-}
-
-// `a` (base or targets) is [n, D], or [n] when D == 1
-void check_rows_by_outputs(const Input &a, const char *name, int n, int D) {
-    const bool shape_ok = (a.shape.size() == 2 && a.shape[0] == static_cast<size_t>(n) && a.shape[1] == static_cast<size_t>(D)) ||
-                          (a.shape.size() == 1 && D == 1 && a.shape[0] == static_cast<size_t>(n));
-    if (shape_ok) return;
-    std::stringstream ss;
-    ss << "Expected " << name << " of shape (" << n << ", " << D << ")" << (D == 1 ? " or (" + std::to_string(n) + ",)" : std::string()) << ", but got (";
-    for (size_t i = 0; i < a.shape.size(); ++i) ss << (i ? ", " : "") << a.shape[i];
-    ss << ")";
-    fail(ss.str());
-}
-
-// The result of a call, `count` elements: on the MODEL's device for "cuda" delivery (one rank per GPU: not necessarily device 0; the capsule says
-// so), new[] on the host otherwise.  Freed when the call fails; release() hands it to a DLPack capsule or a NumPy array.
-template <typename T>
-class Result {
-   public:
-    Result(PyGBRL &self, size_t count) : dev_(self.device == 1) {
-        if (dev_) {
-            dev_id_ = gbrl_hip_device_ordinal(self.h);
-            if (dev_id_ < 0) fail(gbrl_hip_last_error());
-            p_ = static_cast<T *>(gbrl_hip_device_alloc_on(dev_id_, sizeof(T) * count));
-            if (!p_) fail(gbrl_hip_last_error());
-        } else {
-            p_ = new T[count];
-        }
-    }
-    Result(const Result &) = delete;
-    Result &operator=(const Result &) = delete;
-    ~Result() {   // still owned: the call has failed
-        if (!p_) return;
-        if (dev_) gbrl_hip_device_free(p_); else delete[] p_;
-    }
-    T *get() const { return p_; }
-    bool on_device() const { return dev_; }
-    py::object release(const std::vector<int64_t> &shape, bool dlpack_on_host = false) {
-        T *p = p_;
-        p_ = nullptr;
-        if (dev_ || dlpack_on_host) return make_dlpack(p, shape, dev_, dev_id_, /*int32=*/std::is_same<T, int32_t>::value);
-        py::capsule owner(p, [](void *q) { delete[] static_cast<T *>(q); });
-        return py::array_t<T>(std::vector<py::ssize_t>(shape.begin(), shape.end()), p, owner);
-    }
-
-   private:
-    T *p_ = nullptr;
-    bool dev_;
-    int dev_id_ = 0;
-};
 
 py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object start_obj, py::object stop_obj,
                         bool return_torch, const uint64_t *ids_token = nullptr /* non-null: `cat` holds int32 dictionary ids (predict_encoded) */) {
     const gbrl_hip_metadata md = self.meta();
-    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
-    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    const auto [start, stop] = read_tree_range(start_obj, stop_obj);
     // bounds as binding.cpp:800-811
-    if (start < 0 || (start >= md.n_trees && md.n_trees > 0)) {
-        std::stringstream ss;
-        ss << "start_tree_idx is out of bounds! Got " << start << ", but valid range is [0, " << md.n_trees - 1 << "]";
-        fail(ss.str());
-    }
-    if (stop < 0 || stop > md.n_trees) {
-        std::stringstream ss;
-        ss << "stop_tree_idx is out of bounds! Got " << stop << ", but valid range is [0, " << md.n_trees << "]";
-        fail(ss.str());
-    }
+    if (start < 0 || (start >= md.n_trees && md.n_trees > 0)) fail_cat("start_tree_idx is out of bounds! Got ", start, ", but valid range is [0, ", md.n_trees - 1, "]");
+    if (stop < 0 || stop > md.n_trees) fail_cat("stop_tree_idx is out of bounds! Got ", stop, ", but valid range is [0, ", md.n_trees, "]");
     const Batch b = read_batch(obs, cat, "predict", md.input_dim, ids_token != nullptr);
     const Input &o = b.o, &c = b.c;
     const int n = b.s.n, n_num = b.s.n_num, n_cat = b.s.n_cat;
@@ -326,17 +29,13 @@ py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::obje
     std::vector<int64_t> shape;
     if (D == 1) shape = {n}; else shape = {n, D};  // binding.cpp:281-286
     Result<float> out(self, static_cast<size_t>(n) * D);
-    int rc;
     {
         py::gil_scoped_release release;  // binding.cpp:934
         if (ids_token)
-            rc = gbrl_hip_predict_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device, *ids_token,
-                                          n, n_num, n_cat, start, stop, out.get(), out.on_device());
+            check(gbrl_hip_predict_encoded(self.h, o.f32(), o.on_device, c.i32(), c.on_device, *ids_token, n, n_num, n_cat, start, stop, out.get(), out.on_device()));
         else
-            rc = gbrl_hip_predict(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr),
-                                  c.on_device, n, n_num, n_cat, start, stop, out.get(), out.on_device());
+            check(gbrl_hip_predict(self.h, o.f32(), o.on_device, c.cells(), c.on_device, n, n_num, n_cat, start, stop, out.get(), out.on_device()));
     }
-    check(rc);
     return out.release(shape, return_torch);
 }
 
@@ -347,58 +46,28 @@ py::object predict_impl(PyGBRL &self, py::object &obs, py::object &cat, py::obje
 py::object predict_continue_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &base, py::object start_obj, py::object stop_obj,
                                  const uint64_t *ids_token = nullptr) {
     const gbrl_hip_metadata md = self.meta();
-    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
-    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    const auto [start, stop] = read_tree_range(start_obj, stop_obj);
     const Batch batch = read_batch(obs, cat, "predict_continue", md.input_dim, ids_token != nullptr, &base, "base");
     const Input &o = batch.o, &c = batch.c, &b = batch.extra;
     const int n = batch.s.n, n_num = batch.s.n_num, n_cat = batch.s.n_cat, D = md.output_dim;
     check_rows_by_outputs(b, "base", n, D);
-    const bool in_place = py::isinstance<py::tuple>(base);
-    float *out = in_place ? static_cast<float *>(const_cast<void *>(b.ptr)) : new float[static_cast<size_t>(n) * D];
-    const int out_dev = in_place && b.on_device;
-    int rc;
+    Result<float> out = py::isinstance<py::tuple>(base) ? Result<float>::adopt(b) : Result<float>(false, 0, static_cast<size_t>(n) * D);
     {
         py::gil_scoped_release release;
         if (ids_token)
-            rc = gbrl_hip_predict_continue_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device,
-                                                   *ids_token, n, n_num, n_cat, start, stop, static_cast<const float *>(b.ptr), b.on_device, out, out_dev);
+            check(gbrl_hip_predict_continue_encoded(self.h, o.f32(), o.on_device, c.i32(), c.on_device,
+                                                    *ids_token, n, n_num, n_cat, start, stop, b.f32(), b.on_device, out.get(), out.on_device()));
         else
-            rc = gbrl_hip_predict_continue(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, n_num,
-                                           n_cat, start, stop, static_cast<const float *>(b.ptr), b.on_device, out, out_dev);
+            check(gbrl_hip_predict_continue(self.h, o.f32(), o.on_device, c.cells(), c.on_device, n, n_num,
+                                            n_cat, start, stop, b.f32(), b.on_device, out.get(), out.on_device()));
     }
-    if (rc != GBRL_HIP_OK) {
-        if (!in_place) delete[] out;
-        fail(gbrl_hip_last_error());
-    }
-    if (in_place) return py::none();
-    py::capsule owner(out, [](void *p) { delete[] static_cast<float *>(p); });
-    std::vector<py::ssize_t> shp(b.shape.begin(), b.shape.end());
-    return py::array_t<float>(shp, out, owner);
+    return out.release(shape_of(b));
 }
 
 // Extension: predict_staged(obs, categorical_obs, stops=None) / staged_loss(obs, categorical_obs, targets, stops=None): every ensemble prefix in
 // one walk (include/gbrl_hip.h).  `stops`: a strictly ascending sequence of tree counts k, 0 <= k <= n_trees; k == 0 is the bias alone (0 never
 // means "all trees" here); None means 1, 2, ..., n_trees.  predict_staged returns float32 [len(stops), n, D] ([len(stops), n] when D == 1) --
 // NumPy for a "cpu" model, a DLPack capsule on the model's device for a "cuda" one, as predict does; staged_loss returns float64 [len(stops)].
-std::vector<int32_t> read_stops(py::object &stops_obj, int n_trees) {
-    std::vector<int32_t> stops;
-    if (stops_obj.is_none()) {
-        for (int k = 1; k <= n_trees; ++k) stops.push_back(k);
-    } else {
-        for (py::handle k : py::iter(stops_obj)) stops.push_back(k.cast<int32_t>());
-    }
-    // the engine checks the same (c_api callers); here too because a "cuda" model allocates its result on the device before the C call
-    if (stops.empty()) fail("stops is empty: nothing to evaluate");
-    for (size_t i = 0; i < stops.size(); ++i) {
-        if (stops[i] < 0 || stops[i] > n_trees) {
-            std::stringstream ss;
-            ss << "a stop is out of bounds! Got " << stops[i] << ", but valid range is [0, " << n_trees << "]";
-            fail(ss.str());
-        }
-        if (i > 0 && stops[i] <= stops[i - 1]) fail("stops must be strictly ascending");
-    }
-    return stops;
-}
 
 py::object predict_staged_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &stops_obj) {
     const gbrl_hip_metadata md = self.meta();
@@ -409,13 +78,10 @@ py::object predict_staged_impl(PyGBRL &self, py::object &obs, py::object &cat, p
     std::vector<int64_t> shape;
     if (D == 1) shape = {S, n}; else shape = {S, n, D};
     Result<float> out(self, static_cast<size_t>(S) * n * D);
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_predict_staged(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, b.s.n_num,
-                                     b.s.n_cat, stops.data(), S, out.get(), out.on_device());
+        check(gbrl_hip_predict_staged(self.h, o.f32(), o.on_device, c.cells(), c.on_device, n, b.s.n_num, b.s.n_cat, stops.data(), S, out.get(), out.on_device()));
     }
-    check(rc);
     return out.release(shape);
 }
 
@@ -429,13 +95,11 @@ py::object staged_loss_impl(PyGBRL &self, py::object &obs, py::object &cat, py::
     const std::vector<int32_t> stops = read_stops(stops_obj, md.n_trees);
     py::array_t<double> loss(static_cast<py::ssize_t>(stops.size()));
     double *lp = loss.mutable_data();
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_staged_loss(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device,
-                                  static_cast<const float *>(y.ptr), y.on_device, n, bs.n_num, bs.n_cat, stops.data(), static_cast<int>(stops.size()), lp);
+        check(gbrl_hip_staged_loss(self.h, o.f32(), o.on_device, c.cells(), c.on_device,
+                                    y.f32(), y.on_device, n, bs.n_num, bs.n_cat, stops.data(), static_cast<int>(stops.size()), lp));
     }
-    check(rc);
     return loss;
 }
 
@@ -444,21 +108,17 @@ py::object staged_loss_impl(PyGBRL &self, py::object &obs, py::object &cat, py::
 // staged_loss(obs, categorical_obs, targets, stops=[stop])[0] called right after, bit for bit.
 double refit_leaves_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, py::object start_obj, py::object stop_obj, double decay) {
     const gbrl_hip_metadata md = self.meta();
-    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
-    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    const auto [start, stop] = read_tree_range(start_obj, stop_obj);
     const Batch b = read_batch(obs, cat, "refit_leaves", md.input_dim, false, &targets, "targets");
     const Input &o = b.o, &c = b.c, &y = b.extra;
     const BatchShape &bs = b.s;
     const int n = bs.n, D = md.output_dim;
     check_rows_by_outputs(y, "targets", n, D);
     double loss = 0.0;
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_refit_leaves(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device,
-                                   static_cast<const float *>(y.ptr), y.on_device, n, bs.n_num, bs.n_cat, start, stop, decay, &loss);
+        check(gbrl_hip_refit_leaves(self.h, o.f32(), o.on_device, c.cells(), c.on_device, y.f32(), y.on_device, n, bs.n_num, bs.n_cat, start, stop, decay, &loss));
     }
-    check(rc);
     return loss;
 }
 
@@ -469,172 +129,84 @@ py::object leaves_impl(PyGBRL &self, py::object &obs, py::object &cat, py::objec
                        const uint64_t *ids_token = nullptr) {
     const gbrl_hip_metadata md = self.meta();
     const char *fn = counts ? "leaf_counts" : "predict_leaves";
-    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
-    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
+    const auto [start, stop] = read_tree_range(start_obj, stop_obj);
     const Batch b = read_batch(obs, cat, fn, md.input_dim, ids_token != nullptr);
     const Input &o = b.o, &c = b.c;
     const int n = b.s.n, n_num = b.s.n_num, n_cat = b.s.n_cat;
     // the engine checks the same (c_api callers); here too because the result is allocated before the C call
     if (md.n_trees == 0) fail(std::string(fn) + ": the model has no trees");
     const int resolved = stop == 0 ? md.n_trees : stop;
-    if (start < 0 || stop < 0 || resolved > md.n_trees || start >= resolved) {
-        std::stringstream ss;
-        ss << fn << ": invalid tree range [" << start << ", " << stop << ") for " << md.n_trees << " trees";
-        fail(ss.str());
-    }
+    if (start < 0 || stop < 0 || resolved > md.n_trees || start >= resolved) fail_cat(fn, ": invalid tree range [", start, ", ", stop, ") for ", md.n_trees, " trees");
     if (counts) {
         py::array_t<int64_t> res(static_cast<py::ssize_t>(md.n_leaves));
         int64_t *rp = res.mutable_data();
-        int rc;
         {
             py::gil_scoped_release release;
             if (ids_token)
-                rc = gbrl_hip_leaf_counts_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device,
-                                                  *ids_token, n, n_num, n_cat, start, stop, rp);
+                check(gbrl_hip_leaf_counts_encoded(self.h, o.f32(), o.on_device, c.i32(), c.on_device, *ids_token, n, n_num, n_cat, start, stop, rp));
             else
-                rc = gbrl_hip_leaf_counts(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, n_num,
-                                          n_cat, start, stop, rp);
+                check(gbrl_hip_leaf_counts(self.h, o.f32(), o.on_device, c.cells(), c.on_device, n, n_num, n_cat, start, stop, rp));
         }
-        check(rc);
         return res;
     }
     const int T = resolved - start;
     if (static_cast<int64_t>(n) * T >= (int64_t(1) << 31)) fail("predict_leaves: n_samples x trees >= 2^31 indices: slice the tree range");
     Result<int32_t> out(self, static_cast<size_t>(n) * T);
-    int rc;
     {
         py::gil_scoped_release release;
         if (ids_token)
-            rc = gbrl_hip_predict_leaves_encoded(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const int32_t *>(c.ptr), c.on_device,
-                                                 *ids_token, n, n_num, n_cat, start, stop, out.get(), out.on_device());
+            check(gbrl_hip_predict_leaves_encoded(self.h, o.f32(), o.on_device, c.i32(), c.on_device,
+                                                  *ids_token, n, n_num, n_cat, start, stop, out.get(), out.on_device()));
         else
-            rc = gbrl_hip_predict_leaves(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device, n, n_num,
-                                         n_cat, start, stop, out.get(), out.on_device());
+            check(gbrl_hip_predict_leaves(self.h, o.f32(), o.on_device, c.cells(), c.on_device, n, n_num, n_cat, start, stop, out.get(), out.on_device()));
     }
-    check(rc);
     return out.release({n, T});
 }
 
 // Extension: (ids, token) = encode_categorical(categorical_obs): int32 dictionary ids [n, n_cat] of a batch of cells -- a DLPack capsule on the
 // model's device for a "cuda" model, a NumPy array otherwise -- for predict_encoded(obs, ids, token, ...).
 py::tuple encode_categorical_impl(PyGBRL &self, py::object &cat) {
-    Input c = read_input(cat, "cat_obs", false, "encode_categorical", 1);
-    if (!c.ptr) fail("Cannot call encode_categorical without cat_obs!");
+    Input c = require_input(cat, "cat_obs", "encode_categorical", 1);
     const int n = static_cast<int>(c.shape[0]), n_cat = c.shape.size() > 1 ? static_cast<int>(c.shape[1]) : 1;
     Result<int32_t> ids(self, static_cast<size_t>(n) * n_cat);
     uint64_t token = 0;
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_encode_categorical(self.h, static_cast<const char *>(c.ptr), c.on_device, n, n_cat, ids.get(), ids.on_device(), &token);
+        check(gbrl_hip_encode_categorical(self.h, c.cells(), c.on_device, n, n_cat, ids.get(), ids.on_device(), &token));
     }
-    check(rc);
     return py::make_tuple(ids.release({n, n_cat}), token);
 }
 
+// What step and fit read alike (binding.cpp:462-515, 541-556): the gradients or targets (`first`, called `noun` where their output dim is refused)
+// give n and the output dim; obs and cat_obs are then held against n -- a 1-D one is one row when n == 1, else a column -- and the feature total
+// against input_dim.  fit words its row-count refusals as step does ("gradient samples").
+struct SampleShape { Input first, o, c; int n = 0, n_num = 0, n_cat = 0; };
+SampleShape read_sample_shape(const gbrl_hip_metadata &md, const std::string &fn, py::object &first, const char *first_name, const char *noun, py::object &obs,
+                              py::object &cat) {
+    SampleShape s;
+    s.first = read_input(first, first_name, false, fn, false);
+    s.n = read_output_rows(s.first, md.output_dim, noun).n;
+    auto rows_and_width = [&](const Input &a, int &width, const char *what) {
+        if (!a.ptr) return;
+        int rows;
+        if (a.shape.size() == 1) { width = (s.n == 1) ? static_cast<int>(a.shape[0]) : 1; rows = (s.n == 1) ? 1 : static_cast<int>(a.shape[0]); }
+        else { rows = static_cast<int>(a.shape[0]); width = static_cast<int>(a.shape[1]); }
+        if (rows != s.n) fail_cat("Number of ", what, " ", rows, " != number of gradient samples ", s.n);
+    };
+    s.o = read_input(obs, "obs", true, fn, false);
+    rows_and_width(s.o, s.n_num, "observations");
+    s.c = read_input(cat, "cat_obs", true, fn, true);
+    rows_and_width(s.c, s.n_cat, "categorical observations");
+    if (s.n_cat + s.n_num != md.input_dim) fail_cat("Total number of features ", s.n_cat + s.n_num, " != correct input dim ", md.input_dim);
+    return s;
+}
+
 void step_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &grads) {
-    const gbrl_hip_metadata md = self.meta();
-    Input g = read_input(grads, "grads", false, "step", false);
-    int n, gdim;
-    // binding.cpp:462-478
-    if (g.shape.size() == 1) {
-        if (md.output_dim > 1) { n = 1; gdim = static_cast<int>(g.shape[0]); } else { n = static_cast<int>(g.shape[0]); gdim = 1; }
-    } else { n = static_cast<int>(g.shape[0]); gdim = static_cast<int>(g.shape[1]); }
-    if (gdim != md.output_dim) {
-        std::stringstream ss;
-        ss << "Gradient output dim " << gdim << " != correct output dim " << md.output_dim;
-        fail(ss.str());
-    }
-    int n_num = 0, n_cat = 0;
-    Input o = read_input(obs, "obs", true, "step", false);
-    if (o.ptr) {  // binding.cpp:483-496
-        int no;
-        if (o.shape.size() == 1) { n_num = (n == 1) ? static_cast<int>(o.shape[0]) : 1; no = (n == 1) ? 1 : static_cast<int>(o.shape[0]); }
-        else { no = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]); }
-        if (no != n) {
-            std::stringstream ss;
-            ss << "Number of observations " << no << " != number of gradient samples " << n;
-            fail(ss.str());
-        }
-    }
-    Input c = read_input(cat, "cat_obs", true, "step", true);
-    if (c.ptr) {  // binding.cpp:502-515
-        int nc;
-        if (c.shape.size() == 1) { n_cat = (n == 1) ? static_cast<int>(c.shape[0]) : 1; nc = (n == 1) ? 1 : static_cast<int>(c.shape[0]); }
-        else { nc = static_cast<int>(c.shape[0]); n_cat = static_cast<int>(c.shape[1]); }
-        if (nc != n) {
-            std::stringstream ss;
-            ss << "Number of categorical observations " << nc << " != number of gradient samples " << n;
-            fail(ss.str());
-        }
-    }
-    if (n_cat + n_num != md.input_dim) {
-        std::stringstream ss;
-        ss << "Total number of features " << n_cat + n_num << " != correct input dim " << md.input_dim;
-        fail(ss.str());
-    }
-    int rc;
+    const SampleShape s = read_sample_shape(self.meta(), "step", grads, "grads", "Gradient", obs, cat);
     {
         py::gil_scoped_release release;  // binding.cpp:525
-        rc = gbrl_hip_step(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device,
-                           static_cast<const float *>(g.ptr), g.on_device, n, n_num, n_cat);
+        check(gbrl_hip_step(self.h, s.o.f32(), s.o.on_device, s.c.cells(), s.c.on_device, s.first.f32(), s.first.on_device, s.n, s.n_num, s.n_cat));
     }
-    check(rc);
-}
-
-// Extension: a batch binned once and stepped on many times (gbrl_hip_dataset, include/gbrl_hip.h).
-class PyDataset {
-   public:
-    gbrl_hip_dataset *h = nullptr;
-    explicit PyDataset(gbrl_hip_dataset *d) : h(d) {}
-    PyDataset(const PyDataset &) = delete;
-    PyDataset &operator=(const PyDataset &) = delete;
-    ~PyDataset() { gbrl_hip_dataset_destroy(h); }
-    gbrl_hip_dataset_desc info() const {
-        gbrl_hip_dataset_desc d{};
-        check(gbrl_hip_dataset_info(h, &d));
-        return d;
-    }
-};
-
-// rows=None | int32 NumPy vector | (data_ptr, (m,), "torch.int32", device)
-Input read_rows(py::object &rows, const std::string &fn) {
-    Input r = read_input(rows, "rows", true, fn, 2);
-    if (!rows.is_none() && !r.ptr && !(r.shape.size() == 1 && r.shape[0] == 0)) fail("Cannot call " + fn + " with a null rows pointer!");
-    if (!rows.is_none() && r.shape.size() != 1) fail("rows must be a one-dimensional int32 vector");
-    return r;
-}
-
-// A rows= argument as the C ABI takes it: the pointer (None: null, every row), where it lives, and m -- the vector's length, else the data set's
-// rows, else those of the call's first array.
-struct RowsArg {
-    const int32_t *ptr;
-    int on_device, m;
-};
-RowsArg read_rows_arg(py::object &rows, const std::string &fn, py::object &ds_obj, const Input &first) {
-    static const int32_t kNoRows = 0;   // an empty rows vector is "m == 0", not "every row"
-    const Input r = read_rows(rows, fn);
-    int m = first.shape.empty() ? 0 : static_cast<int>(first.shape[0]);
-    if (!rows.is_none()) m = static_cast<int>(r.shape[0]);
-    else if (!ds_obj.is_none()) m = ds_obj.cast<const PyDataset &>().info().n_rows;
-    return {rows.is_none() ? nullptr : (r.ptr ? static_cast<const int32_t *>(r.ptr) : &kNoRows), r.ptr ? r.on_device : 0, m};
-}
-
-// cols=: a one-dimensional vector of column indices in host memory (a NumPy integer array or a sequence of ints); the C ABI checks its contents
-std::vector<int32_t> read_cols(py::object &cols, const std::string &fn) {
-    py::array any = py::array::ensure(cols);
-    if (!any) { PyErr_Clear(); fail(fn + ": cols must be a vector of integers"); }
-    if (any.ndim() != 1) fail(fn + ": cols must be one-dimensional");
-    if (any.size() == 0) return {};   // (an empty list has no integer dtype; the caller refuses "no column")
-    if (any.dtype().kind() != 'i' && any.dtype().kind() != 'u') fail(fn + ": cols must be a vector of integers");
-    auto a = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(any);
-    if (!a) { PyErr_Clear(); fail(fn + ": cols must be a vector of integers"); }
-    std::vector<int32_t> out(static_cast<size_t>(a.shape(0)));
-    for (size_t i = 0; i < out.size(); ++i) {
-        const int64_t v = a.at(static_cast<py::ssize_t>(i));
-        out[i] = v < INT32_MIN ? INT32_MIN : v > INT32_MAX ? INT32_MAX : static_cast<int32_t>(v);   // (out of any range either way)
-    }
-    return out;
 }
 
 std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs, py::object reference = py::none()) {
@@ -644,29 +216,25 @@ std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs, p
     else if (py::isinstance<py::tuple>(obs) && py::len(obs) == 4) { const std::string dt = py::str(obs.cast<py::tuple>()[2]); cells = dt == "S128" || dt == "|S128"; }
     if (cells) fail("prepare_dataset: categorical columns are not supported (their split candidates depend on the step's gradients)");
     const gbrl_hip_metadata md = self.meta();
-    Input o = read_input(obs, "obs", false, "prepare_dataset", false);
-    if (!o.ptr) fail("Cannot call prepare_dataset without obs!");
+    Input o = require_input(obs, "obs", "prepare_dataset");
     int n, n_num;
-    if (o.shape.size() == 1) {   // as predict reads a 1-D input: one row of input_dim features, or a column
-        if (static_cast<int>(o.shape[0]) == md.input_dim) { n = 1; n_num = md.input_dim; } else { n = static_cast<int>(o.shape[0]); n_num = 1; }
-    } else if (o.shape.size() == 2) { n = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]);
-    } else fail("obs must have one or two dimensions");
+    if (o.shape.size() == 1) one_dim_obs(o.shape[0], md.input_dim, n, n_num);   // as predict reads a 1-D input
+    else if (o.shape.size() == 2) { n = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]); }
+    else fail("obs must have one or two dimensions");
     gbrl_hip_dataset *d = nullptr;
     if (!reference.is_none()) {   // bound to the reference's thresholds: the width is the reference's
         const PyDataset &ref = reference.cast<const PyDataset &>();
         gbrl_hip_dataset_desc rd{};
         if (gbrl_hip_dataset_info(ref.h, &rd) == GBRL_HIP_OK && n_num != rd.n_features) {
-            std::stringstream ss;
-            ss << "prepare_dataset: obs has " << n_num << " features, the reference " << rd.n_features;
-            fail(ss.str());
+            fail_cat("prepare_dataset: obs has ", n_num, " features, the reference ", rd.n_features);
         }
         {
             py::gil_scoped_release release;
-            d = gbrl_hip_dataset_create_like(self.h, ref.h, static_cast<const float *>(o.ptr), o.on_device, n);
+            d = gbrl_hip_dataset_create_like(self.h, ref.h, o.f32(), o.on_device, n);
         }
     } else {
         py::gil_scoped_release release;
-        d = gbrl_hip_dataset_create(self.h, static_cast<const float *>(o.ptr), o.on_device, n, n_num);
+        d = gbrl_hip_dataset_create(self.h, o.f32(), o.on_device, n, n_num);
     }
     if (!d) fail(gbrl_hip_last_error());
     return std::unique_ptr<PyDataset>(new PyDataset(d));
@@ -674,34 +242,20 @@ std::unique_ptr<PyDataset> prepare_dataset_impl(PyGBRL &self, py::object &obs, p
 
 void step_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &grads, py::object &rows, py::object cols = py::none()) {
     const gbrl_hip_metadata md = self.meta();
-    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
     Input g = read_input(grads, "grads", false, "step_prepared", false);
-    int n, gdim;   // as step reads its gradients
-    if (g.shape.size() == 1) {
-        if (md.output_dim > 1) { n = 1; gdim = static_cast<int>(g.shape[0]); } else { n = static_cast<int>(g.shape[0]); gdim = 1; }
-    } else { n = static_cast<int>(g.shape[0]); gdim = static_cast<int>(g.shape[1]); }
-    if (gdim != md.output_dim) {
-        std::stringstream ss;
-        ss << "Gradient output dim " << gdim << " != correct output dim " << md.output_dim;
-        fail(ss.str());
-    }
+    const int n = read_output_rows(g, md.output_dim, "Gradient").n;   // as step reads its gradients
     const RowsArg r = read_rows_arg(rows, "step_prepared", ds_obj, g);
-    if (!rows.is_none() && r.m != n) {
-        std::stringstream ss;
-        ss << "Number of rows " << r.m << " != number of gradient samples " << n;
-        fail(ss.str());
-    }
+    if (!rows.is_none() && r.m != n) fail_cat("Number of rows ", r.m, " != number of gradient samples ", n);
     std::vector<int32_t> cv;
     if (!cols.is_none()) cv = read_cols(cols, "step_prepared");
     static const int32_t kNoCols = 0;   // an empty cols vector is "no column", not "every column"
-    int rc;
     {
         py::gil_scoped_release release;
-        if (cols.is_none()) rc = gbrl_hip_step_prepared(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, r.ptr, r.on_device, n);
-        else rc = gbrl_hip_step_prepared_cols(self.h, ds, static_cast<const float *>(g.ptr), g.on_device, r.ptr, r.on_device, n,
-                                              cv.empty() ? &kNoCols : cv.data(), static_cast<int>(cv.size()));
+        if (cols.is_none()) check(gbrl_hip_step_prepared(self.h, ds, g.f32(), g.on_device, r.ptr, r.on_device, n));
+        else check(gbrl_hip_step_prepared_cols(self.h, ds, g.f32(), g.on_device, r.ptr, r.on_device, n,
+                                               cv.empty() ? &kNoCols : cv.data(), static_cast<int>(cv.size())));
     }
-    check(rc);
 }
 
 py::array dataset_codes_impl(PyDataset &self, py::object &rows, py::object &cols) {
@@ -717,13 +271,11 @@ py::array dataset_codes_impl(PyDataset &self, py::object &rows, py::object &cols
     const py::ssize_t groups = cols.is_none() ? d.code_groups : static_cast<py::ssize_t>((cv.size() + 15) / 16);
     py::array_t<uint16_t> out({groups, static_cast<py::ssize_t>(m), static_cast<py::ssize_t>(16)});
     uint16_t *op = out.mutable_data();
-    int rc;
     {
         py::gil_scoped_release release;
-        if (cols.is_none()) rc = gbrl_hip_dataset_codes(self.h, static_cast<const int32_t *>(r.ptr), r.on_device, m, op);
-        else rc = gbrl_hip_dataset_codes_cols(self.h, static_cast<const int32_t *>(r.ptr), r.on_device, m, cv.data(), static_cast<int>(cv.size()), op);
+        if (cols.is_none()) check(gbrl_hip_dataset_codes(self.h, r.i32(), r.on_device, m, op));
+        else check(gbrl_hip_dataset_codes_cols(self.h, r.i32(), r.on_device, m, cv.data(), static_cast<int>(cv.size()), op));
     }
-    check(rc);
     return std::move(out);
 }
 
@@ -743,24 +295,15 @@ py::array_t<int32_t> sample_cols_host_impl(int F, double colsample, uint64_t see
 py::object dataset_sample_rows_impl(PyDataset &self, double subsample, uint64_t seed, int draw, int start, py::object stop_obj) {
     const gbrl_hip_dataset_desc d = self.info();
     const int stop = stop_obj.is_none() ? d.n_rows : stop_obj.cast<int>();
-    if (start < 0 || stop > d.n_rows || stop <= start) {
-        std::stringstream ss;
-        ss << "sample_rows: rows [" << start << ", " << stop << ") are not a non-empty range inside [0, " << d.n_rows << ")";
-        fail(ss.str());
-    }
+    if (start < 0 || stop > d.n_rows || stop <= start) fail_cat("sample_rows: rows [", start, ", ", stop, ") are not a non-empty range inside [0, ", d.n_rows, ")");
     const int n = stop - start;
-    int32_t *p = static_cast<int32_t *>(gbrl_hip_device_alloc_on(d.device, sizeof(int32_t) * static_cast<size_t>(n)));
-    if (!p) fail(gbrl_hip_last_error());
-    int rc, m = 0;
+    Result<int32_t> out(true, d.device, static_cast<size_t>(n));
+    int m = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_dataset_sample_rows(self.h, start, n, subsample, seed, draw, p, 1, &m);
+        check(gbrl_hip_dataset_sample_rows(self.h, start, n, subsample, seed, draw, out.get(), 1, &m));
     }
-    if (rc != GBRL_HIP_OK) {
-        gbrl_hip_device_free(p);
-        fail(gbrl_hip_last_error());
-    }
-    return make_dlpack(p, {static_cast<int64_t>(m)}, true, d.device, /*int32=*/true);
+    return out.release({static_cast<int64_t>(m)});
 }
 
 py::array_t<int32_t> sample_rows_host_impl(int n, double subsample, uint64_t seed, int draw, int row0) {
@@ -777,8 +320,7 @@ py::array_t<int32_t> sample_rows_host_impl(int n, double subsample, uint64_t see
 struct GossGrads { Input g; int n = 0, D = 1; bool flat = false; };
 GossGrads read_goss_grads(py::object &grads, const std::string &fn) {
     GossGrads r;
-    r.g = read_input(grads, "grads", false, fn, false);
-    if (!r.g.ptr) fail("Cannot call " + fn + " without grads!");
+    r.g = require_input(grads, "grads", fn);
     if (r.g.shape.empty() || r.g.shape.size() > 2) fail("grads must be a float32 array of shape (n, D) or (n,)");
     r.flat = r.g.shape.size() == 1;
     r.n = static_cast<int>(r.g.shape[0]);
@@ -789,11 +331,11 @@ GossGrads read_goss_grads(py::object &grads, const std::string &fn) {
 // gbrl_cpp.goss_rows_host(grads, top_rate, other_rate, seed=0, draw=0, row0=0) -> (rows int32 [m], factor float32 [m])
 py::tuple goss_rows_host_impl(py::object &grads, double top_rate, double other_rate, uint64_t seed, int draw, int row0) {
     GossGrads in = read_goss_grads(grads, "goss_rows_host");
-    if (in.g.on_device) fail("goss_rows_host takes a NumPy array");
+    require_host(in.g, "goss_rows_host takes a NumPy array");
     std::vector<int32_t> rows(static_cast<size_t>(std::max(in.n, 1)));
     std::vector<float> factor(rows.size());
     int m = 0;
-    check(gbrl_hip_goss_rows_host(static_cast<const float *>(in.g.ptr), in.D, row0, in.n, top_rate, other_rate, seed, draw, rows.data(), factor.data(), nullptr, &m));
+    check(gbrl_hip_goss_rows_host(in.g.f32(), in.D, row0, in.n, top_rate, other_rate, seed, draw, rows.data(), factor.data(), nullptr, &m));
     py::array_t<int32_t> ro(static_cast<py::ssize_t>(m));
     py::array_t<float> fo(static_cast<py::ssize_t>(m));
     std::copy(rows.begin(), rows.begin() + m, ro.mutable_data());
@@ -807,56 +349,37 @@ py::tuple goss_rows_host_impl(py::object &grads, double top_rate, double other_r
 py::dict dataset_sample_goss_impl(PyDataset &self, py::object &grads, double top_rate, double other_rate, uint64_t seed, int draw, int start, py::object stop_obj) {
     const gbrl_hip_dataset_desc d = self.info();
     const int stop = stop_obj.is_none() ? d.n_rows : stop_obj.cast<int>();
-    if (start < 0 || stop > d.n_rows || stop <= start) {
-        std::stringstream ss;
-        ss << "sample_goss: rows [" << start << ", " << stop << ") are not a non-empty range inside [0, " << d.n_rows << ")";
-        fail(ss.str());
-    }
+    if (start < 0 || stop > d.n_rows || stop <= start) fail_cat("sample_goss: rows [", start, ", ", stop, ") are not a non-empty range inside [0, ", d.n_rows, ")");
     const int n = stop - start;
     GossGrads in = read_goss_grads(grads, "sample_goss");
-    if (in.n != n) {
-        std::stringstream ss;
-        ss << "sample_goss: grads has " << in.n << " rows, the range [" << start << ", " << stop << ") has " << n;
-        fail(ss.str());
-    }
+    if (in.n != n) fail_cat("sample_goss: grads has ", in.n, " rows, the range [", start, ", ", stop, ") has ", n);
     const size_t n_el = static_cast<size_t>(n) * static_cast<size_t>(std::max(in.D, 1));
     const bool dev = in.g.on_device;
-    int32_t *rp = nullptr;
-    float *fp = nullptr, *gp = nullptr;
+    // device results hold the whole range and are handed out as they are; host results are written to vectors and their first m entries copied out
+    std::optional<Result<int32_t>> drows;
+    std::optional<Result<float>> dfactor, dgrads;
     std::vector<int32_t> hrows;
     std::vector<float> hfactor, hgrads;
     if (dev) {
-        rp = static_cast<int32_t *>(gbrl_hip_device_alloc_on(d.device, sizeof(int32_t) * static_cast<size_t>(n)));
-        fp = static_cast<float *>(gbrl_hip_device_alloc_on(d.device, sizeof(float) * static_cast<size_t>(n)));
-        gp = static_cast<float *>(gbrl_hip_device_alloc_on(d.device, sizeof(float) * n_el));
-        if (!rp || !fp || !gp) {
-            if (rp) gbrl_hip_device_free(rp);
-            if (fp) gbrl_hip_device_free(fp);
-            if (gp) gbrl_hip_device_free(gp);
-            fail(gbrl_hip_last_error());
-        }
+        drows.emplace(true, d.device, static_cast<size_t>(n)); dfactor.emplace(true, d.device, static_cast<size_t>(n)); dgrads.emplace(true, d.device, n_el);
     } else {
         hrows.resize(static_cast<size_t>(n)); hfactor.resize(static_cast<size_t>(n)); hgrads.resize(n_el);
-        rp = hrows.data(); fp = hfactor.data(); gp = hgrads.data();
     }
-    int rc, m = 0, n_top = 0;
+    int32_t *rp = dev ? drows->get() : hrows.data();
+    float *fp = dev ? dfactor->get() : hfactor.data(), *gp = dev ? dgrads->get() : hgrads.data();
+    int m = 0, n_top = 0;
     uint32_t tau = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_dataset_sample_goss(self.h, static_cast<const float *>(in.g.ptr), in.D, start, n, top_rate, other_rate, seed, draw, rp, fp, gp, dev ? 1 : 0, &m,
-                                          &n_top, &tau);
-    }
-    if (rc != GBRL_HIP_OK) {
-        if (dev) { gbrl_hip_device_free(rp); gbrl_hip_device_free(fp); gbrl_hip_device_free(gp); }
-        fail(gbrl_hip_last_error());
+        check(gbrl_hip_dataset_sample_goss(self.h, in.g.f32(), in.D, start, n, top_rate, other_rate, seed, draw, rp, fp, gp, dev ? 1 : 0, &m, &n_top, &tau));
     }
     py::dict out;
     std::vector<int64_t> gshape{static_cast<int64_t>(m)};
     if (!in.flat) gshape.push_back(in.D);
     if (dev) {
-        out["rows"] = make_dlpack(rp, {static_cast<int64_t>(m)}, true, d.device, /*int32=*/true);
-        out["factor"] = make_dlpack(fp, {static_cast<int64_t>(m)}, true, d.device);
-        out["grads"] = make_dlpack(gp, gshape, true, d.device);
+        out["rows"] = drows->release({static_cast<int64_t>(m)});
+        out["factor"] = dfactor->release({static_cast<int64_t>(m)});
+        out["grads"] = dgrads->release(gshape);
     } else {
         py::array_t<int32_t> ro(static_cast<py::ssize_t>(m));
         py::array_t<float> fo(static_cast<py::ssize_t>(m));
@@ -875,101 +398,34 @@ py::dict dataset_sample_goss_impl(PyDataset &self, py::object &grads, double top
 py::array_t<int32_t> condition_bins_impl(PyGBRL &self, py::object &thresholds) {
     const gbrl_hip_metadata md = self.meta();
     Input t = read_input(thresholds, "thresholds", false, "condition_bins", false);
-    if (t.on_device) fail("condition_bins takes a NumPy array");
+    require_host(t, "condition_bins takes a NumPy array");
     if (t.shape.size() != 2) fail("thresholds must be a float32 array of shape (n_features, n_bins)");
     const py::ssize_t S = md.grow_policy == GBRL_HIP_GROW_OBLIVIOUS ? md.n_trees : md.n_leaves;
     py::array_t<int32_t> out({S, static_cast<py::ssize_t>(md.max_depth)});
-    check(gbrl_hip_condition_bins(self.h, static_cast<const float *>(t.ptr), static_cast<int>(t.shape[0]), static_cast<int>(t.shape[1]), out.mutable_data()));
+    check(gbrl_hip_condition_bins(self.h, t.f32(), static_cast<int>(t.shape[0]), static_cast<int>(t.shape[1]), out.mutable_data()));
     return out;
 }
 
 // predict_continue_prepared(ds, base, start, stop, rows=None): predict_continue's conventions for base and the range, step_prepared's for rows
 py::object predict_continue_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &base, py::object start_obj, py::object stop_obj, py::object &rows) {
     const gbrl_hip_metadata md = self.meta();
-    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
-    const int start = start_obj.is_none() ? 0 : start_obj.cast<int>();
-    const int stop = stop_obj.is_none() ? 0 : stop_obj.cast<int>();
-    Input b = read_input(base, "base", false, "predict_continue_prepared", false);
-    if (!b.ptr) fail("Cannot call predict_continue_prepared without base!");
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
+    const auto [start, stop] = read_tree_range(start_obj, stop_obj);
+    Input b = require_input(base, "base", "predict_continue_prepared");
     const RowsArg r = read_rows_arg(rows, "predict_continue_prepared", ds_obj, b);
     const int D = md.output_dim, m = r.m;
     check_rows_by_outputs(b, "base", m, D);
-    const bool in_place = py::isinstance<py::tuple>(base);
-    float *out = in_place ? static_cast<float *>(const_cast<void *>(b.ptr)) : new float[std::max<size_t>(static_cast<size_t>(m) * D, 1)];
-    int rc;
+    Result<float> out = py::isinstance<py::tuple>(base) ? Result<float>::adopt(b) : Result<float>(false, 0, std::max<size_t>(static_cast<size_t>(m) * D, 1));
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_predict_continue_prepared(self.h, ds, r.ptr, r.on_device, m, static_cast<const float *>(b.ptr), b.on_device, start, stop, out);
+        check(gbrl_hip_predict_continue_prepared(self.h, ds, r.ptr, r.on_device, m, b.f32(), b.on_device, start, stop, out.get()));
     }
-    if (rc != GBRL_HIP_OK) {
-        if (!in_place) delete[] out;
-        fail(gbrl_hip_last_error());
-    }
-    if (in_place) return py::none();
-    py::capsule owner(out, [](void *p) { delete[] static_cast<float *>(p); });
-    std::vector<py::ssize_t> shp(b.shape.begin(), b.shape.end());
-    return py::array_t<float>(shp, out, owner);
-}
-
-// the targets of an objective: float32 [n, D] ([n] when D == 1) for rmse and logistic, int32 [n] labels for softmax
-Input read_objective_targets(py::object &targets, const char *name, bool none_allowed, const std::string &fn, int objective, int n, int D, bool check_shape) {
-    const bool ranking = objective == GBRL_HIP_OBJ_PAIRWISE || objective == GBRL_HIP_OBJ_LAMBDARANK;   // int32 relevance labels [n]
-    if (objective != GBRL_HIP_OBJ_SOFTMAX && !ranking) {
-        Input t = read_input(targets, name, none_allowed, fn, false);
-        if (check_shape && t.ptr) check_rows_by_outputs(t, name, n, D);
-        return t;
-    }
-    Input t = read_input(targets, name, none_allowed, fn, 2);
-    if (check_shape && t.ptr && !(t.shape.size() == 1 && t.shape[0] == static_cast<size_t>(n))) {
-        std::stringstream ss;
-        ss << "Expected " << name << " of the " << (ranking ? "ranking objective as int32 relevance labels" : "softmax objective as int32 class labels") << " of shape (" << n << ",)";
-        fail(ss.str());
-    }
-    return t;
-}
-
-// row weights (include/gbrl_hip.h, "Row weights"): None, or float32 [n] as a NumPy array or a device tuple
-Input read_weights(py::object &weights, const char *name, const std::string &fn, int n, bool check_shape) {
-    if (weights.is_none()) return Input{};
-    Input w = read_input(weights, name, false, fn, false);
-    if (!w.ptr) fail("Cannot call " + fn + " with a null " + name + " pointer!");
-    if (check_shape && !(w.shape.size() == 1 && w.shape[0] == static_cast<size_t>(n))) {
-        std::stringstream ss;
-        ss << "Expected " << name << " as a float32 vector of shape (" << n << ",), one weight per row";
-        fail(ss.str());
-    }
-    return w;
-}
-
-// the levels of the quantile objective (include/gbrl_hip.h, "Quantile regression"): None (empty), a scalar broadcast to the D outputs, or a sequence of D;
-// the levels themselves are checked behind the C ABI, which names the output
-std::vector<float> read_alpha(const py::object &alpha, int D, const std::string &fn) {
-    std::vector<float> a;
-    if (alpha.is_none()) return a;
-    if (py::isinstance<py::float_>(alpha) || py::isinstance<py::int_>(alpha)) {
-        a.assign(static_cast<size_t>(std::max(D, 1)), alpha.cast<float>());
-        return a;
-    }
-    py::array_t<float, py::array::c_style | py::array::forcecast> arr = py::array_t<float, py::array::c_style | py::array::forcecast>::ensure(alpha);
-    if (!arr) fail(fn + ": alpha must be a number or a sequence of numbers");
-    if (arr.ndim() == 0) {
-        a.assign(static_cast<size_t>(std::max(D, 1)), *arr.data());
-        return a;
-    }
-    if (arr.ndim() != 1 || arr.shape(0) != D) {
-        std::stringstream ss;
-        ss << fn << ": alpha must be a scalar or hold one level per output (" << D << ")";
-        fail(ss.str());
-    }
-    a.assign(arr.data(), arr.data() + D);
-    return a;
+    return out.release(shape_of(b));
 }
 
 // fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,
 // objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
 // with either.  A missing valid_targets is left to the C ABI's message.
-std::vector<int32_t> read_group(py::object &group, const std::string &fn, const char *name = "group");
-int read_ndcg_at(py::object &ndcg_at, const std::string &fn);
 py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, int iterations, py::object valid_obj, py::object &valid_targets,
                              int early_stopping_rounds, double min_delta, double subsample, double colsample, uint64_t seed, const std::string &objective_name,
                              py::object metric_obj, const std::string &leaf_update_name, double leaf_l2, py::object &weights, py::object &valid_weights,
@@ -989,15 +445,15 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
         goss_other = g[1].cast<double>();
         if (goss_other == 0.0) fail("fit_prepared: goss needs other_rate in (0, 1], got 0");
     }
-    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
     const int objective = parse_objective(objective_name), leaf_update = parse_leaf_update(leaf_update_name);
     const int metric = metric_obj.is_none() ? GBRL_HIP_METRIC_NONE : parse_metric(metric_obj.cast<std::string>());
     if (valid_obj.is_none() && (!valid_targets.is_none() || early_stopping_rounds != 0 || min_delta != 0.0))
         fail("fit_prepared: valid_targets, early_stopping_rounds and min_delta need a validation set (valid=)");
     if (valid_obj.is_none() && !valid_weights.is_none()) fail("fit_prepared: valid_weights need a validation set (valid=)");
     if (valid_obj.is_none() && !valid_group_obj.is_none()) fail("fit_prepared: valid_group needs a validation set (valid=)");
-    const gbrl_hip_dataset *dsv = valid_obj.is_none() ? nullptr : valid_obj.cast<const PyDataset &>().h;
-    const int n = ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, nv = dsv ? valid_obj.cast<const PyDataset &>().info().n_rows : 0;
+    const gbrl_hip_dataset *dsv = dataset_handle(valid_obj);
+    const int n = dataset_info(ds_obj).n_rows, nv = dataset_info(valid_obj).n_rows;
     Input w = read_weights(weights, "weights", "fit_prepared", n, ds != nullptr), wv;
     if (dsv) wv = read_weights(valid_weights, "valid_weights", "fit_prepared", nv, true);
     Input t = read_objective_targets(targets, "targets", false, "fit", objective, n, md.output_dim, ds != nullptr);
@@ -1005,17 +461,15 @@ py::object fit_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &target
     if (dsv) tv = read_objective_targets(valid_targets, "valid_targets", true, "fit", objective, nv, md.output_dim, true);
     std::vector<double> curve(static_cast<size_t>(std::max(iterations, 0)) + 1, 0.0), mcurve(metric != GBRL_HIP_METRIC_NONE ? curve.size() : 0, 0.0);
     float loss = 0.0f, weight_max = 0.0f;
-    int rc, done = 0, best = 0;
+    int done = 0, best = 0;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit_prepared_rank(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
-                                        colsample, seed, objective, metric, leaf_update, leaf_l2, static_cast<const float *>(w.ptr), w.on_device,
-                                        static_cast<const float *>(wv.ptr), wv.on_device, goss_top, goss_other, alpha.empty() ? nullptr : alpha.data(),
-                                        group.empty() ? nullptr : group.data(), static_cast<int>(group.size()), ndcg_at,
-                                        valid_group.empty() ? nullptr : valid_group.data(), static_cast<int>(valid_group.size()), &loss,
-                                        dsv ? curve.data() : nullptr, dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max);
+        check(gbrl_hip_fit_prepared_rank(self.h, ds, t.ptr, t.on_device, iterations, dsv, tv.ptr, tv.on_device, early_stopping_rounds, min_delta, subsample,
+                                         colsample, seed, objective, metric, leaf_update, leaf_l2, w.f32(), w.on_device, wv.f32(), wv.on_device, goss_top, goss_other,
+                                         alpha.empty() ? nullptr : alpha.data(), group.empty() ? nullptr : group.data(), static_cast<int>(group.size()), ndcg_at,
+                                         valid_group.empty() ? nullptr : valid_group.data(), static_cast<int>(valid_group.size()), &loss,
+                                         dsv ? curve.data() : nullptr, dsv && metric != GBRL_HIP_METRIC_NONE ? mcurve.data() : nullptr, &done, &best, &weight_max));
     }
-    check(rc);
     if (!dsv) return py::float_(loss);
     py::array_t<double> vl(static_cast<py::ssize_t>(done) + 1);
     std::copy(curve.begin(), curve.begin() + done + 1, vl.mutable_data());
@@ -1074,7 +528,7 @@ py::dict leaf_quantile_result(py::ssize_t leaves, py::ssize_t D, Call &&call) {
 py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &pred, py::object &targets, const std::string &objective_name, double leaf_l2,
                                      py::object &rows, int tree, py::object &weights, py::object weight_max_obj, py::object group_obj, py::object ndcg_at_obj) {
     const gbrl_hip_metadata md = self.meta();
-    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
     const int objective = parse_objective(objective_name), D = md.output_dim;
     const bool ranking = objective == GBRL_HIP_OBJ_PAIRWISE || objective == GBRL_HIP_OBJ_LAMBDARANK;
     if (!ranking && (!group_obj.is_none() || !ndcg_at_obj.is_none())) fail("newton_leaves_prepared: group and ndcg_at belong to the ranking objectives 'pairwise' and 'lambdarank'");
@@ -1084,20 +538,18 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
         if (!weights.is_none() || !weight_max_obj.is_none()) fail("newton_leaves_prepared: weights with a ranking objective are not supported");
         const std::vector<int32_t> grp = read_group(group_obj, fn);
         const int ndcg_at = read_ndcg_at(ndcg_at_obj, fn);
-        Input p = read_input(pred, "pred", false, fn, false);
-        if (!p.ptr) fail("Cannot call newton_leaves_prepared without pred!");
-        const int n = ds ? ds_obj.cast<const PyDataset &>().info().n_rows : (p.shape.empty() ? 0 : static_cast<int>(p.shape[0]));
+        Input p = require_input(pred, "pred", fn);
+        const int n = ds ? dataset_info(ds_obj).n_rows : (p.shape.empty() ? 0 : static_cast<int>(p.shape[0]));
         check_rows_by_outputs(p, "pred", n, 1);
         Input l = read_objective_targets(targets, "targets", false, fn, objective, n, 1, true);
         if (!l.ptr) fail("Cannot call newton_leaves_prepared without targets!");
         return newton_leaves_result(tree_leaf_count(self, md, tree), 1, [&](int64_t *sp, int *bits, float *vp) {
             py::gil_scoped_release release;
-            return gbrl_hip_newton_leaves_prepared_rank(self.h, ds, static_cast<const float *>(p.ptr), p.on_device, static_cast<const int32_t *>(l.ptr), l.on_device,
+            return gbrl_hip_newton_leaves_prepared_rank(self.h, ds, p.f32(), p.on_device, l.i32(), l.on_device,
                                                         grp.data(), static_cast<int>(grp.size()), objective, ndcg_at, tree, leaf_l2, sp, bits, vp);
         });
     }
-    Input p = read_input(pred, "pred", false, "newton_leaves_prepared", false);
-    if (!p.ptr) fail("Cannot call newton_leaves_prepared without pred!");
+    Input p = require_input(pred, "pred", "newton_leaves_prepared");
     const RowsArg r = read_rows_arg(rows, "newton_leaves_prepared", ds_obj, p);
     const int m = r.m;
     check_rows_by_outputs(p, "pred", m, D);
@@ -1109,8 +561,8 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
     if (!weight_max_obj.is_none() && !(weight_max >= 0.0f)) fail("newton_leaves_prepared: weight_max must be in [0, 65536] (and not NaN)");
     return newton_leaves_result(tree_leaf_count(self, md, tree), D, [&](int64_t *sp, int *bits, float *vp) {
         py::gil_scoped_release release;
-        return gbrl_hip_newton_leaves_prepared_weighted(self.h, ds, r.ptr, r.on_device, m, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device,
-                                                        objective, tree, leaf_l2, static_cast<const float *>(w.ptr), w.on_device, weight_max, sp, bits, vp);
+        return gbrl_hip_newton_leaves_prepared_weighted(self.h, ds, r.ptr, r.on_device, m, p.f32(), p.on_device, t.ptr, t.on_device,
+                                                        objective, tree, leaf_l2, w.f32(), w.on_device, weight_max, sp, bits, vp);
     });
 }
 
@@ -1118,11 +570,10 @@ py::dict newton_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object
 // quantile_leaves_prepared(ds, pred, targets, alpha, rows=None, tree=-1) -> {'values': float32 [leaves, D], 'counts': int64 [leaves], 'ranks': int64 [leaves, D]}
 py::dict quantile_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &pred, py::object &targets, py::object alpha_obj, py::object &rows, int tree) {
     const gbrl_hip_metadata md = self.meta();
-    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
     const int D = md.output_dim;
     const std::vector<float> alpha = read_alpha(alpha_obj, D, "quantile_leaves_prepared");
-    Input p = read_input(pred, "pred", false, "quantile_leaves_prepared", false);
-    if (!p.ptr) fail("Cannot call quantile_leaves_prepared without pred!");
+    Input p = require_input(pred, "pred", "quantile_leaves_prepared");
     const RowsArg r = read_rows_arg(rows, "quantile_leaves_prepared", ds_obj, p);
     const int m = r.m;
     check_rows_by_outputs(p, "pred", m, D);
@@ -1130,8 +581,8 @@ py::dict quantile_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::obje
     if (!t.ptr) fail("Cannot call quantile_leaves_prepared without targets!");
     return leaf_quantile_result(tree_leaf_count(self, md, tree), D, [&](float *vp, int64_t *cp, int64_t *kp) {
         py::gil_scoped_release release;
-        return gbrl_hip_quantile_leaves_prepared(self.h, ds, r.ptr, r.on_device, m, static_cast<const float *>(p.ptr), p.on_device,
-                                                 static_cast<const float *>(t.ptr), t.on_device, alpha.empty() ? nullptr : alpha.data(), tree, vp, cp, kp);
+        return gbrl_hip_quantile_leaves_prepared(self.h, ds, r.ptr, r.on_device, m, p.f32(), p.on_device,
+                                                 t.f32(), t.on_device, alpha.empty() ? nullptr : alpha.data(), tree, vp, cp, kp);
     });
 }
 
@@ -1150,15 +601,14 @@ py::dict leaf_quantile_host_impl(py::array_t<float, py::array::c_style | py::arr
 py::array_t<float> objective_hessian_host_impl(py::object &pred, py::object targets, const std::string &objective_name, py::object &weights) {
     const int objective = parse_objective(objective_name);
     Input p = read_input(pred, "pred", false, "objective_hessian_host", false);
-    if (p.on_device) fail("objective_hessian_host takes NumPy arrays");
+    require_host(p, "objective_hessian_host takes NumPy arrays");
     if (p.shape.empty() || p.shape.size() > 2) fail("pred must be a float32 array of shape (n, D) or (n,)");
     const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
     Input w = read_weights(weights, "weights", "objective_hessian_host", n, true);
-    if (w.on_device) fail("objective_hessian_host takes NumPy arrays");
+    require_host(w, "objective_hessian_host takes NumPy arrays");
     py::array_t<float> out(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
     float none = 0.0f;
-    check(gbrl_hip_objective_hessian_host_weighted(static_cast<const float *>(p.ptr), static_cast<const float *>(w.ptr), n, D, objective,
-                                                   out.size() ? out.mutable_data() : &none));
+    check(gbrl_hip_objective_hessian_host_weighted(p.f32(), w.f32(), n, D, objective, out.size() ? out.mutable_data() : &none));
     return out;
 }
 
@@ -1185,20 +635,17 @@ py::array_t<int64_t> metric_counts_array(int objective, int metric, int D) {
 py::tuple eval_metric_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, const std::string &metric_name) {
     const gbrl_hip_metadata md = self.meta();
     const int objective = parse_objective(objective_name), metric = parse_metric(metric_name), D = md.output_dim;
-    Input p = read_input(pred, "pred", false, "eval_metric", false);
-    if (!p.ptr) fail("Cannot call eval_metric without pred!");
+    Input p = require_input(pred, "pred", "eval_metric");
     const int n = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
     check_rows_by_outputs(p, "pred", n, D);
     Input t = read_objective_targets(targets, "targets", false, "eval_metric", objective, n, D, true);
     if (!t.ptr) fail("Cannot call eval_metric without targets!");
     py::array_t<int64_t> counts = metric_counts_array(objective, metric, D);
     double value = 0.0;
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_eval_metric(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, n, objective, metric, &value, counts.mutable_data());
+        check(gbrl_hip_eval_metric(self.h, p.f32(), p.on_device, t.ptr, t.on_device, n, objective, metric, &value, counts.mutable_data()));
     }
-    check(rc);
     return py::make_tuple(py::float_(value), counts);
 }
 
@@ -1206,94 +653,15 @@ py::tuple eval_metric_impl(PyGBRL &self, py::object &pred, py::object &targets, 
 py::tuple eval_metric_host_impl(py::object &pred, py::object &targets, const std::string &objective_name, const std::string &metric_name) {
     const int objective = parse_objective(objective_name), metric = parse_metric(metric_name);
     Input p = read_input(pred, "pred", false, "eval_metric_host", false);
-    if (p.on_device) fail("eval_metric_host takes NumPy arrays");
+    require_host(p, "eval_metric_host takes NumPy arrays");
     if (p.shape.empty() || p.shape.size() > 2) fail("pred must be a float32 array of shape (n, D) or (n,)");
     const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
     Input t = read_objective_targets(targets, "targets", false, "eval_metric_host", objective, n, D, true);
-    if (t.on_device) fail("eval_metric_host takes NumPy arrays");
+    require_host(t, "eval_metric_host takes NumPy arrays");
     py::array_t<int64_t> counts = metric_counts_array(objective, metric, std::max(D, 1));
     double value = 0.0;
-    check(gbrl_hip_eval_metric_host(static_cast<const float *>(p.ptr), t.ptr, n, D, objective, metric, &value, counts.mutable_data()));
+    check(gbrl_hip_eval_metric_host(p.f32(), t.ptr, n, D, objective, metric, &value, counts.mutable_data()));
     return py::make_tuple(py::float_(value), counts);
-}
-
-// objective_gradient(pred, targets, objective, weights=None) -> (grad, loss): NumPy in, NumPy out; a device tuple gives a DLPack capsule on the model's device
-py::dict rank_gradient_impl(PyGBRL &self, py::object &pred, py::object &labels, py::object &group, const std::string &objective_name, py::object ndcg_at_obj);
-bool rank_objective_name(const std::string &s);
-py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights, py::object alpha_obj,
-                                  py::object group, py::object ndcg_at) {
-    if (rank_objective_name(objective_name)) {   // the ranking objectives: targets are the int32 labels, the rows of a query are named by group
-        if (!weights.is_none() || !alpha_obj.is_none()) fail("objective_gradient: weights and alpha do not go with a ranking objective");
-        py::dict r = rank_gradient_impl(self, pred, targets, group, objective_name, ndcg_at);
-        return py::make_tuple(r["grad"], r["loss"]);
-    }
-    if (!group.is_none() || !ndcg_at.is_none()) fail("objective_gradient: group and ndcg_at belong to the ranking objectives 'pairwise' and 'lambdarank'");
-    const gbrl_hip_metadata md = self.meta();
-    const int objective = parse_objective(objective_name), D = md.output_dim;
-    const std::vector<float> alpha = read_alpha(alpha_obj, D, "objective_gradient");
-    Input p = read_input(pred, "pred", false, "objective_gradient", false);
-    if (!p.ptr) fail("Cannot call objective_gradient without pred!");
-    const int n = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
-    check_rows_by_outputs(p, "pred", n, D);
-    Input t = read_objective_targets(targets, "targets", false, "objective_gradient", objective, n, D, true);
-    if (!t.ptr) fail("Cannot call objective_gradient without targets!");
-    Input w = read_weights(weights, "weights", "objective_gradient", n, true);
-    if (w.ptr && (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty())) fail("objective_gradient: row weights with the quantile objective (alpha=) are not supported");
-    const size_t n_el = std::max<size_t>(static_cast<size_t>(n) * D, 1);
-    float *g = nullptr;
-    int dev_id = 0;
-    if (p.on_device) {
-        dev_id = gbrl_hip_device_ordinal(self.h);
-        if (dev_id < 0) fail(gbrl_hip_last_error());
-        g = static_cast<float *>(gbrl_hip_device_alloc_on(dev_id, sizeof(float) * n_el));
-        if (!g) fail(gbrl_hip_last_error());
-    } else {
-        g = new float[n_el];
-    }
-    double loss = 0.0;
-    int rc;
-    {
-        py::gil_scoped_release release;
-        if (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty())
-            rc = gbrl_hip_objective_gradient_quantile(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, alpha.empty() ? nullptr : alpha.data(),
-                                                      n, objective, g, &loss);
-        else
-            rc = gbrl_hip_objective_gradient_weighted(self.h, static_cast<const float *>(p.ptr), p.on_device, t.ptr, t.on_device, static_cast<const float *>(w.ptr),
-                                                      w.on_device, n, objective, g, &loss);
-    }
-    if (rc != GBRL_HIP_OK) {
-        if (p.on_device) gbrl_hip_device_free(g); else delete[] g;
-        fail(gbrl_hip_last_error());
-    }
-    std::vector<int64_t> shape(p.shape.begin(), p.shape.end());
-    if (p.on_device) return py::make_tuple(make_dlpack(g, shape, true, dev_id), py::float_(loss));
-    py::capsule owner(g, [](void *q) { delete[] static_cast<float *>(q); });
-    return py::make_tuple(py::array_t<float>(std::vector<py::ssize_t>(shape.begin(), shape.end()), g, owner), py::float_(loss));
-}
-
-// the gradient rule on the host (include/gbrl_hip.h, "Classification objectives"): no device, no model
-py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights, py::object alpha_obj) {
-    const int objective = parse_objective(objective_name);
-    Input p = read_input(pred, "pred", false, "objective_gradient_host", false);
-    if (p.on_device) fail("objective_gradient_host takes NumPy arrays");
-    if (p.shape.empty() || p.shape.size() > 2) fail("pred must be a float32 array of shape (n, D) or (n,)");
-    const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
-    Input t = read_objective_targets(targets, "targets", false, "objective_gradient_host", objective, n, D, true);
-    if (t.on_device) fail("objective_gradient_host takes NumPy arrays");
-    Input w = read_weights(weights, "weights", "objective_gradient_host", n, true);
-    if (w.on_device) fail("objective_gradient_host takes NumPy arrays");
-    const std::vector<float> alpha = read_alpha(alpha_obj, D, "objective_gradient_host");
-    py::array_t<float> out(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
-    float none = 0.0f;
-    if (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty()) {
-        if (w.ptr) fail("objective_gradient_host: row weights with the quantile objective (alpha=) are not supported");
-        check(gbrl_hip_objective_gradient_host_quantile(static_cast<const float *>(p.ptr), t.ptr, alpha.empty() ? nullptr : alpha.data(), n, D, objective,
-                                                        out.size() ? out.mutable_data() : &none));
-        return out;
-    }
-    check(gbrl_hip_objective_gradient_host_weighted(static_cast<const float *>(p.ptr), t.ptr, static_cast<const float *>(w.ptr), n, D, objective,
-                                                    out.size() ? out.mutable_data() : &none));
-    return out;
 }
 
 // ---- ranking objectives on query groups (include/gbrl_hip.h, "Ranking objectives")
@@ -1301,34 +669,6 @@ bool rank_objective_name(const std::string &s) { return s == "pairwise" || s == 
 int parse_rank_objective(const std::string &s) {
     return parse_enum(s, {{"pairwise", GBRL_HIP_OBJ_PAIRWISE}, {"lambdarank", GBRL_HIP_OBJ_LAMBDARANK}},
                       "Invalid objective! The ranking objectives are: pairwise/lambdarank");
-}
-int read_ndcg_at(py::object &ndcg_at, const std::string &fn) {
-    if (ndcg_at.is_none()) return 0;
-    const long long k = ndcg_at.cast<long long>();
-    if (k < 0 || k > 0x7fffffffLL) fail(fn + ": ndcg_at must be positive (or 0 / None for no truncation), got " + std::to_string(k));
-    return static_cast<int>(k);
-}
-// group: the query sizes, any integer sequence -> int32 (a size that does not fit is refused here, naming the query)
-std::vector<int32_t> read_group(py::object &group, const std::string &fn, const char *name) {
-    const std::string gname(name);
-    if (group.is_none()) fail(fn + ": a ranking objective needs " + gname + ", the sizes of the queries' consecutive row runs");
-    py::array_t<int64_t, py::array::c_style | py::array::forcecast> g = py::array_t<int64_t, py::array::c_style | py::array::forcecast>::ensure(group);
-    if (!g || g.ndim() != 1) fail(fn + ": " + gname + " must be a one-dimensional sequence of integers");
-    std::vector<int32_t> out(static_cast<size_t>(g.size()));
-    for (py::ssize_t q = 0; q < g.size(); ++q) {
-        const int64_t v = g.data()[q];
-        if (v < 1 || v > 0x7fffffffLL) fail(fn + ": " + gname + "[" + std::to_string(q) + "] = " + std::to_string(v) + " (query " + std::to_string(q) + ") is outside [1, 1024]");
-        out[static_cast<size_t>(q)] = static_cast<int32_t>(v);
-    }
-    if (out.empty()) fail(fn + ": a ranking objective needs " + gname + ", the sizes of the queries' consecutive row runs");
-    return out;
-}
-Input read_rank_labels(py::object &labels, const std::string &fn, int n) {
-    if (py::isinstance<py::array>(labels) && !py::isinstance<py::array_t<int32_t>>(labels)) fail(fn + ": labels must be an int32 array of shape (n,)");
-    Input l = read_input(labels, "labels", false, fn, 2);
-    if (!l.ptr) fail("Cannot call " + fn + " without labels!");
-    if (l.shape.size() != 1 || l.shape[0] != static_cast<size_t>(n)) fail(fn + ": labels must be an int32 array of shape (" + std::to_string(n) + ",)");
-    return l;
 }
 int rank_rows_of(const Input &p, const std::string &fn) {
     const bool ok = (p.shape.size() == 1 && p.shape[0] > 0) || (p.shape.size() == 2 && p.shape[1] == 1 && p.shape[0] > 0);
@@ -1341,8 +681,7 @@ py::dict rank_gradient_impl(PyGBRL &self, py::object &pred, py::object &labels, 
     const std::string fn = "rank_gradient";
     const int objective = parse_rank_objective(objective_name);
     const int ndcg_at = read_ndcg_at(ndcg_at_obj, fn);
-    Input p = read_input(pred, "pred", false, fn, false);
-    if (!p.ptr) fail("Cannot call rank_gradient without pred!");
+    Input p = require_input(pred, "pred", fn);
     const int n = rank_rows_of(p, fn);
     Input l = read_rank_labels(labels, fn, n);
     const std::vector<int32_t> grp = read_group(group, fn);
@@ -1350,43 +689,19 @@ py::dict rank_gradient_impl(PyGBRL &self, py::object &pred, py::object &labels, 
     py::array_t<double> ndcg(std::vector<py::ssize_t>{Q});
     double loss = 0.0;
     int64_t pairs = 0;
-    const std::vector<int64_t> shape(p.shape.begin(), p.shape.end());
-    py::dict out;
-    if (p.on_device) {
-        const int dev_id = gbrl_hip_device_ordinal(self.h);
-        if (dev_id < 0) fail(gbrl_hip_last_error());
-        struct DevMem {
-            void *p = nullptr;
-            ~DevMem() { if (p) gbrl_hip_device_free(p); }
-        } g, h, pos;
-        g.p = gbrl_hip_device_alloc_on(dev_id, sizeof(float) * n);
-        h.p = gbrl_hip_device_alloc_on(dev_id, sizeof(float) * n);
-        pos.p = gbrl_hip_device_alloc_on(dev_id, sizeof(int32_t) * n);
-        if (!g.p || !h.p || !pos.p) fail(gbrl_hip_last_error());
-        int rc;
-        {
-            py::gil_scoped_release release;
-            rc = gbrl_hip_rank_gradient(self.h, static_cast<const float *>(p.ptr), 1, static_cast<const int32_t *>(l.ptr), l.on_device, grp.data(), Q, n, objective, ndcg_at,
-                                        static_cast<float *>(g.p), static_cast<float *>(h.p), &loss, ndcg.mutable_data(), static_cast<int32_t *>(pos.p), &pairs);
-        }
-        check(rc);
-        out["grad"] = make_dlpack(g.p, shape, true, dev_id); g.p = nullptr;
-        out["hess"] = make_dlpack(h.p, shape, true, dev_id); h.p = nullptr;
-        out["positions"] = make_dlpack(pos.p, {n}, true, dev_id, /*int32=*/true); pos.p = nullptr;
-    } else {
-        py::array_t<float> g(std::vector<py::ssize_t>(shape.begin(), shape.end())), h(std::vector<py::ssize_t>(shape.begin(), shape.end()));
-        py::array_t<int32_t> pos(std::vector<py::ssize_t>{n});
-        int rc;
-        {
-            py::gil_scoped_release release;
-            rc = gbrl_hip_rank_gradient(self.h, static_cast<const float *>(p.ptr), 0, static_cast<const int32_t *>(l.ptr), l.on_device, grp.data(), Q, n, objective, ndcg_at,
-                                        g.mutable_data(), h.mutable_data(), &loss, ndcg.mutable_data(), pos.mutable_data(), &pairs);
-        }
-        check(rc);
-        out["grad"] = g;
-        out["hess"] = h;
-        out["positions"] = pos;
+    // grad, hess and positions go where pred lives: the model's device, or the host
+    const int dev_id = result_device(self, p.on_device);
+    Result<float> g(p.on_device, dev_id, static_cast<size_t>(n)), h(p.on_device, dev_id, static_cast<size_t>(n));
+    Result<int32_t> pos(p.on_device, dev_id, static_cast<size_t>(n));
+    {
+        py::gil_scoped_release release;
+        check(gbrl_hip_rank_gradient(self.h, p.f32(), p.on_device, l.i32(), l.on_device, grp.data(), Q, n, objective, ndcg_at, g.get(), h.get(), &loss,
+                                      ndcg.mutable_data(), pos.get(), &pairs));
     }
+    py::dict out;
+    out["grad"] = g.release(shape_of(p));
+    out["hess"] = h.release(shape_of(p));
+    out["positions"] = pos.release({n});
     out["loss"] = py::float_(loss);
     out["ndcg"] = ndcg;
     out["pairs"] = py::int_(pairs);
@@ -1399,10 +714,10 @@ py::dict rank_gradient_host_impl(py::object &scores, py::object &labels, py::obj
     const int objective = parse_rank_objective(objective_name);
     const int ndcg_at = read_ndcg_at(ndcg_at_obj, fn);
     Input p = read_input(scores, "scores", false, fn, false);
-    if (p.on_device) fail("rank_gradient_host takes NumPy arrays");
+    require_host(p, "rank_gradient_host takes NumPy arrays");
     const int n = rank_rows_of(p, fn);
     Input l = read_rank_labels(labels, fn, n);
-    if (l.on_device) fail("rank_gradient_host takes NumPy arrays");
+    require_host(l, "rank_gradient_host takes NumPy arrays");
     const std::vector<int32_t> grp = read_group(group, fn);
     const int Q = static_cast<int>(grp.size());
     py::array_t<float> g(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end())), h(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
@@ -1411,7 +726,7 @@ py::dict rank_gradient_host_impl(py::object &scores, py::object &labels, py::obj
     double loss = 0.0;
     int64_t pairs = 0;
     const bool with_loss = objective == GBRL_HIP_OBJ_LAMBDARANK;
-    check(gbrl_hip_rank_gradient_host(static_cast<const float *>(p.ptr), static_cast<const int32_t *>(l.ptr), grp.data(), Q, n, objective, ndcg_at, g.mutable_data(),
+    check(gbrl_hip_rank_gradient_host(p.f32(), l.i32(), grp.data(), Q, n, objective, ndcg_at, g.mutable_data(),
                                       h.mutable_data(), with_loss ? &loss : nullptr, ndcg.mutable_data(), pos.mutable_data(), &pairs));
     py::dict out;
     out["grad"] = g;
@@ -1454,6 +769,62 @@ py::object objective_exp_host_impl(py::array_t<float, py::array::c_style | py::a
     return std::move(out);
 }
 
+// objective_gradient(pred, targets, objective, weights=None) -> (grad, loss): NumPy in, NumPy out; a device tuple gives a DLPack capsule on the model's device
+py::tuple objective_gradient_impl(PyGBRL &self, py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights, py::object alpha_obj,
+                                  py::object group, py::object ndcg_at) {
+    if (rank_objective_name(objective_name)) {   // the ranking objectives: targets are the int32 labels, the rows of a query are named by group
+        if (!weights.is_none() || !alpha_obj.is_none()) fail("objective_gradient: weights and alpha do not go with a ranking objective");
+        py::dict r = rank_gradient_impl(self, pred, targets, group, objective_name, ndcg_at);
+        return py::make_tuple(r["grad"], r["loss"]);
+    }
+    if (!group.is_none() || !ndcg_at.is_none()) fail("objective_gradient: group and ndcg_at belong to the ranking objectives 'pairwise' and 'lambdarank'");
+    const gbrl_hip_metadata md = self.meta();
+    const int objective = parse_objective(objective_name), D = md.output_dim;
+    const std::vector<float> alpha = read_alpha(alpha_obj, D, "objective_gradient");
+    Input p = require_input(pred, "pred", "objective_gradient");
+    const int n = p.shape.empty() ? 0 : static_cast<int>(p.shape[0]);
+    check_rows_by_outputs(p, "pred", n, D);
+    Input t = read_objective_targets(targets, "targets", false, "objective_gradient", objective, n, D, true);
+    if (!t.ptr) fail("Cannot call objective_gradient without targets!");
+    Input w = read_weights(weights, "weights", "objective_gradient", n, true);
+    if (w.ptr && (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty())) fail("objective_gradient: row weights with the quantile objective (alpha=) are not supported");
+    Result<float> g(p.on_device, result_device(self, p.on_device), std::max<size_t>(static_cast<size_t>(n) * D, 1));   // where pred lives
+    double loss = 0.0;
+    {
+        py::gil_scoped_release release;
+        if (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty())
+            check(gbrl_hip_objective_gradient_quantile(self.h, p.f32(), p.on_device, t.ptr, t.on_device, alpha.empty() ? nullptr : alpha.data(),
+                                                       n, objective, g.get(), &loss));
+        else
+            check(gbrl_hip_objective_gradient_weighted(self.h, p.f32(), p.on_device, t.ptr, t.on_device, w.f32(), w.on_device, n, objective, g.get(), &loss));
+    }
+    return py::make_tuple(g.release(shape_of(p)), py::float_(loss));
+}
+
+// the gradient rule on the host (include/gbrl_hip.h, "Classification objectives"): no device, no model
+py::array_t<float> objective_gradient_host_impl(py::object &pred, py::object &targets, const std::string &objective_name, py::object &weights, py::object alpha_obj) {
+    const int objective = parse_objective(objective_name);
+    Input p = read_input(pred, "pred", false, "objective_gradient_host", false);
+    require_host(p, "objective_gradient_host takes NumPy arrays");
+    if (p.shape.empty() || p.shape.size() > 2) fail("pred must be a float32 array of shape (n, D) or (n,)");
+    const int n = static_cast<int>(p.shape[0]), D = p.shape.size() == 2 ? static_cast<int>(p.shape[1]) : 1;
+    Input t = read_objective_targets(targets, "targets", false, "objective_gradient_host", objective, n, D, true);
+    require_host(t, "objective_gradient_host takes NumPy arrays");
+    Input w = read_weights(weights, "weights", "objective_gradient_host", n, true);
+    require_host(w, "objective_gradient_host takes NumPy arrays");
+    const std::vector<float> alpha = read_alpha(alpha_obj, D, "objective_gradient_host");
+    py::array_t<float> out(std::vector<py::ssize_t>(p.shape.begin(), p.shape.end()));
+    float none = 0.0f;
+    if (objective == GBRL_HIP_OBJ_QUANTILE || !alpha.empty()) {
+        if (w.ptr) fail("objective_gradient_host: row weights with the quantile objective (alpha=) are not supported");
+        check(gbrl_hip_objective_gradient_host_quantile(p.f32(), t.ptr, alpha.empty() ? nullptr : alpha.data(), n, D, objective,
+                                                        out.size() ? out.mutable_data() : &none));
+        return out;
+    }
+    check(gbrl_hip_objective_gradient_host_weighted(p.f32(), t.ptr, w.f32(), n, D, objective, out.size() ? out.mutable_data() : &none));
+    return out;
+}
+
 // ---- feature importance (include/gbrl_hip.h, "Feature importance")
 // permutation_host(n, seed=0, col=0, repeat=0) -> int32 [n]: the rule on the host, no device
 py::array_t<int32_t> permutation_host_impl(int n, uint64_t seed, int col, int repeat) {
@@ -1477,7 +848,7 @@ py::dict permutation_importance_prepared_impl(PyGBRL &self, py::object ds_obj, p
                                               py::object &cols, py::object n_trees_obj, py::object alpha_obj) {
     const std::string fn = "permutation_importance_prepared";
     const gbrl_hip_metadata md = self.meta();
-    const gbrl_hip_dataset *ds = ds_obj.is_none() ? nullptr : ds_obj.cast<const PyDataset &>().h;
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
     const int objective = parse_objective(objective_name), D = md.output_dim;
     if (n_repeats < 1) fail(fn + ": n_repeats must be >= 1, got " + std::to_string(n_repeats));
     int n_trees = -1;   // None: every tree
@@ -1487,7 +858,8 @@ py::dict permutation_importance_prepared_impl(PyGBRL &self, py::object ds_obj, p
             fail(fn + ": n_trees " + std::to_string(k) + " is outside [1, " + std::to_string(md.n_trees) + "], the model's trees (None / -1: all)");
         n_trees = static_cast<int>(k);
     }
-    const int n = ds ? ds_obj.cast<const PyDataset &>().info().n_rows : 0, F = ds ? ds_obj.cast<const PyDataset &>().info().n_features : 0;
+    const gbrl_hip_dataset_desc info = dataset_info(ds_obj);
+    const int n = info.n_rows, F = info.n_features;
     std::vector<int32_t> cv;
     if (!cols.is_none()) {
         cv = read_cols(cols, fn);
@@ -1503,13 +875,11 @@ py::dict permutation_importance_prepared_impl(PyGBRL &self, py::object ds_obj, p
     const py::ssize_t C = static_cast<py::ssize_t>(cv.size()), R = n_repeats;
     py::array_t<double> loss({std::max<py::ssize_t>(C, 1), R});
     double baseline = 0.0;
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_permutation_importance_prepared(self.h, ds, t.ptr, t.on_device, objective, alpha.empty() ? nullptr : alpha.data(), n_repeats, seed,
-                                                      cols.is_none() ? nullptr : cv.data(), static_cast<int>(cv.size()), n_trees, &baseline, loss.mutable_data());
+        check(gbrl_hip_permutation_importance_prepared(self.h, ds, t.ptr, t.on_device, objective, alpha.empty() ? nullptr : alpha.data(), n_repeats, seed,
+                                                        cols.is_none() ? nullptr : cv.data(), static_cast<int>(cv.size()), n_trees, &baseline, loss.mutable_data()));
     }
-    check(rc);
     py::array_t<double> importance({C, R}), mean(C), sd(C);
     py::array_t<int32_t> cols_out(C);
     const double *L = loss.data();
@@ -1555,20 +925,15 @@ py::array_t<double> feature_importance_impl(PyGBRL &self, const std::string &kin
 }
 
 // ---- partial dependence and ICE (include/gbrl_hip.h, "Partial dependence")
-int read_n_trees(py::object &n_trees_obj) {   // None: every tree (-1); anything else is checked behind the C ABI
-    if (n_trees_obj.is_none()) return -1;
-    const long long k = n_trees_obj.cast<long long>();
-    return k < INT32_MIN ? INT32_MIN : k > INT32_MAX ? INT32_MAX : static_cast<int>(k);
-}
 
 // partial_dependence_codes(thresholds, col, n_trees=None) -> int32 [k + 1]: the break rule on the host, no device
 py::array_t<int32_t> partial_dependence_codes_impl(PyGBRL &self, py::object &thresholds, int col, py::object n_trees_obj) {
     Input t = read_input(thresholds, "thresholds", false, "partial_dependence_codes", false);
-    if (t.on_device) fail("partial_dependence_codes takes a NumPy array");
+    require_host(t, "partial_dependence_codes takes a NumPy array");
     if (t.shape.size() != 2) fail("thresholds must be the [n_features, n_bins] array PreparedDataset.thresholds() returns");
     std::vector<int32_t> buf(t.shape[1] + 1);
     int count = 0;
-    check(gbrl_hip_partial_dependence_codes(self.h, static_cast<const float *>(t.ptr), static_cast<int>(t.shape[0]), static_cast<int>(t.shape[1]), col,
+    check(gbrl_hip_partial_dependence_codes(self.h, t.f32(), static_cast<int>(t.shape[0]), static_cast<int>(t.shape[1]), col,
                                             read_n_trees(n_trees_obj), buf.data(), &count));
     py::array_t<int32_t> out(static_cast<py::ssize_t>(count));
     std::copy(buf.begin(), buf.begin() + count, out.mutable_data());
@@ -1587,17 +952,24 @@ py::dict partial_dependence_geometry_impl(int m, int D) {
     return out;
 }
 
-// partial_dependence_prepared(ds, features, n_trees=None, rows=None, ice=False, max_cells=4096) -> dict
-py::dict partial_dependence_prepared_impl(PyGBRL &self, py::object ds_obj, py::object features, py::object n_trees_obj, py::object &rows, bool ice, long long max_cells) {
-    const std::string fn = "partial_dependence_prepared";
-    const gbrl_hip_metadata md = self.meta();
-    if (ds_obj.is_none()) fail(fn + ": null data set");
-    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
-    const gbrl_hip_dataset_desc info = pds.info();
-    const int F = info.n_features, B = info.n_bins, D = md.output_dim, n_trees = read_n_trees(n_trees_obj);
-    // ---- the entries: an int column, or a pair of two distinct columns
-    struct Entry { int c0, c1; };
+const std::string kPdFn = "partial_dependence_prepared";
+
+// partial_dependence_prepared in four stages -- the entries, the breaks of a column, the cell list, the shaped result -- and what they hand on
+struct PdPlan {
+    struct Entry { int c0, c1; };   // a column, or (c1 >= 0) a pair of two distinct columns
+    gbrl_hip_model *model = nullptr;
+    int F = 0, B = 0, n_trees = -1;
     std::vector<Entry> entries;
+    std::vector<float> thr;                                   // the data set's thresholds [F, B]
+    std::unordered_map<int, std::vector<int32_t>> codes;      // the breaks of every named column
+    std::vector<int32_t> variants{-1, 0, -1, 0};              // pd_core.h's cell list, four ints per variant; variant 0 is the baseline
+    std::vector<size_t> first;                                // the first variant of every entry
+};
+
+// the entries: an int column, or a pair of two distinct columns
+void pd_read_entries(PdPlan &p, py::object &features, long long max_cells) {
+    const std::string &fn = kPdFn;
+    const int F = p.F;
     if (!py::isinstance<py::sequence>(features) || py::isinstance<py::str>(features)) fail(fn + ": features must be a sequence of columns and (c0, c1) pairs");
     auto column = [&](py::handle h, size_t e) {
         if (!py::isinstance<py::int_>(h) && !(py::hasattr(h, "__index__") && !py::isinstance<py::float_>(h))) fail(fn + ": entry " + std::to_string(e) + " of features is neither a column nor a pair of columns");
@@ -1612,95 +984,82 @@ py::dict partial_dependence_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
             if (py::len(pr) != 2) fail(fn + ": entry " + std::to_string(e) + " of features has " + std::to_string(py::len(pr)) + " columns: a pair has two");
             const int c0 = column(pr[0], e), c1 = column(pr[1], e);
             if (c0 == c1) fail(fn + ": entry " + std::to_string(e) + " of features names column " + std::to_string(c0) + " twice: a pair needs two distinct columns");
-            entries.push_back({c0, c1});
+            p.entries.push_back({c0, c1});
         } else {
-            entries.push_back({column(h, e), -1});
+            p.entries.push_back({column(h, e), -1});
         }
         ++e;
     }
-    if (entries.empty()) fail(fn + ": features is empty: name at least one column or pair");
+    if (p.entries.empty()) fail(fn + ": features is empty: name at least one column or pair");
     if (max_cells < 1) fail(fn + ": max_cells must be >= 1, got " + std::to_string(max_cells));
-    // ---- the breaks of every named column (host only), from the data set's thresholds
-    std::vector<float> thr(static_cast<size_t>(F) * B);
-    check(gbrl_hip_dataset_thresholds(pds.h, thr.data()));
-    std::unordered_map<int, std::vector<int32_t>> codes;
-    auto codes_of = [&](int c) -> const std::vector<int32_t> & {
-        auto it = codes.find(c);
-        if (it != codes.end()) return it->second;
-        std::vector<int32_t> buf(static_cast<size_t>(B) + 1);
-        int count = 0;
-        check(gbrl_hip_partial_dependence_codes(self.h, thr.data(), F, B, c, n_trees, buf.data(), &count));
-        buf.resize(static_cast<size_t>(count));
-        return codes.emplace(c, std::move(buf)).first->second;
-    };
-    // ---- the cells: variant 0 is the baseline, then every entry's cells in order
-    std::vector<int32_t> variants{-1, 0, -1, 0};
-    std::vector<size_t> first(entries.size());
-    for (size_t i = 0; i < entries.size(); ++i) {
-        const Entry &en = entries[i];
-        const std::vector<int32_t> &a = codes_of(en.c0);
+}
+
+// the breaks of column c (host only), from the data set's thresholds; worked out when a column is first named
+const std::vector<int32_t> &pd_breaks(PdPlan &p, int c) {
+    auto it = p.codes.find(c);
+    if (it != p.codes.end()) return it->second;
+    std::vector<int32_t> buf(static_cast<size_t>(p.B) + 1);
+    int count = 0;
+    check(gbrl_hip_partial_dependence_codes(p.model, p.thr.data(), p.F, p.B, c, p.n_trees, buf.data(), &count));
+    buf.resize(static_cast<size_t>(count));
+    return p.codes.emplace(c, std::move(buf)).first->second;
+}
+
+// the cells: variant 0 is the baseline, then every entry's cells in order
+void pd_cells(PdPlan &p, const gbrl_hip_dataset *ds, long long max_cells) {
+    p.thr.resize(static_cast<size_t>(p.F) * p.B);
+    check(gbrl_hip_dataset_thresholds(ds, p.thr.data()));
+    p.first.resize(p.entries.size());
+    for (size_t i = 0; i < p.entries.size(); ++i) {
+        const PdPlan::Entry &en = p.entries[i];
+        const std::vector<int32_t> &a = pd_breaks(p, en.c0);
         static const std::vector<int32_t> one{0};
-        const std::vector<int32_t> &b = en.c1 >= 0 ? codes_of(en.c1) : one;
+        const std::vector<int32_t> &b = en.c1 >= 0 ? pd_breaks(p, en.c1) : one;
         const long long cells = static_cast<long long>(a.size()) * static_cast<long long>(b.size());
         if (cells > max_cells) {
             std::stringstream ss;
-            ss << fn << ": entry " << i << " of features (";
+            ss << kPdFn << ": entry " << i << " of features (";
             if (en.c1 >= 0) ss << "columns " << en.c0 << " and " << en.c1 << ") has " << a.size() << " x " << b.size() << " = ";
             else ss << "column " << en.c0 << ") has ";
             ss << cells << " cells, max_cells is " << max_cells;
             fail(ss.str());
         }
-        first[i] = variants.size() / 4;
-        variants.resize(variants.size() + 4 * static_cast<size_t>(cells));   // pd_core.h's cell list: one column, or the row-major product of a pair
+        p.first[i] = p.variants.size() / 4;
+        p.variants.resize(p.variants.size() + 4 * static_cast<size_t>(cells));   // pd_core.h's cell list: one column, or the row-major product of a pair
         check(gbrl_hip_partial_dependence_cells(en.c0, a.data(), static_cast<int>(a.size()), en.c1, en.c1 >= 0 ? b.data() : nullptr, en.c1 >= 0 ? static_cast<int>(b.size()) : 0,
-                                                variants.data() + 4 * first[i]));
+                                                p.variants.data() + 4 * p.first[i]));
     }
-    const size_t V = variants.size() / 4;
-    if (V > static_cast<size_t>(INT32_MAX)) fail(fn + ": " + std::to_string(V) + " variants do not fit the call's int32 count");   // (the 2^20 bound is the engine's: it counts what it launches)
-    Input none;
-    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
-    const py::ssize_t m = std::max(r.m, 0);
-    if (ice && static_cast<unsigned long long>(V) * static_cast<unsigned long long>(m) * static_cast<unsigned long long>(D) >= (1ull << 31))
-        fail(fn + ": the ICE rows of " + std::to_string(V) + " variants x " + std::to_string(m) + " rows x " + std::to_string(D) +
-             " outputs are 2^31 elements or more: pass rows= to evaluate fewer rows, or fewer features per call");
-    py::array_t<double> sums({static_cast<py::ssize_t>(V), static_cast<py::ssize_t>(D)});
-    py::array_t<float> ice_all;
-    if (ice) ice_all = py::array_t<float>({static_cast<py::ssize_t>(V), m, static_cast<py::ssize_t>(D)});
-    int rc;
-    {
-        double *sp = sums.mutable_data();
-        float *ip = ice && ice_all.size() > 0 ? ice_all.mutable_data() : nullptr;
-        py::gil_scoped_release release;
-        rc = gbrl_hip_partial_dependence_prepared(self.h, pds.h, variants.data(), static_cast<int>(V), r.ptr, r.on_device, r.m, n_trees, sp, ip, 0);
-    }
-    check(rc);
-    // ---- the result: sums / m, shaped per entry
+}
+
+// the result: sums / m, shaped per entry
+py::dict pd_shape_result(const PdPlan &p, const py::array_t<double> &sums, const py::array_t<float> &ice_all, bool ice, py::ssize_t m, int D) {
+    const int B = p.B;
     const double *S = sums.data();
     py::array_t<double> baseline(static_cast<py::ssize_t>(D));
     for (int d = 0; d < D; ++d) baseline.mutable_data()[d] = S[d] / static_cast<double>(m);
     py::list l_features, l_codes, l_values, l_pd, l_ice;
-    for (size_t i = 0; i < entries.size(); ++i) {
-        const Entry &en = entries[i];
+    for (size_t i = 0; i < p.entries.size(); ++i) {
+        const PdPlan::Entry &en = p.entries[i];
         auto codes_arr = [&](int c) {
-            const std::vector<int32_t> &a = codes.at(c);
+            const std::vector<int32_t> &a = p.codes.at(c);
             py::array_t<int32_t> out(static_cast<py::ssize_t>(a.size()));
             std::copy(a.begin(), a.end(), out.mutable_data());
             return out;
         };
         auto values_arr = [&](int c) {   // the threshold segment j >= 1 begins just above: thr[c][codes[j] - 1]
-            const std::vector<int32_t> &a = codes.at(c);
+            const std::vector<int32_t> &a = p.codes.at(c);
             py::array_t<float> out(static_cast<py::ssize_t>(a.size() - 1));
-            for (size_t j = 1; j < a.size(); ++j) out.mutable_data()[j - 1] = thr[static_cast<size_t>(c) * B + static_cast<size_t>(a[j] - 1)];
+            for (size_t j = 1; j < a.size(); ++j) out.mutable_data()[j - 1] = p.thr[static_cast<size_t>(c) * B + static_cast<size_t>(a[j] - 1)];
             return out;
         };
-        const py::ssize_t k0 = static_cast<py::ssize_t>(codes.at(en.c0).size()), k1 = en.c1 >= 0 ? static_cast<py::ssize_t>(codes.at(en.c1).size()) : 1;
+        const py::ssize_t k0 = static_cast<py::ssize_t>(p.codes.at(en.c0).size()), k1 = en.c1 >= 0 ? static_cast<py::ssize_t>(p.codes.at(en.c1).size()) : 1;
         std::vector<py::ssize_t> shape{k0};
         if (en.c1 >= 0) shape.push_back(k1);
         std::vector<py::ssize_t> pd_shape(shape), ice_shape(shape);
         pd_shape.push_back(D);
         ice_shape.push_back(m); ice_shape.push_back(D);
         py::array_t<double> pd(pd_shape);
-        const double *src = S + first[i] * static_cast<size_t>(D);
+        const double *src = S + p.first[i] * static_cast<size_t>(D);
         for (py::ssize_t q = 0; q < k0 * k1 * D; ++q) pd.mutable_data()[q] = src[q] / static_cast<double>(m);
         if (en.c1 >= 0) {
             l_features.append(py::make_tuple(en.c0, en.c1));
@@ -1714,7 +1073,7 @@ py::dict partial_dependence_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
         l_pd.append(pd);
         if (ice) {
             py::array_t<float> block(ice_shape);
-            std::copy_n(ice_all.data() + first[i] * static_cast<size_t>(m) * D, static_cast<size_t>(k0 * k1 * m) * D, block.mutable_data());
+            std::copy_n(ice_all.data() + p.first[i] * static_cast<size_t>(m) * D, static_cast<size_t>(k0 * k1 * m) * D, block.mutable_data());
             l_ice.append(block);
         }
     }
@@ -1729,60 +1088,53 @@ py::dict partial_dependence_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
     return out;
 }
 
+// partial_dependence_prepared(ds, features, n_trees=None, rows=None, ice=False, max_cells=4096) -> dict
+py::dict partial_dependence_prepared_impl(PyGBRL &self, py::object ds_obj, py::object features, py::object n_trees_obj, py::object &rows, bool ice, long long max_cells) {
+    PdPlan p;
+    const std::string &fn = kPdFn;
+    const gbrl_hip_metadata md = self.meta();
+    if (ds_obj.is_none()) fail(fn + ": null data set");
+    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
+    const gbrl_hip_dataset_desc info = pds.info();
+    const int D = md.output_dim;
+    p.model = self.h; p.F = info.n_features; p.B = info.n_bins; p.n_trees = read_n_trees(n_trees_obj);
+    pd_read_entries(p, features, max_cells);
+    pd_cells(p, pds.h, max_cells);
+    const size_t V = p.variants.size() / 4;
+    if (V > static_cast<size_t>(INT32_MAX)) fail(fn + ": " + std::to_string(V) + " variants do not fit the call's int32 count");   // (the 2^20 bound is the engine's: it counts what it launches)
+    Input none;
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
+    const py::ssize_t m = std::max(r.m, 0);
+    if (ice && static_cast<unsigned long long>(V) * static_cast<unsigned long long>(m) * static_cast<unsigned long long>(D) >= (1ull << 31))
+        fail(fn + ": the ICE rows of " + std::to_string(V) + " variants x " + std::to_string(m) + " rows x " + std::to_string(D) +
+             " outputs are 2^31 elements or more: pass rows= to evaluate fewer rows, or fewer features per call");
+    py::array_t<double> sums({static_cast<py::ssize_t>(V), static_cast<py::ssize_t>(D)});
+    py::array_t<float> ice_all;
+    if (ice) ice_all = py::array_t<float>({static_cast<py::ssize_t>(V), m, static_cast<py::ssize_t>(D)});
+    {
+        double *sp = sums.mutable_data();
+        float *ip = ice && ice_all.size() > 0 ? ice_all.mutable_data() : nullptr;
+        py::gil_scoped_release release;
+        check(gbrl_hip_partial_dependence_prepared(self.h, pds.h, p.variants.data(), static_cast<int>(V), r.ptr, r.on_device, r.m, p.n_trees, sp, ip, 0));
+    }
+    return pd_shape_result(p, sums, ice_all, ice, m, D);
+}
+
 float fit_impl(PyGBRL &self, py::object &obs, py::object &cat, py::object &targets, int iterations, bool shuffle,
                const std::string &loss_type) {
     if (loss_type != "MultiRMSE") fail("Invalid loss function! Options are: MultiRMSE");   // stringTolossType, types.cpp:52-56
-    const gbrl_hip_metadata md = self.meta();
-    Input t = read_input(targets, "targets", false, "fit", false);
-    int n, tdim;   // binding.cpp:541-556
-    if (t.shape.size() == 1) {
-        if (md.output_dim > 1) { n = 1; tdim = static_cast<int>(t.shape[0]); } else { n = static_cast<int>(t.shape[0]); tdim = 1; }
-    } else { n = static_cast<int>(t.shape[0]); tdim = static_cast<int>(t.shape[1]); }
-    if (tdim != md.output_dim) {
-        std::stringstream ss;
-        ss << "Targets output dim " << tdim << " != correct output dim " << md.output_dim;
-        fail(ss.str());
-    }
-    int n_num = 0, n_cat = 0;
-    Input o = read_input(obs, "obs", true, "fit", false);
-    if (o.ptr) {
-        int no;
-        if (o.shape.size() == 1) { n_num = (n == 1) ? static_cast<int>(o.shape[0]) : 1; no = (n == 1) ? 1 : static_cast<int>(o.shape[0]); }
-        else { no = static_cast<int>(o.shape[0]); n_num = static_cast<int>(o.shape[1]); }
-        if (no != n) {
-            std::stringstream ss;
-            ss << "Number of observations " << no << " != number of gradient samples " << n;
-            fail(ss.str());
-        }
-    }
-    Input c = read_input(cat, "cat_obs", true, "fit", true);
-    if (c.ptr) {
-        int nc;
-        if (c.shape.size() == 1) { n_cat = (n == 1) ? static_cast<int>(c.shape[0]) : 1; nc = (n == 1) ? 1 : static_cast<int>(c.shape[0]); }
-        else { nc = static_cast<int>(c.shape[0]); n_cat = static_cast<int>(c.shape[1]); }
-        if (nc != n) {
-            std::stringstream ss;
-            ss << "Number of categorical observations " << nc << " != number of gradient samples " << n;
-            fail(ss.str());
-        }
-    }
-    if (n_cat + n_num != md.input_dim) {
-        std::stringstream ss;
-        ss << "Total number of features " << n_cat + n_num << " != correct input dim " << md.input_dim;
-        fail(ss.str());
-    }
+    const SampleShape s = read_sample_shape(self.meta(), "fit", targets, "targets", "Targets", obs, cat);
     float loss = 0.0f;
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_fit(self.h, static_cast<const float *>(o.ptr), o.on_device, static_cast<const char *>(c.ptr), c.on_device,
-                          static_cast<const float *>(t.ptr), t.on_device, n, n_num, n_cat, iterations, shuffle ? 1 : 0, &loss);
+        check(gbrl_hip_fit(self.h, s.o.f32(), s.o.on_device, s.c.cells(), s.c.on_device, s.first.f32(), s.first.on_device, s.n, s.n_num, s.n_cat, iterations,
+                            shuffle ? 1 : 0, &loss));
     }
-    check(rc);
     return loss;
 }
 
-// tree_shap / ensemble_shap (binding.cpp:985-1117): NumPy inputs only, result [n_samples][n_num + n_cat][output_dim]
+// tree_shap / ensemble_shap (binding.cpp:985-1117): NumPy inputs only, result [n_samples][n_num + n_cat][output_dim].  A HostArray is no Input: it is
+// never a device tuple, takes any NumPy array of its type as the reference does (contiguity is refused, not mended) and keeps a signed shape
 struct HostArray {
     const void *ptr = nullptr;
     std::vector<py::ssize_t> shape;
@@ -1807,7 +1159,7 @@ py::array_t<float> shap_impl(PyGBRL &self, bool whole_ensemble, int tree_idx, py
     const HostArray c = host_array<py::array>(categorical_obs);
     const HostArray nv = host_array<py::array_t<float>>(norm_values), bp = host_array<py::array_t<float>>(base_poly),
                     of = host_array<py::array_t<float>>(offset);
-    // 1-D inputs are ONE sample (binding.cpp:996-1003, 1014-1021)
+    // 1-D inputs are ONE sample (binding.cpp:996-1003, 1014-1021) -- not predict's rule (one_dim_obs: a row or a column), so these lines stay their own
     py::ssize_t n = 0, n_num = 0, n_cat = 0;
     if (o.ptr) { if (o.shape.size() == 1) { n_num = o.shape[0]; n = 1; } else { n_num = o.shape[1]; n = o.shape[0]; } }
     if (c.ptr) {
@@ -1825,16 +1177,14 @@ py::array_t<float> shap_impl(PyGBRL &self, bool whole_ensemble, int tree_idx, py
     py::array_t<float> out({n, n_num + n_cat, static_cast<py::ssize_t>(md.output_dim)});
     float *dst = out.mutable_data();
     std::fill(dst, dst + out.size(), 0.0f);
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = whole_ensemble
-                 ? gbrl_hip_ensemble_shap(self.h, static_cast<const float *>(o.ptr), static_cast<const char *>(c.ptr), static_cast<int>(n),
-                                          static_cast<const float *>(nv.ptr), static_cast<const float *>(bp.ptr), static_cast<const float *>(of.ptr), dst)
-                 : gbrl_hip_tree_shap(self.h, tree_idx, static_cast<const float *>(o.ptr), static_cast<const char *>(c.ptr), static_cast<int>(n),
-                                      static_cast<const float *>(nv.ptr), static_cast<const float *>(bp.ptr), static_cast<const float *>(of.ptr), dst);
+        check(whole_ensemble
+                   ? gbrl_hip_ensemble_shap(self.h, static_cast<const float *>(o.ptr), static_cast<const char *>(c.ptr), static_cast<int>(n),
+                                            static_cast<const float *>(nv.ptr), static_cast<const float *>(bp.ptr), static_cast<const float *>(of.ptr), dst)
+                   : gbrl_hip_tree_shap(self.h, tree_idx, static_cast<const float *>(o.ptr), static_cast<const char *>(c.ptr), static_cast<int>(n),
+                                        static_cast<const float *>(nv.ptr), static_cast<const float *>(bp.ptr), static_cast<const float *>(of.ptr), dst));
     }
-    check(rc);
     return out;
 }
 
@@ -1890,12 +1240,10 @@ py::object shap_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &norm_
         fail(fn + ": the matrix of " + std::to_string(m) + " rows x " + std::to_string(F) + " features x " + std::to_string(D) +
              " outputs has 2^31 elements or more: pass rows= to explain fewer rows, or use shap_importance_prepared");
     Result<float> out(self, std::max<size_t>(static_cast<size_t>(m * F * D), 1));
-    int rc;
     {
         py::gil_scoped_release release;
-        rc = gbrl_hip_shap_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, tree_idx, poly.norm(), poly.base(), poly.offset(), out.get(), out.on_device());
+        check(gbrl_hip_shap_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, tree_idx, poly.norm(), poly.base(), poly.offset(), out.get(), out.on_device()));
     }
-    check(rc);
     return out.release({m, F, D});
 }
 
@@ -1921,13 +1269,12 @@ py::dict shap_importance_prepared_impl(PyGBRL &self, py::object ds_obj, py::obje
     const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
     const py::ssize_t F = info.n_features, D = md.output_dim;
     py::array_t<double> sum({F, D}), sum_abs({F, D});
-    int used = 0, rc;
+    int used = 0;
     {
         double *sp = sum.mutable_data(), *ap = sum_abs.mutable_data();
         py::gil_scoped_release release;
-        rc = gbrl_hip_shap_importance_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, poly.norm(), poly.base(), poly.offset(), chunk_rows, sp, ap, &used);
+        check(gbrl_hip_shap_importance_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, poly.norm(), poly.base(), poly.offset(), chunk_rows, sp, ap, &used));
     }
-    check(rc);
     py::array_t<double> mean({F, D}), mean_abs({F, D});
     for (py::ssize_t i = 0; i < F * D; ++i) {
         mean.mutable_data()[i] = sum.data()[i] / static_cast<double>(r.m);
@@ -1981,13 +1328,12 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         const int cap = static_cast<int>(std::min<size_t>(n * fc, size_t(1) << 21));
         py::array_t<int32_t> feat(cap), first(cap), count(cap);
         py::array_t<float> total(cap);
-        int nd = -1, rc;
+        int nd = -1;
         {
             py::gil_scoped_release release;
-            rc = gbrl_hip_cat_rank_stats(static_cast<const char *>(c.ptr), static_cast<int>(n), static_cast<int>(fc), static_cast<const float *>(g.ptr),
-                                         static_cast<int>(d), cap, feat.mutable_data(), first.mutable_data(), count.mutable_data(), total.mutable_data(), &nd);
+            check(gbrl_hip_cat_rank_stats(c.cells(), static_cast<int>(n), static_cast<int>(fc), g.f32(),
+                                          static_cast<int>(d), cap, feat.mutable_data(), first.mutable_data(), count.mutable_data(), total.mutable_data(), &nd));
         }
-        check(rc);
         feat.resize({nd}, false); first.resize({nd}, false); count.resize({nd}, false); total.resize({nd}, false);
         return py::make_tuple(feat, first, count, total);
     }, py::arg("categorical_obs"), py::arg("grads"));
@@ -2503,25 +1849,17 @@ PYBIND11_MODULE(gbrl_cpp, m) {
             n = static_cast<int>(b.shape[0]); dim = static_cast<int>(b.shape[1]);
             if (n == md.output_dim && dim == 1) { n = 1; dim = static_cast<int>(b.shape[0]); }
         }
-        if (dim != md.output_dim) {
-            std::stringstream ss;
-            ss << "Targets output dim " << dim << " != correct output dim " << md.output_dim;
-            fail(ss.str());
-        }
+        if (dim != md.output_dim) fail_cat("Targets output dim ", dim, " != correct output dim ", md.output_dim);
         if (n > 1) fail("Set bias with multiple samples is not supported!");
-        check(gbrl_hip_set_bias(self.h, static_cast<const float *>(b.ptr), md.output_dim, b.on_device));
+        check(gbrl_hip_set_bias(self.h, b.f32(), md.output_dim, b.on_device));
     });
     g.def("set_feature_weights", [](PyGBRL &self, py::object &w) {
         const gbrl_hip_metadata md = self.meta();
         Input x = read_input(w, "feature_weights", false, "set_feature_weights", false);
         size_t tot = 1;
         for (size_t d : x.shape) tot *= d;
-        if (static_cast<int>(tot) != md.input_dim) {
-            std::stringstream ss;
-            ss << "feature_weights input dim " << tot << " != correct input dim " << md.input_dim;
-            fail(ss.str());
-        }
-        check(gbrl_hip_set_feature_weights(self.h, static_cast<const float *>(x.ptr), md.input_dim, x.on_device));
+        if (static_cast<int>(tot) != md.input_dim) fail_cat("feature_weights input dim ", tot, " != correct input dim ", md.input_dim);
+        check(gbrl_hip_set_feature_weights(self.h, x.f32(), md.input_dim, x.on_device));
     });
     g.def("set_feature_mapping", [](PyGBRL &self, const py::array_t<int> &fm, const py::array_t<bool> &mn) {
         if (!(fm.flags() & py::array::c_style) || !(mn.flags() & py::array::c_style)) fail("Arrays must be C-contiguous");
@@ -2578,12 +1916,10 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     });
     g.def("export", [](PyGBRL &self, const std::string &filename, const std::string &modelname, const std::string &export_format,
                        const std::string &export_type, const std::string &prefix) -> int {
-        int rc;
         {
             py::gil_scoped_release release;
-            rc = gbrl_hip_export(self.h, filename.c_str(), modelname.c_str(), export_format.c_str(), export_type.c_str(), prefix.c_str());
+            check(gbrl_hip_export(self.h, filename.c_str(), modelname.c_str(), export_format.c_str(), export_type.c_str(), prefix.c_str()));
         }
-        check(rc);
         return 0;
     }, py::arg("filename"), py::arg("modelname") = "", py::arg("export_format") = "float", py::arg("export_type") = "full", py::arg("prefix") = "");
     g.def("get_scheduler_lrs", [](PyGBRL &self) {
@@ -2616,10 +1952,9 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         py::array_t<float> values({L, D}), fval({S, MD}), ew({L, MD}), bias(D), fw(in);
         py::array_t<bool> isnum({S, MD}), ineq({L, MD}), mn(in);
         py::array cats(py::dtype("S128"), std::vector<py::ssize_t>{S, MD});
-        gbrl_hip_get_ensemble(self.h, tree_indices.mutable_data(), depths.mutable_data(), values.mutable_data(), fidx.mutable_data(),
-                              fval.mutable_data(), ew.mutable_data(), reinterpret_cast<uint8_t *>(isnum.mutable_data()),
-                              reinterpret_cast<uint8_t *>(ineq.mutable_data()), static_cast<char *>(cats.mutable_data()),
-                              rn.mutable_data(), rc.mutable_data());
+        gbrl_hip_get_ensemble(self.h, tree_indices.mutable_data(), depths.mutable_data(), values.mutable_data(), fidx.mutable_data(), fval.mutable_data(),
+                              ew.mutable_data(), reinterpret_cast<uint8_t *>(isnum.mutable_data()), reinterpret_cast<uint8_t *>(ineq.mutable_data()),
+                              static_cast<char *>(cats.mutable_data()), rn.mutable_data(), rc.mutable_data());
         gbrl_hip_get_bias(self.h, bias.mutable_data());
         gbrl_hip_get_feature_weights(self.h, fw.mutable_data());
         gbrl_hip_get_feature_mapping(self.h, fm.mutable_data(), reinterpret_cast<uint8_t *>(mn.mutable_data()));
@@ -2634,9 +1969,7 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     g.def("get_device", [](PyGBRL &self) { return std::string(self.device ? "cuda" : "cpu"); });
     g.def("get_learner_name", [](PyGBRL &self) { return std::string(gbrl_hip_learner_name(self.h)); });
     g.def("print_tree", [](PyGBRL &self, int tree_idx) {
-        int rc;
-        { py::gil_scoped_release release; rc = gbrl_hip_print_tree(self.h, tree_idx); }
-        check(rc);
+        { py::gil_scoped_release release; check(gbrl_hip_print_tree(self.h, tree_idx)); }
     }, py::arg("tree_idx") = -1);
     g.def("tree_shap", [](PyGBRL &self, int tree_idx, py::object &obs, py::object &categorical_obs, py::object &norm_values,
                           py::object &base_poly, py::object &offset) {
@@ -2668,9 +2001,7 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         check(gbrl_hip_plot_tree(self.h, tree_idx, filename.c_str()));
     }, py::arg("tree_idx") = -1, py::arg("filename"));
     g.def("print_ensemble_metadata", [](PyGBRL &self) {
-        int rc;
-        { py::gil_scoped_release release; rc = gbrl_hip_print_ensemble_metadata(self.h, self.device ? "cuda" : "cpu"); }
-        check(rc);
+        { py::gil_scoped_release release; check(gbrl_hip_print_ensemble_metadata(self.h, self.device ? "cuda" : "cpu")); }
     });
     // GBRL::cuda_available (gbrl.cpp:542-548): here "is a HIP device usable"
     g.def_static("cuda_available", []() { return gbrl_hip_device_count() > 0; });

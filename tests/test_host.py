@@ -354,6 +354,21 @@ def test_leaf_accumulator_launch_plan_keeps_the_launchers_numbers(tmp_path):
     assert len(out.stdout.strip().split("\n")) == 4, out.stdout
 
 
+def test_binding_result_buffer_is_freed_once_or_handed_over_once(tmp_path):
+    """binding_result.h without pybind11 or a device (tests/cxx/binding_result_check.cpp, built with the address and undefined-behaviour
+    sanitizers): the buffer a binding call writes its result to is freed exactly once when the call fails -- the device one through the
+    memory policy, which the check replaces with counters, the host one by delete[], which the sanitizer watches; take() hands it over
+    exactly once and the destructor then frees nothing; a failed device allocation leaves nothing to free; the adopted (in-place) form
+    allocates nothing and frees nothing, whether the call fails or not."""
+    import subprocess
+    exe = tmp_path / "binding_result_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "gbrl_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "cxx", "binding_result_check.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert out.returncode == 0 and "all sections passed" in out.stdout, out.stdout + out.stderr
+    assert len(out.stdout.strip().split("\n")) == 4, out.stdout
+
+
 def test_register_tile_asm_header_is_current_and_the_compiler_keeps_out_of_the_bank(tmp_path):
     """predict_reg.hip keeps a row tile in a bank of VGPRs that the compiler must never allocate (amdgpu_num_vgpr caps it below the
     bank; the bank is only named in clobber lists).  (1) The generated assembly text is the generator's current output.  (2) Audit of
