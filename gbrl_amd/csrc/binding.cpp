@@ -1301,6 +1301,98 @@ py::tuple shap_sums_host_impl(py::array_t<float, py::array::c_style | py::array:
     return py::make_tuple(sum, sum_abs);
 }
 
+// path_contrib_prepared(ds, rows=None, n_trees=None) -> float32 [m, F, D]: NumPy for a "cpu" model, a DLPack capsule on the model's device for a
+// "cuda" one, as shap_prepared delivers
+py::object path_contrib_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &rows, py::object n_trees_obj) {
+    const std::string fn = "path_contrib_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const int n_trees = read_n_trees(n_trees_obj);
+    if (ds_obj.is_none()) {   // the library's own refusal: what it refuses about the model comes before the missing data set
+        check(gbrl_hip_path_contrib_prepared(self.h, nullptr, nullptr, 0, 0, n_trees, nullptr, 0));
+        fail(fn + ": null data set");
+    }
+    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
+    const gbrl_hip_dataset_desc info = pds.info();
+    Input none;
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
+    const int64_t m = std::max(r.m, 0), F = info.n_features, D = md.output_dim;
+    // the engine refuses the same (C callers); here too because a "cuda" model allocates its result on the device before the C call
+    if (static_cast<unsigned long long>(m) * static_cast<unsigned long long>(F) * static_cast<unsigned long long>(D) >= (1ull << 31))
+        fail(fn + ": the matrix of " + std::to_string(m) + " rows x " + std::to_string(F) + " features x " + std::to_string(D) +
+             " outputs has 2^31 elements or more: pass rows= to explain fewer rows, or use path_importance_prepared");
+    Result<float> out(self, std::max<size_t>(static_cast<size_t>(m * F * D), 1));
+    {
+        py::gil_scoped_release release;
+        check(gbrl_hip_path_contrib_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, n_trees, out.get(), out.on_device()));
+    }
+    return out.release({m, F, D});
+}
+
+// path_importance_prepared(ds, rows=None, n_trees=None) -> dict
+py::dict path_importance_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &rows, py::object n_trees_obj) {
+    const std::string fn = "path_importance_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const int n_trees = read_n_trees(n_trees_obj);
+    if (ds_obj.is_none()) {   // (as path_contrib_prepared)
+        check(gbrl_hip_path_importance_prepared(self.h, nullptr, nullptr, 0, 0, n_trees, nullptr, nullptr, nullptr, nullptr));
+        fail(fn + ": null data set");
+    }
+    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
+    const gbrl_hip_dataset_desc info = pds.info();
+    Input none;
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
+    const py::ssize_t F = info.n_features, D = md.output_dim;
+    py::array_t<double> sum({F, D}), sum_abs({F, D}), expected(D);
+    int passes = 0;
+    {
+        double *sp = sum.mutable_data(), *ap = sum_abs.mutable_data(), *ep = expected.mutable_data();
+        py::gil_scoped_release release;
+        check(gbrl_hip_path_importance_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, n_trees, sp, ap, ep, &passes));
+    }
+    py::array_t<double> mean({F, D}), mean_abs({F, D});
+    for (py::ssize_t i = 0; i < F * D; ++i) {
+        mean.mutable_data()[i] = sum.data()[i] / static_cast<double>(r.m);
+        mean_abs.mutable_data()[i] = sum_abs.data()[i] / static_cast<double>(r.m);
+    }
+    py::dict out;
+    out["sum"] = sum;
+    out["sum_abs"] = sum_abs;
+    out["mean"] = mean;
+    out["mean_abs"] = mean_abs;
+    out["expected"] = expected;
+    out["n_rows"] = py::int_(r.m);
+    out["passes"] = py::int_(passes);
+    return out;
+}
+
+// path_contrib_host(model, X, n_trees=None) -> float32 [n, F, D]; path_expected_host(model, n_trees=None) -> float64 [D]: path_core.h's rule, no device
+py::array_t<float> path_contrib_host_impl(PyGBRL &model, py::array_t<float, py::array::c_style | py::array::forcecast> X, py::object n_trees_obj) {
+    const gbrl_hip_metadata md = model.meta();
+    const py::ssize_t F = md.n_trees > 0 ? md.n_num_features : md.input_dim;   // (the numeric count is set by the first tree)
+    if (X.ndim() != 2 || X.shape(1) != F) fail("path_contrib_host: X must be float32 [n, " + std::to_string(F) + "], the model's numeric features");
+    if (X.shape(0) > INT32_MAX) fail("path_contrib_host: too many rows");
+    py::array_t<float> out({X.shape(0), F, static_cast<py::ssize_t>(md.output_dim)});
+    check(gbrl_hip_path_contrib_host(model.h, X.data(), static_cast<int>(X.shape(0)), read_n_trees(n_trees_obj), out.mutable_data()));
+    return out;
+}
+
+py::array_t<double> path_expected_host_impl(PyGBRL &model, py::object n_trees_obj) {
+    py::array_t<double> out(static_cast<py::ssize_t>(model.meta().output_dim));
+    check(gbrl_hip_path_expected_host(model.h, read_n_trees(n_trees_obj), out.mutable_data()));
+    return out;
+}
+
+py::dict path_geometry_impl(int n_used, int F, int D) {
+    int slots = 0, passes = 0;
+    uint64_t lds = 0;
+    gbrl_hip_path_geometry(n_used, F, D, &slots, &passes, &lds);
+    py::dict out;
+    out["slots"] = slots;
+    out["passes"] = passes;
+    out["lds_bytes"] = py::int_(lds);
+    return out;
+}
+
 py::dict shap_geometry_impl(int F, int D) {
     int tile = 0, chunk = 0;
     uint64_t budget = 0;
@@ -1439,6 +1531,18 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "shap_geometry(F=1, D=1) -> {'tile_rows': 64, 'default_chunk_rows': ..., 'scratch_budget': 67108864}: the rows one float64 partial of\n"
           "shap_importance_prepared sums, and its default chunk_rows for F features and D outputs: the largest multiple of 64 whose float32 scratch\n"
           "[chunk_rows, F, D] stays within the budget, and at least 64");
+    m.def("path_contrib_host", &path_contrib_host_impl, py::arg("model"), py::arg("X"), py::arg("n_trees") = py::none(),
+          "path_contrib_host(model, X, n_trees=None) -> float32 [n, F, D]\n\n"
+          "Path attribution (Saabas; XGBoost's approx_contribs) of the trees [0, n_trees) on float observations X [n, F], from the host copy of the model (no\n"
+          "device is needed): a row's prediction split among the features tested on its root-to-leaf paths, each decision credited with the change of the\n"
+          "subtree's cover-weighted expected value, in units of the prediction.  The bytes GBRL.path_contrib_prepared produces from a data set of X.");
+    m.def("path_expected_host", &path_expected_host_impl, py::arg("model"), py::arg("n_trees") = py::none(),
+          "path_expected_host(model, n_trees=None) -> float64 [D]: bias + the expected values of the trees [0, n_trees); a row's contributions summed over\n"
+          "the features, plus this, are its prediction up to float32 rounding");
+    m.def("path_geometry", &path_geometry_impl, py::arg("n_used"), py::arg("F"), py::arg("D"),
+          "path_geometry(n_used, F, D) -> {'slots', 'passes', 'lds_bytes'}: the streaming kernel's plan for n_used tested features of F columns and D outputs --\n"
+          "the features a pass keeps in LDS beside the code tile, the walks of the trees a tile needs, the dynamic LDS of a block; slots == 0: the\n"
+          "one-thread-per-row kernel takes the shape");
     m.def("leaf_quantile_host", &leaf_quantile_host_impl, py::arg("x"), py::arg("leaves"), py::arg("n_leaves"), py::arg("alpha"),
           "leaf_quantile_host(x, leaves, n_leaves, alpha) -> {'values': float32 [n_leaves, D], 'counts': int64 [n_leaves], 'ranks': int64 [n_leaves, D]}\n\n"
           "The leaf rule of fit_prepared(leaf_update='quantile') and GBRL.quantile_leaves_prepared on the host (no device is needed): x float32 [m, D] are the\n"
@@ -1997,6 +2101,19 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "whole: chunk_rows rows at a time (a positive multiple of 64; None: the largest whose float32 scratch stays within 64 MiB) are evaluated and\n"
           "reduced on the device.  The sums follow gbrl_cpp.shap_sums_host's rule on that matrix byte for byte, whatever chunk_rows is.  Refusals as\n"
           "shap_prepared's, without the 2^31 limit.");
+    g.def("path_contrib_prepared", &path_contrib_prepared_impl, py::arg("ds"), py::arg("rows") = py::none(), py::arg("n_trees") = py::none(),
+          "path_contrib_prepared(ds, rows=None, n_trees=None) -> float32 [m, F, D]\n\n"
+          "Path attribution (Saabas; XGBoost's approx_contribs) of the trees [0, n_trees) (None: all) for the rows of a prepared data set (rows: int32 indices,\n"
+          "duplicates allowed; None: every row), from its bin codes on the device: a row's prediction split among the features tested on its root-to-leaf paths.\n"
+          "Byte for byte gbrl_cpp.path_contrib_host(model, X) on the observations the codes were made from; summed over the features, plus 'expected' of\n"
+          "path_importance_prepared, it is the prediction.  NOT the SHAP value: features near the root are credited more and the rule is not consistent;\n"
+          "shap_prepared has the exact values at the SHAP recursion's cost.  NumPy for a \"cpu\" model, a DLPack capsule for a \"cuda\" one.  m * F * D < 2^31.");
+    g.def("path_importance_prepared", &path_importance_prepared_impl, py::arg("ds"), py::arg("rows") = py::none(), py::arg("n_trees") = py::none(),
+          "path_importance_prepared(ds, rows=None, n_trees=None) -> dict\n\n"
+          "'sum', 'sum_abs', 'mean', 'mean_abs': float64 [F, D], the sums over the m rows of path_contrib_prepared's matrix and of its absolute values, and those\n"
+          "sums / m; 'expected': float64 [D]; 'n_rows' = m; 'passes': the feature passes of the streaming kernel (0: the one-thread-per-row kernel ran).  The\n"
+          "matrix is never held: a tile's contributions live in LDS until they are reduced.  The sums follow gbrl_cpp.shap_sums_host's rule on that matrix byte\n"
+          "for byte.  Refusals as path_contrib_prepared's, without the 2^31 limit.");
     g.def("plot_tree", [](PyGBRL &self, int tree_idx, const std::string &filename) {
         check(gbrl_hip_plot_tree(self.h, tree_idx, filename.c_str()));
     }, py::arg("tree_idx") = -1, py::arg("filename"));

@@ -923,6 +923,47 @@ void gbrl_hip_shap_geometry(int n_features, int output_dim, int *tile_rows, int 
     if (budget_bytes) *budget_bytes = gbrl::kern::kShapScratchBudget;
 }
 
+// ---- path attribution on a data set: the matrix, its column sums, the rule on the host (engine_path.hip; path_core.h has the rule and the plans)
+int gbrl_hip_path_contrib_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int n_trees, float *out,
+                                   int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("path_contrib_prepared");
+        m->engine.path_contrib_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, n_trees, out, out_on_device != 0);
+    });
+}
+
+int gbrl_hip_path_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int n_trees,
+                                      double *sum_out, double *abs_out, double *expected_out, int *passes_used) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("path_importance_prepared");
+        m->engine.path_importance_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, n_trees, sum_out, abs_out, expected_out, passes_used);
+    });
+}
+
+int gbrl_hip_path_contrib_host(const gbrl_hip_model *m, const float *obs, int n_rows, int n_trees, float *out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        if (n_rows < 0) throw gbrl::InvalidArgument("path_contrib_host: a negative row count");
+        gbrl::path_contrib_host(m->engine.model, obs, n_rows, n_trees, out);
+    });
+}
+
+int gbrl_hip_path_expected_host(const gbrl_hip_model *m, int n_trees, double *out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        gbrl::path_expected_host(m->engine.model, n_trees, out);
+    });
+}
+
+void gbrl_hip_path_geometry(int n_used, int n_features, int output_dim, int *slots, int *passes, uint64_t *lds_bytes) {
+    const gbrl::kern::PathSlotPlan p = gbrl::kern::path_slot_plan(n_used, (std::max(n_features, 1) + 15) / 16, output_dim);
+    if (slots) *slots = p.slots;
+    if (passes) *passes = p.passes;
+    if (lds_bytes) *lds_bytes = p.lds;
+}
+
 static_assert(GBRL_HIP_IMPORTANCE_SPLIT == gbrl::kFeatureSplit && GBRL_HIP_IMPORTANCE_COVER == gbrl::kFeatureCover, "the importance kinds are the header's");
 int gbrl_hip_feature_importance(const gbrl_hip_model *m, int kind, const int64_t *leaf_counts, double *out) {
     return guarded([&] {

@@ -18,6 +18,7 @@
 #include "model.h"
 #include "cat_candidates_host.h"   // HipError, Unsupported; detail::CatCandidate, CatMemory
 #include "mirror_records.h"        // detail::GreedyNodes, RateTable, CatDict: the host half of the device mirror
+#include "path_core.h"             // kern::PathTable: the host half of path attribution
 
 namespace gbrl {
 
@@ -481,6 +482,17 @@ class Engine {
     void shap_importance_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *norm, const float *base_poly,
                                   const float *offset, int chunk_rows, double *sum_out, double *abs_out, int *chunk_rows_used);
 
+    // Path attribution (Saabas) on a data set (include/gbrl_hip.h, "Path attribution on a data set"; path_core.h has the rule): the contributions of
+    // the trees [0, n_trees) (-1: all) for the m rows of the row list.  rows / rows_dev / m as step_prepared's (null: every row).  out: float32
+    // [m][F][D], host or device, overwritten -- byte for byte path_contrib_host on the observations the codes were made from.  Refused before the
+    // device is touched: check_path_prepared's list, and for the matrix m * F * D >= 2^31.
+    void path_contrib_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int n_trees, float *out, bool out_dev);
+    // sum_out / abs_out: host float64 [F][D], the sums over the m rows of that matrix and of its absolute values by shap_core.h's rule; the bytes do
+    // not depend on the launches or the feature passes.  expected_out (nullable): float64 [D].  *passes_out (nullable): the feature passes of the
+    // streaming kernel, 0 when the general kernel ran.
+    void path_importance_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int n_trees, double *sum_out, double *abs_out,
+                                  double *expected_out, int *passes_out);
+
     void set_collective(const gbrl_hip_collective *hooks);
     // Native exchange: an RCCL communicator of this engine's own, collectives enqueued on its stream (no host sync).
     // id128 = gbrl_hip_rccl_unique_id() of rank 0, distributed by the caller.  Collective call (all ranks).
@@ -785,6 +797,21 @@ class Engine {
                                         const float *base_poly, const float *offset);
     void launch_shap_codes(const PreparedDataset *ds, const ShapPreparedRun &r, int p0, int count, float *out);
     void finish_shap_prepared(const char *launch, void *host, const void *dev, size_t bytes, const char *what);
+
+    // ---- path attribution (engine_path.hip): the host delta table under a mark of its own (trees it covers; rewind_values / invalidate_mirror lower
+    // it), its device copy, the slot tables of a call, the host-bound matrix (released when the call ends), the general kernel's scratch chunk (kept),
+    // the tile partials (released), the sums
+    kern::PathTable path_;
+    size_t path_trees_ = 0;
+    uint64_t path_version_ = ~0ull, path_dev_version_ = ~0ull;
+    DevBuf m_path_delta_, d_path_used_, d_path_slot_of_, d_path_out_, d_path_scratch_, d_path_part_, d_path_sums_;
+    struct PathRun { kern::PredictModel pm; kern::CodeTables ct; kern::PathTables pt; const int32_t *rows; std::vector<int32_t> used; };
+    // what both calls refuse, in order: check_prepared_dataset's list (categorical columns and a row-sharded model among it), output_dim > 128, a model
+    // without trees, n_trees outside it, check_row_count / check_host_rows, a tree the thresholds cannot express (check_code_range), a tree of the
+    // range that is no proper binary tree with a split.  Returns the tree count.
+    int check_path_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int n_trees);
+    PathRun stage_path_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int stop);
+    void launch_path_matrix(const PreparedDataset *ds, const PathRun &r, int p0, int count, int stop, bool generic, float *out);
 
     // ---- per-step workspace (grow-only, reused across steps) ----
     DevBuf d_obs_, d_grads_, d_qg_, d_stat_, d_partials_f64_, d_meanden_, d_maxbits_;

@@ -83,7 +83,7 @@ void Engine::sync_cat_dict() {
     const size_t T = md.n_trees, L = md.n_leaves, S = model.split_rows();
     if (dict_model_version_ == model.version) return;
     if (up_splits_ > S || up_trees_ > T || up_leaves_ > L || dict_splits_ > S) {   // the ensemble has shrunk: nothing is kept
-        up_splits_ = up_trees_ = up_leaves_ = 0; dict_splits_ = 0; grd_up_nodes_ = 0;
+        up_splits_ = up_trees_ = up_leaves_ = 0; dict_splits_ = 0; grd_up_nodes_ = 0; path_trees_ = 0;
         cat_dict_.clear(); cat_ids_host_.clear(); cond_pack_host_.clear();
         dict_version_ = static_cast<size_t>(-1);
     }
@@ -101,6 +101,7 @@ void Engine::invalidate_mirror() {
     values_redo_tree_ = kNoRedo;
     grd_up_nodes_ = 0;
     rate_trees_ = 0;
+    path_trees_ = 0;
     mirror_version_ = ~0ull;
 }
 
@@ -110,6 +111,7 @@ void Engine::invalidate_mirror() {
 void Engine::rewind_values(int t) {
     up_leaves_ = std::min(up_leaves_, static_cast<size_t>(model.tree_indices[t]));
     values_redo_tree_ = std::min(values_redo_tree_, static_cast<size_t>(t));
+    path_trees_ = std::min(path_trees_, static_cast<size_t>(t));   // (the path attribution's delta table holds the values too)
 }
 
 void Engine::sync_model_to_device() {

@@ -11,6 +11,7 @@
 //     block, leaves N_INPUTS un-prefixed and spells the grow policy "Oblivous" (types.cpp:112-116);
 //   * print_tree writes all 128 bytes of a categorical value, NULs included (node.cpp:531-534).
 #include "explain.h"
+#include "path_core.h"
 
 // the SHAP sums below spell out every rounding (see Walker::edge_term): keep the compiler from fusing anything else
 #pragma clang fp contract(off)
@@ -531,6 +532,63 @@ void feature_importance(const Model &m, int kind, const int64_t *leaf_counts, do
             }
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// path attribution on the host (path_core.h has the rule): the bytes the device kernels of path_rows.hip must produce
+// ------------------------------------------------------------------------------------------------------------------
+static int check_path_host(const Model &m, const kern::PathTable &table, int n_trees) {
+    const std::string bad_trees = kern::path_trees_error(n_trees, m.meta.n_trees);
+    if (!bad_trees.empty()) throw std::runtime_error("path_contrib_host: " + bad_trees);
+    const int stop = n_trees == -1 ? m.meta.n_trees : n_trees;
+    const std::string bad_model = kern::path_model_error(m, table, stop);
+    if (!bad_model.empty()) throw std::runtime_error("path_contrib_host: " + bad_model);
+    return stop;
+}
+
+void path_contrib_host(const Model &m, const float *obs, int n, int n_trees, float *out) {
+    kern::PathTable table;
+    table.extend(m, 0);
+    const int stop = check_path_host(m, table, n_trees);
+    if (n > 0 && (obs == nullptr || out == nullptr)) throw std::runtime_error("path_contrib_host: the observations and a place for the result are needed");
+    const size_t F = m.meta.n_num_features, D = m.meta.output_dim, MD = m.meta.max_depth;
+    std::fill(out, out + static_cast<size_t>(std::max(n, 0)) * F * D, 0.0f);
+    for (int r = 0; r < n; ++r) {
+        const float *x = obs + static_cast<size_t>(r) * F;
+        float *phi = out + static_cast<size_t>(r) * F * D;
+        for (int t = 0; t < stop; ++t) {
+            const int l0 = static_cast<int>(m.first_leaf(t)), nl = static_cast<int>(m.leaf_count(t));
+            int leaf = -1;
+            if (m.oblivious()) {   // predictor.cpp:99-118
+                const int depth = m.depths[t];
+                int l = 0;
+                for (int d = 0; d < depth; ++d) l |= (x[m.feature_indices[t * MD + d]] > m.feature_values[t * MD + d] ? 1 : 0) << (depth - 1 - d);
+                leaf = l0 + l;
+            } else {               // the leaf of the tree whose conditions all hold (a proper tree has exactly one)
+                for (int q = l0; q < l0 + nl && leaf < 0; ++q) {
+                    bool all = true;
+                    for (int d = 0; d < m.depths[q] && all; ++d)
+                        all = (x[m.feature_indices[q * MD + d]] > m.feature_values[q * MD + d]) == (m.inequality_directions[q * MD + d] != 0);
+                    if (all) leaf = q;
+                }
+                if (leaf < 0) continue;
+            }
+            const size_t row = kern::path_cond_row(m, t, leaf);
+            for (int d = 0; d < m.depths[row]; ++d) {
+                float *a = phi + static_cast<size_t>(m.feature_indices[row * MD + d]) * D;
+                const float *dl = &table.delta[(static_cast<size_t>(leaf) * MD + d) * D];
+                for (size_t j = 0; j < D; ++j) a[j] = kern::path_add(a[j], dl[j]);
+            }
+        }
+    }
+}
+
+void path_expected_host(const Model &m, int n_trees, double *out) {
+    kern::PathTable table;
+    table.extend(m, 0);
+    const int stop = check_path_host(m, table, n_trees);
+    if (out == nullptr) throw std::runtime_error("path_contrib_host: no place for the result");
+    table.expected(m, stop, out);
 }
 
 std::string metadata_text(const Model &m, const char *device_name) {

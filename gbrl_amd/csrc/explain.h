@@ -66,6 +66,13 @@ std::string tree_text(const Model &m, int tree_idx);
 constexpr int kFeatureSplit = 0, kFeatureCover = 1;
 void feature_importance(const Model &m, int kind, const int64_t *leaf_counts, double *out);
 
+// Extension: path attribution (Saabas) of the trees [0, n_trees) (-1: all) on float observations, from the host copy of the model (path_core.h has
+// the rule; the device kernels of path_rows.hip produce these bytes from a data set's bin codes).  obs [n][n_num_features]; out float32
+// [n][n_num_features][D], overwritten.  path_expected_host: out float64 [D], bias + the trees' expected values.  Throws std::runtime_error: a model
+// without trees or with categorical columns, n_trees outside [1, n_trees], a tree that is no proper binary tree with a split.
+void path_contrib_host(const Model &m, const float *obs, int n, int n_trees, float *out);
+void path_expected_host(const Model &m, int n_trees, double *out);
+
 // stdout text of GBRL::print_ensemble_metadata (gbrl.cpp:1254-1267)
 std::string metadata_text(const Model &m, const char *device_name);
 

@@ -713,6 +713,19 @@ struct PdVariant;
 void pd_rows(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int n_trees, const PdVariant *variants, const int32_t *slots, int n_variants,
              double *part, float *ice, bool generic, hipStream_t s);
 //
+// Path attribution of a data set's rows (path_rows.hip; path_core.h has the rule, the delta table and the launch plans).  PathTables (device): delta
+// float32 [n_leaves][max_depth][D]; used int32 [n_used], the features the trees [0, n_trees) test, ascending -- slot s stands for feature used[s];
+// slot_of int32 [F], a feature's slot or -1.  The m rows of cr (predict_continue_codes' CodeRows) are walked through the trees [0, n_trees).
+//   path_rows_stream   the streaming kernel, in one of two forms.  part == nullptr: phi (device float32 [m][F][D], ZEROED by the caller) receives the
+//                      contributions of the used columns.  part != nullptr (phi unused): part[(tile0 + j / 64) * 2 * n_used * D + k * n_used * D + s * D + d],
+//                      k = 0 the float64 sum over the tile's rows of slot s, output d, k = 1 of the absolute values (shap_core.h's tile rule).  false:
+//                      not taken -- D > 64, a model without streaming records, a tile too wide, a refused LDS opt-in -- and nothing was launched.
+//   path_rows_general  one thread per row into phi (zeroed by the caller), the same bytes (GBRL_HIP_PATH_GENERIC=1).  Always launches (m > 0).
+struct PathTables { const float *delta; const int32_t *used, *slot_of; int n_used; };
+bool path_rows_stream(const PredictModel &pm, const CodeTables &ct, const PathTables &pt, const CodeRows &cr, int F, int m, int n_trees, float *phi, double *part,
+                      int tile0, hipStream_t s);
+void path_rows_general(const PredictModel &pm, const CodeTables &ct, const float *delta, const CodeRows &cr, int F, int m, int n_trees, float *phi, hipStream_t s);
+//
 // The objectives on a prediction matrix (objective.hip): the device functions of the tails applied to pred [n][D] (device).  targets: float32
 // [n][D] (rmse, logistic) or int32 [n] (softmax; every label in [0, D): the caller checks, label_counts below).  grad_out (device [n][D]) and
 // loss_part (staged_loss_partials(n) doubles, one per 64 rows, finished by staged_loss_finish) may each be null.  D <= 128.

@@ -942,6 +942,42 @@ int gbrl_hip_shap_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset 
                                       double *sum_out /*host [n_features][output_dim]*/, double *abs_out /*likewise*/, int *chunk_rows_used /*may be NULL*/);
 int gbrl_hip_shap_sums_host(const float *phi /*host [n_rows][n_cols]*/, int64_t n_rows, int64_t n_cols, double *sum_out /*[n_cols]*/, double *abs_out /*[n_cols]*/);
 void gbrl_hip_shap_geometry(int n_features, int output_dim, int *tile_rows, int *default_chunk_rows, uint64_t *budget_bytes);
+/* Path attribution on a data set (new: XGBoost's approx_contribs on a Dataset; Saabas).  csrc/path_core.h has the rule, csrc/path_rows.hip the kernels.
+ *   the rule   For tree t and a leaf l of depth k with path nodes n_0 (root) .. n_k (the leaf), the condition at depth j testing feature f_j, and E(n) the
+ *              cover-weighted float64 mean of the leaf values below n (the cover of a leaf is the product of its edge weights, E of a leaf is its value):
+ *              delta[l][j][d] = fl32(-lr_d(t) * (E(n_{j+1})[d] - E(n_j)[d])), the product rounded once from float64, lr_d(t) the sum of the scheduler's
+ *              rates for tree t of the optimizers that own output d (0 without one): the units are the prediction's.  phi[r][f][d] is the float32 sum,
+ *              in tree order and then depth order, of delta[leaf_t(r)][j][d] over the trees t < n_trees and the depths j with f_j == f -- plain float32
+ *              adds.  expected[d] = bias[d] + sum_t -lr_d(t) * E(root_t)[d] in float64.  sum_f phi[r][f][d] + expected[d] is the prediction of the
+ *              trees [0, n_trees) up to float32 rounding.  It is NOT the SHAP value: a feature near the root is credited more, and the rule is not
+ *              consistent in Lundberg's sense; gbrl_hip_shap_importance_prepared has the exact answer at the SHAP recursion's cost.
+ *   gbrl_hip_path_contrib_prepared(m, ds, rows, rows_on_device, n_rows, n_trees, out, out_on_device)  on the model's device, from the data set's bin
+ *     codes.  rows as gbrl_hip_shap_prepared's; n_trees in [1, trees of the model], -1: all.  out: host or device float32
+ *     [n_rows][n_features][output_dim], overwritten: byte for byte gbrl_hip_path_contrib_host on the observations the codes were made from.
+ *   gbrl_hip_path_importance_prepared(m, ds, rows, rows_on_device, n_rows, n_trees, sum_out, abs_out, expected_out, passes_used)
+ *     sum_out / abs_out: host float64 [n_features][output_dim], that matrix reduced over the rows by the rule of gbrl_hip_shap_sums_host (tiles of 64
+ *     positions, sequential float64, one finishing launch); the bytes do not depend on rows == NULL against 0 .. n - 1, on the launches or on the feature
+ *     passes.  No float32 matrix is held: a tile's contributions live in LDS until they are reduced.  expected_out (may be NULL): float64 [output_dim].
+ *     *passes_used (may be NULL): the feature passes of the streaming kernel (gbrl_hip_path_geometry), 0 when the one-thread-per-row kernel ran.
+ *   Both are refused before the device is touched, GBRL_HIP_E_INVALID unless noted: what gbrl_hip_predict_continue_prepared refuses about the model, the
+ *     data set and rows (GBRL_HIP_E_UNSUPPORTED: a row-sharded model, a model with categorical columns, output_dim > 128, a tree the thresholds cannot
+ *     express); a model without trees; n_trees outside [1, n_trees] and not -1; a NULL result; a tree of the range that is no proper binary tree with a
+ *     split -- a greedy tree of one leaf among them (GBRL_HIP_E_UNSUPPORTED, the tree is named); for the matrix n_rows * n_features * output_dim >= 2^31
+ *     (GBRL_HIP_E_UNSUPPORTED).  Model and data set are left byte for byte as they were.
+ *   gbrl_hip_path_contrib_host(m, obs, n_rows, n_trees, out)  the rule with no device, on host float32 observations [n_rows][n_num_features], from the
+ *     host copy of the model; gbrl_hip_path_expected_host(m, n_trees, out) its expected value, float64 [output_dim].
+ *   gbrl_hip_path_geometry(n_used, n_features, output_dim, ...)  the streaming kernel's plan for n_used tested features: the slots (features) a pass keeps
+ *     in LDS, the passes (walks of the trees over a staged tile), the dynamic LDS bytes of a block; slots == 0: the shape takes the one-thread-per-row kernel.
+ *   Out of scope: categorical columns, interaction values, weighted means, a tree range other than a prefix, output_dim > 128. */
+int gbrl_hip_path_contrib_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows, int n_trees /*-1: all*/,
+                                   float *out /*[n_rows][n_features][output_dim]*/, int out_on_device);
+int gbrl_hip_path_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows, int n_trees /*-1: all*/,
+                                      double *sum_out /*host [n_features][output_dim]*/, double *abs_out /*likewise*/, double *expected_out /*host [output_dim], may be NULL*/,
+                                      int *passes_used /*may be NULL*/);
+int gbrl_hip_path_contrib_host(const gbrl_hip_model *m, const float *obs /*host [n_rows][n_num_features]*/, int n_rows, int n_trees /*-1: all*/,
+                               float *out /*host [n_rows][n_num_features][output_dim]*/);
+int gbrl_hip_path_expected_host(const gbrl_hip_model *m, int n_trees /*-1: all*/, double *out /*host [output_dim]*/);
+void gbrl_hip_path_geometry(int n_used, int n_features, int output_dim, int *slots, int *passes, uint64_t *lds_bytes);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
