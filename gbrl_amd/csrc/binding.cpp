@@ -423,6 +423,70 @@ py::object predict_continue_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
     return out.release(shape_of(b));
 }
 
+// Extension: predict_staged_prepared(ds, stops, rows=None) / staged_loss_prepared(ds, targets, stops=None, objective='rmse', alpha=None, weights=None,
+// eval_metric=None, rows=None): every ensemble prefix in one walk over a data set's bin codes (include/gbrl_hip.h).  stops as predict_staged takes
+// them, except that None means 0, 1, ..., n_trees (fit_prepared's validation curve); rows as predict_continue_prepared takes them.
+std::vector<int32_t> read_prepared_stops(py::object &stops_obj, int n_trees, const std::string &fn) {
+    if (!stops_obj.is_none()) return read_stops(stops_obj, n_trees);
+    if (n_trees == 0) fail(fn + ": the model has no trees (stops=None means 0, 1, ..., n_trees)");
+    std::vector<int32_t> stops(static_cast<size_t>(n_trees) + 1);
+    for (int k = 0; k <= n_trees; ++k) stops[k] = k;
+    return stops;
+}
+
+py::object predict_staged_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &stops_obj, py::object &rows) {
+    const std::string fn = "predict_staged_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
+    const std::vector<int32_t> stops = read_prepared_stops(stops_obj, md.n_trees, fn);
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, Input{});
+    const int64_t S = static_cast<int64_t>(stops.size()), m = r.m, D = md.output_dim;
+    if (S * m * D >= (int64_t(1) << 31)) fail(fn + ": n_stops x rows x output_dim >= 2^31 elements: pass fewer stops, or rows= to evaluate a subset");
+    std::vector<int64_t> shape;
+    if (D == 1) shape = {S, m}; else shape = {S, m, D};
+    Result<float> out(self, std::max<size_t>(static_cast<size_t>(S * m * D), 1));
+    {
+        py::gil_scoped_release release;
+        check(gbrl_hip_predict_staged_prepared(self.h, ds, r.ptr, r.on_device, r.m, stops.data(), static_cast<int>(S), out.get(), out.on_device()));
+    }
+    return out.release(shape);
+}
+
+py::dict staged_loss_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, py::object &stops_obj, const std::string &objective_name,
+                                   py::object alpha_obj, py::object &weights, py::object metric_obj, py::object &rows) {
+    const std::string fn = "staged_loss_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
+    const int objective = parse_objective(objective_name), D = md.output_dim;
+    if (objective == GBRL_HIP_OBJ_PAIRWISE || objective == GBRL_HIP_OBJ_LAMBDARANK)
+        fail(fn + ": the ranking objectives are not supported (their loss needs the query groups)");
+    const int metric = metric_obj.is_none() ? GBRL_HIP_METRIC_NONE : parse_metric(metric_obj.cast<std::string>());
+    if (metric == GBRL_HIP_METRIC_AUC)
+        fail(fn + ": eval_metric='auc' is not evaluated per stage (it needs a sort per stage): eval_metric on a stage of predict_staged_prepared gives it");
+    const std::vector<int32_t> stops = read_prepared_stops(stops_obj, md.n_trees, fn);
+    const std::vector<float> alpha = read_alpha(alpha_obj, D, fn);
+    Input first = read_objective_targets(targets, "targets", false, fn, objective, 0, D, false);
+    if (!first.ptr) fail("Cannot call " + fn + " without targets!");
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, first);
+    Input t = read_objective_targets(targets, "targets", false, fn, objective, r.m, D, true);
+    Input w = read_weights(weights, "weights", fn, r.m, true);
+    const py::ssize_t S = static_cast<py::ssize_t>(stops.size()), C = objective == GBRL_HIP_OBJ_SOFTMAX ? 1 : D;
+    py::array_t<double> loss(S), value(S);
+    py::array_t<int64_t> counts = objective == GBRL_HIP_OBJ_SOFTMAX ? py::array_t<int64_t>(S) : py::array_t<int64_t>(std::vector<py::ssize_t>{S, C});
+    {
+        py::gil_scoped_release release;
+        check(gbrl_hip_staged_loss_prepared(self.h, ds, r.ptr, r.on_device, r.m, t.ptr, t.on_device, objective, alpha.empty() ? nullptr : alpha.data(), w.f32(),
+                                            w.on_device, metric, stops.data(), static_cast<int>(S), loss.mutable_data(),
+                                            metric != GBRL_HIP_METRIC_NONE ? value.mutable_data() : nullptr,
+                                            metric != GBRL_HIP_METRIC_NONE ? counts.mutable_data() : nullptr));
+    }
+    py::dict out;
+    out["loss"] = loss;
+    out["stops"] = py::array_t<int32_t>(S, stops.data());
+    if (metric != GBRL_HIP_METRIC_NONE) { out["metric"] = value; out["counts"] = counts; }
+    return out;
+}
+
 // fit_prepared(ds, targets, iterations, valid=None, valid_targets=None, early_stopping_rounds=0, min_delta=0.0, subsample=1.0, colsample=1.0, seed=0,
 // objective='rmse', eval_metric=None, leaf_update='gradient', leaf_l2=1.0, weights=None, valid_weights=None): a float without a validation set (the three validation arguments at their defaults), else a dict; the other keywords go
 // with either.  A missing valid_targets is left to the C ABI's message.
@@ -1933,6 +1997,23 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     // extension: every ensemble prefix in one walk -- the prediction, or the MultiRMSE loss against targets, after every stops[s] trees
     g.def("predict_staged", &predict_staged_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("stops") = py::none());
     g.def("staged_loss", &staged_loss_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("stops") = py::none());
+    g.def("predict_staged_prepared", &predict_staged_prepared_impl, py::arg("ds"), py::arg("stops") = py::none(), py::arg("rows") = py::none(),
+          "predict_staged_prepared(ds, stops=None, rows=None) -> float32 [n_stops, m, D] ([n_stops, m] when D == 1)\n\n"
+          "Every prefix [0, stops[s]) of the ensemble in one walk over the data set's bin codes: stage s is byte for byte\n"
+          "predict_continue_prepared(ds, tile(bias), 0, stops[s], rows=rows) (stops[s] == 0: the bias alone, never 'all trees').  stops: strictly ascending\n"
+          "tree counts in [0, n_trees]; None means 0, 1, ..., n_trees.  rows as predict_continue_prepared takes them.  NumPy for a 'cpu' model, a DLPack\n"
+          "capsule for a 'cuda' one.  Refused: what predict_continue_prepared refuses, bad stops, n_stops * m * D >= 2^31 (pass fewer stops or rows=).");
+    g.def("staged_loss_prepared", &staged_loss_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("stops") = py::none(), py::arg("objective") = "rmse",
+          py::arg("alpha") = py::none(), py::arg("weights") = py::none(), py::arg("eval_metric") = py::none(), py::arg("rows") = py::none(),
+          "staged_loss_prepared(ds, targets, stops=None, objective='rmse', alpha=None, weights=None, eval_metric=None, rows=None) -> dict\n\n"
+          "The loss of every prefix [0, stops[s]) of the ensemble on a data set, in one walk over its bin codes.  'loss' (float64 [n_stops]) is in the units of\n"
+          "fit_prepared's valid_loss: rmse sqrt(0.5 S / m); logistic, softmax, quantile the mean row loss; with weights sum w L / W.  For a model that\n"
+          "fit_prepared(ds, y, T, valid=dsv, valid_targets=yv[, valid_weights=wv], objective=o) grew from empty, staged_loss_prepared(dsv, yv, None, o,\n"
+          "weights=wv)['loss'] equals that call's valid_loss bit for bit.  'stops' echoes the stops used (None: 0, 1, ..., n_trees).  eval_metric='error'\n"
+          "(logistic, softmax; not with weights) adds 'metric' (float64 [n_stops]) and 'counts' (int64 [n_stops], or [n_stops, D] for logistic).  targets,\n"
+          "alpha and weights as fit_prepared takes them; rows as predict_continue_prepared (targets and weights indexed by position).  Refused: what\n"
+          "predict_continue_prepared refuses, a model without trees when stops is None, bad stops, missing or misshapen targets, the ranking objectives,\n"
+          "eval_metric='auc' (eval_metric on a stage of predict_staged_prepared gives it), eval_metric with rmse, quantile or weights.");
     // extension: the leaf values of a tree range fitted again on new data, the structure kept; returns the loss of the refitted prefix
     g.def("refit_leaves", &refit_leaves_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("start_tree_idx") = 0,
           py::arg("stop_tree_idx") = 0, py::arg("decay_rate") = 0.0,

@@ -567,6 +567,26 @@ int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset
     });
 }
 
+int gbrl_hip_predict_staged_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
+                                     const int32_t *stops, int n_stops, float *out, int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("predict_staged_prepared");
+        m->engine.predict_staged_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, stops, n_stops, out, out_on_device != 0);
+    });
+}
+
+int gbrl_hip_staged_loss_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const void *targets,
+                                  int targets_on_device, int objective, const float *alpha, const float *weights, int weights_on_device, int metric,
+                                  const int32_t *stops, int n_stops, double *loss_out, double *metric_out, int64_t *counts_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("staged_loss_prepared");
+        m->engine.staged_loss_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, targets, targets_on_device != 0, objective, alpha, weights,
+                                       weights_on_device != 0, metric, stops, n_stops, loss_out, metric_out, counts_out);
+    });
+}
+
 // The one body of the eight gbrl_hip_fit_prepared* spellings.  valid_required (gbrl_hip_fit_prepared_valid): a NULL valid_ds is a null data set;
 // otherwise it means "no validation", the other validation arguments must then be at their defaults, *iterations_done = iterations and
 // *best_n_trees is left alone.  Every refusal that needs no data set comes before a handle is resolved, the validation handle before the

@@ -434,6 +434,20 @@ class Engine {
                         float *out, bool out_dev);
     void staged_loss(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num, int n_cat,
                      const int32_t *stops, int n_stops, double *loss_out);
+    // Extension: the same on a prepared data set (kern::predict_staged_codes), rows as predict_continue_prepared takes them (rows == nullptr: every
+    // row, m == ds->n; duplicates allowed; targets and weights indexed by position).  Neither the model nor the data set is written.
+    // predict_staged_prepared: out [n_stops][m][D] (device iff out_dev); stage s is, bit for bit, predict_continue_prepared(tiled bias, 0, stops[s]).
+    // staged_loss_prepared: loss_out[s] (host) in the units of fit_prepared's valid_loss -- mean_loss of the objective's row losses (with weights:
+    // sum w L / W), from the partials, butterfly and finishing sum of fit_prepared's validation tail: for a model fit_prepared grew from empty with
+    // this set as valid=, loss_out is its valid_loss bit for bit.  metric == kMetricError (logistic, softmax; never with weights): metric_out[s] and
+    // counts_out [n_stops][C] (C = 1 for softmax, D for logistic) are metric_core.h's value and integers of stage s.  Refused before the device is
+    // touched: what predict_continue_prepared refuses, bad stops, missing targets, what check_objective / check_alpha / check_metric refuse, the
+    // ranking objectives, kMetricAuc (Unsupported: it needs a sort per stage), a metric with weights (Unsupported), and for the predict form
+    // n_stops * m * D >= 2^31 (Unsupported).  A bad label or weight is refused behind the upload, before any kernel of the walk.
+    void predict_staged_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const int32_t *stops, int n_stops, float *out, bool out_dev);
+    void staged_loss_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const void *targets, bool targets_dev, int objective,
+                              const float *alpha, const float *weights, bool weights_dev, int metric, const int32_t *stops, int n_stops, double *loss_out,
+                              double *metric_out, int64_t *counts_out);
     // Extension: where a row lands.  For every tree t of [start_tree, stop_tree) the GLOBAL leaf index -- the row of `values`; minus tree_indices[t]
     // it is the index within the tree.  Oblivious: tree_indices[t] + sum_d pass(cond[t * max_depth + d]) << (depths[t] - 1 - d).  Greedy: the first
     // leaf in storage order from tree_indices[t] on whose conditions all hold (a depth-0 leaf never passes, Q7; -1 when the search runs off the
@@ -530,6 +544,8 @@ class Engine {
     void check_batch(const PredictBatch &b, bool has_result, bool width_limit);
     void check_dict_token(const PredictBatch &b);   // pre-encoded ids are valid only for the dictionary they were made from (host state: no device needed)
     void check_stops(const int32_t *stops, int n_stops) const;
+    // what predict_staged_prepared and staged_loss_prepared both refuse about the model, the data set, the stops and rows (noun: what has m rows)
+    void check_staged_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const int32_t *stops, int n_stops, const char *noun);
     int check_leaves_range(int start_tree, int stop_tree) const;   // predict_leaves / leaf_counts: the resolved stop of a range the ensemble holds
     int check_refit(int start_tree, int stop_tree, const float *targets, double decay_rate, const double *loss_out) const;   // likewise (engine_refit.hip)
     StagedBatch stage_batch(const PredictBatch &b);   // device, event pool, mirror; opens the `inputs` phase: observations up, ids checked and uploaded or cells encoded
@@ -831,6 +847,7 @@ class Engine {
     DevBuf d_leaves_out_, d_leaf_counts_;   // predict_leaves: indices bound for the host; leaf_counts: the uint32 counters
     DevBuf d_refit_p_, d_refit_leaf_, d_refit_acc_, d_refit_values_, d_refit_gmax_;   // refit_leaves: running prediction, leaf per row, int64 sums, new values, max |g| per tree
     DevBuf d_staged_stops_, d_staged_targets_, d_staged_part_, d_staged_sums_;   // predict_staged / staged_loss: stops table, staged targets, loss partials and sums
+    DevBuf d_staged_weights_, d_staged_cnt_, d_staged_counts_, d_staged_rows_;   // staged_loss_prepared: staged weights, count partials and counts, the widest general kernel's stored rows
     DevBuf m_tree_indices_, m_depths_, m_feature_indices_, m_feature_values_, m_values_, m_is_numerics_, m_ineq_,
         m_cat_ids_, m_bias_, m_opt_start_, m_opt_stop_, m_opt_lr_, m_cond_pack_, m_grd_nodes_, m_grd_off_, m_values_sw_, m_cond_ra_;
     DevBuf m_rate_;   // Linear schedules: rate[t][optimizer] for every tree (detail::RateTable).  Not built while every optimizer is Const.

@@ -4,6 +4,7 @@
 //   sync_code_tables                   device copies of the bins and of the mirror's packed conditions / greedy node records with the bin as
 //                                      their second word (appended like the originals: a loop that adds a tree per iteration converts that tree only)
 //   Engine::predict_continue_prepared  predict_continue without the observations (kern::predict_continue_codes)
+//   Engine::predict_staged_prepared / staged_loss_prepared   every prefix of the ensemble in one walk over the codes (kern::predict_staged_codes)
 //   read_back / subset_rows / resolve_tree / join_tail_phase   what the calls on a data set share (engine.h)
 //
 // The rule.  code(r, f) = #{b : thr[f][b] < obs[r, f]} (-0.0 == +0.0; NaN lies below every threshold: code 0).  For a condition x > v whose v
@@ -200,6 +201,103 @@ void Engine::predict_continue_prepared(const PreparedDataset *ds, const int32_t 
     kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, start_tree, stop, dbase, dout,
                                  nullptr, nullptr, nullptr, nullptr, hooks::on(hooks::CONTINUE_GENERIC), stream_);
     finish("predict_continue_prepared launch", "predict", {{out_dev ? nullptr : out, dout, out_bytes, "D2H preds"}});
+}
+
+// Extension: every prefix [0, stops[s]) of the ensemble in one walk over the data set's codes (kern::predict_staged_codes).  The refusals that both
+// forms share, in predict_continue_prepared's order; the walked range is [0, last stop).
+void Engine::check_staged_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const int32_t *stops, int n_stops,
+                                   const char *noun) {
+    check_prepared_dataset(what, ds);
+    if (model.meta.output_dim > 128) throw Unsupported("predict: output_dim > 128");
+    check_stops(stops, n_stops);
+    check_row_count(what, noun, rows, m, ds->n, "evaluate");
+    if (rows != nullptr && !rows_dev) check_host_rows(rows, m, ds->n);
+    check_code_range(*ds, what, 0, stops[n_stops - 1]);
+}
+
+void Engine::predict_staged_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const int32_t *stops, int n_stops, float *out,
+                                     bool out_dev) {
+    const char *what = "predict_staged_prepared";
+    if (out == nullptr) throw InvalidArgument(std::string(what) + ": no place for the result");
+    check_staged_prepared(what, ds, rows, rows_dev, m, stops, n_stops, "the call");
+    const int D = model.meta.output_dim;
+    if (static_cast<int64_t>(n_stops) * m * D >= (int64_t(1) << 31))
+        throw Unsupported(std::string(what) + ": n_stops x rows x output_dim >= 2^31 elements: pass fewer stops, or rows= to evaluate a subset");
+    ensure_device();
+    reset_events();
+    sync_model_to_device();
+    phase_begin();
+    const kern::CodeTables ct = sync_code_tables(*ds);
+    const int32_t *d_rows = subset_rows(ds, rows, rows_dev, m);
+    const kern::StagedStops dstops = stage_stops(stops, n_stops);
+    const size_t out_bytes = sizeof(float) * static_cast<size_t>(n_stops) * m * D;
+    float *dout = out_dev ? out : static_cast<float *>(d_pout_.ensure(out_bytes));
+    phase_end("inputs"); phase_begin(/*key=*/true);
+    kern::StagedCodesOut o{};
+    o.out = dout;
+    kern::predict_staged_codes(mirror_view(), ct, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, dstops, o, kern::kObjRmse,
+                               hooks::on(hooks::STAGED_GENERIC), stream_);
+    finish("predict_staged_prepared launch", "predict", {{out_dev ? nullptr : out, dout, out_bytes, "D2H preds"}});
+}
+
+void Engine::staged_loss_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const void *targets, bool targets_dev, int objective,
+                                  const float *alpha, const float *weights, bool weights_dev, int metric, const int32_t *stops, int n_stops, double *loss_out,
+                                  double *metric_out, int64_t *counts_out) {
+    const char *what = "staged_loss_prepared";
+    const std::string w(what);
+    if (targets == nullptr) throw InvalidArgument("Cannot call " + w + " without targets!");
+    if (loss_out == nullptr) throw InvalidArgument(w + ": no place for the result");
+    check_staged_prepared(what, ds, rows, rows_dev, m, stops, n_stops, "targets");
+    const int D = model.meta.output_dim;
+    check_objective(what, objective, D);
+    check_alpha(what, objective, alpha, D, weights != nullptr);
+    if (metric != kern::kMetricNone) {
+        check_metric(what, objective, metric);
+        if (metric == kern::kMetricAuc)
+            throw Unsupported(w + ": auc is not evaluated per stage (it needs a sort per stage): eval_metric on a stage of predict_staged_prepared gives it");
+        if (weights != nullptr)
+            throw Unsupported(w + ": weights with eval_metric is not supported (the metrics count rows; weighted metrics are not implemented)");
+        if (metric_out == nullptr || counts_out == nullptr) throw InvalidArgument(w + ": no place for the metric");
+    }
+    ensure_device();
+    reset_events();
+    sync_model_to_device();
+    phase_begin();
+    const kern::CodeTables ct = sync_code_tables(*ds);
+    const int32_t *d_rows = subset_rows(ds, rows, rows_dev, m);
+    const kern::StagedStops dstops = stage_stops(stops, n_stops);
+    const size_t tar_el = objective == kern::kObjSoftmax ? static_cast<size_t>(m) : static_cast<size_t>(m) * D;
+    const float *dt = staged(d_staged_targets_, static_cast<const float *>(targets), targets_dev, tar_el, "H2D targets");
+    if (objective == kern::kObjSoftmax) check_labels(what, reinterpret_cast<const int32_t *>(dt), m, D, nullptr);
+    const float *dw = weights ? staged(d_staged_weights_, weights, weights_dev, static_cast<size_t>(m), "H2D weights") : nullptr;
+    const double W = dw ? check_weights("staged_loss_prepared (weights)", dw, m, true).sum : static_cast<double>(m);
+    const int nb = kern::staged_loss_partials(m), C = kern::metric_count_columns(objective == kern::kObjSoftmax, D);
+    kern::StagedCodesOut o{};
+    o.targets = dt; o.weights = dw;
+    o.alpha = alpha ? upload(d_lq_alpha_, alpha, static_cast<size_t>(D), "H2D levels") : nullptr;
+    o.part = static_cast<double *>(d_staged_part_.ensure(sizeof(double) * static_cast<size_t>(n_stops) * nb));
+    o.sums = static_cast<double *>(d_staged_sums_.ensure(sizeof(double) * n_stops));
+    if (metric != kern::kMetricNone) {
+        o.cnt_part = static_cast<unsigned long long *>(d_staged_cnt_.ensure(sizeof(unsigned long long) * static_cast<size_t>(n_stops) * C * nb));
+        o.counts = static_cast<unsigned long long *>(d_staged_counts_.ensure(sizeof(unsigned long long) * static_cast<size_t>(n_stops) * C));
+    }
+    if (const size_t stored = kern::staged_codes_row_scratch(m, D, objective))
+        o.row_scratch = static_cast<float *>(d_staged_rows_.ensure(sizeof(float) * stored));
+    phase_end("inputs"); phase_begin(/*key=*/true);
+    kern::predict_staged_codes(mirror_view(), ct, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, dstops, o, objective,
+                               hooks::on(hooks::STAGED_GENERIC), stream_);
+    std::vector<double> sums(n_stops);
+    std::vector<unsigned long long> counts(o.counts ? static_cast<size_t>(n_stops) * C : 0);
+    finish("staged_loss_prepared launch", "predict", {{sums.data(), o.sums, sizeof(double) * n_stops, "D2H loss sums"},
+                                                     {counts.empty() ? nullptr : counts.data(), o.counts, sizeof(unsigned long long) * counts.size(), "D2H metric counters"}});
+    for (int i = 0; i < n_stops; ++i) loss_out[i] = mean_loss(objective, sums[i], W);
+    if (o.counts == nullptr) return;
+    const uint64_t cells = static_cast<uint64_t>(m) * (objective == kern::kObjSoftmax ? 1 : D);
+    for (int i = 0; i < n_stops; ++i) {
+        const std::vector<uint64_t> c = metric_counts(metric, C, counts.data() + static_cast<size_t>(i) * C, nullptr, m);
+        metric_out[i] = kern::metric_value(metric, c.data(), C, cells);
+        for (int d = 0; d < C; ++d) counts_out[static_cast<size_t>(i) * C + d] = static_cast<int64_t>(c[d]);
+    }
 }
 
 }  // namespace gbrl

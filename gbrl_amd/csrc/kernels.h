@@ -802,6 +802,27 @@ void loss_partials_of_predictions(const float *preds, const float *targets, int 
 void staged_loss_finish(const double *part, int nb, double *sum, hipStream_t s);
 // ... of n_rows vectors of nb partials each, part[r][0 .. nb) -> sums[r]: the same kernel, one block per vector (predict_staged's own finishing launch)
 void staged_loss_finish_rows(const double *part, int nb, int n_rows, double *sums, hipStream_t s);
+// Every prefix in one walk over a prepared data set's bin codes (predict_staged_codes.hip): predict_staged's checkpoints on predict_continue_codes'
+// rows.  Row j of the call is CodeRows' row j; targets / weights are indexed by j.  All pointers are device pointers.
+//   predict mode (out != nullptr)      out[s][j][d], [n_stops][m][D]: stage s has the bits of predict_continue_codes(tiled bias, 0, stops[s]).
+//   loss mode (out == nullptr)         sums[s] = the sum of the objective's row losses (times (double)w with weights) in the loss tail's fixed order:
+//                                      part is scratch for n_stops x staged_loss_partials(m) doubles.  targets: float32 [m][D], or int32 [m] behind
+//                                      the pointer (kObjSoftmax); alpha: the D levels (kObjQuantile, never with weights).
+//   metric mode (counts != nullptr)    also counts[s][c] = the wrong rows (kObjSoftmax, C = 1) or the wrong cells of output c (kObjLogistic, C = D)
+//                                      of stage s, metric_core.h's integers; cnt_part is scratch for n_stops x C x staged_loss_partials(m) integers.
+//                                      Never with weights.
+// row_scratch: staged_codes_row_scratch(m, D, objective) floats in the loss modes (0: not read; else [m][D] -- the widest general kernel sums
+// logistic and quantile losses from the stored row; the kernel's own condition).  generic: the one-thread-per-row kernel only (GBRL_HIP_STAGED_GENERIC=1; same bytes in every mode).  Always launches (m > 0).
+struct StagedCodesOut {
+    float *out;
+    const float *targets, *weights, *alpha;
+    double *part, *sums;
+    unsigned long long *cnt_part, *counts;
+    float *row_scratch;
+};
+size_t staged_codes_row_scratch(int m, int D, int objective);
+void predict_staged_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, const StagedStops &st, const StagedCodesOut &o, int objective,
+                          bool generic, hipStream_t s);
 // Where a row lands (predict_leaves.hip): the GLOBAL leaf index -- the row of `values` -- that each tree of [start_tree, stop_tree) routes a row to.
 // Oblivious: tree_indices[t] + the bits of the tree's conditions.  Greedy: the first leaf in storage order from tree_indices[t] on whose conditions
 // all hold; a depth-0 leaf never passes (Q7), and -1 when the search runs off the ensemble.  No leaf value is read: no limit on output_dim.

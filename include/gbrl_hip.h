@@ -1010,6 +1010,35 @@ int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset
 int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
                           float *loss_out);
 
+/* ---- every ensemble prefix on a prepared data set (new) ------------------------------------------------ */
+/* gbrl_hip_predict_staged / gbrl_hip_staged_loss with the row read from a data set's bin codes, and with the objectives of gbrl_hip_fit_prepared.
+ * `stops` (host, n_stops > 0): strictly ascending tree counts k, 0 <= k <= n_trees; k == 0 is the bias alone, never "all trees".  rows / rows_on_device
+ * / n_rows as gbrl_hip_predict_continue_prepared takes them (rows == NULL: every row, n_rows == the data set's; duplicates allowed; targets and
+ * weights are indexed by position).  Neither the model nor the data set is written.
+ *   gbrl_hip_predict_staged_prepared: out is float32 [n_stops][n_rows][output_dim], device iff out_on_device.  Stage s is, bit for bit,
+ *     gbrl_hip_predict_continue_prepared(base = the tiled bias, 0, stops[s]) (for stops[s] == 0: the tiled bias).
+ *   gbrl_hip_staged_loss_prepared: loss_out (host, n_stops doubles) in the units of gbrl_hip_fit_prepared's validation loss -- rmse:
+ *     sqrt(0.5 * S / n_rows); logistic, softmax, quantile: the mean row loss; with weights (float32 [n_rows], nullable): sum w L / W.  The row loss,
+ *     the wave reduction over 64 consecutive positions, the fixed-order finishing sum and the final float64 expression are those of the validation
+ *     tail: for a model that gbrl_hip_fit_prepared* grew from empty with this data set (targets, weights) as its validation set, loss_out with
+ *     stops = 0 .. n_trees is that call's validation curve, bit for bit.  targets: float32 [n_rows][output_dim], or int32 [n_rows] labels
+ *     (GBRL_HIP_OBJ_SOFTMAX); alpha: the output_dim levels of GBRL_HIP_OBJ_QUANTILE (NULL otherwise).  metric == GBRL_HIP_METRIC_ERROR (logistic,
+ *     softmax): metric_out (host, n_stops doubles) and counts_out (host, int64 [n_stops][C], C = 1 for softmax, output_dim for logistic) are the
+ *     error rate and its integers of every stage ("Classifier metrics"); metric == GBRL_HIP_METRIC_NONE: both may be NULL.
+ *     Two calls return identical bytes.
+ *   Refused before the device is touched, GBRL_HIP_E_INVALID unless noted: what gbrl_hip_predict_continue_prepared refuses about the model, the data
+ *     set and rows (GBRL_HIP_E_UNSUPPORTED: a model with a communicator, categorical columns, output_dim > 128, a tree the thresholds cannot
+ *     express -- named in the message); empty, descending or out-of-range stops; NULL targets or outputs; an unknown or ranking objective; an alpha
+ *     or weights that gbrl_hip_fit_prepared refuses (GBRL_HIP_E_UNSUPPORTED: weights with the quantile objective); a metric with rmse or quantile;
+ *     GBRL_HIP_METRIC_AUC and a metric with weights (GBRL_HIP_E_UNSUPPORTED); n_stops * n_rows * output_dim >= 2^31 for the predict form
+ *     (GBRL_HIP_E_UNSUPPORTED: pass fewer stops, or rows).  A label outside [0, output_dim) or a bad weight is refused behind its upload. */
+int gbrl_hip_predict_staged_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
+                                     const int32_t *stops, int n_stops, float *out, int out_on_device);
+int gbrl_hip_staged_loss_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
+                                  const void *targets, int targets_on_device, int objective, const float *alpha, const float *weights,
+                                  int weights_on_device, int metric, const int32_t *stops, int n_stops, double *loss_out, double *metric_out,
+                                  int64_t *counts_out);
+
 /* ---- row-sharded multi-GPU (new; the reference is single-GPU) ------------------------------------------ */
 /* One process per GPU, each holding a contiguous block of rows.  When hooks are installed, step() calls them at
  * its exchange points so that every rank grows the identical tree; predict() needs no exchange.  Buffers are
