@@ -122,6 +122,46 @@ double refit_leaves_impl(PyGBRL &self, py::object &obs, py::object &cat, py::obj
     return loss;
 }
 
+// Extension: refit_leaves_prepared(ds, targets, start_tree_idx=0, stop_tree_idx=0, decay_rate=0.0, objective='rmse', leaf_update='gradient', leaf_l2=0.0,
+// weights=None) -> {'loss': float, 'values': float32 [leaves of the range, D], 'counts': int64 [leaves of the range], 'bits': int}: refit_leaves on a
+// prepared data set, with fit_prepared's objectives, leaf rules and row weights (include/gbrl_hip.h).
+py::dict refit_leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &targets, py::object start_obj, py::object stop_obj, double decay,
+                                    const std::string &objective_name, const std::string &leaf_update_name, double leaf_l2, py::object &weights) {
+    const std::string fn = "refit_leaves_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
+    const int objective = parse_objective(objective_name), leaf_update = parse_leaf_update(leaf_update_name), D = md.output_dim;
+    if (objective == GBRL_HIP_OBJ_PAIRWISE || objective == GBRL_HIP_OBJ_LAMBDARANK) fail(fn + ": the ranking objectives are not supported (they need the query groups)");
+    const auto [start, stop] = read_tree_range(start_obj, stop_obj);
+    const int n = ds ? dataset_info(ds_obj).n_rows : 0;
+    Input t = read_objective_targets(targets, "targets", false, fn, objective, n, D, ds != nullptr);
+    if (!t.ptr) fail("Cannot call " + fn + " without targets!");
+    Input w = read_weights(weights, "weights", fn, n, ds != nullptr);
+    // the leaves of the range, for the result arrays (a range the call refuses gets room for nothing)
+    const int T = md.n_trees, last = stop == 0 ? T : stop;
+    py::ssize_t leaves = 0;
+    if (T > 0 && start >= 0 && start < last && last <= T) {
+        std::vector<int32_t> ti(static_cast<size_t>(T));
+        check(gbrl_hip_get_ensemble(self.h, ti.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+        leaves = (last < T ? ti[last] : md.n_leaves) - ti[start];
+    }
+    py::array_t<float> values({leaves, static_cast<py::ssize_t>(D)});
+    py::array_t<int64_t> counts(std::vector<py::ssize_t>{leaves});
+    double loss = 0.0;
+    int bits = 0;
+    {
+        py::gil_scoped_release release;
+        check(gbrl_hip_refit_leaves_prepared(self.h, ds, t.ptr, t.on_device, start, stop, decay, objective, leaf_update, leaf_l2, w.f32(), w.on_device, &loss,
+                                             values.mutable_data(), counts.mutable_data(), &bits));
+    }
+    py::dict out;
+    out["loss"] = py::float_(loss);
+    out["values"] = values;
+    out["counts"] = counts;
+    out["bits"] = py::int_(bits);
+    return out;
+}
+
 // Extension: predict_leaves(obs, categorical_obs, start, stop) / leaf_counts(...) and their _encoded variants (obs, ids, token, start, stop): where
 // a row lands (include/gbrl_hip.h).  predict_leaves returns int32 [n, stop - start] global leaf indices -- NumPy for a "cpu" model, a DLPack
 // capsule on the model's device for a "cuda" one; leaf_counts returns int64 NumPy [n_leaves], the rows of the batch per global leaf.
@@ -2022,6 +2062,18 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "New value = decay_rate * old + (1 - decay_rate) * the leaf mean of fit()'s MultiRMSE gradient; a leaf without rows keeps its value.\n"
           "Returns staged_loss(obs, categorical_obs, targets, stops=[stop_tree_idx])[0] of the refitted model.  Trees behind stop_tree_idx are not\n"
           "touched and are stale with respect to the new prefix.");
+    g.def("refit_leaves_prepared", &refit_leaves_prepared_impl, py::arg("ds"), py::arg("targets"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0,
+          py::arg("decay_rate") = 0.0, py::arg("objective") = "rmse", py::arg("leaf_update") = "gradient", py::arg("leaf_l2") = 0.0, py::arg("weights") = py::none(),
+          "refit_leaves_prepared(ds, targets, start_tree_idx=0, stop_tree_idx=0, decay_rate=0.0, objective='rmse', leaf_update='gradient', leaf_l2=0.0,\n"
+          "                      weights=None) -> dict\n\n"
+          "refit_leaves on a prepared data set: the leaf values of the trees [start_tree_idx, stop_tree_idx) fitted again on ds, the structure kept, the whole\n"
+          "range in one enqueue.  leaf_update='gradient' (rmse, logistic, softmax): the leaf mean of the objective's gradient, refit_leaves' rule -- with rmse and\n"
+          "no weights the bytes of refit_leaves(X, None, Y) for the X behind ds.  leaf_update='newton' (logistic, softmax): newton_leaves_prepared's value per\n"
+          "tree in one quantum -- with decay_rate == 0 the loop newton_leaves_prepared(tree=t) -> predict_continue_prepared(t, t + 1), byte for byte.\n"
+          "New value = decay_rate * old + (1 - decay_rate) * value.  Returns 'loss' (staged_loss_prepared(ds, targets, [stop], objective, weights=)['loss'][0] of\n"
+          "the refitted model), 'values' float32 [leaves of the range, D], 'counts' int64 [leaves of the range] and 'bits' (the newton quantum; the first tree's\n"
+          "gradient quantum).  Refused with the model unchanged: what predict_continue_prepared, refit_leaves and fit_prepared refuse, the quantile and\n"
+          "ranking objectives, and a run that meets a non-finite gradient or prediction or (newton) a logistic target outside [0, 1].");
     g.def("fit", &fit_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("iterations"),
           py::arg("shuffle") = true, py::arg("loss_type") = "MultiRMSE");
     g.def("set_bias", [](PyGBRL &self, py::object &bias) {

@@ -576,6 +576,17 @@ int gbrl_hip_predict_staged_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *
     });
 }
 
+int gbrl_hip_refit_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int start_tree, int stop_tree,
+                                   double decay_rate, int objective, int leaf_update, double leaf_l2, const float *weights, int weights_on_device,
+                                   double *loss_out, float *values_out, int64_t *counts_out, int *bits_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("refit_leaves_prepared");
+        m->engine.refit_leaves_prepared(&live_dataset(ds), targets, targets_on_device != 0, start_tree, stop_tree, decay_rate, objective, leaf_update, leaf_l2, weights,
+                                        weights_on_device != 0, loss_out, values_out, counts_out, bits_out);
+    });
+}
+
 int gbrl_hip_staged_loss_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const void *targets,
                                   int targets_on_device, int objective, const float *alpha, const float *weights, int weights_on_device, int metric,
                                   const int32_t *stops, int n_stops, double *loss_out, double *metric_out, int64_t *counts_out) {

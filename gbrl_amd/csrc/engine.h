@@ -470,6 +470,15 @@ class Engine {
     // depth 0 among the trees [start_tree - 1, stop_tree) (the prediction walks past it into values that are not refitted yet).
     void refit_leaves(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const float *targets, bool targets_dev, int n, int n_num, int n_cat,
                       int start_tree, int stop_tree, double decay_rate, double *loss_out);
+    // Extension: refit_leaves on a prepared data set, for the objectives and leaf rules of fit_prepared (kern::refit_leaves_codes; include/gbrl_hip.h has
+    // the contract).  targets: float32 [ds->n][D] (rmse, logistic) or int32 [ds->n] (softmax); weights: nullable float32 [ds->n].  leaf_update gradient:
+    // refit_leaves' mean of the objective's gradient; newton (logistic, softmax): newton_leaves_prepared's value per tree, in ONE quantum
+    // newton_sum_bits(n, largest weight).  values_out [leaves of the range][D], counts_out [leaves of the range], *bits_out (the Newton quantum; the
+    // gradient quantum of the first tree), *loss_out = staged_loss_prepared(ds, targets, {stop}, objective, weights) of the refitted model.  One
+    // enqueue for the whole range and one wait; every refusal comes before anything changes and after any failure the model is unchanged.
+    void refit_leaves_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int start_tree, int stop_tree, double decay_rate, int objective,
+                               int leaf_update, double leaf_l2, const float *weights, bool weights_dev, double *loss_out, float *values_out, int64_t *counts_out,
+                               int *bits_out);
     // GBRL::fit (gbrl.cpp:983-1104) + Fitter::fit_cpu (fitter.cpp:117-261): bias = mean(targets), split candidates from the
     // WHOLE data set once, then `iterations` boosting rounds over consecutive batches of metadata.batch_size rows
     // (predict -> MultiRMSE gradients -> one tree per batch); returns the final MultiRMSE loss on the whole data set.
@@ -845,6 +854,7 @@ class Engine {
     // ---- predict workspace + device mirror of the ensemble ----
     DevBuf d_pobs_, d_pcat_, d_pout_;
     DevBuf d_leaves_out_, d_leaf_counts_;   // predict_leaves: indices bound for the host; leaf_counts: the uint32 counters
+    DevBuf d_refit_counts_, d_refit_weights_;   // refit_leaves_prepared: rows per leaf, staged weights (the rest are refit_leaves' buffers)
     DevBuf d_refit_p_, d_refit_leaf_, d_refit_acc_, d_refit_values_, d_refit_gmax_;   // refit_leaves: running prediction, leaf per row, int64 sums, new values, max |g| per tree
     DevBuf d_staged_stops_, d_staged_targets_, d_staged_part_, d_staged_sums_;   // predict_staged / staged_loss: stops table, staged targets, loss partials and sums
     DevBuf d_staged_weights_, d_staged_cnt_, d_staged_counts_, d_staged_rows_;   // staged_loss_prepared: staged weights, count partials and counts, the widest general kernel's stored rows

@@ -1,7 +1,10 @@
 // engine_refit.hip -- GBRL::refit_leaves (see engine.h).  The call goes through the stages of engine_predict.hip like every predict-family call; what
-// is its own is the order of its checks, its kernels, its three read-backs and the booking of the new values.
-#include "engine.h"
+// is its own is the order of its checks, its kernels, its three read-backs and the booking of the new values.  GBRL::refit_leaves_prepared is the
+// same call on a prepared data set, with fit_prepared's objectives, leaf rules and row weights (kern::refit_leaves_codes).
+#include "engine_codes_detail.h"
 #include "hooks.h"
+#include "newton_core.h"
+#include "quantile_core.h"
 
 #include <algorithm>
 #include <cmath>
@@ -82,6 +85,90 @@ void Engine::refit_leaves(const float *obs, bool obs_dev, const char *cat, bool 
     ++model.version;
     invalidate_mirror();
     *loss_out = std::sqrt(0.5 * sum / static_cast<double>(n));   // staged_loss's expression
+}
+
+// Extension: the same on a prepared data set (kern::refit_leaves_codes).  Every refusal that needs no device comes first, then the targets and
+// weights are staged and checked (labels, weights: fit_prepared's refusals); the model is written after the one wait, when every tree's word is clean.
+void Engine::refit_leaves_prepared(const PreparedDataset *ds, const void *targets, bool targets_dev, int start_tree, int stop_tree, double decay_rate, int objective,
+                                   int leaf_update, double leaf_l2, const float *weights, bool weights_dev, double *loss_out, float *values_out, int64_t *counts_out,
+                                   int *bits_out) {
+    const char *what = "refit_leaves_prepared";
+    const gbrl_hip_metadata &md = model.meta;
+    const int D = md.output_dim;
+    check_prepared_dataset(what, ds);
+    if (D > 128) throw Unsupported("refit_leaves_prepared: output_dim > 128");
+    const int stop = check_refit(start_tree, stop_tree, static_cast<const float *>(targets), decay_rate, loss_out);
+    check_objective(what, objective, D);
+    if (objective == kern::kObjQuantile || leaf_update == kern::kLeafQuantile)
+        throw Unsupported("refit_leaves_prepared: the quantile objective and quantile leaf values are not supported (gradient or newton leaves of rmse, logistic, softmax)");
+    check_leaf_update(what, objective, leaf_update, leaf_l2);
+    check_code_range(*ds, what, 0, stop);
+    const bool newton = leaf_update == kern::kLeafNewton;
+    const int n = ds->n;
+    ensure_device();
+    reset_events();
+    sync_model_to_device();
+    phase_begin();
+    const kern::CodeTables ct = sync_code_tables(*ds);
+    const size_t tar_el = objective == kern::kObjSoftmax ? static_cast<size_t>(n) : static_cast<size_t>(n) * D;
+    const float *dt = staged(d_staged_targets_, static_cast<const float *>(targets), targets_dev, tar_el, "H2D targets");
+    if (objective == kern::kObjSoftmax) check_labels(what, reinterpret_cast<const int32_t *>(dt), n, D, nullptr);
+    const float *dw = weights ? staged(d_refit_weights_, weights, weights_dev, static_cast<size_t>(n), "H2D weights") : nullptr;
+    const WeightStats ws = dw ? check_weights("refit_leaves_prepared (weights)", dw, n, true) : WeightStats{0.0f, static_cast<double>(n)};
+    phase_end("inputs"); phase_begin(/*key=*/true);
+    hipStream_t s = stream_;
+    // the whole range is ONE enqueue: accumulators and the trees' words are zeroed once, nothing is read back between the trees, the host waits once
+    const size_t T = static_cast<size_t>(stop - start_tree);
+    const size_t l0 = model.first_leaf(start_tree), l1 = stop < md.n_trees ? model.first_leaf(stop) : static_cast<size_t>(md.n_leaves);
+    const size_t NL = l1 - l0, W = (newton ? 2 : 1) * static_cast<size_t>(D) + 1, L = static_cast<size_t>(md.n_leaves);
+    float *dP = static_cast<float *>(d_refit_p_.ensure(sizeof(float) * static_cast<size_t>(n) * D));
+    unsigned long long *dacc = zeroed<unsigned long long>(d_refit_acc_, NL * W, "zero leaf sums");
+    uint32_t *dslots = zeroed<uint32_t>(d_refit_gmax_, T, "zero tree words");
+    float *dvals = static_cast<float *>(d_refit_values_.ensure(sizeof(float) * L * D));
+    long long *dcounts = static_cast<long long *>(d_refit_counts_.ensure(sizeof(long long) * NL));
+    const int nb = kern::staged_loss_partials(n);
+    double *dpart = static_cast<double *>(d_staged_part_.ensure(sizeof(double) * nb));
+    double *dsum = static_cast<double *>(d_staged_sums_.ensure(sizeof(double)));
+    const kern::PredictModel pm = mirror_view();
+    hip_check(hipMemcpyAsync(dvals, pm.values, sizeof(float) * L * D, hipMemcpyDeviceToDevice, s), "D2D leaf values");
+    const int nbits = newton ? (dw ? kern::newton_sum_bits(n, ws.max) : kern::newton_sum_bits(n)) : 0;
+    const int streamed = kern::refit_leaves_codes(pm, ct, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), nullptr, 0}, model.tree_indices.data(), n, start_tree, stop,
+                                                  objective, newton, nbits, leaf_l2, decay_rate, dt, dw, dP, dacc, dvals, dcounts, dslots, dpart, hooks::on(hooks::CONTINUE_GENERIC), s);
+    kern::staged_loss_finish(dpart, nb, dsum, s);
+    std::vector<float> hvals(NL * D);
+    std::vector<long long> hcounts(NL);
+    std::vector<uint32_t> hslots(T);
+    double sum = 0.0;
+    finish("refit_leaves_prepared launch", "refit", {{hvals.data(), dvals + l0 * D, sizeof(float) * NL * D, "D2H refitted values"},
+                                                     {hcounts.data(), dcounts, sizeof(long long) * NL, "D2H leaf counts"},
+                                                     {hslots.data(), dslots, sizeof(uint32_t) * T, "D2H tree words"},
+                                                     {&sum, dsum, sizeof(double), "D2H loss sum"}});
+    if (profiling_) phases_.emplace_back("refit_streamed_trees", static_cast<float>(streamed));   // (not a time: trees whose sums the streaming kernel took)
+    for (size_t i = 0; i < T; ++i) {
+        const std::string tree = "refit_leaves_prepared: tree " + std::to_string(start_tree + static_cast<int>(i));
+        if (newton && (hslots[i] & kern::kNewtonBadTarget))
+            throw InvalidArgument(tree + ": a logistic target is outside [0, 1] (or NaN): newton leaf values need targets in [0, 1]; the model is unchanged");
+        if (newton && (hslots[i] & kern::kNewtonBadPred)) throw InvalidArgument(tree + ": a prediction is not finite: no newton leaf values; the model is unchanged");
+        if (!newton && hslots[i] >= 0x7f800000u)
+            throw InvalidArgument(tree + ": the gradient is not finite (non-finite targets or an overflowing prediction); the model is unchanged");
+    }
+    if (!std::isfinite(sum)) throw InvalidArgument("refit_leaves_prepared: the loss of the final prediction is not finite (non-finite targets or an overflowing prediction); the model is unchanged");
+    std::copy(hvals.begin(), hvals.end(), model.values.begin() + static_cast<long>(l0 * D));
+    ++model.version;
+    invalidate_mirror();
+    *loss_out = detail::mean_loss(objective, sum, ws.sum);
+    if (values_out) std::copy(hvals.begin(), hvals.end(), values_out);
+    if (counts_out) std::copy(hcounts.begin(), hcounts.end(), counts_out);
+    if (bits_out) {
+        *bits_out = nbits;
+        float gmax;
+        std::memcpy(&gmax, &hslots[0], sizeof(gmax));
+        if (!newton) {   // kernels_common.h's leaf_sum_bits_dev on the host: the quantum the first tree was summed in
+            int e = 0;
+            if (gmax > 0.0f) (void)std::frexp(4.0e18 / (static_cast<double>(n) * gmax), &e);
+            *bits_out = gmax > 0.0f ? std::min(60, e - 2) : 40;
+        }
+    }
 }
 
 }  // namespace gbrl

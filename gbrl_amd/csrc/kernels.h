@@ -856,6 +856,26 @@ void leaf_counts(const PredictModel &pm, const int32_t *tree_first_leaf, const f
 int refit_leaves(const PredictModel &pm, const int32_t *tree_first_leaf, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree,
                  int stop_tree, double decay, const float *targets, float *P, int32_t *leaf_idx, unsigned long long *acc, float *new_values,
                  uint32_t *gmax, bool generic, hipStream_t s);
+// The same on a prepared data set's bin codes, for an objective's gradient mean or its Newton step (refit_codes.hip).  Everything is enqueued on `s`;
+// nothing is read back and the host never waits.  Per tree t, in order, P = predict_continue_codes(tiled bias, 0, t) over the new values so far:
+//   newton     acc[leaf][2 D + 1] += (q(g)[D], q(h)[D], 1), q(x) = llrint((double)x * 2^bits) (newton_leaf_sums' integers; bits = newton_sum_bits(n,
+//              weight_max), the caller's); the value is newton_leaf_value(..., leaf_l2, old).  slots[t - start] collects kNewtonBadPred / kNewtonBadTarget.
+//   gradient   slots[t - start] = the bits of max |g| (a prediction that is not finite: +inf), acc[leaf][D + 1] += (q(g)[D], 1) in the quantum
+//              leaf_sum_bits_dev(n, max |g|); the value is refit_leaves' (sum / 2^lbits / count).  `bits` and leaf_l2 are not read.
+//   both       g (and h) are the objective's (kObjRmse, kObjLogistic: targets float32 [n][D]; kObjSoftmax: int32 labels [n], checked by the caller), times
+//              the row's weight (weights nullable, device float32 [n]) as fl32(w * g); the value is mixed as decay * old + (1 - decay) * value when
+//              decay != 0; a leaf without rows, a leaf of depth 0 (and a Newton leaf whose denominator is not positive) keep the old value.
+//   P           [n][D]      scratch; on return the prediction of the refitted ensemble over [0, stop_tree)
+//   acc         [leaves of the range][W] int64, W = 2 D + 1 or D + 1, ZEROED by the caller on `s`
+//   new_values  [pm.n_leaves][D]: a COPY of pm.values made by the caller on `s`; the range's rows receive the result.  pm.values is only read.
+//   counts      [leaves of the range] rows per leaf
+//   slots       [trees of the range] uint32, ZEROED by the caller; the caller rejects the run when a flag is set or a maximum is not finite
+//   loss_part   staged_loss_partials(n) doubles: the objective's row losses of the final P (times (double)w), the loss tail's partials
+// The rows are cr's [row0, row0 + n) (cr.rows must be null).  D <= 128.  generic: the one-thread-per-row kernels only (same bytes).  Returns the
+// number of trees whose sums the streaming kernel took.
+int refit_leaves_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, const int32_t *tree_first_leaf, int n, int start_tree, int stop_tree,
+                       int objective, bool newton, int bits, double leaf_l2, double decay, const void *targets, const float *weights, float *P,
+                       unsigned long long *acc, float *new_values, long long *counts, uint32_t *slots, double *loss_part, bool generic, hipStream_t s);
 
 // ---- Linear TreeSHAP (shap.hip): a uniform program over explicit trees, one thread per (sample, output) ----
 enum { SHAP_ENTER = 0, SHAP_AFTER_LEFT = 1, SHAP_AFTER_RIGHT = 2, SHAP_EXIT = 3 };

@@ -142,13 +142,20 @@ GBRL_OBJ_HD inline long long newton_quantise(float x, double scale) {
 #endif
 }
 
-// the leaf value from its integers (host only: double division)
-inline float newton_leaf_value(long long Sg, long long Sh, long long cnt, int depth, double scale, double leaf_l2, float old) {
-    if (cnt <= 0 || depth <= 0) return old;
+// the leaf value from its integers: q = G / (H + leaf_l2) in double, every operation rounded once (two exact divisions by a power of two, one sum,
+// one correctly rounded quotient: host and device give the same bits); false when the leaf keeps its value
+GBRL_OBJ_HD inline bool newton_leaf_quotient(long long Sg, long long Sh, long long cnt, int depth, double scale, double leaf_l2, double &q) {
+#pragma clang fp contract(off)
+    if (cnt <= 0 || depth <= 0) return false;
     const double G = static_cast<double>(Sg) / scale, H = static_cast<double>(Sh) / scale;
     const double den = H + leaf_l2;
-    if (!(den > 0.0)) return old;
-    return static_cast<float>(G / den);
+    if (!(den > 0.0)) return false;
+    q = G / den;
+    return true;
+}
+GBRL_OBJ_HD inline float newton_leaf_value(long long Sg, long long Sh, long long cnt, int depth, double scale, double leaf_l2, float old) {
+    double q = 0.0;
+    return newton_leaf_quotient(Sg, Sh, cnt, depth, scale, leaf_l2, q) ? static_cast<float>(q) : old;
 }
 
 }  // namespace kern

@@ -21,6 +21,7 @@
 #include "kernels_common.h"
 #include "leaf_accum.h"
 #include "predict_rowwalk.h"
+#include "refit_common.h"
 
 namespace gbrl {
 namespace kern {
@@ -36,28 +37,6 @@ struct RefitTree : TreeSpan {
     unsigned long long *acc;         // [n_leaves][D + 1]
     float *new_values;               // [n_leaves][D]
 };
-
-// bits of |g| as an unsigned integer: ordered like the magnitudes; NaN is carried as +inf
-__device__ __forceinline__ uint32_t refit_abs_bits(float g) {
-    const uint32_t u = __float_as_uint(g) & 0x7fffffffu;
-    return u > 0x7f800000u ? 0x7f800000u : u;
-}
-__device__ __forceinline__ double refit_scale(int n, const uint32_t *gmax) {
-    return ldexp(1.0, leaf_sum_bits_dev(static_cast<long long>(n), __uint_as_float(*gmax)));
-}
-__device__ __forceinline__ long long refit_quantise(float g, double scale) { return __double2ll_rn(__dmul_rn(static_cast<double>(g), scale)); }
-// maximum over the block, then one atomic per block
-__device__ __forceinline__ void refit_block_max(uint32_t m, uint32_t *dst) {
-    __shared__ uint32_t sh[4];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) m = max(m, static_cast<uint32_t>(__shfl_xor(static_cast<int>(m), off, kWave)));
-    if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < static_cast<int>(blockDim.x) / kWave; ++w) m = max(m, sh[w]);
-        if (m) atomicMax(dst, m);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------ start of the run
 __global__ __launch_bounds__(256) void k_refit_tile_bias(const float *__restrict__ bias, int D, size_t total, float *__restrict__ P) {
@@ -143,13 +122,7 @@ __global__ __launch_bounds__(256) void k_refit_finalize(RefitTree rt, const int3
     const long long S = static_cast<long long>(rt.acc[static_cast<size_t>(l) * (D + 1) + j]);
     const long long cnt = static_cast<long long>(rt.acc[static_cast<size_t>(l) * (D + 1) + D]);
     const int depth = oblivious ? depths[rt.t] : depths[rt.leaf0 + l];
-    float v = old;   // a leaf without rows and a leaf of depth 0 keep their value
-    if (cnt > 0 && depth > 0) {
-        // append_tree's expression: (sum / scale) / count, every operation rounded once (the first is exact: a power of two)
-        const double mean = __ddiv_rn(__ddiv_rn(static_cast<double>(S), refit_scale(n, rt.gmax)), static_cast<double>(cnt));
-        v = decay == 0.0 ? static_cast<float>(mean) : static_cast<float>(__dadd_rn(__dmul_rn(decay, static_cast<double>(old)), __dmul_rn(keep, mean)));
-    }
-    rt.new_values[i] = v;
+    rt.new_values[i] = refit_mean_value(S, cnt, depth, old, n, rt.gmax, decay, keep);
 }
 
 // ------------------------------------------------------------------------------------------------------------ apply

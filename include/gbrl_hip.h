@@ -679,6 +679,28 @@ int gbrl_hip_newton_leaves_prepared_weighted(gbrl_hip_model *m, const gbrl_hip_d
                                              const float *pred, int pred_on_device, const void *targets, int targets_on_device, int objective, int tree,
                                              double leaf_l2, const float *weights /*[n_rows]*/, int weights_on_device, float weight_max,
                                              int64_t *sums_out /*[leaves, 2 output_dim + 1]*/, int *bits_out, float *values_out /*[leaves, output_dim]*/);
+
+/* gbrl_hip_refit_leaves on a prepared data set (gbrl_hip_refit_leaves above has the rule), for the objectives, leaf
+ * rules and row weights of gbrl_hip_fit_prepared.  No new arithmetic: for t = start_tree .. stop_tree - 1, in order, P = the chain of
+ * gbrl_hip_predict_continue_prepared(ds, tiled bias, 0, t) over the new values of the trees before t.
+ *   leaf_update GBRL_HIP_LEAF_GRADIENT (rmse, logistic, softmax): g = the objective's gradient of (P, targets), fl32(w * g) with weights; the quantum
+ *     and the value are gbrl_hip_refit_leaves' (lbits from max |g|; a prediction that is not finite counts as a gradient that is not).  With rmse, no
+ *     weights and a model whose conditions are thresholds of ds, the model bytes and the loss are gbrl_hip_refit_leaves' on the observations behind ds.
+ *   leaf_update GBRL_HIP_LEAF_NEWTON (logistic, softmax): the sums of gbrl_hip_newton_leaves_prepared_weighted in ONE quantum for the call, bits =
+ *     newton_sum_bits(n_rows, the largest weight given), v = its leaf value, then decay_rate * old + (1 - decay_rate) * v in the expression above.  With
+ *     decay_rate == 0 byte for byte the loop newton_leaves_prepared(ds, P, targets, tree = t, weights) -> predict_continue_prepared(ds, P, t, t + 1).
+ * targets: float32 [n_rows, output_dim] (rmse, logistic) or int32 [n_rows] (softmax); weights: NULL or float32 [n_rows].  values_out (host float32
+ * [leaves of the range, output_dim]: what the model now holds), counts_out (host int64 [leaves of the range]) and bits_out (the Newton quantum; for
+ * gradient leaves the quantum of the first tree) may each be NULL.  *loss_out = gbrl_hip_staged_loss_prepared(ds, targets, objective, weights,
+ * stops = {stop_tree}) right after, bit for bit.
+ * Refused before anything changes: what gbrl_hip_predict_continue_prepared refuses about the model and the data set (a condition outside the
+ * thresholds names its tree; categorical columns; a row-sharded model), gbrl_hip_refit_leaves' range, decay_rate and greedy depth-0 refusals, what
+ * gbrl_hip_fit_prepared refuses about the objective, labels, leaf_l2 and weights (newton with rmse included), output_dim > 128, and -- out of scope --
+ * the quantile and ranking objectives and quantile leaves.  After the one wait GBRL_HIP_E_INVALID names the tree in front of which a gradient
+ * maximum or a prediction was not finite, or (newton) a logistic target lay outside [0, 1].  After ANY failure the model is unchanged. */
+int gbrl_hip_refit_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const void *targets, int targets_on_device, int start_tree, int stop_tree,
+                                   double decay_rate, int objective, int leaf_update, double leaf_l2, const float *weights, int weights_on_device,
+                                   double *loss_out, float *values_out, int64_t *counts_out, int *bits_out);
 int gbrl_hip_objective_gradient_host_weighted(const float *pred, const void *targets, const float *weights /*[n]*/, int n, int D, int objective,
                                               float *grad_out /*[n, D]*/);
 int gbrl_hip_objective_hessian_host_weighted(const float *pred, const float *weights /*[n]*/, int n, int D, int objective, float *hess_out /*[n, D]*/);
