@@ -463,6 +463,36 @@ py::object predict_continue_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
     return out.release(shape_of(b));
 }
 
+// Extension: predict_leaves_prepared(ds, start, stop, rows=None) / leaf_counts_prepared(...): predict_leaves / leaf_counts on a data set's bin codes
+// (include/gbrl_hip.h).  The results are those calls': int32 [m, stop - start] -- NumPy for a "cpu" model, a DLPack capsule for a "cuda" one -- and int64
+// NumPy [n_leaves]; rows as predict_continue_prepared takes them.
+py::object leaves_prepared_impl(PyGBRL &self, py::object ds_obj, py::object start_obj, py::object stop_obj, py::object &rows, bool counts) {
+    const std::string fn = counts ? "leaf_counts_prepared" : "predict_leaves_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const gbrl_hip_dataset *ds = dataset_handle(ds_obj);
+    const auto [start, stop] = read_tree_range(start_obj, stop_obj);
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, Input{});
+    if (counts) {
+        py::array_t<int64_t> res(static_cast<py::ssize_t>(md.n_leaves));
+        int64_t *rp = res.mutable_data();
+        {
+            py::gil_scoped_release release;
+            check(gbrl_hip_leaf_counts_prepared(self.h, ds, r.ptr, r.on_device, r.m, start, stop, rp));
+        }
+        return res;
+    }
+    // (the library refuses a bad range itself; the result is shaped by the range it will resolve)
+    const int resolved = stop == 0 ? md.n_trees : stop;
+    const int64_t T = std::max(resolved - start, 0), m = r.m;
+    if (m * T >= (int64_t(1) << 31)) fail(fn + ": rows x trees >= 2^31 indices: slice the tree range, or pass rows= to route a subset");
+    Result<int32_t> out(self, std::max<size_t>(static_cast<size_t>(m * T), 1));
+    {
+        py::gil_scoped_release release;
+        check(gbrl_hip_predict_leaves_prepared(self.h, ds, r.ptr, r.on_device, r.m, start, stop, out.get(), out.on_device()));
+    }
+    return out.release({m, T});
+}
+
 // Extension: predict_staged_prepared(ds, stops, rows=None) / staged_loss_prepared(ds, targets, stops=None, objective='rmse', alpha=None, weights=None,
 // eval_metric=None, rows=None): every ensemble prefix in one walk over a data set's bin codes (include/gbrl_hip.h).  stops as predict_staged takes
 // them, except that None means 0, 1, ..., n_trees (fit_prepared's validation curve); rows as predict_continue_prepared takes them.
@@ -1993,6 +2023,28 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         return leaves_impl(self, obs, ids, start, stop, true, &token);
     }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0);
     g.def_static("leaf_counts_chunk", []() { return gbrl_hip_leaf_counts_chunk(); });   // leaf counters one launch of leaf_counts holds on chip
+    g.def("predict_leaves_prepared", [](PyGBRL &self, py::object ds, py::object start, py::object stop, py::object &rows) {
+        return leaves_prepared_impl(self, ds, start, stop, rows, false);
+    }, py::arg("ds"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("rows") = py::none(),
+          "predict_leaves_prepared(ds, start_tree_idx=0, stop_tree_idx=0, rows=None) -> int32 [m, trees]\n\n"
+          "predict_leaves on a prepared data set's bin codes (LightGBM's pred_leaf, scikit-learn's apply): entry (i, t) is the global leaf index -- the row of\n"
+          "get_ensemble_data()['values'] -- tree start + t routes row rows[i] of ds to (row i without rows), -1 where a greedy search runs off the ensemble.\n"
+          "stop_tree_idx=0: all trees.  NumPy for a 'cpu' model, a DLPack capsule for a 'cuda' one.  Refused before anything is enqueued: what\n"
+          "predict_continue_prepared refuses about the model, the data set, rows and a tree the thresholds cannot express; a model without trees, an empty or\n"
+          "outside range, rows x trees >= 2^31.  There is no output_dim limit.");
+    g.def("leaf_counts_prepared", [](PyGBRL &self, py::object ds, py::object start, py::object stop, py::object &rows) {
+        return leaves_prepared_impl(self, ds, start, stop, rows, true);
+    }, py::arg("ds"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("rows") = py::none(),
+          "leaf_counts_prepared(ds, start_tree_idx=0, stop_tree_idx=0, rows=None) -> int64 [n_leaves]\n\n"
+          "leaf_counts on a prepared data set's bin codes: the rows of ds (of rows=, duplicates counted as often as they occur) per global leaf, zero outside\n"
+          "the tree range; reduced on the device with integer adds (two calls, the same bytes).  feature_importance('cover', leaf_counts=...) takes it.\n"
+          "Refusals as predict_leaves_prepared.");
+    g.def_static("leaves_prepared_geometry", [](int n_groups) {   // (group_trees, count_chunk, lds_bytes) of leaf_counts_prepared's launch plan; no device
+        int group_trees = 0, chunk = 0;
+        uint64_t lds = 0;
+        gbrl_hip_leaves_prepared_geometry(n_groups, &group_trees, &chunk, &lds);
+        return py::make_tuple(group_trees, chunk, lds);
+    }, py::arg("n_groups"));
     // extension: global feature importance -- two counts from the host copy of the model, and the permuted losses of a data set's columns
     g.def("feature_importance", &feature_importance_impl, py::arg("kind") = "split", py::arg("leaf_counts") = py::none(),
           "feature_importance(kind='split', leaf_counts=None) -> float64 [input_dim]\n\n"

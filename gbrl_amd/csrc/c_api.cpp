@@ -567,6 +567,28 @@ int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset
     });
 }
 
+int gbrl_hip_predict_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int start_tree,
+                                     int stop_tree, int32_t *out, int out_on_device) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("predict_leaves_prepared");
+        m->engine.predict_leaves_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, start_tree, stop_tree, out, out_on_device != 0);
+    });
+}
+
+int gbrl_hip_leaf_counts_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int start_tree,
+                                  int stop_tree, int64_t *out_host) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("leaf_counts_prepared");
+        m->engine.leaf_counts_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, start_tree, stop_tree, out_host);
+    });
+}
+
+void gbrl_hip_leaves_prepared_geometry(int n_groups, int *group_trees, int *count_chunk, uint64_t *lds_bytes) {
+    gbrl::kern::leaves_codes_geometry(n_groups, group_trees, count_chunk, lds_bytes);
+}
+
 int gbrl_hip_predict_staged_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
                                      const int32_t *stops, int n_stops, float *out, int out_on_device) {
     return guarded([&] {

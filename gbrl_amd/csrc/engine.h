@@ -461,6 +461,14 @@ class Engine {
                         int n_num, int n_cat, int start_tree, int stop_tree, int32_t *out, bool out_dev);
     void leaf_counts(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token, int n,
                      int n_num, int n_cat, int start_tree, int stop_tree, int64_t *counts_out);
+    // Extension: the same two answers on a prepared data set (kern::predict_leaves_codes / kern::leaf_counts_codes), rows as predict_continue_prepared
+    // takes them (rows == nullptr: every row, m == ds->n; duplicates allowed, each counted).  predict_leaves_prepared: out int32 [m][stop - start]
+    // (device iff out_dev), entry (i, t) what predict_leaves reports for the observations of row rows[i]; m * trees >= 2^31 is Unsupported.
+    // leaf_counts_prepared: counts_out (host) int64 [n_leaves], leaf_counts' vector.  The range is predict_leaves' (stop_tree == 0: n_trees; empty or
+    // outside the ensemble: InvalidArgument).  Refused before the device is touched: what predict_continue_prepared refuses about the model, the data
+    // set, the rows and a tree of the range the thresholds cannot express (check_code_range), except the output width.  Nothing is written.
+    void predict_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int start_tree, int stop_tree, int32_t *out, bool out_dev);
+    void leaf_counts_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int start_tree, int stop_tree, int64_t *counts_out);
     // Extension: refit the leaf values of the trees [start_tree, stop_tree) on a batch, the structure kept (kern::refit_leaves; include/gbrl_hip.h
     // has the contract).  stop_tree == 0: n_trees; then 0 <= start_tree < stop_tree <= n_trees.  decay_rate in [0, 1]: new value = decay * old +
     // (1 - decay) * leaf mean of fit()'s MultiRMSE gradient.  Only model.values of the range changes; *loss_out = staged_loss(..., {stop_tree})
@@ -556,6 +564,8 @@ class Engine {
     // what predict_staged_prepared and staged_loss_prepared both refuse about the model, the data set, the stops and rows (noun: what has m rows)
     void check_staged_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const int32_t *stops, int n_stops, const char *noun);
     int check_leaves_range(int start_tree, int stop_tree) const;   // predict_leaves / leaf_counts: the resolved stop of a range the ensemble holds
+    // predict_leaves_prepared / leaf_counts_prepared: every refusal the two share (engine_codes.hip); the resolved stop
+    int check_leaves_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int start_tree, int stop_tree);
     int check_refit(int start_tree, int stop_tree, const float *targets, double decay_rate, const double *loss_out) const;   // likewise (engine_refit.hip)
     StagedBatch stage_batch(const PredictBatch &b);   // device, event pool, mirror; opens the `inputs` phase: observations up, ids checked and uploaded or cells encoded
     const float *stage_targets(const float *targets, bool on_device, int n);   // [n][D] targets on the device

@@ -4,6 +4,7 @@
 //   sync_code_tables                   device copies of the bins and of the mirror's packed conditions / greedy node records with the bin as
 //                                      their second word (appended like the originals: a loop that adds a tree per iteration converts that tree only)
 //   Engine::predict_continue_prepared  predict_continue without the observations (kern::predict_continue_codes)
+//   Engine::predict_leaves_prepared / leaf_counts_prepared   where the rows of a data set land, and the rows per leaf (kern::predict_leaves_codes / leaf_counts_codes)
 //   Engine::predict_staged_prepared / staged_loss_prepared   every prefix of the ensemble in one walk over the codes (kern::predict_staged_codes)
 //   read_back / subset_rows / resolve_tree / join_tail_phase   what the calls on a data set share (engine.h)
 //
@@ -201,6 +202,63 @@ void Engine::predict_continue_prepared(const PreparedDataset *ds, const int32_t 
     kern::predict_continue_codes(mirror_view(), ct, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, start_tree, stop, dbase, dout,
                                  nullptr, nullptr, nullptr, nullptr, hooks::on(hooks::CONTINUE_GENERIC), stream_);
     finish("predict_continue_prepared launch", "predict", {{out_dev ? nullptr : out, dout, out_bytes, "D2H preds"}});
+}
+
+// Extension: where the rows of a data set land (kern::predict_leaves_codes / kern::leaf_counts_codes).  The refusals that both forms share, in
+// predict_continue_prepared's order and with its messages; returns the resolved stop.  Leaf routing reads no value: no output width limit.
+int Engine::check_leaves_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int start_tree, int stop_tree) {
+    const std::string w(what);
+    const int T = model.meta.n_trees;
+    check_prepared_dataset(what, ds);
+    if (start_tree < 0 || stop_tree < 0) throw InvalidArgument("invalid tree range");
+    if (T == 0) throw InvalidArgument(w + ": the model has no trees");
+    const int stop = stop_tree == 0 ? T : stop_tree;   // (0 means n_trees)
+    if (stop > T || start_tree >= stop) throw InvalidArgument(w + ": invalid tree range");
+    check_row_count(what, "the call", rows, m, ds->n, "route");
+    if (rows != nullptr && !rows_dev) check_host_rows(rows, m, ds->n);
+    check_code_range(*ds, what, start_tree, stop);
+    return stop;
+}
+
+void Engine::predict_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int start_tree, int stop_tree, int32_t *out,
+                                     bool out_dev) {
+    const char *what = "predict_leaves_prepared";
+    if (out == nullptr) throw InvalidArgument(std::string(what) + ": no place for the result");
+    const int stop = check_leaves_prepared(what, ds, rows, rows_dev, m, start_tree, stop_tree);
+    if (static_cast<int64_t>(m) * (stop - start_tree) >= (int64_t(1) << 31))
+        throw Unsupported(std::string(what) + ": rows x trees >= 2^31 indices: slice the tree range, or pass rows= to route a subset");
+    ensure_device();
+    reset_events();
+    sync_model_to_device();
+    phase_begin();
+    const kern::CodeTables ct = sync_code_tables(*ds);
+    const int32_t *d_rows = subset_rows(ds, rows, rows_dev, m);
+    const size_t out_bytes = sizeof(int32_t) * static_cast<size_t>(m) * (stop - start_tree);
+    int32_t *dl = out_dev ? out : static_cast<int32_t *>(d_leaves_out_.ensure(out_bytes));
+    phase_end("inputs"); phase_begin(/*key=*/true);
+    kern::predict_leaves_codes(mirror_view(), ct, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, m, start_tree, stop, dl,
+                               hooks::on(hooks::LEAVES_GENERIC), stream_);
+    finish("predict_leaves_prepared launch", "predict", {{out_dev ? nullptr : out, dl, out_bytes, "D2H leaves"}});
+}
+
+void Engine::leaf_counts_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int start_tree, int stop_tree, int64_t *counts_out) {
+    const char *what = "leaf_counts_prepared";
+    if (counts_out == nullptr) throw InvalidArgument(std::string(what) + ": no place for the result");
+    const int stop = check_leaves_prepared(what, ds, rows, rows_dev, m, start_tree, stop_tree);
+    ensure_device();
+    reset_events();
+    sync_model_to_device();
+    phase_begin();
+    const kern::CodeTables ct = sync_code_tables(*ds);
+    const int32_t *d_rows = subset_rows(ds, rows, rows_dev, m);
+    const size_t L = static_cast<size_t>(model.meta.n_leaves);
+    uint32_t *dcounts = zeroed<uint32_t>(d_leaf_counts_, std::max<size_t>(L, 1), "zero leaf counters");
+    phase_end("inputs"); phase_begin(/*key=*/true);
+    kern::leaf_counts_codes(mirror_view(), ct, kern::CodeRows{ds->prep.d_codes, ds->n, ds->code_groups(), d_rows, 0}, model.tree_indices.data(), m, start_tree,
+                            stop, dcounts, hooks::on(hooks::LEAVES_GENERIC), stream_);
+    std::vector<uint32_t> h(L);
+    finish("leaf_counts_prepared launch", "predict", {{h.data(), dcounts, sizeof(uint32_t) * L, "D2H leaf counts"}});
+    for (size_t l = 0; l < L; ++l) counts_out[l] = static_cast<int64_t>(h[l]);   // (m < 2^31 rows: a counter cannot wrap)
 }
 
 // Extension: every prefix [0, stops[s]) of the ensemble in one walk over the data set's codes (kern::predict_staged_codes).  The refusals that both

@@ -837,6 +837,18 @@ void predict_leaves(const PredictModel &pm, const float *obs, int F, const int32
                     bool generic, hipStream_t s);
 void leaf_counts(const PredictModel &pm, const int32_t *tree_first_leaf, const float *obs, int F, const int32_t *cat_codes, int Fc, int n, int start_tree,
                  int stop_tree, uint32_t *counts, bool generic, hipStream_t s);
+// The same two answers from a prepared data set's bin codes (predict_leaves_codes.hip): sample j of the m is row cr.rows[cr.row0 + j] (or cr.row0 + j)
+// of cr.codes, and a numeric condition x > v reads code > bin (ct; no categorical conditions).  predict_leaves_codes: out is device int32
+// [m][stop_tree - start_tree], indexed by j.  leaf_counts_codes: counts as leaf_counts takes it (ZEROED by the caller on `s`); a duplicated row counts
+// as often as it occurs.  The counters of a run of trees are kept in LDS, at most leaves_codes_geometry's count_chunk per launch.
+// leaves_codes_geometry (host only, no device): the launch plan for a data set of n_groups 16-column groups -- the trees walked into registers
+// together, the counter chunk (a power of two >= kLeafCountChunk chosen so that the block count per CU is the code tile's; 0: the tile does not fit
+// beside kLeafCountChunk counters and the general kernel takes the call) and the dynamic LDS of a full count launch.  Any pointer may be null.
+void leaves_codes_geometry(int n_groups, int *group_trees, int *count_chunk, uint64_t *lds_bytes);
+void predict_leaves_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, int32_t *out, bool generic,
+                          hipStream_t s);
+void leaf_counts_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, const int32_t *tree_first_leaf, int m, int start_tree, int stop_tree,
+                       uint32_t *counts, bool generic, hipStream_t s);
 
 // Refit the leaf values of the trees [start_tree, stop_tree) on a batch, the structure kept (refit.hip).  Everything is enqueued on `s`; nothing
 // is read back and the host never waits.  Per tree t, in order: g = fl32(P - targets); the fixed point 2^lbits from gmax[t - start_tree] by the

@@ -1029,6 +1029,30 @@ int gbrl_hip_fit_prepared_valid(gbrl_hip_model *m, const gbrl_hip_dataset *ds, c
 int gbrl_hip_early_stop_scan(const double *curve, int n, int rounds, double min_delta, int *stop_after, int *best);
 int gbrl_hip_predict_continue_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,
                                        const float *base, int base_on_device, int start_tree, int stop_tree, float *out);
+/* Where the rows of a data set land (new): gbrl_hip_predict_leaves / gbrl_hip_leaf_counts with the row read from the bin codes -- LightGBM's
+ * pred_leaf, scikit-learn's apply() -- for a learner that has freed its observations.  rows / rows_on_device / n_rows as
+ * gbrl_hip_predict_continue_prepared takes them (rows == NULL: every row, n_rows == the data set's; duplicates allowed).  The range is
+ * gbrl_hip_predict_leaves': stop_tree 0 = n_trees, then 0 <= start_tree < stop_tree <= n_trees.
+ *   gbrl_hip_predict_leaves_prepared  out int32 [n_rows, stop_tree - start_tree], row-major, host or device per out_on_device: entry (i, t) is the
+ *     GLOBAL leaf index -- the row of `values` -- tree start_tree + t routes data set row rows[i] to, exactly what gbrl_hip_predict_leaves
+ *     reports for the observations of that row (-1 where a greedy search runs off the ensemble).  n_rows x trees >= 2^31: GBRL_HIP_E_UNSUPPORTED.
+ *   gbrl_hip_leaf_counts_prepared     out_host int64 [n_leaves] over the WHOLE ensemble, gbrl_hip_leaf_counts' vector: entry l = the rows of the call
+ *     that reach leaf l (a duplicated row counts as often as it occurs), 0 outside the range.  Integer atomics: two calls, the same bytes.
+ *     It is the leaf_counts argument of gbrl_hip_feature_importance's cover kind.
+ *   gbrl_hip_leaves_prepared_geometry(n_groups, group_trees, count_chunk, lds_bytes)  no device needed: the launch plan of the count kernel for a
+ *     data set of n_groups 16-column groups -- the trees a wave walks into registers before it issues their adds, the leaf counters one launch holds
+ *     on chip (a power of two, at least gbrl_hip_leaf_counts_chunk(); 0: the 64-row code tile, 256 * ((8 * n_groups) | 1) bytes, does not fit
+ *     the 156 KiB of LDS beside that many counters, and the one-thread-per-row kernel takes the call) and the LDS bytes of such a launch.  A
+ *     longer range is processed in runs of whole trees, one launch per run.  Any pointer may be NULL.
+ * Refused before the device is touched, GBRL_HIP_E_INVALID unless noted: what gbrl_hip_predict_continue_prepared refuses about the model (a
+ * communicator, categorical columns: GBRL_HIP_E_UNSUPPORTED), the data set (NULL, destroyed, another n_bins / generator / width / device) and rows;
+ * a model without trees, a bad range, a NULL result, and (GBRL_HIP_E_UNSUPPORTED) a tree of the range with a condition the codes cannot express.
+ * There is no output_dim limit: no leaf value is read.  GBRL_HIP_LEAVES_GENERIC=1 selects the one-thread-per-row kernels (same bytes). */
+int gbrl_hip_predict_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int start_tree,
+                                     int stop_tree, int32_t *out, int out_on_device);
+int gbrl_hip_leaf_counts_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int start_tree,
+                                  int stop_tree, int64_t *out_host);
+void gbrl_hip_leaves_prepared_geometry(int n_groups, int *group_trees, int *count_chunk, uint64_t *lds_bytes);
 int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
                           float *loss_out);
 
