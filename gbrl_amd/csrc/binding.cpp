@@ -463,6 +463,87 @@ py::object predict_continue_prepared_impl(PyGBRL &self, py::object ds_obj, py::o
     return out.release(shape_of(b));
 }
 
+// Extension: control variates as a call of its own (include/gbrl_hip.h, "Control variates"): control_variates(obs, None, grads, beta, momentum,
+// start_tree_idx), control_variates_prepared(ds, grads, beta, momentum, start_tree_idx, rows) and gbrl_cpp.control_variates_host(model, X, G, ...).
+// One body: `where` 0 float rows on the device, 1 a data set, 2 the host rule.  The result is a dict; grads and momentum are delivered as predict
+// delivers (NumPy for a "cpu" model and for the host rule, DLPack capsules for a "cuda" one), the statistics are NumPy float32 [D].
+py::dict control_variates_impl(PyGBRL &self, int where, py::object &obs, py::object &cat, py::object ds_obj, py::object &grads, py::object &beta_obj,
+                               py::object &momentum, int start, py::object &rows) {
+    const std::string fn = where == 0 ? "control_variates" : where == 1 ? "control_variates_prepared" : "control_variates_host";
+    const gbrl_hip_metadata md = self.meta();
+    const int D = md.output_dim;
+    float beta = 0.0f;
+    if (!beta_obj.is_none()) beta = beta_obj.cast<float>();
+    const float *bp = beta_obj.is_none() ? nullptr : &beta;
+    Input o, g;
+    RowsArg r{nullptr, 0, 0};
+    int n = 0, n_num = 0;
+    const gbrl_hip_dataset *ds = nullptr;
+    if (where == 1) {
+        ds = dataset_handle(ds_obj);
+        g = require_input(grads, "grads", fn);
+        r = read_rows_arg(rows, fn, ds_obj, g);
+        n = r.m;
+    } else {
+        const Batch b = read_batch(obs, cat, fn, md.input_dim, false, &grads, "grads");
+        if (b.s.n_cat > 0) fail(fn + ": not available on a model with categorical columns");
+        o = b.o; g = b.extra;
+        n = b.s.n; n_num = b.s.n_num;
+    }
+    check_rows_by_outputs(g, "grads", n, D);
+    Input mom = read_input(momentum, "momentum", true, fn, 0);
+    if (mom.ptr != nullptr) {
+        check_rows_by_outputs(mom, "momentum", n, D);   // (host or device, like grads: the engine stages either)
+    }
+    if (where == 2) {
+        require_host(o, fn + " takes NumPy arrays");
+        require_host(g, fn + " takes NumPy arrays");
+        require_host(mom, fn + " takes NumPy arrays");
+    }
+    const bool dev = where != 2 && self.device == 1;
+    const size_t count = std::max<size_t>(static_cast<size_t>(std::max(n, 0)) * D, 1);
+    Result<float> out_g(dev, result_device(self, dev), count), out_m(dev, result_device(self, dev), count);
+    py::array_t<float> stats({static_cast<py::ssize_t>(5), static_cast<py::ssize_t>(D)});
+    float *sp = stats.mutable_data();
+    float scale = 0.0f;
+    int n_trees = 0;
+    {
+        py::gil_scoped_release release;
+        if (where == 0)
+            check(gbrl_hip_control_variates(self.h, o.f32(), o.on_device, n, n_num, g.f32(), g.on_device, bp, mom.f32(), mom.on_device, start, out_g.get(), out_m.get(), dev,
+                                            sp, &scale, &n_trees));
+        else if (where == 1)
+            check(gbrl_hip_control_variates_prepared(self.h, ds, r.ptr, r.on_device, n, g.f32(), g.on_device, bp, mom.f32(), mom.on_device, start, out_g.get(),
+                                                     out_m.get(), dev, sp, &scale, &n_trees));
+        else
+            check(gbrl_hip_control_variates_host(self.h, o.f32(), n, n_num, g.f32(), bp, mom.f32(), start, out_g.get(), out_m.get(), sp, &scale, &n_trees));
+    }
+    py::dict out;
+    out["grads"] = out_g.release(shape_of(g));
+    out["momentum"] = out_m.release(shape_of(g));
+    const char *names[5] = {"alpha", "mean_grads", "mean_momentum", "var", "cov"};
+    for (int k = 0; k < 5; ++k) out[names[k]] = py::array_t<float>(static_cast<py::ssize_t>(D), sp + static_cast<size_t>(k) * D);
+    out["scale"] = py::float_(scale);
+    out["n_trees"] = py::int_(n_trees);
+    return out;
+}
+
+py::dict control_variates_geometry_impl(int64_t n, int width, bool codes, int D) {
+    int streaming = 0, dmax = 0, walk_trees = 0, value_trees = 0, walk_slots = 0, moment_slots = 0, launches = 0;
+    uint64_t lds = 0;
+    gbrl_hip_control_variates_geometry(n, width, codes ? 1 : 0, D, &streaming, &dmax, &walk_trees, &value_trees, &walk_slots, &moment_slots, &launches, &lds);
+    py::dict out;
+    out["streaming"] = streaming != 0;
+    out["dmax"] = dmax;
+    out["walk_trees"] = walk_trees;
+    out["value_trees"] = value_trees;
+    out["walk_slots"] = walk_slots;
+    out["moment_slots"] = moment_slots;
+    out["launches"] = launches;
+    out["lds_bytes"] = py::int_(lds);
+    return out;
+}
+
 // Extension: predict_leaves_prepared(ds, start, stop, rows=None) / leaf_counts_prepared(...): predict_leaves / leaf_counts on a data set's bin codes
 // (include/gbrl_hip.h).  The results are those calls': int32 [m, stop - start] -- NumPy for a "cpu" model, a DLPack capsule for a "cuda" one -- and int64
 // NumPy [n_leaves]; rows as predict_continue_prepared takes them.
@@ -1665,6 +1746,15 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "shap_geometry(F=1, D=1) -> {'tile_rows': 64, 'default_chunk_rows': ..., 'scratch_budget': 67108864}: the rows one float64 partial of\n"
           "shap_importance_prepared sums, and its default chunk_rows for F features and D outputs: the largest multiple of 64 whose float32 scratch\n"
           "[chunk_rows, F, D] stays within the budget, and at least 64");
+    m.def("control_variates_host", [](PyGBRL &model, py::object &X, py::object &G, py::object &beta, py::object &momentum, int start) {
+              py::object none = py::none();
+              return control_variates_impl(model, 2, X, none, none, G, beta, momentum, start, none);
+          }, py::arg("model"), py::arg("X"), py::arg("G"), py::arg("beta") = py::none(), py::arg("momentum") = py::none(), py::arg("start_tree_idx") = 0,
+          "control_variates_host(model, X, G, beta=None, momentum=None, start_tree_idx=0) -> dict\n\n"
+          "GBRL.control_variates on the host from the host copy of the model, no device: cv_core.h's rule, the same bytes.  NumPy arrays only.");
+    m.def("control_variates_geometry", &control_variates_geometry_impl, py::arg("n"), py::arg("width"), py::arg("codes") = false, py::arg("D") = 1,
+          "control_variates_geometry(n, width, codes=False, D=1) -> {'streaming', 'dmax', 'walk_trees', 'value_trees', 'walk_slots', 'moment_slots', 'launches',\n"
+          "'lds_bytes'}: the launch plan of control_variates for n rows of `width` features (codes: of `width` 16-column groups of a data set); no device.");
     m.def("path_contrib_host", &path_contrib_host_impl, py::arg("model"), py::arg("X"), py::arg("n_trees") = py::none(),
           "path_contrib_host(model, X, n_trees=None) -> float32 [n, F, D]\n\n"
           "Path attribution (Saabas; XGBoost's approx_contribs) of the trees [0, n_trees) on float observations X [n, F], from the host copy of the model (no\n"
@@ -2023,6 +2113,26 @@ PYBIND11_MODULE(gbrl_cpp, m) {
         return leaves_impl(self, obs, ids, start, stop, true, &token);
     }, py::arg("obs"), py::arg("categorical_ids"), py::arg("dictionary_token"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0);
     g.def_static("leaf_counts_chunk", []() { return gbrl_hip_leaf_counts_chunk(); });   // leaf counters one launch of leaf_counts holds on chip
+    // extension: control variates as a call of its own (the constructor flag use_control_variates stays refused)
+    g.def("control_variates", [](PyGBRL &self, py::object &obs, py::object &cat, py::object &grads, py::object &beta, py::object &momentum, int start) {
+        py::object none = py::none();
+        return control_variates_impl(self, 0, obs, cat, none, grads, beta, momentum, start, none);
+    }, py::arg("obs"), py::arg("categorical_obs"), py::arg("grads"), py::arg("beta") = py::none(), py::arg("momentum") = py::none(), py::arg("start_tree_idx") = 0,
+          "control_variates(obs, None, grads, beta=None, momentum=None, start_tree_idx=0) -> dict\n\n"
+          "The gradients corrected by an exponential moving average of the leaf values the trees [start_tree_idx, n_trees) assign to each row (the variance\n"
+          "reduction of the GBRL paper), for step(obs, None, r['grads']).  'grads' and 'momentum' are float32 shaped like grads (NumPy for a 'cpu' model, DLPack\n"
+          "capsules for a 'cuda' one; the input is not written) -- 'momentum' is the RAW average: hand it back as momentum= with start_tree_idx = the trees it\n"
+          "covers and only the new trees are walked.  Without momentum the chain starts from zero at start_tree_idx, which omits at most\n"
+          "beta^(n_trees - start) * max |value| of it.  'alpha', 'mean_grads', 'mean_momentum', 'var', 'cov': float32 [D]; 'scale', 'n_trees'.  beta: the\n"
+          "model's cv_beta unless given.  Byte for byte gbrl_cpp.control_variates_host.  Refused before anything is enqueued: fewer than 2 rows, beta outside\n"
+          "(0, 1), a bad start_tree_idx, momentum of another shape, output_dim > 128, categorical columns, a communicator or collective hooks.");
+    g.def("control_variates_prepared", [](PyGBRL &self, py::object ds, py::object &grads, py::object &beta, py::object &momentum, int start, py::object &rows) {
+        py::object none = py::none();
+        return control_variates_impl(self, 1, none, none, ds, grads, beta, momentum, start, rows);
+    }, py::arg("ds"), py::arg("grads"), py::arg("beta") = py::none(), py::arg("momentum") = py::none(), py::arg("start_tree_idx") = 0, py::arg("rows") = py::none(),
+          "control_variates_prepared(ds, grads, beta=None, momentum=None, start_tree_idx=0, rows=None) -> dict\n\n"
+          "control_variates(obs[rows], None, grads, ...) byte for byte, read from the data set's bin codes; rows as predict_continue_prepared takes them (grads and\n"
+          "momentum indexed by position), for step_prepared(ds, r['grads'], rows=rows).  Refused too: what predict_continue_prepared refuses.");
     g.def("predict_leaves_prepared", [](PyGBRL &self, py::object ds, py::object start, py::object stop, py::object &rows) {
         return leaves_prepared_impl(self, ds, start, stop, rows, false);
     }, py::arg("ds"), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("rows") = py::none(),

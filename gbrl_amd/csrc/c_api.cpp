@@ -22,6 +22,7 @@
 #include "quantile_core.h"
 #include "rank_core.h"
 #include "pd_core.h"
+#include "cv_core.h"
 #include "shap_core.h"
 #include "hooks.h"
 #include "explain.h"
@@ -587,6 +588,52 @@ int gbrl_hip_leaf_counts_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds,
 
 void gbrl_hip_leaves_prepared_geometry(int n_groups, int *group_trees, int *count_chunk, uint64_t *lds_bytes) {
     gbrl::kern::leaves_codes_geometry(n_groups, group_trees, count_chunk, lds_bytes);
+}
+
+int gbrl_hip_control_variates(gbrl_hip_model *m, const float *obs, int obs_on_device, int n_samples, int n_num_features, const float *grads, int grads_on_device,
+                              const float *beta, const float *momentum, int momentum_on_device, int start_tree, float *grads_out, float *momentum_out,
+                              int out_on_device, float *stats_out, float *scale_out, int *n_trees_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.control_variates(obs, obs_on_device != 0, n_samples, n_num_features,
+                                   gbrl::Engine::CvArgs{grads, grads_on_device != 0, beta, momentum, momentum_on_device != 0, start_tree, grads_out, momentum_out,
+                                                        out_on_device != 0, stats_out, scale_out, n_trees_out});
+    });
+}
+
+int gbrl_hip_control_variates_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *grads,
+                                       int grads_on_device, const float *beta, const float *momentum, int momentum_on_device, int start_tree, float *grads_out,
+                                       float *momentum_out, int out_on_device, float *stats_out, float *scale_out, int *n_trees_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("control_variates_prepared");
+        m->engine.control_variates_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows,
+                                            gbrl::Engine::CvArgs{grads, grads_on_device != 0, beta, momentum, momentum_on_device != 0, start_tree, grads_out,
+                                                                 momentum_out, out_on_device != 0, stats_out, scale_out, n_trees_out});
+    });
+}
+
+int gbrl_hip_control_variates_host(const gbrl_hip_model *m, const float *obs, int n_samples, int n_num_features, const float *grads, const float *beta,
+                                   const float *momentum, int start_tree, float *grads_out, float *momentum_out, float *stats_out, float *scale_out,
+                                   int *n_trees_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.control_variates_host(obs, n_samples, n_num_features,
+                                        gbrl::Engine::CvArgs{grads, false, beta, momentum, false, start_tree, grads_out, momentum_out, false, stats_out, scale_out, n_trees_out});
+    });
+}
+
+void gbrl_hip_control_variates_geometry(int64_t n_rows, int width, int codes, int output_dim, int *streaming, int *dmax, int *walk_trees, int *value_trees,
+                                        int *walk_slots, int *moment_slots, int *launches, uint64_t *lds_bytes) {
+    const gbrl::kern::CvPlan p = gbrl::kern::cv_plan(std::max<int64_t>(n_rows, 0), std::max(width, 0), codes != 0, std::max(output_dim, 1));
+    if (streaming) *streaming = p.streaming;
+    if (dmax) *dmax = p.dmax;
+    if (walk_trees) *walk_trees = p.walk_trees;
+    if (value_trees) *value_trees = p.value_trees;
+    if (walk_slots) *walk_slots = p.walk_slots;
+    if (moment_slots) *moment_slots = p.moment_slots;
+    if (launches) *launches = p.launches;
+    if (lds_bytes) *lds_bytes = p.lds;
 }
 
 int gbrl_hip_predict_staged_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows,

@@ -461,6 +461,27 @@ class Engine {
                         int n_num, int n_cat, int start_tree, int stop_tree, int32_t *out, bool out_dev);
     void leaf_counts(const float *obs, bool obs_dev, const char *cat, bool cat_dev, const int32_t *cat_ids, bool ids_dev, const uint64_t *token, int n,
                      int n_num, int n_cat, int start_tree, int stop_tree, int64_t *counts_out);
+    // Extension: control variates as a call of its own (cv_core.h has the rule, control_variates.hip the kernels, engine_cv.hip the stages): the
+    // gradients of n rows corrected by the exponential moving average of the leaf values the trees [start_tree, n_trees) assign to each row.
+    // beta == nullptr: the model's cv_beta.  momentum (nullable, [n][D] raw averages of an earlier call over [0, start_tree)) continues that chain;
+    // without it the chain starts from zero at start_tree.  grads_out / momentum_out [n][D] live where out_dev says; stats_out (host) float32
+    // [kCvStats][D]: alpha, mean_grads, mean_momentum, var, cov; *scale_out the bias correction, *n_trees_out the trees at the call.  A model without
+    // trees (and start_tree == n_trees without momentum): grads copied, momentum and statistics zero, no walk.  Refused before anything is enqueued:
+    // a null argument, n < 2, beta outside (0, 1) or NaN, start_tree outside [0, n_trees], output_dim > 128, a model with categorical columns, a
+    // communicator or collective hooks (Unsupported), and for the data set form what predict_continue_prepared refuses.  A non-finite alpha fails the
+    // call (InvalidArgument) behind its one wait.
+    struct CvArgs {
+        const float *grads; bool grads_dev;
+        const float *beta;
+        const float *momentum; bool momentum_dev;
+        int start_tree;
+        float *grads_out, *momentum_out; bool out_dev;
+        float *stats_out, *scale_out; int *n_trees_out;
+    };
+    void control_variates(const float *obs, bool obs_dev, int n, int n_num, const CvArgs &a);
+    void control_variates_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const CvArgs &a);
+    // the same bytes with no device, from the host copy of the model (cv_host.cpp); everything is host memory
+    void control_variates_host(const float *obs, int n, int n_num, const CvArgs &a) const;
     // Extension: the same two answers on a prepared data set (kern::predict_leaves_codes / kern::leaf_counts_codes), rows as predict_continue_prepared
     // takes them (rows == nullptr: every row, m == ds->n; duplicates allowed, each counted).  predict_leaves_prepared: out int32 [m][stop - start]
     // (device iff out_dev), entry (i, t) what predict_leaves reports for the observations of row rows[i]; m * trees >= 2^31 is Unsupported.
@@ -862,6 +883,11 @@ class Engine {
     long long cum_cache_n_ = -1;   // (global rows, n_bins) the device copy of the quantile target ranks was built for
     int cum_cache_b_ = -1;
     // ---- predict workspace + device mirror of the ensemble ----
+    // control variates: the refusals both device forms and the host form share (returns beta), and everything behind the staged rows
+    float check_cv(const char *what, int n, const CvArgs &a) const;
+    template <typename Walk>
+    void run_cv(const char *what, int n, const CvArgs &a, float beta, Walk &&walk);
+    DevBuf d_cv_grads_, d_cv_mom_in_, d_cv_grads_out_, d_cv_mom_out_, d_cv_ms_, d_cv_part_, d_cv_stats_;   // staged inputs, host-bound results, scratch
     DevBuf d_pobs_, d_pcat_, d_pout_;
     DevBuf d_leaves_out_, d_leaf_counts_;   // predict_leaves: indices bound for the host; leaf_counts: the uint32 counters
     DevBuf d_refit_counts_, d_refit_weights_;   // refit_leaves_prepared: rows per leaf, staged weights (the rest are refit_leaves' buffers)

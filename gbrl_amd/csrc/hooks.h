@@ -14,6 +14,7 @@ namespace hooks {
     X(CAT_CHECK) \
     X(CAT_PROF) \
     X(CONTINUE_GENERIC) \
+    X(CV_GENERIC) \
     X(DEVICE_LEVELS) \
     X(EVENT_RESULTS) \
     X(FORCE_BISECTION) \

@@ -850,6 +850,25 @@ void predict_leaves_codes(const PredictModel &pm, const CodeTables &ct, const Co
 void leaf_counts_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, const int32_t *tree_first_leaf, int m, int start_tree, int stop_tree,
                        uint32_t *counts, bool generic, hipStream_t s);
 
+// Control variates (control_variates.hip; cv_core.h has the rule): the momentum walk of the trees [start_tree, stop_tree) over n rows, then fold,
+// moments and apply -- four launches on `s`, nothing read back.  All buffers are device memory; grads_out and momentum_out are written, grads and
+// momentum_in (nullable: the chain starts from zero) only read.  beta in (0, 1), scale = cv_scale(beta, n_trees), n >= 2: the caller has checked.
+// control_variates reads float rows [n][F] of a numeric-only model, control_variates_codes the rows of a prepared data set as
+// predict_continue_codes does.  generic: the one-thread-per-row walk (the same bytes).
+struct CvBuffers {
+    const float *grads, *momentum_in;   // [n][D]
+    float *grads_out, *momentum_out;    // [n][D]
+    float *ms;                          // scratch [n][D]: the scaled averages
+    double *slots;                      // scratch [cv_walk_slots(n)][2 D]
+    double *totals;                     // scratch [2 D]
+    double *moments;                    // scratch [cv_moment_slots(n)][2 D]
+    float *stats;                       // [kCvStats][D]: alpha, mean_grads, mean_momentum, var, cov
+};
+void control_variates(const PredictModel &pm, const float *obs, int F, int n, int start_tree, int stop_tree, float beta, float scale, const CvBuffers &b, bool generic,
+                      hipStream_t s);
+void control_variates_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, float beta, float scale,
+                            const CvBuffers &b, bool generic, hipStream_t s);
+
 // Refit the leaf values of the trees [start_tree, stop_tree) on a batch, the structure kept (refit.hip).  Everything is enqueued on `s`; nothing
 // is read back and the host never waits.  Per tree t, in order: g = fl32(P - targets); the fixed point 2^lbits from gmax[t - start_tree] by the
 // step's rule (leaf_sum_bits_dev, n = the rows of this call); per leaf of the tree, routed as predict_leaves routes, the exact int64 sums of

@@ -1053,6 +1053,44 @@ int gbrl_hip_predict_leaves_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *
 int gbrl_hip_leaf_counts_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int start_tree,
                                   int stop_tree, int64_t *out_host);
 void gbrl_hip_leaves_prepared_geometry(int n_groups, int *group_trees, int *count_chunk, uint64_t *lds_bytes);
+/* Control variates as a call of its own (new: the gradient variance reduction of the GBRL paper, Fitter::control_variates -- CPU-only in the
+ * reference and switched off there on a GPU; the constructor flag use_control_variates stays refused here).  csrc/cv_core.h has the rule,
+ * csrc/control_variates.hip the kernels.  Before a tree is fitted the gradients of n rows are corrected by an exponential moving average of the leaf
+ * values the ensemble assigns to each row:
+ *   chain        for the trees t of [start_tree, n_trees) in order, leaf = the leaf gbrl_hip_predict_leaves reports (-1 ends the walk), for EVERY output j:
+ *                m_j = fl32(fl32(beta * m_j) + fl32(c * values[leaf][j])), c = fl32(1 - beta); three roundings, no fused multiply-add, no learning rate.
+ *                beta == NULL: the model's cv_beta.  momentum == NULL: the chain starts from zero at start_tree -- the dropped trees carry a total
+ *                weight of beta^(n_trees - start_tree), so what is omitted of momentum is at most beta^(n_trees - start_tree) * max |value|.  momentum
+ *                given: the raw averages an earlier call returned for the trees [0, start_tree) are continued (one new tree per step of a learner that
+ *                steps several times on one rollout).
+ *   scale        1 / sqrtf(1 - powf(beta, n_trees)) in float32 on the host; ms = fl32(m * scale).
+ *   statistics   float64 sums in one fixed order (cv_core.h: butterflies of 64, slots, folds), each result rounded to float32 once:
+ *                gbar = sum g / n, mbar = sum ms / n, gc = fl32(g - gbar), mc = fl32(ms - mbar), var = sum mc^2 / (n - 1), cov = sum gc mc / (n - 1).
+ *   coefficient  alpha = clamp(fl32(cov / fl32(var + 1e-8f)), -1, 1);  result g' = fl32(g - fl32(mc * alpha)).
+ * grads_out / momentum_out: float32 [n][output_dim], host or device per out_on_device; momentum_out is the RAW average (hand it back as momentum).
+ * stats_out: host float32 [5][output_dim] -- alpha, mean_grads, mean_momentum, var, cov.  *scale_out, *n_trees_out may be NULL.  grads is not written.
+ * A model without trees (and start_tree == n_trees without momentum): grads copied, momentum and statistics zero, scale as computed (0 without trees),
+ * no walk.  The data set form takes rows / rows_on_device / n_rows as gbrl_hip_predict_continue_prepared does (duplicates allowed).
+ * Refused before anything is enqueued, GBRL_HIP_E_INVALID unless noted: a NULL argument, n < 2, beta outside (0, 1) or NaN, start_tree outside
+ * [0, n_trees]; GBRL_HIP_E_UNSUPPORTED: output_dim > 128, a model with categorical columns, with a communicator or collective hooks; on a data set what
+ * gbrl_hip_predict_continue_prepared refuses.  A non-finite alpha fails the call with GBRL_HIP_E_INVALID.  GBRL_HIP_CV_GENERIC=1 selects the
+ * one-thread-per-row walk (same bytes).  gbrl_hip_control_variates_host: the same bytes from the host copy of the model, no device.
+ * gbrl_hip_control_variates_geometry(n_rows, width, codes, output_dim, ...): the launch plan, no device -- width is the feature count of float rows or
+ * (codes != 0) the data set's 16-column groups; streaming 1: the lane-per-row walk on an LDS tile of lds_bytes, 0: one thread per row; the template
+ * width; the trees walked to leaf indices together and the value rows gathered together; the slots of the walk and of the moments pass; the launches
+ * of a call that walks (walk, fold, moments, apply).  Any pointer may be NULL. */
+int gbrl_hip_control_variates(gbrl_hip_model *m, const float *obs, int obs_on_device, int n_samples, int n_num_features, const float *grads, int grads_on_device,
+                              const float *beta /*may be NULL*/, const float *momentum /*may be NULL*/, int momentum_on_device, int start_tree, float *grads_out,
+                              float *momentum_out, int out_on_device, float *stats_out /*host [5][output_dim]*/, float *scale_out, int *n_trees_out);
+int gbrl_hip_control_variates_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows,
+                                       const float *grads, int grads_on_device, const float *beta /*may be NULL*/, const float *momentum /*may be NULL*/,
+                                       int momentum_on_device, int start_tree, float *grads_out, float *momentum_out, int out_on_device,
+                                       float *stats_out /*host [5][output_dim]*/, float *scale_out, int *n_trees_out);
+int gbrl_hip_control_variates_host(const gbrl_hip_model *m, const float *obs, int n_samples, int n_num_features, const float *grads, const float *beta /*may be NULL*/,
+                                   const float *momentum /*may be NULL*/, int start_tree, float *grads_out, float *momentum_out, float *stats_out, float *scale_out,
+                                   int *n_trees_out);
+void gbrl_hip_control_variates_geometry(int64_t n_rows, int width, int codes, int output_dim, int *streaming, int *dmax, int *walk_trees, int *value_trees,
+                                        int *walk_slots, int *moment_slots, int *launches, uint64_t *lds_bytes);
 int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
                           float *loss_out);
 
