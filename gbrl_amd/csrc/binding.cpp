@@ -1597,6 +1597,123 @@ py::array_t<double> path_expected_host_impl(PyGBRL &model, py::object n_trees_ob
     return out;
 }
 
+// ---- SHAP interaction values (include/gbrl_hip.h, "SHAP interaction values on a data set")
+struct ShapxShape { py::array_t<int32_t> features; py::array_t<double> expected; py::ssize_t K; };
+ShapxShape shapx_describe(PyGBRL &model, int n_trees) {
+    const gbrl_hip_metadata md = model.meta();
+    std::vector<int32_t> f(static_cast<size_t>(std::max(md.n_num_features, 1)));
+    ShapxShape s{py::array_t<int32_t>(0), py::array_t<double>(static_cast<py::ssize_t>(md.output_dim)), 0};
+    int k = 0;
+    check(gbrl_hip_shap_interactions_describe(model.h, n_trees, f.data(), &k, s.expected.mutable_data()));
+    s.K = k;
+    s.features = py::array_t<int32_t>(static_cast<py::ssize_t>(k), f.data());
+    return s;
+}
+
+// shap_interactions_prepared(ds, rows=None, n_trees=None) -> {'values': float32 [m, K, K, D] (NumPy for a "cpu" model, a DLPack capsule for a "cuda"
+// one), 'features': int32 [K], 'expected': float64 [D]}
+py::dict shap_interactions_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &rows, py::object n_trees_obj) {
+    const std::string fn = "shap_interactions_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const int n_trees = read_n_trees(n_trees_obj);
+    if (ds_obj.is_none()) {   // the library's own refusal: what it refuses about the model comes before the missing data set
+        check(gbrl_hip_shap_interactions_prepared(self.h, nullptr, nullptr, 0, 0, n_trees, nullptr, 0, nullptr));
+        fail(fn + ": null data set");
+    }
+    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
+    Input none;
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
+    const ShapxShape s = shapx_describe(self, n_trees);
+    const int64_t m = std::max(r.m, 0), K = s.K, D = md.output_dim;
+    // the engine refuses the same (C callers); here too because a "cuda" model allocates its result on the device before the C call
+    if (static_cast<unsigned long long>(m) * static_cast<unsigned long long>(K) * static_cast<unsigned long long>(K) * static_cast<unsigned long long>(D) >= (1ull << 31))
+        fail(fn + ": the matrix of " + std::to_string(m) + " rows x " + std::to_string(K) + " x " + std::to_string(K) + " features x " + std::to_string(D) +
+             " outputs has 2^31 elements or more: pass rows= to explain fewer rows, or use shap_interaction_importance_prepared");
+    Result<float> out(self, std::max<size_t>(static_cast<size_t>(m * K * K * D), 1));
+    int block_rows = 0;
+    {
+        py::gil_scoped_release release;
+        check(gbrl_hip_shap_interactions_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, n_trees, out.get(), out.on_device(), &block_rows));
+    }
+    py::dict d;
+    d["block_rows"] = py::int_(block_rows);
+    d["values"] = out.release({m, K, K, D});
+    d["features"] = s.features;
+    d["expected"] = s.expected;
+    return d;
+}
+
+// shap_interaction_importance_prepared(ds, rows=None, n_trees=None, chunk_rows=None) -> dict
+py::dict shap_interaction_importance_prepared_impl(PyGBRL &self, py::object ds_obj, py::object &rows, py::object n_trees_obj, py::object chunk_rows_obj) {
+    const std::string fn = "shap_interaction_importance_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const int n_trees = read_n_trees(n_trees_obj);
+    if (ds_obj.is_none()) {   // (as shap_interactions_prepared)
+        check(gbrl_hip_shap_interaction_importance_prepared(self.h, nullptr, nullptr, 0, 0, n_trees, 0, nullptr, nullptr, nullptr, nullptr));
+        fail(fn + ": null data set");
+    }
+    const PyDataset &pds = ds_obj.cast<const PyDataset &>();
+    int chunk_rows = 0;
+    if (!chunk_rows_obj.is_none()) {
+        const long long c = chunk_rows_obj.cast<long long>();
+        if (c <= 0 || c > INT32_MAX || c % 64 != 0) fail(fn + ": chunk_rows " + std::to_string(c) + " is not a positive multiple of 64 (None: the default)");
+        chunk_rows = static_cast<int>(c);
+    }
+    Input none;
+    const RowsArg r = read_rows_arg(rows, fn, ds_obj, none);
+    const ShapxShape s = shapx_describe(self, n_trees);
+    const py::ssize_t K = s.K, D = md.output_dim;
+    py::array_t<double> sum({K, K, D}), sum_abs({K, K, D}), mean({K, K, D}), mean_abs({K, K, D});
+    int used = 0, block_rows = 0;
+    {
+        double *sp = sum.mutable_data(), *ap = sum_abs.mutable_data();
+        py::gil_scoped_release release;
+        check(gbrl_hip_shap_interaction_importance_prepared(self.h, pds.h, r.ptr, r.on_device, r.m, n_trees, chunk_rows, sp, ap, &used, &block_rows));
+    }
+    for (py::ssize_t i = 0; i < K * K * D; ++i) {
+        mean.mutable_data()[i] = sum.data()[i] / static_cast<double>(r.m);
+        mean_abs.mutable_data()[i] = sum_abs.data()[i] / static_cast<double>(r.m);
+    }
+    py::dict out;
+    out["sum"] = sum;
+    out["sum_abs"] = sum_abs;
+    out["mean"] = mean;
+    out["mean_abs"] = mean_abs;
+    out["features"] = s.features;
+    out["expected"] = s.expected;
+    out["n_rows"] = py::int_(r.m);
+    out["chunk_rows"] = py::int_(used);
+    out["block_rows"] = py::int_(block_rows);
+    return out;
+}
+
+// shap_interactions_host(model, X, n_trees=None) -> the same dict from the host copy of the model: shapx_core.h's rule, no device
+py::dict shap_interactions_host_impl(PyGBRL &model, py::array_t<float, py::array::c_style | py::array::forcecast> X, py::object n_trees_obj) {
+    const gbrl_hip_metadata md = model.meta();
+    const int n_trees = read_n_trees(n_trees_obj);
+    const ShapxShape s = shapx_describe(model, n_trees);
+    const py::ssize_t F = md.n_num_features, D = md.output_dim;
+    if (X.ndim() != 2 || X.shape(1) != F) fail("shap_interactions_host: X must be float32 [n, " + std::to_string(F) + "], the model's numeric features");
+    if (X.shape(0) > INT32_MAX) fail("shap_interactions_host: too many rows");
+    py::array_t<float> out({X.shape(0), s.K, s.K, D});
+    check(gbrl_hip_shap_interactions_host(model.h, X.data(), static_cast<int>(X.shape(0)), n_trees, out.mutable_data()));
+    py::dict d;
+    d["values"] = out;
+    d["features"] = s.features;
+    d["expected"] = s.expected;
+    return d;
+}
+
+py::dict shap_interactions_geometry_impl(int K, int tree_features, int path_features, int F, int D, uint64_t table_doubles) {
+    int rows = 0;
+    uint64_t lds = 0;
+    gbrl_hip_shapx_geometry(K, tree_features, path_features, F, D, table_doubles, &rows, &lds);
+    py::dict out;
+    out["block_rows"] = rows;
+    out["lds_bytes"] = py::int_(lds);
+    return out;
+}
+
 py::dict path_geometry_impl(int n_used, int F, int D) {
     int slots = 0, passes = 0;
     uint64_t lds = 0;
@@ -1763,6 +1880,17 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     m.def("path_expected_host", &path_expected_host_impl, py::arg("model"), py::arg("n_trees") = py::none(),
           "path_expected_host(model, n_trees=None) -> float64 [D]: bias + the expected values of the trees [0, n_trees); a row's contributions summed over\n"
           "the features, plus this, are its prediction up to float32 rounding");
+    m.def("shap_interactions_host", &shap_interactions_host_impl, py::arg("model"), py::arg("X"), py::arg("n_trees") = py::none(),
+          "shap_interactions_host(model, X, n_trees=None) -> {'values': float32 [n, K, K, D], 'features': int32 [K], 'expected': float64 [D]}\n\n"
+          "Exact SHAP interaction values of the trees [0, n_trees) on float observations X [n, F], from the host copy of the model (no device is needed): the\n"
+          "value explained is ensemble_shap's (raw leaf values), the background the model's own cover.  features: the ascending features those trees test, which\n"
+          "index the matrix.  values[r].sum((0, 1)) + expected is the raw sum of the leaf values row r reaches; values[r].sum(1) is its SHAP value.  The bytes\n"
+          "GBRL.shap_interactions_prepared produces from a data set of X.");
+    m.def("shap_interactions_geometry", &shap_interactions_geometry_impl, py::arg("K"), py::arg("tree_features"), py::arg("path_features"), py::arg("F"), py::arg("D"),
+          py::arg("table_doubles") = 1,
+          "shap_interactions_geometry(K, tree_features, path_features, F, D, table_doubles=1) -> {'block_rows', 'lds_bytes'}: the streaming kernel's plan for K used\n"
+          "features of F columns, at most tree_features distinct features in a tree and path_features on a path, D outputs: the rows a block owns and its dynamic\n"
+          "LDS; block_rows == 0: the one-thread-per-row kernel takes the shape");
     m.def("path_geometry", &path_geometry_impl, py::arg("n_used"), py::arg("F"), py::arg("D"),
           "path_geometry(n_used, F, D) -> {'slots', 'passes', 'lds_bytes'}: the streaming kernel's plan for n_used tested features of F columns and D outputs --\n"
           "the features a pass keeps in LDS beside the code tile, the walks of the trees a tile needs, the dynamic LDS of a block; slots == 0: the\n"
@@ -2409,6 +2537,22 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "sums / m; 'expected': float64 [D]; 'n_rows' = m; 'passes': the feature passes of the streaming kernel (0: the one-thread-per-row kernel ran).  The\n"
           "matrix is never held: a tile's contributions live in LDS until they are reduced.  The sums follow gbrl_cpp.shap_sums_host's rule on that matrix byte\n"
           "for byte.  Refusals as path_contrib_prepared's, without the 2^31 limit.");
+    g.def("shap_interactions_prepared", &shap_interactions_prepared_impl, py::arg("ds"), py::arg("rows") = py::none(), py::arg("n_trees") = py::none(),
+          "shap_interactions_prepared(ds, rows=None, n_trees=None) -> {'values', 'features', 'expected'}\n\n"
+          "Exact SHAP interaction values (XGBoost's pred_interactions) of the trees [0, n_trees) (None: all) for the rows of a prepared data set (rows: int32\n"
+          "indices, duplicates allowed; None: every row), from its bin codes on the device.  'features': int32 [K], the ascending features those trees test;\n"
+          "'values': float32 [m, K, K, D] indexed by them, NumPy for a \"cpu\" model, a DLPack capsule for a \"cuda\" one; 'expected': float64 [D].  Byte for\n"
+          "byte gbrl_cpp.shap_interactions_host(model, X) on the observations the codes were made from.  m * K * K * D < 2^31.  'block_rows': the rows a\n"
+          "block of the streaming kernel owned; 0: the one-thread-per-row kernel ran (a path of more than 8 features, K * K * D float64 beyond the LDS, a weight\n"
+          "table over 256 MiB -- about 390 oblivious trees of depth 6 --, GBRL_HIP_SHAPX_GENERIC=1): the same bytes, slower.");
+    g.def("shap_interaction_importance_prepared", &shap_interaction_importance_prepared_impl, py::arg("ds"), py::arg("rows") = py::none(),
+          py::arg("n_trees") = py::none(), py::arg("chunk_rows") = py::none(),
+          "shap_interaction_importance_prepared(ds, rows=None, n_trees=None, chunk_rows=None) -> dict\n\n"
+          "'sum', 'sum_abs', 'mean', 'mean_abs': float64 [K, K, D], the sums over the m rows of shap_interactions_prepared's matrix and of its absolute values,\n"
+          "and those sums / m; 'features', 'expected', 'n_rows' = m, 'chunk_rows', 'block_rows' (as shap_interactions_prepared's).  The matrix is never held whole: chunk_rows rows at a time (a positive\n"
+          "multiple of 64; None: the largest whose float32 scratch stays within 64 MiB) are evaluated and reduced on the device.  The sums follow\n"
+          "gbrl_cpp.shap_sums_host's rule on the flattened [m, K * K * D] matrix byte for byte, whatever chunk_rows is.  Refusals as\n"
+          "shap_interactions_prepared's, without the 2^31 limit.");
     g.def("plot_tree", [](PyGBRL &self, int tree_idx, const std::string &filename) {
         check(gbrl_hip_plot_tree(self.h, tree_idx, filename.c_str()));
     }, py::arg("tree_idx") = -1, py::arg("filename"));

@@ -1064,6 +1064,52 @@ void gbrl_hip_path_geometry(int n_used, int n_features, int output_dim, int *slo
     if (lds_bytes) *lds_bytes = p.lds;
 }
 
+// ---- SHAP interaction values on a data set: the matrix, its sums over the rows, the rule on the host (engine_shapx.hip; shapx_core.h has the rule)
+int gbrl_hip_shap_interactions_describe(gbrl_hip_model *m, int n_trees, int32_t *features, int *k, double *expected) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        const gbrl::kern::ShapxRecords &rec = m->engine.shapx_records(n_trees);
+        if (features) std::copy(rec.features.begin(), rec.features.end(), features);
+        if (k) *k = static_cast<int>(rec.features.size());
+        if (expected) std::copy(rec.expected.begin(), rec.expected.end(), expected);
+    });
+}
+
+int gbrl_hip_shap_interactions_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int n_trees, float *out,
+                                        int out_on_device, int *block_rows_used) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("shap_interactions_prepared");
+        m->engine.shapx_records(n_trees);   // what is refused about the model and the range comes before the data set is looked at
+        m->engine.shap_interactions_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, n_trees, out, out_on_device != 0, block_rows_used);
+    });
+}
+
+int gbrl_hip_shap_interaction_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, int n_trees,
+                                                  int chunk_rows, double *sum_out, double *abs_out, int *chunk_rows_used, int *block_rows_used) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("shap_interaction_importance_prepared");
+        m->engine.shapx_records(n_trees);   // (as above)
+        m->engine.shap_interaction_importance_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, n_trees, chunk_rows, sum_out, abs_out, chunk_rows_used, block_rows_used);
+    });
+}
+
+int gbrl_hip_shap_interactions_host(gbrl_hip_model *m, const float *obs, int n_rows, int n_trees, float *out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        if (n_rows < 0) throw gbrl::InvalidArgument("shap_interactions_host: a negative row count");
+        const gbrl::kern::ShapxRecords &rec = m->engine.shapx_records(n_trees);
+        gbrl::shap_interactions_host(m->engine.model, rec, n_trees == -1 ? m->engine.model.meta.n_trees : n_trees, obs, n_rows, out);
+    });
+}
+
+void gbrl_hip_shapx_geometry(int k, int tree_features, int path_features, int n_features, int output_dim, uint64_t table_doubles, int *block_rows, uint64_t *lds_bytes) {
+    const gbrl::kern::ShapxPlan p = gbrl::kern::shapx_plan(k, tree_features, path_features, (std::max(n_features, 1) + 15) / 16, output_dim, table_doubles);
+    if (block_rows) *block_rows = p.rows;
+    if (lds_bytes) *lds_bytes = p.lds;
+}
+
 static_assert(GBRL_HIP_IMPORTANCE_SPLIT == gbrl::kFeatureSplit && GBRL_HIP_IMPORTANCE_COVER == gbrl::kFeatureCover, "the importance kinds are the header's");
 int gbrl_hip_feature_importance(const gbrl_hip_model *m, int kind, const int64_t *leaf_counts, double *out) {
     return guarded([&] {

@@ -19,6 +19,7 @@
 #include "cat_candidates_host.h"   // HipError, Unsupported; detail::CatCandidate, CatMemory
 #include "mirror_records.h"        // detail::GreedyNodes, RateTable, CatDict: the host half of the device mirror
 #include "path_core.h"             // kern::PathTable: the host half of path attribution
+#include "shapx_core.h"            // kern::ShapxRecords: the host half of the SHAP interaction values
 
 namespace gbrl {
 
@@ -545,6 +546,21 @@ class Engine {
     void path_importance_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int n_trees, double *sum_out, double *abs_out,
                                   double *expected_out, int *passes_out);
 
+    // SHAP interaction values on a data set (include/gbrl_hip.h, "SHAP interaction values on a data set"; shapx_core.h has the rule): the matrix of the
+    // trees [0, n_trees) (-1: all) for the m rows of the row list, indexed by the K features those trees test (shap_interactions_describe_host).  out:
+    // float32 [m][K][K][D], host or device, overwritten -- byte for byte shap_interactions_host on the observations the codes were made from.  Refused
+    // before the device is touched: check_shapx_prepared's list, and for the matrix m * K * K * D >= 2^31.
+    // *block_rows_out (nullable): the rows a block of the streaming kernel owned, 0 when the one-thread-per-row kernel ran.
+    void shap_interactions_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int n_trees, float *out, bool out_dev, int *block_rows_out);
+    // the records of the trees [0, n_trees) (-1: all): the features that index the matrix, the expected value.  Host only; kept until the model or the
+    // range changes, so that a caller that asks for the shape first and the values next builds them once.  Throws what shapx_model_error refuses and a
+    // matrix row of 2^31 elements or more.
+    const kern::ShapxRecords &shapx_records(int n_trees);
+    // sum_out / abs_out: host float64 [K][K][D], that matrix reduced over the rows by shap_core.h's rule, chunk_rows rows at a time (0: the largest
+    // multiple of 64 whose float32 scratch stays within 64 MiB); the bytes do not depend on it.  *chunk_rows_used (nullable): the chunk size worked with.
+    void shap_interaction_importance_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int n_trees, int chunk_rows,
+                                              double *sum_out, double *abs_out, int *chunk_rows_used, int *block_rows_out);
+
     void set_collective(const gbrl_hip_collective *hooks);
     // Native exchange: an RCCL communicator of this engine's own, collectives enqueued on its stream (no host sync).
     // id128 = gbrl_hip_rccl_unique_id() of rank 0, distributed by the caller.  Collective call (all ranks).
@@ -868,6 +884,21 @@ class Engine {
     int check_path_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int n_trees);
     PathRun stage_path_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int stop);
     void launch_path_matrix(const PreparedDataset *ds, const PathRun &r, int p0, int count, int stop, bool generic, float *out);
+
+    // ---- SHAP interaction values (engine_shapx.hip): the device copies of a call's records (ShapxRecords is kept per model version and tree range, shapx_records; uploaded per call: it depends on the tree
+    // range), the streaming kernel's weight table, the general kernel's float64 scratch, the host-bound matrix or the importance call's chunk
+    // (released when the call ends, as the table and the scratch are), the tile partials (released), the sums
+    DevBuf d_shapx_leaf_, d_shapx_mslot_, d_shapx_mz_, d_shapx_cond_e_, d_shapx_ent_, d_shapx_ent_first_, d_shapx_tree_, d_shapx_tmap_, d_shapx_wtab_, d_shapx_table_;
+    DevBuf d_shapx_scratch_, d_shapx_out_, d_shapx_part_, d_shapx_sums_;
+    kern::ShapxRecords shapx_rec_;
+    uint64_t shapx_rec_version_ = ~0ull;
+    int shapx_rec_stop_ = -1;
+    struct ShapxRun { kern::PredictModel pm; kern::CodeTables ct; kern::ShapxTables st; const int32_t *rows; bool stream; int block_rows; };
+    // what both calls refuse, in order: check_prepared_dataset's list (categorical columns and a row-sharded model among it), a model without trees,
+    // n_trees outside it, check_row_count / check_host_rows, a tree the thresholds cannot express (check_code_range).  Returns the tree count.
+    int check_shapx_prepared(const char *what, const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int n_trees);
+    ShapxRun stage_shapx_prepared(const PreparedDataset *ds, const kern::ShapxRecords &rec, const int32_t *rows, bool rows_dev, int m);
+    bool launch_shapx_matrix(const PreparedDataset *ds, const ShapxRun &r, int p0, int count, int stop, float *out);   // true: the streaming kernel ran
 
     // ---- per-step workspace (grow-only, reused across steps) ----
     DevBuf d_obs_, d_grads_, d_qg_, d_stat_, d_partials_f64_, d_meanden_, d_maxbits_;

@@ -12,6 +12,7 @@
 //   * print_tree writes all 128 bytes of a categorical value, NULs included (node.cpp:531-534).
 #include "explain.h"
 #include "path_core.h"
+#include "shapx_core.h"
 
 // the SHAP sums below spell out every rounding (see Walker::edge_term): keep the compiler from fusing anything else
 #pragma clang fp contract(off)
@@ -589,6 +590,26 @@ void path_expected_host(const Model &m, int n_trees, double *out) {
     const int stop = check_path_host(m, table, n_trees);
     if (out == nullptr) throw std::runtime_error("path_contrib_host: no place for the result");
     table.expected(m, stop, out);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// SHAP interaction values on the host (shapx_core.h has the rule): the bytes the kernels of shap_interactions.hip must produce
+// ------------------------------------------------------------------------------------------------------------------
+void shap_interactions_host(const Model &m, const kern::ShapxRecords &rec, int stop, const float *obs, int n, float *out) {
+    if (n > 0 && (obs == nullptr || out == nullptr)) throw std::runtime_error("shap_interactions_host: the observations and a place for the result are needed");
+    const std::vector<double> wtab = kern::shapx_w_table();
+    const int K = static_cast<int>(rec.features.size()), D = m.meta.output_dim;
+    const kern::ShapxView v{m.tree_indices.data(), m.depths.data(), m.feature_indices.data(), m.inequality_directions.data(), m.values.data(), rec.leaf.data(),
+                            rec.mslot.data(), rec.mz.data(), rec.cond_e.data(), rec.tree.data(), rec.tmap.data(), wtab.data(), m.meta.n_leaves, m.meta.n_trees,
+                            m.meta.max_depth, D, K, m.oblivious() ? 1 : 0};
+    const size_t KKD = static_cast<size_t>(K) * K * D, F = m.meta.n_num_features;
+    std::vector<double> phi(std::max<size_t>(KKD, 1)), T(std::max<size_t>(static_cast<size_t>(rec.nt_max) * rec.nt_max * D, 1)),
+        w(std::max<size_t>(kern::shapx_weights_len(rec.n_max), 1));
+    for (int r = 0; r < n; ++r) {
+        const float *x = obs + static_cast<size_t>(r) * F;
+        kern::shapx_row(v, stop, [&](int c, int f) { return x[f] > m.feature_values[c]; }, phi.data(), T.data(), w.data());
+        for (size_t i = 0; i < KKD; ++i) out[static_cast<size_t>(r) * KKD + i] = static_cast<float>(phi[i]);
+    }
 }
 
 std::string metadata_text(const Model &m, const char *device_name) {

@@ -11,6 +11,8 @@
 
 namespace gbrl {
 
+namespace kern { struct ShapxRecords; }   // shapx_core.h
+
 // One ensemble member as an explicit binary tree, nodes numbered depth-first (left before right), with everything Linear TreeSHAP
 // needs per node (alloc_shap_data shap.cpp:38-168).  Built on the host; evaluated on the host (explain.cpp) or by k_shap (shap.hip).
 struct ShapNode {
@@ -72,6 +74,11 @@ void feature_importance(const Model &m, int kind, const int64_t *leaf_counts, do
 // without trees or with categorical columns, n_trees outside [1, n_trees], a tree that is no proper binary tree with a split.
 void path_contrib_host(const Model &m, const float *obs, int n, int n_trees, float *out);
 void path_expected_host(const Model &m, int n_trees, double *out);
+
+// Extension: exact SHAP interaction values of the trees [0, stop) on float observations, from the host copy of the model (shapx_core.h has the rule;
+// the kernels of shap_interactions.hip produce these bytes from a data set's bin codes).  rec: the records of that range (Engine::shapx_records), K
+// features.  obs [n][n_num_features]; out float32 [n][K][K][D], overwritten.
+void shap_interactions_host(const Model &m, const kern::ShapxRecords &rec, int stop, const float *obs, int n, float *out);
 
 // stdout text of GBRL::print_ensemble_metadata (gbrl.cpp:1254-1267)
 std::string metadata_text(const Model &m, const char *device_name);

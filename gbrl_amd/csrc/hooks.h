@@ -62,6 +62,7 @@ namespace hooks {
     X(RADIX_PLAIN_LOADS) \
     X(REFIT_GENERIC) \
     X(ROOT_COUNTS) \
+    X(SHAPX_GENERIC) \
     X(SHAP_DEVICE_ONLY) \
     X(SHAP_HOST) \
     X(SMALL_GROW_BLOCKS) \

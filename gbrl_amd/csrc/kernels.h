@@ -726,6 +726,26 @@ bool path_rows_stream(const PredictModel &pm, const CodeTables &ct, const PathTa
                       int tile0, hipStream_t s);
 void path_rows_general(const PredictModel &pm, const CodeTables &ct, const float *delta, const CodeRows &cr, int F, int m, int n_trees, float *phi, hipStream_t s);
 //
+// SHAP interaction values of a data set's rows (shap_interactions.hip; shapx_core.h has the rule, the records and the launch plans).  ShapxTables
+// (device): the records of ShapxRecords, the W table, and `table`, the streaming kernel's weights [leaf.tab + pattern * len(n) + item] (float64,
+// written by shapx_build_table, which both forms of the streaming call need first).  The m rows of cr are walked through the trees [0, n_trees).
+//   shapx_build_table   one block per leaf of [0, n_leaves), one thread per pattern: shapx_leaf_weights once per leaf and distinct pattern
+//   shapx_rows_stream   out (device float32 [m][K][K][D]) is overwritten.  false: not taken -- shapx_plan declines (K or depth too large for the tile,
+//                       no table), an oblivious model without packed conditions, a refused LDS opt-in -- and nothing was launched.
+//   shapx_rows_general  one thread per row, scratch (device float64 [m][shapx_general_row_doubles]) is the caller's; the same bytes
+//                       (GBRL_HIP_SHAPX_GENERIC=1).  Always launches (m > 0).
+struct ShapxLeafRec;
+struct ShapxTreeRec;
+struct ShapxTables {
+    const ShapxLeafRec *leaf; const int32_t *mslot; const double *mz; const uint8_t *cond_e; const uint16_t *ent; const int32_t *ent_first;
+    const ShapxTreeRec *tree; const int32_t *tmap; const double *wtab; double *table;
+    int K, nt_max, n_max, n_leaves; size_t table_doubles;
+};
+void shapx_build_table(const ShapxTables &st, hipStream_t s);
+bool shapx_rows_stream(const PredictModel &pm, const CodeTables &ct, const ShapxTables &st, const CodeRows &cr, int m, int n_trees, float *out, hipStream_t s);
+void shapx_rows_general(const PredictModel &pm, const CodeTables &ct, const ShapxTables &st, const CodeRows &cr, int m, int n_trees, double *scratch, float *out,
+                        hipStream_t s);
+//
 // The objectives on a prediction matrix (objective.hip): the device functions of the tails applied to pred [n][D] (device).  targets: float32
 // [n][D] (rmse, logistic) or int32 [n] (softmax; every label in [0, D): the caller checks, label_counts below).  grad_out (device [n][D]) and
 // loss_part (staged_loss_partials(n) doubles, one per 64 rows, finished by staged_loss_finish) may each be null.  D <= 128.

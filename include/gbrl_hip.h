@@ -956,7 +956,7 @@ void gbrl_hip_partial_dependence_geometry(int n_rows, int output_dim, int *rows_
  *   gbrl_hip_shap_sums_host(phi, n_rows, n_cols, sum_out, abs_out)  the reduction rule with no device: phi host float32 [n_rows][n_cols], both results
  *     float64 [n_cols].
  *   gbrl_hip_shap_geometry(n_features, output_dim, ...)  rows per tile (64), the default chunk_rows at that shape, the scratch budget in bytes (64 MiB).
- *   Out of scope: categorical columns, interaction values, weighted means, a tree range other than all trees or one tree. */
+ *   Out of scope: categorical columns, weighted means, a tree range other than all trees or one tree. */
 int gbrl_hip_shap_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows, int tree_idx /*-1: all*/,
                            const float *norm_values, const float *base_poly, const float *offset, float *out /*[n_rows][n_features][output_dim]*/, int out_on_device);
 int gbrl_hip_shap_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows,
@@ -990,7 +990,7 @@ void gbrl_hip_shap_geometry(int n_features, int output_dim, int *tile_rows, int 
  *     host copy of the model; gbrl_hip_path_expected_host(m, n_trees, out) its expected value, float64 [output_dim].
  *   gbrl_hip_path_geometry(n_used, n_features, output_dim, ...)  the streaming kernel's plan for n_used tested features: the slots (features) a pass keeps
  *     in LDS, the passes (walks of the trees over a staged tile), the dynamic LDS bytes of a block; slots == 0: the shape takes the one-thread-per-row kernel.
- *   Out of scope: categorical columns, interaction values, weighted means, a tree range other than a prefix, output_dim > 128. */
+ *   Out of scope: categorical columns, weighted means, a tree range other than a prefix, output_dim > 128. */
 int gbrl_hip_path_contrib_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows, int n_trees /*-1: all*/,
                                    float *out /*[n_rows][n_features][output_dim]*/, int out_on_device);
 int gbrl_hip_path_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows, int n_trees /*-1: all*/,
@@ -1000,6 +1000,49 @@ int gbrl_hip_path_contrib_host(const gbrl_hip_model *m, const float *obs /*host 
                                float *out /*host [n_rows][n_num_features][output_dim]*/);
 int gbrl_hip_path_expected_host(const gbrl_hip_model *m, int n_trees /*-1: all*/, double *out /*host [output_dim]*/);
 void gbrl_hip_path_geometry(int n_used, int n_features, int output_dim, int *slots, int *passes, uint64_t *lds_bytes);
+/* SHAP interaction values on a data set (new: XGBoost's pred_interactions, shap's shap_interaction_values, on a Dataset).  csrc/shapx_core.h has the
+ * rule with every operation's order, csrc/shap_interactions.hip the kernels.
+ *   the rule   The value explained is gbrl_hip_ensemble_shap's: raw leaf values, no learning rate, sign or bias; "feature absent" at a node follows both
+ *              children weighted by the stored edge weights.  Leaf by leaf: the conditions of the leaf's path are merged by feature into U (n of them), z_e
+ *              is the product of the path's edge weights at e's conditions, o_e is 1 when the row satisfies all of them.  With W(k, n) = k! (n-k-1)! / n! and
+ *              c_k(P) the sum over S in U \ P, |S| = k, of prod_{e in S} o_e * prod_{e in U \ P \ S} z_e, the leaf adds to its tree's matrix
+ *              Phi[i][j][d] += 1/2 v[d] (o_i - z_i)(o_j - z_j) sum_k W(k, n-1) c_k({i, j}) for i != j and phi[i][d] += v[d] (o_i - z_i) sum_k W(k, n) c_k({i});
+ *              after the tree's last leaf Phi[i][i][d] = phi[i][d] - sum_{j != i} Phi[i][j][d].  Float64 throughout, leaves ascending within a tree, trees
+ *              ascending, one rounding to float32 when stored.  A greedy tree of one leaf contributes nothing.  The matrix is symmetric bit for bit and
+ *              sum_{i,j} Phi[r][i][j][d] + expected[d] is the raw sum of the leaf values the row reaches.
+ *   the shape  The answer is indexed by the features the trees [0, n_trees) test: gbrl_hip_shap_interactions_describe writes them ascending (features, room
+ *              for the model's numeric features, may be NULL), their count K, and expected float64 [output_dim] (may be NULL).
+ *   gbrl_hip_shap_interactions_prepared(m, ds, rows, rows_on_device, n_rows, n_trees, out, out_on_device)  on the model's device, from the data set's bin
+ *     codes.  rows as gbrl_hip_shap_prepared's; n_trees in [1, trees of the model], -1: all.  out: host or device float32 [n_rows][K][K][output_dim],
+ *     overwritten: byte for byte gbrl_hip_shap_interactions_host on the observations the codes were made from.
+ *   gbrl_hip_shap_interaction_importance_prepared(..., chunk_rows, sum_out, abs_out, chunk_rows_used)  sum_out / abs_out: host float64 [K][K][output_dim],
+ *     that matrix reduced over the rows by the rule of gbrl_hip_shap_sums_host, chunk_rows rows at a time (0: the largest multiple of 64 whose float32
+ *     scratch stays within 64 MiB); the bytes do not depend on chunk_rows.
+ *   Both are refused before the device is touched, GBRL_HIP_E_INVALID unless noted: what gbrl_hip_predict_continue_prepared refuses about the model, the
+ *     data set and rows (GBRL_HIP_E_UNSUPPORTED: a row-sharded model, a model with categorical columns, a tree the thresholds cannot express); a model
+ *     without trees; n_trees outside [1, n_trees] and not -1; a NULL result; chunk_rows that is no multiple of 64; for the matrix
+ *     n_rows * K * K * output_dim >= 2^31 (GBRL_HIP_E_UNSUPPORTED).  No output_dim limit: a shape the streaming kernel's plan declines takes the
+ *     one-thread-per-row kernel (GBRL_HIP_SHAPX_GENERIC=1 forces it; same bytes).
+ *   *block_rows_used (both calls, may be NULL): the rows a block of the streaming kernel owned; 0: the one-thread-per-row kernel ran -- the plan declined
+ *     the shape (a path of more than 8 features, K * K * output_dim float64 beyond the LDS, a weight table over 256 MiB: about 390 oblivious trees of depth 6),
+ *     the device refused the LDS opt-in, or the hook asked for it.  The records of a (model version, tree range) are built once on the host and kept: the
+ *     describe call and the call that follows it share them.  K * K * output_dim >= 2^31 is refused (GBRL_HIP_E_UNSUPPORTED).
+ *   gbrl_hip_shap_interactions_host(m, obs, n_rows, n_trees, out)  the rule with no device, on host float32 observations [n_rows][n_num_features].
+ *   gbrl_hip_shapx_geometry(k, tree_features, path_features, n_features, output_dim, table_doubles, ...)  the streaming kernel's plan: rows of a block
+ *     (0: the shape takes the one-thread-per-row kernel) and its dynamic LDS bytes, for K used features, at most tree_features distinct features in a
+ *     tree and path_features on a path, and a weight table of table_doubles float64.
+ *   Out of scope: categorical columns, a background data set other than the model's cover, a tree range other than a prefix. */
+int gbrl_hip_shap_interactions_describe(gbrl_hip_model *m, int n_trees /*-1: all*/, int32_t *features /*[n_num_features], may be NULL*/, int *k,
+                                        double *expected /*host [output_dim], may be NULL*/);
+int gbrl_hip_shap_interactions_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows,
+                                        int n_trees /*-1: all*/, float *out /*[n_rows][K][K][output_dim]*/, int out_on_device, int *block_rows_used /*may be NULL*/);
+int gbrl_hip_shap_interaction_importance_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows /*may be NULL*/, int rows_on_device, int n_rows,
+                                                  int n_trees /*-1: all*/, int chunk_rows /*0: the default*/, double *sum_out /*host [K][K][output_dim]*/,
+                                                  double *abs_out /*likewise*/, int *chunk_rows_used /*may be NULL*/, int *block_rows_used /*may be NULL*/);
+int gbrl_hip_shap_interactions_host(gbrl_hip_model *m, const float *obs /*host [n_rows][n_num_features]*/, int n_rows, int n_trees /*-1: all*/,
+                                    float *out /*host [n_rows][K][K][output_dim]*/);
+void gbrl_hip_shapx_geometry(int k, int tree_features, int path_features, int n_features, int output_dim, uint64_t table_doubles, int *block_rows,
+                             uint64_t *lds_bytes);
 int gbrl_hip_sample_rows_host(int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/, int *count);
 int gbrl_hip_dataset_sample_rows(const gbrl_hip_dataset *ds, int row0, int n, double subsample, uint64_t seed, int draw, int32_t *out /*[n]*/,
                                  int out_on_device, int *count);
