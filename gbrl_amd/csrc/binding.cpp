@@ -528,6 +528,65 @@ py::dict control_variates_impl(PyGBRL &self, int where, py::object &obs, py::obj
     return out;
 }
 
+// Extension: tree_gram_prepared(ds, targets=None, start_tree_idx=0, stop_tree_idx=0, rows=None) and gbrl_cpp.tree_gram_host(model, obs, targets, start,
+// stop) -> {'gram': float64 [T, T], 'moment': float64 [T] | None, 'rows': m, 'route': 'stream' | 'general' | 'host'} (include/gbrl_hip.h, "The Gram
+// matrix").  One body: on_host selects the host rule, which takes NumPy arrays only.
+py::dict tree_gram_impl(PyGBRL &self, bool on_host, py::object &obs, py::object ds_obj, py::object &targets, py::object start_obj, py::object stop_obj,
+                        py::object &rows) {
+    const std::string fn = on_host ? "tree_gram_host" : "tree_gram_prepared";
+    const gbrl_hip_metadata md = self.meta();
+    const auto [start, stop] = read_tree_range(start_obj, stop_obj);
+    Input o;
+    RowsArg r{nullptr, 0, 0};
+    int m = 0, n_num = 0;
+    const gbrl_hip_dataset *ds = nullptr;
+    if (on_host) {
+        py::object none = py::none();
+        const Batch b = read_batch(obs, none, fn, md.input_dim);
+        o = b.o;
+        require_host(o, fn + " takes NumPy arrays");
+        m = b.s.n; n_num = b.s.n_num;
+    } else {
+        ds = dataset_handle(ds_obj);
+        r = read_rows_arg(rows, fn, ds_obj, Input{});
+        m = r.m;
+    }
+    Input y = read_input(targets, "targets", true, fn, 0);
+    if (y.ptr != nullptr) check_rows_by_outputs(y, "targets", m, md.output_dim);
+    if (on_host) require_host(y, fn + " takes NumPy arrays");
+    // (the library refuses a bad range itself; the result is shaped by the range it will resolve, and a range beyond the cap gets room for nothing)
+    const int resolved = stop == 0 ? md.n_trees : stop;
+    const py::ssize_t T = (resolved - start >= 0 && resolved - start <= 2048) ? resolved - start : 0;
+    py::array_t<double> gram({T, T});
+    py::array_t<double> moment(std::vector<py::ssize_t>{T});
+    double *gp = gram.mutable_data(), *mp = y.ptr != nullptr ? moment.mutable_data() : nullptr;
+    int route = 0;
+    {
+        py::gil_scoped_release release;
+        if (on_host)
+            check(gbrl_hip_tree_gram_host(self.h, o.f32(), m, n_num, y.f32(), start, stop, gp, mp));
+        else
+            check(gbrl_hip_tree_gram_prepared(self.h, ds, r.ptr, r.on_device, m, y.f32(), y.on_device, start, stop, gp, mp, &route));
+    }
+    py::dict out;
+    out["gram"] = gram;
+    out["moment"] = y.ptr != nullptr ? py::object(moment) : py::object(py::none());
+    out["rows"] = py::int_(m);
+    out["route"] = py::str(on_host ? "host" : route ? "stream" : "general");
+    return out;
+}
+
+// Extension: scale_trees(weights, start_tree_idx=0): the leaf values of tree start + k times float32 weights[k]; host only (include/gbrl_hip.h)
+void scale_trees_impl(PyGBRL &self, py::object &weights, int start) {
+    const std::string fn = "scale_trees";
+    const Input w = require_input(weights, "weights", fn);
+    require_host(w, fn + " takes a NumPy array");
+    size_t n = 1;
+    for (size_t s : w.shape) n *= s;
+    if (w.shape.size() != 1 || n >= (size_t(1) << 31)) fail(fn + ": weights must be a one-dimensional float32 vector, one entry per tree");
+    check(gbrl_hip_scale_trees(self.h, w.f32(), static_cast<int>(n), start));
+}
+
 py::dict control_variates_geometry_impl(int64_t n, int width, bool codes, int D) {
     int streaming = 0, dmax = 0, walk_trees = 0, value_trees = 0, walk_slots = 0, moment_slots = 0, launches = 0;
     uint64_t lds = 0;
@@ -1872,6 +1931,24 @@ PYBIND11_MODULE(gbrl_cpp, m) {
     m.def("control_variates_geometry", &control_variates_geometry_impl, py::arg("n"), py::arg("width"), py::arg("codes") = false, py::arg("D") = 1,
           "control_variates_geometry(n, width, codes=False, D=1) -> {'streaming', 'dmax', 'walk_trees', 'value_trees', 'walk_slots', 'moment_slots', 'launches',\n"
           "'lds_bytes'}: the launch plan of control_variates for n rows of `width` features (codes: of `width` 16-column groups of a data set); no device.");
+    m.def("tree_gram_host", [](PyGBRL &model, py::object &obs, py::object &targets, py::object start, py::object stop) {
+              py::object none = py::none();
+              return tree_gram_impl(model, true, obs, none, targets, start, stop, none);
+          }, py::arg("model"), py::arg("obs"), py::arg("targets") = py::none(), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0,
+          "tree_gram_host(model, obs, targets=None, start_tree_idx=0, stop_tree_idx=0) -> dict\n\n"
+          "GBRL.tree_gram_prepared's result from float32 rows and the host copy of the model, no device: gram_core.h's rule in plain float64 loops,\n"
+          "rows in order.  NumPy arrays only; 'route' is 'host'.");
+    m.def("tree_gram_geometry", [](int64_t n, int T, int D, int n_groups) {
+              int chunk = 0, pairs = 0, row_blocks = 0, streaming = 0;
+              uint64_t scratch = 0, lds = 0;
+              gbrl_hip_tree_gram_geometry(n, T, D, n_groups, &chunk, &pairs, &row_blocks, &scratch, &lds, &streaming);
+              py::dict out;
+              out["chunk"] = chunk; out["pairs"] = pairs; out["row_blocks"] = row_blocks;
+              out["scratch_bytes"] = scratch; out["lds_bytes"] = lds; out["streaming"] = streaming != 0;
+              return out;
+          }, py::arg("n"), py::arg("T"), py::arg("D") = 1, py::arg("n_groups") = 1,
+          "tree_gram_geometry(n, T, D=1, n_groups=1) -> {'chunk', 'pairs', 'row_blocks', 'scratch_bytes', 'lds_bytes', 'streaming'}: the launch plan of\n"
+          "tree_gram_prepared for n rows, T trees and a data set of n_groups 16-column groups; no device.");
     m.def("path_contrib_host", &path_contrib_host_impl, py::arg("model"), py::arg("X"), py::arg("n_trees") = py::none(),
           "path_contrib_host(model, X, n_trees=None) -> float32 [n, F, D]\n\n"
           "Path attribution (Saabas; XGBoost's approx_contribs) of the trees [0, n_trees) on float observations X [n, F], from the host copy of the model (no\n"
@@ -2344,6 +2421,22 @@ PYBIND11_MODULE(gbrl_cpp, m) {
           "alpha and weights as fit_prepared takes them; rows as predict_continue_prepared (targets and weights indexed by position).  Refused: what\n"
           "predict_continue_prepared refuses, a model without trees when stops is None, bad stops, missing or misshapen targets, the ranking objectives,\n"
           "eval_metric='auc' (eval_metric on a stage of predict_staged_prepared gives it), eval_metric with rmse, quantile or weights.");
+    // extension: the Gram matrix of the per-tree outputs over a data set, and the write side of the reweighting loop
+    g.def("tree_gram_prepared", [](PyGBRL &self, py::object ds, py::object &targets, py::object start, py::object stop, py::object &rows) {
+        py::object none = py::none();
+        return tree_gram_impl(self, false, none, ds, targets, start, stop, rows);
+    }, py::arg("ds"), py::arg("targets") = py::none(), py::arg("start_tree_idx") = 0, py::arg("stop_tree_idx") = 0, py::arg("rows") = py::none(),
+          "tree_gram_prepared(ds, targets=None, start_tree_idx=0, stop_tree_idx=0, rows=None) -> dict\n\n"
+          "gram[t, u] = sum over the rows of ds (of rows=, duplicates counted) and the outputs of v_t * v_u, v_t the stored float32 leaf value row tree\n"
+          "start + t routes the row to; moment[t] the same sum of v_t * targets (float32 [m, D], indexed like rows; None: no moment).  Rates and signs\n"
+          "stay with the caller.  Returns {'gram': float64 [T, T], exactly symmetric, 'moment': float64 [T] or None, 'rows': m, 'route': 'stream' (the\n"
+          "row walk feeds the fp64 matrix instructions) or 'general'}, NumPy on the host.  Products are exact in float64, the sums are added in a fixed\n"
+          "order: two calls, the same bytes.  Refused before anything is enqueued: what predict_leaves_prepared refuses, more than 2048 trees,\n"
+          "output_dim > 128, targets of another shape; refused by the kernel's status word: a non-finite leaf value or target.");
+    g.def("scale_trees", &scale_trees_impl, py::arg("weights"), py::arg("start_tree_idx") = 0,
+          "scale_trees(weights, start_tree_idx=0)\n\n"
+          "Every leaf value of tree start_tree_idx + k times float32 weights[k] (one float32 product per value).  Host only; the structure stays, also\n"
+          "for a weight of 0.  Refused with the model unchanged: a NaN or infinite weight, a range outside the model.");
     // extension: the leaf values of a tree range fitted again on new data, the structure kept; returns the loss of the refitted prefix
     g.def("refit_leaves", &refit_leaves_impl, py::arg("obs"), py::arg("categorical_obs"), py::arg("targets"), py::arg("start_tree_idx") = 0,
           py::arg("stop_tree_idx") = 0, py::arg("decay_rate") = 0.0,

@@ -23,6 +23,7 @@
 #include "rank_core.h"
 #include "pd_core.h"
 #include "cv_core.h"
+#include "gram_core.h"
 #include "shap_core.h"
 #include "hooks.h"
 #include "explain.h"
@@ -588,6 +589,42 @@ int gbrl_hip_leaf_counts_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds,
 
 void gbrl_hip_leaves_prepared_geometry(int n_groups, int *group_trees, int *count_chunk, uint64_t *lds_bytes) {
     gbrl::kern::leaves_codes_geometry(n_groups, group_trees, count_chunk, lds_bytes);
+}
+
+int gbrl_hip_tree_gram_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *targets,
+                                int targets_on_device, int start_tree, int stop_tree, double *gram_out, double *moment_out, int *route_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.precheck_prepared("tree_gram_prepared");
+        m->engine.tree_gram_prepared(&live_dataset(ds), rows, rows_on_device != 0, n_rows, targets, targets_on_device != 0, start_tree, stop_tree, gram_out,
+                                     moment_out, route_out);
+    });
+}
+
+int gbrl_hip_tree_gram_host(const gbrl_hip_model *m, const float *obs, int n_samples, int n_num_features, const float *targets, int start_tree, int stop_tree,
+                            double *gram_out, double *moment_out) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.tree_gram_host(obs, n_samples, n_num_features, targets, start_tree, stop_tree, gram_out, moment_out);
+    });
+}
+
+void gbrl_hip_tree_gram_geometry(int64_t n_rows, int n_trees, int output_dim, int n_groups, int *chunk, int *pairs, int *row_blocks, uint64_t *scratch_bytes,
+                                 uint64_t *lds_bytes, int *streaming) {
+    const gbrl::kern::GramPlan p = gbrl::kern::gram_plan(n_rows, n_trees, output_dim, n_groups);
+    if (chunk) *chunk = p.chunk;
+    if (pairs) *pairs = p.pairs;
+    if (row_blocks) *row_blocks = p.row_blocks;
+    if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    if (streaming) *streaming = p.streaming;
+}
+
+int gbrl_hip_scale_trees(gbrl_hip_model *m, const float *weights, int n_weights, int start_tree) {
+    return guarded([&] {
+        if (!m) throw gbrl::InvalidArgument("null model");
+        m->engine.scale_trees(weights, n_weights, start_tree);
+    });
 }
 
 int gbrl_hip_control_variates(gbrl_hip_model *m, const float *obs, int obs_on_device, int n_samples, int n_num_features, const float *grads, int grads_on_device,

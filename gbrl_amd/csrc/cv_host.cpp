@@ -8,9 +8,8 @@
 
 namespace gbrl {
 
-namespace {
 // the global leaf of (row, tree t); greedy: the first leaf in storage order from the tree's first on whose conditions all hold (a depth-0 leaf never
-// passes, so the search walks on into the next tree); -1 when it runs off the ensemble
+// passes, so the search walks on into the next tree); -1 when it runs off the ensemble.  Declared in engine.h: tree_gram_host walks with it too.
 int host_leaf(const Model &m, const float *x, int t) {
     const int md = m.meta.max_depth;
     if (m.oblivious()) {
@@ -30,7 +29,6 @@ int host_leaf(const Model &m, const float *x, int t) {
     }
     return -1;
 }
-}  // namespace
 
 void Engine::control_variates_host(const float *obs, int n, int n_num, const CvArgs &a) const {
     const char *what = "control_variates_host";

@@ -27,6 +27,7 @@ struct NoDeviceError : std::runtime_error { using std::runtime_error::runtime_er
 struct InvalidArgument : std::runtime_error { using std::runtime_error::runtime_error; };
 
 void hip_check(hipError_t e, const char *what);
+int host_leaf(const Model &m, const float *x, int t);   // cv_host.cpp: the reference's walk of tree t on float32 row x (numeric-only), -1: none
 
 // grow-only device buffer
 class DevBuf {
@@ -491,6 +492,19 @@ class Engine {
     // set, the rows and a tree of the range the thresholds cannot express (check_code_range), except the output width.  Nothing is written.
     void predict_leaves_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int start_tree, int stop_tree, int32_t *out, bool out_dev);
     void leaf_counts_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, int start_tree, int stop_tree, int64_t *counts_out);
+    // Extension: the Gram matrix of the per-tree outputs over a data set's rows and their moments against targets (gram_core.h has the rule,
+    // tree_gram.hip the kernels, engine_gram.hip the stages; include/gbrl_hip.h the contract).  rows / range as predict_leaves_prepared; targets
+    // [m][D] float32 indexed by the sample (device iff targets_dev), or null -- moment_out is null exactly then.  gram_out [T][T] and moment_out [T]
+    // are host float64, T = stop - start.  *route_out (nullable): 1 the streaming MFMA kernel, 0 the general one.  Refused before anything is
+    // enqueued: what predict_leaves_prepared refuses, more than 2048 trees, output_dim > 128; after the one wait: a non-finite leaf value or target
+    // (the kernel's status word), nothing written then.
+    void tree_gram_prepared(const PreparedDataset *ds, const int32_t *rows, bool rows_dev, int m, const float *targets, bool targets_dev, int start_tree,
+                            int stop_tree, double *gram_out, double *moment_out, int *route_out);
+    // the rule itself on host float rows, from the host copy of the model; no device
+    void tree_gram_host(const float *obs, int n, int n_num, const float *targets, int start_tree, int stop_tree, double *gram_out, double *moment_out) const;
+    // Extension: every leaf value of tree start_tree + k multiplied by weights[k], one float32 product per value; the structure stays (a weight of 0
+    // too).  Host only; the mirror is invalidated as refit_leaves does.  A non-finite weight or a range outside the model: InvalidArgument, nothing changed.
+    void scale_trees(const float *weights, int n_weights, int start_tree);
     // Extension: refit the leaf values of the trees [start_tree, stop_tree) on a batch, the structure kept (kern::refit_leaves; include/gbrl_hip.h
     // has the contract).  stop_tree == 0: n_trees; then 0 <= start_tree < stop_tree <= n_trees.  decay_rate in [0, 1]: new value = decay * old +
     // (1 - decay) * leaf mean of fit()'s MultiRMSE gradient.  Only model.values of the range changes; *loss_out = staged_loss(..., {stop_tree})
@@ -919,6 +933,7 @@ class Engine {
     template <typename Walk>
     void run_cv(const char *what, int n, const CvArgs &a, float beta, Walk &&walk);
     DevBuf d_cv_grads_, d_cv_mom_in_, d_cv_grads_out_, d_cv_mom_out_, d_cv_ms_, d_cv_part_, d_cv_stats_;   // staged inputs, host-bound results, scratch
+    DevBuf d_gram_y_, d_gram_part_, d_gram_tiles_, d_gram_status_;   // tree_gram_prepared: staged targets, per-block partials, reduced pair tiles, status word
     DevBuf d_pobs_, d_pcat_, d_pout_;
     DevBuf d_leaves_out_, d_leaf_counts_;   // predict_leaves: indices bound for the host; leaf_counts: the uint32 counters
     DevBuf d_refit_counts_, d_refit_weights_;   // refit_leaves_prepared: rows per leaf, staged weights (the rest are refit_leaves' buffers)

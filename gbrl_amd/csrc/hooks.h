@@ -19,6 +19,7 @@ namespace hooks {
     X(EVENT_RESULTS) \
     X(FORCE_BISECTION) \
     X(FORCE_COLLECTIVE) \
+    X(GRAM_GENERIC) \
     X(HIST_ALLREDUCE_MAX_KB) \
     X(HIST_GENERIC) \
     X(HIST_PIPE) \

@@ -869,6 +869,14 @@ void predict_leaves_codes(const PredictModel &pm, const CodeTables &ct, const Co
                           hipStream_t s);
 void leaf_counts_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, const int32_t *tree_first_leaf, int m, int start_tree, int stop_tree,
                        uint32_t *counts, bool generic, hipStream_t s);
+// The Gram matrix of the per-tree outputs over the m samples of a data set and their moments against targets (tree_gram.hip; gram_core.h has the
+// rule and gram_plan, the geometry both kernels and the caller's buffers follow).  targets: device float32 [m][D] indexed by the sample, or null.
+// part: device scratch of plan.scratch_bytes, need not be cleared; tiles: device float64 [plan.per_block] -- the reduced chunk-pair tiles in
+// gram_pair_index's order, then (with targets) the moments [chunks][chunk]: gram_assemble reads it.  status: device int, ZEROED by the caller on
+// `s`; the kernels OR kGramBadValue / kGramBadTarget into it.  Two launches on `s`, no floating-point atomic.  Returns whether the streaming
+// (MFMA) kernel took the call.
+bool tree_gram_codes(const PredictModel &pm, const CodeTables &ct, const CodeRows &cr, int m, int start_tree, int stop_tree, const float *targets,
+                     double *part, double *tiles, int *status, bool generic, hipStream_t s);
 
 // Control variates (control_variates.hip; cv_core.h has the rule): the momentum walk of the trees [start_tree, stop_tree) over n rows, then fold,
 // moments and apply -- four launches on `s`, nothing read back.  All buffers are device memory; grads_out and momentum_out are written, grads and

@@ -1134,6 +1134,36 @@ int gbrl_hip_control_variates_host(const gbrl_hip_model *m, const float *obs, in
                                    int *n_trees_out);
 void gbrl_hip_control_variates_geometry(int64_t n_rows, int width, int codes, int output_dim, int *streaming, int *dmax, int *walk_trees, int *value_trees,
                                         int *walk_slots, int *moment_slots, int *launches, uint64_t *lds_bytes);
+/* The Gram matrix of the per-tree outputs over a data set (new): what post-hoc reweighting of an ensemble needs -- fully-corrective boosting, ridge
+ * or lasso over trees, greedy tree selection, redundancy diagnostics -- without the [n, trees] leaf matrix.  csrc/gram_core.h has the rule,
+ * csrc/tree_gram.hip the kernels.  With v_t(r, :) the stored float32 value row of the leaf tree t routes row r to (zeros where a greedy search runs
+ * off the ensemble; rates and signs stay with the caller), T = stop_tree - start_tree:
+ *     gram[t][u] = sum over rows r, outputs d of v_t(r, d) * v_u(r, d)        moment[t] = sum over rows r, outputs d of v_t(r, d) * targets[r][d]
+ * Products of float32 values are exact in float64; only the additions round: every entry lies within rows * output_dim * 2^-53 * sum |v_t v_u| of
+ * the EXACT sum (two evaluations in different orders -- the two kernels, the host rule -- can therefore differ by twice that at worst; the tests
+ * hold them to (rows * output_dim + 8) * 2^-53 * sum |v_t v_u|).  The partial sums of the blocks are added in block order with no floating-point atomic: two calls, the same bytes; gram is exactly
+ * symmetric (the upper triangle is computed and mirrored).
+ *   gbrl_hip_tree_gram_prepared  rows / rows_on_device / n_rows and the range as gbrl_hip_predict_leaves_prepared takes them.  targets: float32
+ *     [n_rows, output_dim] indexed like rows, host or device, or NULL -- moment_out is NULL exactly then.  gram_out [T, T] and moment_out [T] are
+ *     HOST float64.  *route_out (nullable): 1 the streaming kernel (the row walk feeds v_mfma_f64_16x16x4_f64), 0 the one-thread-per-entry kernel
+ *     (GBRL_HIP_GRAM_GENERIC=1, a data set too wide for the LDS, a model the streaming walk does not take); the two agree within the bound above.
+ *     Refused before the device is touched: what gbrl_hip_predict_leaves_prepared refuses (a communicator -- a row-sharded model -- among it), more
+ *     than 2048 trees in the range and output_dim > 128 (GBRL_HIP_E_UNSUPPORTED), gram_out NULL, targets without moment_out or the reverse.
+ *     Refused after the kernel's status word is read, nothing written: a non-finite leaf value of the range met by a row, a non-finite target.
+ *   gbrl_hip_tree_gram_host      the rule in plain float64 loops, rows in order, on host float32 obs [n_samples, n_num_features] from the host copy
+ *     of a numeric-only model; no device.
+ *   gbrl_hip_tree_gram_geometry  no device: the launch plan, a pure function of its arguments -- trees per chunk (64), chunk pairs a <= b, row
+ *     blocks (each takes every row_blocks-th 64-row tile; the largest count that keeps the scratch [row_blocks][pairs][64][64] + moments under
+ *     64 MiB, at most 512 and at most the tile count), the scratch bytes, the dynamic LDS and whether it fits (streaming).  Any pointer may be NULL.
+ *   gbrl_hip_scale_trees         every leaf value of tree start_tree + k times weights[k] (one float32 product), k < n_weights; host only, the
+ *     structure stays even for a weight of 0.  A NaN or infinite weight, or a range outside the model: GBRL_HIP_E_INVALID, nothing changed. */
+int gbrl_hip_tree_gram_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const int32_t *rows, int rows_on_device, int n_rows, const float *targets,
+                                int targets_on_device, int start_tree, int stop_tree, double *gram_out, double *moment_out, int *route_out);
+int gbrl_hip_tree_gram_host(const gbrl_hip_model *m, const float *obs, int n_samples, int n_num_features, const float *targets, int start_tree, int stop_tree,
+                            double *gram_out, double *moment_out);
+void gbrl_hip_tree_gram_geometry(int64_t n_rows, int n_trees, int output_dim, int n_groups, int *chunk, int *pairs, int *row_blocks, uint64_t *scratch_bytes,
+                                 uint64_t *lds_bytes, int *streaming);
+int gbrl_hip_scale_trees(gbrl_hip_model *m, const float *weights, int n_weights, int start_tree);
 int gbrl_hip_fit_prepared(gbrl_hip_model *m, const gbrl_hip_dataset *ds, const float *targets, int targets_on_device, int iterations,
                           float *loss_out);
 
